@@ -13,11 +13,19 @@ Canny chain on the library's side streams (VQA_OPT_OVERLAP, its default) and two
 batches in flight, each on its own context (--inflight 2: step i+1 is submitted
 before step i is waited for - what a host that streams batches does; measured best
 of {1,2} contexts per batch x {1,2,3} batches in flight, LAB_NOTES.md), per-kernel
-profiling OFF.  Because overlapped kernels share the GPU, their event times say
+profiling OFF.  "ms_per_step" is the wall time of one timed step.
+
+A plain run sets up, warms up, times --steps steps, writes the last timed step's
+records if --dump-outputs DIR is given (DIR/<name>.npy, float64, one file per record
+field: quality_sse, complexity_hist_gray, ...; c1 / c1ref: the row's numeric values)
+and prints the line; the legs below are off ("roofline": null, "kernels": {}).
+--full runs them after the timed region, as follows (an explicit --cpu-sample,
+--e2e-steps, --api-steps, --no-serial-pass or --no-verify still sets its leg).
+Because overlapped kernels share the GPU, their event times say
 nothing about a kernel alone; so after the timed region a SERIAL pass runs the same
 steps on one context with the overlap off and HIP-event profiling on: it fills
 "kernels" / "roofline" and is reported as "ms_per_step_serial" (never `value`).
-Rank 0 prints ONE JSON line (contract in the task statement) with four
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it has four
 extra objects: "roofline" (dominant kernel: algorithmic bytes / HIP-event time
 against the HBM peak, or - for a kernel far below that roof that does counted fp32
 work - flops against the fp32 vector peak, "bound": "valu_fp32"), "end_to_end"
@@ -128,6 +136,67 @@ def stream_chunk(content, rank, h, w, a, n):
 
 
 CHUNK = 32
+
+
+def stream_chunks(content, rank, h, w, n, yuv=False):
+    """Frames 0 .. n-1 of rank's stream, in order, as (a, ref, dist, yref, ydist) per CHUNK frames (yref / ydist: the
+    yuv420p planes, None unless yuv).  Every chunk is stream_chunk's, the same bytes; they are made on a few host threads
+    (NumPy leaves the GIL in the per-frame work), at most as many chunks ahead of the consumer as there are threads."""
+    import collections
+    from concurrent.futures import ThreadPoolExecutor
+
+    def make(a):
+        r, d = stream_chunk(content, rank, h, w, a, min(CHUNK, n - a))
+        if not yuv:
+            return a, r, d, None, None
+        from rtvqa_amd.frames import bgr_to_yuv420p
+        return a, r, d, bgr_to_yuv420p(r), bgr_to_yuv420p(d)
+
+    starts = iter(range(0, n, CHUNK))
+    workers = max(1, min(8, visible_cores(), -(-n // CHUNK)))
+    with ThreadPoolExecutor(max_workers=workers) as ex:
+        ahead = collections.deque(ex.submit(make, a) for _, a in zip(range(workers), starts))
+        while ahead:
+            out = ahead.popleft().result()
+            a = next(starts, None)
+            if a is not None:
+                ahead.append(ex.submit(make, a))
+            yield out
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # (under 64 MB with the .npy headers and the sample's row numbers)
+
+
+def dump_outputs(outdir, outputs):
+    """--dump-outputs: what the timed path returned in its last step, as outdir/<name>.npy in float64.  outputs: name ->
+    structured record array (one file per field: <name>_<field>), dict (<name>_<key>), number or array; strings are skipped.
+    Above DUMP_LIMIT_BYTES in all, a fixed sample of the leading axis (seed 0, the same rows for every array that has that
+    many; the row numbers in sample_rows.npy) is written instead of the whole."""
+    flat = {}
+
+    def add(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                add("%s_%s" % (name, re.sub(r"[^0-9A-Za-z]+", "_", str(k)).strip("_")), x)
+        elif isinstance(v, np.ndarray) and v.dtype.names:
+            for f in v.dtype.names:
+                add("%s_%s" % (name, f), v[f])
+        elif not isinstance(v, (str, bytes)):
+            flat[name] = np.asarray(v, dtype=np.float64)
+
+    for name, v in outputs.items():
+        add(name, v)
+    total = sum(a.nbytes for a in flat.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = max(a.shape[0] for a in flat.values() if a.ndim)
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // (total + 8 * n)))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        flat = {k: (a[rows] if a.ndim and a.shape[0] == n else a) for k, a in flat.items()}
+        flat["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in flat.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return sorted(flat)
 
 
 def verify_frames(B):
@@ -649,9 +718,10 @@ def _c1ref_quality_item(item):
 
 
 def c1_clip(rank, h, w, n):
-    from rtvqa_amd import synth
-    parts = [stream_chunk("natural", rank, h, w, a, min(CHUNK, n - a)) for a in range(0, n, CHUNK)]
-    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    ref, dist = np.empty((n, h, w, 3), np.uint8), np.empty((n, h, w, 3), np.uint8)
+    for a, r, d, _, _ in stream_chunks("natural", rank, h, w, n):
+        ref[a:a + len(r)], dist[a:a + len(d)] = r, d
+    return ref, dist
 
 
 def c1_planar(clip):
@@ -813,6 +883,8 @@ def main_c1(args, rank, local_rank, world):
         metrics = step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # the row the entry point returned (its numeric values)
+        dump_outputs(args.dump_outputs, {"row": metrics})
 
     # ---- serial pass for the per-kernel table: the same pass on ONE context, overlap off, HIP-event profiling on
     prof, dt_serial = {}, None
@@ -973,6 +1045,17 @@ def launch_ranks(n):
 from rtvqa_amd.affinity import _parse_cpulist, bind_numa, gpu_local_cpus  # noqa: E402,F401  (sysfs only: no GPU call, no torch)
 
 
+# the legs beyond the headline figure: option -> (with --full, in a plain run); an option given explicitly keeps its value
+LEGS = {"cpu_sample": (-1, 0), "e2e_steps": (6, 0), "api_steps": (3, 0), "serial_pass": (True, False), "verify": (True, False)}
+
+
+def resolve_legs(args):
+    for k, (on, off) in LEGS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, on if args.full else off)
+    return args
+
+
 # ---------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -983,12 +1066,22 @@ def main():
                     help="c3 (default) = BASELINE.json's headline: 1080p full suite + PSNR/SSIM; c2 = PSNR+SSIM+8x8 DCT only; "
                          "c4 = 2160p full suite; c3ref = the reference's own metric definitions (Farneback, full-frame DCT, vf_ssim on yuv420p)")
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (default: workload's)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="frame pairs for the CPU baseline (0 = skip, -1 = auto)")
-    ap.add_argument("--e2e-steps", type=int, default=6, help="steps of the PCIe-inclusive end_to_end measurement (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: the CPU baseline, the check of the last timed step "
+                         "against the oracle, the serial pass (kernels + roofline), end_to_end and api_end_to_end.  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the line; an explicit leg option below still "
+                         "turns its leg on or off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; one file per record field)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="frame pairs for the CPU baseline (0 = skip, -1 = auto; default: -1 with --full, else 0)")
+    ap.add_argument("--e2e-steps", type=int, default=None,
+                    help="steps of the PCIe-inclusive end_to_end measurement (0 = skip; default: 6 with --full, else 0)")
     ap.add_argument("--e2e-batch", type=int, default=64, help="frames per step of the end_to_end measurement")
-    ap.add_argument("--api-steps", type=int, default=3,
+    ap.add_argument("--api-steps", type=int, default=None,
                     help="timed calls per residence of the api_end_to_end measurement (the reference-shaped Python entry point on "
-                         "the workload's clip; full-suite workloads in their default modes only; 0 = skip)")
+                         "the workload's clip; full-suite workloads in their default modes only; 0 = skip; default: 3 with "
+                         "--full, else 0)")
     ap.add_argument("--dist-always", action="store_true",
                     help="initialise torch.distributed (and run every collective of the N > 1 path) even when WORLD_SIZE is 1: "
                          "the one-rank RCCL bring-up a 1-GPU box can execute")
@@ -1011,10 +1104,11 @@ def main():
     ap.add_argument("--no-overlap", dest="overlap", action="store_false",
                     help="turn VQA_OPT_OVERLAP off for the timed region (the library's default is on: block-SAD and the Canny "
                          "chain on side streams inside the complexity submit)")
-    ap.add_argument("--no-serial-pass", dest="serial_pass", action="store_false",
-                    help="skip the serial pass after the timed region (then the line carries no per-kernel table and no roofline)")
-    ap.add_argument("--no-verify", dest="verify", action="store_false",
-                    help="skip the post-timing check of the last timed step's records against the oracle")
+    ap.add_argument("--no-serial-pass", dest="serial_pass", action="store_false", default=None,
+                    help="with --full: skip the serial pass after the timed region (then the line carries no per-kernel table "
+                         "and no roofline)")
+    ap.add_argument("--no-verify", dest="verify", action="store_false", default=None,
+                    help="with --full: skip the post-timing check of the last timed step's records against the oracle")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse the rank logic)")
     ap.add_argument("--no-bind-numa", dest="bind_numa", action="store_false",
@@ -1022,10 +1116,12 @@ def main():
                          "sysfs tells which CPUs those are; recorded as config.cpu_affinity)")
     ap.add_argument("--stub-engine", action="store_true",
                     help="CPU rehearsal of the N > 1 rank logic under gloo: no kernels run, the line carries \"stub\": true")
-    args = ap.parse_args()
+    args = resolve_legs(ap.parse_args())
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs is not None and args.steps < 1:
+        raise SystemExit("--dump-outputs needs --steps >= 1: it writes what the last timed step returned")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: start the ranks as fresh children, relay, never touch a GPU here (an 8-GPU run that came back
         # with "n_gpus": 1 and rc 0 was the failure mode of round 5)
@@ -1106,7 +1202,7 @@ def main():
         from rtvqa_amd import _native as N
         from rtvqa_amd import synth
         from rtvqa_amd.engine import DeviceBuffer, DeviceFrames, bgr_planes, yuv420p_planes
-        from rtvqa_amd.frames import bgr_to_yuv420p, frame_bytes_yuv420p
+        from rtvqa_amd.frames import frame_bytes_yuv420p
 
         # contexts: a set = (complexity ctx, quality ctx); --streams 2 gives the quality kernels their own context (= their
         # own HIP stream on the same device), --inflight 2 a second set so step i+1 is enqueued while step i drains
@@ -1140,13 +1236,11 @@ def main():
             ref_pin, dist_pin = eng.alloc_pinned((Bh + 1, h, w, 3)), eng.alloc_pinned((Bh + 1, h, w, 3))
             if yuv:  # the quality kernels' planar inputs cross PCIe too (the reference stream only in that form)
                 yref_pin, ydist_pin = eng.alloc_pinned((Bh + 1, ybytes)), eng.alloc_pinned((Bh + 1, ybytes))
-        for a in range(0, B + 1, CHUNK):
-            n = min(CHUNK, B + 1 - a)
-            r, d = stream_chunk(args.content, rank, h, w, a, n)
+        for a, r, d, yr, yd in stream_chunks(args.content, rank, h, w, B + 1, yuv):
+            n = len(r)
             N.check(eng.lib.vqa_copy_h2d(eng.ctx, ref_buf.ptr + a * fbytes, r.ctypes.data, r.nbytes), "h2d", eng.ctx)
             N.check(eng.lib.vqa_copy_h2d(eng.ctx, dist_buf.ptr + a * fbytes, d.ctypes.data, d.nbytes), "h2d", eng.ctx)
             if yuv:
-                yr, yd = bgr_to_yuv420p(r), bgr_to_yuv420p(d)
                 N.check(eng.lib.vqa_copy_h2d(eng.ctx, yref_buf.ptr + a * ybytes, yr.ctypes.data, yr.nbytes), "h2d", eng.ctx)
                 N.check(eng.lib.vqa_copy_h2d(eng.ctx, ydist_buf.ptr + a * ybytes, yd.ctypes.data, yd.nbytes), "h2d", eng.ctx)
             eng.sync()
@@ -1217,6 +1311,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     q, c = last if last is not None else (None, None)
+    if args.dump_outputs and rank == 0:   # per batch position: quality [B, planes], complexity [B]
+        dump_outputs(args.dump_outputs, {"quality": q, "complexity": c})
 
     # ---- serial pass, outside the timed region: ONE context, overlap off, HIP-event profiling on.  Its per-kernel times
     # are free of GPU sharing and add up to (at most) its own step time; they fill "kernels" / "roofline".

@@ -2,6 +2,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 label=$1; shift
+set -- --full "$@"   # the kernels table comes from the serial pass
 python3 bench.py --workload c3 --steps 5 --warmup 2 --cpu-sample 0 --e2e-steps 0 "$@" > gpurun_out/kms_$label.json 2> gpurun_out/kms_$label.err || { tail -3 gpurun_out/kms_$label.err; exit 1; }
 python3 - "$label" <<'PY'
 import json, sys

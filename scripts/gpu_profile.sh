@@ -6,6 +6,7 @@
 #    bench line is kept as gpurun_out/bench_<tag>_serial.log.
 set -o pipefail
 tag=$1; shift
+set -- --full "$@"   # the line carries the serial pass's kernels / roofline, the oracle check and the other legs
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $ROOT/gpurun_out
 timeout -k 10 900 python bench.py "$@" > $ROOT/gpurun_out/bench_$tag.log 2> $ROOT/gpurun_out/bench_$tag.err; rc=$?

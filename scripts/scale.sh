@@ -13,7 +13,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0   # dmabuf IPC: RCCL needs it on this pool
 mkdir -p gpurun_out
 OUT=gpurun_out/scale_$WL.jsonl
 : > $OUT
-# N = 1: plain python (no launcher); the CPU baseline leg runs only here
+# N = 1: plain python (no launcher); with --full the CPU baseline leg would run only here
 python bench.py --gpus 1 --workload $WL --steps $STEPS --warmup $WARMUP | tee -a $OUT || exit 1
 for N in 2 4 8; do
   python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \

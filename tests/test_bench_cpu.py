@@ -59,6 +59,73 @@ def test_workload_defaults_and_overrides_resolve_in_the_line():
     assert line["steps"] == 0 and line["value"] == 0.0
 
 
+def test_plain_run_leaves_the_other_legs_to_full():
+    """A plain run times --steps steps and prints the line; the legs beyond the headline (CPU baseline, oracle check, serial
+    pass, end_to_end, api_end_to_end) are on with --full, and an explicit leg option still wins either way."""
+    import argparse
+
+    def legs(full, **given):
+        ns = argparse.Namespace(full=full, **{k: given.get(k) for k in bench.LEGS})
+        bench.resolve_legs(ns)
+        return tuple(getattr(ns, k) for k in ("cpu_sample", "e2e_steps", "api_steps", "serial_pass", "verify"))
+    assert legs(False) == (0, 0, 0, False, False)
+    assert legs(True) == (-1, 6, 3, True, True)
+    assert legs(False, e2e_steps=2, cpu_sample=8) == (8, 2, 0, False, False)
+    assert legs(True, cpu_sample=0, verify=False) == (0, 6, 3, True, False)
+    # end to end through the stub: no serial figure and no check in a plain line
+    r = _run([sys.executable, "bench.py", "--stub-engine", "--backend", "gloo", "--steps", "3", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-800:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["ms_per_step_serial"] is None and "verified" not in line
+    assert abs(line["value"] - line["config"]["frames_per_step_per_gpu"] * 3 / (line["ms_per_step"] * 1e-3 * 3)) < 1e-3 * line["value"]
+    r = _run([sys.executable, "bench.py", "--stub-engine", "--backend", "gloo", "--steps", "2", "--warmup", "0", "--full"])
+    assert r.returncode == 0, r.stderr[-800:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 2
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's arrays as DIR/<name>.npy in float64, the same bytes from run to run."""
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run([sys.executable, "bench.py", "--stub-engine", "--backend", "gloo", "--steps", "2", "--warmup", "1",
+                  "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-800:]
+        outs.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    assert set(outs[0]) == {"quality_ssim.npy", "complexity_dct_energy.npy"}
+    B = bench.WORKLOADS["c3"]["batch"]
+    assert outs[0]["quality_ssim.npy"].shape == (B, 3) and outs[0]["complexity_dct_energy.npy"].shape == (B,)
+    for name, a in outs[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, outs[1][name]), name
+    r = _run([sys.executable, "bench.py", "--stub-engine", "--backend", "gloo", "--steps", "0", "--dump-outputs", str(tmp_path / "x")])
+    assert r.returncode != 0 and "--steps" in r.stderr and not (tmp_path / "x").exists()
+
+
+def test_dump_outputs_splits_records_and_samples_what_is_too_large(tmp_path):
+    import numpy as np
+    from rtvqa_amd.engine import FRAME_DTYPE, PLANE_DTYPE
+    c = np.zeros(6, FRAME_DTYPE)
+    c["hist_gray"] = np.arange(256)
+    c["sad_sum"] = 2 ** 40 + 3
+    q = np.zeros((6, 3), PLANE_DTYPE)
+    q["ssim"] = 0.25
+    names = bench.dump_outputs(str(tmp_path / "a"), {"quality": q, "complexity": c,
+                                                     "row": {"PSNR": 41.5, "Resolution (px)": "64x48", "DCT Complexity": 2.0}})
+    assert set(names) == {"quality_sse", "quality_ssim", "row_PSNR", "row_DCT_Complexity"} | {"complexity_" + f for f in FRAME_DTYPE.names}
+    assert np.load(tmp_path / "a" / "complexity_hist_gray.npy").shape == (6, 256)
+    assert np.load(tmp_path / "a" / "complexity_sad_sum.npy")[5] == 2 ** 40 + 3 and np.load(tmp_path / "a" / "row_PSNR.npy") == 41.5
+    n = 4000   # ~37 KB per row as float64: 150 MB in all, over the limit
+    big = {"quality": np.zeros((n, 3), PLANE_DTYPE), "complexity": np.zeros(n, FRAME_DTYPE), "wide": np.zeros((n, 4096))}
+    names = bench.dump_outputs(str(tmp_path / "b"), big)
+    total = sum((tmp_path / "b" / (k + ".npy")).stat().st_size for k in names)
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    assert total <= 64 * 10 ** 6 and 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.load(tmp_path / "b" / "wide.npy").shape == (len(rows), 4096)
+    names2 = bench.dump_outputs(str(tmp_path / "c"), big)
+    assert names2 == names and np.array_equal(np.load(tmp_path / "c" / "sample_rows.npy"), rows)   # a fixed sample
+
+
 @pytest.mark.parametrize("world", [2, 8])
 def test_gloo_rank_logic_json_shape(world):
     """The N > 1 rank logic at world 2 and at the node's full width (8): one rank per GPU as the driver launches it."""

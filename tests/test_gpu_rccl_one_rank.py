@@ -33,7 +33,7 @@ def _env():
 def test_bench_runs_its_rccl_path_with_one_rank(workload, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--dist-always", "--workload", workload, "--steps", "2",
-           "--warmup", "1", "--cpu-sample", "0", "--e2e-steps", "0", "--api-steps", "0"] + extra
+           "--warmup", "1", "--full", "--cpu-sample", "0", "--e2e-steps", "0", "--api-steps", "0"] + extra
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2500:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -49,7 +49,7 @@ def test_bench_runs_its_rccl_path_with_one_rank(workload, extra):
 def test_bench_gpus_1_needs_no_launcher_and_binds_to_the_gpus_cpus():
     """the driver's N = 1 command, plainly; the rank is pinned to the CPUs of its GPU's NUMA node before any GPU call when sysfs
     tells which those are (this pool's boxes: through the render node the container holds)"""
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--batch", "8", "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--batch", "8", "--steps", "2", "--warmup", "1", "--full", "--cpu-sample", "0",
            "--e2e-steps", "2", "--e2e-batch", "8", "--api-steps", "0"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2500:])
@@ -92,7 +92,7 @@ def test_configs4_shape_with_two_ranks_on_the_one_gpu_and_no_launcher():
     each verifies its last step against the oracle, and rank 0 prints ONE line for the whole job."""
     e = dict(_env(), VQA_BENCH_DEVICE="0")
     cmd = [sys.executable, "bench.py", "--workload", "c4", "--gpus", "2", "--batch", "4", "--steps", "2", "--warmup", "1",
-           "--cpu-sample", "0", "--e2e-steps", "0", "--api-steps", "0"]
+           "--full", "--cpu-sample", "0", "--e2e-steps", "0", "--api-steps", "0"]
     r = subprocess.run(cmd, cwd=REPO, env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
