@@ -108,7 +108,7 @@ static void *run_device(void *arg)
     vqa_plane_desc planes[3];
     for (int c = 0; c < 3; c++) {
         planes[c].width = w; planes[c].height = h; planes[c].offset = c; planes[c].row_stride = (int64_t)w * 3;
-        planes[c].pixel_step = 3; planes[c].pad_ = 0;
+        planes[c].pixel_step = 3; planes[c].bit_depth = 0;
     }
     const uint8_t *r1 = (const uint8_t *)dref + fb, *d1 = (const uint8_t *)ddist + fb;
     for (int pass = -1; pass < wk->passes; pass++) { /* pass -1 warms the context (allocations, first touch) */

@@ -112,7 +112,7 @@ int main(int argc, char **argv)
     vqa_plane_desc planes[3];
     for (int c = 0; c < 3; c++) {
         planes[c].width = w; planes[c].height = h; planes[c].offset = c; planes[c].row_stride = (int64_t)w * 3;
-        planes[c].pixel_step = 3; planes[c].pad_ = 0;
+        planes[c].pixel_step = 3; planes[c].bit_depth = 0;
     }
     const int nsel = n / iv;                                /* selected frames: 0-based index t with (t + 1) % iv == 0 */
     const int nsamp = nsel > 1 ? nsel - 1 : 0;              /* the first selected frame only primes (complexity_metrics.py:271) */

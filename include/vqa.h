@@ -66,7 +66,7 @@ extern "C" {
 #define VQA_API
 #endif
 
-#define VQA_ABI_VERSION 7
+#define VQA_ABI_VERSION 8
 #define VQA_TABLE_CACHE_GEOMETRIES 16
 
 typedef enum vqa_status {
@@ -166,18 +166,24 @@ typedef struct vqa_frame_metrics {
                                     batch sizes).  Every field of this record is independent of the batch. */
 } vqa_frame_metrics;
 
-/* One 8-bit plane inside a frame buffer (planar YUV plane, or one channel of
- * packed BGR with pixel_step = 3).                                          */
+/* One plane inside a frame buffer (planar YUV plane, or one channel of packed BGR with pixel_step = 3).
+ * bit_depth (ABI 8; the padding word of ABI 7): 0 or 8 = uint8 samples, exactly the ABI 7 behaviour; 9..16 = little-endian
+ * uint16 samples of that depth (yuv420p10le and its kin), whose offset, row_stride and pixel_step must be even.  One depth
+ * per vqa_quality_submit: planes of a submit that mix depths, a depth outside {0, 8..16} and an odd 16-bit offset, stride
+ * or step are VQA_ERR_INVALID.  Samples above max = 2^depth - 1 are read as they are, not clipped (as FFmpeg's psnr / ssim
+ * filters read them).  The metrics follow FFmpeg for that depth: vf_psnr's peak is max (the caller's stats lines), vf_ssim's
+ * constants are .01^2 max^2 64 and .03^2 max^2 64 63 with double end formulas, and the Gaussian SSIM takes data range
+ * L = max (C1 = (.01 L)^2, C2 = (.03 L)^2).                                                                             */
 typedef struct vqa_plane_desc {
     int32_t width, height;
     int64_t offset;      /* bytes from the start of the frame                 */
     int64_t row_stride;  /* bytes between rows                                */
     int32_t pixel_step;  /* bytes between horizontally adjacent samples       */
-    int32_t pad_;
+    int32_t bit_depth;   /* 0 / 8: uint8 samples; 9..16: little-endian uint16 */
 } vqa_plane_desc;
 
 typedef struct vqa_plane_metrics {
-    uint64_t sse;   /* sum (ref - dist)^2 over the plane — FFmpeg psnr's per-component sum */
+    uint64_t sse;   /* sum (ref - dist)^2 over the plane — FFmpeg psnr's per-component sum (exact at every depth) */
     double   ssim;  /* mean SSIM of the plane in the selected ssim_mode.  Independent of how frames are batched: the Gaussian
                        kernel sums the SSIM map in 2^-27 fixed point (integer sums are associative, so the strip geometry a
                        launch picks from its workgroup count cannot show; rounds 1-5 summed floats and differed by <= 1e-8

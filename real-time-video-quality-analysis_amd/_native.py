@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VQA_LIB_PATH") or os.path.join(_HERE, "csrc", "libvqa_hip.so")
 LAB_LIB_PATH = os.path.join(_HERE, "csrc", "lab", "libvqa_hip_lab.so")
 
-VQA_ABI_VERSION = 7
+VQA_ABI_VERSION = 8
 VQA_TABLE_CACHE_GEOMETRIES = 16
 
 VQA_OK = 0
@@ -74,7 +74,7 @@ class VqaFrameMetrics(C.Structure):
 class VqaPlaneDesc(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
                 ("offset", C.c_int64), ("row_stride", C.c_int64),
-                ("pixel_step", C.c_int32), ("pad_", C.c_int32)]
+                ("pixel_step", C.c_int32), ("bit_depth", C.c_int32)]
 
 
 class VqaPlaneMetrics(C.Structure):

@@ -1,7 +1,7 @@
 // k_quality.hip — PSNR's squared-error reduction and SSIM for gfx950.
 //
 // Reference function replaced: run_ffmpeg_metrics, video_processing.py:270-297
-// (FFmpeg `psnr` and `ssim` filters on each 8-bit plane of the two inputs).
+// (FFmpeg `psnr` and `ssim` filters on each plane of the two inputs: 8-bit samples, or 9..16-bit ones since ABI 8).
 //
 //   k_ssim_gauss : SSE + Gaussian-windowed SSIM (11x11, sigma 1.5, K1 .01, K2 .03,
 //                  valid region) — the window BASELINE.json's north_star decrees.
@@ -10,7 +10,7 @@
 //                  4-byte-aligned planar planes and packed BGR24; the byte kernel is the general path for
 //                  every other layout (odd offsets / strides, other pixel steps) — not an A/B variant.
 //
-// k_ssim_gauss design (the shipped kernel is k_ssim_gauss_p2<256, 8>, below).  The separable window needs 2 x 11
+// k_ssim_gauss design (the shipped kernel is k_ssim_gauss_p2<256, 8, false>, below).  The separable window needs 2 x 11
 // taps on 4 moment maps (E[x], E[y], E[x^2+y^2], E[xy]) = 88 FMA per pixel, ~115 VALU ops per pixel in total
 // against 2 bytes of input: ~57 op/B where the chip balances at 78.6 T lane-op/s / 8 TB/s ~ 10 op/B.  The kernel
 // is VALU-bound by construction (at 100 % of the fp32 vector peak it would reach 0.22 of the HBM roof); the design
@@ -120,6 +120,7 @@ struct plane_group {
     int64_t offset[4];
     int plane_index[4];
     int count;
+    float hscale;   // 9..16-bit samples: 255 / (2^depth - 1) (k_ssim_gauss_p2<.., true>); in what was tail padding: same size
 };
 
 #ifdef VQA_AB_VARIANTS // round 3's kernel (one row per barrier): lab build only
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(QT) SSIM_WAVES void k_ssim_gauss(const uint8_t *__r
 #endif // VQA_AB_VARIANTS
 
 // ---------------------------------------------------------------------------
-// k_ssim_gauss_p2<QT, R>: the same arithmetic with a FIFTH of the LDS read traffic.  Round 4 found the kernel
+// k_ssim_gauss_p2<QT, R, W16>: the same arithmetic with a FIFTH of the LDS read traffic.  Round 4 found the kernel
 // POWER-bound: the chip sits at its ~1.27 kW cap and sets the clock to fit (1.9 GHz under round 3's kernel); removing
 // 7 % of the instructions changed neither time nor energy, while the 11 ds_read_b128 per output pixel were worth 19 %
 // of a launch's energy (LAB_NOTES.md L4, profiles/round4_ssim_clock.json).  So the horizontal pass is shared:
@@ -311,7 +312,22 @@ __global__ __launch_bounds__(QT) SSIM_WAVES void k_ssim_gauss(const uint8_t *__r
 // against 4.23-4.25 for R = 4 on that box; R = 8 double-buffered (66 KB, 2 waves/SIMD) 4.54 at the full 2.38 GHz:
 // no longer power-bound but latency-bound.
 // ---------------------------------------------------------------------------
-template <int QT, int R>
+//
+// W16 (9..16-bit samples, k_ssim_gauss_p2<256, 8, true>): the samples are little-endian uint16 (buffer_load_ushort) and are mapped into
+// the 8-bit kernel's numeric range in fp32: x' = x * (255 / L) - 128 with L = 2^depth - 1 (one v_pk_fma on top of the exact
+// u16 -> float conversion).  SSIM is unchanged when samples and data range are scaled together, so C1 = (.01 * 255)^2 and
+// C2 = (.03 * 255)^2 on x' are C1 = (.01 L)^2 and C2 = (.03 L)^2 on x, and from there on every instruction is the 8-bit
+// kernel's.  What the scaling adds to the fp32 cancellation: x' is x * 255 / L rounded once, |x'| <= 128, so each sample is
+// off by d <= 2^-17 (7.6e-6); a window of perturbed samples has its variance moved by <= 2 sigma d + d^2 and its covariance
+// likewise, against a contrast denominator var_x + var_y + C2 >= sigma^2 + 58.5: <= 2 sigma d / (sigma^2 + 58.5) <= 1.0e-6
+// relative (the worst sigma is sqrt(58.5)).  The luminance term moves less.  Everything else is the 8-bit arithmetic on values
+// of the same size, which the 8-bit suite bounds at 1e-4; tests/test_gpu_quality_hbd.py checks 10, 12 and 16 bits against a
+// float64 reference at that bar.  SSE is exact in integers: |x - y| <= 65535, so (x - y)^2 < 2^32 goes through one
+// v_mad_u64_u32 into a 64-bit per-lane sum (the 8-bit flush of fp32 partial sums does not apply: 2^32 per sample is
+// beyond fp32's exact integers at the first pixel).
+// (The 8-bit and 16-bit kernels are one template rather than two kernels around a shared inlined body: the inlined body
+// changed the 8-bit kernel's scalar control flow, the template leaves its ISA as it was, name aside.)
+template <int QT, int R, bool W16>
 __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ dist,
                                                       int64_t ref_fs, int64_t dist_fs, plane_group g, int64_t row_stride,
                                                       int step, int w, int h, int ncb, int nstrips, int QS,
@@ -370,10 +386,14 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
     uint32_t sse_acc = 0;
     float sse_sq = 0.f, sse_xy = 0.f;
     float own_f = own_c ? 1.f : 0.f;
+    unsigned long long sse64 = 0;   // W16: the exact squared error of the lane's owned samples
     const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc((void *)rbase, (short)0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc((void *)dbase, (short)0, -1, 0x00020000);
     auto ld = [&](const __amdgpu_buffer_rsrc_t &rs, int rr) -> uint32_t {
-        return (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, coff, (int)((int64_t)rr * row_stride), 0);
+        if constexpr (W16)
+            return (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, coff, (int)((int64_t)rr * row_stride), 0);
+        else
+            return (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, coff, (int)((int64_t)rr * row_stride), 0);
     };
     uint32_t nr = ld(rres, 0), nd = ld(dres, 0);
 
@@ -394,11 +414,21 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
             nr = ld(rres, rr);
             nd = ld(dres, rr);
         }
-        const f2 xy = f2{__uint_as_float(0x4B000000u | cr), __uint_as_float(0x4B000000u | cd)} - f2{8388736.f, 8388736.f};
+        f2 xy;
+        if constexpr (W16) {   // exact u16 -> float (the 2^23 trick), then x * 255 / L - 128 in one rounding
+            const f2 v = f2{__uint_as_float(0x4B000000u | cr), __uint_as_float(0x4B000000u | cd)} - f2{8388608.f, 8388608.f};
+            xy = __builtin_elementwise_fma(v, f2{g.hscale, g.hscale}, f2{-128.f, -128.f});
+            const uint32_t e = cr > cd ? cr - cd : cd - cr;
+            sse64 += own_f != 0.f ? (unsigned long long)(e * e) : 0ull;   // e^2 <= 65535^2 < 2^32
+        } else {
+            xy = f2{__uint_as_float(0x4B000000u | cr), __uint_as_float(0x4B000000u | cd)} - f2{8388736.f, 8388736.f};
+        }
         f2 v1 = xy.xx * xy;
         v1.x = fmaf(xy.y, xy.y, v1.x);
-        sse_sq = fmaf(own_f, v1.x, sse_sq);
-        sse_xy = fmaf(own_f, v1.y, sse_xy);
+        if constexpr (!W16) {
+            sse_sq = fmaf(own_f, v1.x, sse_sq);
+            sse_xy = fmaf(own_f, v1.y, sse_xy);
+        }
 #pragma unroll
         for (int k = 0; k < 11; k++) {
             const int s = (p - k + NS) % NS;
@@ -484,7 +514,7 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
     static_assert(R <= 8, "2^27 x R must fit an int");
     const double bs = SSIM_FIXED_SUM ? 0.0 : block_sum((double)ssim_acc, red);
     const unsigned long long bf = SSIM_FIXED_SUM ? block_sum_u64((unsigned long long)ssim_fx, redf) : 0ull; // (two's complement: signed sums wrap right)
-    const unsigned long long be = block_sum_u64((unsigned long long)sse_acc, redu);
+    const unsigned long long be = block_sum_u64(W16 ? sse64 : (unsigned long long)sse_acc, redu);
     if (t == 0) {
         const int pidx = g.plane_index[ch];
         double *slot = &partials[(int64_t)pidx * partial_plane_stride + (int64_t)f * bpp + tile];
@@ -513,7 +543,7 @@ __global__ void k_ssim_finalize(const double *__restrict__ partials, int bpp, in
     res[(int64_t)f * n_planes + plane_index].ssim = s * inv_count;
 }
 
-// Shipped: k_ssim_gauss_p2<256>.  Lab build only (-DVQA_AB_VARIANTS, VQA_SSIM_VARIANT): the one-row-per-barrier kernel
+// Shipped: k_ssim_gauss_p2<256, 8, false> (<256, 8, true> for 9..16-bit samples).  Lab build only (-DVQA_AB_VARIANTS, VQA_SSIM_VARIANT): the one-row-per-barrier kernel
 // k_ssim_gauss<threads, -, LDS reads in flight>: 1 = {256,11}, 2 = {256,6}, 3 = {256,4}, 4 = {128,compiler's},
 // 5 = {256,compiler's} (round 3's shipped configuration)
 static int ssim_variant()
@@ -532,20 +562,24 @@ int ssim_gauss_blocks(int h, int w)
 }
 
 // planes[idx[0..count)] share width, height, row_stride and pixel_step
+// depth: 0 / 8 = uint8 samples, 9..16 = uint16 samples of that depth (k_ssim_gauss_p2<.., true>; the lab build's one-row kernels are
+// 8-bit only, so a high-depth launch always takes the shipped geometry)
 void launch_quality_gauss(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
                           int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count,
-                          int n_planes, double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res)
+                          int n_planes, double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res, int depth)
 {
     if (n <= 0 || count <= 0) return;
     const vqa_plane_desc &pd = planes[idx[0]];
     const int w = pd.width, h = pd.height;
-    const int qout = ssim_qout();
+    const bool w16 = depth > 8;
+    const int qout = w16 ? 256 - 10 : ssim_qout();
     const int ncb = (w - 10 + qout - 1) / qout;
     const int ns0 = ssim_strips(h, (long long)n * count * ncb), QS = ssim_strip_rows(h, ns0);
     const int ns = (h - 10 + QS - 1) / QS; // strips actually needed at this strip height
     const int bpp = ncb * ns;
     plane_group g;
     g.count = count;
+    g.hscale = 0.f;
     for (int i = 0; i < 4; i++) { g.offset[i] = planes[idx[i < count ? i : 0]].offset; g.plane_index[i] = idx[i < count ? i : 0]; }
 #ifdef VQA_AB_VARIANTS
 #define LAUNCH_SSIM(NT, PF, HPF)                                                                                      \
@@ -553,7 +587,13 @@ void launch_quality_gauss(hipStream_t st, const uint8_t *ref, const uint8_t *dis
                        dist_frame_stride, g, pd.row_stride, pd.pixel_step, w, h, ncb, ns, QS, partials,               \
                        partial_plane_stride, n_planes, res)
 #endif
-    switch (ssim_variant()) {
+    switch (w16 ? -1 : ssim_variant()) {
+    case -1:
+        g.hscale = (float)(255.0 / (double)((1 << depth) - 1));
+        hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS, true>), dim3((bpp + 7) / 8 * 8 * count, n), dim3(256), 0, st, ref, dist,
+                           ref_frame_stride, dist_frame_stride, g, pd.row_stride, pd.pixel_step, w, h, ncb, ns, QS, partials,
+                           partial_plane_stride, n_planes, res);
+        break;
 #ifdef VQA_AB_VARIANTS
     case 1: LAUNCH_SSIM(256, 2, 11); break;
     case 2: LAUNCH_SSIM(256, 2, 6); break;
@@ -562,13 +602,13 @@ void launch_quality_gauss(hipStream_t st, const uint8_t *ref, const uint8_t *dis
     case 5: LAUNCH_SSIM(256, 2, 0); break; // round 3's shipped kernel (one row per barrier), with round 4's loop structure
 #endif
     default: // the shipped kernel: SSIM_ROWS = 8 rows per LDS round trip, groups of 8 lanes share the horizontal pass
-        hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS>), dim3((bpp + 7) / 8 * 8 * count, n), dim3(256), 0, st, ref, dist, ref_frame_stride,
+        hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS, false>), dim3((bpp + 7) / 8 * 8 * count, n), dim3(256), 0, st, ref, dist, ref_frame_stride,
                            dist_frame_stride, g, pd.row_stride, pd.pixel_step, w, h, ncb, ns, QS, partials,
                            partial_plane_stride, n_planes, res);
         break;
     }
 #undef LAUNCH_SSIM
-    const bool fixed = SSIM_FIXED_SUM && ssim_variant() == 0; // (the lab build's one-row kernels leave doubles)
+    const bool fixed = SSIM_FIXED_SUM && (w16 || ssim_variant() == 0); // (the lab build's one-row kernels leave doubles)
     for (int i = 0; i < count; i++) {
         if (fixed)
             hipLaunchKernelGGL(k_ssim_finalize<true>, dim3((n + 63) / 64), dim3(64), 0, st,
@@ -768,6 +808,114 @@ __global__ void k_sse_ragged(const uint8_t *__restrict__ ref, const uint8_t *__r
     if (s) atomicAdd((unsigned long long *)&res[(int64_t)f * n_planes + plane_index].sse, s);
 }
 
+// ---------------------------------------------------------------------------
+// FFmpeg vf_ssim, 9..16-bit samples: libavfilter/vf_ssim.c ssim_plane_16bit -> ssim_4x4xn_16bit (4x4 block sums of
+// unsigned samples into int64 s1, s2, ss, s12), ssim_endn_16bit (a sample pools a 2x2 group of blocks) and ssim_end1x
+// (vqa_math.hpp: the end formula in double with c1 = .01^2 max^2 64, c2 = .03^2 max^2 64 63, max = 2^depth - 1); the plane's
+// value is the mean over (w/4 - 1)(h/4 - 1) samples, as for 8 bits (FFmpeg 4.0 - 7.x; the 8-bit restatement in
+// oracle/vqa_oracle.c follows the same file).  Sums: s1, s2 <= 64 * 65535 < 2^23 stay 32-bit; ss and s12 are 64-bit from
+// the first sample on (one 4x4 ss reaches 32 * 65535^2 ~ 1.4e11 at 16 bits; 5.4e8 at 12), every depth is exact.  The squared
+// error is ss - 2 s12 of the block, exact in uint64 (the true value is >= 0 and < 2^64).
+// Same mapping as k_ssim_ffmpeg: one lane per column of 4x4 blocks marching down a strip of FS_ROWS block rows, waves
+// overlap by one block column.  V8: pixel_step 2 and 8-byte-aligned rows - one global_load_dwordx2 brings the 4 samples of
+// a block row (a wave reads 512 contiguous bytes); otherwise 4 ushort loads at any even step.
+// grid = (ncw * nstrips, n_frames); block = 64 (one wave)
+// ---------------------------------------------------------------------------
+template <bool V8>
+__global__ __launch_bounds__(64) void k_ssim_ffmpeg16(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ dist,
+                                                      int64_t ref_fs, int64_t dist_fs, int64_t offset, int64_t row_stride,
+                                                      int step, int w, int h, int ncw, int nstrips, double c1, double c2,
+                                                      double *__restrict__ partials, int plane_index, int n_planes,
+                                                      vqa_plane_metrics *__restrict__ res)
+{
+    const int f = blockIdx.y;
+    const int lane = threadIdx.x;
+    const int cw = blockIdx.x % ncw, sb = blockIdx.x / ncw;
+    const int bw = w >> 2, bh = h >> 2;
+    const int bx = cw * 63 + lane;
+    const int by0 = sb * FS_ROWS;
+    const int by_end = min(by0 + FS_ROWS + 1, bh);
+    const bool last_cw = cw == ncw - 1, last_sb = sb == nstrips - 1;
+    const bool have = bx < bw;
+    const uint8_t *rb = ref + (int64_t)f * ref_fs + offset + (int64_t)(have ? bx : 0) * 4 * step;
+    const uint8_t *db = dist + (int64_t)f * dist_fs + offset + (int64_t)(have ? bx : 0) * 4 * step;
+    uint32_t p1 = 0, p2 = 0;
+    unsigned long long pss = 0, p12 = 0;
+    double ssim_acc = 0;
+    unsigned long long sse_acc = 0;
+    for (int by = by0; by < by_end; by++) {
+        uint32_t s1 = 0, s2 = 0;
+        unsigned long long ss = 0, s12 = 0;
+        if (have) {
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                const uint8_t *rr = rb + (int64_t)(by * 4 + y) * row_stride;
+                const uint8_t *dr = db + (int64_t)(by * 4 + y) * row_stride;
+                uint32_t a[4], b[4];
+                if (V8) {
+                    const uint2 ra = *(const uint2 *)rr, da = *(const uint2 *)dr;
+                    a[0] = ra.x & 0xffffu; a[1] = ra.x >> 16; a[2] = ra.y & 0xffffu; a[3] = ra.y >> 16;
+                    b[0] = da.x & 0xffffu; b[1] = da.x >> 16; b[2] = da.y & 0xffffu; b[3] = da.y >> 16;
+                } else {
+#pragma unroll
+                    for (int x = 0; x < 4; x++) {
+                        a[x] = *(const uint16_t *)(rr + (int64_t)x * step);
+                        b[x] = *(const uint16_t *)(dr + (int64_t)x * step);
+                    }
+                }
+#pragma unroll
+                for (int x = 0; x < 4; x++) {
+                    s1 += a[x];
+                    s2 += b[x];
+                    ss += (unsigned long long)(a[x] * a[x]);   // a^2 <= 65535^2 < 2^32: one v_mad_u64_u32
+                    ss += (unsigned long long)(b[x] * b[x]);
+                    s12 += (unsigned long long)(a[x] * b[x]);
+                }
+            }
+        }
+        const bool own = have && (last_cw || lane < 63) && (last_sb || by < by0 + FS_ROWS);
+        if (own) sse_acc += ss - 2ull * s12;
+        if (by > by0) {
+            const uint32_t v1 = p1 + s1, v2 = p2 + s2;
+            const unsigned long long vss = pss + ss, v12 = p12 + s12;
+            const uint32_t n1 = __shfl_down(v1, 1, 64), n2 = __shfl_down(v2, 1, 64);
+            const unsigned long long nss = __shfl_down(vss, 1, 64), n12 = __shfl_down(v12, 1, 64);
+            if (lane < 63 && bx + 1 < bw)
+                ssim_acc += ssim_ffmpeg_end1x((double)(v1 + n1), (double)(v2 + n2), (double)(vss + nss), (double)(v12 + n12), c1, c2);
+        }
+        p1 = s1; p2 = s2; pss = ss; p12 = s12;
+    }
+    ssim_acc = wave_sum(ssim_acc);
+    sse_acc = wave_sum(sse_acc);
+    if (lane == 0) {
+        partials[(int64_t)f * gridDim.x + blockIdx.x] = ssim_acc;
+        if (sse_acc) atomicAdd((unsigned long long *)&res[(int64_t)f * n_planes + plane_index].sse, sse_acc);
+    }
+}
+
+// k_sse_ragged for uint16 samples: (x - y)^2 < 2^32 per sample, summed in uint64
+__global__ void k_sse_ragged16(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ dist, int64_t ref_fs,
+                               int64_t dist_fs, int64_t offset, int64_t row_stride, int step, int w, int h, int n,
+                               int plane_index, int n_planes, vqa_plane_metrics *__restrict__ res)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const uint8_t *rb = ref + (int64_t)f * ref_fs + offset;
+    const uint8_t *db = dist + (int64_t)f * dist_fs + offset;
+    const int bw4 = (w >> 2) << 2, bh4 = (h >> 2) << 2;
+    unsigned long long s = 0;
+    for (int y = 0; y < h; y++) {
+        const int xb = y < bh4 ? bw4 : 0;
+        for (int x = xb; x < w; x++) {
+            const uint32_t a = *(const uint16_t *)(rb + (int64_t)y * row_stride + (int64_t)x * step);
+            const uint32_t b = *(const uint16_t *)(db + (int64_t)y * row_stride + (int64_t)x * step);
+            const uint32_t e = a > b ? a - b : b - a;
+            s += (unsigned long long)(e * e);
+        }
+    }
+    if (s) atomicAdd((unsigned long long *)&res[(int64_t)f * n_planes + plane_index].sse, s);
+}
+
 int ssim_ffmpeg_blocks(int h, int w)
 {
     const int bw = w >> 2, bh = h >> 2;
@@ -784,9 +932,10 @@ static bool aligned4(const void *p, int64_t a, int64_t b, int64_t c, int64_t d)
 // planes[idx[0..count)] share geometry.  count == 3 with pixel_step 3 and byte offsets o, o+1, o+2 (packed
 // BGR24) takes the fused three-channel path; pixel_step 1 takes the planar fast path; anything else the
 // generic byte kernel.  partials: [n_planes][partial_plane_stride].
+// depth 9..16: uint16 samples, k_ssim_ffmpeg16 per plane (+ k_sse_ragged16)
 void launch_quality_ffmpeg(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
                            int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count,
-                           int n_planes, double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res)
+                           int n_planes, double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res, int depth)
 {
     if (n <= 0 || count <= 0) return;
     const vqa_plane_desc &pd = planes[idx[0]];
@@ -794,6 +943,30 @@ void launch_quality_ffmpeg(hipStream_t st, const uint8_t *ref, const uint8_t *di
     const int bw = w >> 2, bh = h >> 2;
     const int ncw = (bw - 1 + 62) / 63, ns = (bh - 1 + FS_ROWS - 1) / FS_ROWS;
     const int bpp = ncw * ns;
+    if (depth > 8) {
+        const int mx = (1 << depth) - 1;   // vf_ssim.c: ssim_c1 / ssim_c2 of ssim_end1x, in its order of evaluation
+        const double c1 = .01 * .01 * mx * mx * 64, c2 = .03 * .03 * mx * mx * 64 * 63;
+        const bool a8 = ((((uintptr_t)ref | (uintptr_t)dist | (uint64_t)ref_frame_stride | (uint64_t)dist_frame_stride |
+                           (uint64_t)pd.row_stride) & 7u) == 0);
+        for (int i = 0; i < count; i++) {
+            const vqa_plane_desc &q = planes[idx[i]];
+            if (a8 && q.pixel_step == 2 && (q.offset & 7) == 0)
+                hipLaunchKernelGGL(k_ssim_ffmpeg16<true>, dim3(bpp, n), dim3(64), 0, st, ref, dist, ref_frame_stride,
+                                   dist_frame_stride, q.offset, q.row_stride, q.pixel_step, w, h, ncw, ns, c1, c2,
+                                   partials + (int64_t)idx[i] * partial_plane_stride, idx[i], n_planes, res);
+            else
+                hipLaunchKernelGGL(k_ssim_ffmpeg16<false>, dim3(bpp, n), dim3(64), 0, st, ref, dist, ref_frame_stride,
+                                   dist_frame_stride, q.offset, q.row_stride, q.pixel_step, w, h, ncw, ns, c1, c2,
+                                   partials + (int64_t)idx[i] * partial_plane_stride, idx[i], n_planes, res);
+            if ((w & 3) || (h & 3))
+                hipLaunchKernelGGL(k_sse_ragged16, dim3((n + 63) / 64), dim3(64), 0, st, ref, dist, ref_frame_stride,
+                                   dist_frame_stride, q.offset, q.row_stride, q.pixel_step, w, h, n, idx[i], n_planes, res);
+            hipLaunchKernelGGL(k_ssim_finalize<false>, dim3((n + 63) / 64), dim3(64), 0, st,
+                               partials + (int64_t)idx[i] * partial_plane_stride, bpp, n,
+                               1.0 / ((double)(bh - 1) * (double)(bw - 1)), idx[i], n_planes, res);
+        }
+        return;
+    }
     const bool al = aligned4(ref, (int64_t)(uintptr_t)dist, ref_frame_stride, dist_frame_stride, pd.row_stride);
     const bool fused3 = al && count == 3 && pd.pixel_step == 3 && (pd.offset & 3) == 0 &&
                         planes[idx[1]].offset == pd.offset + 1 && planes[idx[2]].offset == pd.offset + 2 &&

@@ -1316,18 +1316,25 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
     if (c->pend_q) return VQA_ERR_STATE;
     int64_t span = 0;
     int maxblocks = 1;
+    // sample depth (vqa_plane_desc.bit_depth): 0 / 8 = uint8, 9..16 = little-endian uint16 at even byte offsets, strides and
+    // steps; one depth per submit (FFmpeg's filters see one pixel format per frame)
+    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
+    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
+    const int bps = depth > 8 ? 2 : 1;   // bytes per sample
     for (int p = 0; p < n_planes; p++) {
         const vqa_plane_desc &d = planes[p];
+        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
+        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
         if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
-            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - 1))
+            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
             return VQA_ERR_INVALID;
         // k_ssim_gauss addresses a strip's rows through a 32-bit scalar buffer offset (row * row_stride) plus a 32-bit
         // lane offset: a plane whose rows span 2 GiB (absurd strides / regions of interest only) would wrap silently
         if (ssim_mode == VQA_SSIM_GAUSS &&
-            (int64_t)d.height * d.row_stride + (int64_t)d.width * d.pixel_step >= ((int64_t)1 << 31)) return VQA_ERR_UNSUPPORTED;
+            (int64_t)d.height * d.row_stride + (int64_t)d.width * d.pixel_step + bps >= ((int64_t)1 << 31)) return VQA_ERR_UNSUPPORTED;
         if (ssim_mode == VQA_SSIM_GAUSS && (d.width < 11 || d.height < 11)) return VQA_ERR_UNSUPPORTED;
         if (ssim_mode == VQA_SSIM_FFMPEG && (d.width < 8 || d.height < 8)) return VQA_ERR_UNSUPPORTED;
-        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + 1;
+        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
         span = end > span ? end : span;
         const int b = ssim_mode == VQA_SSIM_GAUSS ? ssim_gauss_blocks(d.height, d.width) : ssim_ffmpeg_blocks(d.height, d.width);
         maxblocks = b > maxblocks ? b : maxblocks;
@@ -1378,10 +1385,10 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
             prof_scope ps_(c, ssim_mode == VQA_SSIM_GAUSS ? VQA_K_SSIM_GAUSS : VQA_K_SSIM_FFMPEG);
             if (ssim_mode == VQA_SSIM_GAUSS)
                 launch_quality_gauss(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes,
-                                     (double *)c->qpartials.p, pstride, res);
+                                     (double *)c->qpartials.p, pstride, res, depth);
             else
                 launch_quality_ffmpeg(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes,
-                                      (double *)c->qpartials.p, pstride, res);
+                                      (double *)c->qpartials.p, pstride, res, depth);
         }
     }
     HIPCHK(c, hipGetLastError());

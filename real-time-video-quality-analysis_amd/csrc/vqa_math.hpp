@@ -184,4 +184,16 @@ VQA_HD float ssim_ffmpeg_end1(int s1, int s2, int ss, int s12)
            ((float)(s1 * s1 + s2 * s2 + c1) * (float)(vars + c2));
 }
 
+// vf_ssim's high-depth end formula, ssim_end1x() of libavfilter/vf_ssim.c (FFmpeg 4.0 - 7.x; ssim_endn_16bit hands it the
+// int64 sums of a 2x2 group of 4x4 blocks and max = (1 << depth) - 1).  Restated: the sums converted to double, vars, covar
+// and the quotient in double; c1 = .01 * .01 * max * max * 64 and c2 = .03 * .03 * max * max * 64 * 63 are evaluated by
+// the caller in that order (ssim_c1 / ssim_c2 of ssim_end1x).  Every product of sums below is an integer < 2^53 (4-block
+// sums <= 64 * 65535, ss <= 128 * 65535^2): exact in double, so fused or not the result is the same bits.
+VQA_HD double ssim_ffmpeg_end1x(double s1, double s2, double ss, double s12, double c1, double c2)
+{
+    const double vars = ss * 64 - s1 * s1 - s2 * s2;
+    const double covar = s12 * 64 - s1 * s2;
+    return (2 * s1 * s2 + c1) * (2 * covar + c2) / ((s1 * s1 + s2 * s2 + c1) * (vars + c2));
+}
+
 } // namespace vqa

@@ -33,35 +33,38 @@ assert PLANE_DTYPE.itemsize == C.sizeof(N.VqaPlaneMetrics)
 
 
 class DeviceFrames:
-    """n packed BGR24 frames resident in device memory."""
+    """n packed BGR24 frames resident in device memory (itemsize 2: frames of uint16 samples, for the quality kernels'
+    9..16-bit planes; strides are in bytes)."""
 
-    def __init__(self, ptr, n, h, w, frame_stride=None, row_stride=None, owner=None, channels=3):
+    def __init__(self, ptr, n, h, w, frame_stride=None, row_stride=None, owner=None, channels=3, itemsize=1):
         self.ptr, self.n, self.h, self.w = int(ptr), int(n), int(h), int(w)
         self.channels = channels
-        self.row_stride = int(row_stride) if row_stride else self.w * channels
+        self.itemsize = int(itemsize)
+        self.row_stride = int(row_stride) if row_stride else self.w * channels * self.itemsize
         self.frame_stride = int(frame_stride) if frame_stride else self.row_stride * self.h
         self._owner = owner  # keeps the allocation (torch tensor / DeviceBuffer) alive
 
     @classmethod
     def from_torch(cls, t):
-        """Wrap a CUDA(HIP) uint8 torch tensor of shape [n,h,w,3] (or [n,h,w]) without copying."""
-        assert t.is_cuda and t.dtype.__str__() == "torch.uint8" and t.is_contiguous()
+        """Wrap a CUDA(HIP) uint8 (or uint16) torch tensor of shape [n,h,w,3] (or [n,h,w]) without copying."""
+        assert t.is_cuda and t.dtype.__str__() in ("torch.uint8", "torch.uint16") and t.is_contiguous()
         ch = t.shape[3] if t.dim() == 4 else 1
-        return cls(t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], owner=t, channels=ch)
+        return cls(t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], owner=t, channels=ch, itemsize=t.element_size())
 
     def frame(self, i):
         return DeviceFrames(self.ptr + i * self.frame_stride, 1, self.h, self.w, self.frame_stride, self.row_stride,
-                            owner=self._owner, channels=self.channels)
+                            owner=self._owner, channels=self.channels, itemsize=self.itemsize)
 
     def slice(self, a, b):
         return DeviceFrames(self.ptr + a * self.frame_stride, b - a, self.h, self.w, self.frame_stride,
-                            self.row_stride, owner=self._owner, channels=self.channels)
+                            self.row_stride, owner=self._owner, channels=self.channels, itemsize=self.itemsize)
 
     def roi(self, y0, y1, x0, x1):
         """The window rows y0..y1, columns x0..x1 of every frame, in place (same memory, padded rows)."""
         assert 0 <= y0 < y1 <= self.h and 0 <= x0 < x1 <= self.w
-        return DeviceFrames(self.ptr + y0 * self.row_stride + x0 * self.channels, self.n, y1 - y0, x1 - x0,
-                            self.frame_stride, self.row_stride, owner=self._owner, channels=self.channels)
+        return DeviceFrames(self.ptr + y0 * self.row_stride + x0 * self.channels * self.itemsize, self.n, y1 - y0, x1 - x0,
+                            self.frame_stride, self.row_stride, owner=self._owner, channels=self.channels,
+                            itemsize=self.itemsize)
 
 
 class DeviceBuffer:
@@ -97,6 +100,52 @@ def yuv420p_planes(h, w):
     return [(w, h, 0, w, 1), (cw, ch, w * h, cw, 1), (cw, ch, w * h + cw * ch, cw, 1)]
 
 
+def yuv_planes(h, w, chroma="420", depth=8):
+    """Y, U, V of one planar frame (chroma "420" | "422" | "444"; "mono": Y only) at `depth` bits: 8 -> uint8 samples
+    (5-tuples, what yuv420p_planes / gray_planes give), 9..16 -> little-endian uint16 samples (6-tuples carrying the
+    depth; offsets and strides in bytes).  Planes follow each other without padding, as FFmpeg's planar formats."""
+    if chroma not in ("420", "422", "444", "mono"):
+        raise ValueError("chroma must be '420', '422', '444' or 'mono' (got %r)" % (chroma,))
+    depth = int(depth)
+    if depth != 8 and not 9 <= depth <= 16:
+        raise ValueError("depth must be 8 or 9..16 (got %d)" % depth)
+    bps = 2 if depth > 8 else 1
+    sizes = [(w, h)]
+    if chroma != "mono":
+        cw = (w + 1) // 2 if chroma in ("420", "422") else w
+        ch = (h + 1) // 2 if chroma == "420" else h
+        sizes += [(cw, ch), (cw, ch)]
+    out, off = [], 0
+    for pw, ph in sizes:
+        out.append((pw, ph, off, pw * bps, bps) + ((depth,) if depth > 8 else ()))
+        off += pw * ph * bps
+    return out
+
+
+def mono_planes(h, w, depth=8):
+    """One gray plane of `depth` bits (gray10le, gray16le ...: uint16 samples above 8 bits)."""
+    return yuv_planes(h, w, "mono", depth)
+
+
+def planes_depth(planes):
+    """The sample depth of a plane list: 8 for 5-tuples (and a 6th element 0 / 8), else the 6th element; one depth per list."""
+    depths = {(int(p[5]) if len(p) > 5 else 0) or 8 for p in planes}
+    if len(depths) != 1:
+        raise ValueError("the planes of one submit must share a sample depth (got %s)" % sorted(depths))
+    return depths.pop()
+
+
+def plane_descs(planes):
+    """Plane tuples (width, height, offset, row_stride, pixel_step[, bit_depth]) -> a ctypes vqa_plane_desc array."""
+    descs = (N.VqaPlaneDesc * len(planes))()
+    for i, p in enumerate(planes):
+        w, h, off, rs, step = p[:5]
+        descs[i].width, descs[i].height, descs[i].offset = w, h, off
+        descs[i].row_stride, descs[i].pixel_step = rs, step
+        descs[i].bit_depth = int(p[5]) if len(p) > 5 else 0
+    return descs
+
+
 class Engine:
     def __init__(self, device=0):
         self.lib = N.load()
@@ -129,13 +178,17 @@ class Engine:
 
     # ---- memory ----------------------------------------------------------
     def upload(self, arr):
-        """Copy a host uint8 array [n,h,w,3] (or [n,h,w]) to device memory."""
-        arr = np.ascontiguousarray(arr, dtype=np.uint8)
+        """Copy a host uint8 array [n,h,w,3] (or [n,h,w]) to device memory.  A uint16 array (9..16-bit planar frames, e.g.
+        [n, samples]) keeps its samples: DeviceFrames with itemsize 2."""
+        arr = np.asarray(arr)
+        arr = np.ascontiguousarray(arr, dtype=np.uint16 if arr.dtype == np.uint16 else np.uint8)
+        if arr.ndim == 2:
+            arr = arr[:, None, :]
         buf = DeviceBuffer(self, arr.nbytes)
         N.check(self.lib.vqa_copy_h2d(self.ctx, buf.ptr, arr.ctypes.data, arr.nbytes), "vqa_copy_h2d", self.ctx)
         N.check(self.lib.vqa_sync(self.ctx), "vqa_sync", self.ctx)
         ch = arr.shape[3] if arr.ndim == 4 else 1
-        return DeviceFrames(buf.ptr, arr.shape[0], arr.shape[1], arr.shape[2], owner=buf, channels=ch)
+        return DeviceFrames(buf.ptr, arr.shape[0], arr.shape[1], arr.shape[2], owner=buf, channels=ch, itemsize=arr.itemsize)
 
     def alloc_pinned(self, shape, dtype=np.uint8):
         """A NumPy array backed by page-locked host memory (hipHostMalloc): H2D from it is a true async DMA.
@@ -297,24 +350,34 @@ class Engine:
 
     # ---- quality -----------------------------------------------------------
     def quality_submit(self, ref, dist, planes, ssim_mode=N.SSIM_GAUSS, frame_bytes=None):
+        """planes: (width, height, offset, row_stride, pixel_step[, bit_depth]) per plane, in bytes.  8-bit planes read uint8
+        frames; 9..16-bit planes (yuv_planes(.., depth=10) ...) read uint16 frames (host arrays or DeviceFrames of itemsize 2),
+        passed through as they are: a frame of the other sample type is a ValueError, not a cast."""
+        wide = planes_depth(planes) > 8
         if isinstance(ref, DeviceFrames):
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
+            for a in (ref, dist):
+                if (a.itemsize == 2) != wide:
+                    raise ValueError("%d-bit planes need frames of %s samples (got DeviceFrames of itemsize %d)"
+                                     % (planes_depth(planes), "uint16" if wide else "uint8", a.itemsize))
             rp, dp, kind, n = ref.ptr, dist.ptr, N.VQA_MEM_DEVICE, ref.n
             rfs, dfs = ref.frame_stride, dist.frame_stride
             keep = (ref, dist)
         else:
-            ref = np.ascontiguousarray(ref, dtype=np.uint8)
-            dist = np.ascontiguousarray(dist, dtype=np.uint8)
+            ref, dist = np.asarray(ref), np.asarray(dist)
+            for a in (ref, dist):
+                if wide != (a.dtype == np.uint16):
+                    raise ValueError("%d-bit planes need %s frames (got %s)" % (planes_depth(planes), "uint16" if wide else "uint8",
+                                                                           a.dtype))
+            ref = np.ascontiguousarray(ref, dtype=np.uint16 if wide else np.uint8)
+            dist = np.ascontiguousarray(dist, dtype=np.uint16 if wide else np.uint8)
             if ref.shape != dist.shape:
                 raise ValueError("ref and dist must have the same shape")
             n = ref.shape[0]
             rfs = dfs = frame_bytes or (ref.nbytes // n)
             rp, dp, kind = ref.ctypes.data, dist.ctypes.data, N.VQA_MEM_HOST
             keep = (ref, dist)
-        descs = (N.VqaPlaneDesc * len(planes))()
-        for i, (w, h, off, rs, step) in enumerate(planes):
-            descs[i].width, descs[i].height, descs[i].offset = w, h, off
-            descs[i].row_stride, descs[i].pixel_step = rs, step
+        descs = plane_descs(planes)
         st = self.lib.vqa_quality_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes), ssim_mode)
         N.check(st, "vqa_quality_submit", self.ctx)
         self._pending_q = (n, len(planes), keep)

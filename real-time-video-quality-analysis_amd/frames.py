@@ -5,17 +5,49 @@ binary decode both inputs of the quality filters (video_processing.py:284-291). 
 target image and decode is out of scope, so streams arrive already decoded:
 
   .npy          [N,H,W,3] uint8 packed BGR24 (complexity path; what cv2 would have produced)
-  .y4m          YUV4MPEG2, 8-bit C420* planar 4:2:0 (quality path: the planes FFmpeg's psnr/ssim see); open_y4m maps the
-                file instead of reading it (a strided view: no host memory up front)
-  .yuv / raw    headerless yuv420p with explicit width/height (mapped)
+  .y4m          YUV4MPEG2, planar 4:2:0 / 4:2:2 / 4:4:4 / mono at 8 bits (C420*, C422, C444, Cmono) or 10 / 12 / 16 bits
+                (C420p10, C444p16, Cmono12 ... the tags FFmpeg's yuv4mpeg muxer writes; little-endian uint16 samples)
+                (quality path: the planes FFmpeg's psnr/ssim see); open_y4m maps the file instead of reading it (a strided
+                view: no host memory up front)
+  .yuv / raw    headerless planar YUV / gray (config pixfmt, default yuv420p) with explicit width/height (mapped)
   .bgr / .bgr24 headerless packed BGR24 with explicit width/height (mapped)
 
 Frames land in (optionally pinned) host buffers the engine can DMA from.
 """
 import os
-import re
 
 import numpy as np
+
+
+# FFmpeg pix_fmt name -> (chroma layout, bit depth, the C tag FFmpeg's yuv4mpeg muxer writes for it).  Samples above 8 bits are
+# little-endian uint16 (the "le" formats); planes follow each other Y, U, V (mono: Y only).
+PIXFMTS = {
+    "yuv420p": ("420", 8, "420jpeg"), "yuv422p": ("422", 8, "422"), "yuv444p": ("444", 8, "444"), "gray": ("mono", 8, "mono"),
+    "yuv420p10le": ("420", 10, "420p10"), "yuv422p10le": ("422", 10, "422p10"), "yuv444p10le": ("444", 10, "444p10"),
+    "yuv420p12le": ("420", 12, "420p12"), "yuv422p12le": ("422", 12, "422p12"), "yuv444p12le": ("444", 12, "444p12"),
+    "yuv420p16le": ("420", 16, "420p16"), "yuv444p16le": ("444", 16, "444p16"),
+    "gray10le": ("mono", 10, "mono10"), "gray12le": ("mono", 12, "mono12"), "gray16le": ("mono", 16, "mono16"),
+}
+_Y4M_TAGS = {tag: name for name, (_c, _d, tag) in PIXFMTS.items()}
+_Y4M_TAGS.update({"420": "yuv420p", "420mpeg2": "yuv420p", "420paldv": "yuv420p"})   # the other 8-bit 4:2:0 siting tags
+
+
+def plane_sizes(h, w, chroma):
+    """-> [(width, height)] of the planes of one frame: Y, then U and V (none for mono)"""
+    if chroma == "mono":
+        return [(w, h)]
+    cw = (w + 1) // 2 if chroma in ("420", "422") else w
+    ch = (h + 1) // 2 if chroma == "420" else h
+    return [(w, h), (cw, ch), (cw, ch)]
+
+
+def frame_samples(h, w, pixfmt="yuv420p"):
+    """samples per frame of a planar pix_fmt (PIXFMTS)"""
+    return sum(pw * ph for pw, ph in plane_sizes(h, w, PIXFMTS[pixfmt][0]))
+
+
+def sample_dtype(pixfmt):
+    return np.dtype("<u2") if PIXFMTS[pixfmt][1] > 8 else np.dtype(np.uint8)
 
 
 def frame_bytes_yuv420p(h, w):
@@ -23,8 +55,8 @@ def frame_bytes_yuv420p(h, w):
     return w * h + 2 * cw * ch
 
 
-def _y4m_header(path):
-    """-> (header length in bytes, height, width, fps)"""
+def _y4m_header_full(path):
+    """-> (header length in bytes, height, width, fps, pix_fmt name)"""
     with open(path, "rb") as f:
         header = f.readline()
     if not header.startswith(b"YUV4MPEG2"):
@@ -33,41 +65,64 @@ def _y4m_header(path):
     w = int(next(t[1:] for t in tok if t.startswith("W")))
     h = int(next(t[1:] for t in tok if t.startswith("H")))
     cs = next((t[1:] for t in tok if t.startswith("C")), "420jpeg")
-    if not cs.startswith("420") or re.search(r"p1[0-6]", cs):
-        raise ValueError("only 8-bit 4:2:0 Y4M is supported (got C%s)" % cs)
+    pixfmt = _Y4M_TAGS.get(cs)
+    if pixfmt is None:
+        raise ValueError("unsupported Y4M colour space C%s (supported: %s)" % (cs, ", ".join("C" + t for t in sorted(_Y4M_TAGS))))
+    il = next((t[1:] for t in tok if t.startswith("I")), "p")
+    if il not in ("p", "?"):
+        raise ValueError("interlaced Y4M (I%s) is not supported: progressive frames only" % il)
     fr = next((t[1:] for t in tok if t.startswith("F")), "30:1")
     num, den = (int(x) for x in fr.split(":"))
-    return len(header), h, w, (num / den if den else 0.0)
+    return len(header), h, w, (num / den if den else 0.0), pixfmt
+
+
+def _y4m_header(path):
+    """-> (header length in bytes, height, width, fps)"""
+    return _y4m_header_full(path)[:4]
+
+
+def y4m_pixfmt(path):
+    """the FFmpeg pix_fmt name (PIXFMTS) of a .y4m file's C tag"""
+    return _y4m_header_full(path)[4]
 
 
 def open_y4m(path, max_frames=None):
-    """-> (frames [N, bytes_per_frame] uint8 in Y,U,V plane order, height, width, fps) WITHOUT reading the file: a strided view
+    """-> (frames [N, samples_per_frame] in Y,U,V plane order - uint8, or little-endian uint16 above 8 bits (y4m_pixfmt tells
+    the format) -, height, width, fps) WITHOUT reading the file: a strided view
     of a memory map (every frame sits a 6-byte FRAME line + bytes_per_frame after the previous one), so a clip of any length costs no
     host memory up front and the pass pages in what it gathers into the pinned ring (stream.py) - the reference hands the file
     to an ffmpeg subprocess that streams it the same way (video_processing.py:284-291).  Falls back to read_y4m (which parses
     frame by frame) when a frame header carries parameters, i.e. the frames are not equally spaced."""
-    hl, h, w, fps = _y4m_header(path)
-    fb = frame_bytes_yuv420p(h, w)
+    hl, h, w, fps, pixfmt = _y4m_header_full(path)
+    dt = sample_dtype(pixfmt)
+    ns = frame_samples(h, w, pixfmt)
+    fb = ns * dt.itemsize
     size = os.path.getsize(path)
     n = (size - hl) // (fb + 6)
     if max_frames is not None:
         n = min(n, max_frames)
     if n <= 0:
-        return np.zeros((0, fb), np.uint8), h, w, fps
+        return np.zeros((0, ns), dt), h, w, fps
     mm = np.memmap(path, dtype=np.uint8, mode="r")
     marks = np.lib.stride_tricks.as_strided(mm[hl:], shape=(n, 6), strides=(fb + 6, 1), writeable=False)
     if not (marks == np.frombuffer(b"FRAME\n", np.uint8)).all():
         del marks, mm
         return read_y4m(path, max_frames)
-    frames = np.lib.stride_tricks.as_strided(mm[hl + 6:], shape=(n, fb), strides=(fb + 6, 1), writeable=False)
+    if dt.itemsize == 1:
+        frames = np.lib.stride_tricks.as_strided(mm[hl + 6:], shape=(n, ns), strides=(fb + 6, 1), writeable=False)
+    else:   # uint16 samples (not necessarily 2-byte aligned: the FRAME lines are 6 bytes), still a view of the map
+        frames = np.ndarray((n, ns), dtype=dt, buffer=mm, offset=hl + 6, strides=(fb + 6, dt.itemsize))
+        frames.flags.writeable = False
     return frames, h, w, fps
 
 
 def read_y4m(path, max_frames=None, out=None):
-    """-> (frames [N, bytes_per_frame] uint8 in Y,U,V plane order, height, width, fps), read into memory frame by frame
-    (frame headers with parameters are accepted); `out`: a (pinned) array to read into."""
-    hl, h, w, fps = _y4m_header(path)
-    fb = frame_bytes_yuv420p(h, w)
+    """-> (frames [N, samples_per_frame] in Y,U,V plane order (uint8, or uint16 above 8 bits), height, width, fps), read into
+    memory frame by frame (frame headers with parameters are accepted); `out`: a (pinned) array to read into."""
+    hl, h, w, fps, pixfmt = _y4m_header_full(path)
+    dt = sample_dtype(pixfmt)
+    ns = frame_samples(h, w, pixfmt)
+    fb = ns * dt.itemsize
     with open(path, "rb") as f:
         f.seek(hl)
         frames = []
@@ -80,20 +135,25 @@ def read_y4m(path, max_frames=None, out=None):
             buf = f.read(fb)
             if len(buf) < fb:
                 break
-            frames.append(np.frombuffer(buf, np.uint8))
-    arr = np.stack(frames) if frames else np.zeros((0, fb), np.uint8)
+            frames.append(np.frombuffer(buf, dt))
+    arr = np.stack(frames) if frames else np.zeros((0, ns), dt)
     if out is not None:
         out[:arr.shape[0]] = arr
         arr = out[:arr.shape[0]]
     return arr, h, w, fps
 
 
-def write_y4m(path, frames, h, w, fps=(30, 1)):
-    """frames: [N, bytes_per_frame] uint8 planar yuv420p."""
-    fb = frame_bytes_yuv420p(h, w)
-    frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
+def write_y4m(path, frames, h, w, fps=(30, 1), pixfmt="yuv420p"):
+    """frames: [N, samples_per_frame] planar `pixfmt` (PIXFMTS: uint8, or uint16 above 8 bits, written little-endian)."""
+    if pixfmt not in PIXFMTS:
+        raise ValueError("unsupported pixfmt %r (supported: %s)" % (pixfmt, ", ".join(PIXFMTS)))
+    dt = sample_dtype(pixfmt)
+    frames = np.asarray(frames)
+    if dt.itemsize > 1 and frames.dtype != np.uint16:
+        raise ValueError("%s frames must be uint16 (got %s)" % (pixfmt, frames.dtype))
+    frames = np.ascontiguousarray(frames, dt).reshape(-1, frame_samples(h, w, pixfmt))
     with open(path, "wb") as f:
-        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg\n" % (w, h, fps[0], fps[1]))
+        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s\n" % (w, h, fps[0], fps[1], PIXFMTS[pixfmt][2].encode()))
         for fr in frames:
             f.write(b"FRAME\n")
             f.write(fr.tobytes())
@@ -101,15 +161,21 @@ def write_y4m(path, frames, h, w, fps=(30, 1)):
 
 def read_raw_yuv420p(path, h, w, max_frames=None, mmap=True):
     """headerless planar yuv420p -> [N, bytes_per_frame]; mapped, not read (mmap=False: loaded into memory)"""
-    fb = frame_bytes_yuv420p(h, w)
-    n = os.path.getsize(path) // fb
+    return read_raw_yuv(path, h, w, "yuv420p", max_frames, mmap)
+
+
+def read_raw_yuv(path, h, w, pixfmt="yuv420p", max_frames=None, mmap=True):
+    """headerless planar `pixfmt` (PIXFMTS) -> [N, samples_per_frame] uint8 / uint16; mapped, not read (mmap=False: loaded)"""
+    dt = sample_dtype(pixfmt)
+    ns = frame_samples(h, w, pixfmt)
+    n = os.path.getsize(path) // (ns * dt.itemsize)
     if max_frames is not None:
         n = min(n, max_frames)
     if n <= 0:
-        return np.zeros((0, fb), np.uint8)
+        return np.zeros((0, ns), dt)
     if mmap:
-        return np.memmap(path, dtype=np.uint8, mode="r", shape=(n, fb))
-    return np.fromfile(path, np.uint8, count=n * fb).reshape(n, fb)
+        return np.memmap(path, dtype=dt, mode="r", shape=(n, ns))
+    return np.fromfile(path, dt, count=n * ns).reshape(n, ns)
 
 
 def open_raw_bgr24(path, h, w, max_frames=None):

@@ -193,18 +193,24 @@ def release_buffers(device=None):
 # sources
 # ---------------------------------------------------------------------------
 class _Source:
-    """n frames of `fb` bytes each: a device-resident clip or a host array whose first axis is the frame."""
+    """n frames of `fb` bytes each: a device-resident clip or a host array whose first axis is the frame.  wide: a stream of
+    the quality half, which may hold uint16 samples (9..16-bit planar frames); the complexity half reads 8-bit BGR only."""
 
-    def __init__(self, frames, engine):
+    def __init__(self, frames, engine, wide=False):
         self.frames = frames
         if isinstance(frames, DeviceFrames):
             self.kind, self.n = "device", frames.n
-            self.fb = frames.h * frames.w * frames.channels
+            self.itemsize = frames.itemsize
+            if self.itemsize != 1 and not wide:
+                raise ValueError("frames must be uint8: decoded 8-bit frames, as cv2.VideoCapture.read yields")
+            self.fb = frames.h * frames.w * frames.channels * self.itemsize
             return
-        if frames.dtype != np.uint8:  # a silent cast (or, from pinned memory, a reinterpretation) would measure garbage
+        if frames.dtype != np.uint8 and not (wide and frames.dtype == np.uint16):
+            # a silent cast (or, from pinned memory, a reinterpretation) would measure garbage
             raise ValueError("frames must be uint8 (got %s): decoded 8-bit frames, as cv2.VideoCapture.read yields" % frames.dtype)
         self.n = frames.shape[0]
-        self.fb = int(np.prod(frames.shape[1:], dtype=np.int64)) if frames.ndim > 1 else 1
+        self.itemsize = frames.itemsize
+        self.fb = (int(np.prod(frames.shape[1:], dtype=np.int64)) if frames.ndim > 1 else 1) * self.itemsize
         compact = self.n == 0 or (frames[0].flags.c_contiguous and (self.n == 1 or frames.strides[0] >= self.fb))
         # padded rows / a region of interest inside larger frames: the ring compacts them on the way
         self.kind = "pinned" if (compact and self.n and engine.is_pinned(frames)) else "pageable"
@@ -382,10 +388,11 @@ class _Feed:
     """One stream of a pass on its way to the kernels: its source and, for a host source, the lane buffers and the region
     of a ring slot its chunks travel through.  `key` names the plan's copy list for it."""
 
-    def __init__(self, name, key, frames, engine):
+    def __init__(self, name, key, frames, engine, wide=False):
         self.name, self.key = name, key
-        self.src = _Source(frames, engine)
+        self.src = _Source(frames, engine, wide)
         self.fb = self.src.fb
+        self.itemsize = self.src.itemsize
         self.host = self.src.kind != "device"
         self.staged = self.src.kind == "pageable"
         self.slots = 0      # frame slots a chunk of this feed needs (from the plans)
@@ -393,7 +400,7 @@ class _Feed:
 
     def geometry(self):
         f = self.src.frames
-        return (f.h, f.w, f.channels) if isinstance(f, DeviceFrames) else tuple(f.shape[1:])
+        return ((f.h, f.w, f.channels) if isinstance(f, DeviceFrames) else tuple(f.shape[1:])) + (self.itemsize,)
 
 
 # One pass at a time per device: the pinned ring, the lane buffers and the engines' pending state are per device, and the
@@ -480,11 +487,11 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     if want_c or not split:
-        feeds["dist"] = _Feed("dist", "copies", dist, first)
+        feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
-        feeds["ref"] = _Feed("ref", "rcopies", ref, first)
+        feeds["ref"] = _Feed("ref", "rcopies", ref, first, wide=True)
         if split:
-            feeds["qdist"] = _Feed("qdist", "qcopies", qd, first)
+            feeds["qdist"] = _Feed("qdist", "qcopies", qd, first, wide=True)
         fq, fr = feeds["qdist" if split else "dist"], feeds["ref"]
         if fr.src.n != fq.src.n or fr.fb != fq.fb:
             raise ValueError("reference and distorted streams must have the same frame count and layout")
@@ -532,6 +539,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
             for bs in range(min(nb, nchunks)):
                 st.device_buffer(bs, f.name, f.slots * f.fb)
         if f.staged:
+            if f.itemsize > 1:
+                off = -(-off // 64) * 64   # uint16 frames start aligned inside the slot
             f.ring_off = off
             off += f.slots * f.fb
     # ring slots: the chunks the lanes hold (a slot is free again when its chunk has been waited for), the chunk being
@@ -556,7 +565,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
             p["slot"], p["ring"], futs = slot, {}, []
             for f in feeds.values():
                 if f.staged and f.slots:
-                    region = blk[f.ring_off:f.ring_off + f.slots * f.fb].reshape(f.slots, f.fb)
+                    region = blk[f.ring_off:f.ring_off + f.slots * f.fb].view(f.src.frames.dtype).reshape(f.slots, f.fb // f.itemsize)
                     p["ring"][f.name] = region
                     futs += _fill_slot(st.copiers(), region, p[f.key])
             p["fill"] = futs
@@ -593,8 +602,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 for f, slot0 in ((fr, 0), (fq, p["qslot"])):
                     if f.host:
                         b = dev[f.name]
-                        pair.append(DeviceFrames(b.ptr + slot0 * f.fb, p["qn"], 1, f.fb, frame_stride=f.fb, row_stride=f.fb,
-                                                 owner=b, channels=1))
+                        pair.append(DeviceFrames(b.ptr + slot0 * f.fb, p["qn"], 1, f.fb // f.itemsize, frame_stride=f.fb,
+                                                 row_stride=f.fb, owner=b, channels=1, itemsize=f.itemsize))
                     else:
                         pair.append(f.src.frames.slice(p["q0"], p["q0"] + p["qn"]))
                 eng.quality_submit(pair[0], pair[1], quality.planes, quality.ssim_mode)

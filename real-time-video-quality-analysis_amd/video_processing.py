@@ -18,7 +18,8 @@ import numpy as np
 from . import _native as N
 from . import stream
 from .complexity_metrics import _open_frames
-from .engine import DeviceFrames, bgr_planes, gray_planes, yuv420p_planes
+from .engine import DeviceFrames, bgr_planes, gray_planes, yuv420p_planes, yuv_planes
+from .frames import PIXFMTS, frame_samples
 
 LAYOUTS = {
     # name: (plane builder, component letters as FFmpeg prints them)
@@ -26,27 +27,43 @@ LAYOUTS = {
     "gray": (gray_planes, "y"),       # [N,H,W]
     "yuv420p": (yuv420p_planes, "yuv"),  # [N, H*W*3/2] planar
 }
+# the other planar pix_fmts, by FFmpeg's names (frames.PIXFMTS): [N, samples per frame] planar, uint16 above 8 bits
+for _name, (_chroma, _depth, _tag) in PIXFMTS.items():
+    if _name not in LAYOUTS:
+        LAYOUTS[_name] = ((lambda h, w, c=_chroma, d=_depth: yuv_planes(h, w, c, d)), "y" if _chroma == "mono" else "yuv")
 _SSIM_MODES = {"gauss": N.SSIM_GAUSS, "ffmpeg": N.SSIM_FFMPEG}
 
 
+def layout_depth(layout):
+    """bits per sample of a layout (8 for bgr24 / gray / yuv420p)"""
+    return PIXFMTS[layout][1] if layout in PIXFMTS else 8
+
+
 def _geometry(reference, layout, height, width):
+    planar = layout not in ("bgr24", "gray")
     if isinstance(reference, DeviceFrames):
+        if planar and reference.h == 1 and height and width:   # [N, samples] planar frames (Engine.upload of a 2-D array)
+            return height, width
         return reference.h, reference.w
-    if layout == "yuv420p":
+    if planar or reference.ndim == 2:   # planar [N, samples]: the geometry comes from the header / config
         return height, width
     return reference.shape[1], reference.shape[2]
 
 
-def _host_stream(a):
+def _host_stream(a, wide=False):
+    """wide: a stream of the quality half, which may hold uint16 samples (9..16-bit planar frames)"""
     if isinstance(a, DeviceFrames):
         return a
     if type(a).__module__.startswith("torch") and hasattr(a, "is_cuda"):
-        from .complexity_metrics import _from_torch
-        a = _from_torch(a)
+        if wide and a.dtype.__str__() == "torch.uint16":
+            a = DeviceFrames.from_torch(a if a.is_contiguous() else a.contiguous()) if a.is_cuda else a.numpy()
+        else:
+            from .complexity_metrics import _from_torch
+            a = _from_torch(a)
         if isinstance(a, DeviceFrames):
             return a
     a = np.asarray(a)
-    if a.dtype != np.uint8:  # a silent cast would turn float frames in 0..1 into all-zero planes
+    if a.dtype != np.uint8 and not (wide and a.dtype == np.uint16):  # a silent cast would turn float frames in 0..1 into all-zero planes
         raise ValueError("frames must be uint8 (got %s)" % a.dtype)
     return a
 
@@ -57,7 +74,7 @@ def frame_quality(reference, distorted, layout="bgr24", ssim_mode="gauss", heigh
     One pass (stream.run): chunks of up to batch_size frame pairs alternate between two engines; host streams travel
     from the caller's pinned memory or through the pinned ring.  on_chunk(first_frame, sse, ssim) sees every finished
     chunk in frame order while the next one is on the GPU."""
-    reference, distorted = _host_stream(reference), _host_stream(distorted)
+    reference, distorted = _host_stream(reference, wide=True), _host_stream(distorted, wide=True)
     if not isinstance(reference, DeviceFrames) and reference.shape != distorted.shape:
         raise ValueError("ref and dist must have the same shape")
     h, w = _geometry(reference, layout, height, width)
@@ -82,9 +99,11 @@ def _psnr(mse, peak=255.0):
         return float(_db(np.float64(peak * peak) / np.float64(mse)))
 
 
-def psnr_stats_lines(n0, sse, sizes, comps):
+def psnr_stats_lines(n0, sse, sizes, comps, peak=255):
     """Lines n0.. of FFmpeg's psnr stats_file (vf_psnr.c) for sse [m,p]: per-component mse = sse/(w*h); mse_avg
-    weights components by plane area; psnr = 10 log10(255^2 / mse) (get_psnr(); mse 0 -> inf); 2-decimal text."""
+    weights components by plane area; psnr = 10 log10(peak^2 / mse) (get_psnr(); mse 0 -> inf); 2-decimal text.
+    peak: vf_psnr's max, (1 << depth) - 1 of the pixel format (255 for 8 bits, 1023 for 10)."""
+    pk = float(peak)
     sse = np.asarray(sse, np.float64).reshape(-1, len(sizes))
     areas = [w * h for w, h in sizes]
     total = float(sum(areas))
@@ -94,7 +113,7 @@ def psnr_stats_lines(n0, sse, sizes, comps):
         mse_avg = mse_avg + mse[:, j] * (a / total)
     with np.errstate(divide="ignore"):
         cols = [np.arange(n0, n0 + len(sse), dtype=np.float64), mse_avg] + [mse[:, j] for j in range(len(areas))]
-        cols += [_db(255.0 * 255.0 / mse_avg)] + [_db(255.0 * 255.0 / mse[:, j]) for j in range(len(areas))]
+        cols += [_db(pk * pk / mse_avg)] + [_db(pk * pk / mse[:, j]) for j in range(len(areas))]
     fmt = ("n:%d mse_avg:%0.2f " + "".join("mse_%c:%%0.2f " % c for c in comps) + "psnr_avg:%0.2f "
            + "".join("psnr_%c:%%0.2f " % c for c in comps) + "\n")
     return (fmt * len(sse)) % tuple(np.column_stack(cols).ravel().tolist())
@@ -115,8 +134,8 @@ def ssim_stats_lines(n0, ssim, sizes, comps):
     return (fmt * len(ssim)) % tuple(np.column_stack(cols).ravel().tolist())
 
 
-def psnr_stats_line(n, sse_row, sizes, comps):
-    return psnr_stats_lines(n, [list(sse_row)], sizes, comps)
+def psnr_stats_line(n, sse_row, sizes, comps, peak=255):
+    return psnr_stats_lines(n, [list(sse_row)], sizes, comps, peak)
 
 
 def ssim_stats_line(n, ssim_row, sizes, comps):
@@ -132,10 +151,11 @@ class _StatsWriter:
         self.order = [2, 1, 0] if layout == "bgr24" else list(range(len(comps)))
         self.names = "rgb" if layout == "bgr24" else comps
         self.sizes = [sizes[j] for j in self.order]
+        self.peak = (1 << layout_depth(layout)) - 1   # vf_psnr.c: max of the pixel format
         self.fp, self.fs = open(psnr_log, "w"), open(ssim_log, "w")
 
     def __call__(self, first_frame, sse, ssim):
-        self.fp.write(psnr_stats_lines(first_frame + 1, sse[:, self.order], self.sizes, self.names))
+        self.fp.write(psnr_stats_lines(first_frame + 1, sse[:, self.order], self.sizes, self.names, self.peak))
         self.fs.write(ssim_stats_lines(first_frame + 1, ssim[:, self.order], self.sizes, self.names))
 
     def close(self):
@@ -144,17 +164,19 @@ class _StatsWriter:
 
 
 def _open_quality_stream(src, layout, height, width):
-    """-> (frames, layout, height, width).  .y4m paths select the yuv420p layout by themselves; headerless .yuv (planar
-    yuv420p) and .bgr / .bgr24 (packed) files take their geometry from height / width."""
+    """-> (frames, layout, height, width).  .y4m paths select their layout by themselves (the header's C tag: yuv420p,
+    yuv422p10le ...); headerless .yuv (planar: `layout` when it names a planar pix_fmt, else yuv420p) and .bgr / .bgr24
+    (packed) files take their geometry from height / width."""
     if isinstance(src, str) and src.endswith(".y4m"):
-        from .frames import open_y4m
+        from .frames import open_y4m, y4m_pixfmt
         arr, h, w, _fps = open_y4m(src)     # a memory map: the pass pages in what it gathers, nothing is read up front
-        return arr, "yuv420p", h, w
+        return arr, y4m_pixfmt(src), h, w
     if isinstance(src, str) and src.endswith(".yuv"):
+        fmt = layout if layout in PIXFMTS else "yuv420p"
         if not height or not width:
-            raise ValueError("a raw yuv420p stream needs height and width")
-        from .frames import read_raw_yuv420p
-        return read_raw_yuv420p(src, height, width), "yuv420p", height, width
+            raise ValueError("a raw %s stream needs height and width" % fmt)
+        from .frames import read_raw_yuv
+        return read_raw_yuv(src, height, width, fmt), fmt, height, width
     if layout == "bgr24":
         return _open_frames(src, height, width), layout, height, width
     if isinstance(src, str):
@@ -200,7 +222,9 @@ def thread_safe_update_csv(metrics, csv_file="video_quality_data.csv"):
 MODE_KEYS = {
     # key: (allowed values, message in the reference's validate_config style)
     "ssim_mode": (("gauss", "ffmpeg"), "ssim_mode must be 'gauss' or 'ffmpeg'."),
-    "pixfmt": ((None, "bgr24", "yuv420p", "gray"), "pixfmt must be 'bgr24', 'yuv420p' or 'gray'."),
+    # (the message names the layouts of ABI 7; the planar pix_fmts of frames.PIXFMTS - yuv422p, yuv420p10le ... - are
+    # accepted as well)
+    "pixfmt": ((None, "bgr24") + tuple(PIXFMTS), "pixfmt must be 'bgr24', 'yuv420p' or 'gray'."),
     "dct_mode": ((None, "auto", "block8", "full"), "dct_mode must be 'auto', 'block8' or 'full'."),
     "motion": ((None, "sad", "farneback"), "motion must be 'sad' or 'farneback'."),
 }
@@ -239,7 +263,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         selected BGR frames are uploaded, each byte once.
     config   the reference's keys (crf, resize_width, resize_height, frame_interval, vmaf_model_path; config.json:1-7) plus
         batch_size, ssim_mode ("gauss" north_star's 11x11 Gaussian, default | "ffmpeg" vf_ssim's 8x8 integer windows),
-        pixfmt (None: by input | "bgr24" | "yuv420p" | "gray"), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
+        pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
+        yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
+        [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
         above | "block8" | "full" the reference's cv2.dct at any size), motion ("sad" north_star's block-SAD | "farneback" the
         reference's own; default: set_motion_mode / VQA_MOTION), device (GPU index; default VQA_DEVICE, LOCAL_RANK, 0) and
         height / width (the geometry of headerless inputs: raw .yuv planar pairs, raw .bgr24 streams).
@@ -273,8 +299,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
             if encoded_bgr is None:
                 raise ValueError("a %s quality pair needs the encoded stream's BGR frames for the complexity half "
                                  "(complexity_metrics.py:100 reads cv2's BGR decode): pass encoded_bgr=" % layout)
-            enc, qdist = _open_frames(encoded_bgr, qh or height, qw or width), _host_stream(qenc)
-            ref = _host_stream(ref)
+            enc, qdist = _open_frames(encoded_bgr, qh or height, qw or width), _host_stream(qenc, wide=True)
+            ref = _host_stream(ref, wide=True)
         eh, ew = (enc.h, enc.w) if isinstance(enc, DeviceFrames) else (enc.shape[1], enc.shape[2])
         if qdist is None:
             h, w = eh, ew
@@ -286,6 +312,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                     if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_bytes_yuv420p(h, w)):
                         raise ValueError("yuv420p streams must be planar [N, H*W*3/2] uint8 arrays of the frames' geometry "
                                          "(%dx%d: %d bytes per frame)" % (w, h, frame_bytes_yuv420p(h, w)))
+            elif layout in PIXFMTS and layout != "gray":
+                dt = np.uint16 if layout_depth(layout) > 8 else np.uint8
+                for a in (ref, qdist):
+                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_samples(h, w, layout)
+                                                            or a.dtype != dt):
+                        raise ValueError("%s streams must be planar [N, %d] %s arrays of the frames' geometry (%dx%d)"
+                                         % (layout, frame_samples(h, w, layout), np.dtype(dt).name, w, h))
         planes = LAYOUTS[layout][0](h, w)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
