@@ -120,6 +120,16 @@ typedef enum vqa_mem_kind {
 #define VQA_SSIM_GAUSS  0 /* 11x11 Gaussian window, sigma 1.5 (north_star)                  */
 #define VQA_SSIM_FFMPEG 1 /* FFmpeg vf_ssim: integer 8x8 window, stride 4 (what the
                              reference's subprocess really computes, video_processing.py:276) */
+#define VQA_SSIM_MS     2 /* multi-scale SSIM (Wang, Simoncelli, Bovik 2003) over the Gaussian window, in the 2x2-mean form of
+                             tf.image.ssim_multiscale / pytorch-msssim: five levels, level s+1 = the exact mean of each 2x2
+                             block of level s (an odd level's last row / column duplicated first; dims ceil(dim / 2)), per
+                             level the means cs_s, ssim_s of the window's contrast-structure and full maps, and
+                             MS-SSIM = prod_{s<4} max(cs_s,0)^w_s * max(ssim_4,0)^w_4, w = (.0448,.2856,.3001,.2363,.1333)
+                             (a negative mean gives 0).  Level 4 must hold a window: every plane of the submit must be at
+                             least 161 x 161 (a 4:2:0 frame 321 x 321), VQA_ERR_UNSUPPORTED below; depths, alignment and
+                             mixed depths are refused as for VQA_SSIM_GAUSS.  Scratch on the device: 2.7 bytes per pixel of
+                             the largest group of same-geometry planes of a batch (levels 1..4 of both images as fp32 sums),
+                             kept by the ctx until vqa_trim / vqa_destroy                                                 */
 
 typedef struct vqa_params {
     int32_t resize_w, resize_h; /* cv2.resize target; 0 or == frame size -> native (copy)  */
@@ -184,12 +194,19 @@ typedef struct vqa_plane_desc {
 
 typedef struct vqa_plane_metrics {
     uint64_t sse;   /* sum (ref - dist)^2 over the plane — FFmpeg psnr's per-component sum (exact at every depth) */
-    double   ssim;  /* mean SSIM of the plane in the selected ssim_mode.  Independent of how frames are batched: the Gaussian
+    double   ssim;  /* mean SSIM of the plane in the selected ssim_mode (VQA_SSIM_MS: the plane's MS-SSIM).  Independent of how frames are batched: the Gaussian
                        kernel sums the SSIM map in 2^-27 fixed point (integer sums are associative, so the strip geometry a
                        launch picks from its workgroup count cannot show; rounds 1-5 summed floats and differed by <= 1e-8
                        between batch sizes); vf_ssim's samples are summed in double, exactly for planes below ~2^28
                        samples.  The same frame pair gives the same bits in any batch; sse is exact */
 } vqa_plane_metrics;
+
+/* The per-scale means behind one VQA_SSIM_MS value (vqa_quality_wait_ms): level 0 is the plane, level 4 the coarsest.
+ * ssim[0] is, bit for bit, what VQA_SSIM_GAUSS returns for the plane.  Independent of the batch, as vqa_plane_metrics.ssim. */
+typedef struct vqa_ms_scales {
+    double cs[5];    /* mean of the contrast-structure map (2 s_xy + C2) / (s_x^2 + s_y^2 + C2) of each level */
+    double ssim[5];  /* mean of the SSIM map of each level                                                   */
+} vqa_ms_scales;
 
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
@@ -274,6 +291,10 @@ VQA_API int vqa_quality_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *
                        int64_t ref_frame_stride, int64_t dist_frame_stride,
                        const vqa_plane_desc *planes, int n_planes, int ssim_mode);
 VQA_API int vqa_quality_wait(vqa_ctx *ctx, vqa_plane_metrics *out, int n_entries);
+/* vqa_quality_wait that also fills scales[0..n_entries) with the per-scale means of a VQA_SSIM_MS submit (out[i].ssim is the
+ * product formed from scales[i]).  scales may be NULL: then it is vqa_quality_wait.  VQA_ERR_STATE, the batch still pending,
+ * when scales is given and the pending submit was not a VQA_SSIM_MS one.  (vqa_quality_wait serves an MS submit as well.) */
+VQA_API int vqa_quality_wait_ms(vqa_ctx *ctx, vqa_plane_metrics *out, vqa_ms_scales *scales, int n_entries);
 
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
@@ -284,11 +305,12 @@ enum vqa_kernel_id {
     VQA_K_CANNY_NMS = 4,
     VQA_K_CANNY_HYST = 5,
     VQA_K_SAD = 6,
-    VQA_K_SSIM_GAUSS = 7,
+    VQA_K_SSIM_GAUSS = 7, /* VQA_SSIM_MS: one entry per level (five per group of same-geometry planes) */
     VQA_K_SSIM_FFMPEG = 8,
     VQA_K_ORB = 9,       /* FAST-9/16 + NMS on the 64x64 thumbnail's centre */
     VQA_K_FARNEBACK = 10, /* the whole Farneback pyramid (about 30 launches per chunk of pairs) */
-    VQA_K_COUNT = 11
+    VQA_K_MS_PYRAMID = 11, /* VQA_SSIM_MS: levels 1..4 of both images from one read of level 0 */
+    VQA_K_COUNT = 12
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

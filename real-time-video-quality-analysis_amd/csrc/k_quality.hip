@@ -96,7 +96,13 @@ __host__ __device__ constexpr float gw(int k)
 // to save three instructions and lost the 1e-4 bar on full-white against full-black (2.5e-4: the luminance numerator
 // 2 ux uy + C1 = 6.5 came out of terms of size 32768) - caught by tests/golden/skimage_pins.json, and the kernel is
 // power-bound, not issue-bound, so the instructions bought nothing (LAB_NOTES.md).
-__device__ __forceinline__ float ssim_centered(f2 o0, f2 o1)
+// CS (multi-scale mode): the contrast/structure term cs = B.num / B.den of the SAME B leaves through `cs`; the ssim value is
+// formed exactly as without it.  x * rcp(x) is 1 or 1 - 2^-24 in fp32, so a quotient whose numerator EQUALS its denominator
+// is set to 1 - identical planes then have cs = 1 in every sample and an MS-SSIM of exactly 1 (for x = y every step above
+// gives num == den bit for bit: the two halves are the same roundings of the same numbers).  EQ1 does that for the ssim
+// value too; only the pyramid levels ask for it, level 0 keeps the single-scale mode's bits.
+template <bool CS = false, bool EQ1 = false>
+__device__ __forceinline__ float ssim_centered(f2 o0, f2 o1, float *cs = nullptr)
 {
     const float C1 = 6.5025f, C2 = 58.5225f;
     const f2 mm = o0 * o0;                                    // (mx^2, my^2)
@@ -108,6 +114,9 @@ __device__ __forceinline__ float ssim_centered(f2 o0, f2 o1)
     const f2 A = __builtin_elementwise_fma(q, f2{1.f, 2.f}, f2{C1, C1});   // (den, num) of the luminance term
     const f2 B = __builtin_elementwise_fma(vc, f2{1.f, 2.f}, f2{C2, C2});  // (den, num) of the contrast/structure term
     const f2 nd = A * B;
+    if constexpr (CS) *cs = B.y == B.x ? 1.f : B.y * __builtin_amdgcn_rcpf(B.x);
+    if constexpr (EQ1)
+        if (nd.y == nd.x) return 1.f;
     return nd.y * __builtin_amdgcn_rcpf(nd.x);
 }
 
@@ -120,7 +129,8 @@ struct plane_group {
     int64_t offset[4];
     int plane_index[4];
     int count;
-    float hscale;   // 9..16-bit samples: 255 / (2^depth - 1) (k_ssim_gauss_p2<.., true>); in what was tail padding: same size
+    float hscale;   // 9..16-bit samples: 255 / (2^depth - 1) (k_ssim_gauss_p2<.., true>); in what was tail padding: same size.
+                    // Pyramid levels (F32): that (1 for 8-bit planes) times 4^-level - the stored 2x2 sums back to sample scale
 };
 
 #ifdef VQA_AB_VARIANTS // round 3's kernel (one row per barrier): lab build only
@@ -327,7 +337,17 @@ __global__ __launch_bounds__(QT) SSIM_WAVES void k_ssim_gauss(const uint8_t *__r
 // beyond fp32's exact integers at the first pixel).
 // (The 8-bit and 16-bit kernels are one template rather than two kernels around a shared inlined body: the inlined body
 // changed the 8-bit kernel's scalar control flow, the template leaves its ISA as it was, name aside.)
-template <int QT, int R, bool W16>
+//
+// CS / F32 (multi-scale SSIM, VQA_SSIM_MS; the single-scale instances are <.., false, false> and compile to what they were):
+//   CS   the cs map is summed beside the ssim map, by the same rule - the float sum of a lane step's <= R values (|cs| <= 1
+//        up to rounding) is rounded once to 2^-27 and added as an integer - so the batch-independence argument above holds for
+//        both sums.  cs is taken from the factors ssim_centered has already formed.  The cs total of a tile is stored
+//        n_planes * partial_plane_stride slots behind its ssim total (the MS submit sizes the partials for two such halves).
+//   F32  a pyramid level (k_ms_pyramid): the samples are fp32 - EXACT sums of 4^level samples of level 0 (< 2^24 at level 4
+//        of a 16-bit plane) - and are mapped like W16 samples, x' = x * hscale - 128 in one rounding, with hscale =
+//        (255 / L) * 4^-level: the power of two takes the sum back to the exact mean, so a level is to this kernel a plane of
+//        depth + 2 level bits at the data range of level 0.  No squared error at a level (sse is level 0's).
+template <int QT, int R, bool W16, bool CS = false, bool F32 = false>
 __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ dist,
                                                       int64_t ref_fs, int64_t dist_fs, plane_group g, int64_t row_stride,
                                                       int step, int w, int h, int ncb, int nstrips, int QS,
@@ -335,6 +355,7 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
                                                       int n_planes, vqa_plane_metrics *__restrict__ res)
 {
     static_assert(R == 2 || R == 4 || R == 8, "rows per barrier = lanes per group = adjacent columns per lane");
+    static_assert(!F32 || (W16 && CS), "a pyramid level takes the scaled-sample path and exists in multi-scale mode only");
     constexpr int QOUT = QT - 10;
     constexpr int NS = 12;                  // accumulator ring: 11 live output rows + 1 spare slot, so that R divides the ring
     constexpr int ST = R == 8 ? 3 : 6;      // steps per loop iteration
@@ -382,6 +403,7 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
     // same total, bit for bit.  The rounding is <= 2^-28 per R values: <= 5e-10 on the mean (the bar is 1e-4), and the
     // integer sum carries none of the float chain's own ~1e-7 drift.
     long long ssim_fx = 0;
+    long long cs_fx = 0;            // CS: the cs map's sum, same fixed point
     float ssim_acc = 0.f;
     uint32_t sse_acc = 0;
     float sse_sq = 0.f, sse_xy = 0.f;
@@ -390,7 +412,9 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
     const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc((void *)rbase, (short)0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc((void *)dbase, (short)0, -1, 0x00020000);
     auto ld = [&](const __amdgpu_buffer_rsrc_t &rs, int rr) -> uint32_t {
-        if constexpr (W16)
+        if constexpr (F32)
+            return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, coff, (int)((int64_t)rr * row_stride), 0);
+        else if constexpr (W16)
             return (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, coff, (int)((int64_t)rr * row_stride), 0);
         else
             return (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, coff, (int)((int64_t)rr * row_stride), 0);
@@ -415,7 +439,9 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
             nd = ld(dres, rr);
         }
         f2 xy;
-        if constexpr (W16) {   // exact u16 -> float (the 2^23 trick), then x * 255 / L - 128 in one rounding
+        if constexpr (F32) {   // the level's exact fp32 sums: x * hscale - 128 in one rounding
+            xy = __builtin_elementwise_fma(f2{__uint_as_float(cr), __uint_as_float(cd)}, f2{g.hscale, g.hscale}, f2{-128.f, -128.f});
+        } else if constexpr (W16) {   // exact u16 -> float (the 2^23 trick), then x * 255 / L - 128 in one rounding
             const f2 v = f2{__uint_as_float(0x4B000000u | cr), __uint_as_float(0x4B000000u | cd)} - f2{8388608.f, 8388608.f};
             xy = __builtin_elementwise_fma(v, f2{g.hscale, g.hscale}, f2{-128.f, -128.f});
             const uint32_t e = cr > cd ? cr - cd : cd - cr;
@@ -460,12 +486,15 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
                         o1[j] = __builtin_elementwise_fma(f2{gw(i - j), gw(i - j)}, f2{q.z, q.w}, o1[j]);
                     }
             }
-            float sum = ssim_centered(o0[0], o1[0]);
+            float c = 0.f, sumc = 0.f;
+            float sum = ssim_centered<CS, F32>(o0[0], o1[0], &sumc);
 #pragma unroll
             for (int j = 1; j < R; j++) {
-                const float v = ssim_centered(o0[j], o1[j]);
+                const float v = ssim_centered<CS, F32>(o0[j], o1[j], &c);
                 sum += out_j[j] ? v : 0.f;
+                if constexpr (CS) sumc += out_j[j] ? c : 0.f;
             }
+            if constexpr (CS) cs_fx += (long long)__float2int_rn(sumc * 134217728.f);
             if (SSIM_FIXED_SUM) ssim_fx += (long long)__float2int_rn(sum * 134217728.f); // 2^27: |sum| <= 8 fits 31 bits
             else ssim_acc += sum;
         }
@@ -514,13 +543,17 @@ __global__ __launch_bounds__(QT) void k_ssim_gauss_p2(const uint8_t *__restrict_
     static_assert(R <= 8, "2^27 x R must fit an int");
     const double bs = SSIM_FIXED_SUM ? 0.0 : block_sum((double)ssim_acc, red);
     const unsigned long long bf = SSIM_FIXED_SUM ? block_sum_u64((unsigned long long)ssim_fx, redf) : 0ull; // (two's complement: signed sums wrap right)
-    const unsigned long long be = block_sum_u64(W16 ? sse64 : (unsigned long long)sse_acc, redu);
+    unsigned long long be = 0ull, bc = 0ull;
+    if constexpr (!F32) be = block_sum_u64(W16 ? sse64 : (unsigned long long)sse_acc, redu);
+    if constexpr (CS) bc = block_sum_u64((unsigned long long)cs_fx, redu);
     if (t == 0) {
         const int pidx = g.plane_index[ch];
         double *slot = &partials[(int64_t)pidx * partial_plane_stride + (int64_t)f * bpp + tile];
         if (SSIM_FIXED_SUM) *reinterpret_cast<unsigned long long *>(slot) = bf;
         else *slot = bs;
-        if (be) atomicAdd((unsigned long long *)&res[(int64_t)f * n_planes + pidx].sse, be);
+        if constexpr (CS) *reinterpret_cast<unsigned long long *>(slot + (int64_t)n_planes * partial_plane_stride) = bc;
+        if constexpr (!F32)
+            if (be) atomicAdd((unsigned long long *)&res[(int64_t)f * n_planes + pidx].sse, be);
     }
 }
 
@@ -619,6 +652,51 @@ void launch_quality_gauss(hipStream_t st, const uint8_t *ref, const uint8_t *dis
                                partials + (int64_t)idx[i] * partial_plane_stride, bpp, n,
                                1.0 / ((double)(w - 10) * (double)(h - 10)), idx[i], n_planes, res);
     }
+}
+
+// One scale of the multi-scale mode (VQA_SSIM_MS): the CS instance of the shipped kernel on level `level` of the group, then
+// the means of its ssim and cs maps into ms[frame * n_planes + plane].  Level 0 reads the caller's planes (uint8 / uint16);
+// levels 1..4 read the fp32 sums k_ms_pyramid left in `scratch` (ms_levels() is the layout).  Always the shipped geometry:
+// the lab build's one-row kernels stay single-scale.
+void launch_quality_ms_level(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                             int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int n_planes,
+                             double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res, int depth, int level,
+                             const float *scratch, vqa_ms_scales *ms)
+{
+    if (n <= 0 || count <= 0) return;
+    const vqa_plane_desc &pd = planes[idx[0]];
+    const ms_layout L = ms_levels(n, count, pd.height, pd.width);
+    const int w = L.w[level], h = L.h[level];
+    const int qout = 256 - 10;
+    const int ncb = (w - 10 + qout - 1) / qout;
+    const int ns0 = ssim_strips(h, (long long)n * count * ncb), QS = ssim_strip_rows(h, ns0);
+    const int ns = (h - 10 + QS - 1) / QS;
+    const int bpp = ncb * ns;
+    plane_group g;
+    g.count = count;
+    g.hscale = ldexpf(depth > 8 ? (float)(255.0 / (double)((1 << depth) - 1)) : 1.f, -2 * level);
+    const dim3 grid((bpp + 7) / 8 * 8 * count, n), block(256);
+    if (level == 0) {
+        for (int i = 0; i < 4; i++) { g.offset[i] = planes[idx[i < count ? i : 0]].offset; g.plane_index[i] = idx[i < count ? i : 0]; }
+        if (depth > 8)
+            hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS, true, true, false>), grid, block, 0, st, ref, dist, ref_frame_stride,
+                               dist_frame_stride, g, pd.row_stride, pd.pixel_step, w, h, ncb, ns, QS, partials,
+                               partial_plane_stride, n_planes, res);
+        else
+            hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS, false, true, false>), grid, block, 0, st, ref, dist, ref_frame_stride,
+                               dist_frame_stride, g, pd.row_stride, pd.pixel_step, w, h, ncb, ns, QS, partials,
+                               partial_plane_stride, n_planes, res);
+    } else {
+        const int64_t plane_bytes = (int64_t)h * w * (int64_t)sizeof(float), fs = plane_bytes * count;
+        for (int i = 0; i < 4; i++) { g.offset[i] = plane_bytes * (i < count ? i : 0); g.plane_index[i] = idx[i < count ? i : 0]; }
+        const uint8_t *lref = (const uint8_t *)(scratch + L.off[level]), *ldist = lref + fs * n;
+        hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS, true, true, true>), grid, block, 0, st, lref, ldist, fs, fs, g,
+                           (int64_t)w * (int64_t)sizeof(float), (int)sizeof(float), w, h, ncb, ns, QS, partials,
+                           partial_plane_stride, n_planes, res);
+    }
+    for (int i = 0; i < count; i++)
+        launch_ms_finalize(st, partials + (int64_t)idx[i] * partial_plane_stride, (int64_t)n_planes * partial_plane_stride, bpp, n,
+                           (double)(w - 10) * (double)(h - 10), idx[i], n_planes, level, ms);
 }
 
 // ---------------------------------------------------------------------------

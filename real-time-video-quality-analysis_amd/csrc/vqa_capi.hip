@@ -62,9 +62,11 @@ struct vqa_ctx {
     dbuf gray_full, planeA, planeB, state, res_dev, partials, tile_flags, dirty0, dirty1, again_dev;
     dbuf stage_frames, stage_prev, dct_scratch, dct_pe, dct_pt;
     dbuf qres_dev, qpartials, qstage_ref, qstage_dist;
+    dbuf qms_pyr, qms_dev;   // VQA_SSIM_MS: pyramid levels 1..4 of the largest plane group seen; per-entry scale means
     // pinned host staging
     void *res_host = nullptr; size_t res_host_cap = 0;
     void *qres_host = nullptr; size_t qres_host_cap = 0;
+    void *qms_host = nullptr; size_t qms_host_cap = 0;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -77,6 +79,7 @@ struct vqa_ctx {
 
     // pending work
     int pend_c = 0, pend_q = 0;
+    bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -800,7 +803,7 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
@@ -809,8 +812,9 @@ static void release_scratch(vqa_ctx *c)
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
     if (c->res_host) (void)hipHostFree(c->res_host);
     if (c->qres_host) (void)hipHostFree(c->qres_host);
-    c->res_host = c->qres_host = nullptr;
-    c->res_host_cap = c->qres_host_cap = 0;
+    if (c->qms_host) (void)hipHostFree(c->qms_host);
+    c->res_host = c->qres_host = c->qms_host = nullptr;
+    c->res_host_cap = c->qres_host_cap = c->qms_host_cap = 0;
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
 }
@@ -1312,8 +1316,9 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
 {
     if (!c || !ref || !dist || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
     if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
-    if (ssim_mode != VQA_SSIM_GAUSS && ssim_mode != VQA_SSIM_FFMPEG) return VQA_ERR_INVALID;
+    if (ssim_mode != VQA_SSIM_GAUSS && ssim_mode != VQA_SSIM_FFMPEG && ssim_mode != VQA_SSIM_MS) return VQA_ERR_INVALID;
     if (c->pend_q) return VQA_ERR_STATE;
+    const bool ms = ssim_mode == VQA_SSIM_MS, gauss = ms || ssim_mode == VQA_SSIM_GAUSS;   // MS: the Gaussian window on five scales
     int64_t span = 0;
     int maxblocks = 1;
     // sample depth (vqa_plane_desc.bit_depth): 0 / 8 = uint8, 9..16 = little-endian uint16 at even byte offsets, strides and
@@ -1330,13 +1335,14 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
             return VQA_ERR_INVALID;
         // k_ssim_gauss addresses a strip's rows through a 32-bit scalar buffer offset (row * row_stride) plus a 32-bit
         // lane offset: a plane whose rows span 2 GiB (absurd strides / regions of interest only) would wrap silently
-        if (ssim_mode == VQA_SSIM_GAUSS &&
+        if (gauss &&
             (int64_t)d.height * d.row_stride + (int64_t)d.width * d.pixel_step + bps >= ((int64_t)1 << 31)) return VQA_ERR_UNSUPPORTED;
-        if (ssim_mode == VQA_SSIM_GAUSS && (d.width < 11 || d.height < 11)) return VQA_ERR_UNSUPPORTED;
+        if (gauss && (d.width < 11 || d.height < 11)) return VQA_ERR_UNSUPPORTED;
+        if (ms && (d.width < MS_MIN_DIM || d.height < MS_MIN_DIM)) return VQA_ERR_UNSUPPORTED;   // level 4 must hold a window
         if (ssim_mode == VQA_SSIM_FFMPEG && (d.width < 8 || d.height < 8)) return VQA_ERR_UNSUPPORTED;
         const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
         span = end > span ? end : span;
-        const int b = ssim_mode == VQA_SSIM_GAUSS ? ssim_gauss_blocks(d.height, d.width) : ssim_ffmpeg_blocks(d.height, d.width);
+        const int b = gauss ? ssim_gauss_blocks(d.height, d.width) : ssim_ffmpeg_blocks(d.height, d.width);
         maxblocks = b > maxblocks ? b : maxblocks;
     }
     if (n > 1 && (ref_fs < span || dist_fs < span)) return VQA_ERR_INVALID;
@@ -1362,8 +1368,26 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
     if (rc) return rc;
     const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
     const int nslice = n < QSLICE ? n : QSLICE;
-    rc = ensure(c, c->qpartials, sizeof(double) * (size_t)maxblocks * nslice * n_planes);
+    // (MS: a second half of the same size for the cs totals; level 0 has the most tiles)
+    rc = ensure(c, c->qpartials, sizeof(double) * (size_t)maxblocks * nslice * n_planes * (ms ? 2 : 1));
     if (rc) return rc;
+    if (ms) {
+        // the pyramid scratch serves one group of same-geometry planes at a time (the groups follow each other on the stream):
+        // sized by the largest group, which no grouping of the planes can exceed when every plane is counted at the largest size
+        size_t pyr = 0;
+        for (int p = 0; p < n_planes; p++) {
+            int cnt = 0;
+            for (int q = 0; q < n_planes; q++) cnt += planes[q].width == planes[p].width && planes[q].height == planes[p].height;
+            const size_t b = sizeof(float) * (size_t)ms_levels(nslice, cnt, planes[p].height, planes[p].width).total;
+            pyr = b > pyr ? b : pyr;
+        }
+        rc = ensure(c, c->qms_pyr, pyr);
+        if (rc) return rc;
+        rc = ensure(c, c->qms_dev, sizeof(vqa_ms_scales) * nent);
+        if (rc) return rc;
+        rc = ensure_pinned(c, c->qms_host, c->qms_host_cap, sizeof(vqa_ms_scales) * nent);
+        if (rc) return rc;
+    }
     HIPCHK(c, hipMemsetAsync(c->qres_dev.p, 0, sizeof(vqa_plane_metrics) * nent, st));
     const int64_t pstride = (int64_t)maxblocks * nslice;
     for (int a0 = 0; a0 < n; a0 += QSLICE) {
@@ -1382,6 +1406,21 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
                     done[q] = true;
                 }
             }
+            if (ms) {
+                // one pyramid launch, then the five scales one after another on the ctx stream (each level's totals leave the
+                // partials through its finalize before the next level's kernel overwrites them)
+                vqa_ms_scales *msd = (vqa_ms_scales *)c->qms_dev.p + (size_t)a0 * n_planes;
+                {
+                    prof_scope pp_(c, VQA_K_MS_PYRAMID);
+                    launch_ms_pyramid(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, depth, (float *)c->qms_pyr.p);
+                }
+                for (int lv = 0; lv < MS_LEVELS; lv++) {
+                    prof_scope pl_(c, VQA_K_SSIM_GAUSS);
+                    launch_quality_ms_level(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes,
+                                            (double *)c->qpartials.p, pstride, res, depth, lv, (const float *)c->qms_pyr.p, msd);
+                }
+                continue;
+            }
             prof_scope ps_(c, ssim_mode == VQA_SSIM_GAUSS ? VQA_K_SSIM_GAUSS : VQA_K_SSIM_FFMPEG);
             if (ssim_mode == VQA_SSIM_GAUSS)
                 launch_quality_gauss(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes,
@@ -1391,8 +1430,11 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
                                       (double *)c->qpartials.p, pstride, res, depth);
         }
     }
+    if (ms) launch_ms_combine(st, (const vqa_ms_scales *)c->qms_dev.p, (int)nent, (vqa_plane_metrics *)c->qres_dev.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->qres_host, c->qres_dev.p, sizeof(vqa_plane_metrics) * nent, hipMemcpyDeviceToHost, st));
+    if (ms) HIPCHK(c, hipMemcpyAsync(c->qms_host, c->qms_dev.p, sizeof(vqa_ms_scales) * nent, hipMemcpyDeviceToHost, st));
+    c->pend_q_ms = ms;
     c->pend_q = (int)nent;
     return VQA_OK;
 }
@@ -1405,15 +1447,23 @@ int vqa_quality_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int 
     return drain_failed_submit(c, rc, touched);
 }
 
-int vqa_quality_wait(vqa_ctx *c, vqa_plane_metrics *out, int n_entries)
+int vqa_quality_wait_ms(vqa_ctx *c, vqa_plane_metrics *out, vqa_ms_scales *scales, int n_entries)
 {
     if (!c || !out) return VQA_ERR_INVALID;
     if (!c->pend_q || n_entries != c->pend_q) return VQA_ERR_STATE;
+    if (scales && !c->pend_q_ms) return VQA_ERR_STATE;   // (the batch stays pending: vqa_quality_wait collects it)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     memcpy(out, c->qres_host, sizeof(vqa_plane_metrics) * (size_t)n_entries);
+    if (scales) memcpy(scales, c->qms_host, sizeof(vqa_ms_scales) * (size_t)n_entries);
     c->pend_q = 0;
+    c->pend_q_ms = false;
     return VQA_OK;
+}
+
+int vqa_quality_wait(vqa_ctx *c, vqa_plane_metrics *out, int n_entries)
+{
+    return vqa_quality_wait_ms(c, out, nullptr, n_entries);
 }
 
 // ---------------------------------------------------------------------------
@@ -1441,7 +1491,7 @@ const char *vqa_kernel_name(int id)
 {
     static const char *names[VQA_K_COUNT] = {"k_bgr2gray_hist", "k_resize_planes", "k_dct8", "k_dct_full",
                                              "k_canny_nms", "k_canny_hyst", "k_block_sad", "k_ssim_gauss",
-                                             "k_ssim_ffmpeg", "k_orb64", "farneback(pyramid)"};
+                                             "k_ssim_ffmpeg", "k_orb64", "farneback(pyramid)", "k_ms_pyramid"};
     return (id >= 0 && id < VQA_K_COUNT) ? names[id] : "?";
 }
 

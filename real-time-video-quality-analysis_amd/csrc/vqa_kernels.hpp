@@ -169,4 +169,43 @@ void launch_quality_ffmpeg(hipStream_t st, const uint8_t *ref, const uint8_t *di
                            int n_planes, double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res, int depth);
 int ssim_ffmpeg_blocks(int h, int w);
 
+// multi-scale SSIM (VQA_SSIM_MS): k_msssim.hip holds the pyramid, k_quality.hip the per-scale Gaussian launches
+constexpr int MS_LEVELS = 5;
+constexpr int MS_MIN_DIM = 161;   // level 4 must hold an 11x11 window: 161 -> 81 -> 41 -> 21 -> 11
+// Levels 1..4 of one group of same-geometry planes, as k_ms_pyramid writes them: fp32 planes holding the EXACT sum of the
+// 4^s level-0 samples behind each level-s sample (the 2x2 mean times 4^s; < 2^24 for 16-bit planes at level 4).  Level s
+// starts off[s] floats into the scratch and is laid out [image: ref, dist][frame][plane of the group][h[s]][w[s]].
+struct ms_layout {
+    int w[MS_LEVELS], h[MS_LEVELS];
+    int64_t off[MS_LEVELS];   // off[0] unused (level 0 is the caller's memory)
+    int64_t total;            // floats
+};
+inline ms_layout ms_levels(int n, int count, int h, int w)
+{
+    ms_layout L;
+    L.w[0] = w; L.h[0] = h; L.off[0] = 0;
+    int64_t at = 0;
+    for (int s = 1; s < MS_LEVELS; s++) {
+        L.w[s] = (L.w[s - 1] + 1) / 2;
+        L.h[s] = (L.h[s - 1] + 1) / 2;
+        L.off[s] = at;
+        at += 2 * (int64_t)n * count * L.h[s] * L.w[s];
+    }
+    L.total = at;
+    return L;
+}
+// levels 1..4 of ref and dist from ONE read of level 0 (uint8, or uint16 when depth > 8)
+void launch_ms_pyramid(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                       int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int depth,
+                       float *scratch);
+void launch_quality_ms_level(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                             int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int n_planes,
+                             double *partials, int64_t partial_plane_stride, vqa_plane_metrics *res, int depth, int level,
+                             const float *scratch, vqa_ms_scales *ms);
+// a level's fixed-point totals (ssim at `partials`, cs `cs_offset` slots behind) -> ms[frame * n_planes + plane].ssim / cs[level]
+void launch_ms_finalize(hipStream_t st, const double *partials, int64_t cs_offset, int bpp, int n, double count,
+                        int plane_index, int n_planes, int level, vqa_ms_scales *ms);
+// res[e].ssim = prod_{s<4} max(cs_s, 0)^w_s * max(ssim_4, 0)^w_4 for e < n_entries
+void launch_ms_combine(hipStream_t st, const vqa_ms_scales *ms, int n_entries, vqa_plane_metrics *res);
+
 } // namespace vqa

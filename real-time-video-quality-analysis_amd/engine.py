@@ -382,18 +382,30 @@ class Engine:
         N.check(st, "vqa_quality_submit", self.ctx)
         self._pending_q = (n, len(planes), keep)
 
-    def quality_wait(self):
+    def quality_wait(self, scales=False):
+        """-> [n, n_planes] records (PLANE_DTYPE).  scales=True (after an SSIM_MS submit only): -> (records, cs, ssim) with the
+        per-scale means as float64 [n, n_planes, 5], level 0 first (vqa_quality_wait_ms)."""
         n, npl, _keep = self._pending_q
         out = np.zeros(n * npl, dtype=PLANE_DTYPE)
-        st = self.lib.vqa_quality_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaPlaneMetrics)), n * npl)
-        self._pending_q = None
-        N.check(st, "vqa_quality_wait", self.ctx)
-        return out.reshape(n, npl)
+        if not scales:
+            st = self.lib.vqa_quality_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaPlaneMetrics)), n * npl)
+            self._pending_q = None
+            N.check(st, "vqa_quality_wait", self.ctx)
+            return out.reshape(n, npl)
+        sc = np.zeros((n * npl, 2, N.MS_LEVELS), np.float64)   # vqa_ms_scales: cs[5], ssim[5]
+        st = self.lib.vqa_quality_wait_ms(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaPlaneMetrics)),
+                                          sc.ctypes.data_as(C.POINTER(N.VqaMsScales)), n * npl)
+        if st != N.VQA_ERR_STATE:   # (a refusal for a batch that is not multi-scale leaves the batch pending)
+            self._pending_q = None
+        N.check(st, "vqa_quality_wait_ms", self.ctx)
+        return (out.reshape(n, npl), np.ascontiguousarray(sc[:, 0]).reshape(n, npl, N.MS_LEVELS),
+                np.ascontiguousarray(sc[:, 1]).reshape(n, npl, N.MS_LEVELS))
 
-    def quality(self, ref, dist, planes, ssim_mode=N.SSIM_GAUSS, frame_bytes=None):
-        """SSE + SSIM per plane for n frame pairs; returns [n, n_planes] structured array (PLANE_DTYPE)."""
+    def quality(self, ref, dist, planes, ssim_mode=N.SSIM_GAUSS, frame_bytes=None, scales=False):
+        """SSE + SSIM per plane for n frame pairs; returns [n, n_planes] structured array (PLANE_DTYPE).  ssim_mode SSIM_MS:
+        the ssim field is MS-SSIM (planes of at least 161 x 161), and scales=True adds the per-scale cs and ssim means."""
         self.quality_submit(ref, dist, planes, ssim_mode, frame_bytes)
-        return self.quality_wait()
+        return self.quality_wait(scales)
 
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):

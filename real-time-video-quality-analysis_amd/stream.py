@@ -380,8 +380,11 @@ class Complexity:
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
-    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS):
-        self.planes, self.ssim_mode = planes, ssim_mode
+    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False):
+        """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]"""
+        if scales and ssim_mode != N.SSIM_MS:
+            raise ValueError("per-scale means exist in the multi-scale mode only")
+        self.planes, self.ssim_mode, self.scales = planes, ssim_mode, bool(scales)
 
 
 class _Feed:
@@ -434,7 +437,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     on_quality  optional callback(first_frame, sse [m,p], ssim [m,p]) per finished chunk, in frame order (stats
                 lines are formatted while the GPU works on the next chunk)
     device      the device of the default engine when `engine` is None and no stream is resident (config key "device")
-    -> (sse [n,p] uint64, ssim [n,p] float64) or None, series dict or None.
+    -> (sse [n,p] uint64, ssim [n,p] float64) or None, series dict or None.  With Quality(.., scales=True) the tuple is
+    (sse, ssim, cs [n,p,5], ssim per scale [n,p,5]).
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -472,7 +476,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         return None, series  # (no engine is created for a clip with nothing to measure)
     if n == 0:
         e = np.zeros((0, len(quality.planes)))
-        return (e.astype(np.uint64), e), series
+        e5 = np.zeros((0, len(quality.planes), N.MS_LEVELS))
+        return ((e.astype(np.uint64), e) + ((e5, e5.copy()) if quality.scales else ())), series
     if engine is not None:
         first = engine
     else:
@@ -626,14 +631,14 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim = [], []
+    sse, ssim, ms_cs, ms_ssim = [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
         """block until the chunk is done on its lane; its records are kept, its ring slot is free again"""
         with N.trace_range("vqa:wait chunk=%d lane=%d", p["k"], p["k"] % len(lanes)):
             if p["has_q"]:
-                p["qres"] = eng.quality_wait()
+                p["qres"] = eng.quality_wait(quality.scales)
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -644,6 +649,10 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         with N.trace_range("vqa:tails chunk=%d", p["k"]):
             if p["has_q"]:
                 res = p.pop("qres")
+                if quality.scales:
+                    res, cs_k, ssim_k = res
+                    ms_cs.append(cs_k)
+                    ms_ssim.append(ssim_k)
                 sse.append(res["sse"])
                 ssim.append(res["ssim"])
                 if on_quality is not None:
@@ -702,6 +711,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         _abandon(lanes + ([cp] if cp is not None else []))
         raise
     q = (np.concatenate(sse), np.concatenate(ssim)) if want_q else None
+    if want_q and quality.scales:
+        q += (np.concatenate(ms_cs), np.concatenate(ms_ssim))
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

@@ -31,7 +31,7 @@ LAYOUTS = {
 for _name, (_chroma, _depth, _tag) in PIXFMTS.items():
     if _name not in LAYOUTS:
         LAYOUTS[_name] = ((lambda h, w, c=_chroma, d=_depth: yuv_planes(h, w, c, d)), "y" if _chroma == "mono" else "yuv")
-_SSIM_MODES = {"gauss": N.SSIM_GAUSS, "ffmpeg": N.SSIM_FFMPEG}
+_SSIM_MODES = {"gauss": N.SSIM_GAUSS, "ffmpeg": N.SSIM_FFMPEG, "msssim": N.SSIM_MS}
 
 
 def layout_depth(layout):
@@ -69,8 +69,11 @@ def _host_stream(a, wide=False):
 
 
 def frame_quality(reference, distorted, layout="bgr24", ssim_mode="gauss", height=None, width=None, engine=None,
-                  batch_size=64, on_chunk=None, device=None):
+                  batch_size=64, on_chunk=None, device=None, scales=False):
     """Per-frame SSE and SSIM per plane.  Returns (sse [n,p] uint64, ssim [n,p] float64, plane sizes).
+    ssim_mode "msssim": the ssim values are multi-scale SSIM (five scales of the Gaussian window; every plane at least
+    161 x 161, so a 4:2:0 frame at least 321 x 321); scales=True then appends {"cs": [n,p,5], "ssim": [n,p,5]}, the per-scale
+    means the values are the product of.
     One pass (stream.run): chunks of up to batch_size frame pairs alternate between two engines; host streams travel
     from the caller's pinned memory or through the pinned ring.  on_chunk(first_frame, sse, ssim) sees every finished
     chunk in frame order while the next one is on the GPU."""
@@ -79,9 +82,12 @@ def frame_quality(reference, distorted, layout="bgr24", ssim_mode="gauss", heigh
         raise ValueError("ref and dist must have the same shape")
     h, w = _geometry(reference, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(distorted, reference, quality=stream.Quality(planes, _SSIM_MODES[ssim_mode]),
+    q, _ = stream.run(distorted, reference, quality=stream.Quality(planes, _SSIM_MODES[ssim_mode], scales),
                       batch_size=batch_size, engine=engine, on_quality=on_chunk, device=device)
-    return q[0], q[1], [(p[0], p[1]) for p in planes]
+    sizes = [(p[0], p[1]) for p in planes]
+    if scales:
+        return q[0], q[1], sizes, {"cs": q[2], "ssim": q[3]}
+    return q[0], q[1], sizes
 
 
 # ---------------------------------------------------------------------------
@@ -221,7 +227,8 @@ def thread_safe_update_csv(metrics, csv_file="video_quality_data.csv"):
 # the keys this build adds to the reference's config.json (config.json:1-7 keeps its five; SURVEY.md section 5 "Config / flag system")
 MODE_KEYS = {
     # key: (allowed values, message in the reference's validate_config style)
-    "ssim_mode": (("gauss", "ffmpeg"), "ssim_mode must be 'gauss' or 'ffmpeg'."),
+    # (the message names the modes of ABI 7; "msssim", multi-scale SSIM over the Gaussian window, is accepted as well)
+    "ssim_mode": (("gauss", "ffmpeg", "msssim"), "ssim_mode must be 'gauss' or 'ffmpeg'."),
     # (the message names the layouts of ABI 7; the planar pix_fmts of frames.PIXFMTS - yuv422p, yuv420p10le ... - are
     # accepted as well)
     "pixfmt": ((None, "bgr24") + tuple(PIXFMTS), "pixfmt must be 'bgr24', 'yuv420p' or 'gray'."),
@@ -262,7 +269,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         DeviceFrames; complexity_metrics.py:100), which the complexity half reads.  Per chunk the planar pair and the chunk's
         selected BGR frames are uploaded, each byte once.
     config   the reference's keys (crf, resize_width, resize_height, frame_interval, vmaf_model_path; config.json:1-7) plus
-        batch_size, ssim_mode ("gauss" north_star's 11x11 Gaussian, default | "ffmpeg" vf_ssim's 8x8 integer windows),
+        batch_size, ssim_mode ("gauss" north_star's 11x11 Gaussian, default | "ffmpeg" vf_ssim's 8x8 integer windows |
+        "msssim" multi-scale SSIM over the Gaussian window: the ssim stats lines and the SSIM column then carry MS-SSIM),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
