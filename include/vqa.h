@@ -208,6 +208,18 @@ typedef struct vqa_ms_scales {
     double ssim[5];  /* mean of the SSIM map of each level                                                   */
 } vqa_ms_scales;
 
+/* VIF (visual information fidelity, Sheikh & Bovik 2006, pixel domain) of one plane pair on four scales: the vif_scale0..3
+ * features of VMAF (vqa_vif_submit / vqa_vif_wait; the definition is stated there).  Level 0 is the plane, level 3 the
+ * coarsest.  num and den are the device's integer totals times 2^-27: every per-sample term is rounded to 2^-27 and summed in
+ * signed 64 bits.  A term is below 64 in magnitude for any 16-bit input (s1 < 2^30 and g <= 100 give num < 43; samples inside
+ * their depth's range give s1 <= 2^14 and num < 27; 1 - s2 smi may be slightly negative), so a plane of 2^28 samples sums to
+ * less than 2^61 and cannot overflow.  Integer sums are associative: the same pair gives the same bits in any batch.      */
+typedef struct vqa_vif_metrics {
+    double num[4], den[4]; /* sum over the level of the per-sample numerator / denominator terms     */
+    double scale[4];       /* num[s] / den[s] (1 when den[s] == 0): libvmaf's vif_scale0..3          */
+    double vif;            /* sum_s num[s] / sum_s den[s] (1 when the denominator is 0)              */
+} vqa_vif_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -296,6 +308,40 @@ VQA_API int vqa_quality_wait(vqa_ctx *ctx, vqa_plane_metrics *out, int n_entries
  * when scales is given and the pending submit was not a VQA_SSIM_MS one.  (vqa_quality_wait serves an MS submit as well.) */
 VQA_API int vqa_quality_wait_ms(vqa_ctx *ctx, vqa_plane_metrics *out, vqa_ms_scales *scales, int n_entries);
 
+/* ---- VIF on four scales (the model-free part of the reference's libvmaf step, video_processing.py:270-297) ----
+ * For one plane pair (ref R, dist D, `depth` bits, h x w), in fp32 on the device:
+ *   samples   x = R / 2^(depth-8) - 128, y = D / 2^(depth-8) - 128 (exact at every depth; samples above 2^depth - 1 are read
+ *             as they are).
+ *   filter    of scale s = 0..3: n_s = 2^(4-s) + 1 taps (17, 9, 5, 3), t[k] = exp(-(k - n_s/2)^2 / (2 (n_s/5)^2)), n_s/2 the
+ *             integer half width, normalised to sum 1; separable, columns (vertical) first, then rows.
+ *   borders   an index i < 0 reads -i; an index i >= n reads 2n - i - 1.  Every level keeps its full size.
+ *   levels    level 0 is (x, y); level s > 0 is level s-1 filtered with the filter OF SCALE s, kept at even rows and even
+ *             columns: dims floor(dim / 2).
+ *   per level with its filter F: mu1 = F(x), mu2 = F(y), s1 = max(F(xx) - mu1^2, 0), s2 = max(F(yy) - mu2^2, 0),
+ *             s12 = F(xy) - mu1 mu2; then per sample, in this order, eps = 1e-10, nsq = 2, smi = 4 / 255^2:
+ *               g = s12 / (s1 + eps); sv = s2 - g s12;
+ *               if s1 < eps: g = 0, sv = s2, s1 = 0;  if s2 < eps: g = 0, sv = 0;  if g < 0: sv = s2, g = 0;
+ *               sv = max(sv, eps); g = min(g, 100);
+ *               num = log2(1 + g^2 s1 / (sv + nsq)), den = log2(1 + s1 / nsq);  if s12 < 0: num = 0;
+ *               if s1 < nsq: num = 1 - s2 smi, den = 1.
+ *   results   num_s = sum num, den_s = sum den, scale_s = num_s / den_s, vif = sum_s num_s / sum_s den_s.
+ * This is libvmaf's float `vif` feature at its default options (vif_enhn_gain_limit 100, vif_kernelscale 1) as the project
+ * states it; it is pinned against the float64 restatement in tests/vif_reference.py (1e-4 on every scale), not against
+ * libvmaf's binary.
+ * The contract of vqa_quality_submit: asynchronous, the same plane descriptors, depths (one per submit), alignment rules and
+ * failure guarantee.  Every plane must be at least 16 x 16 (level 3 is then 2 x 2 and every reflection stays inside its
+ * level): VQA_ERR_UNSUPPORTED below.  VQA_ERR_STATE while a VIF batch is pending.  A VIF batch is a batch of its own: it may
+ * be in flight next to a quality and a complexity batch of the same ctx (one upload then serves PSNR / SSIM and VIF), and
+ * each wait collects its own kind only - vqa_quality_wait with only a VIF batch pending, and vqa_vif_wait with only a
+ * quality batch pending, are VQA_ERR_STATE and leave that batch pending.
+ * Scratch on the device: 2.7 bytes per pixel of the largest group of same-geometry planes of a batch (levels 1..3 of both
+ * images as fp32: 2 x 4 x (1/4 + 1/16 + 1/64)), kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_vif_wait: n * n_planes entries, frame-major.                                                             */
+VQA_API int vqa_vif_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                           int64_t ref_frame_stride, int64_t dist_frame_stride,
+                           const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_vif_wait(vqa_ctx *ctx, vqa_vif_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -310,7 +356,11 @@ enum vqa_kernel_id {
     VQA_K_ORB = 9,       /* FAST-9/16 + NMS on the 64x64 thumbnail's centre */
     VQA_K_FARNEBACK = 10, /* the whole Farneback pyramid (about 30 launches per chunk of pairs) */
     VQA_K_MS_PYRAMID = 11, /* VQA_SSIM_MS: levels 1..4 of both images from one read of level 0 */
-    VQA_K_COUNT = 12
+    VQA_K_COUNT = 12,        /* the ids above, as ABI 8 first shipped them: kept at 12 for callers (and tests) that size
+                                arrays by it; the ids below were added later and lie beyond it                        */
+    VQA_K_VIF = 12,          /* vqa_vif_submit: the per-level statistic (four entries per group of same-geometry planes) */
+    VQA_K_VIF_DECIMATE = 13, /* vqa_vif_submit: level s from level s - 1 (three entries per group)                    */
+    VQA_K_COUNT_ALL = 14     /* every id vqa_profile_read and vqa_kernel_name know: 0 .. VQA_K_COUNT_ALL - 1           */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

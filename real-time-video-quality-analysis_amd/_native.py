@@ -38,6 +38,7 @@ M_ALL = 0x7F
 
 (K_GRAY_HIST, K_RESIZE, K_DCT8, K_DCT_FULL, K_CANNY_NMS, K_CANNY_HYST, K_SAD, K_SSIM_GAUSS, K_SSIM_FFMPEG, K_ORB,
  K_FARNEBACK, K_MS_PYRAMID, K_COUNT) = range(13)
+K_VIF, K_VIF_DECIMATE, K_COUNT_ALL = 12, 13, 14   # added beyond K_COUNT (include/vqa.h: VQA_K_COUNT stays 12)
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -47,6 +48,8 @@ SSIM_GAUSS, SSIM_FFMPEG, SSIM_MS = 0, 1, 2
 MS_LEVELS = 5
 MS_MIN_DIM = 161   # SSIM_MS: level 4 of every plane must hold an 11x11 window (161 -> 81 -> 41 -> 21 -> 11)
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+VIF_LEVELS = 4
+VIF_MIN_DIM = 16   # vqa_vif_submit: level 3 of a 16 x 16 plane is 2 x 2, every reflection stays inside its level
 MOTION_SAD, MOTION_FARNEBACK = 0, 1
 
 
@@ -88,6 +91,10 @@ class VqaMsScales(C.Structure):
     _fields_ = [("cs", C.c_double * 5), ("ssim", C.c_double * 5)]
 
 
+class VqaVifMetrics(C.Structure):
+    _fields_ = [("num", C.c_double * 4), ("den", C.c_double * 4), ("scale", C.c_double * 4), ("vif", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -119,6 +126,9 @@ SIGNATURES = {
                                      C.POINTER(VqaPlaneDesc), C.c_int, C.c_int]),
     "vqa_quality_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaPlaneMetrics), C.c_int]),
     "vqa_quality_wait_ms": (C.c_int, [C.c_void_p, C.POINTER(VqaPlaneMetrics), C.POINTER(VqaMsScales), C.c_int]),
+    "vqa_vif_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                 C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_vif_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaVifMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

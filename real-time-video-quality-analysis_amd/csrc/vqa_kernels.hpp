@@ -208,4 +208,39 @@ void launch_ms_finalize(hipStream_t st, const double *partials, int64_t cs_offse
 // res[e].ssim = prod_{s<4} max(cs_s, 0)^w_s * max(ssim_4, 0)^w_4 for e < n_entries
 void launch_ms_combine(hipStream_t st, const vqa_ms_scales *ms, int n_entries, vqa_plane_metrics *res);
 
+// VIF on four scales (vqa_vif_submit): k_vif.hip
+constexpr int VIF_LEVELS = 4;
+constexpr int VIF_MIN_DIM = 16;   // level 3 of a 16 x 16 plane is 2 x 2: every reflection stays inside its level
+// Levels 1..3 of one group of same-geometry planes, as k_vif_decimate writes them: centred fp32 samples, dims floor(dim / 2)
+// per level.  Level s starts off[s] floats into the scratch and is laid out [image: ref, dist][frame][plane of the group][h[s]][w[s]].
+struct vif_layout {
+    int w[VIF_LEVELS], h[VIF_LEVELS];
+    int64_t off[VIF_LEVELS];   // off[0] unused (level 0 is the caller's memory)
+    int64_t total;             // floats
+};
+inline vif_layout vif_levels(int n, int count, int h, int w)
+{
+    vif_layout L;
+    L.w[0] = w; L.h[0] = h; L.off[0] = 0;
+    int64_t at = 0;
+    for (int s = 1; s < VIF_LEVELS; s++) {
+        L.w[s] = L.w[s - 1] / 2;
+        L.h[s] = L.h[s - 1] / 2;
+        L.off[s] = at;
+        at += 2 * (int64_t)n * count * L.h[s] * L.w[s];
+    }
+    L.total = at;
+    return L;
+}
+// level `level` (1..3) of both images from level - 1, filtered with the taps of scale `level`, even rows and columns only
+void launch_vif_decimate(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                         int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int depth,
+                         int level, float *scratch);
+// one level's num / den, added to acc[((frame * n_planes + plane) * 4 + level) * 2 + {0, 1}] in 2^-27 fixed point (acc zeroed
+// by the caller; integer atomics: the totals do not depend on the launch geometry or the order of the workgroups)
+void launch_vif_stats(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                      int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int n_planes,
+                      int depth, int level, const float *scratch, long long *acc);
+void launch_vif_finalize(hipStream_t st, const long long *acc, int n_entries, vqa_vif_metrics *res);
+
 } // namespace vqa

@@ -29,7 +29,10 @@ FRAME_DTYPE = np.dtype([
 ], align=True)
 PLANE_DTYPE = np.dtype([("sse", np.uint64), ("ssim", np.float64)], align=True)
 assert FRAME_DTYPE.itemsize == C.sizeof(N.VqaFrameMetrics), (FRAME_DTYPE.itemsize, C.sizeof(N.VqaFrameMetrics))
+VIF_DTYPE = np.dtype([("num", np.float64, (4,)), ("den", np.float64, (4,)), ("scale", np.float64, (4,)), ("vif", np.float64)],
+                     align=True)
 assert PLANE_DTYPE.itemsize == C.sizeof(N.VqaPlaneMetrics)
+assert VIF_DTYPE.itemsize == C.sizeof(N.VqaVifMetrics)
 
 
 class DeviceFrames:
@@ -235,10 +238,11 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend, wait in (("_pending_q", self.quality_wait), ("_pending_c", self.complexity_wait)):
+        for pend, wait in (("_pending_q", self.quality_wait), ("_pending_v", self.vif_wait),
+                           ("_pending_c", self.complexity_wait)):
             try:
                 if getattr(self, pend, None):
                     wait()
@@ -353,6 +357,14 @@ class Engine:
         """planes: (width, height, offset, row_stride, pixel_step[, bit_depth]) per plane, in bytes.  8-bit planes read uint8
         frames; 9..16-bit planes (yuv_planes(.., depth=10) ...) read uint16 frames (host arrays or DeviceFrames of itemsize 2),
         passed through as they are: a frame of the other sample type is a ValueError, not a cast."""
+        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        descs = plane_descs(planes)
+        st = self.lib.vqa_quality_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes), ssim_mode)
+        N.check(st, "vqa_quality_submit", self.ctx)
+        self._pending_q = (n, len(planes), keep)
+
+    def _pair_args(self, ref, dist, planes, frame_bytes=None):
+        """the (ref, dist) pair of a quality / VIF submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         wide = planes_depth(planes) > 8
         if isinstance(ref, DeviceFrames):
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -377,10 +389,7 @@ class Engine:
             rfs = dfs = frame_bytes or (ref.nbytes // n)
             rp, dp, kind = ref.ctypes.data, dist.ctypes.data, N.VQA_MEM_HOST
             keep = (ref, dist)
-        descs = plane_descs(planes)
-        st = self.lib.vqa_quality_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes), ssim_mode)
-        N.check(st, "vqa_quality_submit", self.ctx)
-        self._pending_q = (n, len(planes), keep)
+        return rp, dp, kind, n, rfs, dfs, keep
 
     def quality_wait(self, scales=False):
         """-> [n, n_planes] records (PLANE_DTYPE).  scales=True (after an SSIM_MS submit only): -> (records, cs, ssim) with the
@@ -407,6 +416,31 @@ class Engine:
         self.quality_submit(ref, dist, planes, ssim_mode, frame_bytes)
         return self.quality_wait(scales)
 
+    # ---- VIF ---------------------------------------------------------------
+    def vif_submit(self, ref, dist, planes, frame_bytes=None):
+        """VIF on four scales for n frame pairs (vqa_vif_submit): the arrays / DeviceFrames and plane tuples of
+        quality_submit; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit of the same frames
+        before either is waited for."""
+        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        descs = plane_descs(planes)
+        st = self.lib.vqa_vif_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes))
+        N.check(st, "vqa_vif_submit", self.ctx)
+        self._pending_v = (n, len(planes), keep)
+
+    def vif_wait(self):
+        """-> [n, n_planes] records (VIF_DTYPE): num[4], den[4], scale[4] (libvmaf's vif_scale0..3) and vif."""
+        n, npl, _keep = self._pending_v
+        out = np.zeros(n * npl, dtype=VIF_DTYPE)
+        st = self.lib.vqa_vif_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaVifMetrics)), n * npl)
+        self._pending_v = None
+        N.check(st, "vqa_vif_wait", self.ctx)
+        return out.reshape(n, npl)
+
+    def vif(self, ref, dist, planes, frame_bytes=None):
+        """VIF per plane on four scales for n frame pairs; returns [n, n_planes] structured array (VIF_DTYPE)."""
+        self.vif_submit(ref, dist, planes, frame_bytes)
+        return self.vif_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -414,7 +448,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in range(N.K_COUNT):
+        for k in range(N.K_COUNT_ALL):
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

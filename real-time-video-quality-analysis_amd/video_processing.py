@@ -90,6 +90,39 @@ def frame_quality(reference, distorted, layout="bgr24", ssim_mode="gauss", heigh
     return q[0], q[1], sizes
 
 
+def frame_vif(reference, distorted, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame VIF per plane on four scales (Engine.vif through the one-pass pipeline of frame_quality).
+    Returns (scale [n,p,4] float64 - libvmaf's vif_scale0..3 -, vif [n,p] float64 - sum of the numerators over the sum of the
+    denominators of the four scales -, plane sizes).  Every plane at least 16 x 16."""
+    reference, distorted = _host_stream(reference, wide=True), _host_stream(distorted, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != distorted.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(distorted, reference, quality=stream.Quality(planes, vif="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    return q[-1]["scale"], q[-1]["vif"], [(p[0], p[1]) for p in planes]
+
+
+def write_vif_log(vmaf_log, scale):
+    """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
+    .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key: there is no model.
+    scale: [n, 4], the first (luma) plane's values."""
+    import json
+    scale = np.asarray(scale, np.float64).reshape(-1, N.VIF_LEVELS)
+    names = ["vif_scale%d" % s for s in range(N.VIF_LEVELS)]
+    frames = [{"frameNum": i, "metrics": {k: float(v) for k, v in zip(names, row)}} for i, row in enumerate(scale)]
+    pooled = {}
+    for s, k in enumerate(names):
+        x = scale[:, s]
+        if len(x):
+            pooled[k] = {"min": float(x.min()), "max": float(x.max()), "mean": float(x.mean()),
+                         "harmonic_mean": float(len(x) / np.sum(1.0 / (x + 1.0)) - 1.0)}
+    with open(vmaf_log, "w") as f:
+        json.dump({"frames": frames, "pooled_metrics": pooled}, f, indent=1)
+        f.write("\n")
+
+
 # ---------------------------------------------------------------------------
 # FFmpeg-format stats lines, a chunk of frames at a time
 # ---------------------------------------------------------------------------
@@ -191,10 +224,13 @@ def _open_quality_stream(src, layout, height, width):
 
 
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
-                       layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None):
+                       layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
-    arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip)."""
+    arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
+    vif=True: the same pass (one upload per chunk) also measures VIF on four scales and writes vmaf_log in libvmaf's JSON
+    shape (write_vif_log: the first plane's vif_scale0..3 per frame and pooled; no vmaf value).  Without it vmaf_log is not
+    written, as before."""
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     dist, layout_d, _, _ = _open_quality_stream(distorted_video, layout, height, width)
     if layout_d != layout:
@@ -202,7 +238,15 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
-        frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
+        if vif:
+            rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
+            if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
+                raise ValueError("ref and dist must have the same shape")
+            q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=True),
+                              batch_size=batch_size, on_quality=wr, device=device)
+            write_vif_log(vmaf_log, q[-1]["scale"][:, 0])
+        else:
+            frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
         wr.close()
     return None
@@ -244,6 +288,8 @@ def _check_mode_keys(config):
     dev = config.get("device")
     if dev is not None and (isinstance(dev, bool) or not isinstance(dev, int) or dev < 0):
         raise ValueError("device must be a non-negative integer.")
+    if "vif" in config and not isinstance(config["vif"], bool):
+        raise ValueError("vif must be true or false.")
     bs = config.get("batch_size", 100)
     if isinstance(bs, bool) or not isinstance(bs, int) or bs <= 0:
         raise ValueError("batch_size must be a positive integer.")
@@ -271,6 +317,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     config   the reference's keys (crf, resize_width, resize_height, frame_interval, vmaf_model_path; config.json:1-7) plus
         batch_size, ssim_mode ("gauss" north_star's 11x11 Gaussian, default | "ffmpeg" vf_ssim's 8x8 integer windows |
         "msssim" multi-scale SSIM over the Gaussian window: the ssim stats lines and the SSIM column then carry MS-SSIM),
+        vif (true: the row gains VIF_scale0..3, the pooled means of the first plane's VIF on four scales; default false),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -288,6 +335,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     interval = config.get("frame_interval", 10)
     batch_size = config.get("batch_size", 100)
     ssim_mode = _SSIM_MODES[config.get("ssim_mode", "gauss")]
+    vif = config.get("vif", False)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -330,11 +378,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         planes = LAYOUTS[layout][0](h, w)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
-            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode),
+            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
+        if vif:
+            write_vif_log(vmaf_log, _q[-1]["scale"][:, 0])
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -368,6 +418,16 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             match = re.search(r"All:(\s*\d+\.\d+)", f.read())
             if match:
                 metrics["SSIM"] = float(match.group(1))
+    if os.path.isfile(vmaf_log):   # this build's JSON (write_vif_log): the pooled means; there is no VMAF value to add
+        import json
+        try:
+            with open(vmaf_log) as f:
+                pooled = json.load(f).get("pooled_metrics", {})
+        except (ValueError, AttributeError):   # not a JSON log (libvmaf writes XML by default): nothing to add
+            pooled = {}
+        for s in range(N.VIF_LEVELS):
+            if "vif_scale%d" % s in pooled:
+                metrics["VIF_scale%d" % s] = float(pooled["vif_scale%d" % s]["mean"])
     return metrics
 
 
@@ -390,7 +450,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif
 
 
 def main(argv=None):
