@@ -220,6 +220,24 @@ typedef struct vqa_vif_metrics {
     double vif;            /* sum_s num[s] / sum_s den[s] (1 when the denominator is 0)              */
 } vqa_vif_metrics;
 
+/* ADM (detail loss metric, Li et al. 2011, on a four-level db2 wavelet pyramid) of one plane pair: the adm2 and adm_scale0..3
+ * features of VMAF (vqa_adm_submit / vqa_adm_wait; the definition is stated there).  Scale 0 is the finest.
+ * Sums: per scale the device adds six sums of cubes over the pooled region (three bands, numerator and denominator).  A cube
+ * max(|rf r| - thr, 0)^3 or |rf o|^3 is below 242 at scale 0 and 4.7e7 at scale 3 for samples inside their depth's range
+ * (|band| <= 128 * 1.6731^(2 (s + 1)), rf <= 0.0457), and below 7.7e14 for ARBITRARY 16-bit samples (depth 9: 255 times the
+ * range); the region of scale s has at most 2^(28 - 2 (s + 1)) samples, so a total stays below 1e21.  That span (values of
+ * interest from 1e-9 up) does not fit one 64-bit fixed-point scale, so the sums are NOT integers: every workgroup owns a
+ * fixed 32 x 16 tile of the bands - the tiling depends on the plane's geometry alone -, adds its cubes in a fixed order
+ * (fp32 per thread, doubles across the workgroup) and stores one partial; the partials of a plane are then added in double in
+ * a fixed order.  The same pair therefore gives the same num / den bits at any place of any batch, from host or device memory.
+ * The cube roots and quotients are formed in double on the host by vqa_adm_wait.                                        */
+typedef struct vqa_adm_metrics {
+    double num[4], den[4]; /* sum over the three bands of cbrt(sum of cubes over the region) + cbrt(area / 32)  */
+    double scale[4];       /* num[s] / den[s] (den[s] > 0 always): libvmaf's adm_scale0..3                      */
+    double adm2;           /* sum_s num[s] / sum_s den[s] (each sum 0 below 1e-10 h w / (1920 * 1080); 1 when the
+                              denominator is 0)                                                                 */
+} vqa_adm_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -342,6 +360,54 @@ VQA_API int vqa_vif_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist
                            const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_vif_wait(vqa_ctx *ctx, vqa_vif_metrics *out, int n_entries);
 
+/* ---- ADM on four scales (the other model-free feature family of the reference's libvmaf step) ----
+ * For one plane pair (ref R, dist D, `depth` bits, h x w), in fp32 on the device:
+ *   samples   x = R / 2^(depth-8) - 128, y = D / 2^(depth-8) - 128 (samples above 2^depth - 1 are read as they are).
+ *   DWT       of a level, H x W -> four bands of ceil(H/2) x ceil(W/2), with the db2 taps
+ *               lo = ( 0.482962913144690,  0.836516303737469, 0.224143868041857, -0.129409522550921)
+ *               hi = (-0.129409522550921, -0.224143868041857, 0.836516303737469, -0.482962913144690):
+ *             output index i reads the input indices |2i-1|, 2i, 2i+1, 2i+2, paired with taps 0..3; an index k >= n reads
+ *             2n - k - 1.  The vertical pass comes first and gives L = lo, Hh = hi; the horizontal pass then gives a = lo(L),
+ *             v = hi(L), h = lo(Hh), d = hi(Hh).  Scale s + 1 is the DWT of the a band of scale s, for each image.
+ *   decoupling per sample, (oh, ov, od) from ref and (th, tv, td) from dist: for each band k = clamp(t / (o + 1e-30), 0, 1),
+ *             r = k o;  dp = oh th + ov tv;  flag = dp >= 0 && dp^2 >= cos^2(1 degree) (oh^2 + ov^2)(th^2 + tv^2);
+ *             if flag && r > 0: r = min(100 r, t);  if flag && r < 0: r = max(100 r, t)  (h, v and d alike);
+ *             a_band = t - r.
+ *   CSF       rf_s[h] = rf_s[v] = 1 / Q(s, 1), rf_s[d] = 1 / Q(s, 2),
+ *             Q(l, th) = 2 * 0.495 * 10^(0.466 log10(2^(l+1) * 0.401 * g[th] / rho)^2) / A[l][th], rho = 3 * 1080 * pi / 180,
+ *             g = (1.501, 1, 0.534, 1), A (the 7/9 basis amplitudes), rows l = 0..3, columns th = 0..3:
+ *               (0.62171, 0.67234, 0.72709, 0.67234) (0.34537, 0.41317, 0.49428, 0.41317)
+ *               (0.18004, 0.22727, 0.28688, 0.22727) (0.091401, 0.11792, 0.15214, 0.11792);
+ *             (rf[h], rf[d]) per scale: (0.0173815342, 0.0058906866) (0.0319848145, 0.0142990667) (0.0433726647, 0.0243969129)
+ *             (0.0456734100, 0.0313127351).
+ *   masking   per sample thr = sum_bands [ |rf a_band| / 15 at the sample + (sum over its 8 neighbours of |rf a_band|) / 30 ];
+ *             neighbour index -1 reads 1 and index n reads n - 1 (VIF's border rule); one thr serves the three bands.
+ *   region    band dims (bh, bw): left = (int)(bw * 0.1 - 0.5), top = (int)(bh * 0.1 - 0.5); rows [top, bh - top), columns
+ *             [left, bw - left); area = their product.
+ *   pooling   num_s = sum_bands [ cbrt(sum_region max(|rf r| - thr, 0)^3) + cbrt(area / 32) ],
+ *             den_s = sum_bands [ cbrt(sum_region |rf o|^3) + cbrt(area / 32) ].
+ *   results   scale_s = num_s / den_s;  adm2 = N / D with N = sum_s num_s, D = sum_s den_s, each set to 0 when below
+ *             1e-10 h w / (1920 * 1080); adm2 = 1 when D = 0.  Enhancement counts: a sharpened image may score above 1.
+ * This is libvmaf's float `adm` feature at its default options (adm_enhn_gain_limit 100, adm_norm_view_dist 3,
+ * adm_ref_display_height 1080, adm_csf_mode 0) as the project states it; it is pinned against the float64 restatement in
+ * tests/adm_reference.py (1e-4 on every scale and on adm2), not against libvmaf's binary.  The angle test of the decoupling
+ * is a discontinuity: where fp32 rounding decides a sample's flag differently from float64, a small band moves by that
+ * sample's whole contribution; the tests widen the bar for such a (case, scale) by the spread the reference reports when
+ * the flags within 2^-20 of the boundary are forced either way (never beyond 2e-3; the precedent is Farneback's).
+ * The contract of vqa_vif_submit: asynchronous, the same plane descriptors, depths (one per submit), alignment rules and
+ * failure guarantee.  Every plane must be at least 16 x 16 (the bands of scale 3 are then 1 x 1): VQA_ERR_UNSUPPORTED below.
+ * VQA_ERR_STATE while an ADM batch is pending.  An ADM batch is a batch of its own: it may be in flight next to a quality, a
+ * VIF and a complexity batch of the same ctx (one upload then serves all), and each wait collects its own kind only -
+ * vqa_adm_wait with only a quality or VIF batch pending, and vqa_quality_wait / vqa_vif_wait with only an ADM batch
+ * pending, are VQA_ERR_STATE and leave that batch pending.
+ * Scratch on the device: 2.7 bytes per pixel of the largest group of same-geometry planes of a batch (the a bands of scales
+ * 0..2 of both images as fp32: 2 x 4 x (1/4 + 1/16 + 1/64)) plus 48 bytes per 32 x 16 band tile, kept by the ctx until
+ * vqa_trim / vqa_destroy.  out of vqa_adm_wait: n * n_planes entries, frame-major.                                       */
+VQA_API int vqa_adm_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                           int64_t ref_frame_stride, int64_t dist_frame_stride,
+                           const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_adm_wait(vqa_ctx *ctx, vqa_adm_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -360,7 +426,12 @@ enum vqa_kernel_id {
                                 arrays by it; the ids below were added later and lie beyond it                        */
     VQA_K_VIF = 12,          /* vqa_vif_submit: the per-level statistic (four entries per group of same-geometry planes) */
     VQA_K_VIF_DECIMATE = 13, /* vqa_vif_submit: level s from level s - 1 (three entries per group)                    */
-    VQA_K_COUNT_ALL = 14     /* every id vqa_profile_read and vqa_kernel_name know: 0 .. VQA_K_COUNT_ALL - 1           */
+    VQA_K_COUNT_ALL = 14,    /* the ids above: 0 .. VQA_K_COUNT_ALL - 1, as VIF shipped them (kept at 14 for callers and
+                                tests that rely on id 14 being unknown); ids 14 and 15 stay unnamed                    */
+    VQA_K_ADM = 16,          /* vqa_adm_submit: one scale - DWT, decoupling, masking, cube sums (four entries per group)  */
+    VQA_K_ADM_REDUCE = 17,   /* vqa_adm_submit: the tile partials of a scale, added in a fixed order (four per group)     */
+    VQA_K_COUNT_EXT = 18     /* vqa_profile_read and vqa_kernel_name know 0 .. VQA_K_COUNT_ALL - 1 and VQA_K_ADM ..
+                                VQA_K_COUNT_EXT - 1                                                                    */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

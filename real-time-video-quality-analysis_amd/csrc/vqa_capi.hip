@@ -70,6 +70,10 @@ struct vqa_ctx {
     // vqa_vif_submit: levels 1..3 of the largest plane group seen; the integer totals; the records (device, pinned host)
     dbuf vif_pyr, vif_acc, vif_dev;
     void *vif_host = nullptr; size_t vif_host_cap = 0;
+    // vqa_adm_submit: the a bands of scales 0..2 of the largest plane group seen; one scale's tile partials; the six sums per
+    // (entry, scale) (device, pinned host)
+    dbuf adm_pyr, adm_part, adm_sums;
+    void *adm_host = nullptr; size_t adm_host_cap = 0;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -84,6 +88,8 @@ struct vqa_ctx {
     int pend_c = 0, pend_q = 0;
     bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
     int pend_v = 0;           // entries of the pending VIF batch (a batch of its own, next to pend_c and pend_q)
+    int pend_a = 0;           // entries of the pending ADM batch (likewise); its planes' sizes, for the host's cube roots
+    int pend_a_planes = 0, pend_a_w[4] = {0}, pend_a_h[4] = {0};
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -93,8 +99,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_COUNT_ALL] = {0};
-    int64_t prof_n[VQA_K_COUNT_ALL] = {0};
+    double prof_ms[VQA_K_COUNT_EXT] = {0};
+    int64_t prof_n[VQA_K_COUNT_EXT] = {0};
 };
 
 namespace {
@@ -771,7 +777,7 @@ int vqa_create(int device, vqa_ctx **out)
 int vqa_set_option(vqa_ctx *c, int option, int value)
 {
     if (!c) return VQA_ERR_INVALID;
-    if (c->pend_c || c->pend_q || c->pend_v) return VQA_ERR_STATE; // options apply to whole submits
+    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a) return VQA_ERR_STATE; // options apply to whole submits
     switch (option) {
     case VQA_OPT_OVERLAP: c->opt_overlap = value != 0; return VQA_OK;
     case VQA_OPT_HYST_STATS: c->opt_hyst_stats = value != 0; return VQA_OK;
@@ -807,7 +813,7 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
@@ -818,8 +824,9 @@ static void release_scratch(vqa_ctx *c)
     if (c->qres_host) (void)hipHostFree(c->qres_host);
     if (c->qms_host) (void)hipHostFree(c->qms_host);
     if (c->vif_host) (void)hipHostFree(c->vif_host);
-    c->res_host = c->qres_host = c->qms_host = c->vif_host = nullptr;
-    c->res_host_cap = c->qres_host_cap = c->qms_host_cap = c->vif_host_cap = 0;
+    if (c->adm_host) (void)hipHostFree(c->adm_host);
+    c->res_host = c->qres_host = c->qms_host = c->vif_host = c->adm_host = nullptr;
+    c->res_host_cap = c->qres_host_cap = c->qms_host_cap = c->vif_host_cap = c->adm_host_cap = 0;
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
 }
@@ -827,7 +834,7 @@ static void release_scratch(vqa_ctx *c)
 int vqa_trim(vqa_ctx *c)
 {
     if (!c) return VQA_ERR_INVALID;
-    if (c->pend_c || c->pend_q || c->pend_v) return VQA_ERR_STATE;
+    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a) return VQA_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     prof_collect(c);
@@ -1587,6 +1594,126 @@ int vqa_vif_wait(vqa_ctx *c, vqa_vif_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// ADM on four scales.  A batch of its own (pend_a), ordered by the stream like a VIF batch; the checks are vqa_vif_submit's.
+static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                           int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
+{
+    if (!c || !ref || !dist || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
+    if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
+    if (c->pend_a) return VQA_ERR_STATE;
+    int64_t span = 0;
+    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
+    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
+    const int bps = depth > 8 ? 2 : 1;
+    for (int p = 0; p < n_planes; p++) {
+        const vqa_plane_desc &d = planes[p];
+        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
+        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
+        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
+            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
+            return VQA_ERR_INVALID;
+        if (d.width < ADM_MIN_DIM || d.height < ADM_MIN_DIM) return VQA_ERR_UNSUPPORTED;
+        if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;   // the bound of the sums (vqa.h)
+        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
+        span = end > span ? end : span;
+    }
+    if (n > 1 && (ref_fs < span || dist_fs < span)) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    const uint8_t *dref = ref, *ddist = dist;
+    if (mem_kind == VQA_MEM_HOST) {
+        const size_t rs = (size_t)(n - 1) * ref_fs + span, ds = (size_t)(n - 1) * dist_fs + span;
+        int rc = ensure(c, c->qstage_ref, rs);
+        if (rc) return rc;
+        rc = ensure(c, c->qstage_dist, ds);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->qstage_ref.p, ref, rs, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->qstage_dist.p, dist, ds, hipMemcpyHostToDevice, st));
+        dref = (const uint8_t *)c->qstage_ref.p;
+        ddist = (const uint8_t *)c->qstage_dist.p;
+    }
+    const size_t nent = (size_t)n * n_planes;
+    const size_t sums_bytes = sizeof(double) * 6 * ADM_LEVELS * nent;
+    int rc = ensure(c, c->adm_sums, sums_bytes);
+    if (rc) return rc;
+    rc = ensure_pinned(c, c->adm_host, c->adm_host_cap, sums_bytes);
+    if (rc) return rc;
+    const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
+    const int nslice = n < QSLICE ? n : QSLICE;
+    // the band scratch and the partials serve one group of same-geometry planes (and one scale) at a time
+    size_t pyr = 0, part = 0;
+    for (int p = 0; p < n_planes; p++) {
+        int cnt = 0;
+        for (int q = 0; q < n_planes; q++) cnt += planes[q].width == planes[p].width && planes[q].height == planes[p].height;
+        const adm_layout L = adm_levels(nslice, cnt, planes[p].height, planes[p].width);
+        const size_t b = sizeof(float) * (size_t)L.total;
+        const size_t t = sizeof(double) * 6 * (size_t)nslice * cnt * adm_tiles(L.h[1], L.w[1]);
+        pyr = b > pyr ? b : pyr;
+        part = t > part ? t : part;
+    }
+    rc = ensure(c, c->adm_pyr, pyr);
+    if (rc) return rc;
+    rc = ensure(c, c->adm_part, part);
+    if (rc) return rc;
+    for (int a0 = 0; a0 < n; a0 += QSLICE) {
+        const int m = n - a0 < QSLICE ? n - a0 : QSLICE;
+        double *sums = (double *)c->adm_sums.p + (size_t)a0 * n_planes * 6 * ADM_LEVELS;
+        const uint8_t *sref = dref + (int64_t)a0 * ref_fs, *sdist = ddist + (int64_t)a0 * dist_fs;
+        bool done[4] = {false, false, false, false};
+        for (int p = 0; p < n_planes; p++) {
+            if (done[p]) continue;
+            int idx[4], cnt = 0;
+            for (int q = p; q < n_planes; q++) {
+                if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
+                    planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
+                    idx[cnt++] = q;
+                    done[q] = true;
+                }
+            }
+            for (int sc = 0; sc < ADM_LEVELS; sc++) {
+                {
+                    prof_scope ps_(c, VQA_K_ADM);
+                    launch_adm_scale(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, depth, sc, (float *)c->adm_pyr.p,
+                                     (double *)c->adm_part.p);
+                }
+                prof_scope pr_(c, VQA_K_ADM_REDUCE);
+                launch_adm_reduce(st, (const double *)c->adm_part.p, m, planes, idx, cnt, n_planes, sc, sums);
+            }
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->adm_host, c->adm_sums.p, sums_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_a = (int)nent;
+    c->pend_a_planes = n_planes;
+    for (int p = 0; p < n_planes; p++) { c->pend_a_w[p] = planes[p].width; c->pend_a_h[p] = planes[p].height; }
+    return VQA_OK;
+}
+
+int vqa_adm_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                   int64_t dist_fs, const vqa_plane_desc *planes, int n_planes)
+{
+    bool touched = false;
+    const int rc = adm_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, touched);
+    return drain_failed_submit(c, rc, touched);
+}
+
+int vqa_adm_wait(vqa_ctx *c, vqa_adm_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_a || n_entries != c->pend_a) return VQA_ERR_STATE;   // (a pending quality or VIF batch stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const double *sums = (const double *)c->adm_host;
+    for (int e = 0; e < n_entries; e++) {
+        const int p = e % c->pend_a_planes;
+        adm_finalize(sums + (size_t)e * 6 * ADM_LEVELS, c->pend_a_h[p], c->pend_a_w[p], out + e);
+    }
+    c->pend_a = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -1596,8 +1723,8 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_COUNT_ALL) return VQA_ERR_INVALID;
-    if (!c->pend_c && !c->pend_q && !c->pend_v) {
+    if (!c || id < 0 || id >= VQA_K_COUNT_EXT || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM)) return VQA_ERR_INVALID;
+    if (!c->pend_c && !c->pend_q && !c->pend_v && !c->pend_a) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         prof_collect(c);
     }
@@ -1613,6 +1740,8 @@ const char *vqa_kernel_name(int id)
                                              "k_canny_nms", "k_canny_hyst", "k_block_sad", "k_ssim_gauss",
                                              "k_ssim_ffmpeg", "k_orb64", "farneback(pyramid)", "k_ms_pyramid",
                                              "k_vif_stats", "k_vif_decimate"};
+    if (id == VQA_K_ADM) return "k_adm_scale";
+    if (id == VQA_K_ADM_REDUCE) return "k_adm_reduce";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

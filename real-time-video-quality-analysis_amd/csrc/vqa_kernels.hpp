@@ -243,4 +243,58 @@ void launch_vif_stats(hipStream_t st, const uint8_t *ref, const uint8_t *dist, i
                       int depth, int level, const float *scratch, long long *acc);
 void launch_vif_finalize(hipStream_t st, const long long *acc, int n_entries, vqa_vif_metrics *res);
 
+// ADM on four scales (vqa_adm_submit): k_adm.hip
+constexpr int ADM_LEVELS = 4;
+constexpr int ADM_MIN_DIM = 16;   // the bands of scale 3 of a 16 x 16 plane are 1 x 1
+// The input of every scale of one group of same-geometry planes: level 0 is the caller's planes, level s > 0 the a bands of scale
+// s - 1 as k_adm_scale writes them (fp32, dims ceil(dim / 2) per level); level 4 is never stored, its dims are the bands of
+// scale 3.  Level s starts off[s] floats into the scratch and is laid out [image: ref, dist][frame][plane of the group][h[s]][w[s]].
+struct adm_layout {
+    int w[ADM_LEVELS + 1], h[ADM_LEVELS + 1];
+    int64_t off[ADM_LEVELS];   // off[0] unused (level 0 is the caller's memory)
+    int64_t total;             // floats
+};
+inline adm_layout adm_levels(int n, int count, int h, int w)
+{
+    adm_layout L;
+    L.w[0] = w; L.h[0] = h; L.off[0] = 0;
+    int64_t at = 0;
+    for (int s = 1; s <= ADM_LEVELS; s++) {
+        L.w[s] = (L.w[s - 1] + 1) / 2;
+        L.h[s] = (L.h[s - 1] + 1) / 2;
+        if (s < ADM_LEVELS) {
+            L.off[s] = at;
+            at += 2 * (int64_t)n * count * L.h[s] * L.w[s];
+        }
+    }
+    L.total = at;
+    return L;
+}
+// workgroups (32 x 16 band samples each) that cover the bands of one plane at one scale: the tiling depends on nothing else
+inline int adm_tiles(int bh, int bw) { return ((bw + 31) / 32) * ((bh + 15) / 16); }
+// the pooled region of a bh x bw band: rows [top, bottom), columns [left, right)
+struct adm_region { int top, bottom, left, right; int64_t area; };
+inline adm_region adm_region_of(int bh, int bw)
+{
+    adm_region r;
+    r.left = (int)(bw * 0.1 - 0.5);
+    r.top = (int)(bh * 0.1 - 0.5);
+    r.right = bw - r.left;
+    r.bottom = bh - r.top;
+    r.area = (int64_t)(r.bottom - r.top) * (r.right - r.left);
+    return r;
+}
+// the contrast sensitivity weights of scale s: rf[h] = rf[v] = 1 / Q(s, 1), rf[d] = 1 / Q(s, 2) (include/vqa.h)
+void adm_rf(int scale, double *rf_hv, double *rf_d);
+// one scale of a group: reads level `scale`, writes the a bands (level scale + 1, scales 0..2) into `scratch` and one partial of six
+// doubles (num h, v, d; den h, v, d: sums of cubes over the region) per workgroup into part[frame][plane of the group][tile][6]
+void launch_adm_scale(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                      int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int depth, int scale,
+                      float *scratch, double *part);
+// the partials of that launch, added in a fixed order into sums[((frame * n_planes + plane) * 4 + scale) * 6 + k]
+void launch_adm_reduce(hipStream_t st, const double *part, int n, const vqa_plane_desc *planes, const int *idx, int count,
+                       int n_planes, int scale, double *sums);
+// six sums per scale -> the record: cube roots and quotients in double, on the host (h x w: the plane)
+void adm_finalize(const double *sums, int h, int w, vqa_adm_metrics *out);
+
 } // namespace vqa

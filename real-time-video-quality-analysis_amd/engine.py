@@ -33,6 +33,9 @@ VIF_DTYPE = np.dtype([("num", np.float64, (4,)), ("den", np.float64, (4,)), ("sc
                      align=True)
 assert PLANE_DTYPE.itemsize == C.sizeof(N.VqaPlaneMetrics)
 assert VIF_DTYPE.itemsize == C.sizeof(N.VqaVifMetrics)
+ADM_DTYPE = np.dtype([("num", np.float64, (4,)), ("den", np.float64, (4,)), ("scale", np.float64, (4,)), ("adm2", np.float64)],
+                     align=True)
+assert ADM_DTYPE.itemsize == C.sizeof(N.VqaAdmMetrics)
 
 
 class DeviceFrames:
@@ -238,10 +241,10 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend, wait in (("_pending_q", self.quality_wait), ("_pending_v", self.vif_wait),
+        for pend, wait in (("_pending_q", self.quality_wait), ("_pending_v", self.vif_wait), ("_pending_a", self.adm_wait),
                            ("_pending_c", self.complexity_wait)):
             try:
                 if getattr(self, pend, None):
@@ -441,6 +444,31 @@ class Engine:
         self.vif_submit(ref, dist, planes, frame_bytes)
         return self.vif_wait()
 
+    # ---- ADM ---------------------------------------------------------------
+    def adm_submit(self, ref, dist, planes, frame_bytes=None):
+        """ADM on four scales for n frame pairs (vqa_adm_submit): the arrays / DeviceFrames and plane tuples of
+        quality_submit; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit and a vif_submit of
+        the same frames before any of them is waited for."""
+        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        descs = plane_descs(planes)
+        st = self.lib.vqa_adm_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes))
+        N.check(st, "vqa_adm_submit", self.ctx)
+        self._pending_a = (n, len(planes), keep)
+
+    def adm_wait(self):
+        """-> [n, n_planes] records (ADM_DTYPE): num[4], den[4], scale[4] (libvmaf's adm_scale0..3) and adm2."""
+        n, npl, _keep = self._pending_a
+        out = np.zeros(n * npl, dtype=ADM_DTYPE)
+        st = self.lib.vqa_adm_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaAdmMetrics)), n * npl)
+        self._pending_a = None
+        N.check(st, "vqa_adm_wait", self.ctx)
+        return out.reshape(n, npl)
+
+    def adm(self, ref, dist, planes, frame_bytes=None):
+        """ADM per plane on four scales for n frame pairs; returns [n, n_planes] structured array (ADM_DTYPE)."""
+        self.adm_submit(ref, dist, planes, frame_bytes)
+        return self.adm_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -448,7 +476,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in range(N.K_COUNT_ALL):
+        for k in N.K_IDS:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

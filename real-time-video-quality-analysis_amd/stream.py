@@ -380,17 +380,24 @@ class Complexity:
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
-    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False):
+    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
-                returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM"""
+                returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
+        adm     True: likewise through the ADM kernels (Engine.adm_submit); the pass then returns (.., VIF records or None,
+                ADM records [n,p] (engine.ADM_DTYPE)); "only": no SSE / SSIM (with vif=True or "only": VIF and ADM alone)"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
             raise ValueError("vif must be False, True or 'only'")
         if vif == "only" and scales:
             raise ValueError("a VIF-only pass has no SSIM scales")
-        self.planes, self.ssim_mode, self.scales, self.vif = planes, ssim_mode, bool(scales), vif
+        if not (isinstance(adm, bool) or (isinstance(adm, str) and adm == "only")):
+            raise ValueError("adm must be False, True or 'only'")
+        if adm == "only" and scales:
+            raise ValueError("an ADM-only pass has no SSIM scales")
+        self.planes, self.ssim_mode, self.scales, self.vif, self.adm = planes, ssim_mode, bool(scales), vif, adm
+        self.ssim = vif != "only" and adm != "only"   # the pass measures SSE / SSIM
 
 
 class _Feed:
@@ -445,7 +452,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     device      the device of the default engine when `engine` is None and no stream is resident (config key "device")
     -> (sse [n,p] uint64, ssim [n,p] float64) or None, series dict or None.  With Quality(.., scales=True) the tuple is
     (sse, ssim, cs [n,p,5], ssim per scale [n,p,5]); with Quality(.., vif=True) the VIF records [n,p] (engine.VIF_DTYPE) are
-    appended as the last element, and with vif="only" sse and ssim are None.
+    appended as the last element, and with vif="only" sse and ssim are None.  With Quality(.., adm=True) two elements are
+    appended instead: the VIF records (None when VIF was not requested) and the ADM records [n,p] (engine.ADM_DTYPE); adm="only"
+    leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -484,11 +493,13 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     if n == 0:
         e = np.zeros((0, len(quality.planes)))
         e5 = np.zeros((0, len(quality.planes), N.MS_LEVELS))
-        q = (e.astype(np.uint64), e) if quality.vif != "only" else (None, None)
+        q = (e.astype(np.uint64), e) if quality.ssim else (None, None)
         q += (e5, e5.copy()) if quality.scales else ()
-        if quality.vif:
-            from .engine import VIF_DTYPE
-            q += (np.zeros((0, len(quality.planes)), VIF_DTYPE),)
+        if quality.vif or quality.adm:
+            from .engine import ADM_DTYPE, VIF_DTYPE
+            q += (np.zeros((0, len(quality.planes)), VIF_DTYPE) if quality.vif else None,)
+            if quality.adm:
+                q += (np.zeros((0, len(quality.planes)), ADM_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -609,7 +620,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -623,12 +634,15 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                                                  row_stride=f.fb, owner=b, channels=1, itemsize=f.itemsize))
                     else:
                         pair.append(f.src.frames.slice(p["q0"], p["q0"] + p["qn"]))
-                if quality.vif != "only":
+                if quality.ssim:
                     eng.quality_submit(pair[0], pair[1], quality.planes, quality.ssim_mode)
                     p["has_q"] = True
                 if quality.vif:   # the same device frames: the chunk was uploaded once
                     eng.vif_submit(pair[0], pair[1], quality.planes)
                     p["has_v"] = True
+                if quality.adm:
+                    eng.adm_submit(pair[0], pair[1], quality.planes)
+                    p["has_a"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -647,7 +661,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif = [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm = [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -657,6 +671,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["qres"] = eng.quality_wait(quality.scales)
             if p["has_v"]:
                 p["vres"] = eng.vif_wait()
+            if p["has_a"]:
+                p["ares"] = eng.adm_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -677,6 +693,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                     on_quality(p["q0"], sse[-1], ssim[-1])
             if p["has_v"]:
                 vif.append(p.pop("vres"))
+            if p["has_a"]:
+                adm.append(p.pop("ares"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -732,11 +750,13 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         raise
     q = None
     if want_q:
-        q = (np.concatenate(sse), np.concatenate(ssim)) if quality.vif != "only" else (None, None)
+        q = (np.concatenate(sse), np.concatenate(ssim)) if quality.ssim else (None, None)
     if want_q and quality.scales:
         q += (np.concatenate(ms_cs), np.concatenate(ms_ssim))
-    if want_q and quality.vif:
-        q += (np.concatenate(vif),)
+    if want_q and (quality.vif or quality.adm):
+        q += (np.concatenate(vif) if quality.vif else None,)
+    if want_q and quality.adm:
+        q += (np.concatenate(adm),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

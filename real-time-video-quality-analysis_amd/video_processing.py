@@ -104,13 +104,37 @@ def frame_vif(reference, distorted, layout="bgr24", height=None, width=None, eng
     return q[-1]["scale"], q[-1]["vif"], [(p[0], p[1]) for p in planes]
 
 
-def write_vif_log(vmaf_log, scale):
+def frame_adm(reference, distorted, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame ADM per plane on four scales (Engine.adm through the one-pass pipeline of frame_quality).
+    Returns (scale [n,p,4] float64 - libvmaf's adm_scale0..3 -, adm2 [n,p] float64 - sum of the numerators over the sum of the
+    denominators of the four scales -, plane sizes).  Every plane at least 16 x 16."""
+    reference, distorted = _host_stream(reference, wide=True), _host_stream(distorted, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != distorted.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(distorted, reference, quality=stream.Quality(planes, adm="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    return q[-1]["scale"], q[-1]["adm2"], [(p[0], p[1]) for p in planes]
+
+
+def write_vif_log(vmaf_log, scale=None, adm=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key: there is no model.
-    scale: [n, 4], the first (luma) plane's values."""
+    scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
+    adm: None, or the first plane's ADM records [n] (engine.ADM_DTYPE): the log then also carries adm2 and adm_scale0..3, per
+    frame and pooled in the same way."""
     import json
-    scale = np.asarray(scale, np.float64).reshape(-1, N.VIF_LEVELS)
-    names = ["vif_scale%d" % s for s in range(N.VIF_LEVELS)]
+    names, cols = [], []
+    if scale is not None:
+        scale = np.asarray(scale, np.float64).reshape(-1, N.VIF_LEVELS)
+        names += ["vif_scale%d" % s for s in range(N.VIF_LEVELS)]
+        cols += [scale[:, s] for s in range(N.VIF_LEVELS)]
+    if adm is not None:
+        adm = np.asarray(adm).reshape(-1)
+        names += ["adm2"] + ["adm_scale%d" % s for s in range(N.ADM_LEVELS)]
+        cols += [adm["adm2"].astype(np.float64)] + [adm["scale"][:, s].astype(np.float64) for s in range(N.ADM_LEVELS)]
+    scale = np.stack(cols, axis=1) if cols else np.zeros((0, 0))
     frames = [{"frameNum": i, "metrics": {k: float(v) for k, v in zip(names, row)}} for i, row in enumerate(scale)]
     pooled = {}
     for s, k in enumerate(names):
@@ -224,13 +248,15 @@ def _open_quality_stream(src, layout, height, width):
 
 
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
-                       layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False):
+                       layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
+                       adm=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
     vif=True: the same pass (one upload per chunk) also measures VIF on four scales and writes vmaf_log in libvmaf's JSON
     shape (write_vif_log: the first plane's vif_scale0..3 per frame and pooled; no vmaf value).  Without it vmaf_log is not
-    written, as before."""
+    written, as before.
+    adm=True: likewise ADM on four scales (adm2 and adm_scale0..3 of the first plane, per frame and pooled, in the same log)."""
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     dist, layout_d, _, _ = _open_quality_stream(distorted_video, layout, height, width)
     if layout_d != layout:
@@ -238,13 +264,14 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
-        if vif:
+        if vif or adm:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
-            q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=True),
+            q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
+                                                             adm=bool(adm)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            write_vif_log(vmaf_log, q[-1]["scale"][:, 0])
+            _write_feature_log(vmaf_log, q, vif, adm)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -281,6 +308,14 @@ MODE_KEYS = {
 }
 
 
+def _write_feature_log(vmaf_log, q, vif, adm):
+    """the first plane's VIF / ADM of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
+    if adm:
+        write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0])
+    else:
+        write_vif_log(vmaf_log, q[-1]["scale"][:, 0])
+
+
 def _check_mode_keys(config):
     for key, (allowed, message) in MODE_KEYS.items():
         if key in config and config[key] not in allowed:
@@ -290,6 +325,8 @@ def _check_mode_keys(config):
         raise ValueError("device must be a non-negative integer.")
     if "vif" in config and not isinstance(config["vif"], bool):
         raise ValueError("vif must be true or false.")
+    if "adm" in config and not isinstance(config["adm"], bool):
+        raise ValueError("adm must be true or false.")
     bs = config.get("batch_size", 100)
     if isinstance(bs, bool) or not isinstance(bs, int) or bs <= 0:
         raise ValueError("batch_size must be a positive integer.")
@@ -318,6 +355,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         batch_size, ssim_mode ("gauss" north_star's 11x11 Gaussian, default | "ffmpeg" vf_ssim's 8x8 integer windows |
         "msssim" multi-scale SSIM over the Gaussian window: the ssim stats lines and the SSIM column then carry MS-SSIM),
         vif (true: the row gains VIF_scale0..3, the pooled means of the first plane's VIF on four scales; default false),
+        adm (true: the row gains ADM2 and ADM_scale0..3, the pooled means of the first plane's ADM; default false),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -336,6 +374,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     batch_size = config.get("batch_size", 100)
     ssim_mode = _SSIM_MODES[config.get("ssim_mode", "gauss")]
     vif = config.get("vif", False)
+    adm = config.get("adm", False)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -378,13 +417,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         planes = LAYOUTS[layout][0](h, w)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
-            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif),
+            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif:
-            write_vif_log(vmaf_log, _q[-1]["scale"][:, 0])
+        if vif or adm:
+            _write_feature_log(vmaf_log, _q, vif, adm)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -428,6 +467,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         for s in range(N.VIF_LEVELS):
             if "vif_scale%d" % s in pooled:
                 metrics["VIF_scale%d" % s] = float(pooled["vif_scale%d" % s]["mean"])
+        for k in ["adm2"] + ["adm_scale%d" % s for s in range(N.ADM_LEVELS)]:
+            if k in pooled:
+                metrics[k.upper().replace("SCALE", "scale")] = float(pooled[k]["mean"])
     return metrics
 
 
@@ -450,7 +492,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm
 
 
 def main(argv=None):
