@@ -43,7 +43,7 @@ int main(void)
     vqa_plane_desc planes[3];
     for (int c = 0; c < 3; c++) {
         planes[c].width = w; planes[c].height = h; planes[c].offset = c; planes[c].row_stride = (int64_t)w * 3;
-        planes[c].pixel_step = 3;
+        planes[c].pixel_step = 3; planes[c].bit_depth = 0;
     }
     vqa_plane_metrics pm[4 * 3];
     CHECK(vqa_quality_submit(ctx, ref + fb, dist + fb, VQA_MEM_HOST, n, (int64_t)fb, (int64_t)fb, planes, 3, VQA_SSIM_GAUSS));
@@ -63,6 +63,16 @@ int main(void)
         bad += pm[i * 3].sse != (unsigned long long)h * w;   /* ref vs ref + 1: SSE == pixel count  */
         bad += !(pm[i * 3].ssim > 0.99 && pm[i * 3].ssim < 1.0);
         bad += fm[i].has_prev != 1u;
+    }
+    /* VMAF's motion feature of the reference frames of the same pair sequence (frame 0 is the one before them) */
+    {
+        vqa_motion_metrics mm[4 * 3];
+        CHECK(vqa_motion_submit(ctx, ref + fb, ref, VQA_MEM_HOST, n, (int64_t)fb, planes, 3));
+        CHECK(vqa_motion_wait(ctx, mm, n * 3));
+        for (int i = 0; i < n; i++) {
+            printf("frame %d: B-plane motion %.6f (sad %.1f)\n", i, mm[i * 3].motion, mm[i * 3].sad);
+            bad += !(mm[i * 3].motion > 0.0) || mm[i * 3].motion != mm[i * 3].sad / ((double)h * w);
+        }
     }
     /* the path's one collective: pooled scalars summed over the communicator's devices (here: this one device,
      * so the sum is the input).  A multi-GPU host passes one ctx per device, or joins by rank (vqa_comm_create_rank). */

@@ -238,6 +238,17 @@ typedef struct vqa_adm_metrics {
                               denominator is 0)                                                                 */
 } vqa_adm_metrics;
 
+/* VMAF's motion feature of one reference plane against the same plane of the frame before (vqa_motion_submit / vqa_motion_wait;
+ * the definition is stated there).  sad is the device's integer total times 2^-16: every per-sample term |d| is rounded to 2^-16
+ * (at most 2^-17 away) and summed in signed 64 bits - VIF's scheme.  |d| < 2^15 for ANY 16-bit input (depth 9: samples reach
+ * 65535 / 2 - 128), so a term is below 2^31 and a plane of 2^28 samples sums to less than 2^59: no overflow.  Integer sums are
+ * associative: the same pair of frames gives the same bits at any place of any batch, from host or device memory.  The
+ * division by h w is made in double on the host by vqa_motion_wait.                                                        */
+typedef struct vqa_motion_metrics {
+    double sad;     /* sum over the plane of |blur(frame i) - blur(frame i-1)|; 0 without a predecessor      */
+    double motion;  /* sad / (h w): libvmaf's `motion` of the frame                                          */
+} vqa_motion_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -408,6 +419,43 @@ VQA_API int vqa_adm_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist
                            const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_adm_wait(vqa_ctx *ctx, vqa_adm_metrics *out, int n_entries);
 
+/* ---- VMAF's motion feature (the temporal feature of the reference's libvmaf step, video_processing.py:270-297) ----
+ * For one plane of the REFERENCE stream (`depth` bits, h x w), frame i with its predecessor i - 1, in fp32 on the device; the
+ * distorted stream is never looked at:
+ *   samples   x = R / 2^(depth-8) - 128, as VIF states it (exact at every depth; samples above 2^depth - 1 are read as they are).
+ *   blur      5 taps (0.054488685, 0.244201342, 0.402619947, 0.244201342, 0.054488685), each rounded once to fp32; separable,
+ *             columns (vertical) first, then rows; every output sums its taps in ascending order (fused multiply-adds from 0).
+ *   borders   VIF's rule: an index i < 0 reads -i; an index i >= n reads 2n - i - 1.
+ *   motion[i] = sum |blur(x_i) - blur(x_{i-1})| / (h w); 0 for a frame with no predecessor.  Identical frames give exactly 0.
+ *   motion2[i] = min(motion[i], motion[i+1]), motion2[last] = motion[last] (so motion2[0] = 0 whenever motion[0] = 0).  It needs
+ *             the next frame, so it is NOT formed here: the host forms it over the whole clip (the Python binding's
+ *             tails.motion2).
+ * This is libvmaf's float `motion` feature at its default options (no motion_force_zero) as the project states it; where this
+ * text and libvmaf differ in a detail, this text is what is built.  It is pinned against the float64 restatement in
+ * tests/motion_reference.py, not against libvmaf's binary.
+ * Error bound (in-range samples, |x| <= 128, against exact arithmetic on the decimal taps): a rounding of a value below 256 is at
+ * most 2^-17.  Per blurred sample: 5 roundings in the vertical pass, carried through the horizontal pass with weight <= 1, 5 more
+ * there, and the taps' own rounding to fp32 (2^-24 relative on a sum of at most 128: 2^-17 per pass) - 12 x 2^-17.  The
+ * difference of two blurred samples adds one rounding, the fixed-point quantum 2^-17 more: 2 x 12 + 1 + 1 = 26 units of 2^-17,
+ * 1.99e-4 per sample and therefore on motion (a mean of the per-sample terms).  The tests use that figure as their bar.
+ * The contract of vqa_vif_submit: asynchronous, the same plane descriptors, depths (one per submit), alignment rules and
+ * failure guarantee.  prev0: the frame preceding ref[0] (same layout and mem_kind) or NULL, exactly as in
+ * vqa_complexity_submit; frame i's predecessor is frame i - 1 of the batch.  Every plane must be at least 16 x 16:
+ * VQA_ERR_UNSUPPORTED below.  VQA_ERR_STATE while a motion batch is pending.  A motion batch is a batch of its own: it may be
+ * in flight next to a quality, a VIF, an ADM and a complexity batch of the same ctx (one upload then serves all), and each wait
+ * collects its own kind only - vqa_motion_wait with only another kind pending, and another kind's wait with only a motion
+ * batch pending, are VQA_ERR_STATE and leave that batch pending.
+ * One fused kernel: a tile and its apron of 2 samples of both frames go to shared memory, both are blurred there and only the
+ * integer total leaves the kernel.  Scratch on the device: 8 bytes per entry; frames handed over in host memory (and prev0)
+ * are staged in device buffers of the batch's size.  All of it is kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_motion_wait: n * n_planes entries, frame-major.
+ * The VMAF score itself is NOT in this ABI: the predictor (an RBF support-vector sum of a few thousand flops per frame over the
+ * model file the caller names) runs on the host next to the other float tails - the Python binding's vmaf_model module; parsing
+ * a JSON model in C would buy nothing.                                                                                  */
+VQA_API int vqa_motion_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n,
+                              int64_t ref_frame_stride, const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_motion_wait(vqa_ctx *ctx, vqa_motion_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -430,8 +478,11 @@ enum vqa_kernel_id {
                                 tests that rely on id 14 being unknown); ids 14 and 15 stay unnamed                    */
     VQA_K_ADM = 16,          /* vqa_adm_submit: one scale - DWT, decoupling, masking, cube sums (four entries per group)  */
     VQA_K_ADM_REDUCE = 17,   /* vqa_adm_submit: the tile partials of a scale, added in a fixed order (four per group)     */
-    VQA_K_COUNT_EXT = 18     /* vqa_profile_read and vqa_kernel_name know 0 .. VQA_K_COUNT_ALL - 1 and VQA_K_ADM ..
-                                VQA_K_COUNT_EXT - 1                                                                    */
+    VQA_K_COUNT_EXT = 18,    /* vqa_profile_read and vqa_kernel_name know 0 .. VQA_K_COUNT_ALL - 1 and VQA_K_ADM ..
+                                VQA_K_COUNT_EXT - 1 (kept at 18 for callers and tests that rely on id 18 being unknown)  */
+    VQA_K_MOTION = 19,       /* vqa_motion_submit: blur of both frames and the sum of |difference| (one entry per group of
+                                same-geometry planes); id 18 stays unnamed                                              */
+    VQA_K_END = 20           /* one past the last id: ... and VQA_K_MOTION .. VQA_K_END - 1                              */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

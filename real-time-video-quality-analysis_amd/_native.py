@@ -40,7 +40,9 @@ M_ALL = 0x7F
  K_FARNEBACK, K_MS_PYRAMID, K_COUNT) = range(13)
 K_VIF, K_VIF_DECIMATE, K_COUNT_ALL = 12, 13, 14   # added beyond K_COUNT (include/vqa.h: VQA_K_COUNT stays 12)
 K_ADM, K_ADM_REDUCE, K_COUNT_EXT = 16, 17, 18     # added beyond K_COUNT_ALL, which stays 14; ids 14 and 15 are unnamed
-K_IDS = tuple(range(K_COUNT_ALL)) + (K_ADM, K_ADM_REDUCE)   # every id vqa_profile_read and vqa_kernel_name know
+K_MOTION, K_END = 19, 20                          # added beyond K_COUNT_EXT, which stays 18; id 18 is unnamed
+K_IDS = tuple(range(K_COUNT_ALL)) + (K_ADM, K_ADM_REDUCE)   # the ids below K_COUNT_EXT (kept as ADM shipped it)
+K_IDS_ALL = K_IDS + (K_MOTION,)                   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -54,6 +56,7 @@ VIF_LEVELS = 4
 VIF_MIN_DIM = 16   # vqa_vif_submit: level 3 of a 16 x 16 plane is 2 x 2, every reflection stays inside its level
 ADM_LEVELS = 4
 ADM_MIN_DIM = 16   # vqa_adm_submit: the bands of scale 3 of a 16 x 16 plane are 1 x 1
+MOTION_MIN_DIM = 16   # vqa_motion_submit: the limit of VIF and ADM, whose planes it shares
 MOTION_SAD, MOTION_FARNEBACK = 0, 1
 
 
@@ -103,6 +106,10 @@ class VqaAdmMetrics(C.Structure):
     _fields_ = [("num", C.c_double * 4), ("den", C.c_double * 4), ("scale", C.c_double * 4), ("adm2", C.c_double)]
 
 
+class VqaMotionMetrics(C.Structure):
+    _fields_ = [("sad", C.c_double), ("motion", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -140,6 +147,8 @@ SIGNATURES = {
     "vqa_adm_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                  C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_adm_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaAdmMetrics), C.c_int]),
+    "vqa_motion_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_motion_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaMotionMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -74,6 +74,9 @@ struct vqa_ctx {
     // (entry, scale) (device, pinned host)
     dbuf adm_pyr, adm_part, adm_sums;
     void *adm_host = nullptr; size_t adm_host_cap = 0;
+    // vqa_motion_submit: the integer totals (device, pinned host); host frames and their prev0 staged on the device
+    dbuf mot_acc, mot_stage, mot_prev;
+    void *mot_host = nullptr; size_t mot_host_cap = 0;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -90,6 +93,9 @@ struct vqa_ctx {
     int pend_v = 0;           // entries of the pending VIF batch (a batch of its own, next to pend_c and pend_q)
     int pend_a = 0;           // entries of the pending ADM batch (likewise); its planes' sizes, for the host's cube roots
     int pend_a_planes = 0, pend_a_w[4] = {0}, pend_a_h[4] = {0};
+    int pend_m = 0;           // entries of the pending motion batch (likewise); its planes' areas, for the host's division
+    int pend_m_planes = 0;
+    int64_t pend_m_area[4] = {0};
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -99,8 +105,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_COUNT_EXT] = {0};
-    int64_t prof_n[VQA_K_COUNT_EXT] = {0};
+    double prof_ms[VQA_K_END] = {0};
+    int64_t prof_n[VQA_K_END] = {0};
 };
 
 namespace {
@@ -777,7 +783,7 @@ int vqa_create(int device, vqa_ctx **out)
 int vqa_set_option(vqa_ctx *c, int option, int value)
 {
     if (!c) return VQA_ERR_INVALID;
-    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a) return VQA_ERR_STATE; // options apply to whole submits
+    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m) return VQA_ERR_STATE; // options apply to whole submits
     switch (option) {
     case VQA_OPT_OVERLAP: c->opt_overlap = value != 0; return VQA_OK;
     case VQA_OPT_HYST_STATS: c->opt_hyst_stats = value != 0; return VQA_OK;
@@ -813,7 +819,7 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
@@ -825,8 +831,9 @@ static void release_scratch(vqa_ctx *c)
     if (c->qms_host) (void)hipHostFree(c->qms_host);
     if (c->vif_host) (void)hipHostFree(c->vif_host);
     if (c->adm_host) (void)hipHostFree(c->adm_host);
-    c->res_host = c->qres_host = c->qms_host = c->vif_host = c->adm_host = nullptr;
-    c->res_host_cap = c->qres_host_cap = c->qms_host_cap = c->vif_host_cap = c->adm_host_cap = 0;
+    if (c->mot_host) (void)hipHostFree(c->mot_host);
+    c->res_host = c->qres_host = c->qms_host = c->vif_host = c->adm_host = c->mot_host = nullptr;
+    c->res_host_cap = c->qres_host_cap = c->qms_host_cap = c->vif_host_cap = c->adm_host_cap = c->mot_host_cap = 0;
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
 }
@@ -834,7 +841,7 @@ static void release_scratch(vqa_ctx *c)
 int vqa_trim(vqa_ctx *c)
 {
     if (!c) return VQA_ERR_INVALID;
-    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a) return VQA_ERR_STATE;
+    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m) return VQA_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     prof_collect(c);
@@ -1714,6 +1721,108 @@ int vqa_adm_wait(vqa_ctx *c, vqa_adm_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// VMAF's motion feature: the reference stream alone, frame i against frame i - 1.  A batch of its own (pend_m), ordered by the
+// stream like a VIF batch; the checks are vqa_vif_submit's.  Host frames (and prev0) are staged in buffers of their own.
+static int motion_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                              const vqa_plane_desc *planes, int n_planes, bool &touched)
+{
+    if (!c || !ref || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
+    if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
+    if (c->pend_m) return VQA_ERR_STATE;
+    int64_t span = 0;
+    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
+    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
+    const int bps = depth > 8 ? 2 : 1;
+    for (int p = 0; p < n_planes; p++) {
+        const vqa_plane_desc &d = planes[p];
+        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
+        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
+        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
+            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
+            return VQA_ERR_INVALID;
+        if (d.width < MOTION_MIN_DIM || d.height < MOTION_MIN_DIM) return VQA_ERR_UNSUPPORTED;
+        if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;   // the bound of the 64-bit totals (vqa.h)
+        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
+        span = end > span ? end : span;
+    }
+    if (n > 1 && ref_fs < span) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    const uint8_t *dref = ref, *dprev = prev0;
+    if (mem_kind == VQA_MEM_HOST) {
+        const size_t rs = (size_t)(n - 1) * ref_fs + span;
+        int rc = ensure(c, c->mot_stage, rs);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->mot_stage.p, ref, rs, hipMemcpyHostToDevice, st));
+        dref = (const uint8_t *)c->mot_stage.p;
+        if (prev0) {
+            rc = ensure(c, c->mot_prev, (size_t)span);
+            if (rc) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->mot_prev.p, prev0, (size_t)span, hipMemcpyHostToDevice, st));
+            dprev = (const uint8_t *)c->mot_prev.p;
+        }
+    }
+    const size_t nent = (size_t)n * n_planes;
+    const size_t acc_bytes = sizeof(long long) * nent;
+    int rc = ensure(c, c->mot_acc, acc_bytes);
+    if (rc) return rc;
+    rc = ensure_pinned(c, c->mot_host, c->mot_host_cap, acc_bytes);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(c->mot_acc.p, 0, acc_bytes, st));
+    const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
+    for (int a0 = 0; a0 < n; a0 += QSLICE) {
+        const int m = n - a0 < QSLICE ? n - a0 : QSLICE;
+        long long *acc = (long long *)c->mot_acc.p + (size_t)a0 * n_planes;
+        const uint8_t *sref = dref + (int64_t)a0 * ref_fs;
+        const uint8_t *sprev = a0 > 0 ? dref + (int64_t)(a0 - 1) * ref_fs : dprev;
+        bool done[4] = {false, false, false, false};
+        for (int p = 0; p < n_planes; p++) {
+            if (done[p]) continue;
+            int idx[4], cnt = 0;
+            for (int q = p; q < n_planes; q++) {
+                if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
+                    planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
+                    idx[cnt++] = q;
+                    done[q] = true;
+                }
+            }
+            prof_scope ps_(c, VQA_K_MOTION);
+            launch_motion_sad(st, sref, sprev, m, ref_fs, planes, idx, cnt, n_planes, depth, acc);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->mot_host, c->mot_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_m = (int)nent;
+    c->pend_m_planes = n_planes;
+    for (int p = 0; p < n_planes; p++) c->pend_m_area[p] = (int64_t)planes[p].width * planes[p].height;
+    return VQA_OK;
+}
+
+int vqa_motion_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                      const vqa_plane_desc *planes, int n_planes)
+{
+    bool touched = false;
+    const int rc = motion_submit_body(c, ref, prev0, mem_kind, n, ref_fs, planes, n_planes, touched);
+    return drain_failed_submit(c, rc, touched);
+}
+
+int vqa_motion_wait(vqa_ctx *c, vqa_motion_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_m || n_entries != c->pend_m) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const long long *acc = (const long long *)c->mot_host;
+    for (int e = 0; e < n_entries; e++) {
+        out[e].sad = (double)acc[e] * (1.0 / 65536.0);   // exact for in-range samples (a total below 2^52); a total above 2^53 is rounded once, to double
+        out[e].motion = out[e].sad / (double)c->pend_m_area[e % c->pend_m_planes];
+    }
+    c->pend_m = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -1723,8 +1832,9 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_COUNT_EXT || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM)) return VQA_ERR_INVALID;
-    if (!c->pend_c && !c->pend_q && !c->pend_v && !c->pend_a) {
+    if (!c || id < 0 || id >= VQA_K_END || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION))
+        return VQA_ERR_INVALID;
+    if (!c->pend_c && !c->pend_q && !c->pend_v && !c->pend_a && !c->pend_m) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         prof_collect(c);
     }
@@ -1742,6 +1852,7 @@ const char *vqa_kernel_name(int id)
                                              "k_vif_stats", "k_vif_decimate"};
     if (id == VQA_K_ADM) return "k_adm_scale";
     if (id == VQA_K_ADM_REDUCE) return "k_adm_reduce";
+    if (id == VQA_K_MOTION) return "k_motion_sad";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

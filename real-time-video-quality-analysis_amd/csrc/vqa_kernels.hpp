@@ -297,4 +297,15 @@ void launch_adm_reduce(hipStream_t st, const double *part, int n, const vqa_plan
 // six sums per scale -> the record: cube roots and quotients in double, on the host (h x w: the plane)
 void adm_finalize(const double *sums, int h, int w, vqa_adm_metrics *out);
 
+// VMAF's motion feature (vqa_motion_submit): k_motion.hip
+constexpr int MOTION_MIN_DIM = 16;
+constexpr int MOTION_RADIUS = 2;
+// the 5-tap blur of include/vqa.h; the device uses each tap rounded once to fp32
+constexpr double MOTION_TAPS[5] = {0.054488685, 0.244201342, 0.402619947, 0.244201342, 0.054488685};
+// one group of same-geometry planes of n reference frames: frame i against frame i - 1 (frame 0 against prev0; nullptr: frame 0
+// is skipped and keeps its zero).  Adds sum |blur(x_i) - blur(x_{i-1})| in 2^-16 fixed point into acc[frame * n_planes + plane],
+// which the caller has zeroed.
+void launch_motion_sad(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n, int64_t frame_stride,
+                       const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth, long long *acc);
+
 } // namespace vqa

@@ -36,6 +36,8 @@ assert VIF_DTYPE.itemsize == C.sizeof(N.VqaVifMetrics)
 ADM_DTYPE = np.dtype([("num", np.float64, (4,)), ("den", np.float64, (4,)), ("scale", np.float64, (4,)), ("adm2", np.float64)],
                      align=True)
 assert ADM_DTYPE.itemsize == C.sizeof(N.VqaAdmMetrics)
+MOTION_DTYPE = np.dtype([("sad", np.float64), ("motion", np.float64)], align=True)
+assert MOTION_DTYPE.itemsize == C.sizeof(N.VqaMotionMetrics)
 
 
 class DeviceFrames:
@@ -241,10 +243,11 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend, wait in (("_pending_q", self.quality_wait), ("_pending_v", self.vif_wait), ("_pending_a", self.adm_wait),
+                           ("_pending_m", self.motion_wait),
                            ("_pending_c", self.complexity_wait)):
             try:
                 if getattr(self, pend, None):
@@ -469,6 +472,66 @@ class Engine:
         self.adm_submit(ref, dist, planes, frame_bytes)
         return self.adm_wait()
 
+    # ---- VMAF's motion feature -------------------------------------------------
+    def _ref_args(self, ref, planes, prev0, frame_bytes=None):
+        """the reference frames (and the frame before them) of a motion submit -> (ref ptr, prev0 ptr or None, mem kind, n,
+        frame stride, what to keep alive)"""
+        wide = planes_depth(planes) > 8
+        want = "uint16" if wide else "uint8"
+        if isinstance(ref, DeviceFrames):
+            if prev0 is not None and not isinstance(prev0, DeviceFrames):
+                raise TypeError("prev0 must live where ref lives (device)")
+            for a in (ref,) + ((prev0,) if prev0 is not None else ()):
+                if (a.itemsize == 2) != wide:
+                    raise ValueError("%d-bit planes need frames of %s samples (got DeviceFrames of itemsize %d)"
+                                     % (planes_depth(planes), want, a.itemsize))
+            return ref.ptr, (prev0.ptr if prev0 is not None else None), N.VQA_MEM_DEVICE, ref.n, ref.frame_stride, (ref, prev0)
+        if isinstance(prev0, DeviceFrames):
+            raise TypeError("prev0 must live where ref lives (host)")
+        ref = np.asarray(ref)
+        if wide != (ref.dtype == np.uint16):
+            raise ValueError("%d-bit planes need %s frames (got %s)" % (planes_depth(planes), want, ref.dtype))
+        ref = np.ascontiguousarray(ref, dtype=np.uint16 if wide else np.uint8)
+        n = ref.shape[0]
+        fs = frame_bytes or (ref.nbytes // n)
+        pp, keep = None, [ref]
+        if prev0 is not None:
+            p0 = np.asarray(prev0)
+            if wide != (p0.dtype == np.uint16):
+                raise ValueError("%d-bit planes need a %s prev0 (got %s)" % (planes_depth(planes), want, p0.dtype))
+            p0 = np.ascontiguousarray(p0, dtype=ref.dtype)
+            if p0.nbytes != ref.nbytes // n:
+                raise ValueError("prev0 must have the frames' layout (%d bytes, got %d)" % (ref.nbytes // n, p0.nbytes))
+            keep.append(p0)
+            pp = p0.ctypes.data
+        return ref.ctypes.data, pp, N.VQA_MEM_HOST, n, fs, keep
+
+    def motion_submit(self, ref, planes, prev0=None, frame_bytes=None):
+        """VMAF's motion feature for n reference frames (vqa_motion_submit): frame i against frame i - 1, frame 0 against
+        prev0 (None: it has no predecessor and scores 0).  The arrays / DeviceFrames and plane tuples of vif_submit - the
+        reference stream alone; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit, a vif_submit
+        and an adm_submit of the same frames before any of them is waited for."""
+        rp, pp, kind, n, fs, keep = self._ref_args(ref, planes, prev0, frame_bytes)
+        descs = plane_descs(planes)
+        st = self.lib.vqa_motion_submit(self.ctx, rp, pp, kind, n, fs, descs, len(planes))
+        N.check(st, "vqa_motion_submit", self.ctx)
+        self._pending_m = (n, len(planes), keep)
+
+    def motion_wait(self):
+        """-> [n, n_planes] records (MOTION_DTYPE): sad, the sum of |blur(frame) - blur(previous frame)| over the plane, and
+        motion = sad / (h w), libvmaf's `motion`.  (motion2 needs the next frame: tails.motion2 over the whole clip.)"""
+        n, npl, _keep = self._pending_m
+        out = np.zeros(n * npl, dtype=MOTION_DTYPE)
+        st = self.lib.vqa_motion_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaMotionMetrics)), n * npl)
+        self._pending_m = None
+        N.check(st, "vqa_motion_wait", self.ctx)
+        return out.reshape(n, npl)
+
+    def motion(self, ref, planes, prev0=None, frame_bytes=None):
+        """VMAF's motion feature per plane for n reference frames; returns [n, n_planes] structured array (MOTION_DTYPE)."""
+        self.motion_submit(ref, planes, prev0, frame_bytes)
+        return self.motion_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -476,7 +539,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS:
+        for k in N.K_IDS_ALL:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

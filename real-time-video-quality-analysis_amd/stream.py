@@ -295,7 +295,7 @@ def selected_indices(num_frames, frame_interval):
     return np.arange(frame_interval - 1, num_frames, frame_interval)
 
 
-def plan_chunks(n, want_q, interval, lo, hi, cap, split=False):
+def plan_chunks(n, want_q, interval, lo, hi, cap, split=False, motion=False):
     """The chunks of a pass, as pure arithmetic (no engine, no frames): -> list of dicts.
 
     n frames; quality wanted or not; complexity samples lo..hi-1 of the series at `interval` (None: no complexity), where
@@ -311,13 +311,21 @@ def plan_chunks(n, want_q, interval, lo, hi, cap, split=False):
     split: the quality kernels read their OWN pair of streams (planar yuv420p, what FFmpeg's filters compare,
     video_processing.py:274-276) and the complexity kernels the encoded stream as cv2 decodes it (BGR,
     complexity_metrics.py:100): `rcopies` / `qcopies` are the dense range of the quality pair (slots 0 .. qn - 1, qslot = 0)
-    and `copies` the chunk's samples of the BGR stream, compact - every byte of either stream moves once."""
+    and `copies` the chunk's samples of the BGR stream, compact - every byte of either stream moves once.
+    motion: the quality half also measures VMAF's motion feature on the reference stream, which compares every frame with the
+    one before it: the reference feed gets a halo slot of its own, as the complexity stream has - its chunk sits in slots
+    rslot = 1 .. qn and slot 0 holds source frame q0 - 1, the last reference frame of the previous chunk (rhalo = True; the first
+    chunk has no predecessor: rhalo = False, slot 0 stays unused).  The halo is part of the chunk's OWN upload - it never points
+    into the previous chunk's buffer set, which the copy lane may already be overwriting.  Without motion rslot is 0 and the
+    plans are what they were."""
     plans = []
     if want_q:
         idx = selected_indices(n, interval) if interval else None
         for k, a in enumerate(range(0, n, cap)):
             b = min(a + cap, n)
             p = dict(k=k, q0=a, qn=b - a, qslot=0 if split else 1, j0=0, j1=0, copies=[], rcopies=[(0, a, b - a, 1)])
+            if motion:
+                p.update(rslot=1, rhalo=a > 0, rcopies=([(0, a - 1, 1, 1)] if a > 0 else []) + [(1, a, b - a, 1)])
             if split:
                 p["qcopies"] = [(0, a, b - a, 1)]
             if interval and hi > lo:
@@ -380,12 +388,16 @@ class Complexity:
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
-    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False):
+    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
         adm     True: likewise through the ADM kernels (Engine.adm_submit); the pass then returns (.., VIF records or None,
-                ADM records [n,p] (engine.ADM_DTYPE)); "only": no SSE / SSIM (with vif=True or "only": VIF and ADM alone)"""
+                ADM records [n,p] (engine.ADM_DTYPE)); "only": no SSE / SSIM (with vif=True or "only": VIF and ADM alone)
+        motion  True: every chunk's REFERENCE frames also go through the motion kernel (Engine.motion_submit) from the same
+                upload, prev0 being the last reference frame of the previous chunk (the reference feed's halo slot); the pass
+                then returns (.., VIF records or None, ADM records or None, motion records [n,p] (MOTION_PASS_DTYPE: sad, motion
+                and motion2, the last formed once over the whole clip)); "only": no SSE / SSIM"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -396,8 +408,26 @@ class Quality:
             raise ValueError("adm must be False, True or 'only'")
         if adm == "only" and scales:
             raise ValueError("an ADM-only pass has no SSIM scales")
+        if not (isinstance(motion, bool) or (isinstance(motion, str) and motion == "only")):
+            raise ValueError("motion must be False, True or 'only'")
+        if motion == "only" and scales:
+            raise ValueError("a motion-only pass has no SSIM scales")
         self.planes, self.ssim_mode, self.scales, self.vif, self.adm = planes, ssim_mode, bool(scales), vif, adm
-        self.ssim = vif != "only" and adm != "only"   # the pass measures SSE / SSIM
+        self.motion = motion
+        self.ssim = vif != "only" and adm != "only" and motion != "only"   # the pass measures SSE / SSIM
+
+
+# what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
+# frame and is therefore formed once, over the concatenated clip (tails.motion2)
+MOTION_PASS_DTYPE = np.dtype([("sad", np.float64), ("motion", np.float64), ("motion2", np.float64)])
+
+
+def motion_records(rec):
+    """the motion records [n,p] of a whole clip (engine.MOTION_DTYPE) -> [n,p] MOTION_PASS_DTYPE"""
+    out = np.zeros(rec.shape, MOTION_PASS_DTYPE)
+    out["sad"], out["motion"] = rec["sad"], rec["motion"]
+    out["motion2"] = tails.motion2(rec["motion"])
+    return out
 
 
 class _Feed:
@@ -454,7 +484,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     (sse, ssim, cs [n,p,5], ssim per scale [n,p,5]); with Quality(.., vif=True) the VIF records [n,p] (engine.VIF_DTYPE) are
     appended as the last element, and with vif="only" sse and ssim are None.  With Quality(.., adm=True) two elements are
     appended instead: the VIF records (None when VIF was not requested) and the ADM records [n,p] (engine.ADM_DTYPE); adm="only"
-    leaves sse and ssim None as well.
+    leaves sse and ssim None as well.  With Quality(.., motion=True) three elements are appended: the VIF records or None, the ADM
+    records or None and the motion records [n,p] (MOTION_PASS_DTYPE); motion="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -495,11 +526,13 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         e5 = np.zeros((0, len(quality.planes), N.MS_LEVELS))
         q = (e.astype(np.uint64), e) if quality.ssim else (None, None)
         q += (e5, e5.copy()) if quality.scales else ()
-        if quality.vif or quality.adm:
+        if quality.vif or quality.adm or quality.motion:
             from .engine import ADM_DTYPE, VIF_DTYPE
             q += (np.zeros((0, len(quality.planes)), VIF_DTYPE) if quality.vif else None,)
-            if quality.adm:
-                q += (np.zeros((0, len(quality.planes)), ADM_DTYPE),)
+            if quality.adm or quality.motion:
+                q += (np.zeros((0, len(quality.planes)), ADM_DTYPE) if quality.adm else None,)
+            if quality.motion:
+                q += (np.zeros((0, len(quality.planes)), MOTION_PASS_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -514,12 +547,15 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
 def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series, n, batch_size, on_quality):
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
-    if want_c or not split:
+    # motion alone reads the reference stream only: the distorted stream is not even uploaded
+    ref_only = want_q and not want_c and quality.motion == "only" and not quality.vif and not quality.adm
+    if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
         feeds["ref"] = _Feed("ref", "rcopies", ref, first, wide=True)
-        if split:
+        if split and not ref_only:
             feeds["qdist"] = _Feed("qdist", "qcopies", qd, first, wide=True)
+    if want_q and not ref_only:
         fq, fr = feeds["qdist" if split else "dist"], feeds["ref"]
         if fr.src.n != fq.src.n or fr.fb != fq.fb:
             raise ValueError("reference and distorted streams must have the same frame count and layout")
@@ -536,7 +572,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     interval = complexity.interval if want_c else None
     per_frame = 0  # host bytes a source frame brings along
     if want_q:
-        per_frame += sum(feeds[k].fb for k in (("ref", "qdist") if split else ("ref", "dist")) if feeds[k].host)
+        per_frame += sum(feeds[k].fb for k in (("ref", "qdist") if split else ("ref", "dist")) if k in feeds and feeds[k].host)
         if split and want_c and feeds["dist"].host:
             per_frame += -(-feeds["dist"].fb // interval)
     elif feeds["dist"].host:
@@ -544,7 +580,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     host = any(f.host for f in feeds.values())
     staged = any(f.staged for f in feeds.values())
     cap = chunk_frames(batch_size, interval if (want_q and want_c) else None, per_frame if host else 0, staged)
-    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split)
+    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and quality.motion))
     nchunks = len(plans)
     # ---- lanes
     farneback = want_c and (complexity.mask & N.M_MOTION) and complexity.motion_mode == N.MOTION_FARNEBACK
@@ -620,14 +656,15 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
             if want_q:
-                fq, fr = feeds["qdist" if split else "dist"], feeds["ref"]
+                fr = feeds["ref"]
+                fq = None if ref_only else feeds["qdist" if split else "dist"]
                 pair = []
-                for f, slot0 in ((fr, 0), (fq, p["qslot"])):
+                for f, slot0 in ((fr, p.get("rslot", 0)),) + (((fq, p["qslot"]),) if fq is not None else ()):
                     if f.host:
                         b = dev[f.name]
                         pair.append(DeviceFrames(b.ptr + slot0 * f.fb, p["qn"], 1, f.fb // f.itemsize, frame_stride=f.fb,
@@ -643,6 +680,17 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.adm:
                     eng.adm_submit(pair[0], pair[1], quality.planes)
                     p["has_a"] = True
+                if quality.motion:   # the reference frames alone; prev0 = the frame before the chunk: the halo slot of the
+                    prev0 = None     # chunk's own buffer (host streams) or the resident clip's frame in place
+                    if p["q0"] > 0:
+                        if fr.host:
+                            b = dev[fr.name]
+                            prev0 = DeviceFrames(b.ptr, 1, 1, fr.fb // fr.itemsize, frame_stride=fr.fb, row_stride=fr.fb,
+                                                 owner=b, channels=1, itemsize=fr.itemsize)
+                        else:
+                            prev0 = fr.src.frames.frame(p["q0"] - 1)
+                    eng.motion_submit(pair[0], quality.planes, prev0)
+                    p["has_m"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -661,7 +709,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm = [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot = [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -673,6 +721,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["vres"] = eng.vif_wait()
             if p["has_a"]:
                 p["ares"] = eng.adm_wait()
+            if p["has_m"]:
+                p["mres"] = eng.motion_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -695,6 +745,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 vif.append(p.pop("vres"))
             if p["has_a"]:
                 adm.append(p.pop("ares"))
+            if p["has_m"]:
+                mot.append(p.pop("mres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -753,10 +805,12 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q = (np.concatenate(sse), np.concatenate(ssim)) if quality.ssim else (None, None)
     if want_q and quality.scales:
         q += (np.concatenate(ms_cs), np.concatenate(ms_ssim))
-    if want_q and (quality.vif or quality.adm):
+    if want_q and (quality.vif or quality.adm or quality.motion):
         q += (np.concatenate(vif) if quality.vif else None,)
-    if want_q and quality.adm:
-        q += (np.concatenate(adm),)
+    if want_q and (quality.adm or quality.motion):
+        q += (np.concatenate(adm) if quality.adm else None,)
+    if want_q and quality.motion:
+        q += (motion_records(np.concatenate(mot)),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

@@ -148,3 +148,16 @@ def as_list(kind, v):
 def scalars(kind, rec, motion_mode=N.MOTION_SAD):
     """The series of `kind` for a batch of records, as a list whose items have the types scalar() returns."""
     return as_list(kind, values(kind, rec, motion_mode))
+
+
+# ---------------------------------------------------------------------------
+# VMAF's motion2 (include/vqa.h, vqa_motion_submit): it needs the NEXT frame, so it is formed over the whole clip
+# ---------------------------------------------------------------------------
+def motion2(motion):
+    """motion [n] or [n, p] (frame-major) -> motion2 of the same shape: min(motion[i], motion[i+1]), motion2[last] =
+    motion[last]."""
+    m = np.asarray(motion, np.float64)
+    out = m.copy()
+    if len(m) > 1:
+        out[:-1] = np.minimum(m[:-1], m[1:])
+    return out

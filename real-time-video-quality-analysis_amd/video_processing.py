@@ -5,9 +5,12 @@ run_ffmpeg_metrics keeps the reference's contract: it takes the reference and th
 distorted stream plus the log paths, returns None and delivers its results as
 FFmpeg-format stats files, so extract_metrics_from_logs' regular expressions
 (:160, :166) parse them unchanged.  The streams are frame stacks (arrays / .npy)
-instead of container files: decode is out of scope.  VMAF is out of scope: no
-vmaf log is written, and — as in the reference when the file is absent (:169) —
-the 'VMAF' key is simply missing.
+instead of container files: decode is out of scope.  Without a model file
+(vmaf_model_path None) there is no VMAF value and — as in the reference when the
+log has none (:169-173) — the 'VMAF' key is simply missing; with one, the pass
+also measures VIF, ADM and motion, vmaf_model.predict scores every frame and the
+log carries pooled_metrics.vmaf, which extract_metrics_from_logs reads as the
+reference does.
 """
 import os
 import re
@@ -118,12 +121,30 @@ def frame_adm(reference, distorted, layout="bgr24", height=None, width=None, eng
     return q[-1]["scale"], q[-1]["adm2"], [(p[0], p[1]) for p in planes]
 
 
-def write_vif_log(vmaf_log, scale=None, adm=None):
+def frame_motion(reference, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame motion per plane of the REFERENCE stream (Engine.motion through the one-pass pipeline of frame_quality; the
+    stream is uploaded once, there is no distorted stream).
+    Returns (motion [n,p] float64 - libvmaf's `motion`: the mean absolute difference of the blurred frame and the blurred frame
+    before it, 0 for frame 0 -, motion2 [n,p] float64 - min(motion[i], motion[i+1]), the last frame keeping its motion -, plane
+    sizes).  Every plane at least 16 x 16."""
+    reference = _host_stream(reference, wide=True)
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(reference, reference, quality=stream.Quality(planes, motion="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    return q[-1]["motion"], q[-1]["motion2"], [(p[0], p[1]) for p in planes]
+
+
+def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
-    .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key: there is no model.
+    .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
     adm: None, or the first plane's ADM records [n] (engine.ADM_DTYPE): the log then also carries adm2 and adm_scale0..3, per
-    frame and pooled in the same way."""
+    frame and pooled in the same way.
+    motion: None, or the first plane's motion records [n] (stream.MOTION_PASS_DTYPE): the log then also carries motion2 and
+    motion, likewise.
+    model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
+    features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
     names, cols = [], []
     if scale is not None:
@@ -134,6 +155,15 @@ def write_vif_log(vmaf_log, scale=None, adm=None):
         adm = np.asarray(adm).reshape(-1)
         names += ["adm2"] + ["adm_scale%d" % s for s in range(N.ADM_LEVELS)]
         cols += [adm["adm2"].astype(np.float64)] + [adm["scale"][:, s].astype(np.float64) for s in range(N.ADM_LEVELS)]
+    if motion is not None:
+        motion = np.asarray(motion).reshape(-1)
+        names += ["motion2", "motion"]
+        cols += [motion["motion2"].astype(np.float64), motion["motion"].astype(np.float64)]
+    if model is not None:
+        from . import vmaf_model
+        score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
+        names += ["vmaf"]
+        cols += [score]
     scale = np.stack(cols, axis=1) if cols else np.zeros((0, 0))
     frames = [{"frameNum": i, "metrics": {k: float(v) for k, v in zip(names, row)}} for i, row in enumerate(scale)]
     pooled = {}
@@ -249,14 +279,23 @@ def _open_quality_stream(src, layout, height, width):
 
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
-                       adm=False):
+                       adm=False, motion=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
     vif=True: the same pass (one upload per chunk) also measures VIF on four scales and writes vmaf_log in libvmaf's JSON
     shape (write_vif_log: the first plane's vif_scale0..3 per frame and pooled; no vmaf value).  Without it vmaf_log is not
     written, as before.
-    adm=True: likewise ADM on four scales (adm2 and adm_scale0..3 of the first plane, per frame and pooled, in the same log)."""
+    adm=True: likewise ADM on four scales (adm2 and adm_scale0..3 of the first plane, per frame and pooled, in the same log).
+    motion=True: likewise VMAF's motion feature of the reference stream (motion2 and motion of the first plane).
+    vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
+    file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
+    pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
+    model = None
+    if vmaf_model_path is not None:
+        from . import vmaf_model
+        model = vmaf_model.load_model(vmaf_model_path)
+        vif = adm = motion = True
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     dist, layout_d, _, _ = _open_quality_stream(distorted_video, layout, height, width)
     if layout_d != layout:
@@ -264,14 +303,14 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
-        if vif or adm:
+        if vif or adm or motion:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
             q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
-                                                             adm=bool(adm)),
+                                                             adm=bool(adm), motion=bool(motion)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -308,9 +347,12 @@ MODE_KEYS = {
 }
 
 
-def _write_feature_log(vmaf_log, q, vif, adm):
-    """the first plane's VIF / ADM of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
-    if adm:
+def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None):
+    """the first plane's VIF / ADM / motion of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
+    if motion:
+        write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
+                      model=model)
+    elif adm:
         write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0])
     else:
         write_vif_log(vmaf_log, q[-1]["scale"][:, 0])
@@ -327,6 +369,11 @@ def _check_mode_keys(config):
         raise ValueError("vif must be true or false.")
     if "adm" in config and not isinstance(config["adm"], bool):
         raise ValueError("adm must be true or false.")
+    if "motion_feature" in config and not isinstance(config["motion_feature"], bool):
+        raise ValueError("motion_feature must be true or false.")
+    mp = config.get("vmaf_model_path")
+    if mp is not None and not (isinstance(mp, str) and os.path.isfile(mp) and os.access(mp, os.R_OK)):
+        raise ValueError("vmaf_model_path must be null or the path of a readable model file.")
     bs = config.get("batch_size", 100)
     if isinstance(bs, bool) or not isinstance(bs, int) or bs <= 0:
         raise ValueError("batch_size must be a positive integer.")
@@ -356,6 +403,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         "msssim" multi-scale SSIM over the Gaussian window: the ssim stats lines and the SSIM column then carry MS-SSIM),
         vif (true: the row gains VIF_scale0..3, the pooled means of the first plane's VIF on four scales; default false),
         adm (true: the row gains ADM2 and ADM_scale0..3, the pooled means of the first plane's ADM; default false),
+        motion_feature (true: the row gains MOTION2 and MOTION, the pooled means of the first plane's VMAF motion feature of the
+        INPUT stream; default false; the reference's vmaf_model_path, when not null, names a libvmaf model file: it turns vif, adm
+        and motion_feature on and the row gains VMAF, the pooled mean of the per-frame scores, right after SSIM),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -375,6 +425,12 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     ssim_mode = _SSIM_MODES[config.get("ssim_mode", "gauss")]
     vif = config.get("vif", False)
     adm = config.get("adm", False)
+    mot = config.get("motion_feature", False)
+    model = None
+    if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
+        from . import vmaf_model
+        model = vmaf_model.load_model(config["vmaf_model_path"])
+        vif = adm = mot = True
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -417,13 +473,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         planes = LAYOUTS[layout][0](h, w)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
-            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm),
+            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm:
-            _write_feature_log(vmaf_log, _q, vif, adm)
+        if vif or adm or mot:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -457,19 +513,24 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             match = re.search(r"All:(\s*\d+\.\d+)", f.read())
             if match:
                 metrics["SSIM"] = float(match.group(1))
-    if os.path.isfile(vmaf_log):   # this build's JSON (write_vif_log): the pooled means; there is no VMAF value to add
+    if os.path.isfile(vmaf_log):   # this build's JSON (write_vif_log): the pooled means; VMAF when a model scored the frames
         import json
         try:
             with open(vmaf_log) as f:
                 pooled = json.load(f).get("pooled_metrics", {})
         except (ValueError, AttributeError):   # not a JSON log (libvmaf writes XML by default): nothing to add
             pooled = {}
+        if "vmaf" in pooled:       # (:172-173), placed where the reference puts it: right after SSIM
+            metrics["VMAF"] = float(pooled["vmaf"]["mean"])
         for s in range(N.VIF_LEVELS):
             if "vif_scale%d" % s in pooled:
                 metrics["VIF_scale%d" % s] = float(pooled["vif_scale%d" % s]["mean"])
         for k in ["adm2"] + ["adm_scale%d" % s for s in range(N.ADM_LEVELS)]:
             if k in pooled:
                 metrics[k.upper().replace("SCALE", "scale")] = float(pooled[k]["mean"])
+        for k in ("motion2", "motion"):
+            if k in pooled:
+                metrics[k.upper()] = float(pooled[k]["mean"])
     return metrics
 
 
@@ -492,7 +553,8 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature;
+    #                           and that a vmaf_model_path names a readable file
 
 
 def main(argv=None):
