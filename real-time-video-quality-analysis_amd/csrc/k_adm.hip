@@ -44,16 +44,9 @@ constexpr float LO0 = 0.482962913144690f, LO1 = 0.836516303737469f, LO2 = 0.2241
 constexpr float HI0 = -0.129409522550921f, HI1 = -0.224143868041857f, HI2 = 0.836516303737469f, HI3 = -0.482962913144690f;
 constexpr float COS2_1DEG = 0.99969541350954785f;   // cos^2(1 degree)
 
-// one scale's input of both images of a group of same-geometry planes; every stride in bytes
-struct adm_src {
-    const uint8_t *ref, *dist;
-    int64_t ref_fs, dist_fs;   // frame strides
-    int64_t off[4];            // plane offsets inside a frame
-    int64_t row_stride;
-    int step;
-    float sc;                  // 2^-(depth - 8) for integer samples (the fp32 a bands are centred already)
-    int w, h;
-};
+// One scale's input of both images of a group is a pair_src (vqa_dev.hpp; the fp32 a bands are centred already).  Borders:
+// reflect_clamp is the DWT's index rule (|k|, then k >= n reads 2n - k - 1), then a clamp: positions no in-band sample reads
+// stay in the plane.
 
 struct adm_geo {
     int bw, bh;                      // band dims: ceil(h / 2), ceil(w / 2)
@@ -62,19 +55,6 @@ struct adm_geo {
     float rf_hv, rf_d;
     int write_a;
 };
-
-template <typename T>
-__device__ __forceinline__ float adm_ld(const uint8_t *p, float sc) { return fmaf((float)*(const T *)p, sc, -128.f); }
-template <>
-__device__ __forceinline__ float adm_ld<float>(const uint8_t *p, float) { return *(const float *)p; }
-
-// the DWT's index rule (|k|, then k >= n reads 2n - k - 1), then a clamp: positions no in-band sample reads stay in the plane
-__device__ __forceinline__ int adm_mirror(int k, int n)
-{
-    k = k < 0 ? -k : k;
-    k = k >= n ? 2 * n - k - 1 : k;
-    return min(max(k, 0), n - 1);
-}
 
 // never contracted with the addition that follows: the num and the den sums of identical planes take the same roundings
 __device__ __forceinline__ float cube(float x) { return __fmul_rn(__fmul_rn(x, x), x); }
@@ -92,7 +72,7 @@ __device__ __forceinline__ float adm_restore(float o, float t, bool flag)
 // grid = (tiles * count, n_frames); block = 256
 // a_out: [image][frame][plane of the group][bh][bw] fp32;  part: [frame][plane of the group][tile][6] doubles
 template <typename T>
-__global__ __launch_bounds__(256) void k_adm_scale(adm_src s, adm_geo g, int count, float *__restrict__ a_out,
+__global__ __launch_bounds__(256) void k_adm_scale(pair_src s, adm_geo g, int count, float *__restrict__ a_out,
                                                    double *__restrict__ part)
 {
     __shared__ float in[2][IH][IW];       // after the vertical pass: M, the three |rf r| and the three |rf o| maps, [7][EH][EW]
@@ -105,9 +85,9 @@ __global__ __launch_bounds__(256) void k_adm_scale(adm_src s, adm_geo g, int cou
     // (1) tile position (j, c) holds input (2 by0 - 3 + j, 2 bx0 - 3 + c)
     for (int i = t; i < IH * IW; i += 256) {
         const int j = i / IW, c = i - j * IW;
-        const int64_t o = (int64_t)adm_mirror(2 * by0 - 3 + j, s.h) * s.row_stride + (int64_t)adm_mirror(2 * bx0 - 3 + c, s.w) * s.step;
-        in[0][j][c] = adm_ld<T>(pr + o, s.sc);
-        in[1][j][c] = adm_ld<T>(pd + o, s.sc);
+        const int64_t o = (int64_t)reflect_clamp(2 * by0 - 3 + j, s.h) * s.row_stride + (int64_t)reflect_clamp(2 * bx0 - 3 + c, s.w) * s.step;
+        in[0][j][c] = ld_centred<T>(pr + o, s.sc);
+        in[1][j][c] = ld_centred<T>(pd + o, s.sc);
     }
     __syncthreads();
     // (2) band row by0 - 1 + e reads tile rows 2e .. 2e + 3
@@ -255,12 +235,12 @@ void launch_adm_scale(hipStream_t st, const uint8_t *ref, const uint8_t *dist, i
 {
     if (n <= 0 || count <= 0 || scale < 0 || scale >= ADM_LEVELS) return;
     const adm_layout L = adm_levels(n, count, planes[idx[0]].height, planes[idx[0]].width);
-    adm_src s;
+    pair_src s;
     s.w = L.w[scale]; s.h = L.h[scale];
     if (scale == 0) {
         const vqa_plane_desc &pd = planes[idx[0]];
         s.ref = ref; s.dist = dist; s.ref_fs = ref_frame_stride; s.dist_fs = dist_frame_stride;
-        for (int i = 0; i < 4; i++) s.off[i] = planes[idx[i < count ? i : 0]].offset;
+        group_slots(planes, idx, count, s.off, nullptr);
         s.row_stride = pd.row_stride; s.step = pd.pixel_step;
         s.sc = 1.f / (float)(1 << (depth - 8));
     } else {
@@ -297,7 +277,9 @@ void launch_adm_reduce(hipStream_t st, const double *part, int n, const vqa_plan
 {
     if (n <= 0 || count <= 0) return;
     const adm_layout L = adm_levels(n, count, planes[idx[0]].height, planes[idx[0]].width);
-    const int4 pi = make_int4(idx[0], idx[count > 1 ? 1 : 0], idx[count > 2 ? 2 : 0], idx[count > 3 ? 3 : 0]);
+    int p4[4];
+    group_slots(planes, idx, count, nullptr, p4);
+    const int4 pi = make_int4(p4[0], p4[1], p4[2], p4[3]);
     hipLaunchKernelGGL(k_adm_reduce, dim3(count, n), dim3(64), 0, st, part, adm_tiles(L.h[scale + 1], L.w[scale + 1]), count, scale,
                        n_planes, pi, sums);
 }

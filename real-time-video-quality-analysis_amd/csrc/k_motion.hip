@@ -40,16 +40,8 @@ struct motion_src {
     int w, h;
 };
 
-template <typename T>
-__device__ __forceinline__ float motion_ld(const uint8_t *p, float sc) { return fmaf((float)*(const T *)p, sc, -128.f); }
-
-// the border rule (VIF's), then a clamp: a tile that hangs over the plane's edge reads (and discards) in-plane samples
-__device__ __forceinline__ int motion_reflect(int i, int n)
-{
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - i - 1 : i;
-    return min(max(i, 0), n - 1);
-}
+// Borders: reflect_clamp (vqa_dev.hpp) is the border rule (VIF's), then a clamp: a tile that hangs over the plane's edge reads
+// (and discards) in-plane samples.
 
 // grid = (tiles * count, n_frames); block = 256.  acc: [frame][plane of the submit] int64, zeroed by the submit
 template <typename T>
@@ -69,9 +61,9 @@ __global__ __launch_bounds__(256) void k_motion_sad(motion_src s, motion_taps tp
     const uint8_t *pp = (f == 0 ? s.prev0 : s.ref + (int64_t)(f - 1) * s.fs) + s.off[ch];
     for (int i = t; i < IH * IW; i += 256) {
         const int j = i / IW, c = i - j * IW;
-        const int64_t o = (int64_t)motion_reflect(y0 + j - R, s.h) * s.row_stride + (int64_t)motion_reflect(x0 + c - R, s.w) * s.step;
-        in[0][j][c] = motion_ld<T>(pc + o, s.sc);
-        in[1][j][c] = motion_ld<T>(pp + o, s.sc);
+        const int64_t o = (int64_t)reflect_clamp(y0 + j - R, s.h) * s.row_stride + (int64_t)reflect_clamp(x0 + c - R, s.w) * s.step;
+        in[0][j][c] = ld_centred<T>(pc + o, s.sc);
+        in[1][j][c] = ld_centred<T>(pp + o, s.sc);
     }
     __syncthreads();
     // vertical pass, both images: taps in ascending order
@@ -128,14 +120,15 @@ void launch_motion_sad(hipStream_t st, const uint8_t *ref, const uint8_t *prev0,
     const vqa_plane_desc &pd = planes[idx[0]];
     motion_src s;
     s.ref = ref; s.prev0 = prev0; s.fs = frame_stride;
-    for (int i = 0; i < 4; i++) s.off[i] = planes[idx[i < count ? i : 0]].offset;
+    int p4[4];
+    group_slots(planes, idx, count, s.off, p4);
     s.row_stride = pd.row_stride; s.step = pd.pixel_step;
     s.sc = 1.f / (float)(1 << (depth - 8));
     s.w = pd.width; s.h = pd.height;
     motion_taps tp;
     for (int k = 0; k < 5; k++) tp.t[k] = (float)MOTION_TAPS[k];
     const int tiles_x = (s.w + 63) / 64, tiles = tiles_x * ((s.h + 31) / 32);
-    const int4 pi = make_int4(idx[0], idx[count > 1 ? 1 : 0], idx[count > 2 ? 2 : 0], idx[count > 3 ? 3 : 0]);
+    const int4 pi = make_int4(p4[0], p4[1], p4[2], p4[3]);
     const dim3 grid(tiles * count, n), block(256);
     unsigned long long *a = reinterpret_cast<unsigned long long *>(acc);
     if (depth > 8)

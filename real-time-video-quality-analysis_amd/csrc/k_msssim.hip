@@ -112,7 +112,7 @@ void launch_ms_pyramid(hipStream_t st, const uint8_t *ref, const uint8_t *dist, 
     const ms_layout L = ms_levels(n, count, pd.height, pd.width);
     ms_pyr_args a;
     a.count = count;
-    for (int i = 0; i < 4; i++) a.offset[i] = planes[idx[i < count ? i : 0]].offset;
+    group_slots(planes, idx, count, a.offset, nullptr);
     for (int s = 0; s < MS_LEVELS; s++) { a.w[s] = L.w[s]; a.h[s] = L.h[s]; a.off[s] = L.off[s]; }
     const int tiles_x = (pd.width + 63) / 64, tiles = tiles_x * ((pd.height + 63) / 64);
     const dim3 grid(tiles * count, n), block(256);

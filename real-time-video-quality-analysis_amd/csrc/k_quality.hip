@@ -613,7 +613,7 @@ void launch_quality_gauss(hipStream_t st, const uint8_t *ref, const uint8_t *dis
     plane_group g;
     g.count = count;
     g.hscale = 0.f;
-    for (int i = 0; i < 4; i++) { g.offset[i] = planes[idx[i < count ? i : 0]].offset; g.plane_index[i] = idx[i < count ? i : 0]; }
+    group_slots(planes, idx, count, g.offset, g.plane_index);
 #ifdef VQA_AB_VARIANTS
 #define LAUNCH_SSIM(NT, PF, HPF)                                                                                      \
     hipLaunchKernelGGL((k_ssim_gauss<NT, PF, HPF>), dim3((bpp + 7) / 8 * 8 * count, n), dim3(NT), 0, st, ref, dist, ref_frame_stride,\
@@ -677,7 +677,7 @@ void launch_quality_ms_level(hipStream_t st, const uint8_t *ref, const uint8_t *
     g.hscale = ldexpf(depth > 8 ? (float)(255.0 / (double)((1 << depth) - 1)) : 1.f, -2 * level);
     const dim3 grid((bpp + 7) / 8 * 8 * count, n), block(256);
     if (level == 0) {
-        for (int i = 0; i < 4; i++) { g.offset[i] = planes[idx[i < count ? i : 0]].offset; g.plane_index[i] = idx[i < count ? i : 0]; }
+        group_slots(planes, idx, count, g.offset, g.plane_index);
         if (depth > 8)
             hipLaunchKernelGGL((k_ssim_gauss_p2<256, SSIM_ROWS, true, true, false>), grid, block, 0, st, ref, dist, ref_frame_stride,
                                dist_frame_stride, g, pd.row_stride, pd.pixel_step, w, h, ncb, ns, QS, partials,

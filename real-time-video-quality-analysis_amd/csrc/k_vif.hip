@@ -36,33 +36,12 @@ constexpr float VIF_FIX = 134217728.f;   // 2^27
 
 struct vif_taps { float t[17]; };
 
-// one level of both images of a group of same-geometry planes; every stride in bytes
-struct vif_src {
-    const uint8_t *ref, *dist;
-    int64_t ref_fs, dist_fs;   // frame strides
-    int64_t off[4];            // plane offsets inside a frame
-    int64_t row_stride;
-    int step;
-    float sc;                  // 2^-(depth - 8) for integer samples (fp32 levels are centred already)
-    int w, h;
-};
-
-template <typename T>
-__device__ __forceinline__ float vif_ld(const uint8_t *p, float sc) { return fmaf((float)*(const T *)p, sc, -128.f); }
-template <>
-__device__ __forceinline__ float vif_ld<float>(const uint8_t *p, float) { return *(const float *)p; }
-
-// the border rule, then a clamp: a tile that hangs over the plane's edge reads (and discards) in-plane samples
-__device__ __forceinline__ int vif_reflect(int i, int n)
-{
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - i - 1 : i;
-    return min(max(i, 0), n - 1);
-}
+// One level of both images of a group is a pair_src (vqa_dev.hpp).  Borders: reflect_clamp is the border rule stated above
+// (libvmaf's VIF), then a clamp: a tile that hangs over the plane's edge reads (and discards) in-plane samples.
 
 // grid = (tiles * count, n_frames); block = 256.  acc: [frame][plane of the submit][level][num, den] int64
 template <typename T, int R>
-__global__ __launch_bounds__(256) void k_vif_stats(vif_src s, vif_taps tp, int tiles_x, int tiles, int level,
+__global__ __launch_bounds__(256) void k_vif_stats(pair_src s, vif_taps tp, int tiles_x, int tiles, int level,
                                                    int n_planes, int4 plane_index, unsigned long long *__restrict__ acc)
 {
     constexpr int TW = 64, TH = 16, IW = TW + 2 * R, IH = TH + 2 * R, NT = 2 * R + 1;
@@ -77,9 +56,9 @@ __global__ __launch_bounds__(256) void k_vif_stats(vif_src s, vif_taps tp, int t
     const uint8_t *pr = s.ref + (int64_t)f * s.ref_fs + s.off[ch], *pd = s.dist + (int64_t)f * s.dist_fs + s.off[ch];
     for (int i = t; i < IH * IW; i += 256) {
         const int j = i / IW, c = i - j * IW;
-        const int64_t o = (int64_t)vif_reflect(y0 + j - R, s.h) * s.row_stride + (int64_t)vif_reflect(x0 + c - R, s.w) * s.step;
-        in[0][j][c] = vif_ld<T>(pr + o, s.sc);
-        in[1][j][c] = vif_ld<T>(pd + o, s.sc);
+        const int64_t o = (int64_t)reflect_clamp(y0 + j - R, s.h) * s.row_stride + (int64_t)reflect_clamp(x0 + c - R, s.w) * s.step;
+        in[0][j][c] = ld_centred<T>(pr + o, s.sc);
+        in[1][j][c] = ld_centred<T>(pd + o, s.sc);
     }
     if (t < 5 * TH) {   // the pad columns of V are read (never used) by the last float4 of a row
         for (int c = IW; c < VP; c++) V[t / TH][t % TH][c] = 0.f;
@@ -172,7 +151,7 @@ __global__ __launch_bounds__(256) void k_vif_stats(vif_src s, vif_taps tp, int t
 
 // grid = (tiles * count, n_frames, 2 images); block = 256.  out: [image][frame][plane of the group][oh][ow] fp32
 template <typename T, int R>
-__global__ __launch_bounds__(256) void k_vif_decimate(vif_src s, vif_taps tp, int tiles_x, int tiles, int count, int ow,
+__global__ __launch_bounds__(256) void k_vif_decimate(pair_src s, vif_taps tp, int tiles_x, int tiles, int count, int ow,
                                                       int oh, float *__restrict__ out)
 {
     constexpr int TO = 32, IW = 2 * TO + 2 * R, NT = 2 * R + 1;
@@ -185,8 +164,8 @@ __global__ __launch_bounds__(256) void k_vif_decimate(vif_src s, vif_taps tp, in
     const uint8_t *src = (img ? s.dist + (int64_t)f * s.dist_fs : s.ref + (int64_t)f * s.ref_fs) + s.off[ch];
     for (int i = t; i < IW * IW; i += 256) {
         const int j = i / IW, c = i - j * IW;
-        in[j][c] = vif_ld<T>(src + (int64_t)vif_reflect(2 * oy0 + j - R, s.h) * s.row_stride +
-                                 (int64_t)vif_reflect(2 * ox0 + c - R, s.w) * s.step, s.sc);
+        in[j][c] = ld_centred<T>(src + (int64_t)reflect_clamp(2 * oy0 + j - R, s.h) * s.row_stride +
+                                 (int64_t)reflect_clamp(2 * ox0 + c - R, s.w) * s.step, s.sc);
     }
     __syncthreads();
     for (int i = t; i < TO * IW; i += 256) {   // even rows only
@@ -238,15 +217,15 @@ vif_taps taps_of(int level)
 }
 
 // level `lv` of the group as the kernels read it: the caller's planes (lv 0) or the fp32 scratch
-vif_src source_of(int lv, const vif_layout &L, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_fs, int64_t dist_fs,
+pair_src source_of(int lv, const vif_layout &L, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_fs, int64_t dist_fs,
                   const vqa_plane_desc *planes, const int *idx, int count, int depth, const float *scratch)
 {
-    vif_src s;
+    pair_src s;
     s.w = L.w[lv]; s.h = L.h[lv];
     if (lv == 0) {
         const vqa_plane_desc &pd = planes[idx[0]];
         s.ref = ref; s.dist = dist; s.ref_fs = ref_fs; s.dist_fs = dist_fs;
-        for (int i = 0; i < 4; i++) s.off[i] = planes[idx[i < count ? i : 0]].offset;
+        group_slots(planes, idx, count, s.off, nullptr);
         s.row_stride = pd.row_stride; s.step = pd.pixel_step;
         s.sc = 1.f / (float)(1 << (depth - 8));
     } else {
@@ -262,7 +241,7 @@ vif_src source_of(int lv, const vif_layout &L, const uint8_t *ref, const uint8_t
 }
 
 template <int R>
-void stats_level(hipStream_t st, const vif_src &s, int lv, int n, int count, int n_planes, int4 pi, int depth,
+void stats_level(hipStream_t st, const pair_src &s, int lv, int n, int count, int n_planes, int4 pi, int depth,
                  unsigned long long *acc)
 {
     const int tiles_x = (s.w + 63) / 64, tiles = tiles_x * ((s.h + 15) / 16);
@@ -277,7 +256,7 @@ void stats_level(hipStream_t st, const vif_src &s, int lv, int n, int count, int
 }
 
 template <int R>
-void decimate_level(hipStream_t st, const vif_src &s, int lv, int n, int count, int depth, const vif_layout &L, float *scratch)
+void decimate_level(hipStream_t st, const pair_src &s, int lv, int n, int count, int depth, const vif_layout &L, float *scratch)
 {
     const int ow = L.w[lv], oh = L.h[lv];
     const int tiles_x = (ow + 31) / 32, tiles = tiles_x * ((oh + 31) / 32);
@@ -300,8 +279,10 @@ void launch_vif_stats(hipStream_t st, const uint8_t *ref, const uint8_t *dist, i
 {
     if (n <= 0 || count <= 0) return;
     const vif_layout L = vif_levels(n, count, planes[idx[0]].height, planes[idx[0]].width);
-    const vif_src s = source_of(level, L, ref, dist, n, ref_frame_stride, dist_frame_stride, planes, idx, count, depth, scratch);
-    const int4 pi = make_int4(idx[0], idx[count > 1 ? 1 : 0], idx[count > 2 ? 2 : 0], idx[count > 3 ? 3 : 0]);
+    const pair_src s = source_of(level, L, ref, dist, n, ref_frame_stride, dist_frame_stride, planes, idx, count, depth, scratch);
+    int p4[4];
+    group_slots(planes, idx, count, nullptr, p4);
+    const int4 pi = make_int4(p4[0], p4[1], p4[2], p4[3]);
     unsigned long long *a = reinterpret_cast<unsigned long long *>(acc);
     switch (level) {
     case 0: stats_level<8>(st, s, 0, n, count, n_planes, pi, depth, a); break;
@@ -317,7 +298,7 @@ void launch_vif_decimate(hipStream_t st, const uint8_t *ref, const uint8_t *dist
 {
     if (n <= 0 || count <= 0 || level < 1 || level >= VIF_LEVELS) return;
     const vif_layout L = vif_levels(n, count, planes[idx[0]].height, planes[idx[0]].width);
-    const vif_src s = source_of(level - 1, L, ref, dist, n, ref_frame_stride, dist_frame_stride, planes, idx, count, depth, scratch);
+    const pair_src s = source_of(level - 1, L, ref, dist, n, ref_frame_stride, dist_frame_stride, planes, idx, count, depth, scratch);
     switch (level) {
     case 1: decimate_level<4>(st, s, 1, n, count, depth, L, scratch); break;
     case 2: decimate_level<2>(st, s, 2, n, count, depth, L, scratch); break;

@@ -26,6 +26,11 @@ struct dbuf {
     size_t cap = 0;
 };
 
+struct hbuf {   // pinned host staging of result records (grow-only, like dbuf)
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
 struct resize_tabs {
     int32_t *xofs = nullptr, *xa = nullptr, *yofs = nullptr, *yb = nullptr;
     int mode = 0;
@@ -64,19 +69,17 @@ struct vqa_ctx {
     dbuf qres_dev, qpartials, qstage_ref, qstage_dist;
     dbuf qms_pyr, qms_dev;   // VQA_SSIM_MS: pyramid levels 1..4 of the largest plane group seen; per-entry scale means
     // pinned host staging
-    void *res_host = nullptr; size_t res_host_cap = 0;
-    void *qres_host = nullptr; size_t qres_host_cap = 0;
-    void *qms_host = nullptr; size_t qms_host_cap = 0;
+    hbuf res_host, qres_host, qms_host;
     // vqa_vif_submit: levels 1..3 of the largest plane group seen; the integer totals; the records (device, pinned host)
     dbuf vif_pyr, vif_acc, vif_dev;
-    void *vif_host = nullptr; size_t vif_host_cap = 0;
+    hbuf vif_host;
     // vqa_adm_submit: the a bands of scales 0..2 of the largest plane group seen; one scale's tile partials; the six sums per
     // (entry, scale) (device, pinned host)
     dbuf adm_pyr, adm_part, adm_sums;
-    void *adm_host = nullptr; size_t adm_host_cap = 0;
+    hbuf adm_host;
     // vqa_motion_submit: the integer totals (device, pinned host); host frames and their prev0 staged on the device
     dbuf mot_acc, mot_stage, mot_prev;
-    void *mot_host = nullptr; size_t mot_host_cap = 0;
+    hbuf mot_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -178,6 +181,9 @@ static int sync_all(vqa_ctx *c)
     return VQA_OK;
 }
 
+// a submitted batch of any kind has not been waited for
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m; }
+
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
 {
@@ -206,14 +212,14 @@ static int ensure(vqa_ctx *c, dbuf &b, size_t bytes)
     return VQA_OK;
 }
 
-static int ensure_pinned(vqa_ctx *c, void *&p, size_t &cap, size_t bytes)
+static int ensure_pinned(vqa_ctx *c, hbuf &b, size_t bytes)
 {
-    if (bytes <= cap) return VQA_OK;
+    if (bytes <= b.cap) return VQA_OK;
     if (int rc = sync_all(c)) return rc;
-    if (p) HIPCHK(c, hipHostFree(p));
-    p = nullptr; cap = 0;
-    HIPCHK(c, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    cap = bytes;
+    if (b.p) HIPCHK(c, hipHostFree(b.p));
+    b.p = nullptr; b.cap = 0;
+    HIPCHK(c, hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+    b.cap = bytes;
     return VQA_OK;
 }
 
@@ -783,7 +789,7 @@ int vqa_create(int device, vqa_ctx **out)
 int vqa_set_option(vqa_ctx *c, int option, int value)
 {
     if (!c) return VQA_ERR_INVALID;
-    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m) return VQA_ERR_STATE; // options apply to whole submits
+    if (busy(c)) return VQA_ERR_STATE; // options apply to whole submits
     switch (option) {
     case VQA_OPT_OVERLAP: c->opt_overlap = value != 0; return VQA_OK;
     case VQA_OPT_HYST_STATS: c->opt_hyst_stats = value != 0; return VQA_OK;
@@ -826,14 +832,10 @@ static void release_scratch(vqa_ctx *c)
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    if (c->res_host) (void)hipHostFree(c->res_host);
-    if (c->qres_host) (void)hipHostFree(c->qres_host);
-    if (c->qms_host) (void)hipHostFree(c->qms_host);
-    if (c->vif_host) (void)hipHostFree(c->vif_host);
-    if (c->adm_host) (void)hipHostFree(c->adm_host);
-    if (c->mot_host) (void)hipHostFree(c->mot_host);
-    c->res_host = c->qres_host = c->qms_host = c->vif_host = c->adm_host = c->mot_host = nullptr;
-    c->res_host_cap = c->qres_host_cap = c->qms_host_cap = c->vif_host_cap = c->adm_host_cap = c->mot_host_cap = 0;
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host}) {
+        if (b->p) (void)hipHostFree(b->p);
+        b->p = nullptr; b->cap = 0;
+    }
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
 }
@@ -841,7 +843,7 @@ static void release_scratch(vqa_ctx *c)
 int vqa_trim(vqa_ctx *c)
 {
     if (!c) return VQA_ERR_INVALID;
-    if (c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m) return VQA_ERR_STATE;
+    if (busy(c)) return VQA_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     prof_collect(c);
@@ -1040,7 +1042,7 @@ static int complexity_submit_body(vqa_ctx *c, const uint8_t *frames, const uint8
 
     int rc = ensure(c, c->res_dev, sizeof(vqa_frame_metrics) * (size_t)n);
     if (rc) return rc;
-    rc = ensure_pinned(c, c->res_host, c->res_host_cap, sizeof(vqa_frame_metrics) * (size_t)n);
+    rc = ensure_pinned(c, c->res_host, sizeof(vqa_frame_metrics) * (size_t)n);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->res_dev.p, 0, sizeof(vqa_frame_metrics) * (size_t)n, st));
     vqa_frame_metrics *const res_all = (vqa_frame_metrics *)c->res_dev.p;
@@ -1280,12 +1282,12 @@ static int complexity_submit_body(vqa_ctx *c, const uint8_t *frames, const uint8
 
     HIPCHK(c, hipGetLastError());
     if (want_gh || want_ch) {
-        HIPCHK(c, hipMemcpyAsync(c->res_host, c->res_dev.p, sizeof(vqa_frame_metrics) * (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(c->res_host.p, c->res_dev.p, sizeof(vqa_frame_metrics) * (size_t)n, hipMemcpyDeviceToHost, st));
         c->pend_c_tail_only = false;
     } else {
         // no histogram was asked for: bring back only the 0.6 KB of scalars behind the 4 KB of bins of each record
         const size_t off = offsetof(vqa_frame_metrics, sum_gray2), tail = sizeof(vqa_frame_metrics) - off;
-        HIPCHK(c, hipMemcpy2DAsync((uint8_t *)c->res_host + off, sizeof(vqa_frame_metrics), (uint8_t *)c->res_dev.p + off,
+        HIPCHK(c, hipMemcpy2DAsync((uint8_t *)c->res_host.p + off, sizeof(vqa_frame_metrics), (uint8_t *)c->res_dev.p + off,
                                    sizeof(vqa_frame_metrics), tail, (size_t)n, hipMemcpyDeviceToHost, st));
         c->pend_c_tail_only = true;
     }
@@ -1310,7 +1312,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
     if (!c->pend_c || n != c->pend_c) return VQA_ERR_STATE;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    memcpy(out, c->res_host, sizeof(vqa_frame_metrics) * (size_t)n);
+    memcpy(out, c->res_host.p, sizeof(vqa_frame_metrics) * (size_t)n);
     for (int i = 0; i < n; i++) {
         if (c->pend_c_tail_only) memset(&out[i], 0, offsetof(vqa_frame_metrics, sum_gray2)); // bins were not computed
         out[i].has_prev = (i > 0 || c->pend_c_prev0) ? 1u : 0u;
@@ -1330,101 +1332,176 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
+// What the four plane-batch submits (quality, VIF, ADM, motion) share: the checks, the staging of host frames, the walk over
+// slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
+extern "C++" {   // (templates among them)
+
+// arguments and mem_kind (dist: the second stream; a submit that has none passes `ref` again)
+static bool bad_batch_args(const vqa_ctx *c, const void *ref, const void *dist, int mem_kind, int n, const vqa_plane_desc *planes,
+                           int n_planes)
+{
+    return !c || !ref || !dist || n <= 0 || !planes || n_planes <= 0 || n_planes > 4 ||
+           (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE);
+}
+
+struct plane_batch {
+    int depth, bps;   // bits and bytes per sample
+    int64_t span;     // bytes from a frame's first byte to the end of its last plane
+};
+
+// The descriptor rules, per plane in plane order: depth, 16-bit alignment, geometry (VQA_ERR_INVALID), then limits(d) - the
+// metric's own VQA_ERR_UNSUPPORTED rules - and only then the next plane.  The order decides the status of a list that breaks
+// several rules at once.  The frame strides are the caller's to check against B.span, after all planes.
+template <class F> static int check_planes(const vqa_plane_desc *planes, int n_planes, plane_batch &B, F limits)
+{
+    // sample depth (vqa_plane_desc.bit_depth): 0 / 8 = uint8, 9..16 = little-endian uint16 at even byte offsets, strides and
+    // steps; one depth per submit (FFmpeg's filters see one pixel format per frame)
+    B.depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
+    if (B.depth < 8 || B.depth > 16) return VQA_ERR_INVALID;
+    B.bps = B.depth > 8 ? 2 : 1;
+    B.span = 0;
+    for (int p = 0; p < n_planes; p++) {
+        const vqa_plane_desc &d = planes[p];
+        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != B.depth) return VQA_ERR_INVALID;
+        if (B.bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
+        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
+            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - B.bps))
+            return VQA_ERR_INVALID;
+        if (int rc = limits(d)) return rc;
+        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + B.bps;
+        B.span = end > B.span ? end : B.span;
+    }
+    return VQA_OK;
+}
+
+// the limits of VIF, ADM and motion: a smallest side, and the 2^28 samples that bound the 64-bit totals and the sums (vqa.h)
+static int side_and_area_limits(const vqa_plane_desc &d, int min_dim)
+{
+    if (d.width < min_dim || d.height < min_dim) return VQA_ERR_UNSUPPORTED;
+    if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;
+    return VQA_OK;
+}
+
+// host frames brought to the device: `buf` grown to hold them, the copy enqueued on the ctx stream, `frames` moved to the copy
+static int stage(vqa_ctx *c, dbuf &buf, const uint8_t *&frames, size_t bytes)
+{
+    if (int rc = ensure(c, buf, bytes)) return rc;
+    HIPCHK(c, hipMemcpyAsync(buf.p, frames, bytes, hipMemcpyHostToDevice, c->stream));
+    frames = (const uint8_t *)buf.p;
+    return VQA_OK;
+}
+
+// the two host streams of a quality, a VIF or an ADM submit.  The three share qstage_*: the stream orders a batch behind
+// whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
+static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs, const uint8_t *&dist,
+                      int64_t dist_fs)
+{
+    if (mem_kind != VQA_MEM_HOST) return VQA_OK;
+    if (int rc = stage(c, c->qstage_ref, ref, (size_t)(n - 1) * ref_fs + span)) return rc;
+    return stage(c, c->qstage_dist, dist, (size_t)(n - 1) * dist_fs + span);
+}
+
+constexpr int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
+
+// body(a0, m): frames a0 .. a0 + m - 1 of the batch
+template <class F> static void for_each_slice(int n, F body)
+{
+    for (int a0 = 0; a0 < n; a0 += QSLICE) body(a0, n - a0 < QSLICE ? n - a0 : QSLICE);
+}
+
+// body(idx, cnt): planes of identical geometry (B,G,R of packed BGR; U,V of 4:2:0) go out as one group
+template <class F> static void for_each_group(const vqa_plane_desc *planes, int n_planes, F body)
+{
+    bool done[4] = {false, false, false, false};
+    for (int p = 0; p < n_planes; p++) {
+        if (done[p]) continue;
+        int idx[4], cnt = 0;
+        for (int q = p; q < n_planes; q++) {
+            if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
+                planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
+                idx[cnt++] = q;
+                done[q] = true;
+            }
+        }
+        body(idx, cnt);
+    }
+}
+
+// Scratch that serves one group of same-geometry planes at a time (the groups follow each other on the stream) is sized by the
+// largest group, which no grouping of the planes can exceed when every plane is counted at the largest size: the most bytes(cnt,
+// height, width) over the planes, cnt being the planes of that width and height (for_each_group compares strides and steps as
+// well: its groups are no larger)
+template <class F> static size_t largest_group_bytes(const vqa_plane_desc *planes, int n_planes, F bytes)
+{
+    size_t most = 0;
+    for (int p = 0; p < n_planes; p++) {
+        int cnt = 0;
+        for (int q = 0; q < n_planes; q++) cnt += planes[q].width == planes[p].width && planes[q].height == planes[p].height;
+        const size_t b = bytes(cnt, planes[p].height, planes[p].width);
+        most = b > most ? b : most;
+    }
+    return most;
+}
+
+// a public submit: the body, then the drain if it failed after it had started to enqueue
+template <class F> static int submit_and_drain(vqa_ctx *c, F body)
+{
+    bool touched = false;
+    const int rc = body(touched);
+    return drain_failed_submit(c, rc, touched);
+}
+
+} // extern "C++"
+
+// ---------------------------------------------------------------------------
 static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                                int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int ssim_mode, bool &touched)
 {
-    if (!c || !ref || !dist || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
-    if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (ssim_mode != VQA_SSIM_GAUSS && ssim_mode != VQA_SSIM_FFMPEG && ssim_mode != VQA_SSIM_MS) return VQA_ERR_INVALID;
     if (c->pend_q) return VQA_ERR_STATE;
     const bool ms = ssim_mode == VQA_SSIM_MS, gauss = ms || ssim_mode == VQA_SSIM_GAUSS;   // MS: the Gaussian window on five scales
-    int64_t span = 0;
     int maxblocks = 1;
-    // sample depth (vqa_plane_desc.bit_depth): 0 / 8 = uint8, 9..16 = little-endian uint16 at even byte offsets, strides and
-    // steps; one depth per submit (FFmpeg's filters see one pixel format per frame)
-    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
-    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
-    const int bps = depth > 8 ? 2 : 1;   // bytes per sample
-    for (int p = 0; p < n_planes; p++) {
-        const vqa_plane_desc &d = planes[p];
-        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
-        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
-        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
-            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
-            return VQA_ERR_INVALID;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
         // k_ssim_gauss addresses a strip's rows through a 32-bit scalar buffer offset (row * row_stride) plus a 32-bit
         // lane offset: a plane whose rows span 2 GiB (absurd strides / regions of interest only) would wrap silently
         if (gauss &&
-            (int64_t)d.height * d.row_stride + (int64_t)d.width * d.pixel_step + bps >= ((int64_t)1 << 31)) return VQA_ERR_UNSUPPORTED;
+            (int64_t)d.height * d.row_stride + (int64_t)d.width * d.pixel_step + B.bps >= ((int64_t)1 << 31)) return VQA_ERR_UNSUPPORTED;
         if (gauss && (d.width < 11 || d.height < 11)) return VQA_ERR_UNSUPPORTED;
         if (ms && (d.width < MS_MIN_DIM || d.height < MS_MIN_DIM)) return VQA_ERR_UNSUPPORTED;   // level 4 must hold a window
         if (ssim_mode == VQA_SSIM_FFMPEG && (d.width < 8 || d.height < 8)) return VQA_ERR_UNSUPPORTED;
-        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
-        span = end > span ? end : span;
         const int b = gauss ? ssim_gauss_blocks(d.height, d.width) : ssim_ffmpeg_blocks(d.height, d.width);
         maxblocks = b > maxblocks ? b : maxblocks;
-    }
-    if (n > 1 && (ref_fs < span || dist_fs < span)) return VQA_ERR_INVALID;
+        return VQA_OK;
+    });
+    if (rc) return rc;
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     touched = true;
-    const uint8_t *dref = ref, *ddist = dist;
-    if (mem_kind == VQA_MEM_HOST) {
-        const size_t rs = (size_t)(n - 1) * ref_fs + span, ds = (size_t)(n - 1) * dist_fs + span;
-        int rc = ensure(c, c->qstage_ref, rs);
-        if (rc) return rc;
-        rc = ensure(c, c->qstage_dist, ds);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->qstage_ref.p, ref, rs, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->qstage_dist.p, dist, ds, hipMemcpyHostToDevice, st));
-        dref = (const uint8_t *)c->qstage_ref.p;
-        ddist = (const uint8_t *)c->qstage_dist.p;
-    }
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
-    int rc = ensure(c, c->qres_dev, sizeof(vqa_plane_metrics) * nent);
-    if (rc) return rc;
-    rc = ensure_pinned(c, c->qres_host, c->qres_host_cap, sizeof(vqa_plane_metrics) * nent);
-    if (rc) return rc;
-    const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
-    const int nslice = n < QSLICE ? n : QSLICE;
+    if ((rc = ensure(c, c->qres_dev, sizeof(vqa_plane_metrics) * nent))) return rc;
+    if ((rc = ensure_pinned(c, c->qres_host, sizeof(vqa_plane_metrics) * nent))) return rc;
+    const int nslice = n < QSLICE ? n : QSLICE, depth = B.depth;
     // (MS: a second half of the same size for the cs totals; level 0 has the most tiles)
-    rc = ensure(c, c->qpartials, sizeof(double) * (size_t)maxblocks * nslice * n_planes * (ms ? 2 : 1));
-    if (rc) return rc;
+    if ((rc = ensure(c, c->qpartials, sizeof(double) * (size_t)maxblocks * nslice * n_planes * (ms ? 2 : 1)))) return rc;
     if (ms) {
-        // the pyramid scratch serves one group of same-geometry planes at a time (the groups follow each other on the stream):
-        // sized by the largest group, which no grouping of the planes can exceed when every plane is counted at the largest size
-        size_t pyr = 0;
-        for (int p = 0; p < n_planes; p++) {
-            int cnt = 0;
-            for (int q = 0; q < n_planes; q++) cnt += planes[q].width == planes[p].width && planes[q].height == planes[p].height;
-            const size_t b = sizeof(float) * (size_t)ms_levels(nslice, cnt, planes[p].height, planes[p].width).total;
-            pyr = b > pyr ? b : pyr;
-        }
-        rc = ensure(c, c->qms_pyr, pyr);
-        if (rc) return rc;
-        rc = ensure(c, c->qms_dev, sizeof(vqa_ms_scales) * nent);
-        if (rc) return rc;
-        rc = ensure_pinned(c, c->qms_host, c->qms_host_cap, sizeof(vqa_ms_scales) * nent);
-        if (rc) return rc;
+        // the pyramid scratch: levels 1..4 of the largest plane group
+        const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
+            return sizeof(float) * (size_t)ms_levels(nslice, cnt, h, w).total;
+        });
+        if ((rc = ensure(c, c->qms_pyr, pyr))) return rc;
+        if ((rc = ensure(c, c->qms_dev, sizeof(vqa_ms_scales) * nent))) return rc;
+        if ((rc = ensure_pinned(c, c->qms_host, sizeof(vqa_ms_scales) * nent))) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->qres_dev.p, 0, sizeof(vqa_plane_metrics) * nent, st));
     const int64_t pstride = (int64_t)maxblocks * nslice;
-    for (int a0 = 0; a0 < n; a0 += QSLICE) {
-        const int m = n - a0 < QSLICE ? n - a0 : QSLICE;
+    for_each_slice(n, [&](int a0, int m) {
         vqa_plane_metrics *res = (vqa_plane_metrics *)c->qres_dev.p + (size_t)a0 * n_planes;
-        const uint8_t *sref = dref + (int64_t)a0 * ref_fs, *sdist = ddist + (int64_t)a0 * dist_fs;
-        // planes of identical geometry (B,G,R of packed BGR; U,V of 4:2:0) go out as one group
-        bool done[4] = {false, false, false, false};
-        for (int p = 0; p < n_planes; p++) {
-            if (done[p]) continue;
-            int idx[4], cnt = 0;
-            for (int q = p; q < n_planes; q++) {
-                if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
-                    planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
-                    idx[cnt++] = q;
-                    done[q] = true;
-                }
-            }
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             if (ms) {
                 // one pyramid launch, then the five scales one after another on the ctx stream (each level's totals leave the
                 // partials through its finalize before the next level's kernel overwrites them)
@@ -1438,7 +1515,7 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
                     launch_quality_ms_level(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes,
                                             (double *)c->qpartials.p, pstride, res, depth, lv, (const float *)c->qms_pyr.p, msd);
                 }
-                continue;
+                return;
             }
             prof_scope ps_(c, ssim_mode == VQA_SSIM_GAUSS ? VQA_K_SSIM_GAUSS : VQA_K_SSIM_FFMPEG);
             if (ssim_mode == VQA_SSIM_GAUSS)
@@ -1447,12 +1524,12 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
             else
                 launch_quality_ffmpeg(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes,
                                       (double *)c->qpartials.p, pstride, res, depth);
-        }
-    }
+        });
+    });
     if (ms) launch_ms_combine(st, (const vqa_ms_scales *)c->qms_dev.p, (int)nent, (vqa_plane_metrics *)c->qres_dev.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->qres_host, c->qres_dev.p, sizeof(vqa_plane_metrics) * nent, hipMemcpyDeviceToHost, st));
-    if (ms) HIPCHK(c, hipMemcpyAsync(c->qms_host, c->qms_dev.p, sizeof(vqa_ms_scales) * nent, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->qres_host.p, c->qres_dev.p, sizeof(vqa_plane_metrics) * nent, hipMemcpyDeviceToHost, st));
+    if (ms) HIPCHK(c, hipMemcpyAsync(c->qms_host.p, c->qms_dev.p, sizeof(vqa_ms_scales) * nent, hipMemcpyDeviceToHost, st));
     c->pend_q_ms = ms;
     c->pend_q = (int)nent;
     return VQA_OK;
@@ -1461,9 +1538,9 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
 int vqa_quality_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                        int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int ssim_mode)
 {
-    bool touched = false;
-    const int rc = quality_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, ssim_mode, touched);
-    return drain_failed_submit(c, rc, touched);
+    return submit_and_drain(c, [&](bool &touched) {
+        return quality_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, ssim_mode, touched);
+    });
 }
 
 int vqa_quality_wait_ms(vqa_ctx *c, vqa_plane_metrics *out, vqa_ms_scales *scales, int n_entries)
@@ -1473,8 +1550,8 @@ int vqa_quality_wait_ms(vqa_ctx *c, vqa_plane_metrics *out, vqa_ms_scales *scale
     if (scales && !c->pend_q_ms) return VQA_ERR_STATE;   // (the batch stays pending: vqa_quality_wait collects it)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    memcpy(out, c->qres_host, sizeof(vqa_plane_metrics) * (size_t)n_entries);
-    if (scales) memcpy(scales, c->qms_host, sizeof(vqa_ms_scales) * (size_t)n_entries);
+    memcpy(out, c->qres_host.p, sizeof(vqa_plane_metrics) * (size_t)n_entries);
+    if (scales) memcpy(scales, c->qms_host.p, sizeof(vqa_ms_scales) * (size_t)n_entries);
     c->pend_q = 0;
     c->pend_q_ms = false;
     return VQA_OK;
@@ -1491,78 +1568,32 @@ int vqa_quality_wait(vqa_ctx *c, vqa_plane_metrics *out, int n_entries)
 static int vif_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
-    if (!c || !ref || !dist || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
-    if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (c->pend_v) return VQA_ERR_STATE;
-    int64_t span = 0;
-    // depth, alignment and mixed depths: the rules of vqa_quality_submit
-    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
-    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
-    const int bps = depth > 8 ? 2 : 1;
-    for (int p = 0; p < n_planes; p++) {
-        const vqa_plane_desc &d = planes[p];
-        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
-        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
-        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
-            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
-            return VQA_ERR_INVALID;
-        if (d.width < VIF_MIN_DIM || d.height < VIF_MIN_DIM) return VQA_ERR_UNSUPPORTED;
-        if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;   // the bound of the 64-bit totals (vqa.h)
-        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
-        span = end > span ? end : span;
-    }
-    if (n > 1 && (ref_fs < span || dist_fs < span)) return VQA_ERR_INVALID;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, VIF_MIN_DIM); });
+    if (rc) return rc;
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     touched = true;
-    const uint8_t *dref = ref, *ddist = dist;
-    if (mem_kind == VQA_MEM_HOST) {
-        const size_t rs = (size_t)(n - 1) * ref_fs + span, ds = (size_t)(n - 1) * dist_fs + span;
-        int rc = ensure(c, c->qstage_ref, rs);
-        if (rc) return rc;
-        rc = ensure(c, c->qstage_dist, ds);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->qstage_ref.p, ref, rs, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->qstage_dist.p, dist, ds, hipMemcpyHostToDevice, st));
-        dref = (const uint8_t *)c->qstage_ref.p;
-        ddist = (const uint8_t *)c->qstage_dist.p;
-    }
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(long long) * 2 * VIF_LEVELS * nent;
-    int rc = ensure(c, c->vif_acc, acc_bytes);
-    if (rc) return rc;
-    rc = ensure(c, c->vif_dev, sizeof(vqa_vif_metrics) * nent);
-    if (rc) return rc;
-    rc = ensure_pinned(c, c->vif_host, c->vif_host_cap, sizeof(vqa_vif_metrics) * nent);
-    if (rc) return rc;
-    const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
-    const int nslice = n < QSLICE ? n : QSLICE;
-    // the level scratch serves one group of same-geometry planes at a time, as the pyramid of VQA_SSIM_MS does
-    size_t pyr = 0;
-    for (int p = 0; p < n_planes; p++) {
-        int cnt = 0;
-        for (int q = 0; q < n_planes; q++) cnt += planes[q].width == planes[p].width && planes[q].height == planes[p].height;
-        const size_t b = sizeof(float) * (size_t)vif_levels(nslice, cnt, planes[p].height, planes[p].width).total;
-        pyr = b > pyr ? b : pyr;
-    }
-    rc = ensure(c, c->vif_pyr, pyr);
-    if (rc) return rc;
+    if ((rc = ensure(c, c->vif_acc, acc_bytes))) return rc;
+    if ((rc = ensure(c, c->vif_dev, sizeof(vqa_vif_metrics) * nent))) return rc;
+    if ((rc = ensure_pinned(c, c->vif_host, sizeof(vqa_vif_metrics) * nent))) return rc;
+    const int nslice = n < QSLICE ? n : QSLICE, depth = B.depth;
+    // the level scratch: levels 1..3 of the largest plane group
+    const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
+        return sizeof(float) * (size_t)vif_levels(nslice, cnt, h, w).total;
+    });
+    if ((rc = ensure(c, c->vif_pyr, pyr))) return rc;
     HIPCHK(c, hipMemsetAsync(c->vif_acc.p, 0, acc_bytes, st));
-    for (int a0 = 0; a0 < n; a0 += QSLICE) {
-        const int m = n - a0 < QSLICE ? n - a0 : QSLICE;
+    for_each_slice(n, [&](int a0, int m) {
         long long *acc = (long long *)c->vif_acc.p + (size_t)a0 * n_planes * 2 * VIF_LEVELS;
-        const uint8_t *sref = dref + (int64_t)a0 * ref_fs, *sdist = ddist + (int64_t)a0 * dist_fs;
-        bool done[4] = {false, false, false, false};
-        for (int p = 0; p < n_planes; p++) {
-            if (done[p]) continue;
-            int idx[4], cnt = 0;
-            for (int q = p; q < n_planes; q++) {
-                if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
-                    planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
-                    idx[cnt++] = q;
-                    done[q] = true;
-                }
-            }
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             float *scratch = (float *)c->vif_pyr.p;
             for (int lv = 0; lv < VIF_LEVELS; lv++) {
                 if (lv > 0) {
@@ -1572,11 +1603,11 @@ static int vif_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
                 prof_scope ps_(c, VQA_K_VIF);
                 launch_vif_stats(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes, depth, lv, scratch, acc);
             }
-        }
-    }
+        });
+    });
     launch_vif_finalize(st, (const long long *)c->vif_acc.p, (int)nent, (vqa_vif_metrics *)c->vif_dev.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->vif_host, c->vif_dev.p, sizeof(vqa_vif_metrics) * nent, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->vif_host.p, c->vif_dev.p, sizeof(vqa_vif_metrics) * nent, hipMemcpyDeviceToHost, st));
     c->pend_v = (int)nent;
     return VQA_OK;
 }
@@ -1584,9 +1615,9 @@ static int vif_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
 int vqa_vif_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                    int64_t dist_fs, const vqa_plane_desc *planes, int n_planes)
 {
-    bool touched = false;
-    const int rc = vif_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, touched);
-    return drain_failed_submit(c, rc, touched);
+    return submit_and_drain(c, [&](bool &touched) {
+        return vif_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, touched);
+    });
 }
 
 int vqa_vif_wait(vqa_ctx *c, vqa_vif_metrics *out, int n_entries)
@@ -1595,89 +1626,45 @@ int vqa_vif_wait(vqa_ctx *c, vqa_vif_metrics *out, int n_entries)
     if (!c->pend_v || n_entries != c->pend_v) return VQA_ERR_STATE;   // (a pending quality batch stays pending)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    memcpy(out, c->vif_host, sizeof(vqa_vif_metrics) * (size_t)n_entries);
+    memcpy(out, c->vif_host.p, sizeof(vqa_vif_metrics) * (size_t)n_entries);
     c->pend_v = 0;
     return VQA_OK;
 }
 
 // ---------------------------------------------------------------------------
-// ADM on four scales.  A batch of its own (pend_a), ordered by the stream like a VIF batch; the checks are vqa_vif_submit's.
+// ADM on four scales.  A batch of its own (pend_a), ordered by the stream like a VIF batch.
 static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
-    if (!c || !ref || !dist || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
-    if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (c->pend_a) return VQA_ERR_STATE;
-    int64_t span = 0;
-    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
-    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
-    const int bps = depth > 8 ? 2 : 1;
-    for (int p = 0; p < n_planes; p++) {
-        const vqa_plane_desc &d = planes[p];
-        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
-        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
-        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
-            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
-            return VQA_ERR_INVALID;
-        if (d.width < ADM_MIN_DIM || d.height < ADM_MIN_DIM) return VQA_ERR_UNSUPPORTED;
-        if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;   // the bound of the sums (vqa.h)
-        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
-        span = end > span ? end : span;
-    }
-    if (n > 1 && (ref_fs < span || dist_fs < span)) return VQA_ERR_INVALID;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, ADM_MIN_DIM); });
+    if (rc) return rc;
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     touched = true;
-    const uint8_t *dref = ref, *ddist = dist;
-    if (mem_kind == VQA_MEM_HOST) {
-        const size_t rs = (size_t)(n - 1) * ref_fs + span, ds = (size_t)(n - 1) * dist_fs + span;
-        int rc = ensure(c, c->qstage_ref, rs);
-        if (rc) return rc;
-        rc = ensure(c, c->qstage_dist, ds);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->qstage_ref.p, ref, rs, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->qstage_dist.p, dist, ds, hipMemcpyHostToDevice, st));
-        dref = (const uint8_t *)c->qstage_ref.p;
-        ddist = (const uint8_t *)c->qstage_dist.p;
-    }
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t sums_bytes = sizeof(double) * 6 * ADM_LEVELS * nent;
-    int rc = ensure(c, c->adm_sums, sums_bytes);
-    if (rc) return rc;
-    rc = ensure_pinned(c, c->adm_host, c->adm_host_cap, sums_bytes);
-    if (rc) return rc;
-    const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
-    const int nslice = n < QSLICE ? n : QSLICE;
+    if ((rc = ensure(c, c->adm_sums, sums_bytes))) return rc;
+    if ((rc = ensure_pinned(c, c->adm_host, sums_bytes))) return rc;
+    const int nslice = n < QSLICE ? n : QSLICE, depth = B.depth;
     // the band scratch and the partials serve one group of same-geometry planes (and one scale) at a time
-    size_t pyr = 0, part = 0;
-    for (int p = 0; p < n_planes; p++) {
-        int cnt = 0;
-        for (int q = 0; q < n_planes; q++) cnt += planes[q].width == planes[p].width && planes[q].height == planes[p].height;
-        const adm_layout L = adm_levels(nslice, cnt, planes[p].height, planes[p].width);
-        const size_t b = sizeof(float) * (size_t)L.total;
-        const size_t t = sizeof(double) * 6 * (size_t)nslice * cnt * adm_tiles(L.h[1], L.w[1]);
-        pyr = b > pyr ? b : pyr;
-        part = t > part ? t : part;
-    }
-    rc = ensure(c, c->adm_pyr, pyr);
-    if (rc) return rc;
-    rc = ensure(c, c->adm_part, part);
-    if (rc) return rc;
-    for (int a0 = 0; a0 < n; a0 += QSLICE) {
-        const int m = n - a0 < QSLICE ? n - a0 : QSLICE;
+    const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
+        return sizeof(float) * (size_t)adm_levels(nslice, cnt, h, w).total;
+    });
+    const size_t part = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
+        const adm_layout L = adm_levels(nslice, cnt, h, w);
+        return sizeof(double) * 6 * (size_t)nslice * cnt * adm_tiles(L.h[1], L.w[1]);
+    });
+    if ((rc = ensure(c, c->adm_pyr, pyr))) return rc;
+    if ((rc = ensure(c, c->adm_part, part))) return rc;
+    for_each_slice(n, [&](int a0, int m) {
         double *sums = (double *)c->adm_sums.p + (size_t)a0 * n_planes * 6 * ADM_LEVELS;
-        const uint8_t *sref = dref + (int64_t)a0 * ref_fs, *sdist = ddist + (int64_t)a0 * dist_fs;
-        bool done[4] = {false, false, false, false};
-        for (int p = 0; p < n_planes; p++) {
-            if (done[p]) continue;
-            int idx[4], cnt = 0;
-            for (int q = p; q < n_planes; q++) {
-                if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
-                    planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
-                    idx[cnt++] = q;
-                    done[q] = true;
-                }
-            }
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             for (int sc = 0; sc < ADM_LEVELS; sc++) {
                 {
                     prof_scope ps_(c, VQA_K_ADM);
@@ -1687,10 +1674,10 @@ static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
                 prof_scope pr_(c, VQA_K_ADM_REDUCE);
                 launch_adm_reduce(st, (const double *)c->adm_part.p, m, planes, idx, cnt, n_planes, sc, sums);
             }
-        }
-    }
+        });
+    });
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->adm_host, c->adm_sums.p, sums_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->adm_host.p, c->adm_sums.p, sums_bytes, hipMemcpyDeviceToHost, st));
     c->pend_a = (int)nent;
     c->pend_a_planes = n_planes;
     for (int p = 0; p < n_planes; p++) { c->pend_a_w[p] = planes[p].width; c->pend_a_h[p] = planes[p].height; }
@@ -1700,9 +1687,9 @@ static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
 int vqa_adm_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                    int64_t dist_fs, const vqa_plane_desc *planes, int n_planes)
 {
-    bool touched = false;
-    const int rc = adm_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, touched);
-    return drain_failed_submit(c, rc, touched);
+    return submit_and_drain(c, [&](bool &touched) {
+        return adm_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, touched);
+    });
 }
 
 int vqa_adm_wait(vqa_ctx *c, vqa_adm_metrics *out, int n_entries)
@@ -1711,7 +1698,7 @@ int vqa_adm_wait(vqa_ctx *c, vqa_adm_metrics *out, int n_entries)
     if (!c->pend_a || n_entries != c->pend_a) return VQA_ERR_STATE;   // (a pending quality or VIF batch stays pending)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    const double *sums = (const double *)c->adm_host;
+    const double *sums = (const double *)c->adm_host.p;
     for (int e = 0; e < n_entries; e++) {
         const int p = e % c->pend_a_planes;
         adm_finalize(sums + (size_t)e * 6 * ADM_LEVELS, c->pend_a_h[p], c->pend_a_w[p], out + e);
@@ -1722,77 +1709,40 @@ int vqa_adm_wait(vqa_ctx *c, vqa_adm_metrics *out, int n_entries)
 
 // ---------------------------------------------------------------------------
 // VMAF's motion feature: the reference stream alone, frame i against frame i - 1.  A batch of its own (pend_m), ordered by the
-// stream like a VIF batch; the checks are vqa_vif_submit's.  Host frames (and prev0) are staged in buffers of their own.
+// stream like a VIF batch.  Host frames (and prev0) are staged in buffers of their own.
 static int motion_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
                               const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
-    if (!c || !ref || n <= 0 || !planes || n_planes <= 0 || n_planes > 4) return VQA_ERR_INVALID;
-    if (mem_kind != VQA_MEM_HOST && mem_kind != VQA_MEM_DEVICE) return VQA_ERR_INVALID;
+    if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (c->pend_m) return VQA_ERR_STATE;
-    int64_t span = 0;
-    const int depth = planes[0].bit_depth == 0 ? 8 : planes[0].bit_depth;
-    if (depth < 8 || depth > 16) return VQA_ERR_INVALID;
-    const int bps = depth > 8 ? 2 : 1;
-    for (int p = 0; p < n_planes; p++) {
-        const vqa_plane_desc &d = planes[p];
-        if ((d.bit_depth == 0 ? 8 : d.bit_depth) != depth) return VQA_ERR_INVALID;
-        if (bps == 2 && ((d.offset | d.row_stride | (int64_t)d.pixel_step) & 1)) return VQA_ERR_INVALID;
-        if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
-            d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - bps))
-            return VQA_ERR_INVALID;
-        if (d.width < MOTION_MIN_DIM || d.height < MOTION_MIN_DIM) return VQA_ERR_UNSUPPORTED;
-        if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;   // the bound of the 64-bit totals (vqa.h)
-        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + bps;
-        span = end > span ? end : span;
-    }
-    if (n > 1 && ref_fs < span) return VQA_ERR_INVALID;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, MOTION_MIN_DIM); });
+    if (rc) return rc;
+    if (n > 1 && ref_fs < B.span) return VQA_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     touched = true;
-    const uint8_t *dref = ref, *dprev = prev0;
     if (mem_kind == VQA_MEM_HOST) {
-        const size_t rs = (size_t)(n - 1) * ref_fs + span;
-        int rc = ensure(c, c->mot_stage, rs);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->mot_stage.p, ref, rs, hipMemcpyHostToDevice, st));
-        dref = (const uint8_t *)c->mot_stage.p;
-        if (prev0) {
-            rc = ensure(c, c->mot_prev, (size_t)span);
-            if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->mot_prev.p, prev0, (size_t)span, hipMemcpyHostToDevice, st));
-            dprev = (const uint8_t *)c->mot_prev.p;
-        }
+        if ((rc = stage(c, c->mot_stage, ref, (size_t)(n - 1) * ref_fs + B.span))) return rc;
+        if (prev0 && (rc = stage(c, c->mot_prev, prev0, (size_t)B.span))) return rc;
     }
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(long long) * nent;
-    int rc = ensure(c, c->mot_acc, acc_bytes);
-    if (rc) return rc;
-    rc = ensure_pinned(c, c->mot_host, c->mot_host_cap, acc_bytes);
-    if (rc) return rc;
+    if ((rc = ensure(c, c->mot_acc, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, c->mot_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->mot_acc.p, 0, acc_bytes, st));
-    const int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
-    for (int a0 = 0; a0 < n; a0 += QSLICE) {
-        const int m = n - a0 < QSLICE ? n - a0 : QSLICE;
+    const int depth = B.depth;
+    for_each_slice(n, [&](int a0, int m) {
         long long *acc = (long long *)c->mot_acc.p + (size_t)a0 * n_planes;
-        const uint8_t *sref = dref + (int64_t)a0 * ref_fs;
-        const uint8_t *sprev = a0 > 0 ? dref + (int64_t)(a0 - 1) * ref_fs : dprev;
-        bool done[4] = {false, false, false, false};
-        for (int p = 0; p < n_planes; p++) {
-            if (done[p]) continue;
-            int idx[4], cnt = 0;
-            for (int q = p; q < n_planes; q++) {
-                if (!done[q] && planes[q].width == planes[p].width && planes[q].height == planes[p].height &&
-                    planes[q].row_stride == planes[p].row_stride && planes[q].pixel_step == planes[p].pixel_step) {
-                    idx[cnt++] = q;
-                    done[q] = true;
-                }
-            }
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
+        const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             prof_scope ps_(c, VQA_K_MOTION);
             launch_motion_sad(st, sref, sprev, m, ref_fs, planes, idx, cnt, n_planes, depth, acc);
-        }
-    }
+        });
+    });
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->mot_host, c->mot_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->mot_host.p, c->mot_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
     c->pend_m = (int)nent;
     c->pend_m_planes = n_planes;
     for (int p = 0; p < n_planes; p++) c->pend_m_area[p] = (int64_t)planes[p].width * planes[p].height;
@@ -1802,9 +1752,9 @@ static int motion_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *pre
 int vqa_motion_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
                       const vqa_plane_desc *planes, int n_planes)
 {
-    bool touched = false;
-    const int rc = motion_submit_body(c, ref, prev0, mem_kind, n, ref_fs, planes, n_planes, touched);
-    return drain_failed_submit(c, rc, touched);
+    return submit_and_drain(c, [&](bool &touched) {
+        return motion_submit_body(c, ref, prev0, mem_kind, n, ref_fs, planes, n_planes, touched);
+    });
 }
 
 int vqa_motion_wait(vqa_ctx *c, vqa_motion_metrics *out, int n_entries)
@@ -1813,7 +1763,7 @@ int vqa_motion_wait(vqa_ctx *c, vqa_motion_metrics *out, int n_entries)
     if (!c->pend_m || n_entries != c->pend_m) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    const long long *acc = (const long long *)c->mot_host;
+    const long long *acc = (const long long *)c->mot_host.p;
     for (int e = 0; e < n_entries; e++) {
         out[e].sad = (double)acc[e] * (1.0 / 65536.0);   // exact for in-range samples (a total below 2^52); a total above 2^53 is rounded once, to double
         out[e].motion = out[e].sad / (double)c->pend_m_area[e % c->pend_m_planes];
@@ -1834,7 +1784,7 @@ int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, in
 {
     if (!c || id < 0 || id >= VQA_K_END || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION))
         return VQA_ERR_INVALID;
-    if (!c->pend_c && !c->pend_q && !c->pend_v && !c->pend_a && !c->pend_m) {
+    if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         prof_collect(c);
     }

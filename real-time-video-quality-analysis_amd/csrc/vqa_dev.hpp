@@ -54,6 +54,33 @@ __device__ __forceinline__ gptr_u8 uniform_ptr(const uint8_t *p)
     return (gptr_u8)(((uint64_t)hi << 32) | lo);
 }
 
+// Both images of one group of same-geometry planes as the VIF and ADM kernels read them - the caller's planes, or an fp32
+// level of the ctx scratch; every stride in bytes
+struct pair_src {
+    const uint8_t *ref, *dist;
+    int64_t ref_fs, dist_fs;   // frame strides
+    int64_t off[4];            // plane offsets inside a frame
+    int64_t row_stride;
+    int step;
+    float sc;                  // 2^-(depth - 8) for integer samples (fp32 levels are centred already)
+    int w, h;
+};
+
+// one sample as centred fp32: x = v / 2^(depth-8) - 128 (exact at every depth); fp32 levels are stored centred
+template <typename T>
+__device__ __forceinline__ float ld_centred(const uint8_t *p, float sc) { return fmaf((float)*(const T *)p, sc, -128.f); }
+template <>
+__device__ __forceinline__ float ld_centred<float>(const uint8_t *p, float) { return *(const float *)p; }
+
+// index i of a row or column of n samples, mirrored about the edges (i < 0 reads -i, i >= n reads 2n - i - 1), then clamped
+// into the plane.  The kernels that use it say why the mirror is their border rule and what the clamp is there for.
+__device__ __forceinline__ int reflect_clamp(int i, int n)
+{
+    i = i < 0 ? -i : i;
+    i = i >= n ? 2 * n - i - 1 : i;
+    return min(max(i, 0), n - 1);
+}
+
 // cv2.cvtColor BGR2GRAY, uint8: 15-bit fixed point (complexity_metrics.py:358 et al.)
 __device__ __forceinline__ uint32_t gray_u8(uint32_t b, uint32_t g, uint32_t r)
 {

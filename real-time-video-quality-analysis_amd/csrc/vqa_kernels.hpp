@@ -159,6 +159,17 @@ void launch_fb_mag(hipStream_t st, const float *flow, int pairs, int h, int w, d
                    vqa_frame_metrics *res);
 #endif
 
+// One group of same-geometry planes of a submit, planes[idx[0 .. count)], as a kernel's four slots: each plane's byte offset
+// inside a frame and / or its index in the submit (either may be null).  The slots beyond `count` repeat the first plane's.
+inline void group_slots(const vqa_plane_desc *planes, const int *idx, int count, int64_t offset[4], int plane_index[4])
+{
+    for (int i = 0; i < 4; i++) {
+        const int p = idx[i < count ? i : 0];
+        if (offset) offset[i] = planes[p].offset;
+        if (plane_index) plane_index[i] = p;
+    }
+}
+
 // k_quality.hip
 int ssim_gauss_blocks(int h, int w);
 void launch_quality_gauss(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,

@@ -38,6 +38,13 @@ ADM_DTYPE = np.dtype([("num", np.float64, (4,)), ("den", np.float64, (4,)), ("sc
 assert ADM_DTYPE.itemsize == C.sizeof(N.VqaAdmMetrics)
 MOTION_DTYPE = np.dtype([("sad", np.float64), ("motion", np.float64)], align=True)
 assert MOTION_DTYPE.itemsize == C.sizeof(N.VqaMotionMetrics)
+# the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
+_BATCHES = {
+    "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
+    "_pending_v": ("vqa_vif_submit", "vqa_vif_wait", VIF_DTYPE, N.VqaVifMetrics),
+    "_pending_a": ("vqa_adm_submit", "vqa_adm_wait", ADM_DTYPE, N.VqaAdmMetrics),
+    "_pending_m": ("vqa_motion_submit", "vqa_motion_wait", MOTION_DTYPE, N.VqaMotionMetrics),
+}
 
 
 class DeviceFrames:
@@ -246,12 +253,10 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend, wait in (("_pending_q", self.quality_wait), ("_pending_v", self.vif_wait), ("_pending_a", self.adm_wait),
-                           ("_pending_m", self.motion_wait),
-                           ("_pending_c", self.complexity_wait)):
+        for pend in list(_BATCHES) + ["_pending_c"]:
             try:
                 if getattr(self, pend, None):
-                    wait()
+                    self.complexity_wait() if pend == "_pending_c" else self._batch_wait(pend)
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -363,50 +368,64 @@ class Engine:
         """planes: (width, height, offset, row_stride, pixel_step[, bit_depth]) per plane, in bytes.  8-bit planes read uint8
         frames; 9..16-bit planes (yuv_planes(.., depth=10) ...) read uint16 frames (host arrays or DeviceFrames of itemsize 2),
         passed through as they are: a frame of the other sample type is a ValueError, not a cast."""
-        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
-        descs = plane_descs(planes)
-        st = self.lib.vqa_quality_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes), ssim_mode)
-        N.check(st, "vqa_quality_submit", self.ctx)
-        self._pending_q = (n, len(planes), keep)
+        self._batch_submit("_pending_q", self._pair_args(ref, dist, planes, frame_bytes), planes, ssim_mode)
+
+    @staticmethod
+    def _stream_arg(a, planes, device, what="frames"):
+        """one stream of a plane-batch submit, resident where `device` says -> (pointer, what to keep alive: the DeviceFrames or
+        the contiguous host array).  Its samples must be what the planes' depth says: the other type is an error, not a cast."""
+        depth = planes_depth(planes)
+        wide, want = depth > 8, "uint16" if depth > 8 else "uint8"
+        if device:
+            if (a.itemsize == 2) != wide:
+                raise ValueError("%d-bit planes need frames of %s samples (got DeviceFrames of itemsize %d)" % (depth, want, a.itemsize))
+            return a.ptr, a
+        a = np.asarray(a)
+        if wide != (a.dtype == np.uint16):
+            raise ValueError("%d-bit planes need %s %s (got %s)" % (depth, "a " + want if what == "prev0" else want, what, a.dtype))
+        a = np.ascontiguousarray(a, dtype=np.uint16 if wide else np.uint8)
+        return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
-        wide = planes_depth(planes) > 8
-        if isinstance(ref, DeviceFrames):
+        """the (ref, dist) pair of a quality / VIF / ADM submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        dev = isinstance(ref, DeviceFrames)
+        if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
-            for a in (ref, dist):
-                if (a.itemsize == 2) != wide:
-                    raise ValueError("%d-bit planes need frames of %s samples (got DeviceFrames of itemsize %d)"
-                                     % (planes_depth(planes), "uint16" if wide else "uint8", a.itemsize))
-            rp, dp, kind, n = ref.ptr, dist.ptr, N.VQA_MEM_DEVICE, ref.n
-            rfs, dfs = ref.frame_stride, dist.frame_stride
-            keep = (ref, dist)
-        else:
-            ref, dist = np.asarray(ref), np.asarray(dist)
-            for a in (ref, dist):
-                if wide != (a.dtype == np.uint16):
-                    raise ValueError("%d-bit planes need %s frames (got %s)" % (planes_depth(planes), "uint16" if wide else "uint8",
-                                                                           a.dtype))
-            ref = np.ascontiguousarray(ref, dtype=np.uint16 if wide else np.uint8)
-            dist = np.ascontiguousarray(dist, dtype=np.uint16 if wide else np.uint8)
-            if ref.shape != dist.shape:
-                raise ValueError("ref and dist must have the same shape")
-            n = ref.shape[0]
-            rfs = dfs = frame_bytes or (ref.nbytes // n)
-            rp, dp, kind = ref.ctypes.data, dist.ctypes.data, N.VQA_MEM_HOST
-            keep = (ref, dist)
-        return rp, dp, kind, n, rfs, dfs, keep
+        rp, ref = self._stream_arg(ref, planes, dev)
+        dp, dist = self._stream_arg(dist, planes, dev)
+        if dev:
+            return rp, dp, N.VQA_MEM_DEVICE, ref.n, ref.frame_stride, dist.frame_stride, (ref, dist)
+        if ref.shape != dist.shape:
+            raise ValueError("ref and dist must have the same shape")
+        n = ref.shape[0]
+        fs = frame_bytes or (ref.nbytes // n)
+        return rp, dp, N.VQA_MEM_HOST, n, fs, fs, (ref, dist)
+
+    def _batch_submit(self, slot, streams, planes, *mode):
+        """streams: what _pair_args / _ref_args gave - the C arguments up to the frame strides, then what to keep alive"""
+        *args, keep = streams
+        sub = _BATCHES[slot][0]
+        st = getattr(self.lib, sub)(self.ctx, *args, plane_descs(planes), len(planes), *mode)
+        N.check(st, sub, self.ctx)
+        setattr(self, slot, (args[3], len(planes), keep))
+
+    def _batch_wait(self, slot):
+        """-> the pending batch's [n, n_planes] records; the slot is free again whatever the status"""
+        _sub, wait, dtype, ctype = _BATCHES[slot]
+        n, npl, _keep = getattr(self, slot)
+        out = np.zeros(n * npl, dtype=dtype)
+        st = getattr(self.lib, wait)(self.ctx, out.ctypes.data_as(C.POINTER(ctype)), n * npl)
+        setattr(self, slot, None)
+        N.check(st, wait, self.ctx)
+        return out.reshape(n, npl)
 
     def quality_wait(self, scales=False):
         """-> [n, n_planes] records (PLANE_DTYPE).  scales=True (after an SSIM_MS submit only): -> (records, cs, ssim) with the
         per-scale means as float64 [n, n_planes, 5], level 0 first (vqa_quality_wait_ms)."""
+        if not scales:
+            return self._batch_wait("_pending_q")
         n, npl, _keep = self._pending_q
         out = np.zeros(n * npl, dtype=PLANE_DTYPE)
-        if not scales:
-            st = self.lib.vqa_quality_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaPlaneMetrics)), n * npl)
-            self._pending_q = None
-            N.check(st, "vqa_quality_wait", self.ctx)
-            return out.reshape(n, npl)
         sc = np.zeros((n * npl, 2, N.MS_LEVELS), np.float64)   # vqa_ms_scales: cs[5], ssim[5]
         st = self.lib.vqa_quality_wait_ms(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaPlaneMetrics)),
                                           sc.ctypes.data_as(C.POINTER(N.VqaMsScales)), n * npl)
@@ -427,20 +446,11 @@ class Engine:
         """VIF on four scales for n frame pairs (vqa_vif_submit): the arrays / DeviceFrames and plane tuples of
         quality_submit; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit of the same frames
         before either is waited for."""
-        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
-        descs = plane_descs(planes)
-        st = self.lib.vqa_vif_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes))
-        N.check(st, "vqa_vif_submit", self.ctx)
-        self._pending_v = (n, len(planes), keep)
+        self._batch_submit("_pending_v", self._pair_args(ref, dist, planes, frame_bytes), planes)
 
     def vif_wait(self):
         """-> [n, n_planes] records (VIF_DTYPE): num[4], den[4], scale[4] (libvmaf's vif_scale0..3) and vif."""
-        n, npl, _keep = self._pending_v
-        out = np.zeros(n * npl, dtype=VIF_DTYPE)
-        st = self.lib.vqa_vif_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaVifMetrics)), n * npl)
-        self._pending_v = None
-        N.check(st, "vqa_vif_wait", self.ctx)
-        return out.reshape(n, npl)
+        return self._batch_wait("_pending_v")
 
     def vif(self, ref, dist, planes, frame_bytes=None):
         """VIF per plane on four scales for n frame pairs; returns [n, n_planes] structured array (VIF_DTYPE)."""
@@ -452,20 +462,11 @@ class Engine:
         """ADM on four scales for n frame pairs (vqa_adm_submit): the arrays / DeviceFrames and plane tuples of
         quality_submit; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit and a vif_submit of
         the same frames before any of them is waited for."""
-        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
-        descs = plane_descs(planes)
-        st = self.lib.vqa_adm_submit(self.ctx, rp, dp, kind, n, rfs, dfs, descs, len(planes))
-        N.check(st, "vqa_adm_submit", self.ctx)
-        self._pending_a = (n, len(planes), keep)
+        self._batch_submit("_pending_a", self._pair_args(ref, dist, planes, frame_bytes), planes)
 
     def adm_wait(self):
         """-> [n, n_planes] records (ADM_DTYPE): num[4], den[4], scale[4] (libvmaf's adm_scale0..3) and adm2."""
-        n, npl, _keep = self._pending_a
-        out = np.zeros(n * npl, dtype=ADM_DTYPE)
-        st = self.lib.vqa_adm_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaAdmMetrics)), n * npl)
-        self._pending_a = None
-        N.check(st, "vqa_adm_wait", self.ctx)
-        return out.reshape(n, npl)
+        return self._batch_wait("_pending_a")
 
     def adm(self, ref, dist, planes, frame_bytes=None):
         """ADM per plane on four scales for n frame pairs; returns [n, n_planes] structured array (ADM_DTYPE)."""
@@ -476,56 +477,29 @@ class Engine:
     def _ref_args(self, ref, planes, prev0, frame_bytes=None):
         """the reference frames (and the frame before them) of a motion submit -> (ref ptr, prev0 ptr or None, mem kind, n,
         frame stride, what to keep alive)"""
-        wide = planes_depth(planes) > 8
-        want = "uint16" if wide else "uint8"
-        if isinstance(ref, DeviceFrames):
-            if prev0 is not None and not isinstance(prev0, DeviceFrames):
-                raise TypeError("prev0 must live where ref lives (device)")
-            for a in (ref,) + ((prev0,) if prev0 is not None else ()):
-                if (a.itemsize == 2) != wide:
-                    raise ValueError("%d-bit planes need frames of %s samples (got DeviceFrames of itemsize %d)"
-                                     % (planes_depth(planes), want, a.itemsize))
-            return ref.ptr, (prev0.ptr if prev0 is not None else None), N.VQA_MEM_DEVICE, ref.n, ref.frame_stride, (ref, prev0)
-        if isinstance(prev0, DeviceFrames):
-            raise TypeError("prev0 must live where ref lives (host)")
-        ref = np.asarray(ref)
-        if wide != (ref.dtype == np.uint16):
-            raise ValueError("%d-bit planes need %s frames (got %s)" % (planes_depth(planes), want, ref.dtype))
-        ref = np.ascontiguousarray(ref, dtype=np.uint16 if wide else np.uint8)
+        dev = isinstance(ref, DeviceFrames)
+        if prev0 is not None and isinstance(prev0, DeviceFrames) != dev:
+            raise TypeError("prev0 must live where ref lives (%s)" % ("device" if dev else "host"))
+        rp, ref = self._stream_arg(ref, planes, dev)
+        pp, p0 = self._stream_arg(prev0, planes, dev, "prev0") if prev0 is not None else (None, None)
+        if dev:
+            return rp, pp, N.VQA_MEM_DEVICE, ref.n, ref.frame_stride, (ref, p0)
         n = ref.shape[0]
-        fs = frame_bytes or (ref.nbytes // n)
-        pp, keep = None, [ref]
-        if prev0 is not None:
-            p0 = np.asarray(prev0)
-            if wide != (p0.dtype == np.uint16):
-                raise ValueError("%d-bit planes need a %s prev0 (got %s)" % (planes_depth(planes), want, p0.dtype))
-            p0 = np.ascontiguousarray(p0, dtype=ref.dtype)
-            if p0.nbytes != ref.nbytes // n:
-                raise ValueError("prev0 must have the frames' layout (%d bytes, got %d)" % (ref.nbytes // n, p0.nbytes))
-            keep.append(p0)
-            pp = p0.ctypes.data
-        return ref.ctypes.data, pp, N.VQA_MEM_HOST, n, fs, keep
+        if p0 is not None and p0.nbytes != ref.nbytes // n:
+            raise ValueError("prev0 must have the frames' layout (%d bytes, got %d)" % (ref.nbytes // n, p0.nbytes))
+        return rp, pp, N.VQA_MEM_HOST, n, frame_bytes or (ref.nbytes // n), (ref, p0)
 
     def motion_submit(self, ref, planes, prev0=None, frame_bytes=None):
         """VMAF's motion feature for n reference frames (vqa_motion_submit): frame i against frame i - 1, frame 0 against
         prev0 (None: it has no predecessor and scores 0).  The arrays / DeviceFrames and plane tuples of vif_submit - the
         reference stream alone; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit, a vif_submit
         and an adm_submit of the same frames before any of them is waited for."""
-        rp, pp, kind, n, fs, keep = self._ref_args(ref, planes, prev0, frame_bytes)
-        descs = plane_descs(planes)
-        st = self.lib.vqa_motion_submit(self.ctx, rp, pp, kind, n, fs, descs, len(planes))
-        N.check(st, "vqa_motion_submit", self.ctx)
-        self._pending_m = (n, len(planes), keep)
+        self._batch_submit("_pending_m", self._ref_args(ref, planes, prev0, frame_bytes), planes)
 
     def motion_wait(self):
         """-> [n, n_planes] records (MOTION_DTYPE): sad, the sum of |blur(frame) - blur(previous frame)| over the plane, and
         motion = sad / (h w), libvmaf's `motion`.  (motion2 needs the next frame: tails.motion2 over the whole clip.)"""
-        n, npl, _keep = self._pending_m
-        out = np.zeros(n * npl, dtype=MOTION_DTYPE)
-        st = self.lib.vqa_motion_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaMotionMetrics)), n * npl)
-        self._pending_m = None
-        N.check(st, "vqa_motion_wait", self.ctx)
-        return out.reshape(n, npl)
+        return self._batch_wait("_pending_m")
 
     def motion(self, ref, planes, prev0=None, frame_bytes=None):
         """VMAF's motion feature per plane for n reference frames; returns [n, n_planes] structured array (MOTION_DTYPE)."""
