@@ -249,6 +249,20 @@ typedef struct vqa_motion_metrics {
     double motion;  /* sad / (h w): libvmaf's `motion` of the frame                                          */
 } vqa_motion_metrics;
 
+/* ITU-T P.910 spatial and temporal information of one reference plane (vqa_siti_submit / vqa_siti_wait; the definition and the
+ * bounds of the sums are stated there).  The four sums are the device's integers - grad_sum is its 2^-32 fixed-point total,
+ * (double) hi + (double) lo 2^-32 -, so the same frame (with its predecessor) gives the same bits at any place of any batch, from
+ * host or device memory; si and ti are formed from them in double on the host by vqa_siti_wait.                            */
+typedef struct vqa_siti_metrics {
+    double   grad_sum; /* sum over the interior of sqrt(gx^2 + gy^2), each term rounded to 2^-32                   */
+    uint64_t grad_sq;  /* sum over the interior of gx^2 + gy^2                                                    */
+    int64_t  diff_sum; /* sum over the plane of R_i - R_{i-1}; 0 without a predecessor                            */
+    uint64_t diff_sq;  /* sum over the plane of (R_i - R_{i-1})^2; 0 without a predecessor                        */
+    double   si;       /* population standard deviation of the Sobel magnitude over the interior, 8-bit scale     */
+    double   ti;       /* population standard deviation of the frame difference over the plane, 8-bit scale; 0
+                          without a predecessor                                                                   */
+} vqa_siti_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -456,6 +470,50 @@ VQA_API int vqa_motion_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *p
                               int64_t ref_frame_stride, const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_motion_wait(vqa_ctx *ctx, vqa_motion_metrics *out, int n_entries);
 
+/* ---- ITU-T P.910 spatial and temporal information (SI / TI): the standard description of source content ----
+ * For one plane of the REFERENCE stream (`depth` bits, h x w), frame i with its predecessor i - 1, on the raw integer samples R
+ * (samples above 2^depth - 1 are read as they are, as elsewhere); the distorted stream is never looked at.  Where this text
+ * differs from a tool's detail, this text is what is built.
+ *   Sobel     gx = (R[y-1][x+1] + 2 R[y][x+1] + R[y+1][x+1]) - (R[y-1][x-1] + 2 R[y][x-1] + R[y+1][x-1]); gy is its transpose.
+ *             Both on the interior only: rows 1 .. h-2, columns 1 .. w-2, n_i = (h-2)(w-2) samples.  There is no border rule:
+ *             no sample outside the plane is ever needed.  q = gx^2 + gy^2 is an integer, below 2^21 for uint8 samples and
+ *             below 2^37.01 for any uint16 samples.
+ *   sums      of the frame, all integers:
+ *             grad_sq  = sum q (uint64);
+ *             grad_fix = sum rint(sqrt((double) q) 2^32), kept by the device in two uint64 words: every workgroup splits its
+ *                        own 64-bit total into the low and the high 32 bits and adds them to lo and hi separately, grad_fix =
+ *                        hi 2^32 + lo; neither word can overflow for a plane of 2^28 samples;
+ *             diff_sum = sum (R_i - R_{i-1}) (int64) and diff_sq = sum (R_i - R_{i-1})^2 (uint64), both over ALL h w samples,
+ *                        both 0 for a frame with no predecessor.
+ *   results   in double on the host (vqa_siti_wait), sc = 2^-(depth-8):
+ *             grad_sum = (double) hi + (double) lo 2^-32;  m = grad_sum / n_i;
+ *             si = sc sqrt(max(grad_sq / n_i - m m, 0));
+ *             md = diff_sum / (h w);  ti = sc sqrt(max(diff_sq / (h w) - md md, 0)); ti = 0 for a frame with no predecessor.
+ *             Both are population standard deviations on the 8-bit scale, at every depth.
+ *   clip      P.910's SI and TI of a clip are the MAXIMA over its frames; the host forms them (the Python binding's entry
+ *             points).  The first frame's ti = 0 cannot win a maximum.
+ * Limits: every plane at least 16 x 16 (the family's rule), h w <= 2^28 for uint8 samples and h w <= 2^26 at depths above 8 - so
+ * that grad_sq stays below 2^64 for arbitrary 16-bit samples: VQA_ERR_UNSUPPORTED beyond either.
+ * Why integers: the sums are associative.  A frame (with its predecessor) gives the same record bits at any place of any batch,
+ * from host, pinned or device memory, for any tiling - the guarantee every other record of this header gives.
+ * Why the quantum is 2^-32 and not motion's 2^-16: si is a difference of two nearly equal numbers on smooth content, and an
+ * error e on m moves the variance by 2 m e.  On a plane whose gradient is the same everywhere (R = x + y: q = 128, true SI 0)
+ * a 2^-16 quantum would report si near 0.013; with 2^-32 the figure is about 5e-5, and si's error stays below 6e-4 for any
+ * 8-bit content (m <= 1020 sqrt 2: sqrt(2 m 2^-33) = 5.8e-4, the case of a true variance of 0).
+ * The contract of vqa_motion_submit: asynchronous, prev0 (the frame preceding ref[0], same layout and mem_kind) or NULL, the
+ * same plane descriptors, depths (one per submit), alignment rules and failure guarantee: a failed submit leaves nothing in
+ * flight.  VQA_ERR_STATE while an SI/TI batch is pending.  An SI/TI batch is a batch of its own: it may be in flight next to a
+ * quality, a VIF, an ADM, a motion and a complexity batch of the same ctx (one upload then serves all), and each wait collects
+ * its own kind only - vqa_siti_wait with only another kind pending, and another kind's wait with only an SI/TI batch pending,
+ * are VQA_ERR_STATE and leave that batch pending.
+ * One fused kernel: a tile and its apron of one sample of frame i go to shared memory as raw integers, the predecessor's
+ * samples are read straight from global memory, and only the five 64-bit words leave the kernel.  Scratch on the device: 40
+ * bytes per entry; frames handed over in host memory (and prev0) are staged in device buffers of the batch's size.  All of it
+ * is kept by the ctx until vqa_trim / vqa_destroy.  out of vqa_siti_wait: n * n_planes entries, frame-major.              */
+VQA_API int vqa_siti_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n,
+                            int64_t ref_frame_stride, const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_siti_wait(vqa_ctx *ctx, vqa_siti_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -482,7 +540,11 @@ enum vqa_kernel_id {
                                 VQA_K_COUNT_EXT - 1 (kept at 18 for callers and tests that rely on id 18 being unknown)  */
     VQA_K_MOTION = 19,       /* vqa_motion_submit: blur of both frames and the sum of |difference| (one entry per group of
                                 same-geometry planes); id 18 stays unnamed                                              */
-    VQA_K_END = 20           /* one past the last id: ... and VQA_K_MOTION .. VQA_K_END - 1                              */
+    VQA_K_END = 20,          /* one past VQA_K_MOTION, as motion shipped it (kept at 20 for callers and tests that rely on
+                                id 20 being unknown); id 20 stays unnamed                                               */
+    VQA_K_SITI = 21,         /* vqa_siti_submit: Sobel, frame difference and their integer sums (one entry per group of
+                                same-geometry planes)                                                                   */
+    VQA_K_LAST = 22          /* one past the last id: ... VQA_K_MOTION .. VQA_K_END - 1 and VQA_K_SITI .. VQA_K_LAST - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -42,7 +42,9 @@ K_VIF, K_VIF_DECIMATE, K_COUNT_ALL = 12, 13, 14   # added beyond K_COUNT (includ
 K_ADM, K_ADM_REDUCE, K_COUNT_EXT = 16, 17, 18     # added beyond K_COUNT_ALL, which stays 14; ids 14 and 15 are unnamed
 K_MOTION, K_END = 19, 20                          # added beyond K_COUNT_EXT, which stays 18; id 18 is unnamed
 K_IDS = tuple(range(K_COUNT_ALL)) + (K_ADM, K_ADM_REDUCE)   # the ids below K_COUNT_EXT (kept as ADM shipped it)
-K_IDS_ALL = K_IDS + (K_MOTION,)                   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_ALL = K_IDS + (K_MOTION,)                   # the ids below K_END (kept as motion shipped it)
+K_SITI, K_LAST = 21, 22                           # added beyond K_END, which stays 20; id 20 is unnamed
+K_IDS_KNOWN = K_IDS_ALL + (K_SITI,)               # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -57,6 +59,7 @@ VIF_MIN_DIM = 16   # vqa_vif_submit: level 3 of a 16 x 16 plane is 2 x 2, every 
 ADM_LEVELS = 4
 ADM_MIN_DIM = 16   # vqa_adm_submit: the bands of scale 3 of a 16 x 16 plane are 1 x 1
 MOTION_MIN_DIM = 16   # vqa_motion_submit: the limit of VIF and ADM, whose planes it shares
+SITI_MIN_DIM = 16   # vqa_siti_submit: the limit of VIF, ADM and motion, whose planes it shares
 MOTION_SAD, MOTION_FARNEBACK = 0, 1
 
 
@@ -110,6 +113,11 @@ class VqaMotionMetrics(C.Structure):
     _fields_ = [("sad", C.c_double), ("motion", C.c_double)]
 
 
+class VqaSitiMetrics(C.Structure):
+    _fields_ = [("grad_sum", C.c_double), ("grad_sq", C.c_uint64), ("diff_sum", C.c_int64), ("diff_sq", C.c_uint64),
+                ("si", C.c_double), ("ti", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -149,6 +157,8 @@ SIGNATURES = {
     "vqa_adm_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaAdmMetrics), C.c_int]),
     "vqa_motion_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_motion_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaMotionMetrics), C.c_int]),
+    "vqa_siti_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_siti_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaSitiMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -80,6 +80,9 @@ struct vqa_ctx {
     // vqa_motion_submit: the integer totals (device, pinned host); host frames and their prev0 staged on the device
     dbuf mot_acc, mot_stage, mot_prev;
     hbuf mot_host;
+    // vqa_siti_submit: the five integer words per entry (device, pinned host); host frames and their prev0 staged on the device
+    dbuf siti_acc, siti_stage, siti_prev;
+    hbuf siti_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -99,6 +102,8 @@ struct vqa_ctx {
     int pend_m = 0;           // entries of the pending motion batch (likewise); its planes' areas, for the host's division
     int pend_m_planes = 0;
     int64_t pend_m_area[4] = {0};
+    int pend_s = 0;           // entries of the pending SI/TI batch (likewise); its planes' sizes and depth, for the host's formulas
+    int pend_s_planes = 0, pend_s_depth = 8, pend_s_w[4] = {0}, pend_s_h[4] = {0};
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -108,8 +113,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_END] = {0};
-    int64_t prof_n[VQA_K_END] = {0};
+    double prof_ms[VQA_K_LAST] = {0};
+    int64_t prof_n[VQA_K_LAST] = {0};
 };
 
 namespace {
@@ -182,7 +187,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -825,14 +830,14 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -1332,7 +1337,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the four plane-batch submits (quality, VIF, ADM, motion) share: the checks, the staging of host frames, the walk over
+// What the five plane-batch submits (quality, VIF, ADM, motion, SI/TI) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -1773,6 +1778,78 @@ int vqa_motion_wait(vqa_ctx *c, vqa_motion_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// ITU-T P.910 spatial and temporal information: the reference stream alone, Sobel on frame i and frame i against frame i - 1.
+// A batch of its own (pend_s), ordered by the stream like a motion batch.  Host frames (and prev0) are staged in buffers of
+// their own.
+static int siti_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                            const vqa_plane_desc *planes, int n_planes, bool &touched)
+{
+    if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (c->pend_s) return VQA_ERR_STATE;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+        if (int lim = side_and_area_limits(d, SITI_MIN_DIM)) return lim;
+        // grad_sq: q < 2^37.01 for arbitrary 16-bit samples, so 2^26 of them stay below 2^64 (vqa.h)
+        if (B.depth > 8 && (int64_t)d.width * d.height > (1ll << 26)) return VQA_ERR_UNSUPPORTED;
+        return VQA_OK;
+    });
+    if (rc) return rc;
+    if (n > 1 && ref_fs < B.span) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if (mem_kind == VQA_MEM_HOST) {
+        if ((rc = stage(c, c->siti_stage, ref, (size_t)(n - 1) * ref_fs + B.span))) return rc;
+        if (prev0 && (rc = stage(c, c->siti_prev, prev0, (size_t)B.span))) return rc;
+    }
+    const size_t nent = (size_t)n * n_planes;
+    const size_t acc_bytes = sizeof(unsigned long long) * SITI_WORDS * nent;
+    if ((rc = ensure(c, c->siti_acc, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, c->siti_host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->siti_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    for_each_slice(n, [&](int a0, int m) {
+        unsigned long long *acc = (unsigned long long *)c->siti_acc.p + (size_t)a0 * n_planes * SITI_WORDS;
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
+        const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
+            prof_scope ps_(c, VQA_K_SITI);
+            launch_siti(st, sref, sprev, m, ref_fs, planes, idx, cnt, n_planes, depth, acc);
+        });
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->siti_host.p, c->siti_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_s = (int)nent;
+    c->pend_s_planes = n_planes;
+    c->pend_s_depth = depth;
+    for (int p = 0; p < n_planes; p++) { c->pend_s_w[p] = planes[p].width; c->pend_s_h[p] = planes[p].height; }
+    return VQA_OK;
+}
+
+int vqa_siti_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                    const vqa_plane_desc *planes, int n_planes)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return siti_submit_body(c, ref, prev0, mem_kind, n, ref_fs, planes, n_planes, touched);
+    });
+}
+
+int vqa_siti_wait(vqa_ctx *c, vqa_siti_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_s || n_entries != c->pend_s) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->siti_host.p;
+    for (int e = 0; e < n_entries; e++) {
+        const int p = e % c->pend_s_planes;
+        siti_finalize(acc + (size_t)e * SITI_WORDS, c->pend_s_h[p], c->pend_s_w[p], c->pend_s_depth, out + e);
+    }
+    c->pend_s = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -1782,7 +1859,8 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_END || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION))
+    if (!c || id < 0 || id >= VQA_K_LAST || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+        (id >= VQA_K_END && id < VQA_K_SITI))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1803,6 +1881,7 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_ADM) return "k_adm_scale";
     if (id == VQA_K_ADM_REDUCE) return "k_adm_reduce";
     if (id == VQA_K_MOTION) return "k_motion_sad";
+    if (id == VQA_K_SITI) return "k_siti";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

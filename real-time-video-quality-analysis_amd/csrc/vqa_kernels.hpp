@@ -319,4 +319,16 @@ constexpr double MOTION_TAPS[5] = {0.054488685, 0.244201342, 0.402619947, 0.2442
 void launch_motion_sad(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n, int64_t frame_stride,
                        const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth, long long *acc);
 
+// ITU-T P.910 spatial and temporal information (vqa_siti_submit): k_siti.hip
+constexpr int SITI_MIN_DIM = 16;
+constexpr int SITI_WORDS = 5;                 // per (frame, plane): lo, hi (grad_fix = hi 2^32 + lo), grad_sq, diff_sum, diff_sq
+constexpr double SITI_FIX = 4294967296.0;     // 2^32: the quantum of the summed gradient magnitudes is 2^-32
+// one group of same-geometry planes of n reference frames: Sobel on the interior of frame i, frame i against frame i - 1 (frame 0
+// against prev0; nullptr: frame 0 forms its gradient sums only).  Adds the five integer words into
+// acc[(frame * n_planes + plane) * SITI_WORDS ..], which the caller has zeroed.
+void launch_siti(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n, int64_t frame_stride,
+                 const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth, unsigned long long *acc);
+// five words -> the record: the divisions and square roots of include/vqa.h in double, on the host (h x w: the plane)
+void siti_finalize(const unsigned long long *words, int h, int w, int depth, vqa_siti_metrics *out);
+
 } // namespace vqa

@@ -38,12 +38,16 @@ ADM_DTYPE = np.dtype([("num", np.float64, (4,)), ("den", np.float64, (4,)), ("sc
 assert ADM_DTYPE.itemsize == C.sizeof(N.VqaAdmMetrics)
 MOTION_DTYPE = np.dtype([("sad", np.float64), ("motion", np.float64)], align=True)
 assert MOTION_DTYPE.itemsize == C.sizeof(N.VqaMotionMetrics)
+SITI_DTYPE = np.dtype([("grad_sum", np.float64), ("grad_sq", np.uint64), ("diff_sum", np.int64), ("diff_sq", np.uint64),
+                       ("si", np.float64), ("ti", np.float64)], align=True)
+assert SITI_DTYPE.itemsize == C.sizeof(N.VqaSitiMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
     "_pending_v": ("vqa_vif_submit", "vqa_vif_wait", VIF_DTYPE, N.VqaVifMetrics),
     "_pending_a": ("vqa_adm_submit", "vqa_adm_wait", ADM_DTYPE, N.VqaAdmMetrics),
     "_pending_m": ("vqa_motion_submit", "vqa_motion_wait", MOTION_DTYPE, N.VqaMotionMetrics),
+    "_pending_s": ("vqa_siti_submit", "vqa_siti_wait", SITI_DTYPE, N.VqaSitiMetrics),
 }
 
 
@@ -250,7 +254,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -475,7 +479,7 @@ class Engine:
 
     # ---- VMAF's motion feature -------------------------------------------------
     def _ref_args(self, ref, planes, prev0, frame_bytes=None):
-        """the reference frames (and the frame before them) of a motion submit -> (ref ptr, prev0 ptr or None, mem kind, n,
+        """the reference frames (and the frame before them) of a motion or an SI/TI submit -> (ref ptr, prev0 ptr or None, mem kind, n,
         frame stride, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if prev0 is not None and isinstance(prev0, DeviceFrames) != dev:
@@ -506,6 +510,24 @@ class Engine:
         self.motion_submit(ref, planes, prev0, frame_bytes)
         return self.motion_wait()
 
+    # ---- ITU-T P.910 spatial and temporal information -----------------------------
+    def siti_submit(self, ref, planes, prev0=None, frame_bytes=None):
+        """P.910's SI and TI for n reference frames (vqa_siti_submit): Sobel on the interior of frame i, and frame i against
+        frame i - 1, frame 0 against prev0 (None: it has no predecessor and its ti is 0).  The arguments of motion_submit - the
+        reference stream alone; every plane at least 16 x 16.  A batch of its own: it may follow a quality_submit, a vif_submit,
+        an adm_submit and a motion_submit of the same frames before any of them is waited for."""
+        self._batch_submit("_pending_s", self._ref_args(ref, planes, prev0, frame_bytes), planes)
+
+    def siti_wait(self):
+        """-> [n, n_planes] records (SITI_DTYPE): the four integer sums (grad_sum in 2^-32 fixed point, as a double), si and ti
+        on the 8-bit scale.  (P.910's clip values are the maxima over the frames.)"""
+        return self._batch_wait("_pending_s")
+
+    def siti(self, ref, planes, prev0=None, frame_bytes=None):
+        """P.910's SI and TI per plane for n reference frames; returns [n, n_planes] structured array (SITI_DTYPE)."""
+        self.siti_submit(ref, planes, prev0, frame_bytes)
+        return self.siti_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -513,7 +535,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_ALL:
+        for k in N.K_IDS_KNOWN:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

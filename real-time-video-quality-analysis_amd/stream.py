@@ -317,7 +317,7 @@ def plan_chunks(n, want_q, interval, lo, hi, cap, split=False, motion=False):
     rslot = 1 .. qn and slot 0 holds source frame q0 - 1, the last reference frame of the previous chunk (rhalo = True; the first
     chunk has no predecessor: rhalo = False, slot 0 stays unused).  The halo is part of the chunk's OWN upload - it never points
     into the previous chunk's buffer set, which the copy lane may already be overwriting.  Without motion rslot is 0 and the
-    plans are what they were."""
+    plans are what they were.  (P.910's SI / TI needs exactly that halo: a pass with Quality(.., siti=..) asks for it here too.)"""
     plans = []
     if want_q:
         idx = selected_indices(n, interval) if interval else None
@@ -388,7 +388,7 @@ class Complexity:
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
-    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False):
+    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -397,7 +397,11 @@ class Quality:
         motion  True: every chunk's REFERENCE frames also go through the motion kernel (Engine.motion_submit) from the same
                 upload, prev0 being the last reference frame of the previous chunk (the reference feed's halo slot); the pass
                 then returns (.., VIF records or None, ADM records or None, motion records [n,p] (MOTION_PASS_DTYPE: sad, motion
-                and motion2, the last formed once over the whole clip)); "only": no SSE / SSIM"""
+                and motion2, the last formed once over the whole clip)); "only": no SSE / SSIM
+        siti    True: every chunk's REFERENCE frames also go through the SI/TI kernel (Engine.siti_submit) from the same upload,
+                prev0 being the reference feed's halo slot as for motion; the pass's tuple - whatever vif, adm and motion made
+                it - then gains ONE further last element, the SI/TI records [n,p] (engine.SITI_DTYPE: si, ti and the four sums);
+                "only": no SSE / SSIM"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -413,8 +417,12 @@ class Quality:
         if motion == "only" and scales:
             raise ValueError("a motion-only pass has no SSIM scales")
         self.planes, self.ssim_mode, self.scales, self.vif, self.adm = planes, ssim_mode, bool(scales), vif, adm
-        self.motion = motion
-        self.ssim = vif != "only" and adm != "only" and motion != "only"   # the pass measures SSE / SSIM
+        if not (isinstance(siti, bool) or (isinstance(siti, str) and siti == "only")):
+            raise ValueError("siti must be False, True or 'only'")
+        if siti == "only" and scales:
+            raise ValueError("an SI/TI-only pass has no SSIM scales")
+        self.motion, self.siti = motion, siti
+        self.ssim = vif != "only" and adm != "only" and motion != "only" and siti != "only"   # the pass measures SSE / SSIM
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -486,6 +494,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     appended instead: the VIF records (None when VIF was not requested) and the ADM records [n,p] (engine.ADM_DTYPE); adm="only"
     leaves sse and ssim None as well.  With Quality(.., motion=True) three elements are appended: the VIF records or None, the ADM
     records or None and the motion records [n,p] (MOTION_PASS_DTYPE); motion="only" leaves sse and ssim None as well.
+    Quality(.., siti=True) appends ONE further last element to whichever of these tuples the pass returns: the SI/TI records
+    [n,p] (engine.SITI_DTYPE); siti="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -533,6 +543,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
                 q += (np.zeros((0, len(quality.planes)), ADM_DTYPE) if quality.adm else None,)
             if quality.motion:
                 q += (np.zeros((0, len(quality.planes)), MOTION_PASS_DTYPE),)
+        if quality.siti:
+            from .engine import SITI_DTYPE
+            q += (np.zeros((0, len(quality.planes)), SITI_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -547,8 +560,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
 def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series, n, batch_size, on_quality):
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
-    # motion alone reads the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and quality.motion == "only" and not quality.vif and not quality.adm
+    # motion and SI/TI alone read the reference stream only: the distorted stream is not even uploaded
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -580,7 +593,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     host = any(f.host for f in feeds.values())
     staged = any(f.staged for f in feeds.values())
     cap = chunk_frames(batch_size, interval if (want_q and want_c) else None, per_frame if host else 0, staged)
-    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and quality.motion))
+    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and (quality.motion or quality.siti)))
     nchunks = len(plans)
     # ---- lanes
     farneback = want_c and (complexity.mask & N.M_MOTION) and complexity.motion_mode == N.MOTION_FARNEBACK
@@ -656,7 +669,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -680,17 +693,21 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.adm:
                     eng.adm_submit(pair[0], pair[1], quality.planes)
                     p["has_a"] = True
-                if quality.motion:   # the reference frames alone; prev0 = the frame before the chunk: the halo slot of the
-                    prev0 = None     # chunk's own buffer (host streams) or the resident clip's frame in place
-                    if p["q0"] > 0:
+                if quality.motion or quality.siti:   # the reference frames alone; prev0 = the frame before the chunk: the halo
+                    prev0 = None                     # slot of the chunk's own buffer (host streams) or the resident clip's frame
+                    if p["q0"] > 0:                  # in place
                         if fr.host:
                             b = dev[fr.name]
                             prev0 = DeviceFrames(b.ptr, 1, 1, fr.fb // fr.itemsize, frame_stride=fr.fb, row_stride=fr.fb,
                                                  owner=b, channels=1, itemsize=fr.itemsize)
                         else:
                             prev0 = fr.src.frames.frame(p["q0"] - 1)
-                    eng.motion_submit(pair[0], quality.planes, prev0)
-                    p["has_m"] = True
+                    if quality.motion:
+                        eng.motion_submit(pair[0], quality.planes, prev0)
+                        p["has_m"] = True
+                    if quality.siti:
+                        eng.siti_submit(pair[0], quality.planes, prev0)
+                        p["has_s"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -709,7 +726,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot = [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti = [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -723,6 +740,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["ares"] = eng.adm_wait()
             if p["has_m"]:
                 p["mres"] = eng.motion_wait()
+            if p["has_s"]:
+                p["sres"] = eng.siti_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -747,6 +766,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 adm.append(p.pop("ares"))
             if p["has_m"]:
                 mot.append(p.pop("mres"))
+            if p["has_s"]:
+                siti.append(p.pop("sres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -811,6 +832,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(adm) if quality.adm else None,)
     if want_q and quality.motion:
         q += (motion_records(np.concatenate(mot)),)
+    if want_q and quality.siti:
+        q += (np.concatenate(siti),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

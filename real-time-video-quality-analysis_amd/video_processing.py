@@ -135,7 +135,21 @@ def frame_motion(reference, layout="bgr24", height=None, width=None, engine=None
     return q[-1]["motion"], q[-1]["motion2"], [(p[0], p[1]) for p in planes]
 
 
-def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None):
+def frame_siti(reference, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame ITU-T P.910 spatial and temporal information per plane of the REFERENCE stream (Engine.siti through the
+    one-pass pipeline of frame_quality; the stream is uploaded once, there is no distorted stream).
+    Returns (si [n,p] float64 - the standard deviation of the Sobel magnitude over the plane's interior -, ti [n,p] float64 - the
+    standard deviation of the difference to the frame before, 0 for frame 0 -, plane sizes), both on the 8-bit scale.  P.910's
+    SI and TI of the clip are si.max(axis=0) and ti.max(axis=0).  Every plane at least 16 x 16."""
+    reference = _host_stream(reference, wide=True)
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(reference, reference, quality=stream.Quality(planes, siti="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    return q[-1]["si"], q[-1]["ti"], [(p[0], p[1]) for p in planes]
+
+
+def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -143,6 +157,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None):
     frame and pooled in the same way.
     motion: None, or the first plane's motion records [n] (stream.MOTION_PASS_DTYPE): the log then also carries motion2 and
     motion, likewise.
+    siti: None, or the first plane's SI/TI records [n] (engine.SITI_DTYPE): the log then also carries si and ti, after the motion
+    keys and before vmaf, likewise (P.910's clip values are the pooled maxima).  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -159,6 +175,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None):
         motion = np.asarray(motion).reshape(-1)
         names += ["motion2", "motion"]
         cols += [motion["motion2"].astype(np.float64), motion["motion"].astype(np.float64)]
+    if siti is not None:
+        siti = np.asarray(siti).reshape(-1)
+        names += ["si", "ti"]
+        cols += [siti["si"].astype(np.float64), siti["ti"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -279,7 +299,7 @@ def _open_quality_stream(src, layout, height, width):
 
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
-                       adm=False, motion=False):
+                       adm=False, motion=False, siti=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -288,6 +308,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     written, as before.
     adm=True: likewise ADM on four scales (adm2 and adm_scale0..3 of the first plane, per frame and pooled, in the same log).
     motion=True: likewise VMAF's motion feature of the reference stream (motion2 and motion of the first plane).
+    siti=True: likewise ITU-T P.910's spatial and temporal information of the reference stream (si and ti of the first plane; a
+    model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -303,14 +325,14 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
-        if vif or adm or motion:
+        if vif or adm or motion or siti:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
             q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
-                                                             adm=bool(adm), motion=bool(motion)),
+                                                             adm=bool(adm), motion=bool(motion), siti=bool(siti)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -347,15 +369,20 @@ MODE_KEYS = {
 }
 
 
-def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None):
-    """the first plane's VIF / ADM / motion of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
+def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False):
+    """the first plane's VIF / ADM / motion / SI and TI of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
+    rec = None
+    if siti:   # the tuple's one further last element; what is left is the tuple of a pass without it
+        rec, q = q[-1][:, 0], q[:-1]
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
-                      model=model)
+                      model=model, siti=rec)
     elif adm:
-        write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0])
+        write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0], siti=rec)
+    elif vif:
+        write_vif_log(vmaf_log, q[-1]["scale"][:, 0], siti=rec)
     else:
-        write_vif_log(vmaf_log, q[-1]["scale"][:, 0])
+        write_vif_log(vmaf_log, siti=rec)
 
 
 def _check_mode_keys(config):
@@ -371,6 +398,8 @@ def _check_mode_keys(config):
         raise ValueError("adm must be true or false.")
     if "motion_feature" in config and not isinstance(config["motion_feature"], bool):
         raise ValueError("motion_feature must be true or false.")
+    if "siti" in config and not isinstance(config["siti"], bool):
+        raise ValueError("siti must be true or false.")
     mp = config.get("vmaf_model_path")
     if mp is not None and not (isinstance(mp, str) and os.path.isfile(mp) and os.access(mp, os.R_OK)):
         raise ValueError("vmaf_model_path must be null or the path of a readable model file.")
@@ -406,6 +435,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         motion_feature (true: the row gains MOTION2 and MOTION, the pooled means of the first plane's VMAF motion feature of the
         INPUT stream; default false; the reference's vmaf_model_path, when not null, names a libvmaf model file: it turns vif, adm
         and motion_feature on and the row gains VMAF, the pooled mean of the per-frame scores, right after SSIM),
+        siti (true: the row gains SI and TI, ITU-T P.910's spatial and temporal information of the INPUT stream's first plane -
+        the pooled MAXIMA over the frames -, after MOTION; default false; a model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -426,6 +457,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     vif = config.get("vif", False)
     adm = config.get("adm", False)
     mot = config.get("motion_feature", False)
+    siti = config.get("siti", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -473,13 +505,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         planes = LAYOUTS[layout][0](h, w)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
-            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot),
+            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model)
+        if vif or adm or mot or siti:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -531,6 +563,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         for k in ("motion2", "motion"):
             if k in pooled:
                 metrics[k.upper()] = float(pooled[k]["mean"])
+        for k in ("si", "ti"):     # ITU-T P.910: the clip's value is the maximum over its frames
+            if k in pooled:
+                metrics[k.upper()] = float(pooled[k]["max"])
     return metrics
 
 
@@ -553,7 +588,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti;
     #                           and that a vmaf_model_path names a readable file
 
 
