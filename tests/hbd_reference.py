@@ -51,32 +51,40 @@ def ssim_ffmpeg(a, b, mx):
     return float(v.sum() / ((bh - 1) * (bw - 1)))
 
 
-def _gauss11():
+def _gauss11(dtype=np.float64):
     k = np.arange(11) - 5
     g = np.exp(-(k * k) / (2 * 1.5 * 1.5))
-    return g / g.sum()
+    return (g / g.sum()).astype(dtype)
 
 
 def _filt(x):
-    """separable 11x11 Gaussian, valid region"""
-    g = _gauss11()
+    """separable 11x11 Gaussian, valid region, in the type of x"""
+    g = _gauss11(x.dtype)
     h, w = x.shape
     v = sum(g[k] * x[k:k + h - 10, :] for k in range(11))
     return sum(g[k] * v[:, k:k + w - 10] for k in range(11))
 
 
-def ssim_gauss(a, b, data_range):
-    """skimage's Gaussian SSIM at data range L on int64 planes; NaN below 11x11"""
+def ssim_gauss(a, b, data_range, dtype=np.float64):
+    """skimage's Gaussian SSIM at data range L on int64 planes; NaN below 11x11.  dtype float32: the same statements in that
+    type on samples mapped to x 255 / L - 128 (data range 255), the means moved back by 128 for the luminance term - the range
+    a float32 evaluation works in (include/vqa.h); SSIM does not change under the map, the float64 default does not apply it."""
     if a.shape[0] < 11 or a.shape[1] < 11:
         return float("nan")
-    x, y = a.astype(np.float64), b.astype(np.float64)
+    ty = np.dtype(dtype).type
+    if ty is np.float64:
+        scale, centre = ty(1), ty(0)
+    else:
+        scale, centre, data_range = ty(255.0 / data_range), ty(128), 255
+    x, y = a.astype(dtype) * scale - centre, b.astype(dtype) * scale - centre
     mx, my = _filt(x), _filt(y)
     sxx = _filt(x * x) - mx * mx
     syy = _filt(y * y) - my * my
     sxy = _filt(x * y) - mx * my
-    C1, C2 = (.01 * data_range) ** 2, (.03 * data_range) ** 2
-    S = ((2 * mx * my + C1) * (2 * sxy + C2)) / ((mx * mx + my * my + C1) * (sxx + syy + C2))
-    return float(S.mean())
+    ux, uy = mx + centre, my + centre
+    C1, C2 = ty((.01 * data_range) ** 2), ty((.03 * data_range) ** 2)
+    S = ((2 * ux * uy + C1) * (2 * sxy + C2)) / ((ux * ux + uy * uy + C1) * (sxx + syy + C2))
+    return float(S.astype(np.float64).mean())
 
 
 def frame_quality(ref, dist, planes, mode, depth):

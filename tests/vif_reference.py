@@ -20,11 +20,11 @@ MIN_DIM = 16
 EPS, NSQ, SMI, GAIN_LIMIT = 1e-10, 2.0, 4.0 / (255.0 * 255.0), 100.0
 
 
-def taps(s):
+def taps(s, dtype=np.float64):
     n = (1 << (4 - s)) + 1
     k = np.arange(n, dtype=np.float64) - n // 2
     g = np.exp(-(k * k) / (2.0 * (n / 5.0) ** 2))
-    return g / g.sum()
+    return (g / g.sum()).astype(dtype)
 
 
 def border_index(i, n):
@@ -41,7 +41,7 @@ def _gather(n, r):
 
 
 def filt(x, t):
-    """separable filter of a float64 plane, same size: columns (vertical pass) first, then rows"""
+    """separable filter of a plane in its own type, same size: columns (vertical pass) first, then rows"""
     r = len(t) // 2
     h, w = x.shape
     xv = x[_gather(h, r), :]
@@ -58,49 +58,53 @@ def filt(x, t):
 def next_level(x, s):
     """level s from level s - 1"""
     h, w = x.shape
-    return filt(x, taps(s))[0:2 * (h // 2):2, 0:2 * (w // 2):2]
+    return filt(x, taps(s, x.dtype))[0:2 * (h // 2):2, 0:2 * (w // 2):2]
 
 
 def statistic(x, y, s):
-    """-> (num map, den map) of one level"""
-    t = taps(s)
+    """-> (num map, den map) of one level, in the type of x"""
+    ty = x.dtype.type
+    eps, nsq, smi, zero, one = ty(EPS), ty(NSQ), ty(SMI), ty(0), ty(1)
+    t = taps(s, x.dtype)
     mu1, mu2 = filt(x, t), filt(y, t)
-    s1 = np.maximum(filt(x * x, t) - mu1 * mu1, 0.0)
-    s2 = np.maximum(filt(y * y, t) - mu2 * mu2, 0.0)
+    s1 = np.maximum(filt(x * x, t) - mu1 * mu1, zero)
+    s2 = np.maximum(filt(y * y, t) - mu2 * mu2, zero)
     s12 = filt(x * y, t) - mu1 * mu2
-    g = s12 / (s1 + EPS)
+    g = s12 / (s1 + eps)
     sv = s2 - g * s12
-    c = s1 < EPS
-    g, sv, s1 = np.where(c, 0.0, g), np.where(c, s2, sv), np.where(c, 0.0, s1)
-    c = s2 < EPS
-    g, sv = np.where(c, 0.0, g), np.where(c, 0.0, sv)
+    c = s1 < eps
+    g, sv, s1 = np.where(c, zero, g), np.where(c, s2, sv), np.where(c, zero, s1)
+    c = s2 < eps
+    g, sv = np.where(c, zero, g), np.where(c, zero, sv)
     c = g < 0
-    sv, g = np.where(c, s2, sv), np.where(c, 0.0, g)
-    sv = np.maximum(sv, EPS)
-    g = np.minimum(g, GAIN_LIMIT)
-    num = np.log2(1.0 + g * g * s1 / (sv + NSQ))
-    den = np.log2(1.0 + s1 / NSQ)
-    num = np.where(s12 < 0, 0.0, num)
-    c = s1 < NSQ
-    num, den = np.where(c, 1.0 - s2 * SMI, num), np.where(c, 1.0, den)
+    sv, g = np.where(c, s2, sv), np.where(c, zero, g)
+    sv = np.maximum(sv, eps)
+    g = np.minimum(g, ty(GAIN_LIMIT))
+    num = np.log2(one + g * g * s1 / (sv + nsq))
+    den = np.log2(one + s1 / nsq)
+    num = np.where(s12 < 0, zero, num)
+    c = s1 < nsq
+    num, den = np.where(c, one - s2 * smi, num), np.where(c, one, den)
     return num, den
 
 
-def vif(ref, dist, depth=8):
-    """-> (num [4], den [4], scale [4], vif) of one plane pair (integer arrays of `depth` bits)"""
+def vif(ref, dist, depth=8, dtype=np.float64):
+    """-> (num [4], den [4], scale [4], vif) of one plane pair (integer arrays of `depth` bits); dtype float32: the same
+    statements in that type (the maps; their sums are taken in float64)"""
     ref, dist = np.asarray(ref), np.asarray(dist)
     if ref.shape != dist.shape or ref.ndim != 2:
         raise ValueError("two planes of one shape")
     if min(ref.shape) < MIN_DIM:
         raise ValueError("VIF on four scales needs planes of at least %d x %d" % (MIN_DIM, MIN_DIM))
-    sc = float(1 << (depth - 8))
-    x, y = ref.astype(np.float64) / sc - 128.0, dist.astype(np.float64) / sc - 128.0
+    ty = np.dtype(dtype).type
+    sc = ty(1 << (depth - 8))
+    x, y = ref.astype(dtype) / sc - ty(128), dist.astype(dtype) / sc - ty(128)
     num, den = np.zeros(LEVELS), np.zeros(LEVELS)
     for s in range(LEVELS):
         if s:
             x, y = next_level(x, s), next_level(y, s)
         n, d = statistic(x, y, s)
-        num[s], den[s] = n.sum(), d.sum()
+        num[s], den[s] = n.sum(dtype=np.float64), d.sum(dtype=np.float64)
     scale = np.where(den == 0, 1.0, num / np.where(den == 0, 1.0, den))
     total = den.sum()
     return num, den, scale, (num.sum() / total if total else 1.0)
