@@ -263,6 +263,17 @@ typedef struct vqa_siti_metrics {
                           without a predecessor                                                                   */
 } vqa_siti_metrics;
 
+/* PSNR-HVS and PSNR-HVS-M of one plane pair (vqa_psnr_hvs_submit / vqa_psnr_hvs_wait; the definition and the bounds of the
+ * sums are stated there).  s_hvs and s_hvsm are the device's 2^-20 fixed-point integer totals divided by the coefficient
+ * count, so the same pair gives the same bits at any place of any batch, from host or device memory; the two dB values are
+ * formed from them in double on the host by vqa_psnr_hvs_wait.                                                              */
+typedef struct vqa_psnr_hvs_metrics {
+    double s_hvs;     /* mean over the coefficients of the whole 8x8 blocks of (|A - B| csf)^2                        */
+    double s_hvsm;    /* likewise with the contrast-masking threshold taken off |A - B| first; s_hvsm <= s_hvs       */
+    double psnr_hvs;  /* 10 log10((2^depth - 1)^2 / s_hvs), +infinity when s_hvs = 0                                  */
+    double psnr_hvsm; /* 10 log10((2^depth - 1)^2 / s_hvsm), +infinity when s_hvsm = 0                                */
+} vqa_psnr_hvs_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -514,6 +525,59 @@ VQA_API int vqa_siti_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *pre
                             int64_t ref_frame_stride, const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_siti_wait(vqa_ctx *ctx, vqa_siti_metrics *out, int n_entries);
 
+/* ---- PSNR-HVS (Egiazarian et al. 2006) and PSNR-HVS-M (Ponomarenko et al. 2007): the perceptually weighted PSNRs ----
+ * The published MATLAB definition (psnrhvsm.m, block step 8) applied per plane.  It is NOT Daala's / libvmaf's `psnr_hvs`
+ * feature, which walks overlapping blocks at step 7, uses an integer DCT and has chroma CSF tables of its own.  Where this
+ * text and a tool differ in a detail, this text is what is built.
+ * For one plane pair (ref R, dist D, `depth` bits, h x w), on the RAW INTEGER SAMPLES (samples above 2^depth - 1 are read as
+ * they are, as elsewhere):
+ *   blocks    non-overlapping 8x8 blocks with top-left corners at (8 i, 8 j), i < floor(h / 8), j < floor(w / 8).  Rows and
+ *             columns beyond the last whole block are not looked at.  n_c = 64 floor(h / 8) floor(w / 8).
+ *   DCT       the orthonormal 2-D DCT-II of a block, A = C a C^T, C[k][n] = c_k cos((2 n + 1) k pi / 16), c_0 = sqrt(1 / 8) and
+ *             c_k = sqrt(2 / 8) otherwise.
+ *   tables    Q, the JPEG Annex K luminance quantisation table, rows
+ *               (16 11 10 16 24 40 51 61) (12 12 14 19 26 58 60 55) (14 13 16 24 40 57 69 56) (14 17 22 29 51 87 80 62)
+ *               (18 22 37 56 68 109 103 77) (24 35 55 64 81 104 113 92) (49 64 78 87 103 121 120 101) (72 92 95 98 112 100 103 99);
+ *             csf[k][l] = 25.735088 / Q[k][l] and msk[k][l] = (10 / Q[k][l])^2, formed in double and rounded once to fp32 -
+ *             the published CSFCof / MaskCof to six decimals.  The same tables serve every plane.
+ *   masking   of a block z with DCT Z: E = sum over (k,l) != (0,0) of Z[k][l]^2 msk[k][l];
+ *             vari(X) = (sum (x - mean)^2) n / (n - 1) (the factor is 64/63 for the block, 16/15 for a quadrant);
+ *             pop = (vari of the four 4x4 quadrants, summed) / vari(z) when vari(z) > 0, else 0;
+ *             m(z) = sqrt(E pop) / 32; for the pair m = max(m(a), m(b)).
+ *   terms     u = |A[k][l] - B[k][l]|.  PSNR-HVS: (u csf)^2.  PSNR-HVS-M: u' = u at (0,0), elsewhere
+ *             u' = max(u - m / msk[k][l], 0); the term is (u' csf)^2.
+ *   results   S_hvs = sum of the terms / n_c, S_hvsm likewise; psnr_hvs = 10 log10(peak^2 / S_hvs), peak = 2^depth - 1, and
+ *             +infinity when S = 0; psnr_hvsm likewise.  Identical planes give exactly S = 0.
+ * How the device forms it (fp32 on the vector ALUs unless stated):
+ *   variances from EXACT INTEGER SUMS: s1 = sum x and s2 = sum x^2 of a quadrant and of the block are integers (32 bits hold
+ *             them at depth 8, 64 bits above); vari = (n s2 - s1^2) / (n - 1), whose numerator is an integer below 2^44, and
+ *             pop are formed from them in double, once.  A float mean-and-subtract loses the ratio on near-flat content.
+ *   u         as the DCT of the integer difference a - b (the DCT is linear; the difference is exact in fp32 at every depth),
+ *             not as the difference of two rounded DCTs.  m / msk as m (Q / 10)^2, the table rounded once like the others.
+ *   sums      BATCH-INVARIANT BITS: each block's two sums of 64 terms are rounded to a 2^-20 quantum and added as integers.
+ *             The squared DCT differences of a block sum to the squared sample differences (Parseval), at most
+ *             64 * 65535^2 < 2^38 for any uint16 input; times csf^2 <= 6.63 a block sum is below 2^41, its fixed-point value
+ *             below 2^61.  Every block's value is split into its low and its high 32 bits and the halves are added to two
+ *             64-bit words per sum - four words per entry.  A plane of 2^28 samples has 2^22 blocks: the low words stay below
+ *             2^54 and the high words below 2^51, so no word can overflow, for any tiling.  The host joins them as
+ *             hi 2^32 + lo, times 2^-20, over n_c, in double.  The rounding moves S by at most half a quantum per block over
+ *             64 coefficients: |error on S| <= 2^-21 / 64 = 2^-27, under 7.5e-9, whatever the content.
+ * Limits: every plane at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.
+ * The contract of vqa_vif_submit: asynchronous, the same plane descriptors, depths (one per submit), alignment rules, memory
+ * kinds and failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while a PSNR-HVS batch is pending.  A
+ * PSNR-HVS batch is a batch of its own: it may be in flight next to a quality, a VIF, an ADM, a motion, an SI/TI and a
+ * complexity batch of the same ctx (one upload then serves all), and each wait collects its own kind only -
+ * vqa_psnr_hvs_wait with only another kind pending, and another kind's wait with only a PSNR-HVS batch pending, are
+ * VQA_ERR_STATE and leave that batch pending.  The same pair gives the same record bits at any place of any batch, from host,
+ * pinned or device memory.
+ * One fused kernel: a thread owns a whole block of both images, reads every sample once and keeps all three DCTs in its
+ * registers; only the four 64-bit words leave the kernel.  Scratch on the device: 32 bytes per entry; host frames are staged
+ * in the buffers a quality, a VIF or an ADM submit uses.  All of it is kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_psnr_hvs_wait: n * n_planes entries, frame-major.                                                             */
+VQA_API int vqa_psnr_hvs_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                                int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_psnr_hvs_wait(vqa_ctx *ctx, vqa_psnr_hvs_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -544,7 +608,11 @@ enum vqa_kernel_id {
                                 id 20 being unknown); id 20 stays unnamed                                               */
     VQA_K_SITI = 21,         /* vqa_siti_submit: Sobel, frame difference and their integer sums (one entry per group of
                                 same-geometry planes)                                                                   */
-    VQA_K_LAST = 22          /* one past the last id: ... VQA_K_MOTION .. VQA_K_END - 1 and VQA_K_SITI .. VQA_K_LAST - 1 */
+    VQA_K_LAST = 22,         /* one past VQA_K_SITI, as SI/TI shipped it (kept at 22 for callers and tests that rely on id 22
+                                being unknown); id 22 stays unnamed                                                      */
+    VQA_K_PSNR_HVS = 23,     /* vqa_psnr_hvs_submit: the 8x8 DCTs, the masks and the two weighted sums (one entry per group of
+                                same-geometry planes)                                                                    */
+    VQA_K_PAST = 24          /* one past the last id: ... VQA_K_SITI .. VQA_K_LAST - 1 and VQA_K_PSNR_HVS .. VQA_K_PAST - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -44,7 +44,9 @@ K_MOTION, K_END = 19, 20                          # added beyond K_COUNT_EXT, wh
 K_IDS = tuple(range(K_COUNT_ALL)) + (K_ADM, K_ADM_REDUCE)   # the ids below K_COUNT_EXT (kept as ADM shipped it)
 K_IDS_ALL = K_IDS + (K_MOTION,)                   # the ids below K_END (kept as motion shipped it)
 K_SITI, K_LAST = 21, 22                           # added beyond K_END, which stays 20; id 20 is unnamed
-K_IDS_KNOWN = K_IDS_ALL + (K_SITI,)               # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_KNOWN = K_IDS_ALL + (K_SITI,)               # the ids below K_LAST (kept as SI/TI shipped it)
+K_PSNR_HVS, K_PAST = 23, 24                       # added beyond K_LAST, which stays 22; id 22 is unnamed
+K_IDS_EVERY = K_IDS_KNOWN + (K_PSNR_HVS,)         # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -60,6 +62,7 @@ ADM_LEVELS = 4
 ADM_MIN_DIM = 16   # vqa_adm_submit: the bands of scale 3 of a 16 x 16 plane are 1 x 1
 MOTION_MIN_DIM = 16   # vqa_motion_submit: the limit of VIF and ADM, whose planes it shares
 SITI_MIN_DIM = 16   # vqa_siti_submit: the limit of VIF, ADM and motion, whose planes it shares
+PSNR_HVS_MIN_DIM = 16   # vqa_psnr_hvs_submit: the limit of the family, whose planes it shares
 MOTION_SAD, MOTION_FARNEBACK = 0, 1
 
 
@@ -118,6 +121,10 @@ class VqaSitiMetrics(C.Structure):
                 ("si", C.c_double), ("ti", C.c_double)]
 
 
+class VqaPsnrHvsMetrics(C.Structure):
+    _fields_ = [("s_hvs", C.c_double), ("s_hvsm", C.c_double), ("psnr_hvs", C.c_double), ("psnr_hvsm", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -159,6 +166,8 @@ SIGNATURES = {
     "vqa_motion_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaMotionMetrics), C.c_int]),
     "vqa_siti_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_siti_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaSitiMetrics), C.c_int]),
+    "vqa_psnr_hvs_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_psnr_hvs_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaPsnrHvsMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -331,4 +331,21 @@ void launch_siti(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n
 // five words -> the record: the divisions and square roots of include/vqa.h in double, on the host (h x w: the plane)
 void siti_finalize(const unsigned long long *words, int h, int w, int depth, vqa_siti_metrics *out);
 
+// PSNR-HVS and PSNR-HVS-M (vqa_psnr_hvs_submit): k_psnr_hvs.hip
+constexpr int PSNR_HVS_MIN_DIM = 16;
+constexpr int PSNR_HVS_WORDS = 4;                  // per (frame, plane): S_hvs lo, hi and S_hvsm lo, hi (a sum = hi 2^32 + lo)
+constexpr float PSNR_HVS_FIX = 1048576.f;          // 2^20: the quantum of a block's two sums is 2^-20
+constexpr double PSNR_HVS_CSF_SCALE = 25.735088;   // csf = scale / Q
+constexpr int PSNR_HVS_Q[8][8] = {                 // JPEG Annex K, luminance
+    {16, 11, 10, 16, 24, 40, 51, 61},     {12, 12, 14, 19, 26, 58, 60, 55},     {14, 13, 16, 24, 40, 57, 69, 56},
+    {14, 17, 22, 29, 51, 87, 80, 62},     {18, 22, 37, 56, 68, 109, 103, 77},   {24, 35, 55, 64, 81, 104, 113, 92},
+    {49, 64, 78, 87, 103, 121, 120, 101}, {72, 92, 95, 98, 112, 100, 103, 99}};
+// one group of same-geometry planes of n frame pairs: the whole 8x8 blocks of every plane.  Adds the four integer words into
+// acc[(frame * n_planes + plane) * PSNR_HVS_WORDS ..], which the caller has zeroed.
+void launch_psnr_hvs(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                     int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth,
+                     unsigned long long *acc);
+// four words -> the record: the divisions and logarithms of include/vqa.h in double, on the host (h x w: the plane)
+void psnr_hvs_finalize(const unsigned long long *words, int h, int w, int depth, vqa_psnr_hvs_metrics *out);
+
 } // namespace vqa

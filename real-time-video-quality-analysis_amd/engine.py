@@ -41,6 +41,9 @@ assert MOTION_DTYPE.itemsize == C.sizeof(N.VqaMotionMetrics)
 SITI_DTYPE = np.dtype([("grad_sum", np.float64), ("grad_sq", np.uint64), ("diff_sum", np.int64), ("diff_sq", np.uint64),
                        ("si", np.float64), ("ti", np.float64)], align=True)
 assert SITI_DTYPE.itemsize == C.sizeof(N.VqaSitiMetrics)
+PSNR_HVS_DTYPE = np.dtype([("s_hvs", np.float64), ("s_hvsm", np.float64), ("psnr_hvs", np.float64), ("psnr_hvsm", np.float64)],
+                          align=True)
+assert PSNR_HVS_DTYPE.itemsize == C.sizeof(N.VqaPsnrHvsMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -48,6 +51,7 @@ _BATCHES = {
     "_pending_a": ("vqa_adm_submit", "vqa_adm_wait", ADM_DTYPE, N.VqaAdmMetrics),
     "_pending_m": ("vqa_motion_submit", "vqa_motion_wait", MOTION_DTYPE, N.VqaMotionMetrics),
     "_pending_s": ("vqa_siti_submit", "vqa_siti_wait", SITI_DTYPE, N.VqaSitiMetrics),
+    "_pending_h": ("vqa_psnr_hvs_submit", "vqa_psnr_hvs_wait", PSNR_HVS_DTYPE, N.VqaPsnrHvsMetrics),
 }
 
 
@@ -254,7 +258,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -391,7 +395,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -528,6 +532,24 @@ class Engine:
         self.siti_submit(ref, planes, prev0, frame_bytes)
         return self.siti_wait()
 
+    # ---- PSNR-HVS and PSNR-HVS-M ------------------------------------------------
+    def psnr_hvs_submit(self, ref, dist, planes, frame_bytes=None):
+        """PSNR-HVS and PSNR-HVS-M for n frame pairs (vqa_psnr_hvs_submit): the arrays / DeviceFrames and plane tuples of
+        quality_submit; every plane at least 16 x 16, and only its whole 8x8 blocks are looked at.  A batch of its own: it may
+        follow a quality_submit, a vif_submit, an adm_submit, a motion_submit and a siti_submit of the same frames before any of
+        them is waited for."""
+        self._batch_submit("_pending_h", self._pair_args(ref, dist, planes, frame_bytes), planes)
+
+    def psnr_hvs_wait(self):
+        """-> [n, n_planes] records (PSNR_HVS_DTYPE): s_hvs and s_hvsm, the two CSF-weighted mean squared errors, and psnr_hvs
+        and psnr_hvsm in dB (inf for identical planes)."""
+        return self._batch_wait("_pending_h")
+
+    def psnr_hvs(self, ref, dist, planes, frame_bytes=None):
+        """PSNR-HVS and PSNR-HVS-M per plane for n frame pairs; returns [n, n_planes] structured array (PSNR_HVS_DTYPE)."""
+        self.psnr_hvs_submit(ref, dist, planes, frame_bytes)
+        return self.psnr_hvs_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -535,7 +557,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_KNOWN:
+        for k in N.K_IDS_EVERY:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -388,7 +388,8 @@ class Complexity:
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
-    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False):
+    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
+                 psnr_hvs=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -401,7 +402,10 @@ class Quality:
         siti    True: every chunk's REFERENCE frames also go through the SI/TI kernel (Engine.siti_submit) from the same upload,
                 prev0 being the reference feed's halo slot as for motion; the pass's tuple - whatever vif, adm and motion made
                 it - then gains ONE further last element, the SI/TI records [n,p] (engine.SITI_DTYPE: si, ti and the four sums);
-                "only": no SSE / SSIM"""
+                "only": no SSE / SSIM
+        psnr_hvs True: every chunk also goes through the PSNR-HVS kernel (Engine.psnr_hvs_submit) from the SAME upload; the
+                pass's tuple - whatever vif, adm, motion and siti made it - then gains ONE further last element, after SI/TI's:
+                the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE: s_hvs, s_hvsm, psnr_hvs, psnr_hvsm); "only": no SSE / SSIM"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -421,8 +425,13 @@ class Quality:
             raise ValueError("siti must be False, True or 'only'")
         if siti == "only" and scales:
             raise ValueError("an SI/TI-only pass has no SSIM scales")
-        self.motion, self.siti = motion, siti
-        self.ssim = vif != "only" and adm != "only" and motion != "only" and siti != "only"   # the pass measures SSE / SSIM
+        if not (isinstance(psnr_hvs, bool) or (isinstance(psnr_hvs, str) and psnr_hvs == "only")):
+            raise ValueError("psnr_hvs must be False, True or 'only'")
+        if psnr_hvs == "only" and scales:
+            raise ValueError("a PSNR-HVS-only pass has no SSIM scales")
+        self.motion, self.siti, self.psnr_hvs = motion, siti, psnr_hvs
+        # the pass measures SSE / SSIM
+        self.ssim = vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only"
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -495,7 +504,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     leaves sse and ssim None as well.  With Quality(.., motion=True) three elements are appended: the VIF records or None, the ADM
     records or None and the motion records [n,p] (MOTION_PASS_DTYPE); motion="only" leaves sse and ssim None as well.
     Quality(.., siti=True) appends ONE further last element to whichever of these tuples the pass returns: the SI/TI records
-    [n,p] (engine.SITI_DTYPE); siti="only" leaves sse and ssim None as well.
+    [n,p] (engine.SITI_DTYPE); siti="only" leaves sse and ssim None as well.  Quality(.., psnr_hvs=True) likewise appends ONE
+    further last element, after SI/TI's: the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE); psnr_hvs="only" leaves sse and ssim
+    None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -546,6 +557,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.siti:
             from .engine import SITI_DTYPE
             q += (np.zeros((0, len(quality.planes)), SITI_DTYPE),)
+        if quality.psnr_hvs:
+            from .engine import PSNR_HVS_DTYPE
+            q += (np.zeros((0, len(quality.planes)), PSNR_HVS_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -561,7 +575,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion and SI/TI alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -669,7 +683,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -708,6 +722,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                     if quality.siti:
                         eng.siti_submit(pair[0], quality.planes, prev0)
                         p["has_s"] = True
+                if quality.psnr_hvs:
+                    eng.psnr_hvs_submit(pair[0], pair[1], quality.planes)
+                    p["has_h"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -726,7 +743,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti = [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs = [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -742,6 +759,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["mres"] = eng.motion_wait()
             if p["has_s"]:
                 p["sres"] = eng.siti_wait()
+            if p["has_h"]:
+                p["hres"] = eng.psnr_hvs_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -768,6 +787,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 mot.append(p.pop("mres"))
             if p["has_s"]:
                 siti.append(p.pop("sres"))
+            if p["has_h"]:
+                hvs.append(p.pop("hres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -834,6 +855,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (motion_records(np.concatenate(mot)),)
     if want_q and quality.siti:
         q += (np.concatenate(siti),)
+    if want_q and quality.psnr_hvs:
+        q += (np.concatenate(hvs),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

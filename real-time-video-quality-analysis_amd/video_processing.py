@@ -149,7 +149,26 @@ def frame_siti(reference, layout="bgr24", height=None, width=None, engine=None, 
     return q[-1]["si"], q[-1]["ti"], [(p[0], p[1]) for p in planes]
 
 
-def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None):
+PSNR_HVS_DB_CAP = 100.0   # JSON has no infinity: the log and the row carry min(dB, 100); the C record keeps the infinity
+
+
+def frame_psnr_hvs(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame PSNR-HVS and PSNR-HVS-M per plane (Engine.psnr_hvs through the one-pass pipeline of frame_quality; both
+    streams are uploaded once).  The definition is include/vqa.h's: the published 8x8-block form, whole blocks only.
+    Returns (psnr_hvs [n,p] float64 dB, psnr_hvsm [n,p] float64 dB - inf for identical planes: nothing is capped here -,
+    s_hvs [n,p], s_hvsm [n,p] - the two CSF-weighted mean squared errors -, plane sizes).  Every plane at least 16 x 16."""
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, psnr_hvs="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    return r["psnr_hvs"], r["psnr_hvsm"], r["s_hvs"], r["s_hvsm"], [(p[0], p[1]) for p in planes]
+
+
+def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -159,6 +178,9 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     motion, likewise.
     siti: None, or the first plane's SI/TI records [n] (engine.SITI_DTYPE): the log then also carries si and ti, after the motion
     keys and before vmaf, likewise (P.910's clip values are the pooled maxima).  The model never reads them.
+    psnr_hvs: None, or the first plane's PSNR-HVS records [n] (engine.PSNR_HVS_DTYPE): the log then also carries psnr_hvs and
+    psnr_hvsm in dB, after ti and before vmaf, likewise.  JSON has no infinity: the log writes min(value, 100.0) dB
+    (PSNR_HVS_DB_CAP), so identical frames read 100.0.  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -179,6 +201,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         siti = np.asarray(siti).reshape(-1)
         names += ["si", "ti"]
         cols += [siti["si"].astype(np.float64), siti["ti"].astype(np.float64)]
+    if psnr_hvs is not None:
+        psnr_hvs = np.asarray(psnr_hvs).reshape(-1)
+        names += ["psnr_hvs", "psnr_hvsm"]
+        cols += [np.minimum(psnr_hvs[k].astype(np.float64), PSNR_HVS_DB_CAP) for k in ("psnr_hvs", "psnr_hvsm")]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -299,7 +325,7 @@ def _open_quality_stream(src, layout, height, width):
 
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
-                       adm=False, motion=False, siti=False):
+                       adm=False, motion=False, siti=False, psnr_hvs=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -310,6 +336,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     motion=True: likewise VMAF's motion feature of the reference stream (motion2 and motion of the first plane).
     siti=True: likewise ITU-T P.910's spatial and temporal information of the reference stream (si and ti of the first plane; a
     model file does not turn it on).
+    psnr_hvs=True: likewise PSNR-HVS and PSNR-HVS-M (psnr_hvs and psnr_hvsm of the first plane in dB, capped at 100.0 - JSON has
+    no infinity; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -325,14 +353,15 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
-        if vif or adm or motion or siti:
+        if vif or adm or motion or siti or psnr_hvs:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
             q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
-                                                             adm=bool(adm), motion=bool(motion), siti=bool(siti)),
+                                                             adm=bool(adm), motion=bool(motion), siti=bool(siti),
+                                                             psnr_hvs=bool(psnr_hvs)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -369,20 +398,23 @@ MODE_KEYS = {
 }
 
 
-def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False):
-    """the first plane's VIF / ADM / motion / SI and TI of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = None
-    if siti:   # the tuple's one further last element; what is left is the tuple of a pass without it
+def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
+    rec = hvs = None
+    if psnr_hvs:   # the tuple's last element, then SI/TI's; what is left is the tuple of a pass without them
+        hvs, q = q[-1][:, 0], q[:-1]
+    if siti:
         rec, q = q[-1][:, 0], q[:-1]
+    more = {"siti": rec} if hvs is None else {"siti": rec, "psnr_hvs": hvs}
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
-                      model=model, siti=rec)
+                      model=model, **more)
     elif adm:
-        write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0], siti=rec)
+        write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0], **more)
     elif vif:
-        write_vif_log(vmaf_log, q[-1]["scale"][:, 0], siti=rec)
+        write_vif_log(vmaf_log, q[-1]["scale"][:, 0], **more)
     else:
-        write_vif_log(vmaf_log, siti=rec)
+        write_vif_log(vmaf_log, **more)
 
 
 def _check_mode_keys(config):
@@ -400,6 +432,8 @@ def _check_mode_keys(config):
         raise ValueError("motion_feature must be true or false.")
     if "siti" in config and not isinstance(config["siti"], bool):
         raise ValueError("siti must be true or false.")
+    if "psnr_hvs" in config and not isinstance(config["psnr_hvs"], bool):
+        raise ValueError("psnr_hvs must be true or false.")
     mp = config.get("vmaf_model_path")
     if mp is not None and not (isinstance(mp, str) and os.path.isfile(mp) and os.access(mp, os.R_OK)):
         raise ValueError("vmaf_model_path must be null or the path of a readable model file.")
@@ -437,6 +471,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         and motion_feature on and the row gains VMAF, the pooled mean of the per-frame scores, right after SSIM),
         siti (true: the row gains SI and TI, ITU-T P.910's spatial and temporal information of the INPUT stream's first plane -
         the pooled MAXIMA over the frames -, after MOTION; default false; a model file does not turn it on),
+        psnr_hvs (true: the row gains PSNR_HVS and PSNR_HVSM, the pooled means of the first plane's per-frame PSNR-HVS and
+        PSNR-HVS-M in dB, each frame's value capped at 100.0 - JSON and the row have no infinity -, after TI; default false; a
+        model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -458,6 +495,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     adm = config.get("adm", False)
     mot = config.get("motion_feature", False)
     siti = config.get("siti", False)
+    hvs = config.get("psnr_hvs", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -505,13 +543,14 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         planes = LAYOUTS[layout][0](h, w)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
-            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti),
+            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
+                                                                     psnr_hvs=hvs),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti)
+        if vif or adm or mot or siti or hvs:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -566,6 +605,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         for k in ("si", "ti"):     # ITU-T P.910: the clip's value is the maximum over its frames
             if k in pooled:
                 metrics[k.upper()] = float(pooled[k]["max"])
+        for k in ("psnr_hvs", "psnr_hvsm"):   # per-frame dB capped at 100 by the log's writer
+            if k in pooled:
+                metrics[k.upper()] = float(pooled[k]["mean"])
     return metrics
 
 
@@ -588,7 +630,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs;
     #                           and that a vmaf_model_path names a readable file
 
 
