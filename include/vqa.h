@@ -274,6 +274,16 @@ typedef struct vqa_psnr_hvs_metrics {
     double psnr_hvsm; /* 10 log10((2^depth - 1)^2 / s_hvsm), +infinity when s_hvsm = 0                                */
 } vqa_psnr_hvs_metrics;
 
+/* CIEDE2000 colour difference of one frame pair, the three planes of a pixel taken together (vqa_ciede_submit /
+ * vqa_ciede_wait; the definition and the bound of the sum are stated there).  de_sum is the device's 2^-20 fixed-point integer
+ * total, so the same pair gives the same bits at any place of any batch, from host or device memory; the mean and the score
+ * are formed from it in double on the host by vqa_ciede_wait.                                                              */
+typedef struct vqa_ciede_metrics {
+    double de_sum;    /* sum over the luma grid of min(dE00, 4096), each pixel's value rounded to 2^-20              */
+    double de_mean;   /* de_sum / (h w)                                                                               */
+    double ciede2000; /* 45 - 20 log10(de_mean), libvmaf's score shape; +infinity when de_mean = 0                    */
+} vqa_ciede_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -578,6 +588,82 @@ VQA_API int vqa_psnr_hvs_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t 
                                 int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_psnr_hvs_wait(vqa_ctx *ctx, vqa_psnr_hvs_metrics *out, int n_entries);
 
+/* ---- CIEDE2000 (CIE 142-2001; Sharma, Wu and Dalal 2005): the colour difference dE00, three planes jointly ----
+ * Every other metric here looks at one plane at a time; this one turns the three samples of a pixel of either image into
+ * CIELAB and takes the CIEDE2000 difference of the two colours.  Where this text and a tool differ in a detail, this text is
+ * what is built.
+ * A frame is THREE planes of one depth (8 bits, or 9..16 bits as uint16), the RAW INTEGER SAMPLES read as they are.
+ * Colour model (`model`):
+ *   VQA_CIEDE_YUV709   planes Y, U, V.  U and V share one geometry (width, height, row stride, pixel step): the luma's, or the
+ *             ceil-halved one, in each direction independently ((w + 1) / 2, (h + 1) / 2: 4:4:4, 4:2:2, 4:2:0, odd sizes
+ *             included).  With sh = 1 when the chroma width is halved (else 0) and sv likewise for the height, the chroma
+ *             sample of luma (i, j) is (i >> sv, j >> sh): replication, no interpolation.  With s = 2^(depth - 8):
+ *               y = (Y - 16 s) / (219 s), u = (U - 128 s) / (224 s), v = (V - 128 s) / (224 s)
+ *               R' = y + 1.5748 v, G' = y - 0.1873 u - 0.4681 v, B' = y + 1.8556 u            (BT.709, limited range)
+ *   VQA_CIEDE_BGR      planes B, G, R of a common geometry (any pixel step: packed bgr24 has step 3);
+ *               R' = R / (2^depth - 1), G' and B' likewise.
+ *   NO CLAMPING ANYWHERE: every piecewise function below is defined on all reals and takes its linear branch for negative
+ *   arguments, so out-of-gamut triples give finite, smooth values.
+ * R'G'B' -> linear, per channel:  c > 0.04045 ? ((c + 0.055) / 1.055)^2.4 : c / 12.92
+ * linear -> XYZ:   X = 0.4124 R + 0.3576 G + 0.1805 B, Y = 0.2126 R + 0.7152 G + 0.0722 B, Z = 0.0193 R + 0.1192 G + 0.9505 B
+ *             (IEC 61966-2-1), each divided by the white point taken as the matrix's ROW SUMS, (0.9505, 1.0000, 1.0890): a gray
+ *             pixel has a = b = 0 up to rounding.
+ * XYZ -> Lab:      f(t) = t > 0.008856 ? cbrt(t) : 7.787 t + 16 / 116;
+ *             L = 116 f(Y) - 16, a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z)).
+ * dE00 of (L1, a1, b1), (L2, a2, b2) with the parametric weights (kL, kC, kH); angles in degrees:
+ *   C_i = sqrt(a_i^2 + b_i^2), Cm = (C1 + C2) / 2, G = 0.5 (1 - sqrt(Cm^7 / (Cm^7 + 25^7)))
+ *   a'_i = (1 + G) a_i, C'_i = sqrt(a'_i^2 + b_i^2), h'_i = atan2(b_i, a'_i) brought into [0, 360), and 0 when a'_i = b_i = 0
+ *   dL' = L2 - L1, dC' = C'2 - C'1
+ *   dh' = 0 when C'1 C'2 = 0; else h'2 - h'1, less 360 when that is above 180, plus 360 when it is below -180   (eq. 10)
+ *   dH' = 2 sqrt(C'1 C'2) sin(dh' / 2)
+ *   Lm = (L1 + L2) / 2, C'm = (C'1 + C'2) / 2
+ *   hm = h'1 + h'2 when C'1 C'2 = 0; else (h'1 + h'2) / 2 when |h'1 - h'2| <= 180; else (h'1 + h'2 + 360) / 2 when
+ *        h'1 + h'2 < 360, and (h'1 + h'2 - 360) / 2 otherwise                                                    (eq. 14)
+ *   T = 1 - 0.17 cos(hm - 30) + 0.24 cos(2 hm) + 0.32 cos(3 hm + 6) - 0.20 cos(4 hm - 63)
+ *   dtheta = 30 exp(-((hm - 275) / 25)^2), R_C = 2 sqrt(C'm^7 / (C'm^7 + 25^7))
+ *   S_L = 1 + 0.015 (Lm - 50)^2 / sqrt(20 + (Lm - 50)^2), S_C = 1 + 0.045 C'm, S_H = 1 + 0.015 C'm T
+ *   R_T = -sin(2 dtheta) R_C
+ *   dE00 = sqrt(tL^2 + tC^2 + tH^2 + R_T tC tH), tL = dL' / (kL S_L), tC = dC' / (kC S_C), tH = dH' / (kH S_H)
+ *   A pair of triples with equal integer samples gives EXACTLY 0 (the kernel tests for it).
+ * weights: kL, kC, kH as doubles, NULL = (1, 1, 1), the CIE standard.  Non-finite or non-positive: VQA_ERR_INVALID.
+ * Results, ONE ENTRY PER FRAME (not per plane): de_mean = the mean of dE00 over the luma grid;
+ *   ciede2000 = 45 - 20 log10(de_mean), libvmaf's score shape, +infinity when de_mean = 0.
+ * How the device forms it:
+ *   arithmetic per pixel is fp32; the powers of 7 are multiplications (as (25 / C)^7, which cannot overflow); the radicand
+ *   of dE00 is raised to 0 when rounding left it below.
+ *   sums      BATCH-INVARIANT BITS: each pixel's dE00 is rounded to a 2^-20 quantum and added as a 64-bit integer: one word
+ *             per frame, whatever the tiling and the order in which workgroups retire.  In-range colours give dE00 < 2^8.
+ *             For UNCLAMPED input (raw uint16 samples far above 2^depth - 1) two of the three terms stay bounded at weights
+ *             (1, 1, 1): |dC'| <= 2 C'm gives |tC| < 2 / 0.045 < 45; |dH'| <= 2 sqrt(C'1 C'2) <= 2 C'm and
+ *             T >= 1 - 0.17 - 0.24 - 0.32 - 0.20 = 0.07 give |tH| < 2 / (0.015 * 0.07) < 1905; |R_T| <= 2.  tL is NOT bounded:
+ *             S_L = 1 at Lm = 50 whatever dL' is, and L is as wide as the input - a sample of 65535 read at depth 9 gives
+ *             y near 150, R' near 380, a linear value near 1.4e6 and L near 1.3e4, and the linear branches reach L near -5e3
+ *             - so dE00 can exceed 2^14, and weights below 1 divide all three terms further.
+ *             THE PER-PIXEL VALUE IS THEREFORE SATURATED AT 2^12: min(dE00, 4096); a NaN, which no finite input has
+ *             produced, would count as 4096 too.  In-range input never comes near it.  A pixel's fixed-point value is then at
+ *             most 2^32 and a frame of 2^28 pixels gives a word of at most 2^60: it cannot overflow.  The rounding moves
+ *             de_mean by at most half a quantum: 2^-21.
+ *   host      the word -> double, times 2^-20 (de_sum), over h w (de_mean), and the logarithm: in vqa_ciede_wait, in double,
+ *             with contraction off.
+ * Limits: luma at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.  n_planes other than 3, U and V (or
+ * B, G, R) geometries that differ, a chroma size that is neither the luma's nor its ceil-half, mixed depths, an unknown
+ * model: VQA_ERR_INVALID.
+ * The contract of vqa_psnr_hvs_submit: asynchronous, the same plane descriptors, depths (one per submit), alignment rules,
+ * memory kinds and failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while a CIEDE2000 batch is
+ * pending.  A CIEDE2000 batch is a batch of its own: it may be in flight next to a batch of every other kind of the same ctx
+ * (one upload then serves all), and each wait collects its own kind only - vqa_ciede_wait with only another kind pending,
+ * and another kind's wait with only a CIEDE2000 batch pending, are VQA_ERR_STATE and leave that batch pending.
+ * One fused kernel per submit: a thread owns a 2 x 4 luma patch of both images (a 4:2:0 chroma sample is loaded once for four
+ * luma samples), forms both Lab triples and dE00 in registers; only the one word per frame leaves the kernel.  Scratch on the
+ * device: 8 bytes per frame; host frames are staged in the buffers a quality, a VIF, an ADM or a PSNR-HVS submit uses.  All
+ * of it is kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_ciede_wait: n entries (n_entries = n).                                                                      */
+enum vqa_ciede_model { VQA_CIEDE_YUV709 = 0, VQA_CIEDE_BGR = 1 };
+VQA_API int vqa_ciede_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                             int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes,
+                             int model, const double *weights);
+VQA_API int vqa_ciede_wait(vqa_ctx *ctx, vqa_ciede_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -612,7 +698,10 @@ enum vqa_kernel_id {
                                 being unknown); id 22 stays unnamed                                                      */
     VQA_K_PSNR_HVS = 23,     /* vqa_psnr_hvs_submit: the 8x8 DCTs, the masks and the two weighted sums (one entry per group of
                                 same-geometry planes)                                                                    */
-    VQA_K_PAST = 24          /* one past the last id: ... VQA_K_SITI .. VQA_K_LAST - 1 and VQA_K_PSNR_HVS .. VQA_K_PAST - 1 */
+    VQA_K_PAST = 24,         /* one past VQA_K_PSNR_HVS, as PSNR-HVS shipped it (kept at 24 for callers and tests that rely on
+                                id 24 being unknown); id 24 stays unnamed                                                */
+    VQA_K_CIEDE = 25,        /* vqa_ciede_submit: both Lab conversions, dE00 and the fixed-point sum (one entry per submit) */
+    VQA_K_BEYOND = 26        /* one past the last id: ... VQA_K_PSNR_HVS .. VQA_K_PAST - 1 and VQA_K_CIEDE .. VQA_K_BEYOND - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

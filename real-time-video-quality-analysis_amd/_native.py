@@ -46,7 +46,9 @@ K_IDS_ALL = K_IDS + (K_MOTION,)                   # the ids below K_END (kept as
 K_SITI, K_LAST = 21, 22                           # added beyond K_END, which stays 20; id 20 is unnamed
 K_IDS_KNOWN = K_IDS_ALL + (K_SITI,)               # the ids below K_LAST (kept as SI/TI shipped it)
 K_PSNR_HVS, K_PAST = 23, 24                       # added beyond K_LAST, which stays 22; id 22 is unnamed
-K_IDS_EVERY = K_IDS_KNOWN + (K_PSNR_HVS,)         # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_EVERY = K_IDS_KNOWN + (K_PSNR_HVS,)         # the ids below K_PAST (kept as PSNR-HVS shipped it)
+K_CIEDE, K_BEYOND = 25, 26                        # added beyond K_PAST, which stays 24; id 24 is unnamed
+K_IDS_NAMED = K_IDS_EVERY + (K_CIEDE,)            # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -63,6 +65,10 @@ ADM_MIN_DIM = 16   # vqa_adm_submit: the bands of scale 3 of a 16 x 16 plane are
 MOTION_MIN_DIM = 16   # vqa_motion_submit: the limit of VIF and ADM, whose planes it shares
 SITI_MIN_DIM = 16   # vqa_siti_submit: the limit of VIF, ADM and motion, whose planes it shares
 PSNR_HVS_MIN_DIM = 16   # vqa_psnr_hvs_submit: the limit of the family, whose planes it shares
+CIEDE_MIN_DIM = 16   # vqa_ciede_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+CIEDE_YUV709, CIEDE_BGR = 0, 1   # vqa_ciede_submit's colour models
+CIEDE_WEIGHTS_CIE = (1.0, 1.0, 1.0)       # kL, kC, kH of the CIE standard: the default
+CIEDE_WEIGHTS_LIBVMAF = (0.65, 1.0, 4.0)  # what libvmaf's ciede2000 feature is believed to use (unverified: README)
 MOTION_SAD, MOTION_FARNEBACK = 0, 1
 
 
@@ -125,6 +131,10 @@ class VqaPsnrHvsMetrics(C.Structure):
     _fields_ = [("s_hvs", C.c_double), ("s_hvsm", C.c_double), ("psnr_hvs", C.c_double), ("psnr_hvsm", C.c_double)]
 
 
+class VqaCiedeMetrics(C.Structure):
+    _fields_ = [("de_sum", C.c_double), ("de_mean", C.c_double), ("ciede2000", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -168,6 +178,9 @@ SIGNATURES = {
     "vqa_siti_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaSitiMetrics), C.c_int]),
     "vqa_psnr_hvs_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_psnr_hvs_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaPsnrHvsMetrics), C.c_int]),
+    "vqa_ciede_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
+                                   C.c_int, C.POINTER(C.c_double)]),
+    "vqa_ciede_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaCiedeMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

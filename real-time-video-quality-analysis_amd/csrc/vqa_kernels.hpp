@@ -348,4 +348,16 @@ void launch_psnr_hvs(hipStream_t st, const uint8_t *ref, const uint8_t *dist, in
 // four words -> the record: the divisions and logarithms of include/vqa.h in double, on the host (h x w: the plane)
 void psnr_hvs_finalize(const unsigned long long *words, int h, int w, int depth, vqa_psnr_hvs_metrics *out);
 
+// CIEDE2000 (vqa_ciede_submit): k_ciede.hip
+constexpr int CIEDE_MIN_DIM = 16;
+constexpr float CIEDE_FIX = 1048576.f;             // 2^20: the quantum of a pixel's dE00 is 2^-20
+constexpr float CIEDE_SATURATE = 4096.f;           // 2^12: a pixel counts min(dE00, 4096) (include/vqa.h)
+// n frame pairs of three planes (checked by the caller: plane 0 the full grid, planes 1 and 2 of one geometry, the grid's or its
+// ceil-half in either direction).  Adds each frame's integer word into acc[frame], which the caller has zeroed.
+void launch_ciede(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                  int64_t dist_frame_stride, const vqa_plane_desc *planes, int depth, int model, const double *weights,
+                  unsigned long long *acc);
+// the word -> the record: the division and the logarithm of include/vqa.h in double, on the host (h x w: the luma grid)
+void ciede_finalize(unsigned long long word, int h, int w, vqa_ciede_metrics *out);
+
 } // namespace vqa

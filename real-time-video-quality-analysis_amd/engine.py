@@ -44,6 +44,8 @@ assert SITI_DTYPE.itemsize == C.sizeof(N.VqaSitiMetrics)
 PSNR_HVS_DTYPE = np.dtype([("s_hvs", np.float64), ("s_hvsm", np.float64), ("psnr_hvs", np.float64), ("psnr_hvsm", np.float64)],
                           align=True)
 assert PSNR_HVS_DTYPE.itemsize == C.sizeof(N.VqaPsnrHvsMetrics)
+CIEDE_DTYPE = np.dtype([("de_sum", np.float64), ("de_mean", np.float64), ("ciede2000", np.float64)], align=True)
+assert CIEDE_DTYPE.itemsize == C.sizeof(N.VqaCiedeMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -52,6 +54,7 @@ _BATCHES = {
     "_pending_m": ("vqa_motion_submit", "vqa_motion_wait", MOTION_DTYPE, N.VqaMotionMetrics),
     "_pending_s": ("vqa_siti_submit", "vqa_siti_wait", SITI_DTYPE, N.VqaSitiMetrics),
     "_pending_h": ("vqa_psnr_hvs_submit", "vqa_psnr_hvs_wait", PSNR_HVS_DTYPE, N.VqaPsnrHvsMetrics),
+    "_pending_e": ("vqa_ciede_submit", "vqa_ciede_wait", CIEDE_DTYPE, N.VqaCiedeMetrics),   # (one entry per frame)
 }
 
 
@@ -258,7 +261,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000 and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -395,7 +398,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -550,6 +553,40 @@ class Engine:
         self.psnr_hvs_submit(ref, dist, planes, frame_bytes)
         return self.psnr_hvs_wait()
 
+    # ---- CIEDE2000 --------------------------------------------------------------
+    @staticmethod
+    def ciede_model(planes):
+        """the colour model a plane list implies: CIEDE_BGR for three planes whose pixel step is 3 samples (packed bgr24 and its
+        16-bit kin), CIEDE_YUV709 otherwise"""
+        bps = 2 if planes_depth(planes) > 8 else 1
+        return N.CIEDE_BGR if len(planes) == 3 and all(int(p[4]) == 3 * bps for p in planes) else N.CIEDE_YUV709
+
+    def ciede_submit(self, ref, dist, planes, model=None, weights=N.CIEDE_WEIGHTS_CIE, frame_bytes=None):
+        """CIEDE2000 for n frame pairs (vqa_ciede_submit): the arrays / DeviceFrames and plane tuples of quality_submit, exactly
+        THREE planes taken together per pixel - Y, U, V (BT.709 limited range; U and V of the luma's size or its ceil-half in
+        either direction) or B, G, R; luma at least 16 x 16.  model: N.CIEDE_YUV709 | N.CIEDE_BGR | None (ciede_model(planes)).
+        weights: (kL, kC, kH), positive and finite; (1, 1, 1) is the CIE standard, N.CIEDE_WEIGHTS_LIBVMAF = (0.65, 1, 4) what
+        libvmaf's ciede2000 feature is believed to use (unverified).  A batch of its own, like psnr_hvs_submit."""
+        if model is None:
+            model = self.ciede_model(planes)
+        if weights is not None and len(weights) != 3:
+            raise ValueError("weights must be (kL, kC, kH)")
+        k = (C.c_double * 3)(*[float(x) for x in weights]) if weights is not None else None
+        *args, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        st = self.lib.vqa_ciede_submit(self.ctx, *args, plane_descs(planes), len(planes), int(model), k)
+        N.check(st, "vqa_ciede_submit", self.ctx)
+        self._pending_e = (args[3], 1, keep)
+
+    def ciede_wait(self):
+        """-> [n] records (CIEDE_DTYPE), one per frame: de_sum, de_mean (the mean dE00 over the luma grid) and ciede2000 =
+        45 - 20 log10(de_mean) (inf for identical frames)."""
+        return self._batch_wait("_pending_e").reshape(-1)
+
+    def ciede(self, ref, dist, planes, model=None, weights=N.CIEDE_WEIGHTS_CIE, frame_bytes=None):
+        """CIEDE2000 per frame for n frame pairs; returns [n] structured array (CIEDE_DTYPE)."""
+        self.ciede_submit(ref, dist, planes, model, weights, frame_bytes)
+        return self.ciede_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -557,7 +594,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_EVERY:
+        for k in N.K_IDS_NAMED:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -389,7 +389,7 @@ class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
-                 psnr_hvs=False):
+                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -405,7 +405,12 @@ class Quality:
                 "only": no SSE / SSIM
         psnr_hvs True: every chunk also goes through the PSNR-HVS kernel (Engine.psnr_hvs_submit) from the SAME upload; the
                 pass's tuple - whatever vif, adm, motion and siti made it - then gains ONE further last element, after SI/TI's:
-                the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE: s_hvs, s_hvsm, psnr_hvs, psnr_hvsm); "only": no SSE / SSIM"""
+                the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE: s_hvs, s_hvsm, psnr_hvs, psnr_hvsm); "only": no SSE / SSIM
+        ciede   True: every chunk also goes through the CIEDE2000 kernel (Engine.ciede_submit, exactly three planes) from the
+                SAME upload; the pass's tuple then gains ONE further last element, after PSNR-HVS's: the CIEDE2000 records [n]
+                (engine.CIEDE_DTYPE: de_sum, de_mean, ciede2000 - one per frame, not per plane); "only": no SSE / SSIM.
+                ciede_weights: (kL, kC, kH), default the CIE standard (1, 1, 1); the colour model follows from the planes' pixel step
+                (Engine.ciede_model)"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -429,9 +434,20 @@ class Quality:
             raise ValueError("psnr_hvs must be False, True or 'only'")
         if psnr_hvs == "only" and scales:
             raise ValueError("a PSNR-HVS-only pass has no SSIM scales")
+        if not (isinstance(ciede, bool) or (isinstance(ciede, str) and ciede == "only")):
+            raise ValueError("ciede must be False, True or 'only'")
+        if ciede == "only" and scales:
+            raise ValueError("a CIEDE2000-only pass has no SSIM scales")
+        if ciede and len(planes) != 3:
+            raise ValueError("ciede needs three planes")
+        ciede_weights = tuple(float(x) for x in ciede_weights)
+        if len(ciede_weights) != 3 or not all(np.isfinite(x) and x > 0 for x in ciede_weights):
+            raise ValueError("ciede_weights must be three positive finite numbers (kL, kC, kH)")
         self.motion, self.siti, self.psnr_hvs = motion, siti, psnr_hvs
+        self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
-        self.ssim = vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only"
+        self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
+                     ciede != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -506,7 +522,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     Quality(.., siti=True) appends ONE further last element to whichever of these tuples the pass returns: the SI/TI records
     [n,p] (engine.SITI_DTYPE); siti="only" leaves sse and ssim None as well.  Quality(.., psnr_hvs=True) likewise appends ONE
     further last element, after SI/TI's: the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE); psnr_hvs="only" leaves sse and ssim
-    None as well.
+    None as well.  Quality(.., ciede=True) appends ONE further last element, after PSNR-HVS's: the CIEDE2000 records [n]
+    (engine.CIEDE_DTYPE, one per frame); ciede="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -560,6 +577,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.psnr_hvs:
             from .engine import PSNR_HVS_DTYPE
             q += (np.zeros((0, len(quality.planes)), PSNR_HVS_DTYPE),)
+        if quality.ciede:
+            from .engine import CIEDE_DTYPE
+            q += (np.zeros(0, CIEDE_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -575,7 +595,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion and SI/TI alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -683,7 +703,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -725,6 +745,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.psnr_hvs:
                     eng.psnr_hvs_submit(pair[0], pair[1], quality.planes)
                     p["has_h"] = True
+                if quality.ciede:
+                    eng.ciede_submit(pair[0], pair[1], quality.planes, None, quality.ciede_weights)
+                    p["has_e"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -743,7 +766,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs = [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie = [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -761,6 +784,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["sres"] = eng.siti_wait()
             if p["has_h"]:
                 p["hres"] = eng.psnr_hvs_wait()
+            if p["has_e"]:
+                p["eres"] = eng.ciede_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -789,6 +814,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 siti.append(p.pop("sres"))
             if p["has_h"]:
                 hvs.append(p.pop("hres"))
+            if p["has_e"]:
+                cie.append(p.pop("eres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -857,6 +884,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(siti),)
     if want_q and quality.psnr_hvs:
         q += (np.concatenate(hvs),)
+    if want_q and quality.ciede:
+        q += (np.concatenate(cie),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

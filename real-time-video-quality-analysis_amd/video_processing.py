@@ -168,7 +168,28 @@ def frame_psnr_hvs(reference, encoded, layout="bgr24", height=None, width=None, 
     return r["psnr_hvs"], r["psnr_hvsm"], r["s_hvs"], r["s_hvsm"], [(p[0], p[1]) for p in planes]
 
 
-def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None):
+def frame_ciede(reference, encoded, layout="bgr24", height=None, width=None, weights=N.CIEDE_WEIGHTS_CIE, engine=None,
+                batch_size=64, device=None):
+    """Per-frame CIEDE2000 (Engine.ciede through the one-pass pipeline of frame_quality; both streams are uploaded once): the
+    three planes of a pixel taken together, by the definition in include/vqa.h - bgr24 as sRGB, the planar YUV layouts as BT.709
+    limited range with replicated chroma.  weights: (kL, kC, kH); (1, 1, 1) is the CIE standard, N.CIEDE_WEIGHTS_LIBVMAF =
+    (0.65, 1, 4) what libvmaf's ciede2000 feature is believed to use (unverified).
+    Returns (ciede2000 [n] float64 = 45 - 20 log10(de_mean), inf for identical frames: nothing is capped here -, de_mean [n]).
+    Luma at least 16 x 16; a one-plane layout is a ValueError."""
+    if len(LAYOUTS[layout][1]) != 3:
+        raise ValueError("ciede needs three planes")
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, ciede="only", ciede_weights=weights),
+                      batch_size=batch_size, engine=engine, device=device)
+    r = q[-1]
+    return r["ciede2000"], r["de_mean"]
+
+
+def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -181,6 +202,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     psnr_hvs: None, or the first plane's PSNR-HVS records [n] (engine.PSNR_HVS_DTYPE): the log then also carries psnr_hvs and
     psnr_hvsm in dB, after ti and before vmaf, likewise.  JSON has no infinity: the log writes min(value, 100.0) dB
     (PSNR_HVS_DB_CAP), so identical frames read 100.0.  The model never reads them.
+    ciede: None, or the CIEDE2000 records [n] (engine.CIEDE_DTYPE, one per frame): the log then also carries ciede2000, after
+    psnr_hvsm and before vmaf, likewise capped at 100.0.  The model never reads it.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -205,6 +228,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         psnr_hvs = np.asarray(psnr_hvs).reshape(-1)
         names += ["psnr_hvs", "psnr_hvsm"]
         cols += [np.minimum(psnr_hvs[k].astype(np.float64), PSNR_HVS_DB_CAP) for k in ("psnr_hvs", "psnr_hvsm")]
+    if ciede is not None:
+        ciede = np.asarray(ciede).reshape(-1)
+        names += ["ciede2000"]
+        cols += [np.minimum(ciede["ciede2000"].astype(np.float64), PSNR_HVS_DB_CAP)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -325,7 +352,7 @@ def _open_quality_stream(src, layout, height, width):
 
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
-                       adm=False, motion=False, siti=False, psnr_hvs=False):
+                       adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -338,6 +365,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     model file does not turn it on).
     psnr_hvs=True: likewise PSNR-HVS and PSNR-HVS-M (psnr_hvs and psnr_hvsm of the first plane in dB, capped at 100.0 - JSON has
     no infinity; a model file does not turn it on).
+    ciede=True: likewise CIEDE2000 of the three planes together (ciede2000 = 45 - 20 log10 of the frame's mean dE00, capped at
+    100.0; three-plane layouts only; ciede_weights = (kL, kC, kH), default (1, 1, 1); a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -353,15 +382,18 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
-        if vif or adm or motion or siti or psnr_hvs:
+        if ciede and len(LAYOUTS[layout][1]) != 3:
+            raise ValueError("ciede needs three planes")
+        if vif or adm or motion or siti or psnr_hvs or ciede:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
             q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
                                                              adm=bool(adm), motion=bool(motion), siti=bool(siti),
-                                                             psnr_hvs=bool(psnr_hvs)),
+                                                             psnr_hvs=bool(psnr_hvs), ciede=bool(ciede),
+                                                             ciede_weights=ciede_weights),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -398,14 +430,19 @@ MODE_KEYS = {
 }
 
 
-def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS of a pass (the tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = None
-    if psnr_hvs:   # the tuple's last element, then SI/TI's; what is left is the tuple of a pass without them
+def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS and the frame's CIEDE2000 of a pass (the tail of stream.run's
+    quality tuple) -> vmaf_log"""
+    rec = hvs = cie = None
+    if ciede:      # the tuple's last element, then PSNR-HVS's, then SI/TI's; what is left is the tuple of a pass without them
+        cie, q = q[-1], q[:-1]
+    if psnr_hvs:
         hvs, q = q[-1][:, 0], q[:-1]
     if siti:
         rec, q = q[-1][:, 0], q[:-1]
     more = {"siti": rec} if hvs is None else {"siti": rec, "psnr_hvs": hvs}
+    if cie is not None:
+        more["ciede"] = cie
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -434,6 +471,13 @@ def _check_mode_keys(config):
         raise ValueError("siti must be true or false.")
     if "psnr_hvs" in config and not isinstance(config["psnr_hvs"], bool):
         raise ValueError("psnr_hvs must be true or false.")
+    if "ciede" in config and not isinstance(config["ciede"], bool):
+        raise ValueError("ciede must be true or false.")
+    if "ciede_weights" in config:
+        k = config["ciede_weights"]
+        if not (isinstance(k, (list, tuple)) and len(k) == 3 and
+                all(isinstance(x, (int, float)) and not isinstance(x, bool) and np.isfinite(x) and x > 0 for x in k)):
+            raise ValueError("ciede_weights must be three positive numbers [kL, kC, kH].")
     mp = config.get("vmaf_model_path")
     if mp is not None and not (isinstance(mp, str) and os.path.isfile(mp) and os.access(mp, os.R_OK)):
         raise ValueError("vmaf_model_path must be null or the path of a readable model file.")
@@ -474,6 +518,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         psnr_hvs (true: the row gains PSNR_HVS and PSNR_HVSM, the pooled means of the first plane's per-frame PSNR-HVS and
         PSNR-HVS-M in dB, each frame's value capped at 100.0 - JSON and the row have no infinity -, after TI; default false; a
         model file does not turn it on),
+        ciede (true: the row gains CIEDE2000, the pooled mean of the per-frame 45 - 20 log10(mean dE00) of the three planes taken
+        together, each frame's value capped at 100.0, after PSNR_HVSM; three-plane pixfmts only; default false; a model file does
+        not turn it on), ciede_weights ([kL, kC, kH], default [1, 1, 1], the CIE standard),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -496,6 +543,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     mot = config.get("motion_feature", False)
     siti = config.get("siti", False)
     hvs = config.get("psnr_hvs", False)
+    cie = config.get("ciede", False)
+    cie_k = tuple(config.get("ciede_weights", N.CIEDE_WEIGHTS_CIE))
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -544,13 +593,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
-                                                                     psnr_hvs=hvs),
+                                                                     psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs)
+        if vif or adm or mot or siti or hvs or cie:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -608,6 +657,8 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         for k in ("psnr_hvs", "psnr_hvsm"):   # per-frame dB capped at 100 by the log's writer
             if k in pooled:
                 metrics[k.upper()] = float(pooled[k]["mean"])
+        if "ciede2000" in pooled:             # likewise
+            metrics["CIEDE2000"] = float(pooled["ciede2000"]["mean"])
     return metrics
 
 
@@ -630,7 +681,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights;
     #                           and that a vmaf_model_path names a readable file
 
 
