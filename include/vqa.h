@@ -284,6 +284,19 @@ typedef struct vqa_ciede_metrics {
     double ciede2000; /* 45 - 20 log10(de_mean), libvmaf's score shape; +infinity when de_mean = 0                    */
 } vqa_ciede_metrics;
 
+/* GMSD of one plane pair (vqa_gmsd_submit / vqa_gmsd_wait; the definition and the bounds of the sums are stated there).  The
+ * three words are the device's integer totals of u = rint(gms 2^24) and of u^2, so the same pair gives the same words at any
+ * place of any batch, from host or device memory; the mean and the deviation are formed from them on the host by
+ * vqa_gmsd_wait.                                                                                                            */
+typedef struct vqa_gmsd_metrics {
+    uint64_t sum_u;     /* sum of u over the N samples of the downsampled grid                                          */
+    uint64_t sum_u2_lo; /* sum of u^2 = sum_u2_hi 2^32 + sum_u2_lo: the workgroups' totals, split into their low 32 bits  */
+    uint64_t sum_u2_hi; /*   and the rest before they are added                                                         */
+    int64_t count;      /* N = ceil(h / 2) ceil(w / 2)                                                                  */
+    double gms_mean;    /* sum_u / (N 2^24): the paper's GMSM; exactly 1 for identical planes                           */
+    double gmsd;        /* sqrt((N sum u^2 - (sum u)^2) / (N (N - 1))) / 2^24; exactly 0 for identical planes           */
+} vqa_gmsd_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -664,6 +677,50 @@ VQA_API int vqa_ciede_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *di
                              int model, const double *weights);
 VQA_API int vqa_ciede_wait(vqa_ctx *ctx, vqa_ciede_metrics *out, int n_entries);
 
+/* ---- GMSD: gradient magnitude similarity deviation (Xue, Zhang, Mou, Bovik, IEEE TIP 2014) ----
+ * The authors' published GMSD.m applied per plane, as read here; where this text and a tool differ in a detail, this text is
+ * what is built.  For one plane pair (ref r, dist d, `depth` bits, h x w) on the RAW INTEGER SAMPLES, peak = 2^depth - 1:
+ *   2x2 mean  D(i, j) = (x(2i, 2j) + x(2i+1, 2j) + x(2i, 2j+1) + x(2i+1, 2j+1)) / 4 for i < hd = ceil(h / 2) and
+ *             j < wd = ceil(w / 2).  A sample outside the plane counts as 0: MATLAB's conv2(.., 'same') with a 2x2 box reads
+ *             rows and columns i .. i+1, and (1:2:end, 1:2:end) keeps every other one.  The last row or column of an odd-sized
+ *             plane is therefore a half-weight mean, not a dropped row.  S = 4 D is an exact integer.
+ *   Prewitt   gx(i, j) = (D(i-1, j+1) + D(i, j+1) + D(i+1, j+1) - D(i-1, j-1) - D(i, j-1) - D(i+1, j-1)) / 3, gy its
+ *             transpose, at EVERY sample of D with D = 0 outside (conv2 'same' again: a zero fill, not a clamp, so a flat
+ *             non-zero field has gradient on its border ring).  q = (12 gx)^2 + (12 gy)^2 is an exact integer, sums and
+ *             differences of S: |12 gx| <= 12 peak, so q <= 288 peak^2, below 2^25 for 8-bit and below 2^41 for 16-bit samples.
+ *             m^2 = q / 144.
+ *   gms       (2 m_r m_d + T) / (m_r^2 + m_d^2 + T) with T = 170 (peak / 255)^2 - the paper's c = 170 on the 8-bit scale, so a
+ *             clip scores the same at any depth after exact upscaling.  0 < gms <= 1, and gms = 1 where q_r = q_d.
+ *   pooling   gmsd = the standard deviation of gms over the N = hd wd samples with divisor N - 1 (MATLAB's std2);
+ *             gms_mean = their mean (the paper's GMSM).
+ * How the device forms it: S of both images as integers; q_r, q_d as integers (32 bits at depth 8, 64 above); then in double
+ *             gms = (2 sqrt(q_r q_d) + c) / ((q_r + q_d) + c), c = 144 T = 144 (170 ((peak / 255) (peak / 255))), every step
+ *             rounded to double once.  sqrt(x x) = x in IEEE arithmetic, so q_r = q_d gives gms = 1 EXACTLY.
+ *   sums      BATCH-INVARIANT BITS: u = rint(gms 2^24), an integer, u <= 2^24.  Three integer words leave the device per
+ *             entry: sum u, and sum u^2 as two words.  A workgroup's 2048 samples give a total of u^2 below 2^59, which is
+ *             split into its low and its high 32 bits before it is added.  A plane of 2^28 samples has N <= 2^26: sum u < 2^50,
+ *             the low word below 2^58 and the high word below 2^42 - nothing can overflow, for any tiling.
+ *   host      sum u^2 = hi 2^32 + lo and N sum u^2 - (sum u)^2 (below 2^100) in 128-bit integer arithmetic; then
+ *             gmsd = sqrt(that / (N (N - 1))) / 2^24 and gms_mean = sum u / (N 2^24) in double, contraction off.  Identical
+ *             planes give gmsd = 0.0 and gms_mean = 1.0 exactly.  The rounding of u moves either result by less than 2^-24:
+ *             the deviation is 1-Lipschitz in the root mean square of the per-sample changes (at most 2^-25) times
+ *             sqrt(N / (N - 1)).
+ * Limits: every plane at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.
+ * The contract of vqa_psnr_hvs_submit: asynchronous, the same plane descriptors (one to four planes, each measured by itself;
+ * packed layouts through pixel_step), depths (one per submit), alignment rules, memory kinds and failure guarantee: a failed
+ * submit leaves nothing in flight.  VQA_ERR_STATE while a GMSD batch is pending.  A GMSD batch is a batch of its own: it may be
+ * in flight next to a batch of every other kind of the same ctx (one upload then serves all), and each wait collects its own
+ * kind only - vqa_gmsd_wait with only another kind pending, and another kind's wait with only a GMSD batch pending, are
+ * VQA_ERR_STATE and leave that batch pending.
+ * One fused kernel per group of same-geometry planes: a workgroup forms a 64 x 32 tile of S and its one-sample apron for both
+ * images in LDS straight from the input quads; only the three words leave the kernel.  Scratch on the device: 24 bytes per
+ * entry; host frames are staged in the buffers a quality, a VIF, an ADM, a PSNR-HVS or a CIEDE2000 submit uses.  All of it is
+ * kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_gmsd_wait: n * n_planes entries, frame-major.                                                                 */
+VQA_API int vqa_gmsd_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                            int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_gmsd_wait(vqa_ctx *ctx, vqa_gmsd_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -701,7 +758,11 @@ enum vqa_kernel_id {
     VQA_K_PAST = 24,         /* one past VQA_K_PSNR_HVS, as PSNR-HVS shipped it (kept at 24 for callers and tests that rely on
                                 id 24 being unknown); id 24 stays unnamed                                                */
     VQA_K_CIEDE = 25,        /* vqa_ciede_submit: both Lab conversions, dE00 and the fixed-point sum (one entry per submit) */
-    VQA_K_BEYOND = 26        /* one past the last id: ... VQA_K_PSNR_HVS .. VQA_K_PAST - 1 and VQA_K_CIEDE .. VQA_K_BEYOND - 1 */
+    VQA_K_BEYOND = 26,       /* one past VQA_K_CIEDE, as CIEDE2000 shipped it (kept at 26 for callers and tests that rely on
+                                id 26 being unknown); id 26 stays unnamed                                                */
+    VQA_K_GMSD = 27,         /* vqa_gmsd_submit: the 2x2 sums, Prewitt, the similarity and its integer sums (one entry per
+                                group of same-geometry planes)                                                           */
+    VQA_K_LIMIT = 28         /* one past the last id: ... VQA_K_CIEDE .. VQA_K_BEYOND - 1 and VQA_K_GMSD .. VQA_K_LIMIT - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -48,7 +48,9 @@ K_IDS_KNOWN = K_IDS_ALL + (K_SITI,)               # the ids below K_LAST (kept a
 K_PSNR_HVS, K_PAST = 23, 24                       # added beyond K_LAST, which stays 22; id 22 is unnamed
 K_IDS_EVERY = K_IDS_KNOWN + (K_PSNR_HVS,)         # the ids below K_PAST (kept as PSNR-HVS shipped it)
 K_CIEDE, K_BEYOND = 25, 26                        # added beyond K_PAST, which stays 24; id 24 is unnamed
-K_IDS_NAMED = K_IDS_EVERY + (K_CIEDE,)            # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_NAMED = K_IDS_EVERY + (K_CIEDE,)            # the ids below K_BEYOND (kept as CIEDE2000 shipped it)
+K_GMSD, K_LIMIT = 27, 28                          # added beyond K_BEYOND, which stays 26; id 26 is unnamed
+K_IDS_LISTED = K_IDS_NAMED + (K_GMSD,)            # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -66,6 +68,8 @@ MOTION_MIN_DIM = 16   # vqa_motion_submit: the limit of VIF and ADM, whose plane
 SITI_MIN_DIM = 16   # vqa_siti_submit: the limit of VIF, ADM and motion, whose planes it shares
 PSNR_HVS_MIN_DIM = 16   # vqa_psnr_hvs_submit: the limit of the family, whose planes it shares
 CIEDE_MIN_DIM = 16   # vqa_ciede_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+GMSD_MIN_DIM = 16   # vqa_gmsd_submit: the limit of the family, whose planes it shares
+GMSD_FIX = 1 << 24  # vqa_gmsd_metrics: the words are sums of u = rint(gms 2^24) and of u^2
 CIEDE_YUV709, CIEDE_BGR = 0, 1   # vqa_ciede_submit's colour models
 CIEDE_WEIGHTS_CIE = (1.0, 1.0, 1.0)       # kL, kC, kH of the CIE standard: the default
 CIEDE_WEIGHTS_LIBVMAF = (0.65, 1.0, 4.0)  # what libvmaf's ciede2000 feature is believed to use (unverified: README)
@@ -135,6 +139,11 @@ class VqaCiedeMetrics(C.Structure):
     _fields_ = [("de_sum", C.c_double), ("de_mean", C.c_double), ("ciede2000", C.c_double)]
 
 
+class VqaGmsdMetrics(C.Structure):
+    _fields_ = [("sum_u", C.c_uint64), ("sum_u2_lo", C.c_uint64), ("sum_u2_hi", C.c_uint64), ("count", C.c_int64),
+                ("gms_mean", C.c_double), ("gmsd", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -181,6 +190,8 @@ SIGNATURES = {
     "vqa_ciede_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
                                    C.c_int, C.POINTER(C.c_double)]),
     "vqa_ciede_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaCiedeMetrics), C.c_int]),
+    "vqa_gmsd_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_gmsd_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaGmsdMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -360,4 +360,20 @@ void launch_ciede(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n
 // the word -> the record: the division and the logarithm of include/vqa.h in double, on the host (h x w: the luma grid)
 void ciede_finalize(unsigned long long word, int h, int w, vqa_ciede_metrics *out);
 
+// GMSD (vqa_gmsd_submit): k_gmsd.hip
+constexpr int GMSD_MIN_DIM = 16;
+constexpr int GMSD_WORDS = 3;                      // per (frame, plane): sum u, and sum u^2 as lo, hi (the sum = hi 2^32 + lo)
+constexpr double GMSD_FIX = 16777216.0;            // 2^24: u = rint(gms 2^24)
+constexpr double GMSD_T8 = 170.0;                  // the paper's constant on the 8-bit scale: T = 170 (peak / 255)^2
+// 144 T for a depth, as the kernel and vqa.h use it: 144 (170 ((peak / 255) (peak / 255))), every step rounded to double
+double gmsd_constant(int depth);
+// one group of same-geometry planes of n frame pairs.  Adds the three integer words into
+// acc[(frame * n_planes + plane) * GMSD_WORDS ..], which the caller has zeroed.
+void launch_gmsd(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                 int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth,
+                 unsigned long long *acc);
+// three words -> the record: the 128-bit variance numerator, the division and the square root of include/vqa.h, on the host
+// (h x w: the plane)
+void gmsd_finalize(const unsigned long long *words, int h, int w, vqa_gmsd_metrics *out);
+
 } // namespace vqa

@@ -46,6 +46,9 @@ PSNR_HVS_DTYPE = np.dtype([("s_hvs", np.float64), ("s_hvsm", np.float64), ("psnr
 assert PSNR_HVS_DTYPE.itemsize == C.sizeof(N.VqaPsnrHvsMetrics)
 CIEDE_DTYPE = np.dtype([("de_sum", np.float64), ("de_mean", np.float64), ("ciede2000", np.float64)], align=True)
 assert CIEDE_DTYPE.itemsize == C.sizeof(N.VqaCiedeMetrics)
+GMSD_DTYPE = np.dtype([("sum_u", np.uint64), ("sum_u2_lo", np.uint64), ("sum_u2_hi", np.uint64), ("count", np.int64),
+                       ("gms_mean", np.float64), ("gmsd", np.float64)], align=True)
+assert GMSD_DTYPE.itemsize == C.sizeof(N.VqaGmsdMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -55,6 +58,7 @@ _BATCHES = {
     "_pending_s": ("vqa_siti_submit", "vqa_siti_wait", SITI_DTYPE, N.VqaSitiMetrics),
     "_pending_h": ("vqa_psnr_hvs_submit", "vqa_psnr_hvs_wait", PSNR_HVS_DTYPE, N.VqaPsnrHvsMetrics),
     "_pending_e": ("vqa_ciede_submit", "vqa_ciede_wait", CIEDE_DTYPE, N.VqaCiedeMetrics),   # (one entry per frame)
+    "_pending_g": ("vqa_gmsd_submit", "vqa_gmsd_wait", GMSD_DTYPE, N.VqaGmsdMetrics),
 }
 
 
@@ -261,7 +265,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000 and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -398,7 +402,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -587,6 +591,22 @@ class Engine:
         self.ciede_submit(ref, dist, planes, model, weights, frame_bytes)
         return self.ciede_wait()
 
+    # ---- GMSD --------------------------------------------------------------------
+    def gmsd_submit(self, ref, dist, planes, frame_bytes=None):
+        """GMSD for n frame pairs (vqa_gmsd_submit): the arrays / DeviceFrames and plane tuples of quality_submit, every plane
+        measured by itself and at least 16 x 16.  A batch of its own, like psnr_hvs_submit."""
+        self._batch_submit("_pending_g", self._pair_args(ref, dist, planes, frame_bytes), planes)
+
+    def gmsd_wait(self):
+        """-> [n, n_planes] records (GMSD_DTYPE): the three integer words (sum_u, sum_u2_lo, sum_u2_hi), count, gms_mean and
+        gmsd (exactly 1 and 0 for identical planes)."""
+        return self._batch_wait("_pending_g")
+
+    def gmsd(self, ref, dist, planes, frame_bytes=None):
+        """GMSD per plane for n frame pairs; returns [n, n_planes] structured array (GMSD_DTYPE)."""
+        self.gmsd_submit(ref, dist, planes, frame_bytes)
+        return self.gmsd_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -594,7 +614,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_NAMED:
+        for k in N.K_IDS_LISTED:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)
