@@ -297,6 +297,17 @@ typedef struct vqa_gmsd_metrics {
     double gmsd;        /* sqrt((N sum u^2 - (sum u)^2) / (N (N - 1))) / 2^24; exactly 0 for identical planes           */
 } vqa_gmsd_metrics;
 
+/* CAMBI of one plane (vqa_cambi_submit / vqa_cambi_wait; the definition is stated there).  top, k and masked are integers:
+ * the same plane gives the same words at any place of any batch, from host or device memory.  pool and cambi are formed from
+ * them on the host by vqa_cambi_wait.                                                                                        */
+typedef struct vqa_cambi_metrics {
+    uint64_t top[5];    /* top_s: the exact sum of the K_s largest u_s of scale s                                          */
+    int64_t k[5];       /* K_s = max(1, 3 N_s / 10)                                                                        */
+    int64_t masked[5];  /* the number of samples with m_s = 1                                                              */
+    double pool[5];     /* top_s / (K_s 2^16)                                                                              */
+    double cambi;       /* ((((16 pool_0 + 8 pool_1) + 4 pool_2) + 2 pool_3) + pool_4) / 31; exactly 0 without banding     */
+} vqa_cambi_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -721,6 +732,58 @@ VQA_API int vqa_gmsd_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dis
                             int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_gmsd_wait(vqa_ctx *ctx, vqa_gmsd_metrics *out, int n_entries);
 
+/* ---- CAMBI: contrast-aware multiscale banding index (Tandon, Afonso, Sole, Krasula, PCS 2021) ----
+ * The first metric here that scores ONE stream - the encoded one - without comparing it to another: it measures banding (false
+ * contours), smooth gradients quantised into visible steps.  It is the paper's method applied per plane with the details fixed
+ * as below; where this text and a tool differ in a detail, this text is what is built.  It is NOT pinned against libvmaf's
+ * `cambi` feature, whose differences are left out: the upscale to the encode resolution, the 3 x 3 mode filter before
+ * decimation, luminance-dependent visibility thresholds, a resolution-dependent mask threshold, a top-k share of its own and
+ * its own score scale, and the full-reference variant.  The constants (window 65, mask 7 x 7 with more than 24 hits, contrasts
+ * 1..4, top 30 %, scale weights 16, 8, 4, 2, 1) are the paper's as recalled, unverified.
+ * All arithmetic is integer.  For one plane, h x w samples x of `depth` = b bits:
+ *   1 to 10 bits  b < 10: t = min(1023, x << (10 - b)) (b = 8: x << 2).  b >= 10: t = min(1023, (x + r) >> (b - 10)) with
+ *                 r = 1 << (b - 11) for b > 10 and r = 0 for b = 10.  A sample above 2^b - 1 is read as it is and clamped to
+ *                 1023 by the same min, at every depth.
+ *   2 anti-dither y0(i, j) = (t(i, j) + t(i, j+1) + t(i+1, j) + t(i+1, j+1) + 2) >> 2, row and column indices clamped to the
+ *                 plane.
+ *   3 mask        Z(i, j) = 1 when y0(i, j) == y0(i, j+1) and y0(i, j) == y0(i+1, j), otherwise 0; indices clamped, so the
+ *                 comparison across the last row or column holds trivially.  S(i, j) = the sum of Z over the 7 x 7 window
+ *                 centred on (i, j), with zeros outside the plane.  m0(i, j) = (S(i, j) > 24).  A border sample's window is
+ *                 short (a corner sees 16 samples, its neighbours 20 and 24), so the outer ring is seldom in the mask and the
+ *                 four corners never are: that is intended.
+ *   4 scales      s = 0..4: y_{s+1}(i, j) = y_s(2i, 2j), m_{s+1}(i, j) = m_s(2i, 2j), h_{s+1} = ceil(h_s / 2), likewise w;
+ *                 N_s = h_s w_s.
+ *   5 contrast    for a sample with m_s(i, j) = 1 take the 65 x 65 window centred on it, clipped to the plane.  A = the number
+ *                 of plane samples in the clipped window.  n_d, d = -4..4, = the number of window samples with m_s = 1 and
+ *                 y_s = y_s(i, j) + d; n_0 >= 1, the sample counts itself.  For k = 1..4 and both signs the contrast is
+ *                 c = k n_0 n_{+-k} / ((n_0 + n_{+-k}) A), in [0, 1], kept as u = (num 2^17 + den) / (2 den) in 64-bit integer
+ *                 division with num = k n_0 n_{+-k} and den = (n_0 + n_{+-k}) A: round-to-nearest at a step of 2^-16, no
+ *                 floating point anywhere; 0 <= u <= 65536.  u_s(i, j) = the largest of the eight; 0 where m_s = 0.
+ *   6 pool        K_s = max(1, (3 N_s) / 10) in integer division; top_s = the exact sum of the K_s largest u_s of the scale,
+ *                 unmasked samples counting as zeros; pool_s = top_s / (K_s 2^16).
+ *   7 score       cambi = ((((16 pool_0 + 8 pool_1) + 4 pool_2) + 2 pool_3) + pool_4) / 31, in [0, 1]; 0 for a plane with no
+ *                 masked sample or no neighbour level.  vqa_cambi_wait forms pool and cambi on the host in double, contraction
+ *                 off, from the integer words.
+ * Limits: every plane at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.  A 16 x 16 plane reaches 1 x 1 at
+ * scale 4: that is legal.
+ * The contract of vqa_siti_submit without a prev0: asynchronous, ONE stream, the same plane descriptors (one to four planes,
+ * each measured by itself; packed layouts through pixel_step), depths (one per submit, 8..16), alignment rules, memory kinds and
+ * failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while a CAMBI batch is pending.  A CAMBI batch is a
+ * batch of its own: it may be in flight next to a batch of every other kind of the same ctx (one upload then serves all), and
+ * each wait collects its own kind only - vqa_cambi_wait with only another kind pending, and another kind's wait with only a
+ * CAMBI batch pending, are VQA_ERR_STATE and leave that batch pending.
+ * Kernels, per group of same-geometry planes: k_cambi_mask (steps 1-3; one 16-bit word v0 = m0 ? y0 : 65535 per sample),
+ * k_cambi_decimate (scales 1..4 of v in one launch), then per scale k_cambi_contrast (a 32 x 32 tile and its 32-sample apron
+ * in LDS; every lane walks its window; a wave without a masked sample skips it; u > 0 goes into a 65537-bin integer histogram
+ * per frame and plane) and k_cambi_topk (top_s from the histogram, walked from the top).  Scratch on the device: per frame and
+ * plane about 2.7 bytes per sample for the five scales and 263 KB for the histogram, sized by the largest group; ten 64-bit
+ * words per entry; host frames are staged in the buffer of the second stream of a quality submit.  All of it is kept by the
+ * ctx until vqa_trim / vqa_destroy.
+ * out of vqa_cambi_wait: n * n_planes entries, frame-major.                                                                 */
+VQA_API int vqa_cambi_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                             const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_cambi_wait(vqa_ctx *ctx, vqa_cambi_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -762,7 +825,13 @@ enum vqa_kernel_id {
                                 id 26 being unknown); id 26 stays unnamed                                                */
     VQA_K_GMSD = 27,         /* vqa_gmsd_submit: the 2x2 sums, Prewitt, the similarity and its integer sums (one entry per
                                 group of same-geometry planes)                                                           */
-    VQA_K_LIMIT = 28         /* one past the last id: ... VQA_K_CIEDE .. VQA_K_BEYOND - 1 and VQA_K_GMSD .. VQA_K_LIMIT - 1 */
+    VQA_K_LIMIT = 28,        /* one past VQA_K_GMSD, as GMSD shipped it (kept at 28 for callers and tests that rely on id 28
+                                being unknown); id 28 stays unnamed                                                      */
+    VQA_K_CAMBI_MASK = 29,     /* vqa_cambi_submit: 10 bits, anti-dither, mask (one entry per group of same-geometry planes) */
+    VQA_K_CAMBI_DECIMATE = 30, /* vqa_cambi_submit: scales 1..4 (one entry per group)                                      */
+    VQA_K_CAMBI_CONTRAST = 31, /* vqa_cambi_submit: the 65 x 65 counts and u of one scale (five entries per group)         */
+    VQA_K_CAMBI_TOPK = 32,     /* vqa_cambi_submit: a scale's histogram cleared, and its top-K sum (ten entries per group) */
+    VQA_K_TERMINUS = 33      /* one past the last id: ... VQA_K_GMSD .. VQA_K_LIMIT - 1 and VQA_K_CAMBI_MASK .. VQA_K_TERMINUS - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

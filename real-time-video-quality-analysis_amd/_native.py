@@ -50,7 +50,10 @@ K_IDS_EVERY = K_IDS_KNOWN + (K_PSNR_HVS,)         # the ids below K_PAST (kept a
 K_CIEDE, K_BEYOND = 25, 26                        # added beyond K_PAST, which stays 24; id 24 is unnamed
 K_IDS_NAMED = K_IDS_EVERY + (K_CIEDE,)            # the ids below K_BEYOND (kept as CIEDE2000 shipped it)
 K_GMSD, K_LIMIT = 27, 28                          # added beyond K_BEYOND, which stays 26; id 26 is unnamed
-K_IDS_LISTED = K_IDS_NAMED + (K_GMSD,)            # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_LISTED = K_IDS_NAMED + (K_GMSD,)            # the ids below K_LIMIT (kept as GMSD shipped it)
+K_CAMBI_MASK, K_CAMBI_DECIMATE, K_CAMBI_CONTRAST, K_CAMBI_TOPK, K_TERMINUS = 29, 30, 31, 32, 33   # beyond K_LIMIT; id 28 is unnamed
+K_IDS_CAMBI = (K_CAMBI_MASK, K_CAMBI_DECIMATE, K_CAMBI_CONTRAST, K_CAMBI_TOPK)
+K_IDS_TOLD = K_IDS_LISTED + K_IDS_CAMBI           # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -69,6 +72,10 @@ SITI_MIN_DIM = 16   # vqa_siti_submit: the limit of VIF, ADM and motion, whose p
 PSNR_HVS_MIN_DIM = 16   # vqa_psnr_hvs_submit: the limit of the family, whose planes it shares
 CIEDE_MIN_DIM = 16   # vqa_ciede_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 GMSD_MIN_DIM = 16   # vqa_gmsd_submit: the limit of the family, whose planes it shares
+CAMBI_MIN_DIM = 16   # vqa_cambi_submit: the limit of the family, whose planes it shares
+CAMBI_SCALES = 5
+CAMBI_FIX = 1 << 16  # vqa_cambi_metrics: top is a sum of u, contrasts in steps of 2^-16
+CAMBI_WEIGHTS = (16, 8, 4, 2, 1)   # of pool_0 .. pool_4; cambi = their weighted sum / 31
 GMSD_FIX = 1 << 24  # vqa_gmsd_metrics: the words are sums of u = rint(gms 2^24) and of u^2
 CIEDE_YUV709, CIEDE_BGR = 0, 1   # vqa_ciede_submit's colour models
 CIEDE_WEIGHTS_CIE = (1.0, 1.0, 1.0)       # kL, kC, kH of the CIE standard: the default
@@ -144,6 +151,11 @@ class VqaGmsdMetrics(C.Structure):
                 ("gms_mean", C.c_double), ("gmsd", C.c_double)]
 
 
+class VqaCambiMetrics(C.Structure):
+    _fields_ = [("top", C.c_uint64 * 5), ("k", C.c_int64 * 5), ("masked", C.c_int64 * 5), ("pool", C.c_double * 5),
+                ("cambi", C.c_double)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -192,6 +204,8 @@ SIGNATURES = {
     "vqa_ciede_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaCiedeMetrics), C.c_int]),
     "vqa_gmsd_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_gmsd_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaGmsdMetrics), C.c_int]),
+    "vqa_cambi_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_cambi_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaCambiMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -92,6 +93,10 @@ struct vqa_ctx {
     // vqa_gmsd_submit: the three integer words per entry (device, pinned host); host frames are staged in qstage_*
     dbuf gmsd_acc;
     hbuf gmsd_host;
+    // vqa_cambi_submit: the ten integer words per entry (device, pinned host) and the scales and histograms of the largest
+    // group of a slice; host frames are staged in qstage_dist
+    dbuf cambi_acc, cambi_scratch;
+    hbuf cambi_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -119,6 +124,8 @@ struct vqa_ctx {
     int pend_e_w = 0, pend_e_h = 0;
     int pend_g = 0;           // entries of the pending GMSD batch (likewise); its planes' sizes, for the host's formulas
     int pend_g_planes = 0, pend_g_w[4] = {0}, pend_g_h[4] = {0};
+    int pend_b = 0;           // entries of the pending CAMBI batch (likewise); its planes' sizes, for the host's formulas
+    int pend_b_planes = 0, pend_b_w[4] = {0}, pend_b_h[4] = {0};
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -128,8 +135,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_LIMIT] = {0};
-    int64_t prof_n[VQA_K_LIMIT] = {0};
+    double prof_ms[VQA_K_TERMINUS] = {0};
+    int64_t prof_n[VQA_K_TERMINUS] = {0};
 };
 
 namespace {
@@ -202,7 +209,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -845,14 +852,14 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -1352,7 +1359,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the eight plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD) share: the checks, the staging of host frames, the walk over
+// What the nine plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -2061,6 +2068,74 @@ int vqa_gmsd_wait(vqa_ctx *c, vqa_gmsd_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// CAMBI: one stream, every plane by itself.  A batch of its own (pend_b), ordered by the stream like a GMSD batch; host frames
+// are staged in qstage_dist, the buffer of the stream it measures in a one-pass run.
+static int cambi_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
+                             int n_planes, bool &touched)
+{
+    if (bad_batch_args(c, frames, frames, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (c->pend_b) return VQA_ERR_STATE;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, CAMBI_MIN_DIM); });
+    if (rc) return rc;
+    if (n > 1 && fs < B.span) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if (mem_kind == VQA_MEM_HOST && (rc = stage(c, c->qstage_dist, frames, (size_t)(n - 1) * fs + B.span))) return rc;
+    const size_t nent = (size_t)n * n_planes;
+    const size_t acc_bytes = sizeof(unsigned long long) * CAMBI_WORDS * nent;
+    const size_t per_frame = largest_group_bytes(planes, n_planes, [](int cnt, int h, int w) { return cambi_scratch_bytes(cnt, h, w); });
+    if ((rc = ensure(c, c->cambi_acc, acc_bytes))) return rc;
+    if ((rc = ensure(c, c->cambi_scratch, per_frame * (size_t)(n < QSLICE ? n : QSLICE)))) return rc;
+    if ((rc = ensure_pinned(c, c->cambi_host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->cambi_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    // (launch_cambi's marks: one prof_scope per kernel id at a time, open between its begin and its end)
+    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
+    const cambi_mark mark = [](void *p, int id, int begin) {
+        marks *m = (marks *)p;
+        if (begin) m->open.emplace(m->c, id);
+        else m->open.reset();
+    };
+    for_each_slice(n, [&](int a0, int m) {
+        unsigned long long *acc = (unsigned long long *)c->cambi_acc.p + (size_t)a0 * n_planes * CAMBI_WORDS;
+        const uint8_t *sfr = frames + (int64_t)a0 * fs;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
+            launch_cambi(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, c->cambi_scratch.p, acc, mark, &mk);
+        });
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->cambi_host.p, c->cambi_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_b = (int)nent;
+    c->pend_b_planes = n_planes;
+    for (int p = 0; p < n_planes; p++) { c->pend_b_w[p] = planes[p].width; c->pend_b_h[p] = planes[p].height; }
+    return VQA_OK;
+}
+
+int vqa_cambi_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes, int n_planes)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return cambi_submit_body(c, frames, mem_kind, n, fs, planes, n_planes, touched);
+    });
+}
+
+int vqa_cambi_wait(vqa_ctx *c, vqa_cambi_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_b || n_entries != c->pend_b) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->cambi_host.p;
+    for (int e = 0; e < n_entries; e++) {
+        const int p = e % c->pend_b_planes;
+        cambi_finalize(acc + (size_t)e * CAMBI_WORDS, c->pend_b_h[p], c->pend_b_w[p], out + e);
+    }
+    c->pend_b = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2070,9 +2145,9 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_LIMIT || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_TERMINUS || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
-        (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD))
+        (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2097,6 +2172,10 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_PSNR_HVS) return "k_psnr_hvs";
     if (id == VQA_K_CIEDE) return "k_ciede";
     if (id == VQA_K_GMSD) return "k_gmsd";
+    if (id == VQA_K_CAMBI_MASK) return "k_cambi_mask";
+    if (id == VQA_K_CAMBI_DECIMATE) return "k_cambi_decimate";
+    if (id == VQA_K_CAMBI_CONTRAST) return "k_cambi_contrast";
+    if (id == VQA_K_CAMBI_TOPK) return "k_cambi_topk";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

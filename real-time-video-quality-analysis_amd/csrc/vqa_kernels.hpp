@@ -376,4 +376,26 @@ void launch_gmsd(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n,
 // (h x w: the plane)
 void gmsd_finalize(const unsigned long long *words, int h, int w, vqa_gmsd_metrics *out);
 
+// CAMBI (vqa_cambi_submit): k_cambi.hip
+constexpr int CAMBI_MIN_DIM = 16;
+constexpr int CAMBI_SCALES = 5;
+constexpr int CAMBI_WINDOW = 65;                   // the contrast window, centred: 32 samples each way
+constexpr int CAMBI_TILE = 32;                     // k_cambi_contrast's tile (the tests' seam shape follows it)
+constexpr int CAMBI_MASK_HITS = 24;                // m0 = more than 24 of the 49 Z in the 7 x 7 window
+constexpr int CAMBI_WORDS = 2 * CAMBI_SCALES;      // per (frame, plane): top[5], then masked[5]
+constexpr int CAMBI_HIST_WORDS = 256 * 257;        // the histogram of u = 0 .. 65536 (65537 bins), rounded up for k_cambi_topk
+// device scratch of one group of `count` same-geometry planes of ONE frame: the five scales as 16-bit words and the histogram
+size_t cambi_scratch_bytes(int count, int h, int w);
+// K_s = max(1, 3 N_s / 10) of an h x w plane
+int64_t cambi_top_count(int h, int w, int scale);
+// what launch_cambi calls around the launches of one kernel id, so that the caller can bracket them with that id's events:
+// mark(ctx, id, 1) before them, mark(ctx, id, 0) after them
+typedef void (*cambi_mark)(void *ctx, int kernel_id, int begin);
+// one group of same-geometry planes of n frames: every scale's masked count and top-K sum into
+// acc[(frame * n_planes + plane) * CAMBI_WORDS ..], which the caller has zeroed.  scratch: n * cambi_scratch_bytes(count, h, w)
+void launch_cambi(hipStream_t st, const uint8_t *frames, int n, int64_t frame_stride, const vqa_plane_desc *planes, const int *idx,
+                  int count, int n_planes, int depth, void *scratch, unsigned long long *acc, cambi_mark mark, void *mark_ctx);
+// ten words -> the record: pool and cambi of include/vqa.h in double, on the host (h x w: the plane)
+void cambi_finalize(const unsigned long long *words, int h, int w, vqa_cambi_metrics *out);
+
 } // namespace vqa

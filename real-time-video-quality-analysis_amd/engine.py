@@ -49,6 +49,9 @@ assert CIEDE_DTYPE.itemsize == C.sizeof(N.VqaCiedeMetrics)
 GMSD_DTYPE = np.dtype([("sum_u", np.uint64), ("sum_u2_lo", np.uint64), ("sum_u2_hi", np.uint64), ("count", np.int64),
                        ("gms_mean", np.float64), ("gmsd", np.float64)], align=True)
 assert GMSD_DTYPE.itemsize == C.sizeof(N.VqaGmsdMetrics)
+CAMBI_DTYPE = np.dtype([("top", np.uint64, (5,)), ("k", np.int64, (5,)), ("masked", np.int64, (5,)), ("pool", np.float64, (5,)),
+                        ("cambi", np.float64)], align=True)
+assert CAMBI_DTYPE.itemsize == C.sizeof(N.VqaCambiMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -59,6 +62,7 @@ _BATCHES = {
     "_pending_h": ("vqa_psnr_hvs_submit", "vqa_psnr_hvs_wait", PSNR_HVS_DTYPE, N.VqaPsnrHvsMetrics),
     "_pending_e": ("vqa_ciede_submit", "vqa_ciede_wait", CIEDE_DTYPE, N.VqaCiedeMetrics),   # (one entry per frame)
     "_pending_g": ("vqa_gmsd_submit", "vqa_gmsd_wait", GMSD_DTYPE, N.VqaGmsdMetrics),
+    "_pending_b": ("vqa_cambi_submit", "vqa_cambi_wait", CAMBI_DTYPE, N.VqaCambiMetrics),   # (one stream)
 }
 
 
@@ -265,7 +269,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -416,13 +420,14 @@ class Engine:
         fs = frame_bytes or (ref.nbytes // n)
         return rp, dp, N.VQA_MEM_HOST, n, fs, fs, (ref, dist)
 
-    def _batch_submit(self, slot, streams, planes, *mode):
-        """streams: what _pair_args / _ref_args gave - the C arguments up to the frame strides, then what to keep alive"""
+    def _batch_submit(self, slot, streams, planes, *mode, n=None):
+        """streams: what _pair_args / _ref_args / _one_stream_args gave - the C arguments up to the frame strides, then what to
+        keep alive.  n: the batch's frames; None: the fourth argument, where _pair_args and _ref_args have it"""
         *args, keep = streams
         sub = _BATCHES[slot][0]
         st = getattr(self.lib, sub)(self.ctx, *args, plane_descs(planes), len(planes), *mode)
         N.check(st, sub, self.ctx)
-        setattr(self, slot, (args[3], len(planes), keep))
+        setattr(self, slot, (args[3] if n is None else n, len(planes), keep))
 
     def _batch_wait(self, slot):
         """-> the pending batch's [n, n_planes] records; the slot is free again whatever the status"""
@@ -607,6 +612,33 @@ class Engine:
         self.gmsd_submit(ref, dist, planes, frame_bytes)
         return self.gmsd_wait()
 
+    def _one_stream_args(self, frames, planes, frame_bytes=None):
+        """the frames of a submit that reads one stream and no frame before it -> (ptr, mem kind, n, frame stride, what to keep
+        alive)"""
+        dev = isinstance(frames, DeviceFrames)
+        fp, frames = self._stream_arg(frames, planes, dev)
+        if dev:
+            return fp, N.VQA_MEM_DEVICE, frames.n, frames.frame_stride, frames
+        n = frames.shape[0]
+        return fp, N.VQA_MEM_HOST, n, frame_bytes or (frames.nbytes // n), frames
+
+    # ---- CAMBI ---------------------------------------------------------------------
+    def cambi_submit(self, frames, planes, frame_bytes=None):
+        """CAMBI, the banding index, for n frames of ONE stream (vqa_cambi_submit): an array / DeviceFrames and the plane tuples
+        of quality_submit, every plane measured by itself and at least 16 x 16.  A batch of its own, like gmsd_submit."""
+        streams = self._one_stream_args(frames, planes, frame_bytes)
+        self._batch_submit("_pending_b", streams, planes, n=streams[2])
+
+    def cambi_wait(self):
+        """-> [n, n_planes] records (CAMBI_DTYPE): per scale the integer words top, k and masked, pool = top / (k 2^16), and
+        cambi (exactly 0 for a plane without banding)."""
+        return self._batch_wait("_pending_b")
+
+    def cambi(self, frames, planes, frame_bytes=None):
+        """CAMBI per plane for n frames; returns [n, n_planes] structured array (CAMBI_DTYPE)."""
+        self.cambi_submit(frames, planes, frame_bytes)
+        return self.cambi_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -614,7 +646,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_LISTED:
+        for k in N.K_IDS_TOLD:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -389,7 +389,7 @@ class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
-                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False):
+                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -413,7 +413,11 @@ class Quality:
                 (Engine.ciede_model)
         gmsd    True: every chunk also goes through the GMSD kernel (Engine.gmsd_submit) from the SAME upload; the pass's tuple
                 then gains ONE further last element, after CIEDE2000's: the GMSD records [n,p] (engine.GMSD_DTYPE: the three
-                integer words, count, gms_mean, gmsd); "only": no SSE / SSIM"""
+                integer words, count, gms_mean, gmsd); "only": no SSE / SSIM
+        cambi   True: every chunk of the DISTORTED (encoded) stream also goes through the CAMBI kernels (Engine.cambi_submit)
+                from the SAME upload; the pass's tuple then gains ONE further last element, after GMSD's: the CAMBI records
+                [n,p] (engine.CAMBI_DTYPE); "only": no SSE / SSIM, and the pass reads the `ref` stream alone, as a motion-only
+                pass does: give it the frames to measure"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -450,11 +454,15 @@ class Quality:
             raise ValueError("gmsd must be False, True or 'only'")
         if gmsd == "only" and scales:
             raise ValueError("a GMSD-only pass has no SSIM scales")
-        self.motion, self.siti, self.psnr_hvs, self.gmsd = motion, siti, psnr_hvs, gmsd
+        if not (isinstance(cambi, bool) or (isinstance(cambi, str) and cambi == "only")):
+            raise ValueError("cambi must be False, True or 'only'")
+        if cambi == "only" and scales:
+            raise ValueError("a CAMBI-only pass has no SSIM scales")
+        self.motion, self.siti, self.psnr_hvs, self.gmsd, self.cambi = motion, siti, psnr_hvs, gmsd, cambi
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
-                     ciede != "only" and gmsd != "only")
+                     ciede != "only" and gmsd != "only" and cambi != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -532,7 +540,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     None as well.  Quality(.., ciede=True) appends ONE further last element, after PSNR-HVS's: the CIEDE2000 records [n]
     (engine.CIEDE_DTYPE, one per frame); ciede="only" leaves sse and ssim None as well.  Quality(.., gmsd=True) appends ONE
     further last element, after CIEDE2000's: the GMSD records [n,p] (engine.GMSD_DTYPE); gmsd="only" leaves sse and ssim None as
-    well.
+    well.  Quality(.., cambi=True) appends ONE further last element, after GMSD's: the CAMBI records [n,p] (engine.CAMBI_DTYPE)
+    of the distorted stream; cambi="only" leaves sse and ssim None as well and measures `ref`, the only stream it reads.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -592,6 +601,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.gmsd:
             from .engine import GMSD_DTYPE
             q += (np.zeros((0, len(quality.planes)), GMSD_DTYPE),)
+        if quality.cambi:
+            from .engine import CAMBI_DTYPE
+            q += (np.zeros((0, len(quality.planes)), CAMBI_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -606,8 +618,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
 def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series, n, batch_size, on_quality):
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
-    # motion and SI/TI alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd
+    # motion, SI/TI and CAMBI alone read the reference stream only: the distorted stream is not even uploaded
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and quality.cambi is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -715,7 +727,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -763,6 +775,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.gmsd:
                     eng.gmsd_submit(pair[0], pair[1], quality.planes)
                     p["has_g"] = True
+                if quality.cambi:   # the distorted stream; the only stream of a pass that reads one
+                    eng.cambi_submit(pair[-1], quality.planes)
+                    p["has_b"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -781,7 +796,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms = [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam = [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -803,6 +818,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["eres"] = eng.ciede_wait()
             if p["has_g"]:
                 p["gres"] = eng.gmsd_wait()
+            if p["has_b"]:
+                p["bres"] = eng.cambi_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -835,6 +852,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 cie.append(p.pop("eres"))
             if p["has_g"]:
                 gms.append(p.pop("gres"))
+            if p["has_b"]:
+                cam.append(p.pop("bres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -907,6 +926,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(cie),)
     if want_q and quality.gmsd:
         q += (np.concatenate(gms),)
+    if want_q and quality.cambi:
+        q += (np.concatenate(cam),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

@@ -206,7 +206,24 @@ def frame_gmsd(reference, encoded, layout="bgr24", height=None, width=None, engi
     return r["gmsd"], r["gms_mean"], [(p[0], p[1]) for p in planes]
 
 
-def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None):
+def frame_cambi(frames, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame CAMBI, the banding index, per plane of ONE stream (Engine.cambi through the one-pass pipeline of frame_quality;
+    the stream is uploaded once, there is no second stream).  The definition is include/vqa.h's: 10 bits, a 2x2 anti-dither
+    mean, a 7 x 7 flatness mask, five scales, the 65 x 65 contrast counts for steps of 1..4 levels, the top 30 % per scale
+    and the scale weights 16, 8, 4, 2, 1 - integers up to the last division.
+    Returns (cambi [n,p] float64 - exactly 0 for a plane without banding -, pool [n,p,5] float64, plane sizes).  Every plane
+    at least 16 x 16."""
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, cambi="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    return r["cambi"], r["pool"], [(p[0], p[1]) for p in planes]
+
+
+def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
+                  cambi=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -223,6 +240,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     psnr_hvsm and before vmaf, likewise capped at 100.0.  The model never reads it.
     gmsd: None, or the first plane's GMSD records [n] (engine.GMSD_DTYPE): the log then also carries gmsd, after ciede2000 and
     before vmaf, likewise.  The model never reads it.
+    cambi: None, or the first plane's CAMBI records [n] (engine.CAMBI_DTYPE) of the encoded stream: the log then also carries
+    cambi, after gmsd and before vmaf, likewise.  The model never reads it.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -255,6 +274,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         gmsd = np.asarray(gmsd).reshape(-1)
         names += ["gmsd"]
         cols += [gmsd["gmsd"].astype(np.float64)]
+    if cambi is not None:
+        cambi = np.asarray(cambi).reshape(-1)
+        names += ["cambi"]
+        cols += [cambi["cambi"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -376,7 +399,7 @@ def _open_quality_stream(src, layout, height, width):
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
-                       gmsd=False):
+                       gmsd=False, cambi=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -392,6 +415,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     ciede=True: likewise CIEDE2000 of the three planes together (ciede2000 = 45 - 20 log10 of the frame's mean dE00, capped at
     100.0; three-plane layouts only; ciede_weights = (kL, kC, kH), default (1, 1, 1); a model file does not turn it on).
     gmsd=True: likewise GMSD (gmsd of the first plane; a model file does not turn it on).
+    cambi=True: likewise CAMBI, the banding index of the ENCODED stream alone (cambi of the first plane; a model file does not
+    turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -409,16 +434,17 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     try:
         if ciede and len(LAYOUTS[layout][1]) != 3:
             raise ValueError("ciede needs three planes")
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd:
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
             q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
                                                              adm=bool(adm), motion=bool(motion), siti=bool(siti),
                                                              psnr_hvs=bool(psnr_hvs), ciede=bool(ciede),
-                                                             ciede_weights=ciede_weights, gmsd=bool(gmsd)),
+                                                             ciede_weights=ciede_weights, gmsd=bool(gmsd),
+                                                             cambi=bool(cambi)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -455,11 +481,14 @@ MODE_KEYS = {
 }
 
 
-def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD and the frame's CIEDE2000 of a pass (the tail of
+def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
+                       cambi=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI and the frame's CIEDE2000 of a pass (the tail of
     stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = None
-    if gmsd:       # the tuple's last element, then CIEDE2000's, PSNR-HVS's, SI/TI's; what is left is the tuple of a pass without them
+    rec = hvs = cie = gms = cam = None
+    if cambi:      # the tuple's last element, then GMSD's
+        cam, q = q[-1][:, 0], q[:-1]
+    if gmsd:       # then CIEDE2000's, PSNR-HVS's, SI/TI's; what is left is the tuple of a pass without them
         gms, q = q[-1][:, 0], q[:-1]
     if ciede:
         cie, q = q[-1], q[:-1]
@@ -472,6 +501,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["ciede"] = cie
     if gms is not None:
         more["gmsd"] = gms
+    if cam is not None:
+        more["cambi"] = cam
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -504,6 +535,8 @@ def _check_mode_keys(config):
         raise ValueError("ciede must be true or false.")
     if "gmsd" in config and not isinstance(config["gmsd"], bool):
         raise ValueError("gmsd must be true or false.")
+    if "cambi" in config and not isinstance(config["cambi"], bool):
+        raise ValueError("cambi must be true or false.")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -554,6 +587,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         not turn it on), ciede_weights ([kL, kC, kH], default [1, 1, 1], the CIE standard),
         gmsd (true: the row gains GMSD, the pooled mean of the first plane's per-frame gradient magnitude similarity deviation,
         after CIEDE2000; default false; a model file does not turn it on),
+        cambi (true: the row gains CAMBI, the pooled mean of the first plane's per-frame banding index of the ENCODED stream,
+        after GMSD; default false; a model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -579,6 +614,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     cie = config.get("ciede", False)
     cie_k = tuple(config.get("ciede_weights", N.CIEDE_WEIGHTS_CIE))
     gms = config.get("gmsd", False)
+    cam = config.get("cambi", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -628,13 +664,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         try:
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
-                                                                     gmsd=gms),
+                                                                     gmsd=gms, cambi=cam),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms)
+        if vif or adm or mot or siti or hvs or cie or gms or cam:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -696,6 +732,8 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["CIEDE2000"] = float(pooled["ciede2000"]["mean"])
         if "gmsd" in pooled:
             metrics["GMSD"] = float(pooled["gmsd"]["mean"])
+        if "cambi" in pooled:
+            metrics["CAMBI"] = float(pooled["cambi"]["mean"])
     return metrics
 
 
@@ -718,7 +756,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi;
     #                           and that a vmaf_model_path names a readable file
 
 
