@@ -63,6 +63,7 @@ struct vqa_ctx {
     long seam_fail_at = 0;          // VQA_FAIL_ENSURE_AT=N: the N-th scratch reservation of this ctx reports VQA_ERR_OOM
     long seam_ensure_calls = 0;
     long long seam_fb_chunk_bytes = 0; // VQA_FB_CHUNK_BYTES: Farneback's scratch budget per chunk (0 = the shipped 12 GiB): lets a small batch span chunks
+    int seam_qslice = 0;            // VQA_QSLICE: the frames of one slice of a plane batch (0 = the shipped QSLICE): lets a small batch span slices
 
     // device scratch (grow-only)
     dbuf gray_full, planeA, planeB, state, res_dev, partials, tile_flags, dirty0, dirty1, again_dev;
@@ -808,6 +809,15 @@ int vqa_create(int device, vqa_ctx **out)
     if (const char *e = getenv("VQA_HYST_RESCUE_MAX_ROUNDS")) c->seam_hyst_rescue_max_rounds = atoi(e) > 0 ? atoi(e) : 0;
     if (const char *e = getenv("VQA_FAIL_ENSURE_AT")) c->seam_fail_at = atol(e);
     if (const char *e = getenv("VQA_FB_CHUNK_BYTES")) c->seam_fb_chunk_bytes = atoll(e);
+    if (const char *e = getenv("VQA_QSLICE")) {
+        const long long q = atoll(e);   // 0 (or no number): the shipped slice; otherwise 1 .. 32768 (gridDim.y holds no more)
+        if (q != 0 && (q < 1 || q > 32768)) {
+            (void)hipStreamDestroy(c->stream);
+            delete c;
+            return VQA_ERR_INVALID;
+        }
+        c->seam_qslice = (int)q;
+    }
 #endif
     *out = c;
     return VQA_OK;
@@ -1430,10 +1440,27 @@ static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8
 
 constexpr int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
 
-// body(a0, m): frames a0 .. a0 + m - 1 of the batch
-template <class F> static void for_each_slice(int n, F body)
+// the slice length of a ctx: the constant, but for the lab build's VQA_QSLICE seam (every use of QSLICE below goes through here)
+static inline int qslice(const vqa_ctx *c)
 {
-    for (int a0 = 0; a0 < n; a0 += QSLICE) body(a0, n - a0 < QSLICE ? n - a0 : QSLICE);
+#ifdef VQA_TEST_SEAMS
+    if (c->seam_qslice > 0) return c->seam_qslice;
+#endif
+    (void)c;
+    return QSLICE;
+}
+
+// the frames of the longest slice of a batch of n: what per-slice scratch is sized for
+static inline int slice_frames(const vqa_ctx *c, int n)
+{
+    return n < qslice(c) ? n : qslice(c);
+}
+
+// body(a0, m): frames a0 .. a0 + m - 1 of the batch
+template <class F> static void for_each_slice(const vqa_ctx *c, int n, F body)
+{
+    const int q = qslice(c);
+    for (int a0 = 0; a0 < n; a0 += q) body(a0, n - a0 < q ? n - a0 : q);
 }
 
 // body(idx, cnt): planes of identical geometry (B,G,R of packed BGR; U,V of 4:2:0) go out as one group
@@ -1511,7 +1538,7 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
     const size_t nent = (size_t)n * n_planes;
     if ((rc = ensure(c, c->qres_dev, sizeof(vqa_plane_metrics) * nent))) return rc;
     if ((rc = ensure_pinned(c, c->qres_host, sizeof(vqa_plane_metrics) * nent))) return rc;
-    const int nslice = n < QSLICE ? n : QSLICE, depth = B.depth;
+    const int nslice = slice_frames(c, n), depth = B.depth;
     // (MS: a second half of the same size for the cs totals; level 0 has the most tiles)
     if ((rc = ensure(c, c->qpartials, sizeof(double) * (size_t)maxblocks * nslice * n_planes * (ms ? 2 : 1)))) return rc;
     if (ms) {
@@ -1525,7 +1552,7 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
     }
     HIPCHK(c, hipMemsetAsync(c->qres_dev.p, 0, sizeof(vqa_plane_metrics) * nent, st));
     const int64_t pstride = (int64_t)maxblocks * nslice;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         vqa_plane_metrics *res = (vqa_plane_metrics *)c->qres_dev.p + (size_t)a0 * n_planes;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -1610,14 +1637,14 @@ static int vif_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
     if ((rc = ensure(c, c->vif_acc, acc_bytes))) return rc;
     if ((rc = ensure(c, c->vif_dev, sizeof(vqa_vif_metrics) * nent))) return rc;
     if ((rc = ensure_pinned(c, c->vif_host, sizeof(vqa_vif_metrics) * nent))) return rc;
-    const int nslice = n < QSLICE ? n : QSLICE, depth = B.depth;
+    const int nslice = slice_frames(c, n), depth = B.depth;
     // the level scratch: levels 1..3 of the largest plane group
     const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
         return sizeof(float) * (size_t)vif_levels(nslice, cnt, h, w).total;
     });
     if ((rc = ensure(c, c->vif_pyr, pyr))) return rc;
     HIPCHK(c, hipMemsetAsync(c->vif_acc.p, 0, acc_bytes, st));
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         long long *acc = (long long *)c->vif_acc.p + (size_t)a0 * n_planes * 2 * VIF_LEVELS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -1677,7 +1704,7 @@ static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
     const size_t sums_bytes = sizeof(double) * 6 * ADM_LEVELS * nent;
     if ((rc = ensure(c, c->adm_sums, sums_bytes))) return rc;
     if ((rc = ensure_pinned(c, c->adm_host, sums_bytes))) return rc;
-    const int nslice = n < QSLICE ? n : QSLICE, depth = B.depth;
+    const int nslice = slice_frames(c, n), depth = B.depth;
     // the band scratch and the partials serve one group of same-geometry planes (and one scale) at a time
     const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
         return sizeof(float) * (size_t)adm_levels(nslice, cnt, h, w).total;
@@ -1688,7 +1715,7 @@ static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
     });
     if ((rc = ensure(c, c->adm_pyr, pyr))) return rc;
     if ((rc = ensure(c, c->adm_part, part))) return rc;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         double *sums = (double *)c->adm_sums.p + (size_t)a0 * n_planes * 6 * ADM_LEVELS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -1759,7 +1786,7 @@ static int motion_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *pre
     if ((rc = ensure_pinned(c, c->mot_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->mot_acc.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         long long *acc = (long long *)c->mot_acc.p + (size_t)a0 * n_planes;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
         const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
@@ -1830,7 +1857,7 @@ static int siti_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0
     if ((rc = ensure_pinned(c, c->siti_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->siti_acc.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         unsigned long long *acc = (unsigned long long *)c->siti_acc.p + (size_t)a0 * n_planes * SITI_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
         const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
@@ -1893,7 +1920,7 @@ static int psnr_hvs_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *d
     if ((rc = ensure_pinned(c, c->hvs_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->hvs_acc.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         unsigned long long *acc = (unsigned long long *)c->hvs_acc.p + (size_t)a0 * n_planes * PSNR_HVS_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -1973,7 +2000,7 @@ static int ciede_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist
     if ((rc = ensure_pinned(c, c->ciede_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->ciede_acc.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         prof_scope ps_(c, VQA_K_CIEDE);
         launch_ciede(st, ref + (int64_t)a0 * ref_fs, dist + (int64_t)a0 * dist_fs, m, ref_fs, dist_fs, planes, depth, model, k,
                      (unsigned long long *)c->ciede_acc.p + a0);
@@ -2028,7 +2055,7 @@ static int gmsd_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist,
     if ((rc = ensure_pinned(c, c->gmsd_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->gmsd_acc.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         unsigned long long *acc = (unsigned long long *)c->gmsd_acc.p + (size_t)a0 * n_planes * GMSD_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -2087,7 +2114,7 @@ static int cambi_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, in
     const size_t acc_bytes = sizeof(unsigned long long) * CAMBI_WORDS * nent;
     const size_t per_frame = largest_group_bytes(planes, n_planes, [](int cnt, int h, int w) { return cambi_scratch_bytes(cnt, h, w); });
     if ((rc = ensure(c, c->cambi_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->cambi_scratch, per_frame * (size_t)(n < QSLICE ? n : QSLICE)))) return rc;
+    if ((rc = ensure(c, c->cambi_scratch, per_frame * (size_t)slice_frames(c, n)))) return rc;
     if ((rc = ensure_pinned(c, c->cambi_host, acc_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->cambi_acc.p, 0, acc_bytes, st));
     const int depth = B.depth;
@@ -2098,7 +2125,7 @@ static int cambi_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, in
         if (begin) m->open.emplace(m->c, id);
         else m->open.reset();
     };
-    for_each_slice(n, [&](int a0, int m) {
+    for_each_slice(c, n, [&](int a0, int m) {
         unsigned long long *acc = (unsigned long long *)c->cambi_acc.p + (size_t)a0 * n_planes * CAMBI_WORDS;
         const uint8_t *sfr = frames + (int64_t)a0 * fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
