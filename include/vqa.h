@@ -308,6 +308,18 @@ typedef struct vqa_cambi_metrics {
     double cambi;       /* ((((16 pool_0 + 8 pool_1) + 4 pool_2) + 2 pool_3) + pool_4) / 31; exactly 0 without banding     */
 } vqa_cambi_metrics;
 
+/* XPSNR of one plane pair (vqa_xpsnr_submit / vqa_xpsnr_wait; the definition is stated there).  sse is the device's integer
+ * total; wsse and xpsnr are formed on the host by vqa_xpsnr_wait from the per-block integer words, which the wait also hands
+ * out on request: the same pair (with its predecessor) gives the same words at any place of any batch, from host or device
+ * memory.                                                                                                                   */
+typedef struct vqa_xpsnr_metrics {
+    uint64_t sse;       /* sum (r - d)^2 over the plane: the plain total, the sum of the blocks' sse_k                     */
+    double wsse;        /* avg sum_k sse_k / a_k: the activity-weighted squared error                                      */
+    double xpsnr;       /* 10 log10(w h peak^2 / wsse) in dB; +infinity for identical planes                               */
+    int32_t block;      /* B, the side of a luma block; this plane's blocks are B or B / 2 wide and high                   */
+    int32_t nbx, nby;   /* the block grid, ceil(W / B) x ceil(H / B): the same for every plane of the frame               */
+} vqa_xpsnr_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -784,6 +796,62 @@ VQA_API int vqa_cambi_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, 
                              const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_cambi_wait(vqa_ctx *ctx, vqa_cambi_metrics *out, int n_entries);
 
+/* ---- XPSNR: activity-weighted PSNR with block weights (Helmrich, Siekmann, Becker, Bosse, Marpe, Wiegand, ICASSP 2020;
+ *      JVET-H0047) ----
+ * Plain PSNR in which the squared error of every block is divided by the spatial and temporal activity of the REFERENCE's luma
+ * at that block: error in busy or moving regions counts less, error in flat, static regions more.  It is the paper's method
+ * with the details fixed here; where this text and a tool differ in a detail, this text is what is built.  FFmpeg's `xpsnr`
+ * filter differs in three things that are left out on purpose: its second-order temporal activity above 32 fps (first order
+ * only here), its extra smoothing of the weights for pictures of at most 640 x 480, and its 6 x 6 folded high-pass above HD
+ * (plain 2 x 2 sums here).  It is NOT pinned against FFmpeg's binary.
+ * Inputs   a planar layout whose plane 0 is the full-resolution luma, W x H at `depth` bits; planes 1.. are of the luma's
+ *          size or ceil(W / 2) wide and / or ceil(H / 2) high (4:4:4, 4:2:2, 4:2:0; mono has plane 0 alone).  R, D: the RAW
+ *          INTEGER SAMPLES of the reference and the distorted frame; P: the reference frame before it, or none.
+ *          peak = 2^depth - 1.
+ * Blocks   rho = W H / (3840 * 2160) in double; B = max(4, 4 floor(32 sqrt(rho) + 0.5)): 128 at 2160p, 64 at 1080p, 8 at
+ *          135 x 241, 4 at 16 x 16.  Luma blocks tile the plane from (0, 0), nbx = ceil(W / B), nby = ceil(H / B), edge blocks
+ *          truncated; block k = by nbx + bx.  A plane subsampled by 2 in a direction uses B / 2 there (B is a multiple of 4), so
+ *          every plane has the same nbx x nby grid and block k of every plane is co-located.
+ * Grid G   bv = 1 when W H <= 2048 * 1152, else 2; s = bv^2.  bv = 1: G = R (luma).  bv = 2: G[y][x] = R[2y][2x] + R[2y][2x+1] +
+ *          R[2y+1][2x] + R[2y+1][2x+1] on floor(H / 2) x floor(W / 2) = Gh x Gw: the last row or column of an odd plane is not
+ *          looked at.  Gp: the same grid of P.  Origins are the interior of G only, rows 1 .. Gh - 2 and columns 1 .. Gw - 2:
+ *          no sample outside the plane is ever needed.  Block k owns the origins whose sample coordinate (bv x, bv y) lies in
+ *          it; n_k is their number (0 is possible: a last block that holds only the ignored column).
+ * Words    per (frame, luma block), uint64 sums over the owned origins:
+ *            sa_k = sum |f|, f = 12 G[y][x] - 2 (G[y-1][x] + G[y+1][x] + G[y][x-1] + G[y][x+1])
+ *                                - (G[y-1][x-1] + G[y-1][x+1] + G[y+1][x-1] + G[y+1][x+1])
+ *            ta_k = sum |G[y][x] - Gp[y][x]|, 0 for a frame with no predecessor
+ *          per (frame, plane, block): sse_k = sum (R - D)^2 over every sample of the plane's block.
+ *          Bounds: |f| <= 12 s peak <= 48 peak < 2^22; B <= 728 at the size limit, so a block owns fewer than 2^20 origins and
+ *          2^20 samples: sa_k + 2 ta_k < 2^43 and sse_k < 2^52 - every word stays below 2^53 and converts to double exactly.
+ * Host     in double, contraction off, blocks in ascending k:
+ *            a_min = 2^(depth - 6); a_k = (double)(sa_k + 2 ta_k) / (double)(s n_k), raised to a_min where lower, a_min
+ *            where n_k = 0;  avg = sqrt(16 * 2^(2 depth - 9) / sqrt(max(1e-5, rho)));
+ *            wsse_c = avg * sum_k (double) sse_{c,k} / a_k;  xpsnr_c = 10 log10(((double)(Wc Hc) (peak peak)) / wsse_c), and
+ *            +infinity for wsse_c = 0.
+ * Limits   VQA_ERR_UNSUPPORTED for a packed layout (pixel step beyond one sample: bgr24), a plane 1.. of any other ratio to
+ *          plane 0, a plane below 16 x 16, and W H > 2^28 at 8 bits or > 2^26 above.
+ * The contract of vqa_gmsd_submit for both streams - asynchronous, the same plane descriptors, depths (one per submit),
+ * alignment rules, memory kinds and failure guarantee - and of vqa_siti_submit for prev0: the reference frame before frame 0,
+ * one frame of the reference's layout, resident where the frames are, or NULL: frame 0 then has no predecessor (ta = 0).  A
+ * batch of more than 32768 frames goes out in slices; a slice's first frame takes the previous slice's last frame as its
+ * predecessor.  VQA_ERR_STATE while an XPSNR batch is pending.  An XPSNR batch is a batch of its own: it may be in flight next
+ * to a batch of every other kind of the same ctx, and each wait collects its own kind only - vqa_xpsnr_wait with only another
+ * kind pending, and another kind's wait with only an XPSNR batch pending, are VQA_ERR_STATE and leave that batch pending.
+ * Kernels: k_xpsnr_act (a 64 x 32 tile of G and its one-sample apron in LDS as integers, the quad sums of bv = 2 formed on the
+ * way in, Gp straight from global memory) and, per group of same-geometry planes, k_xpsnr_sse; both find the block of every
+ * origin or sample by itself, add into block accumulators in LDS and send one 64-bit integer atomic per touched block and
+ * word.  Integer adds only: tiling, retirement order, batch size and position cannot change a word.  Scratch on the device:
+ * 8 (2 + n_planes) nbx nby bytes per frame (510 blocks at 1080p and at 2160p), zeroed on the stream before the launches,
+ * and as much pinned host memory; host frames are staged in the buffers of a quality submit, prev0 in one of its own.  All of
+ * it is kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_xpsnr_wait: n * n_planes entries, frame-major.  blocks: NULL, or room for n_block_words =
+ * n nbx nby (3 + n_planes) words - per frame nbx nby triples (sa_k, ta_k, n_k), then per plane nbx nby words sse_k: the weight
+ * map, for callers who want it.  Any other n_block_words with blocks given is VQA_ERR_INVALID and leaves the batch pending. */
+VQA_API int vqa_xpsnr_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, const uint8_t *prev0, int mem_kind, int n,
+                             int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_xpsnr_wait(vqa_ctx *ctx, vqa_xpsnr_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -831,7 +899,11 @@ enum vqa_kernel_id {
     VQA_K_CAMBI_DECIMATE = 30, /* vqa_cambi_submit: scales 1..4 (one entry per group)                                      */
     VQA_K_CAMBI_CONTRAST = 31, /* vqa_cambi_submit: the 65 x 65 counts and u of one scale (five entries per group)         */
     VQA_K_CAMBI_TOPK = 32,     /* vqa_cambi_submit: a scale's histogram cleared, and its top-K sum (ten entries per group) */
-    VQA_K_TERMINUS = 33      /* one past the last id: ... VQA_K_GMSD .. VQA_K_LIMIT - 1 and VQA_K_CAMBI_MASK .. VQA_K_TERMINUS - 1 */
+    VQA_K_TERMINUS = 33,     /* one past VQA_K_CAMBI_TOPK, as CAMBI shipped it (kept at 33 for callers and tests that rely on
+                                id 33 being unknown); id 33 stays unnamed                                                */
+    VQA_K_XPSNR_ACT = 34,    /* vqa_xpsnr_submit: the luma activity words sa, ta per block (one entry per slice)          */
+    VQA_K_XPSNR_SSE = 35,    /* vqa_xpsnr_submit: the squared error per block (one entry per group of same-geometry planes) */
+    VQA_K_BOUND = 36         /* one past the last id: ... VQA_K_CAMBI_MASK .. VQA_K_TERMINUS - 1 and VQA_K_XPSNR_ACT .. VQA_K_BOUND - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

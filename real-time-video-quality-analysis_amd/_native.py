@@ -53,7 +53,9 @@ K_GMSD, K_LIMIT = 27, 28                          # added beyond K_BEYOND, which
 K_IDS_LISTED = K_IDS_NAMED + (K_GMSD,)            # the ids below K_LIMIT (kept as GMSD shipped it)
 K_CAMBI_MASK, K_CAMBI_DECIMATE, K_CAMBI_CONTRAST, K_CAMBI_TOPK, K_TERMINUS = 29, 30, 31, 32, 33   # beyond K_LIMIT; id 28 is unnamed
 K_IDS_CAMBI = (K_CAMBI_MASK, K_CAMBI_DECIMATE, K_CAMBI_CONTRAST, K_CAMBI_TOPK)
-K_IDS_TOLD = K_IDS_LISTED + K_IDS_CAMBI           # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_TOLD = K_IDS_LISTED + K_IDS_CAMBI           # the ids below K_TERMINUS (kept as CAMBI shipped it)
+K_XPSNR_ACT, K_XPSNR_SSE, K_BOUND = 34, 35, 36    # added beyond K_TERMINUS, which stays 33; id 33 is unnamed
+K_IDS_GIVEN = K_IDS_TOLD + (K_XPSNR_ACT, K_XPSNR_SSE)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -73,6 +75,7 @@ PSNR_HVS_MIN_DIM = 16   # vqa_psnr_hvs_submit: the limit of the family, whose pl
 CIEDE_MIN_DIM = 16   # vqa_ciede_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 GMSD_MIN_DIM = 16   # vqa_gmsd_submit: the limit of the family, whose planes it shares
 CAMBI_MIN_DIM = 16   # vqa_cambi_submit: the limit of the family, whose planes it shares
+XPSNR_MIN_DIM = 16   # vqa_xpsnr_submit: the limit of the family, whose planes it shares
 CAMBI_SCALES = 5
 CAMBI_FIX = 1 << 16  # vqa_cambi_metrics: top is a sum of u, contrasts in steps of 2^-16
 CAMBI_WEIGHTS = (16, 8, 4, 2, 1)   # of pool_0 .. pool_4; cambi = their weighted sum / 31
@@ -156,6 +159,11 @@ class VqaCambiMetrics(C.Structure):
                 ("cambi", C.c_double)]
 
 
+class VqaXpsnrMetrics(C.Structure):
+    _fields_ = [("sse", C.c_uint64), ("wsse", C.c_double), ("xpsnr", C.c_double), ("block", C.c_int32), ("nbx", C.c_int32),
+                ("nby", C.c_int32)]
+
+
 # every symbol include/vqa.h declares: (restype, argtypes)
 _u8p = C.c_void_p
 SIGNATURES = {
@@ -206,6 +214,9 @@ SIGNATURES = {
     "vqa_gmsd_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaGmsdMetrics), C.c_int]),
     "vqa_cambi_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_cambi_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaCambiMetrics), C.c_int]),
+    "vqa_xpsnr_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc),
+                                   C.c_int]),
+    "vqa_xpsnr_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaXpsnrMetrics), C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

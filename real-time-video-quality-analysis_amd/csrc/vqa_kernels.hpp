@@ -398,4 +398,31 @@ void launch_cambi(hipStream_t st, const uint8_t *frames, int n, int64_t frame_st
 // ten words -> the record: pool and cambi of include/vqa.h in double, on the host (h x w: the plane)
 void cambi_finalize(const unsigned long long *words, int h, int w, vqa_cambi_metrics *out);
 
+// XPSNR (vqa_xpsnr_submit): k_xpsnr.hip
+constexpr int XPSNR_MIN_DIM = 16;
+// the block grid and the activity grid of a W x H luma plane, as include/vqa.h states them
+struct xpsnr_geom {
+    int block;      // B
+    int nbx, nby;   // ceil(W / B), ceil(H / B)
+    int bv;         // 1, or 2 above 2048 x 1152 samples
+    int gw, gh;     // the activity grid G: floor(W / bv) x floor(H / bv)
+    double rho;     // W H / (3840 * 2160)
+};
+xpsnr_geom xpsnr_geometry(int w, int h);
+// the device words of one frame: nbx nby pairs (sa, ta), then per plane of the submit nbx nby words sse
+inline size_t xpsnr_frame_words(const xpsnr_geom &g, int n_planes) { return (size_t)g.nbx * g.nby * (2 + n_planes); }
+// sa and ta of the luma plane (planes[0]) of n reference frames; frame 0's predecessor is prev0 (nullptr: none).  Adds into
+// words[frame * frame_words + 2 k ..], which the caller has zeroed.
+void launch_xpsnr_act(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n, int64_t ref_frame_stride,
+                      const vqa_plane_desc &luma, const xpsnr_geom &g, int depth, size_t frame_words, unsigned long long *words);
+// sse per block of one group of same-geometry planes of n frame pairs.  Adds into
+// words[frame * frame_words + (2 + plane) nbx nby + k], which the caller has zeroed.
+void launch_xpsnr_sse(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                      int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, const xpsnr_geom &g,
+                      int depth, size_t frame_words, unsigned long long *words);
+// one frame's device words -> its n_planes records, and (blocks != nullptr) its nbx nby (3 + n_planes) words of the weight map:
+// the host part of include/vqa.h in double
+void xpsnr_finalize(const unsigned long long *words, const xpsnr_geom &g, int depth, int n_planes, const int *pw, const int *ph,
+                    vqa_xpsnr_metrics *out, uint64_t *blocks);
+
 } // namespace vqa

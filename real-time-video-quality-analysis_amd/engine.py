@@ -5,6 +5,7 @@ turns the result records into NumPy arrays.  All pixel arithmetic happens in
 the HIP kernels; nothing here computes a metric on the CPU.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -52,6 +53,9 @@ assert GMSD_DTYPE.itemsize == C.sizeof(N.VqaGmsdMetrics)
 CAMBI_DTYPE = np.dtype([("top", np.uint64, (5,)), ("k", np.int64, (5,)), ("masked", np.int64, (5,)), ("pool", np.float64, (5,)),
                         ("cambi", np.float64)], align=True)
 assert CAMBI_DTYPE.itemsize == C.sizeof(N.VqaCambiMetrics)
+XPSNR_DTYPE = np.dtype([("sse", np.uint64), ("wsse", np.float64), ("xpsnr", np.float64), ("block", np.int32), ("nbx", np.int32),
+                        ("nby", np.int32)], align=True)
+assert XPSNR_DTYPE.itemsize == C.sizeof(N.VqaXpsnrMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -63,7 +67,31 @@ _BATCHES = {
     "_pending_e": ("vqa_ciede_submit", "vqa_ciede_wait", CIEDE_DTYPE, N.VqaCiedeMetrics),   # (one entry per frame)
     "_pending_g": ("vqa_gmsd_submit", "vqa_gmsd_wait", GMSD_DTYPE, N.VqaGmsdMetrics),
     "_pending_b": ("vqa_cambi_submit", "vqa_cambi_wait", CAMBI_DTYPE, N.VqaCambiMetrics),   # (one stream)
+    "_pending_x": ("vqa_xpsnr_submit", "vqa_xpsnr_wait", XPSNR_DTYPE, N.VqaXpsnrMetrics),   # (a pair and the frame before it)
 }
+
+
+def check_xpsnr_planes(planes):
+    """vqa_xpsnr_submit's layout rules, as a ValueError before anything is uploaded: a planar layout (pixel step of one sample)
+    whose first plane is the luma, every other plane of its size or its ceil-half in either direction, all at least 16 x 16"""
+    bps = 2 if planes_depth(planes) > 8 else 1
+    w0, h0 = int(planes[0][0]), int(planes[0][1])
+    for p in planes:
+        w, h = int(p[0]), int(p[1])
+        if int(p[4]) != bps:
+            raise ValueError("xpsnr needs a planar layout whose first plane is the luma (packed layouts such as bgr24 have none)")
+        if w not in (w0, (w0 + 1) // 2) or h not in (h0, (h0 + 1) // 2):
+            raise ValueError("xpsnr needs planes of the luma's size or half of it (%dx%d against %dx%d)" % (w, h, w0, h0))
+        if w < N.XPSNR_MIN_DIM or h < N.XPSNR_MIN_DIM:
+            raise ValueError("xpsnr needs planes of at least %d x %d (got %dx%d)" % (N.XPSNR_MIN_DIM, N.XPSNR_MIN_DIM, w, h))
+
+
+def xpsnr_grid(width, height):
+    """XPSNR's block grid of a width x height luma plane as include/vqa.h states it -> (B, nbx, nby):
+    B = max(4, 4 floor(32 sqrt(rho) + 0.5)) with rho = W H / (3840 * 2160), and ceil(W / B) x ceil(H / B) blocks."""
+    rho = (int(width) * int(height)) / (3840.0 * 2160.0)
+    b = max(4, 4 * int(math.floor(32.0 * math.sqrt(rho) + 0.5)))
+    return b, -(-int(width) // b), -(-int(height) // b)
 
 
 class DeviceFrames:
@@ -269,13 +297,13 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
             try:
                 if getattr(self, pend, None):
-                    self.complexity_wait() if pend == "_pending_c" else self._batch_wait(pend)
+                    {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -612,6 +640,54 @@ class Engine:
         self.gmsd_submit(ref, dist, planes, frame_bytes)
         return self.gmsd_wait()
 
+    # ---- XPSNR --------------------------------------------------------------------
+    def xpsnr_submit(self, ref, dist, planes, prev0=None, frame_bytes=None):
+        """XPSNR for n frame pairs (vqa_xpsnr_submit): the arrays / DeviceFrames and plane tuples of quality_submit - a planar
+        layout whose first plane is the luma, the others of its size or its ceil-half, every plane at least 16 x 16 - and prev0
+        as in siti_submit: the REFERENCE frame before frame 0, resident where the frames are (None: frame 0 has no predecessor
+        and its temporal activity is 0).  A batch of its own, like gmsd_submit."""
+        check_xpsnr_planes(planes)
+        rp, dp, kind, n, rfs, dfs, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        dev = kind == N.VQA_MEM_DEVICE
+        if prev0 is not None and isinstance(prev0, DeviceFrames) != dev:
+            raise TypeError("prev0 must live where ref lives (%s)" % ("device" if dev else "host"))
+        pp, p0 = self._stream_arg(prev0, planes, dev, "prev0") if prev0 is not None else (None, None)
+        if p0 is not None and not dev and p0.nbytes != keep[0].nbytes // n:
+            raise ValueError("prev0 must have the frames' layout (%d bytes, got %d)" % (keep[0].nbytes // n, p0.nbytes))
+        self._batch_submit("_pending_x", (rp, dp, pp, kind, n, rfs, dfs, keep + (p0,)), planes, n=n)
+        self._xpsnr_luma = (int(planes[0][0]), int(planes[0][1]))   # of the pending batch: the block grid follows from it
+
+    def xpsnr_wait(self, blocks=False):
+        """-> [n, n_planes] records (XPSNR_DTYPE): sse (the plain total), wsse, xpsnr in dB (inf for identical planes), block,
+        nbx, nby.  blocks=True: -> (records, map) with the integer words behind them, map = dict(sa, ta, n as uint64
+        [n, nby, nbx]; sse as uint64 [n, n_planes, nby, nbx]; act as float64 [n, nby, nbx], the blocks' a_k before the floor
+        a_min: (sa + 2 ta) / (s n), 0 where n = 0)."""
+        n, npl, _keep = self._pending_x
+        w, h = self._xpsnr_luma
+        _b, nbx, nby = xpsnr_grid(w, h)
+        nb = nbx * nby
+        rec = np.zeros(n * npl, dtype=XPSNR_DTYPE)
+        words = np.zeros((n, (3 + npl) * nb), np.uint64) if blocks else None
+        st = self.lib.vqa_xpsnr_wait(self.ctx, rec.ctypes.data_as(C.POINTER(N.VqaXpsnrMetrics)), n * npl,
+                                     words.ctypes.data_as(C.POINTER(C.c_uint64)) if blocks else None, words.size if blocks else 0)
+        self._pending_x = None
+        N.check(st, "vqa_xpsnr_wait", self.ctx)
+        rec = rec.reshape(n, npl)
+        if not blocks:
+            return rec
+        tri = words[:, :3 * nb].reshape(n, nby, nbx, 3)
+        sa, ta, cnt = (np.ascontiguousarray(tri[..., i]) for i in range(3))
+        s = 1.0 if w * h <= 2048 * 1152 else 4.0
+        act = np.divide((sa + 2 * ta).astype(np.float64), s * cnt.astype(np.float64), out=np.zeros(sa.shape, np.float64),
+                        where=cnt > 0)
+        return rec, dict(sa=sa, ta=ta, n=cnt, sse=np.ascontiguousarray(words[:, 3 * nb:]).reshape(n, npl, nby, nbx), act=act)
+
+    def xpsnr(self, ref, dist, planes, prev0=None, blocks=False, frame_bytes=None):
+        """XPSNR per plane for n frame pairs; returns [n, n_planes] structured array (XPSNR_DTYPE), with blocks=True also the
+        weight map (xpsnr_wait)."""
+        self.xpsnr_submit(ref, dist, planes, prev0, frame_bytes)
+        return self.xpsnr_wait(blocks)
+
     def _one_stream_args(self, frames, planes, frame_bytes=None):
         """the frames of a submit that reads one stream and no frame before it -> (ptr, mem kind, n, frame stride, what to keep
         alive)"""
@@ -646,7 +722,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_TOLD:
+        for k in N.K_IDS_GIVEN:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

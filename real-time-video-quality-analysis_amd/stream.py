@@ -389,7 +389,7 @@ class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
-                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False):
+                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -417,7 +417,11 @@ class Quality:
         cambi   True: every chunk of the DISTORTED (encoded) stream also goes through the CAMBI kernels (Engine.cambi_submit)
                 from the SAME upload; the pass's tuple then gains ONE further last element, after GMSD's: the CAMBI records
                 [n,p] (engine.CAMBI_DTYPE); "only": no SSE / SSIM, and the pass reads the `ref` stream alone, as a motion-only
-                pass does: give it the frames to measure"""
+                pass does: give it the frames to measure
+        xpsnr   True: every chunk also goes through the XPSNR kernels (Engine.xpsnr_submit) from the SAME upload, prev0 being
+                the reference feed's halo slot as for motion and siti; the pass's tuple then gains ONE further last element,
+                after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE: sse, wsse, xpsnr, block, nbx, nby); "only": no SSE /
+                SSIM.  Planar layouts whose first plane is the luma"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -458,11 +462,18 @@ class Quality:
             raise ValueError("cambi must be False, True or 'only'")
         if cambi == "only" and scales:
             raise ValueError("a CAMBI-only pass has no SSIM scales")
-        self.motion, self.siti, self.psnr_hvs, self.gmsd, self.cambi = motion, siti, psnr_hvs, gmsd, cambi
+        if not (isinstance(xpsnr, bool) or (isinstance(xpsnr, str) and xpsnr == "only")):
+            raise ValueError("xpsnr must be False, True or 'only'")
+        if xpsnr == "only" and scales:
+            raise ValueError("an XPSNR-only pass has no SSIM scales")
+        if xpsnr:
+            from .engine import check_xpsnr_planes
+            check_xpsnr_planes(planes)
+        self.motion, self.siti, self.psnr_hvs, self.gmsd, self.cambi, self.xpsnr = motion, siti, psnr_hvs, gmsd, cambi, xpsnr
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
-                     ciede != "only" and gmsd != "only" and cambi != "only")
+                     ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -542,6 +553,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     further last element, after CIEDE2000's: the GMSD records [n,p] (engine.GMSD_DTYPE); gmsd="only" leaves sse and ssim None as
     well.  Quality(.., cambi=True) appends ONE further last element, after GMSD's: the CAMBI records [n,p] (engine.CAMBI_DTYPE)
     of the distorted stream; cambi="only" leaves sse and ssim None as well and measures `ref`, the only stream it reads.
+    Quality(.., xpsnr=True) appends ONE further last element, after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE);
+    xpsnr="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -604,6 +617,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.cambi:
             from .engine import CAMBI_DTYPE
             q += (np.zeros((0, len(quality.planes)), CAMBI_DTYPE),)
+        if quality.xpsnr:
+            from .engine import XPSNR_DTYPE
+            q += (np.zeros((0, len(quality.planes)), XPSNR_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -619,7 +635,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion, SI/TI and CAMBI alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and quality.cambi is not True
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and quality.cambi is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -651,7 +667,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     host = any(f.host for f in feeds.values())
     staged = any(f.staged for f in feeds.values())
     cap = chunk_frames(batch_size, interval if (want_q and want_c) else None, per_frame if host else 0, staged)
-    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and (quality.motion or quality.siti)))
+    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and (quality.motion or quality.siti or quality.xpsnr)))
     nchunks = len(plans)
     # ---- lanes
     farneback = want_c and (complexity.mask & N.M_MOTION) and complexity.motion_mode == N.MOTION_FARNEBACK
@@ -727,7 +743,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -751,7 +767,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.adm:
                     eng.adm_submit(pair[0], pair[1], quality.planes)
                     p["has_a"] = True
-                if quality.motion or quality.siti:   # the reference frames alone; prev0 = the frame before the chunk: the halo
+                if quality.motion or quality.siti or quality.xpsnr:   # prev0 = the reference frame before the chunk: the halo
                     prev0 = None                     # slot of the chunk's own buffer (host streams) or the resident clip's frame
                     if p["q0"] > 0:                  # in place
                         if fr.host:
@@ -778,6 +794,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.cambi:   # the distorted stream; the only stream of a pass that reads one
                     eng.cambi_submit(pair[-1], quality.planes)
                     p["has_b"] = True
+                if quality.xpsnr:   # the pair, and the halo for the activity of the chunk's first frame
+                    eng.xpsnr_submit(pair[0], pair[1], quality.planes, prev0)
+                    p["has_x"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -796,7 +815,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam = [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps = [], [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -820,6 +839,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["gres"] = eng.gmsd_wait()
             if p["has_b"]:
                 p["bres"] = eng.cambi_wait()
+            if p["has_x"]:
+                p["xres"] = eng.xpsnr_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -854,6 +875,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 gms.append(p.pop("gres"))
             if p["has_b"]:
                 cam.append(p.pop("bres"))
+            if p["has_x"]:
+                xps.append(p.pop("xres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -928,6 +951,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(gms),)
     if want_q and quality.cambi:
         q += (np.concatenate(cam),)
+    if want_q and quality.xpsnr:
+        q += (np.concatenate(xps),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series
