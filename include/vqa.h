@@ -320,6 +320,17 @@ typedef struct vqa_xpsnr_metrics {
     int32_t nbx, nby;   /* the block grid, ceil(W / B) x ceil(H / B): the same for every plane of the frame               */
 } vqa_xpsnr_metrics;
 
+/* HaarPSI of one plane pair (vqa_haarpsi_submit / vqa_haarpsi_wait; the definition and the bounds of the sums are stated
+ * there).  The three words are the device's integer totals, so the same pair gives the same words at any place of any batch,
+ * from host or device memory; similarity and haarpsi are formed from them on the host by vqa_haarpsi_wait.                  */
+typedef struct vqa_haarpsi_metrics {
+    uint64_t den;       /* sum of the weights wI_o over both orientations and every sample of the downsampled grid        */
+    uint64_t num_lo;    /* sum of u_o wI_o = num_hi 2^32 + num_lo: the threads' totals, split into their low 32 bits      */
+    uint64_t num_hi;    /*   and the rest before they are added                                                           */
+    double similarity;  /* num / (den 2^30): the weighted mean of the sigmoid; U1 / 2^30 for identical planes             */
+    double haarpsi;     /* (logit(similarity) / alpha')^2; exactly 1 for identical planes                                  */
+} vqa_haarpsi_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -852,6 +863,65 @@ VQA_API int vqa_xpsnr_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *di
                              int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_xpsnr_wait(vqa_ctx *ctx, vqa_xpsnr_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words);
 
+/* ---- HaarPSI: Haar wavelet-based perceptual similarity index (Reisenhofer, Bosse, Kutyniok, Wiegand, Signal Processing:
+ *      Image Communication 61, 2018) ----
+ * The authors' HaarPSI.m for grayscale input applied per plane, AS RECALLED: their code was not at hand when this was written
+ * and nothing here is pinned against their MATLAB or Python files.  Where this text and a tool differ in a detail, this text
+ * is what is built.  For one plane pair (ref r, dist d, `depth` bits, h x w) on the RAW INTEGER SAMPLES, peak = 2^depth - 1,
+ * k = peak / 255:
+ *   2x2 mean  vqa_gmsd_submit's stage exactly: S(i, j) = the integer sum of the input quad at (2i, 2j), a sample outside the
+ *             plane counting 0, for i < hd = ceil(h / 2), j < wd = ceil(w / 2); D = S / 4 (MATLAB's conv2(.., ones(2) / 4,
+ *             'same') and (1:2:end, 1:2:end): the last row or column of an odd plane is a half-weight mean).
+ *   Haar      at EVERY sample of D, with D = 0 outside (conv2 'same': a zero fill, not a clamp).  For scale s = 1, 2, 3 and
+ *             K = 2^s the horizontal-edge coefficient is
+ *               H_s^0(i, j) = sum_{b = -K/2+1 .. K/2} (sum_{a = -K/2+1 .. 0} S(i+a, j+b) - sum_{a = 1 .. K/2} S(i+a, j+b))
+ *             and H_s^1 is its transpose (a and b exchange their roles).  The window i - K/2 + 1 .. i + K/2 is MATLAB's
+ *             centring of an even kernel.  The paper's coefficient is H / 2^(s+2); only |H| is used, so the sign is free.
+ *             |H_1| <= 8 peak, |H_2| <= 32 peak, |H_3| <= 128 peak < 2^23 at 16 bits: 32-bit integers throughout.
+ *   local     for orientation o and s = 1, 2:  sim_s = (2 |H_r H_d| + c_s) / ((H_r^2 + H_d^2) + c_s) with
+ *             c_s = 4^(s+2) (30 (k k)) - the paper's C = 30 on the 8-bit scale, so a clip scores the same at any depth after
+ *             exact upscaling.  In double, every step rounded once, contraction off; the integer products (below 2^45) and
+ *             H_r^2 + H_d^2 are exact, so |H_r| = |H_d| gives sim_s = 1 EXACTLY.  ls_o = (sim_1 + sim_2) / 2.
+ *   weight    wI_o = max(|H_3^o| of ref, |H_3^o| of dist), an integer (the paper's weight is wI / 32; the scale cancels).
+ *   sums      BATCH-INVARIANT BITS: alpha = 4.2, FIX = 2^30, u_o = rint(FIX / (1 + exp(-alpha ls_o))), and u_o = U1 where
+ *             ls_o = 1.0 exactly; U1 = rint(FIX / (1 + exp(-alpha))) is formed once on the host and handed to the kernel, so
+ *             identical planes do not depend on the device's exp.  Three integer words leave the device per entry:
+ *             den = sum_o sum_ij wI_o, and num = sum u_o wI_o as two words.  u <= 2^30 and wI < 2^23: a term is below 2^53.
+ *             A thread's 16 terms total less than 2^57 and are split into their low and their high 32 bits THERE, before
+ *             anything else is added.  hd wd <= 2^26 + 2^22 + 5 for h w <= 2^28, so there are fewer than 2^27.1 terms: den is
+ *             below 2^51 (below 2^50 when h and w are even), num_lo below 2^60 and num_hi below 2^53 however the terms are
+ *             grouped - nothing can overflow, for any tiling.  Integer adds only.
+ *   host      in double, contraction off.  num = num_hi 2^32 + num_lo in 128-bit integers;
+ *             similarity = (floor(num / den) + (num mod den) / den) / FIX - the quotient is below 2^30 and the remainder
+ *             below 2^51, both exact in double, so this is num / (den FIX) with one rounding in the fraction and one in the
+ *             sum; alpha' = logit(U1 / FIX), alpha's fixed-point image (within 8e-9 relative of 4.2);
+ *             haarpsi = (logit(similarity) / alpha')^2, logit(x) = log(x / (1 - x)).  den = 0 happens only when both planes
+ *             are all zero: similarity = U1 / FIX and haarpsi = 1.0.  Identical planes give num = U1 den, similarity =
+ *             U1 / FIX and haarpsi = 1.0 exactly.
+ *   error     against the same formula in plain float64 with the true alpha and no rounding of u: the rounding of u moves
+ *             similarity by at most 2^-31 (a weighted mean of changes of at most 2^-31); similarity = x lies in [1/2, X],
+ *             X = 1 / (1 + exp(-4.2)) = 0.98523, where |d haarpsi / d x| = 2 logit(x) / (alpha^2 x (1 - x)) <=
+ *             2 / (alpha X (1 - X)) = 32.7: at most 1.53e-8.  alpha' for alpha scales haarpsi by (alpha / alpha')^2, within
+ *             1.6e-8 of 1, and haarpsi <= 1.  Together below 3.2e-8; the tests hold the device to 4e-8.
+ * Deliberate differences: the paper's colour variant (YIQ chroma similarity at one mean-filtered scale) is left out - each
+ * plane is measured by itself, like every other metric here; and the authors' Python port uses SciPy's 'same', which centres
+ * an even kernel one sample away from MATLAB's centring - MATLAB's is built.
+ * Limits: every plane at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.
+ * The contract of vqa_gmsd_submit: asynchronous, the same plane descriptors (one to four planes, each measured by itself;
+ * packed layouts through pixel_step), depths (one per submit), alignment rules, memory kinds, slices of 32768 frames and
+ * failure guarantee.  VQA_ERR_STATE while a HaarPSI batch is pending.  A HaarPSI batch is a batch of its own: it may be in
+ * flight next to a batch of every other kind of the same ctx, and each wait collects its own kind only - vqa_haarpsi_wait
+ * with only another kind pending, and another kind's wait with only a HaarPSI batch pending, are VQA_ERR_STATE and leave that
+ * batch pending.
+ * One fused kernel per group of same-geometry planes, k_haarpsi: a workgroup forms a 64 x 32 tile of S and its apron (3
+ * samples before, 4 after) for both images in LDS straight from the input quads; only the three words leave the kernel.
+ * Scratch on the device: 24 bytes per entry; host frames are staged in the buffers a quality submit uses.  All of it is kept
+ * by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_haarpsi_wait: n * n_planes entries, frame-major.                                                              */
+VQA_API int vqa_haarpsi_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                               int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_haarpsi_wait(vqa_ctx *ctx, vqa_haarpsi_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -903,7 +973,11 @@ enum vqa_kernel_id {
                                 id 33 being unknown); id 33 stays unnamed                                                */
     VQA_K_XPSNR_ACT = 34,    /* vqa_xpsnr_submit: the luma activity words sa, ta per block (one entry per slice)          */
     VQA_K_XPSNR_SSE = 35,    /* vqa_xpsnr_submit: the squared error per block (one entry per group of same-geometry planes) */
-    VQA_K_BOUND = 36         /* one past the last id: ... VQA_K_CAMBI_MASK .. VQA_K_TERMINUS - 1 and VQA_K_XPSNR_ACT .. VQA_K_BOUND - 1 */
+    VQA_K_BOUND = 36,        /* one past VQA_K_XPSNR_SSE, as XPSNR shipped it (kept at 36 for callers and tests that rely on id 36
+                                being unknown); id 36 stays unnamed                                                      */
+    VQA_K_HAARPSI = 37,      /* vqa_haarpsi_submit: the 2x2 sums, the Haar coefficients, the similarities and the integer sums
+                                (one entry per group of same-geometry planes)                                            */
+    VQA_K_FINIS = 38         /* one past the last id: ... VQA_K_XPSNR_ACT .. VQA_K_BOUND - 1 and VQA_K_HAARPSI .. VQA_K_FINIS - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

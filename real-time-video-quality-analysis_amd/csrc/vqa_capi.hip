@@ -102,6 +102,9 @@ struct vqa_ctx {
     // prev0 in a buffer of its own
     dbuf xpsnr_acc, xpsnr_prev;
     hbuf xpsnr_host;
+    // vqa_haarpsi_submit: the three integer words per entry (device, pinned host); host frames are staged in qstage_*
+    dbuf haarpsi_acc;
+    hbuf haarpsi_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -133,6 +136,7 @@ struct vqa_ctx {
     int pend_b_planes = 0, pend_b_w[4] = {0}, pend_b_h[4] = {0};
     int pend_x = 0;           // entries of the pending XPSNR batch (likewise); its planes' sizes and depth, for the host's part
     int pend_x_planes = 0, pend_x_depth = 8, pend_x_w[4] = {0}, pend_x_h[4] = {0};
+    int pend_w = 0;           // entries of the pending HaarPSI batch (likewise)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -142,8 +146,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_BOUND] = {0};
-    int64_t prof_n[VQA_K_BOUND] = {0};
+    double prof_ms[VQA_K_FINIS] = {0};
+    int64_t prof_n[VQA_K_FINIS] = {0};
 };
 
 namespace {
@@ -216,7 +220,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -868,14 +872,14 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -1375,7 +1379,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the ten plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR) share: the checks, the staging of host frames, the walk over
+// What the eleven plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -1434,7 +1438,7 @@ static int stage(vqa_ctx *c, dbuf &buf, const uint8_t *&frames, size_t bytes)
     return VQA_OK;
 }
 
-// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD or an XPSNR submit.  The seven share qstage_*: the stream orders a batch behind
+// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR or a HaarPSI submit.  The eight share qstage_*: the stream orders a batch behind
 // whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
 static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs, const uint8_t *&dist,
                       int64_t dist_fs)
@@ -2250,6 +2254,62 @@ int vqa_xpsnr_wait(vqa_ctx *c, vqa_xpsnr_metrics *out, int n_entries, uint64_t *
 }
 
 // ---------------------------------------------------------------------------
+// HaarPSI: both streams, every plane by itself.  A batch of its own (pend_w), ordered by the stream like a GMSD batch, whose
+// host staging (qstage_*) it shares.
+static int haarpsi_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                               int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (c->pend_w) return VQA_ERR_STATE;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, HAARPSI_MIN_DIM); });
+    if (rc) return rc;
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    const size_t nent = (size_t)n * n_planes;
+    const size_t acc_bytes = sizeof(unsigned long long) * HAARPSI_WORDS * nent;
+    if ((rc = ensure(c, c->haarpsi_acc, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, c->haarpsi_host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->haarpsi_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    for_each_slice(c, n, [&](int a0, int m) {
+        unsigned long long *acc = (unsigned long long *)c->haarpsi_acc.p + (size_t)a0 * n_planes * HAARPSI_WORDS;
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
+            prof_scope ps_(c, VQA_K_HAARPSI);
+            launch_haarpsi(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes, depth, acc);
+        });
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->haarpsi_host.p, c->haarpsi_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_w = (int)nent;
+    return VQA_OK;
+}
+
+int vqa_haarpsi_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                       int64_t dist_fs, const vqa_plane_desc *planes, int n_planes)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return haarpsi_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, touched);
+    });
+}
+
+int vqa_haarpsi_wait(vqa_ctx *c, vqa_haarpsi_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_w || n_entries != c->pend_w) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->haarpsi_host.p;
+    for (int e = 0; e < n_entries; e++) haarpsi_finalize(acc + (size_t)e * HAARPSI_WORDS, out + e);
+    c->pend_w = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2259,10 +2319,10 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_BOUND || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_FINIS || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
-        (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT))
+        (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2293,6 +2353,7 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_CAMBI_TOPK) return "k_cambi_topk";
     if (id == VQA_K_XPSNR_ACT) return "k_xpsnr_act";
     if (id == VQA_K_XPSNR_SSE) return "k_xpsnr_sse";
+    if (id == VQA_K_HAARPSI) return "k_haarpsi";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

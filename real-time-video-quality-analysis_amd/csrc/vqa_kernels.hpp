@@ -425,4 +425,22 @@ void launch_xpsnr_sse(hipStream_t st, const uint8_t *ref, const uint8_t *dist, i
 void xpsnr_finalize(const unsigned long long *words, const xpsnr_geom &g, int depth, int n_planes, const int *pw, const int *ph,
                     vqa_xpsnr_metrics *out, uint64_t *blocks);
 
+// HaarPSI (vqa_haarpsi_submit): k_haarpsi.hip
+constexpr int HAARPSI_MIN_DIM = 16;
+constexpr int HAARPSI_WORDS = 3;                   // per (frame, plane): den, and num as lo, hi (num = hi 2^32 + lo)
+constexpr double HAARPSI_FIX = 1073741824.0;       // 2^30: u = rint(2^30 / (1 + exp(-alpha ls)))
+constexpr double HAARPSI_ALPHA = 4.2;              // the paper's alpha
+constexpr double HAARPSI_C8 = 30.0;                // the paper's C on the 8-bit scale
+// 30 (k k), k = peak / 255, every step rounded to double once: c_s = 4^(s+2) times it, which is exact
+double haarpsi_constant(int depth);
+// U1 = rint(2^30 / (1 + exp(-alpha))): u where the local similarity is exactly 1, formed on the host
+unsigned long long haarpsi_u1();
+// one group of same-geometry planes of n frame pairs.  Adds the three integer words into
+// acc[(frame * n_planes + plane) * HAARPSI_WORDS ..], which the caller has zeroed.
+void launch_haarpsi(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                    int64_t dist_frame_stride, const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth,
+                    unsigned long long *acc);
+// three words -> the record: the 128-bit quotient and the two logits of include/vqa.h, on the host
+void haarpsi_finalize(const unsigned long long *words, vqa_haarpsi_metrics *out);
+
 } // namespace vqa

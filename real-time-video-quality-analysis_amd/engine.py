@@ -56,6 +56,9 @@ assert CAMBI_DTYPE.itemsize == C.sizeof(N.VqaCambiMetrics)
 XPSNR_DTYPE = np.dtype([("sse", np.uint64), ("wsse", np.float64), ("xpsnr", np.float64), ("block", np.int32), ("nbx", np.int32),
                         ("nby", np.int32)], align=True)
 assert XPSNR_DTYPE.itemsize == C.sizeof(N.VqaXpsnrMetrics)
+HAARPSI_DTYPE = np.dtype([("den", np.uint64), ("num_lo", np.uint64), ("num_hi", np.uint64), ("similarity", np.float64),
+                          ("haarpsi", np.float64)], align=True)
+assert HAARPSI_DTYPE.itemsize == C.sizeof(N.VqaHaarpsiMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -68,6 +71,7 @@ _BATCHES = {
     "_pending_g": ("vqa_gmsd_submit", "vqa_gmsd_wait", GMSD_DTYPE, N.VqaGmsdMetrics),
     "_pending_b": ("vqa_cambi_submit", "vqa_cambi_wait", CAMBI_DTYPE, N.VqaCambiMetrics),   # (one stream)
     "_pending_x": ("vqa_xpsnr_submit", "vqa_xpsnr_wait", XPSNR_DTYPE, N.VqaXpsnrMetrics),   # (a pair and the frame before it)
+    "_pending_w": ("vqa_haarpsi_submit", "vqa_haarpsi_wait", HAARPSI_DTYPE, N.VqaHaarpsiMetrics),
 }
 
 
@@ -297,7 +301,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -434,7 +438,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -640,6 +644,22 @@ class Engine:
         self.gmsd_submit(ref, dist, planes, frame_bytes)
         return self.gmsd_wait()
 
+    # ---- HaarPSI -----------------------------------------------------------------
+    def haarpsi_submit(self, ref, dist, planes, frame_bytes=None):
+        """HaarPSI for n frame pairs (vqa_haarpsi_submit): the arrays / DeviceFrames and plane tuples of quality_submit, every
+        plane measured by itself and at least 16 x 16.  A batch of its own, like gmsd_submit."""
+        self._batch_submit("_pending_w", self._pair_args(ref, dist, planes, frame_bytes), planes)
+
+    def haarpsi_wait(self):
+        """-> [n, n_planes] records (HAARPSI_DTYPE): the three integer words (den, num_lo, num_hi), similarity and haarpsi
+        (exactly 1 for identical planes)."""
+        return self._batch_wait("_pending_w")
+
+    def haarpsi(self, ref, dist, planes, frame_bytes=None):
+        """HaarPSI per plane for n frame pairs; returns [n, n_planes] structured array (HAARPSI_DTYPE)."""
+        self.haarpsi_submit(ref, dist, planes, frame_bytes)
+        return self.haarpsi_wait()
+
     # ---- XPSNR --------------------------------------------------------------------
     def xpsnr_submit(self, ref, dist, planes, prev0=None, frame_bytes=None):
         """XPSNR for n frame pairs (vqa_xpsnr_submit): the arrays / DeviceFrames and plane tuples of quality_submit - a planar
@@ -722,7 +742,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_GIVEN:
+        for k in N.K_IDS_SHOWN:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

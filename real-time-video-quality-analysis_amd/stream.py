@@ -389,7 +389,8 @@ class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
-                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False):
+                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
+                 haarpsi=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -421,7 +422,10 @@ class Quality:
         xpsnr   True: every chunk also goes through the XPSNR kernels (Engine.xpsnr_submit) from the SAME upload, prev0 being
                 the reference feed's halo slot as for motion and siti; the pass's tuple then gains ONE further last element,
                 after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE: sse, wsse, xpsnr, block, nbx, nby); "only": no SSE /
-                SSIM.  Planar layouts whose first plane is the luma"""
+                SSIM.  Planar layouts whose first plane is the luma
+        haarpsi True: every chunk also goes through the HaarPSI kernel (Engine.haarpsi_submit) from the SAME upload; the pass's
+                tuple then gains ONE further last element, after XPSNR's: the HaarPSI records [n,p] (engine.HAARPSI_DTYPE: the
+                three integer words, similarity, haarpsi); "only": no SSE / SSIM"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -469,11 +473,16 @@ class Quality:
         if xpsnr:
             from .engine import check_xpsnr_planes
             check_xpsnr_planes(planes)
+        if not (isinstance(haarpsi, bool) or (isinstance(haarpsi, str) and haarpsi == "only")):
+            raise ValueError("haarpsi must be False, True or 'only'")
+        if haarpsi == "only" and scales:
+            raise ValueError("a HaarPSI-only pass has no SSIM scales")
         self.motion, self.siti, self.psnr_hvs, self.gmsd, self.cambi, self.xpsnr = motion, siti, psnr_hvs, gmsd, cambi, xpsnr
+        self.haarpsi = haarpsi
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
-                     ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only")
+                     ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -554,7 +563,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     well.  Quality(.., cambi=True) appends ONE further last element, after GMSD's: the CAMBI records [n,p] (engine.CAMBI_DTYPE)
     of the distorted stream; cambi="only" leaves sse and ssim None as well and measures `ref`, the only stream it reads.
     Quality(.., xpsnr=True) appends ONE further last element, after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE);
-    xpsnr="only" leaves sse and ssim None as well.
+    xpsnr="only" leaves sse and ssim None as well.  Quality(.., haarpsi=True) appends ONE further last element, after XPSNR's:
+    the HaarPSI records [n,p] (engine.HAARPSI_DTYPE); haarpsi="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -620,6 +630,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.xpsnr:
             from .engine import XPSNR_DTYPE
             q += (np.zeros((0, len(quality.planes)), XPSNR_DTYPE),)
+        if quality.haarpsi:
+            from .engine import HAARPSI_DTYPE
+            q += (np.zeros((0, len(quality.planes)), HAARPSI_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -635,7 +648,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion, SI/TI and CAMBI alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and quality.cambi is not True
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and quality.cambi is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -743,7 +756,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -797,6 +810,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.xpsnr:   # the pair, and the halo for the activity of the chunk's first frame
                     eng.xpsnr_submit(pair[0], pair[1], quality.planes, prev0)
                     p["has_x"] = True
+                if quality.haarpsi:
+                    eng.haarpsi_submit(pair[0], pair[1], quality.planes)
+                    p["has_w"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -815,7 +831,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps = [], [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps = [], [], [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -841,6 +857,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["bres"] = eng.cambi_wait()
             if p["has_x"]:
                 p["xres"] = eng.xpsnr_wait()
+            if p["has_w"]:
+                p["wres"] = eng.haarpsi_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -877,6 +895,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 cam.append(p.pop("bres"))
             if p["has_x"]:
                 xps.append(p.pop("xres"))
+            if p["has_w"]:
+                hps.append(p.pop("wres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -953,6 +973,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(cam),)
     if want_q and quality.xpsnr:
         q += (np.concatenate(xps),)
+    if want_q and quality.haarpsi:
+        q += (np.concatenate(hps),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

@@ -241,8 +241,26 @@ def frame_xpsnr(reference, encoded, layout="yuv420p", height=None, width=None, e
     return r["xpsnr"], r["wsse"], [(p[0], p[1]) for p in planes], xpsnr_grid(planes[0][0], planes[0][1])[0]
 
 
+def frame_haarpsi(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame HaarPSI per plane (Engine.haarpsi through the one-pass pipeline of frame_quality; both streams are uploaded
+    once).  The definition is include/vqa.h's: a 2x2 mean at step 2, Haar coefficients of three scales and two orientations with
+    a zero border, the local similarity of the two finer scales weighted by the coarsest, a sigmoid with alpha = 4.2 and its
+    inverse - the grayscale index per plane, as recalled from the authors' HaarPSI.m and not pinned against it.
+    Returns (haarpsi [n,p] float64 - exactly 1 for identical planes -, similarity [n,p] float64 - the weighted mean of the
+    sigmoid -, plane sizes).  Every plane at least 16 x 16."""
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, haarpsi="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    return r["haarpsi"], r["similarity"], [(p[0], p[1]) for p in planes]
+
+
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
-                  cambi=None, xpsnr=None):
+                  cambi=None, xpsnr=None, haarpsi=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -263,6 +281,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     cambi, after gmsd and before vmaf, likewise.  The model never reads it.
     xpsnr: None, or the first plane's XPSNR records [n] (engine.XPSNR_DTYPE): the log then also carries xpsnr in dB, after cambi
     and before vmaf, likewise capped at 100.0.  The model never reads it.
+    haarpsi: None, or the first plane's HaarPSI records [n] (engine.HAARPSI_DTYPE): the log then also carries haarpsi, after
+    xpsnr and before vmaf, likewise.  The model never reads it.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -303,6 +323,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         xpsnr = np.asarray(xpsnr).reshape(-1)
         names += ["xpsnr"]
         cols += [np.minimum(xpsnr["xpsnr"].astype(np.float64), PSNR_HVS_DB_CAP)]
+    if haarpsi is not None:
+        haarpsi = np.asarray(haarpsi).reshape(-1)
+        names += ["haarpsi"]
+        cols += [haarpsi["haarpsi"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -424,7 +448,7 @@ def _open_quality_stream(src, layout, height, width):
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
-                       gmsd=False, cambi=False, xpsnr=False):
+                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -444,6 +468,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     turn it on).
     xpsnr=True: likewise XPSNR, the activity-weighted PSNR with block weights (xpsnr of the first plane in dB, capped at 100.0;
     planar layouts only - bgr24 is a ValueError; a model file does not turn it on).
+    haarpsi=True: likewise HaarPSI, the Haar wavelet perceptual similarity (haarpsi of the first plane; a model file does not
+    turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -464,7 +490,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if xpsnr:
             from .engine import check_xpsnr_planes
             check_xpsnr_planes(LAYOUTS[layout][0](h, w))
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr:
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -472,9 +498,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              adm=bool(adm), motion=bool(motion), siti=bool(siti),
                                                              psnr_hvs=bool(psnr_hvs), ciede=bool(ciede),
                                                              ciede_weights=ciede_weights, gmsd=bool(gmsd),
-                                                             cambi=bool(cambi), xpsnr=bool(xpsnr)),
+                                                             cambi=bool(cambi), xpsnr=bool(xpsnr),
+                                                             haarpsi=bool(haarpsi)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -512,11 +539,13 @@ MODE_KEYS = {
 
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
-                       cambi=False, xpsnr=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR and the frame's CIEDE2000 of a pass (the
+                       cambi=False, xpsnr=False, haarpsi=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI and the frame's CIEDE2000 of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = None
-    if xpsnr:      # the tuple's last element, then CAMBI's
+    rec = hvs = cie = gms = cam = xps = hps = None
+    if haarpsi:    # the tuple's last element, then XPSNR's
+        hps, q = q[-1][:, 0], q[:-1]
+    if xpsnr:      # then CAMBI's
         xps, q = q[-1][:, 0], q[:-1]
     if cambi:      # then GMSD's
         cam, q = q[-1][:, 0], q[:-1]
@@ -537,6 +566,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["cambi"] = cam
     if xps is not None:
         more["xpsnr"] = xps
+    if hps is not None:
+        more["haarpsi"] = hps
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -573,6 +604,8 @@ def _check_mode_keys(config):
         raise ValueError("cambi must be true or false.")
     if "xpsnr" in config and not isinstance(config["xpsnr"], bool):
         raise ValueError("xpsnr must be true or false.")
+    if "haarpsi" in config and not isinstance(config["haarpsi"], bool):
+        raise ValueError("haarpsi must be true or false.")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -627,6 +660,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         after GMSD; default false; a model file does not turn it on),
         xpsnr (true: the row gains XPSNR, the pooled mean of the first plane's per-frame activity-weighted PSNR in dB, each
         frame's value capped at 100.0, after CAMBI; planar pixfmts only; default false; a model file does not turn it on),
+        haarpsi (true: the row gains HAARPSI, the pooled mean of the first plane's per-frame Haar wavelet perceptual similarity,
+        after XPSNR; default false; a model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -654,6 +689,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     gms = config.get("gmsd", False)
     cam = config.get("cambi", False)
     xps = config.get("xpsnr", False)
+    hps = config.get("haarpsi", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -706,13 +742,14 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         try:
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
-                                                                     gmsd=gms, cambi=cam, xpsnr=xps),
+                                                                     gmsd=gms, cambi=cam, xpsnr=xps,
+                                                                     haarpsi=hps),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps)
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -778,6 +815,8 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["CAMBI"] = float(pooled["cambi"]["mean"])
         if "xpsnr" in pooled:                 # per-frame dB capped at 100 by the log's writer
             metrics["XPSNR"] = float(pooled["xpsnr"]["mean"])
+        if "haarpsi" in pooled:
+            metrics["HAARPSI"] = float(pooled["haarpsi"]["mean"])
     return metrics
 
 
@@ -800,7 +839,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi;
     #                           and that a vmaf_model_path names a readable file
 
 
