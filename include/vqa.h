@@ -331,6 +331,19 @@ typedef struct vqa_haarpsi_metrics {
     double haarpsi;     /* (logit(similarity) / alpha')^2; exactly 1 for identical planes                                  */
 } vqa_haarpsi_metrics;
 
+/* VCA texture features of one reference plane (vqa_vca_submit / vqa_vca_wait; the definition is stated there).  The three words
+ * are the device's integer totals over the plane's 32 x 32 blocks, so the same frame (with its predecessor) gives the same
+ * words at any place of any batch, from host or device memory; e, h and l are formed from them on the host by vqa_vca_wait. */
+typedef struct vqa_vca_metrics {
+    uint64_t e_sum;     /* sum_k qH_k: the blocks' weighted |DCT| sums in steps of 2^-(24 - depth)                         */
+    uint64_t h_sum;     /* sum_k |qH_k(i) - qH_k(i - 1)|; 0 for a frame with no predecessor                                */
+    uint64_t l_sum;     /* sum_k qL_k, qL_k = rint(sqrt(S_k) 2^24)                                                         */
+    int32_t nbx, nby;   /* the block grid, floor(w / 32) x floor(h / 32)                                                   */
+    double e;           /* spatial texture energy E on the 8-bit scale                                                     */
+    double h;           /* temporal gradient of the energy, on the 8-bit scale; exactly 0 for a static pair                */
+    double l;           /* brightness L on the 8-bit scale: 64 for a flat 8-bit plane of 128                               */
+} vqa_vca_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -922,6 +935,54 @@ VQA_API int vqa_haarpsi_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *
                                int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_haarpsi_wait(vqa_ctx *ctx, vqa_haarpsi_metrics *out, int n_entries);
 
+/* ---- VCA texture features: spatial energy E, its temporal gradient h and brightness L from a weighted 32 x 32 block DCT
+ *      (Menon, Feldmann, Amirpour, Ghanbari, Timmerer: VCA, Video Complexity Analyzer, MMSys 2022) ----
+ * The complexity side of a CRF-prediction row: what the per-title literature measures on the SOURCE.  It reads planes of the
+ * REFERENCE stream only.  It is the paper's method with the details fixed here; where this text and the VCA tool differ, this
+ * text is what is built: VCA uses an integer transform and its own normalisation of L, neither of which was at hand.  It is
+ * NOT pinned against VCA's binary.
+ * Inputs   one to four planes, each measured by itself; R: the RAW INTEGER SAMPLES of a plane, h x w at `depth` bits;
+ *          sc = 2^-(depth - 8).
+ * Blocks   nbx = floor(w / 32), nby = floor(h / 32), C = nbx nby; blocks tile from (0, 0) and the right and bottom remainder
+ *          is not looked at (1080p: 60 x 33); block k = by nbx + bx.
+ * Transform D = T X T^t, the orthonormal 2-D DCT-II of the block's samples X: T[u][x] = c_u cos(pi (2x + 1) u / 64),
+ *          c_0 = sqrt(1 / 32), c_u = sqrt(2 / 32) otherwise.
+ * Energy   H_k = sum over (u, v) != (0, 0) of w(u, v) |D(u, v)|, w(u, v) = exp(|(u v / 1024)^2 - 1|): the DC is left out.
+ * Brightness S_k = the sum of the block's samples, an exact integer below 2^26; the DC coefficient is S_k / 32 and is taken
+ *          from S_k, not from the product.
+ * Words    qH_k = rint(H_k 2^(24 - depth)), below 2^37 at every depth (H_k <= e 32 sqrt(sum X^2) < 2784 2^depth);
+ *          qL_k = rint(sqrt((double) S_k) 2^24), below 2^37.  Per frame and plane three uint64 sums over the blocks:
+ *          e_sum = sum qH_k, h_sum = sum |qH_k(i) - qH_k(i - 1)| (0 for a frame with no predecessor), l_sum = sum qL_k; with
+ *          C <= 2^18 blocks every sum stays below 2^55.
+ * Host     in double: E = sc e_sum 2^-(24 - depth) / (1024 C), h = sc h_sum 2^-(24 - depth) / (1024 C),
+ *          L = sqrt(sc / 32) l_sum 2^-24 / C: all three on the 8-bit scale at every depth.
+ * Device   fp32: T and w rounded to fp32 once; the block's rounded mean (S_k + 512) >> 10 is taken off every sample first (the
+ *          AC coefficients do not change and the DC's rounding stays out of them); both products are k-ordered fp32 fma chains
+ *          of 32 terms on v_mfma_f32_32x32x2_f32 in an order that depends on the block alone; w |D| is summed in double in a
+ *          fixed order.  DESIGN.md 4n derives the error against the formula in float64; the tests hold E, h, L and every
+ *          block's H / 1024 to 1e-4 max(1, |value|) on the 8-bit scale.  l_sum is exact: integers and one double sqrt.
+ * Limits   VQA_ERR_UNSUPPORTED for a plane below 32 x 32, a packed layout (pixel step beyond one sample: bgr24), and
+ *          w h > 2^28 at 8 bits or > 2^26 above (the family's limits).
+ * The contract of vqa_siti_submit for the stream and for prev0 - asynchronous, the same plane descriptors, depths (one per
+ * submit), alignment rules, memory kinds and failure guarantee; prev0: the reference frame before frame 0, one frame of the
+ * reference's layout, resident where the frames are, or NULL: frame 0 then has no predecessor (h_sum = 0).  A batch of more
+ * than 32768 frames goes out in slices; a slice's first frame takes the previous slice's last frame as its predecessor.
+ * VQA_ERR_STATE while a VCA batch is pending.  A VCA batch is a batch of its own: it may be in flight next to a batch of every
+ * other kind of the same ctx, and each wait collects its own kind only - vqa_vca_wait with only another kind pending, and
+ * another kind's wait with only a VCA batch pending, are VQA_ERR_STATE and leave that batch pending.
+ * Kernels: per slice and group of same-geometry planes k_vca_blocks (a wave per block, every sample read once, both products
+ * on the matrix cores, qH_k, S_k, qL_k into a block map with one slot more than frames: prev0's), then k_vca_sum (the map and
+ * its |difference| to the slot before, integer adds only: no order can change a word).  A static clip gives h_sum == 0
+ * exactly.  Scratch on the device: 24 bytes per block and slot, 24 per entry and 12 KiB of tables, and as much pinned host
+ * memory; host frames and prev0 are staged in the buffers of an SI / TI submit.  All of it is kept by the ctx until vqa_trim /
+ * vqa_destroy.
+ * out of vqa_vca_wait: n * n_planes entries, frame-major.  blocks: NULL, or room for n_block_words = 2 n sum_p C_p words - per
+ * frame and plane, in plane order, C_p pairs (qH_k, S_k): the block map, for callers who want it.  Any other n_block_words
+ * with blocks given is VQA_ERR_INVALID and leaves the batch pending.                                                        */
+VQA_API int vqa_vca_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_frame_stride,
+                           const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_vca_wait(vqa_ctx *ctx, vqa_vca_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -977,7 +1038,12 @@ enum vqa_kernel_id {
                                 being unknown); id 36 stays unnamed                                                      */
     VQA_K_HAARPSI = 37,      /* vqa_haarpsi_submit: the 2x2 sums, the Haar coefficients, the similarities and the integer sums
                                 (one entry per group of same-geometry planes)                                            */
-    VQA_K_FINIS = 38         /* one past the last id: ... VQA_K_XPSNR_ACT .. VQA_K_BOUND - 1 and VQA_K_HAARPSI .. VQA_K_FINIS - 1 */
+    VQA_K_FINIS = 38,        /* one past VQA_K_HAARPSI, as HaarPSI shipped it (kept at 38 for callers and tests that rely on id
+                                38 being unknown); id 38 stays unnamed                                                   */
+    VQA_K_VCA_BLOCKS = 39,   /* vqa_vca_submit: the 32 x 32 block DCTs, qH_k, S_k, qL_k (one entry per group of same-geometry
+                                planes)                                                                                  */
+    VQA_K_VCA_SUM = 40,      /* vqa_vca_submit: the block map and its difference to the frame before, summed (one per slice) */
+    VQA_K_CLOSE = 41         /* one past the last id: ... VQA_K_HAARPSI .. VQA_K_FINIS - 1 and VQA_K_VCA_BLOCKS .. VQA_K_CLOSE - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -105,6 +105,10 @@ struct vqa_ctx {
     // vqa_haarpsi_submit: the three integer words per entry (device, pinned host); host frames are staged in qstage_*
     dbuf haarpsi_acc;
     hbuf haarpsi_host;
+    // vqa_vca_submit: the three words per entry, then the block map of n + 1 slots (device; pinned host without the first slot);
+    // the tables of k_vca_blocks; host frames and prev0 are staged in siti_stage / siti_prev
+    dbuf vca_acc, vca_tabs;
+    hbuf vca_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -137,6 +141,8 @@ struct vqa_ctx {
     int pend_x = 0;           // entries of the pending XPSNR batch (likewise); its planes' sizes and depth, for the host's part
     int pend_x_planes = 0, pend_x_depth = 8, pend_x_w[4] = {0}, pend_x_h[4] = {0};
     int pend_w = 0;           // entries of the pending HaarPSI batch (likewise)
+    int pend_t = 0;           // entries of the pending VCA batch (likewise); its planes' sizes and depth, for the host's part
+    int pend_t_planes = 0, pend_t_depth = 8, pend_t_w[4] = {0}, pend_t_h[4] = {0};
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -146,8 +152,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_FINIS] = {0};
-    int64_t prof_n[VQA_K_FINIS] = {0};
+    double prof_ms[VQA_K_CLOSE] = {0};
+    int64_t prof_n[VQA_K_CLOSE] = {0};
 };
 
 namespace {
@@ -220,7 +226,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -872,14 +878,14 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -1379,7 +1385,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the eleven plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI) share: the checks, the staging of host frames, the walk over
+// What the twelve plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -2310,6 +2316,97 @@ int vqa_haarpsi_wait(vqa_ctx *c, vqa_haarpsi_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// VCA texture features: the reference stream alone and the frame before each frame, every plane by itself.  A batch of its own
+// (pend_t), ordered by the stream like an SI/TI batch, whose host staging (siti_stage, siti_prev) it shares.
+static int vca_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                           const vqa_plane_desc *planes, int n_planes, bool &touched)
+{
+    if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (c->pend_t) return VQA_ERR_STATE;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+        if (int lim = side_and_area_limits(d, VCA_MIN_DIM)) return lim;
+        if (B.depth > 8 && (int64_t)d.width * d.height > (1ll << 26)) return VQA_ERR_UNSUPPORTED;
+        if (d.pixel_step != B.bps) return VQA_ERR_UNSUPPORTED;   // planar layouts only
+        return VQA_OK;
+    });
+    if (rc) return rc;
+    if (n > 1 && ref_fs < B.span) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if (mem_kind == VQA_MEM_HOST) {
+        if ((rc = stage(c, c->siti_stage, ref, (size_t)(n - 1) * ref_fs + B.span))) return rc;
+        if (prev0 && (rc = stage(c, c->siti_prev, prev0, (size_t)B.span))) return rc;
+    }
+    int pw[4], ph[4];
+    for (int p = 0; p < n_planes; p++) { pw[p] = planes[p].width; ph[p] = planes[p].height; }
+    const vca_geom g = vca_geometry(pw, ph, n_planes);
+    const size_t acc_words = (size_t)n * n_planes * VCA_WORDS, map_words = g.slot_words * (size_t)n;
+    // device: the words, prev0's slot, the frames' slots; host: the same without prev0's slot
+    if ((rc = ensure(c, c->vca_acc, sizeof(unsigned long long) * (acc_words + g.slot_words + map_words)))) return rc;
+    if ((rc = ensure_pinned(c, c->vca_host, sizeof(unsigned long long) * (acc_words + map_words)))) return rc;
+    const bool fresh_tabs = !c->vca_tabs.p;
+    if ((rc = ensure(c, c->vca_tabs, sizeof(float) * VCA_TABLE_FLOATS))) return rc;
+    if (fresh_tabs) {
+        static const std::vector<float> tabs = [] { std::vector<float> t(VCA_TABLE_FLOATS); vca_tables(t.data()); return t; }();
+        HIPCHK(c, hipMemcpyAsync(c->vca_tabs.p, tabs.data(), sizeof(float) * VCA_TABLE_FLOATS, hipMemcpyHostToDevice, st));
+    }
+    unsigned long long *acc = (unsigned long long *)c->vca_acc.p, *map = acc + acc_words + g.slot_words;   // frame 0's slot
+    const int depth = B.depth;
+    for_each_slice(c, n, [&](int a0, int m) {
+        const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
+        unsigned long long *smap = map + (size_t)a0 * g.slot_words;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
+            prof_scope ps_(c, VQA_K_VCA_BLOCKS);
+            // (a later slice's predecessor is the slice before's last frame, whose slot is filled already)
+            launch_vca_blocks(st, sref, a0 > 0 ? nullptr : prev0, m, ref_fs, planes, idx, cnt, g, depth,
+                              (const float *)c->vca_tabs.p, smap);
+        });
+        prof_scope ps_(c, VQA_K_VCA_SUM);
+        launch_vca_sum(st, m, n_planes, g, a0 > 0 || prev0 != nullptr, smap, acc + (size_t)a0 * n_planes * VCA_WORDS);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->vca_host.p, acc, sizeof(unsigned long long) * acc_words, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync((unsigned long long *)c->vca_host.p + acc_words, map, sizeof(unsigned long long) * map_words,
+                             hipMemcpyDeviceToHost, st));
+    c->pend_t = n * n_planes;
+    c->pend_t_planes = n_planes;
+    c->pend_t_depth = depth;
+    for (int p = 0; p < n_planes; p++) { c->pend_t_w[p] = pw[p]; c->pend_t_h[p] = ph[p]; }
+    return VQA_OK;
+}
+
+int vqa_vca_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                   const vqa_plane_desc *planes, int n_planes)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return vca_submit_body(c, ref, prev0, mem_kind, n, ref_fs, planes, n_planes, touched);
+    });
+}
+
+int vqa_vca_wait(vqa_ctx *c, vqa_vca_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_t || n_entries != c->pend_t) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    const int npl = c->pend_t_planes, n = n_entries / npl;
+    const vca_geom g = vca_geometry(c->pend_t_w, c->pend_t_h, npl);
+    const size_t nb = g.slot_words / 3;
+    if (blocks && n_block_words != (int64_t)(2 * nb * (size_t)n)) return VQA_ERR_INVALID;   // (the batch stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->vca_host.p, *map = acc + (size_t)n_entries * VCA_WORDS;
+    for (int e = 0; e < n_entries; e++) {
+        const int p = e % npl;
+        vca_finalize(acc + (size_t)e * VCA_WORDS, g.nbx[p], g.nby[p], c->pend_t_depth, out + e);
+    }
+    if (blocks)
+        for (size_t i = 0; i < nb * (size_t)n; i++) { blocks[2 * i] = map[3 * i]; blocks[2 * i + 1] = map[3 * i + 1]; }
+    c->pend_t = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2319,10 +2416,11 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_FINIS || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_CLOSE || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
-        (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI))
+        (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
+        (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2354,6 +2452,8 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_XPSNR_ACT) return "k_xpsnr_act";
     if (id == VQA_K_XPSNR_SSE) return "k_xpsnr_sse";
     if (id == VQA_K_HAARPSI) return "k_haarpsi";
+    if (id == VQA_K_VCA_BLOCKS) return "k_vca_blocks";
+    if (id == VQA_K_VCA_SUM) return "k_vca_sum";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

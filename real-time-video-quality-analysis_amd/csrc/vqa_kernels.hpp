@@ -443,4 +443,27 @@ void launch_haarpsi(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int
 // three words -> the record: the 128-bit quotient and the two logits of include/vqa.h, on the host
 void haarpsi_finalize(const unsigned long long *words, vqa_haarpsi_metrics *out);
 
+// VCA texture features (vqa_vca_submit): k_vca.hip
+constexpr int VCA_MIN_DIM = 32;                    // one whole 32 x 32 block
+constexpr int VCA_WORDS = 3;                       // per (frame, plane): e_sum, h_sum, l_sum
+constexpr int VCA_TABLE_FLOATS = 48 * 64;          // T in both operand orders and w, as the lanes hold them
+void vca_tables(float *tabs);
+// the block grids of a submit's planes and where each plane's blocks start in a map slot (in blocks; 3 words a block)
+struct vca_geom {
+    int nbx[4], nby[4], off[4];
+    size_t slot_words;   // 3 sum_p nbx nby: one frame's map
+};
+vca_geom vca_geometry(const int *pw, const int *ph, int n_planes);
+// qH, S, qL of every block of one group of same-geometry planes of n frames, and of prev0 (nullptr: none) into the slot before
+// frame 0's.  map: frame 0's slot.
+void launch_vca_blocks(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n, int64_t frame_stride,
+                       const vqa_plane_desc *planes, const int *idx, int count, const vca_geom &g, int depth, const float *tabs,
+                       unsigned long long *map);
+// the three words of n frames and every plane from the map: acc[(frame * n_planes + plane) * VCA_WORDS ..].  first_has_prev: the
+// slot before frame 0's is filled.
+void launch_vca_sum(hipStream_t st, int n, int n_planes, const vca_geom &g, bool first_has_prev, const unsigned long long *map,
+                    unsigned long long *acc);
+// three words -> the record: E, h and L of include/vqa.h in double, on the host
+void vca_finalize(const unsigned long long *words, int nbx, int nby, int depth, vqa_vca_metrics *out);
+
 } // namespace vqa

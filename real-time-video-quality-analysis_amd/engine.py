@@ -59,6 +59,9 @@ assert XPSNR_DTYPE.itemsize == C.sizeof(N.VqaXpsnrMetrics)
 HAARPSI_DTYPE = np.dtype([("den", np.uint64), ("num_lo", np.uint64), ("num_hi", np.uint64), ("similarity", np.float64),
                           ("haarpsi", np.float64)], align=True)
 assert HAARPSI_DTYPE.itemsize == C.sizeof(N.VqaHaarpsiMetrics)
+VCA_DTYPE = np.dtype([("e_sum", np.uint64), ("h_sum", np.uint64), ("l_sum", np.uint64), ("nbx", np.int32), ("nby", np.int32),
+                      ("e", np.float64), ("h", np.float64), ("l", np.float64)], align=True)
+assert VCA_DTYPE.itemsize == C.sizeof(N.VqaVcaMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -72,6 +75,7 @@ _BATCHES = {
     "_pending_b": ("vqa_cambi_submit", "vqa_cambi_wait", CAMBI_DTYPE, N.VqaCambiMetrics),   # (one stream)
     "_pending_x": ("vqa_xpsnr_submit", "vqa_xpsnr_wait", XPSNR_DTYPE, N.VqaXpsnrMetrics),   # (a pair and the frame before it)
     "_pending_w": ("vqa_haarpsi_submit", "vqa_haarpsi_wait", HAARPSI_DTYPE, N.VqaHaarpsiMetrics),
+    "_pending_t": ("vqa_vca_submit", "vqa_vca_wait", VCA_DTYPE, N.VqaVcaMetrics),   # (one stream and the frame before it)
 }
 
 
@@ -88,6 +92,23 @@ def check_xpsnr_planes(planes):
             raise ValueError("xpsnr needs planes of the luma's size or half of it (%dx%d against %dx%d)" % (w, h, w0, h0))
         if w < N.XPSNR_MIN_DIM or h < N.XPSNR_MIN_DIM:
             raise ValueError("xpsnr needs planes of at least %d x %d (got %dx%d)" % (N.XPSNR_MIN_DIM, N.XPSNR_MIN_DIM, w, h))
+
+
+def check_vca_planes(planes):
+    """vqa_vca_submit's layout rules, as a ValueError before anything is uploaded: a planar layout (pixel step of one sample),
+    every plane at least 32 x 32"""
+    bps = 2 if planes_depth(planes) > 8 else 1
+    for p in planes:
+        w, h = int(p[0]), int(p[1])
+        if int(p[4]) != bps:
+            raise ValueError("vca needs a planar layout (packed layouts such as bgr24 are not measured)")
+        if w < N.VCA_BLOCK or h < N.VCA_BLOCK:
+            raise ValueError("vca needs planes of at least %d x %d (got %dx%d)" % (N.VCA_BLOCK, N.VCA_BLOCK, w, h))
+
+
+def vca_grid(width, height):
+    """VCA's block grid of a width x height plane -> (nbx, nby): its whole 32 x 32 blocks"""
+    return int(width) // N.VCA_BLOCK, int(height) // N.VCA_BLOCK
 
 
 def xpsnr_grid(width, height):
@@ -301,13 +322,13 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
             try:
                 if getattr(self, pend, None):
-                    {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait}.get(pend, lambda: self._batch_wait(pend))()
+                    {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -708,6 +729,44 @@ class Engine:
         self.xpsnr_submit(ref, dist, planes, prev0, frame_bytes)
         return self.xpsnr_wait(blocks)
 
+    # ---- VCA texture features -------------------------------------------------------
+    def vca_submit(self, ref, planes, prev0=None, frame_bytes=None):
+        """VCA's E, h and L for n reference frames (vqa_vca_submit): the weighted 32 x 32 block DCT of every plane of frame i, and
+        its blocks against those of frame i - 1, frame 0 against prev0 (None: it has no predecessor and its h is 0).  The
+        arguments of siti_submit - the reference stream alone; a planar layout, every plane at least 32 x 32.  A batch of its
+        own, like siti_submit."""
+        check_vca_planes(planes)
+        self._batch_submit("_pending_t", self._ref_args(ref, planes, prev0, frame_bytes), planes)
+        self._vca_grids = [vca_grid(p[0], p[1]) for p in planes]   # of the pending batch
+
+    def vca_wait(self, blocks=False):
+        """-> [n, n_planes] records (VCA_DTYPE): the three integer words e_sum, h_sum, l_sum, the block grid nbx, nby, and e, h, l
+        on the 8-bit scale.  blocks=True: -> (records, maps) with the block map behind them, maps = one dict(qh, s as uint64
+        [n, nby, nbx]) per plane."""
+        n, npl, _keep = self._pending_t
+        nb = [gx * gy for gx, gy in self._vca_grids]
+        rec = np.zeros(n * npl, dtype=VCA_DTYPE)
+        words = np.zeros((n, 2 * sum(nb)), np.uint64) if blocks else None
+        st = self.lib.vqa_vca_wait(self.ctx, rec.ctypes.data_as(C.POINTER(N.VqaVcaMetrics)), n * npl,
+                                   words.ctypes.data_as(C.POINTER(C.c_uint64)) if blocks else None, words.size if blocks else 0)
+        self._pending_t = None
+        N.check(st, "vqa_vca_wait", self.ctx)
+        rec = rec.reshape(n, npl)
+        if not blocks:
+            return rec
+        maps, at = [], 0
+        for (gx, gy), c in zip(self._vca_grids, nb):
+            pairs = words[:, at:at + 2 * c].reshape(n, gy, gx, 2)
+            maps.append(dict(qh=np.ascontiguousarray(pairs[..., 0]), s=np.ascontiguousarray(pairs[..., 1])))
+            at += 2 * c
+        return rec, maps
+
+    def vca(self, ref, planes, prev0=None, blocks=False, frame_bytes=None):
+        """VCA's texture features per plane for n reference frames; returns [n, n_planes] structured array (VCA_DTYPE), with
+        blocks=True also the block maps (vca_wait)."""
+        self.vca_submit(ref, planes, prev0, frame_bytes)
+        return self.vca_wait(blocks)
+
     def _one_stream_args(self, frames, planes, frame_bytes=None):
         """the frames of a submit that reads one stream and no frame before it -> (ptr, mem kind, n, frame stride, what to keep
         alive)"""
@@ -742,7 +801,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_SHOWN:
+        for k in N.K_IDS_OPEN:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -390,7 +390,7 @@ class Quality:
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
-                 haarpsi=False):
+                 haarpsi=False, vca=False, vca_blocks=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -425,7 +425,12 @@ class Quality:
                 SSIM.  Planar layouts whose first plane is the luma
         haarpsi True: every chunk also goes through the HaarPSI kernel (Engine.haarpsi_submit) from the SAME upload; the pass's
                 tuple then gains ONE further last element, after XPSNR's: the HaarPSI records [n,p] (engine.HAARPSI_DTYPE: the
-                three integer words, similarity, haarpsi); "only": no SSE / SSIM"""
+                three integer words, similarity, haarpsi); "only": no SSE / SSIM
+        vca     True: every chunk's REFERENCE frames also go through the VCA kernels (Engine.vca_submit) from the same upload,
+                prev0 being the reference feed's halo slot as for motion, siti and xpsnr; the pass's tuple then gains ONE further
+                last element, after HaarPSI's: the VCA records [n,p] (engine.VCA_DTYPE: e_sum, h_sum, l_sum, nbx, nby, e, h, l) -
+                with vca_blocks=True the pair (records, block maps: per plane dict(qh, s as uint64 [n, nby, nbx])); "only": no
+                SSE / SSIM, and the pass reads the `ref` stream alone.  Planar layouts, every plane at least 32 x 32"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -479,10 +484,19 @@ class Quality:
             raise ValueError("a HaarPSI-only pass has no SSIM scales")
         self.motion, self.siti, self.psnr_hvs, self.gmsd, self.cambi, self.xpsnr = motion, siti, psnr_hvs, gmsd, cambi, xpsnr
         self.haarpsi = haarpsi
+        if not (isinstance(vca, bool) or (isinstance(vca, str) and vca == "only")):
+            raise ValueError("vca must be False, True or 'only'")
+        if vca == "only" and scales:
+            raise ValueError("a VCA-only pass has no SSIM scales")
+        if vca:
+            from .engine import check_vca_planes
+            check_vca_planes(planes)
+        self.vca, self.vca_blocks = vca, bool(vca_blocks)
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
-                     ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only")
+                     ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only" and
+                     vca != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -564,7 +578,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     of the distorted stream; cambi="only" leaves sse and ssim None as well and measures `ref`, the only stream it reads.
     Quality(.., xpsnr=True) appends ONE further last element, after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE);
     xpsnr="only" leaves sse and ssim None as well.  Quality(.., haarpsi=True) appends ONE further last element, after XPSNR's:
-    the HaarPSI records [n,p] (engine.HAARPSI_DTYPE); haarpsi="only" leaves sse and ssim None as well.
+    the HaarPSI records [n,p] (engine.HAARPSI_DTYPE); haarpsi="only" leaves sse and ssim None as well.  Quality(.., vca=True)
+    appends ONE further last element, after HaarPSI's: the VCA records [n,p] (engine.VCA_DTYPE) of the reference stream - with
+    vca_blocks=True the pair (records, block maps); vca="only" leaves sse and ssim None as well and reads `ref` alone.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -633,6 +649,12 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.haarpsi:
             from .engine import HAARPSI_DTYPE
             q += (np.zeros((0, len(quality.planes)), HAARPSI_DTYPE),)
+        if quality.vca:
+            from .engine import VCA_DTYPE, vca_grid
+            rec = np.zeros((0, len(quality.planes)), VCA_DTYPE)
+            maps = [dict(qh=np.zeros((0,) + vca_grid(p[0], p[1])[::-1], np.uint64), s=np.zeros((0,) + vca_grid(p[0], p[1])[::-1], np.uint64))
+                    for p in quality.planes]
+            q += ((rec, maps) if quality.vca_blocks else rec,)
         return q, series
     if engine is not None:
         first = engine
@@ -647,7 +669,7 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
 def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series, n, batch_size, on_quality):
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
-    # motion, SI/TI and CAMBI alone read the reference stream only: the distorted stream is not even uploaded
+    # motion, SI/TI, VCA and CAMBI alone read the reference stream only: the distorted stream is not even uploaded
     ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and quality.cambi is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
@@ -680,7 +702,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     host = any(f.host for f in feeds.values())
     staged = any(f.staged for f in feeds.values())
     cap = chunk_frames(batch_size, interval if (want_q and want_c) else None, per_frame if host else 0, staged)
-    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and (quality.motion or quality.siti or quality.xpsnr)))
+    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and (quality.motion or quality.siti or quality.xpsnr or quality.vca)))
     nchunks = len(plans)
     # ---- lanes
     farneback = want_c and (complexity.mask & N.M_MOTION) and complexity.motion_mode == N.MOTION_FARNEBACK
@@ -756,7 +778,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -780,7 +802,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.adm:
                     eng.adm_submit(pair[0], pair[1], quality.planes)
                     p["has_a"] = True
-                if quality.motion or quality.siti or quality.xpsnr:   # prev0 = the reference frame before the chunk: the halo
+                if quality.motion or quality.siti or quality.xpsnr or quality.vca:   # prev0 = the reference frame before the chunk: the halo
                     prev0 = None                     # slot of the chunk's own buffer (host streams) or the resident clip's frame
                     if p["q0"] > 0:                  # in place
                         if fr.host:
@@ -813,6 +835,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.haarpsi:
                     eng.haarpsi_submit(pair[0], pair[1], quality.planes)
                     p["has_w"] = True
+                if quality.vca:   # the reference frames alone, and the halo for the gradient of the chunk's first frame
+                    eng.vca_submit(pair[0], quality.planes, prev0)
+                    p["has_t"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -831,7 +856,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps = [], [], [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs = [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -859,6 +884,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["xres"] = eng.xpsnr_wait()
             if p["has_w"]:
                 p["wres"] = eng.haarpsi_wait()
+            if p["has_t"]:
+                p["tres"] = eng.vca_wait(quality.vca_blocks)
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -897,6 +924,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 xps.append(p.pop("xres"))
             if p["has_w"]:
                 hps.append(p.pop("wres"))
+            if p["has_t"]:
+                vcs.append(p.pop("tres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -975,6 +1004,12 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(xps),)
     if want_q and quality.haarpsi:
         q += (np.concatenate(hps),)
+    if want_q and quality.vca:
+        if quality.vca_blocks:
+            maps = [{k: np.concatenate([c[1][pl][k] for c in vcs]) for k in ("qh", "s")} for pl in range(len(quality.planes))]
+            q += ((np.concatenate([c[0] for c in vcs]), maps),)
+        else:
+            q += (np.concatenate(vcs),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

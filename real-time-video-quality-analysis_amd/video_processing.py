@@ -259,8 +259,28 @@ def frame_haarpsi(reference, encoded, layout="bgr24", height=None, width=None, e
     return r["haarpsi"], r["similarity"], [(p[0], p[1]) for p in planes]
 
 
+def frame_vca(reference, layout="yuv420p", height=None, width=None, engine=None, batch_size=64, device=None, blocks=False):
+    """Per-frame VCA texture features per plane of the REFERENCE stream (Engine.vca through the one-pass pipeline of
+    frame_quality; the stream is uploaded once, there is no distorted stream, and every chunk after the first sees the frame
+    before it).  The definition is include/vqa.h's: per whole 32 x 32 block the orthonormal DCT-II, H_k = the sum of
+    exp(|(u v / 1024)^2 - 1|) |D(u, v)| without the DC, and the block's sample sum - the paper's method, not pinned against the
+    VCA tool, whose integer transform and normalisation of L differ.
+    Returns (e [n,p] float64 - the spatial texture energy -, h [n,p] float64 - its temporal gradient, 0 for frame 0 and exactly 0
+    for a repeated frame -, l [n,p] float64 - the brightness -, plane sizes), all on the 8-bit scale; with blocks=True also the
+    block maps: per plane dict(qh, s as uint64 [n, nby, nbx]), qh in steps of 2^-(24 - depth).  Planar layouts (bgr24 is a
+    ValueError); every plane at least 32 x 32."""
+    reference = _host_stream(reference, wide=True)
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(reference, reference, quality=stream.Quality(planes, vca="only", vca_blocks=blocks), batch_size=batch_size,
+                      engine=engine, device=device)
+    r, maps = q[-1] if blocks else (q[-1], None)
+    out = (r["e"], r["h"], r["l"], [(p[0], p[1]) for p in planes])
+    return out + (maps,) if blocks else out
+
+
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
-                  cambi=None, xpsnr=None, haarpsi=None):
+                  cambi=None, xpsnr=None, haarpsi=None, vca=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -283,6 +303,9 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     and before vmaf, likewise capped at 100.0.  The model never reads it.
     haarpsi: None, or the first plane's HaarPSI records [n] (engine.HAARPSI_DTYPE): the log then also carries haarpsi, after
     xpsnr and before vmaf, likewise.  The model never reads it.
+    vca: None, or the first plane's VCA records [n] (engine.VCA_DTYPE) of the reference stream: the log then also carries vca_e,
+    vca_h and vca_l, after haarpsi and before vmaf, likewise (frame 0's vca_h = 0 is part of the pooled values).  The model never
+    reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -327,6 +350,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         haarpsi = np.asarray(haarpsi).reshape(-1)
         names += ["haarpsi"]
         cols += [haarpsi["haarpsi"].astype(np.float64)]
+    if vca is not None:
+        vca = np.asarray(vca).reshape(-1)
+        names += ["vca_e", "vca_h", "vca_l"]
+        cols += [vca[k].astype(np.float64) for k in ("e", "h", "l")]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -448,7 +475,7 @@ def _open_quality_stream(src, layout, height, width):
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
-                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False):
+                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -470,6 +497,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     planar layouts only - bgr24 is a ValueError; a model file does not turn it on).
     haarpsi=True: likewise HaarPSI, the Haar wavelet perceptual similarity (haarpsi of the first plane; a model file does not
     turn it on).
+    vca=True: likewise VCA's texture features of the REFERENCE stream (vca_e, vca_h, vca_l of the first plane; planar layouts
+    only - bgr24 is a ValueError; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -490,7 +519,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if xpsnr:
             from .engine import check_xpsnr_planes
             check_xpsnr_planes(LAYOUTS[layout][0](h, w))
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi:
+        if vca:
+            from .engine import check_vca_planes
+            check_vca_planes(LAYOUTS[layout][0](h, w))
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -499,9 +531,9 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              psnr_hvs=bool(psnr_hvs), ciede=bool(ciede),
                                                              ciede_weights=ciede_weights, gmsd=bool(gmsd),
                                                              cambi=bool(cambi), xpsnr=bool(xpsnr),
-                                                             haarpsi=bool(haarpsi)),
+                                                             haarpsi=bool(haarpsi), vca=bool(vca)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -539,11 +571,13 @@ MODE_KEYS = {
 
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
-                       cambi=False, xpsnr=False, haarpsi=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI and the frame's CIEDE2000 of a pass (the
+                       cambi=False, xpsnr=False, haarpsi=False, vca=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA and the frame's CIEDE2000 of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = None
-    if haarpsi:    # the tuple's last element, then XPSNR's
+    rec = hvs = cie = gms = cam = xps = hps = vcs = None
+    if vca:        # the tuple's last element, then HaarPSI's
+        vcs, q = q[-1][:, 0], q[:-1]
+    if haarpsi:    # then XPSNR's
         hps, q = q[-1][:, 0], q[:-1]
     if xpsnr:      # then CAMBI's
         xps, q = q[-1][:, 0], q[:-1]
@@ -568,6 +602,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["xpsnr"] = xps
     if hps is not None:
         more["haarpsi"] = hps
+    if vcs is not None:
+        more["vca"] = vcs
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -606,6 +642,8 @@ def _check_mode_keys(config):
         raise ValueError("xpsnr must be true or false.")
     if "haarpsi" in config and not isinstance(config["haarpsi"], bool):
         raise ValueError("haarpsi must be true or false.")
+    if "vca" in config and not isinstance(config["vca"], bool):
+        raise ValueError("vca must be true or false.")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -662,6 +700,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         frame's value capped at 100.0, after CAMBI; planar pixfmts only; default false; a model file does not turn it on),
         haarpsi (true: the row gains HAARPSI, the pooled mean of the first plane's per-frame Haar wavelet perceptual similarity,
         after XPSNR; default false; a model file does not turn it on),
+        vca (true: the row gains VCA_E, VCA_H and VCA_L, the pooled means of the first plane's per-frame VCA texture energy, its
+        temporal gradient - frame 0's 0 included - and brightness of the INPUT stream, after HAARPSI; planar pixfmts only; default
+        false; a model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -690,6 +731,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     cam = config.get("cambi", False)
     xps = config.get("xpsnr", False)
     hps = config.get("haarpsi", False)
+    vcs = config.get("vca", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -738,18 +780,21 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         if xps:
             from .engine import check_xpsnr_planes
             check_xpsnr_planes(planes)
+        if vcs:
+            from .engine import check_vca_planes
+            check_vca_planes(planes)
         wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
         try:
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
                                                                      gmsd=gms, cambi=cam, xpsnr=xps,
-                                                                     haarpsi=hps),
+                                                                     haarpsi=hps, vca=vcs),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps)
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -817,6 +862,10 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["XPSNR"] = float(pooled["xpsnr"]["mean"])
         if "haarpsi" in pooled:
             metrics["HAARPSI"] = float(pooled["haarpsi"]["mean"])
+        if "vca_e" in pooled:                 # the pooled means; frame 0's vca_h = 0 is included
+            metrics["VCA_E"] = float(pooled["vca_e"]["mean"])
+            metrics["VCA_H"] = float(pooled["vca_h"]["mean"])
+            metrics["VCA_L"] = float(pooled["vca_l"]["mean"])
     return metrics
 
 
@@ -839,7 +888,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca;
     #                           and that a vmaf_model_path names a readable file
 
 
