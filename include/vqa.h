@@ -344,6 +344,25 @@ typedef struct vqa_vca_metrics {
     double l;           /* brightness L on the 8-bit scale: 64 for a flat 8-bit plane of 128                               */
 } vqa_vca_metrics;
 
+/* No-reference blockiness, blur and noise of one plane (vqa_artifacts_submit / vqa_artifacts_wait; the definition is stated
+ * there).  The 21 words are the device's integer sums, so the same plane gives the same words at any place of any batch, from
+ * host or device memory; everything below them is formed on the host by vqa_artifacts_wait.                                 */
+typedef struct vqa_artifacts_metrics {
+    uint64_t edge_h[8]; /* per phase p: sum of |x(i, c) - x(i, c - 1)| over all rows and the boundaries c with c mod 8 == p    */
+    uint64_t edge_v[8]; /* the same over rows: |x(r, j) - x(r - 1, j)|, r mod 8 == p                                           */
+    uint64_t blur_f_h;  /* sum dF over the horizontal blur domain                                                              */
+    uint64_t blur_v_h;  /* sum max(0, 9 dF - dB9) there                                                                        */
+    uint64_t blur_f_v;  /* sum dF over the vertical blur domain                                                                */
+    uint64_t blur_v_v;  /* sum max(0, 9 dF - dB9) there                                                                        */
+    uint64_t lap;       /* sum |L| over the interior                                                                           */
+    int32_t phase_h, phase_v;   /* argmax_p r_h[p], argmax_p r_v[p]; the lowest p on a tie                                     */
+    double blockiness;      /* (r_h[0] + r_v[0]) / 2: the 8 x 8 grid anchored at the plane's origin, in [-1, 1]                */
+    double blockiness_max;  /* (r_h[phase_h] + r_v[phase_v]) / 2: the grid of a cropped or shifted picture                     */
+    double blur_h, blur_v;  /* (9 blur_f - blur_v) / (9 blur_f) per direction; exactly 0 where blur_f == 0                     */
+    double blur;            /* max(blur_h, blur_v), in [0, 1]; larger = less sharp                                             */
+    double noise;           /* Immerkaer's sigma on the 8-bit scale                                                            */
+} vqa_artifacts_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -983,6 +1002,62 @@ VQA_API int vqa_vca_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *prev
                            const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_vca_wait(vqa_ctx *ctx, vqa_vca_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words);
 
+/* ---- No-reference artefact measures of ONE stream: blockiness, blur and noise ----
+ * The three artefacts an encode is screened for beside banding (CAMBI).  All three are neighbour-difference statistics of one
+ * plane: integer work up to the last division, no frame before, no model file, no constants from a tool.  They are the three
+ * papers' methods with the details fixed here; no tool is compared (FFmpeg's blockdetect and blurdetect measure other things).
+ * Inputs   one to four planes, each measured by itself; x[H][W]: the RAW INTEGER SAMPLES of a plane at `depth` bits;
+ *          s = 2^(depth - 8).  Packed bgr24 is measured per channel plane, as in SI/TI.
+ * Blockiness  the boundary-difference measure of Wang, Sheikh and Bovik (ICIP 2002), resolved by grid phase; the normalisation
+ *          is this project's own.  A horizontal boundary c lies between columns c - 1 and c, c = 1 .. W - 1; its step in row i
+ *          is |x(i, c) - x(i, c - 1)|.  edge_h[p], p = 0 .. 7: the sum of the steps over all rows and all boundaries with
+ *          c mod 8 == p; cnt_h[p]: the number of such terms, H times the number of c in 1 .. W - 1 with c mod 8 == p (it follows
+ *          from H and W alone and is not a device word).  edge_v[p], cnt_v[p]: the same over rows, boundary r between rows r - 1
+ *          and r.  Per direction and phase, in double:
+ *              m_B = edge[p] / cnt[p],  m_O = (sum_q edge[q] - edge[p]) / (sum_q cnt[q] - cnt[p])   (integer differences),
+ *              r[p] = (m_B - m_O) / (m_B + m_O), and exactly 0 when m_B + m_O == 0;  r[p] lies in [-1, 1].
+ *          blockiness = (r_h[0] + r_v[0]) / 2: the 8 x 8 grid anchored at the plane's origin, where a codec puts it.
+ *          phase_h = argmax_p r_h[p], the lowest p on a tie; phase_v likewise;
+ *          blockiness_max = (r_h[phase_h] + r_v[phase_v]) / 2: the grid of a cropped or shifted picture.
+ *          Constant 8 x 8 blocks read 1; the same blocks shifted by (3, 5) read phase_h 3, phase_v 5, blockiness_max 1 and
+ *          blockiness -1; a flat plane reads 0.
+ * Blur     Crete-Roffet, Dolmiere, Ladret and Nicolas (SPIE 2007), the paper's form: a 9-tap mean and plain neighbour
+ *          differences (not scikit-image's blur_effect: Sobel, 11 taps).  Vertically dF(i, j) = |x(i, j) - x(i - 1, j)|; the
+ *          neighbour difference of the 9-tap column mean telescopes, nine times it is dB9(i, j) = |x(i + 4, j) - x(i - 5, j)|,
+ *          so no blur pass is made.  Domain: i = 5 .. H - 5 and every column j - where the whole window lies inside, H - 9 rows.
+ *          blur_f_v = sum dF, blur_v_v = sum max(0, 9 dF - dB9); in double F9 = 9 blur_f_v,
+ *          blur_v = (F9 - blur_v_v) / F9, and exactly 0 when blur_f_v == 0.  Horizontally the same over columns
+ *          (j = 5 .. W - 5, every row): blur_f_h, blur_v_h, blur_h.  blur = max(blur_h, blur_v), in [0, 1]; larger = less
+ *          sharp.  A 0 / peak checkerboard reads exactly 1/9; the ramp x(i, j) = j reads blur_h 1 and blur_v 0.
+ * Noise    Immerkaer's fast noise estimate (CVIU 1996): L = x(i-1,j-1) - 2 x(i-1,j) + x(i-1,j+1) - 2 x(i,j-1) + 4 x(i,j)
+ *          - 2 x(i,j+1) + x(i+1,j-1) - 2 x(i+1,j) + x(i+1,j+1) over the interior i = 1 .. H - 2, j = 1 .. W - 2;
+ *          lap = sum |L|; in double noise = (c lap) / ((6 N) s) with N = (W - 2)(H - 2) and c = 1.2533141373155003, the
+ *          double nearest sqrt(pi / 2): a standard deviation on the 8-bit scale at every depth.  A ramp reads exactly 0.
+ * Ranges   the largest term per sample is 9 * 65535 (blur_v_*), so the largest word stays below 9 * 65535 H W: under 2^43 at
+ *          2160p and, with H W <= 2^28, under 2^48 < 2^63 at any plane the library accepts.  No lane of the kernel sums more
+ *          than 64 samples (below 2^26) in 32 bits; everything beyond a lane is 64-bit.
+ * Limits   every plane at least 16 x 16 and H W <= 2^28 (the family's limits): VQA_ERR_UNSUPPORTED beyond either.  At 16 rows
+ *          the vertical blur domain is 7 rows.
+ * The contract of vqa_cambi_submit: asynchronous, ONE stream, the same plane descriptors (one to four planes, each measured by
+ * itself; packed layouts through pixel_step), depths (one per submit, 8..16), alignment rules, memory kinds and failure
+ * guarantee: a failed submit leaves nothing in flight.  A batch of more than 32768 frames goes out in slices.  VQA_ERR_STATE
+ * while an artefacts batch is pending.  An artefacts batch is a batch of its own: it may be in flight next to a batch of every
+ * other kind of the same ctx (one upload then serves all), and each wait collects its own kind only - vqa_artifacts_wait with
+ * only another kind pending, and another kind's wait with only an artefacts batch pending, are VQA_ERR_STATE and leave that
+ * batch pending.
+ * Kernel: per slice and group of same-geometry planes one launch of k_artifacts: a 64 x 32 tile and its apron (5 samples up
+ * and left, 4 down and right; 8 are loaded on the left, which keeps groups of four samples aligned) go to LDS as raw integers,
+ * every sample read once apart from aprons, four samples per load where the layout allows; tile origins are multiples of 8, so a boundary's phase is a local index mod 8; every term belongs to one
+ * sample - the right-hand or lower one of a boundary, the centre of a window - so tiles neither share nor drop a term; integer
+ * adds only, 64-bit integer atomics: no order can change a word; no floating point on the device.  vqa_artifacts_wait forms
+ * everything below the words on the host in double, contraction off, in the order written above.  Scratch on the device: the
+ * 21 words per entry, and as much pinned host memory; host frames are staged in the buffer of the second stream of a quality
+ * submit.  All of it is kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_artifacts_wait: n * n_planes entries, frame-major.                                                             */
+VQA_API int vqa_artifacts_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                                 const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_artifacts_wait(vqa_ctx *ctx, vqa_artifacts_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1043,7 +1118,11 @@ enum vqa_kernel_id {
     VQA_K_VCA_BLOCKS = 39,   /* vqa_vca_submit: the 32 x 32 block DCTs, qH_k, S_k, qL_k (one entry per group of same-geometry
                                 planes)                                                                                  */
     VQA_K_VCA_SUM = 40,      /* vqa_vca_submit: the block map and its difference to the frame before, summed (one per slice) */
-    VQA_K_CLOSE = 41         /* one past the last id: ... VQA_K_HAARPSI .. VQA_K_FINIS - 1 and VQA_K_VCA_BLOCKS .. VQA_K_CLOSE - 1 */
+    VQA_K_CLOSE = 41,        /* one past VQA_K_VCA_SUM, as VCA shipped it (kept at 41 for callers and tests that rely on id 41
+                                being unknown); id 41 stays unnamed                                                      */
+    VQA_K_ARTIFACTS = 42,    /* vqa_artifacts_submit: the boundary steps by phase, both blur sums and the Laplacian sum (one
+                                entry per group of same-geometry planes)                                                 */
+    VQA_K_STOP = 43          /* one past the last id: ... VQA_K_VCA_BLOCKS .. VQA_K_CLOSE - 1 and VQA_K_ARTIFACTS .. VQA_K_STOP - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -59,7 +59,9 @@ K_IDS_GIVEN = K_IDS_TOLD + (K_XPSNR_ACT, K_XPSNR_SSE)   # the ids below K_BOUND 
 K_HAARPSI, K_FINIS = 37, 38                       # added beyond K_BOUND, which stays 36; id 36 is unnamed
 K_IDS_SHOWN = K_IDS_GIVEN + (K_HAARPSI,)          # the ids below K_FINIS (kept as HaarPSI shipped it)
 K_VCA_BLOCKS, K_VCA_SUM, K_CLOSE = 39, 40, 41     # added beyond K_FINIS, which stays 38; id 38 is unnamed
-K_IDS_OPEN = K_IDS_SHOWN + (K_VCA_BLOCKS, K_VCA_SUM)   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_OPEN = K_IDS_SHOWN + (K_VCA_BLOCKS, K_VCA_SUM)   # the ids below K_CLOSE (kept as VCA shipped it)
+K_ARTIFACTS, K_STOP = 42, 43                      # added beyond K_CLOSE, which stays 41; id 41 is unnamed
+K_IDS_FULL = K_IDS_OPEN + (K_ARTIFACTS,)          # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -82,6 +84,7 @@ CAMBI_MIN_DIM = 16   # vqa_cambi_submit: the limit of the family, whose planes i
 XPSNR_MIN_DIM = 16   # vqa_xpsnr_submit: the limit of the family, whose planes it shares
 HAARPSI_MIN_DIM = 16   # vqa_haarpsi_submit: the limit of the family, whose planes it shares
 VCA_BLOCK = 32   # vqa_vca_submit: the side of a block, and of the smallest plane
+ARTIFACTS_MIN_DIM = 16   # vqa_artifacts_submit: the limit of the family, whose planes it shares
 HAARPSI_FIX = 1 << 30  # vqa_haarpsi_metrics: num is a sum of u wI with u = rint(2^30 sigmoid)
 HAARPSI_ALPHA = 4.2    # the paper's alpha
 CAMBI_SCALES = 5
@@ -177,6 +180,13 @@ class VqaVcaMetrics(C.Structure):
                 ("e", C.c_double), ("h", C.c_double), ("l", C.c_double)]
 
 
+class VqaArtifactsMetrics(C.Structure):
+    _fields_ = [("edge_h", C.c_uint64 * 8), ("edge_v", C.c_uint64 * 8), ("blur_f_h", C.c_uint64), ("blur_v_h", C.c_uint64),
+                ("blur_f_v", C.c_uint64), ("blur_v_v", C.c_uint64), ("lap", C.c_uint64), ("phase_h", C.c_int32),
+                ("phase_v", C.c_int32), ("blockiness", C.c_double), ("blockiness_max", C.c_double), ("blur_h", C.c_double),
+                ("blur_v", C.c_double), ("blur", C.c_double), ("noise", C.c_double)]
+
+
 class VqaHaarpsiMetrics(C.Structure):
     _fields_ = [("den", C.c_uint64), ("num_lo", C.c_uint64), ("num_hi", C.c_uint64), ("similarity", C.c_double),
                 ("haarpsi", C.c_double)]
@@ -239,6 +249,8 @@ SIGNATURES = {
     "vqa_haarpsi_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaHaarpsiMetrics), C.c_int]),
     "vqa_vca_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_vca_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaVcaMetrics), C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
+    "vqa_artifacts_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_artifacts_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaArtifactsMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

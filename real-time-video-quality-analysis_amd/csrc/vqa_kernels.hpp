@@ -466,4 +466,15 @@ void launch_vca_sum(hipStream_t st, int n, int n_planes, const vca_geom &g, bool
 // three words -> the record: E, h and L of include/vqa.h in double, on the host
 void vca_finalize(const unsigned long long *words, int nbx, int nby, int depth, vqa_vca_metrics *out);
 
+// no-reference blockiness, blur and noise (vqa_artifacts_submit): k_artifacts.hip
+constexpr int ARTIFACTS_MIN_DIM = 16;              // the family's limit
+constexpr int ARTIFACTS_WORDS = 21;                // per (frame, plane): edge_h[8], edge_v[8], blur_f_h, blur_v_h, blur_f_v, blur_v_v, lap
+constexpr double ARTIFACTS_SQRT_HALF_PI = 1.2533141373155003;   // the double nearest sqrt(pi / 2)
+// the 21 integer sums of n frames of one group of same-geometry planes, added to acc[(frame * n_planes + plane) *
+// ARTIFACTS_WORDS ..], which the caller has zeroed
+void launch_artifacts(hipStream_t st, const uint8_t *frames, int n, int64_t frame_stride, const vqa_plane_desc *planes,
+                      const int *idx, int count, int n_planes, int depth, unsigned long long *acc);
+// 21 words -> the record: the phases, blockiness, blur and noise of include/vqa.h in double, on the host
+void artifacts_finalize(const unsigned long long *words, int h, int w, int depth, vqa_artifacts_metrics *out);
+
 } // namespace vqa

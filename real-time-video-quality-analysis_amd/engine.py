@@ -62,6 +62,12 @@ assert HAARPSI_DTYPE.itemsize == C.sizeof(N.VqaHaarpsiMetrics)
 VCA_DTYPE = np.dtype([("e_sum", np.uint64), ("h_sum", np.uint64), ("l_sum", np.uint64), ("nbx", np.int32), ("nby", np.int32),
                       ("e", np.float64), ("h", np.float64), ("l", np.float64)], align=True)
 assert VCA_DTYPE.itemsize == C.sizeof(N.VqaVcaMetrics)
+ARTIFACTS_DTYPE = np.dtype([("edge_h", np.uint64, (8,)), ("edge_v", np.uint64, (8,)), ("blur_f_h", np.uint64),
+                            ("blur_v_h", np.uint64), ("blur_f_v", np.uint64), ("blur_v_v", np.uint64), ("lap", np.uint64),
+                            ("phase_h", np.int32), ("phase_v", np.int32), ("blockiness", np.float64),
+                            ("blockiness_max", np.float64), ("blur_h", np.float64), ("blur_v", np.float64),
+                            ("blur", np.float64), ("noise", np.float64)], align=True)
+assert ARTIFACTS_DTYPE.itemsize == C.sizeof(N.VqaArtifactsMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -76,6 +82,7 @@ _BATCHES = {
     "_pending_x": ("vqa_xpsnr_submit", "vqa_xpsnr_wait", XPSNR_DTYPE, N.VqaXpsnrMetrics),   # (a pair and the frame before it)
     "_pending_w": ("vqa_haarpsi_submit", "vqa_haarpsi_wait", HAARPSI_DTYPE, N.VqaHaarpsiMetrics),
     "_pending_t": ("vqa_vca_submit", "vqa_vca_wait", VCA_DTYPE, N.VqaVcaMetrics),   # (one stream and the frame before it)
+    "_pending_r": ("vqa_artifacts_submit", "vqa_artifacts_wait", ARTIFACTS_DTYPE, N.VqaArtifactsMetrics),   # (one stream)
 }
 
 
@@ -322,7 +329,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -794,6 +801,25 @@ class Engine:
         self.cambi_submit(frames, planes, frame_bytes)
         return self.cambi_wait()
 
+    # ---- blockiness, blur and noise -------------------------------------------------
+    def artifacts_submit(self, frames, planes, frame_bytes=None):
+        """No-reference blockiness, blur and noise for n frames of ONE stream (vqa_artifacts_submit): the arguments of
+        cambi_submit - an array / DeviceFrames (uint16 above 8 bits; a dtype that does not match the depth is a ValueError) and
+        the plane tuples of quality_submit, every plane measured by itself and at least 16 x 16.  A batch of its own, like
+        cambi_submit."""
+        streams = self._one_stream_args(frames, planes, frame_bytes)
+        self._batch_submit("_pending_r", streams, planes, n=streams[2])
+
+    def artifacts_wait(self):
+        """-> [n, n_planes] records (ARTIFACTS_DTYPE): the 21 integer words edge_h[8], edge_v[8], blur_f_h, blur_v_h, blur_f_v,
+        blur_v_v, lap; phase_h, phase_v; blockiness, blockiness_max, blur_h, blur_v, blur, noise (include/vqa.h)."""
+        return self._batch_wait("_pending_r")
+
+    def artifacts(self, frames, planes, frame_bytes=None):
+        """Blockiness, blur and noise per plane for n frames; returns [n, n_planes] structured array (ARTIFACTS_DTYPE)."""
+        self.artifacts_submit(frames, planes, frame_bytes)
+        return self.artifacts_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -801,7 +827,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_OPEN:
+        for k in N.K_IDS_FULL:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -279,8 +279,25 @@ def frame_vca(reference, layout="yuv420p", height=None, width=None, engine=None,
     return out + (maps,) if blocks else out
 
 
+def frame_artifacts(frames, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame no-reference blockiness, blur and noise per plane of ONE stream (Engine.artifacts through the one-pass pipeline of
+    frame_quality; the stream is uploaded once, there is no second stream).  The definition is include/vqa.h's: the boundary
+    steps of Wang, Sheikh and Bovik resolved by the phase of an 8 x 8 grid, the blur measure of Crete-Roffet et al. with a 9-tap
+    mean, Immerkaer's noise estimate on the 8-bit scale - integers up to the last division, no tool compared.
+    Returns (dict of [n,p] arrays: blockiness, blockiness_max, blur, noise as float64 and phase_h, phase_v as int32; plane
+    sizes).  Every plane at least 16 x 16; packed bgr24 is measured per channel."""
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, artifacts="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    keys = ("blockiness", "blockiness_max", "phase_h", "phase_v", "blur", "noise")
+    return {k: r[k] for k in keys}, [(p[0], p[1]) for p in planes]
+
+
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
-                  cambi=None, xpsnr=None, haarpsi=None, vca=None):
+                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -306,6 +323,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     vca: None, or the first plane's VCA records [n] (engine.VCA_DTYPE) of the reference stream: the log then also carries vca_e,
     vca_h and vca_l, after haarpsi and before vmaf, likewise (frame 0's vca_h = 0 is part of the pooled values).  The model never
     reads them.
+    artifacts: None, or the first plane's blockiness / blur / noise records [n] (engine.ARTIFACTS_DTYPE) of the encoded stream:
+    the log then also carries blockiness, blur and noise, after vca_l and before vmaf, likewise.  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -354,6 +373,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         vca = np.asarray(vca).reshape(-1)
         names += ["vca_e", "vca_h", "vca_l"]
         cols += [vca[k].astype(np.float64) for k in ("e", "h", "l")]
+    if artifacts is not None:
+        artifacts = np.asarray(artifacts).reshape(-1)
+        names += ["blockiness", "blur", "noise"]
+        cols += [artifacts[k].astype(np.float64) for k in ("blockiness", "blur", "noise")]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -475,7 +498,7 @@ def _open_quality_stream(src, layout, height, width):
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
-                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False):
+                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -499,6 +522,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     turn it on).
     vca=True: likewise VCA's texture features of the REFERENCE stream (vca_e, vca_h, vca_l of the first plane; planar layouts
     only - bgr24 is a ValueError; a model file does not turn it on).
+    artifacts=True: likewise the no-reference blockiness, blur and noise of the ENCODED stream alone (blockiness, blur, noise of
+    the first plane; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -522,7 +547,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if vca:
             from .engine import check_vca_planes
             check_vca_planes(LAYOUTS[layout][0](h, w))
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca:
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -531,9 +556,11 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              psnr_hvs=bool(psnr_hvs), ciede=bool(ciede),
                                                              ciede_weights=ciede_weights, gmsd=bool(gmsd),
                                                              cambi=bool(cambi), xpsnr=bool(xpsnr),
-                                                             haarpsi=bool(haarpsi), vca=bool(vca)),
+                                                             haarpsi=bool(haarpsi), vca=bool(vca),
+                                                             artifacts=bool(artifacts)),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca)
+            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
+                               artifacts)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -571,11 +598,13 @@ MODE_KEYS = {
 
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
-                       cambi=False, xpsnr=False, haarpsi=False, vca=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA and the frame's CIEDE2000 of a pass (the
+                       cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise and the frame's CIEDE2000 of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = None
-    if vca:        # the tuple's last element, then HaarPSI's
+    rec = hvs = cie = gms = cam = xps = hps = vcs = art = None
+    if artifacts:  # the tuple's last element, then VCA's
+        art, q = q[-1][:, 0], q[:-1]
+    if vca:        # then HaarPSI's
         vcs, q = q[-1][:, 0], q[:-1]
     if haarpsi:    # then XPSNR's
         hps, q = q[-1][:, 0], q[:-1]
@@ -604,6 +633,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["haarpsi"] = hps
     if vcs is not None:
         more["vca"] = vcs
+    if art is not None:
+        more["artifacts"] = art
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -644,6 +675,8 @@ def _check_mode_keys(config):
         raise ValueError("haarpsi must be true or false.")
     if "vca" in config and not isinstance(config["vca"], bool):
         raise ValueError("vca must be true or false.")
+    if "artifacts" in config and not isinstance(config["artifacts"], bool):
+        raise ValueError("artifacts must be true or false.")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -703,6 +736,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         vca (true: the row gains VCA_E, VCA_H and VCA_L, the pooled means of the first plane's per-frame VCA texture energy, its
         temporal gradient - frame 0's 0 included - and brightness of the INPUT stream, after HAARPSI; planar pixfmts only; default
         false; a model file does not turn it on),
+        artifacts (true: the row gains BLOCKINESS, BLUR and NOISE, the pooled means of the first plane's per-frame no-reference
+        blockiness, blur and noise of the ENCODED stream, after VCA_L; default false; a model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -732,6 +767,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     xps = config.get("xpsnr", False)
     hps = config.get("haarpsi", False)
     vcs = config.get("vca", False)
+    art = config.get("artifacts", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -788,13 +824,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
                                                                      gmsd=gms, cambi=cam, xpsnr=xps,
-                                                                     haarpsi=hps, vca=vcs),
+                                                                     haarpsi=hps, vca=vcs, artifacts=art),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs)
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -866,6 +902,10 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["VCA_E"] = float(pooled["vca_e"]["mean"])
             metrics["VCA_H"] = float(pooled["vca_h"]["mean"])
             metrics["VCA_L"] = float(pooled["vca_l"]["mean"])
+        if "blockiness" in pooled:
+            metrics["BLOCKINESS"] = float(pooled["blockiness"]["mean"])
+            metrics["BLUR"] = float(pooled["blur"]["mean"])
+            metrics["NOISE"] = float(pooled["noise"]["mean"])
     return metrics
 
 
@@ -888,7 +928,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts;
     #                           and that a vmaf_model_path names a readable file
 
 
