@@ -363,6 +363,26 @@ typedef struct vqa_artifacts_metrics {
     double noise;           /* Immerkaer's sigma on the 8-bit scale                                                            */
 } vqa_artifacts_metrics;
 
+/* BRISQUE's natural-scene statistics of one plane (vqa_brisque_submit / vqa_brisque_wait; the definition is stated there).  The
+ * 60 words are the device's integer sums, so the same plane gives the same words at any place of any batch, from host or device
+ * memory; flags and features are formed from them on the host by vqa_brisque_wait.  First index: the scale (0: the plane, 1: its
+ * half); second index: the orientation H, V, D1, D2.                                                                        */
+typedef struct vqa_brisque_metrics {
+    uint64_t sum_abs_u[2];      /* sum |u| over the scale's samples, u = rint(m 2^16)                                          */
+    uint64_t sum_u2[2];         /* sum u^2                                                                                     */
+    uint64_t n_neg[2][4];       /* pairs whose exact product u_a u_b is negative                                               */
+    uint64_t n_pos[2][4];       /* pairs whose exact product is positive (a zero product is in neither)                        */
+    uint64_t sum_abs_p[2][4];   /* sum |p| over all pairs, |p| = (|u_a u_b| + 2^15) >> 16: the product's magnitude in 2^-16    */
+    uint64_t sq_neg_lo[2][4];   /* sum of (|p|^2 mod 2^32) over the negative pairs                                             */
+    uint64_t sq_neg_hi[2][4];   /* sum of (|p|^2 >> 32) over them: sum p^2 = sq_neg_hi 2^32 + sq_neg_lo, in 2^-32              */
+    uint64_t sq_pos_lo[2][4];   /* the same over the positive pairs                                                            */
+    uint64_t sq_pos_hi[2][4];
+    uint32_t flags;             /* bit 5 s + k: at scale s the fit k (0: GGD, 1..4: the AGGD of H, V, D1, D2) met a zero
+                                   denominator; its features are 0                                                            */
+    uint32_t reserved;          /* 0                                                                                           */
+    double features[36];        /* per scale 18: GGD alpha, sigma2; then per orientation alpha, mean, l^2, r^2                 */
+} vqa_brisque_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1058,6 +1078,74 @@ VQA_API int vqa_artifacts_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_ki
                                  const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_artifacts_wait(vqa_ctx *ctx, vqa_artifacts_metrics *out, int n_entries);
 
+/* ---- BRISQUE: the natural-scene statistics of ONE stream, 36 features per plane ----
+ * Mittal, Moorthy and Bovik, "No-reference image quality assessment in the spatial domain" (IEEE TIP 2012): the features every
+ * NR-IQA baseline is built on.  The definition follows the authors' brisque_feature.m, estimateggdparam.m and
+ * estimateaggdparam.m AS RECALLED; it is not pinned against their MATLAB nor against OpenCV's QualityBRISQUE.  The score (an
+ * epsilon-SVR over the rescaled features) is not part of this ABI; no model ships.
+ * Inputs   one to four planes, each measured by itself; x[H][W]: the RAW INTEGER SAMPLES of a plane at `depth` bits;
+ *          peak = 2^depth - 1, C = peak / 255 (the authors' constant 1 on the 8-bit scale: the field is the same at every depth).
+ * Scales   scale 0 is x; scale 1 is half(x), of ceil(H / 2) x ceil(W / 2) samples: MATLAB's imresize(x, 0.5) - bicubic with
+ *          antialiasing - of the SAMPLES.  Per axis output o takes the inputs 2 o - 3 .. 2 o + 4 with the weights
+ *          [-3, -9, 29, 111, 111, 29, -9, -3] / 256; an index outside 0 .. n - 1 is mirrored: aux = [0 .. n - 1, n - 1 .. 0],
+ *          index mod 2 n.  The filter is separable, so half(x) is an exact integer over 65536; it may be negative or above peak.
+ * MSCN     window w = g g^t / sum, g_k = exp(-k^2 / (2 (7/6)^2)), k = -3 .. 3 (the library applies g / sum g along rows, then
+ *          along columns).  mu = sum w x, s = sqrt(|sum w x^2 - mu^2|), ZERO outside the plane (filter2(.., 'same'));
+ *          m = (x - mu) / (s + C), in double; u = rint(m 2^16), ties to even: the one rounding.  Everything below is integer.
+ * Pairs    with wrap-around, as circshift does it (indices mod H, mod W):  H: m(i, j) m(i, j - 1);  V: m(i, j) m(i - 1, j);
+ *          D1: m(i, j) m(i - 1, j - 1);  D2: m(i, j) m(i + 1, j - 1).  A pair is CLASSED by the sign of the exact integer
+ *          product e = u_a u_b (negative, positive; e == 0 is in neither and adds nothing); its magnitude is then rounded to
+ *          2^-16: |p| = (|e| + 2^15) >> 16.
+ * Words    per scale: sum |u|, sum u^2; per orientation n_neg, n_pos, sum |p| over all pairs, and sum |p|^2 over the negative
+ *          and over the positive pairs, each as the sum of the squares' low 32 bits and the sum of the rest.  30 words a scale.
+ * GGD fit  N = the scale's sample count.  sigma2 = sum_u2 / 2^32 / N, E = sum_abs_u / 2^16 / N, rho = sigma2 / E^2;
+ *          alpha = the gam of the grid gam_k = (200 + k) / 1000, k = 0 .. 9800, that minimises
+ *          |rho - G(1/gam) G(3/gam) / G(2/gam)^2|, the first on a tie; the ratio is exp(lgamma(1/gam) + lgamma(3/gam) -
+ *          2 lgamma(2/gam)).  Features: alpha, sigma2.
+ * AGGD fit of an orientation: S- = sq_neg_hi 2^32 + sq_neg_lo and S+ likewise, exact integers rounded once to double;
+ *          l = sqrt(S- / 2^32 / n_neg), r = sqrt(S+ / 2^32 / n_pos), gh = l / r;
+ *          rhat = (sum_abs_p / 2^16 / N)^2 / ((S- + S+) / 2^32 / N);  rn = rhat (gh^3 + 1)(gh + 1) / (gh^2 + 1)^2;
+ *          alpha = the gam of the same grid that minimises (G(2/gam)^2 / (G(1/gam) G(3/gam)) - rn)^2, the first on a tie;
+ *          mean = (r - l) exp(lgamma(2/alpha) - lgamma(1/alpha)) exp((lgamma(1/alpha) - lgamma(3/alpha)) / 2).
+ *          Features: alpha, mean, l^2, r^2.
+ * Order    per scale GGD, H, V, D1, D2: 18 features, 36 in all.
+ * Degenerate  GGD: sum_abs_u == 0 (no non-zero m).  AGGD: n_neg == 0, n_pos == 0 or S+ == 0 (then r == 0, the divisor of gh).
+ *          The fit's features are 0 and bit 5 scale + fit of flags is set.  A plane of zeros gives 36 zeros and flags 0x3ff.
+ *          No NaN ever leaves the library.
+ * Ranges   |m| <= sqrt((1 - w0) / w0) = 2.742, w0 = 0.11740 the window's centre weight: with mu' the weighted mean of the
+ *          other 48 samples (zeros outside included), x - mu = (1 - w0)(x - mu') and, by the law of total variance,
+ *          sum w x^2 - mu^2 >= w0 (1 - w0)(x - mu')^2, so |x - mu| / s <= (1 - w0) / sqrt(w0 (1 - w0)); C > 0 only lowers it.
+ *          So |u| <= 2.742 * 2^16 < 2^18, u^2 < 7.52 * 2^32, and with H W <= 2^28 sum_u2 < 7.52 * 2^60 < 2^63 and
+ *          sum_abs_u < 2^46.  |p| <= 7.52 * 2^16 < 2^19, sum_abs_p < 2^47; |p|^2 < 2^38, whose sum could pass 2^63: its low
+ *          32 bits sum to less than 2^60 and the rest (< 2^6 a pair) to less than 2^34.  half(x): |v 65536| <= 304^2 * 65535
+ *          < 2^33, beyond 32 bits above 8-bit depth: the device holds it in a double, exactly.
+ * Accuracy the one rounding moves m by at most d = 2^-17; rounding |p| adds 2^-17.  Per sample m^2 moves by 2 |m| d + d^2, per
+ *          pair p by (|m_a| + |m_b|) d + d^2 + 2^-17 and p^2 by 2 |p| dp + dp^2.  Against the unrounded field, with E = mean |m|
+ *          and A = mean |p|: mean |m| within d = 7.7e-6; mean m^2 within 2 E d + d^2 <= 2 * 2.742 d + d^2 = 4.2e-5; mean |p|
+ *          within 2 E d + d^2 + 2^-17 <= 5.0e-5; sum p^2 / N of a class within 2 A 5.0e-5 + 2.5e-9 <= 7.5e-4.  A pair changes
+ *          class only if one of its m is within d of zero; its |p| is then below 2.742 d.  The moments are formed in double on
+ *          the device; what their own error moves m by is below 2e-9 at 16 bits (64 ulp of 65535^2 under (s + C)^2 >= 257^2).
+ * Limits   every plane at least 16 x 16 and H W <= 2^28 (the family's limits): VQA_ERR_UNSUPPORTED beyond either.
+ * The contract of vqa_cambi_submit: asynchronous, ONE stream, the same plane descriptors (one to four planes, each measured by
+ * itself; packed layouts through pixel_step), depths (one per submit, 8..16), alignment rules, memory kinds and failure
+ * guarantee: a failed submit leaves nothing in flight.  A batch of more than 32768 frames goes out in slices.  VQA_ERR_STATE
+ * while a BRISQUE batch is pending.  A BRISQUE batch is a batch of its own: it may be in flight next to a batch of every other
+ * kind of the same ctx (one upload then serves all), and each wait collects its own kind only - vqa_brisque_wait with only
+ * another kind pending, and another kind's wait with only a BRISQUE batch pending, are VQA_ERR_STATE and leave that batch
+ * pending.
+ * Kernels: per slice and group of same-geometry planes k_brisque_half (the exact scale-1 planes into scratch), then per scale
+ * k_brisque_mscn (a 64 x 16 tile and a 4 / 4 / 4 / 3 apron in LDS, both 7-tap moment passes in double, u, the pairs inside the
+ * plane, 64-bit integer atomics; the u of the first and last row and column go to four strips) and k_brisque_seam (the pairs
+ * that wrap around, corners included, from the strips).  Tiles start at the plane's origin, so u does not depend on the batch.
+ * vqa_brisque_wait forms flags and features on the host in double, contraction off, in the order written above; the two Gamma
+ * ratio tables (9801 entries) are built once from lgamma.  Scratch on the device: the 60 words per entry and as much pinned host
+ * memory; per frame of a slice the scale-1 planes (8 bytes a sample) and strips of the largest plane group; host frames are
+ * staged in the buffer of the second stream of a quality submit.  All of it is kept by the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_brisque_wait: n * n_planes entries, frame-major.                                                                */
+VQA_API int vqa_brisque_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                               const vqa_plane_desc *planes, int n_planes);
+VQA_API int vqa_brisque_wait(vqa_ctx *ctx, vqa_brisque_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1122,7 +1210,12 @@ enum vqa_kernel_id {
                                 being unknown); id 41 stays unnamed                                                      */
     VQA_K_ARTIFACTS = 42,    /* vqa_artifacts_submit: the boundary steps by phase, both blur sums and the Laplacian sum (one
                                 entry per group of same-geometry planes)                                                 */
-    VQA_K_STOP = 43          /* one past the last id: ... VQA_K_VCA_BLOCKS .. VQA_K_CLOSE - 1 and VQA_K_ARTIFACTS .. VQA_K_STOP - 1 */
+    VQA_K_STOP = 43,         /* one past VQA_K_ARTIFACTS, as the artefact measures shipped it (kept at 43 for callers and tests
+                                that rely on id 43 being unknown); id 43 stays unnamed                                   */
+    VQA_K_BRISQUE_HALF = 44, /* vqa_brisque_submit: the exact scale-1 planes (one entry per group of same-geometry planes)   */
+    VQA_K_BRISQUE_MSCN = 45, /* vqa_brisque_submit: the moments, u and the pairs inside the plane (two per group: the scales) */
+    VQA_K_BRISQUE_SEAM = 46, /* vqa_brisque_submit: the pairs that wrap around (two per group)                                */
+    VQA_K_EDGE = 47          /* one past the last id: ... VQA_K_ARTIFACTS .. VQA_K_STOP - 1 and VQA_K_BRISQUE_HALF .. VQA_K_EDGE - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -61,7 +61,9 @@ K_IDS_SHOWN = K_IDS_GIVEN + (K_HAARPSI,)          # the ids below K_FINIS (kept 
 K_VCA_BLOCKS, K_VCA_SUM, K_CLOSE = 39, 40, 41     # added beyond K_FINIS, which stays 38; id 38 is unnamed
 K_IDS_OPEN = K_IDS_SHOWN + (K_VCA_BLOCKS, K_VCA_SUM)   # the ids below K_CLOSE (kept as VCA shipped it)
 K_ARTIFACTS, K_STOP = 42, 43                      # added beyond K_CLOSE, which stays 41; id 41 is unnamed
-K_IDS_FULL = K_IDS_OPEN + (K_ARTIFACTS,)          # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_FULL = K_IDS_OPEN + (K_ARTIFACTS,)          # the ids below K_STOP (kept as the artefact measures shipped it)
+K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM, K_EDGE = 44, 45, 46, 47   # added beyond K_STOP, which stays 43; id 43 is unnamed
+K_IDS_WHOLE = K_IDS_FULL + (K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -85,6 +87,9 @@ XPSNR_MIN_DIM = 16   # vqa_xpsnr_submit: the limit of the family, whose planes i
 HAARPSI_MIN_DIM = 16   # vqa_haarpsi_submit: the limit of the family, whose planes it shares
 VCA_BLOCK = 32   # vqa_vca_submit: the side of a block, and of the smallest plane
 ARTIFACTS_MIN_DIM = 16   # vqa_artifacts_submit: the limit of the family, whose planes it shares
+BRISQUE_MIN_DIM = 16   # vqa_brisque_submit: the limit of the family, whose planes it shares
+BRISQUE_Q = 16         # vqa_brisque_metrics: u = rint(m 2^16)
+BRISQUE_FEATURES = 36
 HAARPSI_FIX = 1 << 30  # vqa_haarpsi_metrics: num is a sum of u wI with u = rint(2^30 sigmoid)
 HAARPSI_ALPHA = 4.2    # the paper's alpha
 CAMBI_SCALES = 5
@@ -187,6 +192,13 @@ class VqaArtifactsMetrics(C.Structure):
                 ("blur_v", C.c_double), ("blur", C.c_double), ("noise", C.c_double)]
 
 
+class VqaBrisqueMetrics(C.Structure):
+    _fields_ = [("sum_abs_u", C.c_uint64 * 2), ("sum_u2", C.c_uint64 * 2)] + \
+               [(k, (C.c_uint64 * 4) * 2) for k in ("n_neg", "n_pos", "sum_abs_p", "sq_neg_lo", "sq_neg_hi", "sq_pos_lo",
+                                                     "sq_pos_hi")] + \
+               [("flags", C.c_uint32), ("reserved", C.c_uint32), ("features", C.c_double * 36)]
+
+
 class VqaHaarpsiMetrics(C.Structure):
     _fields_ = [("den", C.c_uint64), ("num_lo", C.c_uint64), ("num_hi", C.c_uint64), ("similarity", C.c_double),
                 ("haarpsi", C.c_double)]
@@ -251,6 +263,8 @@ SIGNATURES = {
     "vqa_vca_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaVcaMetrics), C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
     "vqa_artifacts_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
     "vqa_artifacts_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaArtifactsMetrics), C.c_int]),
+    "vqa_brisque_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int]),
+    "vqa_brisque_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaBrisqueMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

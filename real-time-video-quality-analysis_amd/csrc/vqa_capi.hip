@@ -112,6 +112,10 @@ struct vqa_ctx {
     // vqa_artifacts_submit: the 21 integer words per entry (device, pinned host); host frames are staged in qstage_dist
     dbuf artifacts_acc;
     hbuf artifacts_host;
+    // vqa_brisque_submit: the 60 integer words per entry (device, pinned host), the scale-1 planes and strips of the largest
+    // plane group of a slice; host frames are staged in qstage_dist
+    dbuf brisque_acc, brisque_scratch;
+    hbuf brisque_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -148,6 +152,8 @@ struct vqa_ctx {
     int pend_t_planes = 0, pend_t_depth = 8, pend_t_w[4] = {0}, pend_t_h[4] = {0};
     int pend_r = 0;           // entries of the pending artefacts batch (likewise); its planes' sizes and depth, for the host's part
     int pend_r_planes = 0, pend_r_depth = 8, pend_r_w[4] = {0}, pend_r_h[4] = {0};
+    int pend_n = 0;           // entries of the pending BRISQUE batch (likewise); its planes' sizes, for the host's part
+    int pend_n_planes = 0, pend_n_w[4] = {0}, pend_n_h[4] = {0};
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -157,8 +163,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_STOP] = {0};
-    int64_t prof_n[VQA_K_STOP] = {0};
+    double prof_ms[VQA_K_EDGE] = {0};
+    int64_t prof_n[VQA_K_EDGE] = {0};
 };
 
 namespace {
@@ -231,7 +237,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -883,14 +889,14 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -1390,7 +1396,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the thirteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts) share: the checks, the staging of host frames, the walk over
+// What the fourteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -2474,6 +2480,75 @@ int vqa_artifacts_wait(vqa_ctx *c, vqa_artifacts_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// BRISQUE: one stream, every plane by itself.  A batch of its own (pend_n), ordered by the stream like a CAMBI batch, whose
+// host staging (qstage_dist, the buffer of the stream it measures in a one-pass run) it shares.
+static int brisque_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
+                               int n_planes, bool &touched)
+{
+    if (bad_batch_args(c, frames, frames, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (c->pend_n) return VQA_ERR_STATE;
+    plane_batch B;
+    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, BRISQUE_MIN_DIM); });
+    if (rc) return rc;
+    if (n > 1 && fs < B.span) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if (mem_kind == VQA_MEM_HOST && (rc = stage(c, c->qstage_dist, frames, (size_t)(n - 1) * fs + B.span))) return rc;
+    const size_t nent = (size_t)n * n_planes;
+    const size_t acc_bytes = sizeof(unsigned long long) * BRISQUE_WORDS * nent;
+    const size_t per_frame = largest_group_bytes(planes, n_planes, [](int cnt, int h, int w) { return brisque_scratch_bytes(cnt, h, w); });
+    if ((rc = ensure(c, c->brisque_acc, acc_bytes))) return rc;
+    if ((rc = ensure(c, c->brisque_scratch, per_frame * (size_t)slice_frames(c, n)))) return rc;
+    if ((rc = ensure_pinned(c, c->brisque_host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->brisque_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    // (launch_brisque's marks: one prof_scope per kernel id at a time, open between its begin and its end)
+    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
+    const brisque_mark mark = [](void *p, int id, int begin) {
+        marks *m = (marks *)p;
+        if (begin) m->open.emplace(m->c, id);
+        else m->open.reset();
+    };
+    for_each_slice(c, n, [&](int a0, int m) {
+        unsigned long long *acc = (unsigned long long *)c->brisque_acc.p + (size_t)a0 * n_planes * BRISQUE_WORDS;
+        const uint8_t *sfr = frames + (int64_t)a0 * fs;
+        for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
+            launch_brisque(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, c->brisque_scratch.p, acc, mark, &mk);
+        });
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->brisque_host.p, c->brisque_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_n = (int)nent;
+    c->pend_n_planes = n_planes;
+    for (int p = 0; p < n_planes; p++) { c->pend_n_w[p] = planes[p].width; c->pend_n_h[p] = planes[p].height; }
+    return VQA_OK;
+}
+
+int vqa_brisque_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
+                       int n_planes)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return brisque_submit_body(c, frames, mem_kind, n, fs, planes, n_planes, touched);
+    });
+}
+
+int vqa_brisque_wait(vqa_ctx *c, vqa_brisque_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_n || n_entries != c->pend_n) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->brisque_host.p;
+    for (int e = 0; e < n_entries; e++) {
+        const int p = e % c->pend_n_planes;
+        brisque_finalize(acc + (size_t)e * BRISQUE_WORDS, c->pend_n_h[p], c->pend_n_w[p], out + e);
+    }
+    c->pend_n = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2483,11 +2558,11 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_STOP || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_EDGE || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
-        (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS) || (id >= VQA_K_CLOSE && id < VQA_K_ARTIFACTS))
+        (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS) || (id >= VQA_K_CLOSE && id < VQA_K_ARTIFACTS) || (id >= VQA_K_STOP && id < VQA_K_BRISQUE_HALF))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2522,6 +2597,9 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_VCA_BLOCKS) return "k_vca_blocks";
     if (id == VQA_K_VCA_SUM) return "k_vca_sum";
     if (id == VQA_K_ARTIFACTS) return "k_artifacts";
+    if (id == VQA_K_BRISQUE_HALF) return "k_brisque_half";
+    if (id == VQA_K_BRISQUE_MSCN) return "k_brisque_mscn";
+    if (id == VQA_K_BRISQUE_SEAM) return "k_brisque_seam";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -477,4 +477,21 @@ void launch_artifacts(hipStream_t st, const uint8_t *frames, int n, int64_t fram
 // 21 words -> the record: the phases, blockiness, blur and noise of include/vqa.h in double, on the host
 void artifacts_finalize(const unsigned long long *words, int h, int w, int depth, vqa_artifacts_metrics *out);
 
+// BRISQUE's natural-scene statistics (vqa_brisque_submit): k_brisque.hip
+constexpr int BRISQUE_MIN_DIM = 16;                // the family's limit
+constexpr int BRISQUE_Q = 16;                      // u = rint(m 2^Q)
+constexpr int BRISQUE_WORDS = 60;                  // per (frame, plane): 30 per scale - sum |u|, sum u^2 and per orientation n_neg,
+                                                   // n_pos, sum |p|, sum p^2 over p < 0 (low 32 bits, the rest), over p > 0 (likewise)
+// bytes of scratch one frame of a group of `count` h x w planes needs: the scale-1 planes and the four strips
+size_t brisque_scratch_bytes(int count, int h, int w);
+// what launch_brisque calls around the launches of one kernel id, so that the caller can bracket them with that id's events
+typedef void (*brisque_mark)(void *ctx, int kernel_id, int begin);
+// the 60 integer sums of n frames of one group of same-geometry planes, added to acc[(frame * n_planes + plane) *
+// BRISQUE_WORDS ..], which the caller has zeroed; scratch: n * brisque_scratch_bytes(count, h, w)
+void launch_brisque(hipStream_t st, const uint8_t *frames, int n, int64_t frame_stride, const vqa_plane_desc *planes,
+                    const int *idx, int count, int n_planes, int depth, void *scratch, unsigned long long *acc,
+                    brisque_mark mark, void *mark_arg);
+// 60 words -> the record: the fits and the 36 features of include/vqa.h in double, on the host
+void brisque_finalize(const unsigned long long *words, int h, int w, vqa_brisque_metrics *out);
+
 } // namespace vqa

@@ -68,6 +68,11 @@ ARTIFACTS_DTYPE = np.dtype([("edge_h", np.uint64, (8,)), ("edge_v", np.uint64, (
                             ("blockiness_max", np.float64), ("blur_h", np.float64), ("blur_v", np.float64),
                             ("blur", np.float64), ("noise", np.float64)], align=True)
 assert ARTIFACTS_DTYPE.itemsize == C.sizeof(N.VqaArtifactsMetrics)
+BRISQUE_DTYPE = np.dtype([("sum_abs_u", np.uint64, (2,)), ("sum_u2", np.uint64, (2,))] +
+                         [(k, np.uint64, (2, 4)) for k in ("n_neg", "n_pos", "sum_abs_p", "sq_neg_lo", "sq_neg_hi",
+                                                          "sq_pos_lo", "sq_pos_hi")] +
+                         [("flags", np.uint32), ("reserved", np.uint32), ("features", np.float64, (36,))], align=True)
+assert BRISQUE_DTYPE.itemsize == C.sizeof(N.VqaBrisqueMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -83,6 +88,7 @@ _BATCHES = {
     "_pending_w": ("vqa_haarpsi_submit", "vqa_haarpsi_wait", HAARPSI_DTYPE, N.VqaHaarpsiMetrics),
     "_pending_t": ("vqa_vca_submit", "vqa_vca_wait", VCA_DTYPE, N.VqaVcaMetrics),   # (one stream and the frame before it)
     "_pending_r": ("vqa_artifacts_submit", "vqa_artifacts_wait", ARTIFACTS_DTYPE, N.VqaArtifactsMetrics),   # (one stream)
+    "_pending_n": ("vqa_brisque_submit", "vqa_brisque_wait", BRISQUE_DTYPE, N.VqaBrisqueMetrics),   # (one stream)
 }
 
 
@@ -329,7 +335,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -820,6 +826,24 @@ class Engine:
         self.artifacts_submit(frames, planes, frame_bytes)
         return self.artifacts_wait()
 
+    # ---- BRISQUE's natural-scene statistics ------------------------------------------
+    def brisque_submit(self, frames, planes, frame_bytes=None):
+        """BRISQUE's 36 natural-scene statistics for n frames of ONE stream (vqa_brisque_submit): the arguments of cambi_submit
+        - an array / DeviceFrames (uint16 above 8 bits; a dtype that does not match the depth is a ValueError) and the plane
+        tuples of quality_submit, every plane measured by itself and at least 16 x 16.  A batch of its own, like cambi_submit."""
+        streams = self._one_stream_args(frames, planes, frame_bytes)
+        self._batch_submit("_pending_n", streams, planes, n=streams[2])
+
+    def brisque_wait(self):
+        """-> [n, n_planes] records (BRISQUE_DTYPE): the 60 integer words ([scale] or [scale, orientation]), flags and
+        features [36] (include/vqa.h)."""
+        return self._batch_wait("_pending_n")
+
+    def brisque(self, frames, planes, frame_bytes=None):
+        """BRISQUE's features per plane for n frames; returns [n, n_planes] structured array (BRISQUE_DTYPE)."""
+        self.brisque_submit(frames, planes, frame_bytes)
+        return self.brisque_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -827,7 +851,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_FULL:
+        for k in N.K_IDS_WHOLE:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

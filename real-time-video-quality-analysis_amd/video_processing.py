@@ -296,8 +296,34 @@ def frame_artifacts(frames, layout="bgr24", height=None, width=None, engine=None
     return {k: r[k] for k in keys}, [(p[0], p[1]) for p in planes]
 
 
+def frame_brisque(frames, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame BRISQUE natural-scene statistics per plane of ONE stream (Engine.brisque through the one-pass pipeline of
+    frame_quality; the stream is uploaded once, there is no second stream).  The definition is include/vqa.h's: the MSCN field
+    and its four neighbour products at two scales, a GGD and four AGGD fits per scale - after Mittal, Moorthy and Bovik's
+    code as recalled, not pinned against it.
+    Returns (features [n, p, 36] float64, flags [n, p] uint32, plane sizes).  Every plane at least 16 x 16; packed bgr24 is
+    measured per channel."""
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, brisque="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    return np.ascontiguousarray(r["features"]), np.ascontiguousarray(r["flags"]), [(p[0], p[1]) for p in planes]
+
+
+def _brisque_model(model_path, range_path):
+    """the config's two paths -> a model or None; loaded before the pass starts, so a bad file costs no GPU time"""
+    if model_path is None:
+        if range_path is not None:
+            raise ValueError("brisque_range_path needs a brisque_model_path")
+        return None
+    from . import brisque_model
+    return brisque_model.load_model(model_path, range_path)
+
+
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
-                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None):
+                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -325,6 +351,9 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     reads them.
     artifacts: None, or the first plane's blockiness / blur / noise records [n] (engine.ARTIFACTS_DTYPE) of the encoded stream:
     the log then also carries blockiness, blur and noise, after vca_l and before vmaf, likewise.  The model never reads them.
+    brisque: None, or the first plane's BRISQUE records [n] (engine.BRISQUE_DTYPE) of the encoded stream: the log then also
+    carries brisque_00 .. brisque_35, after noise and before vmaf, likewise; with brisque_model (brisque_model.load_model) also
+    "brisque" = the model's score over them, after brisque_35.  The VMAF model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -377,6 +406,14 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         artifacts = np.asarray(artifacts).reshape(-1)
         names += ["blockiness", "blur", "noise"]
         cols += [artifacts[k].astype(np.float64) for k in ("blockiness", "blur", "noise")]
+    if brisque is not None:
+        feats = np.asarray(brisque).reshape(-1)["features"].astype(np.float64).reshape(-1, 36)
+        names += ["brisque_%02d" % k for k in range(36)]
+        cols += [feats[:, k] for k in range(36)]
+        if brisque_model is not None:
+            from . import brisque_model as bm
+            names += ["brisque"]
+            cols += [bm.predict(brisque_model, feats)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -498,7 +535,8 @@ def _open_quality_stream(src, layout, height, width):
 def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vmaf_log, vmaf_model_path=None,
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
-                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False):
+                       gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
+                       brisque_model_path=None, brisque_range_path=None):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -524,6 +562,9 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     only - bgr24 is a ValueError; a model file does not turn it on).
     artifacts=True: likewise the no-reference blockiness, blur and noise of the ENCODED stream alone (blockiness, blur, noise of
     the first plane; a model file does not turn it on).
+    brisque=True: likewise BRISQUE's 36 natural-scene statistics of the ENCODED stream alone (brisque_00 .. brisque_35 of the
+    first plane; a VMAF model file does not turn it on).  brisque_model_path (libsvm's text model) and brisque_range_path
+    (svm-scale's range file) turn it on and add "brisque", the score (brisque_model.py; loaded BEFORE the pass starts).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -532,6 +573,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         from . import vmaf_model
         model = vmaf_model.load_model(vmaf_model_path)
         vif = adm = motion = True
+    bmodel = _brisque_model(brisque_model_path, brisque_range_path)
+    brisque = bool(brisque) or bmodel is not None
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     dist, layout_d, _, _ = _open_quality_stream(distorted_video, layout, height, width)
     if layout_d != layout:
@@ -547,7 +590,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if vca:
             from .engine import check_vca_planes
             check_vca_planes(LAYOUTS[layout][0](h, w))
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts:
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -557,10 +600,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              ciede_weights=ciede_weights, gmsd=bool(gmsd),
                                                              cambi=bool(cambi), xpsnr=bool(xpsnr),
                                                              haarpsi=bool(haarpsi), vca=bool(vca),
-                                                             artifacts=bool(artifacts)),
+                                                             artifacts=bool(artifacts), brisque=brisque),
                               batch_size=batch_size, on_quality=wr, device=device)
             _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts)
+                               artifacts, brisque, bmodel)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -598,11 +641,13 @@ MODE_KEYS = {
 
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
-                       cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise and the frame's CIEDE2000 of a pass (the
+                       cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000 of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = art = None
-    if artifacts:  # the tuple's last element, then VCA's
+    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = None
+    if brisque:    # the tuple's last element, then the artefact measures'
+        bsq, q = q[-1][:, 0], q[:-1]
+    if artifacts:  # then VCA's
         art, q = q[-1][:, 0], q[:-1]
     if vca:        # then HaarPSI's
         vcs, q = q[-1][:, 0], q[:-1]
@@ -635,6 +680,9 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["vca"] = vcs
     if art is not None:
         more["artifacts"] = art
+    if bsq is not None:
+        more["brisque"] = bsq
+        more["brisque_model"] = brisque_model
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -677,6 +725,14 @@ def _check_mode_keys(config):
         raise ValueError("vca must be true or false.")
     if "artifacts" in config and not isinstance(config["artifacts"], bool):
         raise ValueError("artifacts must be true or false.")
+    if "brisque" in config and not isinstance(config["brisque"], bool):
+        raise ValueError("brisque must be true or false.")
+    for key in ("brisque_model_path", "brisque_range_path"):
+        bp = config.get(key)
+        if bp is not None and not (isinstance(bp, str) and os.path.isfile(bp) and os.access(bp, os.R_OK)):
+            raise ValueError("%s must be null or the path of a readable file." % key)
+    if config.get("brisque_range_path") is not None and config.get("brisque_model_path") is None:
+        raise ValueError("brisque_range_path needs a brisque_model_path.")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -738,6 +794,11 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         false; a model file does not turn it on),
         artifacts (true: the row gains BLOCKINESS, BLUR and NOISE, the pooled means of the first plane's per-frame no-reference
         blockiness, blur and noise of the ENCODED stream, after VCA_L; default false; a model file does not turn it on),
+        brisque (true: the row gains BRISQUE_ALPHA and BRISQUE_SIGMA2, the pooled means of features 0 and 1 - the GGD shape and
+        variance of the first plane's MSCN field at scale 0 - of the ENCODED stream, after NOISE; the log carries all 36 features;
+        default false; a VMAF model file does not turn it on), brisque_model_path and brisque_range_path (libsvm's text model and
+        svm-scale's range file, brisque_model.py: both turn brisque on, and the row gains BRISQUE, the pooled mean of the score,
+        after BRISQUE_SIGMA2; no model ships),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -768,6 +829,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     hps = config.get("haarpsi", False)
     vcs = config.get("vca", False)
     art = config.get("artifacts", False)
+    bmodel = _brisque_model(config.get("brisque_model_path"), config.get("brisque_range_path"))
+    bsq = bool(config.get("brisque", False)) or bmodel is not None
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -824,13 +887,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
                                                                      gmsd=gms, cambi=cam, xpsnr=xps,
-                                                                     haarpsi=hps, vca=vcs, artifacts=art),
+                                                                     haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art)
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -906,6 +969,11 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["BLOCKINESS"] = float(pooled["blockiness"]["mean"])
             metrics["BLUR"] = float(pooled["blur"]["mean"])
             metrics["NOISE"] = float(pooled["noise"]["mean"])
+        if "brisque_00" in pooled:
+            metrics["BRISQUE_ALPHA"] = float(pooled["brisque_00"]["mean"])
+            metrics["BRISQUE_SIGMA2"] = float(pooled["brisque_01"]["mean"])
+        if "brisque" in pooled:
+            metrics["BRISQUE"] = float(pooled["brisque"]["mean"])
     return metrics
 
 
@@ -928,7 +996,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path;
     #                           and that a vmaf_model_path names a readable file
 
 
