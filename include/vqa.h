@@ -383,6 +383,21 @@ typedef struct vqa_brisque_metrics {
     double features[36];        /* per scale 18: GGD alpha, sigma2; then per orientation alpha, mean, l^2, r^2                 */
 } vqa_brisque_metrics;
 
+/* MDSI of one frame pair, the planes of a pixel taken together (vqa_mdsi_submit / vqa_mdsi_wait; the definition and the bounds
+ * of the words are stated there).  The four words are the device's integer totals, so the same pair gives the same words at any
+ * place of any batch, from host or device memory; dev and mdsi are formed from them on the host by vqa_mdsi_wait.            */
+typedef struct vqa_mdsi_metrics {
+    uint64_t sum_pos; /* A: sum of zq = rint(|g 2^-24|^(1/4) 2^28) over the samples with g >= 0, g = rint(GCS 2^24)          */
+    uint64_t sum_neg; /* B: likewise over the samples with g < 0                                                            */
+    uint64_t n_neg;   /* the samples with g < 0                                                                             */
+    uint64_t sum_dev; /* D: sum of rint(|z - mean z| 2^28), z the complex quarter root in 2^-28 units                        */
+    int64_t count;    /* N = ceil(h / f) ceil(w / f)                                                                        */
+    int32_t factor;   /* f = max(1, floor(min(h, w) / 256 + 0.5))                                                           */
+    int32_t reserved; /* 0                                                                                                  */
+    double dev;       /* D / (N 2^28): the mean absolute deviation; exactly 0 for identical frames                          */
+    double mdsi;      /* dev^(1/4) as sqrt(sqrt(dev)); exactly 0 for identical frames                                       */
+} vqa_mdsi_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1146,6 +1161,80 @@ VQA_API int vqa_brisque_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind
                                const vqa_plane_desc *planes, int n_planes);
 VQA_API int vqa_brisque_wait(vqa_ctx *ctx, vqa_brisque_metrics *out, int n_entries);
 
+/* ---- MDSI (Nafchi, Shahkolaei, Hedjam and Cheriet, IEEE Access 2016): mean deviation similarity index ----
+ * Gradient similarity of the luminance, with the paper's fused-image term, plus a chromaticity similarity of two opponent
+ * channels, the three planes of a pixel taken together, pooled by a deviation.  0 means identical; larger is worse.  The metric
+ * is NOT symmetric in (ref, dist).  This is the authors' MDSI.m with the "sum" combination AS RECALLED: it is NOT pinned against
+ * their MATLAB nor against any Python port (neither was available).  Where this text and a tool differ, this text is what is
+ * built.  The paper's multiplicative combination is not built.
+ * A frame is THREE planes of one depth (8 bits, or 9..16 bits as uint16), or ONE plane; the RAW INTEGER SAMPLES are read as they
+ * are and nothing is clamped anywhere.  With s = 2^(depth - 8) and peak = 2^depth - 1 the planes give R, G, B on the 0..255 scale:
+ *   VQA_MDSI_YUV709  planes Y, U, V; the geometry rules and the chroma replication of vqa_ciede_submit exactly: the chroma sample
+ *             of luma (i, j) is (i >> sv, j >> sh); 4:4:4, 4:2:2, 4:2:0, odd sizes.
+ *               y = (Y - 16 s) / (219 s), u = (U - 128 s) / (224 s), v = (V - 128 s) / (224 s)
+ *               R = 255 (y + 1.5748 v), G = 255 (y - 0.1873 u - 0.4681 v), B = 255 (y + 1.8556 u)
+ *   VQA_MDSI_BGR     planes B, G, R of a common geometry (packed bgr24 through the pixel step); R = 255 R_int / peak, G, B likewise.
+ *   VQA_MDSI_GRAY    one plane Y: the YUV709 model with u = v = 0.
+ * Downsampling.  f = max(1, floor(min(h, w) / 256 + 0.5)) of plane 0 (MATLAB's round: 640 gives 3).  The grid is hd = ceil(h / f)
+ *   by wd = ceil(w / f).  Sample (i, j) of a downsampled channel is the sum of the channel over rows i f + o .. i f + o + f - 1, o =
+ *   floor(f / 2) - (f - 1), and the same columns, over f^2; a position outside the plane counts R = G = B = 0.  This is
+ *   conv2(x, ones(f) / f^2, 'same') kept at 1:f:end; for f = 2 it is vqa_gmsd_submit's 2x2 stage.
+ * Channels.  L = 0.2989 R + 0.5870 G + 0.1140 B, H = 0.30 R + 0.04 G - 0.35 B, M = 0.34 R - 0.60 G + 0.17 B.  All are affine in the
+ *   samples, so the device box-sums the INTEGER samples of each plane, S0, S1, S2, counts the in-plane positions of the window,
+ *   cnt (which carries the YUV offsets: the fill is a zero of R, G, B, not of Y, U, V), and applies one 3 x 4 double matrix:
+ *     rgb[c][0..2] = the coefficient of plane 0, 1, 2 in colour c (R, G, B): with ky = 255 / (219 s), kc = 255 / (224 s)
+ *       YUV709: R (ky, 0, 1.5748 kc), G (ky, -0.1873 kc, -0.4681 kc), B (ky, 1.8556 kc, 0); GRAY: (ky, 0, 0) for all three;
+ *       BGR, k = 255 / peak: R (0, 0, k), G (0, k, 0), B (k, 0, 0);
+ *     rgb[c][3] = -((o0 rgb[c][0] + o1 rgb[c][1]) + o1 rgb[c][2]), o0 = 16 s and o1 = 128 s (both 0 for BGR);
+ *     mat[ch][j] = ((a_R rgb[0][j] + a_G rgb[1][j]) + a_B rgb[2][j]) / (f f), (a_R, a_G, a_B) the row of channel ch above;
+ *     channel = ((mat[ch][0] S0 + mat[ch][1] S1) + mat[ch][2] S2) + mat[ch][3] cnt.
+ * Gradients.  Prewitt over 3, divided by 3, at every downsampled sample, L counting 0 outside the grid (vqa_gmsd_submit's
+ *   convention), with x(di, dj) = L(i + di, j + dj):
+ *     gx = (((x(-1,1) + x(0,1)) + x(1,1)) - ((x(-1,-1) + x(0,-1)) + x(1,-1))) / 3
+ *     gy = (((x(1,-1) + x(1,0)) + x(1,1)) - ((x(-1,-1) + x(-1,0)) + x(-1,1))) / 3
+ *   for the reference (r) and the distorted image (d); the fused image F = 0.5 (L_r + L_d) has, by linearity, the gradient
+ *   0.5 (g_r + g_d) per component, and that form is what is evaluated.  q_x = gx^2 + gy^2 (= m_x^2) for x in r, d, F.
+ * Similarities, C1 = 140, C2 = 55, C3 = 550 on the 8-bit scale (R, G, B are on it at any depth):
+ *     S(a, b, c) = (2 m_a m_b + c) / (m_a^2 + m_b^2 + c), evaluated as (2 sqrt(q_a q_b) + c) / ((q_a + q_b) + c)
+ *     GS = (S(r, d, C1) + S(d, F, C2)) - S(r, F, C2)
+ *     CS = (2 (H_r H_d + M_r M_d) + C3) / (((H_r^2 + H_d^2) + (M_r^2 + M_d^2)) + C3)
+ *     GCS = 0.6 GS + 0.4 CS, in (-1, 1.6)
+ *   Equal samples give S = CS = 1 and GCS = 1 exactly (sqrt(q q) = q, x + x = 2 x, 0.6 + 0.4 = 1 in IEEE double).
+ * Pooling.  z = GCS^(1/4), the principal complex root: |GCS|^(1/4) times 1 for GCS >= 0 and times (1 + i) / sqrt(2) for GCS < 0;
+ *   dev = mean |z - mean z| over the N = hd wd samples; mdsi = dev^(1/4).
+ * How the device forms it: everything up to GCS in double, contraction off, every step rounded once in the order written.
+ *   g = rint(GCS 2^24), a signed 32-bit integer, rounded ONCE; from here on everything is a function of g.
+ *   k_mdsi_map writes g to a scratch map and adds, as 64-bit integers, zq = rint(sqrt(sqrt(|g| 2^-24)) 2^28) into word A where
+ *   g >= 0 and into word B where g < 0, and the count n_neg.  k_mdsi_dev reads the map and the frame's A, B, forms the mean
+ *   (m_re, m_im) = (((double)A + (double)B r) / N, ((double)B r) / N), r = sqrt(0.5) as a double, in 2^-28 units and identically
+ *   in every thread, takes (re, im) = (zq, 0) for g >= 0 and (zq r, zq r) for g < 0, and adds
+ *   rint(sqrt((re - m_re)^2 + (im - m_im)^2)) into word D.  zq < 2^29 and N <= 2^28: no word can overflow.  Integer addition
+ *   is associative: the four words do not depend on the tiling, the batch or the order in which workgroups retire.
+ *   vqa_mdsi_wait forms dev = D / (N 2^28) and mdsi = sqrt(sqrt(dev)) in double, contraction off.  Identical inputs give g = 2^24
+ *   everywhere, so B = n_neg = D = 0 and dev = mdsi = 0.0 EXACTLY (a plain float64 evaluation leaves dev near 1e-16, which the
+ *   quarter power would turn into 1e-4: this is why the record carries dev).
+ * Limits: plane 0 at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.  n_planes other than 1 or 3, one plane
+ *   with a model other than VQA_MDSI_GRAY (or three with it), mixed depths, chroma geometries vqa_ciede_submit would refuse, an
+ *   unknown model: VQA_ERR_INVALID.
+ * The contract of vqa_ciede_submit: asynchronous, ONE ENTRY PER FRAME, the same plane descriptors, depths, alignment rules,
+ * memory kinds and failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while an MDSI batch is pending.
+ * An MDSI batch is a batch of its own: it may be in flight next to a batch of every other kind of the same ctx, and each wait
+ * collects its own kind only - vqa_mdsi_wait with only another kind pending, and another kind's wait with only an MDSI batch
+ * pending, are VQA_ERR_STATE and leave that batch pending.  A batch of more than 32768 frames goes out in slices.
+ * Kernels, one launch each per slice: k_mdsi_map (a workgroup owns a 64 x 32 tile of the downsampled grid and its apron of one
+ * sample; input rows are read coalesced and box-summed in LDS, one loop for every f; L_r, L_d of tile and apron in LDS as
+ * doubles, H and M in registers) and k_mdsi_dev.  Scratch on the device: 32 bytes per frame and the map, 4 bytes per
+ * downsampled sample per frame of a slice; host frames are staged in the buffers a quality submit uses.  All of it is kept by
+ * the ctx until vqa_trim / vqa_destroy.
+ * out of vqa_mdsi_wait: n entries (n_entries = n).                                                                         */
+enum vqa_mdsi_model { VQA_MDSI_YUV709 = 0, VQA_MDSI_BGR = 1, VQA_MDSI_GRAY = 2 };
+VQA_API int vqa_mdsi_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                            int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes,
+                            int model);
+VQA_API int vqa_mdsi_wait(vqa_ctx *ctx, vqa_mdsi_metrics *out, int n_entries);
+/* the downsampling factor f of an h x w plane 0, as stated above; needs no ctx and no device (0 when h or w is not positive) */
+VQA_API int vqa_mdsi_factor(int height, int width);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1215,7 +1304,12 @@ enum vqa_kernel_id {
     VQA_K_BRISQUE_HALF = 44, /* vqa_brisque_submit: the exact scale-1 planes (one entry per group of same-geometry planes)   */
     VQA_K_BRISQUE_MSCN = 45, /* vqa_brisque_submit: the moments, u and the pairs inside the plane (two per group: the scales) */
     VQA_K_BRISQUE_SEAM = 46, /* vqa_brisque_submit: the pairs that wrap around (two per group)                                */
-    VQA_K_EDGE = 47          /* one past the last id: ... VQA_K_ARTIFACTS .. VQA_K_STOP - 1 and VQA_K_BRISQUE_HALF .. VQA_K_EDGE - 1 */
+    VQA_K_EDGE = 47,         /* one past VQA_K_BRISQUE_SEAM, as BRISQUE shipped it (kept at 47 for callers and tests that rely on
+                                id 47 being unknown); id 47 stays unnamed                                                */
+    VQA_K_MDSI_MAP = 48,     /* vqa_mdsi_submit: the box sums, the channels, Prewitt, GCS, the map of g and the words A, B, n_neg
+                                (one entry per slice)                                                                    */
+    VQA_K_MDSI_DEV = 49,     /* vqa_mdsi_submit: the deviation word D from the map and the frame's A, B (one entry per slice) */
+    VQA_K_BRINK = 50         /* one past the last id: ... VQA_K_BRISQUE_HALF .. VQA_K_EDGE - 1 and VQA_K_MDSI_MAP .. VQA_K_BRINK - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -494,4 +494,24 @@ void launch_brisque(hipStream_t st, const uint8_t *frames, int n, int64_t frame_
 // 60 words -> the record: the fits and the 36 features of include/vqa.h in double, on the host
 void brisque_finalize(const unsigned long long *words, int h, int w, vqa_brisque_metrics *out);
 
+// MDSI (vqa_mdsi_submit): k_mdsi.hip
+constexpr int MDSI_MIN_DIM = 16;                   // the limit of plane 0 (the chroma planes of 4:2:0 may be 8 x 8)
+constexpr int MDSI_WORDS = 4;                      // per frame: A, B, n_neg, D (include/vqa.h)
+constexpr double MDSI_FIX_G = 16777216.0;          // 2^24: g = rint(GCS 2^24)
+constexpr double MDSI_FIX_Z = 268435456.0;         // 2^28: zq = rint(|g 2^-24|^(1/4) 2^28)
+// f = max(1, floor(min(h, w) / 256 + 0.5)), in integers
+int mdsi_factor(int h, int w);
+// bytes of scratch one frame needs: the map of g, 4 bytes per downsampled sample
+size_t mdsi_scratch_bytes(int h, int w);
+// the twelve doubles of include/vqa.h: mat[channel L, H, M][plane 0, 1, 2, count]
+void mdsi_matrix(int model, int depth, int f, double mat[3][4]);
+// the four words of n frame pairs (planes checked by the caller: one plane, or plane 0 the full grid and planes 1 and 2 of one
+// geometry, the grid's or its ceil-half in either direction), added to acc[frame * MDSI_WORDS ..], which the caller has zeroed;
+// map: n * mdsi_scratch_bytes(h, w).  mark brackets the launch of each kernel id, as launch_brisque's does
+void launch_mdsi(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                 int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes, int depth, int model, void *map,
+                 unsigned long long *acc, brisque_mark mark, void *mark_arg);
+// four words -> the record: dev and mdsi of include/vqa.h in double, on the host (h x w: plane 0)
+void mdsi_finalize(const unsigned long long *words, int h, int w, vqa_mdsi_metrics *out);
+
 } // namespace vqa

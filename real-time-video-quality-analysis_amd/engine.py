@@ -73,6 +73,10 @@ BRISQUE_DTYPE = np.dtype([("sum_abs_u", np.uint64, (2,)), ("sum_u2", np.uint64, 
                                                           "sq_pos_lo", "sq_pos_hi")] +
                          [("flags", np.uint32), ("reserved", np.uint32), ("features", np.float64, (36,))], align=True)
 assert BRISQUE_DTYPE.itemsize == C.sizeof(N.VqaBrisqueMetrics)
+MDSI_DTYPE = np.dtype([("sum_pos", np.uint64), ("sum_neg", np.uint64), ("n_neg", np.uint64), ("sum_dev", np.uint64),
+                       ("count", np.int64), ("factor", np.int32), ("reserved", np.int32), ("dev", np.float64),
+                       ("mdsi", np.float64)], align=True)
+assert MDSI_DTYPE.itemsize == C.sizeof(N.VqaMdsiMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -89,6 +93,7 @@ _BATCHES = {
     "_pending_t": ("vqa_vca_submit", "vqa_vca_wait", VCA_DTYPE, N.VqaVcaMetrics),   # (one stream and the frame before it)
     "_pending_r": ("vqa_artifacts_submit", "vqa_artifacts_wait", ARTIFACTS_DTYPE, N.VqaArtifactsMetrics),   # (one stream)
     "_pending_n": ("vqa_brisque_submit", "vqa_brisque_wait", BRISQUE_DTYPE, N.VqaBrisqueMetrics),   # (one stream)
+    "_pending_d": ("vqa_mdsi_submit", "vqa_mdsi_wait", MDSI_DTYPE, N.VqaMdsiMetrics),   # (one entry per frame)
 }
 
 
@@ -122,6 +127,12 @@ def check_vca_planes(planes):
 def vca_grid(width, height):
     """VCA's block grid of a width x height plane -> (nbx, nby): its whole 32 x 32 blocks"""
     return int(width) // N.VCA_BLOCK, int(height) // N.VCA_BLOCK
+
+
+def mdsi_factor(h, w):
+    """MDSI's downsampling factor of an h x w plane 0 as include/vqa.h states it: max(1, floor(min(h, w) / 256 + 0.5)) -
+    MATLAB's round, so 640 gives 3 - in integers"""
+    return max(1, (min(int(h), int(w)) + 128) // 256)
 
 
 def xpsnr_grid(width, height):
@@ -335,7 +346,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -472,7 +483,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -844,6 +855,38 @@ class Engine:
         self.brisque_submit(frames, planes, frame_bytes)
         return self.brisque_wait()
 
+    # ---- MDSI -------------------------------------------------------------------
+    @staticmethod
+    def mdsi_model(planes):
+        """the colour model a plane list implies: MDSI_GRAY for one plane, MDSI_BGR for three planes whose pixel step is 3
+        samples (packed bgr24 and its 16-bit kin), MDSI_YUV709 otherwise"""
+        if len(planes) == 1:
+            return N.MDSI_GRAY
+        bps = 2 if planes_depth(planes) > 8 else 1
+        return N.MDSI_BGR if len(planes) == 3 and all(int(p[4]) == 3 * bps for p in planes) else N.MDSI_YUV709
+
+    def mdsi_submit(self, ref, dist, planes, model=None, frame_bytes=None):
+        """MDSI for n frame pairs (vqa_mdsi_submit): the arrays / DeviceFrames and plane tuples of ciede_submit - THREE planes
+        taken together per pixel, Y, U, V (BT.709 limited range; U and V of the luma's size or its ceil-half in either direction)
+        or B, G, R - or ONE plane Y; plane 0 at least 16 x 16.  model: N.MDSI_YUV709 | N.MDSI_BGR | N.MDSI_GRAY | None
+        (mdsi_model(planes)).  (ref, dist) is ordered: the metric is not symmetric.  A batch of its own, like ciede_submit."""
+        if model is None:
+            model = self.mdsi_model(planes)
+        *args, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        st = self.lib.vqa_mdsi_submit(self.ctx, *args, plane_descs(planes), len(planes), int(model))
+        N.check(st, "vqa_mdsi_submit", self.ctx)
+        self._pending_d = (args[3], 1, keep)
+
+    def mdsi_wait(self):
+        """-> [n] records (MDSI_DTYPE), one per frame: the four integer words, count, factor, dev (the mean absolute deviation;
+        exactly 0 for identical frames) and mdsi = dev^(1/4)."""
+        return self._batch_wait("_pending_d").reshape(-1)
+
+    def mdsi(self, ref, dist, planes, model=None, frame_bytes=None):
+        """MDSI per frame for n frame pairs; returns [n] structured array (MDSI_DTYPE)."""
+        self.mdsi_submit(ref, dist, planes, model, frame_bytes)
+        return self.mdsi_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -851,7 +894,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_WHOLE:
+        for k in N.K_IDS_TOTAL:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -390,7 +390,7 @@ class Quality:
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
-                 haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False):
+                 haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -438,7 +438,11 @@ class Quality:
         brisque True: every chunk of the DISTORTED (encoded) stream also goes through the BRISQUE kernels
                 (Engine.brisque_submit) from the SAME upload; the pass's tuple then gains ONE further last element, after the
                 artefact measures': the records [n,p] (engine.BRISQUE_DTYPE); "only": no SSE / SSIM, and the pass reads the
-                `ref` stream alone, as a CAMBI-only pass does: give it the frames to measure"""
+                `ref` stream alone, as a CAMBI-only pass does: give it the frames to measure
+        mdsi    True: every chunk also goes through the MDSI kernels (Engine.mdsi_submit: one plane, or three taken together) from
+                the SAME upload; the pass's tuple then gains ONE further last element, after BRISQUE's: the MDSI records [n]
+                (engine.MDSI_DTYPE: the four integer words, count, factor, dev, mdsi - one per frame, not per plane); "only": no
+                SSE / SSIM.  The colour model follows from the planes (Engine.mdsi_model)"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -510,11 +514,18 @@ class Quality:
         if brisque == "only" and scales:
             raise ValueError("a brisque-only pass has no SSIM scales")
         self.brisque = brisque
+        if not (isinstance(mdsi, bool) or (isinstance(mdsi, str) and mdsi == "only")):
+            raise ValueError("mdsi must be False, True or 'only'")
+        if mdsi == "only" and scales:
+            raise ValueError("an MDSI-only pass has no SSIM scales")
+        if mdsi and len(planes) not in (1, 3):
+            raise ValueError("mdsi needs one plane or three")
+        self.mdsi = mdsi
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
                      ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only" and
-                     vca != "only" and artifacts != "only" and brisque != "only")
+                     vca != "only" and artifacts != "only" and brisque != "only" and mdsi != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -603,7 +614,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     (engine.ARTIFACTS_DTYPE) of the distorted stream; artifacts="only" leaves sse and ssim None as well and measures `ref`, the
     only stream it reads.  Quality(.., brisque=True) appends ONE further last element, after the artefact measures': the BRISQUE
     records [n,p] (engine.BRISQUE_DTYPE) of the distorted stream; brisque="only" leaves sse and ssim None as well and measures
-    `ref`, the only stream it reads.
+    `ref`, the only stream it reads.  Quality(.., mdsi=True) appends ONE further last element, after BRISQUE's: the MDSI records
+    [n] (engine.MDSI_DTYPE, one per frame); mdsi="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -684,6 +696,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.brisque:
             from .engine import BRISQUE_DTYPE
             q += (np.zeros((0, len(quality.planes)), BRISQUE_DTYPE),)
+        if quality.mdsi:
+            from .engine import MDSI_DTYPE
+            q += (np.zeros(0, MDSI_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -699,7 +714,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion, SI/TI, VCA, CAMBI, the artefact measures and BRISQUE alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and not quality.mdsi and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -807,7 +822,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_d"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -873,6 +888,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.brisque:     # likewise
                     eng.brisque_submit(pair[-1], quality.planes)
                     p["has_n"] = True
+                if quality.mdsi:
+                    eng.mdsi_submit(pair[0], pair[1], quality.planes)
+                    p["has_d"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -891,7 +909,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -925,6 +943,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["rres"] = eng.artifacts_wait()
             if p["has_n"]:
                 p["nres"] = eng.brisque_wait()
+            if p["has_d"]:
+                p["dres"] = eng.mdsi_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -969,6 +989,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 art.append(p.pop("rres"))
             if p["has_n"]:
                 bsq.append(p.pop("nres"))
+            if p["has_d"]:
+                mds.append(p.pop("dres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -1057,6 +1079,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(art),)
     if want_q and quality.brisque:
         q += (np.concatenate(bsq),)
+    if want_q and quality.mdsi:
+        q += (np.concatenate(mds),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

@@ -312,6 +312,26 @@ def frame_brisque(frames, layout="bgr24", height=None, width=None, engine=None, 
     return np.ascontiguousarray(r["features"]), np.ascontiguousarray(r["flags"]), [(p[0], p[1]) for p in planes]
 
 
+def frame_mdsi(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame MDSI, the mean deviation similarity index (Engine.mdsi through the one-pass pipeline of frame_quality; both
+    streams are uploaded once): the planes of a pixel taken together, by the definition in include/vqa.h - gradient similarity
+    of the luminance with the fused-image term, chromaticity similarity of two opponent channels, the mean absolute deviation of
+    the complex quarter power; bgr24 as B, G, R, the planar YUV layouts as BT.709 limited range with replicated chroma, gray as
+    luma alone - the authors' MDSI.m with the "sum" combination as recalled, not pinned against it.  (reference, encoded) is
+    ordered: the metric is not symmetric.
+    Returns (mdsi [n] float64 - exactly 0 for identical frames, larger is worse -, dev [n] float64, the deviation before the last
+    quarter power).  Plane 0 at least 16 x 16."""
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, mdsi="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    return np.ascontiguousarray(r["mdsi"]), np.ascontiguousarray(r["dev"])
+
+
 def _brisque_model(model_path, range_path):
     """the config's two paths -> a model or None; loaded before the pass starts, so a bad file costs no GPU time"""
     if model_path is None:
@@ -323,7 +343,7 @@ def _brisque_model(model_path, range_path):
 
 
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
-                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None):
+                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -354,6 +374,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     brisque: None, or the first plane's BRISQUE records [n] (engine.BRISQUE_DTYPE) of the encoded stream: the log then also
     carries brisque_00 .. brisque_35, after noise and before vmaf, likewise; with brisque_model (brisque_model.load_model) also
     "brisque" = the model's score over them, after brisque_35.  The VMAF model never reads them.
+    mdsi: None, or the MDSI records [n] (engine.MDSI_DTYPE, one per frame): the log then also carries mdsi, after the BRISQUE
+    keys and before vmaf, likewise.  The model never reads it.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -414,6 +436,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
             from . import brisque_model as bm
             names += ["brisque"]
             cols += [bm.predict(brisque_model, feats)]
+    if mdsi is not None:
+        mdsi = np.asarray(mdsi).reshape(-1)
+        names += ["mdsi"]
+        cols += [mdsi["mdsi"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -536,7 +562,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
                        gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
-                       brisque_model_path=None, brisque_range_path=None):
+                       brisque_model_path=None, brisque_range_path=None, mdsi=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -565,6 +591,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     brisque=True: likewise BRISQUE's 36 natural-scene statistics of the ENCODED stream alone (brisque_00 .. brisque_35 of the
     first plane; a VMAF model file does not turn it on).  brisque_model_path (libsvm's text model) and brisque_range_path
     (svm-scale's range file) turn it on and add "brisque", the score (brisque_model.py; loaded BEFORE the pass starts).
+    mdsi=True: likewise MDSI, the mean deviation similarity index of the planes taken together (mdsi, one value per frame; one-
+    or three-plane layouts; neither a VMAF nor a BRISQUE model file turns it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -590,7 +618,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if vca:
             from .engine import check_vca_planes
             check_vca_planes(LAYOUTS[layout][0](h, w))
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque:
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -600,10 +628,11 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              ciede_weights=ciede_weights, gmsd=bool(gmsd),
                                                              cambi=bool(cambi), xpsnr=bool(xpsnr),
                                                              haarpsi=bool(haarpsi), vca=bool(vca),
-                                                             artifacts=bool(artifacts), brisque=brisque),
+                                                             artifacts=bool(artifacts), brisque=brisque,
+                                                             mdsi=bool(mdsi)),
                               batch_size=batch_size, on_quality=wr, device=device)
             _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts, brisque, bmodel)
+                               artifacts, brisque, bmodel, mdsi)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -641,11 +670,14 @@ MODE_KEYS = {
 
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
-                       cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000 of a pass (the
+                       cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
+                       mdsi=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000 and MDSI of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = None
-    if brisque:    # the tuple's last element, then the artefact measures'
+    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = None
+    if mdsi:       # the tuple's last element, then BRISQUE's
+        mds, q = q[-1], q[:-1]
+    if brisque:    # then the artefact measures'
         bsq, q = q[-1][:, 0], q[:-1]
     if artifacts:  # then VCA's
         art, q = q[-1][:, 0], q[:-1]
@@ -683,6 +715,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
     if bsq is not None:
         more["brisque"] = bsq
         more["brisque_model"] = brisque_model
+    if mds is not None:
+        more["mdsi"] = mds
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -733,6 +767,8 @@ def _check_mode_keys(config):
             raise ValueError("%s must be null or the path of a readable file." % key)
     if config.get("brisque_range_path") is not None and config.get("brisque_model_path") is None:
         raise ValueError("brisque_range_path needs a brisque_model_path.")
+    if "mdsi" in config and not isinstance(config["mdsi"], bool):
+        raise ValueError("mdsi must be true or false.")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -799,6 +835,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         default false; a VMAF model file does not turn it on), brisque_model_path and brisque_range_path (libsvm's text model and
         svm-scale's range file, brisque_model.py: both turn brisque on, and the row gains BRISQUE, the pooled mean of the score,
         after BRISQUE_SIGMA2; no model ships),
+        mdsi (true: the row gains MDSI, the pooled mean of the per-frame mean deviation similarity index of the planes taken
+        together - 0 for identical frames, larger is worse -, after the BRISQUE columns; one- or three-plane pixfmts; default
+        false; a model file does not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -831,6 +870,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     art = config.get("artifacts", False)
     bmodel = _brisque_model(config.get("brisque_model_path"), config.get("brisque_range_path"))
     bsq = bool(config.get("brisque", False)) or bmodel is not None
+    mds = config.get("mdsi", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -887,13 +927,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
             _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
                                                                      gmsd=gms, cambi=cam, xpsnr=xps,
-                                                                     haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq),
+                                                                     haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq,
+                                                                     mdsi=mds),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq:
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel)
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds:
+            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
+                               mds)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -974,6 +1016,8 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["BRISQUE_SIGMA2"] = float(pooled["brisque_01"]["mean"])
         if "brisque" in pooled:
             metrics["BRISQUE"] = float(pooled["brisque"]["mean"])
+        if "mdsi" in pooled:
+            metrics["MDSI"] = float(pooled["mdsi"]["mean"])
     return metrics
 
 
@@ -996,7 +1040,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi;
     #                           and that a vmaf_model_path names a readable file
 
 
