@@ -1,5 +1,8 @@
-"""The four plane-batch submits (quality, VIF, ADM, motion) answer the shared bad inputs with the same status, in the same
-order of precedence, and a refused submit leaves the ctx idle and usable.  One table, driven through the C ABI.
+"""The plane-batch submits whose arguments are those of VIF or of motion (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, GMSD,
+HaarPSI) answer the shared bad inputs with the same status, in the same order of precedence, and a refused submit leaves the ctx
+idle and usable.  One table, driven through the C ABI.  (The other kinds take further arguments - a colour model, a prev0 beside
+the pair, one stream, a block map at the wait - and have their refusals in their own files; tests/test_gpu_all_kinds.py has all
+sixteen kinds pending at once.)
 
 Order of the checks (include/vqa.h states the rules; the order is behaviour): arguments, mem_kind, [quality: ssim_mode],
 a pending batch of the same kind, then per plane in plane order - depth, 16-bit alignment, geometry (INVALID), the metric's
@@ -31,6 +34,10 @@ METRICS = {
     "vif": ("vqa_vif_submit", "vqa_vif_wait", N.VqaVifMetrics, N.VIF_MIN_DIM, True),
     "adm": ("vqa_adm_submit", "vqa_adm_wait", N.VqaAdmMetrics, N.ADM_MIN_DIM, True),
     "motion": ("vqa_motion_submit", "vqa_motion_wait", N.VqaMotionMetrics, N.MOTION_MIN_DIM, False),
+    "siti": ("vqa_siti_submit", "vqa_siti_wait", N.VqaSitiMetrics, N.SITI_MIN_DIM, False),
+    "psnr_hvs": ("vqa_psnr_hvs_submit", "vqa_psnr_hvs_wait", N.VqaPsnrHvsMetrics, N.PSNR_HVS_MIN_DIM, True),
+    "gmsd": ("vqa_gmsd_submit", "vqa_gmsd_wait", N.VqaGmsdMetrics, N.GMSD_MIN_DIM, True),
+    "haarpsi": ("vqa_haarpsi_submit", "vqa_haarpsi_wait", N.VqaHaarpsiMetrics, N.HAARPSI_MIN_DIM, True),
 }
 
 
@@ -91,7 +98,7 @@ def _idle_and_usable(eng, metric, good, want):
 BASE8, BASE16 = Call(8), Call(10)
 BIG = 1 << 14
 
-# name -> (the call as a function of the metric's smallest plane side, the status every one of the four submits gives)
+# name -> (the call as a function of the metric's smallest plane side, the status every one of the submits gives)
 CASES = {
     # arguments
     "null ctx": (lambda m: BASE8.with_(ctx=False), INVALID),
