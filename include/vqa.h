@@ -398,6 +398,18 @@ typedef struct vqa_mdsi_metrics {
     double mdsi;      /* dev^(1/4) as sqrt(sqrt(dev)); exactly 0 for identical frames                                       */
 } vqa_mdsi_metrics;
 
+/* dE_ITP (ITU-R BT.2124) of one frame pair, the three planes of a pixel taken together (vqa_itp_submit / vqa_itp_wait; the
+ * definition and the bounds of the words are stated there).  The two words are the device's integer totals, so the same pair
+ * gives the same words at any place of any batch, from host or device memory; the doubles are formed from them on the host by
+ * vqa_itp_wait.                                                                                                             */
+typedef struct vqa_itp_metrics {
+    uint64_t sum_q;   /* the sum over the luma grid of q = rint(dE_ITP 2^20), a pixel's difference in 2^-20 units               */
+    uint64_t max_q;   /* the largest q of the frame                                                                         */
+    double de_sum;    /* sum_q 2^-20                                                                                        */
+    double de_mean;   /* de_sum / (h w): the mean dE_ITP; exactly 0 for identical frames                                    */
+    double de_max;    /* max_q 2^-20: the largest dE_ITP of a pixel                                                         */
+} vqa_itp_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1235,6 +1247,74 @@ VQA_API int vqa_mdsi_wait(vqa_ctx *ctx, vqa_mdsi_metrics *out, int n_entries);
 /* the downsampling factor f of an h x w plane 0, as stated above; needs no ctx and no device (0 when h or w is not positive) */
 VQA_API int vqa_mdsi_factor(int height, int width);
 
+/* ---- dE_ITP (Recommendation ITU-R BT.2124-0, 2019): the colour difference for HDR and wide-gamut video, three planes jointly ----
+ * CIEDE2000 above reads every input as BT.709 / sRGB against a 100 cd/m2 white.  This one reads a BT.2020 signal with the PQ or
+ * the HLG transfer function of BT.2100, turns the three samples of a pixel of either image into display light and then into
+ * ICtCp, and takes the Euclidean distance of the two colours, scaled so that 1 is about one just-noticeable difference.
+ * Everything below is the Recommendations' text, constant for constant.  A transfer function and a range travel with the call.
+ * A frame is THREE planes of one depth (8 bits, or 9..16 bits as uint16), the RAW INTEGER SAMPLES read as they are.  With
+ * s = 2^(depth - 8) and P = 2^depth - 1:
+ * Colour model (`model`):
+ *   VQA_ITP_YUV2020   planes Y, Cb, Cr; the geometry rules and the chroma replication of vqa_ciede_submit exactly: Cb and Cr
+ *             share one geometry, the luma's or its ceil-half in each direction independently (4:4:4, 4:2:2, 4:2:0, odd sizes),
+ *             and the chroma sample of luma (i, j) is (i >> sv, j >> sh).
+ *               full_range = 0 (limited):  y = (Y - 16 s) / (219 s), cb = (Cb - 128 s) / (224 s), cr = (Cr - 128 s) / (224 s)
+ *               full_range = 1:            y = Y / P, cb = (Cb - 2^(depth - 1)) / P, cr = (Cr - 2^(depth - 1)) / P
+ *             BT.2020 non-constant luminance, Kr = 0.2627, Kb = 0.0593, Kg = 0.6780:
+ *               R' = y + 1.4746 cr, B' = y + 1.8814 cb, G' = ((y - Kr R') - Kb B') / Kg
+ *   VQA_ITP_BGR       planes B, G, R of a common geometry (any pixel step: packed bgr24 has step 3); R' = R / P, G' and B'
+ *             likewise; full_range is ignored (but must be 0 or 1).
+ * Clamp.  R', G', B' are CLAMPED to [0, 1].  This is deliberate and differs from CIEDE2000's "no clamping anywhere": the PQ
+ *   EOTF has a pole at E'^(1/m2) = c2 / c3, which is E' near 1.99, unclamped limited-range input reaches R' near 1.94, and a
+ *   display shows nothing outside [0, 1].
+ * Transfer (`transfer`): the signal E' of a channel -> display light Fd in cd/m2.
+ *   VQA_ITP_PQ    Fd = 10000 (max(E'^(1/m2) - c1, 0) / (c2 - c3 E'^(1/m2)))^(1/m1),
+ *             m1 = 2610 / 16384, m2 = 2523 / 4096 * 128, c1 = 3424 / 4096, c2 = 2413 / 4096 * 32, c3 = 2392 / 4096 * 32.
+ *   VQA_ITP_HLG   scene light E = E'^2 / 3 for E' <= 1 / 2, otherwise (exp((E' - c) / a) + b) / 12,
+ *             a = 0.17883277, b = 0.28466892, c = 0.55991073; then the BT.2100 OOTF of a 1000 cd/m2 display (gamma 1.2, black
+ *             level 0): Ys = (0.2627 E_R + 0.6780 E_G) + 0.0593 E_B, Fd_ch = (1000 Ys^0.2) E_ch; Ys = 0 gives 0.
+ * ICtCp (BT.2100, the PQ form, for both transfers), on Fd:
+ *   L = ((1688 R + 2146 G) + 262 B) / 4096, M = ((683 R + 2951 G) + 462 B) / 4096, S = ((99 R + 309 G) + 3688 B) / 4096
+ *   X' = ((c1 + c2 Yn^m1) / (1 + c3 Yn^m1))^m2 with Yn = X / 10000, for X = L, M, S
+ *   I = 0.5 (L' + M'), Ct = ((6610 L' - 13613 M') + 7003 S') / 4096, Cp = ((17933 L' - 17390 M') - 543 S') / 4096
+ * BT.2124: T = 0.5 Ct and dE_ITP = 720 sqrt((dI^2 + dT^2) + dCp^2), the differences taken between the two images.
+ *   A pair of triples with equal integer samples gives EXACTLY 0 (the kernel tests for it).
+ * Bound.  L', M', S' lie in [0, 1] (Fd in [0, 10000] by the clamp, and the inverse EOTF maps that onto [c1^m2, 1] within [0, 1]), so
+ *   |dI| <= 1; Ct lies between -13613 / 4096 and (6610 + 7003) / 4096 = 13613 / 4096, so |dT| = |dCt| / 2 <= 13613 / 4096 < 3.3236;
+ *   Cp lies between -(17390 + 543) / 4096 and 17933 / 4096, so |dCp| <= 2 * 17933 / 4096 < 8.7564.  Hence
+ *   dE <= 720 sqrt(1 + 3.3236^2 + 8.7564^2) < 720 * 9.42 < 6800 < 2^13.  A pixel's q = rint(dE 2^20) stays below 2^33 and a frame
+ *   of h w <= 2^28 pixels below 2^61: no word can overflow and NO SATURATION CONSTANT is needed.
+ * Results, ONE ENTRY PER FRAME (not per plane): sum_q, the sum of q over the luma grid, and max_q, the largest q;
+ *   de_sum = sum_q 2^-20, de_mean = de_sum / (h w), de_max = max_q 2^-20.
+ * How the device forms it:
+ *   arithmetic per pixel is DOUBLE with contraction off, every step rounded once in the order written above; the powers and the
+ *   exponential are the accurate library functions.  (fp32 is not enough: E'^(1/m2) - c1 cancels on dark pixels and the 6.28th
+ *   power multiplies what is left - up to 0.1 per pixel and 7e-4 on a frame's mean.)
+ *   sums      BATCH-INVARIANT BITS: q is added as a 64-bit integer and the maximum taken as one: two words per frame, whatever
+ *             the tiling and the order in which workgroups retire.  The rounding moves de_mean and de_max by at most half a
+ *             quantum: 2^-21.
+ *   host      the words -> double, times 2^-20, over h w: in vqa_itp_wait, in double, with contraction off.
+ * Limits: luma at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.  n_planes other than 3, Cb and Cr (or
+ * B, G, R) geometries that differ, a chroma size that is neither the luma's nor its ceil-half, mixed depths, an unknown
+ * model or transfer, a full_range other than 0 or 1: VQA_ERR_INVALID.
+ * The contract of vqa_ciede_submit: asynchronous, ONE ENTRY PER FRAME, the same plane descriptors, depths, alignment rules,
+ * memory kinds and failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while a dE_ITP batch is pending.
+ * A dE_ITP batch is a batch of its own: it may be in flight next to a batch of every other kind of the same ctx, and each wait
+ * collects its own kind only - vqa_itp_wait with only another kind pending, and another kind's wait with only a dE_ITP batch
+ * pending, are VQA_ERR_STATE and leave that batch pending.  A batch of more than 32768 frames goes out in slices.
+ * One fused kernel per slice, k_itp: a thread owns a 2 x 4 luma patch of both images, as in k_ciede; only the two words per
+ * frame leave the kernel.  Scratch on the device: 16 bytes per frame; host frames are staged in the buffers vqa_ciede_submit
+ * uses.  All of it is kept by the ctx until vqa_trim / vqa_destroy.
+ * Not built: ICtCp-coded input planes, constant-luminance BT.2020, HLG display peaks other than 1000 cd/m2, chroma
+ * interpolation other than replication.
+ * out of vqa_itp_wait: n entries (n_entries = n).                                                                          */
+enum vqa_itp_model { VQA_ITP_YUV2020 = 0, VQA_ITP_BGR = 1 };
+enum vqa_itp_transfer { VQA_ITP_PQ = 0, VQA_ITP_HLG = 1 };
+VQA_API int vqa_itp_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                           int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes,
+                           int model, int transfer, int full_range);
+VQA_API int vqa_itp_wait(vqa_ctx *ctx, vqa_itp_metrics *out, int n_entries);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1309,7 +1389,11 @@ enum vqa_kernel_id {
     VQA_K_MDSI_MAP = 48,     /* vqa_mdsi_submit: the box sums, the channels, Prewitt, GCS, the map of g and the words A, B, n_neg
                                 (one entry per slice)                                                                    */
     VQA_K_MDSI_DEV = 49,     /* vqa_mdsi_submit: the deviation word D from the map and the frame's A, B (one entry per slice) */
-    VQA_K_BRINK = 50         /* one past the last id: ... VQA_K_BRISQUE_HALF .. VQA_K_EDGE - 1 and VQA_K_MDSI_MAP .. VQA_K_BRINK - 1 */
+    VQA_K_BRINK = 50,        /* one past VQA_K_MDSI_DEV, as MDSI shipped it (kept at 50 for callers and tests that rely on id 50
+                                being unknown); id 50 stays unnamed                                                      */
+    VQA_K_ITP = 51,          /* vqa_itp_submit: both ICtCp conversions, dE_ITP, the fixed-point sum and maximum (one entry per
+                                slice)                                                                                   */
+    VQA_K_VERGE = 52         /* one past the last id: ... VQA_K_MDSI_MAP .. VQA_K_BRINK - 1 and VQA_K_ITP .. VQA_K_VERGE - 1  */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -65,7 +65,9 @@ K_IDS_FULL = K_IDS_OPEN + (K_ARTIFACTS,)          # the ids below K_STOP (kept a
 K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM, K_EDGE = 44, 45, 46, 47   # added beyond K_STOP, which stays 43; id 43 is unnamed
 K_IDS_WHOLE = K_IDS_FULL + (K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM)   # the ids below K_EDGE (kept as BRISQUE shipped it)
 K_MDSI_MAP, K_MDSI_DEV, K_BRINK = 48, 49, 50      # added beyond K_EDGE, which stays 47; id 47 is unnamed
-K_IDS_TOTAL = K_IDS_WHOLE + (K_MDSI_MAP, K_MDSI_DEV)   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_TOTAL = K_IDS_WHOLE + (K_MDSI_MAP, K_MDSI_DEV)   # the ids below K_BRINK (kept as MDSI shipped it)
+K_ITP, K_VERGE = 51, 52                           # added beyond K_BRINK, which stays 50; id 50 is unnamed
+K_IDS_SUM = K_IDS_TOTAL + (K_ITP,)                # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -96,6 +98,11 @@ MDSI_MIN_DIM = 16   # vqa_mdsi_submit: plane 0's limit (the chroma planes of 4:2
 MDSI_YUV709, MDSI_BGR, MDSI_GRAY = 0, 1, 2   # vqa_mdsi_submit's colour models
 MDSI_FIX_G = 1 << 24  # vqa_mdsi_metrics: g = rint(GCS 2^24)
 MDSI_FIX_Z = 1 << 28  # vqa_mdsi_metrics: the words are sums in 2^-28 units
+ITP_MIN_DIM = 16   # vqa_itp_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+ITP_YUV2020, ITP_BGR = 0, 1   # vqa_itp_submit's colour models
+ITP_PQ, ITP_HLG = 0, 1        # vqa_itp_submit's transfer functions
+ITP_TRANSFERS = {"pq": ITP_PQ, "hlg": ITP_HLG}
+ITP_FIX = 1 << 20  # vqa_itp_metrics: q = rint(dE_ITP 2^20)
 HAARPSI_FIX = 1 << 30  # vqa_haarpsi_metrics: num is a sum of u wI with u = rint(2^30 sigmoid)
 HAARPSI_ALPHA = 4.2    # the paper's alpha
 CAMBI_SCALES = 5
@@ -210,6 +217,11 @@ class VqaMdsiMetrics(C.Structure):
                 ("count", C.c_int64), ("factor", C.c_int32), ("reserved", C.c_int32), ("dev", C.c_double), ("mdsi", C.c_double)]
 
 
+class VqaItpMetrics(C.Structure):
+    _fields_ = [("sum_q", C.c_uint64), ("max_q", C.c_uint64), ("de_sum", C.c_double), ("de_mean", C.c_double),
+                ("de_max", C.c_double)]
+
+
 class VqaHaarpsiMetrics(C.Structure):
     _fields_ = [("den", C.c_uint64), ("num_lo", C.c_uint64), ("num_hi", C.c_uint64), ("similarity", C.c_double),
                 ("haarpsi", C.c_double)]
@@ -280,6 +292,9 @@ SIGNATURES = {
                                   C.c_int]),
     "vqa_mdsi_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaMdsiMetrics), C.c_int]),
     "vqa_mdsi_factor": (C.c_int, [C.c_int, C.c_int]),
+    "vqa_itp_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
+                                 C.c_int, C.c_int, C.c_int]),
+    "vqa_itp_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaItpMetrics), C.c_int]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -120,6 +120,9 @@ struct vqa_ctx {
     // staged in qstage_*
     dbuf mdsi_acc, mdsi_map;
     hbuf mdsi_host;
+    // vqa_itp_submit: the two integer words per frame (device, pinned host); host frames are staged in qstage_*
+    dbuf itp_acc;
+    hbuf itp_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -160,6 +163,8 @@ struct vqa_ctx {
     int pend_n_planes = 0, pend_n_w[4] = {0}, pend_n_h[4] = {0};
     int pend_d = 0;           // frames of the pending MDSI batch (likewise); its plane 0, for the host's part
     int pend_d_w = 0, pend_d_h = 0;
+    int pend_i = 0;           // frames of the pending dE_ITP batch (likewise); its luma grid, for the host's mean
+    int pend_i_w = 0, pend_i_h = 0;
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -169,8 +174,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_BRINK] = {0};
-    int64_t prof_n[VQA_K_BRINK] = {0};
+    double prof_ms[VQA_K_VERGE] = {0};
+    int64_t prof_n[VQA_K_VERGE] = {0};
 };
 
 namespace {
@@ -243,7 +248,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d || c->pend_i; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -895,14 +900,14 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->itp_acc, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host, &c->itp_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -1402,7 +1407,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the fifteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI) share: the checks, the staging of host frames, the walk over
+// What the sixteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI, dE_ITP) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -1461,7 +1466,7 @@ static int stage(vqa_ctx *c, dbuf &buf, const uint8_t *&frames, size_t bytes)
     return VQA_OK;
 }
 
-// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI or an MDSI submit.  The nine share qstage_*: the stream orders a batch behind
+// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI, an MDSI or a dE_ITP submit.  The ten share qstage_*: the stream orders a batch behind
 // whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
 static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs, const uint8_t *&dist,
                       int64_t dist_fs)
@@ -2636,6 +2641,75 @@ int vqa_mdsi_wait(vqa_ctx *c, vqa_mdsi_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// dE_ITP: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own (pend_i), ordered by the
+// stream like a CIEDE2000 batch, whose host staging (qstage_*) and geometry rules it shares.
+static int itp_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                           int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int model, int transfer, int full_range,
+                           bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (n_planes != 3 || (model != VQA_ITP_YUV2020 && model != VQA_ITP_BGR)) return VQA_ERR_INVALID;
+    if ((transfer != VQA_ITP_PQ && transfer != VQA_ITP_HLG) || (full_range != 0 && full_range != 1)) return VQA_ERR_INVALID;
+    if (c->pend_i) return VQA_ERR_STATE;
+    plane_batch B;
+    // the size limits are the luma grid's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
+    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
+        return &d == planes ? side_and_area_limits(d, ITP_MIN_DIM) : (int)VQA_OK;
+    });
+    if (rc) return rc;
+    const vqa_plane_desc &y = planes[0], &u = planes[1], &v = planes[2];
+    if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
+        return VQA_ERR_INVALID;
+    if (model == VQA_ITP_BGR) {
+        if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
+            return VQA_ERR_INVALID;
+    } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
+        return VQA_ERR_INVALID;
+    }
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    const size_t acc_bytes = sizeof(unsigned long long) * ITP_WORDS * (size_t)n;
+    if ((rc = ensure(c, c->itp_acc, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, c->itp_host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->itp_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    for_each_slice(c, n, [&](int a0, int m) {
+        prof_scope ps_(c, VQA_K_ITP);
+        launch_itp(st, ref + (int64_t)a0 * ref_fs, dist + (int64_t)a0 * dist_fs, m, ref_fs, dist_fs, planes, depth, model, transfer,
+                   full_range, (unsigned long long *)c->itp_acc.p + (size_t)a0 * ITP_WORDS);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->itp_host.p, c->itp_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_i = n;
+    c->pend_i_w = y.width;
+    c->pend_i_h = y.height;
+    return VQA_OK;
+}
+
+int vqa_itp_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
+                   const vqa_plane_desc *planes, int n_planes, int model, int transfer, int full_range)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return itp_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, model, transfer, full_range, touched);
+    });
+}
+
+int vqa_itp_wait(vqa_ctx *c, vqa_itp_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_i || n_entries != c->pend_i) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->itp_host.p;
+    for (int e = 0; e < n_entries; e++) itp_finalize(acc + (size_t)e * ITP_WORDS, c->pend_i_h, c->pend_i_w, out + e);
+    c->pend_i = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2645,12 +2719,12 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_BRINK || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_VERGE || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
         (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS) || (id >= VQA_K_CLOSE && id < VQA_K_ARTIFACTS) || (id >= VQA_K_STOP && id < VQA_K_BRISQUE_HALF) ||
-        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP))
+        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP) || (id >= VQA_K_BRINK && id < VQA_K_ITP))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2690,6 +2764,7 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_BRISQUE_SEAM) return "k_brisque_seam";
     if (id == VQA_K_MDSI_MAP) return "k_mdsi_map";
     if (id == VQA_K_MDSI_DEV) return "k_mdsi_dev";
+    if (id == VQA_K_ITP) return "k_itp";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -514,4 +514,17 @@ void launch_mdsi(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n,
 // four words -> the record: dev and mdsi of include/vqa.h in double, on the host (h x w: plane 0)
 void mdsi_finalize(const unsigned long long *words, int h, int w, vqa_mdsi_metrics *out);
 
+// dE_ITP (vqa_itp_submit): k_itp.hip
+constexpr int ITP_MIN_DIM = 16;                    // the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+constexpr int ITP_WORDS = 2;                       // per frame: the sum and the maximum of q = rint(dE 2^20) (include/vqa.h)
+constexpr double ITP_FIX = 1048576.0;              // 2^20: the quantum of a pixel's dE is 2^-20; dE < 2^13, no saturation
+// n frame pairs of three planes (checked by the caller: plane 0 the full grid, planes 1 and 2 of one geometry, the grid's or its
+// ceil-half in either direction; model, transfer and full_range known values).  Adds each frame's sum into acc[frame * ITP_WORDS]
+// and raises acc[frame * ITP_WORDS + 1] to its maximum; the caller has zeroed both.
+void launch_itp(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                int64_t dist_frame_stride, const vqa_plane_desc *planes, int depth, int model, int transfer, int full_range,
+                unsigned long long *acc);
+// two words -> the record: the divisions of include/vqa.h in double, on the host (h x w: the luma grid)
+void itp_finalize(const unsigned long long *words, int h, int w, vqa_itp_metrics *out);
+
 } // namespace vqa

@@ -77,6 +77,9 @@ MDSI_DTYPE = np.dtype([("sum_pos", np.uint64), ("sum_neg", np.uint64), ("n_neg",
                        ("count", np.int64), ("factor", np.int32), ("reserved", np.int32), ("dev", np.float64),
                        ("mdsi", np.float64)], align=True)
 assert MDSI_DTYPE.itemsize == C.sizeof(N.VqaMdsiMetrics)
+ITP_DTYPE = np.dtype([("sum_q", np.uint64), ("max_q", np.uint64), ("de_sum", np.float64), ("de_mean", np.float64),
+                      ("de_max", np.float64)], align=True)
+assert ITP_DTYPE.itemsize == C.sizeof(N.VqaItpMetrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -94,6 +97,7 @@ _BATCHES = {
     "_pending_r": ("vqa_artifacts_submit", "vqa_artifacts_wait", ARTIFACTS_DTYPE, N.VqaArtifactsMetrics),   # (one stream)
     "_pending_n": ("vqa_brisque_submit", "vqa_brisque_wait", BRISQUE_DTYPE, N.VqaBrisqueMetrics),   # (one stream)
     "_pending_d": ("vqa_mdsi_submit", "vqa_mdsi_wait", MDSI_DTYPE, N.VqaMdsiMetrics),   # (one entry per frame)
+    "_pending_i": ("vqa_itp_submit", "vqa_itp_wait", ITP_DTYPE, N.VqaItpMetrics),   # (one entry per frame)
 }
 
 
@@ -346,7 +350,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -483,7 +487,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI / dE_ITP submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -887,6 +891,49 @@ class Engine:
         self.mdsi_submit(ref, dist, planes, model, frame_bytes)
         return self.mdsi_wait()
 
+    # ---- dE_ITP ------------------------------------------------------------------
+    @staticmethod
+    def itp_model(planes):
+        """the colour model a plane list implies: ITP_BGR for three planes whose pixel step is 3 samples (packed bgr24 and its
+        16-bit kin), ITP_YUV2020 otherwise"""
+        bps = 2 if planes_depth(planes) > 8 else 1
+        return N.ITP_BGR if len(planes) == 3 and all(int(p[4]) == 3 * bps for p in planes) else N.ITP_YUV2020
+
+    @staticmethod
+    def itp_transfer(transfer):
+        """"pq" | "hlg" (or N.ITP_PQ | N.ITP_HLG) -> the transfer's number; anything else is a ValueError"""
+        if isinstance(transfer, str) and transfer in N.ITP_TRANSFERS:
+            return N.ITP_TRANSFERS[transfer]
+        if isinstance(transfer, int) and not isinstance(transfer, bool) and transfer in N.ITP_TRANSFERS.values():
+            return transfer
+        raise ValueError("transfer must be 'pq' or 'hlg'")
+
+    def itp_submit(self, ref, dist, planes, model=None, transfer="pq", full_range=False, frame_bytes=None):
+        """dE_ITP (ITU-R BT.2124) for n frame pairs (vqa_itp_submit): the arrays / DeviceFrames and plane tuples of ciede_submit,
+        exactly THREE planes taken together per pixel - Y, Cb, Cr (BT.2020 non-constant luminance; Cb and Cr of the luma's size or
+        its ceil-half in either direction) or B, G, R; luma at least 16 x 16.  model: N.ITP_YUV2020 | N.ITP_BGR | None
+        (itp_model(planes)).  transfer: "pq" | "hlg" (BT.2100; HLG on a 1000 cd/m2 display).  full_range: False (limited, the
+        default) | True; it has no effect on B, G, R.  A batch of its own, like ciede_submit."""
+        if model is None:
+            model = self.itp_model(planes)
+        transfer = self.itp_transfer(transfer)
+        if not isinstance(full_range, (bool, np.bool_)):
+            raise ValueError("full_range must be True or False")
+        *args, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        st = self.lib.vqa_itp_submit(self.ctx, *args, plane_descs(planes), len(planes), int(model), transfer, int(full_range))
+        N.check(st, "vqa_itp_submit", self.ctx)
+        self._pending_i = (args[3], 1, keep)
+
+    def itp_wait(self):
+        """-> [n] records (ITP_DTYPE), one per frame: the two integer words sum_q and max_q (2^-20 units), de_sum, de_mean (the
+        mean dE_ITP over the luma grid; exactly 0 for identical frames) and de_max (the largest dE_ITP of a pixel)."""
+        return self._batch_wait("_pending_i").reshape(-1)
+
+    def itp(self, ref, dist, planes, model=None, transfer="pq", full_range=False, frame_bytes=None):
+        """dE_ITP per frame for n frame pairs; returns [n] structured array (ITP_DTYPE)."""
+        self.itp_submit(ref, dist, planes, model, transfer, full_range, frame_bytes)
+        return self.itp_wait()
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -894,7 +941,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_TOTAL:
+        for k in N.K_IDS_SUM:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -390,7 +390,8 @@ class Quality:
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
-                 haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False):
+                 haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
+                 itp_transfer="pq", itp_full_range=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -442,7 +443,12 @@ class Quality:
         mdsi    True: every chunk also goes through the MDSI kernels (Engine.mdsi_submit: one plane, or three taken together) from
                 the SAME upload; the pass's tuple then gains ONE further last element, after BRISQUE's: the MDSI records [n]
                 (engine.MDSI_DTYPE: the four integer words, count, factor, dev, mdsi - one per frame, not per plane); "only": no
-                SSE / SSIM.  The colour model follows from the planes (Engine.mdsi_model)"""
+                SSE / SSIM.  The colour model follows from the planes (Engine.mdsi_model)
+        itp     True: every chunk also goes through the dE_ITP kernel (Engine.itp_submit, exactly three planes) from the SAME
+                upload; the pass's tuple then gains ONE further last element, after MDSI's: the dE_ITP records [n]
+                (engine.ITP_DTYPE: sum_q, max_q, de_sum, de_mean, de_max - one per frame, not per plane); "only": no SSE / SSIM.
+                itp_transfer: "pq" | "hlg"; itp_full_range: False (limited) | True; the colour model follows from the planes
+                (Engine.itp_model)"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -521,11 +527,23 @@ class Quality:
         if mdsi and len(planes) not in (1, 3):
             raise ValueError("mdsi needs one plane or three")
         self.mdsi = mdsi
+        if not (isinstance(itp, bool) or (isinstance(itp, str) and itp == "only")):
+            raise ValueError("itp must be False, True or 'only'")
+        if itp == "only" and scales:
+            raise ValueError("a dE_ITP-only pass has no SSIM scales")
+        if itp and len(planes) != 3:
+            raise ValueError("itp needs three planes")
+        if not (isinstance(itp_transfer, str) and itp_transfer in N.ITP_TRANSFERS):
+            raise ValueError("itp_transfer must be 'pq' or 'hlg'")
+        if not isinstance(itp_full_range, bool):
+            raise ValueError("itp_full_range must be True or False")
+        self.itp, self.itp_transfer, self.itp_full_range = itp, itp_transfer, itp_full_range
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
                      ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only" and
-                     vca != "only" and artifacts != "only" and brisque != "only" and mdsi != "only")
+                     vca != "only" and artifacts != "only" and brisque != "only" and mdsi != "only" and
+                     itp != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -615,7 +633,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     only stream it reads.  Quality(.., brisque=True) appends ONE further last element, after the artefact measures': the BRISQUE
     records [n,p] (engine.BRISQUE_DTYPE) of the distorted stream; brisque="only" leaves sse and ssim None as well and measures
     `ref`, the only stream it reads.  Quality(.., mdsi=True) appends ONE further last element, after BRISQUE's: the MDSI records
-    [n] (engine.MDSI_DTYPE, one per frame); mdsi="only" leaves sse and ssim None as well.
+    [n] (engine.MDSI_DTYPE, one per frame); mdsi="only" leaves sse and ssim None as well.  Quality(.., itp=True) appends ONE
+    further last element, after MDSI's: the dE_ITP records [n] (engine.ITP_DTYPE, one per frame); itp="only" leaves sse and ssim
+    None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -699,6 +719,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.mdsi:
             from .engine import MDSI_DTYPE
             q += (np.zeros(0, MDSI_DTYPE),)
+        if quality.itp:
+            from .engine import ITP_DTYPE
+            q += (np.zeros(0, ITP_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -714,7 +737,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion, SI/TI, VCA, CAMBI, the artefact measures and BRISQUE alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and not quality.mdsi and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and not quality.mdsi and not quality.itp and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -822,7 +845,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_d"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_d"] = p["has_i"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -891,6 +914,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.mdsi:
                     eng.mdsi_submit(pair[0], pair[1], quality.planes)
                     p["has_d"] = True
+                if quality.itp:
+                    eng.itp_submit(pair[0], pair[1], quality.planes, None, quality.itp_transfer, quality.itp_full_range)
+                    p["has_i"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -909,7 +935,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itps = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -945,6 +971,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["nres"] = eng.brisque_wait()
             if p["has_d"]:
                 p["dres"] = eng.mdsi_wait()
+            if p["has_i"]:
+                p["ires"] = eng.itp_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -991,6 +1019,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 bsq.append(p.pop("nres"))
             if p["has_d"]:
                 mds.append(p.pop("dres"))
+            if p["has_i"]:
+                itps.append(p.pop("ires"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -1081,6 +1111,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(bsq),)
     if want_q and quality.mdsi:
         q += (np.concatenate(mds),)
+    if want_q and quality.itp:
+        q += (np.concatenate(itps),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

@@ -332,6 +332,40 @@ def frame_mdsi(reference, encoded, layout="bgr24", height=None, width=None, engi
     return np.ascontiguousarray(r["mdsi"]), np.ascontiguousarray(r["dev"])
 
 
+ITP_RANGES = {"limited": False, "full": True}   # the config's "delta_itp_range" -> full_range
+
+
+def _check_itp(transfer, full_range):
+    """the transfer and range arguments of the dE_ITP entry points; anything unknown is a ValueError"""
+    if not (isinstance(transfer, str) and transfer in N.ITP_TRANSFERS):
+        raise ValueError("delta_itp_transfer must be 'pq' or 'hlg'")
+    if not isinstance(full_range, bool):
+        raise ValueError("delta_itp_full_range must be True or False")
+
+
+def frame_delta_itp(reference, encoded, layout="bgr24", height=None, width=None, transfer="pq", full_range=False, engine=None,
+                    batch_size=64, device=None):
+    """Per-frame dE_ITP, the HDR colour difference of ITU-R BT.2124 (Engine.itp through the one-pass pipeline of frame_quality;
+    both streams are uploaded once): the three planes of a pixel taken together, by the definition in include/vqa.h - the planar
+    YUV layouts as BT.2020 non-constant luminance with replicated chroma, bgr24 as B, G, R; transfer "pq" or "hlg" (BT.2100, HLG
+    on a 1000 cd/m2 display); full_range False (limited) or True (ignored for bgr24).  1 is about one just-noticeable difference.
+    Returns (delta_itp [n] float64, the mean over the luma grid - exactly 0 for identical frames -, delta_itp_max [n] float64,
+    the largest value of a pixel).  Luma at least 16 x 16; a one-plane layout, an unknown transfer or range is a ValueError."""
+    if len(LAYOUTS[layout][1]) != 3:
+        raise ValueError("delta_itp needs three planes")
+    _check_itp(transfer, full_range)
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, itp="only", itp_transfer=transfer,
+                                                                 itp_full_range=full_range),
+                      batch_size=batch_size, engine=engine, device=device)
+    r = q[-1]
+    return np.ascontiguousarray(r["de_mean"]), np.ascontiguousarray(r["de_max"])
+
+
 def _brisque_model(model_path, range_path):
     """the config's two paths -> a model or None; loaded before the pass starts, so a bad file costs no GPU time"""
     if model_path is None:
@@ -343,7 +377,8 @@ def _brisque_model(model_path, range_path):
 
 
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
-                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None):
+                  cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None,
+                  delta_itp=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -376,6 +411,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     "brisque" = the model's score over them, after brisque_35.  The VMAF model never reads them.
     mdsi: None, or the MDSI records [n] (engine.MDSI_DTYPE, one per frame): the log then also carries mdsi, after the BRISQUE
     keys and before vmaf, likewise.  The model never reads it.
+    delta_itp: None, or the dE_ITP records [n] (engine.ITP_DTYPE, one per frame): the log then also carries delta_itp (the
+    frame's mean) and delta_itp_max (its largest pixel), after mdsi and before vmaf, likewise.  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -440,6 +477,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         mdsi = np.asarray(mdsi).reshape(-1)
         names += ["mdsi"]
         cols += [mdsi["mdsi"].astype(np.float64)]
+    if delta_itp is not None:
+        delta_itp = np.asarray(delta_itp).reshape(-1)
+        names += ["delta_itp", "delta_itp_max"]
+        cols += [delta_itp["de_mean"].astype(np.float64), delta_itp["de_max"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -562,7 +603,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        layout="bgr24", ssim_mode="gauss", height=None, width=None, batch_size=64, device=None, vif=False,
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
                        gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
-                       brisque_model_path=None, brisque_range_path=None, mdsi=False):
+                       brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
+                       delta_itp_transfer="pq", delta_itp_full_range=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -593,6 +635,9 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     (svm-scale's range file) turn it on and add "brisque", the score (brisque_model.py; loaded BEFORE the pass starts).
     mdsi=True: likewise MDSI, the mean deviation similarity index of the planes taken together (mdsi, one value per frame; one-
     or three-plane layouts; neither a VMAF nor a BRISQUE model file turns it on).
+    delta_itp=True: likewise dE_ITP of ITU-R BT.2124, the three planes together read as a BT.2020 signal (delta_itp, the frame's
+    mean, and delta_itp_max, its largest pixel; three-plane layouts only; delta_itp_transfer "pq" | "hlg", delta_itp_full_range
+    False (limited) | True; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -618,7 +663,11 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if vca:
             from .engine import check_vca_planes
             check_vca_planes(LAYOUTS[layout][0](h, w))
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi:
+        if delta_itp:
+            if len(LAYOUTS[layout][1]) != 3:
+                raise ValueError("delta_itp needs three planes")
+            _check_itp(delta_itp_transfer, delta_itp_full_range)
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi or delta_itp:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -629,10 +678,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              cambi=bool(cambi), xpsnr=bool(xpsnr),
                                                              haarpsi=bool(haarpsi), vca=bool(vca),
                                                              artifacts=bool(artifacts), brisque=brisque,
-                                                             mdsi=bool(mdsi)),
+                                                             mdsi=bool(mdsi), itp=bool(delta_itp),
+                                                             itp_transfer=delta_itp_transfer,
+                                                             itp_full_range=delta_itp_full_range),
                               batch_size=batch_size, on_quality=wr, device=device)
             _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts, brisque, bmodel, mdsi)
+                               artifacts, brisque, bmodel, mdsi, delta_itp)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -671,11 +722,13 @@ MODE_KEYS = {
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
                        cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
-                       mdsi=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000 and MDSI of a pass (the
+                       mdsi=False, delta_itp=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000, MDSI and dE_ITP of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = None
-    if mdsi:       # the tuple's last element, then BRISQUE's
+    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = itp = None
+    if delta_itp:  # the tuple's last element, then MDSI's
+        itp, q = q[-1], q[:-1]
+    if mdsi:       # then BRISQUE's
         mds, q = q[-1], q[:-1]
     if brisque:    # then the artefact measures'
         bsq, q = q[-1][:, 0], q[:-1]
@@ -717,6 +770,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["brisque_model"] = brisque_model
     if mds is not None:
         more["mdsi"] = mds
+    if itp is not None:
+        more["delta_itp"] = itp
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -769,6 +824,14 @@ def _check_mode_keys(config):
         raise ValueError("brisque_range_path needs a brisque_model_path.")
     if "mdsi" in config and not isinstance(config["mdsi"], bool):
         raise ValueError("mdsi must be true or false.")
+    if "delta_itp" in config and not isinstance(config["delta_itp"], bool):
+        raise ValueError("delta_itp must be true or false.")
+    if "delta_itp_transfer" in config and not (isinstance(config["delta_itp_transfer"], str) and
+                                               config["delta_itp_transfer"] in N.ITP_TRANSFERS):
+        raise ValueError("delta_itp_transfer must be \"pq\" or \"hlg\".")
+    if "delta_itp_range" in config and not (isinstance(config["delta_itp_range"], str) and
+                                            config["delta_itp_range"] in ITP_RANGES):
+        raise ValueError("delta_itp_range must be \"limited\" or \"full\".")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -838,6 +901,11 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         mdsi (true: the row gains MDSI, the pooled mean of the per-frame mean deviation similarity index of the planes taken
         together - 0 for identical frames, larger is worse -, after the BRISQUE columns; one- or three-plane pixfmts; default
         false; a model file does not turn it on),
+        delta_itp (true: the row gains DELTA_ITP, the pooled mean of the per-frame mean dE_ITP of ITU-R BT.2124 - the three planes
+        taken together, read as a BT.2020 signal; 1 is about one just-noticeable difference -, and DELTA_ITP_MAX, the largest
+        pixel's value over all frames, after MDSI; three-plane pixfmts only; default false; a model file does not turn it on),
+        delta_itp_transfer ("pq" default | "hlg": BT.2100's transfer function, HLG on a 1000 cd/m2 display), delta_itp_range
+        ("limited" default | "full"; no effect on bgr24),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -871,6 +939,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     bmodel = _brisque_model(config.get("brisque_model_path"), config.get("brisque_range_path"))
     bsq = bool(config.get("brisque", False)) or bmodel is not None
     mds = config.get("mdsi", False)
+    itp = config.get("delta_itp", False)
+    itp_tf = config.get("delta_itp_transfer", "pq")
+    itp_full = ITP_RANGES[config.get("delta_itp_range", "limited")]
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -928,14 +999,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                                      psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
                                                                      gmsd=gms, cambi=cam, xpsnr=xps,
                                                                      haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq,
-                                                                     mdsi=mds),
+                                                                     mdsi=mds, itp=itp, itp_transfer=itp_tf,
+                                                                     itp_full_range=itp_full),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds:
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds or itp:
             _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
-                               mds)
+                               mds, itp)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -1018,6 +1090,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["BRISQUE"] = float(pooled["brisque"]["mean"])
         if "mdsi" in pooled:
             metrics["MDSI"] = float(pooled["mdsi"]["mean"])
+        if "delta_itp" in pooled:
+            metrics["DELTA_ITP"] = float(pooled["delta_itp"]["mean"])
+            metrics["DELTA_ITP_MAX"] = float(pooled["delta_itp_max"]["max"])
     return metrics
 
 
@@ -1040,7 +1115,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range;
     #                           and that a vmaf_model_path names a readable file
 
 
