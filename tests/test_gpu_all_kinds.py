@@ -1,6 +1,6 @@
-"""GPU: all sixteen kinds of batch pending on ONE context at once, every kind with frames of its own.
+"""GPU: all seventeen kinds of batch pending on ONE context at once, every kind with frames of its own.
 
-A vqa_ctx has one stream.  Nine pair kinds stage pageable host frames into the same two device buffers (qstage_ref, qstage_dist,
+A vqa_ctx has one stream.  Ten pair kinds stage pageable host frames into the same two device buffers (qstage_ref, qstage_dist,
 through stage_pair of csrc/vqa_capi.hip), CAMBI, the artefact measures and BRISQUE into qstage_dist, VCA into SI/TI's siti_stage
 and siti_prev; what keeps a pending kind's frames from being overwritten is the stream's order, and ensure(), which drains every
 stream before a staging buffer is freed to grow.  The other files queue several kinds from ONE upload: there an overwritten, a
@@ -24,7 +24,7 @@ Queues (all submits before the first wait):
   descending  pageable host arrays, descending staged bytes: no growth, pure reuse of a buffer a pending kind still has to read
   device      every kind's own frames uploaded before (Engine.upload): read in place
   mixed       even kinds from host, odd kinds from device
-(sixteen kinds and four frame counts: kinds of one n_k stage equal byte counts and sit next to each other in the two sorted
+(seventeen kinds and four frame counts: kinds of one n_k stage equal byte counts and sit next to each other in the two sorted
 queues; their contents still differ.)  The waits are collected in submission order, in reverse and in a shuffled order (seed
 SHUFFLE_SEED).  After every queue the context is idle: an option can be set, and a fresh single-kind submit gives its alone-record."""
 import random
@@ -39,7 +39,7 @@ import motion_cases as K
 pytestmark = pytest.mark.gpu
 
 KINDS = ("complexity", "gauss", "vif", "adm", "motion", "siti", "psnr_hvs", "ciede", "gmsd", "cambi", "xpsnr", "haarpsi", "vca",
-         "artifacts", "brisque", "mdsi")
+         "artifacts", "brisque", "mdsi", "itp")
 FRAMES = (2, 3, 4, 5)                            # n_k = FRAMES[k % 4]
 GEOMETRIES = {"yuv420p": (66, 98, 8), "yuv420p10le": (70, 74, 10)}
 MS_GEOMETRY = (177, 263, 8)                      # gray
@@ -100,24 +100,30 @@ class Job:
 
 
 def _submit(eng, j, mem="host"):
+    """j.frame_bytes and j.model, where a job has them (tests/test_gpu_layouts.py: a host layout's frame stride; the colour model
+    of the tight clip, which a layout's pixel step must not change): passed on; otherwise the engine's defaults"""
     from rtvqa_amd import _native as N
     r, d, p0 = j.dev if mem == "device" else j.host
     k = j.kind
+    fb = {"frame_bytes": j.frame_bytes} if mem == "host" and getattr(j, "frame_bytes", None) else {}
+    model = getattr(j, "model", None)
     if k == "complexity":
         j.params = eng.make_params(dct_mode=N.DCT_BLOCK8)
         eng.complexity_submit(r, p0, N.M_ALL, j.params)
     elif k in ("gauss", "ffmpeg", "ms"):
-        eng.quality_submit(r, d, j.planes, _modes()[k])
+        eng.quality_submit(r, d, j.planes, _modes()[k], **fb)
+    elif k in ("mdsi", "itp"):
+        getattr(eng, k + "_submit")(r, d, j.planes, model=model, **fb)
     elif k in PAIRS:
-        getattr(eng, k + "_submit")(r, d, j.planes)
+        getattr(eng, k + "_submit")(r, d, j.planes, **fb)
     elif k == "ciede":
-        eng.ciede_submit(r, d, j.planes, weights=(1.0, 1.0, 1.0))
+        eng.ciede_submit(r, d, j.planes, model=model, weights=(1.0, 1.0, 1.0), **fb)
     elif k == "xpsnr":
-        eng.xpsnr_submit(r, d, j.planes, prev0=p0)
+        eng.xpsnr_submit(r, d, j.planes, prev0=p0, **fb)
     elif k in WITH_PREV0:
-        getattr(eng, k + "_submit")(r, j.planes, prev0=p0)
+        getattr(eng, k + "_submit")(r, j.planes, prev0=p0, **fb)
     elif k in ONE_STREAM:
-        getattr(eng, k + "_submit")(d, j.planes)
+        getattr(eng, k + "_submit")(d, j.planes, **fb)
     else:
         raise KeyError(k)
 
@@ -180,7 +186,7 @@ def rounds(engine):
 def test_the_jobs_are_what_the_queues_need():
     """(host) neighbouring kinds differ in their frame count, every count is used, and no two kinds share a frame"""
     ns = [FRAMES[k % 4] for k in range(len(KINDS))]
-    assert len(KINDS) == 16 and all(a != b for a, b in zip(ns, ns[1:])) and set(ns) == set(FRAMES)
+    assert len(KINDS) == 17 and all(a != b for a, b in zip(ns, ns[1:])) and set(ns) == set(FRAMES)
     h, w, depth = GEOMETRIES["yuv420p"]
     seen = set()
     for k, kind in enumerate(KINDS):
@@ -253,6 +259,12 @@ def _anchor(j, raw, oracle):
         with TSL._fresh(TMD.WORST, "mdsi"):
             for i in range(j.n):
                 TMD._check_one(raw[i], j.lists[0][i], j.lists[1][i], "yuv420p", depth, "%s frame %d" % (tag, i))
+    elif k == "itp":
+        import itp_cases as IC
+        import itp_reference as IR
+        import test_gpu_itp as TI
+        with TSL._fresh(TI.WORST, "itp"):
+            TI._check(raw, IC.reference(r, d, planes, depth, IR.YUV2020, IR.PQ, False), j.h, j.w, tag)
     else:
         raise KeyError(k)
 
@@ -319,6 +331,7 @@ def _run_queue(eng, jobs, want, queue, order, trim_first=False):
 @pytest.mark.parametrize("queue", QUEUES)
 @pytest.mark.parametrize("layout", list(GEOMETRIES))
 def test_sixteen_kinds_in_flight_each_with_frames_of_its_own(engine, rounds, layout, queue):
+    """(named when KINDS held sixteen: every kind of KINDS, seventeen since dE_ITP joined)"""
     rd = rounds[layout]
     assert [j.kind for j in rd.jobs] == list(KINDS)
     if queue in ("ascending", "descending"):
