@@ -410,6 +410,24 @@ typedef struct vqa_itp_metrics {
     double de_max;    /* max_q 2^-20: the largest dE_ITP of a pixel                                                         */
 } vqa_itp_metrics;
 
+/* PU21-PSNR and PU21-SSIM of one frame pair, the three planes of a pixel taken together (vqa_pu21_submit / vqa_pu21_wait; the
+ * definition and the bounds of the words are stated there).  The five words are the device's integer totals, so the same pair
+ * gives the same words at any place of any batch, from host or device memory; windows and the doubles are formed on the host by
+ * vqa_pu21_wait.                                                                                                            */
+typedef struct vqa_pu21_metrics {
+    uint64_t sse_y_lo;    /* the sum over the luma grid of the LOW 32 bits of (q_Y,ref - q_Y,dist)^2                            */
+    uint64_t sse_y_hi;    /* the sum of the same terms >> 32: sse_y = (sse_y_hi << 32) + sse_y_lo, in 128-bit integers          */
+    uint64_t sse_rgb_lo;  /* likewise over the three channels q_R, q_G, q_B                                                    */
+    uint64_t sse_rgb_hi;
+    int64_t ssim_q;       /* the signed sum over the valid windows of u = rint(ssim 2^24)                                      */
+    int64_t windows;      /* (h - 10)(w - 10)                                                                                  */
+    double mse_y;         /* sse_y / (2^32 h w): the mean squared error in PU units                                            */
+    double mse_rgb;       /* sse_rgb / (2^32 3 h w)                                                                            */
+    double pu_psnr;       /* 10 log10(256^2 / mse_y); inf for a zero sum                                                       */
+    double pu_psnr_rgb;   /* 10 log10(256^2 / mse_rgb); inf for a zero sum                                                     */
+    double pu_ssim;       /* ssim_q / (2^24 windows); exactly 1 for identical frames                                           */
+} vqa_pu21_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1315,6 +1333,84 @@ VQA_API int vqa_itp_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist
                            int model, int transfer, int full_range);
 VQA_API int vqa_itp_wait(vqa_ctx *ctx, vqa_itp_metrics *out, int n_entries);
 
+/* ---- PU21 HDR quality: PU21-PSNR and PU21-SSIM (Mantiuk and Azimi, "PU21: A novel perceptually uniform encoding for adapting
+ * existing quality metrics for HDR", PCS 2021), three planes jointly ----
+ * dE_ITP above is a pointwise colour difference.  Every structural or error figure of the other kinds reads a code value as a
+ * linear SDR-like scale, which on a PQ stream weighs an error at 2 cd/m2 like one at 2000 cd/m2.  PU21 maps ABSOLUTE luminance to
+ * perceptually uniform units; the ordinary PSNR and the ordinary Gaussian SSIM then run on those units.
+ * Input.  Exactly vqa_itp_submit's: THREE planes of one depth (8 bits, or 9..16 bits as uint16), the colour models
+ *   VQA_ITP_YUV2020 (Y, Cb, Cr, BT.2020 non-constant luminance, limited or full range, chroma replicated: 4:4:4, 4:2:2, 4:2:0, odd
+ *   sizes) or VQA_ITP_BGR, the transfers VQA_ITP_PQ or VQA_ITP_HLG - the same enums, the same geometry rules.
+ * Display light.  R', G', B' CLAMPED to [0, 1], then per channel the display light Fd in cd/m2 through the PQ EOTF, or through
+ *   HLG's inverse OETF and the OOTF of a 1000 cd/m2 display: word for word the chain vqa_itp_submit states up to "display light",
+ *   in double with contraction off, each step rounded once in the order written there.
+ * Luminance.  Y = (0.2627 R + 0.6780 G) + 0.0593 B on the display-light R, G, B.
+ * PU21 encoding (the authors' banding_glare fit, their default), with L CLAMPED to [0.005, 10000] first:
+ *   V(L) = max(p7 (((p1 + p2 L^p4) / (1 + p3 L^p4))^p5 - p6), 0)
+ *   p1 = 0.353487901, p2 = 0.3734658629, p3 = 8.277049286e-05, p4 = 0.9062562627, p5 = 0.09150303166, p6 = 0.9099517204,
+ *   p7 = 596.3148142.
+ *   In double with these constants V(0.005) = 5.47e-10, V(100) = 256.3838973127, V(10000) = 595.3939200201, and V is strictly
+ *   increasing over the whole range.  The constants are the authors' AS RECALLED, cross-checked only by those design properties
+ *   (zero at the floor, 256 at 100 cd/m2); they are NOT pinned against the authors' MATLAB.  vqa_pu21_encode is V on the host.
+ * Quantisation, ONCE.  q = rint(V 2^16), below 2^26, for four channels of each image: q_Y from V(Y), and q_R, q_G, q_B from V of
+ *   each display-light channel.  Everything below is a function of these integers.
+ * PU21-PSNR.  sse_y = the sum over the luma grid of (q_Y,ref - q_Y,dist)^2, sse_rgb the same sum over the three channels.  A term
+ *   is below 2^52 and a frame of h w <= 2^28 pixels has up to 3 * 2^28 of them, so each sum leaves the device as TWO 64-bit words:
+ *   the sum of the terms' low 32 bits and the sum of the terms >> 32 (each below 2^62: no word can overflow).  The wait joins them
+ *   in 128-bit integers, sse = (hi << 32) + lo, converts that integer to double (round to nearest) and divides:
+ *     mse_y = sse_y / (2^32 h w), mse_rgb = sse_rgb / (2^32 (3 h w))      (both divisors are exact doubles)
+ *     pu_psnr = 10 log10(256^2 / mse_y), pu_psnr_rgb = 10 log10(256^2 / mse_rgb); both are inf for a zero sum.
+ *   The peak of 256 is this project's choice: PU21 puts 100 cd/m2 at 256, so SDR-range content scores near its ordinary PSNR;
+ *   mse_y and mse_rgb are in the record for callers who want another peak.
+ * PU21-SSIM on x = q_Y / 2^16 (exact in double):
+ *   window    11 x 11 Gaussian, g_i = exp(-(i - 5)^2 / 4.5) normalised to sum 1 in double (the sum taken for i = 0 .. 10 in
+ *             order), separable: horizontal first, s(y, x) = the sum over j = 0 .. 10 in order of g_j v(y, x + j), then vertical,
+ *             the sum over i = 0 .. 10 in order of g_i s(y + i, x); v is x_r, x_d, x_r x_r, x_d x_d or x_r x_d (products of two
+ *             26-bit values: exact).  Valid windows only: (h - 10)(w - 10) of them.
+ *   moments   mu = sum w x, var = sum w x^2 - mu^2, cov = sum w x_r x_d - mu_r mu_d
+ *   value     ssim = ((2 (mu_r mu_d) + C1)(2 cov + C2)) / (((mu_r^2 + mu_d^2) + C1)((var_r + var_d) + C2)),
+ *             C1 = (0.01 * 256)^2, C2 = (0.03 * 256)^2 (each as the double product t t of t = 0.01 * 256, t = 0.03 * 256)
+ *   all in double, contraction off.  u = rint(ssim 2^24) is a SIGNED integer (ssim may be negative), ssim_q = the sum of u over
+ *   the valid windows, one signed 64-bit word (|u| <= 2^24 + 1 and at most 2^28 windows: below 2^53);
+ *   pu_ssim = ssim_q / (2^24 windows).  The quantum is 2^-24 and not finer: the cancellation in sum w x^2 - mu^2 at x near 596
+ *   leaves about 1e-10 on a window's value, which must stay far below the quantum.
+ * Consequences.  Identical frames give all-zero SSE words, inf PSNRs, ssim_q == windows << 24 and pu_ssim == 1.0 EXACTLY
+ *   (2 (mu mu) and mu^2 + mu^2 are the same double, and cov is var when computed from the same values).  A frame gives the same
+ *   five words in any batch, from any memory, alone or next to other kinds: a window's value is a fixed-order sum of the same
+ *   doubles whichever tile or thread computes it, and all that is added across threads is integers.
+ * How the device forms it.  Per sub-slice of frames two kernels: k_pu21_encode (a thread owns a 2 x 4 luma patch of both images
+ *   as in k_itp; it writes q_Y of both images as uint32 into a scratch map and adds the four SSE half-words in the thread,
+ *   across the wave, then with one 64-bit atomic add per word per workgroup; a pixel whose two triples are equal skips the second
+ *   chain and still writes both map entries) and k_pu21_ssim (a workgroup owns a 16 x 16 tile of the valid-window grid with a
+ *   5-sample apron of both maps in LDS, the five horizontally filtered moments in LDS, one thread per window, one 64-bit atomic
+ *   add per workgroup).  Scratch on the device: 40 bytes per frame for the words, and the two maps at 8 bytes per luma sample;
+ *   the submit runs the two kernels over sub-slices of at most max(1, 2^28 / (8 h w)) frames, so the maps stay at or below
+ *   256 MiB whatever n is.  Host frames are staged in the buffers vqa_ciede_submit uses.  All of it is kept by the ctx until
+ *   vqa_trim / vqa_destroy.
+ * Limits: luma at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.  n_planes other than 3 (one-plane layouts
+ * are an error), Cb and Cr (or B, G, R) geometries that differ, a chroma size that is neither the luma's nor its ceil-half, mixed
+ * depths, an unknown model or transfer, a full_range other than 0 or 1: VQA_ERR_INVALID.
+ * The contract of vqa_itp_submit: asynchronous, ONE ENTRY PER FRAME, the same plane descriptors, depths, alignment rules,
+ * memory kinds and failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while a PU21 batch is pending.
+ * A PU21 batch is a batch of its own: it may be in flight next to a batch of every other kind of the same ctx, and each wait
+ * collects its own kind only.  A batch of more than 32768 frames goes out in slices, each slice in sub-slices as above.
+ * Not built: an SDR display model (PU21 on gamma-coded input), the other three PU21 fits, PU21-MS-SSIM / VIF / FSIM, and
+ * luminance from anything but the three planes.
+ * out of vqa_pu21_wait: n entries (n_entries = n).                                                                         */
+VQA_API int vqa_pu21_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                            int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes,
+                            int model, int transfer, int full_range);
+VQA_API int vqa_pu21_wait(vqa_ctx *ctx, vqa_pu21_metrics *out, int n_entries);
+/* V(cd_m2) as stated above, in double on the host; needs no ctx and no device                                               */
+VQA_API double vqa_pu21_encode(double cd_m2);
+/* LAB BUILD ONLY (vqa_build_flavour() & 2; the shipped library does not export it, and this header declares it only when
+ * VQA_TEST_SEAMS is defined): the two q_Y maps of the LAST vqa_pu21_submit of the ctx, [n][2][h][w] uint32 (ref, then dist), after
+ * its wait; n_values = n 2 h w.  There, too, the environment may shorten a sub-slice to a given number of frames, so that a
+ * small batch spans several.                                                                                                */
+#ifdef VQA_TEST_SEAMS
+    VQA_API int vqa_pu21_lab_read_maps(vqa_ctx *ctx, uint32_t *dst, int64_t n_values);
+#endif
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1393,7 +1489,12 @@ enum vqa_kernel_id {
                                 being unknown); id 50 stays unnamed                                                      */
     VQA_K_ITP = 51,          /* vqa_itp_submit: both ICtCp conversions, dE_ITP, the fixed-point sum and maximum (one entry per
                                 slice)                                                                                   */
-    VQA_K_VERGE = 52         /* one past the last id: ... VQA_K_MDSI_MAP .. VQA_K_BRINK - 1 and VQA_K_ITP .. VQA_K_VERGE - 1  */
+    VQA_K_VERGE = 52,        /* one past VQA_K_ITP, as dE_ITP shipped it (kept at 52 for callers and tests that rely on id 52
+                                being unknown); id 52 stays unnamed                                                      */
+    VQA_K_PU21_ENCODE = 53,  /* vqa_pu21_submit: display light, the PU21 encodings, the q_Y maps and the four SSE half-words (one
+                                entry per sub-slice)                                                                     */
+    VQA_K_PU21_SSIM = 54,    /* vqa_pu21_submit: the Gaussian SSIM over the maps (one entry per sub-slice)                     */
+    VQA_K_RIM = 55           /* one past the last id: ... VQA_K_ITP .. VQA_K_VERGE - 1 and VQA_K_PU21_ENCODE .. VQA_K_RIM - 1  */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -67,7 +67,9 @@ K_IDS_WHOLE = K_IDS_FULL + (K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM)   # 
 K_MDSI_MAP, K_MDSI_DEV, K_BRINK = 48, 49, 50      # added beyond K_EDGE, which stays 47; id 47 is unnamed
 K_IDS_TOTAL = K_IDS_WHOLE + (K_MDSI_MAP, K_MDSI_DEV)   # the ids below K_BRINK (kept as MDSI shipped it)
 K_ITP, K_VERGE = 51, 52                           # added beyond K_BRINK, which stays 50; id 50 is unnamed
-K_IDS_SUM = K_IDS_TOTAL + (K_ITP,)                # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_SUM = K_IDS_TOTAL + (K_ITP,)                # the ids below K_VERGE (kept as dE_ITP shipped it)
+K_PU21_ENCODE, K_PU21_SSIM, K_RIM = 53, 54, 55    # added beyond K_VERGE, which stays 52; id 52 is unnamed
+K_IDS_GRAND = K_IDS_SUM + (K_PU21_ENCODE, K_PU21_SSIM)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -103,6 +105,10 @@ ITP_YUV2020, ITP_BGR = 0, 1   # vqa_itp_submit's colour models
 ITP_PQ, ITP_HLG = 0, 1        # vqa_itp_submit's transfer functions
 ITP_TRANSFERS = {"pq": ITP_PQ, "hlg": ITP_HLG}
 ITP_FIX = 1 << 20  # vqa_itp_metrics: q = rint(dE_ITP 2^20)
+PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
+PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
+PU21_SSIM_TILE = 16      # k_pu21_ssim: a workgroup owns 16 x 16 windows
 HAARPSI_FIX = 1 << 30  # vqa_haarpsi_metrics: num is a sum of u wI with u = rint(2^30 sigmoid)
 HAARPSI_ALPHA = 4.2    # the paper's alpha
 CAMBI_SCALES = 5
@@ -222,6 +228,12 @@ class VqaItpMetrics(C.Structure):
                 ("de_max", C.c_double)]
 
 
+class VqaPu21Metrics(C.Structure):
+    _fields_ = [("sse_y_lo", C.c_uint64), ("sse_y_hi", C.c_uint64), ("sse_rgb_lo", C.c_uint64), ("sse_rgb_hi", C.c_uint64),
+                ("ssim_q", C.c_int64), ("windows", C.c_int64), ("mse_y", C.c_double), ("mse_rgb", C.c_double),
+                ("pu_psnr", C.c_double), ("pu_psnr_rgb", C.c_double), ("pu_ssim", C.c_double)]
+
+
 class VqaHaarpsiMetrics(C.Structure):
     _fields_ = [("den", C.c_uint64), ("num_lo", C.c_uint64), ("num_hi", C.c_uint64), ("similarity", C.c_double),
                 ("haarpsi", C.c_double)]
@@ -295,6 +307,10 @@ SIGNATURES = {
     "vqa_itp_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
                                  C.c_int, C.c_int, C.c_int]),
     "vqa_itp_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaItpMetrics), C.c_int]),
+    "vqa_pu21_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
+                                  C.c_int, C.c_int, C.c_int]),
+    "vqa_pu21_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaPu21Metrics), C.c_int]),
+    "vqa_pu21_encode": (C.c_double, [C.c_double]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),
@@ -328,6 +344,12 @@ def _strerror(status):
         return "status %d" % status
 
 
+# symbols of the lab build alone (vqa_build_flavour() & FLAVOUR_TEST_SEAMS); include/vqa.h declares them under VQA_TEST_SEAMS
+LAB_SIGNATURES = {
+    "vqa_pu21_lab_read_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]),
+}
+
+
 def load():
     """Load libvqa_hip.so and bind every declared symbol.  Raises if the
     library has not been built (run `python -c 'import __graft_entry__ as g; g.build()'`)."""
@@ -350,6 +372,11 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in LAB_SIGNATURES.items():   # the lab build's own symbols: absent from the shipped library
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     if lib.vqa_abi_version() != VQA_ABI_VERSION:
         raise ImportError("libvqa_hip.so ABI %d != binding ABI %d" % (lib.vqa_abi_version(), VQA_ABI_VERSION))
     _lib = lib

@@ -64,6 +64,7 @@ struct vqa_ctx {
     long seam_ensure_calls = 0;
     long long seam_fb_chunk_bytes = 0; // VQA_FB_CHUNK_BYTES: Farneback's scratch budget per chunk (0 = the shipped 12 GiB): lets a small batch span chunks
     int seam_qslice = 0;            // VQA_QSLICE: the frames of one slice of a plane batch (0 = the shipped QSLICE): lets a small batch span slices
+    int seam_pu21_sub = 0;          // VQA_PU21_SUBSLICE: the frames of one sub-slice of a PU21 batch (0 = the shipped budget): lets a small batch span sub-slices
 
     // device scratch (grow-only)
     dbuf gray_full, planeA, planeB, state, res_dev, partials, tile_flags, dirty0, dirty1, again_dev;
@@ -123,6 +124,10 @@ struct vqa_ctx {
     // vqa_itp_submit: the two integer words per frame (device, pinned host); host frames are staged in qstage_*
     dbuf itp_acc;
     hbuf itp_host;
+    // vqa_pu21_submit: the five integer words per frame (device, pinned host); the two q_Y maps of one sub-slice of frames; lab
+    // build only: the maps of the whole last batch, for vqa_pu21_lab_read_maps; host frames are staged in qstage_*
+    dbuf pu21_acc, pu21_map, pu21_keep;
+    hbuf pu21_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -165,6 +170,9 @@ struct vqa_ctx {
     int pend_d_w = 0, pend_d_h = 0;
     int pend_i = 0;           // frames of the pending dE_ITP batch (likewise); its luma grid, for the host's mean
     int pend_i_w = 0, pend_i_h = 0;
+    int pend_u = 0;           // frames of the pending PU21 batch (likewise); its luma grid, for the host's divisions
+    int pend_u_w = 0, pend_u_h = 0;
+    int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what pu21_keep holds
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -174,8 +182,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_VERGE] = {0};
-    int64_t prof_n[VQA_K_VERGE] = {0};
+    double prof_ms[VQA_K_RIM] = {0};
+    int64_t prof_n[VQA_K_RIM] = {0};
 };
 
 namespace {
@@ -248,7 +256,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d || c->pend_i; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d || c->pend_i || c->pend_u; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -856,6 +864,7 @@ int vqa_create(int device, vqa_ctx **out)
         }
         c->seam_qslice = (int)q;
     }
+    if (const char *e = getenv("VQA_PU21_SUBSLICE")) c->seam_pu21_sub = atoi(e) > 0 ? atoi(e) : 0;
 #endif
     *out = c;
     return VQA_OK;
@@ -900,19 +909,20 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->itp_acc, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->itp_acc, &c->pu21_acc, &c->pu21_map, &c->pu21_keep, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host, &c->itp_host}) {
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host, &c->itp_host, &c->pu21_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
+    c->last_u_n = 0;
 }
 
 int vqa_trim(vqa_ctx *c)
@@ -1407,7 +1417,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the sixteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI, dE_ITP) share: the checks, the staging of host frames, the walk over
+// What the seventeen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI, dE_ITP, PU21) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -1466,7 +1476,7 @@ static int stage(vqa_ctx *c, dbuf &buf, const uint8_t *&frames, size_t bytes)
     return VQA_OK;
 }
 
-// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI, an MDSI or a dE_ITP submit.  The ten share qstage_*: the stream orders a batch behind
+// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI, an MDSI, a dE_ITP or a PU21 submit.  The eleven share qstage_*: the stream orders a batch behind
 // whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
 static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs, const uint8_t *&dist,
                       int64_t dist_fs)
@@ -2710,6 +2720,130 @@ int vqa_itp_wait(vqa_ctx *c, vqa_itp_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
+// PU21-PSNR / PU21-SSIM: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own (pend_u),
+// ordered by the stream like a dE_ITP batch, whose checks, host staging (qstage_*) and geometry rules it shares.
+
+// the frames of one sub-slice: the two q_Y maps of that many frames stay within PU21_MAP_BUDGET (lab build: or what the seam says)
+static inline int pu21_subslice(const vqa_ctx *c, int h, int w)
+{
+#ifdef VQA_TEST_SEAMS
+    if (c->seam_pu21_sub > 0) return c->seam_pu21_sub;
+#endif
+    (void)c;
+    const size_t per = PU21_MAP_BUDGET / pu21_map_bytes(h, w);
+    return per < 1 ? 1 : per > (size_t)QSLICE ? QSLICE : (int)per;
+}
+
+static int pu21_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int model, int transfer, int full_range,
+                            bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (n_planes != 3 || (model != VQA_ITP_YUV2020 && model != VQA_ITP_BGR)) return VQA_ERR_INVALID;
+    if ((transfer != VQA_ITP_PQ && transfer != VQA_ITP_HLG) || (full_range != 0 && full_range != 1)) return VQA_ERR_INVALID;
+    if (c->pend_u) return VQA_ERR_STATE;
+    plane_batch B;
+    // the size limits are the luma grid's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
+    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
+        return &d == planes ? side_and_area_limits(d, PU21_MIN_DIM) : (int)VQA_OK;
+    });
+    if (rc) return rc;
+    const vqa_plane_desc &y = planes[0], &u = planes[1], &v = planes[2];
+    if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
+        return VQA_ERR_INVALID;
+    if (model == VQA_ITP_BGR) {
+        if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
+            return VQA_ERR_INVALID;
+    } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
+        return VQA_ERR_INVALID;
+    }
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    const size_t acc_bytes = sizeof(unsigned long long) * PU21_WORDS * (size_t)n;
+    const size_t map_bytes = pu21_map_bytes(y.height, y.width);
+    const int sub = pu21_subslice(c, y.height, y.width);
+    const int sub_frames = sub < slice_frames(c, n) ? sub : slice_frames(c, n);
+    if ((rc = ensure(c, c->pu21_acc, acc_bytes))) return rc;
+    if ((rc = ensure(c, c->pu21_map, map_bytes * (size_t)sub_frames))) return rc;
+    if ((rc = ensure_pinned(c, c->pu21_host, acc_bytes))) return rc;
+#ifdef VQA_TEST_SEAMS
+    c->last_u_n = 0;
+    if ((rc = ensure(c, c->pu21_keep, map_bytes * (size_t)n))) return rc;
+#endif
+    HIPCHK(c, hipMemsetAsync(c->pu21_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    hipError_t copy_err = hipSuccess;
+    for_each_slice(c, n, [&](int a0, int m) {
+        for (int b0 = 0; b0 < m; b0 += sub_frames) {
+            const int k = m - b0 < sub_frames ? m - b0 : sub_frames, at = a0 + b0;
+            unsigned long long *acc = (unsigned long long *)c->pu21_acc.p + (size_t)at * PU21_WORDS;
+            {
+                prof_scope ps_(c, VQA_K_PU21_ENCODE);
+                launch_pu21_encode(st, ref + (int64_t)at * ref_fs, dist + (int64_t)at * dist_fs, k, ref_fs, dist_fs, planes, depth,
+                                   model, transfer, full_range, (uint32_t *)c->pu21_map.p, acc);
+            }
+            {
+                prof_scope ps_(c, VQA_K_PU21_SSIM);
+                launch_pu21_ssim(st, (const uint32_t *)c->pu21_map.p, k, y.height, y.width, acc);
+            }
+#ifdef VQA_TEST_SEAMS
+            const hipError_t e = hipMemcpyAsync((uint8_t *)c->pu21_keep.p + map_bytes * (size_t)at, c->pu21_map.p,
+                                                map_bytes * (size_t)k, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) copy_err = e;
+#endif
+        }
+    });
+    HIPCHK(c, copy_err);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->pu21_host.p, c->pu21_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_u = n;
+    c->pend_u_w = y.width;
+    c->pend_u_h = y.height;
+#ifdef VQA_TEST_SEAMS
+    c->last_u_n = n; c->last_u_w = y.width; c->last_u_h = y.height;
+#endif
+    return VQA_OK;
+}
+
+int vqa_pu21_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
+                    const vqa_plane_desc *planes, int n_planes, int model, int transfer, int full_range)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return pu21_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, model, transfer, full_range, touched);
+    });
+}
+
+int vqa_pu21_wait(vqa_ctx *c, vqa_pu21_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_u || n_entries != c->pend_u) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->pu21_host.p;
+    for (int e = 0; e < n_entries; e++) pu21_finalize(acc + (size_t)e * PU21_WORDS, c->pend_u_h, c->pend_u_w, out + e);
+    c->pend_u = 0;
+    return VQA_OK;
+}
+
+double vqa_pu21_encode(double cd_m2) { return pu21_encode_host(cd_m2); }
+
+#ifdef VQA_TEST_SEAMS
+int vqa_pu21_lab_read_maps(vqa_ctx *c, uint32_t *dst, int64_t n_values)
+{
+    if (!c || !dst) return VQA_ERR_INVALID;
+    if (c->pend_u || !c->last_u_n) return VQA_ERR_STATE;
+    if (n_values != (int64_t)c->last_u_n * 2 * c->last_u_h * c->last_u_w) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dst, c->pu21_keep.p, sizeof(uint32_t) * (size_t)n_values, hipMemcpyDeviceToHost));
+    return VQA_OK;
+}
+#endif
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2719,12 +2853,12 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_VERGE || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_RIM || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
         (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS) || (id >= VQA_K_CLOSE && id < VQA_K_ARTIFACTS) || (id >= VQA_K_STOP && id < VQA_K_BRISQUE_HALF) ||
-        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP) || (id >= VQA_K_BRINK && id < VQA_K_ITP))
+        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP) || (id >= VQA_K_BRINK && id < VQA_K_ITP) || (id >= VQA_K_VERGE && id < VQA_K_PU21_ENCODE))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2765,6 +2899,8 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_MDSI_MAP) return "k_mdsi_map";
     if (id == VQA_K_MDSI_DEV) return "k_mdsi_dev";
     if (id == VQA_K_ITP) return "k_itp";
+    if (id == VQA_K_PU21_ENCODE) return "k_pu21_encode";
+    if (id == VQA_K_PU21_SSIM) return "k_pu21_ssim";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -527,4 +527,27 @@ void launch_itp(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, 
 // two words -> the record: the divisions of include/vqa.h in double, on the host (h x w: the luma grid)
 void itp_finalize(const unsigned long long *words, int h, int w, vqa_itp_metrics *out);
 
+// PU21-PSNR / PU21-SSIM (vqa_pu21_submit): k_pu21.hip
+constexpr int PU21_MIN_DIM = 16;                   // the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+constexpr int PU21_WORDS = 5;                      // per frame: sse_y lo, hi; sse_rgb lo, hi; ssim_q (include/vqa.h)
+constexpr double PU21_FIX = 65536.0;               // 2^16: q = rint(V 2^16), below 2^26
+constexpr double PU21_SSIM_FIX = 16777216.0;       // 2^24: u = rint(ssim 2^24)
+constexpr double PU21_PEAK = 256.0;                // the peak of both PSNRs: PU21 puts 100 cd/m2 at 256
+constexpr double PU21_C1 = (0.01 * 256.0) * (0.01 * 256.0), PU21_C2 = (0.03 * 256.0) * (0.03 * 256.0);
+constexpr int PU21_SSIM_TILE = 16;                 // k_pu21_ssim: a workgroup owns 16 x 16 windows (26 x 26 samples of both maps)
+constexpr size_t PU21_MAP_BUDGET = (size_t)1 << 28;   // the two maps of a sub-slice of frames stay within 256 MiB
+// the bytes of the two q_Y maps of one frame: 8 per luma sample
+inline size_t pu21_map_bytes(int h, int w) { return 2 * sizeof(uint32_t) * (size_t)h * (size_t)w; }
+// n frame pairs of three planes (checked by the caller as for launch_itp).  Writes q_Y of both images into map
+// [frame][2][h][w] and adds each frame's four squared-error half-words into acc[frame * PU21_WORDS + 0..3]; the caller has zeroed them.
+void launch_pu21_encode(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                        int64_t dist_frame_stride, const vqa_plane_desc *planes, int depth, int model, int transfer,
+                        int full_range, uint32_t *map, unsigned long long *acc);
+// the Gaussian SSIM of n frames of the map -> adds each frame's signed sum of u into acc[frame * PU21_WORDS + 4]
+void launch_pu21_ssim(hipStream_t st, const uint32_t *map, int n, int h, int w, unsigned long long *acc);
+// V(cd/m2) of include/vqa.h, on the host
+double pu21_encode_host(double cd_m2);
+// five words -> the record: the joins and divisions of include/vqa.h in double, on the host (h x w: the luma grid)
+void pu21_finalize(const unsigned long long *words, int h, int w, vqa_pu21_metrics *out);
+
 } // namespace vqa

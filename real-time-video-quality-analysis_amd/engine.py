@@ -80,6 +80,10 @@ assert MDSI_DTYPE.itemsize == C.sizeof(N.VqaMdsiMetrics)
 ITP_DTYPE = np.dtype([("sum_q", np.uint64), ("max_q", np.uint64), ("de_sum", np.float64), ("de_mean", np.float64),
                       ("de_max", np.float64)], align=True)
 assert ITP_DTYPE.itemsize == C.sizeof(N.VqaItpMetrics)
+PU21_DTYPE = np.dtype([("sse_y_lo", np.uint64), ("sse_y_hi", np.uint64), ("sse_rgb_lo", np.uint64), ("sse_rgb_hi", np.uint64),
+                       ("ssim_q", np.int64), ("windows", np.int64), ("mse_y", np.float64), ("mse_rgb", np.float64),
+                       ("pu_psnr", np.float64), ("pu_psnr_rgb", np.float64), ("pu_ssim", np.float64)], align=True)
+assert PU21_DTYPE.itemsize == C.sizeof(N.VqaPu21Metrics)
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -98,6 +102,7 @@ _BATCHES = {
     "_pending_n": ("vqa_brisque_submit", "vqa_brisque_wait", BRISQUE_DTYPE, N.VqaBrisqueMetrics),   # (one stream)
     "_pending_d": ("vqa_mdsi_submit", "vqa_mdsi_wait", MDSI_DTYPE, N.VqaMdsiMetrics),   # (one entry per frame)
     "_pending_i": ("vqa_itp_submit", "vqa_itp_wait", ITP_DTYPE, N.VqaItpMetrics),   # (one entry per frame)
+    "_pending_u": ("vqa_pu21_submit", "vqa_pu21_wait", PU21_DTYPE, N.VqaPu21Metrics),   # (one entry per frame)
 }
 
 
@@ -350,7 +355,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21 and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -487,7 +492,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI / dE_ITP submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI / dE_ITP / PU21 submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -934,6 +939,44 @@ class Engine:
         self.itp_submit(ref, dist, planes, model, transfer, full_range, frame_bytes)
         return self.itp_wait()
 
+    # ---- PU21-PSNR / PU21-SSIM ------------------------------------------------------
+    def pu21_submit(self, ref, dist, planes, model=None, transfer="pq", full_range=False, frame_bytes=None):
+        """PU21-PSNR and PU21-SSIM for n frame pairs (vqa_pu21_submit): the arrays / DeviceFrames, plane tuples, colour models,
+        transfers and ranges of itp_submit, exactly THREE planes taken together per pixel; luma at least 16 x 16.  model:
+        N.ITP_YUV2020 | N.ITP_BGR | None (itp_model(planes)).  transfer: "pq" | "hlg".  full_range: False (limited, the default) |
+        True; it has no effect on B, G, R.  A batch of its own, like itp_submit."""
+        if model is None:
+            model = self.itp_model(planes)
+        transfer = self.itp_transfer(transfer)
+        if not isinstance(full_range, (bool, np.bool_)):
+            raise ValueError("full_range must be True or False")
+        *args, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        st = self.lib.vqa_pu21_submit(self.ctx, *args, plane_descs(planes), len(planes), int(model), transfer, int(full_range))
+        N.check(st, "vqa_pu21_submit", self.ctx)
+        self._pending_u = (args[3], 1, keep)
+        self._pu21_shape = (args[3], 2, int(planes[0][1]), int(planes[0][0]))
+
+    def pu21_wait(self):
+        """-> [n] records (PU21_DTYPE), one per frame: the five integer words (sse_y_lo, sse_y_hi, sse_rgb_lo, sse_rgb_hi,
+        ssim_q), windows, mse_y, mse_rgb, pu_psnr, pu_psnr_rgb (inf for identical frames) and pu_ssim (exactly 1 for them)."""
+        return self._batch_wait("_pending_u").reshape(-1)
+
+    def pu21_maps(self):
+        """LAB LIBRARY ONLY: the two q_Y maps of the last PU21 batch, after its wait -> [n, 2, h, w] uint32 (ref, dist)"""
+        fn = getattr(self.lib, "vqa_pu21_lab_read_maps", None)
+        if fn is None or fn.argtypes is None:
+            raise RuntimeError("the PU21 maps can be read back from the lab library only")
+        out = np.empty(self._pu21_shape, np.uint32)
+        N.check(fn(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size), "vqa_pu21_lab_read_maps", self.ctx)
+        return out
+
+    def pu21(self, ref, dist, planes, model=None, transfer="pq", full_range=False, frame_bytes=None, maps=False):
+        """PU21-PSNR and PU21-SSIM per frame for n frame pairs; returns [n] structured array (PU21_DTYPE); on the lab library
+        maps=True returns (records, q_Y [n, 2, h, w] uint32)."""
+        self.pu21_submit(ref, dist, planes, model, transfer, full_range, frame_bytes)
+        rec = self.pu21_wait()
+        return (rec, self.pu21_maps()) if maps else rec
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -941,7 +984,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_SUM:
+        for k in N.K_IDS_GRAND:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -366,6 +366,41 @@ def frame_delta_itp(reference, encoded, layout="bgr24", height=None, width=None,
     return np.ascontiguousarray(r["de_mean"]), np.ascontiguousarray(r["de_max"])
 
 
+def _check_pu21(transfer, full_range):
+    """the transfer and range arguments of the PU21 entry points; anything unknown is a ValueError"""
+    if not (isinstance(transfer, str) and transfer in N.ITP_TRANSFERS):
+        raise ValueError("pu21_transfer must be 'pq' or 'hlg'")
+    if not isinstance(full_range, bool):
+        raise ValueError("pu21_full_range must be True or False")
+
+
+def frame_pu21(reference, encoded, layout="bgr24", height=None, width=None, transfer="pq", full_range=False, engine=None,
+               batch_size=64, device=None):
+    """Per-frame PU21-PSNR and PU21-SSIM (Engine.pu21 through the one-pass pipeline of frame_quality; both streams are uploaded
+    once): the three planes of a pixel taken together and read as a BT.2020 signal, turned into display light and PU21-encoded, by
+    the definition in include/vqa.h - the planar YUV layouts as BT.2020 non-constant luminance with replicated chroma, bgr24 as
+    B, G, R; transfer "pq" or "hlg" (HLG on a 1000 cd/m2 display); full_range False (limited) or True (ignored for bgr24).
+    Returns (pu_psnr [n], pu_psnr_rgb [n], pu_ssim [n], mse_y [n], mse_rgb [n]), float64: the PSNRs at a peak of 256 PU units (inf
+    for identical frames, not capped here), the Gaussian SSIM of the PU-encoded luminance (exactly 1 for identical frames) and the
+    mean squared errors in PU units.  Luma at least 16 x 16; a one-plane layout, an unknown transfer or range is a ValueError."""
+    if len(LAYOUTS[layout][1]) != 3:
+        raise ValueError("pu21 needs three planes")
+    _check_pu21(transfer, full_range)
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, pu21="only", pu21_transfer=transfer,
+                                                                 pu21_full_range=full_range),
+                      batch_size=batch_size, engine=engine, device=device)
+    r = q[-1]
+    return tuple(np.ascontiguousarray(r[k]) for k in ("pu_psnr", "pu_psnr_rgb", "pu_ssim", "mse_y", "mse_rgb"))
+
+
+PU21_PSNR_CAP = 100.0   # the row's PU_PSNR and PU_PSNR_RGB: a frame's value (inf for identical frames) is capped here before pooling
+
+
 def _brisque_model(model_path, range_path):
     """the config's two paths -> a model or None; loaded before the pass starts, so a bad file costs no GPU time"""
     if model_path is None:
@@ -378,7 +413,7 @@ def _brisque_model(model_path, range_path):
 
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
                   cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None,
-                  delta_itp=None):
+                  delta_itp=None, pu21=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -413,6 +448,9 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     keys and before vmaf, likewise.  The model never reads it.
     delta_itp: None, or the dE_ITP records [n] (engine.ITP_DTYPE, one per frame): the log then also carries delta_itp (the
     frame's mean) and delta_itp_max (its largest pixel), after mdsi and before vmaf, likewise.  The model never reads them.
+    pu21: None, or the PU21 records [n] (engine.PU21_DTYPE, one per frame): the log then also carries pu_psnr, pu_psnr_rgb (each
+    capped at 100.0: identical frames give inf, which JSON cannot hold and a mean cannot pool) and pu_ssim, after delta_itp_max
+    and before vmaf, likewise.  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -481,6 +519,11 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         delta_itp = np.asarray(delta_itp).reshape(-1)
         names += ["delta_itp", "delta_itp_max"]
         cols += [delta_itp["de_mean"].astype(np.float64), delta_itp["de_max"].astype(np.float64)]
+    if pu21 is not None:
+        pu21 = np.asarray(pu21).reshape(-1)
+        names += ["pu_psnr", "pu_psnr_rgb", "pu_ssim"]
+        cols += [np.minimum(pu21["pu_psnr"].astype(np.float64), PU21_PSNR_CAP),
+                 np.minimum(pu21["pu_psnr_rgb"].astype(np.float64), PU21_PSNR_CAP), pu21["pu_ssim"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -604,7 +647,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE,
                        gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
                        brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
-                       delta_itp_transfer="pq", delta_itp_full_range=False):
+                       delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
+                       pu21_full_range=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -638,6 +682,9 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     delta_itp=True: likewise dE_ITP of ITU-R BT.2124, the three planes together read as a BT.2020 signal (delta_itp, the frame's
     mean, and delta_itp_max, its largest pixel; three-plane layouts only; delta_itp_transfer "pq" | "hlg", delta_itp_full_range
     False (limited) | True; a model file does not turn it on).
+    pu21=True: likewise PU21-PSNR and PU21-SSIM, the three planes together read as a BT.2020 signal, as display light in PU21 units
+    (pu_psnr and pu_psnr_rgb, capped at 100.0, and pu_ssim; three-plane layouts only; pu21_transfer "pq" | "hlg", pu21_full_range
+    False (limited) | True; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -667,7 +714,11 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             if len(LAYOUTS[layout][1]) != 3:
                 raise ValueError("delta_itp needs three planes")
             _check_itp(delta_itp_transfer, delta_itp_full_range)
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi or delta_itp:
+        if pu21:
+            if len(LAYOUTS[layout][1]) != 3:
+                raise ValueError("pu21 needs three planes")
+            _check_pu21(pu21_transfer, pu21_full_range)
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi or delta_itp or pu21:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -680,10 +731,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              artifacts=bool(artifacts), brisque=brisque,
                                                              mdsi=bool(mdsi), itp=bool(delta_itp),
                                                              itp_transfer=delta_itp_transfer,
-                                                             itp_full_range=delta_itp_full_range),
+                                                             itp_full_range=delta_itp_full_range, pu21=bool(pu21),
+                                                             pu21_transfer=pu21_transfer,
+                                                             pu21_full_range=pu21_full_range),
                               batch_size=batch_size, on_quality=wr, device=device)
             _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts, brisque, bmodel, mdsi, delta_itp)
+                               artifacts, brisque, bmodel, mdsi, delta_itp, pu21)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -722,11 +775,13 @@ MODE_KEYS = {
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
                        cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
-                       mdsi=False, delta_itp=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000, MDSI and dE_ITP of a pass (the
+                       mdsi=False, delta_itp=False, pu21=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000, MDSI, dE_ITP and PU21 figures of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = itp = None
-    if delta_itp:  # the tuple's last element, then MDSI's
+    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = itp = pus = None
+    if pu21:       # the tuple's last element, then dE_ITP's
+        pus, q = q[-1], q[:-1]
+    if delta_itp:  # then MDSI's
         itp, q = q[-1], q[:-1]
     if mdsi:       # then BRISQUE's
         mds, q = q[-1], q[:-1]
@@ -772,6 +827,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["mdsi"] = mds
     if itp is not None:
         more["delta_itp"] = itp
+    if pus is not None:
+        more["pu21"] = pus
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -832,6 +889,13 @@ def _check_mode_keys(config):
     if "delta_itp_range" in config and not (isinstance(config["delta_itp_range"], str) and
                                             config["delta_itp_range"] in ITP_RANGES):
         raise ValueError("delta_itp_range must be \"limited\" or \"full\".")
+    if "pu21" in config and not isinstance(config["pu21"], bool):
+        raise ValueError("pu21 must be true or false.")
+    if "pu21_transfer" in config and not (isinstance(config["pu21_transfer"], str) and
+                                          config["pu21_transfer"] in N.ITP_TRANSFERS):
+        raise ValueError("pu21_transfer must be \"pq\" or \"hlg\".")
+    if "pu21_range" in config and not (isinstance(config["pu21_range"], str) and config["pu21_range"] in ITP_RANGES):
+        raise ValueError("pu21_range must be \"limited\" or \"full\".")
     if "ciede_weights" in config:
         k = config["ciede_weights"]
         if not (isinstance(k, (list, tuple)) and len(k) == 3 and
@@ -906,6 +970,10 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         pixel's value over all frames, after MDSI; three-plane pixfmts only; default false; a model file does not turn it on),
         delta_itp_transfer ("pq" default | "hlg": BT.2100's transfer function, HLG on a 1000 cd/m2 display), delta_itp_range
         ("limited" default | "full"; no effect on bgr24),
+        pu21 (true: the row gains PU_PSNR and PU_PSNR_RGB, the pooled means of the per-frame PU21-PSNR of the luminance and of the
+        three channels - display light in PU21 units, peak 256, each frame capped at 100.0 -, and PU_SSIM, the pooled mean of the
+        per-frame PU21-SSIM, after DELTA_ITP_MAX; three-plane pixfmts only; default false; a model file does not turn it on),
+        pu21_transfer ("pq" default | "hlg"), pu21_range ("limited" default | "full"; no effect on bgr24),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -942,6 +1010,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     itp = config.get("delta_itp", False)
     itp_tf = config.get("delta_itp_transfer", "pq")
     itp_full = ITP_RANGES[config.get("delta_itp_range", "limited")]
+    pu = config.get("pu21", False)
+    pu_tf = config.get("pu21_transfer", "pq")
+    pu_full = ITP_RANGES[config.get("pu21_range", "limited")]
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -1000,14 +1071,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                                      gmsd=gms, cambi=cam, xpsnr=xps,
                                                                      haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq,
                                                                      mdsi=mds, itp=itp, itp_transfer=itp_tf,
-                                                                     itp_full_range=itp_full),
+                                                                     itp_full_range=itp_full, pu21=pu,
+                                                                     pu21_transfer=pu_tf, pu21_full_range=pu_full),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds or itp:
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds or itp or pu:
             _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
-                               mds, itp)
+                               mds, itp, pu)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -1093,6 +1165,10 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         if "delta_itp" in pooled:
             metrics["DELTA_ITP"] = float(pooled["delta_itp"]["mean"])
             metrics["DELTA_ITP_MAX"] = float(pooled["delta_itp_max"]["max"])
+        if "pu_psnr" in pooled:
+            metrics["PU_PSNR"] = float(pooled["pu_psnr"]["mean"])
+            metrics["PU_PSNR_RGB"] = float(pooled["pu_psnr_rgb"]["mean"])
+            metrics["PU_SSIM"] = float(pooled["pu_ssim"]["mean"])
     return metrics
 
 
@@ -1115,7 +1191,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range, pu21, pu21_transfer, pu21_range;
     #                           and that a vmaf_model_path names a readable file
 
 
