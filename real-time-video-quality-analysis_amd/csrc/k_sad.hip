@@ -9,23 +9,301 @@
 //   the displaced block is inside the frame; winner = min SAD, then min dx^2+dy^2,
 //   then raster order; outputs: sum of winning SADs and a histogram of dx^2+dy^2.
 //
-// Mapping: one wave handles 4 horizontally adjacent blocks.  lane = blk*16 + dyi:
-// each lane owns one vertical displacement dy = dyi-8 of one block and evaluates
-// all 16 horizontal displacements dx = -8..7 with V_QSAD_PK_U16_U8, which yields
-// four packed 16-bit SADs (4 consecutive dx) per instruction: 16 absolute
-// differences per lane-op.  The 16-bit accumulators cannot overflow
-// (16*16*255 = 65280).  The (sad, d2, raster) key is min-reduced over the 16
-// lanes of a block with xor-shuffles.  Current block rows and the previous
-// frame's 31 x 80 search window are staged in LDS per wave.
+// Mapping: one wave handles a tile of 16 blocks, arranged 16x1, 8x2 or 4x4 (chosen per launch: the arrangement
+// that leaves the fewest empty block slots).  lane = blk*4 + g: each lane owns one dx group of one block - the four
+// horizontal displacements dx = 4g-8 .. 4g-5, which is what one V_QSAD_PK_U16_U8 yields (four packed 16-bit SADs:
+// 16 absolute differences per lane-op) - for ALL vertical displacements |dy| <= 7.  The lane holds its block's 16
+// current rows in registers and walks the 30 rows of its search window once: window row q is read from LDS once
+// (5 dwords) and meets every current row r with dy = q - 7 - r in range, accumulating into one packed accumulator
+// per dy (15 x 64 bits; 16*16*255 = 65280 fits 16 bits).  dy = -8, which no range <= 7 can reach, is never
+// evaluated: 960 QSADs per lane for what a lane-per-dy mapping spends 1024 on, and ~2 LDS reads per 16 QSADs
+// instead of 3.  The (sad, d2, raster) key is min-reduced over the lane's 60 candidates, then over the 4 lanes of
+// the block with two DPP quad permutes.  Current rows and the previous frame's search window are staged in
+// wave-private LDS; the next tile's bytes are fetched into registers late in the walk, when the registers of the
+// first current rows are free again.
 //
-// Roofline: HBM 2P bytes per frame pair; ~16 QSADs per pixel of VALU work.
+// Roofline: HBM 2P bytes per frame pair; 15 QSADs per pixel of VALU work.
 #include "vqa_dev.hpp"
 #include "vqa_kernels.hpp"
 
 #include <cstdlib>
+#include <utility>
 
 namespace vqa {
 
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_min(uint32_t v)
+{
+    return min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ void wave_lds_sync()
+{
+    // LDS traffic between lanes of ONE wave: the LDS queue is in order per wave, only the compiler must not reorder
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Geometry of one wave's tile: AX x AY blocks (AX * AY = 16)
+template <int AX, int AY>
+struct sad_tile {
+    static constexpr int WR = AY * 16 + 14;            // window rows y0-7 .. y0+16AY+6
+    static constexpr int WD = AX * 4 + 4;              // dwords per window row: x0-8 .. x0+16AX+7
+    static constexpr int UW = AX + 1;                  // 16-byte units per window row
+    static constexpr int RPI = 64 / UW;                // window rows one wave-wide load covers
+    static constexpr int NW = (WR + RPI - 1) / RPI;    // wave-wide loads per window
+    static constexpr int CR = AY * 16, CD = AX * 4;    // current rows, dwords per current row
+    static constexpr int CRI = 64 / AX;                // current rows one wave-wide load covers (4 loads per tile)
+    static constexpr int QF = 26;                      // the walk fetches the next tile before window row QF: current
+                                                       // rows 0..QF-16 are dead by then and lend their registers
+    struct __align__(16) lds {
+        uint32_t cur[CR][CD];
+        uint32_t prv[WR][WD]; // col 0 <-> x0-8, row 0 <-> y0-7
+    };
+};
+
+// 16 bytes through a scalar base + lane offset (uniform_ptr): one global_load_dwordx4 v, v_off, s[base]
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_a8 __attribute__((aligned(8))); // window columns start 8 bytes before a 16-byte boundary
+__device__ __forceinline__ uint4 load16_g(gptr_u8 p)
+{
+    const u32x4 v = *(const __attribute__((address_space(1))) u32x4_a8 *)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// 16 bytes at p (8-byte aligned), each half read only if it lies inside [0, pitch) of its row; x = column of p
+__device__ __forceinline__ uint4 load16_cols(const uint8_t *p, int x, int pitch)
+{
+    uint2 a = make_uint2(0u, 0u), b = make_uint2(0u, 0u);
+    if (x >= 0 && x + 8 <= pitch) a = *(const uint2 *)p;
+    if (x + 8 >= 0 && x + 16 <= pitch) b = *(const uint2 *)(p + 8);
+    return make_uint4(a.x, a.y, b.x, b.y);
+}
+
+// Window row Q of a lane's walk: its 5 dwords (read from LDS one row ahead, d) meet every current row r = Q - a,
+// a = dy + 7, that has one.  Current row Q + 1 and window row Q + 1 are read here, for the next step; the empty
+// asm statements keep the compiler from hoisting all 46 reads to the top of the walk (318 VGPRs).  Templates, not loops:
+// every register index of the 960-QSAD walk must be a compile-time constant.
+template <int Q, int WD, int CD, bool R7>
+__device__ __forceinline__ void sad_walk_row(const uint32_t *wbase, const uint32_t *cbase, uint32_t (&d)[5], uint4 (&C)[16],
+                                             uint64_t (&acc)[15], int range)
+{
+    uint32_t n[5] = {0, 0, 0, 0, 0};
+    if (Q + 1 < 30) {
+#pragma unroll
+        for (int i = 0; i < 5; i++) n[i] = wbase[(Q + 1) * WD + i];
+    }
+    if (Q + 1 < 16) C[Q + 1] = *(const uint4 *)(cbase + (Q + 1) * CD);
+    const uint64_t s0 = (uint64_t)d[0] | ((uint64_t)d[1] << 32), s1 = (uint64_t)d[1] | ((uint64_t)d[2] << 32);
+    const uint64_t s2 = (uint64_t)d[2] | ((uint64_t)d[3] << 32), s3 = (uint64_t)d[3] | ((uint64_t)d[4] << 32);
+    constexpr int ALO = Q > 15 ? Q - 15 : 0, AHI = Q < 14 ? Q : 14;
+#pragma unroll
+    for (int a = ALO; a <= AHI; a++) {
+        if (R7 || abs(a - 7) <= range) { // (unreachable displacements: a wave-uniform skip)
+            const uint4 c = C[Q - a];
+            uint64_t v = acc[a];
+            v = __builtin_amdgcn_qsad_pk_u16_u8(s0, c.x, v);
+            v = __builtin_amdgcn_qsad_pk_u16_u8(s1, c.y, v);
+            v = __builtin_amdgcn_qsad_pk_u16_u8(s2, c.z, v);
+            v = __builtin_amdgcn_qsad_pk_u16_u8(s3, c.w, v);
+            acc[a] = v;
+        }
+    }
+    // pin the order: this row's QSADs end here, and no LDS read of a later row starts before
+#pragma unroll
+    for (int a = ALO; a <= AHI; a++) asm volatile("" : "+v"(acc[a]));
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < 5; i++) d[i] = n[i];
+}
+template <int WD, int CD, bool R7, int Q0, int... I>
+__device__ __forceinline__ void sad_walk_rows(std::integer_sequence<int, I...>, const uint32_t *wbase, const uint32_t *cbase,
+                                              uint32_t (&d)[5], uint4 (&C)[16], uint64_t (&acc)[15], int range)
+{
+    (sad_walk_row<Q0 + I, WD, CD, R7>(wbase, cbase, d, C, acc, range), ...);
+}
+
+template <int AX, int AY, bool R7> // R7: range == 7, every |dy| <= 7 is searched and no accumulator is skipped
+// (three waves per SIMD: what 42-49 KB of LDS per workgroup allow; the walk needs 134-152 VGPRs of the 168 that leaves)
+__global__ __launch_bounds__(256, 3) void k_block_sad(const uint8_t *__restrict__ planes, int pitch,
+                                                   int64_t plane_stride, int h, int w, int range, int first_has_prev,
+                                                   vqa_frame_metrics *__restrict__ res, int bpf, int n_wg)
+{
+    typedef sad_tile<AX, AY> T;
+    __shared__ typename T::lds lds[4];
+    __shared__ unsigned hist[129];
+    __shared__ unsigned long long red[4];
+    if (R7) range = 7;
+    // XCD-aware placement (workgroup ids go round-robin over the 8 XCDs): XCD c takes the contiguous range
+    // [c * per, (c + 1) * per) of the (frame, tile) space, so all tiles of a frame - whose search windows
+    // overlap - meet in ONE L2 instead of eight (PMC traffic 1.71x -> see profiles/)
+    const int per = (n_wg + 7) >> 3;
+    const int wg = (int)(blockIdx.x & 7u) * per + (int)(blockIdx.x >> 3);
+    if ((int)(blockIdx.x >> 3) >= per || wg >= n_wg) return;
+    const int f = wg / bpf, bx = wg - f * bpf;
+    if (f == 0 && !first_has_prev) return;
+    const uint8_t *curr = planes + (int64_t)(f + 1) * plane_stride;
+    const uint8_t *prev = planes + (int64_t)f * plane_stride;
+    const int nby = h >> 4, nbx = w >> 4;
+    const int ngx = (nbx + AX - 1) / AX, ngy = (nby + AY - 1) / AY;
+    const int tasks = ngy * ngx;
+    const int lane = lane_id();
+    const int wv = __builtin_amdgcn_readfirstlane((int)wave_id()); // wave-uniform: tile geometry stays on the scalar unit
+    typename T::lds &L = lds[wv];
+    for (int i = threadIdx.x; i < 129; i += 256) hist[i] = 0;
+    __syncthreads();
+    unsigned long long sad_total = 0;
+
+    // ---- the staging, in 16-byte units: a lane owns 4 of the tile's 256 current-row units, and one unit in each
+    // group of RPI window rows.  Their offsets from the tile origin never change, so an INTERIOR tile (window inside
+    // the plane) loads with a scalar base + 32-bit lane offsets.  The walk needs every register it can get (64 for the
+    // current rows, 30 for the accumulators), so nothing but the lane id is carried across it: each user derives its
+    // lane constants again (a handful of VALU operations per tile) from an id the compiler cannot see through.
+    struct stage_lane {
+        int cr0, cc;      // current unit i: row cr0 + CRI * i, column unit cc
+        int wr0, wc, wrl; // window unit i: row wr0 + RPI * i (the last one: wrl), column unit wc
+        __device__ __forceinline__ explicit stage_lane(int ln)
+        {
+            asm volatile("" : "+v"(ln));
+            cr0 = ln / AX; cc = ln % AX;
+            const int wu = min(ln, T::RPI * T::UW - 1); // (lanes past the last unit alias it)
+            wr0 = wu / T::UW; wc = wu - wr0 * T::UW;
+            wrl = min(wr0 + T::RPI * (T::NW - 1), T::WR - 1); // (rows past the last one alias it)
+        }
+    };
+
+    uint4 pcur[4], pprv[T::NW]; // the NEXT tile's bytes, in flight while the tail of this tile's QSADs runs
+    auto fetch = [&](int t) {
+        if (t >= tasks) { // wave-uniform; the last tile: nothing to fetch (defined values, so that the registers are
+                          // not carried around the loop)
+#pragma unroll
+            for (int i = 0; i < 4; i++) pcur[i] = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+            for (int i = 0; i < T::NW; i++) pprv[i] = make_uint4(0u, 0u, 0u, 0u);
+            return;
+        }
+        const int gy = t / ngx, gx = t - gy * ngx;
+        const int y0 = gy * (16 * AY), x0 = gx * (16 * AX);
+        const bool interior = (y0 >= 7) && (y0 + 16 * AY + 7 <= h) && (x0 >= 8) && (x0 + 16 * AX + 8 <= pitch);
+        const stage_lane S(lane);
+        const int cr0 = S.cr0, cc = S.cc, wr0 = S.wr0, wc = S.wc, wrl = S.wrl;
+        if (interior) {
+            const int coff = cr0 * pitch + cc * 16;
+            const int woff = wr0 * pitch + wc * 16, woffl = (wrl - T::RPI * (T::NW - 1)) * pitch + wc * 16;
+            const uint8_t *cb = curr + (int64_t)y0 * pitch + x0, *pb = prev + (int64_t)(y0 - 7) * pitch + (x0 - 8);
+#pragma unroll
+            for (int i = 0; i < 4; i++) pcur[i] = load16_g(uniform_ptr(cb + (int64_t)(i * T::CRI) * pitch) + coff);
+#pragma unroll
+            for (int i = 0; i < T::NW; i++)
+                pprv[i] = load16_g(uniform_ptr(pb + (int64_t)(i * T::RPI) * pitch) + (i == T::NW - 1 ? woffl : woff));
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int y = min(y0 + cr0 + T::CRI * i, h - 1), x = x0 + cc * 16;
+                pcur[i] = load16_cols(curr + (int64_t)y * pitch + x, x, pitch);
+            }
+#pragma unroll
+            for (int i = 0; i < T::NW; i++) {
+                const int r = i == T::NW - 1 ? wrl : wr0 + T::RPI * i;
+                const int y = min(max(y0 - 7 + r, 0), h - 1), x = x0 - 8 + wc * 16;
+                pprv[i] = load16_cols(prev + (int64_t)y * pitch + x, x, pitch);
+            }
+        }
+    };
+    const int stride = bpf * 4;
+    fetch(bx * 4 + wv);
+    for (int t = bx * 4 + wv; t < tasks; t += stride) { // wave-uniform: no workgroup barrier inside
+        const int gy = t / ngx, gx = t - gy * ngx;
+        const int y0 = gy * (16 * AY), x0 = gx * (16 * AX);
+        wave_lds_sync(); // the previous tile's LDS reads are done
+        {
+            const stage_lane S(lane);
+#pragma unroll
+            for (int i = 0; i < 4; i++) *(uint4 *)&L.cur[S.cr0 + T::CRI * i][S.cc * 4] = pcur[i];
+#pragma unroll
+            for (int i = 0; i < T::NW; i++) *(uint4 *)&L.prv[i == T::NW - 1 ? S.wrl : S.wr0 + T::RPI * i][S.wc * 4] = pprv[i];
+        }
+        wave_lds_sync();
+
+        int lw = lane; // (opaque per tile: 30 hoisted window-row addresses would cost 60 VGPRs)
+        asm volatile("" : "+v"(lw));
+        const uint32_t *wbase = &L.prv[16 * ((lw >> 2) / AX)][4 * ((lw >> 2) % AX) + (lw & 3)]; // the lane's 30 x 20-byte window
+        const uint32_t *cbase = &L.cur[16 * ((lw >> 2) / AX)][4 * ((lw >> 2) % AX)];            // the lane's block
+        uint4 C[16];
+        uint32_t d[5];
+        uint64_t acc[15];
+#pragma unroll
+        for (int a = 0; a < 15; a++) acc[a] = 0;
+        C[0] = *(const uint4 *)cbase;
+#pragma unroll
+        for (int i = 0; i < 5; i++) d[i] = wbase[i];
+        sad_walk_rows<T::WD, T::CD, R7, 0>(std::make_integer_sequence<int, T::QF>(), wbase, cbase, d, C, acc, range);
+        fetch(t + stride);
+        sad_walk_rows<T::WD, T::CD, R7, T::QF>(std::make_integer_sequence<int, 30 - T::QF>(), wbase, cbase, d, C, acc, range);
+        // ---- winner of the lane's 60 candidates.  An invalid candidate carries SAD 0xffff, which no block can reach.
+        // key = (sad << 16) | (d2 << 8) | raster, raster = (dy + 8) * 16 + dx + 8: the dx part is the lane's own (4 values),
+        // the dy part a compile-time constant of the accumulator
+        int le = lane;
+        asm volatile("" : "+v"(le));
+        const int g = le & 3, blkx = (le >> 2) % AX, blky = (le >> 2) / AX;
+        const int by0 = (gy * AY + blky) * 16, bx0 = (gx * AX + blkx) * 16; // the lane's block
+        const bool interior = (y0 >= 7) && (y0 + 16 * AY + 7 <= h) && (x0 >= 7) && (x0 + 16 * AX + 7 <= w);
+        auto lane_best = [&](bool check) -> uint32_t {
+            const bool there = (by0 + 16 <= h) && (bx0 + 16 <= w);
+            const int dylo = max(-range, -by0), dyhi = there ? min(range, h - 16 - by0) : -99;
+            const int dxlo = max(-range, -bx0), dxhi = min(range, w - 16 - bx0);
+            uint32_t m[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+#pragma unroll
+            for (int a = 0; a < 15; a++) {
+                const int dy = a - 7;
+                const uint32_t dyc = ((uint32_t)(dy * dy) << 8) | ((uint32_t)(dy + 8) << 4);
+                uint32_t lo = (uint32_t)acc[a], hi = (uint32_t)(acc[a] >> 32);
+                if (check && (dy < dylo || dy > dyhi)) lo = hi = 0xffffffffu;
+                m[0] = min(m[0], (lo << 16) | dyc);
+                m[1] = min(m[1], (lo & 0xffff0000u) | dyc);
+                m[2] = min(m[2], (hi << 16) | dyc);
+                m[3] = min(m[3], (hi & 0xffff0000u) | dyc);
+            }
+            uint32_t best = 0xffffffffu;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int dx = 4 * g - 8 + k;
+                // d2 = dy^2 + dx^2 <= 113 and the raster's two nibbles: no carry
+                uint32_t key = m[k] + (((uint32_t)(dx * dx) << 8) | (uint32_t)(dx + 8));
+                // (dx = -8 rides along in group 0's QSADs and is never a candidate: dxlo >= -7)
+                if (dx < -7 || (check && (dx < dxlo || dx > dxhi))) key = 0xffffffffu;
+                best = min(best, key);
+            }
+            return best;
+        };
+        uint32_t best;
+        if (R7 && interior) best = lane_best(false); // wave-uniform: every candidate of every block of the tile is valid
+        else best = lane_best(true);
+        // min over the block's 4 dx groups (one DPP quad); every lane ends with the quad's minimum
+        best = dpp_min<0xB1>(best); // quad_perm [1,0,3,2]
+        best = dpp_min<0x4E>(best); // quad_perm [2,3,0,1]
+        if (g == 0 && best < 0xffff0000u) {
+            sad_total += best >> 16;
+            atomicAdd(&hist[(best >> 8) & 0xffu], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 129; i += 256)
+        if (hist[i]) atomicAdd(&res[f].mv_d2_hist[i], hist[i]);
+    const unsigned long long tot = block_sum_u64(sad_total, red);
+    if (threadIdx.x == 0) {
+        if (tot) atomicAdd((unsigned long long *)&res[f].sad_sum, tot);
+        if (bx == 0) res[f].sad_blocks = (uint32_t)(nby * nbx);
+    }
+}
+
+#ifdef VQA_AB_VARIANTS // lab build only
+// ---------------------------------------------------------------------------
+// Lane-per-dy form (VQA_SAD_VARIANT=1; the shipped kernel until the lane-per-dx-group form above replaced it): one
+// wave handles 4 horizontally adjacent blocks, lane = blk*16 + dyi owns ONE vertical displacement dy = dyi-8 of one
+// block and all 16 horizontal ones.  The lane dy = -8 can never win and still runs its 256 QSADs, and every lane
+// re-reads current and window rows from LDS for each of its 16 rows (3 ds_read_b128 per 16 QSADs).  Kept for the A/B.
+// ---------------------------------------------------------------------------
 constexpr int PW_DW = 20; // prev window row: 80 bytes
 constexpr int PROWS = 31; // rows y0-8 .. y0+22
 
@@ -34,13 +312,7 @@ struct __align__(16) sad_lds {
     uint32_t prv[PROWS][PW_DW];  // 31 rows x 80 bytes, col 0 <-> x0-8
 };
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_min(uint32_t v)
-{
-    return min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false));
-}
-
-__global__ __launch_bounds__(256) void k_block_sad(const uint8_t *__restrict__ planes, int pitch,
+__global__ __launch_bounds__(256) void k_block_sad_dy(const uint8_t *__restrict__ planes, int pitch,
                                                    int64_t plane_stride, int h, int w, int range, int first_has_prev,
                                                    vqa_frame_metrics *__restrict__ res, int bpf, int n_wg)
 {
@@ -200,7 +472,6 @@ __global__ __launch_bounds__(256) void k_block_sad(const uint8_t *__restrict__ p
     }
 }
 
-#ifdef VQA_AB_VARIANTS // lab build only
 // ---------------------------------------------------------------------------
 // Pruned form (VQA_SAD_VARIANT=2; NOT the default): the same winner, found without evaluating most candidates.
 // Measured on MI355X, 256 x 1080p (round 2): S-natural 1.59-1.65 ms, S-noise 3.5 ms, against 1.29 ms for the exhaustive
@@ -236,13 +507,6 @@ struct __align__(16) sea_lds {
     uint32_t best[4];                 // per block: min key of the evaluated candidates
     uint8_t list[256];                // surviving (lane << 2 | group) items
 };
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    // LDS traffic between lanes of ONE wave: the LDS queue is in order per wave, only the compiler must not reorder
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ uint2 add2(uint2 a, uint2 b) { return make_uint2(a.x + b.x, a.y + b.y); }
 
@@ -475,24 +739,55 @@ __global__ __launch_bounds__(256) void k_block_sad_sea(const uint8_t *__restrict
 
 #endif // VQA_AB_VARIANTS
 
+template <int AX, int AY>
+static void launch_tiles(hipStream_t st, const uint8_t *planes, int pitch, int64_t plane_stride, int n, int h, int w, int range,
+                         bool first_has_prev, vqa_frame_metrics *res)
+{
+    const int tasks = ((h / 16 + AY - 1) / AY) * ((w / 16 + AX - 1) / AX);
+    int bpf = (tasks + 4 * 4 - 1) / (4 * 4); // ~4 tiles per wave
+    bpf = bpf < 1 ? 1 : (bpf > 256 ? 256 : bpf);
+    const dim3 grid((unsigned)(8 * (((long long)bpf * n + 7) / 8)));
+    if (range == 7)
+        hipLaunchKernelGGL((k_block_sad<AX, AY, true>), grid, dim3(256), 0, st, planes, pitch, plane_stride, h, w, range,
+                           (int)first_has_prev, res, bpf, bpf * n);
+    else
+        hipLaunchKernelGGL((k_block_sad<AX, AY, false>), grid, dim3(256), 0, st, planes, pitch, plane_stride, h, w, range,
+                           (int)first_has_prev, res, bpf, bpf * n);
+}
+
 void launch_block_sad(hipStream_t st, const uint8_t *planes, int pitch, int64_t plane_stride, int n, int h, int w,
                       int range, bool first_has_prev, vqa_frame_metrics *res)
 {
     if (n <= 0) return;
     const int nby = h / 16, nbx = w / 16;
-    const int tasks = nby * ((nbx + 3) / 4);
-    int bpf = (tasks + 4 * 4 - 1) / (4 * 4); // ~4 tasks per wave
-    bpf = bpf < 1 ? 1 : (bpf > 256 ? 256 : bpf);
 #ifdef VQA_AB_VARIANTS
-    static const int variant = ab_knob("VQA_SAD_VARIANT", 0) == 2 ? 2 : 0; // 0 = exhaustive search (shipped), 2 = pruned search
-    if (variant == 2) {
-        hipLaunchKernelGGL(k_block_sad_sea, dim3(bpf, n), dim3(256), 0, st, planes, pitch, plane_stride, h, w, range,
-                           (int)first_has_prev, res);
+    // 0 = lane per dx group (shipped), 1 = lane per dy (its predecessor), 2 = pruned search
+    static const int variant = ab_knob("VQA_SAD_VARIANT", 0);
+    if (variant == 1 || variant == 2) {
+        const int tasks = nby * ((nbx + 3) / 4);
+        int bpf = (tasks + 4 * 4 - 1) / (4 * 4); // ~4 tasks per wave
+        bpf = bpf < 1 ? 1 : (bpf > 256 ? 256 : bpf);
+        if (variant == 2)
+            hipLaunchKernelGGL(k_block_sad_sea, dim3(bpf, n), dim3(256), 0, st, planes, pitch, plane_stride, h, w, range,
+                               (int)first_has_prev, res);
+        else
+            hipLaunchKernelGGL(k_block_sad_dy, dim3((unsigned)(8 * (((long long)bpf * n + 7) / 8))), dim3(256), 0, st, planes,
+                               pitch, plane_stride, h, w, range, (int)first_has_prev, res, bpf, bpf * n);
         return;
     }
+    static const int force = ab_knob("VQA_SAD_TILE", 0); // 1 = 16x1, 2 = 8x2, 3 = 4x4; anything else: the fewest slots
+#else
+    const int force = 0;
 #endif
-    hipLaunchKernelGGL(k_block_sad, dim3((unsigned)(8 * (((long long)bpf * n + 7) / 8))), dim3(256), 0, st, planes, pitch,
-                       plane_stride, h, w, range, (int)first_has_prev, res, bpf, bpf * n);
+    // a wave's 16 blocks as 8x2, 4x4 or 16x1: the arrangement that leaves the fewest block slots empty (1080p, 120 x 67
+    // blocks: 8x2 and 4x4 waste 1.5 %, 16x1 6.7 %); on a tie the first of that order
+    const long long s82 = (long long)((nbx + 7) / 8) * ((nby + 1) / 2), s44 = (long long)((nbx + 3) / 4) * ((nby + 3) / 4);
+    const long long s161 = (long long)((nbx + 15) / 16) * nby;
+    int pick = (s82 <= s44 && s82 <= s161) ? 2 : (s44 <= s161 ? 3 : 1);
+    if (force >= 1 && force <= 3) pick = force;
+    if (pick == 2) launch_tiles<8, 2>(st, planes, pitch, plane_stride, n, h, w, range, first_has_prev, res);
+    else if (pick == 3) launch_tiles<4, 4>(st, planes, pitch, plane_stride, n, h, w, range, first_has_prev, res);
+    else launch_tiles<16, 1>(st, planes, pitch, plane_stride, n, h, w, range, first_has_prev, res);
 }
 
 } // namespace vqa

@@ -14,4 +14,5 @@ k = d["kernels"]["k_block_sad"]
 print("%-22s k_block_sad %.4f ms/launch  frac_hbm %.3f   value %.0f fps" % (sys.argv[1], k["ms_per_launch"], k.get("frac_hbm", 0), d["value"]))
 PY
 }
-run exhaustive_natural natural VQA_SAD_VARIANT=0 && run exhaustive_noise noise VQA_SAD_VARIANT=0 && run pruned_natural natural VQA_SAD_VARIANT=2 && run pruned_noise noise VQA_SAD_VARIANT=2
+# 0 = lane per dx group (shipped), 1 = lane per dy (its predecessor), 2 = pruned search
+run exhaustive_natural natural VQA_SAD_VARIANT=0 && run exhaustive_noise noise VQA_SAD_VARIANT=0 && run lane_per_dy_natural natural VQA_SAD_VARIANT=1 && run lane_per_dy_noise noise VQA_SAD_VARIANT=1 && run pruned_natural natural VQA_SAD_VARIANT=2 && run pruned_noise noise VQA_SAD_VARIANT=2
