@@ -183,7 +183,13 @@ typedef struct vqa_frame_metrics {
  * or step are VQA_ERR_INVALID.  Samples above max = 2^depth - 1 are read as they are, not clipped (as FFmpeg's psnr / ssim
  * filters read them).  The metrics follow FFmpeg for that depth: vf_psnr's peak is max (the caller's stats lines), vf_ssim's
  * constants are .01^2 max^2 64 and .03^2 max^2 64 63 with double end formulas, and the Gaussian SSIM takes data range
- * L = max (C1 = (.01 L)^2, C2 = (.03 L)^2).                                                                             */
+ * L = max (C1 = (.01 L)^2, C2 = (.03 L)^2).
+ * Magnitudes: offset, row_stride and the frame strides of every submit are honoured at any magnitude the allocation holds - a
+ * frame, a plane or a row may start beyond byte 2^31 or 2^32 of its stream (a resident clip of a few hundred 2160p frames does);
+ * every kind forms these addresses in 64 bits.  The one refusal: VQA_SSIM_GAUSS and VQA_SSIM_MS address the rows of a plane with
+ * 32 bits and return VQA_ERR_UNSUPPORTED for a plane whose height * row_stride + width * pixel_step reaches 2^31 (its frames
+ * and its offset may still lie anywhere).  A plane whose last byte, offset + height * row_stride + width * pixel_step, does not
+ * fit int64_t is VQA_ERR_INVALID.  Every depth from 9 to 16 is a tested input of every kind, not only 10, 12 and 16.          */
 typedef struct vqa_plane_desc {
     int32_t width, height;
     int64_t offset;      /* bytes from the start of the frame                 */

@@ -1452,8 +1452,14 @@ template <class F> static int check_planes(const vqa_plane_desc *planes, int n_p
         if (d.width <= 0 || d.height <= 0 || d.offset < 0 || d.pixel_step <= 0 ||
             d.row_stride < (int64_t)d.width * d.pixel_step - (d.pixel_step - B.bps))
             return VQA_ERR_INVALID;
+        // geometry, still: offset and row_stride are the caller's 64-bit fields, and a plane whose last byte does not fit int64_t is
+        // no plane (a wrapped, negative end would shrink the span and pass the frame-stride rule)
+        int64_t rows, end;
+        if (__builtin_mul_overflow((int64_t)d.height, d.row_stride, &rows) || __builtin_add_overflow(d.offset, rows, &end) ||
+            __builtin_add_overflow(end, (int64_t)d.width * d.pixel_step + B.bps, &end))
+            return VQA_ERR_INVALID;
         if (int rc = limits(d)) return rc;
-        const int64_t end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + B.bps;
+        end = d.offset + (int64_t)(d.height - 1) * d.row_stride + (int64_t)(d.width - 1) * d.pixel_step + B.bps;
         B.span = end > B.span ? end : B.span;
     }
     return VQA_OK;

@@ -74,14 +74,15 @@ def plane8(name, h, w, rng):
 
 def plane(name, h, w, depth, seed=0):
     """-> int64 [h, w] plane of `depth` bits.  From 10 bits up the banded contents are made on the 10-bit scale and brought
-    to the depth exactly (t << (depth - 10)); at 8 bits they are made in 8-bit levels (plane8)."""
+    to the depth exactly (t << (depth - 10); at 9 bits t >> 1); at 8 bits they are made in 8-bit levels (plane8)."""
     rng = np.random.default_rng(1000 * h + w + 7 * depth + seed)
     peak = (1 << depth) - 1
     if depth == 8 and name in BANDED:
         return plane8(name, h, w, rng)
 
     def to_depth(t):
-        return np.clip(t, 0, 1023).astype(np.int64) << (depth - 10)
+        t = np.clip(t, 0, 1023).astype(np.int64)
+        return t << (depth - 10) if depth >= 10 else t >> (10 - depth)     # (9 bits: two 10-bit levels a code)
 
     if name == "staircase":
         return to_depth(ramp10(h, w, 300))

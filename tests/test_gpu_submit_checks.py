@@ -126,6 +126,11 @@ CASES = {
     "row stride too small": (lambda m: BASE8.plane(0, row_stride=W - 1), INVALID),
     "row stride too small at 16 bits": (lambda m: BASE16.plane(1, row_stride=2 * W - 2), INVALID),
     "frame stride below the span": (lambda m: BASE8.with_(frame_stride=2 * W * H - 1), INVALID),
+    # a plane whose last byte does not fit int64_t: a wrapped end is negative, leaves the span to plane 0 and would pass the
+    # frame-stride rule (refused before a byte is read: the frames are the small ones)
+    "plane end beyond int64, by the offset": (lambda m: BASE8.plane(1, offset=(1 << 63) - W * H), INVALID),
+    "plane end beyond int64, by the offset at 16 bits": (lambda m: BASE16.plane(1, offset=(1 << 63) - 2 * W * H), INVALID),
+    "plane end beyond int64, by the row stride": (lambda m: BASE8.plane(1, row_stride=1 << 59), INVALID),
     # the metric's own limits
     "plane too narrow": (lambda m: BASE8.plane(0, width=m - 1), UNSUPPORTED),
     "plane too low": (lambda m: BASE8.plane(1, height=m - 1), UNSUPPORTED),
