@@ -434,6 +434,22 @@ typedef struct vqa_pu21_metrics {
     double pu_ssim;       /* ssim_q / (2^24 windows); exactly 1 for identical frames                                           */
 } vqa_pu21_metrics;
 
+/* FSIM and FSIMc of one frame pair, the planes of a pixel taken together (vqa_fsim_submit / vqa_fsim_wait; the definition and the
+ * bounds of the words are stated there).  The three words are the device's integer totals, so the same pair gives the same
+ * words at any place of any batch, from host or device memory; the doubles are formed from them on the host by vqa_fsim_wait. */
+typedef struct vqa_fsim_metrics {
+    uint64_t sum_pc;    /* P: the sum over the N samples of pm = max(p_r, p_d), p = rint(PC 2^24)                              */
+    uint64_t sum_sim;   /* A: the sum of (g pm + 2^23) >> 24, g = rint(S_L 2^24)                                               */
+    uint64_t sum_simc;  /* B: the sum of (gc pm + 2^23) >> 24, gc = rint(S_L C 2^24); gc may be negative: the word is the SIGNED
+                           64-bit sum in two's complement                                                                    */
+    int64_t count;      /* N = hd wd: the samples of the downsampled grid                                                      */
+    int32_t factor;     /* f                                                                                                   */
+    uint32_t flags;     /* bit 0: P == 0 - neither image has any phase congruency (flat against flat included); both scores
+                           are then 1.0 by definition                                                                        */
+    double fsim;        /* A / P; exactly 1 for identical frames                                                               */
+    double fsimc;       /* (signed) B / P; exactly 1 for identical frames; equals fsim under VQA_FSIM_GRAY                     */
+} vqa_fsim_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1417,6 +1433,89 @@ VQA_API double vqa_pu21_encode(double cd_m2);
     VQA_API int vqa_pu21_lab_read_maps(vqa_ctx *ctx, uint32_t *dst, int64_t n_values);
 #endif
 
+/* ---- FSIM / FSIMc (Zhang, Zhang, Mou and Zhang, "FSIM: a feature similarity index for image quality assessment", IEEE TIP
+ * 2011): phase congruency and gradient similarity, with a chromaticity term in the colour form ----
+ * The reference point GMSD, HaarPSI and MDSI were each published against.  1 means identical; smaller is worse.  This is the
+ * authors' FeatureSIM.m and its embedded phasecong2 (Kovesi) AS RECALLED: it is NOT pinned against their MATLAB nor against any
+ * port (neither was available).  Where this text and a tool differ, this text is what is built.
+ * Input, models, box stage.  Exactly vqa_mdsi_submit's: THREE planes of one depth (8 bits, or 9..16 bits as uint16), or ONE plane;
+ *   VQA_FSIM_YUV709, VQA_FSIM_BGR, VQA_FSIM_GRAY give the same R, G, B on the 0..255 scale by the same formulas, the same chroma
+ *   replication and geometry rules, the same f = max(1, floor(min(h, w) / 256 + 0.5)), hd = ceil(h / f), wd = ceil(w / f), window
+ *   offset o = floor(f / 2) - (f - 1) and zero fill, and the same "box-sum the integer samples S0, S1, S2 and the count cnt, then
+ *   ONE 3 x 4 double matrix" with rgb[c][0..3] as stated there and the channel rows
+ *     Y = 0.299 R + 0.587 G + 0.114 B,  I = 0.596 R - 0.274 G - 0.322 B,  Q = 0.211 R - 0.523 G + 0.312 B
+ *     mat[ch][j] = ((a_R rgb[0][j] + a_G rgb[1][j]) + a_B rgb[2][j]) / (f f);  channel = ((mat[ch][0] S0 + mat[ch][1] S1) + mat[ch][2] S2)
+ *     + mat[ch][3] cnt.  VQA_FSIM_GRAY gives I = Q = 0: both rows of the matrix are zero.
+ * Phase congruency of Y, per image, on the hd x wd grid (rows = hd, cols = wd, N = hd wd).
+ *   Centring.  X = Y - Y(0, 0).  The filters have no DC term, so this does not change the definition; it makes a flat grid exactly
+ *     X = 0, every response exactly 0 and PC = 0 (a dense DFT of a constant would leave rounding noise, and noise over noise).
+ *   Frequency grids.  For a length n, range(n) = (-(n-1)/2 .. (n-1)/2) / (n-1) if n is odd, else (-n/2 .. n/2-1) / n; x over cols, y
+ *     over rows; radius = ifftshift(sqrt(x^2 + y^2)), theta = ifftshift(atan2(-y, x)); lp = 1 / (1 + (radius / 0.45)^30), taken
+ *     BEFORE radius(0,0) is set to 1.
+ *   Scales s = 0..3.  fo = 1 / (6 2^s); logGabor_s = exp(-(ln(radius / fo))^2 / (2 (ln 0.55)^2)) lp, and logGabor_s(0,0) = 0.
+ *   Orientations o = 0..3.  a = o pi / 4; ds = sin(theta) cos a - cos(theta) sin a, dc = cos(theta) cos a + sin(theta) sin a,
+ *     dtheta = |atan2(ds, dc)|, spread_o = exp(-dtheta^2 / (2 sigma^2)), sigma = (pi / 4) / 1.2; filt_{s,o} = logGabor_s spread_o.
+ *     vqa_fsim_filter writes one table, formed in double on the host; the device uses the same tables.
+ *   Responses.  F = fft2(X), EO_{s,o} = ifft2(F filt_{s,o}) (complex).  Per orientation, sums over s = 0..3 in order:
+ *     An = sum |EO_s| (|z| = sqrt(Re^2 + Im^2)), sE = sum Re, sO = sum Im; XE = sqrt(sE^2 + sO^2) + 1e-4, mE = sE / XE, mO = sO / XE;
+ *     Energy_o = sum ((Re_s mE + Im_s mO) - |Re_s mO - Im_s mE|).
+ *   Noise threshold.  med_o = MATLAB's median of |EO_{0,o}|^2 = Re^2 + Im^2 over the N samples (even N: 0.5 (a + b) of the two middle
+ *     values); T_o = c_o sqrt(med_o); c_o = sqrt(S_o / (ln 2 EM_o)) (sqrt(pi / 2) + 2 sqrt(2 - pi / 2)) / 1.7, EM_o = sum filt_{0,o}^2,
+ *     S_o = sum_x (sum_s real(ifft2(filt_{s,o})) sqrt(N))^2 - the file's EstSumAn2 + 2 EstSumAiAj, tau, k = 2 and T / 1.7 folded
+ *     into one geometry constant.  By Parseval S_o = sum_k (sum_s fe_{s,o}(k))^2, fe(k) = (filt(k) + filt(-k mod (hd, wd))) / 2, which is
+ *     how the host forms it; vqa_fsim_noise_factor returns c_o.
+ *   Result.  PC = (sum_o max(Energy_o - T_o, 0)) / (sum_o An_o), sums over o = 0..3 in order, and 0 where the denominator is 0.
+ * Similarity and pooling.
+ *   Scharr gradient of the UNCENTRED Y, zeros outside the grid (vqa_gmsd_submit's convention), with x(di, dj) = Y(i + di, j + dj):
+ *     gx = (((3 x(-1,1) + 10 x(0,1)) + 3 x(1,1)) - ((3 x(-1,-1) + 10 x(0,-1)) + 3 x(1,-1))) / 16
+ *     gy = (((3 x(1,-1) + 10 x(1,0)) + 3 x(1,1)) - ((3 x(-1,-1) + 10 x(-1,0)) + 3 x(-1,1))) / 16
+ *     (conv2(Y, [3 0 -3; 10 0 -10; 3 0 -3] / 16, 'same') and its transpose);  q = gx^2 + gy^2
+ *     S_G = (2 sqrt(q_r q_d) + 160) / ((q_r + q_d) + 160)   (vqa_mdsi_submit's form: equal inputs give exactly 1)
+ *   S_PC = (2 (PC_r PC_d) + 0.85) / ((PC_r^2 + PC_d^2) + 0.85), PC_m = max(PC_r, PC_d), S_L = S_G S_PC.
+ *   Chroma.  S_I = (2 (I_r I_d) + 200) / ((I_r^2 + I_d^2) + 200), S_Q likewise; x = S_I S_Q; C = |x|^0.03 for x >= 0 and
+ *     |x|^0.03 cos(0.03 pi) for x < 0 (the real part of the complex power the file takes).
+ *   FSIM = sum S_L PC_m / sum PC_m;  FSIMc = sum S_L C PC_m / sum PC_m.  (fsim of a colour input is the authors' FSIM on Y.)
+ * How the device rounds.  Everything in double, contraction off, in the order written.  The transforms are dense DFTs, complex
+ *   matrix products on the fp64 matrix cores with the twiddle matrices W_n[j][k] = exp(-2 pi i (j k mod n) / n) formed in double on
+ *   the host: F = W_h (X W_w), EO = (conj(W_h) (F filt)) conj(W_w) / N, every output a sum over k IN ORDER (a matrix instruction
+ *   adds four k at a time), so it does not depend on the batch.  Then TWO roundings:
+ *     p = rint(PC 2^24) ONCE, a uint32 map per image; from there on everything is a function of the two maps and of the input;
+ *     with PC = p 2^-24: g = rint(S_L 2^24), gc = rint((S_L C) 2^24) (signed), pm = max(p_r, p_d).
+ *   The three 64-bit words P = sum pm, A = sum (g pm + 2^23) >> 24, B = sum (gc pm + 2^23) >> 24 (an arithmetic shift) are added
+ *   as integers: no overflow for N <= 2^28, and no dependence on tiling, batch or the order in which workgroups retire.
+ *   vqa_fsim_wait forms fsim = A / P and fsimc = B / P in double.  Identical frames give g = gc = 2^24 (2 (p p) = p p + p p,
+ *   sqrt(q q) = q, 1^0.03 = 1), so A = B = P and both scores are exactly 1.0.  P = 0 (structureless frames, flat against flat
+ *   included) gives 1.0, 1.0 and bit 0 of flags; never a NaN.
+ * Kernels, per sub-slice of frames: k_fsim_luma (MDSI's box stage: Y, I, Q as doubles), k_fsim_dft (the matrix product, 2 + 8
+ *   launches), k_fsim_energy (4), k_fsim_median (the exact median by radix selection on the bit patterns), k_fsim_pc, k_fsim_pool.
+ *   Scratch on the device: 24 bytes per frame for the words, the maps at 8 bytes and the intermediates at 560 bytes per downsampled
+ *   sample per frame; a batch goes out in sub-slices of frames that keep the intermediates within 256 MiB.  The tables of a
+ *   geometry (16 N + 2 hd^2 + 2 wd^2 doubles) are cached by the ctx.  All of it is kept until vqa_trim / vqa_destroy.  The dense
+ *   DFT is a first version: FFT passes for 2-3-5-smooth grids are the next step.
+ * Limits: plane 0 at least 16 x 16, h w <= 2^28 and max(hd, wd) <= 1024: VQA_ERR_UNSUPPORTED beyond any of these.  Every
+ *   VQA_ERR_INVALID / VQA_ERR_STATE rule of vqa_mdsi_submit applies, and its contract: asynchronous, ONE ENTRY PER FRAME, the same
+ *   descriptors, memory kinds and failure guarantee.  An FSIM batch is a batch of its own, next to every other kind; a batch of
+ *   more than 32768 frames goes out in slices.
+ * Not built: PU21-FSIM, a per-plane FSIM, FFT passes, any fp32 or bf16 transform.
+ * out of vqa_fsim_wait: n entries (n_entries = n).                                                                         */
+enum vqa_fsim_model { VQA_FSIM_YUV709 = 0, VQA_FSIM_BGR = 1, VQA_FSIM_GRAY = 2 };
+VQA_API int vqa_fsim_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                            int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes,
+                            int model);
+VQA_API int vqa_fsim_wait(vqa_ctx *ctx, vqa_fsim_metrics *out, int n_entries);
+/* c_o of an hd x wd grid as stated above, in double on the host; needs no ctx and no device (NaN for hd or wd outside 2..1024 or
+ * orient outside 0..3)                                                                                                      */
+VQA_API double vqa_fsim_noise_factor(int hd, int wd, int orient);
+/* filt_{scale,orient} of an hd x wd grid into dst[hd wd], row-major, in double on the host; VQA_ERR_INVALID for the same
+ * arguments or a null dst                                                                                                   */
+VQA_API int vqa_fsim_filter(int hd, int wd, int scale, int orient, double *dst);
+/* LAB BUILD ONLY (vqa_build_flavour() & 2; declared only when VQA_TEST_SEAMS is defined): the p maps of the LAST vqa_fsim_submit of
+ * the ctx, [n][2][hd][wd] uint32 (ref, then dist), after its wait; n_values = n 2 hd wd.  There, too, VQA_FSIM_SUBSLICE in the
+ * environment shortens a sub-slice to a given number of frames, so that a small batch spans several.                        */
+#ifdef VQA_TEST_SEAMS
+    VQA_API int vqa_fsim_lab_read_maps(vqa_ctx *ctx, uint32_t *dst, int64_t n_values);
+#endif
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1500,7 +1599,16 @@ enum vqa_kernel_id {
     VQA_K_PU21_ENCODE = 53,  /* vqa_pu21_submit: display light, the PU21 encodings, the q_Y maps and the four SSE half-words (one
                                 entry per sub-slice)                                                                     */
     VQA_K_PU21_SSIM = 54,    /* vqa_pu21_submit: the Gaussian SSIM over the maps (one entry per sub-slice)                     */
-    VQA_K_RIM = 55           /* one past the last id: ... VQA_K_ITP .. VQA_K_VERGE - 1 and VQA_K_PU21_ENCODE .. VQA_K_RIM - 1  */
+    VQA_K_RIM = 55,          /* one past VQA_K_PU21_SSIM, as PU21 shipped it (kept at 55 for callers and tests that rely on id 55
+                                being unknown); id 55 stays unnamed                                                      */
+    VQA_K_FSIM_LUMA = 56,    /* vqa_fsim_submit: the box sums and Y, I, Q of both images (one entry per sub-slice)             */
+    VQA_K_FSIM_DFT = 57,     /* vqa_fsim_submit: the dense DFTs on the fp64 matrix cores (five entries per sub-slice: the forward
+                                pair and one inverse pair per orientation)                                               */
+    VQA_K_FSIM_ENERGY = 58,  /* vqa_fsim_submit: Energy, An and |EO_0|^2 of an orientation (four entries per sub-slice)       */
+    VQA_K_FSIM_MEDIAN = 59,  /* vqa_fsim_submit: the exact medians and the thresholds T_o (one entry per sub-slice)           */
+    VQA_K_FSIM_PC = 60,      /* vqa_fsim_submit: PC and the p maps (one entry per sub-slice)                                  */
+    VQA_K_FSIM_POOL = 61,    /* vqa_fsim_submit: Scharr, the similarities and the three words (one entry per sub-slice)       */
+    VQA_K_HEM = 62           /* one past the last id: ... VQA_K_PU21_ENCODE .. VQA_K_RIM - 1 and VQA_K_FSIM_LUMA .. VQA_K_HEM - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -69,7 +69,9 @@ K_IDS_TOTAL = K_IDS_WHOLE + (K_MDSI_MAP, K_MDSI_DEV)   # the ids below K_BRINK (
 K_ITP, K_VERGE = 51, 52                           # added beyond K_BRINK, which stays 50; id 50 is unnamed
 K_IDS_SUM = K_IDS_TOTAL + (K_ITP,)                # the ids below K_VERGE (kept as dE_ITP shipped it)
 K_PU21_ENCODE, K_PU21_SSIM, K_RIM = 53, 54, 55    # added beyond K_VERGE, which stays 52; id 52 is unnamed
-K_IDS_GRAND = K_IDS_SUM + (K_PU21_ENCODE, K_PU21_SSIM)   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_GRAND = K_IDS_SUM + (K_PU21_ENCODE, K_PU21_SSIM)   # the ids below K_RIM (kept as PU21 shipped it)
+K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL, K_HEM = 56, 57, 58, 59, 60, 61, 62   # added beyond K_RIM, which stays 55; id 55 is unnamed
+K_IDS_ENTIRE = K_IDS_GRAND + (K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -105,6 +107,10 @@ ITP_YUV2020, ITP_BGR = 0, 1   # vqa_itp_submit's colour models
 ITP_PQ, ITP_HLG = 0, 1        # vqa_itp_submit's transfer functions
 ITP_TRANSFERS = {"pq": ITP_PQ, "hlg": ITP_HLG}
 ITP_FIX = 1 << 20  # vqa_itp_metrics: q = rint(dE_ITP 2^20)
+FSIM_MIN_DIM = 16   # vqa_fsim_submit: plane 0's limit (the chroma planes of 4:2:0 may be 8 x 8)
+FSIM_MAX_GRID = 1024   # vqa_fsim_submit: the limit of either side of the downsampled grid
+FSIM_YUV709, FSIM_BGR, FSIM_GRAY = 0, 1, 2   # vqa_fsim_submit's colour models
+FSIM_FIX = 1 << 24  # vqa_fsim_metrics: p = rint(PC 2^24), g = rint(S_L 2^24)
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -234,6 +240,11 @@ class VqaPu21Metrics(C.Structure):
                 ("pu_psnr", C.c_double), ("pu_psnr_rgb", C.c_double), ("pu_ssim", C.c_double)]
 
 
+class VqaFsimMetrics(C.Structure):
+    _fields_ = [("sum_pc", C.c_uint64), ("sum_sim", C.c_uint64), ("sum_simc", C.c_uint64), ("count", C.c_int64),
+                ("factor", C.c_int32), ("flags", C.c_uint32), ("fsim", C.c_double), ("fsimc", C.c_double)]
+
+
 class VqaHaarpsiMetrics(C.Structure):
     _fields_ = [("den", C.c_uint64), ("num_lo", C.c_uint64), ("num_hi", C.c_uint64), ("similarity", C.c_double),
                 ("haarpsi", C.c_double)]
@@ -311,6 +322,11 @@ SIGNATURES = {
                                   C.c_int, C.c_int, C.c_int]),
     "vqa_pu21_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaPu21Metrics), C.c_int]),
     "vqa_pu21_encode": (C.c_double, [C.c_double]),
+    "vqa_fsim_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
+                                  C.c_int]),
+    "vqa_fsim_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaFsimMetrics), C.c_int]),
+    "vqa_fsim_noise_factor": (C.c_double, [C.c_int, C.c_int, C.c_int]),
+    "vqa_fsim_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),
@@ -347,6 +363,7 @@ def _strerror(status):
 # symbols of the lab build alone (vqa_build_flavour() & FLAVOUR_TEST_SEAMS); include/vqa.h declares them under VQA_TEST_SEAMS
 LAB_SIGNATURES = {
     "vqa_pu21_lab_read_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]),
+    "vqa_fsim_lab_read_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]),
 }
 
 

@@ -64,6 +64,7 @@ struct vqa_ctx {
     long seam_ensure_calls = 0;
     long long seam_fb_chunk_bytes = 0; // VQA_FB_CHUNK_BYTES: Farneback's scratch budget per chunk (0 = the shipped 12 GiB): lets a small batch span chunks
     int seam_qslice = 0;            // VQA_QSLICE: the frames of one slice of a plane batch (0 = the shipped QSLICE): lets a small batch span slices
+    int seam_fsim_sub = 0;          // VQA_FSIM_SUBSLICE: the frames of one sub-slice of an FSIM batch (0 = the shipped budget): lets a small batch span sub-slices
     int seam_pu21_sub = 0;          // VQA_PU21_SUBSLICE: the frames of one sub-slice of a PU21 batch (0 = the shipped budget): lets a small batch span sub-slices
 
     // device scratch (grow-only)
@@ -128,11 +129,16 @@ struct vqa_ctx {
     // build only: the maps of the whole last batch, for vqa_pu21_lab_read_maps; host frames are staged in qstage_*
     dbuf pu21_acc, pu21_map, pu21_keep;
     hbuf pu21_host;
+    // vqa_fsim_submit: the three integer words per frame (device, pinned host); the intermediates and the p maps of one sub-slice
+    // of frames; lab build only: the maps of the whole last batch, for vqa_fsim_lab_read_maps; host frames are staged in qstage_*
+    dbuf fsim_acc, fsim_scratch, fsim_map, fsim_keep;
+    hbuf fsim_host;
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
     std::map<std::tuple<int, int, int, int>, cached<fb_resize_tabs>> fb_tabs;
     std::map<int, cached<float *>> dct_mats;
+    std::map<std::pair<int, int>, cached<fsim_tabs>> fsim_tables;   // k_fsim.hip: DFT matrices, filter bank and noise factors per grid (hd, wd)
     std::map<int, cached<dct_fft_plan>> fft_plans;  // k_dct_fft.hip: twiddle / post-twiddle tables per transform length
     uint64_t cache_clock = 0;
     int dct_wave_slots = 0;                 // wave slots of THIS device for the marching DCT's chunking (set in vqa_create)
@@ -173,6 +179,9 @@ struct vqa_ctx {
     int pend_u = 0;           // frames of the pending PU21 batch (likewise); its luma grid, for the host's divisions
     int pend_u_w = 0, pend_u_h = 0;
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what pu21_keep holds
+    int pend_f = 0;           // frames of the pending FSIM batch (likewise); its plane 0, for the host's part
+    int pend_f_w = 0, pend_f_h = 0;
+    int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what fsim_keep holds (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -182,8 +191,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_RIM] = {0};
-    int64_t prof_n[VQA_K_RIM] = {0};
+    double prof_ms[VQA_K_HEM] = {0};
+    int64_t prof_n[VQA_K_HEM] = {0};
 };
 
 namespace {
@@ -256,7 +265,7 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d || c->pend_i || c->pend_u; }
+static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d || c->pend_i || c->pend_u || c->pend_f; }
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -341,6 +350,7 @@ static void free_table(fb_resize_tabs &t)
     if (t.sy) (void)hipFree(t.sy);
 }
 static void free_table(float *&m) { (void)hipFree(m); }
+static void free_table(fsim_tabs &t) { (void)hipFree(t.wh); (void)hipFree(t.ww); (void)hipFree(t.filt); }
 static void free_table(dct_fft_plan &P) { (void)hipFree((void *)P.tw); (void)hipFree((void *)P.post); }
 
 // lookup that refreshes the entry's stamp
@@ -468,6 +478,28 @@ static int get_fft_plan(vqa_ctx *c, int n, dct_fft_plan *out)
     if ((rc = cache_put(c, c->fft_plans, n, P))) return rc;
     tb.commit();
     *out = P;
+    return VQA_OK;
+}
+
+// k_fsim.hip's tables for an hd x wd grid, formed in double on the host
+static int get_fsim_tabs(vqa_ctx *c, int hd, int wd, fsim_tabs *out)
+{
+    const auto key = std::make_pair(hd, wd);
+    if (cache_get(c, c->fsim_tables, key, *out)) return VQA_OK;
+    const size_t N = (size_t)hd * wd;
+    fsim_tabs t;
+    std::vector<double> filt(16 * N), wh(2 * (size_t)hd * hd), ww(2 * (size_t)wd * wd);
+    fsim_bank_host(hd, wd, filt.data(), t.c);
+    fsim_twiddle_host(hd, wh.data());
+    fsim_twiddle_host(wd, ww.data());
+    table_builder tb(c);
+    int rc;
+    if ((rc = tb.upload(&t.wh, wh.data(), sizeof(double) * wh.size()))) return rc;
+    if ((rc = tb.upload(&t.ww, ww.data(), sizeof(double) * ww.size()))) return rc;
+    if ((rc = tb.upload(&t.filt, filt.data(), sizeof(double) * filt.size()))) return rc;
+    if ((rc = cache_put(c, c->fsim_tables, key, t))) return rc;
+    tb.commit();
+    *out = t;
     return VQA_OK;
 }
 
@@ -864,6 +896,7 @@ int vqa_create(int device, vqa_ctx **out)
         }
         c->seam_qslice = (int)q;
     }
+    if (const char *e = getenv("VQA_FSIM_SUBSLICE")) c->seam_fsim_sub = atoi(e) > 0 ? atoi(e) : 0;
     if (const char *e = getenv("VQA_PU21_SUBSLICE")) c->seam_pu21_sub = atoi(e) > 0 ? atoi(e) : 0;
 #endif
     *out = c;
@@ -909,20 +942,22 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->itp_acc, &c->pu21_acc, &c->pu21_map, &c->pu21_keep, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->itp_acc, &c->pu21_acc, &c->pu21_map, &c->pu21_keep, &c->fsim_acc, &c->fsim_scratch, &c->fsim_map, &c->fsim_keep, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
-    c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host, &c->itp_host, &c->pu21_host}) {
+    for (auto &kv : c->fsim_tables) free_table(kv.second.v);
+    c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear(); c->fsim_tables.clear();
+    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host, &c->itp_host, &c->pu21_host, &c->fsim_host}) {
         if (b->p) (void)hipHostFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
     c->last_u_n = 0;
+    c->last_f_n = 0;
 }
 
 int vqa_trim(vqa_ctx *c)
@@ -1417,7 +1452,7 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the seventeen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI, dE_ITP, PU21) share: the checks, the staging of host frames, the walk over
+// What the eighteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI, dE_ITP, PU21, FSIM) share: the checks, the staging of host frames, the walk over
 // slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
 extern "C++" {   // (templates among them)
 
@@ -1482,7 +1517,7 @@ static int stage(vqa_ctx *c, dbuf &buf, const uint8_t *&frames, size_t bytes)
     return VQA_OK;
 }
 
-// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI, an MDSI, a dE_ITP or a PU21 submit.  The eleven share qstage_*: the stream orders a batch behind
+// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI, an MDSI, a dE_ITP, a PU21 or an FSIM submit.  The twelve share qstage_*: the stream orders a batch behind
 // whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
 static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs, const uint8_t *&dist,
                       int64_t dist_fs)
@@ -2850,6 +2885,154 @@ int vqa_pu21_lab_read_maps(vqa_ctx *c, uint32_t *dst, int64_t n_values)
 #endif
 
 // ---------------------------------------------------------------------------
+// FSIM / FSIMc: both streams, the planes of a pixel together, one entry per frame.  A batch of its own (pend_f), ordered by the
+// stream like an MDSI batch, whose checks, host staging (qstage_*) and geometry rules it shares.
+
+// the frames of one sub-slice: the intermediates of that many frames stay within FSIM_SCRATCH_BUDGET (lab build: or what the seam says)
+static inline int fsim_subslice(const vqa_ctx *c, int h, int w)
+{
+#ifdef VQA_TEST_SEAMS
+    if (c->seam_fsim_sub > 0) return c->seam_fsim_sub < FSIM_MAX_SUBSLICE ? c->seam_fsim_sub : FSIM_MAX_SUBSLICE;
+#endif
+    (void)c;
+    const size_t per = FSIM_SCRATCH_BUDGET / fsim_scratch_bytes(h, w);
+    return per < 1 ? 1 : per > (size_t)FSIM_MAX_SUBSLICE ? FSIM_MAX_SUBSLICE : (int)per;
+}
+
+static int fsim_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int model, bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (n_planes != 1 && n_planes != 3) return VQA_ERR_INVALID;
+    if (model != VQA_FSIM_YUV709 && model != VQA_FSIM_BGR && model != VQA_FSIM_GRAY) return VQA_ERR_INVALID;
+    if ((n_planes == 1) != (model == VQA_FSIM_GRAY)) return VQA_ERR_INVALID;
+    if (c->pend_f) return VQA_ERR_STATE;
+    plane_batch B;
+    // the size limits are plane 0's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
+    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
+        return &d == planes ? side_and_area_limits(d, FSIM_MIN_DIM) : (int)VQA_OK;
+    });
+    if (rc) return rc;
+    const vqa_plane_desc &y = planes[0];
+    if (n_planes == 3) {
+        const vqa_plane_desc &u = planes[1], &v = planes[2];
+        if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
+            return VQA_ERR_INVALID;
+        if (model == VQA_FSIM_BGR) {
+            if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
+                return VQA_ERR_INVALID;
+        } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
+            return VQA_ERR_INVALID;
+        }
+    }
+    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
+    int f, hd, wd;
+    fsim_grid(y.height, y.width, &f, &hd, &wd);
+    if (hd > FSIM_MAX_GRID || wd > FSIM_MAX_GRID) return VQA_ERR_UNSUPPORTED;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    touched = true;
+    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    fsim_tabs tabs;
+    if ((rc = get_fsim_tabs(c, hd, wd, &tabs))) return rc;
+    const size_t acc_bytes = sizeof(unsigned long long) * FSIM_WORDS * (size_t)n;
+    const size_t map_bytes = 2 * sizeof(uint32_t) * (size_t)hd * (size_t)wd;   // the two p maps of a frame
+    const int sub = fsim_subslice(c, y.height, y.width);
+    const int sub_frames = sub < slice_frames(c, n) ? sub : slice_frames(c, n);
+    if ((rc = ensure(c, c->fsim_acc, acc_bytes))) return rc;
+    if ((rc = ensure(c, c->fsim_scratch, fsim_scratch_bytes(y.height, y.width) * (size_t)sub_frames))) return rc;
+    if ((rc = ensure(c, c->fsim_map, map_bytes * (size_t)sub_frames))) return rc;
+    if ((rc = ensure_pinned(c, c->fsim_host, acc_bytes))) return rc;
+#ifdef VQA_TEST_SEAMS
+    c->last_f_n = 0;
+    if ((rc = ensure(c, c->fsim_keep, map_bytes * (size_t)n))) return rc;
+#endif
+    HIPCHK(c, hipMemsetAsync(c->fsim_acc.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    // (launch_fsim's marks: one prof_scope per kernel id at a time, open between its begin and its end)
+    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
+    const brisque_mark mark = [](void *p, int id, int begin) {
+        marks *m = (marks *)p;
+        if (begin) m->open.emplace(m->c, id);
+        else m->open.reset();
+    };
+    hipError_t copy_err = hipSuccess;
+    for_each_slice(c, n, [&](int a0, int m) {
+        for (int b0 = 0; b0 < m; b0 += sub_frames) {
+            const int k = m - b0 < sub_frames ? m - b0 : sub_frames, at = a0 + b0;
+            launch_fsim(st, ref + (int64_t)at * ref_fs, dist + (int64_t)at * dist_fs, k, ref_fs, dist_fs, planes, n_planes, depth,
+                        model, tabs, c->fsim_scratch.p, (uint32_t *)c->fsim_map.p,
+                        (unsigned long long *)c->fsim_acc.p + (size_t)at * FSIM_WORDS, mark, &mk);
+#ifdef VQA_TEST_SEAMS
+            const hipError_t e = hipMemcpyAsync((uint8_t *)c->fsim_keep.p + map_bytes * (size_t)at, c->fsim_map.p,
+                                                map_bytes * (size_t)k, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) copy_err = e;
+#endif
+        }
+    });
+    HIPCHK(c, copy_err);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->fsim_host.p, c->fsim_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
+    c->pend_f = n;
+    c->pend_f_w = y.width;
+    c->pend_f_h = y.height;
+#ifdef VQA_TEST_SEAMS
+    c->last_f_n = n; c->last_f_w = wd; c->last_f_h = hd;
+#endif
+    return VQA_OK;
+}
+
+int vqa_fsim_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
+                    const vqa_plane_desc *planes, int n_planes, int model)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return fsim_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, model, touched);
+    });
+}
+
+int vqa_fsim_wait(vqa_ctx *c, vqa_fsim_metrics *out, int n_entries)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    if (!c->pend_f || n_entries != c->pend_f) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const unsigned long long *acc = (const unsigned long long *)c->fsim_host.p;
+    for (int e = 0; e < n_entries; e++) fsim_finalize(acc + (size_t)e * FSIM_WORDS, c->pend_f_h, c->pend_f_w, out + e);
+    c->pend_f = 0;
+    return VQA_OK;
+}
+
+static inline bool fsim_bad_grid(int hd, int wd, int orient)
+{
+    return hd < 2 || wd < 2 || hd > FSIM_MAX_GRID || wd > FSIM_MAX_GRID || orient < 0 || orient > 3;
+}
+
+double vqa_fsim_noise_factor(int hd, int wd, int orient)
+{
+    return fsim_bad_grid(hd, wd, orient) ? (double)NAN : fsim_noise_factor_host(hd, wd, orient);
+}
+
+int vqa_fsim_filter(int hd, int wd, int scale, int orient, double *dst)
+{
+    if (fsim_bad_grid(hd, wd, orient) || scale < 0 || scale > 3 || !dst) return VQA_ERR_INVALID;
+    fsim_filter_host(hd, wd, scale, orient, dst);
+    return VQA_OK;
+}
+
+#ifdef VQA_TEST_SEAMS
+int vqa_fsim_lab_read_maps(vqa_ctx *c, uint32_t *dst, int64_t n_values)
+{
+    if (!c || !dst) return VQA_ERR_INVALID;
+    if (c->pend_f || !c->last_f_n) return VQA_ERR_STATE;
+    if (n_values != (int64_t)c->last_f_n * 2 * c->last_f_h * c->last_f_w) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dst, c->fsim_keep.p, sizeof(uint32_t) * (size_t)n_values, hipMemcpyDeviceToHost));
+    return VQA_OK;
+}
+#endif
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2859,12 +3042,13 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_RIM || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_HEM || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
         (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS) || (id >= VQA_K_CLOSE && id < VQA_K_ARTIFACTS) || (id >= VQA_K_STOP && id < VQA_K_BRISQUE_HALF) ||
-        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP) || (id >= VQA_K_BRINK && id < VQA_K_ITP) || (id >= VQA_K_VERGE && id < VQA_K_PU21_ENCODE))
+        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP) || (id >= VQA_K_BRINK && id < VQA_K_ITP) || (id >= VQA_K_VERGE && id < VQA_K_PU21_ENCODE) ||
+        (id >= VQA_K_RIM && id < VQA_K_FSIM_LUMA))
         return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2907,6 +3091,12 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_ITP) return "k_itp";
     if (id == VQA_K_PU21_ENCODE) return "k_pu21_encode";
     if (id == VQA_K_PU21_SSIM) return "k_pu21_ssim";
+    if (id == VQA_K_FSIM_LUMA) return "k_fsim_luma";
+    if (id == VQA_K_FSIM_DFT) return "k_fsim_dft";
+    if (id == VQA_K_FSIM_ENERGY) return "k_fsim_energy";
+    if (id == VQA_K_FSIM_MEDIAN) return "k_fsim_median";
+    if (id == VQA_K_FSIM_PC) return "k_fsim_pc";
+    if (id == VQA_K_FSIM_POOL) return "k_fsim_pool";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

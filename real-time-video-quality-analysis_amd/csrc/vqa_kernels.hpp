@@ -550,4 +550,41 @@ double pu21_encode_host(double cd_m2);
 // five words -> the record: the joins and divisions of include/vqa.h in double, on the host (h x w: the luma grid)
 void pu21_finalize(const unsigned long long *words, int h, int w, vqa_pu21_metrics *out);
 
+// FSIM / FSIMc (vqa_fsim_submit): k_fsim.hip
+constexpr int FSIM_MIN_DIM = 16;                   // the limit of plane 0 (the chroma planes of 4:2:0 may be 8 x 8)
+constexpr int FSIM_MAX_GRID = 1024;                // the limit of either side of the downsampled grid
+constexpr int FSIM_WORDS = 3;                      // per frame: P, A, B (include/vqa.h)
+constexpr double FSIM_FIX = 16777216.0;            // 2^24: p = rint(PC 2^24), g = rint(S_L 2^24), gc = rint(S_L C 2^24)
+constexpr int FSIM_IMAGE_DOUBLES = 35;             // scratch doubles per downsampled sample of ONE image: Y, I, Q; the row
+                                                   // transform (2); F (2); the half and the whole inverse of the four scales of one
+                                                   // orientation (8 + 8); Energy, An, |EO_0|^2 of the four orientations (12)
+constexpr size_t FSIM_SCRATCH_BUDGET = (size_t)1 << 28;   // the scratch of a sub-slice of frames stays within 256 MiB
+constexpr int FSIM_MAX_SUBSLICE = 4096;            // frames of a sub-slice at most (a launch's grid is 8 per frame in z)
+// the per-geometry tables on the device: the two DFT matrices ([2][hd][hd] and [2][wd][wd] doubles: real parts, then imaginary
+// ones), the sixteen filter tables [orientation][scale][hd wd], and the noise factors c_o
+struct fsim_tabs {
+    double *wh = nullptr, *ww = nullptr, *filt = nullptr;
+    double c[4] = {0, 0, 0, 0};
+};
+// f of mdsi_factor and the downsampled grid ceil(h / f) x ceil(w / f)
+void fsim_grid(int h, int w, int *f, int *hd, int *wd);
+// the bytes of scratch ONE FRAME (both images) takes
+size_t fsim_scratch_bytes(int h, int w);
+// the host's tables, in double: filt_{scale,orient} (hd wd doubles); all sixteen (filt may be null) with the four c_o; c_o alone;
+// the DFT matrix of length n (2 n n doubles)
+void fsim_filter_host(int hd, int wd, int scale, int orient, double *dst);
+void fsim_bank_host(int hd, int wd, double *filt, double c[4]);
+double fsim_noise_factor_host(int hd, int wd, int orient);
+void fsim_twiddle_host(int n, double *dst);
+// [Y, I, Q][plane 0, 1, 2, count]: the channels from the box SUMS of the integer samples and the count of in-plane positions
+void fsim_matrix(int model, int depth, int f, double mat[3][4]);
+// the three words of n frame pairs (planes checked by the caller as for launch_mdsi), added to acc[frame * FSIM_WORDS ..], which
+// the caller has zeroed; scratch: n * fsim_scratch_bytes(h, w); pmap: [n][2][hd wd] uint32, the p maps (ref, then dist).  mark
+// brackets the launches of each kernel id, as launch_brisque's does
+void launch_fsim(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                 int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes, int depth, int model,
+                 const fsim_tabs &tabs, void *scratch, uint32_t *pmap, unsigned long long *acc, brisque_mark mark, void *mark_arg);
+// three words -> the record: the divisions of include/vqa.h in double, on the host (h x w: plane 0)
+void fsim_finalize(const unsigned long long *words, int h, int w, vqa_fsim_metrics *out);
+
 } // namespace vqa

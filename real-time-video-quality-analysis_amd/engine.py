@@ -84,6 +84,9 @@ PU21_DTYPE = np.dtype([("sse_y_lo", np.uint64), ("sse_y_hi", np.uint64), ("sse_r
                        ("ssim_q", np.int64), ("windows", np.int64), ("mse_y", np.float64), ("mse_rgb", np.float64),
                        ("pu_psnr", np.float64), ("pu_psnr_rgb", np.float64), ("pu_ssim", np.float64)], align=True)
 assert PU21_DTYPE.itemsize == C.sizeof(N.VqaPu21Metrics)
+FSIM_DTYPE = np.dtype([("sum_pc", np.uint64), ("sum_sim", np.uint64), ("sum_simc", np.uint64), ("count", np.int64),
+                       ("factor", np.int32), ("flags", np.uint32), ("fsim", np.float64), ("fsimc", np.float64)], align=True)
+assert FSIM_DTYPE.itemsize == C.sizeof(N.VqaFsimMetrics) == 56
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -103,6 +106,7 @@ _BATCHES = {
     "_pending_d": ("vqa_mdsi_submit", "vqa_mdsi_wait", MDSI_DTYPE, N.VqaMdsiMetrics),   # (one entry per frame)
     "_pending_i": ("vqa_itp_submit", "vqa_itp_wait", ITP_DTYPE, N.VqaItpMetrics),   # (one entry per frame)
     "_pending_u": ("vqa_pu21_submit", "vqa_pu21_wait", PU21_DTYPE, N.VqaPu21Metrics),   # (one entry per frame)
+    "_pending_f": ("vqa_fsim_submit", "vqa_fsim_wait", FSIM_DTYPE, N.VqaFsimMetrics),   # (one entry per frame)
 }
 
 
@@ -355,7 +359,7 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21 and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
@@ -492,7 +496,7 @@ class Engine:
         return a.ctypes.data, a
 
     def _pair_args(self, ref, dist, planes, frame_bytes=None):
-        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI / dE_ITP / PU21 submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
+        """the (ref, dist) pair of a quality / VIF / ADM / PSNR-HVS / CIEDE2000 / GMSD / HaarPSI / MDSI / dE_ITP / PU21 / FSIM submit -> (ref ptr, dist ptr, mem kind, n, frame strides, what to keep alive)"""
         dev = isinstance(ref, DeviceFrames)
         if dev:
             assert isinstance(dist, DeviceFrames) and ref.n == dist.n
@@ -977,6 +981,42 @@ class Engine:
         rec = self.pu21_wait()
         return (rec, self.pu21_maps()) if maps else rec
 
+    # ---- FSIM / FSIMc ------------------------------------------------------------
+    def fsim_submit(self, ref, dist, planes, model=None, frame_bytes=None):
+        """FSIM and FSIMc for n frame pairs (vqa_fsim_submit): the arrays / DeviceFrames, plane tuples and colour models of
+        mdsi_submit - THREE planes of one depth taken together per pixel, or ONE plane Y; plane 0 at least 16 x 16 and the
+        downsampled grid at most 1024 either way.  model: N.FSIM_YUV709 | N.FSIM_BGR | N.FSIM_GRAY | None (mdsi_model(planes):
+        the enums agree).  A batch of its own, like mdsi_submit."""
+        if model is None:
+            model = self.mdsi_model(planes)
+        *args, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        st = self.lib.vqa_fsim_submit(self.ctx, *args, plane_descs(planes), len(planes), int(model))
+        N.check(st, "vqa_fsim_submit", self.ctx)
+        self._pending_f = (args[3], 1, keep)
+        f = mdsi_factor(int(planes[0][1]), int(planes[0][0]))
+        self._fsim_shape = (args[3], 2, -(-int(planes[0][1]) // f), -(-int(planes[0][0]) // f))
+
+    def fsim_wait(self):
+        """-> [n] records (FSIM_DTYPE), one per frame: the three integer words (sum_pc, sum_sim, sum_simc), count, factor,
+        flags (bit 0: no phase congruency anywhere), fsim and fsimc (both exactly 1 for identical frames)."""
+        return self._batch_wait("_pending_f").reshape(-1)
+
+    def fsim_maps(self):
+        """LAB LIBRARY ONLY: the two p maps of the last FSIM batch, after its wait -> [n, 2, hd, wd] uint32 (ref, dist)"""
+        fn = getattr(self.lib, "vqa_fsim_lab_read_maps", None)
+        if fn is None or fn.argtypes is None:
+            raise RuntimeError("the FSIM maps can be read back from the lab library only")
+        out = np.empty(self._fsim_shape, np.uint32)
+        N.check(fn(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size), "vqa_fsim_lab_read_maps", self.ctx)
+        return out
+
+    def fsim(self, ref, dist, planes, model=None, frame_bytes=None, maps=False):
+        """FSIM and FSIMc per frame for n frame pairs; returns [n] structured array (FSIM_DTYPE); on the lab library maps=True
+        returns (records, p [n, 2, hd, wd] uint32)."""
+        self.fsim_submit(ref, dist, planes, model, frame_bytes)
+        rec = self.fsim_wait()
+        return (rec, self.fsim_maps()) if maps else rec
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -984,7 +1024,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_GRAND:
+        for k in N.K_IDS_ENTIRE:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -391,7 +391,7 @@ class Quality:
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
                  haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
-                 itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False):
+                 itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
                 returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
@@ -453,7 +453,11 @@ class Quality:
                 upload; the pass's tuple then gains ONE further last element, after dE_ITP's: the PU21 records [n]
                 (engine.PU21_DTYPE: the five integer words, windows, mse_y, mse_rgb, pu_psnr, pu_psnr_rgb, pu_ssim - one per
                 frame, not per plane); "only": no SSE / SSIM.  pu21_transfer: "pq" | "hlg"; pu21_full_range: False (limited) |
-                True; the colour model follows from the planes (Engine.itp_model)"""
+                True; the colour model follows from the planes (Engine.itp_model)
+        fsim    True: every chunk also goes through the FSIM kernels (Engine.fsim_submit: one plane, or three taken together) from
+                the SAME upload; the pass's tuple then gains ONE further last element, after PU21's: the FSIM records [n]
+                (engine.FSIM_DTYPE: the three integer words, count, factor, flags, fsim, fsimc - one per frame, not per plane);
+                "only": no SSE / SSIM.  The colour model follows from the planes (Engine.mdsi_model)"""
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
@@ -554,12 +558,19 @@ class Quality:
         if not isinstance(pu21_full_range, bool):
             raise ValueError("pu21_full_range must be True or False")
         self.pu21, self.pu21_transfer, self.pu21_full_range = pu21, pu21_transfer, pu21_full_range
+        if not (isinstance(fsim, bool) or (isinstance(fsim, str) and fsim == "only")):
+            raise ValueError("fsim must be False, True or 'only'")
+        if fsim == "only" and scales:
+            raise ValueError("an FSIM-only pass has no SSIM scales")
+        if fsim and len(planes) not in (1, 3):
+            raise ValueError("fsim needs one plane or three")
+        self.fsim = fsim
         self.ciede, self.ciede_weights = ciede, ciede_weights
         # the pass measures SSE / SSIM
         self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
                      ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only" and
                      vca != "only" and artifacts != "only" and brisque != "only" and mdsi != "only" and
-                     itp != "only" and pu21 != "only")
+                     itp != "only" and pu21 != "only" and fsim != "only")
 
 
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
@@ -652,7 +663,8 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     [n] (engine.MDSI_DTYPE, one per frame); mdsi="only" leaves sse and ssim None as well.  Quality(.., itp=True) appends ONE
     further last element, after MDSI's: the dE_ITP records [n] (engine.ITP_DTYPE, one per frame); itp="only" leaves sse and ssim
     None as well.  Quality(.., pu21=True) appends ONE further last element, after dE_ITP's: the PU21 records [n]
-    (engine.PU21_DTYPE, one per frame); pu21="only" leaves sse and ssim None as well.
+    (engine.PU21_DTYPE, one per frame); pu21="only" leaves sse and ssim None as well.  Quality(.., fsim=True) appends ONE further
+    last element, after PU21's: the FSIM records [n] (engine.FSIM_DTYPE, one per frame); fsim="only" leaves sse and ssim None as well.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -742,6 +754,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         if quality.pu21:
             from .engine import PU21_DTYPE
             q += (np.zeros(0, PU21_DTYPE),)
+        if quality.fsim:
+            from .engine import FSIM_DTYPE
+            q += (np.zeros(0, FSIM_DTYPE),)
         return q, series
     if engine is not None:
         first = engine
@@ -757,7 +772,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion, SI/TI, VCA, CAMBI, the artefact measures and BRISQUE alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and not quality.mdsi and not quality.itp and not quality.pu21 and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
+    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and not quality.mdsi and not quality.itp and not quality.pu21 and not quality.fsim and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -865,7 +880,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_d"] = p["has_i"] = p["has_u"] = p["has_c"] = False
+        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_d"] = p["has_i"] = p["has_u"] = p["has_f"] = p["has_c"] = False
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -940,6 +955,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.pu21:
                     eng.pu21_submit(pair[0], pair[1], quality.planes, None, quality.pu21_transfer, quality.pu21_full_range)
                     p["has_u"] = True
+                if quality.fsim:
+                    eng.fsim_submit(pair[0], pair[1], quality.planes)
+                    p["has_f"] = True
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -958,7 +976,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itps, pus = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itps, pus, fss = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -998,6 +1016,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["ires"] = eng.itp_wait()
             if p["has_u"]:
                 p["ures"] = eng.pu21_wait()
+            if p["has_f"]:
+                p["fres"] = eng.fsim_wait()
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -1048,6 +1068,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 itps.append(p.pop("ires"))
             if p["has_u"]:
                 pus.append(p.pop("ures"))
+            if p["has_f"]:
+                fss.append(p.pop("fres"))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -1142,6 +1164,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q += (np.concatenate(itps),)
     if want_q and quality.pu21:
         q += (np.concatenate(pus),)
+    if want_q and quality.fsim:
+        q += (np.concatenate(fss),)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

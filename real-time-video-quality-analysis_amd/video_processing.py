@@ -398,6 +398,24 @@ def frame_pu21(reference, encoded, layout="bgr24", height=None, width=None, tran
     return tuple(np.ascontiguousarray(r[k]) for k in ("pu_psnr", "pu_psnr_rgb", "pu_ssim", "mse_y", "mse_rgb"))
 
 
+def frame_fsim(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
+    """Per-frame FSIM and FSIMc (Engine.fsim through the one-pass pipeline of frame_quality; both streams are uploaded once): phase
+    congruency and Scharr gradient similarity of the luminance, with the chromaticity of I and Q in the colour form, the planes of
+    a pixel taken together by the definition in include/vqa.h - the planar YUV layouts as BT.709 limited range with replicated
+    chroma, bgr24 as B, G, R, the gray layouts as luma alone (fsimc == fsim there) - the authors' FeatureSIM.m as recalled, not
+    pinned against it.  Returns (fsim [n], fsimc [n]) float64, exactly 1 for identical frames, smaller is worse.  Plane 0 at least
+    16 x 16; one- and three-plane layouts."""
+    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(reference, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, fsim="only"), batch_size=batch_size, engine=engine,
+                      device=device)
+    r = q[-1]
+    return np.ascontiguousarray(r["fsim"]), np.ascontiguousarray(r["fsimc"])
+
+
 PU21_PSNR_CAP = 100.0   # the row's PU_PSNR and PU_PSNR_RGB: a frame's value (inf for identical frames) is capped here before pooling
 
 
@@ -413,7 +431,7 @@ def _brisque_model(model_path, range_path):
 
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
                   cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None,
-                  delta_itp=None, pu21=None):
+                  delta_itp=None, pu21=None, fsim=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -450,6 +468,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     frame's mean) and delta_itp_max (its largest pixel), after mdsi and before vmaf, likewise.  The model never reads them.
     pu21: None, or the PU21 records [n] (engine.PU21_DTYPE, one per frame): the log then also carries pu_psnr, pu_psnr_rgb (each
     capped at 100.0: identical frames give inf, which JSON cannot hold and a mean cannot pool) and pu_ssim, after delta_itp_max
+    and before vmaf, likewise.  The model never reads them.
+    fsim: None, or the FSIM records [n] (engine.FSIM_DTYPE, one per frame): the log then also carries fsim and fsimc, after pu_ssim
     and before vmaf, likewise.  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
@@ -524,6 +544,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         names += ["pu_psnr", "pu_psnr_rgb", "pu_ssim"]
         cols += [np.minimum(pu21["pu_psnr"].astype(np.float64), PU21_PSNR_CAP),
                  np.minimum(pu21["pu_psnr_rgb"].astype(np.float64), PU21_PSNR_CAP), pu21["pu_ssim"].astype(np.float64)]
+    if fsim is not None:
+        fsim = np.asarray(fsim).reshape(-1)
+        names += ["fsim", "fsimc"]
+        cols += [fsim["fsim"].astype(np.float64), fsim["fsimc"].astype(np.float64)]
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -648,7 +672,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
                        brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
-                       pu21_full_range=False):
+                       pu21_full_range=False, fsim=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -685,6 +709,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     pu21=True: likewise PU21-PSNR and PU21-SSIM, the three planes together read as a BT.2020 signal, as display light in PU21 units
     (pu_psnr and pu_psnr_rgb, capped at 100.0, and pu_ssim; three-plane layouts only; pu21_transfer "pq" | "hlg", pu21_full_range
     False (limited) | True; a model file does not turn it on).
+    fsim=True: likewise FSIM and FSIMc of the planes taken together (fsim and fsimc, one value each per frame; one- and three-plane
+    layouts; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -718,7 +744,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             if len(LAYOUTS[layout][1]) != 3:
                 raise ValueError("pu21 needs three planes")
             _check_pu21(pu21_transfer, pu21_full_range)
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi or delta_itp or pu21:
+        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi or delta_itp or pu21 or fsim:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -733,10 +759,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              itp_transfer=delta_itp_transfer,
                                                              itp_full_range=delta_itp_full_range, pu21=bool(pu21),
                                                              pu21_transfer=pu21_transfer,
-                                                             pu21_full_range=pu21_full_range),
+                                                             pu21_full_range=pu21_full_range, fsim=bool(fsim)),
                               batch_size=batch_size, on_quality=wr, device=device)
             _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts, brisque, bmodel, mdsi, delta_itp, pu21)
+                               artifacts, brisque, bmodel, mdsi, delta_itp, pu21, fsim)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -775,11 +801,13 @@ MODE_KEYS = {
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
                        cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
-                       mdsi=False, delta_itp=False, pu21=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000, MDSI, dE_ITP and PU21 figures of a pass (the
+                       mdsi=False, delta_itp=False, pu21=False, fsim=False):
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (the
     tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = itp = pus = None
-    if pu21:       # the tuple's last element, then dE_ITP's
+    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = itp = pus = fsm = None
+    if fsim:       # the tuple's last element, then PU21's
+        fsm, q = q[-1], q[:-1]
+    if pu21:       # then dE_ITP's
         pus, q = q[-1], q[:-1]
     if delta_itp:  # then MDSI's
         itp, q = q[-1], q[:-1]
@@ -829,6 +857,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
         more["delta_itp"] = itp
     if pus is not None:
         more["pu21"] = pus
+    if fsm is not None:
+        more["fsim"] = fsm
     if motion:
         write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
                       model=model, **more)
@@ -889,6 +919,8 @@ def _check_mode_keys(config):
     if "delta_itp_range" in config and not (isinstance(config["delta_itp_range"], str) and
                                             config["delta_itp_range"] in ITP_RANGES):
         raise ValueError("delta_itp_range must be \"limited\" or \"full\".")
+    if "fsim" in config and not isinstance(config["fsim"], bool):
+        raise ValueError("fsim must be true or false.")
     if "pu21" in config and not isinstance(config["pu21"], bool):
         raise ValueError("pu21 must be true or false.")
     if "pu21_transfer" in config and not (isinstance(config["pu21_transfer"], str) and
@@ -974,6 +1006,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         three channels - display light in PU21 units, peak 256, each frame capped at 100.0 -, and PU_SSIM, the pooled mean of the
         per-frame PU21-SSIM, after DELTA_ITP_MAX; three-plane pixfmts only; default false; a model file does not turn it on),
         pu21_transfer ("pq" default | "hlg"), pu21_range ("limited" default | "full"; no effect on bgr24),
+        fsim (true: the row gains FSIM and FSIMC, the pooled means of the per-frame feature similarity index of the luminance and of
+        its colour form, the planes taken together, after PU_SSIM; one- and three-plane pixfmts; default false; a model file does
+        not turn it on),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -1013,6 +1048,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     pu = config.get("pu21", False)
     pu_tf = config.get("pu21_transfer", "pq")
     pu_full = ITP_RANGES[config.get("pu21_range", "limited")]
+    fsm = config.get("fsim", False)
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -1072,14 +1108,14 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                                      haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq,
                                                                      mdsi=mds, itp=itp, itp_transfer=itp_tf,
                                                                      itp_full_range=itp_full, pu21=pu,
-                                                                     pu21_transfer=pu_tf, pu21_full_range=pu_full),
+                                                                     pu21_transfer=pu_tf, pu21_full_range=pu_full, fsim=fsm),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds or itp or pu:
+        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds or itp or pu or fsm:
             _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
-                               mds, itp, pu)
+                               mds, itp, pu, fsm)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -1169,6 +1205,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["PU_PSNR"] = float(pooled["pu_psnr"]["mean"])
             metrics["PU_PSNR_RGB"] = float(pooled["pu_psnr_rgb"]["mean"])
             metrics["PU_SSIM"] = float(pooled["pu_ssim"]["mean"])
+        if "fsim" in pooled:
+            metrics["FSIM"] = float(pooled["fsim"]["mean"])
+            metrics["FSIMC"] = float(pooled["fsimc"]["mean"])
     return metrics
 
 
@@ -1191,7 +1230,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range, pu21, pu21_transfer, pu21_range;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range, pu21, pu21_transfer, pu21_range, fsim;
     #                           and that a vmaf_model_path names a readable file
 
 
