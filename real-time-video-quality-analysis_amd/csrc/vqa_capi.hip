@@ -39,6 +39,40 @@ struct resize_tabs {
 
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
+// The plane-batch kinds: each has one batch_slot in the ctx, and a batch of one kind can be pending next to a batch of every
+// other kind and the complexity batch.  A new kind adds its name here; busy() and release_scratch() walk the slots.
+enum batch_kind {
+    KIND_QUALITY,     // vqa_plane_metrics per entry (its extras are named members of the ctx: qpartials, qms_*)
+    KIND_VIF,         // vqa_vif_metrics per entry; work: levels 1..3 of the largest plane group seen, the integer totals
+    KIND_ADM,         // six sums per (entry, scale); work: the a bands of scales 0..2 of the largest plane group, one scale's tile partials
+    KIND_MOTION,      // one integer total per entry (host frames and prev0: mot_stage, mot_prev)
+    KIND_SITI,        // SITI_WORDS per entry (host frames and prev0: siti_stage, siti_prev)
+    KIND_PSNR_HVS,    // PSNR_HVS_WORDS per entry
+    KIND_CIEDE,       // one word per frame
+    KIND_GMSD,        // GMSD_WORDS per entry
+    KIND_CAMBI,       // CAMBI_WORDS per entry; work: the scales and histograms of the largest group of a slice
+    KIND_XPSNR,       // the words per frame and block (prev0 of host frames: xpsnr_prev)
+    KIND_HAARPSI,     // HAARPSI_WORDS per entry
+    KIND_VCA,         // VCA_WORDS per entry, then the block map of n + 1 slots (pinned host: without the first slot); work: the tables
+                      // of k_vca_blocks (host frames and prev0: SI/TI's siti_stage, siti_prev)
+    KIND_ARTIFACTS,   // ARTIFACTS_WORDS per entry
+    KIND_BRISQUE,     // BRISQUE_WORDS per entry; work: the scale-1 planes and strips of the largest plane group of a slice
+    KIND_MDSI,        // MDSI_WORDS per frame; work: the map of g of a slice
+    KIND_ITP,         // ITP_WORDS per frame
+    KIND_PU21,        // PU21_WORDS per frame; work: the two q_Y maps of one sub-slice; lab build: the maps of the whole last batch
+    KIND_FSIM,        // FSIM_WORDS per frame; work: the intermediates and the p maps of one sub-slice; lab build: the maps of the whole last batch
+    KIND_COUNT
+};
+
+// What every plane-batch kind keeps: its result words on the device and their pinned host copy, the kind's own work buffers
+// (each body names them through local references) and the batch in flight - its entries (0 = idle) and the geometry the host
+// needs to finish the records.  Host frames are staged in named members of the ctx, which the kinds share.
+struct batch_slot {
+    dbuf dev, work[3];
+    hbuf host;
+    int entries = 0, planes = 0, depth = 8, w[4] = {0}, h[4] = {0};
+};
+
 // one cached per-geometry table set and when it was last handed out (least recently used goes first, vqa.h "Memory")
 template <class T> struct cached {
     T v;
@@ -70,69 +104,16 @@ struct vqa_ctx {
     // device scratch (grow-only)
     dbuf gray_full, planeA, planeB, state, res_dev, partials, tile_flags, dirty0, dirty1, again_dev;
     dbuf stage_frames, stage_prev, dct_scratch, dct_pe, dct_pt;
-    dbuf qres_dev, qpartials, qstage_ref, qstage_dist;
+    dbuf qpartials;
     dbuf qms_pyr, qms_dev;   // VQA_SSIM_MS: pyramid levels 1..4 of the largest plane group seen; per-entry scale means
     // pinned host staging
-    hbuf res_host, qres_host, qms_host;
-    // vqa_vif_submit: levels 1..3 of the largest plane group seen; the integer totals; the records (device, pinned host)
-    dbuf vif_pyr, vif_acc, vif_dev;
-    hbuf vif_host;
-    // vqa_adm_submit: the a bands of scales 0..2 of the largest plane group seen; one scale's tile partials; the six sums per
-    // (entry, scale) (device, pinned host)
-    dbuf adm_pyr, adm_part, adm_sums;
-    hbuf adm_host;
-    // vqa_motion_submit: the integer totals (device, pinned host); host frames and their prev0 staged on the device
-    dbuf mot_acc, mot_stage, mot_prev;
-    hbuf mot_host;
-    // vqa_siti_submit: the five integer words per entry (device, pinned host); host frames and their prev0 staged on the device
-    dbuf siti_acc, siti_stage, siti_prev;
-    hbuf siti_host;
-    // vqa_psnr_hvs_submit: the four integer words per entry (device, pinned host); host frames are staged in qstage_*
-    dbuf hvs_acc;
-    hbuf hvs_host;
-    // vqa_ciede_submit: the one integer word per frame (device, pinned host); host frames are staged in qstage_*
-    dbuf ciede_acc;
-    hbuf ciede_host;
-    // vqa_gmsd_submit: the three integer words per entry (device, pinned host); host frames are staged in qstage_*
-    dbuf gmsd_acc;
-    hbuf gmsd_host;
-    // vqa_cambi_submit: the ten integer words per entry (device, pinned host) and the scales and histograms of the largest
-    // group of a slice; host frames are staged in qstage_dist
-    dbuf cambi_acc, cambi_scratch;
-    hbuf cambi_host;
-    // vqa_xpsnr_submit: the integer words per frame and block (device, pinned host); host frames are staged in qstage_*, their
-    // prev0 in a buffer of its own
-    dbuf xpsnr_acc, xpsnr_prev;
-    hbuf xpsnr_host;
-    // vqa_haarpsi_submit: the three integer words per entry (device, pinned host); host frames are staged in qstage_*
-    dbuf haarpsi_acc;
-    hbuf haarpsi_host;
-    // vqa_vca_submit: the three words per entry, then the block map of n + 1 slots (device; pinned host without the first slot);
-    // the tables of k_vca_blocks; host frames and prev0 are staged in siti_stage / siti_prev
-    dbuf vca_acc, vca_tabs;
-    hbuf vca_host;
-    // vqa_artifacts_submit: the 21 integer words per entry (device, pinned host); host frames are staged in qstage_dist
-    dbuf artifacts_acc;
-    hbuf artifacts_host;
-    // vqa_brisque_submit: the 60 integer words per entry (device, pinned host), the scale-1 planes and strips of the largest
-    // plane group of a slice; host frames are staged in qstage_dist
-    dbuf brisque_acc, brisque_scratch;
-    hbuf brisque_host;
-    // vqa_mdsi_submit: the four integer words per frame (device, pinned host) and the map of g of a slice; host frames are
-    // staged in qstage_*
-    dbuf mdsi_acc, mdsi_map;
-    hbuf mdsi_host;
-    // vqa_itp_submit: the two integer words per frame (device, pinned host); host frames are staged in qstage_*
-    dbuf itp_acc;
-    hbuf itp_host;
-    // vqa_pu21_submit: the five integer words per frame (device, pinned host); the two q_Y maps of one sub-slice of frames; lab
-    // build only: the maps of the whole last batch, for vqa_pu21_lab_read_maps; host frames are staged in qstage_*
-    dbuf pu21_acc, pu21_map, pu21_keep;
-    hbuf pu21_host;
-    // vqa_fsim_submit: the three integer words per frame (device, pinned host); the intermediates and the p maps of one sub-slice
-    // of frames; lab build only: the maps of the whole last batch, for vqa_fsim_lab_read_maps; host frames are staged in qstage_*
-    dbuf fsim_acc, fsim_scratch, fsim_map, fsim_keep;
-    hbuf fsim_host;
+    hbuf res_host, qms_host;
+    // host frames staged on the device, shared between kinds (the stream orders a batch behind whatever the ctx has in flight):
+    // the two streams of a pair submit, and the one stream of a one-stream submit in qstage_dist; the reference stream and its
+    // prev0 of a motion submit; the same of an SI/TI or a VCA submit; prev0 of an XPSNR submit
+    dbuf qstage_ref, qstage_dist, mot_stage, mot_prev, siti_stage, siti_prev, xpsnr_prev;
+    // the plane-batch kinds: results, work buffers and the batch in flight
+    batch_slot slot[KIND_COUNT];
 
     // per-geometry tables, at most VQA_TABLE_CACHE_GEOMETRIES of each kind (cache_put evicts the least recently used)
     std::map<std::tuple<int, int, int, int>, cached<resize_tabs>> tabs;
@@ -144,44 +125,11 @@ struct vqa_ctx {
     int dct_wave_slots = 0;                 // wave slots of THIS device for the marching DCT's chunking (set in vqa_create)
     dbuf fb_tmp, fb_blur, fb_img, fb_R, fb_M, fb_flow0, fb_flow1, fb_part;
 
-    // pending work
-    int pend_c = 0, pend_q = 0;
+    // pending work: the complexity batch here, a plane batch in its slot
+    int pend_c = 0;
     bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
-    int pend_v = 0;           // entries of the pending VIF batch (a batch of its own, next to pend_c and pend_q)
-    int pend_a = 0;           // entries of the pending ADM batch (likewise); its planes' sizes, for the host's cube roots
-    int pend_a_planes = 0, pend_a_w[4] = {0}, pend_a_h[4] = {0};
-    int pend_m = 0;           // entries of the pending motion batch (likewise); its planes' areas, for the host's division
-    int pend_m_planes = 0;
-    int64_t pend_m_area[4] = {0};
-    int pend_s = 0;           // entries of the pending SI/TI batch (likewise); its planes' sizes and depth, for the host's formulas
-    int pend_s_planes = 0, pend_s_depth = 8, pend_s_w[4] = {0}, pend_s_h[4] = {0};
-    int pend_h = 0;           // entries of the pending PSNR-HVS batch (likewise); its planes' sizes and depth, for the host's formulas
-    int pend_h_planes = 0, pend_h_depth = 8, pend_h_w[4] = {0}, pend_h_h[4] = {0};
-    int pend_e = 0;           // frames of the pending CIEDE2000 batch (likewise); its luma grid, for the host's mean
-    int pend_e_w = 0, pend_e_h = 0;
-    int pend_g = 0;           // entries of the pending GMSD batch (likewise); its planes' sizes, for the host's formulas
-    int pend_g_planes = 0, pend_g_w[4] = {0}, pend_g_h[4] = {0};
-    int pend_b = 0;           // entries of the pending CAMBI batch (likewise); its planes' sizes, for the host's formulas
-    int pend_b_planes = 0, pend_b_w[4] = {0}, pend_b_h[4] = {0};
-    int pend_x = 0;           // entries of the pending XPSNR batch (likewise); its planes' sizes and depth, for the host's part
-    int pend_x_planes = 0, pend_x_depth = 8, pend_x_w[4] = {0}, pend_x_h[4] = {0};
-    int pend_w = 0;           // entries of the pending HaarPSI batch (likewise)
-    int pend_t = 0;           // entries of the pending VCA batch (likewise); its planes' sizes and depth, for the host's part
-    int pend_t_planes = 0, pend_t_depth = 8, pend_t_w[4] = {0}, pend_t_h[4] = {0};
-    int pend_r = 0;           // entries of the pending artefacts batch (likewise); its planes' sizes and depth, for the host's part
-    int pend_r_planes = 0, pend_r_depth = 8, pend_r_w[4] = {0}, pend_r_h[4] = {0};
-    int pend_n = 0;           // entries of the pending BRISQUE batch (likewise); its planes' sizes, for the host's part
-    int pend_n_planes = 0, pend_n_w[4] = {0}, pend_n_h[4] = {0};
-    int pend_d = 0;           // frames of the pending MDSI batch (likewise); its plane 0, for the host's part
-    int pend_d_w = 0, pend_d_h = 0;
-    int pend_i = 0;           // frames of the pending dE_ITP batch (likewise); its luma grid, for the host's mean
-    int pend_i_w = 0, pend_i_h = 0;
-    int pend_u = 0;           // frames of the pending PU21 batch (likewise); its luma grid, for the host's divisions
-    int pend_u_w = 0, pend_u_h = 0;
-    int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what pu21_keep holds
-    int pend_f = 0;           // frames of the pending FSIM batch (likewise); its plane 0, for the host's part
-    int pend_f_w = 0, pend_f_h = 0;
-    int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what fsim_keep holds (the downsampled grid)
+    int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
+    int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what FSIM's kept maps hold (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
@@ -265,7 +213,12 @@ static int sync_all(vqa_ctx *c)
 }
 
 // a submitted batch of any kind has not been waited for
-static bool busy(const vqa_ctx *c) { return c->pend_c || c->pend_q || c->pend_v || c->pend_a || c->pend_m || c->pend_s || c->pend_h || c->pend_e || c->pend_g || c->pend_b || c->pend_x || c->pend_w || c->pend_t || c->pend_r || c->pend_n || c->pend_d || c->pend_i || c->pend_u || c->pend_f; }
+static bool busy(const vqa_ctx *c)
+{
+    for (const batch_slot &s : c->slot)
+        if (s.entries) return true;
+    return c->pend_c != 0;
+}
 
 // lab build: VQA_FAIL_ENSURE_AT=N makes the N-th device reservation of this ctx (scratch buffer or table) report OOM
 static inline bool seam_reservation_fails(vqa_ctx *c)
@@ -309,6 +262,12 @@ static int ensure_pinned(vqa_ctx *c, hbuf &b, size_t bytes)
 static void release(dbuf &b)
 {
     if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+}
+
+static void release(hbuf &b)
+{
+    if (b.p) (void)hipHostFree(b.p);
     b.p = nullptr; b.cap = 0;
 }
 
@@ -936,24 +895,28 @@ int vqa_build_flavour(void)
     return f;
 }
 
-// every grow-only buffer, the result staging and every cached table of an idle ctx (vqa_trim, vqa_destroy)
+// every grow-only buffer, the result staging and every cached table of an idle ctx (vqa_trim, vqa_destroy); named here: the complexity batch's buffers, quality's extras, the shared staging and Farneback's - a plane-batch kind's own are in its slot
 static void release_scratch(vqa_ctx *c)
 {
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
-                    &c->dct_pe, &c->dct_pt, &c->qres_dev, &c->qpartials, &c->qstage_ref, &c->qstage_dist,
-                    &c->qms_pyr, &c->qms_dev, &c->vif_pyr, &c->vif_acc, &c->vif_dev, &c->adm_pyr, &c->adm_part, &c->adm_sums, &c->mot_acc, &c->mot_stage, &c->mot_prev, &c->siti_acc, &c->siti_stage, &c->siti_prev, &c->hvs_acc, &c->ciede_acc, &c->gmsd_acc, &c->cambi_acc, &c->cambi_scratch, &c->xpsnr_acc, &c->xpsnr_prev, &c->haarpsi_acc, &c->vca_acc, &c->vca_tabs, &c->artifacts_acc, &c->brisque_acc, &c->brisque_scratch, &c->mdsi_acc, &c->mdsi_map, &c->itp_acc, &c->pu21_acc, &c->pu21_map, &c->pu21_keep, &c->fsim_acc, &c->fsim_scratch, &c->fsim_map, &c->fsim_keep, &c->fb_tmp, &c->fb_blur, &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
+                    &c->dct_pe, &c->dct_pt, &c->qpartials, &c->qms_pyr, &c->qms_dev, &c->qstage_ref, &c->qstage_dist,
+                    &c->mot_stage, &c->mot_prev, &c->siti_stage, &c->siti_prev, &c->xpsnr_prev, &c->fb_tmp, &c->fb_blur,
+                    &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
+    for (batch_slot &s : c->slot) {   // everything a plane-batch kind owns
+        release(s.dev);
+        release(s.host);
+        for (dbuf &b : s.work) release(b);
+    }
+    release(c->res_host);
+    release(c->qms_host);
     for (auto &kv : c->tabs) free_table(kv.second.v);
     for (auto &kv : c->fb_tabs) free_table(kv.second.v);
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     for (auto &kv : c->fsim_tables) free_table(kv.second.v);
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear(); c->fsim_tables.clear();
-    for (hbuf *b : {&c->res_host, &c->qres_host, &c->qms_host, &c->vif_host, &c->adm_host, &c->mot_host, &c->siti_host, &c->hvs_host, &c->ciede_host, &c->gmsd_host, &c->cambi_host, &c->xpsnr_host, &c->haarpsi_host, &c->vca_host, &c->artifacts_host, &c->brisque_host, &c->mdsi_host, &c->itp_host, &c->pu21_host, &c->fsim_host}) {
-        if (b->p) (void)hipHostFree(b->p);
-        b->p = nullptr; b->cap = 0;
-    }
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
     c->last_u_n = 0;
@@ -1078,7 +1041,7 @@ extern "C" __attribute__((visibility("hidden"))) void *vqa_ctx_stream_(const vqa
 // A submit that fails after it has started to enqueue must not hand the caller's buffers (and this ctx's scratch) back
 // while kernels or copies still use them: whatever the failing step was - a reservation, a copy, a launch, in the first
 // slice or a later one, before or after the fork onto the side streams - the public entry points below drain EVERY
-// stream of the ctx, drop the submit's timing events and leave the ctx idle and usable (pend_* stay 0).  The reference's
+// stream of the ctx, drop the submit's timing events and leave the ctx idle and usable (no batch is recorded as pending).  The reference's
 // convention for a failed step is log-and-re-raise with nothing left running (video_processing.py:295-297).
 static int drain_failed_submit(vqa_ctx *c, int rc, bool touched)
 {
@@ -1452,8 +1415,10 @@ int vqa_complexity_wait(vqa_ctx *c, vqa_frame_metrics *out, int n)
 }
 
 // ---------------------------------------------------------------------------
-// What the eighteen plane-batch submits (quality, VIF, ADM, motion, SI/TI, PSNR-HVS, CIEDE2000, GMSD, CAMBI, XPSNR, HaarPSI, VCA, artefacts, BRISQUE, MDSI, dE_ITP, PU21, FSIM) share: the checks, the staging of host frames, the walk over
-// slices and plane groups, the sizing of per-group scratch and the drain of a failed submit.
+// What the plane-batch kinds (enum batch_kind) share.  A submit body is: bad_batch_args and the kind's own argument checks;
+// check_batch; stage_batch (or stage_pair); the kind's reservations and launches over for_each_slice / for_each_group;
+// finish_batch.  A wait is wait_batch around the kind's finalize, or wait_pending and wait_synced around a check of its own.
+// Every public submit goes through submit_and_drain.
 extern "C++" {   // (templates among them)
 
 // arguments and mem_kind (dist: the second stream; a submit that has none passes `ref` again)
@@ -1471,7 +1436,7 @@ struct plane_batch {
 
 // The descriptor rules, per plane in plane order: depth, 16-bit alignment, geometry (VQA_ERR_INVALID), then limits(d) - the
 // metric's own VQA_ERR_UNSUPPORTED rules - and only then the next plane.  The order decides the status of a list that breaks
-// several rules at once.  The frame strides are the caller's to check against B.span, after all planes.
+// several rules at once.  The frame strides are checked against B.span after all planes (check_batch).
 template <class F> static int check_planes(const vqa_plane_desc *planes, int n_planes, plane_batch &B, F limits)
 {
     // sample depth (vqa_plane_desc.bit_depth): 0 / 8 = uint8, 9..16 = little-endian uint16 at even byte offsets, strides and
@@ -1500,11 +1465,46 @@ template <class F> static int check_planes(const vqa_plane_desc *planes, int n_p
     return VQA_OK;
 }
 
-// the limits of VIF, ADM and motion: a smallest side, and the 2^28 samples that bound the 64-bit totals and the sums (vqa.h)
+// the limits most kinds start from: a smallest side, and the 2^28 samples that bound the 64-bit totals and the sums (vqa.h)
 static int side_and_area_limits(const vqa_plane_desc &d, int min_dim)
 {
     if (d.width < min_dim || d.height < min_dim) return VQA_ERR_UNSUPPORTED;
     if ((int64_t)d.width * d.height > (1ll << 28)) return VQA_ERR_UNSUPPORTED;
+    return VQA_OK;
+}
+
+// the limits of a kind that takes the planes of a pixel together: they are plane 0's (the chroma planes of a 16 x 16 4:2:0
+// frame are 8 x 8)
+static auto plane0_limits(const vqa_plane_desc *planes, int min_dim)
+{
+    return [=](const vqa_plane_desc &d) { return &d == planes ? side_and_area_limits(d, min_dim) : (int)VQA_OK; };
+}
+
+// The three planes of a pixel, taken together: U and V are alike; under a BGR model all three planes are alike; otherwise the
+// chroma planes have the luma's size or its ceil-half, in either direction.
+enum joint_rule { JOINT_NONE, JOINT_YUV, JOINT_BGR };
+
+static bool joint_planes_ok(const vqa_plane_desc *planes, joint_rule rule)
+{
+    const vqa_plane_desc &y = planes[0], &u = planes[1], &v = planes[2];
+    auto alike = [](const vqa_plane_desc &a, const vqa_plane_desc &b) {
+        return a.width == b.width && a.height == b.height && a.row_stride == b.row_stride && a.pixel_step == b.pixel_step;
+    };
+    if (!alike(u, v)) return false;
+    if (rule == JOINT_BGR) return alike(u, y);
+    return (u.width == y.width || u.width == (y.width + 1) / 2) && (u.height == y.height || u.height == (y.height + 1) / 2);
+}
+
+// The checks of a submit that follow the kind's own argument checks, in the order that decides the status: a pending batch of
+// the kind (VQA_ERR_STATE), the planes one by one (check_planes), the joint rule of three planes, the frame strides of the one
+// or two streams (a submit that has one passes its stride twice).
+template <class F> static int check_batch(const batch_slot &s, int n, int64_t fs_a, int64_t fs_b, const vqa_plane_desc *planes,
+                                          int n_planes, plane_batch &B, F limits, joint_rule joint = JOINT_NONE)
+{
+    if (s.entries) return VQA_ERR_STATE;
+    if (int rc = check_planes(planes, n_planes, B, limits)) return rc;
+    if (joint != JOINT_NONE && !joint_planes_ok(planes, joint)) return VQA_ERR_INVALID;
+    if (n > 1 && (fs_a < B.span || fs_b < B.span)) return VQA_ERR_INVALID;
     return VQA_OK;
 }
 
@@ -1517,14 +1517,35 @@ static int stage(vqa_ctx *c, dbuf &buf, const uint8_t *&frames, size_t bytes)
     return VQA_OK;
 }
 
-// the two host streams of a quality, a VIF, an ADM, a PSNR-HVS, a CIEDE2000, a GMSD, an XPSNR, a HaarPSI, an MDSI, a dE_ITP, a PU21 or an FSIM submit.  The twelve share qstage_*: the stream orders a batch behind
-// whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
-static int stage_pair(vqa_ctx *c, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs, const uint8_t *&dist,
-                      int64_t dist_fs)
+// one input of a submit - the caller's pointer to its frames, their stride and where host frames are staged - or none
+struct batch_input {
+    const uint8_t **frames = nullptr;
+    int64_t fs = 0;
+    dbuf *buf = nullptr;
+};
+
+// What follows the checks of a submit: the device is made current, `touched` is set - from here on a failure is drained by the
+// caller (drain_failed_submit) - and host frames are staged, in this order: stream a, stream b if the submit has one, the one
+// frame prev0 if the submit takes one and the caller gave it.  The staged pointers replace the caller's.
+static int stage_batch(vqa_ctx *c, bool &touched, int mem_kind, int n, int64_t span, batch_input a, batch_input b = {},
+                       batch_input prev0 = {})
 {
+    HIPCHK(c, hipSetDevice(c->device));
+    touched = true;
     if (mem_kind != VQA_MEM_HOST) return VQA_OK;
-    if (int rc = stage(c, c->qstage_ref, ref, (size_t)(n - 1) * ref_fs + span)) return rc;
-    return stage(c, c->qstage_dist, dist, (size_t)(n - 1) * dist_fs + span);
+    for (const batch_input &s : {a, b})
+        if (s.frames)
+            if (int rc = stage(c, *s.buf, *s.frames, (size_t)(n - 1) * s.fs + span)) return rc;
+    if (prev0.frames && *prev0.frames) return stage(c, *prev0.buf, *prev0.frames, (size_t)span);
+    return VQA_OK;
+}
+
+// stage_batch for the two host streams of a pair submit.  All pair submits share qstage_*: the stream orders a batch behind
+// whatever the ctx already has in flight, so a pending batch of another kind reads its frames before they are overwritten.
+static int stage_pair(vqa_ctx *c, bool &touched, int mem_kind, int n, int64_t span, const uint8_t *&ref, int64_t ref_fs,
+                      const uint8_t *&dist, int64_t dist_fs, batch_input prev0 = {})
+{
+    return stage_batch(c, touched, mem_kind, n, span, {&ref, ref_fs, &c->qstage_ref}, {&dist, dist_fs, &c->qstage_dist}, prev0);
 }
 
 constexpr int QSLICE = 32768; // frames ride in gridDim.y (<= 65535): larger batches go out as consecutive slices
@@ -1594,6 +1615,71 @@ template <class F> static int submit_and_drain(vqa_ctx *c, F body)
     return drain_failed_submit(c, rc, touched);
 }
 
+// the batch in flight: the last thing a successful submit does (a submit that fails anywhere leaves the slot idle)
+static void record_batch(batch_slot &s, int entries, const vqa_plane_desc *planes, int n_planes, int depth)
+{
+    s.entries = entries;
+    s.planes = n_planes;
+    s.depth = depth;
+    for (int p = 0; p < n_planes; p++) { s.w[p] = planes[p].width; s.h[p] = planes[p].height; }
+}
+
+// the tail of a submit: the launches' status, the first `bytes` of the slot's words to its pinned copy, the record
+static int finish_batch(vqa_ctx *c, batch_slot &s, size_t bytes, int entries, const vqa_plane_desc *planes, int n_planes, int depth)
+{
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(s.host.p, s.dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    record_batch(s, entries, planes, n_planes, depth);
+    return VQA_OK;
+}
+
+// The frame of a wait, in two steps.  wait_pending: the arguments, and the kind's batch in flight (`s`) - a wrong n_entries is
+// VQA_ERR_STATE and the batch stays pending, whatever else is pending.  A kind with more to check does so between the two, and
+// the batch stays pending if it refuses.  wait_synced: the stream synchronised and the timing events folded in; the caller
+// then reads s->host and sets s->entries = 0.
+static int wait_pending(vqa_ctx *c, batch_kind kind, const void *out, int n_entries, batch_slot *&s)
+{
+    if (!c || !out) return VQA_ERR_INVALID;
+    s = &c->slot[kind];
+    if (!s->entries || n_entries != s->entries) return VQA_ERR_STATE;
+    return VQA_OK;
+}
+
+static int wait_synced(vqa_ctx *c)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return VQA_OK;
+}
+
+// the whole wait of a kind whose pinned copy holds `words` words of T per entry: finalize(the entry's words, the slot, the
+// entry's plane index, its record)
+template <class T = unsigned long long, class Out, class F>
+static int wait_batch(vqa_ctx *c, batch_kind kind, Out *out, int n_entries, int words, F finalize)
+{
+    batch_slot *s;
+    if (int rc = wait_pending(c, kind, out, n_entries, s)) return rc;
+    if (int rc = wait_synced(c)) return rc;
+    const T *acc = (const T *)s->host.p;
+    for (int e = 0; e < n_entries; e++) finalize(acc + (size_t)e * words, *s, e % s->planes, out + e);
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// The marks of a launcher that runs several kernels (cambi_mark, brisque_mark): one prof_scope per kernel id at a time, open
+// between its begin and its end.  marks::mark and the address of a marks go to the launcher.
+struct marks {
+    vqa_ctx *c;
+    std::optional<prof_scope> open;
+    explicit marks(vqa_ctx *c_) : c(c_) {}
+    static void mark(void *p, int id, int begin)
+    {
+        marks *m = (marks *)p;
+        if (begin) m->open.emplace(m->c, id);
+        else m->open.reset();
+    }
+};
+
 } // extern "C++"
 
 // ---------------------------------------------------------------------------
@@ -1602,11 +1688,11 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (ssim_mode != VQA_SSIM_GAUSS && ssim_mode != VQA_SSIM_FFMPEG && ssim_mode != VQA_SSIM_MS) return VQA_ERR_INVALID;
-    if (c->pend_q) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_QUALITY];
     const bool ms = ssim_mode == VQA_SSIM_MS, gauss = ms || ssim_mode == VQA_SSIM_GAUSS;   // MS: the Gaussian window on five scales
     int maxblocks = 1;
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
         // k_ssim_gauss addresses a strip's rows through a 32-bit scalar buffer offset (row * row_stride) plus a 32-bit
         // lane offset: a plane whose rows span 2 GiB (absurd strides / regions of interest only) would wrap silently
         if (gauss &&
@@ -1619,14 +1705,11 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
         return VQA_OK;
     });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
-    if ((rc = ensure(c, c->qres_dev, sizeof(vqa_plane_metrics) * nent))) return rc;
-    if ((rc = ensure_pinned(c, c->qres_host, sizeof(vqa_plane_metrics) * nent))) return rc;
+    if ((rc = ensure(c, s.dev, sizeof(vqa_plane_metrics) * nent))) return rc;
+    if ((rc = ensure_pinned(c, s.host, sizeof(vqa_plane_metrics) * nent))) return rc;
     const int nslice = slice_frames(c, n), depth = B.depth;
     // (MS: a second half of the same size for the cs totals; level 0 has the most tiles)
     if ((rc = ensure(c, c->qpartials, sizeof(double) * (size_t)maxblocks * nslice * n_planes * (ms ? 2 : 1)))) return rc;
@@ -1639,10 +1722,10 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
         if ((rc = ensure(c, c->qms_dev, sizeof(vqa_ms_scales) * nent))) return rc;
         if ((rc = ensure_pinned(c, c->qms_host, sizeof(vqa_ms_scales) * nent))) return rc;
     }
-    HIPCHK(c, hipMemsetAsync(c->qres_dev.p, 0, sizeof(vqa_plane_metrics) * nent, st));
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, sizeof(vqa_plane_metrics) * nent, st));
     const int64_t pstride = (int64_t)maxblocks * nslice;
     for_each_slice(c, n, [&](int a0, int m) {
-        vqa_plane_metrics *res = (vqa_plane_metrics *)c->qres_dev.p + (size_t)a0 * n_planes;
+        vqa_plane_metrics *res = (vqa_plane_metrics *)s.dev.p + (size_t)a0 * n_planes;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             if (ms) {
@@ -1669,12 +1752,13 @@ static int quality_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *di
                                       (double *)c->qpartials.p, pstride, res, depth);
         });
     });
-    if (ms) launch_ms_combine(st, (const vqa_ms_scales *)c->qms_dev.p, (int)nent, (vqa_plane_metrics *)c->qres_dev.p);
+    if (ms) launch_ms_combine(st, (const vqa_ms_scales *)c->qms_dev.p, (int)nent, (vqa_plane_metrics *)s.dev.p);
+    // (the tail inline: the scales of an MS batch are copied as well, and the record comes after every copy)
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->qres_host.p, c->qres_dev.p, sizeof(vqa_plane_metrics) * nent, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(s.host.p, s.dev.p, sizeof(vqa_plane_metrics) * nent, hipMemcpyDeviceToHost, st));
     if (ms) HIPCHK(c, hipMemcpyAsync(c->qms_host.p, c->qms_dev.p, sizeof(vqa_ms_scales) * nent, hipMemcpyDeviceToHost, st));
     c->pend_q_ms = ms;
-    c->pend_q = (int)nent;
+    record_batch(s, (int)nent, planes, n_planes, depth);
     return VQA_OK;
 }
 
@@ -1689,13 +1773,14 @@ int vqa_quality_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int 
 int vqa_quality_wait_ms(vqa_ctx *c, vqa_plane_metrics *out, vqa_ms_scales *scales, int n_entries)
 {
     if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_q || n_entries != c->pend_q) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_QUALITY];
+    if (!s.entries || n_entries != s.entries) return VQA_ERR_STATE;
     if (scales && !c->pend_q_ms) return VQA_ERR_STATE;   // (the batch stays pending: vqa_quality_wait collects it)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    memcpy(out, c->qres_host.p, sizeof(vqa_plane_metrics) * (size_t)n_entries);
+    memcpy(out, s.host.p, sizeof(vqa_plane_metrics) * (size_t)n_entries);
     if (scales) memcpy(scales, c->qms_host.p, sizeof(vqa_ms_scales) * (size_t)n_entries);
-    c->pend_q = 0;
+    s.entries = 0;
     c->pend_q_ms = false;
     return VQA_OK;
 }
@@ -1706,38 +1791,37 @@ int vqa_quality_wait(vqa_ctx *c, vqa_plane_metrics *out, int n_entries)
 }
 
 // ---------------------------------------------------------------------------
-// VIF on four scales.  A batch of its own (pend_v): the stream orders it behind whatever the ctx already has in flight, so
-// the host staging (qstage_*) and the caller's device frames are shared with a pending quality batch without a hazard.
+// VIF on four scales.  A batch of its own: the stream orders it behind whatever the ctx already has in flight, so the host
+// staging (qstage_*) and the caller's device frames are shared with a pending batch of another kind without a hazard.
 static int vif_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_v) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_VIF];
+    dbuf &vif_pyr = s.work[0], &vif_acc = s.work[1];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, VIF_MIN_DIM); });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, VIF_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(long long) * 2 * VIF_LEVELS * nent;
-    if ((rc = ensure(c, c->vif_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->vif_dev, sizeof(vqa_vif_metrics) * nent))) return rc;
-    if ((rc = ensure_pinned(c, c->vif_host, sizeof(vqa_vif_metrics) * nent))) return rc;
+    if ((rc = ensure(c, vif_acc, acc_bytes))) return rc;
+    if ((rc = ensure(c, s.dev, sizeof(vqa_vif_metrics) * nent))) return rc;
+    if ((rc = ensure_pinned(c, s.host, sizeof(vqa_vif_metrics) * nent))) return rc;
     const int nslice = slice_frames(c, n), depth = B.depth;
     // the level scratch: levels 1..3 of the largest plane group
     const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
         return sizeof(float) * (size_t)vif_levels(nslice, cnt, h, w).total;
     });
-    if ((rc = ensure(c, c->vif_pyr, pyr))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->vif_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, vif_pyr, pyr))) return rc;
+    HIPCHK(c, hipMemsetAsync(vif_acc.p, 0, acc_bytes, st));
     for_each_slice(c, n, [&](int a0, int m) {
-        long long *acc = (long long *)c->vif_acc.p + (size_t)a0 * n_planes * 2 * VIF_LEVELS;
+        long long *acc = (long long *)vif_acc.p + (size_t)a0 * n_planes * 2 * VIF_LEVELS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
-            float *scratch = (float *)c->vif_pyr.p;
+            float *scratch = (float *)vif_pyr.p;
             for (int lv = 0; lv < VIF_LEVELS; lv++) {
                 if (lv > 0) {
                     prof_scope pd_(c, VQA_K_VIF_DECIMATE);
@@ -1748,11 +1832,8 @@ static int vif_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
             }
         });
     });
-    launch_vif_finalize(st, (const long long *)c->vif_acc.p, (int)nent, (vqa_vif_metrics *)c->vif_dev.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->vif_host.p, c->vif_dev.p, sizeof(vqa_vif_metrics) * nent, hipMemcpyDeviceToHost, st));
-    c->pend_v = (int)nent;
-    return VQA_OK;
+    launch_vif_finalize(st, (const long long *)vif_acc.p, (int)nent, (vqa_vif_metrics *)s.dev.p);
+    return finish_batch(c, s, sizeof(vqa_vif_metrics) * nent, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_vif_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
@@ -1765,34 +1846,29 @@ int vqa_vif_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_
 
 int vqa_vif_wait(vqa_ctx *c, vqa_vif_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_v || n_entries != c->pend_v) return VQA_ERR_STATE;   // (a pending quality batch stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    memcpy(out, c->vif_host.p, sizeof(vqa_vif_metrics) * (size_t)n_entries);
-    c->pend_v = 0;
-    return VQA_OK;
+    // (the device finalizes VIF: the pinned copy holds the records)
+    return wait_batch<vqa_vif_metrics>(c, KIND_VIF, out, n_entries, 1,
+                                       [](const vqa_vif_metrics *r, const batch_slot &, int, vqa_vif_metrics *o) { *o = *r; });
 }
 
 // ---------------------------------------------------------------------------
-// ADM on four scales.  A batch of its own (pend_a), ordered by the stream like a VIF batch.
+// ADM on four scales.  A batch of its own, ordered by the stream like a VIF batch.
 static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_a) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_ADM];
+    dbuf &adm_pyr = s.work[0], &adm_part = s.work[1];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, ADM_MIN_DIM); });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, ADM_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t sums_bytes = sizeof(double) * 6 * ADM_LEVELS * nent;
-    if ((rc = ensure(c, c->adm_sums, sums_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->adm_host, sums_bytes))) return rc;
+    if ((rc = ensure(c, s.dev, sums_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, sums_bytes))) return rc;
     const int nslice = slice_frames(c, n), depth = B.depth;
     // the band scratch and the partials serve one group of same-geometry planes (and one scale) at a time
     const size_t pyr = largest_group_bytes(planes, n_planes, [&](int cnt, int h, int w) {
@@ -1802,29 +1878,24 @@ static int adm_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
         const adm_layout L = adm_levels(nslice, cnt, h, w);
         return sizeof(double) * 6 * (size_t)nslice * cnt * adm_tiles(L.h[1], L.w[1]);
     });
-    if ((rc = ensure(c, c->adm_pyr, pyr))) return rc;
-    if ((rc = ensure(c, c->adm_part, part))) return rc;
+    if ((rc = ensure(c, adm_pyr, pyr))) return rc;
+    if ((rc = ensure(c, adm_part, part))) return rc;
     for_each_slice(c, n, [&](int a0, int m) {
-        double *sums = (double *)c->adm_sums.p + (size_t)a0 * n_planes * 6 * ADM_LEVELS;
+        double *sums = (double *)s.dev.p + (size_t)a0 * n_planes * 6 * ADM_LEVELS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             for (int sc = 0; sc < ADM_LEVELS; sc++) {
                 {
                     prof_scope ps_(c, VQA_K_ADM);
-                    launch_adm_scale(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, depth, sc, (float *)c->adm_pyr.p,
-                                     (double *)c->adm_part.p);
+                    launch_adm_scale(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, depth, sc, (float *)adm_pyr.p,
+                                     (double *)adm_part.p);
                 }
                 prof_scope pr_(c, VQA_K_ADM_REDUCE);
-                launch_adm_reduce(st, (const double *)c->adm_part.p, m, planes, idx, cnt, n_planes, sc, sums);
+                launch_adm_reduce(st, (const double *)adm_part.p, m, planes, idx, cnt, n_planes, sc, sums);
             }
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->adm_host.p, c->adm_sums.p, sums_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_a = (int)nent;
-    c->pend_a_planes = n_planes;
-    for (int p = 0; p < n_planes; p++) { c->pend_a_w[p] = planes[p].width; c->pend_a_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, sums_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_adm_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
@@ -1837,46 +1908,34 @@ int vqa_adm_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_
 
 int vqa_adm_wait(vqa_ctx *c, vqa_adm_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_a || n_entries != c->pend_a) return VQA_ERR_STATE;   // (a pending quality or VIF batch stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const double *sums = (const double *)c->adm_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_a_planes;
-        adm_finalize(sums + (size_t)e * 6 * ADM_LEVELS, c->pend_a_h[p], c->pend_a_w[p], out + e);
-    }
-    c->pend_a = 0;
-    return VQA_OK;
+    return wait_batch<double>(c, KIND_ADM, out, n_entries, 6 * ADM_LEVELS,
+                              [](const double *sums, const batch_slot &s, int p, vqa_adm_metrics *o) {
+                                  adm_finalize(sums, s.h[p], s.w[p], o);   // (the planes' sizes: the host's cube roots)
+                              });
 }
 
 // ---------------------------------------------------------------------------
-// VMAF's motion feature: the reference stream alone, frame i against frame i - 1.  A batch of its own (pend_m), ordered by the
-// stream like a VIF batch.  Host frames (and prev0) are staged in buffers of their own.
+// VMAF's motion feature: the reference stream alone, frame i against frame i - 1.  A batch of its own, ordered by the stream
+// like a VIF batch.  Host frames (and prev0) are staged in buffers of their own.
 static int motion_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
                               const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_m) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_MOTION];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, MOTION_MIN_DIM); });
+    int rc = check_batch(s, n, ref_fs, ref_fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, MOTION_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && ref_fs < B.span) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&ref, ref_fs, &c->mot_stage}, {}, {&prev0, 0, &c->mot_prev}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if (mem_kind == VQA_MEM_HOST) {
-        if ((rc = stage(c, c->mot_stage, ref, (size_t)(n - 1) * ref_fs + B.span))) return rc;
-        if (prev0 && (rc = stage(c, c->mot_prev, prev0, (size_t)B.span))) return rc;
-    }
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(long long) * nent;
-    if ((rc = ensure(c, c->mot_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->mot_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->mot_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        long long *acc = (long long *)c->mot_acc.p + (size_t)a0 * n_planes;
+        long long *acc = (long long *)s.dev.p + (size_t)a0 * n_planes;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
         const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -1884,12 +1943,7 @@ static int motion_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *pre
             launch_motion_sad(st, sref, sprev, m, ref_fs, planes, idx, cnt, n_planes, depth, acc);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->mot_host.p, c->mot_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_m = (int)nent;
-    c->pend_m_planes = n_planes;
-    for (int p = 0; p < n_planes; p++) c->pend_m_area[p] = (int64_t)planes[p].width * planes[p].height;
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_motion_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
@@ -1902,52 +1956,40 @@ int vqa_motion_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int 
 
 int vqa_motion_wait(vqa_ctx *c, vqa_motion_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_m || n_entries != c->pend_m) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const long long *acc = (const long long *)c->mot_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        out[e].sad = (double)acc[e] * (1.0 / 65536.0);   // exact for in-range samples (a total below 2^52); a total above 2^53 is rounded once, to double
-        out[e].motion = out[e].sad / (double)c->pend_m_area[e % c->pend_m_planes];
-    }
-    c->pend_m = 0;
-    return VQA_OK;
+    return wait_batch<long long>(c, KIND_MOTION, out, n_entries, 1,
+                                 [](const long long *acc, const batch_slot &s, int p, vqa_motion_metrics *o) {
+                                     // exact for in-range samples (a total below 2^52); a total above 2^53 is rounded once, to double
+                                     o->sad = (double)*acc * (1.0 / 65536.0);
+                                     o->motion = o->sad / (double)((int64_t)s.w[p] * s.h[p]);
+                                 });
 }
 
 // ---------------------------------------------------------------------------
 // ITU-T P.910 spatial and temporal information: the reference stream alone, Sobel on frame i and frame i against frame i - 1.
-// A batch of its own (pend_s), ordered by the stream like a motion batch.  Host frames (and prev0) are staged in buffers of
-// their own.
+// A batch of its own, ordered by the stream like a motion batch.  Host frames (and prev0) are staged in buffers of their own.
 static int siti_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
                             const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_s) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_SITI];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+    int rc = check_batch(s, n, ref_fs, ref_fs, planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
         if (int lim = side_and_area_limits(d, SITI_MIN_DIM)) return lim;
         // grad_sq: q < 2^37.01 for arbitrary 16-bit samples, so 2^26 of them stay below 2^64 (vqa.h)
         if (B.depth > 8 && (int64_t)d.width * d.height > (1ll << 26)) return VQA_ERR_UNSUPPORTED;
         return VQA_OK;
     });
     if (rc) return rc;
-    if (n > 1 && ref_fs < B.span) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&ref, ref_fs, &c->siti_stage}, {}, {&prev0, 0, &c->siti_prev}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if (mem_kind == VQA_MEM_HOST) {
-        if ((rc = stage(c, c->siti_stage, ref, (size_t)(n - 1) * ref_fs + B.span))) return rc;
-        if (prev0 && (rc = stage(c, c->siti_prev, prev0, (size_t)B.span))) return rc;
-    }
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * SITI_WORDS * nent;
-    if ((rc = ensure(c, c->siti_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->siti_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->siti_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->siti_acc.p + (size_t)a0 * n_planes * SITI_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * SITI_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
         const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
@@ -1955,13 +1997,7 @@ static int siti_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0
             launch_siti(st, sref, sprev, m, ref_fs, planes, idx, cnt, n_planes, depth, acc);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->siti_host.p, c->siti_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_s = (int)nent;
-    c->pend_s_planes = n_planes;
-    c->pend_s_depth = depth;
-    for (int p = 0; p < n_planes; p++) { c->pend_s_w[p] = planes[p].width; c->pend_s_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_siti_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
@@ -1974,56 +2010,41 @@ int vqa_siti_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int me
 
 int vqa_siti_wait(vqa_ctx *c, vqa_siti_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_s || n_entries != c->pend_s) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->siti_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_s_planes;
-        siti_finalize(acc + (size_t)e * SITI_WORDS, c->pend_s_h[p], c->pend_s_w[p], c->pend_s_depth, out + e);
-    }
-    c->pend_s = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_SITI, out, n_entries, SITI_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int p, vqa_siti_metrics *o) {
+                          siti_finalize(acc, s.h[p], s.w[p], s.depth, o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// PSNR-HVS and PSNR-HVS-M: both streams, the whole 8x8 blocks of every plane.  A batch of its own (pend_h), ordered by the
-// stream like a VIF batch, whose host staging (qstage_*) it shares.
+// PSNR-HVS and PSNR-HVS-M: both streams, the whole 8x8 blocks of every plane.  A batch of its own, ordered by the stream
+// like a VIF batch, whose host staging (qstage_*) it shares.
 static int psnr_hvs_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                                 int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_h) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_PSNR_HVS];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, PSNR_HVS_MIN_DIM); });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, PSNR_HVS_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * PSNR_HVS_WORDS * nent;
-    if ((rc = ensure(c, c->hvs_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->hvs_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->hvs_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->hvs_acc.p + (size_t)a0 * n_planes * PSNR_HVS_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * PSNR_HVS_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             prof_scope ps_(c, VQA_K_PSNR_HVS);
             launch_psnr_hvs(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes, depth, acc);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->hvs_host.p, c->hvs_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_h = (int)nent;
-    c->pend_h_planes = n_planes;
-    c->pend_h_depth = depth;
-    for (int p = 0; p < n_planes; p++) { c->pend_h_w[p] = planes[p].width; c->pend_h_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_psnr_hvs_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
@@ -2036,21 +2057,14 @@ int vqa_psnr_hvs_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int
 
 int vqa_psnr_hvs_wait(vqa_ctx *c, vqa_psnr_hvs_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_h || n_entries != c->pend_h) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->hvs_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_h_planes;
-        psnr_hvs_finalize(acc + (size_t)e * PSNR_HVS_WORDS, c->pend_h_h[p], c->pend_h_w[p], c->pend_h_depth, out + e);
-    }
-    c->pend_h = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_PSNR_HVS, out, n_entries, PSNR_HVS_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int p, vqa_psnr_hvs_metrics *o) {
+                          psnr_hvs_finalize(acc, s.h[p], s.w[p], s.depth, o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// CIEDE2000: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own (pend_e), ordered by
+// CIEDE2000: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own, ordered by
 // the stream like a PSNR-HVS batch, whose host staging (qstage_*) it shares.
 static int ciede_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                              int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int model, const double *weights,
@@ -2063,43 +2077,24 @@ static int ciede_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist
         if (!std::isfinite(weights[i]) || !(weights[i] > 0.0)) return VQA_ERR_INVALID;
         k[i] = weights[i];
     }
-    if (c->pend_e) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_CIEDE];
     plane_batch B;
-    // the size limits are the luma grid's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
-        return &d == planes ? side_and_area_limits(d, CIEDE_MIN_DIM) : (int)VQA_OK;
-    });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, plane0_limits(planes, CIEDE_MIN_DIM),
+                         model == VQA_CIEDE_BGR ? JOINT_BGR : JOINT_YUV);
     if (rc) return rc;
-    const vqa_plane_desc &y = planes[0], &u = planes[1], &v = planes[2];
-    if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
-        return VQA_ERR_INVALID;
-    if (model == VQA_CIEDE_BGR) {
-        if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
-            return VQA_ERR_INVALID;
-    } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
-        return VQA_ERR_INVALID;
-    }
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t acc_bytes = sizeof(unsigned long long) * (size_t)n;
-    if ((rc = ensure(c, c->ciede_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->ciede_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->ciede_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
         prof_scope ps_(c, VQA_K_CIEDE);
         launch_ciede(st, ref + (int64_t)a0 * ref_fs, dist + (int64_t)a0 * dist_fs, m, ref_fs, dist_fs, planes, depth, model, k,
-                     (unsigned long long *)c->ciede_acc.p + a0);
+                     (unsigned long long *)s.dev.p + a0);
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->ciede_host.p, c->ciede_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_e = n;
-    c->pend_e_w = y.width;
-    c->pend_e_h = y.height;
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, n, planes, n_planes, depth);
 }
 
 int vqa_ciede_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
@@ -2112,52 +2107,42 @@ int vqa_ciede_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int me
 
 int vqa_ciede_wait(vqa_ctx *c, vqa_ciede_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_e || n_entries != c->pend_e) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->ciede_host.p;
-    for (int e = 0; e < n_entries; e++) ciede_finalize(acc[e], c->pend_e_h, c->pend_e_w, out + e);
-    c->pend_e = 0;
-    return VQA_OK;
+    // (one entry per frame: the luma grid, for the host's mean)
+    return wait_batch(c, KIND_CIEDE, out, n_entries, 1,
+                      [](const unsigned long long *acc, const batch_slot &s, int, vqa_ciede_metrics *o) {
+                          ciede_finalize(*acc, s.h[0], s.w[0], o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// GMSD: both streams, every plane by itself.  A batch of its own (pend_g), ordered by the stream like a PSNR-HVS batch, whose
+// GMSD: both streams, every plane by itself.  A batch of its own, ordered by the stream like a PSNR-HVS batch, whose
 // host staging (qstage_*) it shares.
 static int gmsd_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                             int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_g) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_GMSD];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, GMSD_MIN_DIM); });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, GMSD_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * GMSD_WORDS * nent;
-    if ((rc = ensure(c, c->gmsd_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->gmsd_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->gmsd_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->gmsd_acc.p + (size_t)a0 * n_planes * GMSD_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * GMSD_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             prof_scope ps_(c, VQA_K_GMSD);
             launch_gmsd(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes, depth, acc);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->gmsd_host.p, c->gmsd_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_g = (int)nent;
-    c->pend_g_planes = n_planes;
-    for (int p = 0; p < n_planes; p++) { c->pend_g_w[p] = planes[p].width; c->pend_g_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_gmsd_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
@@ -2170,63 +2155,44 @@ int vqa_gmsd_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem
 
 int vqa_gmsd_wait(vqa_ctx *c, vqa_gmsd_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_g || n_entries != c->pend_g) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->gmsd_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_g_planes;
-        gmsd_finalize(acc + (size_t)e * GMSD_WORDS, c->pend_g_h[p], c->pend_g_w[p], out + e);
-    }
-    c->pend_g = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_GMSD, out, n_entries, GMSD_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int p, vqa_gmsd_metrics *o) {
+                          gmsd_finalize(acc, s.h[p], s.w[p], o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// CAMBI: one stream, every plane by itself.  A batch of its own (pend_b), ordered by the stream like a GMSD batch; host frames
+// CAMBI: one stream, every plane by itself.  A batch of its own, ordered by the stream like a GMSD batch; host frames
 // are staged in qstage_dist, the buffer of the stream it measures in a one-pass run.
 static int cambi_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
                              int n_planes, bool &touched)
 {
     if (bad_batch_args(c, frames, frames, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_b) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_CAMBI];
+    dbuf &cambi_scratch = s.work[0];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, CAMBI_MIN_DIM); });
+    int rc = check_batch(s, n, fs, fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, CAMBI_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && fs < B.span) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &c->qstage_dist}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if (mem_kind == VQA_MEM_HOST && (rc = stage(c, c->qstage_dist, frames, (size_t)(n - 1) * fs + B.span))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * CAMBI_WORDS * nent;
     const size_t per_frame = largest_group_bytes(planes, n_planes, [](int cnt, int h, int w) { return cambi_scratch_bytes(cnt, h, w); });
-    if ((rc = ensure(c, c->cambi_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->cambi_scratch, per_frame * (size_t)slice_frames(c, n)))) return rc;
-    if ((rc = ensure_pinned(c, c->cambi_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->cambi_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure(c, cambi_scratch, per_frame * (size_t)slice_frames(c, n)))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    // (launch_cambi's marks: one prof_scope per kernel id at a time, open between its begin and its end)
-    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
-    const cambi_mark mark = [](void *p, int id, int begin) {
-        marks *m = (marks *)p;
-        if (begin) m->open.emplace(m->c, id);
-        else m->open.reset();
-    };
+    marks mk(c);
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->cambi_acc.p + (size_t)a0 * n_planes * CAMBI_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * CAMBI_WORDS;
         const uint8_t *sfr = frames + (int64_t)a0 * fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
-            launch_cambi(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, c->cambi_scratch.p, acc, mark, &mk);
+            launch_cambi(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, cambi_scratch.p, acc, marks::mark, &mk);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->cambi_host.p, c->cambi_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_b = (int)nent;
-    c->pend_b_planes = n_planes;
-    for (int p = 0; p < n_planes; p++) { c->pend_b_w[p] = planes[p].width; c->pend_b_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_cambi_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes, int n_planes)
@@ -2238,29 +2204,22 @@ int vqa_cambi_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int
 
 int vqa_cambi_wait(vqa_ctx *c, vqa_cambi_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_b || n_entries != c->pend_b) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->cambi_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_b_planes;
-        cambi_finalize(acc + (size_t)e * CAMBI_WORDS, c->pend_b_h[p], c->pend_b_w[p], out + e);
-    }
-    c->pend_b = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_CAMBI, out, n_entries, CAMBI_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int p, vqa_cambi_metrics *o) {
+                          cambi_finalize(acc, s.h[p], s.w[p], o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
 // XPSNR: both streams and the reference frame before each pair; the luma plane steers every plane's weights.  A batch of its
-// own (pend_x), ordered by the stream like a GMSD batch, whose host staging (qstage_*) it shares; prev0 is staged by itself.
+// own, ordered by the stream like a GMSD batch, whose host staging (qstage_*) it shares; prev0 is staged by itself.
 static int xpsnr_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, const uint8_t *prev0, int mem_kind, int n,
                              int64_t ref_fs, int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_x) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_XPSNR];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
         if (int lim = side_and_area_limits(d, XPSNR_MIN_DIM)) return lim;
         // sse of the plane: 2^26 squares below 2^32 stay below 2^64 (vqa.h)
         if (B.depth > 8 && (int64_t)d.width * d.height > (1ll << 26)) return VQA_ERR_UNSUPPORTED;
@@ -2271,21 +2230,17 @@ static int xpsnr_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist
         return VQA_OK;
     });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs, {&prev0, 0, &c->xpsnr_prev}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
-    if (mem_kind == VQA_MEM_HOST && prev0 && (rc = stage(c, c->xpsnr_prev, prev0, (size_t)B.span))) return rc;
     const xpsnr_geom g = xpsnr_geometry(planes[0].width, planes[0].height);
     const size_t fw = xpsnr_frame_words(g, n_planes);
     const size_t acc_bytes = sizeof(unsigned long long) * fw * (size_t)n;
-    if ((rc = ensure(c, c->xpsnr_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->xpsnr_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->xpsnr_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *words = (unsigned long long *)c->xpsnr_acc.p + (size_t)a0 * fw;
+        unsigned long long *words = (unsigned long long *)s.dev.p + (size_t)a0 * fw;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         const uint8_t *sprev = a0 > 0 ? ref + (int64_t)(a0 - 1) * ref_fs : prev0;
         {
@@ -2297,13 +2252,7 @@ static int xpsnr_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist
             launch_xpsnr_sse(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, g, depth, fw, words);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->xpsnr_host.p, c->xpsnr_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_x = n * n_planes;
-    c->pend_x_planes = n_planes;
-    c->pend_x_depth = depth;
-    for (int p = 0; p < n_planes; p++) { c->pend_x_w[p] = planes[p].width; c->pend_x_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, n * n_planes, planes, n_planes, depth);
 }
 
 int vqa_xpsnr_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, const uint8_t *prev0, int mem_kind, int n,
@@ -2316,56 +2265,50 @@ int vqa_xpsnr_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, const 
 
 int vqa_xpsnr_wait(vqa_ctx *c, vqa_xpsnr_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_x || n_entries != c->pend_x) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    const int npl = c->pend_x_planes, n = n_entries / npl;
-    const xpsnr_geom g = xpsnr_geometry(c->pend_x_w[0], c->pend_x_h[0]);
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_XPSNR, out, n_entries, s)) return rc;
+    const int npl = s->planes, n = n_entries / npl;
+    const xpsnr_geom g = xpsnr_geometry(s->w[0], s->h[0]);
     const size_t fw = xpsnr_frame_words(g, npl), bw = (size_t)g.nbx * g.nby * (3 + npl);
     if (blocks && n_block_words != (int64_t)(bw * (size_t)n)) return VQA_ERR_INVALID;   // (the batch stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->xpsnr_host.p;
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *acc = (const unsigned long long *)s->host.p;
     for (int f = 0; f < n; f++)
-        xpsnr_finalize(acc + (size_t)f * fw, g, c->pend_x_depth, npl, c->pend_x_w, c->pend_x_h, out + (size_t)f * npl,
+        xpsnr_finalize(acc + (size_t)f * fw, g, s->depth, npl, s->w, s->h, out + (size_t)f * npl,
                        blocks ? blocks + (size_t)f * bw : nullptr);
-    c->pend_x = 0;
+    s->entries = 0;
     return VQA_OK;
 }
 
 // ---------------------------------------------------------------------------
-// HaarPSI: both streams, every plane by itself.  A batch of its own (pend_w), ordered by the stream like a GMSD batch, whose
+// HaarPSI: both streams, every plane by itself.  A batch of its own, ordered by the stream like a GMSD batch, whose
 // host staging (qstage_*) it shares.
 static int haarpsi_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                                int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_w) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_HAARPSI];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, HAARPSI_MIN_DIM); });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, HAARPSI_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * HAARPSI_WORDS * nent;
-    if ((rc = ensure(c, c->haarpsi_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->haarpsi_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->haarpsi_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->haarpsi_acc.p + (size_t)a0 * n_planes * HAARPSI_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * HAARPSI_WORDS;
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs, *sdist = dist + (int64_t)a0 * dist_fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             prof_scope ps_(c, VQA_K_HAARPSI);
             launch_haarpsi(st, sref, sdist, m, ref_fs, dist_fs, planes, idx, cnt, n_planes, depth, acc);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->haarpsi_host.p, c->haarpsi_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_w = (int)nent;
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_haarpsi_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
@@ -2378,54 +2321,43 @@ int vqa_haarpsi_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int 
 
 int vqa_haarpsi_wait(vqa_ctx *c, vqa_haarpsi_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_w || n_entries != c->pend_w) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->haarpsi_host.p;
-    for (int e = 0; e < n_entries; e++) haarpsi_finalize(acc + (size_t)e * HAARPSI_WORDS, out + e);
-    c->pend_w = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_HAARPSI, out, n_entries, HAARPSI_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &, int, vqa_haarpsi_metrics *o) { haarpsi_finalize(acc, o); });
 }
 
 // ---------------------------------------------------------------------------
-// VCA texture features: the reference stream alone and the frame before each frame, every plane by itself.  A batch of its own
-// (pend_t), ordered by the stream like an SI/TI batch, whose host staging (siti_stage, siti_prev) it shares.
+// VCA texture features: the reference stream alone and the frame before each frame, every plane by itself.  A batch of its
+// own, ordered by the stream like an SI/TI batch, whose host staging (siti_stage, siti_prev) it shares.
 static int vca_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
                            const vqa_plane_desc *planes, int n_planes, bool &touched)
 {
     if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_t) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_VCA];
+    dbuf &vca_tabs = s.work[0];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+    int rc = check_batch(s, n, ref_fs, ref_fs, planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
         if (int lim = side_and_area_limits(d, VCA_MIN_DIM)) return lim;
         if (B.depth > 8 && (int64_t)d.width * d.height > (1ll << 26)) return VQA_ERR_UNSUPPORTED;
         if (d.pixel_step != B.bps) return VQA_ERR_UNSUPPORTED;   // planar layouts only
         return VQA_OK;
     });
     if (rc) return rc;
-    if (n > 1 && ref_fs < B.span) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&ref, ref_fs, &c->siti_stage}, {}, {&prev0, 0, &c->siti_prev}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if (mem_kind == VQA_MEM_HOST) {
-        if ((rc = stage(c, c->siti_stage, ref, (size_t)(n - 1) * ref_fs + B.span))) return rc;
-        if (prev0 && (rc = stage(c, c->siti_prev, prev0, (size_t)B.span))) return rc;
-    }
     int pw[4], ph[4];
     for (int p = 0; p < n_planes; p++) { pw[p] = planes[p].width; ph[p] = planes[p].height; }
     const vca_geom g = vca_geometry(pw, ph, n_planes);
     const size_t acc_words = (size_t)n * n_planes * VCA_WORDS, map_words = g.slot_words * (size_t)n;
     // device: the words, prev0's slot, the frames' slots; host: the same without prev0's slot
-    if ((rc = ensure(c, c->vca_acc, sizeof(unsigned long long) * (acc_words + g.slot_words + map_words)))) return rc;
-    if ((rc = ensure_pinned(c, c->vca_host, sizeof(unsigned long long) * (acc_words + map_words)))) return rc;
-    const bool fresh_tabs = !c->vca_tabs.p;
-    if ((rc = ensure(c, c->vca_tabs, sizeof(float) * VCA_TABLE_FLOATS))) return rc;
+    if ((rc = ensure(c, s.dev, sizeof(unsigned long long) * (acc_words + g.slot_words + map_words)))) return rc;
+    if ((rc = ensure_pinned(c, s.host, sizeof(unsigned long long) * (acc_words + map_words)))) return rc;
+    const bool fresh_tabs = !vca_tabs.p;
+    if ((rc = ensure(c, vca_tabs, sizeof(float) * VCA_TABLE_FLOATS))) return rc;
     if (fresh_tabs) {
         static const std::vector<float> tabs = [] { std::vector<float> t(VCA_TABLE_FLOATS); vca_tables(t.data()); return t; }();
-        HIPCHK(c, hipMemcpyAsync(c->vca_tabs.p, tabs.data(), sizeof(float) * VCA_TABLE_FLOATS, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(vca_tabs.p, tabs.data(), sizeof(float) * VCA_TABLE_FLOATS, hipMemcpyHostToDevice, st));
     }
-    unsigned long long *acc = (unsigned long long *)c->vca_acc.p, *map = acc + acc_words + g.slot_words;   // frame 0's slot
+    unsigned long long *acc = (unsigned long long *)s.dev.p, *map = acc + acc_words + g.slot_words;   // frame 0's slot
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
         const uint8_t *sref = ref + (int64_t)a0 * ref_fs;
@@ -2434,19 +2366,17 @@ static int vca_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0,
             prof_scope ps_(c, VQA_K_VCA_BLOCKS);
             // (a later slice's predecessor is the slice before's last frame, whose slot is filled already)
             launch_vca_blocks(st, sref, a0 > 0 ? nullptr : prev0, m, ref_fs, planes, idx, cnt, g, depth,
-                              (const float *)c->vca_tabs.p, smap);
+                              (const float *)vca_tabs.p, smap);
         });
         prof_scope ps_(c, VQA_K_VCA_SUM);
         launch_vca_sum(st, m, n_planes, g, a0 > 0 || prev0 != nullptr, smap, acc + (size_t)a0 * n_planes * VCA_WORDS);
     });
+    // (the tail inline: the block map follows the words in the pinned copy, without prev0's slot)
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->vca_host.p, acc, sizeof(unsigned long long) * acc_words, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync((unsigned long long *)c->vca_host.p + acc_words, map, sizeof(unsigned long long) * map_words,
+    HIPCHK(c, hipMemcpyAsync(s.host.p, acc, sizeof(unsigned long long) * acc_words, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync((unsigned long long *)s.host.p + acc_words, map, sizeof(unsigned long long) * map_words,
                              hipMemcpyDeviceToHost, st));
-    c->pend_t = n * n_planes;
-    c->pend_t_planes = n_planes;
-    c->pend_t_depth = depth;
-    for (int p = 0; p < n_planes; p++) { c->pend_t_w[p] = pw[p]; c->pend_t_h[p] = ph[p]; }
+    record_batch(s, n * n_planes, planes, n_planes, depth);
     return VQA_OK;
 }
 
@@ -2460,62 +2390,53 @@ int vqa_vca_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem
 
 int vqa_vca_wait(vqa_ctx *c, vqa_vca_metrics *out, int n_entries, uint64_t *blocks, int64_t n_block_words)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_t || n_entries != c->pend_t) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    const int npl = c->pend_t_planes, n = n_entries / npl;
-    const vca_geom g = vca_geometry(c->pend_t_w, c->pend_t_h, npl);
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_VCA, out, n_entries, s)) return rc;
+    const int npl = s->planes, n = n_entries / npl;
+    const vca_geom g = vca_geometry(s->w, s->h, npl);
     const size_t nb = g.slot_words / 3;
     if (blocks && n_block_words != (int64_t)(2 * nb * (size_t)n)) return VQA_ERR_INVALID;   // (the batch stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->vca_host.p, *map = acc + (size_t)n_entries * VCA_WORDS;
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *acc = (const unsigned long long *)s->host.p, *map = acc + (size_t)n_entries * VCA_WORDS;
     for (int e = 0; e < n_entries; e++) {
         const int p = e % npl;
-        vca_finalize(acc + (size_t)e * VCA_WORDS, g.nbx[p], g.nby[p], c->pend_t_depth, out + e);
+        vca_finalize(acc + (size_t)e * VCA_WORDS, g.nbx[p], g.nby[p], s->depth, out + e);
     }
     if (blocks)
         for (size_t i = 0; i < nb * (size_t)n; i++) { blocks[2 * i] = map[3 * i]; blocks[2 * i + 1] = map[3 * i + 1]; }
-    c->pend_t = 0;
+    s->entries = 0;
     return VQA_OK;
 }
 
 // ---------------------------------------------------------------------------
-// Blockiness, blur and noise: one stream, every plane by itself.  A batch of its own (pend_r), ordered by the stream like a
+// Blockiness, blur and noise: one stream, every plane by itself.  A batch of its own, ordered by the stream like a
 // CAMBI batch, whose host staging (qstage_dist, the buffer of the stream it measures in a one-pass run) it shares.
 static int artifacts_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
                                  int n_planes, bool &touched)
 {
     if (bad_batch_args(c, frames, frames, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_r) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_ARTIFACTS];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, ARTIFACTS_MIN_DIM); });
+    int rc = check_batch(s, n, fs, fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, ARTIFACTS_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && fs < B.span) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &c->qstage_dist}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if (mem_kind == VQA_MEM_HOST && (rc = stage(c, c->qstage_dist, frames, (size_t)(n - 1) * fs + B.span))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * ARTIFACTS_WORDS * nent;
-    if ((rc = ensure(c, c->artifacts_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->artifacts_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->artifacts_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->artifacts_acc.p + (size_t)a0 * n_planes * ARTIFACTS_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * ARTIFACTS_WORDS;
         const uint8_t *sfr = frames + (int64_t)a0 * fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
             prof_scope ps_(c, VQA_K_ARTIFACTS);
             launch_artifacts(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, acc);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->artifacts_host.p, c->artifacts_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_r = (int)nent;
-    c->pend_r_planes = n_planes;
-    c->pend_r_depth = depth;
-    for (int p = 0; p < n_planes; p++) { c->pend_r_w[p] = planes[p].width; c->pend_r_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_artifacts_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
@@ -2528,63 +2449,44 @@ int vqa_artifacts_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n,
 
 int vqa_artifacts_wait(vqa_ctx *c, vqa_artifacts_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_r || n_entries != c->pend_r) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->artifacts_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_r_planes;
-        artifacts_finalize(acc + (size_t)e * ARTIFACTS_WORDS, c->pend_r_h[p], c->pend_r_w[p], c->pend_r_depth, out + e);
-    }
-    c->pend_r = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_ARTIFACTS, out, n_entries, ARTIFACTS_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int p, vqa_artifacts_metrics *o) {
+                          artifacts_finalize(acc, s.h[p], s.w[p], s.depth, o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// BRISQUE: one stream, every plane by itself.  A batch of its own (pend_n), ordered by the stream like a CAMBI batch, whose
+// BRISQUE: one stream, every plane by itself.  A batch of its own, ordered by the stream like a CAMBI batch, whose
 // host staging (qstage_dist, the buffer of the stream it measures in a one-pass run) it shares.
 static int brisque_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
                                int n_planes, bool &touched)
 {
     if (bad_batch_args(c, frames, frames, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
-    if (c->pend_n) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_BRISQUE];
+    dbuf &brisque_scratch = s.work[0];
     plane_batch B;
-    int rc = check_planes(planes, n_planes, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, BRISQUE_MIN_DIM); });
+    int rc = check_batch(s, n, fs, fs, planes, n_planes, B,
+                         [](const vqa_plane_desc &d) { return side_and_area_limits(d, BRISQUE_MIN_DIM); });
     if (rc) return rc;
-    if (n > 1 && fs < B.span) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &c->qstage_dist}))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if (mem_kind == VQA_MEM_HOST && (rc = stage(c, c->qstage_dist, frames, (size_t)(n - 1) * fs + B.span))) return rc;
     const size_t nent = (size_t)n * n_planes;
     const size_t acc_bytes = sizeof(unsigned long long) * BRISQUE_WORDS * nent;
     const size_t per_frame = largest_group_bytes(planes, n_planes, [](int cnt, int h, int w) { return brisque_scratch_bytes(cnt, h, w); });
-    if ((rc = ensure(c, c->brisque_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->brisque_scratch, per_frame * (size_t)slice_frames(c, n)))) return rc;
-    if ((rc = ensure_pinned(c, c->brisque_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->brisque_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure(c, brisque_scratch, per_frame * (size_t)slice_frames(c, n)))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    // (launch_brisque's marks: one prof_scope per kernel id at a time, open between its begin and its end)
-    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
-    const brisque_mark mark = [](void *p, int id, int begin) {
-        marks *m = (marks *)p;
-        if (begin) m->open.emplace(m->c, id);
-        else m->open.reset();
-    };
+    marks mk(c);
     for_each_slice(c, n, [&](int a0, int m) {
-        unsigned long long *acc = (unsigned long long *)c->brisque_acc.p + (size_t)a0 * n_planes * BRISQUE_WORDS;
+        unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)a0 * n_planes * BRISQUE_WORDS;
         const uint8_t *sfr = frames + (int64_t)a0 * fs;
         for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
-            launch_brisque(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, c->brisque_scratch.p, acc, mark, &mk);
+            launch_brisque(st, sfr, m, fs, planes, idx, cnt, n_planes, depth, brisque_scratch.p, acc, marks::mark, &mk);
         });
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->brisque_host.p, c->brisque_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_n = (int)nent;
-    c->pend_n_planes = n_planes;
-    for (int p = 0; p < n_planes; p++) { c->pend_n_w[p] = planes[p].width; c->pend_n_h[p] = planes[p].height; }
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, (int)nent, planes, n_planes, depth);
 }
 
 int vqa_brisque_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
@@ -2597,21 +2499,14 @@ int vqa_brisque_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, i
 
 int vqa_brisque_wait(vqa_ctx *c, vqa_brisque_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_n || n_entries != c->pend_n) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->brisque_host.p;
-    for (int e = 0; e < n_entries; e++) {
-        const int p = e % c->pend_n_planes;
-        brisque_finalize(acc + (size_t)e * BRISQUE_WORDS, c->pend_n_h[p], c->pend_n_w[p], out + e);
-    }
-    c->pend_n = 0;
-    return VQA_OK;
+    return wait_batch(c, KIND_BRISQUE, out, n_entries, BRISQUE_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int p, vqa_brisque_metrics *o) {
+                          brisque_finalize(acc, s.h[p], s.w[p], o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// MDSI: both streams, the planes of a pixel together, one entry per frame.  A batch of its own (pend_d), ordered by the stream
+// MDSI: both streams, the planes of a pixel together, one entry per frame.  A batch of its own, ordered by the stream
 // like a CIEDE2000 batch, whose host staging (qstage_*) and geometry rules it shares.
 static int mdsi_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                             int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int model, bool &touched)
@@ -2620,53 +2515,27 @@ static int mdsi_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist,
     if (n_planes != 1 && n_planes != 3) return VQA_ERR_INVALID;
     if (model != VQA_MDSI_YUV709 && model != VQA_MDSI_BGR && model != VQA_MDSI_GRAY) return VQA_ERR_INVALID;
     if ((n_planes == 1) != (model == VQA_MDSI_GRAY)) return VQA_ERR_INVALID;
-    if (c->pend_d) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_MDSI];
+    dbuf &mdsi_map = s.work[0];
     plane_batch B;
-    // the size limits are plane 0's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
-        return &d == planes ? side_and_area_limits(d, MDSI_MIN_DIM) : (int)VQA_OK;
-    });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, plane0_limits(planes, MDSI_MIN_DIM),
+                         n_planes != 3 ? JOINT_NONE : model == VQA_MDSI_BGR ? JOINT_BGR : JOINT_YUV);
     if (rc) return rc;
-    const vqa_plane_desc &y = planes[0];
-    if (n_planes == 3) {
-        const vqa_plane_desc &u = planes[1], &v = planes[2];
-        if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
-            return VQA_ERR_INVALID;
-        if (model == VQA_MDSI_BGR) {
-            if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
-                return VQA_ERR_INVALID;
-        } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
-            return VQA_ERR_INVALID;
-        }
-    }
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    const vqa_plane_desc &y = planes[0];
     const size_t acc_bytes = sizeof(unsigned long long) * MDSI_WORDS * (size_t)n;
-    if ((rc = ensure(c, c->mdsi_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->mdsi_map, mdsi_scratch_bytes(y.height, y.width) * (size_t)slice_frames(c, n)))) return rc;
-    if ((rc = ensure_pinned(c, c->mdsi_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->mdsi_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure(c, mdsi_map, mdsi_scratch_bytes(y.height, y.width) * (size_t)slice_frames(c, n)))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    // (launch_mdsi's marks: one prof_scope per kernel id at a time, open between its begin and its end)
-    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
-    const brisque_mark mark = [](void *p, int id, int begin) {
-        marks *m = (marks *)p;
-        if (begin) m->open.emplace(m->c, id);
-        else m->open.reset();
-    };
+    marks mk(c);
     for_each_slice(c, n, [&](int a0, int m) {
         launch_mdsi(st, ref + (int64_t)a0 * ref_fs, dist + (int64_t)a0 * dist_fs, m, ref_fs, dist_fs, planes, n_planes, depth, model,
-                    c->mdsi_map.p, (unsigned long long *)c->mdsi_acc.p + (size_t)a0 * MDSI_WORDS, mark, &mk);
+                    mdsi_map.p, (unsigned long long *)s.dev.p + (size_t)a0 * MDSI_WORDS, marks::mark, &mk);
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->mdsi_host.p, c->mdsi_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_d = n;
-    c->pend_d_w = y.width;
-    c->pend_d_h = y.height;
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, n, planes, n_planes, depth);
 }
 
 int vqa_mdsi_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
@@ -2681,18 +2550,15 @@ int vqa_mdsi_factor(int height, int width) { return height > 0 && width > 0 ? md
 
 int vqa_mdsi_wait(vqa_ctx *c, vqa_mdsi_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_d || n_entries != c->pend_d) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->mdsi_host.p;
-    for (int e = 0; e < n_entries; e++) mdsi_finalize(acc + (size_t)e * MDSI_WORDS, c->pend_d_h, c->pend_d_w, out + e);
-    c->pend_d = 0;
-    return VQA_OK;
+    // (one entry per frame: plane 0, for the host's part)
+    return wait_batch(c, KIND_MDSI, out, n_entries, MDSI_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int, vqa_mdsi_metrics *o) {
+                          mdsi_finalize(acc, s.h[0], s.w[0], o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// dE_ITP: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own (pend_i), ordered by the
+// dE_ITP: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own, ordered by the
 // stream like a CIEDE2000 batch, whose host staging (qstage_*) and geometry rules it shares.
 static int itp_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
                            int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int model, int transfer, int full_range,
@@ -2701,43 +2567,24 @@ static int itp_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, 
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (n_planes != 3 || (model != VQA_ITP_YUV2020 && model != VQA_ITP_BGR)) return VQA_ERR_INVALID;
     if ((transfer != VQA_ITP_PQ && transfer != VQA_ITP_HLG) || (full_range != 0 && full_range != 1)) return VQA_ERR_INVALID;
-    if (c->pend_i) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_ITP];
     plane_batch B;
-    // the size limits are the luma grid's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
-        return &d == planes ? side_and_area_limits(d, ITP_MIN_DIM) : (int)VQA_OK;
-    });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, plane0_limits(planes, ITP_MIN_DIM),
+                         model == VQA_ITP_BGR ? JOINT_BGR : JOINT_YUV);
     if (rc) return rc;
-    const vqa_plane_desc &y = planes[0], &u = planes[1], &v = planes[2];
-    if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
-        return VQA_ERR_INVALID;
-    if (model == VQA_ITP_BGR) {
-        if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
-            return VQA_ERR_INVALID;
-    } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
-        return VQA_ERR_INVALID;
-    }
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     const size_t acc_bytes = sizeof(unsigned long long) * ITP_WORDS * (size_t)n;
-    if ((rc = ensure(c, c->itp_acc, acc_bytes))) return rc;
-    if ((rc = ensure_pinned(c, c->itp_host, acc_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->itp_acc.p, 0, acc_bytes, st));
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     for_each_slice(c, n, [&](int a0, int m) {
         prof_scope ps_(c, VQA_K_ITP);
         launch_itp(st, ref + (int64_t)a0 * ref_fs, dist + (int64_t)a0 * dist_fs, m, ref_fs, dist_fs, planes, depth, model, transfer,
-                   full_range, (unsigned long long *)c->itp_acc.p + (size_t)a0 * ITP_WORDS);
+                   full_range, (unsigned long long *)s.dev.p + (size_t)a0 * ITP_WORDS);
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->itp_host.p, c->itp_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_i = n;
-    c->pend_i_w = y.width;
-    c->pend_i_h = y.height;
-    return VQA_OK;
+    return finish_batch(c, s, acc_bytes, n, planes, n_planes, depth);
 }
 
 int vqa_itp_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
@@ -2750,18 +2597,15 @@ int vqa_itp_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_
 
 int vqa_itp_wait(vqa_ctx *c, vqa_itp_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_i || n_entries != c->pend_i) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->itp_host.p;
-    for (int e = 0; e < n_entries; e++) itp_finalize(acc + (size_t)e * ITP_WORDS, c->pend_i_h, c->pend_i_w, out + e);
-    c->pend_i = 0;
-    return VQA_OK;
+    // (one entry per frame: the luma grid, for the host's mean)
+    return wait_batch(c, KIND_ITP, out, n_entries, ITP_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int, vqa_itp_metrics *o) {
+                          itp_finalize(acc, s.h[0], s.w[0], o);
+                      });
 }
 
 // ---------------------------------------------------------------------------
-// PU21-PSNR / PU21-SSIM: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own (pend_u),
+// PU21-PSNR / PU21-SSIM: both streams, the three planes of a pixel together, one entry per frame.  A batch of its own,
 // ordered by the stream like a dE_ITP batch, whose checks, host staging (qstage_*) and geometry rules it shares.
 
 // the frames of one sub-slice: the two q_Y maps of that many frames stay within PU21_MAP_BUDGET (lab build: or what the seam says)
@@ -2782,67 +2626,52 @@ static int pu21_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist,
     if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
     if (n_planes != 3 || (model != VQA_ITP_YUV2020 && model != VQA_ITP_BGR)) return VQA_ERR_INVALID;
     if ((transfer != VQA_ITP_PQ && transfer != VQA_ITP_HLG) || (full_range != 0 && full_range != 1)) return VQA_ERR_INVALID;
-    if (c->pend_u) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_PU21];
+    dbuf &pu21_map = s.work[0];
     plane_batch B;
-    // the size limits are the luma grid's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
-        return &d == planes ? side_and_area_limits(d, PU21_MIN_DIM) : (int)VQA_OK;
-    });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, plane0_limits(planes, PU21_MIN_DIM),
+                         model == VQA_ITP_BGR ? JOINT_BGR : JOINT_YUV);
     if (rc) return rc;
-    const vqa_plane_desc &y = planes[0], &u = planes[1], &v = planes[2];
-    if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
-        return VQA_ERR_INVALID;
-    if (model == VQA_ITP_BGR) {
-        if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
-            return VQA_ERR_INVALID;
-    } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
-        return VQA_ERR_INVALID;
-    }
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    const vqa_plane_desc &y = planes[0];
     const size_t acc_bytes = sizeof(unsigned long long) * PU21_WORDS * (size_t)n;
     const size_t map_bytes = pu21_map_bytes(y.height, y.width);
     const int sub = pu21_subslice(c, y.height, y.width);
     const int sub_frames = sub < slice_frames(c, n) ? sub : slice_frames(c, n);
-    if ((rc = ensure(c, c->pu21_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->pu21_map, map_bytes * (size_t)sub_frames))) return rc;
-    if ((rc = ensure_pinned(c, c->pu21_host, acc_bytes))) return rc;
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure(c, pu21_map, map_bytes * (size_t)sub_frames))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
 #ifdef VQA_TEST_SEAMS
+    dbuf &pu21_keep = s.work[1];
     c->last_u_n = 0;
-    if ((rc = ensure(c, c->pu21_keep, map_bytes * (size_t)n))) return rc;
+    if ((rc = ensure(c, pu21_keep, map_bytes * (size_t)n))) return rc;
 #endif
-    HIPCHK(c, hipMemsetAsync(c->pu21_acc.p, 0, acc_bytes, st));
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
     hipError_t copy_err = hipSuccess;
     for_each_slice(c, n, [&](int a0, int m) {
         for (int b0 = 0; b0 < m; b0 += sub_frames) {
             const int k = m - b0 < sub_frames ? m - b0 : sub_frames, at = a0 + b0;
-            unsigned long long *acc = (unsigned long long *)c->pu21_acc.p + (size_t)at * PU21_WORDS;
+            unsigned long long *acc = (unsigned long long *)s.dev.p + (size_t)at * PU21_WORDS;
             {
                 prof_scope ps_(c, VQA_K_PU21_ENCODE);
                 launch_pu21_encode(st, ref + (int64_t)at * ref_fs, dist + (int64_t)at * dist_fs, k, ref_fs, dist_fs, planes, depth,
-                                   model, transfer, full_range, (uint32_t *)c->pu21_map.p, acc);
+                                   model, transfer, full_range, (uint32_t *)pu21_map.p, acc);
             }
             {
                 prof_scope ps_(c, VQA_K_PU21_SSIM);
-                launch_pu21_ssim(st, (const uint32_t *)c->pu21_map.p, k, y.height, y.width, acc);
+                launch_pu21_ssim(st, (const uint32_t *)pu21_map.p, k, y.height, y.width, acc);
             }
 #ifdef VQA_TEST_SEAMS
-            const hipError_t e = hipMemcpyAsync((uint8_t *)c->pu21_keep.p + map_bytes * (size_t)at, c->pu21_map.p,
+            const hipError_t e = hipMemcpyAsync((uint8_t *)pu21_keep.p + map_bytes * (size_t)at, pu21_map.p,
                                                 map_bytes * (size_t)k, hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) copy_err = e;
 #endif
         }
     });
     HIPCHK(c, copy_err);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->pu21_host.p, c->pu21_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_u = n;
-    c->pend_u_w = y.width;
-    c->pend_u_h = y.height;
+    if ((rc = finish_batch(c, s, acc_bytes, n, planes, n_planes, depth))) return rc;
 #ifdef VQA_TEST_SEAMS
     c->last_u_n = n; c->last_u_w = y.width; c->last_u_h = y.height;
 #endif
@@ -2859,14 +2688,11 @@ int vqa_pu21_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem
 
 int vqa_pu21_wait(vqa_ctx *c, vqa_pu21_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_u || n_entries != c->pend_u) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->pu21_host.p;
-    for (int e = 0; e < n_entries; e++) pu21_finalize(acc + (size_t)e * PU21_WORDS, c->pend_u_h, c->pend_u_w, out + e);
-    c->pend_u = 0;
-    return VQA_OK;
+    // (one entry per frame: the luma grid, for the host's divisions)
+    return wait_batch(c, KIND_PU21, out, n_entries, PU21_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int, vqa_pu21_metrics *o) {
+                          pu21_finalize(acc, s.h[0], s.w[0], o);
+                      });
 }
 
 double vqa_pu21_encode(double cd_m2) { return pu21_encode_host(cd_m2); }
@@ -2875,17 +2701,17 @@ double vqa_pu21_encode(double cd_m2) { return pu21_encode_host(cd_m2); }
 int vqa_pu21_lab_read_maps(vqa_ctx *c, uint32_t *dst, int64_t n_values)
 {
     if (!c || !dst) return VQA_ERR_INVALID;
-    if (c->pend_u || !c->last_u_n) return VQA_ERR_STATE;
+    if (c->slot[KIND_PU21].entries || !c->last_u_n) return VQA_ERR_STATE;
     if (n_values != (int64_t)c->last_u_n * 2 * c->last_u_h * c->last_u_w) return VQA_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->pu21_keep.p, sizeof(uint32_t) * (size_t)n_values, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->slot[KIND_PU21].work[1].p, sizeof(uint32_t) * (size_t)n_values, hipMemcpyDeviceToHost));
     return VQA_OK;
 }
 #endif
 
 // ---------------------------------------------------------------------------
-// FSIM / FSIMc: both streams, the planes of a pixel together, one entry per frame.  A batch of its own (pend_f), ordered by the
+// FSIM / FSIMc: both streams, the planes of a pixel together, one entry per frame.  A batch of its own, ordered by the
 // stream like an MDSI batch, whose checks, host staging (qstage_*) and geometry rules it shares.
 
 // the frames of one sub-slice: the intermediates of that many frames stay within FSIM_SCRATCH_BUDGET (lab build: or what the seam says)
@@ -2906,76 +2732,52 @@ static int fsim_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist,
     if (n_planes != 1 && n_planes != 3) return VQA_ERR_INVALID;
     if (model != VQA_FSIM_YUV709 && model != VQA_FSIM_BGR && model != VQA_FSIM_GRAY) return VQA_ERR_INVALID;
     if ((n_planes == 1) != (model == VQA_FSIM_GRAY)) return VQA_ERR_INVALID;
-    if (c->pend_f) return VQA_ERR_STATE;
+    batch_slot &s = c->slot[KIND_FSIM];
+    dbuf &fsim_scratch = s.work[0], &fsim_map = s.work[1];
     plane_batch B;
-    // the size limits are plane 0's: the chroma planes of a 16 x 16 4:2:0 frame are 8 x 8
-    int rc = check_planes(planes, n_planes, B, [&](const vqa_plane_desc &d) {
-        return &d == planes ? side_and_area_limits(d, FSIM_MIN_DIM) : (int)VQA_OK;
-    });
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, plane0_limits(planes, FSIM_MIN_DIM),
+                         n_planes != 3 ? JOINT_NONE : model == VQA_FSIM_BGR ? JOINT_BGR : JOINT_YUV);
     if (rc) return rc;
     const vqa_plane_desc &y = planes[0];
-    if (n_planes == 3) {
-        const vqa_plane_desc &u = planes[1], &v = planes[2];
-        if (u.width != v.width || u.height != v.height || u.row_stride != v.row_stride || u.pixel_step != v.pixel_step)
-            return VQA_ERR_INVALID;
-        if (model == VQA_FSIM_BGR) {
-            if (u.width != y.width || u.height != y.height || u.row_stride != y.row_stride || u.pixel_step != y.pixel_step)
-                return VQA_ERR_INVALID;
-        } else if ((u.width != y.width && u.width != (y.width + 1) / 2) || (u.height != y.height && u.height != (y.height + 1) / 2)) {
-            return VQA_ERR_INVALID;
-        }
-    }
-    if (n > 1 && (ref_fs < B.span || dist_fs < B.span)) return VQA_ERR_INVALID;
     int f, hd, wd;
     fsim_grid(y.height, y.width, &f, &hd, &wd);
-    if (hd > FSIM_MAX_GRID || wd > FSIM_MAX_GRID) return VQA_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
+    if (hd > FSIM_MAX_GRID || wd > FSIM_MAX_GRID) return VQA_ERR_UNSUPPORTED;   // (the last refusal, after every check the kinds share)
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     hipStream_t st = c->stream;
-    touched = true;
-    if ((rc = stage_pair(c, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
     fsim_tabs tabs;
     if ((rc = get_fsim_tabs(c, hd, wd, &tabs))) return rc;
     const size_t acc_bytes = sizeof(unsigned long long) * FSIM_WORDS * (size_t)n;
     const size_t map_bytes = 2 * sizeof(uint32_t) * (size_t)hd * (size_t)wd;   // the two p maps of a frame
     const int sub = fsim_subslice(c, y.height, y.width);
     const int sub_frames = sub < slice_frames(c, n) ? sub : slice_frames(c, n);
-    if ((rc = ensure(c, c->fsim_acc, acc_bytes))) return rc;
-    if ((rc = ensure(c, c->fsim_scratch, fsim_scratch_bytes(y.height, y.width) * (size_t)sub_frames))) return rc;
-    if ((rc = ensure(c, c->fsim_map, map_bytes * (size_t)sub_frames))) return rc;
-    if ((rc = ensure_pinned(c, c->fsim_host, acc_bytes))) return rc;
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure(c, fsim_scratch, fsim_scratch_bytes(y.height, y.width) * (size_t)sub_frames))) return rc;
+    if ((rc = ensure(c, fsim_map, map_bytes * (size_t)sub_frames))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes))) return rc;
 #ifdef VQA_TEST_SEAMS
+    dbuf &fsim_keep = s.work[2];
     c->last_f_n = 0;
-    if ((rc = ensure(c, c->fsim_keep, map_bytes * (size_t)n))) return rc;
+    if ((rc = ensure(c, fsim_keep, map_bytes * (size_t)n))) return rc;
 #endif
-    HIPCHK(c, hipMemsetAsync(c->fsim_acc.p, 0, acc_bytes, st));
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
     const int depth = B.depth;
-    // (launch_fsim's marks: one prof_scope per kernel id at a time, open between its begin and its end)
-    struct marks { vqa_ctx *c; std::optional<prof_scope> open; } mk = {c, std::nullopt};
-    const brisque_mark mark = [](void *p, int id, int begin) {
-        marks *m = (marks *)p;
-        if (begin) m->open.emplace(m->c, id);
-        else m->open.reset();
-    };
+    marks mk(c);
     hipError_t copy_err = hipSuccess;
     for_each_slice(c, n, [&](int a0, int m) {
         for (int b0 = 0; b0 < m; b0 += sub_frames) {
             const int k = m - b0 < sub_frames ? m - b0 : sub_frames, at = a0 + b0;
             launch_fsim(st, ref + (int64_t)at * ref_fs, dist + (int64_t)at * dist_fs, k, ref_fs, dist_fs, planes, n_planes, depth,
-                        model, tabs, c->fsim_scratch.p, (uint32_t *)c->fsim_map.p,
-                        (unsigned long long *)c->fsim_acc.p + (size_t)at * FSIM_WORDS, mark, &mk);
+                        model, tabs, fsim_scratch.p, (uint32_t *)fsim_map.p,
+                        (unsigned long long *)s.dev.p + (size_t)at * FSIM_WORDS, marks::mark, &mk);
 #ifdef VQA_TEST_SEAMS
-            const hipError_t e = hipMemcpyAsync((uint8_t *)c->fsim_keep.p + map_bytes * (size_t)at, c->fsim_map.p,
+            const hipError_t e = hipMemcpyAsync((uint8_t *)fsim_keep.p + map_bytes * (size_t)at, fsim_map.p,
                                                 map_bytes * (size_t)k, hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) copy_err = e;
 #endif
         }
     });
     HIPCHK(c, copy_err);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->fsim_host.p, c->fsim_acc.p, acc_bytes, hipMemcpyDeviceToHost, st));
-    c->pend_f = n;
-    c->pend_f_w = y.width;
-    c->pend_f_h = y.height;
+    if ((rc = finish_batch(c, s, acc_bytes, n, planes, n_planes, depth))) return rc;
 #ifdef VQA_TEST_SEAMS
     c->last_f_n = n; c->last_f_w = wd; c->last_f_h = hd;
 #endif
@@ -2992,14 +2794,11 @@ int vqa_fsim_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem
 
 int vqa_fsim_wait(vqa_ctx *c, vqa_fsim_metrics *out, int n_entries)
 {
-    if (!c || !out) return VQA_ERR_INVALID;
-    if (!c->pend_f || n_entries != c->pend_f) return VQA_ERR_STATE;   // (a pending batch of another kind stays pending)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    const unsigned long long *acc = (const unsigned long long *)c->fsim_host.p;
-    for (int e = 0; e < n_entries; e++) fsim_finalize(acc + (size_t)e * FSIM_WORDS, c->pend_f_h, c->pend_f_w, out + e);
-    c->pend_f = 0;
-    return VQA_OK;
+    // (one entry per frame: plane 0, for the host's part)
+    return wait_batch(c, KIND_FSIM, out, n_entries, FSIM_WORDS,
+                      [](const unsigned long long *acc, const batch_slot &s, int, vqa_fsim_metrics *o) {
+                          fsim_finalize(acc, s.h[0], s.w[0], o);
+                      });
 }
 
 static inline bool fsim_bad_grid(int hd, int wd, int orient)
@@ -3023,11 +2822,11 @@ int vqa_fsim_filter(int hd, int wd, int scale, int orient, double *dst)
 int vqa_fsim_lab_read_maps(vqa_ctx *c, uint32_t *dst, int64_t n_values)
 {
     if (!c || !dst) return VQA_ERR_INVALID;
-    if (c->pend_f || !c->last_f_n) return VQA_ERR_STATE;
+    if (c->slot[KIND_FSIM].entries || !c->last_f_n) return VQA_ERR_STATE;
     if (n_values != (int64_t)c->last_f_n * 2 * c->last_f_h * c->last_f_w) return VQA_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->fsim_keep.p, sizeof(uint32_t) * (size_t)n_values, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->slot[KIND_FSIM].work[2].p, sizeof(uint32_t) * (size_t)n_values, hipMemcpyDeviceToHost));
     return VQA_OK;
 }
 #endif
