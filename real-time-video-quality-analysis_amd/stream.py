@@ -25,6 +25,7 @@ upload of chunk k+1 therefore runs under the kernels of chunk k, the copiers gat
 float tails (tails.py) of a finished chunk run while the GPU works on the next.  Nothing here computes a metric: pointers
 in, records out.
 """
+import collections
 import os
 import threading
 from concurrent.futures import ThreadPoolExecutor
@@ -33,7 +34,9 @@ import numpy as np
 
 from . import _native as N
 from . import tails
-from .engine import DeviceBuffer, DeviceFrames, Engine
+from .engine import (ADM_DTYPE, ARTIFACTS_DTYPE, BRISQUE_DTYPE, CAMBI_DTYPE, CIEDE_DTYPE, FSIM_DTYPE, GMSD_DTYPE, HAARPSI_DTYPE,
+                     ITP_DTYPE, MDSI_DTYPE, MOTION_DTYPE, PSNR_HVS_DTYPE, PU21_DTYPE, SITI_DTYPE, VCA_DTYPE, VIF_DTYPE,
+                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_vca_planes, check_xpsnr_planes, vca_grid)
 from .pooling import shard_range
 
 # A chunk is at most batch_size frames and, when it travels over PCIe, at most this many bytes (all streams together).  With the
@@ -385,194 +388,6 @@ class Complexity:
         self.dct_mode, self.motion_mode, self.shard = dct_mode, motion_mode, shard
 
 
-class Quality:
-    """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
-
-    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
-                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
-                 haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
-                 itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False):
-        """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
-        vif     True: every chunk also goes through the VIF kernels (Engine.vif_submit) from the SAME upload, and the pass
-                returns the VIF records [n,p] (engine.VIF_DTYPE) as the last element; "only": VIF alone, no SSE / SSIM
-        adm     True: likewise through the ADM kernels (Engine.adm_submit); the pass then returns (.., VIF records or None,
-                ADM records [n,p] (engine.ADM_DTYPE)); "only": no SSE / SSIM (with vif=True or "only": VIF and ADM alone)
-        motion  True: every chunk's REFERENCE frames also go through the motion kernel (Engine.motion_submit) from the same
-                upload, prev0 being the last reference frame of the previous chunk (the reference feed's halo slot); the pass
-                then returns (.., VIF records or None, ADM records or None, motion records [n,p] (MOTION_PASS_DTYPE: sad, motion
-                and motion2, the last formed once over the whole clip)); "only": no SSE / SSIM
-        siti    True: every chunk's REFERENCE frames also go through the SI/TI kernel (Engine.siti_submit) from the same upload,
-                prev0 being the reference feed's halo slot as for motion; the pass's tuple - whatever vif, adm and motion made
-                it - then gains ONE further last element, the SI/TI records [n,p] (engine.SITI_DTYPE: si, ti and the four sums);
-                "only": no SSE / SSIM
-        psnr_hvs True: every chunk also goes through the PSNR-HVS kernel (Engine.psnr_hvs_submit) from the SAME upload; the
-                pass's tuple - whatever vif, adm, motion and siti made it - then gains ONE further last element, after SI/TI's:
-                the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE: s_hvs, s_hvsm, psnr_hvs, psnr_hvsm); "only": no SSE / SSIM
-        ciede   True: every chunk also goes through the CIEDE2000 kernel (Engine.ciede_submit, exactly three planes) from the
-                SAME upload; the pass's tuple then gains ONE further last element, after PSNR-HVS's: the CIEDE2000 records [n]
-                (engine.CIEDE_DTYPE: de_sum, de_mean, ciede2000 - one per frame, not per plane); "only": no SSE / SSIM.
-                ciede_weights: (kL, kC, kH), default the CIE standard (1, 1, 1); the colour model follows from the planes' pixel step
-                (Engine.ciede_model)
-        gmsd    True: every chunk also goes through the GMSD kernel (Engine.gmsd_submit) from the SAME upload; the pass's tuple
-                then gains ONE further last element, after CIEDE2000's: the GMSD records [n,p] (engine.GMSD_DTYPE: the three
-                integer words, count, gms_mean, gmsd); "only": no SSE / SSIM
-        cambi   True: every chunk of the DISTORTED (encoded) stream also goes through the CAMBI kernels (Engine.cambi_submit)
-                from the SAME upload; the pass's tuple then gains ONE further last element, after GMSD's: the CAMBI records
-                [n,p] (engine.CAMBI_DTYPE); "only": no SSE / SSIM, and the pass reads the `ref` stream alone, as a motion-only
-                pass does: give it the frames to measure
-        xpsnr   True: every chunk also goes through the XPSNR kernels (Engine.xpsnr_submit) from the SAME upload, prev0 being
-                the reference feed's halo slot as for motion and siti; the pass's tuple then gains ONE further last element,
-                after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE: sse, wsse, xpsnr, block, nbx, nby); "only": no SSE /
-                SSIM.  Planar layouts whose first plane is the luma
-        haarpsi True: every chunk also goes through the HaarPSI kernel (Engine.haarpsi_submit) from the SAME upload; the pass's
-                tuple then gains ONE further last element, after XPSNR's: the HaarPSI records [n,p] (engine.HAARPSI_DTYPE: the
-                three integer words, similarity, haarpsi); "only": no SSE / SSIM
-        vca     True: every chunk's REFERENCE frames also go through the VCA kernels (Engine.vca_submit) from the same upload,
-                prev0 being the reference feed's halo slot as for motion, siti and xpsnr; the pass's tuple then gains ONE further
-                last element, after HaarPSI's: the VCA records [n,p] (engine.VCA_DTYPE: e_sum, h_sum, l_sum, nbx, nby, e, h, l) -
-                with vca_blocks=True the pair (records, block maps: per plane dict(qh, s as uint64 [n, nby, nbx])); "only": no
-                SSE / SSIM, and the pass reads the `ref` stream alone.  Planar layouts, every plane at least 32 x 32
-        artifacts  True: every chunk of the DISTORTED (encoded) stream also goes through the blockiness / blur / noise kernel
-                (Engine.artifacts_submit) from the SAME upload; the pass's tuple then gains ONE further last element, after VCA's:
-                the records [n,p] (engine.ARTIFACTS_DTYPE); "only": no SSE / SSIM, and the pass reads the `ref` stream alone, as
-                a CAMBI-only pass does: give it the frames to measure
-        brisque True: every chunk of the DISTORTED (encoded) stream also goes through the BRISQUE kernels
-                (Engine.brisque_submit) from the SAME upload; the pass's tuple then gains ONE further last element, after the
-                artefact measures': the records [n,p] (engine.BRISQUE_DTYPE); "only": no SSE / SSIM, and the pass reads the
-                `ref` stream alone, as a CAMBI-only pass does: give it the frames to measure
-        mdsi    True: every chunk also goes through the MDSI kernels (Engine.mdsi_submit: one plane, or three taken together) from
-                the SAME upload; the pass's tuple then gains ONE further last element, after BRISQUE's: the MDSI records [n]
-                (engine.MDSI_DTYPE: the four integer words, count, factor, dev, mdsi - one per frame, not per plane); "only": no
-                SSE / SSIM.  The colour model follows from the planes (Engine.mdsi_model)
-        itp     True: every chunk also goes through the dE_ITP kernel (Engine.itp_submit, exactly three planes) from the SAME
-                upload; the pass's tuple then gains ONE further last element, after MDSI's: the dE_ITP records [n]
-                (engine.ITP_DTYPE: sum_q, max_q, de_sum, de_mean, de_max - one per frame, not per plane); "only": no SSE / SSIM.
-                itp_transfer: "pq" | "hlg"; itp_full_range: False (limited) | True; the colour model follows from the planes
-                (Engine.itp_model)
-        pu21    True: every chunk also goes through the PU21 kernels (Engine.pu21_submit, exactly three planes) from the SAME
-                upload; the pass's tuple then gains ONE further last element, after dE_ITP's: the PU21 records [n]
-                (engine.PU21_DTYPE: the five integer words, windows, mse_y, mse_rgb, pu_psnr, pu_psnr_rgb, pu_ssim - one per
-                frame, not per plane); "only": no SSE / SSIM.  pu21_transfer: "pq" | "hlg"; pu21_full_range: False (limited) |
-                True; the colour model follows from the planes (Engine.itp_model)
-        fsim    True: every chunk also goes through the FSIM kernels (Engine.fsim_submit: one plane, or three taken together) from
-                the SAME upload; the pass's tuple then gains ONE further last element, after PU21's: the FSIM records [n]
-                (engine.FSIM_DTYPE: the three integer words, count, factor, flags, fsim, fsimc - one per frame, not per plane);
-                "only": no SSE / SSIM.  The colour model follows from the planes (Engine.mdsi_model)"""
-        if scales and ssim_mode != N.SSIM_MS:
-            raise ValueError("per-scale means exist in the multi-scale mode only")
-        if not (isinstance(vif, bool) or (isinstance(vif, str) and vif == "only")):
-            raise ValueError("vif must be False, True or 'only'")
-        if vif == "only" and scales:
-            raise ValueError("a VIF-only pass has no SSIM scales")
-        if not (isinstance(adm, bool) or (isinstance(adm, str) and adm == "only")):
-            raise ValueError("adm must be False, True or 'only'")
-        if adm == "only" and scales:
-            raise ValueError("an ADM-only pass has no SSIM scales")
-        if not (isinstance(motion, bool) or (isinstance(motion, str) and motion == "only")):
-            raise ValueError("motion must be False, True or 'only'")
-        if motion == "only" and scales:
-            raise ValueError("a motion-only pass has no SSIM scales")
-        self.planes, self.ssim_mode, self.scales, self.vif, self.adm = planes, ssim_mode, bool(scales), vif, adm
-        if not (isinstance(siti, bool) or (isinstance(siti, str) and siti == "only")):
-            raise ValueError("siti must be False, True or 'only'")
-        if siti == "only" and scales:
-            raise ValueError("an SI/TI-only pass has no SSIM scales")
-        if not (isinstance(psnr_hvs, bool) or (isinstance(psnr_hvs, str) and psnr_hvs == "only")):
-            raise ValueError("psnr_hvs must be False, True or 'only'")
-        if psnr_hvs == "only" and scales:
-            raise ValueError("a PSNR-HVS-only pass has no SSIM scales")
-        if not (isinstance(ciede, bool) or (isinstance(ciede, str) and ciede == "only")):
-            raise ValueError("ciede must be False, True or 'only'")
-        if ciede == "only" and scales:
-            raise ValueError("a CIEDE2000-only pass has no SSIM scales")
-        if ciede and len(planes) != 3:
-            raise ValueError("ciede needs three planes")
-        ciede_weights = tuple(float(x) for x in ciede_weights)
-        if len(ciede_weights) != 3 or not all(np.isfinite(x) and x > 0 for x in ciede_weights):
-            raise ValueError("ciede_weights must be three positive finite numbers (kL, kC, kH)")
-        if not (isinstance(gmsd, bool) or (isinstance(gmsd, str) and gmsd == "only")):
-            raise ValueError("gmsd must be False, True or 'only'")
-        if gmsd == "only" and scales:
-            raise ValueError("a GMSD-only pass has no SSIM scales")
-        if not (isinstance(cambi, bool) or (isinstance(cambi, str) and cambi == "only")):
-            raise ValueError("cambi must be False, True or 'only'")
-        if cambi == "only" and scales:
-            raise ValueError("a CAMBI-only pass has no SSIM scales")
-        if not (isinstance(xpsnr, bool) or (isinstance(xpsnr, str) and xpsnr == "only")):
-            raise ValueError("xpsnr must be False, True or 'only'")
-        if xpsnr == "only" and scales:
-            raise ValueError("an XPSNR-only pass has no SSIM scales")
-        if xpsnr:
-            from .engine import check_xpsnr_planes
-            check_xpsnr_planes(planes)
-        if not (isinstance(haarpsi, bool) or (isinstance(haarpsi, str) and haarpsi == "only")):
-            raise ValueError("haarpsi must be False, True or 'only'")
-        if haarpsi == "only" and scales:
-            raise ValueError("a HaarPSI-only pass has no SSIM scales")
-        self.motion, self.siti, self.psnr_hvs, self.gmsd, self.cambi, self.xpsnr = motion, siti, psnr_hvs, gmsd, cambi, xpsnr
-        self.haarpsi = haarpsi
-        if not (isinstance(vca, bool) or (isinstance(vca, str) and vca == "only")):
-            raise ValueError("vca must be False, True or 'only'")
-        if vca == "only" and scales:
-            raise ValueError("a VCA-only pass has no SSIM scales")
-        if vca:
-            from .engine import check_vca_planes
-            check_vca_planes(planes)
-        self.vca, self.vca_blocks = vca, bool(vca_blocks)
-        if not (isinstance(artifacts, bool) or (isinstance(artifacts, str) and artifacts == "only")):
-            raise ValueError("artifacts must be False, True or 'only'")
-        if artifacts == "only" and scales:
-            raise ValueError("an artifacts-only pass has no SSIM scales")
-        self.artifacts = artifacts
-        if not (isinstance(brisque, bool) or (isinstance(brisque, str) and brisque == "only")):
-            raise ValueError("brisque must be False, True or 'only'")
-        if brisque == "only" and scales:
-            raise ValueError("a brisque-only pass has no SSIM scales")
-        self.brisque = brisque
-        if not (isinstance(mdsi, bool) or (isinstance(mdsi, str) and mdsi == "only")):
-            raise ValueError("mdsi must be False, True or 'only'")
-        if mdsi == "only" and scales:
-            raise ValueError("an MDSI-only pass has no SSIM scales")
-        if mdsi and len(planes) not in (1, 3):
-            raise ValueError("mdsi needs one plane or three")
-        self.mdsi = mdsi
-        if not (isinstance(itp, bool) or (isinstance(itp, str) and itp == "only")):
-            raise ValueError("itp must be False, True or 'only'")
-        if itp == "only" and scales:
-            raise ValueError("a dE_ITP-only pass has no SSIM scales")
-        if itp and len(planes) != 3:
-            raise ValueError("itp needs three planes")
-        if not (isinstance(itp_transfer, str) and itp_transfer in N.ITP_TRANSFERS):
-            raise ValueError("itp_transfer must be 'pq' or 'hlg'")
-        if not isinstance(itp_full_range, bool):
-            raise ValueError("itp_full_range must be True or False")
-        self.itp, self.itp_transfer, self.itp_full_range = itp, itp_transfer, itp_full_range
-        if not (isinstance(pu21, bool) or (isinstance(pu21, str) and pu21 == "only")):
-            raise ValueError("pu21 must be False, True or 'only'")
-        if pu21 == "only" and scales:
-            raise ValueError("a PU21-only pass has no SSIM scales")
-        if pu21 and len(planes) != 3:
-            raise ValueError("pu21 needs three planes")
-        if not (isinstance(pu21_transfer, str) and pu21_transfer in N.ITP_TRANSFERS):
-            raise ValueError("pu21_transfer must be 'pq' or 'hlg'")
-        if not isinstance(pu21_full_range, bool):
-            raise ValueError("pu21_full_range must be True or False")
-        self.pu21, self.pu21_transfer, self.pu21_full_range = pu21, pu21_transfer, pu21_full_range
-        if not (isinstance(fsim, bool) or (isinstance(fsim, str) and fsim == "only")):
-            raise ValueError("fsim must be False, True or 'only'")
-        if fsim == "only" and scales:
-            raise ValueError("an FSIM-only pass has no SSIM scales")
-        if fsim and len(planes) not in (1, 3):
-            raise ValueError("fsim needs one plane or three")
-        self.fsim = fsim
-        self.ciede, self.ciede_weights = ciede, ciede_weights
-        # the pass measures SSE / SSIM
-        self.ssim = (vif != "only" and adm != "only" and motion != "only" and siti != "only" and psnr_hvs != "only" and
-                     ciede != "only" and gmsd != "only" and cambi != "only" and xpsnr != "only" and haarpsi != "only" and
-                     vca != "only" and artifacts != "only" and brisque != "only" and mdsi != "only" and
-                     itp != "only" and pu21 != "only" and fsim != "only")
-
-
 # what a pass returns for VMAF's motion feature: the engine's records (engine.MOTION_DTYPE) plus motion2, which needs the next
 # frame and is therefore formed once, over the concatenated clip (tails.motion2)
 MOTION_PASS_DTYPE = np.dtype([("sad", np.float64), ("motion", np.float64), ("motion2", np.float64)])
@@ -584,6 +399,164 @@ def motion_records(rec):
     out["sad"], out["motion"] = rec["sad"], rec["motion"]
     out["motion2"] = tails.motion2(rec["motion"])
     return out
+
+
+# ---- the plane-batch kinds of the quality half: ONE table, read by Quality, run / _run_locked, records_by_kind and
+# video_processing._write_feature_log.  A new kind is added here (and to Quality's keyword list), nowhere else on the Python side.
+def _three_planes(kind, planes):
+    if len(planes) != 3:
+        raise ValueError("%s needs three planes" % kind)
+
+
+def _one_plane_or_three(kind, planes):
+    if len(planes) not in (1, 3):
+        raise ValueError("%s needs one plane or three" % kind)
+
+
+def _weights(name, value):
+    value = tuple(float(x) for x in value)
+    if len(value) != 3 or not all(np.isfinite(x) and x > 0 for x in value):
+        raise ValueError("%s must be three positive finite numbers (kL, kC, kH)" % name)
+    return value
+
+
+def _transfer(name, value):
+    if not (isinstance(value, str) and value in N.ITP_TRANSFERS):
+        raise ValueError("%s must be 'pq' or 'hlg'" % name)
+    return value
+
+
+def _full_range(name, value):
+    if not isinstance(value, bool):
+        raise ValueError("%s must be True or False" % name)
+    return value
+
+
+# name      Quality's switch and attribute; Engine.<name>_submit / <name>_wait; the key of records_by_kind
+# label     how the "-only pass has no SSIM scales" message names the kind
+# reads     the chunk's frames the submit gets: "pair" (reference, distorted), "ref" (reference alone) or "dist" (the distorted
+#           stream alone - in a pass that reads one stream only, that stream)
+# dtype     of the records a wait returns: [n, planes], or [n] with per_frame
+# halo      the submit also gets prev0, the reference frame before the chunk, after the planes
+# check     check(name, planes): the kind's rule on the plane list, a ValueError when the kind is on and the planes break it
+# params    (Quality keyword, check(keyword, value) -> value): validated whether the kind is on or not, kept as attributes and
+#           passed to the submit after the planes and a None colour model (= the one that follows from the planes)
+# whole     applied once to the whole clip's concatenated records
+# wait      Quality attributes passed to the wait
+PlaneKind = collections.namedtuple("PlaneKind", "name label reads dtype halo per_frame check params whole wait",
+                                   defaults=(False, False, None, (), None, ()))
+# in the order of the submits of a chunk AND of the elements of the tuple a pass returns
+PLANE_KINDS = (
+    PlaneKind("vif", "a VIF-only", "pair", VIF_DTYPE),
+    PlaneKind("adm", "an ADM-only", "pair", ADM_DTYPE),
+    PlaneKind("motion", "a motion-only", "ref", MOTION_DTYPE, halo=True, whole=motion_records),
+    PlaneKind("siti", "an SI/TI-only", "ref", SITI_DTYPE, halo=True),
+    PlaneKind("psnr_hvs", "a PSNR-HVS-only", "pair", PSNR_HVS_DTYPE),
+    PlaneKind("ciede", "a CIEDE2000-only", "pair", CIEDE_DTYPE, per_frame=True, check=_three_planes,
+              params=(("ciede_weights", _weights),)),
+    PlaneKind("gmsd", "a GMSD-only", "pair", GMSD_DTYPE),
+    PlaneKind("cambi", "a CAMBI-only", "dist", CAMBI_DTYPE),
+    PlaneKind("xpsnr", "an XPSNR-only", "pair", XPSNR_DTYPE, halo=True, check=lambda kind, planes: check_xpsnr_planes(planes)),
+    PlaneKind("haarpsi", "a HaarPSI-only", "pair", HAARPSI_DTYPE),
+    PlaneKind("vca", "a VCA-only", "ref", VCA_DTYPE, halo=True, check=lambda kind, planes: check_vca_planes(planes),
+              wait=("vca_blocks",)),
+    PlaneKind("artifacts", "an artifacts-only", "dist", ARTIFACTS_DTYPE),
+    PlaneKind("brisque", "a brisque-only", "dist", BRISQUE_DTYPE),
+    PlaneKind("mdsi", "an MDSI-only", "pair", MDSI_DTYPE, per_frame=True, check=_one_plane_or_three),
+    PlaneKind("itp", "a dE_ITP-only", "pair", ITP_DTYPE, per_frame=True, check=_three_planes,
+              params=(("itp_transfer", _transfer), ("itp_full_range", _full_range))),
+    PlaneKind("pu21", "a PU21-only", "pair", PU21_DTYPE, per_frame=True, check=_three_planes,
+              params=(("pu21_transfer", _transfer), ("pu21_full_range", _full_range))),
+    PlaneKind("fsim", "an FSIM-only", "pair", FSIM_DTYPE, per_frame=True, check=_one_plane_or_three),
+)
+
+
+def _elements(on):
+    """The kinds that have an element in a pass's tuple after sse, ssim and the scales, in order; on: kind name -> switch.
+    vif, adm and motion form the tuple's head: vif has an element (None when it is off) as soon as one of the three is on, adm
+    as soon as adm or motion is; every later kind has one when it is on."""
+    head = 3 if on["motion"] else 2 if on["adm"] else 1 if on["vif"] else 0
+    return list(PLANE_KINDS[:head]) + [k for k in PLANE_KINDS[3:] if on[k.name]]
+
+
+def _switches(quality):
+    return quality if isinstance(quality, dict) else {k.name: getattr(quality, k.name) for k in PLANE_KINDS}
+
+
+def records_by_kind(q, quality):
+    """The quality tuple `q` of a pass (run) as a dict: "sse" and "ssim" (None after an "only"), with Quality(.., scales=True)
+    "cs" and "ssim_scales", and every element after them under its kind's name - the requested kinds, plus vif / adm = None where
+    the tuple holds their placeholder.  quality: the pass's Quality, or a dict kind name -> switch."""
+    kinds = _elements(_switches(quality))
+    head = len(q) - len(kinds)
+    out = dict(zip(("sse", "ssim", "cs", "ssim_scales"), q[:head]))
+    out.update(zip((k.name for k in kinds), q[head:]))
+    return out
+
+
+class Quality:
+    """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
+
+    def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
+                 psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
+                 haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
+                 itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False):
+        """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
+        Every other switch turns on one plane-batch kind (PLANE_KINDS) and is False, True or "only":
+        True    every chunk also goes through the kind's kernels (Engine.<kind>_submit) from the SAME upload - the chunk was
+                uploaded once - and the pass's tuple gains the kind's records as ONE further element, in the table's order
+                (run states the layout)
+        "only"  likewise, and the pass measures no SSE / SSIM (any "only" drops them: vif="only", adm=True is VIF and ADM alone)
+
+        kind      reads      records (engine.<KIND>_DTYPE)                                            planes
+        vif       pair       [n,p] num[4], den[4], scale[4], vif
+        adm       pair       [n,p] num[4], den[4], scale[4], adm2
+        motion    ref, halo  [n,p] MOTION_PASS_DTYPE: sad, motion and motion2, the last formed once
+                             over the whole clip (motion_records)
+        siti      ref, halo  [n,p] si, ti and the four sums
+        psnr_hvs  pair       [n,p] s_hvs, s_hvsm, psnr_hvs, psnr_hvsm
+        ciede     pair       [n]   de_sum, de_mean, ciede2000                                         exactly three
+        gmsd      pair       [n,p] the three integer words, count, gms_mean, gmsd
+        cambi     dist       [n,p] CAMBI_DTYPE
+        xpsnr     pair, halo [n,p] sse, wsse, xpsnr, block, nbx, nby                                  planar, the first the luma
+        haarpsi   pair       [n,p] the three integer words, similarity, haarpsi
+        vca       ref, halo  [n,p] e_sum, h_sum, l_sum, nbx, nby, e, h, l                             planar, each >= 32 x 32
+        artifacts dist       [n,p] ARTIFACTS_DTYPE (blockiness / blur / noise)
+        brisque   dist       [n,p] BRISQUE_DTYPE
+        mdsi      pair       [n]   the four integer words, count, factor, dev, mdsi                   one, or three together
+        itp       pair       [n]   sum_q, max_q, de_sum, de_mean, de_max                              exactly three
+        pu21      pair       [n]   the five integer words, windows, mse_y, mse_rgb, pu_psnr,          exactly three
+                                   pu_psnr_rgb, pu_ssim
+        fsim      pair       [n]   the three integer words, count, factor, flags, fsim, fsimc         one, or three together
+
+        reads   pair: the chunk's reference and distorted frames.  ref: its REFERENCE frames alone.  dist: its frames of the
+                DISTORTED (encoded) stream alone.  halo: the submit also gets prev0, the last reference frame of the previous
+                chunk (the reference feed's halo slot; XPSNR needs it for the activity of the chunk's first frame, VCA for its
+                gradient).  A pass whose kinds read one stream - motion, siti, vca and, as "only", cambi, artifacts and brisque,
+                with nothing else that needs the pair - reads the `ref` stream alone: give it the frames to measure
+        records [n,p]: one per frame and plane; [n]: one per frame, not per plane (the planes are taken together)
+        vca_blocks=True: VCA's element is the pair (records, block maps: per plane dict(qh, s as uint64 [n, nby, nbx]))
+        ciede_weights: (kL, kC, kH), default the CIE standard (1, 1, 1); the colour model follows from the planes' pixel step
+                (Engine.ciede_model)
+        itp_transfer, pu21_transfer: "pq" | "hlg"; itp_full_range, pu21_full_range: False (limited) | True; the colour model
+                of both follows from the planes (Engine.itp_model), that of mdsi and fsim likewise (Engine.mdsi_model)"""
+        given = dict(locals())   # the keyword arguments by name, for the table
+        if scales and ssim_mode != N.SSIM_MS:
+            raise ValueError("per-scale means exist in the multi-scale mode only")
+        for kind in PLANE_KINDS:
+            on = given[kind.name]
+            if not (isinstance(on, bool) or (isinstance(on, str) and on == "only")):
+                raise ValueError("%s must be False, True or 'only'" % kind.name)
+            if on == "only" and scales:
+                raise ValueError("%s pass has no SSIM scales" % kind.label)
+            if on and kind.check is not None:
+                kind.check(kind.name, planes)
+            setattr(self, kind.name, on)
+            for name, check in kind.params:
+                setattr(self, name, check(name, given[name]))
+        self.planes, self.ssim_mode, self.scales, self.vca_blocks = planes, ssim_mode, bool(scales), bool(vca_blocks)
+        # the pass measures SSE / SSIM
+        self.ssim = all(given[kind.name] != "only" for kind in PLANE_KINDS)
 
 
 class _Feed:
@@ -622,6 +595,29 @@ def pass_lock(device=None):
         return lk
 
 
+def _clip_records(kind, chunks, quality):
+    """A kind's element of the quality tuple from its chunks' results, in frame order (an empty clip has no chunks)."""
+    blocks = kind.name == "vca" and quality.vca_blocks   # a chunk's result is then the pair (records, block maps)
+    rec = [c[0] for c in chunks] if blocks else chunks
+    rec = np.concatenate(rec) if rec else np.zeros(0 if kind.per_frame else (0, len(quality.planes)), kind.dtype)
+    if kind.whole is not None:
+        rec = kind.whole(rec)
+    if not blocks:
+        return rec
+    maps = []
+    for pl, p in enumerate(quality.planes):
+        none = np.zeros((0,) + vca_grid(p[0], p[1])[::-1], np.uint64)
+        maps.append({k: np.concatenate([c[1][pl][k] for c in chunks]) if chunks else none.copy() for k in ("qh", "s")})
+    return rec, maps
+
+
+def _tail(quality, records):
+    """The quality tuple after sse, ssim and the scales; records: kind name -> its chunks' results (none: an empty clip).  vif and
+    adm hold a None placeholder where a later kind of the tuple's head is on and they are not (_elements)."""
+    return tuple(_clip_records(kind, records.get(kind.name, []), quality) if getattr(quality, kind.name) else None
+                 for kind in _elements(_switches(quality)))
+
+
 def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=None, on_quality=None, qdist=None, device=None):
     """One pass over a clip.
 
@@ -636,35 +632,20 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     on_quality  optional callback(first_frame, sse [m,p], ssim [m,p]) per finished chunk, in frame order (stats
                 lines are formatted while the GPU works on the next chunk)
     device      the device of the default engine when `engine` is None and no stream is resident (config key "device")
-    -> (sse [n,p] uint64, ssim [n,p] float64) or None, series dict or None.  With Quality(.., scales=True) the tuple is
-    (sse, ssim, cs [n,p,5], ssim per scale [n,p,5]); with Quality(.., vif=True) the VIF records [n,p] (engine.VIF_DTYPE) are
-    appended as the last element, and with vif="only" sse and ssim are None.  With Quality(.., adm=True) two elements are
-    appended instead: the VIF records (None when VIF was not requested) and the ADM records [n,p] (engine.ADM_DTYPE); adm="only"
-    leaves sse and ssim None as well.  With Quality(.., motion=True) three elements are appended: the VIF records or None, the ADM
-    records or None and the motion records [n,p] (MOTION_PASS_DTYPE); motion="only" leaves sse and ssim None as well.
-    Quality(.., siti=True) appends ONE further last element to whichever of these tuples the pass returns: the SI/TI records
-    [n,p] (engine.SITI_DTYPE); siti="only" leaves sse and ssim None as well.  Quality(.., psnr_hvs=True) likewise appends ONE
-    further last element, after SI/TI's: the PSNR-HVS records [n,p] (engine.PSNR_HVS_DTYPE); psnr_hvs="only" leaves sse and ssim
-    None as well.  Quality(.., ciede=True) appends ONE further last element, after PSNR-HVS's: the CIEDE2000 records [n]
-    (engine.CIEDE_DTYPE, one per frame); ciede="only" leaves sse and ssim None as well.  Quality(.., gmsd=True) appends ONE
-    further last element, after CIEDE2000's: the GMSD records [n,p] (engine.GMSD_DTYPE); gmsd="only" leaves sse and ssim None as
-    well.  Quality(.., cambi=True) appends ONE further last element, after GMSD's: the CAMBI records [n,p] (engine.CAMBI_DTYPE)
-    of the distorted stream; cambi="only" leaves sse and ssim None as well and measures `ref`, the only stream it reads.
-    Quality(.., xpsnr=True) appends ONE further last element, after CAMBI's: the XPSNR records [n,p] (engine.XPSNR_DTYPE);
-    xpsnr="only" leaves sse and ssim None as well.  Quality(.., haarpsi=True) appends ONE further last element, after XPSNR's:
-    the HaarPSI records [n,p] (engine.HAARPSI_DTYPE); haarpsi="only" leaves sse and ssim None as well.  Quality(.., vca=True)
-    appends ONE further last element, after HaarPSI's: the VCA records [n,p] (engine.VCA_DTYPE) of the reference stream - with
-    vca_blocks=True the pair (records, block maps); vca="only" leaves sse and ssim None as well and reads `ref` alone.
-    Quality(.., artifacts=True) appends ONE further last element, after VCA's: the blockiness / blur / noise records [n,p]
-    (engine.ARTIFACTS_DTYPE) of the distorted stream; artifacts="only" leaves sse and ssim None as well and measures `ref`, the
-    only stream it reads.  Quality(.., brisque=True) appends ONE further last element, after the artefact measures': the BRISQUE
-    records [n,p] (engine.BRISQUE_DTYPE) of the distorted stream; brisque="only" leaves sse and ssim None as well and measures
-    `ref`, the only stream it reads.  Quality(.., mdsi=True) appends ONE further last element, after BRISQUE's: the MDSI records
-    [n] (engine.MDSI_DTYPE, one per frame); mdsi="only" leaves sse and ssim None as well.  Quality(.., itp=True) appends ONE
-    further last element, after MDSI's: the dE_ITP records [n] (engine.ITP_DTYPE, one per frame); itp="only" leaves sse and ssim
-    None as well.  Quality(.., pu21=True) appends ONE further last element, after dE_ITP's: the PU21 records [n]
-    (engine.PU21_DTYPE, one per frame); pu21="only" leaves sse and ssim None as well.  Quality(.., fsim=True) appends ONE further
-    last element, after PU21's: the FSIM records [n] (engine.FSIM_DTYPE, one per frame); fsim="only" leaves sse and ssim None as well.
+    -> (sse [n,p] uint64, ssim [n,p] float64) or None, series dict or None.  The quality tuple, from its front:
+      sse, ssim            both None when any switch of the Quality is "only"
+      cs, ssim per scale   [n,p,5] each, with Quality(.., scales=True) alone
+      vif, adm, motion     with Quality(.., vif=True): the VIF records [n,p] (engine.VIF_DTYPE); with adm=True two elements: the
+                           VIF records (None when VIF was not requested) and the ADM records [n,p] (engine.ADM_DTYPE); with
+                           motion=True three: the VIF records or None, the ADM records or None and the motion records [n,p]
+                           (MOTION_PASS_DTYPE)
+      every later kind     that is requested appends ONE element, in the order of PLANE_KINDS: siti, psnr_hvs, ciede, gmsd, cambi,
+                           xpsnr, haarpsi, vca, artifacts, brisque, mdsi, itp, pu21, fsim - its records [n,p], for ciede, mdsi,
+                           itp, pu21 and fsim [n] (one per frame), of engine.<KIND>_DTYPE; with vca_blocks=True VCA's is the
+                           pair (records, block maps)
+    (records_by_kind names the elements.)  Quality's docstring has the table of the kinds: motion, siti and vca measure the
+    reference stream, cambi, artifacts and brisque the distorted one - as "only", in a pass that reads nothing else, they measure
+    `ref`, the only stream the pass reads then.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
     Streams may live in different places (device / pinned / pageable): each travels its own way.  Passes on one device
@@ -705,58 +686,7 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         e5 = np.zeros((0, len(quality.planes), N.MS_LEVELS))
         q = (e.astype(np.uint64), e) if quality.ssim else (None, None)
         q += (e5, e5.copy()) if quality.scales else ()
-        if quality.vif or quality.adm or quality.motion:
-            from .engine import ADM_DTYPE, VIF_DTYPE
-            q += (np.zeros((0, len(quality.planes)), VIF_DTYPE) if quality.vif else None,)
-            if quality.adm or quality.motion:
-                q += (np.zeros((0, len(quality.planes)), ADM_DTYPE) if quality.adm else None,)
-            if quality.motion:
-                q += (np.zeros((0, len(quality.planes)), MOTION_PASS_DTYPE),)
-        if quality.siti:
-            from .engine import SITI_DTYPE
-            q += (np.zeros((0, len(quality.planes)), SITI_DTYPE),)
-        if quality.psnr_hvs:
-            from .engine import PSNR_HVS_DTYPE
-            q += (np.zeros((0, len(quality.planes)), PSNR_HVS_DTYPE),)
-        if quality.ciede:
-            from .engine import CIEDE_DTYPE
-            q += (np.zeros(0, CIEDE_DTYPE),)
-        if quality.gmsd:
-            from .engine import GMSD_DTYPE
-            q += (np.zeros((0, len(quality.planes)), GMSD_DTYPE),)
-        if quality.cambi:
-            from .engine import CAMBI_DTYPE
-            q += (np.zeros((0, len(quality.planes)), CAMBI_DTYPE),)
-        if quality.xpsnr:
-            from .engine import XPSNR_DTYPE
-            q += (np.zeros((0, len(quality.planes)), XPSNR_DTYPE),)
-        if quality.haarpsi:
-            from .engine import HAARPSI_DTYPE
-            q += (np.zeros((0, len(quality.planes)), HAARPSI_DTYPE),)
-        if quality.vca:
-            from .engine import VCA_DTYPE, vca_grid
-            rec = np.zeros((0, len(quality.planes)), VCA_DTYPE)
-            maps = [dict(qh=np.zeros((0,) + vca_grid(p[0], p[1])[::-1], np.uint64), s=np.zeros((0,) + vca_grid(p[0], p[1])[::-1], np.uint64))
-                    for p in quality.planes]
-            q += ((rec, maps) if quality.vca_blocks else rec,)
-        if quality.artifacts:
-            from .engine import ARTIFACTS_DTYPE
-            q += (np.zeros((0, len(quality.planes)), ARTIFACTS_DTYPE),)
-        if quality.brisque:
-            from .engine import BRISQUE_DTYPE
-            q += (np.zeros((0, len(quality.planes)), BRISQUE_DTYPE),)
-        if quality.mdsi:
-            from .engine import MDSI_DTYPE
-            q += (np.zeros(0, MDSI_DTYPE),)
-        if quality.itp:
-            from .engine import ITP_DTYPE
-            q += (np.zeros(0, ITP_DTYPE),)
-        if quality.pu21:
-            from .engine import PU21_DTYPE
-            q += (np.zeros(0, PU21_DTYPE),)
-        if quality.fsim:
-            from .engine import FSIM_DTYPE
-            q += (np.zeros(0, FSIM_DTYPE),)
+        q += _tail(quality, {})
         return q, series
     if engine is not None:
         first = engine
@@ -772,7 +702,10 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
     # motion, SI/TI, VCA, CAMBI, the artefact measures and BRISQUE alone read the reference stream only: the distorted stream is not even uploaded
-    ref_only = want_q and not want_c and not quality.ssim and not quality.vif and not quality.adm and not quality.psnr_hvs and not quality.ciede and not quality.gmsd and not quality.xpsnr and not quality.haarpsi and not quality.mdsi and not quality.itp and not quality.pu21 and not quality.fsim and quality.cambi is not True and quality.artifacts is not True and quality.brisque is not True
+    requested = [k for k in PLANE_KINDS if getattr(quality, k.name)] if want_q else []   # in submit order
+    ref_only = (want_q and not want_c and not quality.ssim and not any(k.reads == "pair" for k in requested)
+                and not any(k.reads == "dist" and getattr(quality, k.name) is True for k in requested))
+    halo = any(k.halo for k in requested)
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -804,7 +737,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     host = any(f.host for f in feeds.values())
     staged = any(f.staged for f in feeds.values())
     cap = chunk_frames(batch_size, interval if (want_q and want_c) else None, per_frame if host else 0, staged)
-    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=bool(want_q and (quality.motion or quality.siti or quality.xpsnr or quality.vca)))
+    plans = plan_chunks(n, want_q, interval, lo, hi, cap, split, motion=halo)
     nchunks = len(plans)
     # ---- lanes
     farneback = want_c and (complexity.mask & N.M_MOTION) and complexity.motion_mode == N.MOTION_FARNEBACK
@@ -880,7 +813,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     def submit(p, eng):
         ln = p["k"] % len(lanes)
         dev = p["dev"]
-        p["has_q"] = p["has_v"] = p["has_a"] = p["has_m"] = p["has_s"] = p["has_h"] = p["has_e"] = p["has_g"] = p["has_b"] = p["has_x"] = p["has_w"] = p["has_t"] = p["has_r"] = p["has_n"] = p["has_d"] = p["has_i"] = p["has_u"] = p["has_f"] = p["has_c"] = False
+        p["has_q"] = p["has_c"] = False
+        p["sent"] = []   # the kinds whose batch the lane holds for this chunk, in submit order; their results under p["res"]
         with N.trace_range("vqa:submit chunk=%d lane=%d", p["k"], ln):
             if host:
                 eng.wait_for(cp)   # on the device: the lane's stream continues when the uploads enqueued so far are done
@@ -898,66 +832,22 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 if quality.ssim:
                     eng.quality_submit(pair[0], pair[1], quality.planes, quality.ssim_mode)
                     p["has_q"] = True
-                if quality.vif:   # the same device frames: the chunk was uploaded once
-                    eng.vif_submit(pair[0], pair[1], quality.planes)
-                    p["has_v"] = True
-                if quality.adm:
-                    eng.adm_submit(pair[0], pair[1], quality.planes)
-                    p["has_a"] = True
-                if quality.motion or quality.siti or quality.xpsnr or quality.vca:   # prev0 = the reference frame before the chunk: the halo
-                    prev0 = None                     # slot of the chunk's own buffer (host streams) or the resident clip's frame
-                    if p["q0"] > 0:                  # in place
-                        if fr.host:
-                            b = dev[fr.name]
-                            prev0 = DeviceFrames(b.ptr, 1, 1, fr.fb // fr.itemsize, frame_stride=fr.fb, row_stride=fr.fb,
-                                                 owner=b, channels=1, itemsize=fr.itemsize)
-                        else:
-                            prev0 = fr.src.frames.frame(p["q0"] - 1)
-                    if quality.motion:
-                        eng.motion_submit(pair[0], quality.planes, prev0)
-                        p["has_m"] = True
-                    if quality.siti:
-                        eng.siti_submit(pair[0], quality.planes, prev0)
-                        p["has_s"] = True
-                if quality.psnr_hvs:
-                    eng.psnr_hvs_submit(pair[0], pair[1], quality.planes)
-                    p["has_h"] = True
-                if quality.ciede:
-                    eng.ciede_submit(pair[0], pair[1], quality.planes, None, quality.ciede_weights)
-                    p["has_e"] = True
-                if quality.gmsd:
-                    eng.gmsd_submit(pair[0], pair[1], quality.planes)
-                    p["has_g"] = True
-                if quality.cambi:   # the distorted stream; the only stream of a pass that reads one
-                    eng.cambi_submit(pair[-1], quality.planes)
-                    p["has_b"] = True
-                if quality.xpsnr:   # the pair, and the halo for the activity of the chunk's first frame
-                    eng.xpsnr_submit(pair[0], pair[1], quality.planes, prev0)
-                    p["has_x"] = True
-                if quality.haarpsi:
-                    eng.haarpsi_submit(pair[0], pair[1], quality.planes)
-                    p["has_w"] = True
-                if quality.vca:   # the reference frames alone, and the halo for the gradient of the chunk's first frame
-                    eng.vca_submit(pair[0], quality.planes, prev0)
-                    p["has_t"] = True
-                if quality.artifacts:   # the distorted stream; the only stream of a pass that reads one
-                    eng.artifacts_submit(pair[-1], quality.planes)
-                    p["has_r"] = True
-                if quality.brisque:     # likewise
-                    eng.brisque_submit(pair[-1], quality.planes)
-                    p["has_n"] = True
-                if quality.mdsi:
-                    eng.mdsi_submit(pair[0], pair[1], quality.planes)
-                    p["has_d"] = True
-                if quality.itp:
-                    eng.itp_submit(pair[0], pair[1], quality.planes, None, quality.itp_transfer, quality.itp_full_range)
-                    p["has_i"] = True
-                if quality.pu21:
-                    eng.pu21_submit(pair[0], pair[1], quality.planes, None, quality.pu21_transfer, quality.pu21_full_range)
-                    p["has_u"] = True
-                if quality.fsim:
-                    eng.fsim_submit(pair[0], pair[1], quality.planes)
-                    p["has_f"] = True
+                prev0 = None                     # the reference frame before the chunk: the halo slot of the chunk's own buffer
+                if halo and p["q0"] > 0:         # (host streams) or the resident clip's frame in place
+                    if fr.host:
+                        b = dev[fr.name]
+                        prev0 = DeviceFrames(b.ptr, 1, 1, fr.fb // fr.itemsize, frame_stride=fr.fb, row_stride=fr.fb,
+                                             owner=b, channels=1, itemsize=fr.itemsize)
+                    else:
+                        prev0 = fr.src.frames.frame(p["q0"] - 1)
+                # the same device frames for every kind: the chunk was uploaded once.  "dist" is the pair's last stream - in a
+                # pass that reads one stream, that stream
+                streams = {"pair": pair[:2], "ref": pair[:1], "dist": pair[-1:]}
+                for kind in requested:
+                    more = ((prev0,) if kind.halo else ()) + (((None,) + tuple(getattr(quality, a) for a, _ in kind.params))
+                                                              if kind.params else ())
+                    getattr(eng, kind.name + "_submit")(*streams[kind.reads], quality.planes, *more)
+                    p["sent"].append(kind)
             if want_c and p["j1"] > p["j0"]:
                 m = p["j1"] - p["j0"]
                 fd = feeds["dist"]
@@ -976,7 +866,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 eng.complexity_submit(batch, prev0, complexity.mask, params)
                 p["has_c"] = True
 
-    sse, ssim, ms_cs, ms_ssim, vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itps, pus, fss = [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
+    sse, ssim, ms_cs, ms_ssim = [], [], [], []
+    records = {k.name: [] for k in requested}        # kind -> its chunks' results, in frame order
     arrays = {k: [] for k in KINDS + ("temporal",)}  # the same series as float64 arrays, for the pooling (no list round trip)
 
     def wait(p, eng):
@@ -984,40 +875,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         with N.trace_range("vqa:wait chunk=%d lane=%d", p["k"], p["k"] % len(lanes)):
             if p["has_q"]:
                 p["qres"] = eng.quality_wait(quality.scales)
-            if p["has_v"]:
-                p["vres"] = eng.vif_wait()
-            if p["has_a"]:
-                p["ares"] = eng.adm_wait()
-            if p["has_m"]:
-                p["mres"] = eng.motion_wait()
-            if p["has_s"]:
-                p["sres"] = eng.siti_wait()
-            if p["has_h"]:
-                p["hres"] = eng.psnr_hvs_wait()
-            if p["has_e"]:
-                p["eres"] = eng.ciede_wait()
-            if p["has_g"]:
-                p["gres"] = eng.gmsd_wait()
-            if p["has_b"]:
-                p["bres"] = eng.cambi_wait()
-            if p["has_x"]:
-                p["xres"] = eng.xpsnr_wait()
-            if p["has_w"]:
-                p["wres"] = eng.haarpsi_wait()
-            if p["has_t"]:
-                p["tres"] = eng.vca_wait(quality.vca_blocks)
-            if p["has_r"]:
-                p["rres"] = eng.artifacts_wait()
-            if p["has_n"]:
-                p["nres"] = eng.brisque_wait()
-            if p["has_d"]:
-                p["dres"] = eng.mdsi_wait()
-            if p["has_i"]:
-                p["ires"] = eng.itp_wait()
-            if p["has_u"]:
-                p["ures"] = eng.pu21_wait()
-            if p["has_f"]:
-                p["fres"] = eng.fsim_wait()
+            p["res"] = {}
+            for kind in p["sent"]:
+                p["res"][kind.name] = getattr(eng, kind.name + "_wait")(*(getattr(quality, a) for a in kind.wait))
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
         if staged:
@@ -1036,40 +896,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 ssim.append(res["ssim"])
                 if on_quality is not None:
                     on_quality(p["q0"], sse[-1], ssim[-1])
-            if p["has_v"]:
-                vif.append(p.pop("vres"))
-            if p["has_a"]:
-                adm.append(p.pop("ares"))
-            if p["has_m"]:
-                mot.append(p.pop("mres"))
-            if p["has_s"]:
-                siti.append(p.pop("sres"))
-            if p["has_h"]:
-                hvs.append(p.pop("hres"))
-            if p["has_e"]:
-                cie.append(p.pop("eres"))
-            if p["has_g"]:
-                gms.append(p.pop("gres"))
-            if p["has_b"]:
-                cam.append(p.pop("bres"))
-            if p["has_x"]:
-                xps.append(p.pop("xres"))
-            if p["has_w"]:
-                hps.append(p.pop("wres"))
-            if p["has_t"]:
-                vcs.append(p.pop("tres"))
-            if p["has_r"]:
-                art.append(p.pop("rres"))
-            if p["has_n"]:
-                bsq.append(p.pop("nres"))
-            if p["has_d"]:
-                mds.append(p.pop("dres"))
-            if p["has_i"]:
-                itps.append(p.pop("ires"))
-            if p["has_u"]:
-                pus.append(p.pop("ures"))
-            if p["has_f"]:
-                fss.append(p.pop("fres"))
+            for kind in p["sent"]:
+                records[kind.name].append(p["res"].pop(kind.name))
             if p["has_c"]:
                 rec = p.pop("rec")
                 for kind in KINDS:
@@ -1128,44 +956,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         q = (np.concatenate(sse), np.concatenate(ssim)) if quality.ssim else (None, None)
     if want_q and quality.scales:
         q += (np.concatenate(ms_cs), np.concatenate(ms_ssim))
-    if want_q and (quality.vif or quality.adm or quality.motion):
-        q += (np.concatenate(vif) if quality.vif else None,)
-    if want_q and (quality.adm or quality.motion):
-        q += (np.concatenate(adm) if quality.adm else None,)
-    if want_q and quality.motion:
-        q += (motion_records(np.concatenate(mot)),)
-    if want_q and quality.siti:
-        q += (np.concatenate(siti),)
-    if want_q and quality.psnr_hvs:
-        q += (np.concatenate(hvs),)
-    if want_q and quality.ciede:
-        q += (np.concatenate(cie),)
-    if want_q and quality.gmsd:
-        q += (np.concatenate(gms),)
-    if want_q and quality.cambi:
-        q += (np.concatenate(cam),)
-    if want_q and quality.xpsnr:
-        q += (np.concatenate(xps),)
-    if want_q and quality.haarpsi:
-        q += (np.concatenate(hps),)
-    if want_q and quality.vca:
-        if quality.vca_blocks:
-            maps = [{k: np.concatenate([c[1][pl][k] for c in vcs]) for k in ("qh", "s")} for pl in range(len(quality.planes))]
-            q += ((np.concatenate([c[0] for c in vcs]), maps),)
-        else:
-            q += (np.concatenate(vcs),)
-    if want_q and quality.artifacts:
-        q += (np.concatenate(art),)
-    if want_q and quality.brisque:
-        q += (np.concatenate(bsq),)
-    if want_q and quality.mdsi:
-        q += (np.concatenate(mds),)
-    if want_q and quality.itp:
-        q += (np.concatenate(itps),)
-    if want_q and quality.pu21:
-        q += (np.concatenate(pus),)
-    if want_q and quality.fsim:
-        q += (np.concatenate(fss),)
+    if want_q:
+        q += _tail(quality, records)
     if want_c:
         series["_float64"] = {k: (np.concatenate(v).astype(np.float64) if v else np.zeros(0)) for k, v in arrays.items()}
     return q, series

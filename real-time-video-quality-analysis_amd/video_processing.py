@@ -744,7 +744,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             if len(LAYOUTS[layout][1]) != 3:
                 raise ValueError("pu21 needs three planes")
             _check_pu21(pu21_transfer, pu21_full_range)
-        if vif or adm or motion or siti or psnr_hvs or ciede or gmsd or cambi or xpsnr or haarpsi or vca or artifacts or brisque or mdsi or delta_itp or pu21 or fsim:
+        if any((vif, adm, motion, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, mdsi, delta_itp, pu21,
+                fsim)):
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -802,72 +803,17 @@ MODE_KEYS = {
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
                        cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
                        mdsi=False, delta_itp=False, pu21=False, fsim=False):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and noise / BRISQUE and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (the
-    tail of stream.run's quality tuple) -> vmaf_log"""
-    rec = hvs = cie = gms = cam = xps = hps = vcs = art = bsq = mds = itp = pus = fsm = None
-    if fsim:       # the tuple's last element, then PU21's
-        fsm, q = q[-1], q[:-1]
-    if pu21:       # then dE_ITP's
-        pus, q = q[-1], q[:-1]
-    if delta_itp:  # then MDSI's
-        itp, q = q[-1], q[:-1]
-    if mdsi:       # then BRISQUE's
-        mds, q = q[-1], q[:-1]
-    if brisque:    # then the artefact measures'
-        bsq, q = q[-1][:, 0], q[:-1]
-    if artifacts:  # then VCA's
-        art, q = q[-1][:, 0], q[:-1]
-    if vca:        # then HaarPSI's
-        vcs, q = q[-1][:, 0], q[:-1]
-    if haarpsi:    # then XPSNR's
-        hps, q = q[-1][:, 0], q[:-1]
-    if xpsnr:      # then CAMBI's
-        xps, q = q[-1][:, 0], q[:-1]
-    if cambi:      # then GMSD's
-        cam, q = q[-1][:, 0], q[:-1]
-    if gmsd:       # then CIEDE2000's, PSNR-HVS's, SI/TI's; what is left is the tuple of a pass without them
-        gms, q = q[-1][:, 0], q[:-1]
-    if ciede:
-        cie, q = q[-1], q[:-1]
-    if psnr_hvs:
-        hvs, q = q[-1][:, 0], q[:-1]
-    if siti:
-        rec, q = q[-1][:, 0], q[:-1]
-    more = {"siti": rec} if hvs is None else {"siti": rec, "psnr_hvs": hvs}
-    if cie is not None:
-        more["ciede"] = cie
-    if gms is not None:
-        more["gmsd"] = gms
-    if cam is not None:
-        more["cambi"] = cam
-    if xps is not None:
-        more["xpsnr"] = xps
-    if hps is not None:
-        more["haarpsi"] = hps
-    if vcs is not None:
-        more["vca"] = vcs
-    if art is not None:
-        more["artifacts"] = art
-    if bsq is not None:
-        more["brisque"] = bsq
-        more["brisque_model"] = brisque_model
-    if mds is not None:
-        more["mdsi"] = mds
-    if itp is not None:
-        more["delta_itp"] = itp
-    if pus is not None:
-        more["pu21"] = pus
-    if fsm is not None:
-        more["fsim"] = fsm
-    if motion:
-        write_vif_log(vmaf_log, q[-3]["scale"][:, 0] if vif else None, q[-2][:, 0] if adm else None, motion=q[-1][:, 0],
-                      model=model, **more)
-    elif adm:
-        write_vif_log(vmaf_log, q[-2]["scale"][:, 0] if vif else None, q[-1][:, 0], **more)
-    elif vif:
-        write_vif_log(vmaf_log, q[-1]["scale"][:, 0], **more)
-    else:
-        write_vif_log(vmaf_log, **more)
+    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and
+    noise / BRISQUE and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (stream.run's quality tuple, whose
+    elements stream.records_by_kind names) -> vmaf_log"""
+    on = dict(vif=vif, adm=adm, motion=motion, siti=siti, psnr_hvs=psnr_hvs, ciede=ciede, gmsd=gmsd, cambi=cambi, xpsnr=xpsnr,
+              haarpsi=haarpsi, vca=vca, artifacts=artifacts, brisque=brisque, mdsi=mdsi, itp=delta_itp, pu21=pu21, fsim=fsim)
+    rec = stream.records_by_kind(q, on)
+    # write_vif_log's keywords (the kinds' names but for dE_ITP's): the per-plane kinds' first plane, the per-frame kinds' records
+    log = {{"itp": "delta_itp"}.get(k.name, k.name): rec[k.name] if k.per_frame else rec[k.name][:, 0]
+           for k in stream.PLANE_KINDS if on[k.name]}
+    scale = log.pop("vif")["scale"] if vif else None
+    write_vif_log(vmaf_log, scale, log.pop("adm", None), model=model if motion else None, brisque_model=brisque_model, **log)
 
 
 def _check_mode_keys(config):
@@ -1113,7 +1059,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if vif or adm or mot or siti or hvs or cie or gms or cam or xps or hps or vcs or art or bsq or mds or itp or pu or fsm:
+        if any((vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itp, pu, fsm)):
             _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
                                mds, itp, pu, fsm)
         resolution = "%dx%d" % (ew, eh)

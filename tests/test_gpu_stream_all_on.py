@@ -1,8 +1,9 @@
 """GPU: one pass with every switch of stream.Quality on - the configuration "all true" in config.json gives.
 
-stream._run_locked then issues sixteen submits per chunk on one lane (fifteen plane-batch kinds and, fused, the complexity
-batch), collects sixteen results and builds a positional tuple whose layout depends on the switches;
-video_processing._write_feature_log peels that tuple from its end.  Every other file turns on three switches at most.
+stream._run_locked then issues nineteen submits per chunk on one lane (SSE / SSIM, the seventeen plane-batch kinds of
+stream.PLANE_KINDS and, fused, the complexity batch), collects nineteen results and builds a positional tuple whose layout depends on
+the switches; video_processing._write_feature_log reads that tuple by kind name (stream.records_by_kind).  Every other file turns
+on three switches at most.
 
 Expected values: the whole clip (seven frames and a distorted copy; yuv420p at 66 x 98, yuv420p10le at 70 x 74) through the
 direct engine calls, one kind at a time, n = 7 from host frames, on the session engine - CAMBI, the artefact measures and
@@ -25,10 +26,11 @@ N_FRAMES = 7
 GEOMETRIES = {"yuv420p": (66, 98, 8), "yuv420p10le": (70, 74, 10)}
 # the switches in the order their elements take in the tuple (vca_blocks shapes VCA's element)
 SWITCHES = ("vif", "adm", "motion", "siti", "psnr_hvs", "ciede", "gmsd", "cambi", "xpsnr", "haarpsi", "vca", "vca_blocks", "artifacts",
-            "brisque", "mdsi")
+            "brisque", "mdsi", "itp", "pu21", "fsim")
 ALL_ON = {k: True for k in SWITCHES}
-ELEMENTS = 2 + 14                               # sse, ssim and one element per switch but vca_blocks
-AFTER_MOTION = ("siti", "psnr_hvs", "ciede", "gmsd", "cambi", "xpsnr", "haarpsi", "vca", "artifacts", "brisque", "mdsi")
+ELEMENTS = 2 + 17                               # sse, ssim and one element per switch but vca_blocks
+AFTER_MOTION = ("siti", "psnr_hvs", "ciede", "gmsd", "cambi", "xpsnr", "haarpsi", "vca", "artifacts", "brisque", "mdsi",
+                "itp", "pu21", "fsim")
 ONE_STREAM = {"cambi": "dist", "artifacts": "dist", "brisque": "dist", "vca": "ref", "motion": "ref", "siti": "ref"}
 
 
@@ -53,7 +55,8 @@ def _expected(eng, r, d, planes):
             "psnr_hvs": eng.psnr_hvs(r, d, planes), "ciede": eng.ciede(r, d, planes), "gmsd": eng.gmsd(r, d, planes),
             "cambi": eng.cambi(d, planes), "xpsnr": eng.xpsnr(r, d, planes), "haarpsi": eng.haarpsi(r, d, planes),
             "vca": rec, "vca_maps": maps, "artifacts": eng.artifacts(d, planes), "brisque": eng.brisque(d, planes),
-            "mdsi": eng.mdsi(r, d, planes)}
+            "mdsi": eng.mdsi(r, d, planes), "itp": eng.itp(r, d, planes), "pu21": eng.pu21(r, d, planes),
+            "fsim": eng.fsim(r, d, planes)}
 
 
 @pytest.fixture(scope="module")
@@ -116,12 +119,13 @@ def _promised(q, planes, n):
     assert len(q) == ELEMENTS
     assert q[0].dtype == np.uint64 and q[1].dtype == np.float64 and q[0].shape == q[1].shape == (n, p)
     per_plane = (E.VIF_DTYPE, E.ADM_DTYPE, stream.MOTION_PASS_DTYPE, E.SITI_DTYPE, E.PSNR_HVS_DTYPE, None, E.GMSD_DTYPE, E.CAMBI_DTYPE,
-                 E.XPSNR_DTYPE, E.HAARPSI_DTYPE, None, E.ARTIFACTS_DTYPE, E.BRISQUE_DTYPE, None)
+                 E.XPSNR_DTYPE, E.HAARPSI_DTYPE, None, E.ARTIFACTS_DTYPE, E.BRISQUE_DTYPE, None, None, None, None)
     for at, dt in enumerate(per_plane, start=2):
         if dt is not None:
             assert q[at].dtype == dt and q[at].shape == (n, p), at
     assert q[7].dtype == E.CIEDE_DTYPE and q[7].shape == (n,)                    # one per frame
-    assert q[15].dtype == E.MDSI_DTYPE and q[15].shape == (n,)
+    for at, dt in ((15, E.MDSI_DTYPE), (16, E.ITP_DTYPE), (17, E.PU21_DTYPE), (18, E.FSIM_DTYPE)):
+        assert q[at].dtype == dt and q[at].shape == (n,), at
     rec, maps = q[12]
     assert rec.dtype == E.VCA_DTYPE and rec.shape == (n, p) and len(maps) == p
     for pl, m in zip(planes, maps):
@@ -235,7 +239,8 @@ def test_the_fused_pass_with_every_switch_on(clips, layout):
 
 
 # ---- the log and the row ----------------------------------------------------------------------------------------------------
-FLAGS = ("vif", "adm", "motion", "siti", "psnr_hvs", "ciede", "gmsd", "cambi", "xpsnr", "haarpsi", "vca", "artifacts", "brisque", "mdsi")
+FLAGS = ("vif", "adm", "motion", "siti", "psnr_hvs", "ciede", "gmsd", "cambi", "xpsnr", "haarpsi", "vca", "artifacts", "brisque", "mdsi",
+         "delta_itp", "pu21", "fsim")
 BASE_COLUMNS = ["Bitrate (kbps)", "Resolution (px)", "Frame Rate (fps)", "CRF", "PSNR", "SSIM"]
 
 
@@ -274,7 +279,7 @@ def test_run_ffmpeg_metrics_with_every_flag(clips, tmp_path, layout):
             assert open(logs[run][k], "rb").read() == plain, (run, k)
     # the keys and their order
     names = [k for flag in FLAGS for k in one[flag][0]]
-    assert len(names) == len(set(names)) == 4 + 5 + 2 + 2 + 2 + 1 + 1 + 1 + 1 + 1 + 3 + 3 + 36 + 1
+    assert len(names) == len(set(names)) == 4 + 5 + 2 + 2 + 2 + 1 + 1 + 1 + 1 + 1 + 3 + 3 + 36 + 1 + 2 + 3 + 2
     assert len(doc["frames"]) == N_FRAMES
     assert list(doc["pooled_metrics"]) == names + ["vmaf"]
     for i in range(N_FRAMES):
@@ -296,6 +301,9 @@ def test_run_ffmpeg_metrics_with_every_flag(clips, tmp_path, layout):
         assert m["cambi"] == float(exp["cambi"][i, 0]["cambi"]) and m["vca_e"] == float(exp["vca"][i, 0]["e"])
         assert m["motion"] == float(exp["motion"][i, 0]["motion"]) and m["si"] == float(exp["siti"][i, 0]["si"])
         assert m["brisque_07"] == float(exp["brisque"][i, 0]["features"][7]) and m["noise"] == float(exp["artifacts"][i, 0]["noise"])
+        assert m["delta_itp"] == float(exp["itp"][i]["de_mean"]) and m["delta_itp_max"] == float(exp["itp"][i]["de_max"])
+        assert m["pu_ssim"] == float(exp["pu21"][i]["pu_ssim"]) and m["pu_psnr"] == min(float(exp["pu21"][i]["pu_psnr"]), vp.PU21_PSNR_CAP)
+        assert m["fsim"] == float(exp["fsim"][i]["fsim"]) and m["fsimc"] == float(exp["fsim"][i]["fsimc"])
     # the row
     args = ("x", 23, 1000, "%dx%d" % (w, h), 30.0)
     row = vp.extract_metrics_from_logs(*logs["all"], *args)
