@@ -450,6 +450,33 @@ typedef struct vqa_fsim_metrics {
     double fsimc;       /* (signed) B / P; exactly 1 for identical frames; equals fsim under VQA_FSIM_GRAY                     */
 } vqa_fsim_metrics;
 
+/* Signal statistics of one plane of one frame of ONE stream (vqa_sigstats_submit / vqa_sigstats_wait; the definition and the bounds
+ * of the words are stated there).  Every word but the last three doubles and bits_used is an integer the device formed, so the
+ * same frame (with its predecessor) gives the same record bytes at any place of any batch, from host or device memory;
+ * vqa_sigstats_wait forms bits_used, mean, stdev and dif from them on the host. */
+typedef struct vqa_sigstats_metrics {
+    int64_t count;         /* N = h w                                                                                          */
+    uint64_t sum;          /* sum x                                                                                            */
+    uint64_t sum_sq;       /* sum x^2                                                                                          */
+    uint32_t min, max;     /* the smallest and the largest sample                                                              */
+    uint32_t low, median, high; /* the smallest v with C(v) >= (N + 9) / 10, (N + 1) / 2, (9 N + 9) / 10                      */
+    uint32_t or_mask;      /* the bitwise OR of all samples                                                                    */
+    uint32_t and_mask;     /* the bitwise AND of all samples                                                                   */
+    int32_t bits_used;     /* depth - ctz(or_mask); 0 for an all-zero plane                                                    */
+    uint64_t below_black;  /* #{x < black_level}                                                                               */
+    uint64_t under;        /* #{x < 16 s}                                                                                      */
+    uint64_t over_luma;    /* #{x > 235 s}                                                                                     */
+    uint64_t over_chroma;  /* #{x > 240 s}                                                                                     */
+    uint64_t above_peak;   /* #{x > 2^depth - 1}; always 0 for uint8 samples                                                   */
+    uint64_t sad;          /* sum |x - x'|; 0 for a frame with no predecessor                                                  */
+    uint64_t changed;      /* #{x != x'}; 0 for a frame with no predecessor                                                    */
+    int32_t top, bottom;   /* the first and the last row that is not dark; h, -1 for an all-dark plane                         */
+    int32_t left, right;   /* the first and the last column that is not dark; w, -1 for an all-dark plane                      */
+    double mean;           /* sum / N, in sample units                                                                         */
+    double stdev;          /* sqrt(max(sum_sq / N - mean^2, 0))                                                                */
+    double dif;            /* sad / N                                                                                          */
+} vqa_sigstats_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1516,6 +1543,69 @@ VQA_API int vqa_fsim_filter(int hd, int wd, int scale, int orient, double *dst);
     VQA_API int vqa_fsim_lab_read_maps(vqa_ctx *ctx, uint32_t *dst, int64_t n_values);
 #endif
 
+/* ---- Signal statistics and the words QC events are made of: what FFmpeg's signalstats, blackframe, freezedetect, scdet and
+ * cropdetect answer - is the frame black, is the picture frozen, where are the cuts, is it letterboxed, are the levels legal, is
+ * this "10-bit" stream 8-bit content shifted left ----
+ * ONE stream, every plane by itself, frame i with its predecessor i - 1 as halo, like vqa_siti_submit; packed bgr24 planes work as
+ * they do there.  Every word is an integer function of the samples.  Where this text differs from a tool's detail, this text is
+ * what is built.
+ * For one plane of h x w samples, N = h w:  x are the raw integer samples, d = depth, s = 2^(d-8).  The histogram covers the SAMPLE
+ *   TYPE, not the depth: 256 bins for uint8 planes, 65536 for uint16 planes; a uint16 sample above 2^d - 1 is read as it is, as
+ *   elsewhere in this header.  C(v) = #{x <= v}.  x' is the same plane of the frame before: frame i - 1 of the batch, prev0 for
+ *   frame 0, the previous slice's last frame past 32768 frames.
+ *   count        N
+ *   sum, sum_sq  sum x, sum x^2 (uint64)
+ *   min, max     the smallest and the largest sample
+ *   low, median, high   the smallest v with C(v) >= k, k = (N + 9) / 10, (N + 1) / 2, (9 N + 9) / 10 in integer division: exact
+ *                order statistics (FFmpeg's lrint ranks differ by rounding)
+ *   below_black  #{x < black_level}; default black_level = 32 s, blackframe's threshold
+ *   under, over_luma, over_chroma   #{x < 16 s}, #{x > 235 s}, #{x > 240 s}: all three for every plane; the host picks the ones
+ *                that apply to the plane's role
+ *   above_peak   #{x > 2^d - 1}; always 0 for uint8
+ *   or_mask, and_mask   the bitwise OR and AND of all samples; bits_used = d - ctz(or_mask), 0 for an all-zero plane (the host)
+ *   sad, changed sum |x - x'|, #{x != x'}; both 0 for a frame with no predecessor
+ *   top, bottom, left, right (int32)   row r is dark iff sum_x x[r][.] <= crop_level w, column c is dark iff sum_y x[.][c] <=
+ *                crop_level h: integer compares; default crop_level = 24 s, cropdetect's limit.  top and bottom are the first and
+ *                the last row that is not dark, left and right likewise for columns; an all-dark plane gives top = h, bottom = -1,
+ *                left = w, right = -1.
+ *   vqa_sigstats_wait forms three doubles on the host, in sample units, in the order written and without contraction:
+ *   mean = sum / N;  stdev = sqrt(max(sum_sq / N - mean mean, 0));  dif = sad / N.
+ * Limits: every plane at least 16 x 16; N <= 2^28 for uint8 and N <= 2^26 for uint16 planes (vqa_siti_submit's rule):
+ *   VQA_ERR_UNSUPPORTED beyond either.  0 <= black_level, crop_level <= 65535, a NEGATIVE level means the default; a level above
+ *   65535 is VQA_ERR_INVALID.
+ * Why no word can overflow inside the limits.  Every histogram counter is 32 bits and holds at most N <= 2^28 - a flat plane puts
+ *   all N samples into ONE bin, so a packed 16-bit counter would be wrong from 65536 samples on.  sum <= 2^28 255 < 2^36 (uint8) and
+ *   <= 2^26 65535 < 2^42 (uint16); sum_sq <= 2^28 255^2 < 2^44 and <= 2^26 65535^2 < 2^58; sad <= sum's bound; a row or a column sum
+ *   is at most 2^24 65535 < 2^40 (a side is at most N / 16), and so is crop_level w or crop_level h: all inside 64 bits.  The counts
+ *   are at most N.
+ * The usual guarantee: a frame with its predecessor gives the same record bytes at any place of any batch, from host, pinned or
+ *   device memory, alone or next to other kinds.  The kernels do integer adds, min, max, or and compares only - no floating point
+ *   on the device - and all of these are associative and commutative, so neither the tiling nor the order in which workgroups
+ *   retire can change a bit.
+ * Kernels, per sub-slice of frames: k_sigstats_accum, tiled, reads every sample of the frame and of its predecessor once, builds
+ *   the entry's histogram (uint8: in shared memory, then 32-bit global atomics per non-empty bin; uint16: 32-bit global vector
+ *   atomics into the entry's 65536 bins in scratch), adds sad and changed, ORs the masks and adds the row and column sums into a
+ *   profile of h + w uint64 words per entry; k_sigstats_scan, one workgroup per (frame, plane), walks the histogram once for every
+ *   other word and reads the box off the profile.
+ *   Scratch on the device: 168 bytes of words and 8 (h + w) bytes of profile per entry for the whole batch, and the histograms of
+ *   one sub-slice: 1 KiB (uint8) or 256 KiB (uint16) per entry; a batch goes out in sub-slices of frames that keep the histograms
+ *   within 256 MiB.  Frames handed over in host memory (and prev0) are staged in the device buffers an SI/TI batch uses.  All of
+ *   it is kept by the ctx until vqa_trim / vqa_destroy.
+ * The contract of vqa_siti_submit for the stream and prev0, for memory kinds, depths (one per submit) and alignment, and its
+ *   failure guarantee: a failed submit leaves nothing in flight.  VQA_ERR_STATE while a sigstats batch is pending.  A sigstats
+ *   batch is a batch of its own: it may be in flight next to every other kind of the same ctx, and each wait collects its own kind
+ *   only.  A batch of more than 32768 frames goes out in slices.
+ * vqa_sigstats_wait: out holds n * n_planes entries, frame-major.  With profiles != 0, profile_words receives the profiles: for
+ *   every frame, for every plane in order, its h row sums and then its w column sums (n_profile_words = n sum_p (h_p + w_p)); a
+ *   wrong word count or a null pointer is VQA_ERR_INVALID and the batch stays pending.  With profiles == 0 both are ignored.
+ * Not built: signalstats' TOUT, VREP, saturation and hue; durations in seconds; cropdetect's rounding of the box; a joint-pixel
+ *   BRNG.                                                                                                                     */
+VQA_API int vqa_sigstats_submit(vqa_ctx *ctx, const uint8_t *frames, const uint8_t *prev0, int mem_kind, int n,
+                                int64_t frame_stride, const vqa_plane_desc *planes, int n_planes, int black_level,
+                                int crop_level);
+VQA_API int vqa_sigstats_wait(vqa_ctx *ctx, vqa_sigstats_metrics *out, int n_entries, int profiles, uint64_t *profile_words,
+                              int64_t n_profile_words);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1608,7 +1698,13 @@ enum vqa_kernel_id {
     VQA_K_FSIM_MEDIAN = 59,  /* vqa_fsim_submit: the exact medians and the thresholds T_o (one entry per sub-slice)           */
     VQA_K_FSIM_PC = 60,      /* vqa_fsim_submit: PC and the p maps (one entry per sub-slice)                                  */
     VQA_K_FSIM_POOL = 61,    /* vqa_fsim_submit: Scharr, the similarities and the three words (one entry per sub-slice)       */
-    VQA_K_HEM = 62           /* one past the last id: ... VQA_K_PU21_ENCODE .. VQA_K_RIM - 1 and VQA_K_FSIM_LUMA .. VQA_K_HEM - 1 */
+    VQA_K_HEM = 62,          /* one past VQA_K_FSIM_POOL, as FSIM shipped it (kept at 62 for callers and tests that rely on id 62
+                                being unknown); id 62 stays unnamed                                                      */
+    VQA_K_SIGSTATS_ACCUM = 63, /* vqa_sigstats_submit: the histograms, sad, changed, the masks and the profiles (one entry per
+                                  group of same-geometry planes and sub-slice)                                           */
+    VQA_K_SIGSTATS_SCAN = 64,  /* vqa_sigstats_submit: every other word from the histograms and the profiles (one entry per
+                                  sub-slice)                                                                             */
+    VQA_K_FRINGE = 65        /* one past the last id: ... VQA_K_FSIM_LUMA .. VQA_K_HEM - 1 and VQA_K_SIGSTATS_ACCUM .. VQA_K_FRINGE - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

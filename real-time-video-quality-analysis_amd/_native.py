@@ -71,7 +71,9 @@ K_IDS_SUM = K_IDS_TOTAL + (K_ITP,)                # the ids below K_VERGE (kept 
 K_PU21_ENCODE, K_PU21_SSIM, K_RIM = 53, 54, 55    # added beyond K_VERGE, which stays 52; id 52 is unnamed
 K_IDS_GRAND = K_IDS_SUM + (K_PU21_ENCODE, K_PU21_SSIM)   # the ids below K_RIM (kept as PU21 shipped it)
 K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL, K_HEM = 56, 57, 58, 59, 60, 61, 62   # added beyond K_RIM, which stays 55; id 55 is unnamed
-K_IDS_ENTIRE = K_IDS_GRAND + (K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL)   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_ENTIRE = K_IDS_GRAND + (K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL)   # the ids below K_HEM (kept as FSIM shipped it)
+K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN, K_FRINGE = 63, 64, 65   # added beyond K_HEM, which stays 62; id 62 is unnamed
+K_IDS_COMPLETE = K_IDS_ENTIRE + (K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -111,6 +113,8 @@ FSIM_MIN_DIM = 16   # vqa_fsim_submit: plane 0's limit (the chroma planes of 4:2
 FSIM_MAX_GRID = 1024   # vqa_fsim_submit: the limit of either side of the downsampled grid
 FSIM_YUV709, FSIM_BGR, FSIM_GRAY = 0, 1, 2   # vqa_fsim_submit's colour models
 FSIM_FIX = 1 << 24  # vqa_fsim_metrics: p = rint(PC 2^24), g = rint(S_L 2^24)
+SIGSTATS_MIN_DIM = 16   # vqa_sigstats_submit: the limit of the family, whose planes it shares
+SIGSTATS_MAX_LEVEL = 65535   # vqa_sigstats_submit: the largest black_level and crop_level
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -245,6 +249,15 @@ class VqaFsimMetrics(C.Structure):
                 ("factor", C.c_int32), ("flags", C.c_uint32), ("fsim", C.c_double), ("fsimc", C.c_double)]
 
 
+class VqaSigstatsMetrics(C.Structure):
+    _fields_ = [("count", C.c_int64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32),
+                ("low", C.c_uint32), ("median", C.c_uint32), ("high", C.c_uint32), ("or_mask", C.c_uint32),
+                ("and_mask", C.c_uint32), ("bits_used", C.c_int32), ("below_black", C.c_uint64), ("under", C.c_uint64),
+                ("over_luma", C.c_uint64), ("over_chroma", C.c_uint64), ("above_peak", C.c_uint64), ("sad", C.c_uint64),
+                ("changed", C.c_uint64), ("top", C.c_int32), ("bottom", C.c_int32), ("left", C.c_int32), ("right", C.c_int32),
+                ("mean", C.c_double), ("stdev", C.c_double), ("dif", C.c_double)]
+
+
 class VqaHaarpsiMetrics(C.Structure):
     _fields_ = [("den", C.c_uint64), ("num_lo", C.c_uint64), ("num_hi", C.c_uint64), ("similarity", C.c_double),
                 ("haarpsi", C.c_double)]
@@ -327,6 +340,9 @@ SIGNATURES = {
     "vqa_fsim_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaFsimMetrics), C.c_int]),
     "vqa_fsim_noise_factor": (C.c_double, [C.c_int, C.c_int, C.c_int]),
     "vqa_fsim_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "vqa_sigstats_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int, C.c_int,
+                                      C.c_int]),
+    "vqa_sigstats_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaSigstatsMetrics), C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -61,6 +61,8 @@ enum batch_kind {
     KIND_ITP,         // ITP_WORDS per frame
     KIND_PU21,        // PU21_WORDS per frame; work: the two q_Y maps of one sub-slice; lab build: the maps of the whole last batch
     KIND_FSIM,        // FSIM_WORDS per frame; work: the intermediates and the p maps of one sub-slice; lab build: the maps of the whole last batch
+    KIND_SIGSTATS,    // SIGSTATS_WORDS per entry, then the row and column sums of every entry; work: the histograms of one sub-slice
+                      // (host frames and prev0: SI/TI's siti_stage, siti_prev)
     KIND_COUNT
 };
 
@@ -139,8 +141,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_HEM] = {0};
-    int64_t prof_n[VQA_K_HEM] = {0};
+    double prof_ms[VQA_K_FRINGE] = {0};
+    int64_t prof_n[VQA_K_FRINGE] = {0};
 };
 
 namespace {
@@ -2832,6 +2834,100 @@ int vqa_fsim_lab_read_maps(vqa_ctx *c, uint32_t *dst, int64_t n_values)
 #endif
 
 // ---------------------------------------------------------------------------
+// Signal statistics: one stream alone and the frame before each frame, every plane by itself.  A batch of its own, ordered by
+// the stream like an SI/TI batch, whose host staging (siti_stage, siti_prev) it shares.
+
+// the words of a frame's profile (the row sums, then the column sums, of every plane in order) and where each plane's start
+static int sigstats_profile(const int *w, const int *h, int n_planes, int off[4])
+{
+    int at = 0;
+    for (int p = 0; p < 4; p++) {
+        off[p] = at;
+        if (p < n_planes) at += h[p] + w[p];
+    }
+    return at;
+}
+
+static int sigstats_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *prev0, int mem_kind, int n, int64_t ref_fs,
+                                const vqa_plane_desc *planes, int n_planes, int black_level, int crop_level, bool &touched)
+{
+    if (bad_batch_args(c, ref, ref, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if (black_level > 65535 || crop_level > 65535) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_SIGSTATS];
+    dbuf &sig_hist = s.work[0];
+    plane_batch B;
+    int rc = check_batch(s, n, ref_fs, ref_fs, planes, n_planes, B, [&](const vqa_plane_desc &d) -> int {
+        if (int lim = side_and_area_limits(d, SIGSTATS_MIN_DIM)) return lim;
+        // sum_sq: 2^26 squares of 16-bit samples stay below 2^58 (vqa.h)
+        if (B.depth > 8 && (int64_t)d.width * d.height > (1ll << 26)) return VQA_ERR_UNSUPPORTED;
+        return VQA_OK;
+    });
+    if (rc) return rc;
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&ref, ref_fs, &c->siti_stage}, {}, {&prev0, 0, &c->siti_prev}))) return rc;
+    hipStream_t st = c->stream;
+    const int depth = B.depth, bins = sigstats_bins(depth);
+    const int black = black_level < 0 ? 32 << (depth - 8) : black_level, crop = crop_level < 0 ? 24 << (depth - 8) : crop_level;
+    int pw[4], ph[4], prof_off[4];
+    for (int p = 0; p < n_planes; p++) { pw[p] = planes[p].width; ph[p] = planes[p].height; }
+    const int prof_words = sigstats_profile(pw, ph, n_planes, prof_off);
+    const size_t nent = (size_t)n * n_planes;
+    const size_t acc_words = SIGSTATS_WORDS * nent, out_bytes = sizeof(unsigned long long) * (acc_words + (size_t)prof_words * n);
+    // the frames of one sub-slice: their histograms stay within SIGSTATS_HIST_BUDGET
+    const size_t frame_hist = sizeof(uint32_t) * (size_t)bins * n_planes, fit = SIGSTATS_HIST_BUDGET / frame_hist;
+    const int sub_frames = fit < (size_t)slice_frames(c, n) ? (int)fit : slice_frames(c, n);
+    if ((rc = ensure(c, s.dev, out_bytes))) return rc;
+    if ((rc = ensure(c, sig_hist, frame_hist * (size_t)sub_frames))) return rc;
+    if ((rc = ensure_pinned(c, s.host, out_bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, out_bytes, st));
+    unsigned long long *acc = (unsigned long long *)s.dev.p, *prof = acc + acc_words;
+    hipError_t set_err = hipSuccess;
+    for_each_slice(c, n, [&](int a0, int m) {
+        for (int b0 = 0; b0 < m; b0 += sub_frames) {
+            const int k = m - b0 < sub_frames ? m - b0 : sub_frames, at = a0 + b0;
+            const hipError_t e = hipMemsetAsync(sig_hist.p, 0, frame_hist * (size_t)k, st);
+            if (e != hipSuccess) set_err = e;
+            const uint8_t *sref = ref + (int64_t)at * ref_fs;
+            const uint8_t *sprev = at > 0 ? ref + (int64_t)(at - 1) * ref_fs : prev0;
+            unsigned long long *sacc = acc + (size_t)at * n_planes * SIGSTATS_WORDS, *sprof = prof + (size_t)at * prof_words;
+            for_each_group(planes, n_planes, [&](const int *idx, int cnt) {
+                prof_scope ps_(c, VQA_K_SIGSTATS_ACCUM);
+                launch_sigstats_accum(st, sref, sprev, k, ref_fs, planes, idx, cnt, n_planes, depth, prof_off, prof_words,
+                                      (uint32_t *)sig_hist.p, sacc, sprof);
+            });
+            prof_scope ps_(c, VQA_K_SIGSTATS_SCAN);
+            launch_sigstats_scan(st, k, planes, n_planes, depth, black, crop, prof_off, prof_words, (const uint32_t *)sig_hist.p,
+                                 sprof, sacc);
+        }
+    });
+    HIPCHK(c, set_err);
+    return finish_batch(c, s, out_bytes, (int)nent, planes, n_planes, depth);
+}
+
+int vqa_sigstats_submit(vqa_ctx *c, const uint8_t *frames, const uint8_t *prev0, int mem_kind, int n, int64_t frame_stride,
+                        const vqa_plane_desc *planes, int n_planes, int black_level, int crop_level)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return sigstats_submit_body(c, frames, prev0, mem_kind, n, frame_stride, planes, n_planes, black_level, crop_level, touched);
+    });
+}
+
+int vqa_sigstats_wait(vqa_ctx *c, vqa_sigstats_metrics *out, int n_entries, int profiles, uint64_t *profile_words,
+                      int64_t n_profile_words)
+{
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_SIGSTATS, out, n_entries, s)) return rc;
+    int off[4];
+    const int n = n_entries / s->planes, prof_words = sigstats_profile(s->w, s->h, s->planes, off);
+    if (profiles && (!profile_words || n_profile_words != (int64_t)prof_words * n)) return VQA_ERR_INVALID;   // (the batch stays pending)
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *acc = (const unsigned long long *)s->host.p, *prof = acc + (size_t)n_entries * SIGSTATS_WORDS;
+    for (int e = 0; e < n_entries; e++) sigstats_finalize(acc + (size_t)e * SIGSTATS_WORDS, s->depth, out + e);
+    if (profiles) memcpy(profile_words, prof, sizeof(uint64_t) * (size_t)prof_words * n);
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2841,7 +2937,7 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_HEM || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_FRINGE || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
@@ -2896,6 +2992,8 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_FSIM_MEDIAN) return "k_fsim_median";
     if (id == VQA_K_FSIM_PC) return "k_fsim_pc";
     if (id == VQA_K_FSIM_POOL) return "k_fsim_pool";
+    if (id == VQA_K_SIGSTATS_ACCUM) return "k_sigstats_accum";
+    if (id == VQA_K_SIGSTATS_SCAN) return "k_sigstats_scan";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -587,4 +587,29 @@ void launch_fsim(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n,
 // three words -> the record: the divisions of include/vqa.h in double, on the host (h x w: plane 0)
 void fsim_finalize(const unsigned long long *words, int h, int w, vqa_fsim_metrics *out);
 
+// Signal statistics (vqa_sigstats_submit): k_sigstats.hip
+constexpr int SIGSTATS_MIN_DIM = 16;   // the limit of the family, whose planes it shares
+// the words of an entry on the device, all uint64 (the four box words in two's complement): k_sigstats_scan stores the words up
+// to SIG_ABOVE_PEAK and the box, k_sigstats_accum adds or ORs the other four into words the submit has zeroed
+enum sigstats_word {
+    SIG_COUNT, SIG_SUM, SIG_SUM_SQ, SIG_MIN, SIG_MAX, SIG_LOW, SIG_MEDIAN, SIG_HIGH, SIG_BELOW_BLACK, SIG_UNDER, SIG_OVER_LUMA,
+    SIG_OVER_CHROMA, SIG_ABOVE_PEAK, SIG_OR, SIG_NAND /* the OR of ~x */, SIG_SAD, SIG_CHANGED, SIG_TOP, SIG_BOTTOM, SIG_LEFT,
+    SIG_RIGHT, SIGSTATS_WORDS
+};
+constexpr size_t SIGSTATS_HIST_BUDGET = (size_t)1 << 28;   // the histograms of a sub-slice of frames stay within 256 MiB
+// the bins of an entry's histogram: the sample TYPE's range, not the depth's
+inline int sigstats_bins(int depth) { return depth > 8 ? 65536 : 256; }
+// n frames of one group of same-geometry planes: the histograms hist[(frame * n_planes + plane) * bins ..], the words SIG_OR,
+// SIG_NAND, SIG_SAD, SIG_CHANGED of acc[(frame * n_planes + plane) * SIGSTATS_WORDS ..] and the row and column sums
+// prof[frame * prof_words + prof_off[plane] ..] (height row sums, then width column sums); the caller has zeroed all three
+void launch_sigstats_accum(hipStream_t st, const uint8_t *ref, const uint8_t *prev0, int n, int64_t frame_stride,
+                           const vqa_plane_desc *planes, const int *idx, int count, int n_planes, int depth,
+                           const int *prof_off, int prof_words, uint32_t *hist, unsigned long long *acc, unsigned long long *prof);
+// the remaining words of the n * n_planes entries from their histograms and profiles
+void launch_sigstats_scan(hipStream_t st, int n, const vqa_plane_desc *planes, int n_planes, int depth, int black_level,
+                          int crop_level, const int *prof_off, int prof_words, const uint32_t *hist,
+                          const unsigned long long *prof, unsigned long long *acc);
+// the words -> the record; mean, stdev and dif in double on the host (include/vqa.h)
+void sigstats_finalize(const unsigned long long *words, int depth, vqa_sigstats_metrics *out);
+
 } // namespace vqa

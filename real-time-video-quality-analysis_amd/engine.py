@@ -87,6 +87,13 @@ assert PU21_DTYPE.itemsize == C.sizeof(N.VqaPu21Metrics)
 FSIM_DTYPE = np.dtype([("sum_pc", np.uint64), ("sum_sim", np.uint64), ("sum_simc", np.uint64), ("count", np.int64),
                        ("factor", np.int32), ("flags", np.uint32), ("fsim", np.float64), ("fsimc", np.float64)], align=True)
 assert FSIM_DTYPE.itemsize == C.sizeof(N.VqaFsimMetrics) == 56
+SIGSTATS_DTYPE = np.dtype([("count", np.int64), ("sum", np.uint64), ("sum_sq", np.uint64), ("min", np.uint32), ("max", np.uint32),
+                           ("low", np.uint32), ("median", np.uint32), ("high", np.uint32), ("or_mask", np.uint32),
+                           ("and_mask", np.uint32), ("bits_used", np.int32), ("below_black", np.uint64), ("under", np.uint64),
+                           ("over_luma", np.uint64), ("over_chroma", np.uint64), ("above_peak", np.uint64), ("sad", np.uint64),
+                           ("changed", np.uint64), ("top", np.int32), ("bottom", np.int32), ("left", np.int32),
+                           ("right", np.int32), ("mean", np.float64), ("stdev", np.float64), ("dif", np.float64)], align=True)
+assert SIGSTATS_DTYPE.itemsize == C.sizeof(N.VqaSigstatsMetrics) == 152
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -107,6 +114,7 @@ _BATCHES = {
     "_pending_i": ("vqa_itp_submit", "vqa_itp_wait", ITP_DTYPE, N.VqaItpMetrics),   # (one entry per frame)
     "_pending_u": ("vqa_pu21_submit", "vqa_pu21_wait", PU21_DTYPE, N.VqaPu21Metrics),   # (one entry per frame)
     "_pending_f": ("vqa_fsim_submit", "vqa_fsim_wait", FSIM_DTYPE, N.VqaFsimMetrics),   # (one entry per frame)
+    "_pending_z": ("vqa_sigstats_submit", "vqa_sigstats_wait", SIGSTATS_DTYPE, N.VqaSigstatsMetrics),   # (one stream and the frame before it)
 }
 
 
@@ -359,13 +367,14 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
         for pend in list(_BATCHES) + ["_pending_c"]:
             try:
                 if getattr(self, pend, None):
-                    {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait}.get(pend, lambda: self._batch_wait(pend))()
+                    {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
+                     "_pending_z": self.sigstats_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1017,6 +1026,52 @@ class Engine:
         rec = self.fsim_wait()
         return (rec, self.fsim_maps()) if maps else rec
 
+    # ---- signal statistics --------------------------------------------------------
+    @staticmethod
+    def _sigstats_level(name, value):
+        """a level of sigstats_submit -> the C argument: None is the default (negative), else an integer 0 .. 65535"""
+        if value is None:
+            return -1
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= N.SIGSTATS_MAX_LEVEL:
+            raise ValueError("%s must be None or an integer from 0 to %d" % (name, N.SIGSTATS_MAX_LEVEL))
+        return int(value)
+
+    def sigstats_submit(self, frames, planes, prev0=None, black_level=None, crop_level=None, frame_bytes=None):
+        """Signal statistics for n frames of ONE stream (vqa_sigstats_submit): per plane the exact histogram's count, sum, sum of
+        squares, min, max, the 10 % / 50 % / 90 % order statistics, the level counts, the bit masks, the dark-border box, and sad /
+        changed of frame i against frame i - 1, frame 0 against prev0 (None: it has no predecessor and both are 0).  The
+        arguments of siti_submit; every plane at least 16 x 16, packed bgr24 included.  black_level, crop_level: None (32 and 24
+        on the 8-bit scale) or an integer 0 .. 65535 in sample units.  A batch of its own, like siti_submit."""
+        levels = self._sigstats_level("black_level", black_level), self._sigstats_level("crop_level", crop_level)
+        self._batch_submit("_pending_z", self._ref_args(frames, planes, prev0, frame_bytes), planes, *levels)
+        self._sigstats_sides = [(int(p[1]), int(p[0])) for p in planes]   # (h, w) of the pending batch
+
+    def sigstats_wait(self, profiles=False):
+        """-> [n, n_planes] records (SIGSTATS_DTYPE).  profiles=True: -> (records, sums) with the profiles behind them, sums = one
+        dict(rows as uint64 [n, h], cols as uint64 [n, w]) per plane: the row and column sums the box was read off."""
+        n, npl, _keep = self._pending_z
+        rec = np.zeros(n * npl, dtype=SIGSTATS_DTYPE)
+        words = np.zeros((n, sum(h + w for h, w in self._sigstats_sides)), np.uint64) if profiles else None
+        st = self.lib.vqa_sigstats_wait(self.ctx, rec.ctypes.data_as(C.POINTER(N.VqaSigstatsMetrics)), n * npl,
+                                        1 if profiles else 0, words.ctypes.data_as(C.POINTER(C.c_uint64)) if profiles else None,
+                                        words.size if profiles else 0)
+        self._pending_z = None
+        N.check(st, "vqa_sigstats_wait", self.ctx)
+        rec = rec.reshape(n, npl)
+        if not profiles:
+            return rec
+        sums, at = [], 0
+        for h, w in self._sigstats_sides:
+            sums.append(dict(rows=np.ascontiguousarray(words[:, at:at + h]), cols=np.ascontiguousarray(words[:, at + h:at + h + w])))
+            at += h + w
+        return rec, sums
+
+    def sigstats(self, frames, planes, prev0=None, black_level=None, crop_level=None, profiles=False, frame_bytes=None):
+        """Signal statistics per plane for n frames; returns [n, n_planes] structured array (SIGSTATS_DTYPE), with profiles=True
+        also the row and column sums (sigstats_wait)."""
+        self.sigstats_submit(frames, planes, prev0, black_level, crop_level, frame_bytes)
+        return self.sigstats_wait(profiles)
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -1024,7 +1079,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_ENTIRE:
+        for k in N.K_IDS_COMPLETE:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

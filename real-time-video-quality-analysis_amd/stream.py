@@ -35,7 +35,7 @@ import numpy as np
 from . import _native as N
 from . import tails
 from .engine import (ADM_DTYPE, ARTIFACTS_DTYPE, BRISQUE_DTYPE, CAMBI_DTYPE, CIEDE_DTYPE, FSIM_DTYPE, GMSD_DTYPE, HAARPSI_DTYPE,
-                     ITP_DTYPE, MDSI_DTYPE, MOTION_DTYPE, PSNR_HVS_DTYPE, PU21_DTYPE, SITI_DTYPE, VCA_DTYPE, VIF_DTYPE,
+                     ITP_DTYPE, MDSI_DTYPE, MOTION_DTYPE, PSNR_HVS_DTYPE, PU21_DTYPE, SIGSTATS_DTYPE, SITI_DTYPE, VCA_DTYPE, VIF_DTYPE,
                      XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_vca_planes, check_xpsnr_planes, vca_grid)
 from .pooling import shard_range
 
@@ -432,6 +432,13 @@ def _full_range(name, value):
     return value
 
 
+def _level(name, value):
+    if value is not None and (isinstance(value, bool) or not isinstance(value, (int, np.integer))
+                              or not 0 <= int(value) <= N.SIGSTATS_MAX_LEVEL):
+        raise ValueError("%s must be None or an integer from 0 to %d" % (name, N.SIGSTATS_MAX_LEVEL))
+    return None if value is None else int(value)
+
+
 # name      Quality's switch and attribute; Engine.<name>_submit / <name>_wait; the key of records_by_kind
 # label     how the "-only pass has no SSIM scales" message names the kind
 # reads     the chunk's frames the submit gets: "pair" (reference, distorted), "ref" (reference alone) or "dist" (the distorted
@@ -440,7 +447,8 @@ def _full_range(name, value):
 # halo      the submit also gets prev0, the reference frame before the chunk, after the planes
 # check     check(name, planes): the kind's rule on the plane list, a ValueError when the kind is on and the planes break it
 # params    (Quality keyword, check(keyword, value) -> value): validated whether the kind is on or not, kept as attributes and
-#           passed to the submit after the planes and a None colour model (= the one that follows from the planes)
+#           passed to the submit after the planes and a None colour model (= the one that follows from the planes); a kind
+#           with a halo has no colour model: its parameters follow prev0
 # whole     applied once to the whole clip's concatenated records
 # wait      Quality attributes passed to the wait
 PlaneKind = collections.namedtuple("PlaneKind", "name label reads dtype halo per_frame check params whole wait",
@@ -468,6 +476,8 @@ PLANE_KINDS = (
     PlaneKind("pu21", "a PU21-only", "pair", PU21_DTYPE, per_frame=True, check=_three_planes,
               params=(("pu21_transfer", _transfer), ("pu21_full_range", _full_range))),
     PlaneKind("fsim", "an FSIM-only", "pair", FSIM_DTYPE, per_frame=True, check=_one_plane_or_three),
+    PlaneKind("sigstats", "a sigstats-only", "ref", SIGSTATS_DTYPE, halo=True,
+              params=(("sigstats_black", _level), ("sigstats_crop", _level))),
 )
 
 
@@ -476,7 +486,7 @@ def _elements(on):
     vif, adm and motion form the tuple's head: vif has an element (None when it is off) as soon as one of the three is on, adm
     as soon as adm or motion is; every later kind has one when it is on."""
     head = 3 if on["motion"] else 2 if on["adm"] else 1 if on["vif"] else 0
-    return list(PLANE_KINDS[:head]) + [k for k in PLANE_KINDS[3:] if on[k.name]]
+    return list(PLANE_KINDS[:head]) + [k for k in PLANE_KINDS[3:] if on.get(k.name)]   # (a mapping names the kinds that are on)
 
 
 def _switches(quality):
@@ -500,7 +510,8 @@ class Quality:
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
                  haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
-                 itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False):
+                 itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False,
+                 sigstats=False, sigstats_black=None, sigstats_crop=None):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         Every other switch turns on one plane-batch kind (PLANE_KINDS) and is False, True or "only":
         True    every chunk also goes through the kind's kernels (Engine.<kind>_submit) from the SAME upload - the chunk was
@@ -528,18 +539,20 @@ class Quality:
         pu21      pair       [n]   the five integer words, windows, mse_y, mse_rgb, pu_psnr,          exactly three
                                    pu_psnr_rgb, pu_ssim
         fsim      pair       [n]   the three integer words, count, factor, flags, fsim, fsimc         one, or three together
+        sigstats  ref, halo  [n,p] SIGSTATS_DTYPE (levels, order statistics, masks, sad, the box)
 
         reads   pair: the chunk's reference and distorted frames.  ref: its REFERENCE frames alone.  dist: its frames of the
                 DISTORTED (encoded) stream alone.  halo: the submit also gets prev0, the last reference frame of the previous
                 chunk (the reference feed's halo slot; XPSNR needs it for the activity of the chunk's first frame, VCA for its
-                gradient).  A pass whose kinds read one stream - motion, siti, vca and, as "only", cambi, artifacts and brisque,
+                gradient, sigstats for sad and changed).  A pass whose kinds read one stream - motion, siti, vca, sigstats and, as "only", cambi, artifacts and brisque,
                 with nothing else that needs the pair - reads the `ref` stream alone: give it the frames to measure
         records [n,p]: one per frame and plane; [n]: one per frame, not per plane (the planes are taken together)
         vca_blocks=True: VCA's element is the pair (records, block maps: per plane dict(qh, s as uint64 [n, nby, nbx]))
         ciede_weights: (kL, kC, kH), default the CIE standard (1, 1, 1); the colour model follows from the planes' pixel step
                 (Engine.ciede_model)
         itp_transfer, pu21_transfer: "pq" | "hlg"; itp_full_range, pu21_full_range: False (limited) | True; the colour model
-                of both follows from the planes (Engine.itp_model), that of mdsi and fsim likewise (Engine.mdsi_model)"""
+                of both follows from the planes (Engine.itp_model), that of mdsi and fsim likewise (Engine.mdsi_model)
+        sigstats_black, sigstats_crop: None (32 and 24 on the 8-bit scale) or an integer 0 .. 65535 in sample units"""
         given = dict(locals())   # the keyword arguments by name, for the table
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
@@ -640,11 +653,11 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
                            motion=True three: the VIF records or None, the ADM records or None and the motion records [n,p]
                            (MOTION_PASS_DTYPE)
       every later kind     that is requested appends ONE element, in the order of PLANE_KINDS: siti, psnr_hvs, ciede, gmsd, cambi,
-                           xpsnr, haarpsi, vca, artifacts, brisque, mdsi, itp, pu21, fsim - its records [n,p], for ciede, mdsi,
+                           xpsnr, haarpsi, vca, artifacts, brisque, mdsi, itp, pu21, fsim, sigstats - its records [n,p], for ciede, mdsi,
                            itp, pu21 and fsim [n] (one per frame), of engine.<KIND>_DTYPE; with vca_blocks=True VCA's is the
                            pair (records, block maps)
     (records_by_kind names the elements.)  Quality's docstring has the table of the kinds: motion, siti and vca measure the
-    reference stream, cambi, artifacts and brisque the distorted one - as "only", in a pass that reads nothing else, they measure
+    reference stream (sigstats too), cambi, artifacts and brisque the distorted one - as "only", in a pass that reads nothing else, they measure
     `ref`, the only stream the pass reads then.
     series: kind -> list in the reference's sample order (motion/dct/hist/edge/orb/color: T-1 samples, temporal:
     T-2, complexity_metrics.py:268-290, :533-537) and "range" = the shard's place in the whole series.
@@ -701,7 +714,7 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
 def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series, n, batch_size, on_quality):
     want_q, want_c = quality is not None, complexity is not None
     feeds = {}
-    # motion, SI/TI, VCA, CAMBI, the artefact measures and BRISQUE alone read the reference stream only: the distorted stream is not even uploaded
+    # motion, SI/TI, VCA, sigstats, CAMBI, the artefact measures and BRISQUE alone read the reference stream only: the distorted stream is not even uploaded
     requested = [k for k in PLANE_KINDS if getattr(quality, k.name)] if want_q else []   # in submit order
     ref_only = (want_q and not want_c and not quality.ssim and not any(k.reads == "pair" for k in requested)
                 and not any(k.reads == "dist" and getattr(quality, k.name) is True for k in requested))
@@ -844,8 +857,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 # pass that reads one stream, that stream
                 streams = {"pair": pair[:2], "ref": pair[:1], "dist": pair[-1:]}
                 for kind in requested:
-                    more = ((prev0,) if kind.halo else ()) + (((None,) + tuple(getattr(quality, a) for a, _ in kind.params))
-                                                              if kind.params else ())
+                    values = tuple(getattr(quality, a) for a, _ in kind.params)
+                    # (a halo kind's parameters follow prev0; the others' follow a None colour model)
+                    more = (prev0,) + values if kind.halo else ((None,) + values if values else ())
                     getattr(eng, kind.name + "_submit")(*streams[kind.reads], quality.planes, *more)
                     p["sent"].append(kind)
             if want_c and p["j1"] > p["j0"]:

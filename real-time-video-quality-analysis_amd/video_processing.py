@@ -416,6 +416,23 @@ def frame_fsim(reference, encoded, layout="bgr24", height=None, width=None, engi
     return np.ascontiguousarray(r["fsim"]), np.ascontiguousarray(r["fsimc"])
 
 
+def frame_sigstats(frames, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None, black_level=None,
+                   crop_level=None):
+    """Per-frame signal statistics per plane of ANY stream (Engine.sigstats through the one-pass pipeline of frame_quality; the
+    stream is uploaded once, there is no second stream): the exact levels, order statistics, range counts, bit masks, the
+    difference to the frame before and the dark-border box, by the definition in include/vqa.h.  black_level, crop_level: None
+    (32 and 24 on the 8-bit scale) or integers in sample units.  Returns the records [n,p] (engine.SIGSTATS_DTYPE); frame 0 has
+    no predecessor.  events.signal_events turns them into black / frozen runs, cuts and the crop box.  Every plane at least
+    16 x 16."""
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, sigstats="only", sigstats_black=black_level,
+                                                             sigstats_crop=crop_level),
+                      batch_size=batch_size, engine=engine, device=device)
+    return q[-1]
+
+
 PU21_PSNR_CAP = 100.0   # the row's PU_PSNR and PU_PSNR_RGB: a frame's value (inf for identical frames) is capped here before pooling
 
 
@@ -431,7 +448,7 @@ def _brisque_model(model_path, range_path):
 
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
                   cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None,
-                  delta_itp=None, pu21=None, fsim=None):
+                  delta_itp=None, pu21=None, fsim=None, sigstats=None, sigstats_depth=8):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -471,6 +488,11 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     and before vmaf, likewise.  The model never reads them.
     fsim: None, or the FSIM records [n] (engine.FSIM_DTYPE, one per frame): the log then also carries fsim and fsimc, after pu_ssim
     and before vmaf, likewise.  The model never reads them.
+    sigstats: None, or the first plane's signal statistics [n] (engine.SIGSTATS_DTYPE) of the reference stream, whose samples have
+    sigstats_depth bits: the log then also carries y_min, y_low, y_avg, y_high, y_max, y_dif, out_of_range ((under + over_luma) /
+    N), black, frozen (0 or 1) and scene_score (events.signal_events at its defaults), after fsimc and before vmaf, likewise, and
+    next to "frames" and "pooled_metrics" an object "signal": black_frames, frozen_frames, scene_cuts (counts) and crop ([top,
+    bottom, left, right] over the frames that are not black, null when all are).  The model never reads them.
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -548,6 +570,18 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         fsim = np.asarray(fsim).reshape(-1)
         names += ["fsim", "fsimc"]
         cols += [fsim["fsim"].astype(np.float64), fsim["fsimc"].astype(np.float64)]
+    signal = None
+    if sigstats is not None:
+        from . import events
+        sigstats = np.asarray(sigstats).reshape(-1)
+        ev = events.signal_events(sigstats, sigstats_depth)
+        count = sigstats["count"].astype(np.float64)
+        names += ["y_min", "y_low", "y_avg", "y_high", "y_max", "y_dif", "out_of_range", "black", "frozen", "scene_score"]
+        cols += [sigstats[k].astype(np.float64) for k in ("min", "low", "mean", "high", "max", "dif")]
+        cols += [(sigstats["under"].astype(np.float64) + sigstats["over_luma"].astype(np.float64)) / count,
+                 ev["black"].astype(np.float64), ev["frozen"].astype(np.float64), ev["scene_score"]]
+        signal = {"black_frames": int(ev["black"].sum()), "frozen_frames": int(ev["frozen"].sum()),
+                  "scene_cuts": len(ev["cuts"]), "crop": None if ev["crop"] is None else list(ev["crop"])}
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -562,7 +596,10 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
             pooled[k] = {"min": float(x.min()), "max": float(x.max()), "mean": float(x.mean()),
                          "harmonic_mean": float(len(x) / np.sum(1.0 / (x + 1.0)) - 1.0)}
     with open(vmaf_log, "w") as f:
-        json.dump({"frames": frames, "pooled_metrics": pooled}, f, indent=1)
+        doc = {"frames": frames, "pooled_metrics": pooled}
+        if signal is not None:
+            doc["signal"] = signal
+        json.dump(doc, f, indent=1)
         f.write("\n")
 
 
@@ -672,7 +709,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
                        brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
-                       pu21_full_range=False, fsim=False):
+                       pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -711,6 +748,9 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     False (limited) | True; a model file does not turn it on).
     fsim=True: likewise FSIM and FSIMc of the planes taken together (fsim and fsimc, one value each per frame; one- and three-plane
     layouts; a model file does not turn it on).
+    sigstats=True: likewise the signal statistics of the REFERENCE stream - the source SI/TI and VCA describe too - from the same
+    upload (y_min .. scene_score of the first plane and the "signal" object, write_vif_log; sigstats_black, sigstats_crop: None or
+    the black and the dark-border level in sample units; a model file does not turn it on).
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -745,7 +785,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                 raise ValueError("pu21 needs three planes")
             _check_pu21(pu21_transfer, pu21_full_range)
         if any((vif, adm, motion, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, mdsi, delta_itp, pu21,
-                fsim)):
+                fsim, sigstats)):
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
             if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
@@ -760,10 +800,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              itp_transfer=delta_itp_transfer,
                                                              itp_full_range=delta_itp_full_range, pu21=bool(pu21),
                                                              pu21_transfer=pu21_transfer,
-                                                             pu21_full_range=pu21_full_range, fsim=bool(fsim)),
+                                                             pu21_full_range=pu21_full_range, fsim=bool(fsim),
+                                                             sigstats=bool(sigstats), sigstats_black=sigstats_black,
+                                                             sigstats_crop=sigstats_crop),
                               batch_size=batch_size, on_quality=wr, device=device)
             _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts, brisque, bmodel, mdsi, delta_itp, pu21, fsim)
+                               artifacts, brisque, bmodel, mdsi, delta_itp, pu21, fsim, sigstats, layout_depth(layout))
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -802,17 +844,20 @@ MODE_KEYS = {
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
                        cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
-                       mdsi=False, delta_itp=False, pu21=False, fsim=False):
+                       mdsi=False, delta_itp=False, pu21=False, fsim=False, sigstats=False, sigstats_depth=8):
     """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and
-    noise / BRISQUE and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (stream.run's quality tuple, whose
+    noise / BRISQUE / signal statistics and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (stream.run's quality tuple, whose
     elements stream.records_by_kind names) -> vmaf_log"""
     on = dict(vif=vif, adm=adm, motion=motion, siti=siti, psnr_hvs=psnr_hvs, ciede=ciede, gmsd=gmsd, cambi=cambi, xpsnr=xpsnr,
-              haarpsi=haarpsi, vca=vca, artifacts=artifacts, brisque=brisque, mdsi=mdsi, itp=delta_itp, pu21=pu21, fsim=fsim)
+              haarpsi=haarpsi, vca=vca, artifacts=artifacts, brisque=brisque, mdsi=mdsi, itp=delta_itp, pu21=pu21, fsim=fsim,
+              sigstats=sigstats)
     rec = stream.records_by_kind(q, on)
     # write_vif_log's keywords (the kinds' names but for dE_ITP's): the per-plane kinds' first plane, the per-frame kinds' records
     log = {{"itp": "delta_itp"}.get(k.name, k.name): rec[k.name] if k.per_frame else rec[k.name][:, 0]
            for k in stream.PLANE_KINDS if on[k.name]}
     scale = log.pop("vif")["scale"] if vif else None
+    if sigstats:
+        log["sigstats_depth"] = sigstats_depth
     write_vif_log(vmaf_log, scale, log.pop("adm", None), model=model if motion else None, brisque_model=brisque_model, **log)
 
 
@@ -867,6 +912,12 @@ def _check_mode_keys(config):
         raise ValueError("delta_itp_range must be \"limited\" or \"full\".")
     if "fsim" in config and not isinstance(config["fsim"], bool):
         raise ValueError("fsim must be true or false.")
+    if "sigstats" in config and not isinstance(config["sigstats"], bool):
+        raise ValueError("sigstats must be true or false.")
+    for key in ("sigstats_black", "sigstats_crop"):
+        v = config.get(key)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= N.SIGSTATS_MAX_LEVEL):
+            raise ValueError("%s must be null or an integer from 0 to %d." % (key, N.SIGSTATS_MAX_LEVEL))
     if "pu21" in config and not isinstance(config["pu21"], bool):
         raise ValueError("pu21 must be true or false.")
     if "pu21_transfer" in config and not (isinstance(config["pu21_transfer"], str) and
@@ -955,6 +1006,12 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         fsim (true: the row gains FSIM and FSIMC, the pooled means of the per-frame feature similarity index of the luminance and of
         its colour form, the planes taken together, after PU_SSIM; one- and three-plane pixfmts; default false; a model file does
         not turn it on),
+        sigstats (true: the row gains, after FSIMC and from the INPUT stream's first plane, Y_LOW - the minimum over the frames of
+        the 10 % order statistic -, Y_HIGH - the maximum of the 90 % one -, OUT_OF_RANGE - the mean share of samples below 16 s or
+        above 235 s -, BLACK_FRAMES, FROZEN_FRAMES and SCENE_CUTS - counts of frames, events.signal_events at its defaults - and
+        CROP_TOP, CROP_BOTTOM, CROP_LEFT, CROP_RIGHT, the union box over the frames that are not black, -1 each when all are;
+        default false; a model file does not turn it on), sigstats_black and sigstats_crop (null or 0 .. 65535: the black and the
+        dark-border level in sample units; default 32 and 24 on the 8-bit scale),
         pixfmt (None: by input | "bgr24" | "yuv420p" | "gray" | FFmpeg's other planar names: yuv422p, yuv444p, yuv420p10le,
         yuv422p10le, yuv444p10le, the 12-bit three, yuv420p16le, yuv444p16le, gray10le, gray12le, gray16le - uint16
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
@@ -995,6 +1052,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     pu_tf = config.get("pu21_transfer", "pq")
     pu_full = ITP_RANGES[config.get("pu21_range", "limited")]
     fsm = config.get("fsim", False)
+    sig, sig_black, sig_crop = config.get("sigstats", False), config.get("sigstats_black"), config.get("sigstats_crop")
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -1054,14 +1112,16 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                                      haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq,
                                                                      mdsi=mds, itp=itp, itp_transfer=itp_tf,
                                                                      itp_full_range=itp_full, pu21=pu,
-                                                                     pu21_transfer=pu_tf, pu21_full_range=pu_full, fsim=fsm),
+                                                                     pu21_transfer=pu_tf, pu21_full_range=pu_full, fsim=fsm,
+                                                                     sigstats=sig, sigstats_black=sig_black,
+                                                                     sigstats_crop=sig_crop),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if any((vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itp, pu, fsm)):
+        if any((vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itp, pu, fsm, sig)):
             _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
-                               mds, itp, pu, fsm)
+                               mds, itp, pu, fsm, sig, layout_depth(layout))
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -1099,9 +1159,10 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         import json
         try:
             with open(vmaf_log) as f:
-                pooled = json.load(f).get("pooled_metrics", {})
+                doc = json.load(f)
+            pooled, signal = doc.get("pooled_metrics", {}), doc.get("signal")
         except (ValueError, AttributeError):   # not a JSON log (libvmaf writes XML by default): nothing to add
-            pooled = {}
+            pooled, signal = {}, None
         if "vmaf" in pooled:       # (:172-173), placed where the reference puts it: right after SSIM
             metrics["VMAF"] = float(pooled["vmaf"]["mean"])
         for s in range(N.VIF_LEVELS):
@@ -1154,6 +1215,16 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         if "fsim" in pooled:
             metrics["FSIM"] = float(pooled["fsim"]["mean"])
             metrics["FSIMC"] = float(pooled["fsimc"]["mean"])
+        if "y_low" in pooled and signal is not None:   # the source's signal statistics: extremes, a mean share and event counts
+            metrics["Y_LOW"] = float(pooled["y_low"]["min"])
+            metrics["Y_HIGH"] = float(pooled["y_high"]["max"])
+            metrics["OUT_OF_RANGE"] = float(pooled["out_of_range"]["mean"])
+            metrics["BLACK_FRAMES"] = int(signal["black_frames"])
+            metrics["FROZEN_FRAMES"] = int(signal["frozen_frames"])
+            metrics["SCENE_CUTS"] = int(signal["scene_cuts"])
+            crop = signal["crop"] if signal["crop"] is not None else (-1, -1, -1, -1)
+            for k, v in zip(("CROP_TOP", "CROP_BOTTOM", "CROP_LEFT", "CROP_RIGHT"), crop):
+                metrics[k] = int(v)
     return metrics
 
 
@@ -1176,7 +1247,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range, pu21, pu21_transfer, pu21_range, fsim;
+    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range, pu21, pu21_transfer, pu21_range, fsim, sigstats, sigstats_black, sigstats_crop;
     #                           and that a vmaf_model_path names a readable file
 
 
