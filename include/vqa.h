@@ -1606,6 +1606,64 @@ VQA_API int vqa_sigstats_submit(vqa_ctx *ctx, const uint8_t *frames, const uint8
 VQA_API int vqa_sigstats_wait(vqa_ctx *ctx, vqa_sigstats_metrics *out, int n_entries, int profiles, uint64_t *profile_words,
                               int64_t n_profile_words);
 
+/* ---- The resampler: the distorted stream of a ladder rung brought to the reference's size on the device, what
+ * `[dist]scale=1920:1080:flags=bicubic` does before libvmaf in an FFmpeg graph - so a 360p, 540p or 720p encode is uploaded at its
+ * own size and every kind above measures it at the source's ----
+ * It is Pillow's Image.resize for 8-bit images, an exact fixed-point algorithm, carried unchanged to 9..16 bits.  Where this text
+ * differs from a tool's detail, this text is what is built.
+ * Plane i of src_planes is resampled into plane i of dst_planes, each plane by itself, the horizontal pass first and the vertical
+ * pass second.
+ * Tables, per axis, with `in` source samples, `out` destination samples, scale = in / out, fs = max(scale, 1), S the filter's
+ *   support: support = S fs; ksize = 2 ceil(support) + 1; for output x the centre is c = (x + 0.5) scale,
+ *   xmin = max(0, (int)(c - support + 0.5)), xmax = min(in, (int)(c + support + 0.5)), count = xmax - xmin; the weights are
+ *   w_j = f((j + xmin - c + 0.5) / fs), j = 0 .. count - 1, added in index order and each divided by that sum (a window that runs
+ *   off the plane is cut and renormalised: nothing is mirrored or padded); each weight is quantised ONCE,
+ *   k_j = (int)(w_j 2^22 + 0.5), or - 0.5 for a negative weight, the conversion truncating towards zero (Pillow's
+ *   normalize_coeffs_8bpc).  All of it in double, in the order written, without contraction.  vqa_scale_tables builds them.
+ * Filters: VQA_SCALE_BILINEAR, S = 1, the triangle 1 - |x|; VQA_SCALE_BICUBIC, S = 2, Keys' cubic with a = -0.5 written as Pillow
+ *   writes it, ((a + 2) x - (a + 3)) x x + 1 for |x| < 1 and (((x - 5) x + 8) x - 4) a for |x| < 2; VQA_SCALE_LANCZOS, S = 3,
+ *   sinc(x) sinc(x / 3) on [-3, 3) with sinc(x) = sin(pi x) / (pi x), sinc(0) = 1.
+ * Passes: out = clip((2^21 + sum_j k_j in[xmin + j]) >> 22, 0, peak), an arithmetic shift, peak = 2^depth - 1.  The horizontal
+ *   pass is clipped and stored at the sample type before the vertical pass reads it, as Pillow does at 8 bits.  For uint8
+ *   samples the sums fit 32 bits (255 sum |k| < 2^31); for uint16 samples they are 64-bit.  An axis whose size does not change is
+ *   copied, not filtered (its tables are the identity in any case): a copied horizontal axis hands the samples to the vertical
+ *   pass as they are, above peak included; what leaves the vertical pass, copied or filtered, is clipped to peak.
+ * Consequences: a flat plane stays flat at every level, 0 and peak included (a row of k misses 2^22 by at most ksize / 2 units,
+ *   far below what moves the floor of (2^21 + v sum k) 2^-22); the output at depth d never exceeds 2^d - 1, even where the input
+ *   did.  Against Pillow: equal at every sample in mode L; in mode I;16 Pillow filters in double, so the two differ by at most
+ *   one unit a pass where no pass leaves 0 .. 65535 - where one does, Pillow saturates the high byte only and this text clips.
+ * Chroma is resampled over its own grid with the same centres, i.e. it is centre-sited.
+ * Limits: 1 .. 4 planes, the same count and one depth (8, or 9 .. 16) in both lists; every plane of both lists at least 16 x 16
+ *   with h w <= 2^28; per axis 1/4 <= out / in <= 8, so ksize <= 25: VQA_ERR_UNSUPPORTED beyond any of these (and for 8-bit planes
+ *   whose tables had a row with 255 sum |k| + 2^21 >= 2^31: none is known, the submit checks the tables it builds).  pixel_step > 1
+ *   works on either side (packed bgr24 is three planes).  An unknown filter, a dst that is not device memory of the ctx's
+ *   device, and a destination range [dst, dst + (n - 1) dst_frame_stride + the span of dst_planes) that overlaps the source
+ *   frames are VQA_ERR_INVALID.  The bytes of dst that no destination sample covers (row and frame padding) are not written.
+ * frames: host, pinned or device memory, like vqa_cambi_submit; host frames are staged in a buffer of this kind's own.
+ * A scale batch is a batch of its own (no result words): asynchronous on the ctx's stream, VQA_ERR_STATE while one is pending,
+ *   in flight next to every other kind; a failed submit leaves nothing in flight; more than 32768 frames go out in slices.
+ *   Every submit of any kind on the SAME ctx that follows reads dst after the resampler has written it - the stream orders them;
+ *   no wait is needed in between.  vqa_scale_wait returns when dst is complete (another ctx, or the host, may then read it).
+ * The kernel has no atomics and no reduction: the same frame gives the same bytes at any place of any batch, from any memory.
+ * Kernel: k_scale, one fused launch per group of planes alike on both sides; the intermediate of the horizontal pass lives in
+ *   shared memory only.  The tables sit in device memory per (filter, in, out), cached like the other per-geometry tables.
+ * Not built: swscale's bicubic (a = -0.6) and its other flags; left-sited (MPEG-2) chroma; conversion between chroma layouts or
+ *   depths; scaling the reference; ratios beyond 1/4 .. 8.                                                                  */
+enum vqa_scale_filter {
+    VQA_SCALE_BILINEAR = 0,
+    VQA_SCALE_BICUBIC = 1,
+    VQA_SCALE_LANCZOS = 2
+};
+VQA_API int vqa_scale_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                             const vqa_plane_desc *src_planes, uint8_t *dst, int64_t dst_frame_stride,
+                             const vqa_plane_desc *dst_planes, int n_planes, int filter);
+VQA_API int vqa_scale_wait(vqa_ctx *ctx);
+/* One axis' tables on the host.  *ksize receives the row length of k (at most 25); with k, xmin and count all non-NULL they
+ * receive k[out][ksize] (0 past count), xmin[out] and count[out]; all three NULL asks for ksize alone.  An unknown filter, a
+ * non-positive size, ksize == NULL or some but not all of the arrays: VQA_ERR_INVALID; a ratio beyond 1/4 .. 8:
+ * VQA_ERR_UNSUPPORTED.  in == out gives the formula's tables, which are the identity.                                         */
+VQA_API int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int32_t *count, int *ksize);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1704,7 +1762,11 @@ enum vqa_kernel_id {
                                   group of same-geometry planes and sub-slice)                                           */
     VQA_K_SIGSTATS_SCAN = 64,  /* vqa_sigstats_submit: every other word from the histograms and the profiles (one entry per
                                   sub-slice)                                                                             */
-    VQA_K_FRINGE = 65        /* one past the last id: ... VQA_K_FSIM_LUMA .. VQA_K_HEM - 1 and VQA_K_SIGSTATS_ACCUM .. VQA_K_FRINGE - 1 */
+    VQA_K_FRINGE = 65,       /* one past VQA_K_SIGSTATS_SCAN, as the signal statistics shipped it (kept at 65 for callers and
+                                tests that rely on id 65 being unknown); id 65 stays unnamed                             */
+    VQA_K_SCALE = 66,        /* vqa_scale_submit: both passes of the resampler, fused (one entry per group of planes alike on
+                                both sides)                                                                              */
+    VQA_K_MARGIN = 67        /* one past the last id: ... VQA_K_SIGSTATS_ACCUM .. VQA_K_FRINGE - 1 and VQA_K_SCALE .. VQA_K_MARGIN - 1 */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

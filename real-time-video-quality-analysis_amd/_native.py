@@ -73,7 +73,9 @@ K_IDS_GRAND = K_IDS_SUM + (K_PU21_ENCODE, K_PU21_SSIM)   # the ids below K_RIM (
 K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL, K_HEM = 56, 57, 58, 59, 60, 61, 62   # added beyond K_RIM, which stays 55; id 55 is unnamed
 K_IDS_ENTIRE = K_IDS_GRAND + (K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL)   # the ids below K_HEM (kept as FSIM shipped it)
 K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN, K_FRINGE = 63, 64, 65   # added beyond K_HEM, which stays 62; id 62 is unnamed
-K_IDS_COMPLETE = K_IDS_ENTIRE + (K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN)   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_COMPLETE = K_IDS_ENTIRE + (K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN)   # the ids below K_FRINGE (kept as the signal statistics shipped it)
+K_SCALE, K_MARGIN = 66, 67                        # added beyond K_FRINGE, which stays 65; id 65 is unnamed
+K_IDS_PRESENT = K_IDS_COMPLETE + (K_SCALE,)       # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -115,6 +117,12 @@ FSIM_YUV709, FSIM_BGR, FSIM_GRAY = 0, 1, 2   # vqa_fsim_submit's colour models
 FSIM_FIX = 1 << 24  # vqa_fsim_metrics: p = rint(PC 2^24), g = rint(S_L 2^24)
 SIGSTATS_MIN_DIM = 16   # vqa_sigstats_submit: the limit of the family, whose planes it shares
 SIGSTATS_MAX_LEVEL = 65535   # vqa_sigstats_submit: the largest black_level and crop_level
+SCALE_MIN_DIM = 16   # vqa_scale_submit: the limit of the family, on both sides
+SCALE_BILINEAR, SCALE_BICUBIC, SCALE_LANCZOS = 0, 1, 2   # vqa_scale_submit's filters
+SCALE_FILTERS = {"bilinear": SCALE_BILINEAR, "bicubic": SCALE_BICUBIC, "lanczos": SCALE_LANCZOS}
+SCALE_BITS = 22      # the tables are integers in 2^-22 fixed point
+SCALE_MAX_DOWN, SCALE_MAX_UP = 4, 8   # per axis 1/4 <= out / in <= 8
+SCALE_MAX_SAMPLES = 1 << 28   # h w of every plane of both lists
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -343,6 +351,11 @@ SIGNATURES = {
     "vqa_sigstats_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int, C.c_int,
                                       C.c_int]),
     "vqa_sigstats_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaSigstatsMetrics), C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
+    "vqa_scale_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_void_p, C.c_int64,
+                                   C.POINTER(VqaPlaneDesc), C.c_int, C.c_int]),
+    "vqa_scale_wait": (C.c_int, [C.c_void_p]),
+    "vqa_scale_tables": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int)]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

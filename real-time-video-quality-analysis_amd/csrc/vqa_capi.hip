@@ -37,6 +37,13 @@ struct resize_tabs {
     int mode = 0;
 };
 
+// one axis of the resampler (k_scale.hip) on the device, and the widest source footprint of a destination tile along it
+struct scale_tabs {
+    int32_t *k = nullptr, *xmin = nullptr, *count = nullptr;
+    int ksize = 0, span_w = 0, span_h = 0;   // the footprint of SCALE_TILE_W / SCALE_TILE_H consecutive outputs
+    int64_t abs_sum = 0;                     // the largest sum |k| of a row
+};
+
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // The plane-batch kinds: each has one batch_slot in the ctx, and a batch of one kind can be pending next to a batch of every
@@ -63,6 +70,7 @@ enum batch_kind {
     KIND_FSIM,        // FSIM_WORDS per frame; work: the intermediates and the p maps of one sub-slice; lab build: the maps of the whole last batch
     KIND_SIGSTATS,    // SIGSTATS_WORDS per entry, then the row and column sums of every entry; work: the histograms of one sub-slice
                       // (host frames and prev0: SI/TI's siti_stage, siti_prev)
+    KIND_SCALE,       // no result words: the batch writes the caller's dst (host frames: scale_stage)
     KIND_COUNT
 };
 
@@ -114,6 +122,7 @@ struct vqa_ctx {
     // the two streams of a pair submit, and the one stream of a one-stream submit in qstage_dist; the reference stream and its
     // prev0 of a motion submit; the same of an SI/TI or a VCA submit; prev0 of an XPSNR submit
     dbuf qstage_ref, qstage_dist, mot_stage, mot_prev, siti_stage, siti_prev, xpsnr_prev;
+    dbuf scale_stage;   // the host frames of a scale submit: its own, so the frames it reads outlive every pair staged after it
     // the plane-batch kinds: results, work buffers and the batch in flight
     batch_slot slot[KIND_COUNT];
 
@@ -123,6 +132,7 @@ struct vqa_ctx {
     std::map<int, cached<float *>> dct_mats;
     std::map<std::pair<int, int>, cached<fsim_tabs>> fsim_tables;   // k_fsim.hip: DFT matrices, filter bank and noise factors per grid (hd, wd)
     std::map<int, cached<dct_fft_plan>> fft_plans;  // k_dct_fft.hip: twiddle / post-twiddle tables per transform length
+    std::map<std::tuple<int, int, int>, cached<scale_tabs>> scale_tables;   // k_scale.hip: one axis' tables per (filter, in, out)
     uint64_t cache_clock = 0;
     int dct_wave_slots = 0;                 // wave slots of THIS device for the marching DCT's chunking (set in vqa_create)
     dbuf fb_tmp, fb_blur, fb_img, fb_R, fb_M, fb_flow0, fb_flow1, fb_part;
@@ -141,8 +151,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_FRINGE] = {0};
-    int64_t prof_n[VQA_K_FRINGE] = {0};
+    double prof_ms[VQA_K_MARGIN] = {0};
+    int64_t prof_n[VQA_K_MARGIN] = {0};
 };
 
 namespace {
@@ -311,6 +321,7 @@ static void free_table(fb_resize_tabs &t)
     if (t.sy) (void)hipFree(t.sy);
 }
 static void free_table(float *&m) { (void)hipFree(m); }
+static void free_table(scale_tabs &t) { (void)hipFree(t.k); (void)hipFree(t.xmin); (void)hipFree(t.count); }
 static void free_table(fsim_tabs &t) { (void)hipFree(t.wh); (void)hipFree(t.ww); (void)hipFree(t.filt); }
 static void free_table(dct_fft_plan &P) { (void)hipFree((void *)P.tw); (void)hipFree((void *)P.post); }
 
@@ -387,6 +398,37 @@ static int get_tabs(vqa_ctx *c, int h, int w, int rh, int rw, resize_tabs &out)
     if ((rc = cache_put(c, c->tabs, key, t))) return rc;
     tb.commit();
     out = t;
+    return VQA_OK;
+}
+
+// one axis of the resampler: the tables of include/vqa.h (vqa_scale_submit); an axis whose size does not change is a copy
+static int get_scale_tabs(vqa_ctx *c, int filter, int in, int out, scale_tabs &res)
+{
+    auto key = std::make_tuple(filter, in, out);
+    if (cache_get(c, c->scale_tables, key, res)) return VQA_OK;
+    scale_tabs t;
+    t.ksize = in == out ? 1 : scale_ksize(filter, in, out);
+    std::vector<int32_t> k((size_t)out * t.ksize), xmin(out), count(out);
+    if (in == out) {
+        for (int x = 0; x < out; x++) { k[x] = 1 << SCALE_BITS; xmin[x] = x; count[x] = 1; }
+    } else {
+        scale_build_axis(filter, in, out, k.data(), xmin.data(), count.data());
+    }
+    for (int x = 0; x < out; x++) {
+        int64_t a = 0;
+        for (int j = 0; j < t.ksize; j++) a += std::abs((int64_t)k[(size_t)x * t.ksize + j]);
+        t.abs_sum = a > t.abs_sum ? a : t.abs_sum;
+    }
+    t.span_w = scale_footprint(xmin.data(), count.data(), out, SCALE_TILE_W);
+    t.span_h = scale_footprint(xmin.data(), count.data(), out, SCALE_TILE_H);
+    table_builder tb(c);
+    int rc;
+    if ((rc = tb.upload(&t.k, k.data(), sizeof(int32_t) * k.size()))) return rc;
+    if ((rc = tb.upload(&t.xmin, xmin.data(), sizeof(int32_t) * out))) return rc;
+    if ((rc = tb.upload(&t.count, count.data(), sizeof(int32_t) * out))) return rc;
+    if ((rc = cache_put(c, c->scale_tables, key, t))) return rc;
+    tb.commit();
+    res = t;
     return VQA_OK;
 }
 
@@ -903,7 +945,7 @@ static void release_scratch(vqa_ctx *c)
     dbuf *bufs[] = {&c->gray_full, &c->planeA, &c->planeB, &c->state, &c->res_dev, &c->partials, &c->tile_flags,
                     &c->dirty0, &c->dirty1, &c->again_dev, &c->stage_frames, &c->stage_prev, &c->dct_scratch,
                     &c->dct_pe, &c->dct_pt, &c->qpartials, &c->qms_pyr, &c->qms_dev, &c->qstage_ref, &c->qstage_dist,
-                    &c->mot_stage, &c->mot_prev, &c->siti_stage, &c->siti_prev, &c->xpsnr_prev, &c->fb_tmp, &c->fb_blur,
+                    &c->mot_stage, &c->mot_prev, &c->siti_stage, &c->siti_prev, &c->xpsnr_prev, &c->scale_stage, &c->fb_tmp, &c->fb_blur,
                     &c->fb_img, &c->fb_R, &c->fb_M, &c->fb_flow0, &c->fb_flow1, &c->fb_part};
     for (dbuf *b : bufs) release(*b);
     for (batch_slot &s : c->slot) {   // everything a plane-batch kind owns
@@ -918,6 +960,8 @@ static void release_scratch(vqa_ctx *c)
     for (auto &kv : c->dct_mats) free_table(kv.second.v);
     for (auto &kv : c->fft_plans) free_table(kv.second.v);
     for (auto &kv : c->fsim_tables) free_table(kv.second.v);
+    for (auto &kv : c->scale_tables) free_table(kv.second.v);
+    c->scale_tables.clear();
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear(); c->fsim_tables.clear();
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
@@ -2928,6 +2972,124 @@ int vqa_sigstats_wait(vqa_ctx *c, vqa_sigstats_metrics *out, int n_entries, int 
 }
 
 // ---------------------------------------------------------------------------
+// The resampler: one stream, plane i of the source list into plane i of the destination list in the caller's device memory.
+// A batch of its own with no result words, ordered by the stream like every other kind - so whatever the ctx is handed next
+// reads dst after it has been written.  Host frames are staged in scale_stage.
+
+// the memory `p` points into is device memory of the ctx's device
+static bool byte_is_on_device(const vqa_ctx *c, const void *p)
+{
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof a);
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice && a.device == c->device;
+}
+
+static int scale_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
+                             uint8_t *dst, int64_t dst_fs, const vqa_plane_desc *dplanes, int n_planes, int filter, bool &touched)
+{
+    if (bad_batch_args(c, frames, dst, mem_kind, n, planes, n_planes) || !dplanes) return VQA_ERR_INVALID;
+    if (!scale_filter_known(filter)) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_SCALE];
+    plane_batch B, D;
+    auto limits = [](const vqa_plane_desc &d) { return side_and_area_limits(d, SCALE_MIN_DIM); };
+    int rc = check_batch(s, n, fs, fs, planes, n_planes, B, limits);
+    if (rc) return rc;
+    if ((rc = check_planes(dplanes, n_planes, D, limits))) return rc;
+    if (D.depth != B.depth) return VQA_ERR_UNSUPPORTED;
+    if (n > 1 && dst_fs < D.span) return VQA_ERR_INVALID;
+    for (int p = 0; p < n_planes; p++)
+        if (!scale_ratio_ok(planes[p].width, dplanes[p].width) || !scale_ratio_ok(planes[p].height, dplanes[p].height))
+            return VQA_ERR_UNSUPPORTED;
+    const int64_t dst_bytes = (int64_t)(n - 1) * dst_fs + D.span, src_bytes = (int64_t)(n - 1) * fs + B.span;
+    if (!byte_is_on_device(c, dst) || !byte_is_on_device(c, dst + (dst_bytes - 1))) return VQA_ERR_INVALID;
+    if (mem_kind == VQA_MEM_DEVICE && (uintptr_t)frames < (uintptr_t)dst + (uint64_t)dst_bytes &&
+        (uintptr_t)dst < (uintptr_t)frames + (uint64_t)src_bytes)
+        return VQA_ERR_INVALID;
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &c->scale_stage}))) return rc;
+    hipStream_t st = c->stream;
+    const int depth = B.depth;
+    // the groups: planes alike on BOTH sides go out as one launch
+    bool done[4] = {false, false, false, false};
+    auto alike = [](const vqa_plane_desc &a, const vqa_plane_desc &b) {
+        return a.width == b.width && a.height == b.height && a.row_stride == b.row_stride && a.pixel_step == b.pixel_step;
+    };
+    for (int p = 0; p < n_planes; p++) {
+        if (done[p]) continue;
+        scale_job job;
+        int cnt = 0;
+        for (int q = p; q < n_planes; q++)
+            if (!done[q] && alike(planes[q], planes[p]) && alike(dplanes[q], dplanes[p])) {
+                job.src_off[cnt] = planes[q].offset;
+                job.dst_off[cnt] = dplanes[q].offset;
+                cnt++;
+                done[q] = true;
+            }
+        for (int i = cnt; i < 4; i++) { job.src_off[i] = job.src_off[0]; job.dst_off[i] = job.dst_off[0]; }
+        const vqa_plane_desc &a = planes[p], &b = dplanes[p];
+        scale_tabs tx, ty;
+        if ((rc = get_scale_tabs(c, filter, a.width, b.width, tx))) return rc;
+        if ((rc = get_scale_tabs(c, filter, a.height, b.height, ty))) return rc;
+        // what k_scale's shared memory holds (vqa_kernels.hpp): inside the ratio limits no tile's footprint is larger
+        if (tx.span_w > SCALE_FW || ty.span_h > SCALE_FH || tx.ksize > SCALE_KSIZE_MAX || ty.ksize > SCALE_KSIZE_MAX)
+            return VQA_ERR_UNSUPPORTED;
+        // uint8 samples are summed in 32 bits: 255 sum |k| + 2^21 < 2^31 holds for every table seen (sum |w| stays below 2 even
+        // where a window is cut and renormalised); a table that broke it would be refused, not summed wrong
+        const int64_t worst = tx.abs_sum > ty.abs_sum ? tx.abs_sum : ty.abs_sum;
+        if (depth == 8 && 255 * worst + (1ll << (SCALE_BITS - 1)) >= (1ll << 31)) return VQA_ERR_UNSUPPORTED;
+        job.src_fs = fs; job.dst_fs = dst_fs;
+        job.src_rs = a.row_stride; job.dst_rs = b.row_stride;
+        job.src_step = a.pixel_step; job.dst_step = b.pixel_step;
+        job.sw = a.width; job.sh = a.height; job.dw = b.width; job.dh = b.height;
+        job.peak = (1 << depth) - 1;
+        job.peak_x = a.width == b.width ? (depth > 8 ? 65535 : 255) : job.peak;
+        job.kx = tx.k; job.xmin = tx.xmin; job.xcount = tx.count; job.ksx = tx.ksize;
+        job.ky = ty.k; job.ymin = ty.xmin; job.ycount = ty.count; job.ksy = ty.ksize;
+        for_each_slice(c, n, [&](int a0, int m) {
+            job.src = frames + (int64_t)a0 * fs;
+            job.dst = dst + (int64_t)a0 * dst_fs;
+            prof_scope ps_(c, VQA_K_SCALE);
+            launch_scale(st, job, m, cnt, depth);
+        });
+    }
+    HIPCHK(c, hipGetLastError());
+    record_batch(s, n, dplanes, n_planes, depth);
+    return VQA_OK;
+}
+
+int vqa_scale_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride, const vqa_plane_desc *src_planes,
+                     uint8_t *dst, int64_t dst_frame_stride, const vqa_plane_desc *dst_planes, int n_planes, int filter)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return scale_submit_body(c, frames, mem_kind, n, frame_stride, src_planes, dst, dst_frame_stride, dst_planes, n_planes,
+                                 filter, touched);
+    });
+}
+
+int vqa_scale_wait(vqa_ctx *c)
+{
+    if (!c) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_SCALE];
+    if (!s.entries) return VQA_ERR_STATE;
+    if (int rc = wait_synced(c)) return rc;
+    s.entries = 0;
+    return VQA_OK;
+}
+
+int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int32_t *count, int *ksize)
+{
+    const int given = (k != nullptr) + (xmin != nullptr) + (count != nullptr);
+    if (!scale_filter_known(filter) || in <= 0 || out <= 0 || !ksize || (given != 0 && given != 3)) return VQA_ERR_INVALID;
+    if (!scale_ratio_ok(in, out)) return VQA_ERR_UNSUPPORTED;
+    *ksize = scale_ksize(filter, in, out);
+    if (given) scale_build_axis(filter, in, out, k, xmin, count);
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -2937,7 +3099,7 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_FRINGE || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_MARGIN || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
@@ -2994,6 +3156,7 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_FSIM_POOL) return "k_fsim_pool";
     if (id == VQA_K_SIGSTATS_ACCUM) return "k_sigstats_accum";
     if (id == VQA_K_SIGSTATS_SCAN) return "k_sigstats_scan";
+    if (id == VQA_K_SCALE) return "k_scale";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -612,4 +612,38 @@ void launch_sigstats_scan(hipStream_t st, int n, const vqa_plane_desc *planes, i
 // the words -> the record; mean, stdev and dif in double on the host (include/vqa.h)
 void sigstats_finalize(const unsigned long long *words, int depth, vqa_sigstats_metrics *out);
 
+// The resampler (vqa_scale_submit): k_scale.hip
+constexpr int SCALE_MIN_DIM = 16;       // the limit of the family, on both sides
+constexpr int SCALE_BITS = 22;          // the tables are integers in 2^-22 fixed point
+constexpr int SCALE_KSIZE_MAX = 25;     // 2 ceil(3 * 4) + 1: lanczos at 4x down
+constexpr int SCALE_TILE_W = 64, SCALE_TILE_H = 32;   // a workgroup's tile of the destination plane
+// the source footprint of a tile that k_scale's LDS holds: 63 * 4 + 2 * 12 + 2 = 278 columns and 31 * 4 + 26 = 150 rows at the
+// limits; the submit checks every tile of the tables it built against both
+constexpr int SCALE_FW = 288, SCALE_FH = 152;
+constexpr int SCALE_RC = 16;            // the source rows of one chunk of the footprint
+bool scale_filter_known(int filter);
+bool scale_ratio_ok(int in, int out);   // 1/4 <= out / in <= 8
+int scale_ksize(int filter, int in, int out);
+// one axis' tables on the host, as include/vqa.h states them: k[out][ksize] (0 past count), xmin[out], count[out]
+void scale_build_axis(int filter, int in, int out, int32_t *k, int32_t *xmin, int32_t *count);
+// the most source samples the windows of `tile` consecutive outputs span, over the tiles of an axis
+int scale_footprint(const int32_t *xmin, const int32_t *count, int out, int tile);
+// one group of planes alike on both sides; every stride in bytes, the tables in device memory
+struct scale_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t src_fs, dst_fs;            // frame strides
+    int64_t src_off[4], dst_off[4];    // plane offsets inside a frame
+    int64_t src_rs, dst_rs;            // row strides
+    int src_step, dst_step;
+    int sw, sh, dw, dh;
+    int peak;                          // 2^depth - 1
+    int peak_x;                        // what the horizontal pass clips to: peak, or the sample type's largest value where the
+                                       // width does not change - that pass is a copy, and a copy does not clip
+    const int32_t *kx, *xmin, *xcount, *ky, *ymin, *ycount;
+    int ksx, ksy;
+};
+// n frames of `count` planes (the job's offsets): grid (tiles, n, count)
+void launch_scale(hipStream_t st, const scale_job &job, int n, int count, int depth);
+
 } // namespace vqa

@@ -164,6 +164,55 @@ def xpsnr_grid(width, height):
     return b, -(-int(width) // b), -(-int(height) // b)
 
 
+def scale_filter(filter):
+    """a filter of the resampler by name ("bilinear" | "bicubic" | "lanczos") or id -> its id (N.SCALE_*)"""
+    if isinstance(filter, str) and filter in N.SCALE_FILTERS:
+        return N.SCALE_FILTERS[filter]
+    if not isinstance(filter, (str, bool)) and filter in N.SCALE_FILTERS.values():
+        return int(filter)
+    raise ValueError("scale filter must be one of %s (got %r)" % (", ".join(repr(k) for k in N.SCALE_FILTERS), filter))
+
+
+def planes_span(planes):
+    """bytes from a frame's first byte to the end of its last plane"""
+    bps = 2 if planes_depth(planes) > 8 else 1
+    return max(int(p[2]) + (int(p[1]) - 1) * int(p[3]) + (int(p[0]) - 1) * int(p[4]) + bps for p in planes)
+
+
+def check_scale_planes(planes, out_planes):
+    """vqa_scale_submit's rules for the two plane lists, as a ValueError before anything is uploaded: one to four planes, the
+    same count and depth on both sides, every plane of both at least 16 x 16 with h w <= 2^28, per axis 1/4 <= out / in <= 8"""
+    if not 1 <= len(planes) <= 4 or len(planes) != len(out_planes):
+        raise ValueError("scale needs one to four planes and as many on both sides (got %d and %d)" % (len(planes), len(out_planes)))
+    if planes_depth(planes) != planes_depth(out_planes):
+        raise ValueError("scale keeps the sample depth (got %d and %d bits): converting depths is not built"
+                         % (planes_depth(planes), planes_depth(out_planes)))
+    for p in list(planes) + list(out_planes):
+        w, h = int(p[0]), int(p[1])
+        if w < N.SCALE_MIN_DIM or h < N.SCALE_MIN_DIM or w * h > N.SCALE_MAX_SAMPLES:
+            raise ValueError("scale needs planes of at least %d x %d and at most 2^28 samples (got %dx%d)"
+                             % (N.SCALE_MIN_DIM, N.SCALE_MIN_DIM, w, h))
+    for a, b in zip(planes, out_planes):
+        for n_in, n_out in ((int(a[0]), int(b[0])), (int(a[1]), int(b[1]))):
+            if n_in > N.SCALE_MAX_DOWN * n_out or n_out > N.SCALE_MAX_UP * n_in:
+                raise ValueError("scale ratios lie between 1/%d and %d per axis (got %d -> %d)"
+                                 % (N.SCALE_MAX_DOWN, N.SCALE_MAX_UP, n_in, n_out))
+
+
+def scale_tables(filter, n_in, n_out):
+    """vqa_scale_tables: one axis' tables of the resampler as the library builds them on the host (no GPU needed) ->
+    (k int32 [n_out, ksize], xmin int32 [n_out], count int32 [n_out])"""
+    lib, fid = N.load(), scale_filter(filter)
+    ks = C.c_int(0)
+    N.check(lib.vqa_scale_tables(fid, int(n_in), int(n_out), None, None, None, C.byref(ks)), "vqa_scale_tables")
+    k = np.zeros((int(n_out), ks.value), np.int32)
+    xmin, count = np.zeros(int(n_out), np.int32), np.zeros(int(n_out), np.int32)
+    i32 = C.POINTER(C.c_int32)
+    N.check(lib.vqa_scale_tables(fid, int(n_in), int(n_out), k.ctypes.data_as(i32), xmin.ctypes.data_as(i32),
+                                 count.ctypes.data_as(i32), C.byref(ks)), "vqa_scale_tables")
+    return k, xmin, count
+
+
 class DeviceFrames:
     """n packed BGR24 frames resident in device memory (itemsize 2: frames of uint16 samples, for the quality kernels'
     9..16-bit planes; strides are in bytes)."""
@@ -367,14 +416,14 @@ class Engine:
         N.check(self.lib.vqa_stream_wait(self.ctx, other.ctx), "vqa_stream_wait", self.ctx)
 
     def drain(self):
-        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats and / or a complexity batch), discard the results and
+        """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
-                     "_pending_z": self.sigstats_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1072,6 +1121,74 @@ class Engine:
         self.sigstats_submit(frames, planes, prev0, black_level, crop_level, frame_bytes)
         return self.sigstats_wait(profiles)
 
+    # ---- the resampler ---------------------------------------------------------------
+    def scale_submit(self, frames, planes, out_planes, filter="bicubic", out=None, frame_bytes=None, out_frame_bytes=None):
+        """Resample n frames of ONE stream from `planes` to `out_planes` on the device (vqa_scale_submit): Pillow's
+        Image.resize arithmetic, plane i into plane i, filter "bilinear" | "bicubic" | "lanczos".  frames: an array /
+        DeviceFrames as cambi_submit takes them (a sample type that does not match the depth is a ValueError, never a cast).
+        out: a caller's DeviceFrames to write (its frame stride holds unless out_frame_bytes is given), or None: a new
+        DeviceBuffer of n * out_frame_bytes (default: the span of out_planes).  -> the DeviceFrames of the scaled stream, which
+        every submit of THIS engine accepts with out_planes at once: the stream orders it behind the resampler, no scale_wait
+        is needed in between.  A batch of its own, like cambi_submit."""
+        fid = scale_filter(filter)
+        check_scale_planes(planes, out_planes)
+        fp, kind, n, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
+        itemsize = 2 if planes_depth(out_planes) > 8 else 1
+        span = planes_span(out_planes)
+        if out is None:
+            ofs = int(out_frame_bytes) if out_frame_bytes else span
+            if ofs < span:
+                raise ValueError("out_frame_bytes (%d) is smaller than a frame of out_planes (%d)" % (ofs, span))
+            buf = DeviceBuffer(self, n * ofs)
+            out = DeviceFrames(buf.ptr, n, 1, ofs // itemsize, frame_stride=ofs, owner=buf, channels=1, itemsize=itemsize)
+        else:
+            if not isinstance(out, DeviceFrames):
+                raise TypeError("out must be DeviceFrames (device memory)")
+            if out.itemsize != itemsize:
+                raise ValueError("%d-bit planes need an out of %s samples (got DeviceFrames of itemsize %d)"
+                                 % (planes_depth(out_planes), "uint16" if itemsize == 2 else "uint8", out.itemsize))
+            if out.n < n:
+                raise ValueError("out holds %d frames, the batch has %d" % (out.n, n))
+            ofs = int(out_frame_bytes) if out_frame_bytes else out.frame_stride
+            if ofs < span:
+                raise ValueError("a frame of out (%d bytes) is smaller than a frame of out_planes (%d)" % (ofs, span))
+            if out.n != n or ofs != out.frame_stride:
+                out = DeviceFrames(out.ptr, n, out.h, out.w, ofs, out.row_stride, owner=out, channels=out.channels,
+                                   itemsize=itemsize)
+        st = self.lib.vqa_scale_submit(self.ctx, fp, kind, n, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes),
+                                       len(planes), fid)
+        N.check(st, "vqa_scale_submit", self.ctx)
+        self._pending_k = (n, (keep, out))
+        return out
+
+    def scale_wait(self):
+        """Wait for the pending scale batch: the scaled frames are complete (another engine, or a copy to the host, may read
+        them)."""
+        st = self.lib.vqa_scale_wait(self.ctx)
+        self._pending_k = None
+        N.check(st, "vqa_scale_wait", self.ctx)
+
+    def scale(self, frames, planes, out_planes, filter="bicubic", out=None, frame_bytes=None, out_frame_bytes=None):
+        """scale_submit and scale_wait -> the DeviceFrames of the scaled stream."""
+        res = self.scale_submit(frames, planes, out_planes, filter, out, frame_bytes, out_frame_bytes)
+        self.scale_wait()
+        return res
+
+    def download(self, dev, dtype=None):
+        """Copy DeviceFrames back -> a host array [n, frame_stride / itemsize] (uint8, or uint16 for itemsize 2)."""
+        dt = np.dtype(dtype) if dtype is not None else np.dtype(np.uint16 if dev.itemsize == 2 else np.uint8)
+        out = np.empty((dev.n, dev.frame_stride // dt.itemsize), dt)
+        if out.nbytes:
+            # through page-locked memory, like every result the library copies back: the device never writes pageable pages
+            pin = self.alloc_pinned(out.shape, dt)
+            try:
+                N.check(self.lib.vqa_copy_d2h(self.ctx, pin.ctypes.data, dev.ptr, out.nbytes), "vqa_copy_d2h", self.ctx)
+                N.check(self.lib.vqa_sync(self.ctx), "vqa_sync", self.ctx)
+                out[...] = pin
+            finally:
+                self.free_pinned(pin)
+        return out
+
     # ---- per-kernel timing ---------------------------------------------------
     def profile(self, on=True):
         N.check(self.lib.vqa_profile_enable(self.ctx, 1 if on else 0), "vqa_profile_enable", self.ctx)
@@ -1079,7 +1196,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_COMPLETE:
+        for k in N.K_IDS_PRESENT:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -36,7 +36,8 @@ from . import _native as N
 from . import tails
 from .engine import (ADM_DTYPE, ARTIFACTS_DTYPE, BRISQUE_DTYPE, CAMBI_DTYPE, CIEDE_DTYPE, FSIM_DTYPE, GMSD_DTYPE, HAARPSI_DTYPE,
                      ITP_DTYPE, MDSI_DTYPE, MOTION_DTYPE, PSNR_HVS_DTYPE, PU21_DTYPE, SIGSTATS_DTYPE, SITI_DTYPE, VCA_DTYPE, VIF_DTYPE,
-                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_vca_planes, check_xpsnr_planes, vca_grid)
+                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_scale_planes, check_vca_planes, check_xpsnr_planes,
+                     planes_depth, planes_span, scale_filter, vca_grid)
 from .pooling import shard_range
 
 # A chunk is at most batch_size frames and, when it travels over PCIe, at most this many bytes (all streams together).  With the
@@ -511,7 +512,7 @@ class Quality:
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
                  haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
                  itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False,
-                 sigstats=False, sigstats_black=None, sigstats_crop=None):
+                 sigstats=False, sigstats_black=None, sigstats_crop=None, dist_planes=None, scale=None):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         Every other switch turns on one plane-batch kind (PLANE_KINDS) and is False, True or "only":
         True    every chunk also goes through the kind's kernels (Engine.<kind>_submit) from the SAME upload - the chunk was
@@ -552,8 +553,26 @@ class Quality:
                 (Engine.ciede_model)
         itp_transfer, pu21_transfer: "pq" | "hlg"; itp_full_range, pu21_full_range: False (limited) | True; the colour model
                 of both follows from the planes (Engine.itp_model), that of mdsi and fsim likewise (Engine.mdsi_model)
-        sigstats_black, sigstats_crop: None (32 and 24 on the 8-bit scale) or an integer 0 .. 65535 in sample units"""
+        sigstats_black, sigstats_crop: None (32 and 24 on the 8-bit scale) or an integer 0 .. 65535 in sample units
+        dist_planes, scale: the distorted stream of the quality half has frames of its OWN size - a ladder rung against its
+                source: dist_planes describes them, scale ("bilinear" | "bicubic" | "lanczos") is the filter of the resampler
+                (Engine.scale_submit) that brings every chunk to `planes` on the engine that measures it, after it was
+                uploaded at its native size.  Every kind that reads "pair" or "dist" gets the scaled frames, kinds that read
+                "ref" are untouched: whatever the pass says about the distorted stream, cambi, artifacts and brisque
+                included, it says at the REFERENCE's geometry (Engine.cambi ... on the rung itself give the native
+                figure).  Both or neither; the same plane count and depth, ratios within 1/4 .. 8 per axis (ValueError).
+                Allowed where the quality half's distorted stream is a feed of its own: a quality-only pass, or `qdist` next to
+                the BGR stream of the complexity half, which goes on reading that stream at its native size.  Nothing is
+                ever scaled without the two: streams whose sizes merely differ stay an error."""
         given = dict(locals())   # the keyword arguments by name, for the table
+        if (dist_planes is None) != (scale is None):
+            raise ValueError("dist_planes and scale go together: the distorted stream's own planes AND the filter that brings "
+                             "them to the reference's size (got %s without %s)"
+                             % (("dist_planes", "scale") if scale is None else ("scale", "dist_planes")))
+        if scale is not None:
+            scale_filter(scale)
+            check_scale_planes(dist_planes, planes)
+        self.dist_planes, self.scale = dist_planes, scale
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         for kind in PLANE_KINDS:
@@ -670,6 +689,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         qdist = None
     split = qdist is not None
     qd = qdist if split else dist       # the distorted stream of the quality half
+    if want_q and quality.scale is not None and want_c and not split:
+        raise ValueError("scaling needs a distorted stream of the quality half's own: in a combined pass one BGR stream serves "
+                         "both halves at one size (give the rung as qdist next to it, or run the quality half alone)")
 
     def count(fr):
         return fr.n if isinstance(fr, DeviceFrames) else fr.shape[0]
@@ -719,6 +741,9 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     ref_only = (want_q and not want_c and not quality.ssim and not any(k.reads == "pair" for k in requested)
                 and not any(k.reads == "dist" and getattr(quality, k.name) is True for k in requested))
     halo = any(k.halo for k in requested)
+    scaling = want_q and quality.scale is not None
+    if scaling and ref_only:
+        raise ValueError("this pass reads the reference stream alone: there is no distorted stream to scale")
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -727,9 +752,17 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
             feeds["qdist"] = _Feed("qdist", "qcopies", qd, first, wide=True)
     if want_q and not ref_only:
         fq, fr = feeds["qdist" if split else "dist"], feeds["ref"]
-        if fr.src.n != fq.src.n or fr.fb != fq.fb:
+        if scaling:
+            # the distorted feed has its own frame size: each feed against its own plane list
+            if fr.src.n != fq.src.n:
+                raise ValueError("reference and distorted streams must have the same frame count")
+            for f, pl, what in ((fr, quality.planes, "planes"), (fq, quality.dist_planes, "dist_planes")):
+                if f.itemsize != (2 if planes_depth(pl) > 8 else 1) or f.fb < planes_span(pl):
+                    raise ValueError("the %s stream's frames (%d bytes of %d-byte samples) do not hold %s (%d bytes at %d bits)"
+                                     % (f.name, f.fb, f.itemsize, what, planes_span(pl), planes_depth(pl)))
+        elif fr.src.n != fq.src.n or fr.fb != fq.fb:
             raise ValueError("reference and distorted streams must have the same frame count and layout")
-        if fr.geometry() != fq.geometry() and not (fr.host != fq.host):
+        if not scaling and fr.geometry() != fq.geometry() and not (fr.host != fq.host):
             # (an equal-byte reshape - 1080x1920 against 1920x1080 - would be compared plane against garbage)
             raise ValueError("reference and distorted streams must share a geometry (%s vs %s)" % (fr.geometry(), fq.geometry()))
     if want_c:
@@ -759,7 +792,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         lanes = [first]
     else:
         lanes = list(get_engine_lanes(first.device, min(want_lanes, nchunks)))
-    st = _staging_of(first) if host else None
+    st = _staging_of(first) if (host or scaling) else None
     cp = get_copy_engine(first.device) if host else None   # the copy lane: every upload of the pass, in chunk order
     nb = len(lanes) + 1    # buffer sets on the device: the chunks the lanes hold + the one whose upload runs under their kernels
     params = first.make_params(resize=complexity.resize, dct_mode=complexity.dct_mode,
@@ -777,6 +810,11 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 off = -(-off // 64) * 64   # uint16 frames start aligned inside the slot
             f.ring_off = off
             off += f.slots * f.fb
+    if scaling:   # the scaled chunk: a lane buffer per set, of the reference's frame size
+        scaled_fb = feeds["ref"].fb
+        scaled_bytes = max(p["qn"] for p in plans) * scaled_fb
+        for bs in range(min(nb, nchunks)):
+            st.device_buffer(bs, "scaled", scaled_bytes)
     # ring slots: the chunks the lanes hold (a slot is free again when its chunk has been waited for), the chunk being
     # uploaded and the chunk the copiers gather meanwhile
     ring = st.ring(min(len(lanes) + 2, nchunks), off) if staged else None
@@ -842,6 +880,14 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                                                  row_stride=f.fb, owner=b, channels=1, itemsize=f.itemsize))
                     else:
                         pair.append(f.src.frames.slice(p["q0"], p["q0"] + p["qn"]))
+                p["scaled"] = False
+                if scaling:
+                    # the chunk at its native size -> the reference's, on this lane; what follows on the lane reads the result
+                    b = st.device_buffer(p["k"] % nb, "scaled", scaled_bytes)
+                    out = DeviceFrames(b.ptr, p["qn"], 1, scaled_fb // fr.itemsize, frame_stride=scaled_fb, row_stride=scaled_fb,
+                                       owner=b, channels=1, itemsize=fr.itemsize)
+                    pair[1] = eng.scale_submit(pair[1], quality.dist_planes, quality.planes, quality.scale, out=out)
+                    p["scaled"] = True
                 if quality.ssim:
                     eng.quality_submit(pair[0], pair[1], quality.planes, quality.ssim_mode)
                     p["has_q"] = True
@@ -894,6 +940,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["res"][kind.name] = getattr(eng, kind.name + "_wait")(*(getattr(quality, a) for a in kind.wait))
             if p["has_c"]:
                 p["rec"] = eng.complexity_wait()
+            if p.get("scaled"):
+                eng.scale_wait()
         if staged:
             free_slots.append(p["slot"])  # every copy out of the slot has completed
 

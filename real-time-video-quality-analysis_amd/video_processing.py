@@ -436,6 +436,50 @@ def frame_sigstats(frames, layout="bgr24", height=None, width=None, engine=None,
 PU21_PSNR_CAP = 100.0   # the row's PU_PSNR and PU_PSNR_RGB: a frame's value (inf for identical frames) is capped here before pooling
 
 
+def frame_scale(frames, layout, height, width, out_height, out_width, filter="bicubic", engine=None, batch_size=64, device=None):
+    """The stream resampled to out_height x out_width on the GPU (Engine.scale: Pillow's Image.resize arithmetic, include/vqa.h;
+    filter "bilinear" | "bicubic" | "lanczos"; every plane of the layout over its own grid, chroma centre-sited) -> a host
+    array [n, out frame samples] of the input's dtype, in chunks of batch_size frames.  frames: what frame_cambi takes; height
+    and width are read off [N,H,W(,3)] arrays and needed for planar [N, samples] ones.  Every plane on both sides at least
+    16 x 16, ratios within 1/4 .. 8 per axis (ValueError)."""
+    from .engine import check_scale_planes, planes_span, scale_filter
+    frames = _host_stream(frames, wide=True)
+    scale_filter(filter)
+    h, w = _geometry(frames, layout, height, width)
+    planes, out_planes = LAYOUTS[layout][0](h, w), LAYOUTS[layout][0](int(out_height), int(out_width))
+    check_scale_planes(planes, out_planes)
+    wide = layout_depth(layout) > 8
+    n = frames.n if isinstance(frames, DeviceFrames) else frames.shape[0]
+    out = np.zeros((n, planes_span(out_planes) // (2 if wide else 1)), np.uint16 if wide else np.uint8)
+    if n == 0:
+        return out
+    eng = engine if engine is not None else stream.get_engine(device)
+    with stream.pass_lock(eng.device):
+        for a in range(0, n, int(batch_size)):
+            b = min(n, a + int(batch_size))
+            chunk = frames.slice(a, b) if isinstance(frames, DeviceFrames) else np.ascontiguousarray(frames[a:b]).reshape(b - a, -1)
+            res = eng.scale(chunk, planes, out_planes, filter)
+            out[a:b] = eng.download(res)
+            res._owner.free()
+    return out
+
+
+def _scale_request(scale, dist_height, dist_width):
+    """the three arguments that turn scaling on -> whether it is on; a ValueError for a set that does not fit together"""
+    for name, v in (("dist_height", dist_height), ("dist_width", dist_width)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0):
+            raise ValueError("%s must be a positive integer." % name)
+    if scale is None:
+        if dist_height is not None or dist_width is not None:
+            raise ValueError("dist_height / dist_width need scale: nothing is scaled without a filter being named.")
+        return False
+    if not (isinstance(scale, str) and scale in N.SCALE_FILTERS):
+        raise ValueError("scale must be \"bilinear\", \"bicubic\" or \"lanczos\".")
+    if (dist_height is None) != (dist_width is None):
+        raise ValueError("dist_height and dist_width go together.")
+    return True
+
+
 def _brisque_model(model_path, range_path):
     """the config's two paths -> a model or None; loaded before the pass starts, so a bad file costs no GPU time"""
     if model_path is None:
@@ -448,7 +492,7 @@ def _brisque_model(model_path, range_path):
 
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
                   cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None,
-                  delta_itp=None, pu21=None, fsim=None, sigstats=None, sigstats_depth=8):
+                  delta_itp=None, pu21=None, fsim=None, sigstats=None, sigstats_depth=8, extra=None):
     """libvmaf's JSON log, restricted to what is computed: frames[i].metrics.vif_scale0..3 and pooled_metrics.vif_scaleN
     .{min, max, mean, harmonic_mean} (libvmaf's harmonic mean: n / sum 1 / (x + 1) - 1).  No "vmaf" key without a model.
     scale: [n, 4], the first (luma) plane's values, or None when VIF was not measured.
@@ -493,6 +537,7 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     N), black, frozen (0 or 1) and scene_score (events.signal_events at its defaults), after fsimc and before vmaf, likewise, and
     next to "frames" and "pooled_metrics" an object "signal": black_frames, frozen_frames, scene_cuts (counts) and crop ([top,
     bottom, left, right] over the frames that are not black, null when all are).  The model never reads them.
+    extra: None, or a dict of further top-level keys, written last (a scaled pass: "DIST_RES" and "SCALE").
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
@@ -599,6 +644,8 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
         doc = {"frames": frames, "pooled_metrics": pooled}
         if signal is not None:
             doc["signal"] = signal
+        if extra:
+            doc.update(extra)
         json.dump(doc, f, indent=1)
         f.write("\n")
 
@@ -709,7 +756,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        gmsd=False, cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False,
                        brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
-                       pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None):
+                       pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
+                       dist_height=None, dist_width=None, scale=None):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -751,6 +799,14 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     sigstats=True: likewise the signal statistics of the REFERENCE stream - the source SI/TI and VCA describe too - from the same
     upload (y_min .. scene_score of the first plane and the "signal" object, write_vif_log; sigstats_black, sigstats_crop: None or
     the black and the dark-border level in sample units; a model file does not turn it on).
+    scale="bilinear" | "bicubic" | "lanczos": the distorted stream is a ladder rung of its OWN size, dist_height x dist_width (a
+    .y4m file brings its size in its header, [N,H,W,3] arrays in their shape; the same layout and depth as the reference).
+    Every chunk is uploaded at that size and resampled to the reference's on the GPU (stream.Quality's dist_planes / scale:
+    what `[dist]scale=W:H:flags=bicubic` does before the filters in an FFmpeg graph, in Pillow's arithmetic), so EVERYTHING the
+    pass says about the distorted stream - cambi, artifacts and brisque included - is said at the reference's geometry
+    (frame_cambi and the other frame_* calls on the rung itself give the native figure).  vmaf_log, when written, gains the
+    top-level keys "DIST_RES" ("1280x720") and "SCALE".  Without scale, streams of different sizes stay the error they were,
+    dist_height / dist_width alone are a ValueError, and every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -761,11 +817,23 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         vif = adm = motion = True
     bmodel = _brisque_model(brisque_model_path, brisque_range_path)
     brisque = bool(brisque) or bmodel is not None
+    scaling = _scale_request(scale, dist_height, dist_width)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
-    dist, layout_d, _, _ = _open_quality_stream(distorted_video, layout, height, width)
+    # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
+    dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
+                                                          dist_width or (None if scaling else width))
     if layout_d != layout:
         raise ValueError("reference and distorted streams must share a pixel layout")
     h, w = _geometry(ref, layout, height, width)
+    dist_planes = extra = None
+    if scaling:
+        from .engine import check_scale_planes
+        dh, dw = _geometry(_host_stream(dist, wide=True), layout, dist_h, dist_w)
+        if not dh or not dw:
+            raise ValueError("scale needs the distorted stream's size: dist_height and dist_width")
+        dist_planes = LAYOUTS[layout][0](dh, dw)
+        check_scale_planes(dist_planes, LAYOUTS[layout][0](h, w))
+        extra = {"DIST_RES": "%dx%d" % (dw, dh), "SCALE": scale}
     wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
     try:
         if ciede and len(LAYOUTS[layout][1]) != 3:
@@ -784,10 +852,11 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             if len(LAYOUTS[layout][1]) != 3:
                 raise ValueError("pu21 needs three planes")
             _check_pu21(pu21_transfer, pu21_full_range)
-        if any((vif, adm, motion, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, mdsi, delta_itp, pu21,
-                fsim, sigstats)):
+        kinds_on = any((vif, adm, motion, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, mdsi, delta_itp,
+                        pu21, fsim, sigstats))
+        if kinds_on or scaling:
             rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
-            if not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
+            if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
                 raise ValueError("ref and dist must have the same shape")
             q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
                                                              adm=bool(adm), motion=bool(motion), siti=bool(siti),
@@ -802,10 +871,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                                                              pu21_transfer=pu21_transfer,
                                                              pu21_full_range=pu21_full_range, fsim=bool(fsim),
                                                              sigstats=bool(sigstats), sigstats_black=sigstats_black,
-                                                             sigstats_crop=sigstats_crop),
+                                                             sigstats_crop=sigstats_crop, dist_planes=dist_planes,
+                                                             scale=scale if scaling else None),
                               batch_size=batch_size, on_quality=wr, device=device)
-            _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                               artifacts, brisque, bmodel, mdsi, delta_itp, pu21, fsim, sigstats, layout_depth(layout))
+            if kinds_on:
+                _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
+                                   artifacts, brisque, bmodel, mdsi, delta_itp, pu21, fsim, sigstats, layout_depth(layout), extra)
         else:
             frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
     finally:
@@ -844,7 +915,7 @@ MODE_KEYS = {
 
 def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
                        cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
-                       mdsi=False, delta_itp=False, pu21=False, fsim=False, sigstats=False, sigstats_depth=8):
+                       mdsi=False, delta_itp=False, pu21=False, fsim=False, sigstats=False, sigstats_depth=8, extra=None):
     """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and
     noise / BRISQUE / signal statistics and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (stream.run's quality tuple, whose
     elements stream.records_by_kind names) -> vmaf_log"""
@@ -858,7 +929,8 @@ def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=Fal
     scale = log.pop("vif")["scale"] if vif else None
     if sigstats:
         log["sigstats_depth"] = sigstats_depth
-    write_vif_log(vmaf_log, scale, log.pop("adm", None), model=model if motion else None, brisque_model=brisque_model, **log)
+    write_vif_log(vmaf_log, scale, log.pop("adm", None), model=model if motion else None, brisque_model=brisque_model, extra=extra,
+                  **log)
 
 
 def _check_mode_keys(config):
@@ -940,6 +1012,7 @@ def _check_mode_keys(config):
         v = config.get(key)
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v <= 0):
             raise ValueError("height and width must be positive integers.")
+    _scale_request(config.get("scale"), config.get("dist_height"), config.get("dist_width"))
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -1017,7 +1090,12 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         [N, samples] arrays above 8 bits; .y4m inputs take theirs from the header), dct_mode ("auto" default: full-frame up to 128x128, 8x8 blocks
         above | "block8" | "full" the reference's cv2.dct at any size), motion ("sad" north_star's block-SAD | "farneback" the
         reference's own; default: set_motion_mode / VQA_MOTION), device (GPU index; default VQA_DEVICE, LOCAL_RANK, 0) and
-        height / width (the geometry of headerless inputs: raw .yuv planar pairs, raw .bgr24 streams).
+        height / width (the geometry of headerless inputs: raw .yuv planar pairs, raw .bgr24 streams),
+        scale ("bilinear" | "bicubic" | "lanczos"; default null) with dist_height / dist_width (the size of the ENCODED pair
+        stream when it is a ladder rung smaller or larger than the input; .y4m files bring theirs): the rung is uploaded at its
+        own size and resampled to the input's on the GPU before anything measures it (run_ffmpeg_metrics), encoded_bgr stays at
+        the rung's size for the complexity half, and the row gains DIST_RES ("1280x720") and SCALE as its LAST columns; needs
+        encoded_bgr next to a planar pair (one BGR stream cannot serve both halves at two sizes: ValueError).
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1053,6 +1131,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     pu_full = ITP_RANGES[config.get("pu21_range", "limited")]
     fsm = config.get("fsim", False)
     sig, sig_black, sig_crop = config.get("sigstats", False), config.get("sigstats_black"), config.get("sigstats_crop")
+    scale = config.get("scale")
+    scaling = scale is not None
     model = None
     if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
         from . import vmaf_model
@@ -1068,36 +1148,51 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     psnr_log, ssim_log, vmaf_log = (os.path.join(tmp, "%s_%s.log" % (k, uid)) for k in ("psnr", "ssim", "vmaf"))
     try:
         ref, layout, qh, qw = _open_quality_stream(input_video, layout, height, width)
-        qenc, layout_d, _h, _w = _open_quality_stream(encoded_video, layout, qh, qw)
+        qenc, layout_d, dqh, dqw = _open_quality_stream(encoded_video, layout, config.get("dist_height") or (None if scaling else qh),
+                                                        config.get("dist_width") or (None if scaling else qw))
         if layout_d != layout:
             raise ValueError("reference and distorted streams must share a pixel layout")
+        if scaling and (layout == "bgr24" and encoded_bgr is None):
+            raise ValueError("scaling needs a distorted stream of the quality half's own: pass the rung as a planar pair next to "
+                             "encoded_bgr (one BGR stream serves both halves at one size)")
+        if not scaling:
+            dqh, dqw = qh, qw
         if layout == "bgr24" and encoded_bgr is None:
             enc, qdist = qenc, None       # (:216 and :242 read the same encoded stream: every chunk is uploaded once)
         else:
             if encoded_bgr is None:
                 raise ValueError("a %s quality pair needs the encoded stream's BGR frames for the complexity half "
                                  "(complexity_metrics.py:100 reads cv2's BGR decode): pass encoded_bgr=" % layout)
-            enc, qdist = _open_frames(encoded_bgr, qh or height, qw or width), _host_stream(qenc, wide=True)
+            enc, qdist = _open_frames(encoded_bgr, dqh or height, dqw or width), _host_stream(qenc, wide=True)
             ref = _host_stream(ref, wide=True)
         eh, ew = (enc.h, enc.w) if isinstance(enc, DeviceFrames) else (enc.shape[1], enc.shape[2])
         if qdist is None:
             h, w = eh, ew
         else:
-            h, w = _geometry(ref, layout, qh or eh, qw or ew)
+            h, w = _geometry(ref, layout, (qh or eh) if not scaling else qh, (qw or ew) if not scaling else qw)
+            if scaling and (not h or not w):
+                raise ValueError("scale needs the input stream's size: height and width")
+            dh, dw = _geometry(qdist, layout, dqh or eh, dqw or ew) if scaling else (h, w)   # (the BGR stream has the rung's size)
             if layout == "yuv420p":
                 from .frames import frame_bytes_yuv420p
-                for a in (ref, qdist):
-                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_bytes_yuv420p(h, w)):
+                for a, (ah, aw) in ((ref, (h, w)), (qdist, (dh, dw))):
+                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_bytes_yuv420p(ah, aw)):
                         raise ValueError("yuv420p streams must be planar [N, H*W*3/2] uint8 arrays of the frames' geometry "
-                                         "(%dx%d: %d bytes per frame)" % (w, h, frame_bytes_yuv420p(h, w)))
+                                         "(%dx%d: %d bytes per frame)" % (aw, ah, frame_bytes_yuv420p(ah, aw)))
             elif layout in PIXFMTS and layout != "gray":
                 dt = np.uint16 if layout_depth(layout) > 8 else np.uint8
-                for a in (ref, qdist):
-                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_samples(h, w, layout)
+                for a, (ah, aw) in ((ref, (h, w)), (qdist, (dh, dw))):
+                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_samples(ah, aw, layout)
                                                             or a.dtype != dt):
                         raise ValueError("%s streams must be planar [N, %d] %s arrays of the frames' geometry (%dx%d)"
-                                         % (layout, frame_samples(h, w, layout), np.dtype(dt).name, w, h))
+                                         % (layout, frame_samples(ah, aw, layout), np.dtype(dt).name, aw, ah))
         planes = LAYOUTS[layout][0](h, w)
+        dist_planes = extra = None
+        if scaling:
+            from .engine import check_scale_planes
+            dist_planes = LAYOUTS[layout][0](dh, dw)
+            check_scale_planes(dist_planes, planes)
+            extra = {"DIST_RES": "%dx%d" % (dw, dh), "SCALE": scale}
         if xps:
             from .engine import check_xpsnr_planes
             check_xpsnr_planes(planes)
@@ -1114,14 +1209,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                                      itp_full_range=itp_full, pu21=pu,
                                                                      pu21_transfer=pu_tf, pu21_full_range=pu_full, fsim=fsm,
                                                                      sigstats=sig, sigstats_black=sig_black,
-                                                                     sigstats_crop=sig_crop),
+                                                                     sigstats_crop=sig_crop, dist_planes=dist_planes,
+                                                                     scale=scale),
                                     complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
                                     batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
         if any((vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itp, pu, fsm, sig)):
             _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
-                               mds, itp, pu, fsm, sig, layout_depth(layout))
+                               mds, itp, pu, fsm, sig, layout_depth(layout), extra)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -1134,6 +1230,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                      "ORB Feature Complexity", "Color Histogram Complexity", "Temporal DCT Complexity",
                      "Framerate Variation")
         metrics.update(dict(zip(names, t)))
+        if scaling:
+            metrics.update(extra)
         thread_safe_update_csv(metrics, csv_file)
         return metrics
     finally:
