@@ -402,8 +402,9 @@ def motion_records(rec):
     return out
 
 
-# ---- the plane-batch kinds of the quality half: ONE table, read by Quality, run / _run_locked, records_by_kind and
-# video_processing._write_feature_log.  A new kind is added here (and to Quality's keyword list), nowhere else on the Python side.
+# ---- the plane-batch kinds of the quality half: ONE table, read by Quality, run / _run_locked and records_by_kind.  A new kind
+# is added here (and to Quality's keyword list) and nowhere else in the pass; what the entry points make of its records - the
+# flag, the config key, the log's keys and the row's columns - is the second table, features.FEATURES, with one entry per entry here.
 def _three_planes(kind, planes):
     if len(planes) != 3:
         raise ValueError("%s needs three planes" % kind)

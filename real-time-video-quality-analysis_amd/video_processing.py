@@ -22,6 +22,8 @@ from . import _native as N
 from . import stream
 from .complexity_metrics import _open_frames
 from .engine import DeviceFrames, bgr_planes, gray_planes, yuv420p_planes, yuv_planes
+from .features import (FEATURES, ITP_RANGES, KINDS, MODEL_PATHS, PARAM_CHECKS, PSNR_HVS_DB_CAP, PU21_PSNR_CAP,  # noqa: F401
+                       check_switch, switches)
 from .frames import PIXFMTS, frame_samples
 
 LAYOUTS = {
@@ -71,6 +73,45 @@ def _host_stream(a, wide=False):
     return a
 
 
+def _config_switches(config):
+    """a validated config -> what it asks of the quality half (features.switches): stream.Quality's keywords for the kinds and
+    their parameters, and the model files' paths.  Pure: no file and no device is touched."""
+    return switches(config, config=True)
+
+
+def _check_request(f, layout, values):
+    """what can be said of a kind's request before a stream is opened, under the names the caller knows: the flag and
+    run_ffmpeg_metrics' keywords, by which `values` goes"""
+    if f.three_planes and len(LAYOUTS[layout][1]) != 3:
+        raise ValueError("%s needs three planes" % f.flag)
+    for p in f.params:
+        if p.early:
+            PARAM_CHECKS[p.quality](p.flag, values[p.flag])
+
+
+def _only_pass(kind, streams, layout, height, width, engine, batch_size, device, **params):
+    """One pass that measures `kind` alone (stream.Quality's "only") over streams = (reference, encoded) or the one stream the
+    kind reads; params: the kind's parameters by run_ffmpeg_metrics' keywords, further Quality keywords as they are.
+    -> (the pass's last element: the kind's records, planes)"""
+    f = next(f for f in FEATURES if f.kind == kind)
+    _check_request(f, layout, params)
+    names = {p.flag: p.quality for p in f.params}   # the entry points' keyword -> Quality's
+    quality = {names.get(k, k): v for k, v in params.items()}
+    quality[kind] = "only"
+    streams = [_host_stream(a, wide=True) for a in streams]
+    if len(streams) == 2 and not isinstance(streams[0], DeviceFrames) and streams[0].shape != streams[1].shape:
+        raise ValueError("ref and dist must have the same shape")
+    h, w = _geometry(streams[0], layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    q, _ = stream.run(streams[-1], streams[0], quality=stream.Quality(planes, **quality), batch_size=batch_size, engine=engine,
+                      device=device)
+    return q[-1], planes
+
+
+def _sizes(planes):
+    return [(p[0], p[1]) for p in planes]
+
+
 def frame_quality(reference, distorted, layout="bgr24", ssim_mode="gauss", height=None, width=None, engine=None,
                   batch_size=64, on_chunk=None, device=None, scales=False):
     """Per-frame SSE and SSIM per plane.  Returns (sse [n,p] uint64, ssim [n,p] float64, plane sizes).
@@ -97,28 +138,16 @@ def frame_vif(reference, distorted, layout="bgr24", height=None, width=None, eng
     """Per-frame VIF per plane on four scales (Engine.vif through the one-pass pipeline of frame_quality).
     Returns (scale [n,p,4] float64 - libvmaf's vif_scale0..3 -, vif [n,p] float64 - sum of the numerators over the sum of the
     denominators of the four scales -, plane sizes).  Every plane at least 16 x 16."""
-    reference, distorted = _host_stream(reference, wide=True), _host_stream(distorted, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != distorted.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(distorted, reference, quality=stream.Quality(planes, vif="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    return q[-1]["scale"], q[-1]["vif"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("vif", (reference, distorted), layout, height, width, engine, batch_size, device)
+    return r["scale"], r["vif"], _sizes(planes)
 
 
 def frame_adm(reference, distorted, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
     """Per-frame ADM per plane on four scales (Engine.adm through the one-pass pipeline of frame_quality).
     Returns (scale [n,p,4] float64 - libvmaf's adm_scale0..3 -, adm2 [n,p] float64 - sum of the numerators over the sum of the
     denominators of the four scales -, plane sizes).  Every plane at least 16 x 16."""
-    reference, distorted = _host_stream(reference, wide=True), _host_stream(distorted, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != distorted.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(distorted, reference, quality=stream.Quality(planes, adm="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    return q[-1]["scale"], q[-1]["adm2"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("adm", (reference, distorted), layout, height, width, engine, batch_size, device)
+    return r["scale"], r["adm2"], _sizes(planes)
 
 
 def frame_motion(reference, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -127,12 +156,8 @@ def frame_motion(reference, layout="bgr24", height=None, width=None, engine=None
     Returns (motion [n,p] float64 - libvmaf's `motion`: the mean absolute difference of the blurred frame and the blurred frame
     before it, 0 for frame 0 -, motion2 [n,p] float64 - min(motion[i], motion[i+1]), the last frame keeping its motion -, plane
     sizes).  Every plane at least 16 x 16."""
-    reference = _host_stream(reference, wide=True)
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(reference, reference, quality=stream.Quality(planes, motion="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    return q[-1]["motion"], q[-1]["motion2"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("motion", (reference,), layout, height, width, engine, batch_size, device)
+    return r["motion"], r["motion2"], _sizes(planes)
 
 
 def frame_siti(reference, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -141,15 +166,8 @@ def frame_siti(reference, layout="bgr24", height=None, width=None, engine=None, 
     Returns (si [n,p] float64 - the standard deviation of the Sobel magnitude over the plane's interior -, ti [n,p] float64 - the
     standard deviation of the difference to the frame before, 0 for frame 0 -, plane sizes), both on the 8-bit scale.  P.910's
     SI and TI of the clip are si.max(axis=0) and ti.max(axis=0).  Every plane at least 16 x 16."""
-    reference = _host_stream(reference, wide=True)
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(reference, reference, quality=stream.Quality(planes, siti="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    return q[-1]["si"], q[-1]["ti"], [(p[0], p[1]) for p in planes]
-
-
-PSNR_HVS_DB_CAP = 100.0   # JSON has no infinity: the log and the row carry min(dB, 100); the C record keeps the infinity
+    r, planes = _only_pass("siti", (reference,), layout, height, width, engine, batch_size, device)
+    return r["si"], r["ti"], _sizes(planes)
 
 
 def frame_psnr_hvs(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -157,15 +175,8 @@ def frame_psnr_hvs(reference, encoded, layout="bgr24", height=None, width=None, 
     streams are uploaded once).  The definition is include/vqa.h's: the published 8x8-block form, whole blocks only.
     Returns (psnr_hvs [n,p] float64 dB, psnr_hvsm [n,p] float64 dB - inf for identical planes: nothing is capped here -,
     s_hvs [n,p], s_hvsm [n,p] - the two CSF-weighted mean squared errors -, plane sizes).  Every plane at least 16 x 16."""
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, psnr_hvs="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
-    return r["psnr_hvs"], r["psnr_hvsm"], r["s_hvs"], r["s_hvsm"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("psnr_hvs", (reference, encoded), layout, height, width, engine, batch_size, device)
+    return r["psnr_hvs"], r["psnr_hvsm"], r["s_hvs"], r["s_hvsm"], _sizes(planes)
 
 
 def frame_ciede(reference, encoded, layout="bgr24", height=None, width=None, weights=N.CIEDE_WEIGHTS_CIE, engine=None,
@@ -176,16 +187,7 @@ def frame_ciede(reference, encoded, layout="bgr24", height=None, width=None, wei
     (0.65, 1, 4) what libvmaf's ciede2000 feature is believed to use (unverified).
     Returns (ciede2000 [n] float64 = 45 - 20 log10(de_mean), inf for identical frames: nothing is capped here -, de_mean [n]).
     Luma at least 16 x 16; a one-plane layout is a ValueError."""
-    if len(LAYOUTS[layout][1]) != 3:
-        raise ValueError("ciede needs three planes")
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, ciede="only", ciede_weights=weights),
-                      batch_size=batch_size, engine=engine, device=device)
-    r = q[-1]
+    r, _ = _only_pass("ciede", (reference, encoded), layout, height, width, engine, batch_size, device, ciede_weights=weights)
     return r["ciede2000"], r["de_mean"]
 
 
@@ -195,15 +197,8 @@ def frame_gmsd(reference, encoded, layout="bgr24", height=None, width=None, engi
     magnitudes and its standard deviation (divisor N - 1) over the downsampled grid.
     Returns (gmsd [n,p] float64 - exactly 0 for identical planes -, gms_mean [n,p] float64 - the paper's GMSM, exactly 1 for
     identical planes -, plane sizes).  Every plane at least 16 x 16."""
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, gmsd="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
-    return r["gmsd"], r["gms_mean"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("gmsd", (reference, encoded), layout, height, width, engine, batch_size, device)
+    return r["gmsd"], r["gms_mean"], _sizes(planes)
 
 
 def frame_cambi(frames, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -213,13 +208,8 @@ def frame_cambi(frames, layout="bgr24", height=None, width=None, engine=None, ba
     and the scale weights 16, 8, 4, 2, 1 - integers up to the last division.
     Returns (cambi [n,p] float64 - exactly 0 for a plane without banding -, pool [n,p,5] float64, plane sizes).  Every plane
     at least 16 x 16."""
-    frames = _host_stream(frames, wide=True)
-    h, w = _geometry(frames, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, cambi="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
-    return r["cambi"], r["pool"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("cambi", (frames,), layout, height, width, engine, batch_size, device)
+    return r["cambi"], r["pool"], _sizes(planes)
 
 
 def frame_xpsnr(reference, encoded, layout="yuv420p", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -229,16 +219,9 @@ def frame_xpsnr(reference, encoded, layout="yuv420p", height=None, width=None, e
     temporal activity, no small-picture smoothing, plain 2 x 2 sums above HD - not FFmpeg's filter in these three).
     Returns (xpsnr [n,p] float64 in dB - inf for identical planes -, wsse [n,p] float64, plane sizes, block).  Planar layouts
     whose first plane is the luma (bgr24 is a ValueError); every plane at least 16 x 16."""
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, xpsnr="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
     from .engine import xpsnr_grid
-    return r["xpsnr"], r["wsse"], [(p[0], p[1]) for p in planes], xpsnr_grid(planes[0][0], planes[0][1])[0]
+    r, planes = _only_pass("xpsnr", (reference, encoded), layout, height, width, engine, batch_size, device)
+    return r["xpsnr"], r["wsse"], _sizes(planes), xpsnr_grid(planes[0][0], planes[0][1])[0]
 
 
 def frame_haarpsi(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -248,15 +231,8 @@ def frame_haarpsi(reference, encoded, layout="bgr24", height=None, width=None, e
     inverse - the grayscale index per plane, as recalled from the authors' HaarPSI.m and not pinned against it.
     Returns (haarpsi [n,p] float64 - exactly 1 for identical planes -, similarity [n,p] float64 - the weighted mean of the
     sigmoid -, plane sizes).  Every plane at least 16 x 16."""
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, haarpsi="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
-    return r["haarpsi"], r["similarity"], [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("haarpsi", (reference, encoded), layout, height, width, engine, batch_size, device)
+    return r["haarpsi"], r["similarity"], _sizes(planes)
 
 
 def frame_vca(reference, layout="yuv420p", height=None, width=None, engine=None, batch_size=64, device=None, blocks=False):
@@ -269,13 +245,9 @@ def frame_vca(reference, layout="yuv420p", height=None, width=None, engine=None,
     for a repeated frame -, l [n,p] float64 - the brightness -, plane sizes), all on the 8-bit scale; with blocks=True also the
     block maps: per plane dict(qh, s as uint64 [n, nby, nbx]), qh in steps of 2^-(24 - depth).  Planar layouts (bgr24 is a
     ValueError); every plane at least 32 x 32."""
-    reference = _host_stream(reference, wide=True)
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(reference, reference, quality=stream.Quality(planes, vca="only", vca_blocks=blocks), batch_size=batch_size,
-                      engine=engine, device=device)
-    r, maps = q[-1] if blocks else (q[-1], None)
-    out = (r["e"], r["h"], r["l"], [(p[0], p[1]) for p in planes])
+    last, planes = _only_pass("vca", (reference,), layout, height, width, engine, batch_size, device, vca_blocks=blocks)
+    r, maps = last if blocks else (last, None)
+    out = (r["e"], r["h"], r["l"], _sizes(planes))
     return out + (maps,) if blocks else out
 
 
@@ -286,14 +258,9 @@ def frame_artifacts(frames, layout="bgr24", height=None, width=None, engine=None
     mean, Immerkaer's noise estimate on the 8-bit scale - integers up to the last division, no tool compared.
     Returns (dict of [n,p] arrays: blockiness, blockiness_max, blur, noise as float64 and phase_h, phase_v as int32; plane
     sizes).  Every plane at least 16 x 16; packed bgr24 is measured per channel."""
-    frames = _host_stream(frames, wide=True)
-    h, w = _geometry(frames, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, artifacts="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
+    r, planes = _only_pass("artifacts", (frames,), layout, height, width, engine, batch_size, device)
     keys = ("blockiness", "blockiness_max", "phase_h", "phase_v", "blur", "noise")
-    return {k: r[k] for k in keys}, [(p[0], p[1]) for p in planes]
+    return {k: r[k] for k in keys}, _sizes(planes)
 
 
 def frame_brisque(frames, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -303,13 +270,8 @@ def frame_brisque(frames, layout="bgr24", height=None, width=None, engine=None, 
     code as recalled, not pinned against it.
     Returns (features [n, p, 36] float64, flags [n, p] uint32, plane sizes).  Every plane at least 16 x 16; packed bgr24 is
     measured per channel."""
-    frames = _host_stream(frames, wide=True)
-    h, w = _geometry(frames, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, brisque="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
-    return np.ascontiguousarray(r["features"]), np.ascontiguousarray(r["flags"]), [(p[0], p[1]) for p in planes]
+    r, planes = _only_pass("brisque", (frames,), layout, height, width, engine, batch_size, device)
+    return np.ascontiguousarray(r["features"]), np.ascontiguousarray(r["flags"]), _sizes(planes)
 
 
 def frame_mdsi(reference, encoded, layout="bgr24", height=None, width=None, engine=None, batch_size=64, device=None):
@@ -321,26 +283,8 @@ def frame_mdsi(reference, encoded, layout="bgr24", height=None, width=None, engi
     ordered: the metric is not symmetric.
     Returns (mdsi [n] float64 - exactly 0 for identical frames, larger is worse -, dev [n] float64, the deviation before the last
     quarter power).  Plane 0 at least 16 x 16."""
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, mdsi="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
+    r, _ = _only_pass("mdsi", (reference, encoded), layout, height, width, engine, batch_size, device)
     return np.ascontiguousarray(r["mdsi"]), np.ascontiguousarray(r["dev"])
-
-
-ITP_RANGES = {"limited": False, "full": True}   # the config's "delta_itp_range" -> full_range
-
-
-def _check_itp(transfer, full_range):
-    """the transfer and range arguments of the dE_ITP entry points; anything unknown is a ValueError"""
-    if not (isinstance(transfer, str) and transfer in N.ITP_TRANSFERS):
-        raise ValueError("delta_itp_transfer must be 'pq' or 'hlg'")
-    if not isinstance(full_range, bool):
-        raise ValueError("delta_itp_full_range must be True or False")
 
 
 def frame_delta_itp(reference, encoded, layout="bgr24", height=None, width=None, transfer="pq", full_range=False, engine=None,
@@ -351,27 +295,9 @@ def frame_delta_itp(reference, encoded, layout="bgr24", height=None, width=None,
     on a 1000 cd/m2 display); full_range False (limited) or True (ignored for bgr24).  1 is about one just-noticeable difference.
     Returns (delta_itp [n] float64, the mean over the luma grid - exactly 0 for identical frames -, delta_itp_max [n] float64,
     the largest value of a pixel).  Luma at least 16 x 16; a one-plane layout, an unknown transfer or range is a ValueError."""
-    if len(LAYOUTS[layout][1]) != 3:
-        raise ValueError("delta_itp needs three planes")
-    _check_itp(transfer, full_range)
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, itp="only", itp_transfer=transfer,
-                                                                 itp_full_range=full_range),
-                      batch_size=batch_size, engine=engine, device=device)
-    r = q[-1]
+    r, _ = _only_pass("itp", (reference, encoded), layout, height, width, engine, batch_size, device,
+                      delta_itp_transfer=transfer, delta_itp_full_range=full_range)
     return np.ascontiguousarray(r["de_mean"]), np.ascontiguousarray(r["de_max"])
-
-
-def _check_pu21(transfer, full_range):
-    """the transfer and range arguments of the PU21 entry points; anything unknown is a ValueError"""
-    if not (isinstance(transfer, str) and transfer in N.ITP_TRANSFERS):
-        raise ValueError("pu21_transfer must be 'pq' or 'hlg'")
-    if not isinstance(full_range, bool):
-        raise ValueError("pu21_full_range must be True or False")
 
 
 def frame_pu21(reference, encoded, layout="bgr24", height=None, width=None, transfer="pq", full_range=False, engine=None,
@@ -383,18 +309,8 @@ def frame_pu21(reference, encoded, layout="bgr24", height=None, width=None, tran
     Returns (pu_psnr [n], pu_psnr_rgb [n], pu_ssim [n], mse_y [n], mse_rgb [n]), float64: the PSNRs at a peak of 256 PU units (inf
     for identical frames, not capped here), the Gaussian SSIM of the PU-encoded luminance (exactly 1 for identical frames) and the
     mean squared errors in PU units.  Luma at least 16 x 16; a one-plane layout, an unknown transfer or range is a ValueError."""
-    if len(LAYOUTS[layout][1]) != 3:
-        raise ValueError("pu21 needs three planes")
-    _check_pu21(transfer, full_range)
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, pu21="only", pu21_transfer=transfer,
-                                                                 pu21_full_range=full_range),
-                      batch_size=batch_size, engine=engine, device=device)
-    r = q[-1]
+    r, _ = _only_pass("pu21", (reference, encoded), layout, height, width, engine, batch_size, device,
+                      pu21_transfer=transfer, pu21_full_range=full_range)
     return tuple(np.ascontiguousarray(r[k]) for k in ("pu_psnr", "pu_psnr_rgb", "pu_ssim", "mse_y", "mse_rgb"))
 
 
@@ -405,14 +321,7 @@ def frame_fsim(reference, encoded, layout="bgr24", height=None, width=None, engi
     chroma, bgr24 as B, G, R, the gray layouts as luma alone (fsimc == fsim there) - the authors' FeatureSIM.m as recalled, not
     pinned against it.  Returns (fsim [n], fsimc [n]) float64, exactly 1 for identical frames, smaller is worse.  Plane 0 at least
     16 x 16; one- and three-plane layouts."""
-    reference, encoded = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
-    if not isinstance(reference, DeviceFrames) and reference.shape != encoded.shape:
-        raise ValueError("ref and dist must have the same shape")
-    h, w = _geometry(reference, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(encoded, reference, quality=stream.Quality(planes, fsim="only"), batch_size=batch_size, engine=engine,
-                      device=device)
-    r = q[-1]
+    r, _ = _only_pass("fsim", (reference, encoded), layout, height, width, engine, batch_size, device)
     return np.ascontiguousarray(r["fsim"]), np.ascontiguousarray(r["fsimc"])
 
 
@@ -424,16 +333,8 @@ def frame_sigstats(frames, layout="bgr24", height=None, width=None, engine=None,
     (32 and 24 on the 8-bit scale) or integers in sample units.  Returns the records [n,p] (engine.SIGSTATS_DTYPE); frame 0 has
     no predecessor.  events.signal_events turns them into black / frozen runs, cuts and the crop box.  Every plane at least
     16 x 16."""
-    frames = _host_stream(frames, wide=True)
-    h, w = _geometry(frames, layout, height, width)
-    planes = LAYOUTS[layout][0](h, w)
-    q, _ = stream.run(frames, frames, quality=stream.Quality(planes, sigstats="only", sigstats_black=black_level,
-                                                             sigstats_crop=crop_level),
-                      batch_size=batch_size, engine=engine, device=device)
-    return q[-1]
-
-
-PU21_PSNR_CAP = 100.0   # the row's PU_PSNR and PU_PSNR_RGB: a frame's value (inf for identical frames) is capped here before pooling
+    return _only_pass("sigstats", (frames,), layout, height, width, engine, batch_size, device, sigstats_black=black_level,
+                      sigstats_crop=crop_level)[0]
 
 
 def frame_scale(frames, layout, height, width, out_height, out_width, filter="bicubic", engine=None, batch_size=64, device=None):
@@ -490,6 +391,16 @@ def _brisque_model(model_path, range_path):
     return brisque_model.load_model(model_path, range_path)
 
 
+def _load_models(sw):
+    """the model files the switches (features.switches) name -> (VMAF model or None, BRISQUE model or None); loaded before the pass
+    starts, so a bad file costs no GPU time"""
+    model = None
+    if sw["vmaf_model_path"] is not None:
+        from . import vmaf_model
+        model = vmaf_model.load_model(sw["vmaf_model_path"])
+    return model, _brisque_model(sw.get("brisque_model_path"), sw.get("brisque_range_path"))
+
+
 def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, siti=None, psnr_hvs=None, ciede=None, gmsd=None,
                   cambi=None, xpsnr=None, haarpsi=None, vca=None, artifacts=None, brisque=None, brisque_model=None, mdsi=None,
                   delta_itp=None, pu21=None, fsim=None, sigstats=None, sigstats_depth=8, extra=None):
@@ -541,92 +452,13 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
     model: None, or a vmaf_model.VmafModel: every frame then also carries "vmaf" = vmaf_model.predict over the frame's logged
     features (a feature the model names and the log lacks is a ValueError), pooled like the features."""
     import json
-    names, cols = [], []
-    if scale is not None:
-        scale = np.asarray(scale, np.float64).reshape(-1, N.VIF_LEVELS)
-        names += ["vif_scale%d" % s for s in range(N.VIF_LEVELS)]
-        cols += [scale[:, s] for s in range(N.VIF_LEVELS)]
-    if adm is not None:
-        adm = np.asarray(adm).reshape(-1)
-        names += ["adm2"] + ["adm_scale%d" % s for s in range(N.ADM_LEVELS)]
-        cols += [adm["adm2"].astype(np.float64)] + [adm["scale"][:, s].astype(np.float64) for s in range(N.ADM_LEVELS)]
-    if motion is not None:
-        motion = np.asarray(motion).reshape(-1)
-        names += ["motion2", "motion"]
-        cols += [motion["motion2"].astype(np.float64), motion["motion"].astype(np.float64)]
-    if siti is not None:
-        siti = np.asarray(siti).reshape(-1)
-        names += ["si", "ti"]
-        cols += [siti["si"].astype(np.float64), siti["ti"].astype(np.float64)]
-    if psnr_hvs is not None:
-        psnr_hvs = np.asarray(psnr_hvs).reshape(-1)
-        names += ["psnr_hvs", "psnr_hvsm"]
-        cols += [np.minimum(psnr_hvs[k].astype(np.float64), PSNR_HVS_DB_CAP) for k in ("psnr_hvs", "psnr_hvsm")]
-    if ciede is not None:
-        ciede = np.asarray(ciede).reshape(-1)
-        names += ["ciede2000"]
-        cols += [np.minimum(ciede["ciede2000"].astype(np.float64), PSNR_HVS_DB_CAP)]
-    if gmsd is not None:
-        gmsd = np.asarray(gmsd).reshape(-1)
-        names += ["gmsd"]
-        cols += [gmsd["gmsd"].astype(np.float64)]
-    if cambi is not None:
-        cambi = np.asarray(cambi).reshape(-1)
-        names += ["cambi"]
-        cols += [cambi["cambi"].astype(np.float64)]
-    if xpsnr is not None:
-        xpsnr = np.asarray(xpsnr).reshape(-1)
-        names += ["xpsnr"]
-        cols += [np.minimum(xpsnr["xpsnr"].astype(np.float64), PSNR_HVS_DB_CAP)]
-    if haarpsi is not None:
-        haarpsi = np.asarray(haarpsi).reshape(-1)
-        names += ["haarpsi"]
-        cols += [haarpsi["haarpsi"].astype(np.float64)]
-    if vca is not None:
-        vca = np.asarray(vca).reshape(-1)
-        names += ["vca_e", "vca_h", "vca_l"]
-        cols += [vca[k].astype(np.float64) for k in ("e", "h", "l")]
-    if artifacts is not None:
-        artifacts = np.asarray(artifacts).reshape(-1)
-        names += ["blockiness", "blur", "noise"]
-        cols += [artifacts[k].astype(np.float64) for k in ("blockiness", "blur", "noise")]
-    if brisque is not None:
-        feats = np.asarray(brisque).reshape(-1)["features"].astype(np.float64).reshape(-1, 36)
-        names += ["brisque_%02d" % k for k in range(36)]
-        cols += [feats[:, k] for k in range(36)]
-        if brisque_model is not None:
-            from . import brisque_model as bm
-            names += ["brisque"]
-            cols += [bm.predict(brisque_model, feats)]
-    if mdsi is not None:
-        mdsi = np.asarray(mdsi).reshape(-1)
-        names += ["mdsi"]
-        cols += [mdsi["mdsi"].astype(np.float64)]
-    if delta_itp is not None:
-        delta_itp = np.asarray(delta_itp).reshape(-1)
-        names += ["delta_itp", "delta_itp_max"]
-        cols += [delta_itp["de_mean"].astype(np.float64), delta_itp["de_max"].astype(np.float64)]
-    if pu21 is not None:
-        pu21 = np.asarray(pu21).reshape(-1)
-        names += ["pu_psnr", "pu_psnr_rgb", "pu_ssim"]
-        cols += [np.minimum(pu21["pu_psnr"].astype(np.float64), PU21_PSNR_CAP),
-                 np.minimum(pu21["pu_psnr_rgb"].astype(np.float64), PU21_PSNR_CAP), pu21["pu_ssim"].astype(np.float64)]
-    if fsim is not None:
-        fsim = np.asarray(fsim).reshape(-1)
-        names += ["fsim", "fsimc"]
-        cols += [fsim["fsim"].astype(np.float64), fsim["fsimc"].astype(np.float64)]
-    signal = None
-    if sigstats is not None:
-        from . import events
-        sigstats = np.asarray(sigstats).reshape(-1)
-        ev = events.signal_events(sigstats, sigstats_depth)
-        count = sigstats["count"].astype(np.float64)
-        names += ["y_min", "y_low", "y_avg", "y_high", "y_max", "y_dif", "out_of_range", "black", "frozen", "scene_score"]
-        cols += [sigstats[k].astype(np.float64) for k in ("min", "low", "mean", "high", "max", "dif")]
-        cols += [(sigstats["under"].astype(np.float64) + sigstats["over_luma"].astype(np.float64)) / count,
-                 ev["black"].astype(np.float64), ev["frozen"].astype(np.float64), ev["scene_score"]]
-        signal = {"black_frames": int(ev["black"].sum()), "frozen_frames": int(ev["frozen"].sum()),
-                  "scene_cuts": len(ev["cuts"]), "crop": None if ev["crop"] is None else list(ev["crop"])}
+    given = dict(locals(), vif=scale)
+    names, cols, top = [], [], {}
+    for f in FEATURES:
+        if given[f.flag] is not None:
+            keys, columns, more = f.to_log(f, given[f.flag], given)
+            names, cols = names + keys, cols + columns
+            top.update(more)
     if model is not None:
         from . import vmaf_model
         score = vmaf_model.predict(model, vmaf_model.feature_matrix(model, dict(zip(names, cols))))
@@ -642,8 +474,7 @@ def write_vif_log(vmaf_log, scale=None, adm=None, *, motion=None, model=None, si
                          "harmonic_mean": float(len(x) / np.sum(1.0 / (x + 1.0)) - 1.0)}
     with open(vmaf_log, "w") as f:
         doc = {"frames": frames, "pooled_metrics": pooled}
-        if signal is not None:
-            doc["signal"] = signal
+        doc.update(top)
         if extra:
             doc.update(extra)
         json.dump(doc, f, indent=1)
@@ -810,13 +641,9 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
-    model = None
-    if vmaf_model_path is not None:
-        from . import vmaf_model
-        model = vmaf_model.load_model(vmaf_model_path)
-        vif = adm = motion = True
-    bmodel = _brisque_model(brisque_model_path, brisque_range_path)
-    brisque = bool(brisque) or bmodel is not None
+    given = dict(locals())
+    sw = switches(given)
+    models = _load_models(sw)
     scaling = _scale_request(scale, dist_height, dist_width)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
@@ -825,6 +652,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     if layout_d != layout:
         raise ValueError("reference and distorted streams must share a pixel layout")
     h, w = _geometry(ref, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
     dist_planes = extra = None
     if scaling:
         from .engine import check_scale_planes
@@ -832,53 +660,20 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if not dh or not dw:
             raise ValueError("scale needs the distorted stream's size: dist_height and dist_width")
         dist_planes = LAYOUTS[layout][0](dh, dw)
-        check_scale_planes(dist_planes, LAYOUTS[layout][0](h, w))
+        check_scale_planes(dist_planes, planes)
         extra = {"DIST_RES": "%dx%d" % (dw, dh), "SCALE": scale}
-    wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in LAYOUTS[layout][0](h, w)])
+    wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
     try:
-        if ciede and len(LAYOUTS[layout][1]) != 3:
-            raise ValueError("ciede needs three planes")
-        if xpsnr:
-            from .engine import check_xpsnr_planes
-            check_xpsnr_planes(LAYOUTS[layout][0](h, w))
-        if vca:
-            from .engine import check_vca_planes
-            check_vca_planes(LAYOUTS[layout][0](h, w))
-        if delta_itp:
-            if len(LAYOUTS[layout][1]) != 3:
-                raise ValueError("delta_itp needs three planes")
-            _check_itp(delta_itp_transfer, delta_itp_full_range)
-        if pu21:
-            if len(LAYOUTS[layout][1]) != 3:
-                raise ValueError("pu21 needs three planes")
-            _check_pu21(pu21_transfer, pu21_full_range)
-        kinds_on = any((vif, adm, motion, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, mdsi, delta_itp,
-                        pu21, fsim, sigstats))
-        if kinds_on or scaling:
-            rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
-            if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
-                raise ValueError("ref and dist must have the same shape")
-            q, _ = stream.run(ds, rs, quality=stream.Quality(LAYOUTS[layout][0](h, w), _SSIM_MODES[ssim_mode], vif=bool(vif),
-                                                             adm=bool(adm), motion=bool(motion), siti=bool(siti),
-                                                             psnr_hvs=bool(psnr_hvs), ciede=bool(ciede),
-                                                             ciede_weights=ciede_weights, gmsd=bool(gmsd),
-                                                             cambi=bool(cambi), xpsnr=bool(xpsnr),
-                                                             haarpsi=bool(haarpsi), vca=bool(vca),
-                                                             artifacts=bool(artifacts), brisque=brisque,
-                                                             mdsi=bool(mdsi), itp=bool(delta_itp),
-                                                             itp_transfer=delta_itp_transfer,
-                                                             itp_full_range=delta_itp_full_range, pu21=bool(pu21),
-                                                             pu21_transfer=pu21_transfer,
-                                                             pu21_full_range=pu21_full_range, fsim=bool(fsim),
-                                                             sigstats=bool(sigstats), sigstats_black=sigstats_black,
-                                                             sigstats_crop=sigstats_crop, dist_planes=dist_planes,
-                                                             scale=scale if scaling else None),
-                              batch_size=batch_size, on_quality=wr, device=device)
-            if kinds_on:
-                _write_feature_log(vmaf_log, q, vif, adm, motion, model, siti, psnr_hvs, ciede, gmsd, cambi, xpsnr, haarpsi, vca,
-                                   artifacts, brisque, bmodel, mdsi, delta_itp, pu21, fsim, sigstats, layout_depth(layout), extra)
-        else:
-            frame_quality(ref, dist, layout, ssim_mode, height, width, batch_size=batch_size, on_chunk=wr, device=device)
+        for f in FEATURES:
+            if sw[f.kind]:
+                _check_request(f, layout, given)
+                if f.plane_check is not None:
+                    f.plane_check(planes)
+        rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
+        if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
+            raise ValueError("ref and dist must have the same shape")
+        _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
+                 batch_size=batch_size, on_quality=wr, device=device)
     finally:
         wr.close()
     return None
@@ -913,24 +708,28 @@ MODE_KEYS = {
 }
 
 
-def _write_feature_log(vmaf_log, q, vif, adm, motion=False, model=None, siti=False, psnr_hvs=False, ciede=False, gmsd=False,
-                       cambi=False, xpsnr=False, haarpsi=False, vca=False, artifacts=False, brisque=False, brisque_model=None,
-                       mdsi=False, delta_itp=False, pu21=False, fsim=False, sigstats=False, sigstats_depth=8, extra=None):
-    """the first plane's VIF / ADM / motion / SI and TI / PSNR-HVS / GMSD / CAMBI / XPSNR / HaarPSI / VCA / blockiness, blur and
-    noise / BRISQUE / signal statistics and the frame's CIEDE2000, MDSI, dE_ITP, PU21 and FSIM figures of a pass (stream.run's quality tuple, whose
-    elements stream.records_by_kind names) -> vmaf_log"""
-    on = dict(vif=vif, adm=adm, motion=motion, siti=siti, psnr_hvs=psnr_hvs, ciede=ciede, gmsd=gmsd, cambi=cambi, xpsnr=xpsnr,
-              haarpsi=haarpsi, vca=vca, artifacts=artifacts, brisque=brisque, mdsi=mdsi, itp=delta_itp, pu21=pu21, fsim=fsim,
-              sigstats=sigstats)
+def _write_feature_log(vmaf_log, q, on, *, model=None, brisque_model=None, sigstats_depth=8, extra=None):
+    """a pass's records (stream.run's quality tuple, whose elements stream.records_by_kind names) -> vmaf_log: the first plane's of
+    the per-plane kinds, the frame's of the per-frame ones.  on: flag (FEATURES) -> switch, the flags that are off may be missing.
+    model: the VMAF model, which scores a pass that measured motion (with it, its other features)."""
+    on = {f.kind: bool(on.get(f.flag)) for f in FEATURES}
     rec = stream.records_by_kind(q, on)
-    # write_vif_log's keywords (the kinds' names but for dE_ITP's): the per-plane kinds' first plane, the per-frame kinds' records
-    log = {{"itp": "delta_itp"}.get(k.name, k.name): rec[k.name] if k.per_frame else rec[k.name][:, 0]
-           for k in stream.PLANE_KINDS if on[k.name]}
-    scale = log.pop("vif")["scale"] if vif else None
-    if sigstats:
-        log["sigstats_depth"] = sigstats_depth
-    write_vif_log(vmaf_log, scale, log.pop("adm", None), model=model if motion else None, brisque_model=brisque_model, extra=extra,
-                  **log)
+    log = {f.flag: rec[f.kind] if KINDS[f.kind].per_frame else rec[f.kind][:, 0] for f in FEATURES if on[f.kind]}
+    write_vif_log(vmaf_log, log.pop("vif", None), model=model if on["motion"] else None, brisque_model=brisque_model,
+                  sigstats_depth=sigstats_depth, extra=extra, **log)
+
+
+def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, **run):
+    """One pass (stream.run with its further arguments `run`) whose Quality the switches sw (features.switches) spell, and the feature
+    log of what it measured, when a kind is on.  models: _load_models(sw).  -> stream.run's pair"""
+    quality = stream.Quality(planes, ssim_mode, dist_planes=dist_planes, scale=scale,
+                             **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
+    q, series = stream.run(dist, ref, quality=quality, **run)
+    on = {f.flag: sw[f.kind] for f in FEATURES}
+    if any(on.values()):
+        _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
+                           extra=extra)
+    return q, series
 
 
 def _check_mode_keys(config):
@@ -940,68 +739,10 @@ def _check_mode_keys(config):
     dev = config.get("device")
     if dev is not None and (isinstance(dev, bool) or not isinstance(dev, int) or dev < 0):
         raise ValueError("device must be a non-negative integer.")
-    if "vif" in config and not isinstance(config["vif"], bool):
-        raise ValueError("vif must be true or false.")
-    if "adm" in config and not isinstance(config["adm"], bool):
-        raise ValueError("adm must be true or false.")
-    if "motion_feature" in config and not isinstance(config["motion_feature"], bool):
-        raise ValueError("motion_feature must be true or false.")
-    if "siti" in config and not isinstance(config["siti"], bool):
-        raise ValueError("siti must be true or false.")
-    if "psnr_hvs" in config and not isinstance(config["psnr_hvs"], bool):
-        raise ValueError("psnr_hvs must be true or false.")
-    if "ciede" in config and not isinstance(config["ciede"], bool):
-        raise ValueError("ciede must be true or false.")
-    if "gmsd" in config and not isinstance(config["gmsd"], bool):
-        raise ValueError("gmsd must be true or false.")
-    if "cambi" in config and not isinstance(config["cambi"], bool):
-        raise ValueError("cambi must be true or false.")
-    if "xpsnr" in config and not isinstance(config["xpsnr"], bool):
-        raise ValueError("xpsnr must be true or false.")
-    if "haarpsi" in config and not isinstance(config["haarpsi"], bool):
-        raise ValueError("haarpsi must be true or false.")
-    if "vca" in config and not isinstance(config["vca"], bool):
-        raise ValueError("vca must be true or false.")
-    if "artifacts" in config and not isinstance(config["artifacts"], bool):
-        raise ValueError("artifacts must be true or false.")
-    if "brisque" in config and not isinstance(config["brisque"], bool):
-        raise ValueError("brisque must be true or false.")
-    for key in ("brisque_model_path", "brisque_range_path"):
-        bp = config.get(key)
-        if bp is not None and not (isinstance(bp, str) and os.path.isfile(bp) and os.access(bp, os.R_OK)):
-            raise ValueError("%s must be null or the path of a readable file." % key)
-    if config.get("brisque_range_path") is not None and config.get("brisque_model_path") is None:
-        raise ValueError("brisque_range_path needs a brisque_model_path.")
-    if "mdsi" in config and not isinstance(config["mdsi"], bool):
-        raise ValueError("mdsi must be true or false.")
-    if "delta_itp" in config and not isinstance(config["delta_itp"], bool):
-        raise ValueError("delta_itp must be true or false.")
-    if "delta_itp_transfer" in config and not (isinstance(config["delta_itp_transfer"], str) and
-                                               config["delta_itp_transfer"] in N.ITP_TRANSFERS):
-        raise ValueError("delta_itp_transfer must be \"pq\" or \"hlg\".")
-    if "delta_itp_range" in config and not (isinstance(config["delta_itp_range"], str) and
-                                            config["delta_itp_range"] in ITP_RANGES):
-        raise ValueError("delta_itp_range must be \"limited\" or \"full\".")
-    if "fsim" in config and not isinstance(config["fsim"], bool):
-        raise ValueError("fsim must be true or false.")
-    if "sigstats" in config and not isinstance(config["sigstats"], bool):
-        raise ValueError("sigstats must be true or false.")
-    for key in ("sigstats_black", "sigstats_crop"):
-        v = config.get(key)
-        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= N.SIGSTATS_MAX_LEVEL):
-            raise ValueError("%s must be null or an integer from 0 to %d." % (key, N.SIGSTATS_MAX_LEVEL))
-    if "pu21" in config and not isinstance(config["pu21"], bool):
-        raise ValueError("pu21 must be true or false.")
-    if "pu21_transfer" in config and not (isinstance(config["pu21_transfer"], str) and
-                                          config["pu21_transfer"] in N.ITP_TRANSFERS):
-        raise ValueError("pu21_transfer must be \"pq\" or \"hlg\".")
-    if "pu21_range" in config and not (isinstance(config["pu21_range"], str) and config["pu21_range"] in ITP_RANGES):
-        raise ValueError("pu21_range must be \"limited\" or \"full\".")
-    if "ciede_weights" in config:
-        k = config["ciede_weights"]
-        if not (isinstance(k, (list, tuple)) and len(k) == 3 and
-                all(isinstance(x, (int, float)) and not isinstance(x, bool) and np.isfinite(x) and x > 0 for x in k)):
-            raise ValueError("ciede_weights must be three positive numbers [kL, kC, kH].")
+    for f in FEATURES:   # every kind's switch, then its parameters (validated whether the kind is on or not)
+        check_switch(f.config_key, config)
+        for p in f.params:
+            p.check(p.config, config)
     mp = config.get("vmaf_model_path")
     if mp is not None and not (isinstance(mp, str) and os.path.isfile(mp) and os.access(mp, os.R_OK)):
         raise ValueError("vmaf_model_path must be null or the path of a readable model file.")
@@ -1107,37 +848,10 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     interval = config.get("frame_interval", 10)
     batch_size = config.get("batch_size", 100)
     ssim_mode = _SSIM_MODES[config.get("ssim_mode", "gauss")]
-    vif = config.get("vif", False)
-    adm = config.get("adm", False)
-    mot = config.get("motion_feature", False)
-    siti = config.get("siti", False)
-    hvs = config.get("psnr_hvs", False)
-    cie = config.get("ciede", False)
-    cie_k = tuple(config.get("ciede_weights", N.CIEDE_WEIGHTS_CIE))
-    gms = config.get("gmsd", False)
-    cam = config.get("cambi", False)
-    xps = config.get("xpsnr", False)
-    hps = config.get("haarpsi", False)
-    vcs = config.get("vca", False)
-    art = config.get("artifacts", False)
-    bmodel = _brisque_model(config.get("brisque_model_path"), config.get("brisque_range_path"))
-    bsq = bool(config.get("brisque", False)) or bmodel is not None
-    mds = config.get("mdsi", False)
-    itp = config.get("delta_itp", False)
-    itp_tf = config.get("delta_itp_transfer", "pq")
-    itp_full = ITP_RANGES[config.get("delta_itp_range", "limited")]
-    pu = config.get("pu21", False)
-    pu_tf = config.get("pu21_transfer", "pq")
-    pu_full = ITP_RANGES[config.get("pu21_range", "limited")]
-    fsm = config.get("fsim", False)
-    sig, sig_black, sig_crop = config.get("sigstats", False), config.get("sigstats_black"), config.get("sigstats_crop")
+    sw = _config_switches(config)
+    models = _load_models(sw)   # before the pass starts: a bad file costs no GPU time
     scale = config.get("scale")
     scaling = scale is not None
-    model = None
-    if config.get("vmaf_model_path") is not None:   # loaded before the pass starts: a bad file costs no GPU time
-        from . import vmaf_model
-        model = vmaf_model.load_model(config["vmaf_model_path"])
-        vif = adm = mot = True
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -1193,31 +907,16 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
             dist_planes = LAYOUTS[layout][0](dh, dw)
             check_scale_planes(dist_planes, planes)
             extra = {"DIST_RES": "%dx%d" % (dw, dh), "SCALE": scale}
-        if xps:
-            from .engine import check_xpsnr_planes
-            check_xpsnr_planes(planes)
-        if vcs:
-            from .engine import check_vca_planes
-            check_vca_planes(planes)
-        wr = _StatsWriter(psnr_log, ssim_log, layout, [(p[0], p[1]) for p in planes])
+        for f in FEATURES:
+            if sw[f.kind] and f.plane_check is not None:
+                f.plane_check(planes)
+        wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
-            _q, series = stream.run(enc, ref, quality=stream.Quality(planes, ssim_mode, vif=vif, adm=adm, motion=mot, siti=siti,
-                                                                     psnr_hvs=hvs, ciede=cie, ciede_weights=cie_k,
-                                                                     gmsd=gms, cambi=cam, xpsnr=xps,
-                                                                     haarpsi=hps, vca=vcs, artifacts=art, brisque=bsq,
-                                                                     mdsi=mds, itp=itp, itp_transfer=itp_tf,
-                                                                     itp_full_range=itp_full, pu21=pu,
-                                                                     pu21_transfer=pu_tf, pu21_full_range=pu_full, fsim=fsm,
-                                                                     sigstats=sig, sigstats_black=sig_black,
-                                                                     sigstats_crop=sig_crop, dist_planes=dist_planes,
-                                                                     scale=scale),
-                                    complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
-                                    batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
+            _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
+                                  complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
+                                  batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
         finally:
             wr.close()
-        if any((vif, adm, mot, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, mds, itp, pu, fsm, sig)):
-            _write_feature_log(vmaf_log, _q, vif, adm, mot, model, siti, hvs, cie, gms, cam, xps, hps, vcs, art, bsq, bmodel,
-                               mds, itp, pu, fsm, sig, layout_depth(layout), extra)
         resolution = "%dx%d" % (ew, eh)
         metrics = extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, input_video, crf, bitrate, resolution, frame_rate)
         t = cm.pool_series(series, enc, interval, batch_size=batch_size, fps=frame_rate)
@@ -1263,66 +962,8 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             pooled, signal = {}, None
         if "vmaf" in pooled:       # (:172-173), placed where the reference puts it: right after SSIM
             metrics["VMAF"] = float(pooled["vmaf"]["mean"])
-        for s in range(N.VIF_LEVELS):
-            if "vif_scale%d" % s in pooled:
-                metrics["VIF_scale%d" % s] = float(pooled["vif_scale%d" % s]["mean"])
-        for k in ["adm2"] + ["adm_scale%d" % s for s in range(N.ADM_LEVELS)]:
-            if k in pooled:
-                metrics[k.upper().replace("SCALE", "scale")] = float(pooled[k]["mean"])
-        for k in ("motion2", "motion"):
-            if k in pooled:
-                metrics[k.upper()] = float(pooled[k]["mean"])
-        for k in ("si", "ti"):     # ITU-T P.910: the clip's value is the maximum over its frames
-            if k in pooled:
-                metrics[k.upper()] = float(pooled[k]["max"])
-        for k in ("psnr_hvs", "psnr_hvsm"):   # per-frame dB capped at 100 by the log's writer
-            if k in pooled:
-                metrics[k.upper()] = float(pooled[k]["mean"])
-        if "ciede2000" in pooled:             # likewise
-            metrics["CIEDE2000"] = float(pooled["ciede2000"]["mean"])
-        if "gmsd" in pooled:
-            metrics["GMSD"] = float(pooled["gmsd"]["mean"])
-        if "cambi" in pooled:
-            metrics["CAMBI"] = float(pooled["cambi"]["mean"])
-        if "xpsnr" in pooled:                 # per-frame dB capped at 100 by the log's writer
-            metrics["XPSNR"] = float(pooled["xpsnr"]["mean"])
-        if "haarpsi" in pooled:
-            metrics["HAARPSI"] = float(pooled["haarpsi"]["mean"])
-        if "vca_e" in pooled:                 # the pooled means; frame 0's vca_h = 0 is included
-            metrics["VCA_E"] = float(pooled["vca_e"]["mean"])
-            metrics["VCA_H"] = float(pooled["vca_h"]["mean"])
-            metrics["VCA_L"] = float(pooled["vca_l"]["mean"])
-        if "blockiness" in pooled:
-            metrics["BLOCKINESS"] = float(pooled["blockiness"]["mean"])
-            metrics["BLUR"] = float(pooled["blur"]["mean"])
-            metrics["NOISE"] = float(pooled["noise"]["mean"])
-        if "brisque_00" in pooled:
-            metrics["BRISQUE_ALPHA"] = float(pooled["brisque_00"]["mean"])
-            metrics["BRISQUE_SIGMA2"] = float(pooled["brisque_01"]["mean"])
-        if "brisque" in pooled:
-            metrics["BRISQUE"] = float(pooled["brisque"]["mean"])
-        if "mdsi" in pooled:
-            metrics["MDSI"] = float(pooled["mdsi"]["mean"])
-        if "delta_itp" in pooled:
-            metrics["DELTA_ITP"] = float(pooled["delta_itp"]["mean"])
-            metrics["DELTA_ITP_MAX"] = float(pooled["delta_itp_max"]["max"])
-        if "pu_psnr" in pooled:
-            metrics["PU_PSNR"] = float(pooled["pu_psnr"]["mean"])
-            metrics["PU_PSNR_RGB"] = float(pooled["pu_psnr_rgb"]["mean"])
-            metrics["PU_SSIM"] = float(pooled["pu_ssim"]["mean"])
-        if "fsim" in pooled:
-            metrics["FSIM"] = float(pooled["fsim"]["mean"])
-            metrics["FSIMC"] = float(pooled["fsimc"]["mean"])
-        if "y_low" in pooled and signal is not None:   # the source's signal statistics: extremes, a mean share and event counts
-            metrics["Y_LOW"] = float(pooled["y_low"]["min"])
-            metrics["Y_HIGH"] = float(pooled["y_high"]["max"])
-            metrics["OUT_OF_RANGE"] = float(pooled["out_of_range"]["mean"])
-            metrics["BLACK_FRAMES"] = int(signal["black_frames"])
-            metrics["FROZEN_FRAMES"] = int(signal["frozen_frames"])
-            metrics["SCENE_CUTS"] = int(signal["scene_cuts"])
-            crop = signal["crop"] if signal["crop"] is not None else (-1, -1, -1, -1)
-            for k, v in zip(("CROP_TOP", "CROP_BOTTOM", "CROP_LEFT", "CROP_RIGHT"), crop):
-                metrics[k] = int(v)
+        for f in FEATURES:         # (per-frame dB values were capped by the log's writer)
+            f.to_row(f, pooled, signal, metrics)
     return metrics
 
 
@@ -1345,8 +986,9 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    _check_mode_keys(config)  # this build's keys: ssim_mode, pixfmt, dct_mode, motion, device, batch_size, vif, adm, motion_feature, siti, psnr_hvs, ciede, ciede_weights, gmsd, cambi, xpsnr, haarpsi, vca, artifacts, brisque, brisque_model_path, brisque_range_path, mdsi, delta_itp, delta_itp_transfer, delta_itp_range, pu21, pu21_transfer, pu21_range, fsim, sigstats, sigstats_black, sigstats_crop;
-    #                           and that a vmaf_model_path names a readable file
+    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale request and every config key of FEATURES (the
+    # kinds' switches and their parameters); and that a vmaf_model_path names a readable file
+    _check_mode_keys(config)
 
 
 def main(argv=None):

@@ -242,11 +242,11 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     v = np.zeros((3, 1), VIF_DTYPE)
     v["scale"][:, 0, :] = vif
     q = (None, None, v, vca[:, None], rec[:, None])
-    vp._write_feature_log(again, q, True, False, vca=True, artifacts=True)
+    vp._write_feature_log(again, q, dict(vif=True, adm=False, vca=True, artifacts=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], True, False, vca=True)
+    vp._write_feature_log(again, q[:-1], dict(vif=True, adm=False, vca=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec[:, None]), False, False, artifacts=True)
+    vp._write_feature_log(again, (None, None, rec[:, None]), dict(vif=False, adm=False, artifacts=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

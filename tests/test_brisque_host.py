@@ -404,13 +404,13 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     v = np.zeros((3, 1), VIF_DTYPE)
     v["scale"][:, 0, :] = vif
     q = (None, None, v, art[:, None], rec[:, None])
-    vp._write_feature_log(again, q, True, False, artifacts=True, brisque=True)
+    vp._write_feature_log(again, q, dict(vif=True, adm=False, artifacts=True, brisque=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q, True, False, artifacts=True, brisque=True, brisque_model=model)
+    vp._write_feature_log(again, q, dict(vif=True, adm=False, artifacts=True, brisque=True), brisque_model=model)
     assert open(again, "rb").read() == open(scored, "rb").read()
-    vp._write_feature_log(again, q[:-1], True, False, artifacts=True)
+    vp._write_feature_log(again, q[:-1], dict(vif=True, adm=False, artifacts=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec[:, None]), False, False, brisque=True)
+    vp._write_feature_log(again, (None, None, rec[:, None]), dict(vif=False, adm=False, brisque=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

@@ -271,11 +271,11 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     v = np.zeros((3, 1), VIF_DTYPE)
     v["scale"][:, 0, :] = vif
     q = (None, None, v, adm[:, None], gm[:, None], rec[:, None])
-    vp._write_feature_log(again, q, True, True, False, None, False, False, False, True, True)
+    vp._write_feature_log(again, q, dict(vif=True, adm=True, motion=False, siti=False, psnr_hvs=False, ciede=False, gmsd=True, cambi=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], True, True, False, None, False, False, False, True)
+    vp._write_feature_log(again, q[:-1], dict(vif=True, adm=True, motion=False, siti=False, psnr_hvs=False, ciede=False, gmsd=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec[:, None]), False, False, False, None, False, False, False, False, True)
+    vp._write_feature_log(again, (None, None, rec[:, None]), dict(vif=False, adm=False, motion=False, siti=False, psnr_hvs=False, ciede=False, gmsd=False, cambi=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

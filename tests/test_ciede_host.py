@@ -282,11 +282,11 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     v = np.zeros((3, 1), VIF_DTYPE)
     v["scale"][:, 0, :] = vif
     q = (None, None, v, adm[:, None], mot[:, None], st[:, None], hv[:, None], rec)
-    vp._write_feature_log(again, q, True, True, True, None, True, True, True)
+    vp._write_feature_log(again, q, dict(vif=True, adm=True, motion=True, siti=True, psnr_hvs=True, ciede=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], True, True, True, None, True, True)
+    vp._write_feature_log(again, q[:-1], dict(vif=True, adm=True, motion=True, siti=True, psnr_hvs=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec), False, False, False, None, False, False, True)
+    vp._write_feature_log(again, (None, None, rec), dict(vif=False, adm=False, motion=False, siti=False, psnr_hvs=False, ciede=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

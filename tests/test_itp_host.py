@@ -261,11 +261,11 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     assert open(again, "rb").read() == open(old, "rb").read()
     # the pass's tuple -> the log: the last element is dE_ITP's [n], MDSI's [n] the one before it
     q = (None, None, md, rec)
-    vp._write_feature_log(again, q, False, False, mdsi=True, delta_itp=True)
+    vp._write_feature_log(again, q, dict(vif=False, adm=False, mdsi=True, delta_itp=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], False, False, mdsi=True)
+    vp._write_feature_log(again, q[:-1], dict(vif=False, adm=False, mdsi=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec), False, False, delta_itp=True)
+    vp._write_feature_log(again, (None, None, rec), dict(vif=False, adm=False, delta_itp=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

@@ -282,11 +282,11 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     assert open(again, "rb").read() == open(old, "rb").read()
     # the pass's tuple -> the log: the last element is MDSI's [n], BRISQUE's [n, p] the one before it
     q = (None, None, gm[:, None], bq[:, None], rec)
-    vp._write_feature_log(again, q, False, False, gmsd=True, brisque=True, mdsi=True)
+    vp._write_feature_log(again, q, dict(vif=False, adm=False, gmsd=True, brisque=True, mdsi=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], False, False, gmsd=True, brisque=True)
+    vp._write_feature_log(again, q[:-1], dict(vif=False, adm=False, gmsd=True, brisque=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec), False, False, mdsi=True)
+    vp._write_feature_log(again, (None, None, rec), dict(vif=False, adm=False, mdsi=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

@@ -225,9 +225,9 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     v = np.zeros((3, 1), VIF_DTYPE)
     v["scale"][:, 0, :] = vif
     q = (None, None, v, adm[:, None], mot[:, None], st[:, None], rec[:, None])
-    vp._write_feature_log(again, q, True, True, True, None, True, True)
+    vp._write_feature_log(again, q, dict(vif=True, adm=True, motion=True, siti=True, psnr_hvs=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], True, True, True, None, True)
+    vp._write_feature_log(again, q[:-1], dict(vif=True, adm=True, motion=True, siti=True))
     assert open(again, "rb").read() == open(old, "rb").read()
 
 

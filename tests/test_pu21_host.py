@@ -217,11 +217,11 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     assert open(again, "rb").read() == open(old, "rb").read()
     # the pass's tuple -> the log: the last element is PU21's [n], dE_ITP's [n] the one before it
     q = (None, None, it, rec)
-    vp._write_feature_log(again, q, False, False, delta_itp=True, pu21=True)
+    vp._write_feature_log(again, q, dict(vif=False, adm=False, delta_itp=True, pu21=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], False, False, delta_itp=True)
+    vp._write_feature_log(again, q[:-1], dict(vif=False, adm=False, delta_itp=True))
     assert open(again, "rb").read() == open(old, "rb").read()
-    vp._write_feature_log(again, (None, None, rec), False, False, pu21=True)
+    vp._write_feature_log(again, (None, None, rec), dict(vif=False, adm=False, pu21=True))
     assert open(again, "rb").read() == open(only, "rb").read()
 
 

@@ -252,9 +252,9 @@ def test_the_json_log_and_what_the_row_takes_from_it(tmp_path):
     assert open(again, "rb").read() == open(old, "rb").read()
     # the pass's tuple -> the log: the last element is the kind's [n, p], FSIM's [n] the one before it
     q = (None, None, fs, np.stack([rec, rec], axis=1))
-    vp._write_feature_log(again, q, False, False, fsim=True, sigstats=True)
+    vp._write_feature_log(again, q, dict(vif=False, adm=False, fsim=True, sigstats=True))
     assert open(again, "rb").read() == open(log, "rb").read()
-    vp._write_feature_log(again, q[:-1], False, False, fsim=True)
+    vp._write_feature_log(again, q[:-1], dict(vif=False, adm=False, fsim=True))
     assert open(again, "rb").read() == open(old, "rb").read()
 
 
