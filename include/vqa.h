@@ -1809,6 +1809,19 @@ VQA_API int vqa_allreduce(vqa_comm *comm, double *vals, int count);
  * which = 2: Canny edge map, 0/255                    [n][ph][pw]
  * which = 3: full-resolution gray (motion input)      [n][h][w]              */
 VQA_API int vqa_debug_read_plane(vqa_ctx *ctx, int which, int frame, uint8_t *dst, int dst_h, int dst_w);
+/* Copies float intermediates of the LAST CHUNK of the last VQA_MOTION_FARNEBACK submit to host memory (a submit is cut into
+ * chunks of pairs only when its scratch would pass ~12 GiB: a small batch is one chunk).  Pair i of a submit is
+ * (frame i - 1, frame i), pair 0 = (prev0, frame 0); gray plane q is prev0 for q = 0 and frame q - 1 otherwise.
+ * which = 0: the final flow field of pair `index`; level must be 0; dst is [h][w][2] (dx, dy), dst_h x dst_w = h x w.
+ * which = 1: the polynomial expansion of gray plane `index` at pyramid level `level` (0 = finest .. the coarsest the
+ *            frame size allows, at most 3); dst is [5][lh][lw], FIVE PLANES as the device keeps them, dst_h x dst_w =
+ *            lh x lw = lrint(h / 2^level) x lrint(w / 2^level).  Plane c holds coefficient c of OpenCV's [lh][lw][5]
+ *            layout (FarnebackPolyExp: 0, 1 = the linear terms in y and x, 2, 3 = the quadratic ones, 4 = the mixed one).
+ * VQA_ERR_STATE: no Farneback submit has completed its launches on this ctx, or its buffers were released since
+ * (vqa_trim).  VQA_ERR_INVALID: a pair or plane outside the last chunk (pair 0 and plane 0 of a submit without prev0
+ * among them), a level the pyramid does not have, dimensions that are not the level's.  Copy only; waits for the
+ * streams of the ctx first.  An added entry point, not a layout change: VQA_ABI_VERSION stays.                          */
+VQA_API int vqa_debug_read_farneback(vqa_ctx *ctx, int which, int index, int level, float *dst, int dst_h, int dst_w);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,9 @@ def lib():
         L.vqo_orb64_count.restype = C.c_int
         L.vqo_farneback_mean_mag.argtypes = [u8p, u8p, C.c_int, C.c_int, C.c_ssize_t, C.POINTER(C.c_float)]
         L.vqo_farneback_mean_mag.restype = C.c_double
+        L.vqo_farneback_expansion.argtypes = [u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.vqo_farneback_expansion.restype = C.c_int
         L.vqo_fb_prepare.argtypes = [C.c_int, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.POINTER(C.c_double)]
         L.vqo_fb_prepare.restype = None
@@ -249,6 +252,20 @@ def farneback(prev, curr, want_flow=False):
     if m < 0:
         raise MemoryError
     return (m, flow) if want_flow else m
+
+
+def farneback_expansion(gray, level):
+    """The polynomial expansion [lh][lw][5] (float32) of one gray plane at pyramid level `level` (0 = finest), exactly as
+    vqo_farneback_mean_mag forms it (blur, resize, FarnebackPolyExp) -> (expansion, coarser levels the frame has)."""
+    gray = _c(gray)
+    h, w = gray.shape
+    buf = np.zeros(h * w * 5, np.float32)
+    lh, lw = C.c_int(0), C.c_int(0)
+    levels = lib().vqo_farneback_expansion(_u8(gray), h, w, w, level, buf.ctypes.data_as(C.POINTER(C.c_float)),
+                                           C.byref(lh), C.byref(lw))
+    if levels < 0:
+        raise ValueError("level %d: a %dx%d frame has no such pyramid level (or out of memory)" % (level, h, w))
+    return buf[:lh.value * lw.value * 5].reshape(lh.value, lw.value, 5).copy(), levels
 
 
 def fb_prepare(n=5, sigma=1.2):

@@ -12,8 +12,12 @@
 // this translation unit is compiled with floating-point contraction OFF, so the float planes (blurred
 // images, expansions, products) are bit-identical to the oracle's: the 2x2 solve is ill-conditioned wherever
 // the image is flat or has a single orientation, and a fused multiply-add in the products would show up
-// in the flow there.  (The vertical box sums follow the oracle's order exactly; the horizontal ones differ from it at the
-// 1e-16 level only.)
+// in the flow there.  The pragma below needs -ffp-contract=fast-honor-pragmas: plain `fast`, the rest of the library's
+// setting, fuses in the backend regardless, and did so here until the expansions were first compared bit for bit - the
+// Makefile gives this file its own flag.  tests/test_gpu_farneback_field.py holds the expansions of every level to the
+// oracle's bits.  (The vertical box sums follow the oracle's order between restarts; the horizontal ones differ from it at
+// the 1e-16 level.  In the flow field that comes to at most 3.8e-6 absolute on textured frames with components of 2 to 3.6,
+// largest in the border rows and columns - inside the oracle's own float32-to-float64 distance)
 //
 // Structure per pyramid level (coarse to fine), for a chunk of frame pairs whose planes stay resident (round 4):
 //   k_fb_level3 / k_fb_level: float(gray) -> separable Gaussian (BORDER_REFLECT_101) -> resize to the level    (per plane,

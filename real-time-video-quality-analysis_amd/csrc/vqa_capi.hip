@@ -146,6 +146,15 @@ struct vqa_ctx {
     // geometry of the last complexity batch (debug reads)
     int last_n = 0, last_h = 0, last_w = 0, last_ph = 0, last_pw = 0, last_pp = 0, last_gp = 0;
     bool last_resized = false, last_has_full = false, last_has_state = false, last_has_planes = false;
+    // what the last chunk of the last Farneback submit left resident (vqa_debug_read_farneback): valid from the end of
+    // run_farneback until the next one begins, fails or the buffers are released
+    struct {
+        bool valid = false, first_valid = false; // first_valid: pair 0 / plane 0 of the submit exist (prev0 was given)
+        int levels = 0, h = 0, w = 0, lh[4] = {0, 0, 0, 0}, lw[4] = {0, 0, 0, 0};
+        size_t Roff[4] = {0, 0, 0, 0};           // floats from fb_R to level k's expansions: [planes][5][lh][lw]
+        int flow_buf = 0;                         // the final flow [pairs][h][w][2] is in fb_flow0 (0) or fb_flow1 (1)
+        int first_pair = 0, pairs = 0;            // the chunk's pairs, counted from the submit's first
+    } last_fb;
 
     // per-kernel timing
     bool prof_on = false;
@@ -653,6 +662,7 @@ static int run_farneback(vqa_ctx *c, hipStream_t st, const uint8_t *gray, int gp
         if (w * scale < min_size || h * scale < min_size) break;
     }
     levels = k;
+    c->last_fb.valid = false; // the buffers are about to be re-reserved and rewritten; set again when every launch is in
     const fb_poly PC = fb_poly_consts();
     const size_t P = (size_t)h * w;
     // per pair ~59 B/pixel of scratch (planes: blur tmp 4 + blurred 4 + level image 4 + expansions of every level 26.7;
@@ -826,7 +836,12 @@ static int run_farneback(vqa_ctx *c, hipStream_t st, const uint8_t *gray, int gp
         launch_fb_mag_finalize(st, (const double *)c->fb_part.p, fb_iter_blocks(pairs, h, w), pairs, h, w, a > 0 || first_has_prev,
                                res + a);
         if (piped && a + mc < n) HIPCHK(c, hipEventRecord(c->fb_ev[5], st));
+        c->last_fb.flow_buf = prev_flow == (float *)c->fb_flow0.p ? 0 : 1;
+        c->last_fb.first_pair = a; c->last_fb.pairs = pairs;
     }
+    c->last_fb.levels = levels; c->last_fb.h = h; c->last_fb.w = w; c->last_fb.first_valid = first_has_prev;
+    for (k = 0; k <= levels; k++) { c->last_fb.lh[k] = lhk[k]; c->last_fb.lw[k] = lwk[k]; c->last_fb.Roff[k] = Roff[k]; }
+    c->last_fb.valid = true;
     return VQA_OK;
 }
 
@@ -965,6 +980,7 @@ static void release_scratch(vqa_ctx *c)
     c->tabs.clear(); c->fb_tabs.clear(); c->dct_mats.clear(); c->fft_plans.clear(); c->fsim_tables.clear();
     // the planes vqa_debug_read_plane would read are gone
     c->last_n = 0; c->last_has_full = c->last_has_state = c->last_has_planes = false;
+    c->last_fb.valid = false;
     c->last_u_n = 0;
     c->last_f_n = 0;
 }
@@ -1307,6 +1323,7 @@ static int complexity_submit_body(vqa_ctx *c, const uint8_t *frames, const uint8
         prof_scope ps_(c, VQA_K_FARNEBACK);
         rc = run_farneback(c, st, gfull, gp, full_stride, n, h, w, has_prev0, res);
         if (rc) return rc;
+        c->last_fb.first_pair += a0; c->last_fb.first_valid = batch_has_prev0; // (counted from the submit's first pair, not the slice's)
     }
 
     // ---- Canny (input: plane B)
@@ -3202,6 +3219,30 @@ int vqa_debug_read_plane(vqa_ctx *c, int which, int frame, uint8_t *dst, int dst
     if (dst_h != h || dst_w != w) return VQA_ERR_INVALID;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy2D(dst, (size_t)w, src, (size_t)pitch, (size_t)w, (size_t)h, hipMemcpyDeviceToHost));
+    return VQA_OK;
+}
+
+int vqa_debug_read_farneback(vqa_ctx *c, int which, int index, int level, float *dst, int dst_h, int dst_w)
+{
+    if (!c || !dst || (which != 0 && which != 1)) return VQA_ERR_INVALID;
+    const auto &F = c->last_fb;
+    if (!F.valid) return VQA_ERR_STATE;
+    if (level < 0 || level > F.levels || (which == 0 && level != 0)) return VQA_ERR_INVALID;
+    if (dst_h != F.lh[level] || dst_w != F.lw[level]) return VQA_ERR_INVALID;
+    // pairs first_pair .. first_pair + pairs - 1 and their planes first_pair .. first_pair + pairs are resident
+    const int local = index - F.first_pair;
+    if (local < 0 || local >= F.pairs + which) return VQA_ERR_INVALID;
+    if (index == 0 && !F.first_valid) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = sync_all(c)) return rc; // the piped mode's expansions are written on the side stream
+    const size_t L = (size_t)F.lh[level] * F.lw[level];
+    if (which == 0) {
+        const float *flow = (const float *)(F.flow_buf ? c->fb_flow1.p : c->fb_flow0.p);
+        HIPCHK(c, hipMemcpy(dst, flow + (size_t)local * L * 2, sizeof(float) * L * 2, hipMemcpyDeviceToHost));
+    } else {
+        const float *R = (const float *)c->fb_R.p + F.Roff[level];
+        HIPCHK(c, hipMemcpy(dst, R + (size_t)local * L * 5, sizeof(float) * L * 5, hipMemcpyDeviceToHost));
+    }
     return VQA_OK;
 }
 

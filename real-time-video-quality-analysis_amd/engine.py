@@ -1210,3 +1210,18 @@ class Engine:
         st = self.lib.vqa_debug_read_plane(self.ctx, which, frame, out.ctypes.data, h, w)
         N.check(st, "vqa_debug_read_plane", self.ctx)
         return out
+
+    def debug_farneback_flow(self, pair, h, w):
+        """The final flow field [h][w][2] (dx, dy) of pair `pair` of the last Farneback submit (its last chunk)."""
+        out = np.empty((h, w, 2), np.float32)
+        st = self.lib.vqa_debug_read_farneback(self.ctx, 0, pair, 0, out.ctypes.data, h, w)
+        N.check(st, "vqa_debug_read_farneback", self.ctx)
+        return out
+
+    def debug_farneback_expansion(self, plane, level, lh, lw):
+        """The polynomial expansion of gray plane `plane` (0 = prev0, q = frame q - 1) at pyramid level `level` of the last
+        Farneback submit, as [lh][lw][5] like OpenCV keeps it (the device keeps, and the C call returns, five planes)."""
+        out = np.empty((5, lh, lw), np.float32)
+        st = self.lib.vqa_debug_read_farneback(self.ctx, 1, plane, level, out.ctypes.data, lh, lw)
+        N.check(st, "vqa_debug_read_farneback", self.ctx)
+        return np.ascontiguousarray(out.transpose(1, 2, 0))
