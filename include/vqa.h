@@ -1664,6 +1664,49 @@ VQA_API int vqa_scale_wait(vqa_ctx *ctx);
  * VQA_ERR_UNSUPPORTED.  in == out gives the formula's tables, which are the identity.                                         */
 VQA_API int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int32_t *count, int *ksize);
 
+/* ---- Temporal alignment: is the distorted stream the same frames as the reference, in the same places? ----
+ * Every full-reference kind above compares reference frame i with distorted frame i and trusts the caller that they belong
+ * together.  This kind measures that: the squared error between distorted frame j and reference frame j + offset + k for every
+ * k of a band -R .. R.  A dropped first frame, a repeated frame or a late start are read off the band by the host.
+ * Input: ONE plane descriptor, applied to both streams - plane 0 of a layout: the luma of planar YUV, the gray plane, or whatever
+ *   single plane the caller describes.  bit_depth 8 (0), or 9 .. 16 as little-endian uint16; samples above 2^depth - 1 are read
+ *   as they are.  Any offset, row_stride and pixel_step the other kinds accept: rows that start at odd addresses, padded rows, a
+ *   frame whose last row ends its allocation, and non-contiguous planes (pixel_step = 3: one channel of packed BGR) - the last
+ *   through a gather, THE SLOW PATH, which gives the same words.  No byte beyond offset + (h - 1) row_stride + w pixel_step of a
+ *   frame is read.  The streams have their own frame counts n_ref and n_dist and their own frame strides, and one mem_kind.
+ * Parameters: radius R, 0 <= R <= VQA_ALIGN_MAX_RADIUS, and an integer offset (any value).
+ * Output: sse[j][c], uint64, j = 0 .. n_dist - 1, c = 0 .. 2R, row-major, n_dist (2R + 1) words.  With k = c - R and
+ *   i = j + offset + k: sse[j][c] = sum over the plane of (d_j - r_i)^2, exact, if 0 <= i < n_ref; VQA_ALIGN_NONE otherwise.
+ * What follows: every word is an integer function of the samples of its two frames alone.  The same pair of frames gives the
+ *   same word whatever else is in the submit, from host, pinned or device memory, for any offset / radius / windowing that covers
+ *   it, alone or next to other kinds pending on the ctx.  Identical frames give exactly 0.
+ * How: with X = x - s (s = 128 for uint8, 32896 for uint16: the same shift on both sides, so it cancels in the difference),
+ *   sse = E_d[j] + E_r[i] - 2 C[j][i], E = sum X^2 per frame and C[j][i] = sum X_d,j X_r,i, a Gram matrix of frames over pixels on
+ *   the int8 matrix cores; a uint16 X is 256 (hi - 128) + (lo - 128) and its products are four int8 products.  32-bit
+ *   accumulators are added into 64-bit words before they can overflow (a product is at most 2^14; at most 2^16 of them are
+ *   added between two flushes); |C| <= E <= 2^28 32896^2 < 2^59 and sse <= 2^28 65535^2 < 2^60.  Integer adds only: neither the
+ *   tiling nor the order in which waves retire can change a bit.  vqa_align_wait forms sse and the VQA_ALIGN_NONE entries on
+ *   the host; the caller gets finished words.
+ * Limits: the plane at least 1 x 1 (this kind has no 16 x 16 floor) with h w <= 2^28; n_dist >= 1, n_ref >= 1; n_dist <= 32768
+ *   and n_ref <= 32768 + 64 per submit, VQA_ERR_UNSUPPORTED beyond (a longer clip is measured in windows: distorted frames
+ *   a .. b - 1 against reference frames max(a - R, 0) .. min(b + R, n) - 1 with offset = a - max(a - R, 0) give rows a .. b - 1 of
+ *   the whole clip's array).  R outside 0 .. 32 is VQA_ERR_INVALID.  The descriptor rules, memory kinds and the failure
+ *   guarantee are vqa_gmsd_submit's: a failed submit leaves nothing in flight; a frame stride smaller than the plane's span is
+ *   VQA_ERR_INVALID for a stream of more than one frame.
+ * An alignment batch is a batch of its own: VQA_ERR_STATE for a second submit while one is pending and for a wait without a
+ *   submit or with a word count that is not n_dist (2R + 1) (the batch stays pending); in flight next to every other kind.
+ *   Host frames are staged in the buffers the pair kinds share.  Scratch: 8 (n_dist (2R + 2) + n_ref) bytes on the device and
+ *   pinned, kept by the ctx until vqa_trim / vqa_destroy.
+ * Kernel: k_align_cross, ONE launch per submit.  Only 16 x 16 tiles of (distorted, reference) frames that meet the band are
+ *   computed; the frames that pad a tile to 16 are not read.
+ * Not built: a spatial shift or crop search; radii above 32; more than one plane; timestamps, frame-rate conversion, pulldown. */
+#define VQA_ALIGN_NONE UINT64_MAX
+#define VQA_ALIGN_MAX_RADIUS 32
+VQA_API int vqa_align_submit(vqa_ctx *ctx, const uint8_t *ref, int n_ref, const uint8_t *dist, int n_dist, int mem_kind,
+                             int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *plane, int offset,
+                             int radius);
+VQA_API int vqa_align_wait(vqa_ctx *ctx, uint64_t *sse, int64_t n_words);   /* n_words == n_dist * (2 radius + 1) */
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1766,7 +1809,12 @@ enum vqa_kernel_id {
                                 tests that rely on id 65 being unknown); id 65 stays unnamed                             */
     VQA_K_SCALE = 66,        /* vqa_scale_submit: both passes of the resampler, fused (one entry per group of planes alike on
                                 both sides)                                                                              */
-    VQA_K_MARGIN = 67        /* one past the last id: ... VQA_K_SIGSTATS_ACCUM .. VQA_K_FRINGE - 1 and VQA_K_SCALE .. VQA_K_MARGIN - 1 */
+    VQA_K_MARGIN = 67,       /* one past the last id: ... VQA_K_SIGSTATS_ACCUM .. VQA_K_FRINGE - 1 and VQA_K_SCALE .. VQA_K_MARGIN - 1 */
+    VQA_K_ALIGN_CROSS = 68,  /* vqa_align_submit: the Gram tiles of the band and E of every frame (one entry per submit); VQA_K_MARGIN
+                                stays 67 as the resampler shipped it (callers and tests rely on id 67 being unknown); id 67 stays
+                                unnamed                                                                                  */
+    VQA_K_LEDGE = 69         /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+                                one-past names list, and VQA_K_ALIGN_CROSS .. VQA_K_LEDGE - 1                             */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

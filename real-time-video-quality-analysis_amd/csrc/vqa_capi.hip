@@ -71,6 +71,8 @@ enum batch_kind {
     KIND_SIGSTATS,    // SIGSTATS_WORDS per entry, then the row and column sums of every entry; work: the histograms of one sub-slice
                       // (host frames and prev0: SI/TI's siti_stage, siti_prev)
     KIND_SCALE,       // no result words: the batch writes the caller's dst (host frames: scale_stage)
+    KIND_ALIGN,       // one word per (distorted frame, band column), then E of every distorted and every reference frame; the two
+                      // frame counts, offset and radius of the batch in flight are named members of the ctx (align_*)
     KIND_COUNT
 };
 
@@ -140,6 +142,7 @@ struct vqa_ctx {
     // pending work: the complexity batch here, a plane batch in its slot
     int pend_c = 0;
     bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
+    int align_n_ref = 0, align_n_dist = 0, align_offset = 0, align_radius = 0;   // the pending alignment batch (slot[KIND_ALIGN])
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
     int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what FSIM's kept maps hold (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
@@ -160,8 +163,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_MARGIN] = {0};
-    int64_t prof_n[VQA_K_MARGIN] = {0};
+    double prof_ms[VQA_K_LEDGE] = {0};
+    int64_t prof_n[VQA_K_LEDGE] = {0};
 };
 
 namespace {
@@ -3107,6 +3110,73 @@ int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int
 }
 
 // ---------------------------------------------------------------------------
+// Temporal alignment: plane 0 of both streams, every distorted frame against a band of reference frames.  A batch of its own,
+// ordered by the stream like a GMSD batch, whose host staging (qstage_*) it shares; the two streams have their own frame counts,
+// which is the one thing the shared frame does not carry: they are staged one by one.
+static int align_submit_body(vqa_ctx *c, const uint8_t *ref, int n_ref, const uint8_t *dist, int n_dist, int mem_kind, int64_t ref_fs,
+                             int64_t dist_fs, const vqa_plane_desc *plane, int offset, int radius, bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n_ref < n_dist ? n_ref : n_dist, plane, 1)) return VQA_ERR_INVALID;
+    if (radius < 0 || radius > VQA_ALIGN_MAX_RADIUS) return VQA_ERR_INVALID;
+    if (n_dist > ALIGN_MAX_DIST || n_ref > ALIGN_MAX_REF) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_ALIGN];
+    plane_batch B;
+    int rc = check_batch(s, n_ref, ref_fs, ref_fs, plane, 1, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, 1); });
+    if (rc) return rc;
+    if (n_dist > 1 && dist_fs < B.span) return VQA_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    touched = true;
+    if (mem_kind == VQA_MEM_HOST) {
+        if ((rc = stage(c, c->qstage_ref, ref, (size_t)(n_ref - 1) * ref_fs + B.span))) return rc;
+        if ((rc = stage(c, c->qstage_dist, dist, (size_t)(n_dist - 1) * dist_fs + B.span))) return rc;
+    }
+    hipStream_t st = c->stream;
+    const size_t band = 2 * (size_t)radius + 1, words = (size_t)n_dist * band, bytes = sizeof(unsigned long long) * (words + n_dist + n_ref);
+    if ((rc = ensure(c, s.dev, bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, bytes, st));
+    // a pair (j, k) with 0 <= j + offset + k < n_ref exists: only then is anything launched (and offset is small)
+    const int64_t lo = (int64_t)offset - radius, hi = (int64_t)n_dist - 1 + offset + radius;
+    if (hi >= 0 && lo < n_ref) {
+        unsigned long long *cross = (unsigned long long *)s.dev.p;
+        prof_scope ps_(c, VQA_K_ALIGN_CROSS);
+        launch_align_cross(st, ref, n_ref, dist, n_dist, ref_fs, dist_fs, plane[0], B.depth, offset, radius, cross, cross + words,
+                           cross + words + n_dist);
+    }
+    c->align_n_ref = n_ref; c->align_n_dist = n_dist; c->align_offset = offset; c->align_radius = radius;
+    return finish_batch(c, s, bytes, (int)words, plane, 1, B.depth);
+}
+
+int vqa_align_submit(vqa_ctx *c, const uint8_t *ref, int n_ref, const uint8_t *dist, int n_dist, int mem_kind, int64_t ref_frame_stride,
+                     int64_t dist_frame_stride, const vqa_plane_desc *plane, int offset, int radius)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return align_submit_body(c, ref, n_ref, dist, n_dist, mem_kind, ref_frame_stride, dist_frame_stride, plane, offset, radius,
+                                 touched);
+    });
+}
+
+// sse = E_d[j] + E_r[i] - 2 C[j][i] in 64-bit words (the true value is below 2^60, so the wrap-around arithmetic is exact)
+int vqa_align_wait(vqa_ctx *c, uint64_t *sse, int64_t n_words)
+{
+    batch_slot *s;
+    if (!c || !sse) return VQA_ERR_INVALID;
+    if (n_words != (int64_t)c->slot[KIND_ALIGN].entries) return VQA_ERR_STATE;
+    if (int rc = wait_pending(c, KIND_ALIGN, sse, (int)n_words, s)) return rc;
+    if (int rc = wait_synced(c)) return rc;
+    const int n_dist = c->align_n_dist, n_ref = c->align_n_ref, band = 2 * c->align_radius + 1;
+    const unsigned long long *cross = (const unsigned long long *)s->host.p, *ed = cross + (size_t)n_dist * band, *er = ed + n_dist;
+    for (int j = 0; j < n_dist; j++)
+        for (int k = 0; k < band; k++) {
+            const int64_t i = (int64_t)j + c->align_offset + k - c->align_radius;
+            const size_t at = (size_t)j * band + k;
+            sse[at] = i >= 0 && i < n_ref ? (uint64_t)(ed[j] + er[i] - 2 * cross[at]) : VQA_ALIGN_NONE;
+        }
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -3116,7 +3186,7 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_MARGIN || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_LEDGE || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
@@ -3174,6 +3244,7 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_SIGSTATS_ACCUM) return "k_sigstats_accum";
     if (id == VQA_K_SIGSTATS_SCAN) return "k_sigstats_scan";
     if (id == VQA_K_SCALE) return "k_scale";
+    if (id == VQA_K_ALIGN_CROSS) return "k_align_cross";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -646,4 +646,15 @@ struct scale_job {
 // n frames of `count` planes (the job's offsets): grid (tiles, n, count)
 void launch_scale(hipStream_t st, const scale_job &job, int n, int count, int depth);
 
+// Temporal alignment (vqa_align_submit): k_align.hip
+constexpr int ALIGN_MAX_DIST = 32768, ALIGN_MAX_REF = 32768 + 64;   // frames of one submit
+// One launch for the whole band of the whole submit: adds C[j][i] = sum X_d,j X_r,i into cross[j * (2 radius + 1) + c] for the pairs
+// of the band (c = i - j - offset + radius, 0 <= i < n_ref), sum X_d,j^2 into e_dist[j] and sum X_r,i^2 into e_ref[i] for every
+// frame some pair of the band names; two's complement uint64 words the submit has zeroed.  false: no pair of the band exists
+// and nothing was launched.  |offset| must be small enough for 16 n + offset + radius to stay inside int: the caller launches
+// only where a pair exists, which bounds it by the frame counts.
+bool launch_align_cross(hipStream_t st, const uint8_t *ref, int n_ref, const uint8_t *dist, int n_dist, int64_t ref_frame_stride,
+                        int64_t dist_frame_stride, const vqa_plane_desc &plane, int depth, int offset, int radius,
+                        unsigned long long *cross, unsigned long long *e_dist, unsigned long long *e_ref);
+
 } // namespace vqa

@@ -419,11 +419,12 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
-                     "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait,
+                     "_pending_l": self.align_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1174,6 +1175,45 @@ class Engine:
         self.scale_wait()
         return res
 
+    # ---- temporal alignment ------------------------------------------------------------
+    def align_submit(self, ref, dist, planes, radius=8, offset=0, plane=0, frame_bytes=None, dist_frame_bytes=None):
+        """The squared error of planes[plane] between distorted frame j and reference frame j + offset + k, k = -radius ..
+        radius (vqa_align_submit).  ref, dist: uint8 / uint16 arrays (the first axis is the frame; the other type than the
+        planes' depth says is a ValueError, not a cast) or DeviceFrames, roi and strided views included - the two streams may
+        hold different numbers of frames.  frame_bytes: the frame stride of host arrays (dist_frame_bytes: the distorted
+        stream's, where it differs).  planes[plane] is what is measured, at least 1 x 1.  A batch of its own, like gmsd_submit."""
+        one = [planes[plane]]
+        dev = isinstance(ref, DeviceFrames)
+        if dev and not isinstance(dist, DeviceFrames):
+            raise TypeError("ref and dist must both be DeviceFrames or both be arrays")
+        rp, ref = self._stream_arg(ref, one, dev)
+        dp, dist = self._stream_arg(dist, one, dev)
+        if dev:
+            n_ref, n_dist, rfs, dfs, kind = ref.n, dist.n, ref.frame_stride, dist.frame_stride, N.VQA_MEM_DEVICE
+        else:
+            n_ref, n_dist, kind = ref.shape[0], dist.shape[0], N.VQA_MEM_HOST
+            if not n_ref or not n_dist:
+                raise ValueError("ref and dist must hold at least one frame each")
+            rfs = int(frame_bytes) if frame_bytes else ref.nbytes // n_ref
+            dfs = int(dist_frame_bytes) if dist_frame_bytes else (int(frame_bytes) if frame_bytes else dist.nbytes // n_dist)
+        st = self.lib.vqa_align_submit(self.ctx, rp, n_ref, dp, n_dist, kind, rfs, dfs, plane_descs(one), int(offset), int(radius))
+        N.check(st, "vqa_align_submit", self.ctx)
+        self._pending_l = (n_dist, 2 * int(radius) + 1, (ref, dist))
+
+    def align_wait(self):
+        """-> uint64 [n_dist, 2 radius + 1]: column c is k = c - radius; N.ALIGN_NONE where the reference frame does not exist."""
+        n, band, _keep = getattr(self, "_pending_l", None) or (1, 1, None)   # (nothing pending: the library says so)
+        out = np.zeros((n, band), np.uint64)
+        st = self.lib.vqa_align_wait(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size)
+        self._pending_l = None
+        N.check(st, "vqa_align_wait", self.ctx)
+        return out
+
+    def align(self, ref, dist, planes, radius=8, offset=0, plane=0, frame_bytes=None, dist_frame_bytes=None):
+        """align_submit and align_wait -> uint64 [n_dist, 2 radius + 1]; align.analyse reads offset, drops and repeats off it."""
+        self.align_submit(ref, dist, planes, radius, offset, plane, frame_bytes, dist_frame_bytes)
+        return self.align_wait()
+
     def download(self, dev, dtype=None):
         """Copy DeviceFrames back -> a host array [n, frame_stride / itemsize] (uint8, or uint16 for itemsize 2)."""
         dt = np.dtype(dtype) if dtype is not None else np.dtype(np.uint16 if dev.itemsize == 2 else np.uint8)
@@ -1196,7 +1236,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_PRESENT:
+        for k in N.K_IDS_CURRENT:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

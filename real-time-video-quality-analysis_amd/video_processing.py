@@ -365,6 +365,73 @@ def frame_scale(frames, layout, height, width, out_height, out_width, filter="bi
     return out
 
 
+ALIGN_WINDOW = 4096   # the distorted frames of one submit of frame_align (the C limit is 32768)
+
+
+def _align_request(align, scale=None):
+    """the align argument / config key -> the radius, or None when alignment is off; a ValueError for anything else"""
+    if align is None:
+        return None
+    if isinstance(align, bool) or not isinstance(align, (int, np.integer)) or not 1 <= align <= N.ALIGN_MAX_RADIUS:
+        raise ValueError("align must be null or an integer radius from 1 to %d." % N.ALIGN_MAX_RADIUS)
+    if scale is not None:
+        raise ValueError("align and scale do not go together: a ladder rung is not aligned at its own size.")
+    return int(align)
+
+
+def frame_align(reference, encoded, layout, height=None, width=None, radius=8, engine=None, device=None, window=ALIGN_WINDOW):
+    """Temporal alignment of two whole clips of any lengths (Engine.align, include/vqa.h): the squared error of plane 0 of the
+    layout between encoded frame j and reference frame j + k, k = -radius .. radius, and what align.analyse reads off it.  The
+    encoded stream is walked in windows of `window` frames; a window [a, b) submits the reference frames [a - radius, b + radius),
+    clipped, with the matching offset, and the bands are joined - any window size gives the same array.  -> analyse's dict
+    (offset, match, ref_index, dropped, repeated, mismatched, sse_given, sse_aligned, psnr_gain) plus "sse", uint64
+    [n, 2 radius + 1] with align.NONE where the reference frame does not exist.  Nothing is re-paired."""
+    from . import align as A
+    R, window = int(radius), int(window)
+    if not 0 <= R <= N.ALIGN_MAX_RADIUS:
+        raise ValueError("radius must be an integer from 0 to %d." % N.ALIGN_MAX_RADIUS)
+    if not 1 <= window <= N.ALIGN_MAX_DIST:
+        raise ValueError("window must be an integer from 1 to %d." % N.ALIGN_MAX_DIST)
+    ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    h, w = _geometry(ref, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+
+    def count(a):
+        return a.n if isinstance(a, DeviceFrames) else a.shape[0]
+
+    def part(a, lo, hi):
+        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
+
+    n_ref, n = count(ref), count(enc)
+    if not n_ref or not n:
+        raise ValueError("both clips must hold at least one frame")
+    sse = np.full((n, 2 * R + 1), A.NONE, np.uint64)
+    eng = engine if engine is not None else stream.get_engine(device)
+    with stream.pass_lock(eng.device):
+        for a in range(0, n, window):
+            b, lo = min(n, a + window), max(a - R, 0)
+            hi = min(b + R, n_ref)
+            if hi > lo:   # (else: no reference frame near this window, its rows stay NONE)
+                sse[a:b] = eng.align(part(ref, lo, hi), part(enc, a, b), planes, R, offset=a - lo)
+    out = A.analyse(sse)
+    out["sse"] = sse
+    return out
+
+
+def align_extra(result, radius):
+    """frame_align's (align.analyse's) dict -> the five top-level keys of the log and the row; a clip that is not aligned is
+    also a warning in the log of this module"""
+    import logging
+    from . import align as A
+    extra = A.log_keys(result, radius)
+    if extra["ALIGN_OFFSET"] or extra["ALIGN_DROPPED"] or extra["ALIGN_REPEATED"]:
+        logging.getLogger(__name__).warning(
+            "the distorted stream is not aligned with the reference: offset %d, %d dropped, %d repeated frame(s); pairing the "
+            "frames as given costs %.2f dB of PSNR (the frames are NOT re-paired)", extra["ALIGN_OFFSET"], extra["ALIGN_DROPPED"],
+            extra["ALIGN_REPEATED"], extra["ALIGN_PSNR_GAIN"])
+    return extra
+
+
 def _scale_request(scale, dist_height, dist_width):
     """the three arguments that turn scaling on -> whether it is on; a ValueError for a set that does not fit together"""
     for name, v in (("dist_height", dist_height), ("dist_width", dist_width)):
@@ -588,7 +655,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
-                       dist_height=None, dist_width=None, scale=None):
+                       dist_height=None, dist_width=None, scale=None, align=None):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -638,6 +705,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     (frame_cambi and the other frame_* calls on the rung itself give the native figure).  vmaf_log, when written, gains the
     top-level keys "DIST_RES" ("1280x720") and "SCALE".  Without scale, streams of different sizes stay the error they were,
     dist_height / dist_width alone are a ValueError, and every file is byte for byte what it was.
+    align=R (an integer radius 1 .. 32; default None): before the pass starts, a pass of its own (frame_align) measures whether
+    the distorted stream holds the reference's frames in the reference's places - its answer is about how the frames are PAIRED,
+    which is what the pass takes on trust.  vmaf_log is then written in any case and gains the top-level keys "ALIGN_RADIUS",
+    "ALIGN_OFFSET", "ALIGN_DROPPED", "ALIGN_REPEATED" and "ALIGN_PSNR_GAIN" (align.analyse); a non-zero offset, drop or repeat is
+    also logged as a warning.  The frames are NOT re-paired: nothing is changed silently.  align with scale is a ValueError.
+    Without align every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -645,6 +718,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     sw = switches(given)
     models = _load_models(sw)
     scaling = _scale_request(scale, dist_height, dist_width)
+    radius = _align_request(align, scale)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -672,6 +746,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
         if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
             raise ValueError("ref and dist must have the same shape")
+        if radius is not None:
+            extra = align_extra(frame_align(rs, ds, layout, h, w, radius, device=device), radius)
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
                  batch_size=batch_size, on_quality=wr, device=device)
     finally:
@@ -726,7 +802,7 @@ def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scal
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
-    if any(on.values()):
+    if any(on.values()) or (extra and "ALIGN_RADIUS" in extra):   # (an alignment pre-pass always has something to say)
         _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
                            extra=extra)
     return q, series
@@ -754,6 +830,7 @@ def _check_mode_keys(config):
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v <= 0):
             raise ValueError("height and width must be positive integers.")
     _scale_request(config.get("scale"), config.get("dist_height"), config.get("dist_width"))
+    _align_request(config.get("align"), config.get("scale"))
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -836,7 +913,11 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         stream when it is a ladder rung smaller or larger than the input; .y4m files bring theirs): the rung is uploaded at its
         own size and resampled to the input's on the GPU before anything measures it (run_ffmpeg_metrics), encoded_bgr stays at
         the rung's size for the complexity half, and the row gains DIST_RES ("1280x720") and SCALE as its LAST columns; needs
-        encoded_bgr next to a planar pair (one BGR stream cannot serve both halves at two sizes: ValueError).
+        encoded_bgr next to a planar pair (one BGR stream cannot serve both halves at two sizes: ValueError),
+        align (null default | an integer radius 1 .. 32): a pre-pass of its own (frame_align) measures, before the pass starts,
+        whether the encoded pair stream holds the input's frames in the input's places, and the row gains ALIGN_RADIUS,
+        ALIGN_OFFSET, ALIGN_DROPPED, ALIGN_REPEATED and ALIGN_PSNR_GAIN as its LAST columns; an offset, drop or repeat is also
+        a warning; the frames are not re-paired; with scale it is a ValueError.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -852,6 +933,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     models = _load_models(sw)   # before the pass starts: a bad file costs no GPU time
     scale = config.get("scale")
     scaling = scale is not None
+    radius = _align_request(config.get("align"), scale)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -910,6 +992,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         for f in FEATURES:
             if sw[f.kind] and f.plane_check is not None:
                 f.plane_check(planes)
+        if radius is not None:   # the alignment pre-pass over the quality pair, before the pass starts
+            extra = align_extra(frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius, device=device), radius)
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
@@ -931,6 +1015,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
+        if radius is not None:   # (extract_metrics_from_logs read them off the log: they go last)
+            metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
     finally:
@@ -957,13 +1043,16 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         try:
             with open(vmaf_log) as f:
                 doc = json.load(f)
-            pooled, signal = doc.get("pooled_metrics", {}), doc.get("signal")
+            pooled, signal, doc_top = doc.get("pooled_metrics", {}), doc.get("signal"), doc
         except (ValueError, AttributeError):   # not a JSON log (libvmaf writes XML by default): nothing to add
-            pooled, signal = {}, None
+            pooled, signal, doc_top = {}, None, None
         if "vmaf" in pooled:       # (:172-173), placed where the reference puts it: right after SSIM
             metrics["VMAF"] = float(pooled["vmaf"]["mean"])
         for f in FEATURES:         # (per-frame dB values were capped by the log's writer)
             f.to_row(f, pooled, signal, metrics)
+        from .align import ALIGN_KEYS
+        if isinstance(doc_top, dict) and all(k in doc_top for k in ALIGN_KEYS):   # an alignment pre-pass: the row's last columns
+            metrics.update((k, doc_top[k]) for k in ALIGN_KEYS)
     return metrics
 
 
