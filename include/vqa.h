@@ -1699,13 +1699,65 @@ VQA_API int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *x
  *   pinned, kept by the ctx until vqa_trim / vqa_destroy.
  * Kernel: k_align_cross, ONE launch per submit.  Only 16 x 16 tiles of (distorted, reference) frames that meet the band are
  *   computed; the frames that pad a tile to 16 are not read.
- * Not built: a spatial shift or crop search; radii above 32; more than one plane; timestamps, frame-rate conversion, pulldown. */
+ * Not built: a crop search (a spatial shift is vqa_shift_submit's); radii above 32; more than one plane; timestamps, frame-rate
+ *   conversion, pulldown. */
 #define VQA_ALIGN_NONE UINT64_MAX
 #define VQA_ALIGN_MAX_RADIUS 32
 VQA_API int vqa_align_submit(vqa_ctx *ctx, const uint8_t *ref, int n_ref, const uint8_t *dist, int n_dist, int mem_kind,
                              int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *plane, int offset,
                              int radius);
 VQA_API int vqa_align_wait(vqa_ctx *ctx, uint64_t *sse, int64_t n_words);   /* n_words == n_dist * (2 radius + 1) */
+
+/* ---- Spatial registration: does the distorted picture sit where the reference picture sits? ----
+ * Every full-reference kind above compares sample (y, x) of the reference with sample (y, x) of the distorted frame and trusts
+ * the caller that the two pictures sit in the same place.  This kind measures that: the squared error between each distorted
+ * frame and its reference frame for every integer shift (dy, dx) of a square band -R .. R.  A scaler with another siting, a crop
+ * that is off by two or a capture with a one-line offset are read off the grid by the host.
+ * Input: ONE plane descriptor, applied to both streams - plane 0 of a layout, or whatever single plane the caller describes.
+ *   bit_depth 8 (0), or 9 .. 16 as little-endian uint16; samples above 2^depth - 1 are read as they are.  Any offset,
+ *   row_stride and pixel_step vqa_align_submit accepts: rows that start at odd addresses, padded rows, a frame whose last row
+ *   ends its allocation, and non-contiguous planes (pixel_step = 3: one channel of packed BGR) - the last through a gather,
+ *   THE SLOW PATH, which gives the same words.  No byte beyond offset + (h - 1) row_stride + w pixel_step of a frame is read
+ *   on either stream.  n frames per stream, frame j against frame j; each stream has its own frame stride; one mem_kind.
+ * Parameters: radius R, 1 <= R <= VQA_SHIFT_MAX_RADIUS, and margin M >= R.
+ * Output: sse[j][a][b], uint64, a = dy + R, b = dx + R, row-major, n (2R + 1)^2 words:
+ *   sse[j][a][b] = sum over M <= y < h - M, M <= x < w - M of (d_j(y, x) - r_j(y + dy, x + dx))^2, exact.
+ *   Every shift is summed over the SAME core of (h - 2M)(w - 2M) distorted samples: the entries of a grid are comparable
+ *   without normalisation, and no sample outside the reference plane is ever needed, because M >= R.
+ * The sign: a minimum at (dy, dx) says that the distorted picture shows at (y, x) what the reference shows at (y + dy, x + dx) -
+ *   the picture has moved up by dy rows and left by dx samples on its way through the chain (down and right where they are
+ *   negative), and the reference read at (y + dy, x + dx) is the frame to compare with.
+ * What follows: every word is an integer function of the samples of its two frames, M and (dy, dx) alone.  The same pair gives
+ *   the same word under any R that contains the shift at the same M, in any batch and at any position in it, from host, pinned
+ *   or device memory, alone or next to other kinds pending on the ctx.  Identical frames give exactly 0 at (0, 0); a distorted
+ *   frame that is the reference translated by (dy, dx) inside the core gives exactly 0 at that entry.
+ * How: with X = x - s (s = 128 for uint8, 32896 for uint16: the same shift on both sides, so it cancels),
+ *   sse(dy, dx) = E_d + E_r(dy, dx) - 2 C(dy, dx): E_d the core's sum of X_d^2, E_r(dy, dx) the sum of X_r^2 over the core moved
+ *   by the shift, and C(dy, dx) = sum X_d(y, x) X_r(y + dy, x + dx), a cross-correlation taken as a Toeplitz product on the int8
+ *   matrix cores: for a reference row y' and 64 core columns from x0 on, A[m][k] = X_d(y' - dy_m, x0 + k) (zero outside the core)
+ *   and B[k][n] = X_r(y', x0 + k + dx_n), so one instruction adds 64 samples into a 16 (dy) x 16 (dx) tile of C; R <= 7 is one
+ *   tile, R = 8 .. 15 four, R = 16 nine.  A uint16 X is 256 (hi - 128) + (lo - 128) and its products are four int8 products.
+ *   E_r comes from the B operand cut to the core's columns, squared with the dot-product instruction, per reference row and dx,
+ *   and added to the dy whose core holds that row: no second read of the plane.  32-bit accumulators are added into 64-bit words
+ *   before they can overflow (a product is at most 2^14; at most 2^16 of them are added between two flushes); |C| <= E <=
+ *   2^28 32896^2 < 2^59 and sse <= 2^28 65535^2 < 2^60.  Integer adds only: neither the tiling nor the order in which waves
+ *   retire can change a bit.  vqa_shift_wait adds E_d on the host; the caller gets finished words.
+ * Limits: h >= 2M + 1 and w >= 2M + 1 (a core of at least one sample), else VQA_ERR_UNSUPPORTED; h w <= 2^28; 1 <= n <= 32768
+ *   per submit, VQA_ERR_UNSUPPORTED beyond (a longer clip is measured in windows).  R outside 1 .. 16 or M < R is
+ *   VQA_ERR_INVALID.  The descriptor rules, memory kinds and the failure guarantee are vqa_align_submit's: a failed submit
+ *   leaves nothing in flight; a frame stride smaller than the plane's span is VQA_ERR_INVALID for a stream of more than one
+ *   frame.
+ * A registration batch is a batch of its own: VQA_ERR_STATE for a second submit while one is pending and for a wait without a
+ *   submit or with a word count that is not n (2R + 1)^2 (the batch stays pending); in flight next to every other kind.  Host
+ *   frames are staged in the buffers the pair kinds share.  Scratch: 8 n ((2R + 1)^2 + 1) bytes on the device and pinned, kept
+ *   by the ctx until vqa_trim / vqa_destroy.
+ * Kernel: k_shift, ONE launch per submit.  Rows and columns that pad a tile beyond 2R + 1 are not read.
+ * Not built: moving the pass by the found shift; a sub-pixel search on the GPU (the host fits a parabola to the integer grid);
+ *   a per-plane or chroma-siting search; scale or rotation; a shift search combined with the temporal band; radii above 16. */
+#define VQA_SHIFT_MAX_RADIUS 16
+VQA_API int vqa_shift_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int n, int mem_kind, int64_t ref_frame_stride,
+                             int64_t dist_frame_stride, const vqa_plane_desc *plane, int radius, int margin);
+VQA_API int vqa_shift_wait(vqa_ctx *ctx, uint64_t *sse, int64_t n_words);   /* n_words == n * (2 radius + 1)^2 */
 
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
@@ -1813,8 +1865,13 @@ enum vqa_kernel_id {
     VQA_K_ALIGN_CROSS = 68,  /* vqa_align_submit: the Gram tiles of the band and E of every frame (one entry per submit); VQA_K_MARGIN
                                 stays 67 as the resampler shipped it (callers and tests rely on id 67 being unknown); id 67 stays
                                 unnamed                                                                                  */
-    VQA_K_LEDGE = 69         /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+    VQA_K_LEDGE = 69,        /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
                                 one-past names list, and VQA_K_ALIGN_CROSS .. VQA_K_LEDGE - 1                             */
+    VQA_K_SHIFT = 70,        /* vqa_shift_submit: the tiles of the grid of shifts, E_r and E_d (one entry per submit); VQA_K_LEDGE
+                                stays 69 as the alignment shipped it (callers and tests rely on id 69 being unknown); id 69 stays
+                                unnamed                                                                                  */
+    VQA_K_SILL = 71          /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+                                one-past names list, and VQA_K_SHIFT .. VQA_K_SILL - 1                                    */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

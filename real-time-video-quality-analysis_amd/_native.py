@@ -77,7 +77,9 @@ K_IDS_COMPLETE = K_IDS_ENTIRE + (K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN)   # the ids 
 K_SCALE, K_MARGIN = 66, 67                        # added beyond K_FRINGE, which stays 65; id 65 is unnamed
 K_IDS_PRESENT = K_IDS_COMPLETE + (K_SCALE,)       # the ids below K_MARGIN (kept as the resampler shipped it)
 K_ALIGN_CROSS, K_LEDGE = 68, 69                   # added beyond K_MARGIN, which stays 67; id 67 is unnamed
-K_IDS_CURRENT = K_IDS_PRESENT + (K_ALIGN_CROSS,)  # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_CURRENT = K_IDS_PRESENT + (K_ALIGN_CROSS,)  # the ids below K_LEDGE (kept as the alignment shipped it)
+K_SHIFT, K_SILL = 70, 71                          # added beyond K_LEDGE, which stays 69; id 69 is unnamed
+K_IDS_LATEST = K_IDS_CURRENT + (K_SHIFT,)         # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -128,6 +130,9 @@ SCALE_MAX_SAMPLES = 1 << 28   # h w of every plane of both lists
 ALIGN_NONE = (1 << 64) - 1    # vqa_align_wait: the word of a pair whose reference frame does not exist
 ALIGN_MAX_RADIUS = 32         # vqa_align_submit: the largest band radius
 ALIGN_MAX_DIST, ALIGN_MAX_REF = 32768, 32768 + 64   # vqa_align_submit: the frames of one submit
+SHIFT_MAX_RADIUS = 16         # vqa_shift_submit: the largest radius of the square band of shifts
+SHIFT_MAX_FRAMES = 32768      # vqa_shift_submit: the frames of one submit
+SHIFT_ROWS, SHIFT_FLUSH = 8, 512   # k_shift: the reference rows of a workgroup's visit, and its matrix steps between two flushes
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -364,6 +369,9 @@ SIGNATURES = {
     "vqa_align_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc),
                                    C.c_int, C.c_int]),
     "vqa_align_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]),
+    "vqa_shift_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
+                                   C.c_int]),
+    "vqa_shift_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -73,6 +73,8 @@ enum batch_kind {
     KIND_SCALE,       // no result words: the batch writes the caller's dst (host frames: scale_stage)
     KIND_ALIGN,       // one word per (distorted frame, band column), then E of every distorted and every reference frame; the two
                       // frame counts, offset and radius of the batch in flight are named members of the ctx (align_*)
+    KIND_SHIFT,       // one word per (frame, dy, dx), then E_d of every frame; the frame count and radius of the batch in flight are
+                      // named members of the ctx (shift_*)
     KIND_COUNT
 };
 
@@ -143,6 +145,7 @@ struct vqa_ctx {
     int pend_c = 0;
     bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
     int align_n_ref = 0, align_n_dist = 0, align_offset = 0, align_radius = 0;   // the pending alignment batch (slot[KIND_ALIGN])
+    int shift_n = 0, shift_radius = 0;   // the pending registration batch (slot[KIND_SHIFT])
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
     int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what FSIM's kept maps hold (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
@@ -163,8 +166,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_LEDGE] = {0};
-    int64_t prof_n[VQA_K_LEDGE] = {0};
+    double prof_ms[VQA_K_SILL] = {0};
+    int64_t prof_n[VQA_K_SILL] = {0};
 };
 
 namespace {
@@ -3177,6 +3180,62 @@ int vqa_align_wait(vqa_ctx *c, uint64_t *sse, int64_t n_words)
 }
 
 // ---------------------------------------------------------------------------
+// Spatial registration: plane 0 of both streams, every distorted frame against its reference frame at every shift of the band.  A
+// batch of its own, ordered by the stream like an alignment batch, whose host staging (qstage_*) it shares.
+static int shift_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int n, int mem_kind, int64_t ref_fs, int64_t dist_fs,
+                             const vqa_plane_desc *plane, int radius, int margin, bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n, plane, 1)) return VQA_ERR_INVALID;
+    if (radius < 1 || radius > VQA_SHIFT_MAX_RADIUS || margin < radius) return VQA_ERR_INVALID;
+    if (n > SHIFT_MAX_FRAMES) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_SHIFT];
+    plane_batch B;
+    // (a margin of half the int range or more leaves no core in any plane: the comparison is made without forming 2M + 1)
+    int rc = check_batch(s, n, ref_fs, dist_fs, plane, 1, B, [margin](const vqa_plane_desc &d) {
+        if ((d.width - 1) / 2 < margin || (d.height - 1) / 2 < margin) return (int)VQA_ERR_UNSUPPORTED;
+        return side_and_area_limits(d, 1);
+    });
+    if (rc) return rc;
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    hipStream_t st = c->stream;
+    const size_t grid = (size_t)(2 * radius + 1) * (2 * radius + 1), words = (size_t)n * grid, bytes = sizeof(unsigned long long) * (words + n);
+    if ((rc = ensure(c, s.dev, bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, bytes, st));
+    {
+        unsigned long long *out = (unsigned long long *)s.dev.p;
+        prof_scope ps_(c, VQA_K_SHIFT);
+        launch_shift(st, ref, dist, n, ref_fs, dist_fs, plane[0], B.depth, radius, margin, out, out + words);
+    }
+    c->shift_n = n; c->shift_radius = radius;
+    return finish_batch(c, s, bytes, (int)words, plane, 1, B.depth);
+}
+
+int vqa_shift_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int n, int mem_kind, int64_t ref_frame_stride,
+                     int64_t dist_frame_stride, const vqa_plane_desc *plane, int radius, int margin)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return shift_submit_body(c, ref, dist, n, mem_kind, ref_frame_stride, dist_frame_stride, plane, radius, margin, touched);
+    });
+}
+
+// sse = E_d[j] + (E_r - 2 C)[j][a][b] in 64-bit words (the true value is below 2^60, so the wrap-around arithmetic is exact)
+int vqa_shift_wait(vqa_ctx *c, uint64_t *sse, int64_t n_words)
+{
+    batch_slot *s;
+    if (!c || !sse) return VQA_ERR_INVALID;
+    if (n_words != (int64_t)c->slot[KIND_SHIFT].entries) return VQA_ERR_STATE;
+    if (int rc = wait_pending(c, KIND_SHIFT, sse, (int)n_words, s)) return rc;
+    if (int rc = wait_synced(c)) return rc;
+    const size_t grid = (size_t)(2 * c->shift_radius + 1) * (2 * c->shift_radius + 1);
+    const unsigned long long *acc = (const unsigned long long *)s->host.p, *ed = acc + (size_t)c->shift_n * grid;
+    for (int j = 0; j < c->shift_n; j++)
+        for (size_t k = 0; k < grid; k++) sse[j * grid + k] = (uint64_t)(ed[j] + acc[j * grid + k]);
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -3186,7 +3245,7 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_LEDGE || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_SILL || (id >= VQA_K_LEDGE && id < VQA_K_SHIFT) || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
@@ -3245,6 +3304,7 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_SIGSTATS_SCAN) return "k_sigstats_scan";
     if (id == VQA_K_SCALE) return "k_scale";
     if (id == VQA_K_ALIGN_CROSS) return "k_align_cross";
+    if (id == VQA_K_SHIFT) return "k_shift";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

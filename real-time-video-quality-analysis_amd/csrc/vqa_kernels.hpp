@@ -657,4 +657,24 @@ bool launch_align_cross(hipStream_t st, const uint8_t *ref, int n_ref, const uin
                         int64_t dist_frame_stride, const vqa_plane_desc &plane, int depth, int offset, int radius,
                         unsigned long long *cross, unsigned long long *e_dist, unsigned long long *e_ref);
 
+// Spatial registration (vqa_shift_submit): k_shift.hip
+constexpr int SHIFT_MAX_FRAMES = 32768;   // frames of one submit (they ride in gridDim.y)
+constexpr int SHIFT_ROWS = 8;             // reference rows of a workgroup's visit
+// the 16 x 16 tiles per axis that cover the 2R + 1 shifts of an axis: 1 (R <= 7), 2 (R <= 15), 3 (R = 16)
+constexpr int shift_tiles(int radius) { return (2 * radius + 16) / 16; }
+// row blocks of the reference rows M - R .. h - M + R - 1 a core row can meet
+constexpr int shift_row_blocks(int h, int radius, int margin) { return (h - 2 * margin + 2 * radius + SHIFT_ROWS - 1) / SHIFT_ROWS; }
+// gridDim.x: every row block its own workgroup while the launch stays below 2^31 threads of 64-lane workgroups, else the
+// workgroups stride over the blocks
+constexpr int shift_grid_x(int blocks, int n, int tiles)
+{
+    const int64_t cap = (int64_t(1) << 25) / ((int64_t)n * tiles);
+    return (int)(blocks < cap ? blocks : (cap > 1 ? cap : 1));
+}
+// One launch per submit: adds E_r(dy, dx) - 2 C(dy, dx) of frame j into out[(j (2R + 1) + dy + R) (2R + 1) + dx + R] and the core's
+// sum of X_d^2 into e_dist[j]; two's complement uint64 words the submit has zeroed.  The caller has checked 1 <= radius <= 16,
+// margin >= radius, h, w >= 2 margin + 1 and n <= SHIFT_MAX_FRAMES.
+void launch_shift(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride, int64_t dist_frame_stride,
+                  const vqa_plane_desc &plane, int depth, int radius, int margin, unsigned long long *out, unsigned long long *e_dist);
+
 } // namespace vqa

@@ -419,12 +419,12 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
                      "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait,
-                     "_pending_l": self.align_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_l": self.align_wait, "_pending_j": self.shift_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1214,6 +1214,50 @@ class Engine:
         self.align_submit(ref, dist, planes, radius, offset, plane, frame_bytes, dist_frame_bytes)
         return self.align_wait()
 
+    # ---- spatial registration ----------------------------------------------------------
+    def shift_submit(self, ref, dist, planes, radius=4, margin=None, plane=0, frame_bytes=None, dist_frame_bytes=None):
+        """The squared error of planes[plane] between distorted frame j and reference frame j read at every shift (dy, dx),
+        dy, dx = -radius .. radius, over the core that lies `margin` (default: radius) samples inside the plane
+        (vqa_shift_submit).  ref, dist: uint8 / uint16 arrays of as many frames (the first axis is the frame; the other type
+        than the planes' depth says is a ValueError, not a cast) or DeviceFrames, roi and strided views included.
+        frame_bytes: the frame stride of host arrays (dist_frame_bytes: the distorted stream's, where it differs).  A batch
+        of its own, like align_submit."""
+        one = [planes[plane]]
+        dev = isinstance(ref, DeviceFrames)
+        if dev and not isinstance(dist, DeviceFrames):
+            raise TypeError("ref and dist must both be DeviceFrames or both be arrays")
+        rp, ref = self._stream_arg(ref, one, dev)
+        dp, dist = self._stream_arg(dist, one, dev)
+        if dev:
+            n, n_dist, rfs, dfs, kind = ref.n, dist.n, ref.frame_stride, dist.frame_stride, N.VQA_MEM_DEVICE
+        else:
+            n, n_dist, kind = ref.shape[0], dist.shape[0], N.VQA_MEM_HOST
+            if not n:
+                raise ValueError("ref and dist must hold at least one frame each")
+            rfs = int(frame_bytes) if frame_bytes else ref.nbytes // n
+            dfs = int(dist_frame_bytes) if dist_frame_bytes else (int(frame_bytes) if frame_bytes else dist.nbytes // max(n_dist, 1))
+        if n != n_dist:
+            raise ValueError("ref and dist must hold the same number of frames")
+        radius = int(radius)
+        margin = radius if margin is None else int(margin)
+        st = self.lib.vqa_shift_submit(self.ctx, rp, dp, n, kind, rfs, dfs, plane_descs(one), radius, margin)
+        N.check(st, "vqa_shift_submit", self.ctx)
+        self._pending_j = (n, 2 * radius + 1, (ref, dist))
+
+    def shift_wait(self):
+        """-> uint64 [n, 2 radius + 1, 2 radius + 1]: entry [j][a][b] is the shift (dy, dx) = (a - radius, b - radius)."""
+        n, side, _keep = getattr(self, "_pending_j", None) or (1, 1, None)   # (nothing pending: the library says so)
+        out = np.zeros((n, side, side), np.uint64)
+        st = self.lib.vqa_shift_wait(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size)
+        self._pending_j = None
+        N.check(st, "vqa_shift_wait", self.ctx)
+        return out
+
+    def shift(self, ref, dist, planes, radius=4, margin=None, plane=0, frame_bytes=None, dist_frame_bytes=None):
+        """shift_submit and shift_wait -> uint64 [n, 2 radius + 1, 2 radius + 1]; shift.analyse reads the shift and its cost off it."""
+        self.shift_submit(ref, dist, planes, radius, margin, plane, frame_bytes, dist_frame_bytes)
+        return self.shift_wait()
+
     def download(self, dev, dtype=None):
         """Copy DeviceFrames back -> a host array [n, frame_stride / itemsize] (uint8, or uint16 for itemsize 2)."""
         dt = np.dtype(dtype) if dtype is not None else np.dtype(np.uint16 if dev.itemsize == 2 else np.uint8)
@@ -1236,7 +1280,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_CURRENT:
+        for k in N.K_IDS_LATEST:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

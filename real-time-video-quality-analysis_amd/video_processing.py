@@ -432,6 +432,80 @@ def align_extra(result, radius):
     return extra
 
 
+SHIFT_WINDOW = 1024   # the frames of one submit of frame_shift (the C limit is 32768)
+
+
+def _shift_request(shift, margin=None, scale=None):
+    """the shift and shift_margin arguments / config keys -> (radius, margin), or None when the search is off; a ValueError
+    for anything else"""
+    def integer(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+    if shift is None:
+        if margin is not None:
+            raise ValueError("shift_margin needs shift: nothing is searched without a radius.")
+        return None
+    if not integer(shift) or not 1 <= shift <= N.SHIFT_MAX_RADIUS:
+        raise ValueError("shift must be null or an integer radius from 1 to %d." % N.SHIFT_MAX_RADIUS)
+    if margin is not None and (not integer(margin) or margin < shift):
+        raise ValueError("shift_margin must be null or an integer not below shift.")
+    if scale is not None:
+        raise ValueError("shift and scale do not go together: a ladder rung is not registered at its own size.")
+    return int(shift), int(shift if margin is None else margin)
+
+
+def frame_shift(reference, encoded, layout, height=None, width=None, radius=4, margin=None, engine=None, device=None,
+                window=SHIFT_WINDOW):
+    """Spatial registration of two whole clips of one length (Engine.shift, include/vqa.h): the squared error of plane 0 of the
+    layout between encoded frame j and reference frame j read at every shift (dy, dx) of -radius .. radius, over the core
+    `margin` (default: radius) samples inside the plane, and what shift.analyse reads off it.  The clip is walked in windows
+    of `window` frames; a frame's grid depends on its own pair alone - any window size gives the same array.  -> analyse's dict
+    (shift, per_frame, frames_off, edge, sse_given, sse_shifted, psnr_gain, subpixel) plus "sse", uint64
+    [n, 2 radius + 1, 2 radius + 1].  Nothing is moved."""
+    from . import shift as S
+    window = int(window)
+    R, M = _shift_request(radius, margin)
+    if not 1 <= window <= N.SHIFT_MAX_FRAMES:
+        raise ValueError("window must be an integer from 1 to %d." % N.SHIFT_MAX_FRAMES)
+    ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    h, w = _geometry(ref, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+
+    def count(a):
+        return a.n if isinstance(a, DeviceFrames) else a.shape[0]
+
+    def part(a, lo, hi):
+        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
+
+    n = count(enc)
+    if not n or count(ref) != n:
+        raise ValueError("both clips must hold the same number of frames, at least one")
+    sse = np.zeros((n, 2 * R + 1, 2 * R + 1), np.uint64)
+    eng = engine if engine is not None else stream.get_engine(device)
+    with stream.pass_lock(eng.device):
+        for a in range(0, n, window):
+            b = min(n, a + window)
+            sse[a:b] = eng.shift(part(ref, a, b), part(enc, a, b), planes, R, M)
+    out = S.analyse(sse)
+    out["sse"] = sse
+    return out
+
+
+def shift_extra(result, radius):
+    """frame_shift's (shift.analyse's) dict -> the five top-level keys of the log and the row; a clip that is not in place, or
+    whose best shift lies on the band's border, is also a warning in the log of this module"""
+    import logging
+    from . import shift as S
+    extra = S.log_keys(result, radius)
+    if extra["SHIFT_DY"] or extra["SHIFT_DX"] or result["edge"]:
+        logging.getLogger(__name__).warning(
+            "the distorted picture is not in place: it shows at (y, x) what the reference shows at (y %+d, x %+d)%s; %d frame(s) "
+            "have another best shift; comparing in place costs %.2f dB of PSNR (the frames are NOT moved)", extra["SHIFT_DY"],
+            extra["SHIFT_DX"], ", which is the border of the band: the true shift may lie beyond radius %d" % radius
+            if result["edge"] else "", extra["SHIFT_FRAMES_OFF"], extra["SHIFT_PSNR_GAIN"])
+    return extra
+
+
 def _scale_request(scale, dist_height, dist_width):
     """the three arguments that turn scaling on -> whether it is on; a ValueError for a set that does not fit together"""
     for name, v in (("dist_height", dist_height), ("dist_width", dist_width)):
@@ -655,7 +729,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        brisque_model_path=None, brisque_range_path=None, mdsi=False, delta_itp=False,
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
-                       dist_height=None, dist_width=None, scale=None, align=None):
+                       dist_height=None, dist_width=None, scale=None, align=None, shift=None,
+                       shift_margin=None):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -711,6 +786,13 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     "ALIGN_OFFSET", "ALIGN_DROPPED", "ALIGN_REPEATED" and "ALIGN_PSNR_GAIN" (align.analyse); a non-zero offset, drop or repeat is
     also logged as a warning.  The frames are NOT re-paired: nothing is changed silently.  align with scale is a ValueError.
     Without align every file is byte for byte what it was.
+    shift=R (an integer radius 1 .. 16; default None) with shift_margin (default None: R): before the pass starts, a pass of its
+    own (frame_shift) measures whether the distorted picture sits where the reference picture sits - the squared error of plane
+    0 at every integer shift of -R .. R over the core shift_margin samples inside the plane.  vmaf_log is then written in any
+    case and gains the top-level keys "SHIFT_RADIUS", "SHIFT_DY", "SHIFT_DX", "SHIFT_FRAMES_OFF" and "SHIFT_PSNR_GAIN"
+    (shift.analyse), after the ALIGN_* keys when both are on; a non-zero shift, or a best shift on the band's border, is also
+    logged as a warning.  The frames are NOT moved: nothing is changed silently.  shift with scale is a ValueError.  Without
+    shift every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -719,6 +801,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     models = _load_models(sw)
     scaling = _scale_request(scale, dist_height, dist_width)
     radius = _align_request(align, scale)
+    search = _shift_request(shift, shift_margin, scale)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -748,6 +831,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             raise ValueError("ref and dist must have the same shape")
         if radius is not None:
             extra = align_extra(frame_align(rs, ds, layout, h, w, radius, device=device), radius)
+        if search is not None:
+            extra = dict(extra or {}, **shift_extra(frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device), search[0]))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
                  batch_size=batch_size, on_quality=wr, device=device)
     finally:
@@ -802,7 +887,7 @@ def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scal
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
-    if any(on.values()) or (extra and "ALIGN_RADIUS" in extra):   # (an alignment pre-pass always has something to say)
+    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra)):   # (a pre-pass always has something to say)
         _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
                            extra=extra)
     return q, series
@@ -831,6 +916,7 @@ def _check_mode_keys(config):
             raise ValueError("height and width must be positive integers.")
     _scale_request(config.get("scale"), config.get("dist_height"), config.get("dist_width"))
     _align_request(config.get("align"), config.get("scale"))
+    _shift_request(config.get("shift"), config.get("shift_margin"), config.get("scale"))
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -917,7 +1003,12 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         align (null default | an integer radius 1 .. 32): a pre-pass of its own (frame_align) measures, before the pass starts,
         whether the encoded pair stream holds the input's frames in the input's places, and the row gains ALIGN_RADIUS,
         ALIGN_OFFSET, ALIGN_DROPPED, ALIGN_REPEATED and ALIGN_PSNR_GAIN as its LAST columns; an offset, drop or repeat is also
-        a warning; the frames are not re-paired; with scale it is a ValueError.
+        a warning; the frames are not re-paired; with scale it is a ValueError,
+        shift (null default | an integer radius 1 .. 16) with shift_margin (null default: the radius | an integer not below it):
+        a pre-pass of its own (frame_shift) measures, before the pass starts, whether the encoded pair stream's picture sits
+        where the input's sits, and the row gains SHIFT_RADIUS, SHIFT_DY, SHIFT_DX, SHIFT_FRAMES_OFF and SHIFT_PSNR_GAIN as its
+        LAST columns, after the ALIGN_* columns when both are on; a non-zero shift or a best shift on the band's border is also
+        a warning; the frames are not moved; with scale it is a ValueError.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -934,6 +1025,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     scale = config.get("scale")
     scaling = scale is not None
     radius = _align_request(config.get("align"), scale)
+    search = _shift_request(config.get("shift"), config.get("shift_margin"), scale)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -994,6 +1086,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                 f.plane_check(planes)
         if radius is not None:   # the alignment pre-pass over the quality pair, before the pass starts
             extra = align_extra(frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius, device=device), radius)
+        if search is not None:   # the registration pre-pass over the quality pair, likewise
+            extra = dict(extra or {}, **shift_extra(frame_shift(ref, enc if qdist is None else qdist, layout, h, w, search[0],
+                                                                search[1], device=device), search[0]))
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
@@ -1015,7 +1110,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
-        if radius is not None:   # (extract_metrics_from_logs read them off the log: they go last)
+        if radius is not None or search is not None:   # (extract_metrics_from_logs read them off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
@@ -1053,6 +1148,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         from .align import ALIGN_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in ALIGN_KEYS):   # an alignment pre-pass: the row's last columns
             metrics.update((k, doc_top[k]) for k in ALIGN_KEYS)
+        from .shift import SHIFT_KEYS
+        if isinstance(doc_top, dict) and all(k in doc_top for k in SHIFT_KEYS):   # a registration pre-pass: after them
+            metrics.update((k, doc_top[k]) for k in SHIFT_KEYS)
     return metrics
 
 
@@ -1075,7 +1173,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale request and every config key of FEATURES (the
+    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align and shift requests and every config key of FEATURES (the
     # kinds' switches and their parameters); and that a vmaf_model_path names a readable file
     _check_mode_keys(config)
 
