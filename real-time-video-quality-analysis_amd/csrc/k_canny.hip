@@ -5,11 +5,15 @@
 //
 // Stage 1 — gradient, non-maximum suppression, double threshold.  Output: two BIT-PLANES (edge,
 //   weak candidate), one u64 per 64 pixels, 2 x P/8 bytes instead of a P-byte map.
-//   k_canny_nms3 (default): lane = column; a vector compare of 64 columns IS a bit-plane word and every NMS decision is
-//     mask logic on the scalar unit; one unaligned dword load per pixel; v_sad_u32 magnitudes; DPP ring for the
-//     horizontal neighbours; lane r captures row r, so a strip leaves as four 512-byte tile stores (details below).
+//   k_canny_nms4 (default): lane = column, one wave per 256 x 64 strip; one unaligned dword load per pixel; v_sad_u16
+//     magnitudes; the four tiles of a strip are PAIRED in 16-bit halves, so the neighbour ring (DPP), the sector test
+//     (two per-|gx| thresholds) and every NMS decision run on packed registers, two pixels per instruction, with truth
+//     values as the sign bits of the halves; only the kept and the above-high pixels become bit-plane words (vector
+//     compares); lane r captures row r, so a strip leaves as four 512-byte tile stores (details below).
 //   k_canny_nms  (frames narrower than 4 pixels, which the dword window cannot serve): 64x32 tile per workgroup through
 //     LDS, words built with __ballot (round 1's kernel).
+//   k_canny_nms3 (lab build only, VQA_NMS_VARIANT=3: round 3's kernel): as nms4 up to the magnitudes, then every
+//     condition becomes a 64-bit mask at once and the decisions are mask logic on the scalar unit.
 //   k_canny_nms2 (lab build only, VQA_NMS_VARIANT=2: round 2's kernel): 4 pixels per lane, packed 16-bit Sobel.
 //   All: Sobel 3x3 on replicated borders, L1 magnitude = 0 outside the image (OpenCV's zero-bordered
 //   buffer), TG22 fixed-point sector test.
@@ -26,7 +30,7 @@
 // Stage 3 (k_canny_count): np.sum(edges > 0) = the set bits of the final edge plane, one pass.
 //
 // Roofline: HBM, P + P/4 (+ P/4 per hysteresis pass over live tiles) bytes per frame; in practice stage 1 is bound by
-// the CU's scalar unit and the vector ALUs, stage 2 by latency.
+// vector-ALU issue (127 instructions per 256-pixel row), stage 2 by latency.
 #include "vqa_dev.hpp"
 #include "vqa_kernels.hpp"
 #include "vqa_math.hpp"
@@ -309,7 +313,8 @@ __global__ __launch_bounds__(64) void k_canny_nms2(const uint8_t *__restrict__ g
 #endif // VQA_AB_VARIANTS
 
 // ---------------------------------------------------------------------------
-// Stage 1, lane-per-column form (k_canny_nms3, the default): a wave still covers 256 columns x a 64-row strip
+// Stage 1, lane-per-column form with mask logic on the scalar unit (k_canny_nms3, round 3's kernel; its helpers below
+// also serve k_canny_nms4): a wave still covers 256 columns x a 64-row strip
 // (= 4 hysteresis tiles), but lane L owns the FOUR COLUMNS x0 + 64 k + L (k = 0..3), so the 64 lanes of group k
 // are the 64 columns of tile k and a vector compare of group k IS that tile row's bit-plane word (one
 // v_cmp writing an SGPR pair): every NMS decision is taken on 64-pixel masks by the scalar unit, there is no
@@ -355,6 +360,7 @@ __device__ __forceinline__ void writelane2(uint32_t &a, uint32_t &b, int lane, u
 
 typedef unsigned long long u64;
 
+#ifdef VQA_AB_VARIANTS // round 3's kernel, lab build only (VQA_NMS_VARIANT=3)
 struct nms3_state {
     // gradient pipeline, 5 column groups (0..3 = tiles, 4 = halo): previous row's h1, previous running sum,
     // h2 of the two previous rows (slot = row parity)
@@ -572,6 +578,298 @@ __global__ __launch_bounds__(64) void k_canny_nms3(const uint8_t *__restrict__ g
                 const int64_t o = bp_index(f, y0 + lane, tx, ww, tiles_y);
                 const uint32_t s_lo = S.cs[k][0] & S.cw[k][0], s_hi = S.cs[k][1] & S.cw[k][1];
                 const uint32_t w_lo = S.cs[k][0] & ~S.cw[k][0], w_hi = S.cs[k][1] & ~S.cw[k][1];
+                strong[o] = (u64)s_lo | ((u64)s_hi << 32);
+                weak[o] = (u64)w_lo | ((u64)w_hi << 32);
+                n_strong += __popc(s_lo) + __popc(s_hi);
+                n_weak += __popc(w_lo) + __popc(w_hi);
+            }
+        }
+    }
+    n_strong = wave_sum(n_strong);
+    n_weak = wave_sum(n_weak);
+    if (lane == 0) {
+        if (n_strong) atomicAdd(&res[f].edge_strong, n_strong);
+        if (n_weak) atomicAdd(&res[f].edge_weak, n_weak);
+    }
+}
+
+#endif // VQA_AB_VARIANTS
+
+// ---------------------------------------------------------------------------
+// Stage 1, pair-packed form (k_canny_nms4, the default).  The wave, the loads, the gradient and the captures are
+// k_canny_nms3's: a wave covers 256 columns x a 64-row strip, lane L owns the columns x0 + 64 k + L, one unaligned
+// dword per pixel requested a row ahead, |gx| and |gx| + |gy| as two sums of absolute differences, lane r captures
+// row r.  What changed is where the NMS decisions are taken.  nms3 turned every condition into a 64-bit mask at once (about 60 v_cmp per row) and ran the
+// boolean logic on the scalar unit (about 140 scalar instructions per row), which kept the CU's one scalar unit and
+// the vector ALUs busy at the same time.  Here every quantity a decision reads fits 16 bits (m <= 2040, thresholds
+// <= 3482), so
+//   * the tiles are PAIRED: one VGPR holds the magnitudes of tile 2q (low half) and tile 2q + 1 (high half) of the
+//     lane's column, and so do the neighbour magnitudes and the thresholds: one packed instruction decides two pixels;
+//   * a truth value is the SIGN BIT of a half: "a > b" is bit 15 / bit 31 of v_pk_sub_u16(b, a) (the halves differ by
+//     less than 2^15), AND / OR / NOT of truth values are bitwise and fuse three at a time into v_bitop3_b32; the other
+//     15 bits of a half carry garbage that nothing reads;
+//   * the sector test is two compares of m against thresholds that depend on |gx| alone.  OpenCV: horizontal iff
+//     |gy| << 15 < 13573 |gx|, vertical iff |gy| << 15 > 79109 |gx|; with |gy| = m - |gx| that is
+//     m < th1 = (92682 |gx| + 65534) >> 16 and m > th2 = (223754 |gx|) >> 16: two 24-bit multiplies per pixel and one
+//     v_perm per pair that picks the two high halves;
+//   * (gx ^ gy) < 0: the running sums carry gx + 32768, whose bit 15 is "gx >= 0", packed h2[R] - h2[R-2] has "gy < 0"
+//     in bit 15: one packed subtract and one xor per pair;
+//   * the ring of horizontal neighbours moves packed registers (2 DPP moves per direction instead of 5); the seam lane
+//     needs halves of two registers, which the SENDING lane puts together with one v_perm whose selector is per lane;
+//   * only what leaves the loop becomes a mask: the kept pixels and the above-high pixels, two ballots per pair each.
+//     The scalar unit is left with the loop control, the clamped row offset and the lane select of the captures;
+//   * the loop is ONE basic block of four steps: rows outside the image are zeroed by a wave-uniform v_perm selector
+//     instead of a branch, captures are unconditional, h2 has a slot per row mod 4 (no register copies).
+// -S, interior loop, per 256-pixel row: 127 vector + 26 scalar instructions (nms3: 146 + 142), 109 VGPRs, no spills.
+// A strip with at most two real tiles (1920 columns: every eighth strip) runs ONE pair (NP = 1): half the work.
+// ---------------------------------------------------------------------------
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+// halves of a minus halves of b, mod 2^16 (v_pk_sub_u16)
+__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b));
+}
+// "a > b" per half, as the sign bit of the half (|a - b| < 2^15)
+__device__ __forceinline__ uint32_t pk_gt(uint32_t a, uint32_t b) { return pk_sub(b, a); }
+// v_perm_b32 picks bytes of {hi operand, lo operand}: selectors 0-3 = bytes of the second operand, 4-7 = of the first
+__device__ __forceinline__ uint32_t pack_lo(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x05040100u); }  // (lo & 0xffff) | (hi << 16)
+__device__ __forceinline__ uint32_t pack_hi(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }  // (lo >> 16) | (hi & 0xffff0000)
+
+// lane `lane` of (a0, a1) <- the words of ma, of (b0, b1) <- the words of mb: one M0 write per captured row and pair
+// (M0 is written and read inside one statement, see writelane2).  The s_nop keeps two wait states between a vector
+// compare that wrote one of the masks and the first v_writelane that reads it, whatever the compiler put in front.
+__device__ __forceinline__ void writelane4(uint32_t &a0, uint32_t &a1, uint32_t &b0, uint32_t &b1, int lane, u64 ma, u64 mb)
+{
+    asm volatile("s_mov_b32 m0, %4\n\ts_nop 0\n\tv_writelane_b32 %0, %5, m0\n\tv_writelane_b32 %1, %6, m0\n\t"
+                 "v_writelane_b32 %2, %7, m0\n\tv_writelane_b32 %3, %8, m0"
+                 : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1)
+                 : "s"(lane), "s"((uint32_t)ma), "s"((uint32_t)(ma >> 32)), "s"((uint32_t)mb), "s"((uint32_t)(mb >> 32))
+                 : "m0");
+}
+
+// the lanes whose LOW half has its sign bit set: one 16-bit compare.  In C++, "(short)v < 0" becomes a test of bit 15 and
+// costs a bit-field extract or a shift in front of a 32-bit compare.  The asm is safe where it stands: its operand comes
+// from a plain vector-ALU instruction (no DOT / transcendental result, see sad_u32), and its result is only read by
+// writelane4, which keeps its own wait states in front of the first reader
+__device__ __forceinline__ u64 ballot_lo(uint32_t v)
+{
+    u64 m;
+    asm("v_cmp_gt_i16_e64 %0, 0, %1" : "=s"(m) : "v"(v));
+    return m;
+}
+
+struct nms4_state {
+    // gradient pipeline per column group (0..3 = tiles, 4 = halo), slot = row parity: as in nms3, but s carries
+    // a bias of 16384 so that the row sum is gx + 32768 and has "gx >= 0" in bit 15
+    uint32_t h1[2][5], s[2][5];
+    // h2 is read two rows later, while the new row's value is already there: with a slot per row MOD 4 the new value
+    // lands in a register whose content is dead, where two slots cost a register copy per value and row
+    uint32_t h2[4][5];
+    uint32_t H2[4][2];                   // h2 packed per pair (for the sign of gy), slot = row mod 4
+    uint32_t M[2][2], ML[2][2], MR[2][2]; // packed magnitudes of the previous mag row (slot PH^1) and the new one (PH)
+    uint32_t HH[2], VV[2], DS[2], DO[2]; // decisions of the previous mag row that wait for the row below (sign bits)
+    uint32_t ST[2];                      // "above high" of the previous mag row
+    uint32_t cs[4][2], cw[4][2];         // captured words: lane r <-> row r of the strip
+    uint32_t pn[2][5];                   // gray bytes of the next step's row
+};
+
+// |a - b| + c for a, b < 2^16: v_sad_u16 adds the absolute differences of both halves, and the high halves are 0.  The
+// intrinsic, not the (max - min) + c shape nms3 relies on: here the optimiser re-associated that shape across the two
+// chained uses and lost the instruction.  (Not inline asm either: see the hazard note at sad_u32.)
+__device__ __forceinline__ uint32_t sad16(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_sad_u16(a, b, c); }
+
+// v_perm selectors of the lanes that send across the ring's seam (see nms4_step)
+struct nms4_ring {
+    uint32_t l0, l1, r;
+};
+
+template <int NP>
+__device__ __forceinline__ void nms4_load(uint32_t (&p)[5], const __amdgpu_buffer_rsrc_t rs, const int (&off)[5], int R, int h, int pitch)
+{
+    const int soff = min(max(R, 0), h - 1) * pitch; // vertical border: replicate
+#pragma unroll
+    for (int g = 0; g < 2 * NP; g++) p[g] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, off[g], soff, 0);
+    p[4] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, off[4], soff, 0);
+}
+
+template <int J4, bool EDGE, int NP>
+__device__ __forceinline__ void nms4_step(nms4_state &S, int j, const __amdgpu_buffer_rsrc_t rs, int pitch, int h, int y0,
+                                          const int (&off)[5], const uint32_t (&sel)[5], const uint32_t (&cmask)[5],
+                                          uint32_t lowp, uint32_t highp, const nms4_ring &ring)
+{
+    constexpr int NT = 2 * NP, PH = J4 & 1; // J4 = step mod 4, PH = its parity
+    const int R = y0 - 2 + j;            // gray row loaded by this step
+    const int yy = R - 1;                // magnitude row completed by this step
+    nms4_load<NP>(S.pn[PH ^ 1], rs, off, R + 1, h, pitch);
+    __builtin_amdgcn_sched_barrier(0);   // (keeps the prefetch a prefetch, see nms3)
+    const uint32_t (&p)[5] = S.pn[PH];
+    const bool row_in = yy >= 0 && yy < h;
+    uint32_t mnew[5], ax[4], gxb[4], h2n[4];
+#pragma unroll
+    for (int gi = 0; gi <= NT; gi++) {
+        const int g = gi < NT ? gi : 4;
+        const uint32_t v = EDGE ? __builtin_amdgcn_perm(p[g], p[g], sel[g]) : p[g];
+        const uint32_t h1 = ((v >> 16) & 0xffu) - (v & 0xffu);                 // v_sub_u32_sdwa
+        const uint32_t h2 = __builtin_amdgcn_udot4(v, 0x00010201u, 0u, false);   // p[x-1] + 2 p[x] + p[x+1]
+        const uint32_t s = S.h1[PH ^ 1][g] + h1 + 16384u;
+        const uint32_t gb = S.s[PH ^ 1][g] + s;           // gx + 32768
+        const uint32_t a = sad16(gb, 32768u, 0u);         // |gx|
+        const uint32_t h2a = S.h2[J4 ^ 2][g];             // row R-2
+        mnew[g] = EDGE ? (sad16(h2, h2a, a) & cmask[g]) : sad16(h2, h2a, a);
+        if (g < 4) { ax[g] = a; gxb[g] = gb; h2n[g] = h2; }
+        S.h1[PH][g] = h1; S.s[PH][g] = s; S.h2[J4][g] = h2;
+    }
+    // ---- pack the pairs: magnitudes, sector thresholds, NOT (gx ^ gy) < 0.  Rows -1 and h have magnitude 0: the
+    // selector that packs the magnitudes is wave-uniform per row and picks constant zeros there (no branch: the loop
+    // stays one basic block), the halo group takes one AND
+    const uint32_t row_sel = row_in ? 0x05040100u : 0x0c0c0c0cu;
+    const uint32_t halo = mnew[4] & (row_in ? ~0u : 0u);
+    uint32_t Mn[2], TH1[2], TH2[2], SS[2];
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+        const int k0 = 2 * q, k1 = 2 * q + 1;
+        Mn[q] = __builtin_amdgcn_perm(mnew[k1], mnew[k0], row_sel);
+        TH1[q] = pack_hi(__umul24(ax[k0], 92682u) + 65534u, __umul24(ax[k1], 92682u) + 65534u);
+        TH2[q] = pack_hi(__umul24(ax[k0], 223754u), __umul24(ax[k1], 223754u));
+        const uint32_t H2n = pack_lo(h2n[k0], h2n[k1]);
+        SS[q] = pack_lo(gxb[k0], gxb[k1]) ^ pk_sub(H2n, S.H2[J4 ^ 2][q]); // sign bit: (gx >= 0) != (gy < 0), the SAME-sign diagonal
+        S.H2[J4][q] = H2n;
+    }
+    // ---- left / right neighbours of the new row through the ring H,0,1,2,3,H, on packed registers.  Away from the seam
+    // lane a pair's neighbours are the pair one lane over; the seam lane receives halves of two registers, which the
+    // lane that SENDS them puts together: one v_perm with a per-lane selector (ring.l0 / l1 / r: the register itself in
+    // every lane but 63 / 63 / 0) in front of the rotation
+    {
+        S.M[PH][0] = Mn[0];
+        S.ML[PH][0] = wave_ror1(__builtin_amdgcn_perm(Mn[0], halo, ring.l0));     // lane 63 sends (halo, tile 0)
+        if (NP == 2) {
+            S.M[PH][1] = Mn[1];
+            S.ML[PH][1] = wave_ror1(__builtin_amdgcn_perm(Mn[1], Mn[0], ring.l1));   // lane 63 sends (tile 1, tile 2)
+            S.MR[PH][0] = wave_rol1(__builtin_amdgcn_perm(Mn[1], Mn[0], ring.r));    // lane 0 sends (tile 1, tile 2)
+            S.MR[PH][1] = wave_rol1(__builtin_amdgcn_perm(halo, Mn[1], ring.r));  // lane 0 sends (tile 3, halo)
+        } else {
+            S.MR[PH][0] = wave_rol1(__builtin_amdgcn_perm(halo, Mn[0], ring.r));  // lane 0 sends (tile 1, halo)
+        }
+    }
+    // Lane yout captures the finished row: its kept pixels and its above-high pixels, which waited one step in ST so
+    // that both leave with one lane select.  The capture is unconditional: the steps before the strip's first row
+    // (yout < 0) write lane 0, which row 0 overwrites afterwards
+    const int yout = max(yy - 1 - y0, 0); // strip row finished by this step (wave-uniform)
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+        const uint32_t m1 = S.M[PH][q], m1L = S.ML[PH][q], m1R = S.MR[PH][q];
+        const uint32_t m2 = S.M[PH ^ 1][q], m2L = S.ML[PH ^ 1][q], m2R = S.MR[PH ^ 1][q];
+        const uint32_t gt = pk_gt(m1, m2); // serves both rows: "m2 >= m1" of the row above, "m1 > m2" of the new row
+        // row above: vertical needs m2 >= m1, same-sign diagonal m2 > m1[x+1], opposite-sign diagonal m2 > m1[x-1]
+        uint32_t keep = S.HH[q] | (S.VV[q] & ~gt);
+        keep |= S.DS[q] & pk_gt(m2, m1R);
+        keep |= S.DO[q] & pk_gt(m2, m1L);
+        const uint32_t st = S.ST[q];
+        writelane4(S.cs[2 * q][0], S.cs[2 * q][1], S.cs[2 * q + 1][0], S.cs[2 * q + 1][1], yout,
+                   ballot_lo(keep), __ballot((int)keep < 0));
+        writelane4(S.cw[2 * q][0], S.cw[2 * q][1], S.cw[2 * q + 1][0], S.cw[2 * q + 1][1], yout,
+                   ballot_lo(st), __ballot((int)st < 0));
+        // new row as the centre: candidates, direction sectors (exclusive: th1 <= th2), same-row and upward compares
+        const uint32_t cand = pk_gt(m1, lowp);
+        const uint32_t ch = pk_gt(TH1[q], m1), cv = pk_gt(m1, TH2[q]);
+        const uint32_t diag = cand & ~(ch | cv);
+        S.HH[q] = (cand & ch & pk_gt(m1, m1L)) & ~pk_gt(m1R, m1);
+        S.VV[q] = cand & cv & gt;
+        S.DS[q] = diag & SS[q] & pk_gt(m1, m2L);
+        S.DO[q] = diag & ~SS[q] & pk_gt(m1, m2R);
+        S.ST[q] = pk_gt(m1, highp);
+    }
+}
+
+template <bool EDGE, int NP>
+__device__ __forceinline__ void nms4_strip(nms4_state &S, int steps, const __amdgpu_buffer_rsrc_t rs, int pitch, int h, int y0,
+                                           const int (&off)[5], const uint32_t (&sel)[5], const uint32_t (&cmask)[5],
+                                           uint32_t lowp, uint32_t highp, const nms4_ring &ring)
+{
+    nms4_load<NP>(S.pn[0], rs, off, y0 - 2, h, pitch);
+    // four steps per trip (the state's slots go by the step mod 2 and mod 4), no exit between them: the steps beyond
+    // rows_out + 4 load clamped rows and capture into lanes rows_out .. 63, which are not stored
+    for (int j0 = 0; j0 < steps; j0 += 4) {
+        nms4_step<0, EDGE, NP>(S, j0, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+        nms4_step<1, EDGE, NP>(S, j0 + 1, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+        nms4_step<2, EDGE, NP>(S, j0 + 2, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+        nms4_step<3, EDGE, NP>(S, j0 + 3, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    }
+}
+
+// grid and XCD-contiguous strip placement as in k_canny_nms3: 8 * ceil(strips / 8) workgroups of one wave, XCD c takes
+// the contiguous strip range [c * per, (c + 1) * per), so that a strip's left and right neighbours share an L2.
+__global__ __launch_bounds__(64) void k_canny_nms4(const uint8_t *__restrict__ gray, int pitch, int64_t plane_stride,
+                                                   int h, int w, int low, int high,
+                                                   unsigned long long *__restrict__ strong,
+                                                   unsigned long long *__restrict__ weak, int ww,
+                                                   vqa_frame_metrics *__restrict__ res, int strips_x, int strips_y,
+                                                   int n_strips)
+{
+    const int per = (n_strips + 7) >> 3;
+    const int t = (int)(blockIdx.x & 7u) * per + (int)(blockIdx.x >> 3);
+    if ((int)(blockIdx.x >> 3) >= per || t >= n_strips) return; // (uniform: the whole wave leaves)
+    const int bx = t % strips_x, by = (t / strips_x) % strips_y;
+    const int f = t / (strips_x * strips_y);
+    const int lane = lane_id();
+    const int x0 = bx * 256, y0 = by * 64;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(gray + (int64_t)f * plane_stride), (short)0, -1, 0x00020000);
+    const int tiles_y = (h + 63) >> 6;
+    const bool one_pair = w - x0 <= 128; // wave-uniform: tiles 2 and 3 of this strip do not exist
+    // column of (group, lane); the halo group holds x0 - 1 in lane 63 and the column right of the last tile in lane 0.
+    // Every lane loads the dword at clamp(x - 1, 0, w - 4); sel[] maps the replicated-border columns x-1, x, x+1 into it
+    int off[5];
+    uint32_t sel[5], cmask[5];
+    u64 colmask[4];
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        const int x = k < 4 ? x0 + 64 * k + lane : (lane == 63 ? x0 - 1 : x0 + (one_pair ? 128 : 256));
+        const bool in = x >= 0 && x < w && (k < 4 || lane == 0 || lane == 63);
+        cmask[k] = in ? ~0u : 0u;
+        if (k < 4) colmask[k] = __ballot(in);
+        const int xc = min(max(x, -1), w); // columns beyond the border behave like the first one outside (magnitude 0 anyway)
+        off[k] = min(max(xc - 1, 0), w - 4);
+        uint32_t sl = 0x0c000000u;
+#pragma unroll
+        for (int t = 0; t < 3; t++) sl |= (uint32_t)(min(max(xc - 1 + t, 0), w - 1) - off[k]) << (8 * t);
+        sel[k] = sl;
+    }
+    const bool edge = x0 == 0 || x0 + 259 > w; // wave-uniform: some lane's dword window (x-1 .. x+2) leaves the image
+    nms4_state S;
+#pragma unroll
+    for (int k = 0; k < 5; k++) { S.h1[0][k] = S.h1[1][k] = S.s[0][k] = S.s[1][k] = S.h2[0][k] = S.h2[1][k] = S.h2[2][k] = S.h2[3][k] = 0; }
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        S.M[0][q] = S.M[1][q] = S.ML[0][q] = S.ML[1][q] = S.MR[0][q] = S.MR[1][q] = 0;
+        S.H2[0][q] = S.H2[1][q] = S.H2[2][q] = S.H2[3][q] = 0;
+        S.HH[q] = S.VV[q] = S.DO[q] = S.DS[q] = S.ST[q] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) S.cs[k][0] = S.cs[k][1] = S.cw[k][0] = S.cw[k][1] = 0;
+    // m > threshold on halves: m is in [0, 2040], so a threshold outside [-1, 2040] acts like the nearer end (-1 = 0xffff:
+    // 0xffff - m has its sign bit set for every m)
+    const uint32_t lowp = (uint32_t)(min(max(low, -1), 2040) & 0xffff) * 0x10001u;
+    const uint32_t highp = (uint32_t)(min(max(high, -1), 2040) & 0xffff) * 0x10001u;
+    // v_perm_b32(a, b, sel): selectors 4-7 = bytes of a, 0-3 = bytes of b
+    const nms4_ring ring = {lane == 63 ? 0x05040100u : 0x07060504u, lane == 63 ? 0x05040302u : 0x07060504u,
+                            lane == 0 ? 0x05040302u : 0x03020100u};
+    const int rows_out = min(64, h - y0);
+    const int steps = rows_out + 4;
+    if (one_pair) nms4_strip<true, 1>(S, steps, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    else if (edge) nms4_strip<true, 2>(S, steps, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    else nms4_strip<false, 2>(S, steps, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    // ---- lane r holds row y0 + r of the four tiles: contiguous tile stores, strong / weak totals.  Columns outside the
+    // image have magnitude 0 and are candidates under a negative threshold: colmask drops them here
+    unsigned n_strong = 0, n_weak = 0;
+    if (lane < rows_out) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int tx = bx * 4 + k;
+            if (tx < ww) {
+                const int64_t o = bp_index(f, y0 + lane, tx, ww, tiles_y);
+                const uint32_t k_lo = S.cs[k][0] & (uint32_t)colmask[k], k_hi = S.cs[k][1] & (uint32_t)(colmask[k] >> 32);
+                const uint32_t s_lo = k_lo & S.cw[k][0], s_hi = k_hi & S.cw[k][1];
+                const uint32_t w_lo = k_lo & ~S.cw[k][0], w_hi = k_hi & ~S.cw[k][1];
                 strong[o] = (u64)s_lo | ((u64)s_hi << 32);
                 weak[o] = (u64)w_lo | ((u64)w_hi << 32);
                 n_strong += __popc(s_lo) + __popc(s_hi);
@@ -992,14 +1290,22 @@ void launch_canny_nms(hipStream_t st, const uint8_t *gray, int pitch, int64_t pl
                       vqa_frame_metrics *res)
 {
     if (n <= 0) return;
-    // w < 4: the dword window of k_canny_nms3 needs 4 columns; such slivers take the LDS-tile kernel.
-    // Lab build (VQA_NMS_VARIANT): 3 = lane-per-column kernel (shipped), 2 = round 2's register-rolling kernel, 1 = LDS tiles
-    static const int variant = ab_knob("VQA_NMS_VARIANT", 3);
-    if (variant == 3 && w >= 4) {
+    // w < 4: the dword window of k_canny_nms4 needs 4 columns; such slivers take the LDS-tile kernel.
+    // Lab build (VQA_NMS_VARIANT): 4 = pair-packed kernel (shipped), 3 = round 3's lane-per-column kernel with its mask
+    // logic on the scalar unit, 2 = round 2's register-rolling kernel, 1 = LDS tiles
+    static const int variant = ab_knob("VQA_NMS_VARIANT", 4);
+    if ((variant == 4 || variant == 3) && w >= 4) {
         const int sx = (w + 255) / 256, sy = (h + 63) / 64;
         const long long ns = (long long)sx * sy * n; // (n <= 32768 per launch: fits an int)
-        hipLaunchKernelGGL(k_canny_nms3, dim3((unsigned)(8 * ((ns + 7) / 8))), dim3(64), 0, st, gray, pitch,
-                           plane_stride, h, w, low, high, strong, weak, (w + 63) / 64, res, sx, sy, (int)ns);
+        const dim3 grid((unsigned)(8 * ((ns + 7) / 8)));
+#ifdef VQA_AB_VARIANTS
+        if (variant == 3)
+            hipLaunchKernelGGL(k_canny_nms3, grid, dim3(64), 0, st, gray, pitch, plane_stride, h, w, low, high, strong, weak,
+                               (w + 63) / 64, res, sx, sy, (int)ns);
+        else
+#endif
+            hipLaunchKernelGGL(k_canny_nms4, grid, dim3(64), 0, st, gray, pitch, plane_stride, h, w, low, high, strong, weak,
+                               (w + 63) / 64, res, sx, sy, (int)ns);
 #ifdef VQA_AB_VARIANTS
     } else if (variant == 2) {
         hipLaunchKernelGGL(k_canny_nms2, dim3((w + 255) / 256, (h + 63) / 64, n), dim3(64), 0, st, gray, pitch,
