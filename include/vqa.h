@@ -477,6 +477,37 @@ typedef struct vqa_sigstats_metrics {
     double dif;            /* sad / N                                                                                          */
 } vqa_sigstats_metrics;
 
+/* HDR light levels and gamut QC of one frame of ONE stream, the three planes of a pixel taken together (vqa_light_submit /
+ * vqa_light_wait; the definition and the bounds of the words are stated there).  Every word up to pct_bin is an integer the
+ * device formed, so the same frame gives the same words at any place of any batch, from host or device memory; vqa_light_wait
+ * forms the doubles from them and the call's table T on the host: x nits = T[code] 2^-20. */
+#define VQA_LIGHT_PERCENTILES 10
+#define VQA_LIGHT_BINS 4096
+typedef struct vqa_light_metrics {
+    int64_t count;             /* N = h w                                                                                       */
+    uint32_t max_code[3];      /* the largest code of R, G, B: the codes behind maxSCL                                          */
+    uint32_t max_code_rgb;     /* the largest m = max(cR, cG, cB)                                                               */
+    uint32_t min_code_rgb;     /* the smallest m                                                                                */
+    uint32_t reserved;         /* 0                                                                                             */
+    uint64_t sum_q;            /* sum T[m], in 2^-20 cd/m2                                                                      */
+    uint64_t sum_y;            /* sum y, the BT.2020 luminance, in 2^-20 cd/m2                                                  */
+    uint64_t max_y;            /* the largest y                                                                                 */
+    uint64_t out_709;          /* pixels outside BT.709                                                                         */
+    uint64_t out_p3;           /* pixels outside P3-D65                                                                         */
+    uint64_t clamped;          /* pixels with R', G' or B' below 0 or above 1 before the clamp                                  */
+    uint32_t pct_bin[VQA_LIGHT_PERCENTILES];  /* of the histogram of m >> 4: the smallest bin b with C(b) >= (p N + 9999) / 10000,
+                                                 p = 100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998 per ten thousand */
+    double max_nits;           /* T[max_code_rgb] 2^-20: the frame's term of MaxCLL                                             */
+    double min_nits;           /* T[min_code_rgb] 2^-20                                                                         */
+    double avg_nits;           /* sum_q 2^-20 / N: the frame average light level, the frame's term of MaxFALL                   */
+    double y_avg;              /* sum_y 2^-20 / N                                                                               */
+    double y_max;              /* max_y 2^-20                                                                                   */
+    double maxscl[3];          /* T[max_code[k]] 2^-20, k = R, G, B                                                             */
+    double pct_nits[VQA_LIGHT_PERCENTILES];   /* T[pct_bin << 4] 2^-20: THE BIN'S LOWER EDGE                                   */
+    double share_709;          /* out_709 / N                                                                                   */
+    double share_p3;           /* out_p3 / N                                                                                    */
+} vqa_light_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1759,6 +1790,80 @@ VQA_API int vqa_shift_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *di
                              int64_t dist_frame_stride, const vqa_plane_desc *plane, int radius, int margin);
 VQA_API int vqa_shift_wait(vqa_ctx *ctx, uint64_t *sse, int64_t n_words);   /* n_words == n * (2 radius + 1)^2 */
 
+/* ---- HDR light levels and gamut QC: MaxCLL / MaxFALL (CTA-861.3), per-frame light statistics, and "is this BT.2020 container
+ * wider than BT.709 or P3?", ONE stream, three planes jointly ----
+ * dE_ITP and PU21 score an HDR encode against its source; sigstats answers the QC questions of an SDR signal.  This kind answers
+ * the two every HDR10 delivery answers before it ships: the largest max(R, G, B) of any pixel and the largest frame average of
+ * it, in cd/m2 (CTA-861.3's MaxCLL and MaxFALL, the static metadata of an encode), and whether any pixel of a BT.2020 stream lies
+ * outside a smaller gamut - the HDR twin of sigstats' bits_used.  The same pass gives the per-frame statistics dynamic metadata is
+ * made from (in the manner of ST 2094-40 / Dolby Vision L1): min / average / max of maxRGB, the per-channel maxima, a percentile
+ * distribution and the frame's luminance.  This is CTA-861.3's definition AS STATED HERE; it is not compared with any tool.
+ * Input.  Exactly vqa_itp_submit's, but ONE stream: THREE planes of one depth (8 bits, or 9..16 bits as uint16), the colour models
+ *   VQA_ITP_YUV2020 (Y, Cb, Cr, BT.2020 non-constant luminance, limited or full range, chroma replicated: 4:4:4, 4:2:2, 4:2:0, odd
+ *   sizes) or VQA_ITP_BGR; the same geometry rules, the same errors.  R', G', B' are formed word for word as vqa_itp_submit states
+ *   them, in double with contraction off.
+ * One rounding.  Per channel c = rint(min(max(E', 0), 1) 65535), a 16-bit code: THE ONLY ROUNDING; everything after it is integer.
+ *   A pixel with any of R', G', B' below 0 or above 1 BEFORE the clamp is counted in `clamped`: illegal Y'CbCr combinations and
+ *   uint16 samples above 2^depth - 1, a QC figure by itself.
+ * Table.  T[65536] of uint64: the display light of code c in units of 2^-20 cd/m2.  It TRAVELS WITH THE CALL and must be
+ *   non-decreasing with T[65535] < 2^34, else VQA_ERR_INVALID (checked on the host in the submit).  vqa_light_table(transfer, T)
+ *   fills it on the host, with no ctx and no GPU: VQA_ITP_PQ gives T[c] = rint(2^20 EOTF_PQ(c / 65535)) with the PQ constants
+ *   above (T[0] = 0, the first non-zero entry is code 6, T[65535] = 10485760000 = 10000 2^20); VQA_ITP_HLG is VQA_ERR_UNSUPPORTED -
+ *   HLG's display light is not a per-channel function (the OOTF needs Ys), and CTA-861.3's figures are HDR10's.  A caller may pass
+ *   any monotone table of their own, e.g. BT.1886 at 100 cd/m2 for SDR.
+ * Per pixel.  qR, qG, qB = T[cR], T[cG], T[cB]; m = max(cR, cG, cB) and qm = T[m] - T is monotone, so this is the pixel's maxRGB;
+ *   y = (2627 qR + 6780 qG + 593 qB + 5000) / 10000 in integer division, the BT.2020 luminance.
+ * Gamut test.  For G in {BT.709, P3-D65} an integer matrix M_G = rint(2^16 A_G), A_G the linear BT.2020 -> G matrix, derived in
+ *   double on the host from the published chromaticities and D65 (0.3127, 0.3290) by the usual primaries-to-XYZ construction -
+ *   BT.2020: R (0.708, 0.292), G (0.170, 0.797), B (0.131, 0.046); BT.709: R (0.64, 0.33), G (0.30, 0.60), B (0.15, 0.06); P3: R (0.680,
+ *   0.320), G (0.265, 0.690), B (0.150, 0.060) - not typed in; vqa_light_gamut returns it (the 709 matrix is BT.2087's to four
+ *   decimals).  With S_k = sum_j M_G[k][j] q_j in int64, the pixel is OUTSIDE G iff
+ *     min_k S_k < -((max(qR, qG, qB) << 16) >> VQA_LIGHT_GAMUT_REL_SHIFT) - VQA_LIGHT_GAMUT_FLOOR:
+ *   a negative component larger than 2^-6 of the pixel's largest component plus 2^-4 cd/m2 (S is in units of 2^-36 cd/m2).  Both
+ *   constants are this project's own.  Why these: 400 000 random in-gamut colours per gamut, saturated primaries included, at
+ *   1e-4 .. 1 of 1000 cd/m2, encoded to limited-range BT.2020 PQ Y'CbCr 4:4:4 and decoded by this chain, flag 0 at 10 and 12 bits
+ *   (2^-7 and a floor of 2^28 units, 2^-8 cd/m2, already flag 3216 at 10 bits); AT 8 BITS QUANTISATION ALONE CROSSES IT (8074 flagged): THE COUNTS MEAN
+ *   SOMETHING FROM 10 BITS ON.  Pure BT.2020 red and green at 5, 100 and 1000 cd/m2 are outside both gamuts; red at 0.5 cd/m2 is
+ *   not: the floor hides saturated colours below about half a cd/m2.
+ * Overflow.  q < 2^34 and |M| < 2^17, so |S_k| < 3 2^51; every per-frame sum is below 2^34 2^28 = 2^62.
+ * Record, ONE ENTRY PER FRAME (vqa_light_metrics): count; max_code[3] (R, G, B), max_code_rgb and min_code_rgb (the largest and
+ *   smallest m); sum_q = sum qm, sum_y, max_y; out_709, out_p3, clamped (pixel counts); pct_bin[10]: over the 4096-bin histogram
+ *   of m >> 4, the smallest bin b with C(b) >= (p N + 9999) / 10000 for p = 100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900,
+ *   9998 - sigstats' exact-rank rule, per ten thousand.  The wait forms max_nits = T[max_code_rgb] 2^-20, min_nits, avg_nits =
+ *   sum_q 2^-20 / count, y_avg, y_max, maxscl[3], pct_nits[10] = T[pct_bin << 4] 2^-20 (the bin's LOWER EDGE) and the two shares.
+ *   With want_histogram the wait also returns the [n, 4096] uint32 histograms.
+ * What follows: integer sums, maxima and minima are order-free, so a frame gives the same words in any batch, from any memory,
+ *   alone or next to other kinds.  MaxCLL is the largest max_nits of a clip, MaxFALL the largest avg_nits (rtvqa_amd/light.py).
+ * Limits: luma at least 16 x 16 and h w <= 2^28: VQA_ERR_UNSUPPORTED beyond either.  n_planes other than 3, Cb and Cr (or B, G, R)
+ *   geometries that differ, a chroma size that is neither the luma's nor its ceil-half, mixed depths, an unknown model, a
+ *   full_range other than 0 or 1, a null or a bad table: VQA_ERR_INVALID.
+ * The contract of vqa_itp_submit: asynchronous, the same plane descriptors, depths, alignment rules, memory kinds and failure
+ *   guarantee: a failed submit leaves nothing in flight.  A light batch is a batch of its own: VQA_ERR_STATE while one is pending,
+ *   in flight next to a batch of every other kind, and each wait collects its own kind only.  vqa_light_wait: hist must be NULL
+ *   unless the submit asked for histograms (VQA_ERR_INVALID, the batch stays pending); NULL is always accepted.
+ * Kernels: k_light_accum (a thread owns a 2 x 4 luma patch as in k_itp; no transcendental: three 8-byte gathers per pixel from
+ *   the table, which the submit copies to the device and the ctx keeps; the histogram in 16 KB of LDS, a workgroup walks 16384
+ *   pixels of one frame before it flushes) and k_light_scan (one workgroup per frame).  Scratch on the device: 168 bytes and a
+ *   16 KB histogram per frame; batches go out in sub-slices that keep the histograms within 256 MiB (16384 frames), and beyond
+ *   32768 frames in slices; the 512 KB table; host frames are staged in the buffer a one-stream submit uses.  All of it is kept
+ *   by the ctx until vqa_trim / vqa_destroy.
+ * Not built: HLG; a conformant ST 2094-40 / Dolby Vision metadata writer; automatic cropping to the active picture (a letterbox
+ *   lowers MaxFALL: pass a region of interest); chroma interpolation other than replication; measuring inside another kind's pass.
+ * out of vqa_light_wait: n entries (n_entries = n); hist: n * 4096 words or NULL.                                             */
+enum vqa_light_gamut_id { VQA_LIGHT_GAMUT_709 = 0, VQA_LIGHT_GAMUT_P3 = 1 };
+#define VQA_LIGHT_GAMUT_REL_SHIFT 6                /* outside: beyond 2^-6 of the pixel's largest component ...               */
+#define VQA_LIGHT_GAMUT_FLOOR 4294967296LL         /* ... plus 2^32 units of 2^-36 cd/m2 = 2^-4 cd/m2                          */
+#define VQA_LIGHT_TABLE_LIMIT 17179869184ULL       /* 2^34: every table entry is below it                                     */
+VQA_API int vqa_light_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                             const vqa_plane_desc *planes, int n_planes, int model, int full_range, const uint64_t *table,
+                             int want_histogram);
+VQA_API int vqa_light_wait(vqa_ctx *ctx, vqa_light_metrics *out, int n_entries, uint32_t *hist);
+/* T[65536] of `transfer` on the host: no ctx, no device.  VQA_ITP_HLG: VQA_ERR_UNSUPPORTED; anything else but VQA_ITP_PQ, or a
+ * null table: VQA_ERR_INVALID. */
+VQA_API int vqa_light_table(int transfer, uint64_t *table);
+/* M_G = rint(2^16 A_G), row-major, rows R, G, B of G, columns R, G, B of BT.2020: no ctx, no device */
+VQA_API int vqa_light_gamut(int gamut, int64_t m[9]);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1870,8 +1975,14 @@ enum vqa_kernel_id {
     VQA_K_SHIFT = 70,        /* vqa_shift_submit: the tiles of the grid of shifts, E_r and E_d (one entry per submit); VQA_K_LEDGE
                                 stays 69 as the alignment shipped it (callers and tests rely on id 69 being unknown); id 69 stays
                                 unnamed                                                                                  */
-    VQA_K_SILL = 71          /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+    VQA_K_SILL = 71,         /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
                                 one-past names list, and VQA_K_SHIFT .. VQA_K_SILL - 1                                    */
+    VQA_K_LIGHT_ACCUM = 72,  /* vqa_light_submit: the decode, the table gathers, the histogram and the per-frame words (one entry
+                                per sub-slice); VQA_K_SILL stays 71 as the registration shipped it (callers and tests rely on id
+                                71 being unknown); id 71 stays unnamed                                                    */
+    VQA_K_LIGHT_SCAN = 73,   /* the percentile bins off the histograms (one entry per sub-slice)                          */
+    VQA_K_LINTEL = 74        /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+                                one-past names list, and VQA_K_LIGHT_ACCUM .. VQA_K_LINTEL - 1                            */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -79,7 +79,9 @@ K_IDS_PRESENT = K_IDS_COMPLETE + (K_SCALE,)       # the ids below K_MARGIN (kept
 K_ALIGN_CROSS, K_LEDGE = 68, 69                   # added beyond K_MARGIN, which stays 67; id 67 is unnamed
 K_IDS_CURRENT = K_IDS_PRESENT + (K_ALIGN_CROSS,)  # the ids below K_LEDGE (kept as the alignment shipped it)
 K_SHIFT, K_SILL = 70, 71                          # added beyond K_LEDGE, which stays 69; id 69 is unnamed
-K_IDS_LATEST = K_IDS_CURRENT + (K_SHIFT,)         # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_LATEST = K_IDS_CURRENT + (K_SHIFT,)         # the ids below K_SILL (kept as the registration shipped it)
+K_LIGHT_ACCUM, K_LIGHT_SCAN, K_LINTEL = 72, 73, 74   # added beyond K_SILL, which stays 71; id 71 is unnamed
+K_IDS_NEWEST = K_IDS_LATEST + (K_LIGHT_ACCUM, K_LIGHT_SCAN)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -133,6 +135,15 @@ ALIGN_MAX_DIST, ALIGN_MAX_REF = 32768, 32768 + 64   # vqa_align_submit: the fram
 SHIFT_MAX_RADIUS = 16         # vqa_shift_submit: the largest radius of the square band of shifts
 SHIFT_MAX_FRAMES = 32768      # vqa_shift_submit: the frames of one submit
 SHIFT_ROWS, SHIFT_FLUSH = 8, 512   # k_shift: the reference rows of a workgroup's visit, and its matrix steps between two flushes
+LIGHT_MIN_DIM = 16            # vqa_light_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+LIGHT_BINS = 4096             # vqa_light_metrics: the histogram of m >> 4
+LIGHT_PERCENTILES = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)   # pct_bin's ranks, per ten thousand
+LIGHT_FIX = 1 << 20           # the table's unit: 2^-20 cd/m2
+LIGHT_TABLE_LIMIT = 1 << 34   # every table entry is below it
+LIGHT_GAMUT_709, LIGHT_GAMUT_P3 = 0, 1   # vqa_light_gamut's gamuts
+LIGHT_GAMUTS = {"bt709": LIGHT_GAMUT_709, "p3": LIGHT_GAMUT_P3}
+LIGHT_GAMUT_REL_SHIFT, LIGHT_GAMUT_FLOOR = 6, 1 << 32   # outside: min S < -((qmax << 16) >> 6) - 2^32
+LIGHT_WALK, LIGHT_SUB_FRAMES = 8, 16384   # k_light_accum: chunks of 256 patches per workgroup; frames of one sub-slice
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -267,6 +278,15 @@ class VqaFsimMetrics(C.Structure):
                 ("factor", C.c_int32), ("flags", C.c_uint32), ("fsim", C.c_double), ("fsimc", C.c_double)]
 
 
+class VqaLightMetrics(C.Structure):
+    _fields_ = [("count", C.c_int64), ("max_code", C.c_uint32 * 3), ("max_code_rgb", C.c_uint32), ("min_code_rgb", C.c_uint32),
+                ("reserved", C.c_uint32), ("sum_q", C.c_uint64), ("sum_y", C.c_uint64), ("max_y", C.c_uint64),
+                ("out_709", C.c_uint64), ("out_p3", C.c_uint64), ("clamped", C.c_uint64), ("pct_bin", C.c_uint32 * 10),
+                ("max_nits", C.c_double), ("min_nits", C.c_double), ("avg_nits", C.c_double), ("y_avg", C.c_double),
+                ("y_max", C.c_double), ("maxscl", C.c_double * 3), ("pct_nits", C.c_double * 10), ("share_709", C.c_double),
+                ("share_p3", C.c_double)]
+
+
 class VqaSigstatsMetrics(C.Structure):
     _fields_ = [("count", C.c_int64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32),
                 ("low", C.c_uint32), ("median", C.c_uint32), ("high", C.c_uint32), ("or_mask", C.c_uint32),
@@ -372,6 +392,11 @@ SIGNATURES = {
     "vqa_shift_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
                                    C.c_int]),
     "vqa_shift_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]),
+    "vqa_light_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(C.c_uint64), C.c_int]),
+    "vqa_light_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaLightMetrics), C.c_int, C.POINTER(C.c_uint32)]),
+    "vqa_light_table": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "vqa_light_gamut": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -75,6 +75,9 @@ enum batch_kind {
                       // frame counts, offset and radius of the batch in flight are named members of the ctx (align_*)
     KIND_SHIFT,       // one word per (frame, dy, dx), then E_d of every frame; the frame count and radius of the batch in flight are
                       // named members of the ctx (shift_*)
+    KIND_LIGHT,       // LIGHT_WORDS per frame, then (want_histogram) the histograms of every frame in the pinned copy only; work: the
+                      // table T on the device, the histograms of one sub-slice; the table's host copy and the histogram switch of
+                      // the batch in flight are named members of the ctx (light_*)
     KIND_COUNT
 };
 
@@ -146,6 +149,8 @@ struct vqa_ctx {
     bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
     int align_n_ref = 0, align_n_dist = 0, align_offset = 0, align_radius = 0;   // the pending alignment batch (slot[KIND_ALIGN])
     int shift_n = 0, shift_radius = 0;   // the pending registration batch (slot[KIND_SHIFT])
+    bool light_hist = false;             // the pending light batch (slot[KIND_LIGHT]) keeps its histograms for the wait
+    std::vector<uint64_t> light_table;   // the table of the last light submit: what slot[KIND_LIGHT].work[0] holds, and what the wait reads
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
     int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what FSIM's kept maps hold (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
@@ -166,8 +171,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_SILL] = {0};
-    int64_t prof_n[VQA_K_SILL] = {0};
+    double prof_ms[VQA_K_LINTEL] = {0};
+    int64_t prof_n[VQA_K_LINTEL] = {0};
 };
 
 namespace {
@@ -3236,6 +3241,110 @@ int vqa_shift_wait(vqa_ctx *c, uint64_t *sse, int64_t n_words)
 }
 
 // ---------------------------------------------------------------------------
+// HDR light levels and gamut QC: one stream alone, the three planes of a pixel together, one entry per frame.  A batch of its
+// own, ordered by the stream like a dE_ITP batch, whose checks and geometry rules it shares; host frames are staged in qstage_dist.
+static int light_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
+                             int n_planes, int model, int full_range, const uint64_t *table, int want_histogram, bool &touched)
+{
+    if (bad_batch_args(c, frames, frames, mem_kind, n, planes, n_planes) || !table) return VQA_ERR_INVALID;
+    if (n_planes != 3 || (model != VQA_ITP_YUV2020 && model != VQA_ITP_BGR)) return VQA_ERR_INVALID;
+    if (full_range != 0 && full_range != 1) return VQA_ERR_INVALID;
+    if (table[65535] >= VQA_LIGHT_TABLE_LIMIT) return VQA_ERR_INVALID;
+    for (int i = 1; i < 65536; i++)
+        if (table[i] < table[i - 1]) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_LIGHT];
+    dbuf &tab_dev = s.work[0], &hist_dev = s.work[1];
+    plane_batch B;
+    int rc = check_batch(s, n, fs, fs, planes, n_planes, B, plane0_limits(planes, LIGHT_MIN_DIM),
+                         model == VQA_ITP_BGR ? JOINT_BGR : JOINT_YUV);
+    if (rc) return rc;
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &c->qstage_dist}))) return rc;
+    hipStream_t st = c->stream;
+    const bool hist = want_histogram != 0;
+    const size_t tab_bytes = sizeof(uint64_t) * 65536, frame_hist = sizeof(uint32_t) * LIGHT_BINS;
+    const size_t acc_bytes = sizeof(unsigned long long) * LIGHT_WORDS * (size_t)n;
+    const int sub_frames = slice_frames(c, n) < LIGHT_SUB_FRAMES ? slice_frames(c, n) : LIGHT_SUB_FRAMES;
+    // the table: no light batch is in flight (check_batch) and nothing else reads it, so the copy needs no ordering; it is
+    // skipped when the device still holds this very table
+    const bool same = tab_dev.p && c->light_table.size() == 65536 && !memcmp(c->light_table.data(), table, tab_bytes);
+    if (!same) {
+        c->light_table.clear();
+        if ((rc = ensure(c, tab_dev, tab_bytes))) return rc;
+        HIPCHK(c, hipMemcpy(tab_dev.p, table, tab_bytes, hipMemcpyHostToDevice));
+        c->light_table.assign(table, table + 65536);
+    }
+    if ((rc = ensure(c, s.dev, acc_bytes))) return rc;
+    if ((rc = ensure(c, hist_dev, frame_hist * (size_t)sub_frames))) return rc;
+    if ((rc = ensure_pinned(c, s.host, acc_bytes + (hist ? frame_hist * (size_t)n : 0)))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, acc_bytes, st));
+    const int depth = B.depth;
+    hipError_t err = hipSuccess;
+    for_each_slice(c, n, [&](int a0, int m) {
+        for (int b0 = 0; b0 < m; b0 += sub_frames) {
+            const int k = m - b0 < sub_frames ? m - b0 : sub_frames, at = a0 + b0;
+            hipError_t e = hipMemsetAsync(hist_dev.p, 0, frame_hist * (size_t)k, st);
+            if (e != hipSuccess) err = e;
+            unsigned long long *sacc = (unsigned long long *)s.dev.p + (size_t)at * LIGHT_WORDS;
+            {
+                prof_scope ps_(c, VQA_K_LIGHT_ACCUM);
+                launch_light_accum(st, frames + (int64_t)at * fs, k, fs, planes, depth, model, full_range,
+                                   (const unsigned long long *)tab_dev.p, (uint32_t *)hist_dev.p, sacc);
+            }
+            {
+                prof_scope ps_(c, VQA_K_LIGHT_SCAN);
+                launch_light_scan(st, k, planes[0].height, planes[0].width, (const uint32_t *)hist_dev.p, sacc);
+            }
+            if (hist) {   // the sub-slice's histograms leave before the next sub-slice zeroes them (the stream orders the three)
+                e = hipMemcpyAsync((uint8_t *)s.host.p + acc_bytes + frame_hist * (size_t)at, hist_dev.p, frame_hist * (size_t)k,
+                                   hipMemcpyDeviceToHost, st);
+                if (e != hipSuccess) err = e;
+            }
+        }
+    });
+    HIPCHK(c, err);
+    c->light_hist = hist;
+    return finish_batch(c, s, acc_bytes, n, planes, n_planes, depth);
+}
+
+int vqa_light_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride, const vqa_plane_desc *planes,
+                     int n_planes, int model, int full_range, const uint64_t *table, int want_histogram)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return light_submit_body(c, frames, mem_kind, n, frame_stride, planes, n_planes, model, full_range, table, want_histogram,
+                                 touched);
+    });
+}
+
+int vqa_light_wait(vqa_ctx *c, vqa_light_metrics *out, int n_entries, uint32_t *hist)
+{
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_LIGHT, out, n_entries, s)) return rc;
+    if (hist && !c->light_hist) return VQA_ERR_INVALID;   // (the batch stays pending)
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *acc = (const unsigned long long *)s->host.p;
+    for (int e = 0; e < n_entries; e++)
+        light_finalize(acc + (size_t)e * LIGHT_WORDS, s->h[0], s->w[0], c->light_table.data(), out + e);
+    if (hist) memcpy(hist, acc + (size_t)n_entries * LIGHT_WORDS, sizeof(uint32_t) * LIGHT_BINS * (size_t)n_entries);
+    s->entries = 0;
+    return VQA_OK;
+}
+
+int vqa_light_table(int transfer, uint64_t *table)
+{
+    if (!table) return VQA_ERR_INVALID;
+    if (transfer == VQA_ITP_HLG) return VQA_ERR_UNSUPPORTED;   // HLG's display light is not a per-channel function
+    if (transfer != VQA_ITP_PQ) return VQA_ERR_INVALID;
+    light_table_host(table);
+    return VQA_OK;
+}
+
+int vqa_light_gamut(int gamut, int64_t m[9])
+{
+    if (!m) return VQA_ERR_INVALID;
+    return light_gamut_host(gamut, m) ? VQA_OK : VQA_ERR_INVALID;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -3245,7 +3354,7 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_SILL || (id >= VQA_K_LEDGE && id < VQA_K_SHIFT) || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_LINTEL || (id >= VQA_K_SILL && id < VQA_K_LIGHT_ACCUM) || (id >= VQA_K_LEDGE && id < VQA_K_SHIFT) || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
@@ -3305,6 +3414,8 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_SCALE) return "k_scale";
     if (id == VQA_K_ALIGN_CROSS) return "k_align_cross";
     if (id == VQA_K_SHIFT) return "k_shift";
+    if (id == VQA_K_LIGHT_ACCUM) return "k_light_accum";
+    if (id == VQA_K_LIGHT_SCAN) return "k_light_scan";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

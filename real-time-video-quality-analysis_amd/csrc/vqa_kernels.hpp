@@ -677,4 +677,29 @@ constexpr int shift_grid_x(int blocks, int n, int tiles)
 void launch_shift(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride, int64_t dist_frame_stride,
                   const vqa_plane_desc &plane, int depth, int radius, int margin, unsigned long long *out, unsigned long long *e_dist);
 
+// HDR light levels and gamut QC (vqa_light_submit): k_light.hip
+constexpr int LIGHT_MIN_DIM = 16;                  // the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+constexpr int LIGHT_BINS = VQA_LIGHT_BINS;         // the histogram of m >> 4
+constexpr int LIGHT_WALK = 8;                      // chunks of 256 patches a workgroup walks before it flushes (16384 pixels)
+constexpr int LIGHT_SUB_FRAMES = 16384;            // frames of one sub-slice: their histograms stay within 256 MiB
+// the words of a frame: sums, maxima (LIGHT_MAX_Y .. LIGHT_MIN_INV: raised, not added), counts, then pct_bin[10]
+enum light_word {
+    LIGHT_SUM_Q, LIGHT_SUM_Y, LIGHT_MAX_Y, LIGHT_MAX_R, LIGHT_MAX_G, LIGHT_MAX_B, LIGHT_MAX_M,
+    LIGHT_MIN_INV,   // the largest 65535 - m: the smallest m, in a word the submit can zero
+    LIGHT_OUT_709, LIGHT_OUT_P3, LIGHT_CLAMPED, LIGHT_PCT,
+    LIGHT_WORDS = LIGHT_PCT + VQA_LIGHT_PERCENTILES
+};
+// n frames of three planes of one stream (checked by the caller as for launch_itp).  Adds / raises the first LIGHT_PCT words of
+// acc[frame * LIGHT_WORDS ..] and counts m >> 4 into hist[frame * LIGHT_BINS ..]; the caller has zeroed both.  table: T[65536] on
+// the device.
+void launch_light_accum(hipStream_t st, const uint8_t *frames, int n, int64_t frame_stride, const vqa_plane_desc *planes, int depth,
+                        int model, int full_range, const unsigned long long *table, uint32_t *hist, unsigned long long *acc);
+// the ten percentile bins of n frames of h x w pixels off their histograms -> acc[frame * LIGHT_WORDS + LIGHT_PCT ..]
+void launch_light_scan(hipStream_t st, int n, int h, int w, const uint32_t *hist, unsigned long long *acc);
+// vqa_light_table's PQ table and vqa_light_gamut's matrix (false: an unknown gamut), in double on the host
+void light_table_host(uint64_t *table);
+bool light_gamut_host(int gamut, int64_t m[9]);
+// the words -> the record: the doubles of include/vqa.h, on the host (h x w: the luma grid; table: the call's, on the host)
+void light_finalize(const unsigned long long *words, int h, int w, const uint64_t *table, vqa_light_metrics *out);
+
 } // namespace vqa

@@ -94,6 +94,13 @@ SIGSTATS_DTYPE = np.dtype([("count", np.int64), ("sum", np.uint64), ("sum_sq", n
                            ("changed", np.uint64), ("top", np.int32), ("bottom", np.int32), ("left", np.int32),
                            ("right", np.int32), ("mean", np.float64), ("stdev", np.float64), ("dif", np.float64)], align=True)
 assert SIGSTATS_DTYPE.itemsize == C.sizeof(N.VqaSigstatsMetrics) == 152
+LIGHT_DTYPE = np.dtype([("count", np.int64), ("max_code", np.uint32, (3,)), ("max_code_rgb", np.uint32), ("min_code_rgb", np.uint32),
+                        ("reserved", np.uint32), ("sum_q", np.uint64), ("sum_y", np.uint64), ("max_y", np.uint64),
+                        ("out_709", np.uint64), ("out_p3", np.uint64), ("clamped", np.uint64), ("pct_bin", np.uint32, (10,)),
+                        ("max_nits", np.float64), ("min_nits", np.float64), ("avg_nits", np.float64), ("y_avg", np.float64),
+                        ("y_max", np.float64), ("maxscl", np.float64, (3,)), ("pct_nits", np.float64, (10,)),
+                        ("share_709", np.float64), ("share_p3", np.float64)], align=True)
+assert LIGHT_DTYPE.itemsize == C.sizeof(N.VqaLightMetrics) == 280
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -171,6 +178,41 @@ def scale_filter(filter):
     if not isinstance(filter, (str, bool)) and filter in N.SCALE_FILTERS.values():
         return int(filter)
     raise ValueError("scale filter must be one of %s (got %r)" % (", ".join(repr(k) for k in N.SCALE_FILTERS), filter))
+
+
+def light_table(transfer="pq"):
+    """T[65536] uint64 of vqa_light_table: the display light of a 16-bit code in 2^-20 cd/m2.  "pq" (or N.ITP_PQ); "hlg" is a
+    ValueError - HLG's display light is not a per-channel function (the OOTF needs Ys), and CTA-861.3's figures are HDR10's.
+    Needs no GPU."""
+    if transfer in ("hlg", N.ITP_HLG) and not isinstance(transfer, bool):
+        raise ValueError("light levels are not built for 'hlg': its display light is not a per-channel function (the OOTF needs "
+                         "Ys) and CTA-861.3's figures are HDR10's; transfer must be 'pq'")
+    if isinstance(transfer, bool) or transfer not in ("pq", N.ITP_PQ):
+        raise ValueError("transfer must be 'pq'")
+    table = np.zeros(65536, np.uint64)
+    N.check(N.load().vqa_light_table(N.ITP_PQ, table.ctypes.data_as(C.POINTER(C.c_uint64))), "vqa_light_table")
+    return table
+
+
+def check_light_table(table):
+    """a caller's table -> contiguous uint64 [65536]; a ValueError for another type or shape, a table that decreases anywhere or
+    an entry of 2^34 or more (vqa_light_submit refuses the same with VQA_ERR_INVALID).  Needs no GPU."""
+    table = np.ascontiguousarray(table)
+    if table.dtype != np.uint64 or table.shape != (65536,):
+        raise ValueError("table must be uint64 [65536]")
+    if int(table[-1]) >= N.LIGHT_TABLE_LIMIT or (table[1:] < table[:-1]).any():
+        raise ValueError("table must not decrease and must stay below 2^34")
+    return table
+
+
+def light_gamut(name):
+    """rint(2^16 A) as int64 [3, 3], A the linear BT.2020 -> "bt709" | "p3" matrix (vqa_light_gamut): rows R, G, B of the
+    gamut, columns R, G, B of BT.2020.  Needs no GPU."""
+    if not isinstance(name, str) or name not in N.LIGHT_GAMUTS:
+        raise ValueError("gamut must be 'bt709' or 'p3'")
+    m = np.zeros(9, np.int64)
+    N.check(N.load().vqa_light_gamut(N.LIGHT_GAMUTS[name], m.ctypes.data_as(C.POINTER(C.c_int64))), "vqa_light_gamut")
+    return m.reshape(3, 3)
 
 
 def planes_span(planes):
@@ -419,12 +461,13 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
                      "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait,
-                     "_pending_l": self.align_wait, "_pending_j": self.shift_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_l": self.align_wait, "_pending_j": self.shift_wait,
+                     "_pending_o": self.light_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1258,6 +1301,48 @@ class Engine:
         self.shift_submit(ref, dist, planes, radius, margin, plane, frame_bytes, dist_frame_bytes)
         return self.shift_wait()
 
+    # ---- HDR light levels and gamut QC ---------------------------------------------------
+    light_table = staticmethod(light_table)
+    light_gamut = staticmethod(light_gamut)
+
+    def light_submit(self, frames, planes, model=None, transfer="pq", full_range=False, table=None, histogram=False,
+                     frame_bytes=None):
+        """MaxCLL / MaxFALL's per-frame words, light statistics and gamut counts for n frames of ONE stream (vqa_light_submit): an
+        array / DeviceFrames and the plane tuples of itp_submit, exactly THREE planes taken together per pixel - Y, Cb, Cr (BT.2020
+        non-constant luminance) or B, G, R; luma at least 16 x 16.  model: N.ITP_YUV2020 | N.ITP_BGR | None (itp_model(planes)).
+        table: uint64 [65536], the display light of a 16-bit code in 2^-20 cd/m2, non-decreasing and below 2^34; None:
+        light_table(transfer) ("pq" only).  full_range: False (limited, the default) | True; no effect on B, G, R.
+        histogram: keep the [n, 4096] histograms for light_wait.  A batch of its own, like itp_submit."""
+        if model is None:
+            model = self.itp_model(planes)
+        if not isinstance(full_range, (bool, np.bool_)):
+            raise ValueError("full_range must be True or False")
+        if table is None:
+            table = light_table(transfer)
+        table = check_light_table(table)
+        fp, kind, n, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
+        st = self.lib.vqa_light_submit(self.ctx, fp, kind, n, fs, plane_descs(planes), len(planes), int(model), int(full_range),
+                                       table.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if histogram else 0)
+        N.check(st, "vqa_light_submit", self.ctx)
+        self._pending_o = (n, bool(histogram), keep)
+
+    def light_wait(self):
+        """-> [n] records (LIGHT_DTYPE), one per frame; after a submit with histogram=True: (records, uint32 [n, 4096])."""
+        n, want, _keep = getattr(self, "_pending_o", None) or (1, False, None)   # (nothing pending: the library says so)
+        rec = np.zeros(n, dtype=LIGHT_DTYPE)
+        hist = np.zeros((n, N.LIGHT_BINS), np.uint32) if want else None
+        st = self.lib.vqa_light_wait(self.ctx, rec.ctypes.data_as(C.POINTER(N.VqaLightMetrics)), n,
+                                     hist.ctypes.data_as(C.POINTER(C.c_uint32)) if want else None)
+        self._pending_o = None
+        N.check(st, "vqa_light_wait", self.ctx)
+        return (rec, hist) if want else rec
+
+    def light(self, frames, planes, model=None, transfer="pq", full_range=False, table=None, histogram=False, frame_bytes=None):
+        """light_submit and light_wait -> [n] records (LIGHT_DTYPE), with histogram=True also the histograms;
+        light.summarise reads MaxCLL, MaxFALL and the shares off the records."""
+        self.light_submit(frames, planes, model, transfer, full_range, table, histogram, frame_bytes)
+        return self.light_wait()
+
     def download(self, dev, dtype=None):
         """Copy DeviceFrames back -> a host array [n, frame_stride / itemsize] (uint8, or uint16 for itemsize 2)."""
         dt = np.dtype(dtype) if dtype is not None else np.dtype(np.uint16 if dev.itemsize == 2 else np.uint8)
@@ -1280,7 +1365,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_LATEST:
+        for k in N.K_IDS_NEWEST:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

@@ -506,6 +506,91 @@ def shift_extra(result, radius):
     return extra
 
 
+LIGHT_WINDOW = 1024   # the frames of one submit of frame_light (a batch of any length goes out in slices by itself)
+
+
+def _light_request(light, transfer="pq", full_range=False):
+    """the light, light_transfer and light_full_range arguments (the config's "light_range" already turned into the last) ->
+    (transfer, full_range), or None when the measurement is off; a ValueError for anything else.  The parameters are checked
+    whether light is on or not."""
+    if not isinstance(light, (bool, np.bool_)):
+        raise ValueError("light must be true or false.")
+    if transfer == "hlg":
+        raise ValueError("light_transfer 'hlg' is not built: HLG's display light is not a per-channel function (the OOTF needs Ys) "
+                         "and CTA-861.3's MaxCLL / MaxFALL are HDR10's; light_transfer must be 'pq'.")
+    if transfer != "pq":
+        raise ValueError("light_transfer must be 'pq'.")
+    if not isinstance(full_range, (bool, np.bool_)):
+        raise ValueError("light_full_range must be true or false.")
+    return ("pq", bool(full_range)) if light else None
+
+
+def _light_config(config):
+    """the config keys "light", "light_transfer" and "light_range" -> _light_request's answer"""
+    rng = config.get("light_range", "limited")
+    if not (isinstance(rng, str) and rng in ITP_RANGES):
+        raise ValueError('light_range must be "limited" or "full".')
+    return _light_request(config.get("light", False), config.get("light_transfer", "pq"), ITP_RANGES[rng])
+
+
+def frame_light(frames, layout, height=None, width=None, transfer="pq", full_range=False, engine=None, device=None,
+                window=LIGHT_WINDOW, table=None, histogram=False):
+    """HDR light levels and gamut QC of ONE whole clip (Engine.light, include/vqa.h): per frame the words behind MaxCLL and
+    MaxFALL (CTA-861.3, as the header states it - not compared with any tool), the per-channel maxima, the BT.2020 luminance, ten
+    percentiles of maxRGB and the counts of pixels outside BT.709 and P3 and of clamped pixels; the planar YUV layouts as BT.2020
+    non-constant luminance with replicated chroma, bgr24 as B, G, R; transfer "pq" ("hlg" is a ValueError that says why), or a
+    table of the caller's own.  The clip is walked in windows of `window` frames; a frame's record depends on its own samples
+    alone - any window size gives the same records.  -> (records [n] of engine.LIGHT_DTYPE, light.summarise's dict), with
+    histogram=True (records, summary, uint32 [n, 4096]).  Luma at least 16 x 16; a one-plane layout is a ValueError."""
+    from . import light as L
+    from .engine import LIGHT_DTYPE
+    window = int(window)
+    if window < 1:
+        raise ValueError("window must be a positive integer.")
+    if table is None:
+        _light_request(True, transfer, full_range)
+    if not isinstance(full_range, (bool, np.bool_)):
+        raise ValueError("light_full_range must be true or false.")
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    if len(planes) != 3:
+        raise ValueError("light levels take the three planes of a pixel together: %s has %d" % (layout, len(planes)))
+    n = frames.n if isinstance(frames, DeviceFrames) else frames.shape[0]
+    if not n:
+        raise ValueError("the clip must hold at least one frame")
+    eng = engine if engine is not None else stream.get_engine(device)
+    if table is None:
+        table = eng.light_table(transfer)
+    rec = np.zeros(n, LIGHT_DTYPE)
+    hist = np.zeros((n, N.LIGHT_BINS), np.uint32) if histogram else None
+    with stream.pass_lock(eng.device):
+        for a in range(0, n, window):
+            b = min(n, a + window)
+            part = frames.slice(a, b) if isinstance(frames, DeviceFrames) else np.ascontiguousarray(frames[a:b]).reshape(b - a, -1)
+            got = eng.light(part, planes, None, transfer, bool(full_range), table, histogram)
+            if histogram:
+                rec[a:b], hist[a:b] = got
+            else:
+                rec[a:b] = got
+    summary = L.summarise(rec)
+    return (rec, summary, hist) if histogram else (rec, summary)
+
+
+def light_extra(summary):
+    """frame_light's summary -> the eight top-level keys of the log and the row (light.LIGHT_KEYS, in that order).  A MaxCLL
+    above 10000 cd/m2 or a MaxFALL above MaxCLL is a bug and raises; clamped pixels are also a warning in the log of this module"""
+    import logging
+    from . import light as L
+    L.check(summary)
+    extra = {k: (int(summary[k]) if k == "LIGHT_MAXCLL_FRAME" else float(summary[k])) for k in L.LIGHT_KEYS}
+    if extra["LIGHT_CLAMPED"] > 0:
+        logging.getLogger(__name__).warning(
+            "%.4f %% of the reference stream's pixels decode to R'G'B' outside [0, 1] (illegal Y'CbCr combinations or samples above "
+            "the depth's peak): they were clamped and counted", 100.0 * extra["LIGHT_CLAMPED"])
+    return extra
+
+
 def _scale_request(scale, dist_height, dist_width):
     """the three arguments that turn scaling on -> whether it is on; a ValueError for a set that does not fit together"""
     for name, v in (("dist_height", dist_height), ("dist_width", dist_width)):
@@ -730,7 +815,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
                        dist_height=None, dist_width=None, scale=None, align=None, shift=None,
-                       shift_margin=None):
+                       shift_margin=None, light=False, light_transfer="pq", light_full_range=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -793,6 +878,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     (shift.analyse), after the ALIGN_* keys when both are on; a non-zero shift, or a best shift on the band's border, is also
     logged as a warning.  The frames are NOT moved: nothing is changed silently.  shift with scale is a ValueError.  Without
     shift every file is byte for byte what it was.
+    light=True (default False) with light_transfer ("pq"; "hlg" is a ValueError that says why) and light_full_range (False:
+    limited): before the pass starts, a pass of its own over the REFERENCE stream (frame_light) measures the HDR10 light levels
+    and the gamut - CTA-861.3's MaxCLL and MaxFALL as include/vqa.h states them, not compared with any tool.  vmaf_log is then
+    written in any case and gains the top-level keys "LIGHT_MAXCLL", "LIGHT_MAXFALL", "LIGHT_MAXCLL_FRAME", "LIGHT_P9998",
+    "LIGHT_Y_AVG", "LIGHT_OUT_709", "LIGHT_OUT_P3" and "LIGHT_CLAMPED" (light.summarise), BEFORE the ALIGN_* and SHIFT_* keys.  A
+    one-plane layout is a ValueError.  Without light every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -802,6 +893,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     scaling = _scale_request(scale, dist_height, dist_width)
     radius = _align_request(align, scale)
     search = _shift_request(shift, shift_margin, scale)
+    lit = _light_request(light, light_transfer, light_full_range)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -829,8 +921,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
         if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
             raise ValueError("ref and dist must have the same shape")
+        if lit is not None:   # the light pre-pass over the reference stream: its keys go before the other pre-passes
+            extra = dict(extra or {}, **light_extra(frame_light(rs, layout, h, w, lit[0], lit[1], device=device)[1]))
         if radius is not None:
-            extra = align_extra(frame_align(rs, ds, layout, h, w, radius, device=device), radius)
+            extra = dict(extra or {}, **align_extra(frame_align(rs, ds, layout, h, w, radius, device=device), radius))
         if search is not None:
             extra = dict(extra or {}, **shift_extra(frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device), search[0]))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
@@ -887,7 +981,7 @@ def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scal
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
-    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra)):   # (a pre-pass always has something to say)
+    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra or "LIGHT_MAXCLL" in extra)):   # (a pre-pass always has something to say)
         _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
                            extra=extra)
     return q, series
@@ -917,6 +1011,7 @@ def _check_mode_keys(config):
     _scale_request(config.get("scale"), config.get("dist_height"), config.get("dist_width"))
     _align_request(config.get("align"), config.get("scale"))
     _shift_request(config.get("shift"), config.get("shift_margin"), config.get("scale"))
+    _light_config(config)
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -1008,7 +1103,12 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         a pre-pass of its own (frame_shift) measures, before the pass starts, whether the encoded pair stream's picture sits
         where the input's sits, and the row gains SHIFT_RADIUS, SHIFT_DY, SHIFT_DX, SHIFT_FRAMES_OFF and SHIFT_PSNR_GAIN as its
         LAST columns, after the ALIGN_* columns when both are on; a non-zero shift or a best shift on the band's border is also
-        a warning; the frames are not moved; with scale it is a ValueError.
+        a warning; the frames are not moved; with scale it is a ValueError,
+        light (false default | true) with light_transfer ("pq" default; "hlg" is a ValueError that says why) and light_range
+        ("limited" default | "full"): a pre-pass of its own over the INPUT stream (frame_light) measures, before the pass starts,
+        the HDR10 light levels and the gamut, and the row gains LIGHT_MAXCLL, LIGHT_MAXFALL, LIGHT_MAXCLL_FRAME, LIGHT_P9998,
+        LIGHT_Y_AVG, LIGHT_OUT_709, LIGHT_OUT_P3 and LIGHT_CLAMPED BEFORE the ALIGN_* and SHIFT_* columns, which stay the last;
+        three-plane pixfmts only.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1026,6 +1126,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     scaling = scale is not None
     radius = _align_request(config.get("align"), scale)
     search = _shift_request(config.get("shift"), config.get("shift_margin"), scale)
+    lit = _light_config(config)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -1084,8 +1185,11 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         for f in FEATURES:
             if sw[f.kind] and f.plane_check is not None:
                 f.plane_check(planes)
-        if radius is not None:   # the alignment pre-pass over the quality pair, before the pass starts
-            extra = align_extra(frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius, device=device), radius)
+        if lit is not None:   # the light pre-pass over the input stream, before the pass starts: its keys go first
+            extra = dict(extra or {}, **light_extra(frame_light(ref, layout, h, w, lit[0], lit[1], device=device)[1]))
+        if radius is not None:   # the alignment pre-pass over the quality pair, likewise
+            extra = dict(extra or {}, **align_extra(frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius,
+                                                                device=device), radius))
         if search is not None:   # the registration pre-pass over the quality pair, likewise
             extra = dict(extra or {}, **shift_extra(frame_shift(ref, enc if qdist is None else qdist, layout, h, w, search[0],
                                                                 search[1], device=device), search[0]))
@@ -1110,7 +1214,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
-        if radius is not None or search is not None:   # (extract_metrics_from_logs read them off the log: they go last)
+        if radius is not None or search is not None or lit is not None:   # (extract_metrics_from_logs read them off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
@@ -1145,6 +1249,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["VMAF"] = float(pooled["vmaf"]["mean"])
         for f in FEATURES:         # (per-frame dB values were capped by the log's writer)
             f.to_row(f, pooled, signal, metrics)
+        from .light import LIGHT_KEYS
+        if isinstance(doc_top, dict) and all(k in doc_top for k in LIGHT_KEYS):   # a light pre-pass: before the other pre-passes
+            metrics.update((k, doc_top[k]) for k in LIGHT_KEYS)
         from .align import ALIGN_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in ALIGN_KEYS):   # an alignment pre-pass: the row's last columns
             metrics.update((k, doc_top[k]) for k in ALIGN_KEYS)
@@ -1173,7 +1280,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align and shift requests and every config key of FEATURES (the
+    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align, shift and light requests and every config key of FEATURES (the
     # kinds' switches and their parameters); and that a vmaf_model_path names a readable file
     _check_mode_keys(config)
 
