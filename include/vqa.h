@@ -1864,6 +1864,61 @@ VQA_API int vqa_light_table(int transfer, uint64_t *table);
 /* M_G = rint(2^16 A_G), row-major, rows R, G, B of G, columns R, G, B of BT.2020: no ctx, no device */
 VQA_API int vqa_light_gamut(int gamut, int64_t m[9]);
 
+/* ---- Clip-wide sync: a signature per frame, and every pairing of two clips' signatures at once ----
+ * vqa_align_submit answers inside a band of at most +-32 frames around the pairing the caller supplied.  An encode with a long
+ * leader, a trimmed head or an excerpt of a long source lies outside every band.  This kind finds the pairing anywhere in the
+ * clip: a signature of VQA_SIG_BYTES bytes per frame, read in one pass over one plane, and the squared distance between every
+ * distorted and every reference signature, from which the host reads the best constant offset and every frame's best partner.
+ * The signature is a fixed grid whatever the frame size: a ladder rung and its source are synchronised without scaling either.
+ *
+ * Signature (vqa_sig_submit / vqa_sig_wait).  Input: ONE stream and ONE plane descriptor under vqa_align_submit's rules:
+ *   bit_depth 8 (0), or 9 .. 16 as little-endian uint16; any offset, row_stride and pixel_step the other kinds accept (rows at
+ *   odd addresses, padded rows, pixel_step = 3: one channel of packed BGR - the last through a gather, THE SLOW PATH, which
+ *   gives the same bytes); host (pinned or not) and device memory.  No byte beyond offset + (h - 1) row_stride + w pixel_step of
+ *   a frame is read.
+ * Definition: G = VQA_SIG_GRID = 16.  Cell (a, b) covers rows floor(a h / 16) .. floor((a + 1) h / 16) - 1 and columns
+ *   floor(b w / 16) .. floor((b + 1) w / 16) - 1.  With S the exact sum of the cell's samples and c its sample count,
+ *   sig[16 a + b] = min(255, floor(S / (c << (depth - 8)))), an exact unsigned 64-bit integer division.  Samples above
+ *   2^depth - 1 are read as they are; the min is what bounds them.
+ * Output: uint8 [n][256].  A frame gives the same 256 bytes at any place of any batch and from any memory.
+ * Limits: the plane at least 16 x 16 (no cell is empty) with h w <= 2^28, VQA_ERR_UNSUPPORTED otherwise; 1 <= n <= 32768 per
+ *   submit, VQA_ERR_UNSUPPORTED beyond (a longer clip goes in windows).  The descriptor rules and the failure guarantee are
+ *   vqa_gmsd_submit's: a failed submit leaves nothing in flight.  Host frames are staged in the buffer the one-stream kinds share.
+ * Kernel: k_sig, ONE launch per submit; a workgroup owns one (frame, cell row), sums in 64-bit integers, divides and writes its 16
+ *   bytes.  No global atomics.
+ *
+ * Cross (vqa_sig_cross_submit / vqa_sig_cross_wait).  Input: two HOST arrays of signatures, dist_sig [n_dist][256] and ref_sig
+ *   [n_ref][256], 1 <= n_dist, n_ref <= VQA_SIG_MAX_FRAMES (VQA_ERR_UNSUPPORTED beyond; below 1 is VQA_ERR_INVALID).
+ * Definition: D[j][i] = sum_k (dist_sig[j][k] - ref_sig[i][k])^2 <= 256 * 255^2 < 2^24.
+ *   diag[k + n_dist - 1], uint64, k = -(n_dist - 1) .. n_ref - 1: the sum of D[j][j + k] over every j with 0 <= j < n_dist and
+ *     0 <= j + k < n_ref; n_dist + n_ref - 1 words.  k has vqa_align_submit's sign: distorted frame j belongs to reference
+ *     frame j + k.
+ *   best[j], uint64, j = 0 .. n_dist - 1: min over i of ((D[j][i] << 32) | i): the smallest distance, ties to the smallest i.
+ *   Everything is an integer function of the signatures.
+ * How: with X = x - 128 (`x ^ 0x80` read as a signed byte; the shift cancels in the difference), D = E_d[j] + E_r[i] - 2 C[j][i],
+ *   C a Gram matrix on the int8 matrix cores, four steps of K = 64 per 16 x 16 tile; |C| <= 2^22 and E <= 2^22, one 32-bit
+ *   accumulator.  Kernels: k_sig_diag (a wave walks one diagonal of tiles and keeps its 31 diagonal sums in registers; global
+ *   64-bit atomics: 31 per tile diagonal, so their number grows with n_dist + n_ref, not with the product) and k_sig_best (a
+ *   wave walks one strip of 16 distorted frames over all reference tiles and keeps the running minimum; no atomics).  Frames
+ *   that pad a tile to 16 contribute to neither.
+ * Scratch: 256 (n_dist + n_ref) bytes of staged signatures and 8 (2 n_dist + n_ref - 1) bytes of words on the device, the words
+ *   also pinned, kept by the ctx until vqa_trim / vqa_destroy.
+ *
+ * Each of the two is a batch of its own: VQA_ERR_STATE for a second submit while one is pending and for a wait without a submit
+ *   or with counts that are not the submit's (the batch stays pending); in flight next to a batch of every other kind.
+ * Not built: re-pairing by a per-frame path; an FFT-based offset search; signatures of more than one plane or another grid;
+ *   signatures kept on the device between the two calls; timestamps and frame-rate conversion. */
+#define VQA_SIG_GRID 16
+#define VQA_SIG_BYTES 256
+#define VQA_SIG_MAX_BATCH 32768
+#define VQA_SIG_MAX_FRAMES 262144
+VQA_API int vqa_sig_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                           const vqa_plane_desc *plane);
+VQA_API int vqa_sig_wait(vqa_ctx *ctx, uint8_t *sig, int n);   /* n == the submit's n; sig: n * 256 bytes */
+VQA_API int vqa_sig_cross_submit(vqa_ctx *ctx, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref);
+/* n_diag == n_dist + n_ref - 1 and n_best == n_dist */
+VQA_API int vqa_sig_cross_wait(vqa_ctx *ctx, uint64_t *diag, int64_t n_diag, uint64_t *best, int64_t n_best);
+
 /* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
@@ -1981,8 +2036,15 @@ enum vqa_kernel_id {
                                 per sub-slice); VQA_K_SILL stays 71 as the registration shipped it (callers and tests rely on id
                                 71 being unknown); id 71 stays unnamed                                                    */
     VQA_K_LIGHT_SCAN = 73,   /* the percentile bins off the histograms (one entry per sub-slice)                          */
-    VQA_K_LINTEL = 74        /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+    VQA_K_LINTEL = 74,       /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
                                 one-past names list, and VQA_K_LIGHT_ACCUM .. VQA_K_LINTEL - 1                            */
+    VQA_K_SIG = 75,          /* vqa_sig_submit: the cell sums and the signature bytes (one entry per submit); VQA_K_LINTEL stays
+                                74 as the light kind shipped it (callers and tests rely on id 74 being unknown); id 74 stays
+                                unnamed                                                                                  */
+    VQA_K_SIG_DIAG = 76,     /* vqa_sig_cross_submit: the walk along the tile diagonals, diag (one entry per submit)       */
+    VQA_K_SIG_BEST = 77,     /* vqa_sig_cross_submit: the walk along the row strips, best (one entry per submit)           */
+    VQA_K_EAVE = 78          /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
+                                one-past names list, and VQA_K_SIG .. VQA_K_EAVE - 1                                      */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -81,7 +81,9 @@ K_IDS_CURRENT = K_IDS_PRESENT + (K_ALIGN_CROSS,)  # the ids below K_LEDGE (kept 
 K_SHIFT, K_SILL = 70, 71                          # added beyond K_LEDGE, which stays 69; id 69 is unnamed
 K_IDS_LATEST = K_IDS_CURRENT + (K_SHIFT,)         # the ids below K_SILL (kept as the registration shipped it)
 K_LIGHT_ACCUM, K_LIGHT_SCAN, K_LINTEL = 72, 73, 74   # added beyond K_SILL, which stays 71; id 71 is unnamed
-K_IDS_NEWEST = K_IDS_LATEST + (K_LIGHT_ACCUM, K_LIGHT_SCAN)   # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_NEWEST = K_IDS_LATEST + (K_LIGHT_ACCUM, K_LIGHT_SCAN)   # the ids below K_LINTEL (kept as the light kind shipped it)
+K_SIG, K_SIG_DIAG, K_SIG_BEST, K_EAVE = 75, 76, 77, 78   # added beyond K_LINTEL, which stays 74; id 74 is unnamed
+K_IDS_EXTANT = K_IDS_NEWEST + (K_SIG, K_SIG_DIAG, K_SIG_BEST)   # every id vqa_profile_read and vqa_kernel_name know
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2
@@ -135,6 +137,9 @@ ALIGN_MAX_DIST, ALIGN_MAX_REF = 32768, 32768 + 64   # vqa_align_submit: the fram
 SHIFT_MAX_RADIUS = 16         # vqa_shift_submit: the largest radius of the square band of shifts
 SHIFT_MAX_FRAMES = 32768      # vqa_shift_submit: the frames of one submit
 SHIFT_ROWS, SHIFT_FLUSH = 8, 512   # k_shift: the reference rows of a workgroup's visit, and its matrix steps between two flushes
+SIG_GRID, SIG_BYTES = 16, 256     # vqa_sig_submit: the grid of cells and the bytes of a signature
+SIG_MAX_BATCH = 32768         # vqa_sig_submit: the frames of one submit
+SIG_MAX_FRAMES = 262144       # vqa_sig_cross_submit: the signatures of either side
 LIGHT_MIN_DIM = 16            # vqa_light_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 LIGHT_BINS = 4096             # vqa_light_metrics: the histogram of m >> 4
 LIGHT_PERCENTILES = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)   # pct_bin's ranks, per ten thousand
@@ -397,6 +402,10 @@ SIGNATURES = {
     "vqa_light_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaLightMetrics), C.c_int, C.POINTER(C.c_uint32)]),
     "vqa_light_table": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
     "vqa_light_gamut": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
+    "vqa_sig_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc)]),
+    "vqa_sig_wait": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
+    "vqa_sig_cross_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, _u8p, C.c_int]),
+    "vqa_sig_cross_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_uint64), C.c_int64]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -78,6 +78,9 @@ enum batch_kind {
     KIND_LIGHT,       // LIGHT_WORDS per frame, then (want_histogram) the histograms of every frame in the pinned copy only; work: the
                       // table T on the device, the histograms of one sub-slice; the table's host copy and the histogram switch of
                       // the batch in flight are named members of the ctx (light_*)
+    KIND_SIG,         // VQA_SIG_BYTES bytes per frame (host frames: qstage_dist)
+    KIND_SIGX,        // the words of diag, then the words of best; work: the staged signatures of either side; the two counts of
+                      // the batch in flight are named members of the ctx (sigx_*)
     KIND_COUNT
 };
 
@@ -149,6 +152,7 @@ struct vqa_ctx {
     bool pend_q_ms = false;   // the pending quality batch is a VQA_SSIM_MS one (qms_host holds its scales)
     int align_n_ref = 0, align_n_dist = 0, align_offset = 0, align_radius = 0;   // the pending alignment batch (slot[KIND_ALIGN])
     int shift_n = 0, shift_radius = 0;   // the pending registration batch (slot[KIND_SHIFT])
+    int sigx_n_dist = 0, sigx_n_ref = 0; // the pending cross batch (slot[KIND_SIGX])
     bool light_hist = false;             // the pending light batch (slot[KIND_LIGHT]) keeps its histograms for the wait
     std::vector<uint64_t> light_table;   // the table of the last light submit: what slot[KIND_LIGHT].work[0] holds, and what the wait reads
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
@@ -171,8 +175,8 @@ struct vqa_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> ev_pool;                   // recycled events
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev_open; // (kernel id, start, stop) not yet read
-    double prof_ms[VQA_K_LINTEL] = {0};
-    int64_t prof_n[VQA_K_LINTEL] = {0};
+    double prof_ms[VQA_K_EAVE] = {0};
+    int64_t prof_n[VQA_K_EAVE] = {0};
 };
 
 namespace {
@@ -3345,6 +3349,97 @@ int vqa_light_gamut(int gamut, int64_t m[9])
 }
 
 // ---------------------------------------------------------------------------
+// Clip-wide sync, first half: the signature of one plane of every frame of one stream.  A batch of its own, ordered by the
+// stream like a CAMBI batch, whose host staging (qstage_dist) it shares.
+static int sig_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *plane,
+                           bool &touched)
+{
+    if (bad_batch_args(c, frames, frames, mem_kind, n, plane, 1)) return VQA_ERR_INVALID;
+    if (n > VQA_SIG_MAX_BATCH) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_SIG];
+    plane_batch B;
+    int rc = check_batch(s, n, fs, fs, plane, 1, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, VQA_SIG_GRID); });
+    if (rc) return rc;
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &c->qstage_dist}))) return rc;
+    const size_t bytes = (size_t)VQA_SIG_BYTES * n;
+    if ((rc = ensure(c, s.dev, bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, bytes))) return rc;
+    {
+        prof_scope ps_(c, VQA_K_SIG);
+        launch_sig(c->stream, frames, n, fs, plane[0], B.depth, (uint8_t *)s.dev.p);
+    }
+    return finish_batch(c, s, bytes, n, plane, 1, B.depth);
+}
+
+int vqa_sig_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride, const vqa_plane_desc *plane)
+{
+    return submit_and_drain(c, [&](bool &touched) { return sig_submit_body(c, frames, mem_kind, n, frame_stride, plane, touched); });
+}
+
+int vqa_sig_wait(vqa_ctx *c, uint8_t *sig, int n)
+{
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_SIG, sig, n, s)) return rc;
+    if (int rc = wait_synced(c)) return rc;
+    memcpy(sig, s->host.p, (size_t)VQA_SIG_BYTES * n);
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// Clip-wide sync, second half: every distorted signature against every reference signature.  A batch of its own; the two host
+// arrays are staged in the slot's own work buffers (they are no frames, and nothing else reads them).
+static int sig_cross_submit_body(vqa_ctx *c, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref, bool &touched)
+{
+    if (!c || !dist_sig || !ref_sig || n_dist < 1 || n_ref < 1) return VQA_ERR_INVALID;
+    if (n_dist > VQA_SIG_MAX_FRAMES || n_ref > VQA_SIG_MAX_FRAMES) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_SIGX];
+    if (s.entries) return VQA_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    touched = true;
+    int rc;
+    if ((rc = stage(c, s.work[0], dist_sig, (size_t)VQA_SIG_BYTES * n_dist))) return rc;
+    if ((rc = stage(c, s.work[1], ref_sig, (size_t)VQA_SIG_BYTES * n_ref))) return rc;
+    const size_t n_diag = (size_t)n_dist + n_ref - 1, bytes = sizeof(unsigned long long) * (n_diag + n_dist);
+    if ((rc = ensure(c, s.dev, bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, bytes))) return rc;
+    hipStream_t st = c->stream;
+    unsigned long long *diag = (unsigned long long *)s.dev.p;
+    HIPCHK(c, hipMemsetAsync(diag, 0, sizeof(unsigned long long) * n_diag, st));
+    {
+        prof_scope ps_(c, VQA_K_SIG_DIAG);
+        launch_sig_diag(st, dist_sig, n_dist, ref_sig, n_ref, diag);
+    }
+    {
+        prof_scope ps_(c, VQA_K_SIG_BEST);
+        launch_sig_best(st, dist_sig, n_dist, ref_sig, n_ref, diag + n_diag);
+    }
+    c->sigx_n_dist = n_dist; c->sigx_n_ref = n_ref;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(s.host.p, s.dev.p, bytes, hipMemcpyDeviceToHost, st));
+    s.entries = n_dist;
+    s.planes = 0;
+    return VQA_OK;
+}
+
+int vqa_sig_cross_submit(vqa_ctx *c, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref)
+{
+    return submit_and_drain(c, [&](bool &touched) { return sig_cross_submit_body(c, dist_sig, n_dist, ref_sig, n_ref, touched); });
+}
+
+int vqa_sig_cross_wait(vqa_ctx *c, uint64_t *diag, int64_t n_diag, uint64_t *best, int64_t n_best)
+{
+    if (!c || !diag || !best) return VQA_ERR_INVALID;
+    batch_slot *s = &c->slot[KIND_SIGX];
+    if (!s->entries || n_best != c->sigx_n_dist || n_diag != (int64_t)c->sigx_n_dist + c->sigx_n_ref - 1) return VQA_ERR_STATE;
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *words = (const unsigned long long *)s->host.p;
+    memcpy(diag, words, sizeof(uint64_t) * (size_t)n_diag);
+    memcpy(best, words + n_diag, sizeof(uint64_t) * (size_t)n_best);
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
 int vqa_profile_enable(vqa_ctx *c, int on)
 {
     if (!c) return VQA_ERR_INVALID;
@@ -3354,7 +3449,7 @@ int vqa_profile_enable(vqa_ctx *c, int on)
 
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_LINTEL || (id >= VQA_K_SILL && id < VQA_K_LIGHT_ACCUM) || (id >= VQA_K_LEDGE && id < VQA_K_SHIFT) || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
+    if (!c || id < 0 || id >= VQA_K_EAVE || (id >= VQA_K_LINTEL && id < VQA_K_SIG) || (id >= VQA_K_SILL && id < VQA_K_LIGHT_ACCUM) || (id >= VQA_K_LEDGE && id < VQA_K_SHIFT) || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
         (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
         (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
         (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
@@ -3416,6 +3511,9 @@ const char *vqa_kernel_name(int id)
     if (id == VQA_K_SHIFT) return "k_shift";
     if (id == VQA_K_LIGHT_ACCUM) return "k_light_accum";
     if (id == VQA_K_LIGHT_SCAN) return "k_light_scan";
+    if (id == VQA_K_SIG) return "k_sig";
+    if (id == VQA_K_SIG_DIAG) return "k_sig_diag";
+    if (id == VQA_K_SIG_BEST) return "k_sig_best";
     return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
 }
 

@@ -702,4 +702,14 @@ bool light_gamut_host(int gamut, int64_t m[9]);
 // the words -> the record: the doubles of include/vqa.h, on the host (h x w: the luma grid; table: the call's, on the host)
 void light_finalize(const unsigned long long *words, int h, int w, const uint64_t *table, vqa_light_metrics *out);
 
+// Clip-wide sync (vqa_sig_submit, vqa_sig_cross_submit): k_sig.hip
+// the signatures of n frames of one plane (at least 16 x 16, checked by the caller) -> out[frame * VQA_SIG_BYTES ..], every byte
+// written; n rides in gridDim.y (<= VQA_SIG_MAX_BATCH)
+void launch_sig(hipStream_t st, const uint8_t *frames, int n, int64_t frame_stride, const vqa_plane_desc &plane, int depth,
+                uint8_t *out);
+// dist_sig [n_dist][256] and ref_sig [n_ref][256] on the device, 16-byte aligned.  diag: adds the sums of D along every diagonal
+// into diag[k + n_dist - 1], n_dist + n_ref - 1 words the caller has zeroed.  best: writes every word of best[n_dist].
+void launch_sig_diag(hipStream_t st, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref, unsigned long long *diag);
+void launch_sig_best(hipStream_t st, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref, unsigned long long *best);
+
 } // namespace vqa

@@ -461,13 +461,14 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
                      "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait,
                      "_pending_l": self.align_wait, "_pending_j": self.shift_wait,
-                     "_pending_o": self.light_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_o": self.light_wait, "_pending_sg": self.signature_wait,
+                     "_pending_sx": self.sig_cross_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1343,6 +1344,59 @@ class Engine:
         self.light_submit(frames, planes, model, transfer, full_range, table, histogram, frame_bytes)
         return self.light_wait()
 
+    # ---- clip-wide sync: frame signatures and their all-pairs distance ------------------
+    def signature_submit(self, frames, planes, plane=0, frame_bytes=None):
+        """The 256-byte signature of planes[plane] of n frames of ONE stream (vqa_sig_submit): the floor of the mean of each
+        cell of a 16 x 16 grid, brought to 8 bits.  frames: a uint8 / uint16 array (the first axis is the frame; the other type
+        than the planes' depth says is a ValueError, not a cast) or DeviceFrames, roi and strided views included.  The plane
+        is at least 16 x 16; at most N.SIG_MAX_BATCH frames per submit.  A batch of its own, like cambi_submit."""
+        one = [planes[plane]]
+        fp, kind, n, fs, keep = self._one_stream_args(frames, one, frame_bytes)
+        st = self.lib.vqa_sig_submit(self.ctx, fp, kind, n, fs, plane_descs(one))
+        N.check(st, "vqa_sig_submit", self.ctx)
+        self._pending_sg = (n, keep)
+
+    def signature_wait(self):
+        """-> uint8 [n, 256]: byte 16 a + b is cell (a, b)."""
+        n, _keep = getattr(self, "_pending_sg", None) or (1, None)   # (nothing pending: the library says so)
+        out = np.zeros((n, N.SIG_BYTES), np.uint8)
+        st = self.lib.vqa_sig_wait(self.ctx, out.ctypes.data, n)
+        self._pending_sg = None
+        N.check(st, "vqa_sig_wait", self.ctx)
+        return out
+
+    def signature(self, frames, planes, plane=0, frame_bytes=None):
+        """signature_submit and signature_wait -> uint8 [n, 256]"""
+        self.signature_submit(frames, planes, plane, frame_bytes)
+        return self.signature_wait()
+
+    def sig_cross_submit(self, dist_sig, ref_sig):
+        """Every distorted signature against every reference signature (vqa_sig_cross_submit): two uint8 [n, 256] host arrays
+        of at most N.SIG_MAX_FRAMES rows each.  A batch of its own."""
+        d, r = (np.ascontiguousarray(a) for a in (dist_sig, ref_sig))
+        for a in (d, r):
+            if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != N.SIG_BYTES or not a.shape[0]:
+                raise ValueError("signatures must be uint8 [n, %d] with n >= 1 (got %s %s)" % (N.SIG_BYTES, a.dtype, a.shape))
+        st = self.lib.vqa_sig_cross_submit(self.ctx, d.ctypes.data, d.shape[0], r.ctypes.data, r.shape[0])
+        N.check(st, "vqa_sig_cross_submit", self.ctx)
+        self._pending_sx = (d.shape[0], r.shape[0], (d, r))
+
+    def sig_cross_wait(self):
+        """-> (diag uint64 [n_dist + n_ref - 1], best uint64 [n_dist]): diag[k + n_dist - 1] is the sum of the squared
+        distances of the pairs (j, j + k); best[j] is (the smallest distance << 32) | its smallest reference index."""
+        nd, nr, _keep = getattr(self, "_pending_sx", None) or (1, 1, None)   # (nothing pending: the library says so)
+        diag, best = np.zeros(nd + nr - 1, np.uint64), np.zeros(nd, np.uint64)
+        st = self.lib.vqa_sig_cross_wait(self.ctx, diag.ctypes.data_as(C.POINTER(C.c_uint64)), diag.size,
+                                         best.ctypes.data_as(C.POINTER(C.c_uint64)), best.size)
+        self._pending_sx = None
+        N.check(st, "vqa_sig_cross_wait", self.ctx)
+        return diag, best
+
+    def sig_cross(self, dist_sig, ref_sig):
+        """sig_cross_submit and sig_cross_wait -> (diag, best); sync.analyse reads the offset and the re-pairing off them."""
+        self.sig_cross_submit(dist_sig, ref_sig)
+        return self.sig_cross_wait()
+
     def download(self, dev, dtype=None):
         """Copy DeviceFrames back -> a host array [n, frame_stride / itemsize] (uint8, or uint16 for itemsize 2)."""
         dt = np.dtype(dtype) if dtype is not None else np.dtype(np.uint16 if dev.itemsize == 2 else np.uint8)
@@ -1365,7 +1419,7 @@ class Engine:
     def profile_read(self, reset=False):
         """-> {kernel name: (total_ms, launches)} for kernels launched since the last reset."""
         out = {}
-        for k in N.K_IDS_NEWEST:
+        for k in N.K_IDS_EXTANT:
             ms, cnt = C.c_double(0), C.c_int64(0)
             N.check(self.lib.vqa_profile_read(self.ctx, k, C.byref(ms), C.byref(cnt), 1 if reset else 0),
                     "vqa_profile_read", self.ctx)

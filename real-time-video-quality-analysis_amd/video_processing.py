@@ -432,6 +432,131 @@ def align_extra(result, radius):
     return extra
 
 
+SYNC_WINDOW = 4096   # the frames of one submit of frame_sync's signatures (the C limit is 32768)
+
+
+def _sync_request(sync, min_overlap=None, apply=False):
+    """the sync arguments / config keys -> (min_overlap, apply), or None when sync is off; a ValueError for anything else"""
+    if not isinstance(sync, (bool, np.bool_)):
+        raise ValueError("sync must be true or false.")
+    if not isinstance(apply, (bool, np.bool_)):
+        raise ValueError("sync_apply must be true or false.")
+    if min_overlap is not None and (isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, np.integer))
+                                    or min_overlap < 1):
+        raise ValueError("sync_min_overlap must be null or an integer >= 1.")
+    if apply and not sync:
+        raise ValueError("sync_apply needs sync: nothing is trimmed by an offset that was not measured.")
+    return (None if min_overlap is None else int(min_overlap), bool(apply)) if sync else None
+
+
+def _sync_config(config):
+    """the config keys "sync", "sync_min_overlap" and "sync_apply" -> _sync_request's answer"""
+    return _sync_request(config.get("sync", False), config.get("sync_min_overlap"), config.get("sync_apply", False))
+
+
+def _frame_count(a):
+    return a.n if isinstance(a, DeviceFrames) else a.shape[0]
+
+
+def _frame_slice(a, lo, length):
+    """frames lo .. lo + length - 1 of a stream: a view of an array, DeviceFrames.slice of resident frames"""
+    return a.slice(lo, lo + length) if isinstance(a, DeviceFrames) else a[lo:lo + length]
+
+
+def frame_sync(reference, encoded, layout, height=None, width=None, dist_height=None, dist_width=None, min_overlap=None,
+               refine=None, engine=None, device=None, window=SYNC_WINDOW):
+    """Clip-wide sync of two whole clips of any lengths (Engine.signature, Engine.sig_cross, include/vqa.h): the 256-byte
+    signature of plane 0 of every frame of both streams, taken in windows of `window` frames - any window size gives the same
+    arrays - then ONE cross of all distorted against all reference signatures, and what sync.analyse reads off it.  The
+    signature is a 16 x 16 grid whatever the size, so the encoded stream may have a geometry of its own (dist_height,
+    dist_width: a ladder rung); nothing is scaled.  -> analyse's dict (offset, mean, overlap, runner_up, ambiguous, per_frame,
+    frames_off, runs, trim) plus "ref_sig" and "dist_sig" (uint8 [n, 256]), "diag" and "best".  refine=R (streams of one
+    geometry only): also "align", frame_align of radius R on the two streams trimmed to the found overlap - the exact band
+    around the found offset.  Nothing is re-paired."""
+    from . import sync as S
+    window = int(window)
+    if not 1 <= window <= N.SIG_MAX_BATCH:
+        raise ValueError("window must be an integer from 1 to %d." % N.SIG_MAX_BATCH)
+    own = dist_height is not None or dist_width is not None
+    if refine is not None:
+        if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= refine <= N.ALIGN_MAX_RADIUS:
+            raise ValueError("refine must be null or an integer radius from 0 to %d." % N.ALIGN_MAX_RADIUS)
+        if own:
+            raise ValueError("refine needs streams of one geometry: frame_align compares samples.")
+    ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    h, w = _geometry(ref, layout, height, width)
+    dh, dw = _geometry(enc, layout, dist_height or height, dist_width or width) if own else _geometry(enc, layout, h, w)
+    planes_r, planes_d = LAYOUTS[layout][0](h, w), LAYOUTS[layout][0](dh, dw)
+    n_ref, n = _frame_count(ref), _frame_count(enc)
+    if not n_ref or not n:
+        raise ValueError("both clips must hold at least one frame")
+    if n_ref > N.SIG_MAX_FRAMES or n > N.SIG_MAX_FRAMES:
+        raise ValueError("a clip of more than %d frames is not synchronised in one cross." % N.SIG_MAX_FRAMES)
+
+    def part(a, lo, hi):
+        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
+
+    eng = engine if engine is not None else stream.get_engine(device)
+    sigs = []
+    with stream.pass_lock(eng.device):
+        for a, count, planes in ((ref, n_ref, planes_r), (enc, n, planes_d)):
+            sig = np.empty((count, N.SIG_BYTES), np.uint8)
+            for lo in range(0, count, window):
+                hi = min(count, lo + window)
+                sig[lo:hi] = eng.signature(part(a, lo, hi), planes)
+            sigs.append(sig)
+        diag, best = eng.sig_cross(sigs[1], sigs[0])
+    out = S.analyse(diag, best, n, n_ref, min_overlap)
+    out.update(ref_sig=sigs[0], dist_sig=sigs[1], diag=diag, best=best)
+    if refine is not None:
+        ref_lo, dist_lo, length = out["trim"]
+        out["align"] = frame_align(_frame_slice(ref, ref_lo, length), _frame_slice(enc, dist_lo, length), layout, h, w,
+                                   int(refine), engine=engine, device=device)
+    return out
+
+
+def sync_extra(result, applied):
+    """frame_sync's (sync.analyse's) dict -> the six top-level keys of the log and the row; an offset, frames that pair
+    elsewhere, an ambiguous answer and a trim that was applied are also warnings in the log of this module"""
+    import logging
+    from . import sync as S
+    extra = S.log_keys(result, applied)
+    log = logging.getLogger(__name__)
+    if result["ambiguous"]:
+        log.warning("the sync of the two streams is ambiguous: offset %d and offset %d fit equally well (a static or looping "
+                    "clip); the streams go on as given", extra["SYNC_OFFSET"], result["runner_up"][0])
+    elif applied:
+        log.warning("the streams were trimmed to their overlap: %d frame(s) from reference frame %d and distorted frame %d "
+                    "(offset %d, %d frame(s) pair elsewhere)", result["trim"][2], result["trim"][0], result["trim"][1],
+                    extra["SYNC_OFFSET"], extra["SYNC_FRAMES_OFF"])
+    elif extra["SYNC_OFFSET"] or extra["SYNC_FRAMES_OFF"]:
+        log.warning("the distorted stream is not in sync with the reference: offset %d over %d frame(s), %d frame(s) pair "
+                    "elsewhere (the frames are NOT re-paired: sync_apply trims both streams to the overlap)",
+                    extra["SYNC_OFFSET"], extra["SYNC_OVERLAP"], extra["SYNC_FRAMES_OFF"])
+    return extra
+
+
+def _sync_streams(request, ref, dist, layout, h, w, dh, dw, device):
+    """the sync pre-pass of the two entry points: request is _sync_request's (min_overlap, apply).  -> (the six keys, the trim
+    to apply or None).  The trim is applied only where the answer is not ambiguous, and counts as applied only where it cuts."""
+    own = (dh, dw) != (h, w)
+    res = frame_sync(ref, dist, layout, h, w, dh if own else None, dw if own else None, request[0], device=device)
+    ref_lo, dist_lo, length = res["trim"]
+    cuts = request[1] and not res["ambiguous"] and (ref_lo or dist_lo or length != _frame_count(_host_stream(ref, wide=True))
+                                                    or length != _frame_count(_host_stream(dist, wide=True)))
+    return sync_extra(res, bool(cuts)), (res["trim"] if cuts else None)
+
+
+def _with_sync_keys(extra, keys):
+    """the log's further keys with the six SYNC_* keys in their place: after what is there (DIST_RES, SCALE and the LIGHT_*
+    keys) and before the ALIGN_* / SHIFT_* keys, which stay last"""
+    late = {k: v for k, v in (extra or {}).items() if k.startswith(("ALIGN_", "SHIFT_"))}
+    out = {k: v for k, v in (extra or {}).items() if k not in late}
+    out.update(keys)
+    out.update(late)
+    return out
+
+
 SHIFT_WINDOW = 1024   # the frames of one submit of frame_shift (the C limit is 32768)
 
 
@@ -815,7 +940,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        delta_itp_transfer="pq", delta_itp_full_range=False, pu21=False, pu21_transfer="pq",
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
                        dist_height=None, dist_width=None, scale=None, align=None, shift=None,
-                       shift_margin=None, light=False, light_transfer="pq", light_full_range=False):
+                       shift_margin=None, light=False, light_transfer="pq", light_full_range=False, sync=False,
+                       sync_min_overlap=None, sync_apply=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -884,6 +1010,15 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     written in any case and gains the top-level keys "LIGHT_MAXCLL", "LIGHT_MAXFALL", "LIGHT_MAXCLL_FRAME", "LIGHT_P9998",
     "LIGHT_Y_AVG", "LIGHT_OUT_709", "LIGHT_OUT_P3" and "LIGHT_CLAMPED" (light.summarise), BEFORE the ALIGN_* and SHIFT_* keys.  A
     one-plane layout is a ValueError.  Without light every file is byte for byte what it was.
+    sync=True (default False) with sync_min_overlap (default None: half the shorter clip) and sync_apply (default False): before
+    every other pre-pass, a pass of its own (frame_sync) finds where in the reference the distorted stream belongs, anywhere in
+    the clip and for streams of unequal length - or, under scale, of unequal size.  vmaf_log is then written in any case and
+    gains the top-level keys "SYNC_OFFSET", "SYNC_OVERLAP", "SYNC_DISTANCE", "SYNC_RUNNER_UP", "SYNC_FRAMES_OFF" and
+    "SYNC_APPLIED" (sync.analyse), after the LIGHT_* and before the ALIGN_* / SHIFT_* keys.  With sync_apply and an answer that
+    is not ambiguous, both streams are sliced to the found overlap BEFORE the equal-shape check, every later pre-pass and the
+    pass, which is logged as a warning; SYNC_APPLIED is 1 only when something was cut.  An ambiguous answer (a static clip) is
+    never applied: a warning, SYNC_APPLIED 0, and the streams go on as given.  sync_apply without sync is a ValueError.
+    Without sync every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -894,6 +1029,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     radius = _align_request(align, scale)
     search = _shift_request(shift, shift_margin, scale)
     lit = _light_request(light, light_transfer, light_full_range)
+    syn = _sync_request(sync, sync_min_overlap, sync_apply)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -919,6 +1055,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                 if f.plane_check is not None:
                     f.plane_check(planes)
         rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
+        sync_keys = None
+        if syn is not None:   # the sync pre-pass, before everything else: it may trim what everything else reads
+            dg = (dist_planes[0][1], dist_planes[0][0]) if scaling else (h, w)
+            sync_keys, trim = _sync_streams(syn, rs, ds, layout, h, w, dg[0], dg[1], device)
+            if trim is not None:
+                rs, ds = _frame_slice(rs, trim[0], trim[2]), _frame_slice(ds, trim[1], trim[2])
         if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
             raise ValueError("ref and dist must have the same shape")
         if lit is not None:   # the light pre-pass over the reference stream: its keys go before the other pre-passes
@@ -927,6 +1069,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             extra = dict(extra or {}, **align_extra(frame_align(rs, ds, layout, h, w, radius, device=device), radius))
         if search is not None:
             extra = dict(extra or {}, **shift_extra(frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device), search[0]))
+        if sync_keys is not None:
+            extra = _with_sync_keys(extra, sync_keys)
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
                  batch_size=batch_size, on_quality=wr, device=device)
     finally:
@@ -981,7 +1125,7 @@ def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scal
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
-    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra or "LIGHT_MAXCLL" in extra)):   # (a pre-pass always has something to say)
+    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra or "LIGHT_MAXCLL" in extra or "SYNC_OFFSET" in extra)):   # (a pre-pass always has something to say)
         _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
                            extra=extra)
     return q, series
@@ -1012,6 +1156,7 @@ def _check_mode_keys(config):
     _align_request(config.get("align"), config.get("scale"))
     _shift_request(config.get("shift"), config.get("shift_margin"), config.get("scale"))
     _light_config(config)
+    _sync_config(config)
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -1108,7 +1253,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         ("limited" default | "full"): a pre-pass of its own over the INPUT stream (frame_light) measures, before the pass starts,
         the HDR10 light levels and the gamut, and the row gains LIGHT_MAXCLL, LIGHT_MAXFALL, LIGHT_MAXCLL_FRAME, LIGHT_P9998,
         LIGHT_Y_AVG, LIGHT_OUT_709, LIGHT_OUT_P3 and LIGHT_CLAMPED BEFORE the ALIGN_* and SHIFT_* columns, which stay the last;
-        three-plane pixfmts only.
+        three-plane pixfmts only,
+        sync (false default | true) with sync_min_overlap (null default: half the shorter clip | an integer >= 1) and sync_apply
+        (false default | true): a pre-pass of its own over the quality pair (frame_sync), before every other pre-pass, finds
+        where in the input the encoded stream belongs - anywhere in the clip, for streams of unequal length and, under scale,
+        of unequal size - and the row gains SYNC_OFFSET, SYNC_OVERLAP, SYNC_DISTANCE, SYNC_RUNNER_UP, SYNC_FRAMES_OFF and
+        SYNC_APPLIED before the ALIGN_* / SHIFT_* columns; with sync_apply and an answer that is not ambiguous the input is
+        sliced by the reference side's trim and BOTH the encoded BGR stream and the encoded pair stream by the distorted
+        side's, so both halves of the pass see the same frames; an ambiguous answer is a warning and is never applied;
+        sync_apply without sync is a ValueError.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1127,6 +1280,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     radius = _align_request(config.get("align"), scale)
     search = _shift_request(config.get("shift"), config.get("shift_margin"), scale)
     lit = _light_config(config)
+    syn = _sync_config(config)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -1185,6 +1339,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         for f in FEATURES:
             if sw[f.kind] and f.plane_check is not None:
                 f.plane_check(planes)
+        sync_keys = None
+        if syn is not None:   # the sync pre-pass over the quality pair, before everything else: it may trim what everything else reads
+            sync_keys, trim = _sync_streams(syn, ref, enc if qdist is None else qdist, layout, h, w,
+                                            dh if scaling else h, dw if scaling else w, device)
+            if trim is not None:   # both halves of the pass see the same frames
+                ref = _frame_slice(_host_stream(ref, wide=True), trim[0], trim[2])
+                enc = _frame_slice(enc, trim[1], trim[2])
+                if qdist is not None:
+                    qdist = _frame_slice(qdist, trim[1], trim[2])
         if lit is not None:   # the light pre-pass over the input stream, before the pass starts: its keys go first
             extra = dict(extra or {}, **light_extra(frame_light(ref, layout, h, w, lit[0], lit[1], device=device)[1]))
         if radius is not None:   # the alignment pre-pass over the quality pair, likewise
@@ -1193,6 +1356,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         if search is not None:   # the registration pre-pass over the quality pair, likewise
             extra = dict(extra or {}, **shift_extra(frame_shift(ref, enc if qdist is None else qdist, layout, h, w, search[0],
                                                                 search[1], device=device), search[0]))
+        if sync_keys is not None:
+            extra = _with_sync_keys(extra, sync_keys)
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
@@ -1214,7 +1379,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
-        if radius is not None or search is not None or lit is not None:   # (extract_metrics_from_logs read them off the log: they go last)
+        if radius is not None or search is not None or lit is not None or syn is not None:   # (extract_metrics_from_logs read them off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
@@ -1252,6 +1417,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         from .light import LIGHT_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in LIGHT_KEYS):   # a light pre-pass: before the other pre-passes
             metrics.update((k, doc_top[k]) for k in LIGHT_KEYS)
+        from .sync import SYNC_KEYS
+        if isinstance(doc_top, dict) and all(k in doc_top for k in SYNC_KEYS):   # a sync pre-pass: before the two below
+            metrics.update((k, doc_top[k]) for k in SYNC_KEYS)
         from .align import ALIGN_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in ALIGN_KEYS):   # an alignment pre-pass: the row's last columns
             metrics.update((k, doc_top[k]) for k in ALIGN_KEYS)
@@ -1280,7 +1448,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align, shift and light requests and every config key of FEATURES (the
+    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align, shift, light and sync requests and every config key of FEATURES (the
     # kinds' switches and their parameters); and that a vmaf_model_path names a readable file
     _check_mode_keys(config)
 
