@@ -1919,7 +1919,13 @@ VQA_API int vqa_sig_cross_submit(vqa_ctx *ctx, const uint8_t *dist_sig, int n_di
 /* n_diag == n_dist + n_ref - 1 and n_best == n_dist */
 VQA_API int vqa_sig_cross_wait(vqa_ctx *ctx, uint64_t *diag, int64_t n_diag, uint64_t *best, int64_t n_best);
 
-/* ---- per-kernel timing (HIP events on the ctx stream) ----------------------- */
+/* ---- per-kernel timing (HIP events on the ctx stream) -----------------------
+ * The named kernel ids are exactly the ids for which vqa_kernel_name does not return "?"; vqa_profile_read accepts those and
+ * no others.  The other names of the enum (VQA_K_COUNT, VQA_K_COUNT_ALL, ... VQA_K_EAVE) are frozen markers: each records
+ * where the id list ended when one feature shipped, and is kept, name and value, for source compatibility.  The ids equal to
+ * those markers, and the gap 15, are permanently unknown to both functions - with one exception from before the rule:
+ * VQA_K_COUNT = 12 is also VQA_K_VIF's id, which is named.  A new kernel takes the next free id above the current last one
+ * (a marker's value is not free) and needs no new marker. */
 enum vqa_kernel_id {
     VQA_K_GRAY_HIST = 0, /* BGR->gray + histograms, native resolution   */
     VQA_K_RESIZE = 1,    /* cv2.resize gather + gray + histograms       */
@@ -1933,77 +1939,60 @@ enum vqa_kernel_id {
     VQA_K_ORB = 9,       /* FAST-9/16 + NMS on the 64x64 thumbnail's centre */
     VQA_K_FARNEBACK = 10, /* the whole Farneback pyramid (about 30 launches per chunk of pairs) */
     VQA_K_MS_PYRAMID = 11, /* VQA_SSIM_MS: levels 1..4 of both images from one read of level 0 */
-    VQA_K_COUNT = 12,        /* the ids above, as ABI 8 first shipped them: kept at 12 for callers (and tests) that size
-                                arrays by it; the ids below were added later and lie beyond it                        */
+    VQA_K_COUNT = 12,        /* frozen marker (= 12): the list as ABI 8 first shipped it                                  */
     VQA_K_VIF = 12,          /* vqa_vif_submit: the per-level statistic (four entries per group of same-geometry planes) */
     VQA_K_VIF_DECIMATE = 13, /* vqa_vif_submit: level s from level s - 1 (three entries per group)                    */
-    VQA_K_COUNT_ALL = 14,    /* the ids above: 0 .. VQA_K_COUNT_ALL - 1, as VIF shipped them (kept at 14 for callers and
-                                tests that rely on id 14 being unknown); ids 14 and 15 stay unnamed                    */
+    VQA_K_COUNT_ALL = 14,    /* frozen marker (= 14)                                                                     */
     VQA_K_ADM = 16,          /* vqa_adm_submit: one scale - DWT, decoupling, masking, cube sums (four entries per group)  */
     VQA_K_ADM_REDUCE = 17,   /* vqa_adm_submit: the tile partials of a scale, added in a fixed order (four per group)     */
-    VQA_K_COUNT_EXT = 18,    /* vqa_profile_read and vqa_kernel_name know 0 .. VQA_K_COUNT_ALL - 1 and VQA_K_ADM ..
-                                VQA_K_COUNT_EXT - 1 (kept at 18 for callers and tests that rely on id 18 being unknown)  */
+    VQA_K_COUNT_EXT = 18,    /* frozen marker (= 18)                                                                     */
     VQA_K_MOTION = 19,       /* vqa_motion_submit: blur of both frames and the sum of |difference| (one entry per group of
-                                same-geometry planes); id 18 stays unnamed                                              */
-    VQA_K_END = 20,          /* one past VQA_K_MOTION, as motion shipped it (kept at 20 for callers and tests that rely on
-                                id 20 being unknown); id 20 stays unnamed                                               */
+                                same-geometry planes)                                                                   */
+    VQA_K_END = 20,          /* frozen marker (= 20)                                                                     */
     VQA_K_SITI = 21,         /* vqa_siti_submit: Sobel, frame difference and their integer sums (one entry per group of
                                 same-geometry planes)                                                                   */
-    VQA_K_LAST = 22,         /* one past VQA_K_SITI, as SI/TI shipped it (kept at 22 for callers and tests that rely on id 22
-                                being unknown); id 22 stays unnamed                                                      */
+    VQA_K_LAST = 22,         /* frozen marker (= 22)                                                                     */
     VQA_K_PSNR_HVS = 23,     /* vqa_psnr_hvs_submit: the 8x8 DCTs, the masks and the two weighted sums (one entry per group of
                                 same-geometry planes)                                                                    */
-    VQA_K_PAST = 24,         /* one past VQA_K_PSNR_HVS, as PSNR-HVS shipped it (kept at 24 for callers and tests that rely on
-                                id 24 being unknown); id 24 stays unnamed                                                */
+    VQA_K_PAST = 24,         /* frozen marker (= 24)                                                                     */
     VQA_K_CIEDE = 25,        /* vqa_ciede_submit: both Lab conversions, dE00 and the fixed-point sum (one entry per submit) */
-    VQA_K_BEYOND = 26,       /* one past VQA_K_CIEDE, as CIEDE2000 shipped it (kept at 26 for callers and tests that rely on
-                                id 26 being unknown); id 26 stays unnamed                                                */
+    VQA_K_BEYOND = 26,       /* frozen marker (= 26)                                                                     */
     VQA_K_GMSD = 27,         /* vqa_gmsd_submit: the 2x2 sums, Prewitt, the similarity and its integer sums (one entry per
                                 group of same-geometry planes)                                                           */
-    VQA_K_LIMIT = 28,        /* one past VQA_K_GMSD, as GMSD shipped it (kept at 28 for callers and tests that rely on id 28
-                                being unknown); id 28 stays unnamed                                                      */
+    VQA_K_LIMIT = 28,        /* frozen marker (= 28)                                                                     */
     VQA_K_CAMBI_MASK = 29,     /* vqa_cambi_submit: 10 bits, anti-dither, mask (one entry per group of same-geometry planes) */
     VQA_K_CAMBI_DECIMATE = 30, /* vqa_cambi_submit: scales 1..4 (one entry per group)                                      */
     VQA_K_CAMBI_CONTRAST = 31, /* vqa_cambi_submit: the 65 x 65 counts and u of one scale (five entries per group)         */
     VQA_K_CAMBI_TOPK = 32,     /* vqa_cambi_submit: a scale's histogram cleared, and its top-K sum (ten entries per group) */
-    VQA_K_TERMINUS = 33,     /* one past VQA_K_CAMBI_TOPK, as CAMBI shipped it (kept at 33 for callers and tests that rely on
-                                id 33 being unknown); id 33 stays unnamed                                                */
+    VQA_K_TERMINUS = 33,     /* frozen marker (= 33)                                                                     */
     VQA_K_XPSNR_ACT = 34,    /* vqa_xpsnr_submit: the luma activity words sa, ta per block (one entry per slice)          */
     VQA_K_XPSNR_SSE = 35,    /* vqa_xpsnr_submit: the squared error per block (one entry per group of same-geometry planes) */
-    VQA_K_BOUND = 36,        /* one past VQA_K_XPSNR_SSE, as XPSNR shipped it (kept at 36 for callers and tests that rely on id 36
-                                being unknown); id 36 stays unnamed                                                      */
+    VQA_K_BOUND = 36,        /* frozen marker (= 36)                                                                     */
     VQA_K_HAARPSI = 37,      /* vqa_haarpsi_submit: the 2x2 sums, the Haar coefficients, the similarities and the integer sums
                                 (one entry per group of same-geometry planes)                                            */
-    VQA_K_FINIS = 38,        /* one past VQA_K_HAARPSI, as HaarPSI shipped it (kept at 38 for callers and tests that rely on id
-                                38 being unknown); id 38 stays unnamed                                                   */
+    VQA_K_FINIS = 38,        /* frozen marker (= 38)                                                                     */
     VQA_K_VCA_BLOCKS = 39,   /* vqa_vca_submit: the 32 x 32 block DCTs, qH_k, S_k, qL_k (one entry per group of same-geometry
                                 planes)                                                                                  */
     VQA_K_VCA_SUM = 40,      /* vqa_vca_submit: the block map and its difference to the frame before, summed (one per slice) */
-    VQA_K_CLOSE = 41,        /* one past VQA_K_VCA_SUM, as VCA shipped it (kept at 41 for callers and tests that rely on id 41
-                                being unknown); id 41 stays unnamed                                                      */
+    VQA_K_CLOSE = 41,        /* frozen marker (= 41)                                                                     */
     VQA_K_ARTIFACTS = 42,    /* vqa_artifacts_submit: the boundary steps by phase, both blur sums and the Laplacian sum (one
                                 entry per group of same-geometry planes)                                                 */
-    VQA_K_STOP = 43,         /* one past VQA_K_ARTIFACTS, as the artefact measures shipped it (kept at 43 for callers and tests
-                                that rely on id 43 being unknown); id 43 stays unnamed                                   */
+    VQA_K_STOP = 43,         /* frozen marker (= 43)                                                                     */
     VQA_K_BRISQUE_HALF = 44, /* vqa_brisque_submit: the exact scale-1 planes (one entry per group of same-geometry planes)   */
     VQA_K_BRISQUE_MSCN = 45, /* vqa_brisque_submit: the moments, u and the pairs inside the plane (two per group: the scales) */
     VQA_K_BRISQUE_SEAM = 46, /* vqa_brisque_submit: the pairs that wrap around (two per group)                                */
-    VQA_K_EDGE = 47,         /* one past VQA_K_BRISQUE_SEAM, as BRISQUE shipped it (kept at 47 for callers and tests that rely on
-                                id 47 being unknown); id 47 stays unnamed                                                */
+    VQA_K_EDGE = 47,         /* frozen marker (= 47)                                                                     */
     VQA_K_MDSI_MAP = 48,     /* vqa_mdsi_submit: the box sums, the channels, Prewitt, GCS, the map of g and the words A, B, n_neg
                                 (one entry per slice)                                                                    */
     VQA_K_MDSI_DEV = 49,     /* vqa_mdsi_submit: the deviation word D from the map and the frame's A, B (one entry per slice) */
-    VQA_K_BRINK = 50,        /* one past VQA_K_MDSI_DEV, as MDSI shipped it (kept at 50 for callers and tests that rely on id 50
-                                being unknown); id 50 stays unnamed                                                      */
+    VQA_K_BRINK = 50,        /* frozen marker (= 50)                                                                     */
     VQA_K_ITP = 51,          /* vqa_itp_submit: both ICtCp conversions, dE_ITP, the fixed-point sum and maximum (one entry per
                                 slice)                                                                                   */
-    VQA_K_VERGE = 52,        /* one past VQA_K_ITP, as dE_ITP shipped it (kept at 52 for callers and tests that rely on id 52
-                                being unknown); id 52 stays unnamed                                                      */
+    VQA_K_VERGE = 52,        /* frozen marker (= 52)                                                                     */
     VQA_K_PU21_ENCODE = 53,  /* vqa_pu21_submit: display light, the PU21 encodings, the q_Y maps and the four SSE half-words (one
                                 entry per sub-slice)                                                                     */
     VQA_K_PU21_SSIM = 54,    /* vqa_pu21_submit: the Gaussian SSIM over the maps (one entry per sub-slice)                     */
-    VQA_K_RIM = 55,          /* one past VQA_K_PU21_SSIM, as PU21 shipped it (kept at 55 for callers and tests that rely on id 55
-                                being unknown); id 55 stays unnamed                                                      */
+    VQA_K_RIM = 55,          /* frozen marker (= 55)                                                                     */
     VQA_K_FSIM_LUMA = 56,    /* vqa_fsim_submit: the box sums and Y, I, Q of both images (one entry per sub-slice)             */
     VQA_K_FSIM_DFT = 57,     /* vqa_fsim_submit: the dense DFTs on the fp64 matrix cores (five entries per sub-slice: the forward
                                 pair and one inverse pair per orientation)                                               */
@@ -2011,40 +2000,27 @@ enum vqa_kernel_id {
     VQA_K_FSIM_MEDIAN = 59,  /* vqa_fsim_submit: the exact medians and the thresholds T_o (one entry per sub-slice)           */
     VQA_K_FSIM_PC = 60,      /* vqa_fsim_submit: PC and the p maps (one entry per sub-slice)                                  */
     VQA_K_FSIM_POOL = 61,    /* vqa_fsim_submit: Scharr, the similarities and the three words (one entry per sub-slice)       */
-    VQA_K_HEM = 62,          /* one past VQA_K_FSIM_POOL, as FSIM shipped it (kept at 62 for callers and tests that rely on id 62
-                                being unknown); id 62 stays unnamed                                                      */
+    VQA_K_HEM = 62,          /* frozen marker (= 62)                                                                     */
     VQA_K_SIGSTATS_ACCUM = 63, /* vqa_sigstats_submit: the histograms, sad, changed, the masks and the profiles (one entry per
                                   group of same-geometry planes and sub-slice)                                           */
     VQA_K_SIGSTATS_SCAN = 64,  /* vqa_sigstats_submit: every other word from the histograms and the profiles (one entry per
                                   sub-slice)                                                                             */
-    VQA_K_FRINGE = 65,       /* one past VQA_K_SIGSTATS_SCAN, as the signal statistics shipped it (kept at 65 for callers and
-                                tests that rely on id 65 being unknown); id 65 stays unnamed                             */
+    VQA_K_FRINGE = 65,       /* frozen marker (= 65)                                                                     */
     VQA_K_SCALE = 66,        /* vqa_scale_submit: both passes of the resampler, fused (one entry per group of planes alike on
                                 both sides)                                                                              */
-    VQA_K_MARGIN = 67,       /* one past the last id: ... VQA_K_SIGSTATS_ACCUM .. VQA_K_FRINGE - 1 and VQA_K_SCALE .. VQA_K_MARGIN - 1 */
-    VQA_K_ALIGN_CROSS = 68,  /* vqa_align_submit: the Gram tiles of the band and E of every frame (one entry per submit); VQA_K_MARGIN
-                                stays 67 as the resampler shipped it (callers and tests rely on id 67 being unknown); id 67 stays
-                                unnamed                                                                                  */
-    VQA_K_LEDGE = 69,        /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
-                                one-past names list, and VQA_K_ALIGN_CROSS .. VQA_K_LEDGE - 1                             */
-    VQA_K_SHIFT = 70,        /* vqa_shift_submit: the tiles of the grid of shifts, E_r and E_d (one entry per submit); VQA_K_LEDGE
-                                stays 69 as the alignment shipped it (callers and tests rely on id 69 being unknown); id 69 stays
-                                unnamed                                                                                  */
-    VQA_K_SILL = 71,         /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
-                                one-past names list, and VQA_K_SHIFT .. VQA_K_SILL - 1                                    */
+    VQA_K_MARGIN = 67,       /* frozen marker (= 67)                                                                     */
+    VQA_K_ALIGN_CROSS = 68,  /* vqa_align_submit: the Gram tiles of the band and E of every frame (one entry per submit)  */
+    VQA_K_LEDGE = 69,        /* frozen marker (= 69)                                                                     */
+    VQA_K_SHIFT = 70,        /* vqa_shift_submit: the tiles of the grid of shifts, E_r and E_d (one entry per submit)     */
+    VQA_K_SILL = 71,         /* frozen marker (= 71)                                                                     */
     VQA_K_LIGHT_ACCUM = 72,  /* vqa_light_submit: the decode, the table gathers, the histogram and the per-frame words (one entry
-                                per sub-slice); VQA_K_SILL stays 71 as the registration shipped it (callers and tests rely on id
-                                71 being unknown); id 71 stays unnamed                                                    */
-    VQA_K_LIGHT_SCAN = 73,   /* the percentile bins off the histograms (one entry per sub-slice)                          */
-    VQA_K_LINTEL = 74,       /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
-                                one-past names list, and VQA_K_LIGHT_ACCUM .. VQA_K_LINTEL - 1                            */
-    VQA_K_SIG = 75,          /* vqa_sig_submit: the cell sums and the signature bytes (one entry per submit); VQA_K_LINTEL stays
-                                74 as the light kind shipped it (callers and tests rely on id 74 being unknown); id 74 stays
-                                unnamed                                                                                  */
+                                per sub-slice)                                                                           */
+    VQA_K_LIGHT_SCAN = 73,   /* vqa_light_submit: the percentile bins off the histograms (one entry per sub-slice)        */
+    VQA_K_LINTEL = 74,       /* frozen marker (= 74)                                                                     */
+    VQA_K_SIG = 75,          /* vqa_sig_submit: the cell sums and the signature bytes (one entry per submit)              */
     VQA_K_SIG_DIAG = 76,     /* vqa_sig_cross_submit: the walk along the tile diagonals, diag (one entry per submit)       */
     VQA_K_SIG_BEST = 77,     /* vqa_sig_cross_submit: the walk along the row strips, best (one entry per submit)           */
-    VQA_K_EAVE = 78          /* one past the last id: vqa_profile_read and vqa_kernel_name know the ids above that the earlier
-                                one-past names list, and VQA_K_SIG .. VQA_K_EAVE - 1                                      */
+    VQA_K_EAVE = 78          /* frozen marker (= 78): one past the last id                                               */
 };
 /* When enabled, every kernel launch made by a submit call is bracketed by a
  * hipEvent pair recorded on the ctx stream; the elapsed times are accumulated

@@ -36,54 +36,57 @@ M_MOTION = 1 << 5
 M_ORB = 1 << 6
 M_ALL = 0x7F
 
-(K_GRAY_HIST, K_RESIZE, K_DCT8, K_DCT_FULL, K_CANNY_NMS, K_CANNY_HYST, K_SAD, K_SSIM_GAUSS, K_SSIM_FFMPEG, K_ORB,
- K_FARNEBACK, K_MS_PYRAMID, K_COUNT) = range(13)
-K_VIF, K_VIF_DECIMATE, K_COUNT_ALL = 12, 13, 14   # added beyond K_COUNT (include/vqa.h: VQA_K_COUNT stays 12)
-K_ADM, K_ADM_REDUCE, K_COUNT_EXT = 16, 17, 18     # added beyond K_COUNT_ALL, which stays 14; ids 14 and 15 are unnamed
-K_MOTION, K_END = 19, 20                          # added beyond K_COUNT_EXT, which stays 18; id 18 is unnamed
-K_IDS = tuple(range(K_COUNT_ALL)) + (K_ADM, K_ADM_REDUCE)   # the ids below K_COUNT_EXT (kept as ADM shipped it)
-K_IDS_ALL = K_IDS + (K_MOTION,)                   # the ids below K_END (kept as motion shipped it)
-K_SITI, K_LAST = 21, 22                           # added beyond K_END, which stays 20; id 20 is unnamed
-K_IDS_KNOWN = K_IDS_ALL + (K_SITI,)               # the ids below K_LAST (kept as SI/TI shipped it)
-K_PSNR_HVS, K_PAST = 23, 24                       # added beyond K_LAST, which stays 22; id 22 is unnamed
-K_IDS_EVERY = K_IDS_KNOWN + (K_PSNR_HVS,)         # the ids below K_PAST (kept as PSNR-HVS shipped it)
-K_CIEDE, K_BEYOND = 25, 26                        # added beyond K_PAST, which stays 24; id 24 is unnamed
-K_IDS_NAMED = K_IDS_EVERY + (K_CIEDE,)            # the ids below K_BEYOND (kept as CIEDE2000 shipped it)
-K_GMSD, K_LIMIT = 27, 28                          # added beyond K_BEYOND, which stays 26; id 26 is unnamed
-K_IDS_LISTED = K_IDS_NAMED + (K_GMSD,)            # the ids below K_LIMIT (kept as GMSD shipped it)
-K_CAMBI_MASK, K_CAMBI_DECIMATE, K_CAMBI_CONTRAST, K_CAMBI_TOPK, K_TERMINUS = 29, 30, 31, 32, 33   # beyond K_LIMIT; id 28 is unnamed
-K_IDS_CAMBI = (K_CAMBI_MASK, K_CAMBI_DECIMATE, K_CAMBI_CONTRAST, K_CAMBI_TOPK)
-K_IDS_TOLD = K_IDS_LISTED + K_IDS_CAMBI           # the ids below K_TERMINUS (kept as CAMBI shipped it)
-K_XPSNR_ACT, K_XPSNR_SSE, K_BOUND = 34, 35, 36    # added beyond K_TERMINUS, which stays 33; id 33 is unnamed
-K_IDS_GIVEN = K_IDS_TOLD + (K_XPSNR_ACT, K_XPSNR_SSE)   # the ids below K_BOUND (kept as XPSNR shipped it)
-K_HAARPSI, K_FINIS = 37, 38                       # added beyond K_BOUND, which stays 36; id 36 is unnamed
-K_IDS_SHOWN = K_IDS_GIVEN + (K_HAARPSI,)          # the ids below K_FINIS (kept as HaarPSI shipped it)
-K_VCA_BLOCKS, K_VCA_SUM, K_CLOSE = 39, 40, 41     # added beyond K_FINIS, which stays 38; id 38 is unnamed
-K_IDS_OPEN = K_IDS_SHOWN + (K_VCA_BLOCKS, K_VCA_SUM)   # the ids below K_CLOSE (kept as VCA shipped it)
-K_ARTIFACTS, K_STOP = 42, 43                      # added beyond K_CLOSE, which stays 41; id 41 is unnamed
-K_IDS_FULL = K_IDS_OPEN + (K_ARTIFACTS,)          # the ids below K_STOP (kept as the artefact measures shipped it)
-K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM, K_EDGE = 44, 45, 46, 47   # added beyond K_STOP, which stays 43; id 43 is unnamed
-K_IDS_WHOLE = K_IDS_FULL + (K_BRISQUE_HALF, K_BRISQUE_MSCN, K_BRISQUE_SEAM)   # the ids below K_EDGE (kept as BRISQUE shipped it)
-K_MDSI_MAP, K_MDSI_DEV, K_BRINK = 48, 49, 50      # added beyond K_EDGE, which stays 47; id 47 is unnamed
-K_IDS_TOTAL = K_IDS_WHOLE + (K_MDSI_MAP, K_MDSI_DEV)   # the ids below K_BRINK (kept as MDSI shipped it)
-K_ITP, K_VERGE = 51, 52                           # added beyond K_BRINK, which stays 50; id 50 is unnamed
-K_IDS_SUM = K_IDS_TOTAL + (K_ITP,)                # the ids below K_VERGE (kept as dE_ITP shipped it)
-K_PU21_ENCODE, K_PU21_SSIM, K_RIM = 53, 54, 55    # added beyond K_VERGE, which stays 52; id 52 is unnamed
-K_IDS_GRAND = K_IDS_SUM + (K_PU21_ENCODE, K_PU21_SSIM)   # the ids below K_RIM (kept as PU21 shipped it)
-K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL, K_HEM = 56, 57, 58, 59, 60, 61, 62   # added beyond K_RIM, which stays 55; id 55 is unnamed
-K_IDS_ENTIRE = K_IDS_GRAND + (K_FSIM_LUMA, K_FSIM_DFT, K_FSIM_ENERGY, K_FSIM_MEDIAN, K_FSIM_PC, K_FSIM_POOL)   # the ids below K_HEM (kept as FSIM shipped it)
-K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN, K_FRINGE = 63, 64, 65   # added beyond K_HEM, which stays 62; id 62 is unnamed
-K_IDS_COMPLETE = K_IDS_ENTIRE + (K_SIGSTATS_ACCUM, K_SIGSTATS_SCAN)   # the ids below K_FRINGE (kept as the signal statistics shipped it)
-K_SCALE, K_MARGIN = 66, 67                        # added beyond K_FRINGE, which stays 65; id 65 is unnamed
-K_IDS_PRESENT = K_IDS_COMPLETE + (K_SCALE,)       # the ids below K_MARGIN (kept as the resampler shipped it)
-K_ALIGN_CROSS, K_LEDGE = 68, 69                   # added beyond K_MARGIN, which stays 67; id 67 is unnamed
-K_IDS_CURRENT = K_IDS_PRESENT + (K_ALIGN_CROSS,)  # the ids below K_LEDGE (kept as the alignment shipped it)
-K_SHIFT, K_SILL = 70, 71                          # added beyond K_LEDGE, which stays 69; id 69 is unnamed
-K_IDS_LATEST = K_IDS_CURRENT + (K_SHIFT,)         # the ids below K_SILL (kept as the registration shipped it)
-K_LIGHT_ACCUM, K_LIGHT_SCAN, K_LINTEL = 72, 73, 74   # added beyond K_SILL, which stays 71; id 71 is unnamed
-K_IDS_NEWEST = K_IDS_LATEST + (K_LIGHT_ACCUM, K_LIGHT_SCAN)   # the ids below K_LINTEL (kept as the light kind shipped it)
-K_SIG, K_SIG_DIAG, K_SIG_BEST, K_EAVE = 75, 76, 77, 78   # added beyond K_LINTEL, which stays 74; id 74 is unnamed
-K_IDS_EXTANT = K_IDS_NEWEST + (K_SIG, K_SIG_DIAG, K_SIG_BEST)   # every id vqa_profile_read and vqa_kernel_name know
+# The kernel ids of include/vqa.h, each written once: (name, id, what vqa_kernel_name answers), ascending, a line per feature.
+# csrc/vqa_capi.hip's KERNELS holds the same rows; a new kernel takes the next id after the last and adds its row to both.
+K_TABLE = (
+    ("K_GRAY_HIST", 0, "k_bgr2gray_hist"), ("K_RESIZE", 1, "k_resize_planes"), ("K_DCT8", 2, "k_dct8"), ("K_DCT_FULL", 3, "k_dct_full"),
+    ("K_CANNY_NMS", 4, "k_canny_nms"), ("K_CANNY_HYST", 5, "k_canny_hyst"), ("K_SAD", 6, "k_block_sad"),
+    ("K_SSIM_GAUSS", 7, "k_ssim_gauss"), ("K_SSIM_FFMPEG", 8, "k_ssim_ffmpeg"), ("K_ORB", 9, "k_orb64"),
+    ("K_FARNEBACK", 10, "farneback(pyramid)"), ("K_MS_PYRAMID", 11, "k_ms_pyramid"),
+    ("K_VIF", 12, "k_vif_stats"), ("K_VIF_DECIMATE", 13, "k_vif_decimate"),
+    ("K_ADM", 16, "k_adm_scale"), ("K_ADM_REDUCE", 17, "k_adm_reduce"),
+    ("K_MOTION", 19, "k_motion_sad"),
+    ("K_SITI", 21, "k_siti"),
+    ("K_PSNR_HVS", 23, "k_psnr_hvs"),
+    ("K_CIEDE", 25, "k_ciede"),
+    ("K_GMSD", 27, "k_gmsd"),
+    ("K_CAMBI_MASK", 29, "k_cambi_mask"), ("K_CAMBI_DECIMATE", 30, "k_cambi_decimate"), ("K_CAMBI_CONTRAST", 31, "k_cambi_contrast"),
+    ("K_CAMBI_TOPK", 32, "k_cambi_topk"),
+    ("K_XPSNR_ACT", 34, "k_xpsnr_act"), ("K_XPSNR_SSE", 35, "k_xpsnr_sse"),
+    ("K_HAARPSI", 37, "k_haarpsi"),
+    ("K_VCA_BLOCKS", 39, "k_vca_blocks"), ("K_VCA_SUM", 40, "k_vca_sum"),
+    ("K_ARTIFACTS", 42, "k_artifacts"),
+    ("K_BRISQUE_HALF", 44, "k_brisque_half"), ("K_BRISQUE_MSCN", 45, "k_brisque_mscn"), ("K_BRISQUE_SEAM", 46, "k_brisque_seam"),
+    ("K_MDSI_MAP", 48, "k_mdsi_map"), ("K_MDSI_DEV", 49, "k_mdsi_dev"),
+    ("K_ITP", 51, "k_itp"),
+    ("K_PU21_ENCODE", 53, "k_pu21_encode"), ("K_PU21_SSIM", 54, "k_pu21_ssim"),
+    ("K_FSIM_LUMA", 56, "k_fsim_luma"), ("K_FSIM_DFT", 57, "k_fsim_dft"), ("K_FSIM_ENERGY", 58, "k_fsim_energy"),
+    ("K_FSIM_MEDIAN", 59, "k_fsim_median"), ("K_FSIM_PC", 60, "k_fsim_pc"), ("K_FSIM_POOL", 61, "k_fsim_pool"),
+    ("K_SIGSTATS_ACCUM", 63, "k_sigstats_accum"), ("K_SIGSTATS_SCAN", 64, "k_sigstats_scan"),
+    ("K_SCALE", 66, "k_scale"),
+    ("K_ALIGN_CROSS", 68, "k_align_cross"),
+    ("K_SHIFT", 70, "k_shift"),
+    ("K_LIGHT_ACCUM", 72, "k_light_accum"), ("K_LIGHT_SCAN", 73, "k_light_scan"),
+    ("K_SIG", 75, "k_sig"), ("K_SIG_DIAG", 76, "k_sig_diag"), ("K_SIG_BEST", 77, "k_sig_best"),
+)
+# The frozen markers: where the id list ended when each feature shipped.  No kernel has a marker's id, but for K_COUNT's: the
+# first kernel added after it, K_VIF, took id 12.  K_EAVE is one past the last id.
+K_MARKERS = {"K_COUNT": 12, "K_COUNT_ALL": 14, "K_COUNT_EXT": 18, "K_END": 20, "K_LAST": 22, "K_PAST": 24, "K_BEYOND": 26,
+             "K_LIMIT": 28, "K_TERMINUS": 33, "K_BOUND": 36, "K_FINIS": 38, "K_CLOSE": 41, "K_STOP": 43, "K_EDGE": 47, "K_BRINK": 50,
+             "K_VERGE": 52, "K_RIM": 55, "K_HEM": 62, "K_FRINGE": 65, "K_MARGIN": 67, "K_LEDGE": 69, "K_SILL": 71, "K_LINTEL": 74,
+             "K_EAVE": 78}
+globals().update({name: k for name, k, _ in K_TABLE}, **K_MARKERS)   # K_GRAY_HIST = 0, ..., K_EAVE = 78
+K_NAMES = {k: kernel for _, k, kernel in K_TABLE}
+K_IDS_EXTANT = tuple(K_NAMES)                     # every id vqa_profile_read and vqa_kernel_name know
+K_IDS_CAMBI = tuple(k for name, k, _ in K_TABLE if name.startswith("K_CAMBI_"))
+# the id lists as earlier features shipped them, each under the name that feature gave it: the ids below that feature's marker
+globals().update({ids: tuple(k for k in K_IDS_EXTANT if k < K_MARKERS[marker]) for ids, marker in (
+    ("K_IDS", "K_COUNT_EXT"), ("K_IDS_ALL", "K_END"), ("K_IDS_KNOWN", "K_LAST"), ("K_IDS_EVERY", "K_PAST"),
+    ("K_IDS_NAMED", "K_BEYOND"), ("K_IDS_LISTED", "K_LIMIT"), ("K_IDS_TOLD", "K_TERMINUS"), ("K_IDS_GIVEN", "K_BOUND"),
+    ("K_IDS_SHOWN", "K_FINIS"), ("K_IDS_OPEN", "K_CLOSE"), ("K_IDS_FULL", "K_STOP"), ("K_IDS_WHOLE", "K_EDGE"),
+    ("K_IDS_TOTAL", "K_BRINK"), ("K_IDS_SUM", "K_VERGE"), ("K_IDS_GRAND", "K_RIM"), ("K_IDS_ENTIRE", "K_HEM"),
+    ("K_IDS_COMPLETE", "K_FRINGE"), ("K_IDS_PRESENT", "K_MARGIN"), ("K_IDS_CURRENT", "K_LEDGE"), ("K_IDS_LATEST", "K_SILL"),
+    ("K_IDS_NEWEST", "K_LINTEL"))})
 
 OPT_OVERLAP, OPT_HYST_STATS = 0, 1
 FLAVOUR_AB_VARIANTS, FLAVOUR_TEST_SEAMS = 1, 2

@@ -3447,16 +3447,68 @@ int vqa_profile_enable(vqa_ctx *c, int on)
     return VQA_OK;
 }
 
+// The kernel ids, written once: a row per id that exists, ascending, a line per feature.  vqa_kernel_name and vqa_profile_read
+// know exactly these rows; every other id below VQA_K_EAVE is a gap and stays unknown.  A new kernel takes the next id after the
+// last and adds its row here and in _native.py's K_TABLE ("Kernel ids").
+namespace {
+struct kernel_row { int id; const char *name; };
+constexpr kernel_row KERNELS[] = {
+    {VQA_K_GRAY_HIST, "k_bgr2gray_hist"}, {VQA_K_RESIZE, "k_resize_planes"}, {VQA_K_DCT8, "k_dct8"}, {VQA_K_DCT_FULL, "k_dct_full"},
+    {VQA_K_CANNY_NMS, "k_canny_nms"}, {VQA_K_CANNY_HYST, "k_canny_hyst"}, {VQA_K_SAD, "k_block_sad"},
+    {VQA_K_SSIM_GAUSS, "k_ssim_gauss"}, {VQA_K_SSIM_FFMPEG, "k_ssim_ffmpeg"}, {VQA_K_ORB, "k_orb64"},
+    {VQA_K_FARNEBACK, "farneback(pyramid)"}, {VQA_K_MS_PYRAMID, "k_ms_pyramid"},
+    {VQA_K_VIF, "k_vif_stats"}, {VQA_K_VIF_DECIMATE, "k_vif_decimate"},
+    {VQA_K_ADM, "k_adm_scale"}, {VQA_K_ADM_REDUCE, "k_adm_reduce"},
+    {VQA_K_MOTION, "k_motion_sad"},
+    {VQA_K_SITI, "k_siti"},
+    {VQA_K_PSNR_HVS, "k_psnr_hvs"},
+    {VQA_K_CIEDE, "k_ciede"},
+    {VQA_K_GMSD, "k_gmsd"},
+    {VQA_K_CAMBI_MASK, "k_cambi_mask"}, {VQA_K_CAMBI_DECIMATE, "k_cambi_decimate"}, {VQA_K_CAMBI_CONTRAST, "k_cambi_contrast"},
+    {VQA_K_CAMBI_TOPK, "k_cambi_topk"},
+    {VQA_K_XPSNR_ACT, "k_xpsnr_act"}, {VQA_K_XPSNR_SSE, "k_xpsnr_sse"},
+    {VQA_K_HAARPSI, "k_haarpsi"},
+    {VQA_K_VCA_BLOCKS, "k_vca_blocks"}, {VQA_K_VCA_SUM, "k_vca_sum"},
+    {VQA_K_ARTIFACTS, "k_artifacts"},
+    {VQA_K_BRISQUE_HALF, "k_brisque_half"}, {VQA_K_BRISQUE_MSCN, "k_brisque_mscn"}, {VQA_K_BRISQUE_SEAM, "k_brisque_seam"},
+    {VQA_K_MDSI_MAP, "k_mdsi_map"}, {VQA_K_MDSI_DEV, "k_mdsi_dev"},
+    {VQA_K_ITP, "k_itp"},
+    {VQA_K_PU21_ENCODE, "k_pu21_encode"}, {VQA_K_PU21_SSIM, "k_pu21_ssim"},
+    {VQA_K_FSIM_LUMA, "k_fsim_luma"}, {VQA_K_FSIM_DFT, "k_fsim_dft"}, {VQA_K_FSIM_ENERGY, "k_fsim_energy"},
+    {VQA_K_FSIM_MEDIAN, "k_fsim_median"}, {VQA_K_FSIM_PC, "k_fsim_pc"}, {VQA_K_FSIM_POOL, "k_fsim_pool"},
+    {VQA_K_SIGSTATS_ACCUM, "k_sigstats_accum"}, {VQA_K_SIGSTATS_SCAN, "k_sigstats_scan"},
+    {VQA_K_SCALE, "k_scale"},
+    {VQA_K_ALIGN_CROSS, "k_align_cross"},
+    {VQA_K_SHIFT, "k_shift"},
+    {VQA_K_LIGHT_ACCUM, "k_light_accum"}, {VQA_K_LIGHT_SCAN, "k_light_scan"},
+    {VQA_K_SIG, "k_sig"}, {VQA_K_SIG_DIAG, "k_sig_diag"}, {VQA_K_SIG_BEST, "k_sig_best"},
+};
+constexpr int N_KERNELS = sizeof(KERNELS) / sizeof(KERNELS[0]);
+
+constexpr bool kernels_ascending()
+{
+    for (int i = 1; i < N_KERNELS; i++)
+        if (KERNELS[i - 1].id >= KERNELS[i].id) return false;
+    return KERNELS[0].id >= 0;
+}
+static_assert(kernels_ascending(), "KERNELS: the rows are in strictly ascending id order");
+static_assert(KERNELS[N_KERNELS - 1].id == VQA_K_EAVE - 1, "KERNELS: the last row is the last id, and VQA_K_EAVE sizes prof_ms / prof_n");
+static_assert(N_KERNELS == 55, "KERNELS: a kernel id was added or removed without its row");
+
+// id -> name, null for a gap
+struct kernel_names { const char *of[VQA_K_EAVE]; };
+constexpr kernel_names kernel_names_by_id()
+{
+    kernel_names t{};
+    for (const kernel_row &r : KERNELS) t.of[r.id] = r.name;
+    return t;
+}
+constexpr kernel_names KERNEL_NAME = kernel_names_by_id();
+} // namespace
+
 int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, int reset)
 {
-    if (!c || id < 0 || id >= VQA_K_EAVE || (id >= VQA_K_LINTEL && id < VQA_K_SIG) || (id >= VQA_K_SILL && id < VQA_K_LIGHT_ACCUM) || (id >= VQA_K_LEDGE && id < VQA_K_SHIFT) || (id >= VQA_K_MARGIN && id < VQA_K_ALIGN_CROSS) || (id >= VQA_K_FRINGE && id < VQA_K_SCALE) || (id >= VQA_K_HEM && id < VQA_K_SIGSTATS_ACCUM) || (id >= VQA_K_COUNT_ALL && id < VQA_K_ADM) || (id >= VQA_K_COUNT_EXT && id < VQA_K_MOTION) ||
-        (id >= VQA_K_END && id < VQA_K_SITI) || (id >= VQA_K_LAST && id < VQA_K_PSNR_HVS) ||
-        (id >= VQA_K_PAST && id < VQA_K_CIEDE) || (id >= VQA_K_BEYOND && id < VQA_K_GMSD) || (id >= VQA_K_LIMIT && id < VQA_K_CAMBI_MASK) ||
-        (id >= VQA_K_TERMINUS && id < VQA_K_XPSNR_ACT) || (id >= VQA_K_BOUND && id < VQA_K_HAARPSI) ||
-        (id >= VQA_K_FINIS && id < VQA_K_VCA_BLOCKS) || (id >= VQA_K_CLOSE && id < VQA_K_ARTIFACTS) || (id >= VQA_K_STOP && id < VQA_K_BRISQUE_HALF) ||
-        (id >= VQA_K_EDGE && id < VQA_K_MDSI_MAP) || (id >= VQA_K_BRINK && id < VQA_K_ITP) || (id >= VQA_K_VERGE && id < VQA_K_PU21_ENCODE) ||
-        (id >= VQA_K_RIM && id < VQA_K_FSIM_LUMA))
-        return VQA_ERR_INVALID;
+    if (!c || id < 0 || id >= VQA_K_EAVE || !KERNEL_NAME.of[id]) return VQA_ERR_INVALID;
     if (!busy(c)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         prof_collect(c);
@@ -3469,52 +3521,8 @@ int vqa_profile_read(vqa_ctx *c, int id, double *total_ms, int64_t *launches, in
 
 const char *vqa_kernel_name(int id)
 {
-    static const char *names[VQA_K_COUNT_ALL] = {"k_bgr2gray_hist", "k_resize_planes", "k_dct8", "k_dct_full",
-                                             "k_canny_nms", "k_canny_hyst", "k_block_sad", "k_ssim_gauss",
-                                             "k_ssim_ffmpeg", "k_orb64", "farneback(pyramid)", "k_ms_pyramid",
-                                             "k_vif_stats", "k_vif_decimate"};
-    if (id == VQA_K_ADM) return "k_adm_scale";
-    if (id == VQA_K_ADM_REDUCE) return "k_adm_reduce";
-    if (id == VQA_K_MOTION) return "k_motion_sad";
-    if (id == VQA_K_SITI) return "k_siti";
-    if (id == VQA_K_PSNR_HVS) return "k_psnr_hvs";
-    if (id == VQA_K_CIEDE) return "k_ciede";
-    if (id == VQA_K_GMSD) return "k_gmsd";
-    if (id == VQA_K_CAMBI_MASK) return "k_cambi_mask";
-    if (id == VQA_K_CAMBI_DECIMATE) return "k_cambi_decimate";
-    if (id == VQA_K_CAMBI_CONTRAST) return "k_cambi_contrast";
-    if (id == VQA_K_CAMBI_TOPK) return "k_cambi_topk";
-    if (id == VQA_K_XPSNR_ACT) return "k_xpsnr_act";
-    if (id == VQA_K_XPSNR_SSE) return "k_xpsnr_sse";
-    if (id == VQA_K_HAARPSI) return "k_haarpsi";
-    if (id == VQA_K_VCA_BLOCKS) return "k_vca_blocks";
-    if (id == VQA_K_VCA_SUM) return "k_vca_sum";
-    if (id == VQA_K_ARTIFACTS) return "k_artifacts";
-    if (id == VQA_K_BRISQUE_HALF) return "k_brisque_half";
-    if (id == VQA_K_BRISQUE_MSCN) return "k_brisque_mscn";
-    if (id == VQA_K_BRISQUE_SEAM) return "k_brisque_seam";
-    if (id == VQA_K_MDSI_MAP) return "k_mdsi_map";
-    if (id == VQA_K_MDSI_DEV) return "k_mdsi_dev";
-    if (id == VQA_K_ITP) return "k_itp";
-    if (id == VQA_K_PU21_ENCODE) return "k_pu21_encode";
-    if (id == VQA_K_PU21_SSIM) return "k_pu21_ssim";
-    if (id == VQA_K_FSIM_LUMA) return "k_fsim_luma";
-    if (id == VQA_K_FSIM_DFT) return "k_fsim_dft";
-    if (id == VQA_K_FSIM_ENERGY) return "k_fsim_energy";
-    if (id == VQA_K_FSIM_MEDIAN) return "k_fsim_median";
-    if (id == VQA_K_FSIM_PC) return "k_fsim_pc";
-    if (id == VQA_K_FSIM_POOL) return "k_fsim_pool";
-    if (id == VQA_K_SIGSTATS_ACCUM) return "k_sigstats_accum";
-    if (id == VQA_K_SIGSTATS_SCAN) return "k_sigstats_scan";
-    if (id == VQA_K_SCALE) return "k_scale";
-    if (id == VQA_K_ALIGN_CROSS) return "k_align_cross";
-    if (id == VQA_K_SHIFT) return "k_shift";
-    if (id == VQA_K_LIGHT_ACCUM) return "k_light_accum";
-    if (id == VQA_K_LIGHT_SCAN) return "k_light_scan";
-    if (id == VQA_K_SIG) return "k_sig";
-    if (id == VQA_K_SIG_DIAG) return "k_sig_diag";
-    if (id == VQA_K_SIG_BEST) return "k_sig_best";
-    return (id >= 0 && id < VQA_K_COUNT_ALL) ? names[id] : "?";
+    const char *name = (id >= 0 && id < VQA_K_EAVE) ? KERNEL_NAME.of[id] : nullptr;
+    return name ? name : "?";
 }
 
 // ---------------------------------------------------------------------------
