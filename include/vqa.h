@@ -508,6 +508,21 @@ typedef struct vqa_light_metrics {
     double share_p3;           /* out_p3 / N                                                                                    */
 } vqa_light_metrics;
 
+/* Colour registration of one frame pair, the planes of a pixel taken together on the luma grid (vqa_colorfit_submit /
+ * vqa_colorfit_wait; the definition, the bounds and the host formulas are stated there).  r_i: the sample of plane i of the
+ * reference, d_k: of plane k of the distorted frame; every sum runs over the h w luma positions and every word is an exact
+ * integer below 2^60.  With one plane the words of planes 1 and 2 are 0. */
+typedef struct vqa_colorfit_metrics {
+    uint64_t count;            /* N = h w                                                                                       */
+    uint64_t sum_r[3];         /* sum r_i                                                                                       */
+    uint64_t sum_d[3];         /* sum d_k                                                                                       */
+    uint64_t rr[6];            /* sum r_i r_i' for (i, i') = 00, 01, 02, 11, 12, 22                                             */
+    uint64_t rd[9];            /* rd[3 i + k] = sum r_i d_k                                                                     */
+    uint64_t dd[3];            /* sum d_k^2                                                                                     */
+    uint64_t sse[3];           /* dd[k] - 2 rd[4 k] + rr(k, k), formed by the wait: the exact squared error of plane k on this
+                                  grid; for plane 0 exactly vqa_plane_metrics.sse of the same pair                              */
+} vqa_colorfit_metrics;
+
 /* ---- lifecycle ------------------------------------------------------------ */
 VQA_API int vqa_abi_version(void);
 VQA_API const char *vqa_strerror(int status);
@@ -1918,6 +1933,85 @@ VQA_API int vqa_sig_wait(vqa_ctx *ctx, uint8_t *sig, int n);   /* n == the submi
 VQA_API int vqa_sig_cross_submit(vqa_ctx *ctx, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref);
 /* n_diag == n_dist + n_ref - 1 and n_best == n_dist */
 VQA_API int vqa_sig_cross_wait(vqa_ctx *ctx, uint64_t *diag, int64_t n_diag, uint64_t *best, int64_t n_best);
+
+/* ---- Colour registration: does a code value mean the same in both streams? ----
+ * vqa_align_submit and vqa_sig_submit find which frame pairs with which, vqa_shift_submit where the picture sits, vqa_light_submit
+ * checks the container.  This kind measures what is still taken on trust: a limited / full range mix-up, a BT.601 matrix applied
+ * to BT.709 material and a gamma or transfer mismatch do to every full-reference figure what a dropped frame does.  Per frame
+ * pair it returns the joint first and second moments of the planes of both streams and, per reference code, the count, sum and
+ * sum of squares of the distorted samples; from those the host derives, in exact rational arithmetic, the per-plane gain and
+ * offset, the best 3 x 3 matrix plus offset, the best per-code tone curve and the error each would leave.  It reports and never
+ * corrects.
+ * Input.  Two streams of n frames, frame j against frame j; n_planes is 1 or 3, one depth per submit: 8 bits (bit_depth 0 or 8), or
+ *   9 .. 16 bits as little-endian uint16; samples above 2^depth - 1 are read as they are.  The geometry rules and errors are
+ *   vqa_ciede_submit's / vqa_itp_submit's: luma at least 16 x 16 and h w <= 2^28 (VQA_ERR_UNSUPPORTED beyond either); planes 1
+ *   and 2 of equal geometry, each side either the luma's or its ceil-half; any offset, row stride and pixel step those kinds
+ *   accept, packed bgr24 included; host, pinned or device memory.  1 <= n <= VQA_COLORFIT_MAX_FRAMES per submit,
+ *   VQA_ERR_UNSUPPORTED beyond: a longer clip goes in windows, so this kind has no slice seam.  The device needs no colour model:
+ *   it forms integer moments only.
+ * Grid.  The luma grid, chroma replicated, as in vqa_ciede_submit: plane p at luma position (y, x) is its sample at
+ *   (y >> sy, x >> sx), sx / sy = 1 where the plane is halved in that direction.  Every sum runs over the h w luma positions.
+ * Record, ONE ENTRY PER FRAME (vqa_colorfit_metrics): count = h w; sum_r[3], sum_d[3]; rr[6] = sum r_i r_i' for (i, i') = 00, 01,
+ *   02, 11, 12, 22; rd[3 i + k] = sum r_i d_k; dd[3] = sum d_k^2; sse[k] = dd[k] - 2 rd[4 k] + rr(k, k), formed by the wait.
+ *   Bound: 65535^2 2^28 < 2^60.
+ * Transfer tables.  Optional (want_tables) and ONE set per submit, not per frame.  bins = 1 << min(depth, 10) and
+ *   bin = min(r_p >> max(depth - 10, 0), bins - 1).  Per plane and bin three uint64 words, summed over all frames and luma
+ *   positions of the submit: count, sum_d (of d_p of the same plane) and sum_dd.  Layout [n_planes][bins][3].  With tables
+ *   n h w <= VQA_COLORFIT_TABLE_POSITIONS = 2^31 is required (then sum_dd < 2^63): VQA_ERR_UNSUPPORTED beyond, checked before any
+ *   byte is read.  Without want_tables no table work is done at all.
+ * What follows: every word is an integer sum.  A frame pair gives the same record in any batch at any position, from any memory,
+ *   alone or next to other kinds pending on the ctx.  The tables of a submit equal the sum of the tables of its frames submitted
+ *   one by one.  Identical streams give sse == 0, rd[4 k] == rr(k, k) == dd[k], and every bin has sum_d == the sum over the bin
+ *   of r.
+ * Host formulas (rtvqa_amd/colorfit.py forms them in exact fractions; a C caller can do the same from the record).  Sum the
+ *   records of a clip.  With n = count, A = [[n, sum_r^T], [sum_r, rr]] (4 x 4, rr as the symmetric matrix) and
+ *   c_k = (sum_d[k], rd[., k]), a map d_k ~ b_k + sum_i M[k][i] r_i with x = (b_k, M[k][.]) leaves
+ *     sse_k(x) = dd[k] - 2 x . c_k + x^T A x.
+ *   Given: sse_given[k] = sse[k].
+ *   Levels: var = n rr(k, k) - sum_r[k]^2, cov = n rd[4 k] - sum_r[k] sum_d[k]; gain = cov / var,
+ *     offset = (sum_d[k] - gain sum_r[k]) / n, sse_affine[k] = dd[k] - sum_d[k]^2 / n - cov^2 / (n var).  A flat reference plane
+ *     (var == 0): gain = 1, offset = (sum_d[k] - sum_r[k]) / n, sse_affine[k] = dd[k] - sum_d[k]^2 / n.
+ *   Matrix: V[i][i'] = n rr(i, i') - sum_r[i] sum_r[i'], W[i][k] = n rd[3 i + k] - sum_r[i] sum_d[k]; solve V m_k = W[., k] by
+ *     elimination in the order 0, 1, 2 without exchanges (V is positive semidefinite: the pivots are Schur complements >= 0; a
+ *     zero pivot drops that reference plane, its coefficient is 0 in all three fits); b_k from the means;
+ *     sse_matrix[k] = dd[k] - sum_d[k]^2 / n - sum_i m_ki W[i][k] / n.
+ *   Tone (tables): curve[p][bin] = sum_d / count; sse_lut[p] = the sum over non-empty bins of (sum_dd - sum_d^2 / count);
+ *     dB(sse_affine, sse_lut) is what a per-code curve explains beyond gain and offset: a gamma or transfer mismatch.
+ *   Catalogue of known mishaps, exact rational maps in code space scored by sse_k(x), s = 2^(depth - 8), P = 2^depth - 1:
+ *     limited_to_full: d_Y = (r_Y - 16 s) P / (219 s), d_C = (r_C - 128 s) P / (224 s) + 128 s; full_to_limited: its inverse;
+ *     bt601_to_bt709 (Y'CbCr, three planes): S F709 F601^-1 S^-1 about the centre (16 s, 128 s, 128 s), F the R'G'B' -> Y'PbPr
+ *     matrix of (Kr, Kb) = (0.299, 0.114) and (0.2126, 0.0722), S = diag(219, 224, 224); bt709_to_bt601: the reverse.  B, G, R
+ *     and one plane take the two range maps with the luma constants on every plane.  The candidate with the smallest total
+ *     error (ties: this order) is NAMED when 2 sse_candidate <= sse_given and sse_given > 0 - it accounts for at least as much
+ *     error as everything else together; the factor 2 is the rule's definition.  dB(a, b) = 0 if a == 0, infinite if b == 0 < a,
+ *     else 10 log10(a / b).
+ *   No clipping is modelled anywhere: clipped samples stay in the residual.
+ * Limits and errors: n_planes other than 1 or 3, mixed depths, chroma geometries that differ or are neither the luma's nor its
+ *   ceil-half, a want_tables other than 0 or 1: VQA_ERR_INVALID.  The contract of vqa_ciede_submit otherwise: asynchronous, the
+ *   same descriptors, alignment rules, memory kinds and failure guarantee - a failed submit leaves nothing in flight; a frame
+ *   stride smaller than the planes' span is VQA_ERR_INVALID for a stream of more than one frame.
+ * A colour-fit batch is a batch of its own: VQA_ERR_STATE for a second submit while one is pending and for a wait without a
+ *   submit or with n_entries != n (the batch stays pending); in flight next to a batch of every other kind.  vqa_colorfit_wait:
+ *   tables must be NULL unless the submit asked for them (VQA_ERR_INVALID), and n_table_words must then be n_planes bins 3
+ *   (VQA_ERR_STATE); either refusal leaves the batch pending; NULL is always accepted.  Host frames are staged in the buffers the
+ *   pair kinds share.  Scratch: 192 bytes per frame and 24 n_planes bins bytes of tables, on the device and pinned, kept by the
+ *   ctx until vqa_trim / vqa_destroy.
+ * Kernel: k_colorfit, ONE launch per submit, tables fused: a thread owns a 2 x 4 luma patch of both images as in k_ciede, so every
+ *   sample of both streams is read once; a workgroup walks 16384 positions of one frame, then one 64-bit atomic add per word.  The
+ *   tables live in LDS (at most 48 KB: count and sum_d in 32 bits, sum_dd in 64; 16384 positions keep them below 2^14, 2^30 and
+ *   2^46); equal adjacent bins of a thread, and a wave whose entries all name one bin, are joined before they reach LDS, so a
+ *   chroma sample enters once with its weight and flat content does not serialise.  The kernel has no profiling id
+ *   (enum vqa_kernel_id is closed): time it from outside.
+ * Not built: applying the fit; clipping-aware fits; per-frame tables; chroma interpolation other than replication; a fit after
+ *   vqa_scale_submit; running inside another kind's pass.
+ * out of vqa_colorfit_wait: n entries (n_entries = n); tables: n_table_words = n_planes * bins * 3 words, or NULL.            */
+#define VQA_COLORFIT_MAX_FRAMES 32768
+#define VQA_COLORFIT_MAX_BINS 1024
+#define VQA_COLORFIT_TABLE_POSITIONS 2147483648LL   /* 2^31: n h w of a submit with tables                                   */
+VQA_API int vqa_colorfit_submit(vqa_ctx *ctx, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n,
+                                int64_t ref_frame_stride, int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes,
+                                int want_tables);
+VQA_API int vqa_colorfit_wait(vqa_ctx *ctx, vqa_colorfit_metrics *out, int n_entries, uint64_t *tables, int64_t n_table_words);
 
 /* ---- per-kernel timing (HIP events on the ctx stream) -----------------------
  * The named kernel ids are exactly the ids for which vqa_kernel_name does not return "?"; vqa_profile_read accepts those and

@@ -152,6 +152,10 @@ LIGHT_GAMUT_709, LIGHT_GAMUT_P3 = 0, 1   # vqa_light_gamut's gamuts
 LIGHT_GAMUTS = {"bt709": LIGHT_GAMUT_709, "p3": LIGHT_GAMUT_P3}
 LIGHT_GAMUT_REL_SHIFT, LIGHT_GAMUT_FLOOR = 6, 1 << 32   # outside: min S < -((qmax << 16) >> 6) - 2^32
 LIGHT_WALK, LIGHT_SUB_FRAMES = 8, 16384   # k_light_accum: chunks of 256 patches per workgroup; frames of one sub-slice
+COLORFIT_MIN_DIM = 16         # vqa_colorfit_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+COLORFIT_MAX_FRAMES = 32768   # vqa_colorfit_submit: the frames of one submit
+COLORFIT_MAX_BINS = 1024      # the bins of one plane's transfer table: 1 << min(depth, 10)
+COLORFIT_TABLE_POSITIONS = 1 << 31   # n h w of a submit with tables
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -295,6 +299,11 @@ class VqaLightMetrics(C.Structure):
                 ("share_p3", C.c_double)]
 
 
+class VqaColorfitMetrics(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("sum_r", C.c_uint64 * 3), ("sum_d", C.c_uint64 * 3), ("rr", C.c_uint64 * 6),
+                ("rd", C.c_uint64 * 9), ("dd", C.c_uint64 * 3), ("sse", C.c_uint64 * 3)]
+
+
 class VqaSigstatsMetrics(C.Structure):
     _fields_ = [("count", C.c_int64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32),
                 ("low", C.c_uint32), ("median", C.c_uint32), ("high", C.c_uint32), ("or_mask", C.c_uint32),
@@ -409,6 +418,9 @@ SIGNATURES = {
     "vqa_sig_wait": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "vqa_sig_cross_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, _u8p, C.c_int]),
     "vqa_sig_cross_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_uint64), C.c_int64]),
+    "vqa_colorfit_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
+                                      C.c_int]),
+    "vqa_colorfit_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaColorfitMetrics), C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

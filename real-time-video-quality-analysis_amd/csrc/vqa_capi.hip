@@ -81,6 +81,8 @@ enum batch_kind {
     KIND_SIG,         // VQA_SIG_BYTES bytes per frame (host frames: qstage_dist)
     KIND_SIGX,        // the words of diag, then the words of best; work: the staged signatures of either side; the two counts of
                       // the batch in flight are named members of the ctx (sigx_*)
+    KIND_COLORFIT,    // COLORFIT_WORDS per frame, then (want_tables) the table words of the submit; their count is a named member
+                      // of the ctx (colorfit_table_words)
     KIND_COUNT
 };
 
@@ -155,6 +157,7 @@ struct vqa_ctx {
     int sigx_n_dist = 0, sigx_n_ref = 0; // the pending cross batch (slot[KIND_SIGX])
     bool light_hist = false;             // the pending light batch (slot[KIND_LIGHT]) keeps its histograms for the wait
     std::vector<uint64_t> light_table;   // the table of the last light submit: what slot[KIND_LIGHT].work[0] holds, and what the wait reads
+    int64_t colorfit_table_words = 0;    // the pending colour-fit batch (slot[KIND_COLORFIT]) keeps that many table words (0: none)
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
     int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what FSIM's kept maps hold (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
@@ -3346,6 +3349,60 @@ int vqa_light_gamut(int gamut, int64_t m[9])
 {
     if (!m) return VQA_ERR_INVALID;
     return light_gamut_host(gamut, m) ? VQA_OK : VQA_ERR_INVALID;
+}
+
+// ---------------------------------------------------------------------------
+// Colour registration: both streams, the planes of a pixel together, one entry per frame and ONE set of tables per submit.  A
+// batch of its own, ordered by the stream like a CIEDE2000 batch, whose checks, geometry rules and host staging (qstage_*) it
+// shares.  No kernel id: the kernel carries no prof_scope.
+static int colorfit_submit_body(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs,
+                                int64_t dist_fs, const vqa_plane_desc *planes, int n_planes, int want_tables, bool &touched)
+{
+    if (bad_batch_args(c, ref, dist, mem_kind, n, planes, n_planes)) return VQA_ERR_INVALID;
+    if ((n_planes != 1 && n_planes != 3) || (want_tables != 0 && want_tables != 1)) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_COLORFIT];
+    plane_batch B;
+    int rc = check_batch(s, n, ref_fs, dist_fs, planes, n_planes, B, plane0_limits(planes, COLORFIT_MIN_DIM),
+                         n_planes == 3 ? JOINT_YUV : JOINT_NONE);
+    if (rc) return rc;
+    if (n > VQA_COLORFIT_MAX_FRAMES) return VQA_ERR_UNSUPPORTED;
+    // (n h w <= 2^31 keeps a table's sum_dd below 2^63; no byte has been read so far)
+    if (want_tables && (int64_t)n * planes[0].width * planes[0].height > VQA_COLORFIT_TABLE_POSITIONS) return VQA_ERR_UNSUPPORTED;
+    if ((rc = stage_pair(c, touched, mem_kind, n, B.span, ref, ref_fs, dist, dist_fs))) return rc;
+    const int depth = B.depth;
+    const size_t acc_words = (size_t)COLORFIT_WORDS * (size_t)n;
+    const size_t tab_words = want_tables ? (size_t)n_planes * colorfit_bins(depth) * 3 : 0;
+    const size_t bytes = sizeof(unsigned long long) * (acc_words + tab_words);
+    if ((rc = ensure(c, s.dev, bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, bytes, c->stream));
+    unsigned long long *acc = (unsigned long long *)s.dev.p;
+    launch_colorfit(c->stream, ref, dist, n, ref_fs, dist_fs, planes, n_planes, depth, acc, want_tables ? acc + acc_words : nullptr);
+    c->colorfit_table_words = (int64_t)tab_words;
+    return finish_batch(c, s, bytes, n, planes, n_planes, depth);
+}
+
+int vqa_colorfit_submit(vqa_ctx *c, const uint8_t *ref, const uint8_t *dist, int mem_kind, int n, int64_t ref_fs, int64_t dist_fs,
+                        const vqa_plane_desc *planes, int n_planes, int want_tables)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return colorfit_submit_body(c, ref, dist, mem_kind, n, ref_fs, dist_fs, planes, n_planes, want_tables, touched);
+    });
+}
+
+int vqa_colorfit_wait(vqa_ctx *c, vqa_colorfit_metrics *out, int n_entries, uint64_t *tables, int64_t n_table_words)
+{
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_COLORFIT, out, n_entries, s)) return rc;
+    // (either refusal leaves the batch pending)
+    if (tables && !c->colorfit_table_words) return VQA_ERR_INVALID;
+    if (tables && n_table_words != c->colorfit_table_words) return VQA_ERR_STATE;
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *acc = (const unsigned long long *)s->host.p;
+    for (int e = 0; e < n_entries; e++) colorfit_finalize(acc + (size_t)e * COLORFIT_WORDS, s->h[0], s->w[0], s->planes, out + e);
+    if (tables) memcpy(tables, acc + (size_t)n_entries * COLORFIT_WORDS, sizeof(uint64_t) * (size_t)n_table_words);
+    s->entries = 0;
+    return VQA_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -712,4 +712,19 @@ void launch_sig(hipStream_t st, const uint8_t *frames, int n, int64_t frame_stri
 void launch_sig_diag(hipStream_t st, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref, unsigned long long *diag);
 void launch_sig_best(hipStream_t st, const uint8_t *dist_sig, int n_dist, const uint8_t *ref_sig, int n_ref, unsigned long long *best);
 
+// Colour registration (vqa_colorfit_submit): k_colorfit.hip
+constexpr int COLORFIT_MIN_DIM = 16;   // the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
+constexpr int COLORFIT_WALK = 8;       // chunks of 256 patches a workgroup walks before it flushes (16384 positions)
+// the words of a frame: sum_r[3], sum_d[3], rr[6], rd[9], dd[3] of vqa_colorfit_metrics, in its order
+enum colorfit_word { COLORFIT_SUM_R = 0, COLORFIT_SUM_D = 3, COLORFIT_RR = 6, COLORFIT_RD = 12, COLORFIT_DD = 21, COLORFIT_WORDS = 24 };
+// the bins of one plane's transfer table
+constexpr int colorfit_bins(int depth) { return 1 << (depth < 10 ? depth : 10); }
+// n frame pairs of one or three planes (checked by the caller as for launch_ciede; n rides in gridDim.y).  Adds into
+// acc[frame * COLORFIT_WORDS ..] and, unless tables is null, into tables[plane][bin][3] of the whole call; the caller has zeroed both.
+void launch_colorfit(hipStream_t st, const uint8_t *ref, const uint8_t *dist, int n, int64_t ref_frame_stride,
+                     int64_t dist_frame_stride, const vqa_plane_desc *planes, int n_planes, int depth, unsigned long long *acc,
+                     unsigned long long *tables);
+// the words -> the record (h x w: the luma grid): count, the words, and sse = dd - 2 rd + rr of the planes the submit had
+void colorfit_finalize(const unsigned long long *words, int h, int w, int n_planes, vqa_colorfit_metrics *out);
+
 } // namespace vqa

@@ -101,6 +101,9 @@ LIGHT_DTYPE = np.dtype([("count", np.int64), ("max_code", np.uint32, (3,)), ("ma
                         ("y_max", np.float64), ("maxscl", np.float64, (3,)), ("pct_nits", np.float64, (10,)),
                         ("share_709", np.float64), ("share_p3", np.float64)], align=True)
 assert LIGHT_DTYPE.itemsize == C.sizeof(N.VqaLightMetrics) == 280
+COLORFIT_DTYPE = np.dtype([("count", np.uint64), ("sum_r", np.uint64, (3,)), ("sum_d", np.uint64, (3,)), ("rr", np.uint64, (6,)),
+                           ("rd", np.uint64, (9,)), ("dd", np.uint64, (3,)), ("sse", np.uint64, (3,))], align=True)
+assert COLORFIT_DTYPE.itemsize == C.sizeof(N.VqaColorfitMetrics) == 224
 # the plane-batch kinds, each a batch of its own: the Engine's pending slot -> (submit, wait, record dtype, record ctype)
 _BATCHES = {
     "_pending_q": ("vqa_quality_submit", "vqa_quality_wait", PLANE_DTYPE, N.VqaPlaneMetrics),
@@ -178,6 +181,11 @@ def scale_filter(filter):
     if not isinstance(filter, (str, bool)) and filter in N.SCALE_FILTERS.values():
         return int(filter)
     raise ValueError("scale filter must be one of %s (got %r)" % (", ".join(repr(k) for k in N.SCALE_FILTERS), filter))
+
+
+def colorfit_bins(depth):
+    """the bins of one plane's transfer table of vqa_colorfit_submit: 1 << min(depth, 10)"""
+    return 1 << min(int(depth), 10)
 
 
 def light_table(transfer="pq"):
@@ -461,14 +469,14 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
                      "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait,
                      "_pending_l": self.align_wait, "_pending_j": self.shift_wait,
                      "_pending_o": self.light_wait, "_pending_sg": self.signature_wait,
-                     "_pending_sx": self.sig_cross_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_sx": self.sig_cross_wait, "_pending_cf": self.colorfit_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1343,6 +1351,34 @@ class Engine:
         light.summarise reads MaxCLL, MaxFALL and the shares off the records."""
         self.light_submit(frames, planes, model, transfer, full_range, table, histogram, frame_bytes)
         return self.light_wait()
+
+    # ---- colour registration ------------------------------------------------------------
+    def colorfit_submit(self, ref, dist, planes, tables=False, frame_bytes=None):
+        """The joint integer moments of the planes of n frame pairs and, with tables=True, ONE set of per-code transfer tables
+        for the whole submit (vqa_colorfit_submit): the arrays / DeviceFrames and plane tuples of ciede_submit, ONE or THREE
+        planes taken together on the luma grid, chroma replicated; luma at least 16 x 16; at most N.COLORFIT_MAX_FRAMES frames,
+        and with tables n h w <= 2^31.  A batch of its own, like ciede_submit."""
+        *args, keep = self._pair_args(ref, dist, planes, frame_bytes)
+        st = self.lib.vqa_colorfit_submit(self.ctx, *args, plane_descs(planes), len(planes), 1 if tables else 0)
+        N.check(st, "vqa_colorfit_submit", self.ctx)
+        words = len(planes) * colorfit_bins(planes_depth(planes)) * 3 if tables else 0
+        self._pending_cf = (args[3], len(planes), words, keep)
+
+    def colorfit_wait(self):
+        """-> ([n] records (COLORFIT_DTYPE), uint64 [n_planes, bins, 3] tables (count, sum_d, sum_dd) or None)."""
+        n, npl, words, _keep = getattr(self, "_pending_cf", None) or (1, 1, 0, None)   # (nothing pending: the library says so)
+        rec = np.zeros(n, dtype=COLORFIT_DTYPE)
+        tab = np.zeros(words, np.uint64) if words else None
+        st = self.lib.vqa_colorfit_wait(self.ctx, rec.ctypes.data_as(C.POINTER(N.VqaColorfitMetrics)), n,
+                                        tab.ctypes.data_as(C.POINTER(C.c_uint64)) if words else None, words)
+        self._pending_cf = None
+        N.check(st, "vqa_colorfit_wait", self.ctx)
+        return rec, (tab.reshape(npl, -1, 3) if words else None)
+
+    def colorfit(self, ref, dist, planes, tables=False, frame_bytes=None):
+        """colorfit_submit and colorfit_wait -> (records, tables or None); colorfit.analyse reads the fits off them."""
+        self.colorfit_submit(ref, dist, planes, tables, frame_bytes)
+        return self.colorfit_wait()
 
     # ---- clip-wide sync: frame signatures and their all-pairs distance ------------------
     def signature_submit(self, frames, planes, plane=0, frame_bytes=None):

@@ -548,8 +548,8 @@ def _sync_streams(request, ref, dist, layout, h, w, dh, dw, device):
 
 
 def _with_sync_keys(extra, keys):
-    """the log's further keys with the six SYNC_* keys in their place: after what is there (DIST_RES, SCALE and the LIGHT_*
-    keys) and before the ALIGN_* / SHIFT_* keys, which stay last"""
+    """the log's further keys with the six SYNC_* keys (or, after them, the seven COLORFIT_* keys) in their place: after what is
+    there (DIST_RES, SCALE, the LIGHT_* and SYNC_* keys) and before the ALIGN_* / SHIFT_* keys, which stay last"""
     late = {k: v for k, v in (extra or {}).items() if k.startswith(("ALIGN_", "SHIFT_"))}
     out = {k: v for k, v in (extra or {}).items() if k not in late}
     out.update(keys)
@@ -628,6 +628,95 @@ def shift_extra(result, radius):
             "have another best shift; comparing in place costs %.2f dB of PSNR (the frames are NOT moved)", extra["SHIFT_DY"],
             extra["SHIFT_DX"], ", which is the border of the band: the true shift may lie beyond radius %d" % radius
             if result["edge"] else "", extra["SHIFT_FRAMES_OFF"], extra["SHIFT_PSNR_GAIN"])
+    return extra
+
+
+COLORFIT_WINDOW = 1024   # the frames of one submit of frame_colorfit (the C limit is 32768, and n h w <= 2^31 with tables)
+
+
+def _colorfit_request(colorfit, scale=None, layout=None):
+    """the colorfit argument / config key -> whether the fit is on; a ValueError for anything else"""
+    if not isinstance(colorfit, (bool, np.bool_)):
+        raise ValueError("colorfit must be true or false.")
+    if colorfit and scale is not None:
+        raise ValueError("colorfit and scale do not go together: the fit is taken sample against sample on one grid, and a "
+                         "ladder rung is not fitted at its own size.")
+    if colorfit and layout is not None and len(LAYOUTS[layout][0](16, 16)) not in (1, 3):
+        raise ValueError("colorfit takes one plane or the three planes of a pixel together: %s has %d"
+                         % (layout, len(LAYOUTS[layout][0](16, 16))))
+    return bool(colorfit)
+
+
+def colorfit_model(layout):
+    """the model colorfit.analyse reads a layout as: "bgr" for bgr24, "gray" for one plane, "yuv" otherwise"""
+    return "bgr" if layout == "bgr24" else "gray" if len(LAYOUTS[layout][0](16, 16)) == 1 else "yuv"
+
+
+def frame_colorfit(reference, encoded, layout, height=None, width=None, tables=True, engine=None, device=None,
+                   window=COLORFIT_WINDOW):
+    """Colour registration of two whole clips of one length (Engine.colorfit, include/vqa.h): per frame pair the joint integer
+    moments of the planes of both streams on the luma grid and, with tables, per reference code the count, sum and sum of
+    squares of the encoded samples over the whole clip; and what colorfit.analyse reads off them - the per-plane gain and
+    offset, the best 3 x 3 matrix, the per-code tone curve, the error each would leave and whether a known mishap (a range
+    mix-up, a BT.601 / BT.709 matrix swap) explains the error.  The clip is walked in windows of `window` frames, cut to
+    2^31 // (h w) when tables are on, and the tables are summed in Python integers: any window size gives the same arrays.  The
+    model and depth come from the layout: bgr24 is "bgr", one plane "gray", otherwise "yuv".  -> (records [n] of
+    engine.COLORFIT_DTYPE, tables uint64 [planes, bins, 3] or None, analyse's dict).  Nothing is corrected."""
+    from . import colorfit as CF
+    from .engine import COLORFIT_DTYPE
+    window = int(window)
+    if not 1 <= window <= N.COLORFIT_MAX_FRAMES:
+        raise ValueError("window must be an integer from 1 to %d." % N.COLORFIT_MAX_FRAMES)
+    _colorfit_request(True, None, layout)
+    ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    h, w = _geometry(ref, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    if tables:
+        window = max(1, min(window, N.COLORFIT_TABLE_POSITIONS // (h * w)))
+
+    def count(a):
+        return a.n if isinstance(a, DeviceFrames) else a.shape[0]
+
+    def part(a, lo, hi):
+        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
+
+    n = count(enc)
+    if not n or count(ref) != n:
+        raise ValueError("both clips must hold the same number of frames, at least one")
+    rec = np.zeros(n, COLORFIT_DTYPE)
+    total = None
+    eng = engine if engine is not None else stream.get_engine(device)
+    with stream.pass_lock(eng.device):
+        for a in range(0, n, window):
+            b = min(n, a + window)
+            rec[a:b], tab = eng.colorfit(part(ref, a, b), part(enc, a, b), planes, bool(tables))
+            if tables:
+                words = [int(v) for v in tab.reshape(-1)]
+                total = words if total is None else [x + y for x, y in zip(total, words)]
+    nested = None
+    if tables:   # [planes][bins][3] in Python integers for the analysis; the array for the caller
+        bins = len(total) // (3 * len(planes))
+        nested = [[total[(p * bins + i) * 3:(p * bins + i) * 3 + 3] for i in range(bins)] for p in range(len(planes))]
+    tab = np.array(nested, np.uint64) if tables else None
+    return rec, tab, CF.analyse(rec, layout_depth(layout), colorfit_model(layout), nested)
+
+
+def colorfit_extra(result, depth):
+    """frame_colorfit's (colorfit.analyse's) dict -> the seven top-level keys of the log and the row; a named mishap, or a
+    matrix fit that at least halves the error, is also a warning in the log of this module"""
+    import logging
+    import math
+    from . import colorfit as CF
+    extra = CF.log_keys(result, depth)
+    if result["match"] != "none" or result["psnr_gain"] >= 10.0 * math.log10(2.0):
+        found = ("the mishap '%s' explains it: putting it right would gain %.2f dB of PSNR" % (
+            extra["COLORFIT_MATCH"], extra["COLORFIT_MATCH_PSNR_GAIN"])) if result["match"] != "none" else \
+            "no known mishap explains it"
+        logging.getLogger(__name__).warning(
+            "a code value does not mean the same in both streams: %s; the best matrix and offset would gain %.2f dB (luma gain "
+            "%.4f, offset %+.2f on the 8-bit scale; a per-code curve %.2f dB beyond that); %d frame(s) have another match; "
+            "comparing as given costs that much (the frames are NOT corrected)", found, extra["COLORFIT_PSNR_GAIN"],
+            extra["COLORFIT_GAIN_Y"], extra["COLORFIT_OFFSET_Y"], extra["COLORFIT_TONE_PSNR_GAIN"], extra["COLORFIT_FRAMES_OFF"])
     return extra
 
 
@@ -941,7 +1030,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
                        dist_height=None, dist_width=None, scale=None, align=None, shift=None,
                        shift_margin=None, light=False, light_transfer="pq", light_full_range=False, sync=False,
-                       sync_min_overlap=None, sync_apply=False):
+                       sync_min_overlap=None, sync_apply=False, colorfit=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -1019,6 +1108,15 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     pass, which is logged as a warning; SYNC_APPLIED is 1 only when something was cut.  An ambiguous answer (a static clip) is
     never applied: a warning, SYNC_APPLIED 0, and the streams go on as given.  sync_apply without sync is a ValueError.
     Without sync every file is byte for byte what it was.
+    colorfit=True (default False): after the sync pre-pass - so with sync_apply over the trimmed pair - a pass of its own
+    (frame_colorfit) measures whether a code value means the same in both streams: the joint integer moments of the planes and
+    the per-code transfer tables, from which colorfit.analyse reads the per-plane gain and offset, the best 3 x 3 matrix, the tone
+    curve and whether a known mishap (limited / full range, BT.601 / BT.709 matrix) explains the error.  vmaf_log is then written
+    in any case and gains the top-level keys "COLORFIT_MATCH", "COLORFIT_MATCH_PSNR_GAIN", "COLORFIT_PSNR_GAIN",
+    "COLORFIT_GAIN_Y", "COLORFIT_OFFSET_Y" (on the 8-bit scale), "COLORFIT_TONE_PSNR_GAIN" (plane 0) and "COLORFIT_FRAMES_OFF",
+    after the SYNC_* and before the ALIGN_* / SHIFT_* keys; gains are capped at 100.0.  A named mishap, or a matrix fit worth
+    10 log10(2) dB or more, is also logged as a warning.  The frames are NOT corrected.  colorfit with scale, and a two-plane
+    layout, are a ValueError.  Without colorfit every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -1030,6 +1128,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     search = _shift_request(shift, shift_margin, scale)
     lit = _light_request(light, light_transfer, light_full_range)
     syn = _sync_request(sync, sync_min_overlap, sync_apply)
+    fit = _colorfit_request(colorfit, scale)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -1038,6 +1137,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         raise ValueError("reference and distorted streams must share a pixel layout")
     h, w = _geometry(ref, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
+    _colorfit_request(fit, scale, layout)
     dist_planes = extra = None
     if scaling:
         from .engine import check_scale_planes
@@ -1071,6 +1171,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
             extra = dict(extra or {}, **shift_extra(frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device), search[0]))
         if sync_keys is not None:
             extra = _with_sync_keys(extra, sync_keys)
+        if fit:   # the colour-fit pre-pass over the (trimmed) pair: its keys go after the SYNC_* keys
+            extra = _with_sync_keys(extra, colorfit_extra(frame_colorfit(rs, ds, layout, h, w, device=device)[2], layout_depth(layout)))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
                  batch_size=batch_size, on_quality=wr, device=device)
     finally:
@@ -1125,7 +1227,7 @@ def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scal
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
-    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra or "LIGHT_MAXCLL" in extra or "SYNC_OFFSET" in extra)):   # (a pre-pass always has something to say)
+    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra or "LIGHT_MAXCLL" in extra or "SYNC_OFFSET" in extra or "COLORFIT_MATCH" in extra)):   # (a pre-pass always has something to say)
         _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
                            extra=extra)
     return q, series
@@ -1157,6 +1259,8 @@ def _check_mode_keys(config):
     _shift_request(config.get("shift"), config.get("shift_margin"), config.get("scale"))
     _light_config(config)
     _sync_config(config)
+    check_switch("colorfit", config)
+    _colorfit_request(config.get("colorfit", False), config.get("scale"))
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -1261,7 +1365,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         SYNC_APPLIED before the ALIGN_* / SHIFT_* columns; with sync_apply and an answer that is not ambiguous the input is
         sliced by the reference side's trim and BOTH the encoded BGR stream and the encoded pair stream by the distorted
         side's, so both halves of the pass see the same frames; an ambiguous answer is a warning and is never applied;
-        sync_apply without sync is a ValueError.
+        sync_apply without sync is a ValueError,
+        colorfit (false default | true): a pre-pass of its own over the quality pair (frame_colorfit), after the sync pre-pass
+        and so over the trimmed pair, measures whether a code value means the same in both streams, and the row gains
+        COLORFIT_MATCH, COLORFIT_MATCH_PSNR_GAIN, COLORFIT_PSNR_GAIN, COLORFIT_GAIN_Y, COLORFIT_OFFSET_Y,
+        COLORFIT_TONE_PSNR_GAIN and COLORFIT_FRAMES_OFF after the SYNC_* and before the ALIGN_* / SHIFT_* columns; a named
+        mishap or a matrix fit worth 10 log10(2) dB or more is also a warning; the frames are not corrected; with scale, and
+        for a two-plane pixfmt, it is a ValueError.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1281,6 +1391,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     search = _shift_request(config.get("shift"), config.get("shift_margin"), scale)
     lit = _light_config(config)
     syn = _sync_config(config)
+    fit = _colorfit_request(config.get("colorfit", False), scale)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -1358,6 +1469,9 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                                 search[1], device=device), search[0]))
         if sync_keys is not None:
             extra = _with_sync_keys(extra, sync_keys)
+        if fit:   # the colour-fit pre-pass over the (trimmed) quality pair: its keys go after the SYNC_* keys
+            extra = _with_sync_keys(extra, colorfit_extra(frame_colorfit(ref, enc if qdist is None else qdist, layout, h, w,
+                                                                         device=device)[2], layout_depth(layout)))
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
@@ -1379,7 +1493,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
-        if radius is not None or search is not None or lit is not None or syn is not None:   # (extract_metrics_from_logs read them off the log: they go last)
+        if radius is not None or search is not None or lit is not None or syn is not None or fit:   # (extract_metrics_from_logs read them off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
@@ -1420,6 +1534,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         from .sync import SYNC_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in SYNC_KEYS):   # a sync pre-pass: before the two below
             metrics.update((k, doc_top[k]) for k in SYNC_KEYS)
+        from .colorfit import COLORFIT_KEYS
+        if isinstance(doc_top, dict) and all(k in doc_top for k in COLORFIT_KEYS):   # a colour-fit pre-pass: after the sync keys
+            metrics.update((k, doc_top[k]) for k in COLORFIT_KEYS)
         from .align import ALIGN_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in ALIGN_KEYS):   # an alignment pre-pass: the row's last columns
             metrics.update((k, doc_top[k]) for k in ALIGN_KEYS)
@@ -1448,7 +1565,7 @@ def validate_config(config):
         raise ValueError("Frame interval must be a positive integer.")
     if not isinstance(config.get("num_workers", (os.cpu_count() or 2) // 2), int):
         raise ValueError("num_workers must be an integer.")
-    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align, shift, light and sync requests and every config key of FEATURES (the
+    # this build's keys: MODE_KEYS, device, batch_size, height / width, the scale, align, shift, light, sync and colorfit requests and every config key of FEATURES (the
     # kinds' switches and their parameters); and that a vmaf_model_path names a readable file
     _check_mode_keys(config)
 
