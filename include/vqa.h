@@ -1710,6 +1710,48 @@ VQA_API int vqa_scale_wait(vqa_ctx *ctx);
  * VQA_ERR_UNSUPPORTED.  in == out gives the formula's tables, which are the identity.                                         */
 VQA_API int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int32_t *count, int *ksize);
 
+/* ---- Conform: the registration that align, sync, shift and colorfit FIND, applied on the device ----
+ * One input stream, one output stream: out[j][p][y][x] is a function of in[index[j]][p][y0_p + y][x0_p + x].  A pair is conformed
+ * by two submits.  Everything is integer arithmetic; where this text differs from a tool's detail, this text is what is built.
+ * frames: n_in frames described by src_planes, one to four planes of one depth (8, or 9 .. 16), any offset, row stride and pixel
+ *   step (packed bgr24 is three planes); host, pinned or device memory, what vqa_scale_submit takes on its input side.
+ * dst_planes: the same plane count and depth, sizes (oh_p, ow_p), strides and pads of their own: plane 0 at least 16 x 16, the
+ *   others at least 8 x 8 (the chroma of a 16 x 16 4:2:0 frame), h w <= 2^28: VQA_ERR_UNSUPPORTED beyond.
+ * origin: NULL (all zero) or [n_planes][2] = (y0_p, x0_p), the window's corner in source plane p; y0_p + oh_p <= h_p and
+ *   x0_p + ow_p <= w_p, else VQA_ERR_INVALID.
+ * index: NULL (identity, n_out is taken as n_in) or n_out source frames, 0 <= index[j] < n_in, in any order, repeats allowed: a
+ *   constant offset, a drop, a repeat, or vqa_align's path.  n_out <= 32768, VQA_ERR_UNSUPPORTED beyond.
+ * lut: NULL or [n_planes][2^depth] entries of the sample type, each at most peak = 2^depth - 1 (else VQA_ERR_INVALID), applied
+ *   first: s_p = lut[p][min(sample, peak)] (a sample above the peak is no code of the depth; it reads the peak's entry).
+ * matrix: NULL or int64 [3][4] in 2^-16 fixed point, three planes only; |M[k][i]| <= 2^20 for i < 3, |M[k][3]| <= 2^33, else
+ *   VQA_ERR_INVALID.  The source planes follow the joint rule of vqa_ciede_submit (planes 1 and 2 alike; the size of plane 0 or
+ *   its ceil-half per axis), sy, sx the chroma shifts that gives.  Stated in SOURCE coordinates:
+ *     plane 0 at (Y, X):   t_0 = clip((M00 s_0(Y, X) + M01 s_1(cy, cx) + M02 s_2(cy, cx) + M03 + 2^15) >> 16, 0, peak) with
+ *       cy = min(Y >> sy, h_c - 1), cx = min(X >> sx, w_c - 1): chroma replicated, the convention of colorfit, ciede and itp;
+ *     planes k = 1, 2 at (Cy, Cx): t_k = clip((Mk0 Ybar + Mk1 s_1(Cy, Cx) + Mk2 s_2(Cy, Cx) + Mk3 + 2^15) >> 16, 0, peak), Ybar
+ *       the rounded mean (sum + cnt / 2) / cnt of the luma samples s_0 of the source cell rows (Cy << sy) .., columns
+ *       (Cx << sx) .. that exist, so cnt is 1, 2 or 4; in 4:4:4 and bgr24 the cell is one sample.
+ *   >> is an arithmetic shift on 64-bit values.  Without a matrix t_p = s_p.
+ * Output: out[j][p][y][x] = t_p at source sample (y0_p + y, x0_p + x) of frame index[j].  The bytes of dst that no destination
+ *   sample covers (row and frame padding) are never written.  dst must be device memory of the ctx's device and must not
+ *   overlap the source frames (VQA_ERR_INVALID).
+ * A conform batch is a batch of its own (no result words) with the resampler's slot semantics: VQA_ERR_STATE while one is
+ *   pending, in flight next to every other kind; every submit of any kind on the SAME ctx that follows reads dst after it has
+ *   been written - the stream orders them; vqa_conform_wait is needed only before another ctx or the host reads dst.  The
+ *   caller's origin, index, lut and matrix are free when the submit returns.
+ * No atomics: the same input gives the same bytes in any batch, from any memory.  It takes no kernel id (like
+ *   vqa_colorfit_submit): an added entry point, not a layout change, VQA_ABI_VERSION stays.
+ * Kernels (k_conform.hip): k_conform_copy - a lane a 16-byte granule of the destination, the source loaded as aligned 16-byte
+ *   words and realigned in registers, the tables in LDS up to 12 bits; k_conform_gather - a lane a sample, for a pixel step that
+ *   is neither contiguous nor interleaved alike on both sides; k_conform_matrix - a lane a 2 x 4 patch of source cells.
+ * Not built: interpolation (sub-pixel shifts, chroma of an odd shift on a subsampled axis); conversion between layouts or
+ *   depths; a matrix for other than three planes.                                                                            */
+VQA_API int vqa_conform_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n_in, int64_t frame_stride,
+                               const vqa_plane_desc *src_planes, uint8_t *dst, int64_t dst_frame_stride,
+                               const vqa_plane_desc *dst_planes, int n_planes, const int32_t *origin, const int32_t *index,
+                               int n_out, const void *lut, const int64_t *matrix);
+VQA_API int vqa_conform_wait(vqa_ctx *ctx);
+
 /* ---- Temporal alignment: is the distorted stream the same frames as the reference, in the same places? ----
  * Every full-reference kind above compares reference frame i with distorted frame i and trusts the caller that they belong
  * together.  This kind measures that: the squared error between distorted frame j and reference frame j + offset + k for every
@@ -2002,7 +2044,7 @@ VQA_API int vqa_sig_cross_wait(vqa_ctx *ctx, uint64_t *diag, int64_t n_diag, uin
  *   2^46); equal adjacent bins of a thread, and a wave whose entries all name one bin, are joined before they reach LDS, so a
  *   chroma sample enters once with its weight and flat content does not serialise.  The kernel has no profiling id
  *   (enum vqa_kernel_id is closed): time it from outside.
- * Not built: applying the fit; clipping-aware fits; per-frame tables; chroma interpolation other than replication; a fit after
+ * Not built: applying the fit (vqa_conform_submit does); clipping-aware fits; per-frame tables; chroma interpolation other than replication; a fit after
  *   vqa_scale_submit; running inside another kind's pass.
  * out of vqa_colorfit_wait: n entries (n_entries = n); tables: n_table_words = n_planes * bins * 3 words, or NULL.            */
 #define VQA_COLORFIT_MAX_FRAMES 32768

@@ -156,6 +156,9 @@ COLORFIT_MIN_DIM = 16         # vqa_colorfit_submit: the luma grid's limit (the 
 COLORFIT_MAX_FRAMES = 32768   # vqa_colorfit_submit: the frames of one submit
 COLORFIT_MAX_BINS = 1024      # the bins of one plane's transfer table: 1 << min(depth, 10)
 COLORFIT_TABLE_POSITIONS = 1 << 31   # n h w of a submit with tables
+CONFORM_MIN_DIM = 16          # vqa_conform_submit: plane 0 of the destination (the other planes: 8, the chroma of 4:2:0)
+CONFORM_MAX_OUT = 32768       # vqa_conform_submit: the output frames of one submit
+CONFORM_MAX_COEF, CONFORM_MAX_BIAS = 1 << 20, 1 << 33   # |M[k][i]|, i < 3, and |M[k][3]| of its matrix (2^-16 fixed point)
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -421,6 +424,10 @@ SIGNATURES = {
     "vqa_colorfit_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_int,
                                       C.c_int]),
     "vqa_colorfit_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaColorfitMetrics), C.c_int, C.POINTER(C.c_uint64), C.c_int64]),
+    "vqa_conform_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_void_p, C.c_int64,
+                                     C.POINTER(VqaPlaneDesc), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_int64)]),
+    "vqa_conform_wait": (C.c_int, [C.c_void_p]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

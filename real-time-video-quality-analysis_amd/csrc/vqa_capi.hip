@@ -83,6 +83,8 @@ enum batch_kind {
                       // the batch in flight are named members of the ctx (sigx_*)
     KIND_COLORFIT,    // COLORFIT_WORDS per frame, then (want_tables) the table words of the submit; their count is a named member
                       // of the ctx (colorfit_table_words)
+    KIND_CONFORM,     // no result words: the batch writes the caller's dst; work: host frames staged (0), the frame index and the
+                      // tables on the device (1); the pinned copy holds what (1) is filled from
     KIND_COUNT
 };
 
@@ -3121,6 +3123,147 @@ int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int
     if (!scale_ratio_ok(in, out)) return VQA_ERR_UNSUPPORTED;
     *ksize = scale_ksize(filter, in, out);
     if (given) scale_build_axis(filter, in, out, k, xmin, count);
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Conform: a registered copy of one stream - window, frame gather, table, matrix - into the caller's device memory.  A batch of
+// its own with no result words and the resampler's slot semantics.  The frame index and the tables reach the device through the
+// slot's pinned copy, so the caller's arrays are free when the submit returns.
+static int conform_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n_in, int64_t fs, const vqa_plane_desc *planes,
+                               uint8_t *dst, int64_t dst_fs, const vqa_plane_desc *dplanes, int n_planes, const int32_t *origin,
+                               const int32_t *index, int n_out, const void *lut, const int64_t *matrix, bool &touched)
+{
+    if (bad_batch_args(c, frames, dst, mem_kind, n_in, planes, n_planes) || !dplanes) return VQA_ERR_INVALID;
+    if (!index) n_out = n_in;
+    if (n_out <= 0 || (matrix && n_planes != 3)) return VQA_ERR_INVALID;
+    if (n_out > CONFORM_MAX_OUT) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_CONFORM];
+    plane_batch B, D;
+    auto src_limits = [](const vqa_plane_desc &d) { return side_and_area_limits(d, 1); };
+    auto dst_limits = [=](const vqa_plane_desc &d) { return side_and_area_limits(d, &d == dplanes ? CONFORM_MIN_DIM : CONFORM_MIN_DIM / 2); };
+    int rc = check_batch(s, n_in, fs, fs, planes, n_planes, B, src_limits, matrix ? JOINT_YUV : JOINT_NONE);
+    if (rc) return rc;
+    if ((rc = check_planes(dplanes, n_planes, D, dst_limits))) return rc;
+    if (D.depth != B.depth) return VQA_ERR_UNSUPPORTED;
+    if (n_out > 1 && dst_fs < D.span) return VQA_ERR_INVALID;
+    const int depth = B.depth, bps = B.bps, bins = 1 << depth, peak = bins - 1;
+    for (int p = 0; p < n_planes; p++) {
+        const int64_t y0 = origin ? origin[2 * p] : 0, x0 = origin ? origin[2 * p + 1] : 0;
+        if (y0 < 0 || x0 < 0 || y0 + dplanes[p].height > planes[p].height || x0 + dplanes[p].width > planes[p].width)
+            return VQA_ERR_INVALID;
+    }
+    if (index)
+        for (int j = 0; j < n_out; j++)
+            if (index[j] < 0 || index[j] >= n_in) return VQA_ERR_INVALID;
+    if (lut)
+        for (size_t i = 0; i < (size_t)n_planes * bins; i++)
+            if ((bps == 2 ? (int)((const uint16_t *)lut)[i] : (int)((const uint8_t *)lut)[i]) > peak) return VQA_ERR_INVALID;
+    if (matrix)
+        for (int k = 0; k < 3; k++)
+            for (int i = 0; i < 4; i++) {
+                const int64_t v = matrix[4 * k + i], lim = i < 3 ? CONFORM_MAX_COEF : CONFORM_MAX_BIAS;
+                if (v > lim || v < -lim) return VQA_ERR_INVALID;
+            }
+    const int64_t dst_bytes = (int64_t)(n_out - 1) * dst_fs + D.span, src_bytes = (int64_t)(n_in - 1) * fs + B.span;
+    if (!byte_is_on_device(c, dst) || !byte_is_on_device(c, dst + (dst_bytes - 1))) return VQA_ERR_INVALID;
+    if (mem_kind == VQA_MEM_DEVICE && (uintptr_t)frames < (uintptr_t)dst + (uint64_t)dst_bytes &&
+        (uintptr_t)dst < (uintptr_t)frames + (uint64_t)src_bytes)
+        return VQA_ERR_INVALID;
+    if ((rc = stage_batch(c, touched, mem_kind, n_in, B.span, {&frames, fs, &s.work[0]}))) return rc;
+    hipStream_t st = c->stream;
+
+    conform_job job;
+    memset(&job, 0, sizeof job);
+    job.src = frames; job.dst = dst;
+    job.src_fs = fs; job.dst_fs = dst_fs;
+    job.peak = peak;
+    // the index and the tables: the caller's -> the pinned copy -> the device, the tables 16-byte aligned behind the index
+    const size_t index_bytes = index ? ((size_t)n_out * sizeof(int32_t) + 15) / 16 * 16 : 0;
+    const size_t lut_bytes = lut ? (size_t)n_planes * bins * bps : 0;
+    if (index_bytes + lut_bytes) {
+        if ((rc = ensure(c, s.work[1], index_bytes + lut_bytes))) return rc;
+        if ((rc = ensure_pinned(c, s.host, index_bytes + lut_bytes))) return rc;
+        if (index) memcpy(s.host.p, index, (size_t)n_out * sizeof(int32_t));
+        if (lut) memcpy((uint8_t *)s.host.p + index_bytes, lut, lut_bytes);
+        HIPCHK(c, hipMemcpyAsync(s.work[1].p, s.host.p, index_bytes + lut_bytes, hipMemcpyHostToDevice, st));
+        if (index) job.index = (const int32_t *)s.work[1].p;
+        if (lut) job.lut = (const uint8_t *)s.work[1].p + index_bytes;
+    }
+    auto fill = [&](int p, conform_plane &P) {
+        const vqa_plane_desc &a = planes[p], &b = dplanes[p];
+        P.src_off = a.offset; P.dst_off = b.offset;
+        P.src_rs = a.row_stride; P.dst_rs = b.row_stride;
+        P.src_step = a.pixel_step; P.dst_step = b.pixel_step;
+        P.w = b.width; P.h = b.height;
+        P.y0 = origin ? origin[2 * p] : 0; P.x0 = origin ? origin[2 * p + 1] : 0;
+        P.inter = 1; P.lut0 = p;
+    };
+    if (matrix) {
+        for (int k = 0; k < 3; k++)
+            for (int i = 0; i < 4; i++) job.m[k][i] = matrix[4 * k + i];
+        for (int p = 0; p < 3; p++) fill(p, job.plane[p]);
+        launch_conform_matrix(st, job, planes[0].height, planes[0].width, planes[1].height, planes[1].width, n_out, depth);
+    } else {
+        // three launches at most: the planes a granule copy can take (a contiguous pixel step on both sides; `k` planes that
+        // interleave on both sides with one window go as one plane of k times the samples), then the others by the gather.
+        // 16-bit samples at odd addresses would straddle a granule's dwords: the gather takes them.
+        const bool odd = bps == 2 && (((uintptr_t)frames | (uintptr_t)dst | (uintptr_t)fs | (uintptr_t)dst_fs) & 1);
+        conform_job fast = job, slow = job;
+        int n_fast = 0, n_slow = 0;
+        bool done[4] = {false, false, false, false};
+        for (int p = 0; p < n_planes; p++) {
+            if (done[p]) continue;
+            conform_plane P;
+            fill(p, P);
+            done[p] = true;
+            const int k = P.src_step / bps;
+            if (!odd && P.src_step == P.dst_step && P.src_step == bps) {
+                fast.plane[n_fast++] = P;
+                continue;
+            }
+            // planes p .. p + k - 1 interleave: the same geometry and window, offsets one sample apart on both sides
+            bool inter = !odd && P.src_step == P.dst_step && P.src_step == k * bps && k >= 2 && k <= 3 && p + k <= n_planes;
+            for (int q = 1; inter && q < k; q++) {
+                conform_plane Q;
+                fill(p + q, Q);
+                inter = !done[p + q] && Q.src_off == P.src_off + (int64_t)q * bps && Q.dst_off == P.dst_off + (int64_t)q * bps &&
+                        Q.src_rs == P.src_rs && Q.dst_rs == P.dst_rs && Q.src_step == P.src_step && Q.dst_step == P.dst_step &&
+                        Q.w == P.w && Q.h == P.h && Q.y0 == P.y0 && Q.x0 == P.x0;
+            }
+            if (inter) {
+                for (int q = 1; q < k; q++) done[p + q] = true;
+                P.inter = k; P.w *= k; P.x0 *= k;
+                fast.plane[n_fast++] = P;
+            } else {
+                slow.plane[n_slow++] = P;
+            }
+        }
+        launch_conform_copy(st, fast, n_out, n_fast, depth, false);
+        launch_conform_copy(st, slow, n_out, n_slow, depth, true);
+    }
+    HIPCHK(c, hipGetLastError());
+    record_batch(s, n_out, dplanes, n_planes, depth);
+    return VQA_OK;
+}
+
+int vqa_conform_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n_in, int64_t frame_stride,
+                       const vqa_plane_desc *src_planes, uint8_t *dst, int64_t dst_frame_stride, const vqa_plane_desc *dst_planes,
+                       int n_planes, const int32_t *origin, const int32_t *index, int n_out, const void *lut, const int64_t *matrix)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return conform_submit_body(c, frames, mem_kind, n_in, frame_stride, src_planes, dst, dst_frame_stride, dst_planes, n_planes,
+                                   origin, index, n_out, lut, matrix, touched);
+    });
+}
+
+int vqa_conform_wait(vqa_ctx *c)
+{
+    if (!c) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_CONFORM];
+    if (!s.entries) return VQA_ERR_STATE;
+    if (int rc = wait_synced(c)) return rc;
+    s.entries = 0;
     return VQA_OK;
 }
 

@@ -646,6 +646,42 @@ struct scale_job {
 // n frames of `count` planes (the job's offsets): grid (tiles, n, count)
 void launch_scale(hipStream_t st, const scale_job &job, int n, int count, int depth);
 
+// Conform (vqa_conform_submit): k_conform.hip
+constexpr int CONFORM_MIN_DIM = 16;         // the limit of plane 0 of the destination (the other planes: 8, the chroma of 4:2:0)
+constexpr int CONFORM_MAX_OUT = 32768;      // output frames of one submit (they ride in gridDim.y)
+constexpr int CONFORM_LDS_DEPTH = 12;       // up to this depth the tables sit in LDS: 2^12 samples a plane
+constexpr int CONFORM_LDS_SAMPLES = 1 << CONFORM_LDS_DEPTH;
+constexpr int64_t CONFORM_MAX_COEF = 1ll << 20, CONFORM_MAX_BIAS = 1ll << 33;   // |M[k][i]|, i < 3; |M[k][3]|
+// one plane of a job: the window's corner in the source plane, the window's size, both sides' addressing in bytes.  inter > 1:
+// `inter` planes that interleave on both sides, taken as one plane of inter times the samples (w and x0 count those); lut0: the
+// table of the plane (of the first of the interleaved planes)
+struct conform_plane {
+    int64_t src_off, dst_off, src_rs, dst_rs;
+    int src_step, dst_step;
+    int w, h, y0, x0;
+    int inter, lut0;
+};
+struct conform_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t src_fs, dst_fs;
+    const int32_t *index;              // on the device; null: output frame j is source frame j
+    const void *lut;                   // on the device: [planes][2^depth] of the sample type; null: none
+    long long m[3][4];                 // the matrix path only
+    conform_plane plane[4];
+    int peak;                          // 2^depth - 1
+};
+// the source cells the matrix path walks (filled by launch_conform_matrix)
+struct conform_cells {
+    int sh, sw, ch, cw;                // the source's luma and chroma sizes
+    int sx, sy;                        // the chroma shifts
+    int cy0, cy1, X0, patches, tiles_x;
+};
+// n_out frames of the job's first `count` planes: window, gather and table; gather: a lane a sample (any pixel step)
+void launch_conform_copy(hipStream_t st, const conform_job &job, int n_out, int count, int depth, bool gather);
+// n_out frames of three planes taken together, the job's m applied after its table; sh x sw, ch x cw: the SOURCE planes' sizes
+void launch_conform_matrix(hipStream_t st, const conform_job &job, int sh, int sw, int ch, int cw, int n_out, int depth);
+
 // Temporal alignment (vqa_align_submit): k_align.hip
 constexpr int ALIGN_MAX_DIST = 32768, ALIGN_MAX_REF = 32768 + 64;   // frames of one submit
 // One launch for the whole band of the whole submit: adds C[j][i] = sum X_d,j X_r,i into cross[j * (2 radius + 1) + c] for the pairs

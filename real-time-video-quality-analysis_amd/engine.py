@@ -249,6 +249,57 @@ def check_scale_planes(planes, out_planes):
                                  % (N.SCALE_MAX_DOWN, N.SCALE_MAX_UP, n_in, n_out))
 
 
+def check_conform_args(planes, out_planes, origin=None, index=None, lut=None, matrix=None):
+    """vqa_conform_submit's rules for its lists and arrays, as a ValueError before anything is uploaded -> (origin int32
+    [n_planes, 2] or None, index int32 [n_out] or None, lut [n_planes, 2^depth] of the sample type or None, matrix int64 [3, 4]
+    or None), each contiguous.  Needs no GPU."""
+    if not 1 <= len(planes) <= 4 or len(planes) != len(out_planes):
+        raise ValueError("conform needs one to four planes and as many on both sides (got %d and %d)" % (len(planes), len(out_planes)))
+    depth = planes_depth(planes)
+    if depth != planes_depth(out_planes):
+        raise ValueError("conform keeps the sample depth (got %d and %d bits): converting depths is not built"
+                         % (depth, planes_depth(out_planes)))
+    for i, q in enumerate(out_planes):
+        w, h, least = int(q[0]), int(q[1]), N.CONFORM_MIN_DIM if i == 0 else N.CONFORM_MIN_DIM // 2
+        if w < least or h < least or w * h > N.SCALE_MAX_SAMPLES:
+            raise ValueError("conform writes planes of at least %d x %d and at most 2^28 samples (plane %d: %dx%d)"
+                             % (least, least, i, w, h))
+    if origin is not None:
+        origin = np.ascontiguousarray(np.asarray(origin, np.int64).reshape(-1, 2))
+        if origin.shape[0] != len(planes):
+            raise ValueError("origin needs one (y0, x0) per plane")
+    for i, (p, q) in enumerate(zip(planes, out_planes)):
+        y0, x0 = (int(origin[i, 0]), int(origin[i, 1])) if origin is not None else (0, 0)
+        if y0 < 0 or x0 < 0 or y0 + int(q[1]) > int(p[1]) or x0 + int(q[0]) > int(p[0]):
+            raise ValueError("the window of plane %d (%dx%d at y0 %d, x0 %d) leaves its source plane (%dx%d)"
+                             % (i, int(q[0]), int(q[1]), y0, x0, int(p[0]), int(p[1])))
+    if origin is not None:
+        origin = origin.astype(np.int32)
+    if index is not None:
+        index = np.asarray(index)
+        if index.ndim != 1 or index.size == 0 or not np.issubdtype(index.dtype, np.integer):
+            raise ValueError("index must be a non-empty one-dimensional integer array")
+        index = np.ascontiguousarray(index, np.int32)
+    sample = np.uint16 if depth > 8 else np.uint8
+    if lut is not None:
+        lut = np.asarray(lut)
+        if not np.issubdtype(lut.dtype, np.integer) or lut.shape != (len(planes), 1 << depth):
+            raise ValueError("lut must be an integer array [%d, %d] (got %s %s)" % (len(planes), 1 << depth, lut.dtype, lut.shape))
+        if int(lut.min()) < 0 or int(lut.max()) > (1 << depth) - 1:
+            raise ValueError("lut entries must lie in 0 .. %d" % ((1 << depth) - 1))
+        lut = np.ascontiguousarray(lut, sample)
+    if matrix is not None:
+        if len(planes) != 3:
+            raise ValueError("a matrix needs three planes (got %d)" % len(planes))
+        matrix = np.asarray(matrix)
+        if matrix.shape != (3, 4) or not np.issubdtype(matrix.dtype, np.integer):
+            raise ValueError("matrix must be an integer [3, 4] array in 2^-16 fixed point")
+        matrix = np.ascontiguousarray(matrix, np.int64)
+        if int(np.abs(matrix[:, :3]).max()) > N.CONFORM_MAX_COEF or int(np.abs(matrix[:, 3]).max()) > N.CONFORM_MAX_BIAS:
+            raise ValueError("matrix coefficients are bounded by 2^20 and its offsets by 2^33 (2^-16 fixed point)")
+    return origin, index, lut, matrix
+
+
 def scale_tables(filter, n_in, n_out):
     """vqa_scale_tables: one axis' tables of the resampler as the library builds them on the host (no GPU needed) ->
     (k int32 [n_out, ksize], xmin int32 [n_out], count int32 [n_out])"""
@@ -469,14 +520,15 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf", "_pending_cm"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
                      "_pending_z": self.sigstats_wait, "_pending_k": self.scale_wait,
                      "_pending_l": self.align_wait, "_pending_j": self.shift_wait,
                      "_pending_o": self.light_wait, "_pending_sg": self.signature_wait,
-                     "_pending_sx": self.sig_cross_wait, "_pending_cf": self.colorfit_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_sx": self.sig_cross_wait, "_pending_cf": self.colorfit_wait,
+                     "_pending_cm": self.conform_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1225,6 +1277,72 @@ class Engine:
         """scale_submit and scale_wait -> the DeviceFrames of the scaled stream."""
         res = self.scale_submit(frames, planes, out_planes, filter, out, frame_bytes, out_frame_bytes)
         self.scale_wait()
+        return res
+
+    # ---- conform: the found registration, applied -------------------------------------------
+    def conform_submit(self, frames, planes, out_planes, origin=None, index=None, lut=None, matrix=None, out=None,
+                       frame_bytes=None, out_frame_bytes=None):
+        """A registered copy of n_in frames of ONE stream on the device (vqa_conform_submit): out[j][p][y][x] is a function of
+        in[index[j]][p][y0_p + y][x0_p + x].  frames: an array / DeviceFrames as scale_submit takes them (a sample type that
+        does not match the depth is a ValueError, never a cast).  out_planes: the windows' sizes, strides and pads.  origin:
+        None or one (y0, x0) per plane.  index: None (identity) or the source frame of every output frame.  lut: None or
+        [n_planes, 2^depth] of the sample type, applied first.  matrix: None or int64 [3, 4] in 2^-16 fixed point (three
+        planes).  out / out_frame_bytes: as for scale_submit.  -> the DeviceFrames of the conformed stream, which every submit
+        of THIS engine accepts with out_planes at once; conform_wait is needed only before another engine or the host reads
+        them.  A batch of its own, like scale_submit."""
+        args = check_conform_args(planes, out_planes, origin, index, lut, matrix)
+        origin_a, index_a, lut_a, matrix_a = args
+        fp, kind, n_in, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
+        if index_a is not None and index_a.size and (int(index_a.min()) < 0 or int(index_a.max()) >= n_in):
+            raise ValueError("index must name source frames 0 .. %d" % (n_in - 1))
+        n = n_in if index_a is None else int(index_a.size)
+        if not 1 <= n <= N.CONFORM_MAX_OUT:
+            raise ValueError("a conform submit writes 1 .. %d frames (got %d)" % (N.CONFORM_MAX_OUT, n))
+        itemsize = 2 if planes_depth(out_planes) > 8 else 1
+        span = planes_span(out_planes)
+        if out is None:
+            ofs = int(out_frame_bytes) if out_frame_bytes else span
+            if ofs < span:
+                raise ValueError("out_frame_bytes (%d) is smaller than a frame of out_planes (%d)" % (ofs, span))
+            buf = DeviceBuffer(self, n * ofs)
+            out = DeviceFrames(buf.ptr, n, 1, ofs // itemsize, frame_stride=ofs, owner=buf, channels=1, itemsize=itemsize)
+        else:
+            if not isinstance(out, DeviceFrames):
+                raise TypeError("out must be DeviceFrames (device memory)")
+            if out.itemsize != itemsize:
+                raise ValueError("%d-bit planes need an out of %s samples (got DeviceFrames of itemsize %d)"
+                                 % (planes_depth(out_planes), "uint16" if itemsize == 2 else "uint8", out.itemsize))
+            if out.n < n:
+                raise ValueError("out holds %d frames, the batch has %d" % (out.n, n))
+            ofs = int(out_frame_bytes) if out_frame_bytes else out.frame_stride
+            if ofs < span:
+                raise ValueError("a frame of out (%d bytes) is smaller than a frame of out_planes (%d)" % (ofs, span))
+            if out.n != n or ofs != out.frame_stride:
+                out = DeviceFrames(out.ptr, n, out.h, out.w, ofs, out.row_stride, owner=out, channels=out.channels,
+                                   itemsize=itemsize)
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        st = self.lib.vqa_conform_submit(
+            self.ctx, fp, kind, n_in, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes), len(planes),
+            origin_a.ctypes.data_as(i32) if origin_a is not None else None,
+            index_a.ctypes.data_as(i32) if index_a is not None else None, n,
+            lut_a.ctypes.data if lut_a is not None else None,
+            matrix_a.ctypes.data_as(i64) if matrix_a is not None else None)
+        N.check(st, "vqa_conform_submit", self.ctx)
+        self._pending_cm = (n, (keep, out))
+        return out
+
+    def conform_wait(self):
+        """Wait for the pending conform batch: the conformed frames are complete (another engine, or a copy to the host, may
+        read them)."""
+        st = self.lib.vqa_conform_wait(self.ctx)
+        self._pending_cm = None
+        N.check(st, "vqa_conform_wait", self.ctx)
+
+    def conform(self, frames, planes, out_planes, origin=None, index=None, lut=None, matrix=None, out=None, frame_bytes=None,
+                out_frame_bytes=None):
+        """conform_submit and conform_wait -> the DeviceFrames of the conformed stream."""
+        res = self.conform_submit(frames, planes, out_planes, origin, index, lut, matrix, out, frame_bytes, out_frame_bytes)
+        self.conform_wait()
         return res
 
     # ---- temporal alignment ------------------------------------------------------------

@@ -36,7 +36,7 @@ from . import _native as N
 from . import tails
 from .engine import (ADM_DTYPE, ARTIFACTS_DTYPE, BRISQUE_DTYPE, CAMBI_DTYPE, CIEDE_DTYPE, FSIM_DTYPE, GMSD_DTYPE, HAARPSI_DTYPE,
                      ITP_DTYPE, MDSI_DTYPE, MOTION_DTYPE, PSNR_HVS_DTYPE, PU21_DTYPE, SIGSTATS_DTYPE, SITI_DTYPE, VCA_DTYPE, VIF_DTYPE,
-                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_scale_planes, check_vca_planes, check_xpsnr_planes,
+                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_conform_args, check_scale_planes, check_vca_planes, check_xpsnr_planes,
                      planes_depth, planes_span, scale_filter, vca_grid)
 from .pooling import shard_range
 
@@ -509,11 +509,13 @@ def records_by_kind(q, quality):
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
+    conform = conform_args = None   # the plan a conformed pass applies and its checked arrays (set by __init__ when given)
+
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
                  haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
                  itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False,
-                 sigstats=False, sigstats_black=None, sigstats_crop=None, dist_planes=None, scale=None):
+                 sigstats=False, sigstats_black=None, sigstats_crop=None, dist_planes=None, scale=None, conform=None):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         Every other switch turns on one plane-batch kind (PLANE_KINDS) and is False, True or "only":
         True    every chunk also goes through the kind's kernels (Engine.<kind>_submit) from the SAME upload - the chunk was
@@ -564,7 +566,15 @@ class Quality:
                 figure).  Both or neither; the same plane count and depth, ratios within 1/4 .. 8 per axis (ValueError).
                 Allowed where the quality half's distorted stream is a feed of its own: a quality-only pass, or `qdist` next to
                 the BGR stream of the complexity half, which goes on reading that stream at its native size.  Nothing is
-                ever scaled without the two: streams whose sizes merely differ stay an error."""
+                ever scaled without the two: streams whose sizes merely differ stay an error.
+        conform: None, or a plan of conform.plan - the registration that sync, align, shift and colorfit found.  Every chunk of
+                BOTH streams is uploaded as given, at the size of the plan's "planes", and conformed on the engine that
+                measures it (Engine.conform_submit: the window of the found shift, the colour map on the distorted stream)
+                into lane buffers of the conformed frame size; `planes` must be the plan's "out_planes", so every kind that
+                reads ref, dist or the pair sees the registered streams, the halo frame of the reference included.  Time is
+                not the pass's business: a constant offset is applied by the feeds the caller hands over (slices of the
+                streams), a per-frame path is Engine.conform's.  Allowed where scale is (the quality half's distorted stream
+                is a feed of its own) and never together with it."""
         given = dict(locals())   # the keyword arguments by name, for the table
         if (dist_planes is None) != (scale is None):
             raise ValueError("dist_planes and scale go together: the distorted stream's own planes AND the filter that brings "
@@ -574,6 +584,16 @@ class Quality:
             scale_filter(scale)
             check_scale_planes(dist_planes, planes)
         self.dist_planes, self.scale = dist_planes, scale
+        if conform is not None:
+            if scale is not None:
+                raise ValueError("conform and scale do not go together: a ladder rung is not registered at its own size")
+            if [tuple(q) for q in conform["out_planes"]] != [tuple(q) for q in planes]:
+                raise ValueError("a conformed pass measures the plan's out_planes: give them as planes")
+            # the arrays of both submits, checked and converted once (the index stays out: time is the feeds' business)
+            self.conform = conform
+            self.conform_args = {side: check_conform_args(conform["planes"], planes, conform[side]["origin"], None,
+                                                          conform[side]["lut"], conform[side]["matrix"])
+                                 for side in ("ref", "dist")}
         if scales and ssim_mode != N.SSIM_MS:
             raise ValueError("per-scale means exist in the multi-scale mode only")
         for kind in PLANE_KINDS:
@@ -690,6 +710,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
         qdist = None
     split = qdist is not None
     qd = qdist if split else dist       # the distorted stream of the quality half
+    if want_q and quality.conform is not None and want_c and not split:
+        raise ValueError("conform needs a distorted stream of the quality half's own: in a combined pass one BGR stream serves "
+                         "both halves as it is (give the quality pair as qdist next to it, or run the quality half alone)")
     if want_q and quality.scale is not None and want_c and not split:
         raise ValueError("scaling needs a distorted stream of the quality half's own: in a combined pass one BGR stream serves "
                          "both halves at one size (give the rung as qdist next to it, or run the quality half alone)")
@@ -743,6 +766,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 and not any(k.reads == "dist" and getattr(quality, k.name) is True for k in requested))
     halo = any(k.halo for k in requested)
     scaling = want_q and quality.scale is not None
+    conforming = want_q and quality.conform is not None
     if scaling and ref_only:
         raise ValueError("this pass reads the reference stream alone: there is no distorted stream to scale")
     if (want_c or not split) and not ref_only:
@@ -766,6 +790,12 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         if not scaling and fr.geometry() != fq.geometry() and not (fr.host != fq.host):
             # (an equal-byte reshape - 1080x1920 against 1920x1080 - would be compared plane against garbage)
             raise ValueError("reference and distorted streams must share a geometry (%s vs %s)" % (fr.geometry(), fq.geometry()))
+    if conforming:
+        src_planes = quality.conform["planes"]
+        for f in [feeds["ref"]] + ([] if ref_only else [feeds["qdist" if split else "dist"]]):
+            if f.itemsize != (2 if planes_depth(src_planes) > 8 else 1) or f.fb < planes_span(src_planes):
+                raise ValueError("the %s stream's frames (%d bytes of %d-byte samples) do not hold the plan's planes (%d bytes at "
+                                 "%d bits)" % (f.name, f.fb, f.itemsize, planes_span(src_planes), planes_depth(src_planes)))
     if want_c:
         lo, hi = series["range"]
         idx = selected_indices(n, complexity.interval)
@@ -793,7 +823,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         lanes = [first]
     else:
         lanes = list(get_engine_lanes(first.device, min(want_lanes, nchunks)))
-    st = _staging_of(first) if (host or scaling) else None
+    st = _staging_of(first) if (host or scaling or conforming) else None
     cp = get_copy_engine(first.device) if host else None   # the copy lane: every upload of the pass, in chunk order
     nb = len(lanes) + 1    # buffer sets on the device: the chunks the lanes hold + the one whose upload runs under their kernels
     params = first.make_params(resize=complexity.resize, dct_mode=complexity.dct_mode,
@@ -816,6 +846,13 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         scaled_bytes = max(p["qn"] for p in plans) * scaled_fb
         for bs in range(min(nb, nchunks)):
             st.device_buffer(bs, "scaled", scaled_bytes)
+    if conforming:   # the conformed chunk of either stream (the reference's with its halo frame): a lane buffer per set
+        conf_isz = 2 if planes_depth(quality.planes) > 8 else 1
+        conf_fb = -(-planes_span(quality.planes) // 16) * 16
+        conf_bytes = (max(p["qn"] for p in plans) + 1) * conf_fb
+        for bs in range(min(nb, nchunks)):
+            for side in ("conf_ref", "conf_dist"):
+                st.device_buffer(bs, side, conf_bytes)
     # ring slots: the chunks the lanes hold (a slot is free again when its chunk has been waited for), the chunk being
     # uploaded and the chunk the copiers gather meanwhile
     ring = st.ring(min(len(lanes) + 2, nchunks), off) if staged else None
@@ -889,11 +926,37 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                                        owner=b, channels=1, itemsize=fr.itemsize)
                     pair[1] = eng.scale_submit(pair[1], quality.dist_planes, quality.planes, quality.scale, out=out)
                     p["scaled"] = True
+                conf_prev0 = None
+                p["conformed"] = False
+                if conforming:
+                    # both chunks as uploaded -> the registered pair, on this lane; what follows on the lane reads the results.
+                    # The reference goes with the frame before it where a kind wants the halo: in the chunk's own buffer
+                    # (host streams) and in a resident clip alike that frame lies right before the chunk's first.
+                    for i, side in enumerate(("ref", "dist")[:len(pair)]):
+                        src, m = pair[i], p["qn"]
+                        with_halo = i == 0 and halo and p["q0"] > 0
+                        if with_halo:
+                            m += 1
+                            src = DeviceFrames(src.ptr - src.frame_stride, m, src.h, src.w, src.frame_stride, src.row_stride,
+                                               owner=src, channels=src.channels, itemsize=src.itemsize)
+                        if p["conformed"]:
+                            eng.conform_wait()   # (one conform batch is pending at a time: the reference's has to leave first)
+                        b = st.device_buffer(p["k"] % nb, "conf_" + side, conf_bytes)
+                        out = DeviceFrames(b.ptr, m, 1, conf_fb // conf_isz, frame_stride=conf_fb, row_stride=conf_fb, owner=b,
+                                           channels=1, itemsize=conf_isz)
+                        origin, _ix, lut, matrix = quality.conform_args[side]
+                        res = eng.conform_submit(src, quality.conform["planes"], quality.planes, origin, None, lut, matrix, out=out)
+                        p["conformed"] = True
+                        if with_halo:
+                            conf_prev0, res = res.frame(0), res.slice(1, m)
+                        pair[i] = res
                 if quality.ssim:
                     eng.quality_submit(pair[0], pair[1], quality.planes, quality.ssim_mode)
                     p["has_q"] = True
                 prev0 = None                     # the reference frame before the chunk: the halo slot of the chunk's own buffer
-                if halo and p["q0"] > 0:         # (host streams) or the resident clip's frame in place
+                if conforming:
+                    prev0 = conf_prev0
+                elif halo and p["q0"] > 0:       # (host streams) or the resident clip's frame in place
                     if fr.host:
                         b = dev[fr.name]
                         prev0 = DeviceFrames(b.ptr, 1, 1, fr.fb // fr.itemsize, frame_stride=fr.fb, row_stride=fr.fb,
@@ -943,6 +1006,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["rec"] = eng.complexity_wait()
             if p.get("scaled"):
                 eng.scale_wait()
+            if p.get("conformed"):
+                eng.conform_wait()
         if staged:
             free_slots.append(p["slot"])  # every copy out of the slot has completed
 

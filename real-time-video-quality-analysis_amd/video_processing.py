@@ -538,13 +538,14 @@ def sync_extra(result, applied):
 
 def _sync_streams(request, ref, dist, layout, h, w, dh, dw, device):
     """the sync pre-pass of the two entry points: request is _sync_request's (min_overlap, apply).  -> (the six keys, the trim
-    to apply or None).  The trim is applied only where the answer is not ambiguous, and counts as applied only where it cuts."""
+    to apply or None, sync.analyse's dict).  The trim is applied only where the answer is not ambiguous, and counts as applied
+    only where it cuts."""
     own = (dh, dw) != (h, w)
     res = frame_sync(ref, dist, layout, h, w, dh if own else None, dw if own else None, request[0], device=device)
     ref_lo, dist_lo, length = res["trim"]
     cuts = request[1] and not res["ambiguous"] and (ref_lo or dist_lo or length != _frame_count(_host_stream(ref, wide=True))
                                                     or length != _frame_count(_host_stream(dist, wide=True)))
-    return sync_extra(res, bool(cuts)), (res["trim"] if cuts else None)
+    return sync_extra(res, bool(cuts)), (res["trim"] if cuts else None), res
 
 
 def _with_sync_keys(extra, keys):
@@ -717,6 +718,142 @@ def colorfit_extra(result, depth):
             "%.4f, offset %+.2f on the 8-bit scale; a per-code curve %.2f dB beyond that); %d frame(s) have another match; "
             "comparing as given costs that much (the frames are NOT corrected)", found, extra["COLORFIT_PSNR_GAIN"],
             extra["COLORFIT_GAIN_Y"], extra["COLORFIT_OFFSET_Y"], extra["COLORFIT_TONE_PSNR_GAIN"], extra["COLORFIT_FRAMES_OFF"])
+    return extra
+
+
+CONFORM_WINDOW = 256   # the output frames of one submit of frame_conform (the C limit is 32768)
+
+
+def _conform_request(conform, color="match", sync=False, align=None, shift=None, colorfit=False, scale=None):
+    """the conform and conform_color arguments / config keys next to the requests they build on -> the colour mode ("none" |
+    "match" | "levels" | "matrix" | "tone"), or None when conform is off; a ValueError for anything else"""
+    from .conform import COLOR_MODES
+    if not isinstance(conform, (bool, np.bool_)):
+        raise ValueError("conform must be true or false.")
+    if not isinstance(color, str) or color not in COLOR_MODES:
+        raise ValueError("conform_color must be one of %s." % ", ".join("'%s'" % m for m in COLOR_MODES))
+    if not conform:
+        return None
+    if scale is not None:
+        raise ValueError("conform and scale do not go together: a ladder rung is not registered at its own size.")
+    if not (sync or align is not None or shift is not None or colorfit):
+        raise ValueError("conform needs at least one of sync, align, shift and colorfit: nothing is applied that was not measured.")
+    if color != "none" and not colorfit:
+        raise ValueError("conform_color '%s' needs colorfit: no colour map is applied that was not fitted "
+                         "(conform_color 'none' applies time and place alone)." % color)
+    return color
+
+
+def _conform_config(config):
+    """the config keys "conform" and "conform_color" -> _conform_request's answer"""
+    return _conform_request(config.get("conform", False), config.get("conform_color", "match"), config.get("sync", False),
+                            config.get("align"), config.get("shift"), config.get("colorfit", False), config.get("scale"))
+
+
+def _conform_tone_depth(mode, layout):
+    """a tone table has one entry per code and colorfit's tables one bin per code up to 10 bits: refused before any pre-pass"""
+    from .conform import TONE_MAX_DEPTH
+    if mode == "tone" and layout_depth(layout) > TONE_MAX_DEPTH:
+        raise ValueError("conform_color 'tone' is built up to %d bits (%s has %d): above, colorfit's bins hold several codes."
+                         % (TONE_MAX_DEPTH, layout, layout_depth(layout)))
+
+
+def _conform_plan(layout, height, width, **found):
+    """conform.plan for a layout of this module: the plane builder, depth and colour model follow from it"""
+    from . import conform as CO
+    return CO.plan(LAYOUTS[layout][0], int(height), int(width), layout_depth(layout), colorfit_model(layout), **found)
+
+
+def frame_conform(reference, encoded, layout, height=None, width=None, shift=(0, 0), offset=0, ref_index=None, color=None,
+                  engine=None, device=None, window=CONFORM_WINDOW):
+    """Both streams of a pair registered on the GPU (Engine.conform, include/vqa.h) by what align / sync, shift and colorfit
+    found: the frames re-paired by the constant `offset` (or align's ref_index path; frames without a partner are dropped from
+    both), the common window of the shift (dy, dx) cut out of both pictures, the colour map `color` applied to the ENCODED
+    stream (conform.plan states all three).  -> (reference, encoded, summary): two host arrays [n, conformed frame samples] of
+    the inputs' dtype and plan's summary (the CONFORM_* keys, chroma_half, frames).  The output is walked in windows of `window`
+    frames; a frame's bytes depend on its own source frame alone - any window size gives the same arrays."""
+    from .engine import planes_span
+    window = int(window)
+    if not 1 <= window <= N.CONFORM_MAX_OUT:
+        raise ValueError("window must be an integer from 1 to %d." % N.CONFORM_MAX_OUT)
+    ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
+    h, w = _geometry(ref, layout, height, width)
+    n_ref, n_enc = _frame_count(ref), _frame_count(enc)
+    if not n_ref or not n_enc:
+        raise ValueError("both clips must hold at least one frame")
+    plan = _conform_plan(layout, h, w, shift=shift, offset=offset, ref_index=ref_index, n_ref=n_ref, n_dist=n_enc, color=color)
+    planes, out_planes = plan["planes"], plan["out_planes"]
+    wide = layout_depth(layout) > 8
+    n = plan["summary"]["frames"]
+    eng = engine if engine is not None else stream.get_engine(device)
+
+    def part(a, lo, hi):
+        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
+
+    outs = []
+    with stream.pass_lock(eng.device):
+        for src, count, side in ((ref, n_ref, plan["ref"]), (enc, n_enc, plan["dist"])):
+            index = np.arange(count) if side["index"] is None else np.asarray(side["index"])
+            out = np.zeros((n, planes_span(out_planes) // (2 if wide else 1)), np.uint16 if wide else np.uint8)
+            for a in range(0, n, window):
+                ix = index[a:min(n, a + window)]
+                lo, hi = int(ix.min()), int(ix.max()) + 1   # the source frames this window names
+                res = eng.conform(part(src, lo, hi), planes, out_planes, side["origin"], ix - lo, side["lut"], side["matrix"])
+                out[a:a + len(ix)] = eng.download(res)
+                res._owner.free()
+            outs.append(out)
+    return outs[0], outs[1], plan["summary"]
+
+
+def _conform_offset(align_result, sync_result, trimmed):
+    """the constant offset conform applies: align's where it ran (it ran after sync's trim), else sync's where the answer is
+    not ambiguous and was not applied already, else 0"""
+    if align_result is not None:
+        return int(align_result["offset"])
+    if sync_result is not None and not sync_result["ambiguous"] and not trimmed:
+        return int(sync_result["offset"])
+    return 0
+
+
+def _conform_color(mode, ref, enc, layout, h, w, shift, device):
+    """the colour-fit pre-pass of a conformed run: over the pair already registered in time (the caller's slices) and place
+    (frame_conform by the found shift), with the roles SWAPPED where the mode applies a fit - frame_colorfit(enc, ref): its
+    least-squares map r ~ b + M d is then directly the correction of the encoded stream.  -> (conform.plan's `color`, the
+    colorfit result the COLORFIT_* keys are read off)"""
+    cr, ce, _ = frame_conform(ref, enc, layout, h, w, shift=shift, device=device)
+    place = _conform_plan(layout, h, w, shift=shift)
+    oh, ow = place["out_height"], place["out_width"]
+    swapped = mode in ("levels", "matrix", "tone")
+    _rec, tab, res = frame_colorfit(ce, cr, layout, oh, ow, device=device) if swapped else \
+        frame_colorfit(cr, ce, layout, oh, ow, device=device)
+    if mode == "match":
+        color = None if res["match"] == "none" else ("match", res["match"])
+    elif mode == "levels":
+        color = ("levels", res["gain"], res["offset"])
+    elif mode == "matrix":
+        color = ("matrix", res["matrix"], res["matrix_offset"])
+    elif mode == "tone":
+        color = ("tone", tab.tolist())
+    else:
+        color = None
+    return color, res
+
+
+def conform_extra(plan, frames, align_result=None, shift_result=None):
+    """a plan of conform.plan and the frames the pass will pair -> the seven top-level keys of the log and the row; what conform
+    does NOT put right is a warning in the log of this module"""
+    import logging
+    from . import conform as CO
+    extra = CO.log_keys(dict(plan["summary"], CONFORM_FRAMES=int(frames)))
+    log = logging.getLogger(__name__)
+    if align_result is not None and (align_result["dropped"] or align_result["repeated"]):
+        log.warning("conform applies the constant offset %d alone: %d dropped and %d repeated frame(s) stay where they are (a "
+                    "per-frame path is frame_conform's)", extra["CONFORM_OFFSET"], align_result["dropped"], align_result["repeated"])
+    if shift_result is not None and shift_result["edge"]:
+        log.warning("conform applies a shift on the border of the searched band: the true shift may lie beyond it")
+    if extra["CONFORM_CHROMA_HALF"]:
+        log.warning("conform moved the picture by an odd shift on a subsampled axis: the chroma planes stay half a chroma "
+                    "sample apart (nothing is interpolated)")
     return extra
 
 
@@ -991,6 +1128,10 @@ class _StatsWriter:
         self.peak = (1 << layout_depth(layout)) - 1   # vf_psnr.c: max of the pixel format
         self.fp, self.fs = open(psnr_log, "w"), open(ssim_log, "w")
 
+    def resize(self, sizes):
+        """the planes' sizes changed before the first line was written (a conformed pass measures the common window)"""
+        self.sizes = [sizes[j] for j in self.order]
+
     def __call__(self, first_frame, sse, ssim):
         self.fp.write(psnr_stats_lines(first_frame + 1, sse[:, self.order], self.sizes, self.names, self.peak))
         self.fs.write(ssim_stats_lines(first_frame + 1, ssim[:, self.order], self.sizes, self.names))
@@ -1030,7 +1171,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
                        dist_height=None, dist_width=None, scale=None, align=None, shift=None,
                        shift_margin=None, light=False, light_transfer="pq", light_full_range=False, sync=False,
-                       sync_min_overlap=None, sync_apply=False, colorfit=False):
+                       sync_min_overlap=None, sync_apply=False, colorfit=False, conform=False, conform_color="match"):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -1117,6 +1258,22 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     after the SYNC_* and before the ALIGN_* / SHIFT_* keys; gains are capped at 100.0.  A named mishap, or a matrix fit worth
     10 log10(2) dB or more, is also logged as a warning.  The frames are NOT corrected.  colorfit with scale, and a two-plane
     layout, are a ValueError.  Without colorfit every file is byte for byte what it was.
+    conform=True (default False) with conform_color ("none" | "match" (default) | "levels" | "matrix" | "tone"): what the
+    pre-passes FOUND is applied on the GPU before anything is measured (conform.py, Engine.conform_submit), in this order: align's
+    constant offset - after sync's trim with sync_apply; sync's own offset where align is off and nothing was trimmed - by
+    slicing both streams right after the alignment pre-pass, so the shift search already sees the re-paired frames; the clip's
+    shift (dy, dx), as the common window of both pictures; the colour mode, on the distorted stream.  The colour-fit pre-pass then
+    runs over the pair ALREADY registered in time and place, with the roles swapped for "levels", "matrix" and "tone" (its
+    least-squares map is then the correction itself): the COLORFIT_* keys of such a run describe the registered pair.  "match"
+    applies the inverse of the named mishap and nothing when COLORFIT_MATCH is "none"; an ambiguous sync applies no offset.  Every
+    chunk of both streams is uploaded as given and conformed on the engine that measures it (stream.Quality's conform), so the
+    psnr / ssim stats lines and every feature are those of the conformed pair, at the conformed size.  vmaf_log gains, as its
+    LAST top-level keys, "CONFORM_OFFSET", "CONFORM_DY", "CONFORM_DX", "CONFORM_COLOR" ("none", "match:<mishap>", "levels",
+    "matrix", "tone"), "CONFORM_RES" ("1918x1078"), "CONFORM_FRAMES" and "CONFORM_CHROMA_HALF" (1: an odd shift on a subsampled
+    axis left the chroma planes half a chroma sample apart; nothing is interpolated).  A non-zero ALIGN_DROPPED / ALIGN_REPEATED
+    (only the constant offset is applied in the pass), a shift on the band's border and CONFORM_CHROMA_HALF are warnings.
+    conform needs at least one of sync, align, shift and colorfit, a colour mode other than "none" needs colorfit, "tone" needs a
+    depth of at most 10 bits, and conform with scale is a ValueError.  Without conform every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -1129,6 +1286,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     lit = _light_request(light, light_transfer, light_full_range)
     syn = _sync_request(sync, sync_min_overlap, sync_apply)
     fit = _colorfit_request(colorfit, scale)
+    mode = _conform_request(conform, conform_color, sync, align, shift, colorfit, scale)
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -1138,6 +1296,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     h, w = _geometry(ref, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
     _colorfit_request(fit, scale, layout)
+    _conform_tone_depth(mode, layout)
     dist_planes = extra = None
     if scaling:
         from .engine import check_scale_planes
@@ -1155,10 +1314,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                 if f.plane_check is not None:
                     f.plane_check(planes)
         rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
-        sync_keys = None
+        sync_keys = trim = synced = aligned = moved = None
         if syn is not None:   # the sync pre-pass, before everything else: it may trim what everything else reads
             dg = (dist_planes[0][1], dist_planes[0][0]) if scaling else (h, w)
-            sync_keys, trim = _sync_streams(syn, rs, ds, layout, h, w, dg[0], dg[1], device)
+            sync_keys, trim, synced = _sync_streams(syn, rs, ds, layout, h, w, dg[0], dg[1], device)
             if trim is not None:
                 rs, ds = _frame_slice(rs, trim[0], trim[2]), _frame_slice(ds, trim[1], trim[2])
         if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
@@ -1166,15 +1325,39 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         if lit is not None:   # the light pre-pass over the reference stream: its keys go before the other pre-passes
             extra = dict(extra or {}, **light_extra(frame_light(rs, layout, h, w, lit[0], lit[1], device=device)[1]))
         if radius is not None:
-            extra = dict(extra or {}, **align_extra(frame_align(rs, ds, layout, h, w, radius, device=device), radius))
+            aligned = frame_align(rs, ds, layout, h, w, radius, device=device)
+            extra = dict(extra or {}, **align_extra(aligned, radius))
+        offset = 0
+        if mode is not None:   # conform, time: the constant offset by the feeds, before the shift is searched
+            offset = _conform_offset(aligned, synced, trim is not None)
+            ref_lo, dist_lo, length = max(0, offset), max(0, -offset), max(0, min(_frame_count(ds), _frame_count(rs) - offset)
+                                                                           - max(0, -offset))
+            if length < 1:
+                raise ValueError("the offset %d leaves no frame pair to conform" % offset)
+            rs, ds = _frame_slice(rs, ref_lo, length), _frame_slice(ds, dist_lo, length)
         if search is not None:
-            extra = dict(extra or {}, **shift_extra(frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device), search[0]))
+            moved = frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device)
+            extra = dict(extra or {}, **shift_extra(moved, search[0]))
         if sync_keys is not None:
             extra = _with_sync_keys(extra, sync_keys)
-        if fit:   # the colour-fit pre-pass over the (trimmed) pair: its keys go after the SYNC_* keys
+        plan = None
+        if mode is not None:   # conform, place and colour: the fit is taken over the pair registered so far
+            place = tuple(moved["shift"]) if moved is not None else (0, 0)
+            color = None
+            if fit:
+                color, fitted = _conform_color(mode, rs, ds, layout, h, w, place, device)
+                extra = _with_sync_keys(extra, colorfit_extra(fitted, layout_depth(layout)))
+            plan = _conform_plan(layout, h, w, shift=place, offset=offset, color=color)
+            extra = dict(extra or {}, **conform_extra(plan, _frame_count(rs), aligned, moved))
+            planes = plan["out_planes"]
+            wr.resize(_sizes(planes))
+            for f in FEATURES:
+                if sw[f.kind] and f.plane_check is not None:
+                    f.plane_check(planes)
+        elif fit:   # the colour-fit pre-pass over the (trimmed) pair: its keys go after the SYNC_* keys
             extra = _with_sync_keys(extra, colorfit_extra(frame_colorfit(rs, ds, layout, h, w, device=device)[2], layout_depth(layout)))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
-                 batch_size=batch_size, on_quality=wr, device=device)
+                 batch_size=batch_size, on_quality=wr, device=device, conform=plan)
     finally:
         wr.close()
     return None
@@ -1220,10 +1403,11 @@ def _write_feature_log(vmaf_log, q, on, *, model=None, brisque_model=None, sigst
                   sigstats_depth=sigstats_depth, extra=extra, **log)
 
 
-def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, **run):
+def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, conform=None, **run):
     """One pass (stream.run with its further arguments `run`) whose Quality the switches sw (features.switches) spell, and the feature
-    log of what it measured, when a kind is on.  models: _load_models(sw).  -> stream.run's pair"""
-    quality = stream.Quality(planes, ssim_mode, dist_planes=dist_planes, scale=scale,
+    log of what it measured, when a kind is on.  models: _load_models(sw).  conform: None or the plan the pass applies (planes
+    are then its out_planes).  -> stream.run's pair"""
+    quality = stream.Quality(planes, ssim_mode, dist_planes=dist_planes, scale=scale, conform=conform,
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
@@ -1261,6 +1445,7 @@ def _check_mode_keys(config):
     _sync_config(config)
     check_switch("colorfit", config)
     _colorfit_request(config.get("colorfit", False), config.get("scale"))
+    _conform_config(config)
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -1371,7 +1556,16 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         COLORFIT_MATCH, COLORFIT_MATCH_PSNR_GAIN, COLORFIT_PSNR_GAIN, COLORFIT_GAIN_Y, COLORFIT_OFFSET_Y,
         COLORFIT_TONE_PSNR_GAIN and COLORFIT_FRAMES_OFF after the SYNC_* and before the ALIGN_* / SHIFT_* columns; a named
         mishap or a matrix fit worth 10 log10(2) dB or more is also a warning; the frames are not corrected; with scale, and
-        for a two-plane pixfmt, it is a ValueError.
+        for a two-plane pixfmt, it is a ValueError,
+        conform (false default | true) with conform_color ("none" | "match" default | "levels" | "matrix" | "tone"): what sync,
+        align, shift and colorfit found is APPLIED to the quality pair on the GPU before anything is measured, as
+        run_ffmpeg_metrics states it - the constant offset by slicing the input, the encoded quality stream AND its BGR frames
+        alike, the shift as the common window, the colour mode on the encoded quality stream; PSNR, SSIM and every feature of the
+        row are then those of the conformed pair, the COLORFIT_* columns describe the registered pair, and the row gains
+        CONFORM_OFFSET, CONFORM_DY, CONFORM_DX, CONFORM_COLOR, CONFORM_RES, CONFORM_FRAMES and CONFORM_CHROMA_HALF as its LAST
+        columns; the complexity half reads the BGR frames as they are.  It needs at least one of sync, align, shift and
+        colorfit, a colour mode other than "none" needs colorfit, and a quality pair of its own (planar streams next to
+        encoded_bgr); with scale it is a ValueError.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1392,6 +1586,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     lit = _light_config(config)
     syn = _sync_config(config)
     fit = _colorfit_request(config.get("colorfit", False), scale)
+    mode = _conform_config(config)
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -1440,6 +1635,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                             or a.dtype != dt):
                         raise ValueError("%s streams must be planar [N, %d] %s arrays of the frames' geometry (%dx%d)"
                                          % (layout, frame_samples(ah, aw, layout), np.dtype(dt).name, aw, ah))
+        _conform_tone_depth(mode, layout)
         planes = LAYOUTS[layout][0](h, w)
         dist_planes = extra = None
         if scaling:
@@ -1450,9 +1646,12 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         for f in FEATURES:
             if sw[f.kind] and f.plane_check is not None:
                 f.plane_check(planes)
-        sync_keys = None
+        if mode is not None and qdist is None:
+            raise ValueError("conform needs a distorted stream of the quality half's own: pass the quality pair as planar "
+                             "streams next to encoded_bgr (one BGR stream serves both halves as it is)")
+        sync_keys = trim = synced = aligned = moved = None
         if syn is not None:   # the sync pre-pass over the quality pair, before everything else: it may trim what everything else reads
-            sync_keys, trim = _sync_streams(syn, ref, enc if qdist is None else qdist, layout, h, w,
+            sync_keys, trim, synced = _sync_streams(syn, ref, enc if qdist is None else qdist, layout, h, w,
                                             dh if scaling else h, dw if scaling else w, device)
             if trim is not None:   # both halves of the pass see the same frames
                 ref = _frame_slice(_host_stream(ref, wide=True), trim[0], trim[2])
@@ -1462,21 +1661,43 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         if lit is not None:   # the light pre-pass over the input stream, before the pass starts: its keys go first
             extra = dict(extra or {}, **light_extra(frame_light(ref, layout, h, w, lit[0], lit[1], device=device)[1]))
         if radius is not None:   # the alignment pre-pass over the quality pair, likewise
-            extra = dict(extra or {}, **align_extra(frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius,
-                                                                device=device), radius))
+            aligned = frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius, device=device)
+            extra = dict(extra or {}, **align_extra(aligned, radius))
+        offset = 0
+        if mode is not None:   # conform, time: the constant offset by the feeds of BOTH halves, before the shift is searched
+            offset = _conform_offset(aligned, synced, trim is not None)
+            ref = _host_stream(ref, wide=True)
+            ref_lo, dist_lo, length = max(0, offset), max(0, -offset), max(0, min(_frame_count(qdist), _frame_count(ref) - offset)
+                                                                           - max(0, -offset))
+            if length < 1:
+                raise ValueError("the offset %d leaves no frame pair to conform" % offset)
+            ref, enc, qdist = _frame_slice(ref, ref_lo, length), _frame_slice(enc, dist_lo, length), _frame_slice(qdist, dist_lo, length)
         if search is not None:   # the registration pre-pass over the quality pair, likewise
-            extra = dict(extra or {}, **shift_extra(frame_shift(ref, enc if qdist is None else qdist, layout, h, w, search[0],
-                                                                search[1], device=device), search[0]))
+            moved = frame_shift(ref, enc if qdist is None else qdist, layout, h, w, search[0], search[1], device=device)
+            extra = dict(extra or {}, **shift_extra(moved, search[0]))
         if sync_keys is not None:
             extra = _with_sync_keys(extra, sync_keys)
-        if fit:   # the colour-fit pre-pass over the (trimmed) quality pair: its keys go after the SYNC_* keys
+        plan = None
+        if mode is not None:   # conform, place and colour: the fit is taken over the pair registered so far
+            place = tuple(moved["shift"]) if moved is not None else (0, 0)
+            color = None
+            if fit:
+                color, fitted = _conform_color(mode, ref, qdist, layout, h, w, place, device)
+                extra = _with_sync_keys(extra, colorfit_extra(fitted, layout_depth(layout)))
+            plan = _conform_plan(layout, h, w, shift=place, offset=offset, color=color)
+            extra = dict(extra or {}, **conform_extra(plan, _frame_count(ref), aligned, moved))
+            planes = plan["out_planes"]
+            for f in FEATURES:
+                if sw[f.kind] and f.plane_check is not None:
+                    f.plane_check(planes)
+        elif fit:   # the colour-fit pre-pass over the (trimmed) quality pair: its keys go after the SYNC_* keys
             extra = _with_sync_keys(extra, colorfit_extra(frame_colorfit(ref, enc if qdist is None else qdist, layout, h, w,
                                                                          device=device)[2], layout_depth(layout)))
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
                                   complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
-                                  batch_size=batch_size, on_quality=wr, qdist=qdist, device=device)
+                                  batch_size=batch_size, on_quality=wr, qdist=qdist, device=device, conform=plan)
         finally:
             wr.close()
         resolution = "%dx%d" % (ew, eh)
@@ -1493,7 +1714,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
-        if radius is not None or search is not None or lit is not None or syn is not None or fit:   # (extract_metrics_from_logs read them off the log: they go last)
+        if radius is not None or search is not None or lit is not None or syn is not None or fit or mode is not None:   # (extract_metrics_from_logs read them off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
@@ -1543,6 +1764,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
         from .shift import SHIFT_KEYS
         if isinstance(doc_top, dict) and all(k in doc_top for k in SHIFT_KEYS):   # a registration pre-pass: after them
             metrics.update((k, doc_top[k]) for k in SHIFT_KEYS)
+        from .conform import CONFORM_KEYS
+        if isinstance(doc_top, dict) and all(k in doc_top for k in CONFORM_KEYS):   # a conformed pass: the very last
+            metrics.update((k, doc_top[k]) for k in CONFORM_KEYS)
     return metrics
 
 
