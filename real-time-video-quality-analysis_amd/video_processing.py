@@ -15,16 +15,23 @@ reference does.
 import os
 import re
 import threading
+from collections import namedtuple
 
 import numpy as np
 
 from . import _native as N
 from . import stream
+from .align import ALIGN_KEYS
+from .colorfit import COLORFIT_KEYS
 from .complexity_metrics import _open_frames
+from .conform import CONFORM_KEYS
 from .engine import DeviceFrames, bgr_planes, gray_planes, yuv420p_planes, yuv_planes
 from .features import (FEATURES, ITP_RANGES, KINDS, MODEL_PATHS, PARAM_CHECKS, PSNR_HVS_DB_CAP, PU21_PSNR_CAP,  # noqa: F401
                        check_switch, switches)
 from .frames import PIXFMTS, frame_samples
+from .light import LIGHT_KEYS
+from .shift import SHIFT_KEYS
+from .sync import SYNC_KEYS
 
 LAYOUTS = {
     # name: (plane builder, component letters as FFmpeg prints them)
@@ -350,16 +357,14 @@ def frame_scale(frames, layout, height, width, out_height, out_width, filter="bi
     planes, out_planes = LAYOUTS[layout][0](h, w), LAYOUTS[layout][0](int(out_height), int(out_width))
     check_scale_planes(planes, out_planes)
     wide = layout_depth(layout) > 8
-    n = frames.n if isinstance(frames, DeviceFrames) else frames.shape[0]
+    n = _frame_count(frames)
     out = np.zeros((n, planes_span(out_planes) // (2 if wide else 1)), np.uint16 if wide else np.uint8)
     if n == 0:
         return out
     eng = engine if engine is not None else stream.get_engine(device)
     with stream.pass_lock(eng.device):
-        for a in range(0, n, int(batch_size)):
-            b = min(n, a + int(batch_size))
-            chunk = frames.slice(a, b) if isinstance(frames, DeviceFrames) else np.ascontiguousarray(frames[a:b]).reshape(b - a, -1)
-            res = eng.scale(chunk, planes, out_planes, filter)
+        for a, b in _frame_windows(n, int(batch_size)):
+            res = eng.scale(_frame_part(frames, a, b), planes, out_planes, filter)
             out[a:b] = eng.download(res)
             res._owner.free()
     return out
@@ -395,24 +400,16 @@ def frame_align(reference, encoded, layout, height=None, width=None, radius=8, e
     ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
     h, w = _geometry(ref, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
-
-    def count(a):
-        return a.n if isinstance(a, DeviceFrames) else a.shape[0]
-
-    def part(a, lo, hi):
-        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
-
-    n_ref, n = count(ref), count(enc)
+    n_ref, n = _frame_count(ref), _frame_count(enc)
     if not n_ref or not n:
         raise ValueError("both clips must hold at least one frame")
     sse = np.full((n, 2 * R + 1), A.NONE, np.uint64)
     eng = engine if engine is not None else stream.get_engine(device)
     with stream.pass_lock(eng.device):
-        for a in range(0, n, window):
-            b, lo = min(n, a + window), max(a - R, 0)
-            hi = min(b + R, n_ref)
+        for a, b in _frame_windows(n, window):
+            lo, hi = max(a - R, 0), min(b + R, n_ref)
             if hi > lo:   # (else: no reference frame near this window, its rows stay NONE)
-                sse[a:b] = eng.align(part(ref, lo, hi), part(enc, a, b), planes, R, offset=a - lo)
+                sse[a:b] = eng.align(_frame_part(ref, lo, hi), _frame_part(enc, a, b), planes, R, offset=a - lo)
     out = A.analyse(sse)
     out["sse"] = sse
     return out
@@ -463,6 +460,17 @@ def _frame_slice(a, lo, length):
     return a.slice(lo, lo + length) if isinstance(a, DeviceFrames) else a[lo:lo + length]
 
 
+def _frame_part(a, lo, hi):
+    """frames lo .. hi - 1 of a stream as ONE SUBMIT of a frame_* walk: DeviceFrames.slice of resident frames, a contiguous
+    [hi - lo, samples] array of host frames"""
+    return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
+
+
+def _frame_windows(n, window):
+    """the bounds (a, b) of the windows of `window` frames a clip of n frames is walked in"""
+    return [(a, min(n, a + window)) for a in range(0, n, window)]
+
+
 def frame_sync(reference, encoded, layout, height=None, width=None, dist_height=None, dist_width=None, min_overlap=None,
                refine=None, engine=None, device=None, window=SYNC_WINDOW):
     """Clip-wide sync of two whole clips of any lengths (Engine.signature, Engine.sig_cross, include/vqa.h): the 256-byte
@@ -492,18 +500,13 @@ def frame_sync(reference, encoded, layout, height=None, width=None, dist_height=
         raise ValueError("both clips must hold at least one frame")
     if n_ref > N.SIG_MAX_FRAMES or n > N.SIG_MAX_FRAMES:
         raise ValueError("a clip of more than %d frames is not synchronised in one cross." % N.SIG_MAX_FRAMES)
-
-    def part(a, lo, hi):
-        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
-
     eng = engine if engine is not None else stream.get_engine(device)
     sigs = []
     with stream.pass_lock(eng.device):
         for a, count, planes in ((ref, n_ref, planes_r), (enc, n, planes_d)):
             sig = np.empty((count, N.SIG_BYTES), np.uint8)
-            for lo in range(0, count, window):
-                hi = min(count, lo + window)
-                sig[lo:hi] = eng.signature(part(a, lo, hi), planes)
+            for lo, hi in _frame_windows(count, window):
+                sig[lo:hi] = eng.signature(_frame_part(a, lo, hi), planes)
             sigs.append(sig)
         diag, best = eng.sig_cross(sigs[1], sigs[0])
     out = S.analyse(diag, best, n, n_ref, min_overlap)
@@ -548,16 +551,6 @@ def _sync_streams(request, ref, dist, layout, h, w, dh, dw, device):
     return sync_extra(res, bool(cuts)), (res["trim"] if cuts else None), res
 
 
-def _with_sync_keys(extra, keys):
-    """the log's further keys with the six SYNC_* keys (or, after them, the seven COLORFIT_* keys) in their place: after what is
-    there (DIST_RES, SCALE, the LIGHT_* and SYNC_* keys) and before the ALIGN_* / SHIFT_* keys, which stay last"""
-    late = {k: v for k, v in (extra or {}).items() if k.startswith(("ALIGN_", "SHIFT_"))}
-    out = {k: v for k, v in (extra or {}).items() if k not in late}
-    out.update(keys)
-    out.update(late)
-    return out
-
-
 SHIFT_WINDOW = 1024   # the frames of one submit of frame_shift (the C limit is 32768)
 
 
@@ -596,22 +589,14 @@ def frame_shift(reference, encoded, layout, height=None, width=None, radius=4, m
     ref, enc = _host_stream(reference, wide=True), _host_stream(encoded, wide=True)
     h, w = _geometry(ref, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
-
-    def count(a):
-        return a.n if isinstance(a, DeviceFrames) else a.shape[0]
-
-    def part(a, lo, hi):
-        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
-
-    n = count(enc)
-    if not n or count(ref) != n:
+    n = _frame_count(enc)
+    if not n or _frame_count(ref) != n:
         raise ValueError("both clips must hold the same number of frames, at least one")
     sse = np.zeros((n, 2 * R + 1, 2 * R + 1), np.uint64)
     eng = engine if engine is not None else stream.get_engine(device)
     with stream.pass_lock(eng.device):
-        for a in range(0, n, window):
-            b = min(n, a + window)
-            sse[a:b] = eng.shift(part(ref, a, b), part(enc, a, b), planes, R, M)
+        for a, b in _frame_windows(n, window):
+            sse[a:b] = eng.shift(_frame_part(ref, a, b), _frame_part(enc, a, b), planes, R, M)
     out = S.analyse(sse)
     out["sse"] = sse
     return out
@@ -648,6 +633,12 @@ def _colorfit_request(colorfit, scale=None, layout=None):
     return bool(colorfit)
 
 
+def _colorfit_config(config):
+    """the config keys "colorfit" and "scale" -> _colorfit_request's answer"""
+    check_switch("colorfit", config)
+    return _colorfit_request(config.get("colorfit", False), config.get("scale"))
+
+
 def colorfit_model(layout):
     """the model colorfit.analyse reads a layout as: "bgr" for bgr24, "gray" for one plane, "yuv" otherwise"""
     return "bgr" if layout == "bgr24" else "gray" if len(LAYOUTS[layout][0](16, 16)) == 1 else "yuv"
@@ -674,23 +665,15 @@ def frame_colorfit(reference, encoded, layout, height=None, width=None, tables=T
     planes = LAYOUTS[layout][0](h, w)
     if tables:
         window = max(1, min(window, N.COLORFIT_TABLE_POSITIONS // (h * w)))
-
-    def count(a):
-        return a.n if isinstance(a, DeviceFrames) else a.shape[0]
-
-    def part(a, lo, hi):
-        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
-
-    n = count(enc)
-    if not n or count(ref) != n:
+    n = _frame_count(enc)
+    if not n or _frame_count(ref) != n:
         raise ValueError("both clips must hold the same number of frames, at least one")
     rec = np.zeros(n, COLORFIT_DTYPE)
     total = None
     eng = engine if engine is not None else stream.get_engine(device)
     with stream.pass_lock(eng.device):
-        for a in range(0, n, window):
-            b = min(n, a + window)
-            rec[a:b], tab = eng.colorfit(part(ref, a, b), part(enc, a, b), planes, bool(tables))
+        for a, b in _frame_windows(n, window):
+            rec[a:b], tab = eng.colorfit(_frame_part(ref, a, b), _frame_part(enc, a, b), planes, bool(tables))
             if tables:
                 words = [int(v) for v in tab.reshape(-1)]
                 total = words if total is None else [x + y for x, y in zip(total, words)]
@@ -786,19 +769,15 @@ def frame_conform(reference, encoded, layout, height=None, width=None, shift=(0,
     wide = layout_depth(layout) > 8
     n = plan["summary"]["frames"]
     eng = engine if engine is not None else stream.get_engine(device)
-
-    def part(a, lo, hi):
-        return a.slice(lo, hi) if isinstance(a, DeviceFrames) else np.ascontiguousarray(a[lo:hi]).reshape(hi - lo, -1)
-
     outs = []
     with stream.pass_lock(eng.device):
         for src, count, side in ((ref, n_ref, plan["ref"]), (enc, n_enc, plan["dist"])):
             index = np.arange(count) if side["index"] is None else np.asarray(side["index"])
             out = np.zeros((n, planes_span(out_planes) // (2 if wide else 1)), np.uint16 if wide else np.uint8)
-            for a in range(0, n, window):
-                ix = index[a:min(n, a + window)]
+            for a, b in _frame_windows(n, window):
+                ix = index[a:b]
                 lo, hi = int(ix.min()), int(ix.max()) + 1   # the source frames this window names
-                res = eng.conform(part(src, lo, hi), planes, out_planes, side["origin"], ix - lo, side["lut"], side["matrix"])
+                res = eng.conform(_frame_part(src, lo, hi), planes, out_planes, side["origin"], ix - lo, side["lut"], side["matrix"])
                 out[a:a + len(ix)] = eng.download(res)
                 res._owner.free()
             outs.append(out)
@@ -907,7 +886,7 @@ def frame_light(frames, layout, height=None, width=None, transfer="pq", full_ran
     planes = LAYOUTS[layout][0](h, w)
     if len(planes) != 3:
         raise ValueError("light levels take the three planes of a pixel together: %s has %d" % (layout, len(planes)))
-    n = frames.n if isinstance(frames, DeviceFrames) else frames.shape[0]
+    n = _frame_count(frames)
     if not n:
         raise ValueError("the clip must hold at least one frame")
     eng = engine if engine is not None else stream.get_engine(device)
@@ -916,10 +895,8 @@ def frame_light(frames, layout, height=None, width=None, transfer="pq", full_ran
     rec = np.zeros(n, LIGHT_DTYPE)
     hist = np.zeros((n, N.LIGHT_BINS), np.uint32) if histogram else None
     with stream.pass_lock(eng.device):
-        for a in range(0, n, window):
-            b = min(n, a + window)
-            part = frames.slice(a, b) if isinstance(frames, DeviceFrames) else np.ascontiguousarray(frames[a:b]).reshape(b - a, -1)
-            got = eng.light(part, planes, None, transfer, bool(full_range), table, histogram)
+        for a, b in _frame_windows(n, window):
+            got = eng.light(_frame_part(frames, a, b), planes, None, transfer, bool(full_range), table, histogram)
             if histogram:
                 rec[a:b], hist[a:b] = got
             else:
@@ -956,6 +933,101 @@ def _scale_request(scale, dist_height, dist_width):
     if (dist_height is None) != (dist_width is None):
         raise ValueError("dist_height and dist_width go together.")
     return True
+
+
+# ---------------------------------------------------------------------------
+# The pre-passes of the two entry points: one table, one request parser, one chain
+# ---------------------------------------------------------------------------
+# a pre-pass: its name, the top-level keys it adds to the log and the row, and its request parser - (values, config) -> what
+# was asked, None / False when it is off; values: run_ffmpeg_metrics' keywords or a config, which name all but the light range
+# alike.  The table's order is the order of the KEYS; the checks and the run have orders of their own (_requests, _prepass_chain)
+Prepass = namedtuple("Prepass", "name keys request")
+PREPASSES = (
+    Prepass("light", LIGHT_KEYS, lambda v, config: _light_config(v) if config else
+            _light_request(v["light"], v["light_transfer"], v["light_full_range"])),
+    Prepass("sync", SYNC_KEYS, lambda v, config: _sync_config(v)),
+    Prepass("colorfit", COLORFIT_KEYS, lambda v, config: _colorfit_config(v) if config else
+            _colorfit_request(v["colorfit"], v["scale"])),
+    Prepass("align", ALIGN_KEYS, lambda v, config: _align_request(v.get("align"), v.get("scale"))),
+    Prepass("shift", SHIFT_KEYS, lambda v, config: _shift_request(v.get("shift"), v.get("shift_margin"), v.get("scale"))),
+    Prepass("conform", CONFORM_KEYS, lambda v, config: _conform_config(v)),
+)
+# what was asked of a pass before it starts: whether the rung is scaled, align's radius, shift's (radius, margin), light's
+# (transfer, full_range), sync's (min_overlap, apply), whether the colour fit is on, conform's colour mode
+Requests = namedtuple("Requests", "scaling radius search lit syn fit mode")
+
+
+def _requests(values, config=False):
+    """run_ffmpeg_metrics' keywords, or with config=True a config -> Requests.  The order of the checks, and so the first error
+    of a bad combination: scale, align, shift, light, sync, colorfit, conform."""
+    parse = {p.name: p.request for p in PREPASSES}
+    return Requests(_scale_request(values.get("scale"), values.get("dist_height"), values.get("dist_width")),
+                    *(parse[name](values, config) for name in ("align", "shift", "light", "sync", "colorfit", "conform")))
+
+
+def _prepass_keys(found, extra=None):
+    """the log's further keys: extra (a scaled pass's DIST_RES and SCALE, or None) and then the keys the pre-passes found
+    (name -> keys), in the table's order whatever order they ran in.  Nothing found: extra as it is."""
+    if not found:
+        return extra
+    out = dict(extra or {})
+    for p in PREPASSES:
+        out.update(found.get(p.name, {}))
+    return out
+
+
+def _prepass_chain(req, ref, dist, also, layout, h, w, dist_hw, planes, sw, device, extra=None, same_shape=False):
+    """The pre-passes of an entry point, in the order they run: sync and its trim, light over the reference, align, conform's
+    constant offset by slicing the feeds, shift, the colour fit - over the trimmed pair, or with conform over the pair
+    registered in time and place - and conform's plan.  ref, dist: the pair they read; also: further streams cut like dist;
+    dist_hw: dist's own (height, width) under scale; planes: what the pass measures; sw: the switches, for the plane checks at the
+    conformed size; extra: _prepass_keys'; same_shape: a pair of unequal shapes is an error once sync had its say.
+    -> ([ref, dist] + also as they are left, the log's further keys, the plan or None, the planes to measure at, whether a
+    pre-pass ran).  With everything off no stream is touched."""
+    streams, found = [ref, dist] + list(also), {}
+    trim = synced = aligned = moved = plan = None
+
+    def cut(ref_lo, dist_lo, length):
+        streams[0] = _frame_slice(_host_stream(streams[0], wide=True), ref_lo, length)
+        streams[1:] = [_frame_slice(a, dist_lo, length) for a in streams[1:]]
+
+    if req.syn is not None:   # before everything else: it may trim what everything else reads
+        found["sync"], trim, synced = _sync_streams(req.syn, ref, dist, layout, h, w, dist_hw[0], dist_hw[1], device)
+        if trim is not None:
+            cut(*trim)
+    if same_shape and not isinstance(streams[0], DeviceFrames) and streams[0].shape != streams[1].shape:
+        raise ValueError("ref and dist must have the same shape")
+    if req.lit is not None:
+        found["light"] = light_extra(frame_light(streams[0], layout, h, w, req.lit[0], req.lit[1], device=device)[1])
+    if req.radius is not None:
+        aligned = frame_align(streams[0], streams[1], layout, h, w, req.radius, device=device)
+        found["align"] = align_extra(aligned, req.radius)
+    if req.mode is not None:   # conform, time: the constant offset by the feeds, before the shift is searched
+        offset = _conform_offset(aligned, synced, trim is not None)
+        streams[0] = _host_stream(streams[0], wide=True)
+        length = max(0, min(_frame_count(streams[1]), _frame_count(streams[0]) - offset) - max(0, -offset))
+        if length < 1:
+            raise ValueError("the offset %d leaves no frame pair to conform" % offset)
+        cut(max(0, offset), max(0, -offset), length)
+    if req.search is not None:
+        moved = frame_shift(streams[0], streams[1], layout, h, w, req.search[0], req.search[1], device=device)
+        found["shift"] = shift_extra(moved, req.search[0])
+    if req.mode is not None:   # conform, place and colour: the fit is taken over the pair registered so far
+        place = tuple(moved["shift"]) if moved is not None else (0, 0)
+        color = None
+        if req.fit:
+            color, fitted = _conform_color(req.mode, streams[0], streams[1], layout, h, w, place, device)
+            found["colorfit"] = colorfit_extra(fitted, layout_depth(layout))
+        plan = _conform_plan(layout, h, w, shift=place, offset=offset, color=color)
+        found["conform"] = conform_extra(plan, _frame_count(streams[0]), aligned, moved)
+        planes = plan["out_planes"]
+        for f in FEATURES:
+            if sw[f.kind] and f.plane_check is not None:
+                f.plane_check(planes)
+    elif req.fit:   # the colour-fit pre-pass over the (trimmed) pair
+        found["colorfit"] = colorfit_extra(frame_colorfit(streams[0], streams[1], layout, h, w, device=device)[2],
+                                           layout_depth(layout))
+    return streams, _prepass_keys(found, extra), plan, planes, bool(found)
 
 
 def _brisque_model(model_path, range_path):
@@ -1280,13 +1352,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     given = dict(locals())
     sw = switches(given)
     models = _load_models(sw)
-    scaling = _scale_request(scale, dist_height, dist_width)
-    radius = _align_request(align, scale)
-    search = _shift_request(shift, shift_margin, scale)
-    lit = _light_request(light, light_transfer, light_full_range)
-    syn = _sync_request(sync, sync_min_overlap, sync_apply)
-    fit = _colorfit_request(colorfit, scale)
-    mode = _conform_request(conform, conform_color, sync, align, shift, colorfit, scale)
+    req = _requests(given)
+    scaling = req.scaling
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
     dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
@@ -1295,9 +1362,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
         raise ValueError("reference and distorted streams must share a pixel layout")
     h, w = _geometry(ref, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
-    _colorfit_request(fit, scale, layout)
-    _conform_tone_depth(mode, layout)
+    _colorfit_request(req.fit, scale, layout)
+    _conform_tone_depth(req.mode, layout)
     dist_planes = extra = None
+    dh, dw = h, w
     if scaling:
         from .engine import check_scale_planes
         dh, dw = _geometry(_host_stream(dist, wide=True), layout, dist_h, dist_w)
@@ -1313,51 +1381,13 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                 _check_request(f, layout, given)
                 if f.plane_check is not None:
                     f.plane_check(planes)
-        rs, ds = _host_stream(ref, wide=True), _host_stream(dist, wide=True)
-        sync_keys = trim = synced = aligned = moved = None
-        if syn is not None:   # the sync pre-pass, before everything else: it may trim what everything else reads
-            dg = (dist_planes[0][1], dist_planes[0][0]) if scaling else (h, w)
-            sync_keys, trim, synced = _sync_streams(syn, rs, ds, layout, h, w, dg[0], dg[1], device)
-            if trim is not None:
-                rs, ds = _frame_slice(rs, trim[0], trim[2]), _frame_slice(ds, trim[1], trim[2])
-        if not scaling and not isinstance(rs, DeviceFrames) and rs.shape != ds.shape:
-            raise ValueError("ref and dist must have the same shape")
-        if lit is not None:   # the light pre-pass over the reference stream: its keys go before the other pre-passes
-            extra = dict(extra or {}, **light_extra(frame_light(rs, layout, h, w, lit[0], lit[1], device=device)[1]))
-        if radius is not None:
-            aligned = frame_align(rs, ds, layout, h, w, radius, device=device)
-            extra = dict(extra or {}, **align_extra(aligned, radius))
-        offset = 0
-        if mode is not None:   # conform, time: the constant offset by the feeds, before the shift is searched
-            offset = _conform_offset(aligned, synced, trim is not None)
-            ref_lo, dist_lo, length = max(0, offset), max(0, -offset), max(0, min(_frame_count(ds), _frame_count(rs) - offset)
-                                                                           - max(0, -offset))
-            if length < 1:
-                raise ValueError("the offset %d leaves no frame pair to conform" % offset)
-            rs, ds = _frame_slice(rs, ref_lo, length), _frame_slice(ds, dist_lo, length)
-        if search is not None:
-            moved = frame_shift(rs, ds, layout, h, w, search[0], search[1], device=device)
-            extra = dict(extra or {}, **shift_extra(moved, search[0]))
-        if sync_keys is not None:
-            extra = _with_sync_keys(extra, sync_keys)
-        plan = None
-        if mode is not None:   # conform, place and colour: the fit is taken over the pair registered so far
-            place = tuple(moved["shift"]) if moved is not None else (0, 0)
-            color = None
-            if fit:
-                color, fitted = _conform_color(mode, rs, ds, layout, h, w, place, device)
-                extra = _with_sync_keys(extra, colorfit_extra(fitted, layout_depth(layout)))
-            plan = _conform_plan(layout, h, w, shift=place, offset=offset, color=color)
-            extra = dict(extra or {}, **conform_extra(plan, _frame_count(rs), aligned, moved))
-            planes = plan["out_planes"]
+        (rs, ds), extra, plan, planes, ran = _prepass_chain(
+            req, _host_stream(ref, wide=True), _host_stream(dist, wide=True), (), layout, h, w, (dh, dw), planes, sw, device,
+            extra=extra, same_shape=not scaling)
+        if plan is not None:
             wr.resize(_sizes(planes))
-            for f in FEATURES:
-                if sw[f.kind] and f.plane_check is not None:
-                    f.plane_check(planes)
-        elif fit:   # the colour-fit pre-pass over the (trimmed) pair: its keys go after the SYNC_* keys
-            extra = _with_sync_keys(extra, colorfit_extra(frame_colorfit(rs, ds, layout, h, w, device=device)[2], layout_depth(layout)))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
-                 batch_size=batch_size, on_quality=wr, device=device, conform=plan)
+                 ran=ran, batch_size=batch_size, on_quality=wr, device=device, conform=plan)
     finally:
         wr.close()
     return None
@@ -1403,15 +1433,15 @@ def _write_feature_log(vmaf_log, q, on, *, model=None, brisque_model=None, sigst
                   sigstats_depth=sigstats_depth, extra=extra, **log)
 
 
-def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, conform=None, **run):
+def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, conform=None, ran=False, **run):
     """One pass (stream.run with its further arguments `run`) whose Quality the switches sw (features.switches) spell, and the feature
     log of what it measured, when a kind is on.  models: _load_models(sw).  conform: None or the plan the pass applies (planes
-    are then its out_planes).  -> stream.run's pair"""
+    are then its out_planes).  ran: a pre-pass ran (_prepass_chain).  -> stream.run's pair"""
     quality = stream.Quality(planes, ssim_mode, dist_planes=dist_planes, scale=scale, conform=conform,
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
-    if any(on.values()) or (extra and ("ALIGN_RADIUS" in extra or "SHIFT_RADIUS" in extra or "LIGHT_MAXCLL" in extra or "SYNC_OFFSET" in extra or "COLORFIT_MATCH" in extra)):   # (a pre-pass always has something to say)
+    if any(on.values()) or ran:   # (a pre-pass always has something to say; DIST_RES and SCALE alone do not ask for a log)
         _write_feature_log(vmaf_log, q, on, model=models[0], brisque_model=models[1], sigstats_depth=layout_depth(layout),
                            extra=extra)
     return q, series
@@ -1438,14 +1468,7 @@ def _check_mode_keys(config):
         v = config.get(key)
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v <= 0):
             raise ValueError("height and width must be positive integers.")
-    _scale_request(config.get("scale"), config.get("dist_height"), config.get("dist_width"))
-    _align_request(config.get("align"), config.get("scale"))
-    _shift_request(config.get("shift"), config.get("shift_margin"), config.get("scale"))
-    _light_config(config)
-    _sync_config(config)
-    check_switch("colorfit", config)
-    _colorfit_request(config.get("colorfit", False), config.get("scale"))
-    _conform_config(config)
+    _requests(config, config=True)
 
 
 def process_video_and_extract_metrics(input_video, encoded_video, config, csv_file="video_quality_data.csv",
@@ -1580,13 +1603,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     sw = _config_switches(config)
     models = _load_models(sw)   # before the pass starts: a bad file costs no GPU time
     scale = config.get("scale")
-    scaling = scale is not None
-    radius = _align_request(config.get("align"), scale)
-    search = _shift_request(config.get("shift"), config.get("shift_margin"), scale)
-    lit = _light_config(config)
-    syn = _sync_config(config)
-    fit = _colorfit_request(config.get("colorfit", False), scale)
-    mode = _conform_config(config)
+    req = _requests(config, config=True)
+    scaling = req.scaling
     dct_mode = cm._DCT_MODES[config.get("dct_mode")]
     motion_mode = cm.motion_mode_of(config.get("motion"))
     device = config.get("device")
@@ -1635,7 +1653,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                                                             or a.dtype != dt):
                         raise ValueError("%s streams must be planar [N, %d] %s arrays of the frames' geometry (%dx%d)"
                                          % (layout, frame_samples(ah, aw, layout), np.dtype(dt).name, aw, ah))
-        _conform_tone_depth(mode, layout)
+        _conform_tone_depth(req.mode, layout)
         planes = LAYOUTS[layout][0](h, w)
         dist_planes = extra = None
         if scaling:
@@ -1646,58 +1664,19 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         for f in FEATURES:
             if sw[f.kind] and f.plane_check is not None:
                 f.plane_check(planes)
-        if mode is not None and qdist is None:
+        if req.mode is not None and qdist is None:
             raise ValueError("conform needs a distorted stream of the quality half's own: pass the quality pair as planar "
                              "streams next to encoded_bgr (one BGR stream serves both halves as it is)")
-        sync_keys = trim = synced = aligned = moved = None
-        if syn is not None:   # the sync pre-pass over the quality pair, before everything else: it may trim what everything else reads
-            sync_keys, trim, synced = _sync_streams(syn, ref, enc if qdist is None else qdist, layout, h, w,
-                                            dh if scaling else h, dw if scaling else w, device)
-            if trim is not None:   # both halves of the pass see the same frames
-                ref = _frame_slice(_host_stream(ref, wide=True), trim[0], trim[2])
-                enc = _frame_slice(enc, trim[1], trim[2])
-                if qdist is not None:
-                    qdist = _frame_slice(qdist, trim[1], trim[2])
-        if lit is not None:   # the light pre-pass over the input stream, before the pass starts: its keys go first
-            extra = dict(extra or {}, **light_extra(frame_light(ref, layout, h, w, lit[0], lit[1], device=device)[1]))
-        if radius is not None:   # the alignment pre-pass over the quality pair, likewise
-            aligned = frame_align(ref, enc if qdist is None else qdist, layout, h, w, radius, device=device)
-            extra = dict(extra or {}, **align_extra(aligned, radius))
-        offset = 0
-        if mode is not None:   # conform, time: the constant offset by the feeds of BOTH halves, before the shift is searched
-            offset = _conform_offset(aligned, synced, trim is not None)
-            ref = _host_stream(ref, wide=True)
-            ref_lo, dist_lo, length = max(0, offset), max(0, -offset), max(0, min(_frame_count(qdist), _frame_count(ref) - offset)
-                                                                           - max(0, -offset))
-            if length < 1:
-                raise ValueError("the offset %d leaves no frame pair to conform" % offset)
-            ref, enc, qdist = _frame_slice(ref, ref_lo, length), _frame_slice(enc, dist_lo, length), _frame_slice(qdist, dist_lo, length)
-        if search is not None:   # the registration pre-pass over the quality pair, likewise
-            moved = frame_shift(ref, enc if qdist is None else qdist, layout, h, w, search[0], search[1], device=device)
-            extra = dict(extra or {}, **shift_extra(moved, search[0]))
-        if sync_keys is not None:
-            extra = _with_sync_keys(extra, sync_keys)
-        plan = None
-        if mode is not None:   # conform, place and colour: the fit is taken over the pair registered so far
-            place = tuple(moved["shift"]) if moved is not None else (0, 0)
-            color = None
-            if fit:
-                color, fitted = _conform_color(mode, ref, qdist, layout, h, w, place, device)
-                extra = _with_sync_keys(extra, colorfit_extra(fitted, layout_depth(layout)))
-            plan = _conform_plan(layout, h, w, shift=place, offset=offset, color=color)
-            extra = dict(extra or {}, **conform_extra(plan, _frame_count(ref), aligned, moved))
-            planes = plan["out_planes"]
-            for f in FEATURES:
-                if sw[f.kind] and f.plane_check is not None:
-                    f.plane_check(planes)
-        elif fit:   # the colour-fit pre-pass over the (trimmed) quality pair: its keys go after the SYNC_* keys
-            extra = _with_sync_keys(extra, colorfit_extra(frame_colorfit(ref, enc if qdist is None else qdist, layout, h, w,
-                                                                         device=device)[2], layout_depth(layout)))
+        # the pre-passes read the quality pair; the BGR frames beside it are cut with it, so both halves see the same frames
+        streams, extra, plan, planes, ran = _prepass_chain(
+            req, ref, enc if qdist is None else qdist, () if qdist is None else (enc,), layout, h, w,
+            (dh, dw) if scaling else (h, w), planes, sw, device, extra=extra)
+        ref, enc, qdist = (streams[0], streams[1], None) if qdist is None else (streams[0], streams[2], streams[1])
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
                                   complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
-                                  batch_size=batch_size, on_quality=wr, qdist=qdist, device=device, conform=plan)
+                                  ran=ran, batch_size=batch_size, on_quality=wr, qdist=qdist, device=device, conform=plan)
         finally:
             wr.close()
         resolution = "%dx%d" % (ew, eh)
@@ -1714,7 +1693,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         metrics.update(dict(zip(names, t)))
         if scaling:
             metrics.update(extra)
-        if radius is not None or search is not None or lit is not None or syn is not None or fit or mode is not None:   # (extract_metrics_from_logs read them off the log: they go last)
+        if ran:   # (extract_metrics_from_logs read the pre-passes' keys off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
         thread_safe_update_csv(metrics, csv_file)
         return metrics
@@ -1749,24 +1728,9 @@ def extract_metrics_from_logs(psnr_log, ssim_log, vmaf_log, video_file, crf, bit
             metrics["VMAF"] = float(pooled["vmaf"]["mean"])
         for f in FEATURES:         # (per-frame dB values were capped by the log's writer)
             f.to_row(f, pooled, signal, metrics)
-        from .light import LIGHT_KEYS
-        if isinstance(doc_top, dict) and all(k in doc_top for k in LIGHT_KEYS):   # a light pre-pass: before the other pre-passes
-            metrics.update((k, doc_top[k]) for k in LIGHT_KEYS)
-        from .sync import SYNC_KEYS
-        if isinstance(doc_top, dict) and all(k in doc_top for k in SYNC_KEYS):   # a sync pre-pass: before the two below
-            metrics.update((k, doc_top[k]) for k in SYNC_KEYS)
-        from .colorfit import COLORFIT_KEYS
-        if isinstance(doc_top, dict) and all(k in doc_top for k in COLORFIT_KEYS):   # a colour-fit pre-pass: after the sync keys
-            metrics.update((k, doc_top[k]) for k in COLORFIT_KEYS)
-        from .align import ALIGN_KEYS
-        if isinstance(doc_top, dict) and all(k in doc_top for k in ALIGN_KEYS):   # an alignment pre-pass: the row's last columns
-            metrics.update((k, doc_top[k]) for k in ALIGN_KEYS)
-        from .shift import SHIFT_KEYS
-        if isinstance(doc_top, dict) and all(k in doc_top for k in SHIFT_KEYS):   # a registration pre-pass: after them
-            metrics.update((k, doc_top[k]) for k in SHIFT_KEYS)
-        from .conform import CONFORM_KEYS
-        if isinstance(doc_top, dict) and all(k in doc_top for k in CONFORM_KEYS):   # a conformed pass: the very last
-            metrics.update((k, doc_top[k]) for k in CONFORM_KEYS)
+        for p in PREPASSES:        # a pre-pass's keys, when the log holds them all: the row's last columns, in the table's order
+            if isinstance(doc_top, dict) and all(k in doc_top for k in p.keys):
+                metrics.update((k, doc_top[k]) for k in p.keys)
     return metrics
 
 

@@ -136,6 +136,38 @@ def test_a_delayed_shifted_range_squeezed_stream_is_put_right(engine, tmp_path, 
     assert psnr_y(got) > psnr_y(_run(tmp_path, "given", ref, dist, depth)) + 10.0
 
 
+def test_every_prepass_on_through_both_entry_points(engine, tmp_path):
+    """all six pre-passes at once: the one chain behind both entry points finds and writes the same, in the table's order"""
+    from rtvqa_amd import synth
+    from rtvqa_amd import video_processing as vp
+    shift = (-1, 2)
+    ref, dist = _pair(8, shift, _full_to_limited)
+    on = dict(sync=True, sync_apply=True, light=True, align=3, shift=4, colorfit=True, conform=True)
+    got = _run(tmp_path, "all", ref, dist, 8, batch_size=4, **on, **KINDS)
+    doc = json.load(open(got[2]))
+    cfg = {"crf": 23, "resize_width": 64, "resize_height": 64, "frame_interval": 1, "batch_size": 4, "pixfmt": "yuv420p",
+           "height": H, "width": W}
+    row = vp.process_video_and_extract_metrics(ref, dist, dict(cfg, **on), csv_file=str(tmp_path / "all.csv"), column_order="fixed",
+                                               encoded_bgr=synth.s_natural(N_FRAMES, H, W, seed=3))
+    keys = [k for p in vp.PREPASSES for k in p.keys]
+    assert [p.name for p in vp.PREPASSES] == ["light", "sync", "colorfit", "align", "shift", "conform"]
+    assert list(doc)[-len(keys):] == keys == list(row)[-len(keys):]                  # the table's order, log and row
+    assert [(k, repr(doc[k])) for k in keys] == [(k, repr(row[k])) for k in keys]    # found alike by both entry points
+    # sync's trim re-paired the streams, so align finds nothing left and conform applies no offset of its own
+    want = {"SYNC_OFFSET": -DELAY, "SYNC_APPLIED": 1, "ALIGN_OFFSET": 0, "SHIFT_DY": shift[0], "SHIFT_DX": shift[1],
+            "COLORFIT_MATCH": "full_to_limited", "CONFORM_OFFSET": 0, "CONFORM_DY": shift[0], "CONFORM_DX": shift[1],
+            "CONFORM_COLOR": "match:full_to_limited", "CONFORM_FRAMES": N_FRAMES - DELAY, "CONFORM_CHROMA_HALF": 1}
+    assert {k: doc[k] for k in want} == want
+    assert 0.0 < doc["LIGHT_MAXFALL"] <= doc["LIGHT_MAXCLL"] <= 10000.0
+    # the files are those of a plain run over the pair the restatement conformed: the same frames, named from the untrimmed streams
+    plan = vp._conform_plan(LAYOUT[8], H, W, shift=shift, offset=-DELAY, n_ref=N_FRAMES, n_dist=N_FRAMES,
+                            color=("match", "full_to_limited"))
+    _check_against_plain(tmp_path, "all", ref, dist, 8, plan, got, {k: v for k, v in doc.items() if not k.startswith("LIGHT_")})
+    # and the row's PSNR and SSIM are the first lines' of those files
+    first = vp.extract_metrics_from_logs(got[0], got[1], "absent", "x", 23, 0, "%dx%d" % (W, H), 30.0)
+    assert (row["PSNR"], row["SSIM"]) == (first["PSNR"], first["SSIM"])
+
+
 def test_an_even_shift_leaves_the_chroma_exact(engine):
     from rtvqa_amd import video_processing as vp
     clean = lambda fr, depth: [a.astype(np.float64) for a in fr]

@@ -198,10 +198,11 @@ def test_the_key_order_and_the_log(tmp_path, caplog):
     from rtvqa_amd.align import ALIGN_KEYS
     from rtvqa_amd.light import LIGHT_KEYS
     from rtvqa_amd.shift import SHIFT_KEYS
-    extra = {k: 1 for k in LIGHT_KEYS + ALIGN_KEYS + SHIFT_KEYS}
-    merged = vp._with_sync_keys(extra, keys)
+    found = {"shift": {k: 1 for k in SHIFT_KEYS}, "align": {k: 1 for k in ALIGN_KEYS}, "sync": keys,
+             "light": {k: 1 for k in LIGHT_KEYS}}   # (in no order: the table orders them)
+    merged = vp._prepass_keys(found)
     assert list(merged) == list(LIGHT_KEYS) + list(S.SYNC_KEYS) + list(ALIGN_KEYS) + list(SHIFT_KEYS)
-    assert list(vp._with_sync_keys(None, keys)) == list(S.SYNC_KEYS)
+    assert list(vp._prepass_keys({"sync": keys})) == list(S.SYNC_KEYS)
     log = str(tmp_path / "v.json")
     vp.write_vif_log(log, extra=merged)
     doc = json.load(open(log))
