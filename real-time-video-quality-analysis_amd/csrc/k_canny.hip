@@ -4,21 +4,26 @@
 //   cv2.Canny(gray, 100, 200) (aperture 3, L1 gradient) -> np.sum(edges > 0)
 //
 // Stage 1 — gradient, non-maximum suppression, double threshold.  Output: two BIT-PLANES (edge,
-//   weak candidate), one u64 per 64 pixels, 2 x P/8 bytes instead of a P-byte map.
+//   weak candidate), one u64 per 64 pixels, 2 x P/8 bytes instead of a P-byte map.  The planes hold the TRANSPOSED
+//   image: one word is 64 rows of ONE COLUMN (layout at bp_index below).  8-connected hysteresis commutes with
+//   transposition and the three counts are population counts, so stages 2 and 3 run on the planes as they are, with
+//   height and width swapped (canny_plane_geom is the one place that swaps them).
 //   k_canny_nms4 (default): lane = column, one wave per 256 x 64 strip; one unaligned dword load per pixel; v_sad_u16
 //     magnitudes; the four tiles of a strip are PAIRED in 16-bit halves, so the neighbour ring (DPP), the sector test
 //     (two per-|gx| thresholds) and every NMS decision run on packed registers, two pixels per instruction, with truth
-//     values as the sign bits of the halves; only the kept and the above-high pixels become bit-plane words (vector
-//     compares); lane r captures row r, so a strip leaves as four 512-byte tile stores (details below).
+//     values as the sign bits of the halves; the kept and the above-high decisions never leave that form: every lane
+//     shifts its own two sign bits into a per-column shift register (a shift and a v_bfi per pair and mask), so a
+//     strip leaves as four 512-byte tile stores, lane L writing the word of its column (details below).
 //   k_canny_nms  (frames narrower than 4 pixels, which the dword window cannot serve): 64x32 tile per workgroup through
-//     LDS, words built with __ballot (round 1's kernel).
+//     LDS, column words gathered with LDS atomics (round 1's kernel).
 //   k_canny_nms3 (lab build only, VQA_NMS_VARIANT=3: round 3's kernel): as nms4 up to the magnitudes, then every
 //     condition becomes a 64-bit mask at once and the decisions are mask logic on the scalar unit.
 //   k_canny_nms2 (lab build only, VQA_NMS_VARIANT=2: round 2's kernel): 4 pixels per lane, packed 16-bit Sobel.
+//     Both lab kernels still capture "lane r holds row r" and transpose each tile in the wave before they store it.
 //   All: Sobel 3x3 on replicated borders, L1 magnitude = 0 outside the image (OpenCV's zero-bordered
 //   buffer), TG22 fixed-point sector test.
 // Stage 2 (k_canny_hyst_*): 8-connected hysteresis as an iterate-to-fixpoint on
-//   64x64-pixel tiles held ENTIRELY IN REGISTERS: lane r owns row r as a u64.
+//   64x64-pixel tiles held ENTIRELY IN REGISTERS: lane r owns row r OF THE PLANES (a column of the frame) as a u64.
 //   One step = vertical neighbours by whole-wave DPP shifts, 3x3 dilation, then a flood along the row done by the
 //   integer adder (carry propagation through runs; bit-reversed for the other direction), so a horizontal chain of
 //   any length is absorbed in ONE step.  Promotion is monotone (weak -> edge only), so the fixpoint is unique and
@@ -30,7 +35,7 @@
 // Stage 3 (k_canny_count): np.sum(edges > 0) = the set bits of the final edge plane, one pass.
 //
 // Roofline: HBM, P + P/4 (+ P/4 per hysteresis pass over live tiles) bytes per frame; in practice stage 1 is bound by
-// vector-ALU issue (127 instructions per 256-pixel row), stage 2 by latency.
+// vector-ALU issue (111 instructions per 256-pixel row), stage 2 by latency.
 #include "vqa_dev.hpp"
 #include "vqa_kernels.hpp"
 #include "vqa_math.hpp"
@@ -44,14 +49,41 @@ constexpr int GP = 72;      // LDS gray row pitch (bytes): [0,4) left halo slot,
 constexpr int GR = TH + 4;  // gray rows
 constexpr int MW = TW + 2, MH = TH + 2;
 
-canny_geom canny_tiles(int h, int w) { return canny_geom{(w + TW - 1) / TW, (h + TH - 1) / TH}; }
-
-// strong / weak: bit-planes in TILE-MAJOR order, [n][tiles_y][ww][64] u64 (ww = ceil(w/64), tiles_y =
-// ceil(h/64)): word r of tile (ty, tx) holds pixels (64 ty + r, 64 tx .. 64 tx + 63), bit k <-> column
-// 64 tx + k.  A hysteresis wave therefore reads its tile as 512 contiguous bytes.
+// strong / weak: bit-planes OF THE TRANSPOSED IMAGE in TILE-MAJOR order.  A frame of h rows and w columns is stored
+// as the plane image of h' = w rows and w' = h columns: [n][tiles_y'][ww'][64] u64 with tiles_y' = ceil(w/64) and
+// ww' = ceil(h/64).  Word c of plane tile (ty', tx') holds the frame's COLUMN 64 ty' + c, rows 64 tx' .. 64 tx' + 63:
+// bit r <-> frame row 64 tx' + r.  Bits of rows >= h are 0; words of columns >= w are never read (and never
+// written).  Stage 1 owns one frame column per lane and appends one decision bit per row, so it writes this layout
+// without any cross-lane traffic; a hysteresis wave still reads its tile as 512 contiguous bytes.
+// Everything below stage 1 is written in PLANE coordinates: bp_index's y is a plane row (a frame column).
 __host__ __device__ __forceinline__ int64_t bp_index(int f, int y, int tx, int ww, int tiles_y)
 {
     return ((((int64_t)f * tiles_y + (y >> 6)) * ww + tx) << 6) + (y & 63);
+}
+
+// THE swap: the geometry of the planes of an h x w frame.  Stage 1 stores through it, the stage 2 / 3 launchers and
+// the host-side reader (canny_plane_word) read through it; the C ABI's call sites keep passing the frame's (h, w).
+struct canny_planes {
+    int h, ww, tiles_y; // plane rows (= frame columns), plane tiles per row, plane tile rows
+};
+__host__ __device__ __forceinline__ canny_planes canny_plane_geom(int h, int w)
+{
+    return canny_planes{w, (h + 63) >> 6, (w + 63) >> 6};
+}
+// word of frame pixel (y, x) of frame f; its bit is y & 63
+__host__ __device__ __forceinline__ int64_t bp_pixel_word(int f, int y, int x, int h, int w)
+{
+    const canny_planes g = canny_plane_geom(h, w);
+    return bp_index(f, x, y >> 6, g.ww, g.tiles_y);
+}
+
+int64_t canny_plane_word(int h, int w, int y, int x) { return bp_pixel_word(0, y, x, h, w); }
+
+// tiles of the PLANE image, 64 wide and TH high (the hysteresis launchers size their grids and round counts by it)
+canny_geom canny_tiles(int h, int w)
+{
+    const canny_planes g = canny_plane_geom(h, w);
+    return canny_geom{g.ww, (g.h + TH - 1) / TH};
 }
 
 __global__ __launch_bounds__(256) void k_canny_nms(const uint8_t *__restrict__ gray, int pitch, int64_t plane_stride,
@@ -64,11 +96,13 @@ __global__ __launch_bounds__(256) void k_canny_nms(const uint8_t *__restrict__ g
     __shared__ uint16_t smag[MH * MW];
     __shared__ int sgxy[MH * MW]; // (gy << 16) | (gx & 0xffff)
     __shared__ unsigned s_cnt[2];
+    __shared__ unsigned s_col[2][TW]; // kept-and-above-high / kept-only bits of the tile's columns, bit = row
     const int f = blockIdx.z;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     const uint8_t *g = gray + (int64_t)f * plane_stride;
     const int tid = threadIdx.x;
     if (tid < 2) s_cnt[tid] = 0;
+    if (tid < 2 * TW) (&s_col[0][0])[tid] = 0;
     // ---- stage gray rows y0-2 .. y0+TH+1, columns x0-2 .. x0+TW+1 (replicated borders)
     for (int i = tid; i < GR * 18; i += 256) {
         const int ry = i / 18, u = i - ry * 18; // u: 0 = left halo, 1..16 = interior dwords, 17 = right halo
@@ -114,34 +148,32 @@ __global__ __launch_bounds__(256) void k_canny_nms(const uint8_t *__restrict__ g
         sgxy[i] = (int)(((uint32_t)gy << 16) | ((uint32_t)gx & 0xffffu));
     }
     __syncthreads();
-    // ---- NMS + double threshold on the TH x TW interior; a wave owns one 64-pixel row per step,
-    //      so __ballot hands us that row's strong / weak words directly
-    unsigned n_strong = 0, n_weak = 0;
-    const int tiles_y = (h + 63) >> 6;
+    // ---- NMS + double threshold on the TH x TW interior.  The planes want one word per COLUMN (bit = row): every pixel
+    //      ORs its decision into its column's LDS word, 32 rows = one half of a plane word
     for (int i = tid; i < TH * TW; i += 256) {
         const int ly = i / TW, lx = i - ly * TW;
         const int y = y0 + ly, x = x0 + lx;
-        int s = 0;
-        if (y < h && x < w) {
+        if (y < h && x < w) { // rows >= h leave 0 bits
             const uint16_t *c = smag + (ly + 1) * MW + (lx + 1);
             const int m = c[0];
             const int nb[8] = {c[-MW - 1], c[-MW], c[-MW + 1], c[-1], c[1], c[MW - 1], c[MW], c[MW + 1]};
             const int pk = sgxy[(ly + 1) * MW + (lx + 1)];
             const int gx = (int)(int16_t)(pk & 0xffff), gy = pk >> 16;
-            s = canny_classify(m, gx, gy, nb, low, high);
-        }
-        const unsigned long long sm = __ballot(s == 2), wm = __ballot(s == 1);
-        if (lane_id() == 0 && y < h) {
-            const int64_t j = bp_index(f, y, blockIdx.x, ww, tiles_y);
-            strong[j] = sm;
-            weak[j] = wm;
-            n_strong += __popcll(sm);
-            n_weak += __popcll(wm);
+            const int s = canny_classify(m, gx, gy, nb, low, high);
+            if (s) atomicOr(&s_col[s == 2 ? 0 : 1][lx], 1u << ly);
         }
     }
-    if (lane_id() == 0) {
-        if (n_strong) atomicAdd(&s_cnt[0], n_strong);
-        if (n_weak) atomicAdd(&s_cnt[1], n_weak);
+    __syncthreads();
+    if (tid < TW && x0 + tid < w) { // columns >= w are not stored
+        const int64_t j = bp_pixel_word(f, y0, x0 + tid, h, w);
+        const int half = (y0 >> 5) & 1; // TH = 32: rows y0 .. y0 + 31 are bits 0-31 or 32-63 of the word
+        uint32_t *sp = (uint32_t *)(strong + j), *wp = (uint32_t *)(weak + j);
+        const unsigned sm = s_col[0][tid], wm = s_col[1][tid];
+        sp[half] = sm;
+        wp[half] = wm;
+        if (half == 0 && y0 + TH >= h) { sp[1] = 0u; wp[1] = 0u; } // no workgroup owns the upper half
+        if (sm) atomicAdd(&s_cnt[0], (unsigned)__popc(sm));
+        if (wm) atomicAdd(&s_cnt[1], (unsigned)__popc(wm));
     }
     __syncthreads();
     if (tid == 0) {
@@ -180,11 +212,52 @@ __device__ __forceinline__ uint32_t dpp_or_row(uint32_t v)
     return v;
 }
 
+// The lab kernels (nms2, nms3) capture a strip as "lane r holds row r of tile k"; the planes hold one word per
+// COLUMN.  A 64 x 64 bit transpose inside the wave: column c's word is the ballot of bit c over the lanes.  64 ballots
+// per tile and plane - slow, and only here: the shipped kernel never has the row-major form.
+__device__ __forceinline__ unsigned long long lab_transpose_tile(unsigned long long rowword)
+{
+    unsigned long long out = 0;
+    const int lane = lane_id();
+    for (int c = 0; c < 64; c++) {
+        const unsigned long long m = __ballot((rowword >> c) & 1ull);
+        if (lane == c) out = m;
+    }
+    return out;
+}
+
+// rows[k] / above[k]: lane r holds the kept / the above-high pixels of row y0 + r of tile 4 bx + k (lanes >= rows_out
+// and bits of columns >= w must be 0).  Stores the strip's tiles in the planes' layout and returns the totals.
+__device__ __forceinline__ void lab_store_strip(const unsigned long long (&sw)[4], const unsigned long long (&wk)[4], int f,
+                                                int bx, int by, int h, int w, unsigned long long *__restrict__ strong,
+                                                unsigned long long *__restrict__ weak, vqa_frame_metrics *__restrict__ res)
+{
+    const int lane = lane_id();
+    unsigned n_strong = 0, n_weak = 0;
+    for (int k = 0; k < 4; k++) {
+        const int x = (bx * 4 + k) * 64 + lane;
+        if ((bx * 4 + k) * 64 >= w) break; // (wave-uniform)
+        const unsigned long long s = lab_transpose_tile(sw[k]), v = lab_transpose_tile(wk[k]);
+        if (x < w) {
+            const int64_t o = bp_pixel_word(f, by * 64, x, h, w);
+            strong[o] = s;
+            weak[o] = v;
+            n_strong += __popcll(s);
+            n_weak += __popcll(v);
+        }
+    }
+    n_strong = wave_sum(n_strong);
+    n_weak = wave_sum(n_weak);
+    if (lane == 0) {
+        if (n_strong) atomicAdd(&res[f].edge_strong, n_strong);
+        if (n_weak) atomicAdd(&res[f].edge_weak, n_weak);
+    }
+}
+
 template <int PH>
 __device__ __forceinline__ void nms2_step(nms_rows &S, int j, const uint8_t *__restrict__ g, int pitch, int h, int w,
-                                          int y0, int xm2, const s2 (&cmask)[3], int low, int high, int f, int tx,
-                                          int ww, int tiles_y, unsigned long long *__restrict__ strong,
-                                          unsigned long long *__restrict__ weak, unsigned &n_strong, unsigned &n_weak)
+                                          int y0, int xm2, const s2 (&cmask)[3], int low, int high,
+                                          unsigned long long (&cap_s)[4], unsigned long long (&cap_w)[4])
 {
     constexpr int A = (PH + 1) % 3, B = (PH + 2) % 3, Cc = PH; // rows R-2, R-1, R of the h window
     const int lane = lane_id();
@@ -232,14 +305,7 @@ __device__ __forceinline__ void nms2_step(nms_rows &S, int j, const uint8_t *__r
         uint32_t nib_s = 0, nib_w = 0;
         // a row of 256 pixels with no gradient above `low` (flat regions) skips NMS and the word assembly
         const bool any_cand = __any(max(max(md[1], md[2]), max(md[3], md[4])) > low);
-        if (!any_cand) {
-            if ((lane & 15) == 15 && tx < ww) {
-                const int64_t o = bp_index(f, y, tx, ww, tiles_y);
-                strong[o] = 0ull;
-                weak[o] = 0ull;
-            }
-            return;
-        }
+        if (!any_cand) return; // (the captures start as 0)
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int nb[8] = {up[k], up[k + 1], up[k + 2], md[k], md[k + 2], dn[k], dn[k + 1], dn[k + 2]};
@@ -254,12 +320,13 @@ __device__ __forceinline__ void nms2_step(nms_rows &S, int j, const uint8_t *__r
         uint32_t w_lo = i16 < 8 ? nib_w << sh : 0u, w_hi = i16 < 8 ? 0u : nib_w << sh;
         s_lo = dpp_or_row(s_lo); s_hi = dpp_or_row(s_hi);
         w_lo = dpp_or_row(w_lo); w_hi = dpp_or_row(w_hi);
-        if (i16 == 15 && tx < ww) {
-            const int64_t o = bp_index(f, y, tx, ww, tiles_y);
-            strong[o] = (unsigned long long)s_lo | ((unsigned long long)s_hi << 32);
-            weak[o] = (unsigned long long)w_lo | ((unsigned long long)w_hi << 32);
-            n_strong += __popc(s_lo) + __popc(s_hi);
-            n_weak += __popc(w_lo) + __popc(w_hi);
+        // lane 16 q + 15 holds the row's words of tile q; lane (y - y0) captures them (transposed at the strip's end)
+        const unsigned long long sw = (unsigned long long)s_lo | ((unsigned long long)s_hi << 32);
+        const unsigned long long ww_ = (unsigned long long)w_lo | ((unsigned long long)w_hi << 32);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const unsigned long long a = __shfl(sw, 16 * q + 15, 64), b = __shfl(ww_, 16 * q + 15, 64);
+            if (lane == y - y0) { cap_s[q] = a; cap_w[q] = b; }
         }
     }
 }
@@ -276,8 +343,6 @@ __global__ __launch_bounds__(64) void k_canny_nms2(const uint8_t *__restrict__ g
     const int x0 = blockIdx.x * 256, y0 = blockIdx.y * 64;
     const int x = x0 + 4 * lane; // first of the lane's four pixels
     const uint8_t *g = gray + (int64_t)f * plane_stride;
-    const int tiles_y = (h + 63) >> 6;
-    const int tx = blockIdx.x * 4 + (lane >> 4);
     // pixels -1..4 of this lane that lie inside the image keep their magnitude, the others read 0
     s2 cmask[3];
 #pragma unroll
@@ -292,22 +357,17 @@ __global__ __launch_bounds__(64) void k_canny_nms2(const uint8_t *__restrict__ g
         for (int i = 0; i < 3; i++) {
             S.h1[r][i] = S.h2[r][i] = S.mag[r][i] = S.gx[r][i] = S.gy[r][i] = s2{0, 0};
         }
-    unsigned n_strong = 0, n_weak = 0;
+    unsigned long long cap_s[4] = {0, 0, 0, 0}, cap_w[4] = {0, 0, 0, 0}; // lane r <-> row r of the strip's four tiles
     const int rows_out = min(64, h - y0);
     const int steps = rows_out + 4;
     for (int j0 = 0; j0 < steps; j0 += 3) {
-        nms2_step<0>(S, j0, g, pitch, h, w, y0, x - 2, cmask, low, high, f, tx, ww, tiles_y, strong, weak, n_strong, n_weak);
+        nms2_step<0>(S, j0, g, pitch, h, w, y0, x - 2, cmask, low, high, cap_s, cap_w);
         if (j0 + 1 < steps)
-            nms2_step<1>(S, j0 + 1, g, pitch, h, w, y0, x - 2, cmask, low, high, f, tx, ww, tiles_y, strong, weak, n_strong, n_weak);
+            nms2_step<1>(S, j0 + 1, g, pitch, h, w, y0, x - 2, cmask, low, high, cap_s, cap_w);
         if (j0 + 2 < steps)
-            nms2_step<2>(S, j0 + 2, g, pitch, h, w, y0, x - 2, cmask, low, high, f, tx, ww, tiles_y, strong, weak, n_strong, n_weak);
+            nms2_step<2>(S, j0 + 2, g, pitch, h, w, y0, x - 2, cmask, low, high, cap_s, cap_w);
     }
-    n_strong = wave_sum(n_strong);
-    n_weak = wave_sum(n_weak);
-    if (lane == 0) {
-        if (n_strong) atomicAdd(&res[f].edge_strong, n_strong);
-        if (n_weak) atomicAdd(&res[f].edge_weak, n_weak);
-    }
+    lab_store_strip(cap_s, cap_w, f, blockIdx.x, blockIdx.y, h, w, strong, weak, res);
 }
 
 #endif // VQA_AB_VARIANTS
@@ -333,8 +393,9 @@ __global__ __launch_bounds__(64) void k_canny_nms2(const uint8_t *__restrict__ g
 //   * all compares between two consecutive rows are made once, when the lower row is new, and serve both rows
 //     (as "below" of the upper one, as "above" of the lower one): only TWO rows of magnitudes live in registers,
 //     the upper row's partial decisions wait in scalar registers as masks;
-//   * lane r captures row r's words (v_writelane), so after the strip every lane holds its row of the 4 tiles -
-//     the layout the hysteresis uses - and the bit-planes leave as 512-byte contiguous tile stores.
+//   * lane r captures row r's words (v_writelane), so after the strip every lane holds its row of the 4 tiles; the
+//     planes want one word per column, so the tiles are transposed in the wave (lab_store_strip) and leave as
+//     512-byte contiguous tile stores.
 // ---------------------------------------------------------------------------
 // |a - b| + c: the compiler selects v_sad_u32 for this shape.  NOT inline asm: the hazard recognizer does not see
 // an asm statement as a vector-ALU reader, so a v_sad_u32 written in asm right behind the v_dot4_u32_u8 that
@@ -524,7 +585,6 @@ __global__ __launch_bounds__(64) void k_canny_nms3(const uint8_t *__restrict__ g
     const int lane = lane_id();
     const int x0 = bx * 256, y0 = by * 64;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(gray + (int64_t)f * plane_stride), (short)0, -1, 0x00020000);
-    const int tiles_y = (h + 63) >> 6;
     // column of (group, lane); the halo group holds x0 - 1 in lane 63 and x0 + 256 in lane 0.  Every lane loads
     // the dword at clamp(x - 1, 0, w - 4); sel[] maps the replicated-border columns x-1, x, x+1 into that dword
     int off[5];
@@ -568,38 +628,25 @@ __global__ __launch_bounds__(64) void k_canny_nms3(const uint8_t *__restrict__ g
             if (j0 + 1 < steps) nms3_step<1, false>(S, j0 + 1, rs, pitch, h, y0, off, sel, cmask, colmask, low, high, lane0, lane63);
         }
     }
-    // ---- lane r holds row y0 + r of the four tiles: contiguous tile stores, strong / weak totals
-    unsigned n_strong = 0, n_weak = 0;
-    if (lane < rows_out) {
+    // ---- lane r holds row y0 + r of the four tiles: transposed into the planes' layout, stored, counted
+    u64 cap_s[4], cap_w[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int tx = bx * 4 + k;
-            if (tx < ww) {
-                const int64_t o = bp_index(f, y0 + lane, tx, ww, tiles_y);
-                const uint32_t s_lo = S.cs[k][0] & S.cw[k][0], s_hi = S.cs[k][1] & S.cw[k][1];
-                const uint32_t w_lo = S.cs[k][0] & ~S.cw[k][0], w_hi = S.cs[k][1] & ~S.cw[k][1];
-                strong[o] = (u64)s_lo | ((u64)s_hi << 32);
-                weak[o] = (u64)w_lo | ((u64)w_hi << 32);
-                n_strong += __popc(s_lo) + __popc(s_hi);
-                n_weak += __popc(w_lo) + __popc(w_hi);
-            }
-        }
+    for (int k = 0; k < 4; k++) {
+        const bool in = lane < rows_out;
+        const u64 cs = in ? ((u64)S.cs[k][0] | ((u64)S.cs[k][1] << 32)) & colmask[k] : 0ull;
+        const u64 cw = (u64)S.cw[k][0] | ((u64)S.cw[k][1] << 32);
+        cap_s[k] = cs & cw;
+        cap_w[k] = cs & ~cw;
     }
-    n_strong = wave_sum(n_strong);
-    n_weak = wave_sum(n_weak);
-    if (lane == 0) {
-        if (n_strong) atomicAdd(&res[f].edge_strong, n_strong);
-        if (n_weak) atomicAdd(&res[f].edge_weak, n_weak);
-    }
+    lab_store_strip(cap_s, cap_w, f, bx, by, h, w, strong, weak, res);
 }
 
 #endif // VQA_AB_VARIANTS
 
 // ---------------------------------------------------------------------------
-// Stage 1, pair-packed form (k_canny_nms4, the default).  The wave, the loads, the gradient and the captures are
+// Stage 1, pair-packed form (k_canny_nms4, the default).  The wave, the loads and the gradient are
 // k_canny_nms3's: a wave covers 256 columns x a 64-row strip, lane L owns the columns x0 + 64 k + L, one unaligned
-// dword per pixel requested a row ahead, |gx| and |gx| + |gy| as two sums of absolute differences, lane r captures
-// row r.  What changed is where the NMS decisions are taken.  nms3 turned every condition into a 64-bit mask at once (about 60 v_cmp per row) and ran the
+// dword per pixel requested a row ahead, |gx| and |gx| + |gy| as two sums of absolute differences.  What changed is where the NMS decisions are taken.  nms3 turned every condition into a 64-bit mask at once (about 60 v_cmp per row) and ran the
 // boolean logic on the scalar unit (about 140 scalar instructions per row), which kept the CU's one scalar unit and
 // the vector ALUs busy at the same time.  Here every quantity a decision reads fits 16 bits (m <= 2040, thresholds
 // <= 3482), so
@@ -616,11 +663,14 @@ __global__ __launch_bounds__(64) void k_canny_nms3(const uint8_t *__restrict__ g
 //     in bit 15: one packed subtract and one xor per pair;
 //   * the ring of horizontal neighbours moves packed registers (2 DPP moves per direction instead of 5); the seam lane
 //     needs halves of two registers, which the SENDING lane puts together with one v_perm whose selector is per lane;
-//   * only what leaves the loop becomes a mask: the kept pixels and the above-high pixels, two ballots per pair each.
-//     The scalar unit is left with the loop control, the clamped row offset and the lane select of the captures;
+//   * nothing becomes a mask: what leaves the loop, the kept pixels and the above-high pixels, is appended by each lane
+//     to the 16-row shift registers of its own columns (cap_row: 8 vector instructions per row, where ballots and
+//     v_writelane took 24).  The scalar unit is left with the loop control and the clamped row offset;
 //   * the loop is ONE basic block of four steps: rows outside the image are zeroed by a wave-uniform v_perm selector
-//     instead of a branch, captures are unconditional, h2 has a slot per row mod 4 (no register copies).
-// -S, interior loop, per 256-pixel row: 127 vector + 26 scalar instructions (nms3: 146 + 142), 109 VGPRs, no spills.
+//     instead of a branch, captures are unconditional, h2 has a slot per row mod 4 (no register copies); a strip is four
+//     such loops, one per group of 16 rows, each with its own capture registers (nms4_strip).
+// -S, interior loop, per 256-pixel row: 111 vector + 16.5 scalar instructions (before the per-column capture: 127 + 26;
+// nms3: 146 + 142), 122 VGPRs, no spills, no scratch.
 // A strip with at most two real tiles (1920 columns: every eighth strip) runs ONE pair (NP = 1): half the work.
 // ---------------------------------------------------------------------------
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -635,27 +685,20 @@ __device__ __forceinline__ uint32_t pk_gt(uint32_t a, uint32_t b) { return pk_su
 __device__ __forceinline__ uint32_t pack_lo(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x05040100u); }  // (lo & 0xffff) | (hi << 16)
 __device__ __forceinline__ uint32_t pack_hi(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }  // (lo >> 16) | (hi & 0xffff0000)
 
-// lane `lane` of (a0, a1) <- the words of ma, of (b0, b1) <- the words of mb: one M0 write per captured row and pair
-// (M0 is written and read inside one statement, see writelane2).  The s_nop keeps two wait states between a vector
-// compare that wrote one of the masks and the first v_writelane that reads it, whatever the compiler put in front.
-__device__ __forceinline__ void writelane4(uint32_t &a0, uint32_t &a1, uint32_t &b0, uint32_t &b1, int lane, u64 ma, u64 mb)
+// The captures.  A finished row's decisions are the sign bits of the two halves of a packed register, and they stay
+// there: every lane (= column) keeps a 16-row shift register per half.  One row = shift the pair down by one, then
+// take bits 15 and 31 from the truth register (v_lshrrev_b32 + v_bfi_b32: the bit the 32-bit shift carries from the
+// high half into bit 15 is the very bit the insert overwrites).  After 16 rows bit i of a half is row i of the group.
+struct nms4_cap {
+    uint32_t k[2], a[2]; // kept / above-high, per pair: low half = tile 2q, high half = tile 2q + 1
+};
+__device__ __forceinline__ uint32_t cap_row(uint32_t acc, uint32_t truth)
 {
-    asm volatile("s_mov_b32 m0, %4\n\ts_nop 0\n\tv_writelane_b32 %0, %5, m0\n\tv_writelane_b32 %1, %6, m0\n\t"
-                 "v_writelane_b32 %2, %7, m0\n\tv_writelane_b32 %3, %8, m0"
-                 : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1)
-                 : "s"(lane), "s"((uint32_t)ma), "s"((uint32_t)(ma >> 32)), "s"((uint32_t)mb), "s"((uint32_t)(mb >> 32))
-                 : "m0");
-}
-
-// the lanes whose LOW half has its sign bit set: one 16-bit compare.  In C++, "(short)v < 0" becomes a test of bit 15 and
-// costs a bit-field extract or a shift in front of a 32-bit compare.  The asm is safe where it stands: its operand comes
-// from a plain vector-ALU instruction (no DOT / transcendental result, see sad_u32), and its result is only read by
-// writelane4, which keeps its own wait states in front of the first reader
-__device__ __forceinline__ u64 ballot_lo(uint32_t v)
-{
-    u64 m;
-    asm("v_cmp_gt_i16_e64 %0, 0, %1" : "=s"(m) : "v"(v));
-    return m;
+    // (the empty asm makes each row's result opaque: left alone, the optimiser folds the four rows of a trip into one
+    // shift by 4 plus a tree of shifted and masked truth registers, three times the instructions)
+    uint32_t r = ((acc >> 1) & 0x7fff7fffu) | (truth & 0x80008000u);
+    asm("" : "+v"(r));
+    return r;
 }
 
 struct nms4_state {
@@ -669,7 +712,6 @@ struct nms4_state {
     uint32_t M[2][2], ML[2][2], MR[2][2]; // packed magnitudes of the previous mag row (slot PH^1) and the new one (PH)
     uint32_t HH[2], VV[2], DS[2], DO[2]; // decisions of the previous mag row that wait for the row below (sign bits)
     uint32_t ST[2];                      // "above high" of the previous mag row
-    uint32_t cs[4][2], cw[4][2];         // captured words: lane r <-> row r of the strip
     uint32_t pn[2][5];                   // gray bytes of the next step's row
 };
 
@@ -695,7 +737,7 @@ __device__ __forceinline__ void nms4_load(uint32_t (&p)[5], const __amdgpu_buffe
 template <int J4, bool EDGE, int NP>
 __device__ __forceinline__ void nms4_step(nms4_state &S, int j, const __amdgpu_buffer_rsrc_t rs, int pitch, int h, int y0,
                                           const int (&off)[5], const uint32_t (&sel)[5], const uint32_t (&cmask)[5],
-                                          uint32_t lowp, uint32_t highp, const nms4_ring &ring)
+                                          uint32_t lowp, uint32_t highp, const nms4_ring &ring, nms4_cap &C)
 {
     constexpr int NT = 2 * NP, PH = J4 & 1; // J4 = step mod 4, PH = its parity
     const int R = y0 - 2 + j;            // gray row loaded by this step
@@ -751,10 +793,9 @@ __device__ __forceinline__ void nms4_step(nms4_state &S, int j, const __amdgpu_b
             S.MR[PH][0] = wave_rol1(__builtin_amdgcn_perm(halo, Mn[0], ring.r));  // lane 0 sends (tile 1, halo)
         }
     }
-    // Lane yout captures the finished row: its kept pixels and its above-high pixels, which waited one step in ST so
-    // that both leave with one lane select.  The capture is unconditional: the steps before the strip's first row
-    // (yout < 0) write lane 0, which row 0 overwrites afterwards
-    const int yout = max(yy - 1 - y0, 0); // strip row finished by this step (wave-uniform)
+    // The row above (strip row j - 4) is finished here: its kept pixels and its above-high pixels, which waited one step
+    // in ST, go into the lane's shift registers.  The capture is unconditional: what the four steps before the strip's
+    // first row append has left the 16-bit registers again when the first group of 16 rows is complete
 #pragma unroll
     for (int q = 0; q < NP; q++) {
         const uint32_t m1 = S.M[PH][q], m1L = S.ML[PH][q], m1R = S.MR[PH][q];
@@ -765,10 +806,8 @@ __device__ __forceinline__ void nms4_step(nms4_state &S, int j, const __amdgpu_b
         keep |= S.DS[q] & pk_gt(m2, m1R);
         keep |= S.DO[q] & pk_gt(m2, m1L);
         const uint32_t st = S.ST[q];
-        writelane4(S.cs[2 * q][0], S.cs[2 * q][1], S.cs[2 * q + 1][0], S.cs[2 * q + 1][1], yout,
-                   ballot_lo(keep), __ballot((int)keep < 0));
-        writelane4(S.cw[2 * q][0], S.cw[2 * q][1], S.cw[2 * q + 1][0], S.cw[2 * q + 1][1], yout,
-                   ballot_lo(st), __ballot((int)st < 0));
+        C.k[q] = cap_row(C.k[q], keep);
+        C.a[q] = cap_row(C.a[q], st);
         // new row as the centre: candidates, direction sectors (exclusive: th1 <= th2), same-row and upward compares
         const uint32_t cand = pk_gt(m1, lowp);
         const uint32_t ch = pk_gt(TH1[q], m1), cv = pk_gt(m1, TH2[q]);
@@ -781,20 +820,37 @@ __device__ __forceinline__ void nms4_step(nms4_state &S, int j, const __amdgpu_b
     }
 }
 
+// steps j0 .. j1 - 1, four per trip (the state's slots go by the step mod 2 and mod 4), no exit between them
 template <bool EDGE, int NP>
-__device__ __forceinline__ void nms4_strip(nms4_state &S, int steps, const __amdgpu_buffer_rsrc_t rs, int pitch, int h, int y0,
-                                           const int (&off)[5], const uint32_t (&sel)[5], const uint32_t (&cmask)[5],
-                                           uint32_t lowp, uint32_t highp, const nms4_ring &ring)
+__device__ __forceinline__ void nms4_rows(nms4_state &S, nms4_cap &C, int j0, int j1, const __amdgpu_buffer_rsrc_t rs, int pitch,
+                                          int h, int y0, const int (&off)[5], const uint32_t (&sel)[5],
+                                          const uint32_t (&cmask)[5], uint32_t lowp, uint32_t highp, const nms4_ring &ring)
+{
+    for (int j = j0; j < j1; j += 4) {
+        nms4_step<0, EDGE, NP>(S, j, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring, C);
+        nms4_step<1, EDGE, NP>(S, j + 1, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring, C);
+        nms4_step<2, EDGE, NP>(S, j + 2, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring, C);
+        nms4_step<3, EDGE, NP>(S, j + 3, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring, C);
+    }
+}
+
+// Step j finishes strip row j - 4, so group g of 16 rows is complete after step 16 g + 19.  The group boundaries are
+// STATIC: one loop per group, each filling its own four capture registers, so there is neither a flush instruction nor
+// a branch inside a step (G[0] also swallows the four steps before row 0: they are shifted out again).  A group runs
+// whole or not at all: the steps beyond rows_out + 4 load clamped rows, and what they capture is masked off at the end.
+template <bool EDGE, int NP>
+__device__ __forceinline__ void nms4_strip(nms4_state &S, nms4_cap (&G)[4], int rows_out, const __amdgpu_buffer_rsrc_t rs, int pitch,
+                                           int h, int y0, const int (&off)[5], const uint32_t (&sel)[5],
+                                           const uint32_t (&cmask)[5], uint32_t lowp, uint32_t highp, const nms4_ring &ring)
 {
     nms4_load<NP>(S.pn[0], rs, off, y0 - 2, h, pitch);
-    // four steps per trip (the state's slots go by the step mod 2 and mod 4), no exit between them: the steps beyond
-    // rows_out + 4 load clamped rows and capture into lanes rows_out .. 63, which are not stored
-    for (int j0 = 0; j0 < steps; j0 += 4) {
-        nms4_step<0, EDGE, NP>(S, j0, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-        nms4_step<1, EDGE, NP>(S, j0 + 1, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-        nms4_step<2, EDGE, NP>(S, j0 + 2, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-        nms4_step<3, EDGE, NP>(S, j0 + 3, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-    }
+    nms4_rows<EDGE, NP>(S, G[0], 0, 20, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    if (rows_out <= 16) return;
+    nms4_rows<EDGE, NP>(S, G[1], 20, 36, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    if (rows_out <= 32) return;
+    nms4_rows<EDGE, NP>(S, G[2], 36, 52, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    if (rows_out <= 48) return;
+    nms4_rows<EDGE, NP>(S, G[3], 52, 68, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
 }
 
 // grid and XCD-contiguous strip placement as in k_canny_nms3: 8 * ceil(strips / 8) workgroups of one wave, XCD c takes
@@ -814,19 +870,16 @@ __global__ __launch_bounds__(64) void k_canny_nms4(const uint8_t *__restrict__ g
     const int lane = lane_id();
     const int x0 = bx * 256, y0 = by * 64;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(gray + (int64_t)f * plane_stride), (short)0, -1, 0x00020000);
-    const int tiles_y = (h + 63) >> 6;
     const bool one_pair = w - x0 <= 128; // wave-uniform: tiles 2 and 3 of this strip do not exist
     // column of (group, lane); the halo group holds x0 - 1 in lane 63 and the column right of the last tile in lane 0.
     // Every lane loads the dword at clamp(x - 1, 0, w - 4); sel[] maps the replicated-border columns x-1, x, x+1 into it
     int off[5];
     uint32_t sel[5], cmask[5];
-    u64 colmask[4];
 #pragma unroll
     for (int k = 0; k < 5; k++) {
         const int x = k < 4 ? x0 + 64 * k + lane : (lane == 63 ? x0 - 1 : x0 + (one_pair ? 128 : 256));
         const bool in = x >= 0 && x < w && (k < 4 || lane == 0 || lane == 63);
         cmask[k] = in ? ~0u : 0u;
-        if (k < 4) colmask[k] = __ballot(in);
         const int xc = min(max(x, -1), w); // columns beyond the border behave like the first one outside (magnitude 0 anyway)
         off[k] = min(max(xc - 1, 0), w - 4);
         uint32_t sl = 0x0c000000u;
@@ -844,8 +897,9 @@ __global__ __launch_bounds__(64) void k_canny_nms4(const uint8_t *__restrict__ g
         S.H2[0][q] = S.H2[1][q] = S.H2[2][q] = S.H2[3][q] = 0;
         S.HH[q] = S.VV[q] = S.DO[q] = S.DS[q] = S.ST[q] = 0;
     }
+    nms4_cap G[4]; // one set of shift registers per group of 16 rows
 #pragma unroll
-    for (int k = 0; k < 4; k++) S.cs[k][0] = S.cs[k][1] = S.cw[k][0] = S.cw[k][1] = 0;
+    for (int g = 0; g < 4; g++) G[g].k[0] = G[g].k[1] = G[g].a[0] = G[g].a[1] = 0;
     // m > threshold on halves: m is in [0, 2040], so a threshold outside [-1, 2040] acts like the nearer end (-1 = 0xffff:
     // 0xffff - m has its sign bit set for every m)
     const uint32_t lowp = (uint32_t)(min(max(low, -1), 2040) & 0xffff) * 0x10001u;
@@ -854,27 +908,37 @@ __global__ __launch_bounds__(64) void k_canny_nms4(const uint8_t *__restrict__ g
     const nms4_ring ring = {lane == 63 ? 0x05040100u : 0x07060504u, lane == 63 ? 0x05040302u : 0x07060504u,
                             lane == 0 ? 0x05040302u : 0x03020100u};
     const int rows_out = min(64, h - y0);
-    const int steps = rows_out + 4;
-    if (one_pair) nms4_strip<true, 1>(S, steps, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-    else if (edge) nms4_strip<true, 2>(S, steps, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-    else nms4_strip<false, 2>(S, steps, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
-    // ---- lane r holds row y0 + r of the four tiles: contiguous tile stores, strong / weak totals.  Columns outside the
-    // image have magnitude 0 and are candidates under a negative threshold: colmask drops them here
+    if (one_pair) nms4_strip<true, 1>(S, G, rows_out, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    else if (edge) nms4_strip<true, 2>(S, G, rows_out, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    else nms4_strip<false, 2>(S, G, rows_out, rs, pitch, h, y0, off, sel, cmask, lowp, highp, ring);
+    // ---- lane L holds the columns x0 + 64 k + L of the four tiles, 16 rows per register half: the halves of the four
+    // groups make the column's word (rows 0-31, rows 32-63), which is word L of the plane tile - 512 contiguous bytes
+    // per tile again.  Rows beyond the image were computed on clamped rows: masked off (wave-uniform).  Columns outside
+    // the image have magnitude 0 and are candidates under a negative threshold: their lanes store nothing
+    const u64 rowmask = rows_out >= 64 ? ~0ull : (1ull << rows_out) - 1ull;
+    const uint32_t rm_lo = (uint32_t)rowmask, rm_hi = (uint32_t)(rowmask >> 32);
     unsigned n_strong = 0, n_weak = 0;
-    if (lane < rows_out) {
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int tx = bx * 4 + k;
-            if (tx < ww) {
-                const int64_t o = bp_index(f, y0 + lane, tx, ww, tiles_y);
-                const uint32_t k_lo = S.cs[k][0] & (uint32_t)colmask[k], k_hi = S.cs[k][1] & (uint32_t)(colmask[k] >> 32);
-                const uint32_t s_lo = k_lo & S.cw[k][0], s_hi = k_hi & S.cw[k][1];
-                const uint32_t w_lo = k_lo & ~S.cw[k][0], w_hi = k_hi & ~S.cw[k][1];
-                strong[o] = (u64)s_lo | ((u64)s_hi << 32);
-                weak[o] = (u64)w_lo | ((u64)w_hi << 32);
-                n_strong += __popc(s_lo) + __popc(s_hi);
-                n_weak += __popc(w_lo) + __popc(w_hi);
-            }
+    for (int k = 0; k < 4; k++) {
+        const int q = k >> 1;
+        uint32_t k_lo, k_hi, a_lo, a_hi;
+        if (k & 1) {
+            k_lo = pack_hi(G[0].k[q], G[1].k[q]); k_hi = pack_hi(G[2].k[q], G[3].k[q]);
+            a_lo = pack_hi(G[0].a[q], G[1].a[q]); a_hi = pack_hi(G[2].a[q], G[3].a[q]);
+        } else {
+            k_lo = pack_lo(G[0].k[q], G[1].k[q]); k_hi = pack_lo(G[2].k[q], G[3].k[q]);
+            a_lo = pack_lo(G[0].a[q], G[1].a[q]); a_hi = pack_lo(G[2].a[q], G[3].a[q]);
+        }
+        k_lo &= rm_lo; k_hi &= rm_hi;
+        const int x = x0 + 64 * k + lane;
+        if (x < w) {
+            const int64_t o = bp_pixel_word(f, y0, x, h, w);
+            const uint32_t s_lo = k_lo & a_lo, s_hi = k_hi & a_hi;
+            const uint32_t w_lo = k_lo & ~a_lo, w_hi = k_hi & ~a_hi;
+            strong[o] = (u64)s_lo | ((u64)s_hi << 32);
+            weak[o] = (u64)w_lo | ((u64)w_hi << 32);
+            n_strong += __popc(s_lo) + __popc(s_hi);
+            n_weak += __popc(w_lo) + __popc(w_hi);
         }
     }
     n_strong = wave_sum(n_strong);
@@ -886,7 +950,8 @@ __global__ __launch_bounds__(64) void k_canny_nms4(const uint8_t *__restrict__ g
 }
 
 // ---------------------------------------------------------------------------
-// Hysteresis on bit-planes.  Tile = 64 columns x 64 rows = one wave; lane r <-> row r.
+// Hysteresis on bit-planes, in PLANE coordinates (the transposed frame: a plane row is a frame column).
+// Tile = 64 columns x 64 rows = one wave; lane r <-> row r.
 // ---------------------------------------------------------------------------
 
 __device__ __forceinline__ u64 shfl_up64(u64 v) { return __shfl_up(v, 1, 64); }
@@ -1312,8 +1377,7 @@ void launch_canny_nms(hipStream_t st, const uint8_t *gray, int pitch, int64_t pl
                            plane_stride, h, w, low, high, strong, weak, (w + 63) / 64, res);
 #endif
     } else {
-        const canny_geom g = canny_tiles(h, w);
-        hipLaunchKernelGGL(k_canny_nms, dim3(g.tiles_x, g.tiles_y, n), dim3(256), 0, st, gray, pitch, plane_stride, h, w,
+        hipLaunchKernelGGL(k_canny_nms, dim3((w + TW - 1) / TW, (h + TH - 1) / TH, n), dim3(256), 0, st, gray, pitch, plane_stride, h, w,
                            low, high, strong, weak, (w + 63) / 64, res);
     }
 }
@@ -1322,7 +1386,8 @@ static hyst_args make_hyst_args(unsigned long long *strong, const unsigned long 
                                 unsigned *queued, unsigned *out_list, unsigned *out_count, vqa_frame_metrics *res, int stats)
 {
     hyst_args A;
-    A.strong = strong; A.weak = weak; A.h = h; A.ww = (w + 63) / 64; A.tiles_y = (h + 63) / 64;
+    const canny_planes g = canny_plane_geom(h, w); // the planes hold the transposed frame
+    A.strong = strong; A.weak = weak; A.h = g.h; A.ww = g.ww; A.tiles_y = g.tiles_y;
     A.queued = queued; A.out_list = out_list; A.out_count = out_count; A.res = res;
     // 0 = dilation + carry flood (shipped); lab build, VQA_HYST_SUB=1..8: round 2's shift/and/or ladder with that many sub-steps
     static const int sub = [] { const int e = ab_knob("VQA_HYST_SUB", 0); return (e >= 1 && e <= 8) ? e : 0; }();
@@ -1377,8 +1442,8 @@ void launch_canny_hyst_tail(hipStream_t st, unsigned long long *strong, const un
 void launch_canny_finish(hipStream_t st, const unsigned long long *strong, int n, int h, int w, vqa_frame_metrics *res)
 {
     if (n <= 0) return;
-    const int ww = (w + 63) / 64, tiles_y = (h + 63) / 64;
-    hipLaunchKernelGGL(k_canny_count, dim3((tiles_y * ww + 31) / 32, n), dim3(256), 0, st, strong, h, ww, tiles_y, res);
+    const canny_planes g = canny_plane_geom(h, w);
+    hipLaunchKernelGGL(k_canny_count, dim3((g.tiles_y * g.ww + 31) / 32, n), dim3(256), 0, st, strong, g.h, g.ww, g.tiles_y, res);
 }
 
 } // namespace vqa

@@ -1350,7 +1350,7 @@ static int complexity_submit_body(vqa_ctx *c, const uint8_t *frames, const uint8
     c->last_has_state = false;
     if (want_e) {
         const int ww = (pw + 63) / 64;
-        const size_t words = (size_t)n * ((ph + 63) / 64) * ww * 64; // tile-major bit-planes
+        const size_t words = (size_t)n * ((ph + 63) / 64) * ww * 64; // tile-major bit-planes (of the transposed frame: the same count)
         const unsigned ntiles = canny_hyst_tiles(n, ph, pw);
         rc = ensure(c, c->state, sizeof(uint64_t) * words * 2); // strong plane, then weak plane
         if (rc) return rc;
@@ -3757,8 +3757,9 @@ int vqa_debug_read_plane(vqa_ctx *c, int which, int frame, uint8_t *dst, int dst
                             sizeof(uint64_t) * bits.size(), hipMemcpyDeviceToHost));
         for (int y = 0; y < h; y++)
             for (int x = 0; x < w; x++) {
-                const uint64_t wd = bits[(((size_t)(y >> 6) * ww + (x >> 6)) << 6) + (y & 63)];
-                dst[(size_t)y * w + x] = ((wd >> (x & 63)) & 1ull) ? 255 : 0;
+                // the planes hold the transposed frame, one word per column and 64 rows: unpacked into the row-major map
+                const uint64_t wd = bits[(size_t)canny_plane_word(h, w, y, x)];
+                dst[(size_t)y * w + x] = ((wd >> (y & 63)) & 1ull) ? 255 : 0;
             }
         return VQA_OK;
     } else {

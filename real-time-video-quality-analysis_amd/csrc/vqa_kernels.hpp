@@ -80,7 +80,9 @@ void launch_dct_full_fft(hipStream_t st, const uint8_t *planes, int pitch, int64
 struct canny_geom {
     int tiles_x, tiles_y;
 };
-canny_geom canny_tiles(int h, int w);
+canny_geom canny_tiles(int h, int w); // tiles of the bit-planes, which hold the TRANSPOSED frame (k_canny.hip)
+// word (inside one frame's plane) that holds pixel (y, x) of an h x w frame; the pixel is bit y & 63 of it
+int64_t canny_plane_word(int h, int w, int y, int x);
 void launch_canny_nms(hipStream_t st, const uint8_t *gray, int pitch, int64_t plane_stride, int n, int h, int w,
                       int low, int high, unsigned long long *strong, unsigned long long *weak,
                       vqa_frame_metrics *res);
