@@ -1693,8 +1693,8 @@ VQA_API int vqa_sigstats_wait(vqa_ctx *ctx, vqa_sigstats_metrics *out, int n_ent
  * The kernel has no atomics and no reduction: the same frame gives the same bytes at any place of any batch, from any memory.
  * Kernel: k_scale, one fused launch per group of planes alike on both sides; the intermediate of the horizontal pass lives in
  *   shared memory only.  The tables sit in device memory per (filter, in, out), cached like the other per-geometry tables.
- * Not built: swscale's bicubic (a = -0.6) and its other flags; left-sited (MPEG-2) chroma; conversion between chroma layouts or
- *   depths; scaling the reference; ratios beyond 1/4 .. 8.                                                                  */
+ * Not built: swscale's bicubic (a = -0.6) and its other flags; left-sited (MPEG-2) chroma; scaling the reference; ratios beyond
+ *   1/4 .. 8.  Conversion between chroma layouts or depths is vqa_convert_submit's.                                          */
 enum vqa_scale_filter {
     VQA_SCALE_BILINEAR = 0,
     VQA_SCALE_BICUBIC = 1,
@@ -1744,13 +1744,80 @@ VQA_API int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *x
  * Kernels (k_conform.hip): k_conform_copy - a lane a 16-byte granule of the destination, the source loaded as aligned 16-byte
  *   words and realigned in registers, the tables in LDS up to 12 bits; k_conform_gather - a lane a sample, for a pixel step that
  *   is neither contiguous nor interleaved alike on both sides; k_conform_matrix - a lane a 2 x 4 patch of source cells.
- * Not built: interpolation (sub-pixel shifts, chroma of an odd shift on a subsampled axis); conversion between layouts or
- *   depths; a matrix for other than three planes.                                                                            */
+ * Not built: interpolation (sub-pixel shifts, chroma of an odd shift on a subsampled axis); a matrix for other than three
+ *   planes.  Conversion between layouts or depths is vqa_convert_submit's.                                                   */
 VQA_API int vqa_conform_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n_in, int64_t frame_stride,
                                const vqa_plane_desc *src_planes, uint8_t *dst, int64_t dst_frame_stride,
                                const vqa_plane_desc *dst_planes, int n_planes, const int32_t *origin, const int32_t *index,
                                int n_out, const void *lut, const int64_t *matrix);
 VQA_API int vqa_conform_wait(vqa_ctx *ctx);
+
+/* ---- Convert: one stream written at another sample depth and / or chroma layout on the device - what an auto-inserted
+ * `format=` does in an FFmpeg graph, so a 10-bit 4:2:2 mezzanine is measured against its 8-bit 4:2:0 encode (or an 8-bit rung
+ * against a 10-bit master) with the distorted stream uploaded as it is ----
+ * Plane i of src_planes goes into plane i of dst_planes, each plane by itself.  Everything is integer arithmetic with ONE
+ * rounding per output sample.  Where this text differs from a tool's detail, this text is what is built.
+ * Planes: 1 to 4, the same count on both sides; one depth per list (8, or 9 .. 16 as little-endian uint16): ds on the source
+ *   side, dd on the destination side.  On both sides plane 0 is at least 16 x 16, the others at least 8 x 8, and h w <= 2^28:
+ *   VQA_ERR_UNSUPPORTED beyond.  Per plane and per axis, with n_s source and n_d destination samples, the relation is one of
+ *     same: n_d == n_s;    up: n_s == (n_d + 1) >> 1 (a 2x upsample: n_d is 2 n_s or 2 n_s - 1);    down: n_d == (n_s + 1) >> 1;
+ *   any other relation is VQA_ERR_UNSUPPORTED.  Plane 0 of the layouts this project builds is always `same`; the rule is per
+ *   plane, not per role.
+ * Taps, per axis; the weights sum to 4 and c(i) = min(max(i, 0), n_s - 1) replicates the edge:
+ *     relation     VQA_CHROMA_BOX                VQA_CHROMA_LINEAR, centre-sited    VQA_CHROMA_LINEAR, left-sited (horizontal only)
+ *     same         4 s[x]                        4 s[x]                             4 s[x]
+ *     up, x even   4 s[x>>1]                     3 s[x>>1] + s[c((x>>1) - 1)]       4 s[x>>1]
+ *     up, x odd    4 s[x>>1]                     3 s[x>>1] + s[c((x>>1) + 1)]       2 s[x>>1] + 2 s[c((x>>1) + 1)]
+ *     down         2 s[2x] + 2 s[c(2x + 1)]      the same                           s[c(2x - 1)] + 2 s[2x] + s[c(2x + 1)]
+ *   The vertical axis is always centre-sited (the MPEG-2 / H.264 default for 4:2:0); siting (VQA_SITING_CENTER,
+ *   VQA_SITING_LEFT) changes the horizontal axis of VQA_CHROMA_LINEAR only.  VQA_CHROMA_BOX is the convention the joint kinds
+ *   already use: chroma replicated on the way up, the mean of the cell's existing samples on the way down (conform's Ybar
+ *   rule).  The horizontal taps are applied first, then the vertical ones, with NO rounding in between: v is the exact integer
+ *   with denominator 16, v <= 16 * 65535.
+ * Depth and range, then the one rounding, in 64-bit arithmetic with Ps = 2^ds - 1, Pd = 2^dd - 1:
+ *   VQA_RANGE_LIMITED keeps the code's meaning by a power of two (16 becomes 64, 235 becomes 940):
+ *     dd >= ds: out = ((v << (dd - ds)) + 8) >> 4;      dd < ds: out = (v + (1 << (3 + ds - dd))) >> (4 + ds - dd);
+ *   VQA_RANGE_FULL rescales by the peaks: out = (2 v Pd + 16 Ps) / (32 Ps), an integer division: v Pd / (16 Ps) rounded half up.
+ *   Both are then clipped to Pd.  A source sample above Ps is read as it is; only the output is clipped.
+ * Consequences: equal formats give the identity; a flat plane stays flat at every level, 0 and the peak included; at an
+ *   unchanged layout ds -> dd -> ds with dd >= ds returns every code of the depth under both ranges; VQA_RANGE_FULL maps 0 to 0
+ *   and Ps to Pd.
+ * Pinned: the centre-sited linear taps equal torch's bilinear interpolation (scale 2, align_corners false) and the down taps
+ *   equal its 2 x 2 average pooling, both times 16, exactly; the rest by hand-computed answers and a NumPy restatement of this
+ *   text.  NOT pinned: FFmpeg's swscale is not matched - it dithers on the way down and uses other chroma filters - and no
+ *   FFmpeg binary was at hand to compare with.
+ * frames: host, pinned or device memory, what vqa_scale_submit takes; host frames are staged in a buffer of this kind's own.
+ *   n <= 32768, VQA_ERR_UNSUPPORTED beyond.  dst is device memory of the ctx's device and does not overlap the source frames,
+ *   else VQA_ERR_INVALID; an unknown chroma filter, siting or range is VQA_ERR_INVALID.  The bytes of dst that no destination
+ *   sample covers (row, plane and frame padding) are never written.
+ * A convert batch has conform's slot semantics exactly: a batch of its own with no result words, asynchronous on the ctx's
+ *   stream, VQA_ERR_STATE while one is pending, in flight next to every other kind; a failed submit leaves nothing in flight;
+ *   every later submit of any kind on the SAME ctx reads dst after it is written - no wait is needed in between;
+ *   vqa_convert_wait is needed only before another ctx or the host reads dst.
+ * No atomics, no reduction: a frame gives the same bytes at any place of any batch, from any memory.  It takes no kernel id
+ *   (like vqa_conform_submit): an added entry point, not a layout change, VQA_ABI_VERSION stays.
+ * Kernels (k_convert.hip): k_convert_rows - a pixel step equal to the sample size on both sides: a lane owns a 16-byte granule of
+ *   the destination's address (in both destination rows fed by the same source rows where the vertical relation is up and the
+ *   rows share a phase), the source loaded as aligned 16-byte words and realigned in registers, the ends of a row written
+ *   sample by sample; k_convert_gather - the same function, a lane a sample, for any other pixel step.
+ * Not built: packed bgr24 to or from planar YUV (a colour-matrix question); mono to or from three planes; dither; swscale's
+ *   filters; chroma ratios other than 1 and 2; converting the reference of a pass; the pair-reading pre-passes on a mixed pair. */
+enum vqa_convert_chroma {
+    VQA_CHROMA_BOX = 0,
+    VQA_CHROMA_LINEAR = 1
+};
+enum vqa_convert_siting {
+    VQA_SITING_CENTER = 0,
+    VQA_SITING_LEFT = 1
+};
+enum vqa_convert_range {
+    VQA_RANGE_LIMITED = 0,
+    VQA_RANGE_FULL = 1
+};
+VQA_API int vqa_convert_submit(vqa_ctx *ctx, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride,
+                               const vqa_plane_desc *src_planes, uint8_t *dst, int64_t dst_frame_stride,
+                               const vqa_plane_desc *dst_planes, int n_planes, int chroma, int siting, int range);
+VQA_API int vqa_convert_wait(vqa_ctx *ctx);
 
 /* ---- Temporal alignment: is the distorted stream the same frames as the reference, in the same places? ----
  * Every full-reference kind above compares reference frame i with distorted frame i and trusts the caller that they belong

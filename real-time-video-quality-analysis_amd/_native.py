@@ -159,6 +159,11 @@ COLORFIT_TABLE_POSITIONS = 1 << 31   # n h w of a submit with tables
 CONFORM_MIN_DIM = 16          # vqa_conform_submit: plane 0 of the destination (the other planes: 8, the chroma of 4:2:0)
 CONFORM_MAX_OUT = 32768       # vqa_conform_submit: the output frames of one submit
 CONFORM_MAX_COEF, CONFORM_MAX_BIAS = 1 << 20, 1 << 33   # |M[k][i]|, i < 3, and |M[k][3]| of its matrix (2^-16 fixed point)
+CONVERT_MIN_DIM = 16          # vqa_convert_submit: plane 0 of both sides (the other planes: 8, the chroma of 4:2:0)
+CONVERT_MAX_FRAMES = 32768    # vqa_convert_submit: the frames of one submit
+CHROMA_BOX, CHROMA_LINEAR = 0, 1       # vqa_convert_submit's chroma filters
+SITING_CENTER, SITING_LEFT = 0, 1      # its horizontal sitings (LINEAR only)
+RANGE_LIMITED, RANGE_FULL = 0, 1       # its ranges
 PU21_MIN_DIM = 16  # vqa_pu21_submit: the luma grid's limit (the chroma planes of 4:2:0 may be 8 x 8)
 PU21_FIX = 1 << 16       # vqa_pu21_metrics: q = rint(V 2^16)
 PU21_SSIM_FIX = 1 << 24  # vqa_pu21_metrics: u = rint(ssim 2^24)
@@ -428,6 +433,9 @@ SIGNATURES = {
                                      C.POINTER(VqaPlaneDesc), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                      C.c_void_p, C.POINTER(C.c_int64)]),
     "vqa_conform_wait": (C.c_int, [C.c_void_p]),
+    "vqa_convert_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_void_p, C.c_int64,
+                                     C.POINTER(VqaPlaneDesc), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vqa_convert_wait": (C.c_int, [C.c_void_p]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

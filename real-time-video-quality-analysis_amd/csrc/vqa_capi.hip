@@ -85,6 +85,7 @@ enum batch_kind {
                       // of the ctx (colorfit_table_words)
     KIND_CONFORM,     // no result words: the batch writes the caller's dst; work: host frames staged (0), the frame index and the
                       // tables on the device (1); the pinned copy holds what (1) is filled from
+    KIND_CONVERT,     // no result words: the batch writes the caller's dst; work: host frames staged (0)
     KIND_COUNT
 };
 
@@ -3261,6 +3262,89 @@ int vqa_conform_wait(vqa_ctx *c)
 {
     if (!c) return VQA_ERR_INVALID;
     batch_slot &s = c->slot[KIND_CONFORM];
+    if (!s.entries) return VQA_ERR_STATE;
+    if (int rc = wait_synced(c)) return rc;
+    s.entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Convert: one stream at another sample depth and / or chroma layout, into the caller's device memory.  A batch of its own with
+// no result words and conform's slot semantics.  Host frames are staged in the slot's own work buffer (vqa_trim releases it with
+// the slot).
+static int convert_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t fs, const vqa_plane_desc *planes,
+                               uint8_t *dst, int64_t dst_fs, const vqa_plane_desc *dplanes, int n_planes, int chroma, int siting,
+                               int range, bool &touched)
+{
+    if (bad_batch_args(c, frames, dst, mem_kind, n, planes, n_planes) || !dplanes) return VQA_ERR_INVALID;
+    if ((chroma != VQA_CHROMA_BOX && chroma != VQA_CHROMA_LINEAR) || (siting != VQA_SITING_CENTER && siting != VQA_SITING_LEFT) ||
+        (range != VQA_RANGE_LIMITED && range != VQA_RANGE_FULL))
+        return VQA_ERR_INVALID;
+    if (n > CONVERT_MAX_FRAMES) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_CONVERT];
+    plane_batch B, D;
+    auto src_limits = [=](const vqa_plane_desc &d) { return side_and_area_limits(d, &d == planes ? CONVERT_MIN_DIM : CONVERT_MIN_DIM / 2); };
+    auto dst_limits = [=](const vqa_plane_desc &d) { return side_and_area_limits(d, &d == dplanes ? CONVERT_MIN_DIM : CONVERT_MIN_DIM / 2); };
+    int rc = check_batch(s, n, fs, fs, planes, n_planes, B, src_limits);
+    if (rc) return rc;
+    if ((rc = check_planes(dplanes, n_planes, D, dst_limits))) return rc;
+    for (int p = 0; p < n_planes; p++)
+        if (convert_relation_of(planes[p].width, dplanes[p].width) < 0 || convert_relation_of(planes[p].height, dplanes[p].height) < 0)
+            return VQA_ERR_UNSUPPORTED;
+    if (n > 1 && dst_fs < D.span) return VQA_ERR_INVALID;
+    const int64_t dst_bytes = (int64_t)(n - 1) * dst_fs + D.span, src_bytes = (int64_t)(n - 1) * fs + B.span;
+    if (!byte_is_on_device(c, dst) || !byte_is_on_device(c, dst + (dst_bytes - 1))) return VQA_ERR_INVALID;
+    if (mem_kind == VQA_MEM_DEVICE && (uintptr_t)frames < (uintptr_t)dst + (uint64_t)dst_bytes &&
+        (uintptr_t)dst < (uintptr_t)frames + (uint64_t)src_bytes)
+        return VQA_ERR_INVALID;
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &s.work[0]}))) return rc;
+
+    convert_job job;
+    memset(&job, 0, sizeof job);
+    job.src = frames; job.dst = dst;
+    job.src_fs = fs; job.dst_fs = dst_fs;
+    job.chroma = chroma; job.siting = siting; job.range = range;
+    job.ds = B.depth; job.dd = D.depth;
+    job.inv_ps = 1.0f / (float)((1 << B.depth) - 1);
+    // four launches at most: the planes the rows kernel can take (a contiguous pixel step on both sides), one launch per
+    // horizontal relation, then the others by the gather.  16-bit samples at odd addresses would straddle a granule's dwords: the
+    // gather takes them.
+    const bool odd = (B.bps == 2 && (((uintptr_t)frames | (uintptr_t)fs) & 1)) || (D.bps == 2 && (((uintptr_t)dst | (uintptr_t)dst_fs) & 1));
+    convert_job group[4] = {job, job, job, job};   // same, up, down; the gather
+    int count[4] = {0, 0, 0, 0};
+    for (int p = 0; p < n_planes; p++) {
+        const vqa_plane_desc &a = planes[p], &b = dplanes[p];
+        convert_plane P;
+        P.src_off = a.offset; P.dst_off = b.offset;
+        P.src_rs = a.row_stride; P.dst_rs = b.row_stride;
+        P.src_step = a.pixel_step; P.dst_step = b.pixel_step;
+        P.sw = a.width; P.sh = a.height; P.dw = b.width; P.dh = b.height;
+        P.rx = convert_relation_of(a.width, b.width); P.ry = convert_relation_of(a.height, b.height);
+        const bool rows = !odd && a.pixel_step == B.bps && b.pixel_step == D.bps;
+        P.pair = rows && P.ry == CONVERT_UP && b.row_stride % 16 == 0;
+        const int g = rows ? P.rx : 3;
+        group[g].plane[count[g]++] = P;
+    }
+    for (int g = 0; g < 4; g++) launch_convert(c->stream, group[g], n, count[g], g, g == 3);
+    HIPCHK(c, hipGetLastError());
+    record_batch(s, n, dplanes, n_planes, D.depth);
+    return VQA_OK;
+}
+
+int vqa_convert_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n, int64_t frame_stride, const vqa_plane_desc *src_planes,
+                       uint8_t *dst, int64_t dst_frame_stride, const vqa_plane_desc *dst_planes, int n_planes, int chroma, int siting,
+                       int range)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return convert_submit_body(c, frames, mem_kind, n, frame_stride, src_planes, dst, dst_frame_stride, dst_planes, n_planes,
+                                   chroma, siting, range, touched);
+    });
+}
+
+int vqa_convert_wait(vqa_ctx *c)
+{
+    if (!c) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_CONVERT];
     if (!s.entries) return VQA_ERR_STATE;
     if (int rc = wait_synced(c)) return rc;
     s.entries = 0;

@@ -684,6 +684,40 @@ void launch_conform_copy(hipStream_t st, const conform_job &job, int n_out, int 
 // n_out frames of three planes taken together, the job's m applied after its table; sh x sw, ch x cw: the SOURCE planes' sizes
 void launch_conform_matrix(hipStream_t st, const conform_job &job, int sh, int sw, int ch, int cw, int n_out, int depth);
 
+// Convert (vqa_convert_submit): k_convert.hip
+constexpr int CONVERT_MIN_DIM = 16;         // the limit of plane 0 on both sides (the other planes: 8, the chroma of 4:2:0)
+constexpr int CONVERT_MAX_FRAMES = 32768;   // frames of one submit (they ride in gridDim.y)
+enum convert_relation { CONVERT_SAME = 0, CONVERT_UP = 1, CONVERT_DOWN = 2 };
+// the relation of one axis by include/vqa.h's rule, or -1 where there is none
+inline int convert_relation_of(int n_s, int n_d)
+{
+    if (n_d == n_s) return CONVERT_SAME;
+    if (n_s == (n_d + 1) >> 1) return CONVERT_UP;
+    if (n_d == (n_s + 1) >> 1) return CONVERT_DOWN;
+    return -1;
+}
+// one plane of a job: both sides' sizes and addressing in bytes, the relation per axis.  pair: the vertical relation is UP and
+// the destination's row stride is a multiple of 16, so a lane of k_convert_rows takes its granule in the two destination rows
+// that the same two source rows feed
+struct convert_plane {
+    int64_t src_off, dst_off, src_rs, dst_rs;
+    int src_step, dst_step;
+    int sw, sh, dw, dh;
+    int rx, ry, pair;
+};
+struct convert_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t src_fs, dst_fs;
+    convert_plane plane[4];
+    int chroma, siting, range;         // vqa_convert_chroma, vqa_convert_siting, vqa_convert_range
+    int ds, dd;                        // the two depths
+    float inv_ps;                      // VQA_RANGE_FULL: 1 / Ps, the first guess of the one division
+};
+// n frames of the job's first `count` planes.  gather false: k_convert_rows, the planes have a contiguous pixel step on both
+// sides and share ONE horizontal relation `rx`; gather true: k_convert_gather, a lane a sample, any pixel step and relation
+void launch_convert(hipStream_t st, const convert_job &job, int n, int count, int rx, bool gather);
+
 // Temporal alignment (vqa_align_submit): k_align.hip
 constexpr int ALIGN_MAX_DIST = 32768, ALIGN_MAX_REF = 32768 + 64;   // frames of one submit
 // One launch for the whole band of the whole submit: adds C[j][i] = sum X_d,j X_r,i into cross[j * (2 radius + 1) + c] for the pairs

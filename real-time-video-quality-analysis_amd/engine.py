@@ -235,7 +235,7 @@ def check_scale_planes(planes, out_planes):
     if not 1 <= len(planes) <= 4 or len(planes) != len(out_planes):
         raise ValueError("scale needs one to four planes and as many on both sides (got %d and %d)" % (len(planes), len(out_planes)))
     if planes_depth(planes) != planes_depth(out_planes):
-        raise ValueError("scale keeps the sample depth (got %d and %d bits): converting depths is not built"
+        raise ValueError("scale keeps the sample depth (got %d and %d bits): converting depths is Engine.convert's"
                          % (planes_depth(planes), planes_depth(out_planes)))
     for p in list(planes) + list(out_planes):
         w, h = int(p[0]), int(p[1])
@@ -257,7 +257,7 @@ def check_conform_args(planes, out_planes, origin=None, index=None, lut=None, ma
         raise ValueError("conform needs one to four planes and as many on both sides (got %d and %d)" % (len(planes), len(out_planes)))
     depth = planes_depth(planes)
     if depth != planes_depth(out_planes):
-        raise ValueError("conform keeps the sample depth (got %d and %d bits): converting depths is not built"
+        raise ValueError("conform keeps the sample depth (got %d and %d bits): converting depths is Engine.convert's"
                          % (depth, planes_depth(out_planes)))
     for i, q in enumerate(out_planes):
         w, h, least = int(q[0]), int(q[1]), N.CONFORM_MIN_DIM if i == 0 else N.CONFORM_MIN_DIM // 2
@@ -298,6 +298,53 @@ def check_conform_args(planes, out_planes, origin=None, index=None, lut=None, ma
         if int(np.abs(matrix[:, :3]).max()) > N.CONFORM_MAX_COEF or int(np.abs(matrix[:, 3]).max()) > N.CONFORM_MAX_BIAS:
             raise ValueError("matrix coefficients are bounded by 2^20 and its offsets by 2^33 (2^-16 fixed point)")
     return origin, index, lut, matrix
+
+
+CONVERT_CHROMA = ("box", "linear")      # vqa_convert_submit's chroma filters, by id
+CONVERT_SITING = ("center", "left")     # its horizontal sitings
+CONVERT_RANGE = ("limited", "full")     # its ranges
+
+
+def convert_options(chroma="linear", siting="center", range="limited"):
+    """the three options of convert by name -> their ids (N.CHROMA_*, N.SITING_*, N.RANGE_*); a ValueError for anything else"""
+    ids = []
+    for what, names, v in (("chroma", CONVERT_CHROMA, chroma), ("siting", CONVERT_SITING, siting), ("range", CONVERT_RANGE, range)):
+        if not isinstance(v, str) or v not in names:
+            raise ValueError("convert %s must be one of %s (got %r)" % (what, ", ".join(repr(k) for k in names), v))
+        ids.append(names.index(v))
+    return tuple(ids)
+
+
+def convert_relation(n_s, n_d):
+    """the relation of one axis by include/vqa.h's rule: "same" | "up" | "down", or None where there is none"""
+    n_s, n_d = int(n_s), int(n_d)
+    if n_d == n_s:
+        return "same"
+    if n_s == (n_d + 1) >> 1:
+        return "up"
+    if n_d == (n_s + 1) >> 1:
+        return "down"
+    return None
+
+
+def check_convert_planes(planes, out_planes):
+    """vqa_convert_submit's rules for the two plane lists, as a ValueError before anything is uploaded: one to four planes and
+    as many on both sides, one depth per list, plane 0 of both at least 16 x 16 and the others at least 8 x 8 with h w <= 2^28,
+    per plane and axis the same size, twice (2 n or 2 n - 1) or half (rounded up) of it.  Needs no GPU."""
+    if not 1 <= len(planes) <= 4 or len(planes) != len(out_planes):
+        raise ValueError("convert needs one to four planes and as many on both sides (got %d and %d)" % (len(planes), len(out_planes)))
+    planes_depth(planes), planes_depth(out_planes)
+    for side, lst in (("source", planes), ("destination", out_planes)):
+        for i, q in enumerate(lst):
+            w, h, least = int(q[0]), int(q[1]), N.CONVERT_MIN_DIM if i == 0 else N.CONVERT_MIN_DIM // 2
+            if w < least or h < least or w * h > N.SCALE_MAX_SAMPLES:
+                raise ValueError("convert needs planes of at least %d x %d and at most 2^28 samples (%s plane %d: %dx%d)"
+                                 % (least, least, side, i, w, h))
+    for i, (a, b) in enumerate(zip(planes, out_planes)):
+        for axis, n_s, n_d in (("width", a[0], b[0]), ("height", a[1], b[1])):
+            if convert_relation(n_s, n_d) is None:
+                raise ValueError("convert takes a plane to the same size, twice or half of it per axis (plane %d %s: %d -> %d): "
+                                 "chroma ratios other than 1 and 2 are not built" % (i, axis, int(n_s), int(n_d)))
 
 
 def scale_tables(filter, n_in, n_out):
@@ -520,7 +567,7 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf", "_pending_cm"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf", "_pending_cm", "_pending_cv"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
@@ -528,7 +575,7 @@ class Engine:
                      "_pending_l": self.align_wait, "_pending_j": self.shift_wait,
                      "_pending_o": self.light_wait, "_pending_sg": self.signature_wait,
                      "_pending_sx": self.sig_cross_wait, "_pending_cf": self.colorfit_wait,
-                     "_pending_cm": self.conform_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_cm": self.conform_wait, "_pending_cv": self.convert_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1343,6 +1390,64 @@ class Engine:
         """conform_submit and conform_wait -> the DeviceFrames of the conformed stream."""
         res = self.conform_submit(frames, planes, out_planes, origin, index, lut, matrix, out, frame_bytes, out_frame_bytes)
         self.conform_wait()
+        return res
+
+    # ---- convert: another sample depth and / or chroma layout ----------------------------------
+    def convert_submit(self, frames, planes, out_planes, chroma="linear", siting="center", range="limited", out=None,
+                       frame_bytes=None, out_frame_bytes=None):
+        """n frames of ONE stream written at another sample depth and / or chroma layout on the device (vqa_convert_submit):
+        plane i of `planes` into plane i of `out_planes`, per axis the same size, twice or half of it (include/vqa.h), integer
+        arithmetic with one rounding.  chroma "box" | "linear", siting "center" | "left" (the horizontal axis of "linear"),
+        range "limited" | "full".  frames: an array / DeviceFrames as scale_submit takes them (a sample type that does not
+        match the depth of `planes` is a ValueError, never a cast).  out / out_frame_bytes: as for scale_submit, at the sample
+        type of out_planes.  -> the DeviceFrames of the converted stream, which every submit of THIS engine accepts with
+        out_planes at once; convert_wait is needed only before another engine or the host reads them.  A batch of its own,
+        like conform_submit."""
+        ids = convert_options(chroma, siting, range)
+        check_convert_planes(planes, out_planes)
+        fp, kind, n, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
+        if not 1 <= n <= N.CONVERT_MAX_FRAMES:
+            raise ValueError("a convert submit takes 1 .. %d frames (got %d)" % (N.CONVERT_MAX_FRAMES, n))
+        itemsize = 2 if planes_depth(out_planes) > 8 else 1
+        span = planes_span(out_planes)
+        if out is None:
+            ofs = int(out_frame_bytes) if out_frame_bytes else span
+            if ofs < span:
+                raise ValueError("out_frame_bytes (%d) is smaller than a frame of out_planes (%d)" % (ofs, span))
+            buf = DeviceBuffer(self, n * ofs)
+            out = DeviceFrames(buf.ptr, n, 1, ofs // itemsize, frame_stride=ofs, owner=buf, channels=1, itemsize=itemsize)
+        else:
+            if not isinstance(out, DeviceFrames):
+                raise TypeError("out must be DeviceFrames (device memory)")
+            if out.itemsize != itemsize:
+                raise ValueError("%d-bit planes need an out of %s samples (got DeviceFrames of itemsize %d)"
+                                 % (planes_depth(out_planes), "uint16" if itemsize == 2 else "uint8", out.itemsize))
+            if out.n < n:
+                raise ValueError("out holds %d frames, the batch has %d" % (out.n, n))
+            ofs = int(out_frame_bytes) if out_frame_bytes else out.frame_stride
+            if ofs < span:
+                raise ValueError("a frame of out (%d bytes) is smaller than a frame of out_planes (%d)" % (ofs, span))
+            if out.n != n or ofs != out.frame_stride:
+                out = DeviceFrames(out.ptr, n, out.h, out.w, ofs, out.row_stride, owner=out, channels=out.channels,
+                                   itemsize=itemsize)
+        st = self.lib.vqa_convert_submit(self.ctx, fp, kind, n, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes),
+                                         len(planes), *ids)
+        N.check(st, "vqa_convert_submit", self.ctx)
+        self._pending_cv = (n, (keep, out))
+        return out
+
+    def convert_wait(self):
+        """Wait for the pending convert batch: the converted frames are complete (another engine, or a copy to the host, may
+        read them)."""
+        st = self.lib.vqa_convert_wait(self.ctx)
+        self._pending_cv = None
+        N.check(st, "vqa_convert_wait", self.ctx)
+
+    def convert(self, frames, planes, out_planes, chroma="linear", siting="center", range="limited", out=None, frame_bytes=None,
+                out_frame_bytes=None):
+        """convert_submit and convert_wait -> the DeviceFrames of the converted stream."""
+        res = self.convert_submit(frames, planes, out_planes, chroma, siting, range, out, frame_bytes, out_frame_bytes)
+        self.convert_wait()
         return res
 
     # ---- temporal alignment ------------------------------------------------------------

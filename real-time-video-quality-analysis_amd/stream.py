@@ -36,7 +36,8 @@ from . import _native as N
 from . import tails
 from .engine import (ADM_DTYPE, ARTIFACTS_DTYPE, BRISQUE_DTYPE, CAMBI_DTYPE, CIEDE_DTYPE, FSIM_DTYPE, GMSD_DTYPE, HAARPSI_DTYPE,
                      ITP_DTYPE, MDSI_DTYPE, MOTION_DTYPE, PSNR_HVS_DTYPE, PU21_DTYPE, SIGSTATS_DTYPE, SITI_DTYPE, VCA_DTYPE, VIF_DTYPE,
-                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_conform_args, check_scale_planes, check_vca_planes, check_xpsnr_planes,
+                     XPSNR_DTYPE, DeviceBuffer, DeviceFrames, Engine, check_conform_args, check_convert_planes, check_scale_planes,
+                     convert_options, check_vca_planes, check_xpsnr_planes,
                      planes_depth, planes_span, scale_filter, vca_grid)
 from .pooling import shard_range
 
@@ -506,16 +507,38 @@ def records_by_kind(q, quality):
     return out
 
 
+def _mid_planes(planes, dist_planes):
+    """What convert writes ahead of scale: tightly packed planes of the reference's depth and chroma layout (`planes`) at the
+    rung's size (plane 0 of dist_planes) - a plane that has plane 0's size along an axis keeps it, one that has its ceil-half
+    gets the rung's ceil-half."""
+    depth = planes_depth(planes)
+    bps = 2 if depth > 8 else 1
+    w0, h0, dw0, dh0 = int(planes[0][0]), int(planes[0][1]), int(dist_planes[0][0]), int(dist_planes[0][1])
+    out, off = [], 0
+    for p in planes:
+        size = []
+        for n, n0, d0 in ((int(p[0]), w0, dw0), (int(p[1]), h0, dh0)):
+            if n != n0 and n != (n0 + 1) >> 1:
+                raise ValueError("convert with scale needs planes of the first plane's size or its half per axis (got %d of %d)"
+                                 % (n, n0))
+            size.append(d0 if n == n0 else (d0 + 1) >> 1)
+        out.append((size[0], size[1], off, size[0] * bps, bps, depth))
+        off += size[0] * size[1] * bps
+    return out
+
+
 class Quality:
     """What the quality half compares: `planes` of every frame (engine.bgr_planes / yuv420p_planes ...)."""
 
     conform = conform_args = None   # the plan a conformed pass applies and its checked arrays (set by __init__ when given)
+    convert = mid_planes = None     # a converting pass's (chroma, siting, range) and what convert writes (set by __init__ when given)
 
     def __init__(self, planes, ssim_mode=N.SSIM_GAUSS, scales=False, vif=False, adm=False, motion=False, siti=False,
                  psnr_hvs=False, ciede=False, ciede_weights=N.CIEDE_WEIGHTS_CIE, gmsd=False, cambi=False, xpsnr=False,
                  haarpsi=False, vca=False, vca_blocks=False, artifacts=False, brisque=False, mdsi=False, itp=False,
                  itp_transfer="pq", itp_full_range=False, pu21=False, pu21_transfer="pq", pu21_full_range=False, fsim=False,
-                 sigstats=False, sigstats_black=None, sigstats_crop=None, dist_planes=None, scale=None, conform=None):
+                 sigstats=False, sigstats_black=None, sigstats_crop=None, dist_planes=None, scale=None, conform=None,
+                 convert=None):
         """scales (N.SSIM_MS only): the pass also returns the per-scale means, cs [n,p,5] and ssim [n,p,5]
         Every other switch turns on one plane-batch kind (PLANE_KINDS) and is False, True or "only":
         True    every chunk also goes through the kind's kernels (Engine.<kind>_submit) from the SAME upload - the chunk was
@@ -574,16 +597,40 @@ class Quality:
                 reads ref, dist or the pair sees the registered streams, the halo frame of the reference included.  Time is
                 not the pass's business: a constant offset is applied by the feeds the caller hands over (slices of the
                 streams), a per-frame path is Engine.conform's.  Allowed where scale is (the quality half's distorted stream
-                is a feed of its own) and never together with it."""
+                is a feed of its own) and never together with it.
+        convert: None, or (chroma, siting, range) - "box" | "linear", "center" | "left", "limited" | "full": the distorted
+                stream of the quality half has its OWN sample depth and / or chroma layout, which dist_planes describes (a
+                10-bit 4:2:2 mezzanine against its 8-bit 4:2:0 encode).  Every chunk of the distorted feed is uploaded at its
+                own sample type and layout and converted on the engine that measures it (Engine.convert_submit, include/vqa.h)
+                into a lane buffer of the reference's frame size.  dist_planes then goes with scale, with convert or with both;
+                with both convert runs first, to the reference's depth and chroma layout at the rung's size (mid_planes), and
+                the resampler follows on the same lane - the 8-bit rung against the 10-bit master.  Every kind that reads
+                "pair" or "dist" sees the converted frames, kinds that read "ref" are untouched.  Allowed where scale is;
+                with conform it is a ValueError.  Nothing is converted unless it is named."""
         given = dict(locals())   # the keyword arguments by name, for the table
-        if (dist_planes is None) != (scale is None):
+        if convert is not None and dist_planes is None:
+            raise ValueError("convert needs dist_planes: the distorted stream's own planes, at its own depth and chroma layout")
+        if (dist_planes is None) != (scale is None) and convert is None:
             raise ValueError("dist_planes and scale go together: the distorted stream's own planes AND the filter that brings "
                              "them to the reference's size (got %s without %s)"
                              % (("dist_planes", "scale") if scale is None else ("scale", "dist_planes")))
+        if convert is not None:
+            if conform is not None:
+                raise ValueError("convert and conform do not go together: the registration is found and applied on a pair of one "
+                                 "pixel layout")
+            convert = tuple(convert)
+            if len(convert) != 3:
+                raise ValueError("convert is a (chroma, siting, range) tuple")
+            convert_options(*convert)
+            # with scale: first to the reference's depth and chroma layout at the rung's size, then the resampler
+            self.mid_planes = _mid_planes(planes, dist_planes) if scale is not None else planes
+            check_convert_planes(dist_planes, self.mid_planes)
         if scale is not None:
             scale_filter(scale)
-            check_scale_planes(dist_planes, planes)
+            check_scale_planes(dist_planes if convert is None else self.mid_planes, planes)
         self.dist_planes, self.scale = dist_planes, scale
+        if convert is not None:
+            self.convert = convert
         if conform is not None:
             if scale is not None:
                 raise ValueError("conform and scale do not go together: a ladder rung is not registered at its own size")
@@ -716,6 +763,9 @@ def run(dist, ref=None, quality=None, complexity=None, batch_size=100, engine=No
     if want_q and quality.scale is not None and want_c and not split:
         raise ValueError("scaling needs a distorted stream of the quality half's own: in a combined pass one BGR stream serves "
                          "both halves at one size (give the rung as qdist next to it, or run the quality half alone)")
+    if want_q and quality.convert is not None and want_c and not split:
+        raise ValueError("converting needs a distorted stream of the quality half's own: in a combined pass one BGR stream serves "
+                         "both halves as it is (give the quality pair as qdist next to it, or run the quality half alone)")
 
     def count(fr):
         return fr.n if isinstance(fr, DeviceFrames) else fr.shape[0]
@@ -767,8 +817,12 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
     halo = any(k.halo for k in requested)
     scaling = want_q and quality.scale is not None
     conforming = want_q and quality.conform is not None
+    converting = want_q and quality.convert is not None
+    own = scaling or converting   # the distorted feed has planes of its own (dist_planes)
     if scaling and ref_only:
         raise ValueError("this pass reads the reference stream alone: there is no distorted stream to scale")
+    if converting and ref_only:
+        raise ValueError("this pass reads the reference stream alone: there is no distorted stream to convert")
     if (want_c or not split) and not ref_only:
         feeds["dist"] = _Feed("dist", "copies", dist, first, wide=not want_c)
     if want_q:
@@ -777,8 +831,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
             feeds["qdist"] = _Feed("qdist", "qcopies", qd, first, wide=True)
     if want_q and not ref_only:
         fq, fr = feeds["qdist" if split else "dist"], feeds["ref"]
-        if scaling:
-            # the distorted feed has its own frame size: each feed against its own plane list
+        if own:
+            # the distorted feed has its own frame size (and, converting, sample type): each feed against its own plane list
             if fr.src.n != fq.src.n:
                 raise ValueError("reference and distorted streams must have the same frame count")
             for f, pl, what in ((fr, quality.planes, "planes"), (fq, quality.dist_planes, "dist_planes")):
@@ -787,7 +841,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                                      % (f.name, f.fb, f.itemsize, what, planes_span(pl), planes_depth(pl)))
         elif fr.src.n != fq.src.n or fr.fb != fq.fb:
             raise ValueError("reference and distorted streams must have the same frame count and layout")
-        if not scaling and fr.geometry() != fq.geometry() and not (fr.host != fq.host):
+        if not own and fr.geometry() != fq.geometry() and not (fr.host != fq.host):
             # (an equal-byte reshape - 1080x1920 against 1920x1080 - would be compared plane against garbage)
             raise ValueError("reference and distorted streams must share a geometry (%s vs %s)" % (fr.geometry(), fq.geometry()))
     if conforming:
@@ -823,7 +877,7 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         lanes = [first]
     else:
         lanes = list(get_engine_lanes(first.device, min(want_lanes, nchunks)))
-    st = _staging_of(first) if (host or scaling or conforming) else None
+    st = _staging_of(first) if (host or own or conforming) else None
     cp = get_copy_engine(first.device) if host else None   # the copy lane: every upload of the pass, in chunk order
     nb = len(lanes) + 1    # buffer sets on the device: the chunks the lanes hold + the one whose upload runs under their kernels
     params = first.make_params(resize=complexity.resize, dct_mode=complexity.dct_mode,
@@ -846,6 +900,12 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
         scaled_bytes = max(p["qn"] for p in plans) * scaled_fb
         for bs in range(min(nb, nchunks)):
             st.device_buffer(bs, "scaled", scaled_bytes)
+    if converting:   # the converted chunk: a lane buffer per set, of the reference's frame size - ahead of scale, of mid_planes
+        conv_isz = feeds["ref"].itemsize
+        conv_fb = -(-planes_span(quality.mid_planes) // 16) * 16 if scaling else feeds["ref"].fb
+        conv_bytes = max(p["qn"] for p in plans) * conv_fb
+        for bs in range(min(nb, nchunks)):
+            st.device_buffer(bs, "converted", conv_bytes)
     if conforming:   # the conformed chunk of either stream (the reference's with its halo frame): a lane buffer per set
         conf_isz = 2 if planes_depth(quality.planes) > 8 else 1
         conf_fb = -(-planes_span(quality.planes) // 16) * 16
@@ -918,13 +978,21 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                                                  row_stride=f.fb, owner=b, channels=1, itemsize=f.itemsize))
                     else:
                         pair.append(f.src.frames.slice(p["q0"], p["q0"] + p["qn"]))
-                p["scaled"] = False
+                p["scaled"] = p["converted"] = False
+                if converting:
+                    # the chunk at its own depth and chroma layout -> the reference's, on this lane; what follows reads the result
+                    b = st.device_buffer(p["k"] % nb, "converted", conv_bytes)
+                    out = DeviceFrames(b.ptr, p["qn"], 1, conv_fb // conv_isz, frame_stride=conv_fb, row_stride=conv_fb, owner=b,
+                                       channels=1, itemsize=conv_isz)
+                    pair[1] = eng.convert_submit(pair[1], quality.dist_planes, quality.mid_planes, *quality.convert, out=out)
+                    p["converted"] = True
                 if scaling:
                     # the chunk at its native size -> the reference's, on this lane; what follows on the lane reads the result
                     b = st.device_buffer(p["k"] % nb, "scaled", scaled_bytes)
                     out = DeviceFrames(b.ptr, p["qn"], 1, scaled_fb // fr.itemsize, frame_stride=scaled_fb, row_stride=scaled_fb,
                                        owner=b, channels=1, itemsize=fr.itemsize)
-                    pair[1] = eng.scale_submit(pair[1], quality.dist_planes, quality.planes, quality.scale, out=out)
+                    pair[1] = eng.scale_submit(pair[1], quality.mid_planes if converting else quality.dist_planes, quality.planes,
+                                               quality.scale, out=out)
                     p["scaled"] = True
                 conf_prev0 = None
                 p["conformed"] = False
@@ -1006,6 +1074,8 @@ def _run_locked(first, engine, dist, ref, qd, split, quality, complexity, series
                 p["rec"] = eng.complexity_wait()
             if p.get("scaled"):
                 eng.scale_wait()
+            if p.get("converted"):
+                eng.convert_wait()
             if p.get("conformed"):
                 eng.conform_wait()
         if staged:

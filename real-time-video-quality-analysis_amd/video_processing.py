@@ -370,6 +370,34 @@ def frame_scale(frames, layout, height, width, out_height, out_width, filter="bi
     return out
 
 
+def frame_convert(frames, layout, out_layout, height=None, width=None, chroma="linear", siting="center", range="limited",
+                  engine=None, batch_size=64, device=None):
+    """The stream written at another sample depth and / or chroma layout on the GPU (Engine.convert: include/vqa.h's integer
+    definition, one rounding per sample; chroma "box" | "linear", siting "center" | "left", range "limited" | "full") -> a host
+    array [n, frame samples of out_layout] of out_layout's sample type, in chunks of batch_size frames.  frames: what
+    frame_scale takes, at `layout`; height and width are needed for planar [N, samples] arrays.  Both layouts have the same
+    number of planes (mono to mono, three planes to three planes; packed bgr24 is not built): ValueError otherwise."""
+    from .engine import check_convert_planes, convert_options, planes_span
+    frames = _host_stream(frames, wide=True)
+    convert_options(chroma, siting, range)
+    _check_convert_layouts(layout, out_layout, equal_ok=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes, out_planes = LAYOUTS[layout][0](h, w), LAYOUTS[out_layout][0](h, w)
+    check_convert_planes(planes, out_planes)
+    wide = layout_depth(out_layout) > 8
+    n = _frame_count(frames)
+    out = np.zeros((n, planes_span(out_planes) // (2 if wide else 1)), np.uint16 if wide else np.uint8)
+    if n == 0:
+        return out
+    eng = engine if engine is not None else stream.get_engine(device)
+    with stream.pass_lock(eng.device):
+        for a, b in _frame_windows(n, int(batch_size)):
+            res = eng.convert(_frame_part(frames, a, b), planes, out_planes, chroma, siting, range)
+            out[a:b] = eng.download(res)
+            res._owner.free()
+    return out
+
+
 ALIGN_WINDOW = 4096   # the distorted frames of one submit of frame_align (the C limit is 32768)
 
 
@@ -935,6 +963,62 @@ def _scale_request(scale, dist_height, dist_width):
     return True
 
 
+def _convert_request(values):
+    """the four arguments of the conversion - run_ffmpeg_metrics' keywords or a config's keys, named alike - and the pre-passes
+    named next to them -> (chroma, siting, range), or None when nothing is converted; a ValueError for a set that does not fit
+    together"""
+    from .engine import CONVERT_CHROMA, CONVERT_RANGE, CONVERT_SITING
+    convert, dist_pixfmt = values.get("convert"), values.get("dist_pixfmt")
+    siting, rng = values.get("convert_siting") or "center", values.get("convert_range") or "limited"
+    if dist_pixfmt is not None and not (isinstance(dist_pixfmt, str) and dist_pixfmt in LAYOUTS):
+        raise ValueError("dist_pixfmt must be null or one of the pixel layouts pixfmt takes.")
+    if not (isinstance(siting, str) and siting in CONVERT_SITING):
+        raise ValueError("convert_siting must be \"center\" or \"left\".")
+    if not (isinstance(rng, str) and rng in CONVERT_RANGE):
+        raise ValueError("convert_range must be \"limited\" or \"full\".")
+    if convert is None:
+        if dist_pixfmt is not None:
+            raise ValueError("dist_pixfmt needs convert: nothing is converted without being named.")
+        return None
+    if not (isinstance(convert, str) and convert in CONVERT_CHROMA):
+        raise ValueError("convert must be \"box\" or \"linear\".")
+    for key, on in (("sync", values.get("sync")), ("align", values.get("align") is not None), ("shift", values.get("shift") is not None),
+                    ("colorfit", values.get("colorfit")), ("conform", values.get("conform"))):
+        if on:
+            raise ValueError("%s and convert do not go together: the pair-reading pre-passes are not built on a pair of mixed pixel "
+                             "layouts (Engine.convert's frames can be handed to them by the caller)." % key)
+    return convert, siting, rng
+
+
+def _check_convert_layouts(layout, dist_layout, converting=True, equal_ok=False):
+    """the two layouts of a pair against the conversion asked for; a ValueError for a pair that does not fit it"""
+    if not converting:
+        if dist_layout != layout:
+            raise ValueError("reference and distorted streams must share a pixel layout (%s and %s: name the conversion with "
+                             "convert to measure them)" % (layout, dist_layout))
+        return
+    if dist_layout == layout and not equal_ok:
+        raise ValueError("convert needs streams of different pixel layouts (both are %s): equal formats are measured as they are."
+                         % layout)
+    if "bgr24" in (layout, dist_layout):
+        raise ValueError("convert between packed bgr24 and planar YUV is a colour-matrix question: not built.")
+    if len(LAYOUTS[layout][1]) != len(LAYOUTS[dist_layout][1]):
+        raise ValueError("convert needs as many planes on both sides (%s has %d, %s has %d): mono to or from three planes is not "
+                         "built." % (layout, len(LAYOUTS[layout][1]), dist_layout, len(LAYOUTS[dist_layout][1])))
+
+
+def _convert_planes(conv, scaling, scale, layout, dist_layout, planes, dh, dw, extra):
+    """the distorted stream's own planes of a converting pass and the log's keys -> (dist_planes, extra): DIST_PIXFMT and CONVERT
+    right after DIST_RES / SCALE where those exist"""
+    from .engine import check_convert_planes, check_scale_planes
+    dist_planes = LAYOUTS[dist_layout][0](dh, dw)
+    mid = LAYOUTS[layout][0](dh, dw) if scaling else planes
+    check_convert_planes(dist_planes, mid)
+    if scaling:
+        check_scale_planes(mid, planes)
+    return dist_planes, dict(extra or {}, DIST_PIXFMT=dist_layout, CONVERT="/".join(conv))
+
+
 # ---------------------------------------------------------------------------
 # The pre-passes of the two entry points: one table, one request parser, one chain
 # ---------------------------------------------------------------------------
@@ -954,15 +1038,20 @@ PREPASSES = (
 )
 # what was asked of a pass before it starts: whether the rung is scaled, align's radius, shift's (radius, margin), light's
 # (transfer, full_range), sync's (min_overlap, apply), whether the colour fit is on, conform's colour mode
-Requests = namedtuple("Requests", "scaling radius search lit syn fit mode")
+class Requests(namedtuple("Requests", "scaling radius search lit syn fit mode")):
+    """the seven fields, and beside them `convert`: None or the (chroma, siting, range) of a converting pass - no pre-pass and no
+    field, so that a request without it is the tuple it was"""
+    convert = None
 
 
 def _requests(values, config=False):
     """run_ffmpeg_metrics' keywords, or with config=True a config -> Requests.  The order of the checks, and so the first error
-    of a bad combination: scale, align, shift, light, sync, colorfit, conform."""
+    of a bad combination: scale, align, shift, light, sync, colorfit, conform, convert."""
     parse = {p.name: p.request for p in PREPASSES}
-    return Requests(_scale_request(values.get("scale"), values.get("dist_height"), values.get("dist_width")),
-                    *(parse[name](values, config) for name in ("align", "shift", "light", "sync", "colorfit", "conform")))
+    req = Requests(_scale_request(values.get("scale"), values.get("dist_height"), values.get("dist_width")),
+                   *(parse[name](values, config) for name in ("align", "shift", "light", "sync", "colorfit", "conform")))
+    req.convert = _convert_request(values)
+    return req
 
 
 def _prepass_keys(found, extra=None):
@@ -1243,7 +1332,8 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        pu21_full_range=False, fsim=False, sigstats=False, sigstats_black=None, sigstats_crop=None,
                        dist_height=None, dist_width=None, scale=None, align=None, shift=None,
                        shift_margin=None, light=False, light_transfer="pq", light_full_range=False, sync=False,
-                       sync_min_overlap=None, sync_apply=False, colorfit=False, conform=False, conform_color="match"):
+                       sync_min_overlap=None, sync_apply=False, colorfit=False, conform=False, conform_color="match",
+                       dist_pixfmt=None, convert=None, convert_siting="center", convert_range="limited"):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -1346,6 +1436,16 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     (only the constant offset is applied in the pass), a shift on the band's border and CONFORM_CHROMA_HALF are warnings.
     conform needs at least one of sync, align, shift and colorfit, a colour mode other than "none" needs colorfit, "tone" needs a
     depth of at most 10 bits, and conform with scale is a ValueError.  Without conform every file is byte for byte what it was.
+    convert="box" | "linear": the distorted stream has its OWN pixel layout - another sample depth and / or chroma layout than
+    the reference, a 10-bit 4:2:2 mezzanine against its 8-bit 4:2:0 encode.  A .y4m pair brings its two layouts in its headers;
+    arrays and raw .yuv take the distorted one from dist_pixfmt (layout names the reference's).  Every chunk is uploaded as it is
+    and converted to the reference's layout on the GPU (stream.Quality's convert; include/vqa.h's integer definition: what an
+    auto-inserted `format=` does in an FFmpeg graph, NOT swscale's arithmetic), convert_siting "center" | "left" and
+    convert_range "limited" | "full" with it.  With scale the conversion runs first, at the rung's size.  vmaf_log gains the
+    top-level keys "DIST_PIXFMT" and "CONVERT" ("linear/center/limited"), right after DIST_RES / SCALE where those exist.
+    Layouts that differ without convert stay the error they were; dist_pixfmt without convert, convert on equal layouts, on a
+    differing plane count or packed bgr24, and convert with sync, align, shift, colorfit or conform are ValueErrors (light reads
+    the reference only and stays allowed).  Without the keywords every file is byte for byte what it was.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -1356,10 +1456,10 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     scaling = req.scaling
     ref, layout, height, width = _open_quality_stream(reference_video, layout, height, width)
     # (a scaled pass never borrows the reference's size for the rung: a .y4m header, the array's shape or the two arguments say it)
-    dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, layout, dist_height or (None if scaling else height),
+    dist, layout_d, dist_h, dist_w = _open_quality_stream(distorted_video, (dist_pixfmt or layout) if req.convert else layout,
+                                                          dist_height or (None if scaling else height),
                                                           dist_width or (None if scaling else width))
-    if layout_d != layout:
-        raise ValueError("reference and distorted streams must share a pixel layout")
+    _check_convert_layouts(layout, layout_d, req.convert is not None)
     h, w = _geometry(ref, layout, height, width)
     planes = LAYOUTS[layout][0](h, w)
     _colorfit_request(req.fit, scale, layout)
@@ -1368,12 +1468,15 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     dh, dw = h, w
     if scaling:
         from .engine import check_scale_planes
-        dh, dw = _geometry(_host_stream(dist, wide=True), layout, dist_h, dist_w)
+        dh, dw = _geometry(_host_stream(dist, wide=True), layout_d, dist_h, dist_w)
         if not dh or not dw:
             raise ValueError("scale needs the distorted stream's size: dist_height and dist_width")
         dist_planes = LAYOUTS[layout][0](dh, dw)
-        check_scale_planes(dist_planes, planes)
+        if not req.convert:
+            check_scale_planes(dist_planes, planes)
         extra = {"DIST_RES": "%dx%d" % (dw, dh), "SCALE": scale}
+    if req.convert:
+        dist_planes, extra = _convert_planes(req.convert, scaling, scale, layout, layout_d, planes, dh, dw, extra)
     wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
     try:
         for f in FEATURES:
@@ -1383,11 +1486,11 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                     f.plane_check(planes)
         (rs, ds), extra, plan, planes, ran = _prepass_chain(
             req, _host_stream(ref, wide=True), _host_stream(dist, wide=True), (), layout, h, w, (dh, dw), planes, sw, device,
-            extra=extra, same_shape=not scaling)
+            extra=extra, same_shape=not scaling and not req.convert)
         if plan is not None:
             wr.resize(_sizes(planes))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
-                 ran=ran, batch_size=batch_size, on_quality=wr, device=device, conform=plan)
+                 ran=ran, batch_size=batch_size, on_quality=wr, device=device, conform=plan, convert=req.convert)
     finally:
         wr.close()
     return None
@@ -1433,11 +1536,13 @@ def _write_feature_log(vmaf_log, q, on, *, model=None, brisque_model=None, sigst
                   sigstats_depth=sigstats_depth, extra=extra, **log)
 
 
-def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, conform=None, ran=False, **run):
+def _measure(dist, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log, conform=None, ran=False,
+             convert=None, **run):
     """One pass (stream.run with its further arguments `run`) whose Quality the switches sw (features.switches) spell, and the feature
     log of what it measured, when a kind is on.  models: _load_models(sw).  conform: None or the plan the pass applies (planes
-    are then its out_planes).  ran: a pre-pass ran (_prepass_chain).  -> stream.run's pair"""
-    quality = stream.Quality(planes, ssim_mode, dist_planes=dist_planes, scale=scale, conform=conform,
+    are then its out_planes).  ran: a pre-pass ran (_prepass_chain).  convert: None or the (chroma, siting, range) of a converting
+    pass.  -> stream.run's pair"""
+    quality = stream.Quality(planes, ssim_mode, dist_planes=dist_planes, scale=scale, conform=conform, convert=convert,
                              **{k: v for k, v in sw.items() if k not in MODEL_PATHS})
     q, series = stream.run(dist, ref, quality=quality, **run)
     on = {f.flag: sw[f.kind] for f in FEATURES}
@@ -1588,7 +1693,15 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         CONFORM_OFFSET, CONFORM_DY, CONFORM_DX, CONFORM_COLOR, CONFORM_RES, CONFORM_FRAMES and CONFORM_CHROMA_HALF as its LAST
         columns; the complexity half reads the BGR frames as they are.  It needs at least one of sync, align, shift and
         colorfit, a colour mode other than "none" needs colorfit, and a quality pair of its own (planar streams next to
-        encoded_bgr); with scale it is a ValueError.
+        encoded_bgr); with scale it is a ValueError,
+        convert (null | "box" | "linear"; default null) with dist_pixfmt (the ENCODED pair stream's own pixel layout, one of
+        pixfmt's names; a .y4m pair brings both in its headers), convert_siting ("center" | "left") and convert_range ("limited" |
+        "full"): the encoded pair stream differs from the input in sample depth and / or chroma layout; every chunk is uploaded
+        as it is and converted to the input's layout on the GPU (run_ffmpeg_metrics' convert; include/vqa.h's integer definition,
+        not swscale's), ahead of scale where both are named.  The row gains DIST_PIXFMT and CONVERT ("linear/center/limited")
+        right after DIST_RES / SCALE where those exist.  It needs a quality pair of its own (planar streams next to encoded_bgr);
+        dist_pixfmt without convert, convert on equal layouts, on a differing plane count or bgr24, and convert with sync, align,
+        shift, colorfit or conform are ValueErrors; light stays allowed.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1615,10 +1728,10 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
     psnr_log, ssim_log, vmaf_log = (os.path.join(tmp, "%s_%s.log" % (k, uid)) for k in ("psnr", "ssim", "vmaf"))
     try:
         ref, layout, qh, qw = _open_quality_stream(input_video, layout, height, width)
-        qenc, layout_d, dqh, dqw = _open_quality_stream(encoded_video, layout, config.get("dist_height") or (None if scaling else qh),
+        qenc, layout_d, dqh, dqw = _open_quality_stream(encoded_video, (config.get("dist_pixfmt") or layout) if req.convert else layout,
+                                                        config.get("dist_height") or (None if scaling else qh),
                                                         config.get("dist_width") or (None if scaling else qw))
-        if layout_d != layout:
-            raise ValueError("reference and distorted streams must share a pixel layout")
+        _check_convert_layouts(layout, layout_d, req.convert is not None)
         if scaling and (layout == "bgr24" and encoded_bgr is None):
             raise ValueError("scaling needs a distorted stream of the quality half's own: pass the rung as a planar pair next to "
                              "encoded_bgr (one BGR stream serves both halves at one size)")
@@ -1639,28 +1752,33 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
             h, w = _geometry(ref, layout, (qh or eh) if not scaling else qh, (qw or ew) if not scaling else qw)
             if scaling and (not h or not w):
                 raise ValueError("scale needs the input stream's size: height and width")
-            dh, dw = _geometry(qdist, layout, dqh or eh, dqw or ew) if scaling else (h, w)   # (the BGR stream has the rung's size)
-            if layout == "yuv420p":
-                from .frames import frame_bytes_yuv420p
-                for a, (ah, aw) in ((ref, (h, w)), (qdist, (dh, dw))):
+            dh, dw = _geometry(qdist, layout_d, dqh or eh, dqw or ew) if scaling else (h, w)   # (the BGR stream has the rung's size)
+            for a, lay, (ah, aw) in ((ref, layout, (h, w)), (qdist, layout_d, (dh, dw))):   # (layout_d is layout unless converting)
+                if lay == "yuv420p":
+                    from .frames import frame_bytes_yuv420p
                     if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_bytes_yuv420p(ah, aw)):
                         raise ValueError("yuv420p streams must be planar [N, H*W*3/2] uint8 arrays of the frames' geometry "
                                          "(%dx%d: %d bytes per frame)" % (aw, ah, frame_bytes_yuv420p(ah, aw)))
-            elif layout in PIXFMTS and layout != "gray":
-                dt = np.uint16 if layout_depth(layout) > 8 else np.uint8
-                for a, (ah, aw) in ((ref, (h, w)), (qdist, (dh, dw))):
-                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_samples(ah, aw, layout)
+                elif lay in PIXFMTS and lay != "gray":
+                    dt = np.uint16 if layout_depth(lay) > 8 else np.uint8
+                    if not isinstance(a, DeviceFrames) and (a.ndim != 2 or a.shape[1] != frame_samples(ah, aw, lay)
                                                             or a.dtype != dt):
                         raise ValueError("%s streams must be planar [N, %d] %s arrays of the frames' geometry (%dx%d)"
-                                         % (layout, frame_samples(ah, aw, layout), np.dtype(dt).name, aw, ah))
+                                         % (lay, frame_samples(ah, aw, lay), np.dtype(dt).name, aw, ah))
         _conform_tone_depth(req.mode, layout)
         planes = LAYOUTS[layout][0](h, w)
         dist_planes = extra = None
         if scaling:
             from .engine import check_scale_planes
             dist_planes = LAYOUTS[layout][0](dh, dw)
-            check_scale_planes(dist_planes, planes)
+            if not req.convert:
+                check_scale_planes(dist_planes, planes)
             extra = {"DIST_RES": "%dx%d" % (dw, dh), "SCALE": scale}
+        if req.convert:
+            if qdist is None:
+                raise ValueError("converting needs a distorted stream of the quality half's own: pass the quality pair as planar "
+                                 "streams next to encoded_bgr (one BGR stream serves both halves as it is)")
+            dist_planes, extra = _convert_planes(req.convert, scaling, scale, layout, layout_d, planes, dh, dw, extra)
         for f in FEATURES:
             if sw[f.kind] and f.plane_check is not None:
                 f.plane_check(planes)
@@ -1676,7 +1794,8 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         try:
             _q, series = _measure(enc, ref, sw, models, planes, ssim_mode, layout, dist_planes, scale, extra, vmaf_log,
                                   complexity=stream.Complexity((rw, rh), interval, dct_mode=dct_mode, motion_mode=motion_mode),
-                                  ran=ran, batch_size=batch_size, on_quality=wr, qdist=qdist, device=device, conform=plan)
+                                  ran=ran, batch_size=batch_size, on_quality=wr, qdist=qdist, device=device, conform=plan,
+                                  convert=req.convert)
         finally:
             wr.close()
         resolution = "%dx%d" % (ew, eh)
@@ -1691,7 +1810,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                      "ORB Feature Complexity", "Color Histogram Complexity", "Temporal DCT Complexity",
                      "Framerate Variation")
         metrics.update(dict(zip(names, t)))
-        if scaling:
+        if scaling or req.convert:
             metrics.update(extra)
         if ran:   # (extract_metrics_from_logs read the pre-passes' keys off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
