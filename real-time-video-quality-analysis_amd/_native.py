@@ -6,6 +6,8 @@ visible, importing the library or creating a context raises.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VQA_LIB_PATH: load another build of the same ABI (the lab build csrc/lab/libvqa_hip_lab.so for A/B re-measurement and
 # fault injection, or a probe build); default = the shipped in-tree library
@@ -161,6 +163,11 @@ CONFORM_MAX_OUT = 32768       # vqa_conform_submit: the output frames of one sub
 CONFORM_MAX_COEF, CONFORM_MAX_BIAS = 1 << 20, 1 << 33   # |M[k][i]|, i < 3, and |M[k][3]| of its matrix (2^-16 fixed point)
 CONVERT_MIN_DIM = 16          # vqa_convert_submit: plane 0 of both sides (the other planes: 8, the chroma of 4:2:0)
 CONVERT_MAX_FRAMES = 32768    # vqa_convert_submit: the frames of one submit
+FIELDS_MIN_DIM = 16           # vqa_fields_submit: the measured plane
+FIELDS_MAX_FRAMES = 32768     # vqa_fields_submit: the frames of one submit
+FIELDS_BAND_ROWS = 32         # k_fields_accum: the rows a lane marches (tests straddle it)
+WEAVE_MIN_DIM = 16            # vqa_weave_submit: plane 0 (the other planes: 8, the chroma of 4:2:0)
+WEAVE_MAX_OUT = 32768         # vqa_weave_submit: the output frames of one submit
 CHROMA_BOX, CHROMA_LINEAR = 0, 1       # vqa_convert_submit's chroma filters
 SITING_CENTER, SITING_LEFT = 0, 1      # its horizontal sitings (LINEAR only)
 RANGE_LIMITED, RANGE_FULL = 0, 1       # its ranges
@@ -312,6 +319,16 @@ class VqaColorfitMetrics(C.Structure):
                 ("rd", C.c_uint64 * 9), ("dd", C.c_uint64 * 3), ("sse", C.c_uint64 * 3)]
 
 
+class VqaFieldsMetrics(C.Structure):
+    _fields_ = [("comb", C.c_uint64 * 2), ("fwd", C.c_uint64 * 2), ("bwd", C.c_uint64 * 2), ("sad", C.c_uint64 * 2),
+                ("changed", C.c_uint64 * 2), ("count", C.c_uint64), ("has_prev", C.c_uint64)]
+
+
+# vqa_fields_metrics as a NumPy record: what Engine.fields returns
+FIELDS_DTYPE = np.dtype([("comb", np.uint64, (2,)), ("fwd", np.uint64, (2,)), ("bwd", np.uint64, (2,)), ("sad", np.uint64, (2,)),
+                         ("changed", np.uint64, (2,)), ("count", np.uint64), ("has_prev", np.uint64)], align=True)
+
+
 class VqaSigstatsMetrics(C.Structure):
     _fields_ = [("count", C.c_int64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32),
                 ("low", C.c_uint32), ("median", C.c_uint32), ("high", C.c_uint32), ("or_mask", C.c_uint32),
@@ -436,6 +453,11 @@ SIGNATURES = {
     "vqa_convert_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_void_p, C.c_int64,
                                      C.POINTER(VqaPlaneDesc), C.c_int, C.c_int, C.c_int, C.c_int]),
     "vqa_convert_wait": (C.c_int, [C.c_void_p]),
+    "vqa_fields_submit": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc)]),
+    "vqa_fields_wait": (C.c_int, [C.c_void_p, C.POINTER(VqaFieldsMetrics), C.c_int]),
+    "vqa_weave_submit": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(VqaPlaneDesc), C.c_void_p, C.c_int64,
+                                   C.POINTER(VqaPlaneDesc), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    "vqa_weave_wait": (C.c_int, [C.c_void_p]),
     "vqa_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vqa_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "vqa_kernel_name": (C.c_char_p, [C.c_int]),

@@ -86,6 +86,10 @@ enum batch_kind {
     KIND_CONFORM,     // no result words: the batch writes the caller's dst; work: host frames staged (0), the frame index and the
                       // tables on the device (1); the pinned copy holds what (1) is filled from
     KIND_CONVERT,     // no result words: the batch writes the caller's dst; work: host frames staged (0)
+    KIND_FIELDS,      // FIELDS_WORDS per frame; work: host frames staged (0), prev0 (1); whether frame 0 had a predecessor is a
+                      // named member of the ctx (fields_prev0)
+    KIND_WEAVE,       // no result words: the batch writes the caller's dst; work: host frames staged (0), the two frame indices on
+                      // the device (1); the pinned copy holds what (1) is filled from
     KIND_COUNT
 };
 
@@ -161,6 +165,7 @@ struct vqa_ctx {
     bool light_hist = false;             // the pending light batch (slot[KIND_LIGHT]) keeps its histograms for the wait
     std::vector<uint64_t> light_table;   // the table of the last light submit: what slot[KIND_LIGHT].work[0] holds, and what the wait reads
     int64_t colorfit_table_words = 0;    // the pending colour-fit batch (slot[KIND_COLORFIT]) keeps that many table words (0: none)
+    bool fields_prev0 = false;           // frame 0 of the pending fields batch (slot[KIND_FIELDS]) had a predecessor
     int last_u_n = 0, last_u_w = 0, last_u_h = 0;   // lab build: what PU21's kept maps hold
     int last_f_n = 0, last_f_w = 0, last_f_h = 0;   // lab build: what FSIM's kept maps hold (the downsampled grid)
     bool pend_c_prev0 = false, pend_c_tail_only = false;
@@ -3127,6 +3132,43 @@ int vqa_scale_tables(int filter, int in, int out, int32_t *k, int32_t *xmin, int
     return VQA_OK;
 }
 
+// The planes of a copy (conform, weave) sorted into those a granule copy can take - a contiguous pixel step on both sides; `k`
+// planes that interleave on both sides with one window go as one plane of k times the samples - and the others, which the gather
+// takes.  odd: 16-bit samples at odd addresses would straddle a granule's dwords: the gather takes them all.  fill(p, P): plane p
+// of the submit.
+extern "C++" template <class Fill>
+static void copy_plan(int n_planes, int bps, bool odd, Fill fill, conform_plane *fast, int &n_fast, conform_plane *slow, int &n_slow)
+{
+    bool done[4] = {false, false, false, false};
+    for (int p = 0; p < n_planes; p++) {
+        if (done[p]) continue;
+        conform_plane P;
+        fill(p, P);
+        done[p] = true;
+        const int k = P.src_step / bps;
+        if (!odd && P.src_step == P.dst_step && P.src_step == bps) {
+            fast[n_fast++] = P;
+            continue;
+        }
+        // planes p .. p + k - 1 interleave: the same geometry and window, offsets one sample apart on both sides
+        bool inter = !odd && P.src_step == P.dst_step && P.src_step == k * bps && k >= 2 && k <= 3 && p + k <= n_planes;
+        for (int q = 1; inter && q < k; q++) {
+            conform_plane Q;
+            fill(p + q, Q);
+            inter = !done[p + q] && Q.src_off == P.src_off + (int64_t)q * bps && Q.dst_off == P.dst_off + (int64_t)q * bps &&
+                    Q.src_rs == P.src_rs && Q.dst_rs == P.dst_rs && Q.src_step == P.src_step && Q.dst_step == P.dst_step &&
+                    Q.w == P.w && Q.h == P.h && Q.y0 == P.y0 && Q.x0 == P.x0;
+        }
+        if (inter) {
+            for (int q = 1; q < k; q++) done[p + q] = true;
+            P.inter = k; P.w *= k; P.x0 *= k;
+            fast[n_fast++] = P;
+        } else {
+            slow[n_slow++] = P;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Conform: a registered copy of one stream - window, frame gather, table, matrix - into the caller's device memory.  A batch of
 // its own with no result words and the resampler's slot semantics.  The frame index and the tables reach the device through the
@@ -3206,40 +3248,11 @@ static int conform_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, 
         for (int p = 0; p < 3; p++) fill(p, job.plane[p]);
         launch_conform_matrix(st, job, planes[0].height, planes[0].width, planes[1].height, planes[1].width, n_out, depth);
     } else {
-        // three launches at most: the planes a granule copy can take (a contiguous pixel step on both sides; `k` planes that
-        // interleave on both sides with one window go as one plane of k times the samples), then the others by the gather.
-        // 16-bit samples at odd addresses would straddle a granule's dwords: the gather takes them.
+        // three launches at most: the granule copy's planes, then the others by the gather (copy_plan)
         const bool odd = bps == 2 && (((uintptr_t)frames | (uintptr_t)dst | (uintptr_t)fs | (uintptr_t)dst_fs) & 1);
         conform_job fast = job, slow = job;
         int n_fast = 0, n_slow = 0;
-        bool done[4] = {false, false, false, false};
-        for (int p = 0; p < n_planes; p++) {
-            if (done[p]) continue;
-            conform_plane P;
-            fill(p, P);
-            done[p] = true;
-            const int k = P.src_step / bps;
-            if (!odd && P.src_step == P.dst_step && P.src_step == bps) {
-                fast.plane[n_fast++] = P;
-                continue;
-            }
-            // planes p .. p + k - 1 interleave: the same geometry and window, offsets one sample apart on both sides
-            bool inter = !odd && P.src_step == P.dst_step && P.src_step == k * bps && k >= 2 && k <= 3 && p + k <= n_planes;
-            for (int q = 1; inter && q < k; q++) {
-                conform_plane Q;
-                fill(p + q, Q);
-                inter = !done[p + q] && Q.src_off == P.src_off + (int64_t)q * bps && Q.dst_off == P.dst_off + (int64_t)q * bps &&
-                        Q.src_rs == P.src_rs && Q.dst_rs == P.dst_rs && Q.src_step == P.src_step && Q.dst_step == P.dst_step &&
-                        Q.w == P.w && Q.h == P.h && Q.y0 == P.y0 && Q.x0 == P.x0;
-            }
-            if (inter) {
-                for (int q = 1; q < k; q++) done[p + q] = true;
-                P.inter = k; P.w *= k; P.x0 *= k;
-                fast.plane[n_fast++] = P;
-            } else {
-                slow.plane[n_slow++] = P;
-            }
-        }
+        copy_plan(n_planes, bps, odd, fill, fast.plane, n_fast, slow.plane, n_slow);
         launch_conform_copy(st, fast, n_out, n_fast, depth, false);
         launch_conform_copy(st, slow, n_out, n_slow, depth, true);
     }
@@ -3345,6 +3358,137 @@ int vqa_convert_wait(vqa_ctx *c)
 {
     if (!c) return VQA_ERR_INVALID;
     batch_slot &s = c->slot[KIND_CONVERT];
+    if (!s.entries) return VQA_ERR_STATE;
+    if (int rc = wait_synced(c)) return rc;
+    s.entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Fields: the field statistics of one plane of one stream, frame i against frame i - 1.  A batch of its own, ordered by the
+// stream like an SI/TI batch.  Host frames and prev0 are staged in the slot's own work buffers.
+static int fields_submit_body(vqa_ctx *c, const uint8_t *frames, const uint8_t *prev0, int mem_kind, int n, int64_t fs,
+                              const vqa_plane_desc *plane, bool &touched)
+{
+    if (bad_batch_args(c, frames, frames, mem_kind, n, plane, 1)) return VQA_ERR_INVALID;
+    if (n > FIELDS_MAX_FRAMES) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_FIELDS];
+    plane_batch B;
+    int rc = check_batch(s, n, fs, fs, plane, 1, B, [](const vqa_plane_desc &d) { return side_and_area_limits(d, FIELDS_MIN_DIM); });
+    if (rc) return rc;
+    if ((rc = stage_batch(c, touched, mem_kind, n, B.span, {&frames, fs, &s.work[0]}, {}, {&prev0, 0, &s.work[1]}))) return rc;
+    const size_t bytes = sizeof(unsigned long long) * FIELDS_WORDS * (size_t)n;
+    if ((rc = ensure(c, s.dev, bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(s.dev.p, 0, bytes, c->stream));
+    launch_fields_accum(c->stream, frames, prev0, n, fs, plane[0], B.depth, (unsigned long long *)s.dev.p);
+    c->fields_prev0 = prev0 != nullptr;
+    return finish_batch(c, s, bytes, n, plane, 1, B.depth);
+}
+
+int vqa_fields_submit(vqa_ctx *c, const uint8_t *frames, const uint8_t *prev0, int mem_kind, int n, int64_t frame_stride,
+                      const vqa_plane_desc *plane)
+{
+    return submit_and_drain(c, [&](bool &touched) { return fields_submit_body(c, frames, prev0, mem_kind, n, frame_stride, plane, touched); });
+}
+
+int vqa_fields_wait(vqa_ctx *c, vqa_fields_metrics *out, int n)
+{
+    batch_slot *s;
+    if (int rc = wait_pending(c, KIND_FIELDS, out, n, s)) return rc;
+    if (int rc = wait_synced(c)) return rc;
+    const unsigned long long *acc = (const unsigned long long *)s->host.p;
+    for (int i = 0; i < n; i++, acc += FIELDS_WORDS) {
+        vqa_fields_metrics &o = out[i];
+        for (int f = 0; f < 2; f++) {
+            o.comb[f] = acc[f]; o.fwd[f] = acc[2 + f]; o.bwd[f] = acc[4 + f]; o.sad[f] = acc[6 + f]; o.changed[f] = acc[8 + f];
+        }
+        o.count = (uint64_t)(s->h[0] - 4) * (uint64_t)s->w[0];
+        o.has_prev = i > 0 || c->fields_prev0;
+    }
+    s->entries = 0;
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Weave: frames out of the fields of other frames, into the caller's device memory.  A batch of its own with no result words
+// and conform's slot semantics.  The two frame indices reach the device through the slot's pinned copy, so the caller's arrays
+// are free when the submit returns.
+static int weave_submit_body(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n_in, int64_t fs, const vqa_plane_desc *planes,
+                             uint8_t *dst, int64_t dst_fs, const vqa_plane_desc *dplanes, int n_planes, const int32_t *top,
+                             const int32_t *bottom, int n_out, bool &touched)
+{
+    if (bad_batch_args(c, frames, dst, mem_kind, n_in, planes, n_planes) || !dplanes || !top || !bottom || n_out <= 0)
+        return VQA_ERR_INVALID;
+    if (n_out > WEAVE_MAX_OUT) return VQA_ERR_UNSUPPORTED;
+    batch_slot &s = c->slot[KIND_WEAVE];
+    plane_batch B, D;
+    auto src_limits = [=](const vqa_plane_desc &d) { return side_and_area_limits(d, &d == planes ? WEAVE_MIN_DIM : WEAVE_MIN_DIM / 2); };
+    auto dst_limits = [=](const vqa_plane_desc &d) { return side_and_area_limits(d, &d == dplanes ? WEAVE_MIN_DIM : WEAVE_MIN_DIM / 2); };
+    int rc = check_batch(s, n_in, fs, fs, planes, n_planes, B, src_limits);
+    if (rc) return rc;
+    if ((rc = check_planes(dplanes, n_planes, D, dst_limits))) return rc;
+    if (D.depth != B.depth) return VQA_ERR_INVALID;
+    for (int p = 0; p < n_planes; p++)
+        if (planes[p].width != dplanes[p].width || planes[p].height != dplanes[p].height) return VQA_ERR_INVALID;
+    if (n_out > 1 && dst_fs < D.span) return VQA_ERR_INVALID;
+    for (int j = 0; j < n_out; j++)
+        if (top[j] < 0 || top[j] >= n_in || bottom[j] < 0 || bottom[j] >= n_in) return VQA_ERR_INVALID;
+    const int64_t dst_bytes = (int64_t)(n_out - 1) * dst_fs + D.span, src_bytes = (int64_t)(n_in - 1) * fs + B.span;
+    if (!byte_is_on_device(c, dst) || !byte_is_on_device(c, dst + (dst_bytes - 1))) return VQA_ERR_INVALID;
+    if (mem_kind == VQA_MEM_DEVICE && (uintptr_t)frames < (uintptr_t)dst + (uint64_t)dst_bytes &&
+        (uintptr_t)dst < (uintptr_t)frames + (uint64_t)src_bytes)
+        return VQA_ERR_INVALID;
+    if ((rc = stage_batch(c, touched, mem_kind, n_in, B.span, {&frames, fs, &s.work[0]}))) return rc;
+    hipStream_t st = c->stream;
+
+    // the indices: the caller's -> the pinned copy -> the device, top then bottom
+    const size_t index_bytes = (size_t)n_out * sizeof(int32_t);
+    if ((rc = ensure(c, s.work[1], 2 * index_bytes))) return rc;
+    if ((rc = ensure_pinned(c, s.host, 2 * index_bytes))) return rc;
+    memcpy(s.host.p, top, index_bytes);
+    memcpy((uint8_t *)s.host.p + index_bytes, bottom, index_bytes);
+    HIPCHK(c, hipMemcpyAsync(s.work[1].p, s.host.p, 2 * index_bytes, hipMemcpyHostToDevice, st));
+
+    weave_job job;
+    memset(&job, 0, sizeof job);
+    job.src = frames; job.dst = dst;
+    job.src_fs = fs; job.dst_fs = dst_fs;
+    job.top = (const int32_t *)s.work[1].p; job.bottom = job.top + n_out;
+    auto fill = [&](int p, conform_plane &P) {
+        const vqa_plane_desc &a = planes[p], &b = dplanes[p];
+        P.src_off = a.offset; P.dst_off = b.offset;
+        P.src_rs = a.row_stride; P.dst_rs = b.row_stride;
+        P.src_step = a.pixel_step; P.dst_step = b.pixel_step;
+        P.w = b.width; P.h = b.height;
+        P.y0 = 0; P.x0 = 0;
+        P.inter = 1; P.lut0 = 0;
+    };
+    const bool odd = B.bps == 2 && (((uintptr_t)frames | (uintptr_t)dst | (uintptr_t)fs | (uintptr_t)dst_fs) & 1);
+    weave_job fast = job, slow = job;
+    int n_fast = 0, n_slow = 0;
+    copy_plan(n_planes, B.bps, odd, fill, fast.plane, n_fast, slow.plane, n_slow);
+    launch_fields_weave(st, fast, n_out, n_fast, B.depth, false);
+    launch_fields_weave(st, slow, n_out, n_slow, B.depth, true);
+    HIPCHK(c, hipGetLastError());
+    record_batch(s, n_out, dplanes, n_planes, B.depth);
+    return VQA_OK;
+}
+
+int vqa_weave_submit(vqa_ctx *c, const uint8_t *frames, int mem_kind, int n_in, int64_t frame_stride, const vqa_plane_desc *src_planes,
+                     uint8_t *dst, int64_t dst_frame_stride, const vqa_plane_desc *dst_planes, int n_planes, const int32_t *top_index,
+                     const int32_t *bottom_index, int n_out)
+{
+    return submit_and_drain(c, [&](bool &touched) {
+        return weave_submit_body(c, frames, mem_kind, n_in, frame_stride, src_planes, dst, dst_frame_stride, dst_planes, n_planes,
+                                 top_index, bottom_index, n_out, touched);
+    });
+}
+
+int vqa_weave_wait(vqa_ctx *c)
+{
+    if (!c) return VQA_ERR_INVALID;
+    batch_slot &s = c->slot[KIND_WEAVE];
     if (!s.entries) return VQA_ERR_STATE;
     if (int rc = wait_synced(c)) return rc;
     s.entries = 0;

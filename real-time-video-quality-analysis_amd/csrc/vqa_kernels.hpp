@@ -718,6 +718,28 @@ struct convert_job {
 // sides and share ONE horizontal relation `rx`; gather true: k_convert_gather, a lane a sample, any pixel step and relation
 void launch_convert(hipStream_t st, const convert_job &job, int n, int count, int rx, bool gather);
 
+// Fields and weave (vqa_fields_submit, vqa_weave_submit): k_fields.hip
+constexpr int FIELDS_MIN_DIM = 16;          // the limit of the measured plane
+constexpr int FIELDS_BAND_ROWS = 32;        // the rows a lane of k_fields_accum marches (even: a band starts on a top-field row)
+constexpr int FIELDS_WORDS = 10;            // the sums a frame keeps on the device: [comb, fwd, bwd, sad, changed][parity]
+constexpr int FIELDS_MAX_FRAMES = 32768;    // frames of one submit (they ride in gridDim.y)
+constexpr int WEAVE_MIN_DIM = 16;           // the limit of plane 0 (the other planes: 8, the chroma of 4:2:0)
+constexpr int WEAVE_MAX_OUT = 32768;        // output frames of one submit (they ride in gridDim.y)
+// n frames of one plane, frame i against frame i - 1 and frame 0 against prev0 (null: it has none): adds the FIELDS_WORDS sums of
+// frame i into acc[i * FIELDS_WORDS ..], which the caller has zeroed
+void launch_fields_accum(hipStream_t st, const uint8_t *frames, const uint8_t *prev0, int n, int64_t frame_stride,
+                         const vqa_plane_desc &plane, int depth, unsigned long long *acc);
+// a weave: conform's planes (y0 = x0 = 0, no table) and the source frame of the even and of the odd rows of every output frame
+struct weave_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t src_fs, dst_fs;
+    const int32_t *top, *bottom;       // on the device: [n_out] each
+    conform_plane plane[4];
+};
+// n_out frames of the job's first `count` planes; gather: a lane a sample (any pixel step)
+void launch_fields_weave(hipStream_t st, const weave_job &job, int n_out, int count, int depth, bool gather);
+
 // Temporal alignment (vqa_align_submit): k_align.hip
 constexpr int ALIGN_MAX_DIST = 32768, ALIGN_MAX_REF = 32768 + 64;   // frames of one submit
 // One launch for the whole band of the whole submit: adds C[j][i] = sum X_d,j X_r,i into cross[j * (2 radius + 1) + c] for the pairs

@@ -567,7 +567,7 @@ class Engine:
         """Wait out whatever this engine still has pending (a quality, a VIF, an ADM, a motion, an SI/TI, a PSNR-HVS, a CIEDE2000, a GMSD, a CAMBI, an XPSNR, a HaarPSI, a VCA, an artefacts, a BRISQUE, an MDSI, a dE_ITP, a PU21, an FSIM, a sigstats, a scale and / or a complexity batch), discard the results and
         synchronise its streams: after a failure in the caller's loop nothing reads the caller's buffers any more and the
         engine is usable again.  Never raises."""
-        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf", "_pending_cm", "_pending_cv"]:
+        for pend in list(_BATCHES) + ["_pending_c", "_pending_k", "_pending_l", "_pending_j", "_pending_o", "_pending_sg", "_pending_sx", "_pending_cf", "_pending_cm", "_pending_cv", "_pending_fd", "_pending_wv"]:
             try:
                 if getattr(self, pend, None):
                     {"_pending_c": self.complexity_wait, "_pending_x": self.xpsnr_wait, "_pending_t": self.vca_wait,
@@ -575,7 +575,8 @@ class Engine:
                      "_pending_l": self.align_wait, "_pending_j": self.shift_wait,
                      "_pending_o": self.light_wait, "_pending_sg": self.signature_wait,
                      "_pending_sx": self.sig_cross_wait, "_pending_cf": self.colorfit_wait,
-                     "_pending_cm": self.conform_wait, "_pending_cv": self.convert_wait}.get(pend, lambda: self._batch_wait(pend))()
+                     "_pending_cm": self.conform_wait, "_pending_cv": self.convert_wait,
+                     "_pending_fd": self.fields_wait, "_pending_wv": self.weave_wait}.get(pend, lambda: self._batch_wait(pend))()
             except Exception:
                 setattr(self, pend, None)
         try:
@@ -1285,6 +1286,29 @@ class Engine:
         fid = scale_filter(filter)
         check_scale_planes(planes, out_planes)
         fp, kind, n, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
+        out, ofs = self._out_frames(n, out_planes, out, out_frame_bytes)
+        st = self.lib.vqa_scale_submit(self.ctx, fp, kind, n, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes),
+                                       len(planes), fid)
+        N.check(st, "vqa_scale_submit", self.ctx)
+        self._pending_k = (n, (keep, out))
+        return out
+
+    def scale_wait(self):
+        """Wait for the pending scale batch: the scaled frames are complete (another engine, or a copy to the host, may read
+        them)."""
+        st = self.lib.vqa_scale_wait(self.ctx)
+        self._pending_k = None
+        N.check(st, "vqa_scale_wait", self.ctx)
+
+    def scale(self, frames, planes, out_planes, filter="bicubic", out=None, frame_bytes=None, out_frame_bytes=None):
+        """scale_submit and scale_wait -> the DeviceFrames of the scaled stream."""
+        res = self.scale_submit(frames, planes, out_planes, filter, out, frame_bytes, out_frame_bytes)
+        self.scale_wait()
+        return res
+
+    def _out_frames(self, n, out_planes, out, out_frame_bytes):
+        """the destination of a scale, conform, convert or weave submit -> (DeviceFrames of n frames, its frame stride in
+        bytes): a fresh allocation for out None, else the caller's DeviceFrames, checked against out_planes and cut to n frames"""
         itemsize = 2 if planes_depth(out_planes) > 8 else 1
         span = planes_span(out_planes)
         if out is None:
@@ -1307,24 +1331,7 @@ class Engine:
             if out.n != n or ofs != out.frame_stride:
                 out = DeviceFrames(out.ptr, n, out.h, out.w, ofs, out.row_stride, owner=out, channels=out.channels,
                                    itemsize=itemsize)
-        st = self.lib.vqa_scale_submit(self.ctx, fp, kind, n, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes),
-                                       len(planes), fid)
-        N.check(st, "vqa_scale_submit", self.ctx)
-        self._pending_k = (n, (keep, out))
-        return out
-
-    def scale_wait(self):
-        """Wait for the pending scale batch: the scaled frames are complete (another engine, or a copy to the host, may read
-        them)."""
-        st = self.lib.vqa_scale_wait(self.ctx)
-        self._pending_k = None
-        N.check(st, "vqa_scale_wait", self.ctx)
-
-    def scale(self, frames, planes, out_planes, filter="bicubic", out=None, frame_bytes=None, out_frame_bytes=None):
-        """scale_submit and scale_wait -> the DeviceFrames of the scaled stream."""
-        res = self.scale_submit(frames, planes, out_planes, filter, out, frame_bytes, out_frame_bytes)
-        self.scale_wait()
-        return res
+        return out, ofs
 
     # ---- conform: the found registration, applied -------------------------------------------
     def conform_submit(self, frames, planes, out_planes, origin=None, index=None, lut=None, matrix=None, out=None,
@@ -1345,28 +1352,7 @@ class Engine:
         n = n_in if index_a is None else int(index_a.size)
         if not 1 <= n <= N.CONFORM_MAX_OUT:
             raise ValueError("a conform submit writes 1 .. %d frames (got %d)" % (N.CONFORM_MAX_OUT, n))
-        itemsize = 2 if planes_depth(out_planes) > 8 else 1
-        span = planes_span(out_planes)
-        if out is None:
-            ofs = int(out_frame_bytes) if out_frame_bytes else span
-            if ofs < span:
-                raise ValueError("out_frame_bytes (%d) is smaller than a frame of out_planes (%d)" % (ofs, span))
-            buf = DeviceBuffer(self, n * ofs)
-            out = DeviceFrames(buf.ptr, n, 1, ofs // itemsize, frame_stride=ofs, owner=buf, channels=1, itemsize=itemsize)
-        else:
-            if not isinstance(out, DeviceFrames):
-                raise TypeError("out must be DeviceFrames (device memory)")
-            if out.itemsize != itemsize:
-                raise ValueError("%d-bit planes need an out of %s samples (got DeviceFrames of itemsize %d)"
-                                 % (planes_depth(out_planes), "uint16" if itemsize == 2 else "uint8", out.itemsize))
-            if out.n < n:
-                raise ValueError("out holds %d frames, the batch has %d" % (out.n, n))
-            ofs = int(out_frame_bytes) if out_frame_bytes else out.frame_stride
-            if ofs < span:
-                raise ValueError("a frame of out (%d bytes) is smaller than a frame of out_planes (%d)" % (ofs, span))
-            if out.n != n or ofs != out.frame_stride:
-                out = DeviceFrames(out.ptr, n, out.h, out.w, ofs, out.row_stride, owner=out, channels=out.channels,
-                                   itemsize=itemsize)
+        out, ofs = self._out_frames(n, out_planes, out, out_frame_bytes)
         i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         st = self.lib.vqa_conform_submit(
             self.ctx, fp, kind, n_in, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes), len(planes),
@@ -1408,28 +1394,7 @@ class Engine:
         fp, kind, n, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
         if not 1 <= n <= N.CONVERT_MAX_FRAMES:
             raise ValueError("a convert submit takes 1 .. %d frames (got %d)" % (N.CONVERT_MAX_FRAMES, n))
-        itemsize = 2 if planes_depth(out_planes) > 8 else 1
-        span = planes_span(out_planes)
-        if out is None:
-            ofs = int(out_frame_bytes) if out_frame_bytes else span
-            if ofs < span:
-                raise ValueError("out_frame_bytes (%d) is smaller than a frame of out_planes (%d)" % (ofs, span))
-            buf = DeviceBuffer(self, n * ofs)
-            out = DeviceFrames(buf.ptr, n, 1, ofs // itemsize, frame_stride=ofs, owner=buf, channels=1, itemsize=itemsize)
-        else:
-            if not isinstance(out, DeviceFrames):
-                raise TypeError("out must be DeviceFrames (device memory)")
-            if out.itemsize != itemsize:
-                raise ValueError("%d-bit planes need an out of %s samples (got DeviceFrames of itemsize %d)"
-                                 % (planes_depth(out_planes), "uint16" if itemsize == 2 else "uint8", out.itemsize))
-            if out.n < n:
-                raise ValueError("out holds %d frames, the batch has %d" % (out.n, n))
-            ofs = int(out_frame_bytes) if out_frame_bytes else out.frame_stride
-            if ofs < span:
-                raise ValueError("a frame of out (%d bytes) is smaller than a frame of out_planes (%d)" % (ofs, span))
-            if out.n != n or ofs != out.frame_stride:
-                out = DeviceFrames(out.ptr, n, out.h, out.w, ofs, out.row_stride, owner=out, channels=out.channels,
-                                   itemsize=itemsize)
+        out, ofs = self._out_frames(n, out_planes, out, out_frame_bytes)
         st = self.lib.vqa_convert_submit(self.ctx, fp, kind, n, fs, plane_descs(planes), out.ptr, ofs, plane_descs(out_planes),
                                          len(planes), *ids)
         N.check(st, "vqa_convert_submit", self.ctx)
@@ -1448,6 +1413,80 @@ class Engine:
         """convert_submit and convert_wait -> the DeviceFrames of the converted stream."""
         res = self.convert_submit(frames, planes, out_planes, chroma, siting, range, out, frame_bytes, out_frame_bytes)
         self.convert_wait()
+        return res
+
+    # ---- fields: interlace and pulldown statistics; weave: frames out of fields -----------------
+    def fields_submit(self, frames, planes, prev0=None, plane=0, frame_bytes=None):
+        """The field statistics of planes[plane] of n frames of ONE stream (vqa_fields_submit): comb, fwd, bwd, sad and changed
+        per row parity, frame i against frame i - 1 and frame 0 against prev0 (None: it has no predecessor, its pair words are 0
+        and has_prev is 0).  frames / prev0: as motion_submit takes them (a sample type that does not match the depth is a
+        ValueError, never a cast), roi and strided views included.  The plane is at least 16 x 16: a ValueError before anything
+        is uploaded.  A batch of its own, like signature_submit."""
+        one = [planes[plane]]
+        w, h = int(one[0][0]), int(one[0][1])
+        if w < N.FIELDS_MIN_DIM or h < N.FIELDS_MIN_DIM:
+            raise ValueError("fields needs a plane of at least %d x %d (got %dx%d)" % (N.FIELDS_MIN_DIM, N.FIELDS_MIN_DIM, w, h))
+        fp, pp, kind, n, fs, keep = self._ref_args(frames, one, prev0, frame_bytes)
+        if not 1 <= n <= N.FIELDS_MAX_FRAMES:
+            raise ValueError("a fields submit takes 1 .. %d frames (got %d)" % (N.FIELDS_MAX_FRAMES, n))
+        st = self.lib.vqa_fields_submit(self.ctx, fp, pp, kind, n, fs, plane_descs(one))
+        N.check(st, "vqa_fields_submit", self.ctx)
+        self._pending_fd = (n, keep)
+
+    def fields_wait(self):
+        """-> [n] records (N.FIELDS_DTYPE): exact integers; fields.analyse reads the field order and the cadence off them."""
+        n, _keep = getattr(self, "_pending_fd", None) or (1, None)   # (nothing pending: the library says so)
+        out = np.zeros(n, dtype=N.FIELDS_DTYPE)
+        st = self.lib.vqa_fields_wait(self.ctx, out.ctypes.data_as(C.POINTER(N.VqaFieldsMetrics)), n)
+        self._pending_fd = None
+        N.check(st, "vqa_fields_wait", self.ctx)
+        return out
+
+    def fields(self, frames, planes, prev0=None, plane=0, frame_bytes=None):
+        """fields_submit and fields_wait -> [n] records (N.FIELDS_DTYPE)"""
+        self.fields_submit(frames, planes, prev0, plane, frame_bytes)
+        return self.fields_wait()
+
+    def weave_submit(self, frames, planes, top_index, bottom_index, out=None, frame_bytes=None, out_frame_bytes=None):
+        """Frames out of the fields of other frames on the device (vqa_weave_submit): the even rows of every plane of output
+        frame j come from source frame top_index[j], the odd rows from source frame bottom_index[j].  frames: an array /
+        DeviceFrames as conform_submit takes them; `planes` describes both sides.  The indices name source frames 0 .. n - 1 and
+        are equally long: a ValueError otherwise.  out / out_frame_bytes: as for conform_submit.  -> the DeviceFrames of the
+        woven stream, which every submit of THIS engine accepts with `planes` at once; weave_wait is needed only before another
+        engine or the host reads them.  A batch of its own, like conform_submit."""
+        if not 1 <= len(planes) <= 4:
+            raise ValueError("weave needs one to four planes (got %d)" % len(planes))
+        for i, q in enumerate(planes):
+            w, h, least = int(q[0]), int(q[1]), N.WEAVE_MIN_DIM if i == 0 else N.WEAVE_MIN_DIM // 2
+            if w < least or h < least:
+                raise ValueError("weave needs planes of at least %d x %d (plane %d: %dx%d)" % (least, least, i, w, h))
+        top, bot = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (top_index, bottom_index))
+        if top.size != bot.size or not 1 <= top.size <= N.WEAVE_MAX_OUT:
+            raise ValueError("top_index and bottom_index must be equally long, 1 .. %d entries (got %d and %d)"
+                             % (N.WEAVE_MAX_OUT, top.size, bot.size))
+        fp, kind, n_in, fs, keep = self._one_stream_args(frames, planes, frame_bytes)
+        if min(int(top.min()), int(bot.min())) < 0 or max(int(top.max()), int(bot.max())) >= n_in:
+            raise ValueError("top_index and bottom_index must name source frames 0 .. %d" % (n_in - 1))
+        n = int(top.size)
+        out, ofs = self._out_frames(n, planes, out, out_frame_bytes)
+        i32 = C.POINTER(C.c_int32)
+        st = self.lib.vqa_weave_submit(self.ctx, fp, kind, n_in, fs, plane_descs(planes), out.ptr, ofs, plane_descs(planes),
+                                       len(planes), top.ctypes.data_as(i32), bot.ctypes.data_as(i32), n)
+        N.check(st, "vqa_weave_submit", self.ctx)
+        self._pending_wv = (n, (keep, out))
+        return out
+
+    def weave_wait(self):
+        """Wait for the pending weave batch: the woven frames are complete (another engine, or a copy to the host, may read
+        them)."""
+        st = self.lib.vqa_weave_wait(self.ctx)
+        self._pending_wv = None
+        N.check(st, "vqa_weave_wait", self.ctx)
+
+    def weave(self, frames, planes, top_index, bottom_index, out=None, frame_bytes=None, out_frame_bytes=None):
+        """weave_submit and weave_wait -> the DeviceFrames of the woven stream."""
+        res = self.weave_submit(frames, planes, top_index, bottom_index, out, frame_bytes, out_frame_bytes)
+        self.weave_wait()
         return res
 
     # ---- temporal alignment ------------------------------------------------------------

@@ -398,6 +398,107 @@ def frame_convert(frames, layout, out_layout, height=None, width=None, chroma="l
     return out
 
 
+FIELDS_WINDOW = 1024   # the frames of one submit of frame_fields and frame_weave (the C limit is 32768)
+
+
+def _fields_request(values):
+    """the fields argument / config key -> whether the measurement is on; a ValueError for anything but a boolean"""
+    fields = values.get("fields", False)
+    if not isinstance(fields, (bool, np.bool_)):
+        raise ValueError("fields must be true or false.")
+    return bool(fields)
+
+
+def frame_fields(frames, layout, height=None, width=None, plane=0, engine=None, device=None, window=FIELDS_WINDOW):
+    """Interlace and 3:2 pulldown detection of ONE whole clip (Engine.fields, include/vqa.h): per frame the comb, forward,
+    backward, SAD and changed words of planes[plane] per row parity, exact integers; then fields.analyse: idet's single-frame
+    rule as recalled (NOT pinned against FFmpeg), the repeated fields and a 3:2 cadence with its phase, field order and breaks.
+    The clip is walked in windows of `window` frames and the last frame of a window is the next one's prev0: any window size
+    gives the same records.  -> (records [n] of N.FIELDS_DTYPE, the analysis).  The plane at least 16 x 16."""
+    from . import fields as F
+    window = int(window)
+    if window < 1:
+        raise ValueError("window must be a positive integer.")
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    if not 0 <= int(plane) < len(planes):
+        raise ValueError("plane must be 0 .. %d for %s (got %r)" % (len(planes) - 1, layout, plane))
+    n = _frame_count(frames)
+    if not n:
+        raise ValueError("the clip must hold at least one frame")
+    eng = engine if engine is not None else stream.get_engine(device)
+    rec = np.zeros(n, N.FIELDS_DTYPE)
+    with stream.pass_lock(eng.device):
+        for a, b in _frame_windows(n, window):
+            prev0 = None if a == 0 else (frames.frame(a - 1) if isinstance(frames, DeviceFrames) else _frame_part(frames, a - 1, a))
+            rec[a:b] = eng.fields(_frame_part(frames, a, b), planes, prev0, int(plane))
+    return rec, F.analyse(rec)
+
+
+def frame_weave(frames, layout, top_index, bottom_index, height=None, width=None, engine=None, device=None, window=FIELDS_WINDOW):
+    """Frames out of the fields of other frames on the GPU (Engine.weave): the even rows of every plane of output frame j from
+    frame top_index[j], the odd rows from frame bottom_index[j] - fields.telecine_plan, ivtc_plan and field_plan give such
+    pairs.  The source clip is uploaded once and the output walked in windows of `window` frames.  -> a host array [n_out, frame
+    samples] of the input's dtype."""
+    from .engine import planes_span
+    window = int(window)
+    if window < 1:
+        raise ValueError("window must be a positive integer.")
+    frames = _host_stream(frames, wide=True)
+    h, w = _geometry(frames, layout, height, width)
+    planes = LAYOUTS[layout][0](h, w)
+    wide = layout_depth(layout) > 8
+    top, bottom = (np.asarray(a, np.int64).reshape(-1) for a in (top_index, bottom_index))
+    if top.size != bottom.size:
+        raise ValueError("top_index and bottom_index must be equally long (got %d and %d)" % (top.size, bottom.size))
+    n = _frame_count(frames)
+    out = np.zeros((top.size, planes_span(planes) // (2 if wide else 1)), np.uint16 if wide else np.uint8)
+    if top.size == 0:
+        return out
+    if min(top.min(), bottom.min()) < 0 or max(top.max(), bottom.max()) >= n:
+        raise ValueError("top_index and bottom_index must name source frames 0 .. %d" % (n - 1))
+    eng = engine if engine is not None else stream.get_engine(device)
+    with stream.pass_lock(eng.device):
+        for a, b in _frame_windows(top.size, window):
+            # the source frames this window names, and the indices counted from the first of them
+            lo, hi = int(min(top[a:b].min(), bottom[a:b].min())), int(max(top[a:b].max(), bottom[a:b].max())) + 1
+            res = eng.weave(_frame_part(frames, lo, hi), planes, top[a:b] - lo, bottom[a:b] - lo)
+            out[a:b] = eng.download(res)
+            res._owner.free()
+    return out
+
+
+def fields_extra(ref_analysis, dist_analysis):
+    """the two analyses of frame_fields -> the nine top-level keys of the log and the row (fields.FIELDS_KEYS, in that order).  A
+    distorted stream that is not progressive, or streams that do not match, are also a warning in the log of this module"""
+    import logging
+    from . import fields as F
+    extra = F.summary_keys(ref_analysis, dist_analysis)
+    if extra["FIELDS_DIST_TYPE"] != "progressive" or extra["FIELDS_DIST_CADENCE"] != "none":
+        logging.getLogger(__name__).warning(
+            "the distorted stream is not progressive at the reference's cadence (type %s, cadence %s, %d combed frames, %d frames "
+            "that repeat a field): frame i of it need not be frame i of the reference", extra["FIELDS_DIST_TYPE"],
+            extra["FIELDS_DIST_CADENCE"], extra["FIELDS_DIST_COMBED"], extra["FIELDS_DIST_REPEATS"])
+    if not extra["FIELDS_MATCH"]:
+        logging.getLogger(__name__).warning(
+            "the two streams differ in field structure (reference: %s, cadence %s; distorted: %s, cadence %s): nothing was changed, "
+            "fields.ivtc_plan and Engine.weave undo a pulldown", extra["FIELDS_REF_TYPE"], extra["FIELDS_REF_CADENCE"],
+            extra["FIELDS_DIST_TYPE"], extra["FIELDS_DIST_CADENCE"])
+    return extra
+
+
+def _fields_keys(on, ref, layout, h, w, dist, dist_layout, dh, dw, extra, device):
+    """the fields measurement of an entry point, over the streams as given - the reference at its layout, the distorted stream
+    at its own size and layout - before any pre-pass: extra (DIST_RES, SCALE, DIST_PIXFMT, CONVERT or None) with the nine keys
+    behind it.  Off: extra as it is, and no stream is touched."""
+    if not on:
+        return extra
+    ra = frame_fields(ref, layout, h, w, device=device)[1]
+    da = frame_fields(dist, dist_layout, dh, dw, device=device)[1]
+    return dict(extra or {}, **fields_extra(ra, da))
+
+
 ALIGN_WINDOW = 4096   # the distorted frames of one submit of frame_align (the C limit is 32768)
 
 
@@ -1040,17 +1141,20 @@ PREPASSES = (
 # (transfer, full_range), sync's (min_overlap, apply), whether the colour fit is on, conform's colour mode
 class Requests(namedtuple("Requests", "scaling radius search lit syn fit mode")):
     """the seven fields, and beside them `convert`: None or the (chroma, siting, range) of a converting pass - no pre-pass and no
-    field, so that a request without it is the tuple it was"""
+    field, so that a request without it is the tuple it was - and `fields`: whether the field statistics of both streams are
+    measured ahead of the chain"""
     convert = None
+    fields = False
 
 
 def _requests(values, config=False):
     """run_ffmpeg_metrics' keywords, or with config=True a config -> Requests.  The order of the checks, and so the first error
-    of a bad combination: scale, align, shift, light, sync, colorfit, conform, convert."""
+    of a bad combination: scale, align, shift, light, sync, colorfit, conform, convert, fields."""
     parse = {p.name: p.request for p in PREPASSES}
     req = Requests(_scale_request(values.get("scale"), values.get("dist_height"), values.get("dist_width")),
                    *(parse[name](values, config) for name in ("align", "shift", "light", "sync", "colorfit", "conform")))
     req.convert = _convert_request(values)
+    req.fields = _fields_request(values)
     return req
 
 
@@ -1333,7 +1437,7 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                        dist_height=None, dist_width=None, scale=None, align=None, shift=None,
                        shift_margin=None, light=False, light_transfer="pq", light_full_range=False, sync=False,
                        sync_min_overlap=None, sync_apply=False, colorfit=False, conform=False, conform_color="match",
-                       dist_pixfmt=None, convert=None, convert_siting="center", convert_range="limited"):
+                       dist_pixfmt=None, convert=None, convert_siting="center", convert_range="limited", fields=False):
     """video_processing.py:270-297 — PSNR and SSIM between two streams, one stats line per frame.
     Streams: [N,H,W,3] BGR arrays / .npy (components r,g,b as FFmpeg labels RGB input), planar yuv420p
     arrays with height/width, or .y4m files (components y,u,v — what FFmpeg sees for an H.264 clip).
@@ -1446,6 +1550,12 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
     Layouts that differ without convert stay the error they were; dist_pixfmt without convert, convert on equal layouts, on a
     differing plane count or packed bgr24, and convert with sync, align, shift, colorfit or conform are ValueErrors (light reads
     the reference only and stays allowed).  Without the keywords every file is byte for byte what it was.
+    fields=True: before every pre-pass frame_fields reads both streams as given - the reference at its layout, the distorted
+    stream at its own size and layout, so it goes with scale and with convert - and vmaf_log, written in any case, gains nine
+    top-level keys before every pre-pass key: FIELDS_REF_TYPE, FIELDS_REF_COMBED (frames classed tff or bff), FIELDS_REF_CADENCE,
+    FIELDS_REF_REPEATS, the same four as FIELDS_DIST_*, and FIELDS_MATCH (1 when type, cadence and phase agree).  A distorted
+    stream that is not progressive, or FIELDS_MATCH 0, is also a logged warning.  The frames are NOT changed: applying a plan
+    (fields.ivtc_plan) is the caller's Engine.weave.  idet's rule as recalled, not pinned against FFmpeg.
     vmaf_model_path: a libvmaf JSON model or a bare libsvm model (vmaf_model.load_model; loaded BEFORE the pass starts, so a bad
     file costs no GPU time).  It turns vif, adm and motion on; the log then also carries frames[i].metrics.vmaf and
     pooled_metrics.vmaf.{min, max, mean, harmonic_mean}, which extract_metrics_from_logs reads as the reference does."""
@@ -1484,13 +1594,14 @@ def run_ffmpeg_metrics(reference_video, distorted_video, psnr_log, ssim_log, vma
                 _check_request(f, layout, given)
                 if f.plane_check is not None:
                     f.plane_check(planes)
+        extra = _fields_keys(req.fields, ref, layout, h, w, dist, layout_d, dh, dw, extra, device)
         (rs, ds), extra, plan, planes, ran = _prepass_chain(
             req, _host_stream(ref, wide=True), _host_stream(dist, wide=True), (), layout, h, w, (dh, dw), planes, sw, device,
             extra=extra, same_shape=not scaling and not req.convert)
         if plan is not None:
             wr.resize(_sizes(planes))
         _measure(ds, rs, sw, models, planes, _SSIM_MODES[ssim_mode], layout, dist_planes, scale, extra, vmaf_log,
-                 ran=ran, batch_size=batch_size, on_quality=wr, device=device, conform=plan, convert=req.convert)
+                 ran=ran or req.fields, batch_size=batch_size, on_quality=wr, device=device, conform=plan, convert=req.convert)
     finally:
         wr.close()
     return None
@@ -1701,7 +1812,11 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         not swscale's), ahead of scale where both are named.  The row gains DIST_PIXFMT and CONVERT ("linear/center/limited")
         right after DIST_RES / SCALE where those exist.  It needs a quality pair of its own (planar streams next to encoded_bgr);
         dist_pixfmt without convert, convert on equal layouts, on a differing plane count or bgr24, and convert with sync, align,
-        shift, colorfit or conform are ValueErrors; light stays allowed.
+        shift, colorfit or conform are ValueErrors; light stays allowed,
+        fields (true | false; default false): frame_fields reads both streams of the quality pair as given, ahead of every
+        pre-pass, and the row gains FIELDS_REF_TYPE, FIELDS_REF_COMBED, FIELDS_REF_CADENCE, FIELDS_REF_REPEATS, the same four as
+        FIELDS_DIST_* and FIELDS_MATCH right after DIST_RES / SCALE / DIST_PIXFMT / CONVERT where those exist and before every
+        pre-pass column (run_ffmpeg_metrics' fields).  The frames are not changed; it goes with every other key.
     column_order="reference" keeps the reference's unpacking of the 8-tuple (:235-242), which shifts five labels
     (SURVEY.md §3.2); "fixed" uses the tuple's true order."""
     import tempfile
@@ -1785,10 +1900,13 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
         if req.mode is not None and qdist is None:
             raise ValueError("conform needs a distorted stream of the quality half's own: pass the quality pair as planar "
                              "streams next to encoded_bgr (one BGR stream serves both halves as it is)")
+        extra = _fields_keys(req.fields, ref, layout, h, w, enc if qdist is None else qdist, layout_d,
+                             *((dh, dw) if scaling else (h, w)), extra, device)
         # the pre-passes read the quality pair; the BGR frames beside it are cut with it, so both halves see the same frames
         streams, extra, plan, planes, ran = _prepass_chain(
             req, ref, enc if qdist is None else qdist, () if qdist is None else (enc,), layout, h, w,
             (dh, dw) if scaling else (h, w), planes, sw, device, extra=extra)
+        ran = ran or req.fields
         ref, enc, qdist = (streams[0], streams[1], None) if qdist is None else (streams[0], streams[2], streams[1])
         wr = _StatsWriter(psnr_log, ssim_log, layout, _sizes(planes))
         try:
@@ -1810,7 +1928,7 @@ def process_video_and_extract_metrics(input_video, encoded_video, config, csv_fi
                      "ORB Feature Complexity", "Color Histogram Complexity", "Temporal DCT Complexity",
                      "Framerate Variation")
         metrics.update(dict(zip(names, t)))
-        if scaling or req.convert:
+        if scaling or req.convert or req.fields:
             metrics.update(extra)
         if ran:   # (extract_metrics_from_logs read the pre-passes' keys off the log: they go last)
             metrics.update((k, metrics.pop(k)) for k in list(extra))
