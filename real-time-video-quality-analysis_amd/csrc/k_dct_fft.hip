@@ -548,6 +548,9 @@ void launch_dct_full_fft(hipStream_t st, const uint8_t *planes, int pitch, int64
         // against 5.6 for the pair-per-workgroup kernel, 64 x 2160p): the pair kernel stays
         tiles = w >> 1;
         const dim3 gp((tiles + 7) / 8 * 8, n);
+        // <true> is unreachable through the C ABI: it needs 2040 < h <= 2046, and dct_fft_factor admits no length there
+        // (2042 = 2 * 1021, 2044 = 4 * 7 * 73, 2046 = 2 * 3 * 11 * 31; tests/test_dct_full_host.py restates the list).  Every
+        // height that gets here, 2048 .. 4000, runs <false>.
         if (4 * h * 8 <= cap - 64)
             hipLaunchKernelGGL(k_dct_fft_cols<true>, gp, dim3(256), (size_t)4 * h * 8, st, Ra, Rb, h, w, ph_, pe, pt, (int)energy, (int)temporal);
         else
